@@ -3,7 +3,7 @@
 backward [-> RCCL gradient all-reduce over xGMI when N > 1] -> Adam step) on synthetic
 ActivityNet-Captions-shaped input (BASELINE.json configs[2]: activitynet.yml with T=256, batch 64 per GPU).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -22,9 +22,7 @@ import os
 import sys
 import time
 
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")      # see video-moment-localization_amd/__init__.py (read when the HIP runtime initialises)
-
-import torch  # noqa: E402
+import torch
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
@@ -73,7 +71,7 @@ def cpu_baseline(cfg, seconds_budget=25.0):
     """Time the CPU oracle (oracle/smin_oracle.py, a port of the reference's dense algorithm, pinned to the
     reference by tests/golden) on micro-batches of the same workload, BASELINE.md section 3 style: micro-batch 8 (1 for
     the 512 x 512 map), the 16 host threads of a one-GPU box's CPU share, median step.  Checker code, used here only as the
-    reported baseline; `kind` stays "port" because /root/reference does not exist on the GPU box."""
+    reported baseline; `kind` stays "port" because the reference itself is not part of this repository."""
     import statistics
     from oracle import smin_oracle as O
     from tests import helpers as H
@@ -128,6 +126,30 @@ def step_work(C, D, dl, Nq, layers):
     return flops_alg, 3 * f_exec, bytes_alg
 
 
+DUMP_BUDGET_BYTES = 60 << 20          # the whole dump stays under 64 MB (10^6 bytes) with its .npy headers
+
+
+def dump_outputs(out_dir, arrays, budget=DUMP_BUDGET_BYTES):
+    """Write each tensor of `arrays` (name -> tensor) as out_dir/<name>.npy in float32 (float64 stays float64).  When the whole set
+    is larger than `budget`, the budget is shared out smallest array first, and an array that gets less than its size is written as
+    a fixed sample of its flattened elements (seeded by its name and size, so two runs or two builds sample the same elements)."""
+    import zlib
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    host = {k: v.detach().to("cpu", torch.float64 if v.dtype == torch.float64 else torch.float32) for k, v in arrays.items()}
+    left, n = budget, len(host)
+    for k in sorted(host, key=lambda k: host[k].nbytes):
+        t = host[k]
+        cap = min(t.numel(), left // n // t.element_size())
+        if cap < t.numel():
+            g = torch.Generator().manual_seed(zlib.crc32(f"{k}:{t.numel()}".encode()))
+            idx = torch.randperm(t.numel(), generator=g)[:cap].sort().values
+            t = t.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, k + ".npy"), t.numpy())
+        left -= t.nbytes
+        n -= 1
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -144,7 +166,11 @@ def main():
     ap.add_argument("--feed", default="resident", choices=["resident", "host"],
                     help="resident (default, the headline): inputs live in HBM; host: every step's batch comes through BatchFeeder "
                          "(pinned host buffers -> async H2D on a copy stream -> masks/targets built on the device), the PCIe-inclusive rate")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (scores, loss, parameter gradients) as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -206,7 +232,7 @@ def main():
     def step(with_opt=True, eager=False):
         nonlocal batch
         if captured and not eager:
-            return captured[with_opt and not args.no_optimizer](batch)[0]
+            return captured[with_opt and not args.no_optimizer](batch)
         if feed_iter is not None:
             batch = next(feed_iter)
             batch["sm"] = torch.nan_to_num(batch["sm"])       # 0/0 IoU of degenerate windows (the reference has the same NaNs)
@@ -218,7 +244,7 @@ def main():
         loss.backward()
         if with_opt and not args.no_optimizer:
             opt.step()
-        return loss
+        return loss, (pm, ps, pe, pa)
 
     def fence():
         dp.barrier()
@@ -231,11 +257,14 @@ def main():
     fence()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        loss = step()
+        loss, scores = step()
     fence()
     elapsed = time.perf_counter() - t0
     lib.prof_enable(False)
     prof = lib.prof_read()
+    if args.dump_outputs and rank == 0:                       # before any later step overwrites the scores or the gradients
+        dump_outputs(args.dump_outputs, {"loss": loss, **dict(zip(("pm", "ps", "pe", "pa"), scores)),
+                                         **{"grad." + k: p.grad for k, p in model.named_parameters() if p.grad is not None}})
     if captured:                                              # a replay runs no host code, so no launch is bracketed: kernel timings from eager steps
         lib.prof_enable(True)
         for _ in range(5):

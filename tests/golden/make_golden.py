@@ -1,7 +1,8 @@
 """Generate the golden fixtures under tests/golden/ from the REFERENCE implementation.
 
-Run only in the build container (``/root/reference`` is read-only and absent on
-the GPU box):  ``python -B tests/golden/make_golden.py``
+Run where a checkout of the reference exists (it is not needed anywhere else):
+``python -B tests/golden/make_golden.py <reference checkout> [fixture ...]``
+(every fixture by default; a fixture is named by its file name without ``.npz``).
 
 The reference's ``models.py`` (imports only math/torch) and ``utils.py`` are
 imported as-is on CPU; nothing from them is copied into this repo -- only
@@ -19,6 +20,8 @@ Fixtures:
         weights: outputs, loss, grad norms (inputs/weights are regenerated from
         closed forms + seed; checksums stored).
   g6_ious.npz        utils.compute_ious on a fixed input.
+  g7_init_seed43.npz default initialisation (state_dict) of a small config under
+        the training seed 43.
 """
 import os
 import sys
@@ -30,7 +33,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 sys.path.insert(0, ROOT)
 sys.dont_write_bytecode = True
-sys.path.insert(0, "/root/reference")
+sys.path.insert(0, os.path.abspath(sys.argv[1]))
 
 import models as ref_models          # noqa: E402  (the reference)
 import utils as ref_utils            # noqa: E402
@@ -171,12 +174,22 @@ def ious_case():
     print("g6 ok", dict(met))
 
 
+def init_case():
+    """The reference's default initialisation under config/*.yml's seed 43 (tests/test_host_api.py)."""
+    args = (32, 8, 4, 32, 16, 2, 24, 5, 16)
+    torch.manual_seed(43)
+    sd = ref_models.SMIN(*args).state_dict()
+    np.savez_compressed(os.path.join(HERE, "g7_init_seed43.npz"), cfg=np.array(args, dtype=np.int64), **np_sd(sd))
+    print("g7_init_seed43 ok")
+
+
 if __name__ == "__main__":
-    #            name            T   L  C  D   dl lay Din Nq H   B seed boost
-    tiny_case("g1_r4",          32, 8, 4, 32, 16, 2, 24, 5, 16, 3, 11, 2.0)
-    tiny_case("g2_r2_ragged",   16, 8, 4, 32, 16, 2, 24, 6, 16, 4, 12, 2.0)
-    tiny_case("g3_c3",          32, 8, 3, 32, 16, 3, 20, 7, 16, 5, 13, 1.6)
-    wc_case()
-    for name, cfg in FULL.items():
-        full_case(name, cfg)
-    ious_case()
+    #              name            T   L  C  D   dl lay Din Nq H   B seed boost
+    cases = {"g1_r4": lambda: tiny_case("g1_r4",          32, 8, 4, 32, 16, 2, 24, 5, 16, 3, 11, 2.0),
+             "g2_r2_ragged": lambda: tiny_case("g2_r2_ragged", 16, 8, 4, 32, 16, 2, 24, 6, 16, 4, 12, 2.0),
+             "g3_c3": lambda: tiny_case("g3_c3",          32, 8, 3, 32, 16, 3, 20, 7, 16, 5, 13, 1.6),
+             "g4_wc": wc_case}
+    cases.update({"g5_" + name: (lambda name=name, cfg=cfg: full_case(name, cfg)) for name, cfg in FULL.items()})
+    cases.update(g6_ious=ious_case, g7_init_seed43=init_case)
+    for name in sys.argv[2:] or cases:
+        cases[name]()

@@ -1298,15 +1298,17 @@ def test_degenerate_samples_and_empty_batch(dev):
     assert all(p.grad is None or bool(torch.isfinite(p.grad).all()) for p in m.parameters())
 
 
-def test_bench_contract_line(dev):
-    """bench.py prints one JSON line with the keys the driver reads (short run of a small workload)."""
+def test_bench_contract_line(dev, tmp_path):
+    """bench.py prints one JSON line with the keys the driver reads (short run of a small workload), and --dump-outputs writes
+    what the last timed step computed."""
+    import glob
     import json
     import os
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "2", "--warmup", "1", "--no-cpu-baseline",
-                          "--workload", "charadessta"], capture_output=True, text=True, timeout=300, cwd=root)
+                          "--workload", "charadessta", "--dump-outputs", str(tmp_path / "dump")], capture_output=True, text=True, timeout=300, cwd=root)
     assert out.returncode == 0, out.stderr[-2000:]
     line = [ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1]
     j = json.loads(line)
@@ -1321,6 +1323,19 @@ def test_bench_contract_line(dev):
     if default_mode == "f32":
         oa = j["other_arithmetic"]
         assert set(oa) == {"f32e", "bf16x3"} and oa["f32e"]["max_score_deviation_from_f32"] < 5e-6 and oa["bf16x3"]["max_score_deviation_from_f32"] < 1e-4
+    # the dump: scores, loss and every parameter gradient of the last timed step, as float arrays, at most 64 MB in all
+    import models
+    files = glob.glob(str(tmp_path / "dump" / "*.npy"))
+    names = {os.path.basename(f)[:-4] for f in files}
+    B, L = 32, 16
+    params = [k for k, _ in models.SMIN(64, 16, 4, 512, 128, 3, 1024, 13, 256).named_parameters()]
+    assert names == {"loss", "pm", "ps", "pe", "pa"} | {"grad." + k for k in params}
+    assert sum(os.path.getsize(f) for f in files) <= 64e6
+    d = {n: np.load(str(tmp_path / "dump" / (n + ".npy"))) for n in names}
+    assert all(a.dtype in (np.float32, np.float64) and np.isfinite(a).all() for a in d.values())
+    assert d["pm"].shape == (B, L, L) and d["ps"].shape == d["pe"].shape == d["pa"].shape == (B, L)
+    assert float(d["loss"]) == j["config"]["final_loss"]
+    assert any(np.abs(d["grad." + k]).max() > 0 for k in params)
 
 
 def test_layout_build_kernels(dev):

@@ -1,5 +1,5 @@
-import sys, ctypes, torch
-sys.path.insert(0, "/root/repo")
+import os, sys, ctypes, torch
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import models
 from vml_amd._lib import call, ptr, stream
 V = models.vml_amd

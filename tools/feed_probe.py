@@ -1,5 +1,5 @@
-import sys, time, itertools, torch
-sys.path.insert(0, '/root/repo')
+import os, sys, time, itertools, torch
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import bench, models
 dev = torch.device('cuda:0')
 T,L,C,D,dl,layers,Din,Nq,Hh,B = bench.WORKLOADS['activitynet_t256']

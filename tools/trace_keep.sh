@@ -1,8 +1,8 @@
 #!/bin/bash
 # usage: tools/trace_keep.sh <tag> [bench args...] -> gpurun_out/trace_<tag>.csv.gz (kernel trace of a short bench run) + underfill summary
 tag=$1; shift
+R=$(cd "$(dirname "$0")/.." && pwd)
 cd /tmp && export TMPDIR=/tmp
-R=${GRAFT_REPO_ROOT:-/root/repo}
 rm -rf /tmp/tl_$tag
 cd $R
 rocprofv3 --kernel-trace --output-format csv -d /tmp/tl_$tag -- python3 bench.py --steps 8 --warmup 4 --no-cpu-baseline --no-other-modes "$@" > /dev/null 2>&1
