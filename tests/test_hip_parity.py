@@ -290,11 +290,10 @@ def test_batch_targets_on_device(dev):
 
 
 def test_native_host_equals_python_host(dev):
-    """The torch-extension host (csrc/torch_binding.cpp) with a node per module and the Python host (functional.py / modules.py)
-    drive the same kernels in the same order: scores and every parameter gradient must agree bit for bit.  The default host runs
-    whole model as ONE node (SminCore): the same kernels except for the parameter products (its own kernel instead of hipBLASLt: scores
-    within 2e-6); gradients of tensors with several consumers are summed in one launch instead of by the autograd engine (a different
-    but fixed order: tight tolerance)."""
+    """The torch-extension host (csrc/torch_binding.cpp: the whole model as ONE node, SminCore) against the Python host (functional.py /
+    modules.py: a node per module).  The same kernels except for the parameter products (the node's own kernel instead of hipBLASLt:
+    scores within 2e-6); gradients of tensors with several consumers are summed in one launch instead of by the autograd engine (a
+    different but fixed order: tight tolerance)."""
     from oracle import smin_oracle as O
     import vml_amd.training as TR
     from vml_amd import loss_fn
@@ -305,10 +304,9 @@ def test_native_host_equals_python_host(dev):
         batch = O.synthetic_batch(B, T, L, Nq, Din, seed=21)
         b = {k: v.to(dev) for k, v in batch.items()}
         res = []
-        for native, fused in ((True, True), (True, False), (False, False)):
+        for native in (True, False):
             m = build_model(dict(T=T, L=L, C=C, D=D, dl=dl, layers=layers, Din=Din, Nq=Nq, H=Hh), sd, dev)
             m.native_host = native
-            m.fused_core = fused
             TR.NATIVE_LOSS = native
             try:
                 out = m(*H.model_inputs(b))
@@ -317,14 +315,12 @@ def test_native_host_equals_python_host(dev):
             finally:
                 TR.NATIVE_LOSS = True
             res.append(([o.detach().clone() for o in out], loss.detach().clone(), {k: p.grad.clone() for k, p in m.named_parameters()}))
-        (o0, l0, g0), (o1, l1, g1), (o2, l2, g2) = res
-        assert torch.equal(l1, l2) and abs(float(l0) - float(l1)) <= 2e-6 * max(1.0, abs(float(l1)))
-        for x, y, z in zip(o0, o1, o2):
-            assert torch.equal(y, z)
+        (o0, l0, g0), (o1, l1, g1) = res
+        assert abs(float(l0) - float(l1)) <= 2e-6 * max(1.0, abs(float(l1)))
+        for x, y in zip(o0, o1):
             assert float((x - y).abs().max()) <= 2e-6          # (the one-node step forms the weight products with its own kernel: last-bit differences)
         gmax = max(float(v.abs().max()) for v in g1.values())
         for k in g1:
-            assert torch.equal(g1[k], g2[k]), k
             assert g0[k].shape == g1[k].shape, k
             err = float((g0[k] - g1[k]).abs().max())
             assert err <= 2e-5 * float(g1[k].abs().max()) + 1e-6 * gmax + 1e-9, (k, err, float(g1[k].abs().max()), gmax)
@@ -343,6 +339,52 @@ def test_native_host_equals_python_host(dev):
             for k, p in m.named_parameters():
                 assert torch.equal(p.grad, g0[k]), (k, async_weights)
 
+
+def test_inputs_that_require_grad_take_the_python_host(dev):
+    """The one-node step forms no gradients of its inputs: SMIN.forward with video_features / query_features that require grad runs
+    the Python host.  Scores and parameter gradients hold the tolerances of test_against_oracle_random, query_features.grad the same
+    2e-3 relative bound against the oracle's autograd (video_features.grad stays None: neither host forms it).  The extension itself
+    refuses such inputs, and a cfg asking for a node per module (cfg[10] = 0), pointing to the Python host."""
+    from oracle import smin_oracle as O
+    from vml_amd import loss_fn
+    import models
+    T, L, C, D, dl, layers, Din, Nq, Hh, B = 64, 16, 4, 64, 32, 2, 40, 9, 32, 5
+    sd = O.formula_state_dict(H.smin_shapes(T, L, C, D, dl, layers, Din, Nq, Hh), gain=1.2)
+    batch = O.synthetic_batch(B, T, L, Nq, Din, seed=T + L + D)
+    sdg = {k: v.clone().requires_grad_(True) for k, v in sd.items()}
+    inp0 = list(H.model_inputs(batch))
+    inp0[2] = inp0[2].clone().requires_grad_(True)
+    ref = O.smin_forward(sdg, dict(T=T, L=L, C=C), *inp0)
+    O.loss_fn(ref[0], batch["ym"], batch["sm"], batch["moment_mask"], ref[1], batch["ys"], batch["ss"], ref[2], batch["ye"], batch["se"],
+              ref[3], batch["ya"], batch["length_mask"]).backward()
+    m = build_model(dict(T=T, L=L, C=C, D=D, dl=dl, layers=layers, Din=Din, Nq=Nq, H=Hh), sd, dev)
+    b = {k: v.to(dev) for k, v in batch.items()}
+    inp = list(H.model_inputs(b))
+    inp[0] = inp[0].clone().requires_grad_(True)
+    inp[2] = inp[2].clone().requires_grad_(True)
+    assert not m._native_ok(inp[0], inp[2])
+    streams = []
+    python_host = m._forward_stream
+    m._forward_stream = lambda *a: streams.append(1) or python_host(*a)
+    out = m(*inp)
+    assert streams == [1]
+    for got, want in zip(out, ref):
+        assert (got.detach().cpu() - want.detach()).abs().max().item() < SCORE_TOL
+    loss_fn(out[0], b["ym"], b["sm"], b["moment_mask"], out[1], b["ys"], b["ss"], out[2], b["ye"], b["se"], out[3], b["ya"], b["length_mask"]).backward()
+    for k, p in m.named_parameters():
+        g0 = sdg[k].grad
+        assert (p.grad.cpu() - g0).abs().max().item() <= 2e-3 * g0.abs().max().item() + 1e-7, k
+    assert inp[0].grad is None
+    g0, err = inp0[2].grad, (inp[2].grad.cpu() - inp0[2].grad).abs().max().item()
+    print("query_features.grad: max abs err", err, "relative", err / g0.abs().max().item())
+    assert err <= 2e-3 * g0.abs().max().item() + 1e-7, err
+    # the extension refuses both cases before it launches anything
+    ops = models.vml_amd._lib.load_torch()
+    cfg = [T, L, C, D, dl, layers, Nq, Hh, 1, 1, 1, 1, 1, 0, -1, 1]
+    with pytest.raises(RuntimeError, match=r"cfg\[10\].*SMIN\.native_host = False"):
+        ops.smin_forward(*H.model_inputs(b), m._native_params(), cfg[:10] + [0] + cfg[11:])
+    with pytest.raises(RuntimeError, match=r"require grad.*SMIN\.native_host = False"):
+        ops.smin_forward(*inp, m._native_params(), cfg)
 
 def test_target_kernel_and_feeder(dev):
     """csrc/labels.hip (one launch for every mask / target of a batch) against the per-sample restatement of dataset.py:95-155

@@ -1,5 +1,6 @@
 """Host time of each phase of the train step (no device synchronisation inside the step): how long the Python thread needs to
-queue forward / loss / backward / optimizer, against the step's wall time.  WL=<workload> FUSED=0|1"""
+queue forward / loss / backward / optimizer, against the step's wall time.  WL=<workload> FUSED=0|1 (FUSED=0: SMIN.fused_core = False,
+i.e. a node per module on the Python host)"""
 import os, sys, time
 import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

@@ -1,5 +1,6 @@
 """Run the train step's forward + backward several times on the same weights and batch and compare every gradient bit for bit,
-for each combination of stream switches.  MODE=f32e WL=...  (a timing-dependent difference = a cross-stream race)"""
+for each combination of stream switches (fused=0: SMIN.fused_core = False, i.e. the Python host).  MODE=f32e WL=...  (a timing-dependent
+difference = a cross-stream race)"""
 import os, sys, itertools
 import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

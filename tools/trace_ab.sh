@@ -1,5 +1,5 @@
 #!/bin/bash
-# kernel-trace timelines of the fused core and of the node-per-module graph on one box
+# kernel-trace timelines of the fused core and of a node per module (SMIN_NODE_GRAPH=1: the Python host) on one box
 # usage: tools/trace_ab.sh [bench args...]   -> gpurun_out/tl_fused.txt, gpurun_out/tl_nodes.txt
 R=$(cd "$(dirname "$0")/.." && pwd)
 cd /tmp && export TMPDIR=/tmp

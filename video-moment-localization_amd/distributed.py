@@ -64,8 +64,8 @@ class InNodeDataParallel(torch.nn.Module):
 
 def wrap(model, device=None, bucket_cap_mb=8):
     """Data parallel over the default process group (28-36 MB of fp32 gradients per step: SURVEY 5).  The one-node step
-    exchanges its gradients itself, overlapped with its backward pass (InNodeDataParallel); the node-per-module graph and
-    the Python host go through DistributedDataParallel with small buckets."""
+    exchanges its gradients itself, overlapped with its backward pass (InNodeDataParallel); the Python host (a node per module)
+    goes through DistributedDataParallel with small buckets."""
     if not dist.is_initialized() or (dist.get_world_size() == 1 and not os.environ.get("SMIN_FORCE_DDP")):
         return model
     changed = {}
@@ -76,8 +76,8 @@ def wrap(model, device=None, bucket_cap_mb=8):
         model.overlap_boundary = changed["overlap_boundary"] = False
     one_node = getattr(model, "fused_core", False) and getattr(model, "native_host", False) and not os.environ.get("SMIN_DDP_NO_PREP_OVERLAP")
     if getattr(model, "overlap_prep", False) and (gloo_on_gpu or not one_node):
-        # node-per-module graph: DDP creates every parameter's gradient accumulator on the stream it is constructed on; parameters
-        # that the step touches only on the second stream then make the main stream wait at each accumulation (measured +0.7 ms
+        # a node per module (the Python host): DDP creates every parameter's gradient accumulator on the stream it is constructed on;
+        # parameters that the step touches only on the second stream then make the main stream wait at each accumulation (measured +0.7 ms
         # over keeping that work on the main stream; the boundary unit's overlap still pays).  The one-node step hands every
         # gradient over on the main stream and keeps its second-stream tail under RCCL.
         model.overlap_prep = changed["overlap_prep"] = False

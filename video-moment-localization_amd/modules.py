@@ -431,7 +431,8 @@ class SMIN(nn.Module):
     grad_sync = False              # data parallel: the one-node backward averages its gradients over the process group itself, group by
                                    # group as they become final (set by distributed.wrap; torch_binding.cpp GradSync)
     bf16_operand_storage = True    # under set_gemm_mode("bf16"): tensors that only feed contractions are stored as bf16 (no bit of the step changes)
-    fused_core = True              # ... with proposal map + SMI layers + localization as one autograd node (False: a node per module)
+    fused_core = True              # ... with proposal map + SMI layers + localization as one autograd node (False: a node per module,
+                                   # which only the Python host builds)
     content_stream = True          # dl < D: keep the content stream in the dl-dimensional space (see _forward_stream)
     overlap_boundary = True        # boundary unit on a second HIP stream beside the content stream
     overlap_prep = True            # parameter-only work (word-side operands, weight products) on that stream as well
@@ -567,11 +568,12 @@ class SMIN(nn.Module):
         return self.fused_core and self.D % 32 == 0 and self.D <= 1056 and self.dl % 32 == 0 and len(self.smis) <= 8
 
     def _native_ok(self, video_features, query_features):
-        """The torch-extension path covers the production configuration: content stream on a mask-driven cell list, fused
-        BiLSTM and video encoder kernels.  Anything else (dl >= D, C outside 2..4, > 8 layers, H > 256, odd widths) runs the
-        same kernels from the Python host below."""
+        """The torch-extension path (one autograd node) covers the production configuration: content stream on a mask-driven cell
+        list, fused BiLSTM and video encoder kernels, inputs that need no gradient.  Anything else (fused_core = False, dl >= D, C outside
+        2..4, > 8 layers, H > 256, odd widths, video / query features that require grad) runs the same kernels from the Python host below."""
         H, ve, nl = self.lstm_hidden_size, self.backbone.videoencoder, len(self.smis)
-        return (self.native_host and self.content_stream and self.dl < self.D and 2 <= self.C <= 4 and 1 <= nl <= 8 and nl * self.dl <= 2048
+        return (self.native_host and self.fused_core and not video_features.requires_grad and not query_features.requires_grad
+                and self.content_stream and self.dl < self.D and 2 <= self.C <= 4 and 1 <= nl <= 8 and nl * self.dl <= 2048
                 and self.backbone.queryencoder.fused_lstm and H <= 256 and H % 4 == 0
                 and video_features.dtype == torch.float32 and query_features.dtype == torch.float32 and ve.d0 % 4 == 0 and ve.d % 4 == 0
                 and video_features.shape[1] == self.T and video_features.shape[1] <= ve.pe.weight.shape[0])
@@ -588,7 +590,7 @@ class SMIN(nn.Module):
         if self.grad_sync and not self._streams_allowed("torch"):
             raise RuntimeError("SMIN.grad_sync: the in-node gradient exchange runs RCCL beside the contraction kernels and is limited to the exact "
                                "fp32 mode; call distributed.wrap after set_gemm_mode (it then uses torch DDP)")
-        if self.grad_sync and not (self._native_ok(video_features, query_features) and self.fused_core):
+        if self.grad_sync and not self._native_ok(video_features, query_features):
             raise RuntimeError("SMIN.grad_sync (distributed.wrap's in-node gradient exchange) needs the one-node extension path; this "
                                "call does not qualify (see SMIN._native_ok) -- wrap the model with SMIN_TORCH_DDP=1 instead")
         if self._native_ok(video_features, query_features):
