@@ -235,6 +235,30 @@ int smin_build_targets(void* stream, const float* times, const float* duration, 
 int smin_compute_ious(void* stream, const float* pm, const float* ps, const float* pe, const uint8_t* mm, const float* sm,
                       int B, int L, float* counts, float* ws);
 
+/* ---- top-k moments with greedy temporal NMS (csrc/moments.hip).  For each sample b:
+ *   candidates: cells (i, j) with mm[b,i,j] != 0 (masked cells are never returned);
+ *   score = (pm[b,i,j] * sqrtf(ps[b,i])) * sqrtf(pe[b,j]) in fp32, in this order, correctly rounded sqrtf;
+ *   order: higher score first, ties -> lower flat index i*L + j (a score of -0 counts as +0);
+ *   IoU of two cells (moment (i, j) spans clips [i, j+1)): inter = max(0, min(j1,j2) + 1 - max(i1,i2)),
+ *     union = max(j1,j2) + 1 - min(i1,i2), iou = (float)inter / (float)union (one correctly rounded division);
+ *   greedy NMS: walk the candidates in order, keep one unless its IoU with a kept cell is > nms_thresh; stop after k kept or
+ *     when the candidates run out.  nms_thresh >= 1: no suppression (plain top-k over the valid cells).
+ * Outputs: idx [B][k][2] (start clip i, end clip j; -1 for empty slots), score [B][k] (0 for empty slots), count [B] (kept).
+ * Limits: 1 <= k <= 64, B >= 1, L >= 1, L*L < 2^31.  The result is exact and independent of the internal candidate buffers.
+ * No host synchronisation (capturable in a HIP graph).  ws: device scratch of at least the _ws_bytes size (0 = arguments rejected). */
+size_t smin_top_moments_ws_bytes(int B, int L, int k);
+int smin_top_moments(void* stream, const float* pm, const float* ps, const float* pe, const uint8_t* mm, int B, int L, int k,
+                     float nms_thresh, long long* idx, float* score, int* count, void* ws, size_t ws_bytes);
+
+/* ---- R@n, IoU=m over the NMS-kept moments: the top-k moments above with k = max(n_list), then for each pair (a, c)
+ * counts[a * nm + c] = number of samples with sm[b] > m_list[c] at any of the first n_list[a] kept cells (an empty slot
+ * counts as IoU 0).  1 <= n_list[a] <= k, 1 <= nn <= 64, 1 <= nm <= 16; host arrays n_list / m_list; deterministic sum
+ * over the samples.  ws: device scratch of at least the _ws_bytes size. */
+size_t smin_compute_ious_nms_ws_bytes(int B, int L, int k, int nn, int nm);
+int smin_compute_ious_nms(void* stream, const float* pm, const float* ps, const float* pe, const uint8_t* mm, const float* sm,
+                          int B, int L, int k, float nms_thresh, const int* n_list, int nn, const float* m_list, int nm,
+                          float* counts, void* ws, size_t ws_bytes);
+
 /* ---- content stream (reference models.py:242-276 + 115-119, re-associated): the content unit's output
  *   f_c' = m*(cc Wc^T + bc) + f_c + hbar   (models.py:269-276)
  * is consumed only by the next unit's linear_c_hat (models.py:247) and, through mean_c, by the moment unit

@@ -11,7 +11,7 @@ LIB_PATH = os.path.join(_HERE, "libsmin_hip.so")
 TORCH_LIB_PATH = os.path.join(_HERE, "libsmin_torch.so")        # TORCH_LIBRARY(smin_hip, ...): csrc/torch_binding.cpp
 CSRC = os.path.join(_HERE, "csrc")
 
-_vp, _i, _sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t
+_vp, _i, _sz, _f = ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t, ctypes.c_float
 ABI_VERSION = 2                                                 # include/smin_hip.h SMIN_HIP_ABI_VERSION
 
 # name -> argtypes (restype is int unless listed in _RESTYPE); mirrors include/smin_hip.h one to one
@@ -52,6 +52,10 @@ SIGNATURES = {
     "smin_loss_fwd": [_vp] * 14 + [_i] * 2 + [_vp] * 2,
     "smin_loss_bwd": [_vp] * 16 + [_i] * 2 + [_vp] * 4,
     "smin_compute_ious": [_vp] * 6 + [_i] * 2 + [_vp] * 2,
+    "smin_top_moments_ws_bytes": [_i] * 3,
+    "smin_top_moments": [_vp] * 5 + [_i] * 3 + [_f] + [_vp] * 4 + [_sz],
+    "smin_compute_ious_nms_ws_bytes": [_i] * 5,
+    "smin_compute_ious_nms": [_vp] * 6 + [_i] * 3 + [_f, _vp, _i, _vp, _i] + [_vp, _vp, _sz],
     "smin_build_targets": [_vp] * 5 + [_i] * 4 + [_vp] * 12,
     "smin_word_prep_fwd": [_vp] * 5 + [_i] * 5 + [_vp] * 5,
     "smin_word_prep_bwd_workspace_bytes": [_i] * 5,
@@ -93,7 +97,7 @@ SIGNATURES = {
 _RESTYPE = {"smin_target_arch": ctypes.c_char_p, "smin_workspace_bytes": _sz,
             "smin_content_attn_bwd_workspace_bytes": _sz, "smin_linear_rows_bwd_workspace_bytes": _sz,
             "smin_bilstm_layer_bwd_workspace_bytes": _sz, "smin_video_encoder_bwd_workspace_bytes": _sz, "smin_word_prep_bwd_workspace_bytes": _sz,
-            "smin_col_sum_workspace_bytes": _sz}
+            "smin_col_sum_workspace_bytes": _sz, "smin_top_moments_ws_bytes": _sz, "smin_compute_ious_nms_ws_bytes": _sz}
 
 _lib = None
 _ws = {}

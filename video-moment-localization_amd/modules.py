@@ -578,6 +578,16 @@ class SMIN(nn.Module):
                 and video_features.dtype == torch.float32 and query_features.dtype == torch.float32 and ve.d0 % 4 == 0 and ve.d % 4 == 0
                 and video_features.shape[1] == self.T and video_features.shape[1] <= ve.pe.weight.shape[0])
 
+    def localize(self, video_features, video_mask, query_features, query_mask, length_mask, moment_mask, k=5, nms_thresh=0.5,
+                 duration=None):
+        """The k best moments per sample: the forward under torch.no_grad(), then moments.top_moments of its (pm, ps, pe) -- greedy
+        temporal NMS at ``nms_thresh`` over the valid cells of ``moment_mask``.  Returns top_moments' dict (``idx`` (B, k, 2) start
+        / end clip, ``score``, ``count``; with ``duration`` (B,) seconds also ``times`` (B, k, 2) in seconds)."""
+        from .moments import top_moments
+        with torch.no_grad():
+            pm, ps, pe, _ = self(video_features, video_mask, query_features, query_mask, length_mask, moment_mask)
+        return top_moments(pm, ps, pe, moment_mask, k=k, nms_thresh=nms_thresh, duration=duration)
+
     @_hip_forward
     def forward(self, video_features, video_mask, query_features, query_mask, length_mask, moment_mask):
         # the reference's dataset pads queries and their mask to max_query_length (dataset.py:35, 173); a batch cut to its longest query is taken

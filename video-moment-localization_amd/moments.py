@@ -1,0 +1,187 @@
+"""Top-k moment retrieval with greedy temporal NMS: which moments of a video match the query, as clip indices or seconds.
+
+Semantics (csrc/moments.hip, include/smin_hip.h), for each sample b:
+  * candidates: the cells (i, j) with ``moment_mask[b, i, j] != 0``; masked cells are never returned (the reference's plain
+    ``topk`` can pick a masked cell with score 0 -- that is why the NMS path of ``compute_ious`` is opt-in);
+  * score = ``(pm[b,i,j] * sqrtf(ps[b,i])) * sqrtf(pe[b,j])`` in fp32, in this order (the formula of ``compute_ious``);
+  * order: higher score first, ties -> lower flat index ``i*L + j``; a score of -0 counts as +0;
+  * temporal IoU of two cells in clip units (moment (i, j) spans [i, j+1), as dataset.get_iou defines it):
+    ``inter = max(0, min(j1, j2) + 1 - max(i1, i2))``, ``union = max(j1, j2) + 1 - min(i1, i2)``,
+    ``iou = (float)inter / (float)union`` (one correctly rounded fp32 division);
+  * greedy NMS: walk the candidates in order; keep one unless its IoU with an already kept cell is > ``nms_thresh``
+    (converted to fp32 once); stop after k kept or when the candidates run out.  ``nms_thresh >= 1``: no suppression,
+    i.e. plain top-k over the valid cells;
+  * empty slots: index -1 and score 0; ``count[b]`` = number kept;
+  * limits: 1 <= k <= 64, B >= 1, L >= 1 with L*L < 2**31.
+
+``top_moments`` is the product entry point (HIP kernels, HIP tensors only, no host synchronisation, capturable in a graph);
+``top_moments_torch`` is the same function as plain torch + Python on any device, kept under its own name as the restatement
+the tests compare against -- nothing routes to it silently."""
+import ctypes
+
+import torch
+
+MAX_K = 64
+MAX_N, MAX_M = 64, 16               # compute_ious(..., nms_thresh=t): at most 64 values of n and 16 thresholds m
+
+
+def _check(pm, ps, pe, moment_mask, k):
+    if pm.dim() != 3 or pm.shape[1] != pm.shape[2]:
+        raise ValueError(f"pm must be (B, L, L), got {tuple(pm.shape)}")
+    B, L = pm.shape[0], pm.shape[1]
+    if tuple(ps.shape) != (B, L) or tuple(pe.shape) != (B, L) or tuple(moment_mask.shape) != (B, L, L):
+        raise ValueError(f"ps / pe must be (B, L) = {(B, L)} and moment_mask (B, L, L); got {tuple(ps.shape)}, {tuple(pe.shape)}, "
+                         f"{tuple(moment_mask.shape)}")
+    if B < 1 or L < 1 or L * L >= 2 ** 31:
+        raise ValueError(f"top_moments needs B >= 1 and 1 <= L with L*L < 2**31 (B={B}, L={L})")
+    if not (isinstance(k, int) and 1 <= k <= MAX_K):
+        raise ValueError(f"top_moments needs an integer 1 <= k <= {MAX_K} (got {k!r})")
+    return B, L
+
+
+def _times(idx, duration, L):
+    """(B, k, 2) seconds (i * duration / L, (j + 1) * duration / L) in fp32, NaN for empty slots (dataset.get_iou's clip units)."""
+    d = duration.to(device=idx.device, dtype=torch.float32).reshape(-1, 1, 1)
+    edge = idx.to(torch.float32) + torch.tensor([0.0, 1.0], device=idx.device)
+    t = edge * d / L
+    return torch.where(idx >= 0, t, torch.full_like(t, float("nan")))
+
+
+def _result(idx, score, count, duration, L):
+    out = {"idx": idx, "score": score, "count": count}
+    if duration is not None:
+        out["times"] = _times(idx, duration, L)
+    return out
+
+
+def _mask_u8(moment_mask):
+    return (moment_mask if moment_mask.dtype in (torch.bool, torch.uint8) else moment_mask != 0).contiguous()
+
+
+def top_moments(pm, ps, pe, moment_mask, k=5, nms_thresh=0.5, duration=None):
+    """The k best moments of each sample after greedy temporal NMS (module docstring), on the device: a band-parallel select
+    and one NMS workgroup per sample (csrc/moments.hip).  HIP tensors only; no host synchronisation.
+
+    Returns a dict: ``idx`` (B, k, 2) int64 start / end clip (-1 for empty slots), ``score`` (B, k) float32 (0 for empty
+    slots), ``count`` (B,) int32; with ``duration`` (B,) seconds also ``times`` (B, k, 2) float32:
+    ``(i * duration / L, (j + 1) * duration / L)``, NaN for empty slots."""
+    from .training import _require_hip
+    from ._lib import call, ptr, stream, load
+    _require_hip(pm, "top_moments")
+    B, L = _check(pm, ps, pe, moment_mask, k)
+    pm_, ps_, pe_ = (x.detach().float().contiguous() for x in (pm, ps, pe))
+    mm_ = _mask_u8(moment_mask)
+    idx = torch.empty((B, k, 2), dtype=torch.int64, device=pm.device)
+    score = torch.empty((B, k), dtype=torch.float32, device=pm.device)
+    count = torch.empty((B,), dtype=torch.int32, device=pm.device)
+    with torch.cuda.device(pm.device):
+        nbytes = load().smin_top_moments_ws_bytes(B, L, k)
+        ws = torch.empty((nbytes,), dtype=torch.uint8, device=pm.device)
+        call("smin_top_moments", stream(), ptr(pm_), ptr(ps_), ptr(pe_), ptr(mm_), B, L, k, float(nms_thresh),
+             ptr(idx), ptr(score), ptr(count), ptr(ws), nbytes)
+    return _result(idx, score, count, duration, L)
+
+
+# Correctly rounded fp32 sqrt / product / quotient on any device: computed in fp64 and rounded once to fp32 (fp64 carries more than
+# 2 * 24 + 2 bits, so the double rounding is exact for these three operations).  torch's own fp32 sqrt is not correctly rounded
+# on every CPU code path.
+def _sqrt32(x):
+    return torch.sqrt(x.float().double()).float()
+
+
+def _mul32(a, b):
+    return (a.float().double() * b.float().double()).float()
+
+
+def _iou(i1, j1, i2, j2):
+    inter = (torch.minimum(j1, j2) + 1 - torch.maximum(i1, i2)).clamp_min(0)
+    union = torch.maximum(j1, j2) + 1 - torch.minimum(i1, i2)
+    return (inter.to(torch.float32).double() / union.to(torch.float32).double()).float()
+
+
+def top_moments_torch(pm, ps, pe, moment_mask, k=5, nms_thresh=0.5, duration=None, chunk=256):
+    """``top_moments`` as plain torch + Python on any device (same result, bit for bit): the candidates sorted by (score, index),
+    then greedy NMS, testing ``chunk`` candidates at a time against the kept set."""
+    B, L = _check(pm, ps, pe, moment_mask, k)
+    dev = pm.device
+    score = _mul32(_mul32(pm.detach(), _sqrt32(ps.detach()).unsqueeze(2)), _sqrt32(pe.detach()).unsqueeze(1))
+    score = torch.where(score == 0, torch.zeros_like(score), score).reshape(B, -1)              # -0 -> +0
+    u = score.view(torch.int32).to(torch.int64) & 0xFFFFFFFF                                     # fp32 bits -> unsigned order word
+    o = torch.where(u >= 0x80000000, u ^ 0xFFFFFFFF, u | 0x80000000).clamp_min(1)
+    valid = _mask_u8(moment_mask).reshape(B, -1) != 0
+    o = torch.where(valid, o, torch.zeros_like(o))
+    order = torch.sort(o, dim=1, descending=True, stable=True).indices                          # ties keep index order
+    nvalid = valid.sum(dim=1).tolist()
+    thr = torch.tensor(float(nms_thresh), dtype=torch.float32, device=dev)
+    idx = torch.full((B, k, 2), -1, dtype=torch.int64, device=dev)
+    out_score = torch.zeros((B, k), dtype=torch.float32, device=dev)
+    count = torch.zeros((B,), dtype=torch.int32, device=dev)
+    for b in range(B):
+        cand = order[b, :nvalid[b]]
+        ki = torch.empty(0, dtype=torch.int64, device=dev)
+        kj = torch.empty(0, dtype=torch.int64, device=dev)
+        kc = []
+        for s in range(0, cand.numel(), chunk):
+            if len(kc) >= k:
+                break
+            c = cand[s:s + chunk]
+            ci, cj = c // L, c % L
+            if len(kc):
+                sup = (_iou(ci.unsqueeze(1), cj.unsqueeze(1), ki.unsqueeze(0), kj.unsqueeze(0)) > thr).any(dim=1)
+            else:
+                sup = torch.zeros_like(c, dtype=torch.bool)
+            n0 = len(kc)
+            for q in (~sup).nonzero().flatten().tolist():
+                if len(kc) >= k:
+                    break
+                if len(kc) > n0 and bool((_iou(ci[q], cj[q], ki[n0:], kj[n0:]) > thr).any()):
+                    continue                                                                     # suppressed inside the chunk
+                ki, kj = torch.cat([ki, ci[q:q + 1]]), torch.cat([kj, cj[q:q + 1]])
+                kc.append(int(c[q]))
+        n = len(kc)
+        if n:
+            idx[b, :n, 0], idx[b, :n, 1] = ki, kj
+            out_score[b, :n] = score[b, torch.tensor(kc, dtype=torch.int64, device=dev)]
+        count[b] = n
+    return _result(idx, out_score, count, duration, L)
+
+
+def _nm_check(n, m):
+    n, m = [int(x) for x in n], [float(x) for x in m]
+    if not (1 <= len(n) <= MAX_N and 1 <= len(m) <= MAX_M and min(n) >= 1 and max(n) <= MAX_K):
+        raise ValueError(f"compute_ious with nms_thresh: needs 1..{MAX_N} values 1 <= n <= {MAX_K} and 1..{MAX_M} thresholds m "
+                         f"(got n={n}, m={m})")
+    return n, m
+
+
+def compute_ious_nms(pm, ps, pe, moment_mask, sm, n, m, nms_thresh):
+    """R@n, IoU=m over the NMS-kept moments on the device (training.compute_ious(..., nms_thresh=t)): top-k with k = max(n), then
+    sm gathered at the kept cells (empty slot = IoU 0) and the hits summed over the samples by the device.  One host read."""
+    from ._lib import call, ptr, stream, load
+    B, L = _check(pm, ps, pe, moment_mask, 1)
+    keys = [f"R@{n_}, IoU={m_}" for n_ in n for m_ in m]
+    n, m = _nm_check(n, m)
+    k = max(n)
+    pm_, ps_, pe_, sm_ = (x.detach().float().contiguous() for x in (pm, ps, pe, sm))
+    mm_ = _mask_u8(moment_mask)
+    nl, ml = (ctypes.c_int * len(n))(*n), (ctypes.c_float * len(m))(*m)
+    counts = torch.empty((len(n) * len(m),), dtype=torch.float32, device=pm.device)
+    with torch.cuda.device(pm.device):
+        nbytes = load().smin_compute_ious_nms_ws_bytes(B, L, k, len(n), len(m))
+        ws = torch.empty((nbytes,), dtype=torch.uint8, device=pm.device)
+        call("smin_compute_ious_nms", stream(), ptr(pm_), ptr(ps_), ptr(pe_), ptr(mm_), ptr(sm_), B, L, k, float(nms_thresh),
+             ctypes.cast(nl, ctypes.c_void_p), len(n), ctypes.cast(ml, ctypes.c_void_p), len(m), ptr(counts), ptr(ws), nbytes)
+    return dict(zip(keys, counts.tolist()))
+
+
+def compute_ious_nms_torch(pm, ps, pe, moment_mask, sm, n, m, nms_thresh):
+    """``compute_ious_nms`` through ``top_moments_torch`` (any device)."""
+    B, L = _check(pm, ps, pe, moment_mask, 1)
+    keys = [f"R@{n_}, IoU={m_}" for n_ in n for m_ in m]
+    n, m = _nm_check(n, m)
+    r = top_moments_torch(pm, ps, pe, moment_mask, k=max(n), nms_thresh=nms_thresh)
+    flat = r["idx"][..., 0] * L + r["idx"][..., 1]
+    ious = torch.gather(sm.detach().float().reshape(B, -1), 1, flat.clamp_min(0))
+    ious = torch.where(flat >= 0, ious, torch.zeros_like(ious))
+    counts = torch.stack([((ious[:, :n_] > m_).sum(dim=1) > 0).sum() for n_ in n for m_ in m]).tolist()
+    return {k_: float(v) for k_, v in zip(keys, counts)}

@@ -49,8 +49,12 @@ def loss_fn(pm, ym, sm, moment_mask, ps, ys, ss, pe, ye, se, pa, ya, length_mask
         return LossFn.apply(pm, ps, pe, pa, ym, sm, moment_mask, ys, ss, ye, se, ya, length_mask)
 
 
-def compute_ious_torch(pm, ps, pe, moment_mask, sm, n=(1, 5), m=(0.1, 0.3, 0.5, 0.7)):
-    """reference utils.py:10-31 as plain torch ops with a single host sync (the reference syncs once per (n, m) pair)."""
+def compute_ious_torch(pm, ps, pe, moment_mask, sm, n=(1, 5), m=(0.1, 0.3, 0.5, 0.7), nms_thresh=None):
+    """reference utils.py:10-31 as plain torch ops with a single host sync (the reference syncs once per (n, m) pair).
+    ``nms_thresh`` set: R@n, IoU=m over the moments kept by greedy temporal NMS (moments.top_moments_torch) instead."""
+    if nms_thresh is not None:
+        from .moments import compute_ious_nms_torch
+        return compute_ious_nms_torch(pm, ps, pe, moment_mask, sm, n, m, nms_thresh)
     score = pm * torch.sqrt(ps.unsqueeze(2)) * torch.sqrt(pe.unsqueeze(1)) * moment_mask
     B = score.shape[0]
     _, top = score.reshape(B, -1).topk(k=max(n), dim=1)
@@ -60,11 +64,16 @@ def compute_ious_torch(pm, ps, pe, moment_mask, sm, n=(1, 5), m=(0.1, 0.3, 0.5, 
     return {k: float(v) for k, v in zip(keys, counts)}
 
 
-def compute_ious(pm, ps, pe, moment_mask, sm, n=(1, 5), m=(0.1, 0.3, 0.5, 0.7)):
+def compute_ious(pm, ps, pe, moment_mask, sm, n=(1, 5), m=(0.1, 0.3, 0.5, 0.7), nms_thresh=None):
     """reference utils.py:10-31 on the device.  With the reference's default n / m the whole metric is one kernel
     (csrc/metrics.hip) and one host read, for any L -- the 512 x 512 long-video map included.  Other (n, m), or a map
-    with fewer than five proposals (where the reference's topk raises), take the torch form on the device."""
+    with fewer than five proposals (where the reference's topk raises), take the torch form on the device.
+    ``nms_thresh`` set: R@n, IoU=m over the moments kept by greedy temporal NMS among the valid cells (moments.top_moments;
+    csrc/moments.hip), any n <= 64 and up to 16 thresholds m, one host read.  The reference has no NMS, so this is opt-in."""
     _require_hip(pm, "compute_ious")
+    if nms_thresh is not None:
+        from .moments import compute_ious_nms
+        return compute_ious_nms(pm, ps, pe, moment_mask, sm, n, m, nms_thresh)
     if tuple(n) == (1, 5) and tuple(m) == (0.1, 0.3, 0.5, 0.7) and pm.shape[1] * pm.shape[2] >= 5:
         from ._lib import call, ptr, stream
         B, L = ps.shape
