@@ -230,6 +230,27 @@ int smin_build_targets(void* stream, const float* times, const float* duration, 
                        const float* two_sigma_sq /* [B] or NULL: 2 sigma^2 of the boundary Gaussians as computed in double from the unrounded
                                                     annotation times (dataset.py:116-119); NULL: formed in double from the fp32 times */);
 
+/* ---- clip resampling of raw per-video features (reference dataset.py:40-74, AbstractDataset.get_fixed_length_features, per
+ * sample in numpy on the host there; csrc/sampling.hip).  raw [sum n_b][Din] (16-byte aligned), offsets [B+1] int64: sample b owns
+ * rows offsets[b] .. offsets[b+1], n = their count.  Outputs video_features [B][T][Din], nfeats [B] = min(n, T).
+ *   mode 0 (pick, the reference), in double: stride = 1 if n <= T else n / T; delta = (spos + stride) - spos (numpy arange's fill);
+ *     row t < min(n, T) = raw row rint(spos + t * delta) of the sample (round half to even, np.round).  spos [B] or NULL (all 0, the
+ *     eval split); a value outside the reference's draw range [0, int(r + 1)), r = stride - 0.5 minus 1 when integral
+ *     (dataset.py:45-49), is clamped into it.
+ *   mode 1 (mean; spos must be NULL): n <= T as pick; n > T: row t = mean of raw rows [a_t, a_{t+1}), a_t = rint(t * n / T) in double,
+ *     a_T = n, summed in fp32 in ascending row order and divided once in fp32 by the row count (the 2D-TAN alternative the
+ *     reference's comment at dataset.py:68-70 names).
+ *   Rows t >= min(n, T) are zero (dataset.py:72-73).  Requires Din % 4 == 0, B <= 65535.  No host read; B = 0 is a no-op. */
+int smin_sample_clips(void* stream, const float* raw, const int64_t* offsets, const int32_t* spos, int B, int T, int Din, int mode,
+                      float* video_features, int32_t* nfeats);
+
+/* ---- query word vectors from token ids (reference dataset.py:32-38 get_query_features, dataset.py:173 query mask).
+ * tokens [B][Nq] int32, table [V][E] (e.g. GloVe with <unk> and <pad> appended; 16-byte aligned, E % 4 == 0).
+ * query_features [B][Nq][E] = table[tokens] (an id outside [0, V) gives a zero row), query_mask [B][Nq] = 0 <= id < pad_id
+ * (bytes 0/1; an out-of-range id gives 0), qlen [B] = sum of the mask.  No host read; B = 0 is a no-op. */
+int smin_embed_tokens(void* stream, const int32_t* tokens, const float* table, int B, int Nq, int V, int E, int pad_id,
+                      float* query_features, uint8_t* query_mask, int32_t* qlen);
+
 /* ---- compute_ious (reference utils.py:10-31): counts [8] = number of samples with a hit for
  * R@1 x IoU {0.1, 0.3, 0.5, 0.7} then R@5 x the same; ws [B][8] scratch.  Any L with L*L >= 5 (the reference's topk(5) needs as many). */
 int smin_compute_ious(void* stream, const float* pm, const float* ps, const float* pe, const uint8_t* mm, const float* sm,

@@ -57,6 +57,8 @@ SIGNATURES = {
     "smin_compute_ious_nms_ws_bytes": [_i] * 5,
     "smin_compute_ious_nms": [_vp] * 6 + [_i] * 3 + [_f, _vp, _i, _vp, _i] + [_vp, _vp, _sz],
     "smin_build_targets": [_vp] * 5 + [_i] * 4 + [_vp] * 12,
+    "smin_sample_clips": [_vp] * 4 + [_i] * 4 + [_vp] * 2,
+    "smin_embed_tokens": [_vp] * 3 + [_i] * 5 + [_vp] * 3,
     "smin_word_prep_fwd": [_vp] * 5 + [_i] * 5 + [_vp] * 5,
     "smin_word_prep_bwd_workspace_bytes": [_i] * 5,
     "smin_word_prep_bwd": [_vp] * 11 + [_i] * 5 + [_vp] * 3 + [_vp, _sz],

@@ -6,7 +6,12 @@ derived -- the sampled clip features, the query word vectors and five scalars pe
 truth start / end, duration) -- in pinned host buffers, copies them on a dedicated HIP stream while the previous step computes,
 and one kernel (csrc/labels.hip) writes every mask and target on the device.  Two slots alternate; a slot is refilled only
 after the step that consumed it has been queued, which an event orders without host synchronisation.
+
+A loader may instead hand over each video's raw feature rows and the query's token ids (the raw batch form, ``BatchFeeder``
+docstring): the clip resampling of dataset.py:40-74 and the word-vector lookup of dataset.py:32-38 then run on the copy stream
+as well (csrc/sampling.hip), and the host only packs the ragged rows into a pinned buffer.
 """
+import numpy as np
 import torch
 
 from . import _lib
@@ -50,12 +55,27 @@ class BatchFeeder:
     """Double-buffered host -> device feeder.  ``feed(sample_batches)`` takes an iterable of host batches
     ``dict(video_features (B,T,Din) float32, query_features (B,Nq,300) float32, nfeats (B,), qlen (B,), times (B,2), duration (B,))``
     (numpy arrays or CPU tensors) and yields device batches with the thirteen entries main.py's loop reads, one batch ahead of
-    the consumer."""
+    the consumer.
 
-    def __init__(self, T, L, Nq, device, depth=3):
+    Raw batch form (chosen by its keys): ``dict(raw_features, tokens (B,Nq) int, times (B,2), duration (B,), spos (B,) optional)``
+    with ``raw_features`` a list of B arrays ``(n_b, Din)`` or one packed ``(sum n_b, Din)`` array plus ``raw_lengths (B,)``.  The
+    device resamples the rows to T clips (``pool``: "pick", the reference's rule, with start offsets ``spos``, default 0; or "mean",
+    sampling.py) and looks the ids up in ``embedding`` (a device ``(V, E)`` table, required for this form) with ``pad_id``
+    (default ``V - 1``); nfeats and qlen come from those kernels' outputs and query_mask is ``tokens < pad_id`` (dataset.py:173).
+    Token ids and ``spos`` are validated on the host (ValueError).  The yielded batch has the same thirteen entries."""
+
+    def __init__(self, T, L, Nq, device, depth=3, embedding=None, pad_id=None, pool="pick"):
+        from .sampling import MODES
         self.T, self.L, self.Nq, self.device = T, L, Nq, torch.device(device)
         if self.device.type != "cuda":
             raise _lib.SminHipError("BatchFeeder feeds a HIP device; there is no CPU path")
+        if pool not in MODES:
+            raise ValueError(f"pool must be one of {sorted(MODES)} (got {pool!r})")
+        if embedding is not None and not (embedding.is_cuda and embedding.dim() == 2):
+            raise _lib.SminHipError("BatchFeeder(embedding=...) takes a (V, E) table on the HIP device")
+        self.embedding = None if embedding is None else embedding.detach().float().contiguous()
+        self.pad_id = None if embedding is None else (embedding.shape[0] - 1 if pad_id is None else int(pad_id))
+        self.pool = pool
         self.copy_stream = torch.cuda.Stream(self.device)
         self.slots = [dict(host={}, ready=torch.cuda.Event(), consumed=None) for _ in range(depth)]
 
@@ -72,6 +92,8 @@ class BatchFeeder:
         """Host side of one batch: into the slot's pinned buffers, then H2D + target construction on the copy stream."""
         if "batch" in slot:
             slot["ready"].synchronize()                                      # the slot's previous H2D copies have left its pinned buffers
+        if "raw_features" in hb:
+            return self._stage_raw(slot, hb)
         t = {k: torch.as_tensor(v) for k, v in hb.items()}
         host = {k: self._pinned(slot, k, t[k].float() if k in ("video_features", "query_features", "times", "duration") else t[k].to(torch.int32))
                 for k in ("video_features", "query_features", "nfeats", "qlen", "times", "duration")}
@@ -83,6 +105,71 @@ class BatchFeeder:
             # (rows past a sample's sampled frames / words arrive as zeros, as the reference's loader makes them: dataset.py:72-73, 172)
             tg = build_targets_hip(d["times"], d["duration"], d["nfeats"], d["qlen"], self.T, self.L, self.Nq)
             batch = dict(video_features=d["video_features"], query_features=d["query_features"], **tg)
+            slot["ready"].record(self.copy_stream)
+        slot["batch"] = {k: batch[k] for k in _BATCH_KEYS}
+        return B
+
+    def _stage_raw(self, slot, hb):
+        """Raw batch form: pack the ragged rows into the slot's pinned buffer (grown on demand, then reused), stage offsets, ids,
+        start offsets and annotations, and enqueue H2D + resampling + lookup + targets on the copy stream.  No host read."""
+        from .sampling import embed_tokens, sample_clips, _check_spos
+        if self.embedding is None:
+            raise ValueError("a raw batch (tokens) needs BatchFeeder(embedding=<(V, E) device table>)")
+        raw = hb["raw_features"]
+        if isinstance(raw, (list, tuple)):
+            parts = [r if isinstance(r, torch.Tensor) else np.asarray(r) for r in raw]
+            lengths = np.array([p.shape[0] for p in parts], dtype=np.int64)
+        else:
+            parts = [raw if isinstance(raw, torch.Tensor) else np.asarray(raw)]
+            if "raw_lengths" not in hb:
+                raise ValueError("a packed raw_features array needs raw_lengths (B,)")
+            lengths = np.asarray(hb["raw_lengths"], dtype=np.int64).reshape(-1)
+            if (lengths < 0).any() or int(lengths.sum()) != parts[0].shape[0]:
+                raise ValueError(f"raw_lengths must be >= 0 and sum to the {parts[0].shape[0]} rows of raw_features")
+        B = lengths.shape[0]
+        Din = parts[0].shape[1] if parts and parts[0].ndim == 2 else -1
+        if B < 1 or Din < 4 or Din % 4 or any(p.ndim != 2 or p.shape[1] != Din for p in parts):
+            raise ValueError("raw_features must be (n_b, Din) arrays with one Din, Din % 4 == 0, and at least one sample")
+        tok = np.asarray(hb["tokens"].cpu() if isinstance(hb["tokens"], torch.Tensor) else hb["tokens"])
+        V = self.embedding.shape[0]
+        if tok.dtype.kind not in "iu" or tok.shape != (B, self.Nq):
+            raise ValueError(f"tokens must be an integer array of shape (B, Nq) = {(B, self.Nq)} (got {tok.dtype}, {tok.shape})")
+        if tok.size and (int(tok.min()) < 0 or int(tok.max()) >= V):
+            raise ValueError(f"token ids must lie in [0, {V}) (the embedding table's rows)")
+        spos = hb.get("spos")
+        spos = None if spos is None else _check_spos(spos, lengths, self.T, self.pool)
+        if self.pool == "mean":
+            spos = None                                                      # validated to be all 0
+        N = int(lengths.sum())
+        p0 = parts[0]
+        if len(parts) == 1 and isinstance(p0, torch.Tensor) and p0.dtype == torch.float32 and p0.is_contiguous() and p0.is_pinned():
+            packed = p0                                                      # a loader's pinned packed rows: no staging copy
+        else:
+            buf = slot["host"].get("raw")
+            if buf is None or buf.numel() < N * Din:                         # grows on demand, then is reused
+                buf = slot["host"]["raw"] = torch.empty(max(N * Din, 4), dtype=torch.float32, pin_memory=True)
+            packed = buf[:N * Din].view(N, Din)
+            # one plain memcpy per video through numpy: a single core and no GIL, where a torch copy_ of this size would start
+            # the intra-op thread pool and take cores from the thread that launches the step
+            dst = packed.numpy()
+            o = 0
+            for p in parts:
+                np.copyto(dst[o:o + p.shape[0]], p.detach().cpu().numpy() if isinstance(p, torch.Tensor) else p, casting="same_kind")
+                o += p.shape[0]
+        small = dict(offsets=torch.from_numpy(np.concatenate([[0], np.cumsum(lengths)]).astype(np.int64)), tokens=torch.from_numpy(tok.astype(np.int32)),
+                     times=torch.as_tensor(hb["times"]).float(), duration=torch.as_tensor(hb["duration"]).float())
+        if spos is not None:
+            small["spos"] = torch.from_numpy(spos)
+        host = {k: self._pinned(slot, "raw_" + k, v) for k, v in small.items()}
+        with torch.cuda.device(self.device), torch.cuda.stream(self.copy_stream):
+            if slot["consumed"] is not None:
+                self.copy_stream.wait_event(slot["consumed"])
+            d = {k: v.to(self.device, non_blocking=True) for k, v in host.items()}
+            raw_d = packed.to(self.device, non_blocking=True)
+            vf, nfeats = sample_clips(raw_d, d["offsets"], self.T, spos=d.get("spos"), mode=self.pool)
+            qf, qm, qlen = embed_tokens(d["tokens"], self.embedding, self.pad_id)
+            tg = build_targets_hip(d["times"], d["duration"], nfeats, None, self.T, self.L, self.Nq)
+            batch = dict(video_features=vf, query_features=qf, query_mask=qm.view(B, self.Nq, 1), **tg)
             slot["ready"].record(self.copy_stream)
         slot["batch"] = {k: batch[k] for k in _BATCH_KEYS}
         return B

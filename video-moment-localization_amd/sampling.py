@@ -1,0 +1,217 @@
+"""Clip resampling of raw per-video features and word-vector lookup of token ids, on the device (csrc/sampling.hip).
+
+The reference does both per sample on the host, in ``AbstractDataset.__getitem__``: ``get_fixed_length_features``
+(dataset.py:40-74) picks ``min(n, T)`` of a video's ``n`` raw feature rows at a stride of ``n / T`` and zero-pads the rest, and
+``get_query_features`` (dataset.py:32-38) turns token ids into GloVe vectors.  Here a loader hands over the raw rows and the ids.
+
+Pick (``mode="pick"``, the reference), for a video of ``n`` rows and a start offset ``spos``, all in double:
+
+* ``stride = 1.0`` if ``n <= T`` else ``n / T``; ``delta = (spos + stride) - spos`` (numpy ``arange``'s fill step);
+* row ``t < min(n, T)`` is raw row ``rint(spos + t * delta)`` (round half to even, as ``np.round``); later rows are zero;
+* ``spos`` is 0 in the eval split; the train split draws it from ``[0, int(r + 1))`` with ``r = stride - 0.5``, minus 1 when ``r``
+  is integral (dataset.py:45-49).  ``draw_offsets`` draws from that range; the kernel clamps a value outside it.
+
+Mean (``mode="mean"``, the 2D-TAN alternative the reference's comment at dataset.py:68-70 names; ``spos`` must be 0): for
+``n <= T`` the same as pick; for ``n > T`` row ``t`` is the mean of raw rows ``[a_t, a_{t+1})`` with ``a_t = rint(t * n / T)`` in
+double and ``a_T = n``, summed in fp32 in ascending row order and divided once in fp32 by the row count.
+
+``sample_clips`` / ``embed_tokens`` are the product entry points (HIP tensors only, no host read, capturable in a graph);
+``sample_clips_torch`` / ``clip_indices`` are the plain numpy / torch restatement the tests compare against -- nothing routes to
+them silently."""
+import numpy as np
+import torch
+
+MODES = {"pick": 0, "mean": 1}
+
+
+def spos_high(n, T):
+    """Exclusive upper end of the train split's start offset for videos of ``n`` rows: ``int(r + 1)`` with ``r = stride - 0.5``,
+    minus 1 when integral (dataset.py:45-49; ``np.random.randint(0, r + 1)`` draws from ``[0, int(r + 1))``).  1 when n <= T."""
+    n, T = np.asarray(n, dtype=np.int64), np.asarray(T, dtype=np.int64)
+    stride = np.where(n <= T, 1.0, n / T.astype(np.float64))
+    r = stride - 0.5
+    r = np.where(r == np.floor(r), r - 1.0, r)
+    return (r + 1.0).astype(np.int64)
+
+
+def draw_offsets(n, T, rng):
+    """Train-split start offsets for videos of ``n`` rows (array-like), drawn uniformly from ``[0, spos_high(n, T))`` with a
+    ``numpy.random.Generator`` (the reference's distribution; drawn on the host so a run is reproducible from its seed)."""
+    return rng.integers(0, spos_high(n, T)).astype(np.int32)
+
+
+def clip_indices(n, T, spos=0):
+    """The raw row indices the pick rule takes for a video of ``n`` rows (length ``min(n, T)``), from the definition above."""
+    n, spos = int(n), int(spos)
+    stride = 1.0 if n <= T else n / float(T)
+    s = float(spos)
+    delta = (s + stride) - s
+    idx = np.rint(s + np.arange(min(n, T), dtype=np.float64) * delta).astype(np.int64)
+    return np.clip(idx, 0, max(n - 1, 0))
+
+
+def mean_windows(n, T):
+    """Mean mode's window starts ``a_t`` (T + 1 entries, ``a_T = n``) for a video of ``n > T`` rows."""
+    a = np.rint(np.arange(T + 1, dtype=np.float64) * float(n) / float(T)).astype(np.int64)
+    a[T] = n
+    return a
+
+
+def _lengths_host(x):
+    return np.asarray(x.cpu() if isinstance(x, torch.Tensor) else x, dtype=np.int64).reshape(-1)
+
+
+def _check_spos(spos, lengths, T, mode):
+    """Host-side validation of start offsets against the reference's range (ValueError)."""
+    s = np.asarray(spos.cpu() if isinstance(spos, torch.Tensor) else spos, dtype=np.int64).reshape(-1)
+    if s.shape[0] != lengths.shape[0]:
+        raise ValueError(f"spos has {s.shape[0]} entries for {lengths.shape[0]} samples")
+    if mode == "mean" and s.any():
+        raise ValueError("mode='mean' takes no start offset (spos must be 0)")
+    hi = spos_high(lengths, T)
+    bad = np.nonzero((s < 0) | (s >= hi))[0]
+    if bad.size:
+        b = int(bad[0])
+        raise ValueError(f"spos[{b}] = {int(s[b])} is outside [0, {int(hi[b])}) for a video of {int(lengths[b])} rows at T = {T} "
+                         "(dataset.py:45-49)")
+    return s.astype(np.int32)
+
+
+def _pack(raw, offsets_or_lengths):
+    """-> (raw (N, Din) tensor, host lengths (B,) or None, device offsets (B+1,) int64 or None)."""
+    if isinstance(raw, (list, tuple)):
+        if offsets_or_lengths is not None:
+            raise ValueError("a list of per-video tensors carries its own lengths (offsets_or_lengths must be None)")
+        lengths = np.array([int(r.shape[0]) for r in raw], dtype=np.int64)
+        if len(raw) == 0:
+            return None, lengths, None
+        return torch.cat([r.reshape(-1, r.shape[-1]) for r in raw], 0), lengths, None
+    if isinstance(offsets_or_lengths, torch.Tensor) and offsets_or_lengths.is_cuda:
+        return raw, None, offsets_or_lengths
+    return raw, _lengths_host(offsets_or_lengths), None
+
+
+def sample_clips(raw, offsets_or_lengths, T, spos=None, mode="pick"):
+    """Resample a batch of ragged raw feature sequences to ``(B, T, Din)`` on the device (module docstring).
+
+    ``raw``: one packed HIP tensor ``(sum n_b, Din)`` with ``offsets_or_lengths`` either host lengths ``(B,)`` (list, numpy or CPU
+    tensor: validated here) or device offsets ``(B + 1,)`` int64 (nothing is read back: graph-capturable; they must be non-decreasing
+    and within ``raw``, which is not checked); or a list of ``B`` HIP tensors ``(n_b, Din)`` with ``offsets_or_lengths=None``.
+    ``spos``: ``None`` (all 0, the eval split), host values (validated against the reference's range: ValueError) or a device int
+    tensor ``(B,)``.  Returns ``(video_features (B, T, Din) float32, nfeats (B,) int32)`` with ``nfeats = min(n_b, T)``."""
+    from ._lib import SminHipError, call, ptr, stream
+    if mode not in MODES:
+        raise ValueError(f"mode must be one of {sorted(MODES)} (got {mode!r})")
+    raw, lengths, offsets = _pack(raw, offsets_or_lengths)
+    if raw is None:
+        raise ValueError("sample_clips needs at least one video (or a packed tensor with B = 0 lengths)")
+    if not raw.is_cuda:
+        raise SminHipError("sample_clips runs on a HIP device only (got a CPU tensor); there is no CPU fallback -- "
+                           "the plain restatement is available under the explicit name sample_clips_torch")
+    if raw.dim() != 2 or raw.shape[1] % 4 != 0 or raw.shape[1] < 4:
+        raise ValueError(f"raw must be (rows, Din) with Din % 4 == 0 (got {tuple(raw.shape)})")
+    dev, Din, T = raw.device, raw.shape[1], int(T)
+    if T < 1:
+        raise ValueError(f"T must be >= 1 (got {T})")
+    raw = raw.detach().float().contiguous()
+    if raw.data_ptr() % 16:
+        raw = raw.clone()
+    if lengths is not None:
+        if (lengths < 0).any() or int(lengths.sum()) != raw.shape[0]:
+            raise ValueError(f"lengths must be >= 0 and sum to raw's {raw.shape[0]} rows (got {lengths.sum()})")
+        offsets = torch.from_numpy(np.concatenate([[0], np.cumsum(lengths)]).astype(np.int64)).to(dev, non_blocking=False)
+        B = int(lengths.shape[0])
+    else:
+        if offsets.dtype != torch.int64 or offsets.dim() != 1 or offsets.shape[0] < 1:
+            raise ValueError("device offsets must be a 1-D int64 tensor of B + 1 entries")
+        B = offsets.shape[0] - 1
+    sp = None
+    if spos is not None:
+        if isinstance(spos, torch.Tensor) and spos.is_cuda:
+            if mode != "pick":
+                raise ValueError("mode='mean' takes no start offset (spos must be None)")
+            sp = spos.to(torch.int32).contiguous()
+        elif lengths is not None:
+            s = _check_spos(spos, lengths, T, mode)
+            sp = torch.from_numpy(s).to(dev) if mode == "pick" else None
+        else:
+            raise ValueError("host spos needs host lengths to be checked against (pass lengths, or spos as a device tensor)")
+    out = torch.empty((B, T, Din), dtype=torch.float32, device=dev)
+    nfeats = torch.empty((B,), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        call("smin_sample_clips", stream(), ptr(raw), ptr(offsets.contiguous()), ptr(sp), B, T, Din, MODES[mode], ptr(out), ptr(nfeats))
+    return out, nfeats
+
+
+def sample_clips_torch(raw, offsets_or_lengths, T, spos=None, mode="pick"):
+    """``sample_clips`` as plain numpy on the host (same result, bit for bit): the restatement the device is checked against.
+    Takes the same argument forms (host lengths or offsets; CPU or device tensors, copied to the host); returns CPU tensors."""
+    if mode not in MODES:
+        raise ValueError(f"mode must be one of {sorted(MODES)} (got {mode!r})")
+    if isinstance(raw, (list, tuple)):
+        rows = [np.asarray(r.detach().cpu() if isinstance(r, torch.Tensor) else r, dtype=np.float32).reshape(-1, r.shape[-1]) for r in raw]
+        lengths = np.array([r.shape[0] for r in rows], dtype=np.int64)
+        Din = rows[0].shape[1] if rows else 0
+        packed = np.concatenate(rows, 0) if rows else np.zeros((0, Din), np.float32)
+    else:
+        packed = np.asarray(raw.detach().cpu() if isinstance(raw, torch.Tensor) else raw, dtype=np.float32)
+        lengths = _lengths_host(offsets_or_lengths)
+        if isinstance(offsets_or_lengths, torch.Tensor) and offsets_or_lengths.is_cuda:
+            lengths = np.diff(lengths)                                        # device offsets -> lengths
+        Din = packed.shape[1]
+    B = lengths.shape[0]
+    s = np.zeros(B, np.int64) if spos is None else _check_spos(spos, lengths, T, mode)
+    offs = np.concatenate([[0], np.cumsum(lengths)]).astype(np.int64)
+    out = np.zeros((B, T, Din), np.float32)
+    for b in range(B):
+        n, x = int(lengths[b]), packed[offs[b]:offs[b + 1]]
+        if mode == "pick" or n <= T:
+            idx = clip_indices(n, T, s[b])
+            out[b, :idx.shape[0]] = x[idx]
+        else:
+            a = mean_windows(n, T)
+            cnt = a[1:] - a[:-1]
+            acc = x[a[:-1]].copy()
+            for q in range(1, int(cnt.max())):                               # fp32 sum in ascending row order
+                m = cnt > q
+                acc[m] += x[a[:-1][m] + q]
+            out[b] = acc / cnt.astype(np.float32)[:, None]
+    return torch.from_numpy(out), torch.from_numpy(np.minimum(lengths, T).astype(np.int32))
+
+
+def embed_tokens(tokens, table, pad_id=None):
+    """Query word vectors from token ids on the device (dataset.py:32-38, 173).  ``tokens`` (B, Nq) integer HIP tensor, ``table``
+    (V, E) float32 HIP tensor (E % 4 == 0), ``pad_id`` default ``V - 1`` (the reference's ``<pad>``, appended last).
+
+    Returns ``(query_features (B, Nq, E) float32 = table[tokens], query_mask (B, Nq) uint8 = tokens < pad_id, qlen (B,) int32 = sum
+    of the mask)``.  An id outside ``[0, V)`` gives a zero row and mask 0; it is never read."""
+    from ._lib import SminHipError, call, ptr, stream
+    if not (tokens.is_cuda and table.is_cuda):
+        raise SminHipError("embed_tokens runs on a HIP device only (got a CPU tensor); there is no CPU fallback")
+    if tokens.dim() != 2 or table.dim() != 2 or table.shape[1] % 4 != 0 or table.shape[1] < 4 or tokens.shape[1] < 1:
+        raise ValueError(f"tokens must be (B, Nq >= 1) and table (V, E) with E % 4 == 0 (got {tuple(tokens.shape)}, {tuple(table.shape)})")
+    (B, Nq), (V, E) = tokens.shape, table.shape
+    pad_id = V - 1 if pad_id is None else int(pad_id)
+    tok = tokens.to(torch.int32).contiguous()
+    tab = table.detach().float().contiguous()
+    if tab.data_ptr() % 16:
+        tab = tab.clone()
+    dev = tokens.device
+    qf = torch.empty((B, Nq, E), dtype=torch.float32, device=dev)
+    qm = torch.empty((B, Nq), dtype=torch.uint8, device=dev)
+    ql = torch.empty((B,), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        call("smin_embed_tokens", stream(), ptr(tok), ptr(tab), B, Nq, V, E, pad_id, ptr(qf), ptr(qm), ptr(ql))
+    return qf, qm, ql
+
+
+def embed_tokens_torch(tokens, table, pad_id=None):
+    """``embed_tokens`` as plain torch on any device (the restatement)."""
+    V = table.shape[0]
+    pad_id = V - 1 if pad_id is None else int(pad_id)
+    t = tokens.to(torch.int64)
+    ok = (t >= 0) & (t < V)
+    qf = table.float()[t.clamp(0, V - 1)]
+    qf = torch.where(ok.unsqueeze(-1), qf, torch.zeros_like(qf))
+    qm = (ok & (t < pad_id)).to(torch.uint8)
+    return qf, qm, qm.sum(1, dtype=torch.int32)
