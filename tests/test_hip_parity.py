@@ -185,6 +185,16 @@ def test_full_size_against_golden(dev, name):
 
 
 # ---------------------------------------------------------------- oracle on fresh seeded inputs
+# rows that send the one-node extension path into attention-core forms no other model-level case reaches
+# (form <DL,WS,EXACT> as SMIN_ATTN_DISPATCH in csrc/content_attn.hip picks it)
+NATIVE_ROWS = [
+    (64, 16, 4, 128, 64, 2, 40, 9, 64, 3),       # <64,4,T>
+    (32, 16, 4, 64, 32, 1, 24, 17, 32, 5),       # <32,8,T>, extra-word slots partly used
+    (32, 8, 4, 64, 16, 2, 24, 32, 32, 2),        # <16,8,T>
+    (64, 16, 4, 256, 128, 2, 40, 23, 128, 3),    # <128,6,T>
+    (32, 8, 4, 192, 128, 2, 24, 29, 96, 4),      # <128,8,T>; parameter products in csrc/param_prep.hip
+    (64, 16, 4, 104, 48, 2, 24, 18, 52, 3),      # <64,8,F> with dl < DL; torch parameter prep (D % 32 != 0)
+]
 @pytest.mark.parametrize("T,L,C,D,dl,layers,Din,Nq,Hh,B", [
     (64, 16, 4, 64, 32, 2, 40, 9, 32, 5),
     (48, 24, 4, 128, 64, 1, 32, 20, 64, 3),      # r = 2 < C: empty clips and dropped frames
@@ -193,7 +203,7 @@ def test_full_size_against_golden(dev, name):
     (16, 16, 4, 64, 32, 2, 24, 6, 32, 3),        # r = 1: one frame per snippet (general proposal-map backward path)
     (32, 8, 4, 64, 16, 5, 24, 6, 32, 2),         # 5 layers: the content stream's history spills into a second 4-wide partition
     (32, 8, 4, 64, 16, 9, 24, 6, 32, 2),         # 9 layers: beyond the clip-window-means launch limit -> unit as written
-])
+] + NATIVE_ROWS)
 def test_against_oracle_random(dev, T, L, C, D, dl, layers, Din, Nq, Hh, B):
     from oracle import smin_oracle as O
     from vml_amd import loss_fn
@@ -206,7 +216,10 @@ def test_against_oracle_random(dev, T, L, C, D, dl, layers, Din, Nq, Hh, B):
     l0.backward()
     m = build_model(dict(T=T, L=L, C=C, D=D, dl=dl, layers=layers, Din=Din, Nq=Nq, H=Hh), sd, dev)
     b = {k: v.to(dev) for k, v in batch.items()}
-    pm, ps, pe, pa = m(*H.model_inputs(b))
+    xs = H.model_inputs(b)
+    if (T, L, C, D, dl, layers, Din, Nq, Hh, B) in NATIVE_ROWS:
+        assert m._native_ok(xs[0], xs[2])
+    pm, ps, pe, pa = m(*xs)
     for got, ref in ((pm, pm0), (ps, ps0), (pe, pe0), (pa, pa0)):
         assert (got.detach().cpu() - ref.detach()).abs().max().item() < SCORE_TOL
     loss = loss_fn(pm, b["ym"], b["sm"], b["moment_mask"], ps, b["ys"], b["ss"], pe, b["ye"], b["se"], pa, b["ya"], b["length_mask"])

@@ -258,12 +258,16 @@ using namespace smin;
 
 static size_t wp_fwd_lds(int rpp, int D, int dl) { return sizeof(float) * ((size_t)(rpp + 1) * D + 2 * (size_t)rpp * dl); }
 static size_t wp_bwd_lds(int rpp, int D, int dl) { return sizeof(float) * ((size_t)rpp * D + 5 * (size_t)rpp * dl + 32 + dl); }
-// rows per part: enough (sample, layer, part) workgroups to fill the chip, at least one word each
-static int wp_rows_per_part(int nl, int B, int Nq)
+constexpr size_t WP_MAX_LDS = 160 * 1024;
+// rows per part: enough (sample, layer, part) workgroups to fill the chip, at least one word each, and few enough rows that
+// both directions' LDS images fit (large batches would otherwise take a whole query per part: at D = 768, dl = 128 the
+// backward of 32 rows needs 180 KB)
+static int wp_rows_per_part(int nl, int B, int Nq, int D, int dl)
 {
     int parts = cdiv(384, nl * B);
     if (parts > Nq) parts = Nq;
     if (parts < 1) parts = 1;
+    while (parts < Nq && (wp_fwd_lds(cdiv(Nq, parts), D, dl) > WP_MAX_LDS || wp_bwd_lds(cdiv(Nq, parts), D, dl) > WP_MAX_LDS)) ++parts;
     return cdiv(Nq, parts);
 }
 
@@ -271,8 +275,8 @@ extern "C" int smin_word_prep_fwd(void* stream, const float* fw, const float* fs
                                   int dl, float* what, float* shat, float* kb, float* Mq, float* uq)
 {
     if (B == 0) return 0;
-    const int rpp = wp_rows_per_part(nl, B, Nq), parts = cdiv(Nq, rpp);
-    SMIN_REQUIRE(nl >= 1 && nl <= WP_MAXL && Nq >= 1 && Nq <= 32 && D % 4 == 0 && dl % 4 == 0 && dl <= 128 && wp_fwd_lds(rpp, D, dl) <= 160 * 1024);
+    const int rpp = wp_rows_per_part(nl, B, Nq, D, dl), parts = cdiv(Nq, rpp);
+    SMIN_REQUIRE(nl >= 1 && nl <= WP_MAXL && Nq >= 1 && Nq <= 32 && D % 4 == 0 && dl % 4 == 0 && dl <= 128 && wp_fwd_lds(rpp, D, dl) <= WP_MAX_LDS);
     WordParams P;
     for (int i = 0; i < WP_MAXL * 8; ++i) P.p[i] = params[i < nl * 8 ? i : 0];
     const size_t lds = wp_fwd_lds(rpp, D, dl);
@@ -289,7 +293,7 @@ extern "C" int smin_word_prep_fwd(void* stream, const float* fw, const float* fs
 
 extern "C" size_t smin_word_prep_bwd_workspace_bytes(int nl, int B, int Nq, int D, int dl)
 {
-    const int parts = B > 0 ? cdiv(Nq, wp_rows_per_part(nl, B, Nq)) : 1;
+    const int parts = B > 0 ? cdiv(Nq, wp_rows_per_part(nl, B, Nq, D, dl)) : 1;
     return sizeof(float) * ((size_t)nl * B * parts * wp_slab_floats(D, dl) + (size_t)nl * B * Nq * D + (size_t)nl * B * D + 64);
 }
 
@@ -299,8 +303,8 @@ extern "C" int smin_word_prep_bwd(void* stream, const float* const* dwhat, const
 {
     hipStream_t st = (hipStream_t)stream;
     if (B == 0) return 0;
-    const int rpp = wp_rows_per_part(nl, B, Nq), parts = cdiv(Nq, rpp);
-    SMIN_REQUIRE(nl >= 1 && nl <= WP_MAXL && Nq >= 1 && Nq <= 32 && D % 4 == 0 && dl % 4 == 0 && dl <= 128 && wp_bwd_lds(rpp, D, dl) <= 160 * 1024);
+    const int rpp = wp_rows_per_part(nl, B, Nq, D, dl), parts = cdiv(Nq, rpp);
+    SMIN_REQUIRE(nl >= 1 && nl <= WP_MAXL && Nq >= 1 && Nq <= 32 && D % 4 == 0 && dl % 4 == 0 && dl <= 128 && wp_bwd_lds(rpp, D, dl) <= WP_MAX_LDS);
     SMIN_REQUIRE(ws_bytes >= smin_word_prep_bwd_workspace_bytes(nl, B, Nq, D, dl));
     WordParams P; WordGrads Q; WordOuts G;
     for (int i = 0; i < WP_MAXL * 8; ++i) { P.p[i] = params[i < nl * 8 ? i : 0]; Q.p[i] = dparams[i < nl * 8 ? i : 0]; }
