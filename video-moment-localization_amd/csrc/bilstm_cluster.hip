@@ -16,7 +16,9 @@
 // start at 1), so replays of a captured step see no stale tags.  Every poll is bounded: on expiry an error word is set and the
 // launch finishes with wrong values instead of hanging.
 // Residency: the grid never exceeds one workgroup per CU (clusters loop over their sample groups), so every workgroup of a
-// cluster becomes resident without waiting for another workgroup of this launch to exit.
+// cluster becomes resident without waiting for another workgroup of this launch to exit.  The grid is padded to whole groups of
+// 8 clusters (cluster_of), so the cluster count is capped at (CUs / (8 P)) * 8, not CUs / P: at P = 5, 6, 7 the latter padded
+// to 280 / 288 / 280 workgroups on 256 CUs, where the forward's LDS (90-124 KB) leaves room for one workgroup per CU.
 #include "gemm.h"
 #include "smin_hip.h"
 #include <stdlib.h>
@@ -484,7 +486,7 @@ static void cl_geometry(int B, int H, int& P, int& nclus, int& grid)
 {
     P = H / CL_U;
     const int ngroups = cdiv(B, CL_BS) * 2;
-    int maxclus = cl_num_cus() / P;                                  // never more than one workgroup per CU: see the header
+    int maxclus = cl_num_cus() / (8 * P) * 8;                        // never more than one workgroup per CU: see the header
     if (maxclus < 1) maxclus = 1;
     nclus = ngroups < maxclus ? ngroups : maxclus;
     grid = cdiv(nclus, 8) * 8 * P;                                   // cluster_of deals ids over 8 XCD classes
