@@ -154,6 +154,36 @@ def test_fused_step_repeats_bit_for_bit(dev):
             assert torch.equal(ref[k], cur[k]), (it, k)
 
 
+def test_fused_step_on_a_second_device_bit_identical(dev):
+    """The one-node step on cuda:0, then on cuda:1 in the same process with cuda:0 left current: the library's per-device launch
+    state (CU count, dynamic-LDS opt-ins) has to be set up again for cuda:1.  The shape reaches the cluster LSTM (H = 256), the
+    attention backward above 64 KB of LDS (dl = 128) and the word-prep backward's opt-in (16 words per part at D = 512).  Scores and
+    every parameter gradient are equal bit for bit on both devices, and no bounded poll of the cluster recurrence expires."""
+    if torch.cuda.device_count() < 2:
+        pytest.skip(f"needs two HIP devices in one process; {torch.cuda.device_count()} visible")
+    from oracle import smin_oracle as O
+    from vml_amd import loss_fn
+    import models
+    T, L, C, D, dl, layers, Din, Nq, Hh, B = 32, 16, 4, 512, 128, 3, 64, 32, 256, 64
+    sd = O.formula_state_dict(H.smin_shapes(T, L, C, D, dl, layers, Din, Nq, Hh), gain=1.2)
+    batch = O.synthetic_batch(B, T, L, Nq, Din, seed=23)
+    torch.cuda.set_device(0)
+    runs = []
+    for d in (torch.device("cuda:0"), torch.device("cuda:1")):
+        m = build_model(dict(T=T, L=L, C=C, D=D, dl=dl, layers=layers, Din=Din, Nq=Nq, H=Hh), sd, d)
+        b = {k: v.to(d) for k, v in batch.items()}
+        out = m(*H.model_inputs(b))
+        loss_fn(out[0], b["ym"], b["sm"], b["moment_mask"], out[1], b["ys"], b["ss"], out[2], b["ye"], b["se"], out[3], b["ya"], b["length_mask"]).backward()
+        assert torch.cuda.current_device() == 0
+        runs.append([o.detach().cpu() for o in out] + [p.grad.cpu() for _, p in m.named_parameters()])
+    names = ["pm", "ps", "pe", "pa"] + [k for k, _ in m.named_parameters()]
+    for k, on0, on1 in zip(names, *runs):
+        assert torch.equal(on0, on1), k
+    for d in (0, 1):
+        with torch.cuda.device(d):
+            assert models.vml_amd._lib.load().smin_lstm_cluster_error() == 0, f"a bounded poll of the cluster recurrence expired on cuda:{d}"
+
+
 # ---------------------------------------------------------------- full BASELINE shapes vs golden (formula weights)
 @pytest.mark.parametrize("name", ["tacos_yml", "tacos_d500", "charades", "anet_yml", "anet_t256"])
 def test_full_size_against_golden(dev, name):

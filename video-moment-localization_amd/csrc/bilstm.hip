@@ -300,8 +300,7 @@ extern "C" int smin_bilstm_layer_fwd(void* stream, const float* X, const float* 
     if (bilstm_cluster_ok(B, Nq, H)) return launch_bilstm_cluster_fwd(st, G, W4, len, B, Nq, H, Hout, Cs);
     const int Hp = cdiv(H, 64) * 64;
     const size_t lds = sizeof(float) * ((size_t)H * LSTM_BS + (size_t)16 * LSTM_BS * Hp);
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(bilstm_fwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return (int)e;
+    if (int e = lds_optin(reinterpret_cast<const void*>(bilstm_fwd_kernel), lds)) return e;
     hipLaunchKernelGGL(bilstm_fwd_kernel, dim3(cdiv(B, LSTM_BS), 2), dim3(4 * Hp), lds, st, G, W4, len, B, Nq, H, Hout, Cs);
     SMIN_LAUNCH_CHECK();
     return 0;
@@ -379,8 +378,7 @@ extern "C" int smin_bilstm_layer_bwd(void* stream, const float* dHout, const flo
     const int Hp = cdiv(H, 64) * 64;
     const size_t lds = sizeof(float) * ((size_t)H4 * LSTM_BS + (size_t)16 * LSTM_BS * Hp);
     SMIN_REQUIRE(H4 % 16 == 0);
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(bilstm_bwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return (int)e;
+    if (int e = lds_optin(reinterpret_cast<const void*>(bilstm_bwd_kernel), lds)) return e;
     SMIN_REQUIRE(dHout != nullptr || dWih_cat != nullptr);
     int rc;
     if (dHout) {                                                       // inputs half: the recurrence (gate gradients stay in ws), dX

@@ -425,16 +425,6 @@ void bilstm_cluster_bwd_kernel(const float* __restrict__ dHout, const float* __r
 }
 
 // ---- launchers ----------------------------------------------------------------------------------------------------------------
-static int cl_num_cus()
-{
-    static int n = 0;
-    if (n == 0) {
-        int dev = 0, v = 0;
-        if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) n = v;
-        else n = 256;
-    }
-    return n;
-}
 // Exchange buffers, one per (device, direction), allocated ONCE at the size the largest geometry needs on this device (the cluster
 // count is capped by the CU count, so the bound does not depend on the batch): forward <= 256 CUs + 64 H granules, backward
 // <= 2048 CUs + 2048 P^2.  Never reallocated, so a captured graph's launches keep a valid address.  The step runs its recurrences
@@ -451,7 +441,7 @@ static unsigned long long* cl_exchange(int which, size_t granules)
     std::lock_guard<std::mutex> lk(mu);
     auto& b = bufs[std::make_pair(dev, which)];
     if (!b.first) {
-        const size_t ncu = (size_t)cl_num_cus();
+        const size_t ncu = (size_t)device_cus();
         const size_t cap = which == 0 ? 256 * ncu + 64 * 256 : 2048 * ncu + 2048 * 64;
         if (hipMalloc(reinterpret_cast<void**>(&b.first), cap * sizeof(unsigned long long)) != hipSuccess) { b.first = nullptr; return nullptr; }
         b.second = cap;
@@ -486,7 +476,7 @@ static void cl_geometry(int B, int H, int& P, int& nclus, int& grid)
 {
     P = H / CL_U;
     const int ngroups = cdiv(B, CL_BS) * 2;
-    int maxclus = cl_num_cus() / (8 * P) * 8;                        // never more than one workgroup per CU: see the header
+    int maxclus = device_cus() / (8 * P) * 8;                        // never more than one workgroup per CU: see the header
     if (maxclus < 1) maxclus = 1;
     nclus = ngroups < maxclus ? ngroups : maxclus;
     grid = cdiv(nclus, 8) * 8 * P;                                   // cluster_of deals ids over 8 XCD classes
@@ -497,11 +487,7 @@ int launch_bilstm_cluster_fwd(hipStream_t st, float* G, const float* W4, const i
     int P, nclus, grid;
     cl_geometry(B, H, P, nclus, grid);
     const size_t lds = sizeof(float) * ((size_t)H * CL_U * 4 + (size_t)H * CL_BS + (size_t)4 * 2 * 4 * 64);
-    static bool attr = false;
-    if (!attr) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(bilstm_cluster_fwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return -1;
-        attr = true;
-    }
+    if (lds_optin(reinterpret_cast<const void*>(bilstm_cluster_fwd_kernel), 160 * 1024)) return -1;
     const size_t gran = (size_t)cdiv(nclus, 8) * 8 * 2 * H * CL_BS;
     unsigned long long* xch = cl_exchange(0, gran);
     if (!xch) return -2;
@@ -518,11 +504,7 @@ int launch_bilstm_cluster_bwd(hipStream_t st, const float* dHout, const float* G
     int P, nclus, grid;
     cl_geometry(B, H, P, nclus, grid);
     const size_t lds = sizeof(float) * ((size_t)4 * CL_U * H + (size_t)4 * CL_U * CL_BS + (size_t)CL_U * CL_BS);
-    static bool attr = false;
-    if (!attr) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(bilstm_cluster_bwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return -1;
-        attr = true;
-    }
+    if (lds_optin(reinterpret_cast<const void*>(bilstm_cluster_bwd_kernel), 160 * 1024)) return -1;
     const size_t gran = (size_t)cdiv(nclus, 8) * 8 * 2 * P * P * CL_U * CL_BS;
     unsigned long long* xch = cl_exchange(1, gran);
     if (!xch) return -2;

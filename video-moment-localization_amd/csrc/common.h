@@ -25,6 +25,12 @@ struct ProfScope {
     ProfScope(hipStream_t s, int t) : st(s), tag(t), on(g_prof_on != 0) { if (on) prof_record(st, tag, true); }
     ~ProfScope() { if (on) prof_record(st, tag, false); }
 };
+
+// launch-time state of the CURRENT device (util.hip), cached per device under one lock (the backward runs on autograd's thread):
+// its CU count (256 if the query fails), and the dynamic-LDS opt-in of `kernel` raised to `bytes` unless that much was granted
+// already on this device (never lowered; returns the hipError_t of hipFuncSetAttribute, 0 when nothing had to be set)
+int device_cus();
+int lds_optin(const void* kernel, size_t bytes);
 }  // namespace smin
 
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }

@@ -943,23 +943,13 @@ __global__ void content_attn_reduce_kernel(const float* __restrict__ slab, const
 }
 
 // ---- launchers --------------------------------------------------------------------------------------------------
-static int attn_num_cus()
-{
-    static int n = 0;
-    if (n == 0) {
-        int dev = 0, v = 0;
-        if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) n = v;
-        else n = 256;
-    }
-    return n;
-}
 // equal ranges of the cell list, one per workgroup slot; whole tiles (4 cells), at least `min_cells`
 static int range_cells(int N, int slots, int min_cells)
 {
     int c = cdiv(cdiv(N, slots), 4) * 4;
     return c < min_cells ? min_cells : c;
 }
-int content_attn_bwd_range_cells(int N) { return range_cells(N, 2 * attn_num_cus(), 16); }      // two 256-thread workgroups per CU, whole rounds
+int content_attn_bwd_range_cells(int N) { return range_cells(N, 2 * device_cus(), 16); }      // two 256-thread workgroups per CU, whole rounds
 
 template <int DL, int WS, bool EXACT>
 static int fwd_t(hipStream_t st, const float* chat, const int* cells, const int* row_ptr, int N, int B, int L, int C,
@@ -968,7 +958,7 @@ static int fwd_t(hipStream_t st, const float* chat, const int* cells, const int*
 {
     (void)B;
     static const int wgs_per_cu = getenv("SMIN_ATTN_FWD_WGS") ? atoi(getenv("SMIN_ATTN_FWD_WGS")) : 3;
-    const int cpr = range_cells(N, wgs_per_cu * attn_num_cus(), 16);      // three 256-thread workgroups per CU (118 registers, 36 KB of LDS each; four measured no faster: the launch is bound by HBM)
+    const int cpr = range_cells(N, wgs_per_cu * device_cus(), 16);      // three 256-thread workgroups per CU (118 registers, 36 KB of LDS each; four measured no faster: the launch is bound by HBM)
     const dim3 grid(cdiv(N, cpr));
     const size_t lds = fwd_lds_bytes<DL>();
     const float scale = 1.0f / sqrtf((float)dl);
@@ -1041,14 +1031,8 @@ static int bwd_v(hipStream_t st, const float* chat, const float* dcchat, const i
                  const float* dmean2, float mscale)
 {
     const int cpr = content_attn_bwd_range_cells(N);
-    static bool attr_set = false;                                // > 64 KB of dynamic LDS needs the opt-in, once per instantiation
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&content_attn_bwd_kernel<DL, WS, MEAN2, PERCELL, EXACT>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           (int)(bwd_lds_bytes<DL, WS>()));
-        if (e != hipSuccess) return (int)e;
-        attr_set = true;
-    }
-    const size_t lds = bwd_lds_bytes<DL, WS>();
+    const size_t lds = bwd_lds_bytes<DL, WS>();                  // > 64 KB of dynamic LDS needs the opt-in
+    if (int e = lds_optin(reinterpret_cast<const void*>(&content_attn_bwd_kernel<DL, WS, MEAN2, PERCELL, EXACT>), lds)) return e;
     hipLaunchKernelGGL((content_attn_bwd_kernel<DL, WS, MEAN2, PERCELL, EXACT>), dim3(cdiv(N, cpr)), dim3(256), lds, st, chat, dcchat, cells, row_ptr, L, C,
                        Mq, uq, what, shat, qmask, dchat, ws, dl, Nq, N, cpr, 1.0f / sqrtf((float)dl), g_per_cell, gscale, dmean2, mscale);
     SMIN_LAUNCH_CHECK();

@@ -463,11 +463,8 @@ template <class Src, int NS, int UNR, bool HAS_M>
 static int launch_events2_t(hipStream_t st, const Src& src, const float* dfm, const int32_t* cells, const int32_t* cellmap,
                             const int32_t* ev_off, const Ev* ev_tab, int B, int T, int L, int C, int D, float* E, size_t lds)
 {
-    if (lds > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(proposal_map_bwd_events2_kernel<Src, NS, UNR, HAS_M>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return (int)e;
-    }
+    if (lds > 48 * 1024)
+        if (int e = lds_optin(reinterpret_cast<const void*>(proposal_map_bwd_events2_kernel<Src, NS, UNR, HAS_M>), lds)) return e;
     hipLaunchKernelGGL((proposal_map_bwd_events2_kernel<Src, NS, UNR, HAS_M>), dim3(T * 8 * cdiv(B, 8)), dim3(128), lds, st, src, dfm, cells, cellmap, ev_off, ev_tab,
                        B, T, L, C, D, E, 1);
     SMIN_LAUNCH_CHECK();

@@ -58,6 +58,21 @@ struct StreamScope {                       // torch's current stream for the sco
     ~StreamScope() { c10::hip::setCurrentHIPStream(prev); }
 };
 
+// The process-wide caches below: a map under its own lock (the forward runs on the caller's thread, the backward on the autograd
+// engine's).  get() returns the key's entry, made by `make` under the lock the first time; entries are never erased.
+template <class K, class V>
+struct Cache {
+    std::mutex mu;
+    std::map<K, V> m;
+    template <class Make> V& get(const K& key, Make make)
+    {
+        std::lock_guard<std::mutex> lk(mu);
+        auto it = m.find(key);
+        if (it == m.end()) it = m.emplace(key, make()).first;
+        return it->second;
+    }
+};
+
 // Events for stream joins: a ring per device (an event is bound to the device it was created on), created under that device's
 // guard.  A draw is consumed (recorded and waited for by hipStreamWaitEvent, or synchronised by the host) within the call that
 // drew it; the ring is far longer than the draws of one forward + backward pass (~60 at three layers), so no event is
@@ -65,12 +80,11 @@ struct StreamScope {                       // torch's current stream for the sco
 hipEvent_t next_event()
 {
     constexpr size_t RING = 1024;
-    static std::mutex mu;
-    static std::map<int, std::pair<std::vector<hipEvent_t>, size_t>> rings;
+    static Cache<int, std::pair<std::vector<hipEvent_t>, size_t>> rings;   // (its draw counter advances: locked here)
     int dev = 0;
     TORCH_CHECK(hipGetDevice(&dev) == hipSuccess, "hipGetDevice failed");
-    std::lock_guard<std::mutex> lk(mu);
-    auto& ring = rings[dev];
+    std::lock_guard<std::mutex> lk(rings.mu);
+    auto& ring = rings.m[dev];
     if (ring.first.empty()) {
         ring.first.resize(RING);
         for (auto& e : ring.first) TORCH_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming) == hipSuccess, "hipEventCreate failed");
@@ -87,45 +101,36 @@ void wait_stream(HStream waiter, HStream on)
 }
 HStream side_stream(c10::DeviceIndex dev, int which = 0)
 {
-    static std::mutex mu;
-    static std::map<std::pair<int, int>, HStream> streams;
-    std::lock_guard<std::mutex> lk(mu);
-    auto it = streams.find({(int)dev, which});
-    if (it == streams.end()) {
+    static Cache<std::pair<int, int>, HStream> streams;
+    return streams.get({(int)dev, which}, [&] {
         HStream st = c10::hip::getStreamFromPool(false, dev);
-        for (auto& kv : streams)                                  // the pool hands its streams out round robin: never the same one twice
+        for (auto& kv : streams.m)                                // the pool hands its streams out round robin: never the same one twice
             while (kv.first.first == (int)dev && kv.second == st) st = c10::hip::getStreamFromPool(false, dev);
-        it = streams.emplace(std::make_pair((int)dev, which), st).first;
-    }
-    return it->second;
+        return st;
+    });
 }
 
 // lowest-priority stream for work nobody waits for until the end of the step (weight-gradient contractions)
 HStream weight_stream(c10::DeviceIndex dev)
 {
-    static std::mutex mu;
-    static std::map<int, HStream> streams;
-    std::lock_guard<std::mutex> lk(mu);
-    auto it = streams.find(dev);
-    if (it == streams.end()) {
+    static Cache<int, HStream> streams;
+    return streams.get(dev, [&] {
         int least = 0, greatest = 0;
         TORCH_CHECK(hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess, "hipDeviceGetStreamPriorityRange failed");
         hipStream_t raw;
         TORCH_CHECK(hipStreamCreateWithPriority(&raw, hipStreamNonBlocking, least) == hipSuccess, "hipStreamCreateWithPriority failed");
-        it = streams.emplace((int)dev, c10::hip::getStreamFromExternal(raw, dev)).first;
-    }
-    return it->second;
+        return c10::hip::getStreamFromExternal(raw, dev);
+    });
 }
 
 // persistent scratch per (device, stream): calls on one stream are stream-ordered, two streams never share scratch
 struct Scratch { void* p; size_t n; Tensor hold; };
 Scratch scratch(size_t nbytes, const at::Device& dev)
 {
-    static std::mutex mu;
-    static std::map<std::pair<int, int64_t>, Tensor> bufs;
+    static Cache<std::pair<int, int64_t>, Tensor> bufs;                 // (an entry grows: locked here)
     const auto st = c10::hip::getCurrentHIPStream(dev.index());
-    std::lock_guard<std::mutex> lk(mu);
-    Tensor& b = bufs[{(int)dev.index(), (int64_t)st.id()}];
+    std::lock_guard<std::mutex> lk(bufs.mu);
+    Tensor& b = bufs.m[{(int)dev.index(), (int64_t)st.id()}];
     if (!b.defined() || (size_t)b.numel() < nbytes)
         b = at::empty({(int64_t)(nbytes + nbytes / 4 + 4096)}, at::TensorOptions().dtype(at::kByte).device(dev));
     return Scratch{b.data_ptr(), (size_t)b.numel(), b};
@@ -134,22 +139,22 @@ Scratch scratch(size_t nbytes, const at::Device& dev)
 // the geometry's clip-boundary table, built once per (device, T, L, C)
 std::pair<Tensor, Tensor> clip_event_table(const at::Device& dev, int T, int L, int C, bool* built_now = nullptr)
 {
-    static std::mutex mu;
-    static std::map<std::tuple<int, int, int, int>, std::pair<Tensor, Tensor>> tabs;
-    std::lock_guard<std::mutex> lk(mu);
-    auto key = std::make_tuple((int)dev.index(), T, L, C);
-    auto it = tabs.find(key);
-    if (built_now) *built_now = it == tabs.end();                 // built on the CURRENT stream: a consumer on another stream has to wait for it
-    if (it != tabs.end()) return it->second;
-    auto io = at::TensorOptions().dtype(at::kInt).device(dev);
-    Tensor counts = at::empty({T}, io);
-    SMIN_CK(smin_clip_event_table(cur(), T, L, C, counts.data_ptr<int32_t>(), nullptr, nullptr));
-    Tensor offsets = at::zeros({T + 1}, io);
-    offsets.slice(0, 1).copy_(at::cumsum(counts, 0).to(at::kInt));
-    const int64_t n = std::max<int64_t>(1, offsets[T].item<int64_t>());
-    Tensor table = at::empty({n, 2}, io);
-    SMIN_CK(smin_clip_event_table(cur(), T, L, C, nullptr, ip(offsets), table.data_ptr()));
-    return tabs.emplace(key, std::make_pair(offsets, table)).first->second;
+    static Cache<std::tuple<int, int, int, int>, std::pair<Tensor, Tensor>> tabs;
+    bool built = false;
+    auto& tab = tabs.get(std::make_tuple((int)dev.index(), T, L, C), [&] {
+        built = true;
+        auto io = at::TensorOptions().dtype(at::kInt).device(dev);
+        Tensor counts = at::empty({T}, io);
+        SMIN_CK(smin_clip_event_table(cur(), T, L, C, counts.data_ptr<int32_t>(), nullptr, nullptr));
+        Tensor offsets = at::zeros({T + 1}, io);
+        offsets.slice(0, 1).copy_(at::cumsum(counts, 0).to(at::kInt));
+        const int64_t n = std::max<int64_t>(1, offsets[T].item<int64_t>());
+        Tensor table = at::empty({n, 2}, io);
+        SMIN_CK(smin_clip_event_table(cur(), T, L, C, nullptr, ip(offsets), table.data_ptr()));
+        return std::make_pair(offsets, table);
+    });
+    if (built_now) *built_now = built;                            // built on the CURRENT stream: a consumer on another stream has to wait for it
+    return tab;
 }
 
 Tensor undef() { return Tensor(); }
@@ -157,23 +162,15 @@ Tensor undef() { return Tensor(); }
 // device word that smin_build_cells_n sets when a caller-supplied cell count does not match the mask (see csrc/layout.hip)
 Tensor layout_status(const at::Device& dev)
 {
-    static std::mutex mu;
-    static std::map<int, Tensor> st;
-    std::lock_guard<std::mutex> lk(mu);
-    Tensor& t = st[(int)dev.index()];
-    if (!t.defined()) t = at::zeros({1}, at::TensorOptions().dtype(at::kInt).device(dev));
-    return t;
+    static Cache<int, Tensor> st;
+    return st.get(dev.index(), [&] { return at::zeros({1}, at::TensorOptions().dtype(at::kInt).device(dev)); });
 }
 
 // the two device words smin_step_prologue counts with (zero between launches)
 Tensor prologue_words(const at::Device& dev)
 {
-    static std::mutex mu;
-    static std::map<int, Tensor> st;
-    std::lock_guard<std::mutex> lk(mu);
-    Tensor& t = st[(int)dev.index()];
-    if (!t.defined()) t = at::zeros({2}, at::TensorOptions().dtype(at::kLong).device(dev));
-    return t;
+    static Cache<int, Tensor> st;
+    return st.get(dev.index(), [&] { return at::zeros({2}, at::TensorOptions().dtype(at::kLong).device(dev)); });
 }
 
 // ---------------------------------------------------------------- gradient exchange inside the node (data parallel)

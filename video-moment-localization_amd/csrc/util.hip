@@ -2,7 +2,9 @@
 #include "gemm.h"
 #include "smin_hip.h"
 #include <stdlib.h>
+#include <map>
 #include <mutex>
+#include <utility>
 #include <vector>
 
 namespace smin {
@@ -44,6 +46,36 @@ void prof_record(hipStream_t st, int tag, bool begin)
         for (size_t k = g_prof.size(); k-- > 0;)
             if (g_prof[k].tag == tag && !g_prof[k].closed) { (void)hipEventRecord(g_prof[k].e1, st); g_prof[k].closed = true; break; }
     }
+}
+
+// ---- per-device launch state (common.h): (device, kernel) -> bytes of dynamic LDS opted in; (device, nullptr) -> CU count
+static std::mutex g_dev_mu;
+static std::map<std::pair<int, const void*>, size_t> g_dev_state;
+
+int device_cus()
+{
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return 256;
+    std::lock_guard<std::mutex> lk(g_dev_mu);
+    size_t& n = g_dev_state[{dev, nullptr}];
+    if (n == 0) {
+        int v = 0;
+        n = hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0 ? v : 256;
+    }
+    return (int)n;
+}
+
+int lds_optin(const void* kernel, size_t bytes)
+{
+    int dev = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e != hipSuccess) return (int)e;
+    std::lock_guard<std::mutex> lk(g_dev_mu);
+    size_t& granted = g_dev_state[{dev, kernel}];
+    if (granted >= bytes) return 0;
+    e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    if (e == hipSuccess) granted = bytes;
+    return (int)e;
 }
 
 __global__ void reduce_slabs_kernel(const float* __restrict__ slab, float* __restrict__ out, int n, int P)

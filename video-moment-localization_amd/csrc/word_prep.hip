@@ -280,12 +280,8 @@ extern "C" int smin_word_prep_fwd(void* stream, const float* fw, const float* fs
     WordParams P;
     for (int i = 0; i < WP_MAXL * 8; ++i) P.p[i] = params[i < nl * 8 ? i : 0];
     const size_t lds = wp_fwd_lds(rpp, D, dl);
-    static size_t lds_set = 0;
-    if (lds > 64 * 1024 && lds > lds_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&word_prep_fwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return (int)e;
-        lds_set = lds;
-    }
+    if (lds > 64 * 1024)
+        if (int e = lds_optin(reinterpret_cast<const void*>(&word_prep_fwd_kernel), lds)) return e;
     hipLaunchKernelGGL(word_prep_fwd_kernel, dim3(B, nl, parts), dim3(256), lds, (hipStream_t)stream, fw, fs, qmask, P, B, Nq, D, dl, rpp, what, shat, kb, Mq, uq);
     SMIN_LAUNCH_CHECK();
     return 0;
@@ -315,12 +311,8 @@ extern "C" int smin_word_prep_bwd(void* stream, const float* const* dwhat, const
     float* dfw_part = slab + (size_t)nl * B * parts * wp_slab_floats(D, dl);
     float* dfs_part = dfw_part + (size_t)nl * B * Nq * D;
     const size_t lds = wp_bwd_lds(rpp, D, dl);
-    static size_t lds_set = 0;
-    if (lds > 64 * 1024 && lds > lds_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&word_prep_bwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return (int)e;
-        lds_set = lds;
-    }
+    if (lds > 64 * 1024)
+        if (int e = lds_optin(reinterpret_cast<const void*>(&word_prep_bwd_kernel), lds)) return e;
     hipLaunchKernelGGL(word_prep_bwd_kernel, dim3(B, nl, parts), dim3(256), lds, st, G, fw, fs, qmask, what, kb, P, B, Nq, D, dl, rpp, dfw_part, dfs_part, slab);
     SMIN_LAUNCH_CHECK();
     const size_t per_layer = wp_slab_floats(D, dl) + (size_t)dl * D + dl, rows = (size_t)B * Nq * D + (size_t)B * D;
