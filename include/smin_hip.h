@@ -147,7 +147,8 @@ int smin_boundary_reduce_bwd(void* stream, const float* dfbm, const float* Ab, c
  *   out = (A_b f_b) * lm + f_b + sum_j A_b[i,j] hbar[(i,j)],  A_b = softmax(mask(bq bq^T / sqrt(D))) * lm,
  *   bq = f_b * (softmax(mask(W_q f_b . (W_k f_w)^T / sqrt(D))) f_w * lm + f_s).
  * fb [B][L][D], fw [B][Nq][D], fs [B][D], qmask [B][Nq], lmask [B][L] fp32 0/1; Wq, Wk [D][D] (+ biases).
- * Saved for backward (caller-allocated): Qb, baq, bqv [B][L][D], Kb [B][Nq][D], P [B][L][Nq], A [B][L][L]. */
+ * Saved for backward (caller-allocated): Qb, baq, bqv [B][L][D], Kb [B][Nq][D], P [B][L][Nq], A [B][L][L].
+ * P is also the boundary unit's Attention.attn_weights (models.py:137-154), every row i (length_mask 0 included). */
 int smin_boundary_unit_fwd(void* stream, const float* fb, const float* fw, const float* fs, const float* hbar,
                            const int32_t* cells, const int32_t* row_ptr, int N, int B, int L, int Nq, int D,
                            const float* Wq, const float* bq, const float* Wk, const float* bk,
@@ -310,6 +311,25 @@ int smin_content_attn_fwd_cch(void* stream, const float* chat, const int32_t* ce
                               int N, int B, int L, int C, int dl, int Nq,
                               const float* Mq, const float* uq, const float* what, const float* shat, const float* qmask,
                               uint16_t* cc_h, float* ccmean);
+/* smin_content_attn_fwd that also stores the word probabilities of every packed row, ContentAttention.attn_weights
+ * (models.py:207-226): probs [N*C][Nq] fp32, padded words exactly 0.  cc may be NULL (no rows), fp32 [N*C][dl], or, with
+ * cc_bf16 != 0, bf16 [N*C][dl] (then ccmean is required).  cc / ccmean are bit-identical to smin_content_attn_fwd(_cch). */
+int smin_content_attn_fwd_probs(void* stream, const float* chat, const int32_t* cells, const int32_t* row_ptr,
+                                int N, int B, int L, int C, int dl, int Nq,
+                                const float* Mq, const float* uq, const float* what, const float* shat, const float* qmask,
+                                void* cc, int cc_bf16, float* ccmean, float* probs);
+/* Dense ContentAttention.attn_weights out [B][L][L][C][Nq] (models.py:207-226) from packed probs [N*C][Nq]: a cell with
+ * cellmap[b][i][j] = n >= 0 and m = cells[n][3] != 0 copies rows n*C .. n*C+C-1; any other cell gets the reference's value
+ * there, softmax over words of mask(uq[b] / sqrt(dl)) (its c_hat is 0, so its query is W_q.bias; uq from smin_word_prep_fwd). */
+int smin_content_attn_maps_dense(void* stream, const float* probs, const int32_t* cellmap, const int32_t* cells,
+                                 int B, int L, int C, int dl, int Nq, const float* uq, const float* qmask, float* out);
+/* The maps of the moments top_moments kept (idx [B][k][2] int64 start / end, -1 = empty slot), without a dense map:
+ * probs / bmaps are HOST arrays of nl <= SMIN_ATTN_MAPS_MAX_LAYERS device pointers, probs[l] [N*C][Nq] (content, models.py:207-226)
+ * and bmaps[l] [B][L][Nq] (boundary, Attention.attn_weights, models.py:137-154).  content [B][k][nl][C][Nq] = probs[l] rows of the
+ * cell cellmap[b][i][j]; boundary [B][k][nl][2][Nq] = bmaps[l] rows i and j.  Empty slots are 0. */
+#define SMIN_ATTN_MAPS_MAX_LAYERS 8
+int smin_attn_maps_gather(void* stream, const float* const* probs, const float* const* bmaps, int nl, const int32_t* cellmap,
+                          const int64_t* idx, int B, int L, int C, int Nq, int k, float* content, float* boundary);
 size_t smin_content_attn_bwd_workspace_bytes(int N, int B, int C, int dl);
 /* dcc [N*C][dl] and/or dccmean [N][dl] (one may be NULL) -> dchat [N*C][dl], dMq, duq, dwhat, dshat. */
 int smin_content_attn_bwd(void* stream, const float* dcc, const float* dccmean, const float* chat,

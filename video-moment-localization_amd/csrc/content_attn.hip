@@ -451,12 +451,16 @@ static size_t fwd_lds_bytes() { return sizeof(float) * (size_t)(32 * (DL + 4) + 
 // ROWS: 0 none, 1 fp32 rows, 2 rows stored as bf16 (round to nearest even; cchat then points to 16-bit elements)
 // EXACT: dl == DL and C == 4 (every shipped configuration): row strides, feature clamps and clip predicates are constants --
 // fewer address instructions and far fewer scalar registers (the general form keeps a clamped offset and a predicate per block)
-template <int DL, int WS, int ROWS, bool MEAN, bool EXACT>
+// PROBS: the word probabilities of every row also go to probs [N*C][Nq] (models.py:224-225, ContentAttention.attn_weights): a store
+// of the registers P, nothing else of the arithmetic changes.  With PROBS = false `probs` is never read: those instantiations
+// compile to the code they had before the flag existed.
+template <int DL, int WS, int ROWS, bool MEAN, bool EXACT, bool PROBS = false>
 __global__ __launch_bounds__(256, 4)
 void content_attn_fwd_kernel(const float* __restrict__ chat, const int* __restrict__ cells, const int* __restrict__ row_ptr, int L, int C,
                              const float* __restrict__ Mq, const float* __restrict__ uq, const float* __restrict__ what,
                              const float* __restrict__ shat, const float* __restrict__ qmask,
-                             float* __restrict__ cchat, float* __restrict__ ccmean, int dl, int Nq, int N, int cells_per_range, float scale)
+                             float* __restrict__ cchat, float* __restrict__ ccmean, int dl, int Nq, int N, int cells_per_range, float scale,
+                             float* __restrict__ probs)
 {
     extern __shared__ __attribute__((aligned(16))) float smem_dyn[];
     constexpr int KJ = DL / 16;
@@ -491,6 +495,13 @@ void content_attn_fwd_kernel(const float* __restrict__ chat, const int* __restri
             g = row_geom16(cells, n0 + 16, seg_end, C, lane);
             fetch_rows16<DL>(raw, chat, g.row, dl, kg);
             scores_softmax16<DL, WS>(P, ch, sM, sU, sQ, Nq, scale, lane);
+            if (PROBS && gc.ok) {                                     // register r of lane group kg is word 16 (r >> 2) + 4 (r & 3) + kg
+#pragma unroll
+                for (int r = 0; r < 8; ++r) {
+                    const int w = 16 * (r >> 2) + 4 * (r & 3) + kg;
+                    if (w < Nq) probs[(size_t)gc.row * Nq + w] = P[r];
+                }
+            }
             __builtin_amdgcn_sched_barrier(0);
             clip_attention16<DL>(Ao, ch, sS, gc, scale, lane, [&](int j) {
                 f32x4v z4 = {0.f, 0.f, 0.f, 0.f};
@@ -530,6 +541,66 @@ void content_attn_fwd_kernel(const float* __restrict__ chat, const int* __restri
             __builtin_amdgcn_sched_barrier(0);
         }
         n = seg_end;
+    }
+}
+
+// ---- the maps in the reference's layout ---------------------------------------------------------------------------
+// Dense ContentAttention.attn_weights (B, L, L, C, Nq) from the packed rows: a listed cell with m == 1 copies its C rows; every
+// other cell holds what the reference computes there.  Its query is W_q(c_hat) with c_hat = 0 (models.py:247, masked), i.e.
+// W_q.bias, so its scores are uq[b] / sqrt(dl) and its weights softmax(mask(uq[b] / sqrt(dl))) -- the same for every clip and
+// every masked cell of the sample.  One workgroup per (i, b): the sample's masked row in LDS, then L*C*Nq consecutive floats.
+__global__ __launch_bounds__(256)
+void content_attn_maps_dense_kernel(const float* __restrict__ probs, const int* __restrict__ cellmap, const int* __restrict__ cells,
+                                    const float* __restrict__ uq, const float* __restrict__ qmask, int L, int C, int Nq, float scale,
+                                    float* __restrict__ out)
+{
+    __shared__ float sP[32];
+    const int i = blockIdx.x, b = blockIdx.y, t = threadIdx.x;
+    if (t < 64) {                                                 // one wave: the masked row (models.py:213-224 with query W_q.bias)
+        float v = -INFINITY;
+        if (t < Nq) {
+            const float qm = qmask[(size_t)b * Nq + t];
+            v = qm == 0.f ? -1e9f : uq[(size_t)b * Nq + t] * scale * qm;
+        }
+        float mx = v;
+        for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
+        const float e = t < Nq ? expf(v - mx) : 0.f;
+        float den = e;
+        for (int o = 32; o > 0; o >>= 1) den += __shfl_xor(den, o);
+        if (t < Nq) sP[t] = e / den;
+    }
+    __syncthreads();
+    const int per_cell = C * Nq, tot = L * per_cell;
+    const size_t base = ((size_t)b * L + i) * tot;
+    for (int x = t; x < tot; x += 256) {
+        const int j = x / per_cell, r = x - j * per_cell, w = r % Nq;
+        const int n = cellmap[((size_t)b * L + i) * L + j];
+        const bool listed = n >= 0 && cells[4 * (size_t)n + 3] != 0;
+        out[base + x] = listed ? probs[(size_t)n * per_cell + r] : sP[w];
+    }
+}
+
+// Per kept moment of top_moments (idx [B][k][2] int64, -1 = empty slot): content[b][s][l][c][w] = probs_l[cellmap[b][i][j] C + c][w],
+// boundary[b][s][l][e][w] = bmaps_l[b][(i, j)[e]][w]; empty slots and unlisted cells give 0.
+struct MapPtrs { const float* p[SMIN_ATTN_MAPS_MAX_LAYERS]; };
+__global__ __launch_bounds__(256)
+void attn_maps_gather_kernel(MapPtrs probs, MapPtrs bmaps, const int* __restrict__ cellmap, const long long* __restrict__ idx, int L, int C, int Nq,
+                             int k, int nl, float* __restrict__ content, float* __restrict__ boundary)
+{
+    const int s = blockIdx.x, b = blockIdx.y, t = threadIdx.x;
+    const long long i = idx[((size_t)b * k + s) * 2], j = idx[((size_t)b * k + s) * 2 + 1];
+    const bool ok = i >= 0 && j >= 0 && i < L && j < L;
+    const int n = ok ? cellmap[((size_t)b * L + i) * L + j] : -1;
+    const int pc = C * Nq;
+    float* co = content + ((size_t)b * k + s) * nl * pc;
+    float* bo = boundary + ((size_t)b * k + s) * nl * 2 * Nq;
+    for (int x = t; x < nl * pc; x += 256) {
+        const int l = x / pc, r = x - l * pc;
+        co[x] = n >= 0 ? probs.p[l][(size_t)n * pc + r] : 0.f;
+    }
+    for (int x = t; x < nl * 2 * Nq; x += 256) {
+        const int l = x / (2 * Nq), e = (x / Nq) & 1, w = x % Nq;
+        bo[x] = ok ? bmaps.p[l][((size_t)b * L + (e ? j : i)) * Nq + w] : 0.f;
     }
 }
 
@@ -951,10 +1022,24 @@ static int range_cells(int N, int slots, int min_cells)
 }
 int content_attn_bwd_range_cells(int N) { return range_cells(N, 2 * device_cus(), 16); }      // two 256-thread workgroups per CU, whole rounds
 
+template <int DL, int WS, int ROWS, bool MEAN, bool EXACT>
+static void fwd_launch(dim3 grid, size_t lds, hipStream_t st, const float* chat, const int* cells, const int* row_ptr, int L, int C,
+                       const float* Mq, const float* uq, const float* what, const float* shat, const float* qmask,
+                       float* cc_rows, float* cc_mean, int dl, int Nq, int N, int cpr, float scale, float* probs)
+{
+    if (probs)
+        hipLaunchKernelGGL((content_attn_fwd_kernel<DL, WS, ROWS, MEAN, EXACT, true>), grid, dim3(256), lds, st, chat, cells, row_ptr, L, C, Mq, uq, what, shat,
+                           qmask, cc_rows, cc_mean, dl, Nq, N, cpr, scale, probs);
+    else
+        hipLaunchKernelGGL((content_attn_fwd_kernel<DL, WS, ROWS, MEAN, EXACT, false>), grid, dim3(256), lds, st, chat, cells, row_ptr, L, C, Mq, uq, what, shat,
+                           qmask, cc_rows, cc_mean, dl, Nq, N, cpr, scale, nullptr);
+}
+
+// probs: NULL, or [N*C][Nq] for the word probabilities (the PROBS twin of the same instantiation)
 template <int DL, int WS, bool EXACT>
 static int fwd_t(hipStream_t st, const float* chat, const int* cells, const int* row_ptr, int N, int B, int L, int C,
                  const float* Mq, const float* uq, const float* what, const float* shat, const float* qmask,
-                 float* cc_rows, float* cc_mean, int dl, int Nq, bool rows_bf16)
+                 float* cc_rows, float* cc_mean, int dl, int Nq, bool rows_bf16, float* probs)
 {
     (void)B;
     static const int wgs_per_cu = getenv("SMIN_ATTN_FWD_WGS") ? atoi(getenv("SMIN_ATTN_FWD_WGS")) : 3;
@@ -963,17 +1048,13 @@ static int fwd_t(hipStream_t st, const float* chat, const int* cells, const int*
     const size_t lds = fwd_lds_bytes<DL>();
     const float scale = 1.0f / sqrtf((float)dl);
     if (rows_bf16)                                                // (rows + mean: the only bf16-rows combination a host asks for)
-        hipLaunchKernelGGL((content_attn_fwd_kernel<DL, WS, 2, true, EXACT>), grid, dim3(256), lds, st, chat, cells, row_ptr, L, C, Mq, uq, what, shat, qmask,
-                           cc_rows, cc_mean, dl, Nq, N, cpr, scale);
+        fwd_launch<DL, WS, 2, true, EXACT>(grid, lds, st, chat, cells, row_ptr, L, C, Mq, uq, what, shat, qmask, cc_rows, cc_mean, dl, Nq, N, cpr, scale, probs);
     else if (cc_rows && cc_mean)
-        hipLaunchKernelGGL((content_attn_fwd_kernel<DL, WS, 1, true, EXACT>), grid, dim3(256), lds, st, chat, cells, row_ptr, L, C, Mq, uq, what, shat, qmask,
-                           cc_rows, cc_mean, dl, Nq, N, cpr, scale);
+        fwd_launch<DL, WS, 1, true, EXACT>(grid, lds, st, chat, cells, row_ptr, L, C, Mq, uq, what, shat, qmask, cc_rows, cc_mean, dl, Nq, N, cpr, scale, probs);
     else if (cc_rows)
-        hipLaunchKernelGGL((content_attn_fwd_kernel<DL, WS, 1, false, EXACT>), grid, dim3(256), lds, st, chat, cells, row_ptr, L, C, Mq, uq, what, shat, qmask,
-                           cc_rows, cc_mean, dl, Nq, N, cpr, scale);
+        fwd_launch<DL, WS, 1, false, EXACT>(grid, lds, st, chat, cells, row_ptr, L, C, Mq, uq, what, shat, qmask, cc_rows, cc_mean, dl, Nq, N, cpr, scale, probs);
     else
-        hipLaunchKernelGGL((content_attn_fwd_kernel<DL, WS, 0, true, EXACT>), grid, dim3(256), lds, st, chat, cells, row_ptr, L, C, Mq, uq, what, shat, qmask,
-                           cc_rows, cc_mean, dl, Nq, N, cpr, scale);
+        fwd_launch<DL, WS, 0, true, EXACT>(grid, lds, st, chat, cells, row_ptr, L, C, Mq, uq, what, shat, qmask, cc_rows, cc_mean, dl, Nq, N, cpr, scale, probs);
     SMIN_LAUNCH_CHECK();
     return 0;
 }
@@ -1004,7 +1085,7 @@ int launch_content_attn_fwd(hipStream_t st, const float* chat, const int* cells,
                             float* cc_rows, float* cc_mean, int dl, int Nq)
 {
     if (N <= 0) return 0;
-    SMIN_ATTN_DISPATCH(fwd_t, st, chat, cells, row_ptr, N, B, L, C, Mq, uq, what, shat, qmask, cc_rows, cc_mean, dl, Nq, false);
+    SMIN_ATTN_DISPATCH(fwd_t, st, chat, cells, row_ptr, N, B, L, C, Mq, uq, what, shat, qmask, cc_rows, cc_mean, dl, Nq, false, nullptr);
 }
 
 // the same with the rows stored as bf16 (cc_rows_h [N*C][dl] 16-bit) beside the fp32 clip mean
@@ -1014,7 +1095,16 @@ int launch_content_attn_fwd_h(hipStream_t st, const float* chat, const int* cell
 {
     if (N <= 0) return 0;
     float* cc_rows = reinterpret_cast<float*>(cc_rows_h);
-    SMIN_ATTN_DISPATCH(fwd_t, st, chat, cells, row_ptr, N, B, L, C, Mq, uq, what, shat, qmask, cc_rows, cc_mean, dl, Nq, true);
+    SMIN_ATTN_DISPATCH(fwd_t, st, chat, cells, row_ptr, N, B, L, C, Mq, uq, what, shat, qmask, cc_rows, cc_mean, dl, Nq, true, nullptr);
+}
+
+// either of the above with the word probabilities stored as well (probs [N*C][Nq]); rows fp32 (cc_rows_h NULL) or bf16
+static int launch_content_attn_fwd_probs(hipStream_t st, const float* chat, const int* cells, const int* row_ptr, int N, int B, int L, int C,
+                                         const float* Mq, const float* uq, const float* what, const float* shat, const float* qmask,
+                                         float* cc_rows, bool rows_bf16, float* cc_mean, float* probs, int dl, int Nq)
+{
+    if (N <= 0) return 0;
+    SMIN_ATTN_DISPATCH(fwd_t, st, chat, cells, row_ptr, N, B, L, C, Mq, uq, what, shat, qmask, cc_rows, cc_mean, dl, Nq, rows_bf16, probs);
 }
 
 // slabs: one per (range, sample) segment, indexed range + sample
@@ -1091,6 +1181,45 @@ extern "C" int smin_content_attn_fwd_cch(void* stream, const float* chat, const 
     if (N == 0) return 0;
     SMIN_REQUIRE(cc_h && ccmean);
     return launch_content_attn_fwd_h((hipStream_t)stream, chat, cells, row_ptr, N, B, L, C, Mq, uq, what, shat, qmask, cc_h, ccmean, dl, Nq);
+}
+
+extern "C" int smin_content_attn_fwd_probs(void* stream, const float* chat, const int32_t* cells, const int32_t* row_ptr,
+                                           int N, int B, int L, int C, int dl, int Nq,
+                                           const float* Mq, const float* uq, const float* what, const float* shat, const float* qmask,
+                                           void* cc, int cc_bf16, float* ccmean, float* probs)
+{
+    SMIN_REQUIRE(dl % 16 == 0 && dl >= 16 && dl <= 128 && C >= 2 && C <= 4 && Nq >= 1 && Nq <= 32);
+    if (N == 0) return 0;
+    SMIN_REQUIRE(probs && (cc || ccmean));
+    SMIN_REQUIRE(!cc_bf16 || (cc && ccmean));                      // bf16 rows: beside the clip mean, as smin_content_attn_fwd_cch
+    ProfScope prof((hipStream_t)stream, SMIN_PROF_ATTN_FWD);
+    return launch_content_attn_fwd_probs((hipStream_t)stream, chat, cells, row_ptr, N, B, L, C, Mq, uq, what, shat, qmask, static_cast<float*>(cc),
+                                         cc_bf16 != 0, ccmean, probs, dl, Nq);
+}
+
+extern "C" int smin_content_attn_maps_dense(void* stream, const float* probs, const int32_t* cellmap, const int32_t* cells,
+                                            int B, int L, int C, int dl, int Nq, const float* uq, const float* qmask, float* out)
+{
+    SMIN_REQUIRE(B >= 0 && L >= 1 && C >= 1 && C <= 4 && dl >= 1 && Nq >= 1 && Nq <= 32 && out && uq && qmask && cellmap);
+    if (B == 0) return 0;
+    hipLaunchKernelGGL(content_attn_maps_dense_kernel, dim3(L, B), dim3(256), 0, (hipStream_t)stream, probs, cellmap, cells, uq, qmask, L, C, Nq,
+                       1.0f / sqrtf((float)dl), out);
+    SMIN_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int smin_attn_maps_gather(void* stream, const float* const* probs, const float* const* bmaps, int nl, const int32_t* cellmap,
+                                     const int64_t* idx, int B, int L, int C, int Nq, int k, float* content, float* boundary)
+{
+    SMIN_REQUIRE(nl >= 1 && nl <= SMIN_ATTN_MAPS_MAX_LAYERS && B >= 0 && L >= 1 && C >= 1 && C <= 4 && Nq >= 1 && Nq <= 32 && k >= 0);
+    if (B == 0 || k == 0) return 0;
+    SMIN_REQUIRE(probs && bmaps && cellmap && idx && content && boundary);
+    MapPtrs p{}, q{};
+    for (int l = 0; l < nl; ++l) { SMIN_REQUIRE(probs[l] && bmaps[l]); p.p[l] = probs[l]; q.p[l] = bmaps[l]; }
+    hipLaunchKernelGGL(attn_maps_gather_kernel, dim3(k, B), dim3(256), 0, (hipStream_t)stream, p, q, cellmap, reinterpret_cast<const long long*>(idx),
+                       L, C, Nq, k, nl, content, boundary);
+    SMIN_LAUNCH_CHECK();
+    return 0;
 }
 
 #ifdef SMIN_ATTN_STAMPS

@@ -333,7 +333,10 @@ Tensor sum_list(const std::vector<Tensor>& ts)
 }
 
 struct SminCore : torch::autograd::Function<SminCore> {
-    enum { F_OVERLAP_BOUNDARY = 1, F_OVERLAP_PREP = 2, F_ASYNC_WEIGHTS = 4, F_BF16_OPERANDS = 8, F_GRAD_SYNC = 16, F_NO_TAIL_SPLIT = 32 };
+    // F_KEEP_ATTENTION: every layer's word-attention maps leave as extra outputs (not differentiable; the backward ignores them):
+    // the content maps dense (B, L, L, C, Nq), or with F_ATTN_PACKED as packed rows [N*C][Nq] followed by the cellmap; the boundary maps (B, L, Nq)
+    enum { F_OVERLAP_BOUNDARY = 1, F_OVERLAP_PREP = 2, F_ASYNC_WEIGHTS = 4, F_BF16_OPERANDS = 8, F_GRAD_SYNC = 16, F_NO_TAIL_SPLIT = 32, F_KEEP_ATTENTION = 64,
+           F_ATTN_PACKED = 128 };
     enum { N_FIXED = 13 };          // forward arguments ahead of the parameter list (tensors and scalars alike take one gradient slot)
 
     static variable_list forward(AutogradContext* ctx, Tensor video_features, Tensor video_mask, Tensor query_features, Tensor query_mask, Tensor length_mask,
@@ -558,6 +561,8 @@ struct SminCore : torch::autograd::Function<SminCore> {
         // round their operands to bf16 anyway (smin_set_gemm_mode(2)): no bit of the step changes, half the bytes
         const bool bf16_operands = (flags & F_BF16_OPERANDS) && smin_get_gemm_mode() == 2;
         const bool cc_bf16 = bf16_operands && dl % 8 == 0;
+        const bool keep_maps = (flags & F_KEEP_ATTENTION) != 0;
+        std::vector<Tensor> cmaps, bmaps;                                          // the attention maps (F_KEEP_ATTENTION)
         for (int64_t k = 0; k < nl; ++k) {
             LayerState& ls = st.layer[k];
             const bool lastl = k == nl - 1;
@@ -573,6 +578,7 @@ struct SminCore : torch::autograd::Function<SminCore> {
                 if (!lastl) Hs = Hs.defined() ? Hs + ls.hbar : ls.hbar;
             }
             // boundary unit on the second stream beside the content stream; joins before the moment unit
+            Tensor bmap = keep_maps ? at::empty({B, L, Nq}, opt) : Tensor();       // (allocated on the main stream, written on the boundary stream)
             wait_stream(side, curs);
             {
                 StreamScope sc(side);
@@ -581,7 +587,11 @@ struct SminCore : torch::autograd::Function<SminCore> {
                 SMIN_CK(smin_boundary_unit_fwd(cur(), fp(fb), fp(fw), fp(fs), fp(ls.hbar), ip(cells), ip(row_ptr), n, B, Li, Nq, D, fp(lp(k, L_BQ_W)), fp(lp(k, L_BQ_B)),
                                                fp(lp(k, L_BK_W)), fp(lp(k, L_BK_B)), fp(qmf), fp(lmf), fpm(ls.bu), fpm(ls.Qb), fpm(ls.Kb), fpm(ls.P), fpm(ls.baq),
                                                fpm(ls.bqv), fpm(ls.A)));
+                if (keep_maps)                                                     // Attention.attn_weights (models.py:153) is P as written
+                    TORCH_CHECK(hipMemcpyAsync(bmap.data_ptr(), ls.P.const_data_ptr(), sizeof(float) * ls.P.numel(), hipMemcpyDeviceToDevice, side.stream()) == hipSuccess,
+                                "hipMemcpyAsync failed");
             }
+            if (keep_maps) bmaps.push_back(bmap);
             // chat_k = clip-window term + [cc_0 | ..] Pcat^T + const_k + (Hs Wch^T per cell)
             Tensor chat = pgs[k];
             const Tensor& Hs_k = ls.Hs;
@@ -608,7 +618,18 @@ struct SminCore : torch::autograd::Function<SminCore> {
             ls.chat = chat;
             if (k == 0 && prep != curs) await(curs, words_ready);
             ls.cc = at::empty({lastl ? 0 : N * C, dl}, cc_bf16 ? opt.dtype(at::kBFloat16) : opt); ls.ccmean = at::empty({N, dl}, opt);
-            if (cc_bf16 && !lastl)
+            if (keep_maps) {                                                       // the same launch with the word probabilities stored
+                Tensor probs = at::empty({N * C, (int64_t)Nq}, opt);
+                SMIN_CK(smin_content_attn_fwd_probs(cur(), fp(chat), ip(cells), ip(row_ptr), n, B, Li, Ci, dl, Nq, fp(st.Mq[k]), fp(st.uq[k]), fp(st.what[k]),
+                                                    fp(st.shat[k]), fp(qmf), lastl ? nullptr : ls.cc.data_ptr(), cc_bf16 && !lastl ? 1 : 0, fpm(ls.ccmean), fpm(probs)));
+                if (flags & F_ATTN_PACKED) {
+                    cmaps.push_back(probs);
+                } else {                                                           // ContentAttention.attn_weights in the reference's layout
+                    Tensor dense = at::empty({Bq, L, L, C, (int64_t)Nq}, opt);
+                    SMIN_CK(smin_content_attn_maps_dense(cur(), fp(probs), ip(cellmap), ip(cells), B, Li, Ci, dl, Nq, fp(st.uq[k]), fp(qmf), fpm(dense)));
+                    cmaps.push_back(dense);
+                }
+            } else if (cc_bf16 && !lastl)
                 SMIN_CK(smin_content_attn_fwd_cch(cur(), fp(chat), ip(cells), ip(row_ptr), n, B, Li, Ci, dl, Nq, fp(st.Mq[k]), fp(st.uq[k]), fp(st.what[k]), fp(st.shat[k]),
                                                   fp(qmf), reinterpret_cast<uint16_t*>(ls.cc.data_ptr()), fpm(ls.ccmean)));
             else
@@ -646,7 +667,13 @@ struct SminCore : torch::autograd::Function<SminCore> {
         ctx->saved_data["d"] = std::vector<int64_t>{N, T, L, C, nl, flags, H, Nq_in, prep_kernel ? 1 : 0};
         // ps / pe / pa leave as three outputs of the node (rows of one buffer), not as selections of one output: the selections'
         // backward nodes cost three zero fills, three copies and two adds between the loss and this node's backward
-        return {pm, psea[0], psea[1], psea[2]};
+        if (!keep_maps) return {pm, psea[0], psea[1], psea[2]};
+        if (flags & F_ATTN_PACKED) cmaps.push_back(cellmap.clone());
+        variable_list out{pm, psea[0], psea[1], psea[2]};
+        for (auto& t : cmaps) out.push_back(t);
+        for (auto& t : bmaps) out.push_back(t);
+        ctx->mark_non_differentiable(variable_list(out.begin() + 4, out.end()));
+        return out;
     }
 
     static variable_list backward(AutogradContext* ctx, variable_list g)
@@ -1162,8 +1189,8 @@ struct SminCore : torch::autograd::Function<SminCore> {
 
 // ---------------------------------------------------------------- the model
 
-std::tuple<Tensor, Tensor, Tensor, Tensor> smin_forward(const Tensor& video_features, const Tensor& video_mask, const Tensor& query_features, const Tensor& query_mask_in,
-                                                        const Tensor& length_mask, const Tensor& moment_mask, at::TensorList prm, at::IntArrayRef cfg)
+variable_list smin_forward_impl(const Tensor& video_features, const Tensor& video_mask, const Tensor& query_features, const Tensor& query_mask_in,
+                                const Tensor& length_mask, const Tensor& moment_mask, at::TensorList prm, at::IntArrayRef cfg, int64_t extra_flags)
 {
     TORCH_CHECK(video_features.is_cuda(), "smin_forward runs on a HIP device only (there is no CPU fallback)");
     TORCH_CHECK(cfg.size() == 16, "smin_forward: cfg = [T, L, C, D, dl, layers, max_query_length, H, overlap_boundary, overlap_prep, fused_core, async_weights, "
@@ -1184,9 +1211,33 @@ std::tuple<Tensor, Tensor, Tensor, Tensor> smin_forward(const Tensor& video_feat
     c10::hip::HIPGuard device_guard(video_features.device().index());
     const int64_t flags = (cfg[8] != 0 ? SminCore::F_OVERLAP_BOUNDARY : 0) | (cfg[9] != 0 ? SminCore::F_OVERLAP_PREP : 0) | (cfg[11] != 0 ? SminCore::F_ASYNC_WEIGHTS : 0) |
                           (cfg[12] != 0 ? SminCore::F_BF16_OPERANDS : 0) | (cfg[13] != 0 ? SminCore::F_GRAD_SYNC : 0) | (cfg[15] == 0 ? SminCore::F_NO_TAIL_SPLIT : 0) |
-                          (cfg[14] >= 0 ? ((cfg[14] + 1) << 16) : 0);      // cfg[14]: the number of valid cells, when the caller knows it
-    auto out = SminCore::apply(video_features, video_mask, query_features, query_mask, length_mask, moment_mask, T, L, C, nl, maxq, H, flags, prm);
+                          (cfg[14] >= 0 ? ((cfg[14] + 1) << 16) : 0) | extra_flags;      // cfg[14]: the number of valid cells, when the caller knows it
+    return SminCore::apply(video_features, video_mask, query_features, query_mask, length_mask, moment_mask, T, L, C, nl, maxq, H, flags, prm);
+}
+
+std::tuple<Tensor, Tensor, Tensor, Tensor> smin_forward(const Tensor& video_features, const Tensor& video_mask, const Tensor& query_features, const Tensor& query_mask,
+                                                        const Tensor& length_mask, const Tensor& moment_mask, at::TensorList prm, at::IntArrayRef cfg)
+{
+    auto out = smin_forward_impl(video_features, video_mask, query_features, query_mask, length_mask, moment_mask, prm, cfg, 0);
     return std::make_tuple(out[0], out[1], out[2], out[3]);
+}
+
+// smin_forward that also returns every layer's word-attention maps (detached): content[k] = ContentAttention.attn_weights (B, L, L, C, Nq)
+// (models.py:207-226), boundary[k] = Attention.attn_weights (B, L, Nq) (models.py:137-154).  cfg: smin_forward's 16 entries, optionally a 17th:
+// 1 = the content maps packed, content = [probs_0 [N*C, Nq], .., probs_{layers-1}, cellmap (B, L, L) int32] (what SMIN.localize gathers from)
+std::tuple<Tensor, Tensor, Tensor, Tensor, std::vector<Tensor>, std::vector<Tensor>> smin_forward_with_attention(
+    const Tensor& video_features, const Tensor& video_mask, const Tensor& query_features, const Tensor& query_mask, const Tensor& length_mask,
+    const Tensor& moment_mask, at::TensorList prm, at::IntArrayRef cfg)
+{
+    TORCH_CHECK(cfg.size() == 16 || cfg.size() == 17, "smin_forward_with_attention: cfg = smin_forward's 16 entries [+ packed content maps 0 / 1], got ",
+                cfg.size(), " entries");
+    const bool packed = cfg.size() == 17 && cfg[16] != 0;
+    auto out = smin_forward_impl(video_features, video_mask, query_features, query_mask, length_mask, moment_mask, prm, cfg.slice(0, 16),
+                                 SminCore::F_KEEP_ATTENTION | (packed ? SminCore::F_ATTN_PACKED : 0));
+    const int64_t nl = cfg[5], nc = nl + (packed ? 1 : 0);
+    TORCH_CHECK((int64_t)out.size() == 4 + nc + nl, "smin_forward_with_attention: ", out.size(), " outputs");
+    std::vector<Tensor> content(out.begin() + 4, out.begin() + 4 + nc), boundary(out.begin() + 4 + nc, out.end());
+    return std::make_tuple(out[0], out[1], out[2], out[3], content, boundary);
 }
 
 Tensor smin_loss(const Tensor& pm, const Tensor& ym, const Tensor& sm, const Tensor& moment_mask, const Tensor& ps, const Tensor& ys, const Tensor& ss, const Tensor& pe,
@@ -1206,6 +1257,9 @@ TORCH_LIBRARY(smin_hip, m)
     //        async_weights, bf16_operand_storage, grad_sync, known_cell_count or -1, tail_split]  
     m.def("smin_forward(Tensor video_features, Tensor video_mask, Tensor query_features, Tensor query_mask, Tensor length_mask, Tensor moment_mask, "
           "Tensor[] params, int[] cfg) -> (Tensor, Tensor, Tensor, Tensor)", &smin_forward);
+    // the same node with every layer's word-attention maps as extra, non-differentiable outputs
+    m.def("smin_forward_with_attention(Tensor video_features, Tensor video_mask, Tensor query_features, Tensor query_mask, Tensor length_mask, "
+          "Tensor moment_mask, Tensor[] params, int[] cfg) -> (Tensor, Tensor, Tensor, Tensor, Tensor[], Tensor[])", &smin_forward_with_attention);
     // restated loss_fn of the reference's train loop (main.py:110-116), same argument order
     m.def("smin_loss(Tensor pm, Tensor ym, Tensor sm, Tensor moment_mask, Tensor ps, Tensor ys, Tensor ss, Tensor pe, Tensor ye, Tensor se, Tensor pa, Tensor ya, "
           "Tensor length_mask) -> Tensor", &smin_loss);

@@ -142,25 +142,35 @@ class ClipWindowMeansFn(Function):
 
 class ContentAttnFn(Function):
     """The content unit's attention core alone (reference models.py:252-267): chat [N*C, dl] -> (cc [N*C, dl],
-    ccmean [N, dl] = mean_c cc).  want_rows=False (last layer) returns an empty cc."""
+    ccmean [N, dl] = mean_c cc).  want_rows=False (last layer) returns an empty cc.  keep_probs=True also returns the word
+    probabilities of every row, probs [N*C, Nq] (ContentAttention.attn_weights, models.py:224-225; not differentiable): the same
+    launch with a store added, cc / ccmean bit-identical."""
 
     @staticmethod
-    def forward(ctx, chat, Mq, uq, what, shat, qmask, layout, C, want_rows):
+    def forward(ctx, chat, Mq, uq, what, shat, qmask, layout, C, want_rows, keep_probs=False):
         chat, Mq, uq, what, shat, qmask = map(_c, (chat, Mq, uq, what, shat, qmask))
         B, Nq, dl = what.shape
         N = layout.N
         cc = chat.new_empty((N * C, dl) if want_rows else (0, dl))
         ccmean = chat.new_empty((N, dl))
-        call("smin_content_attn_fwd", stream(), ptr(chat), ptr(layout.cells), ptr(layout.row_ptr), N, B, layout.L, C, dl, Nq,
-             ptr(Mq), ptr(uq), ptr(what), ptr(shat), ptr(qmask), ptr(cc) if want_rows else None, ptr(ccmean))
+        if keep_probs:
+            probs = chat.new_empty((N * C, Nq))
+            call("smin_content_attn_fwd_probs", stream(), ptr(chat), ptr(layout.cells), ptr(layout.row_ptr), N, B, layout.L, C, dl, Nq,
+                 ptr(Mq), ptr(uq), ptr(what), ptr(shat), ptr(qmask), ptr(cc) if want_rows else None, 0, ptr(ccmean), ptr(probs))
+        else:
+            call("smin_content_attn_fwd", stream(), ptr(chat), ptr(layout.cells), ptr(layout.row_ptr), N, B, layout.L, C, dl, Nq,
+                 ptr(Mq), ptr(uq), ptr(what), ptr(shat), ptr(qmask), ptr(cc) if want_rows else None, ptr(ccmean))
         ctx.save_for_backward(chat, Mq, uq, what, shat, qmask)
         ctx.layout, ctx.C, ctx.want_rows = layout, C, want_rows
         if not want_rows:
             ctx.mark_non_differentiable(cc)
+        if keep_probs:
+            ctx.mark_non_differentiable(probs)
+            return cc, ccmean, probs
         return cc, ccmean
 
     @staticmethod
-    def backward(ctx, dcc, dccmean):
+    def backward(ctx, dcc, dccmean, dprobs=None):
         chat, Mq, uq, what, shat, qmask = ctx.saved_tensors
         layout, C = ctx.layout, ctx.C
         B, Nq, dl = what.shape
@@ -179,7 +189,37 @@ class ContentAttnFn(Function):
             call("smin_content_attn_bwd", stream(), ptr(dcc), ptr(dccmean), ptr(chat), ptr(layout.cells), ptr(layout.row_ptr),
                  N, B, layout.L, C, dl, Nq, ptr(Mq), ptr(uq), ptr(what), ptr(shat), ptr(qmask),
                  ptr(dchat), ptr(dMq), ptr(duq), ptr(dwhat), ptr(dshat), wp, wn)
-        return dchat, dMq, duq, dwhat, dshat, None, None, None, None
+        return dchat, dMq, duq, dwhat, dshat, None, None, None, None, None
+
+
+def content_attn_maps_dense(probs, layout, uq, qmask, C, dl):
+    """ContentAttention.attn_weights in the reference's layout (B, L, L, C, Nq) from ContentAttnFn's packed probs [N*C, Nq]:
+    listed cells copy their rows, every other cell gets the reference's value there, softmax(mask(uq[b] / sqrt(dl)))
+    (its c_hat is 0, so its query is W_q.bias; csrc/content_attn.hip content_attn_maps_dense_kernel).  B*L*L*C*Nq*4 bytes."""
+    uq, qmask = _c(uq), _c(qmask)
+    B, Nq = uq.shape
+    L = layout.L
+    out = uq.new_empty((B, L, L, C, Nq))
+    call("smin_content_attn_maps_dense", stream(), ptr(_c(probs)), ptr(layout.cellmap), ptr(layout.cells), B, L, C, dl, Nq, ptr(uq), ptr(qmask),
+         ptr(out))
+    return out
+
+
+def attn_maps_gather(probs, bmaps, cellmap, idx, C):
+    """The maps of the moments top_moments kept (idx (B, k, 2) int64, -1 = empty slot), from the packed forms without a dense map:
+    probs / bmaps lists of every layer's content rows [N*C, Nq] / boundary maps (B, L, Nq).  Returns (content (B, k, layers, C, Nq),
+    boundary (B, k, layers, 2, Nq): the start and end rows); empty slots are 0."""
+    nl = len(probs)
+    B, L, Nq = bmaps[0].shape
+    k = idx.shape[1]
+    probs, bmaps = [_c(p) for p in probs], [_c(m) for m in bmaps]
+    for t in probs + bmaps:
+        ptr(t)                                                      # device / contiguity checks
+    content = bmaps[0].new_empty((B, k, nl, C, Nq))
+    boundary = bmaps[0].new_empty((B, k, nl, 2, Nq))
+    call("smin_attn_maps_gather", stream(), _ptr_array(probs), _ptr_array(bmaps), nl, ptr(_c(cellmap)), ptr(_c(idx)), B, L, C, Nq, k,
+         ptr(content), ptr(boundary))
+    return content, boundary
 
 
 def _ptr_array(tensors):
@@ -434,7 +474,8 @@ class BoundaryUnitFn(Function):
     """BoundaryUnit.forward with its word attention (reference models.py:137-196), all in HIP."""
 
     @staticmethod
-    def forward(ctx, fb, fw, fs, hbar, Wq, bq, Wk, bk, qmask, lmask, layout):
+    def forward(ctx, fb, fw, fs, hbar, Wq, bq, Wk, bk, qmask, lmask, layout, keep_p=False):
+        """keep_p=True also returns a copy of P (B, L, Nq), Attention.attn_weights (models.py:153), not differentiable."""
         fb, fw, fs, hbar, Wq, bq, Wk, bk, qmask, lmask = map(_c, (fb, fw, fs, hbar, Wq, bq, Wk, bk, qmask, lmask))
         B, L, D = fb.shape
         Nq = fw.shape[1]
@@ -448,10 +489,14 @@ class BoundaryUnitFn(Function):
              ptr(out), ptr(Qb), ptr(Kb), ptr(P), ptr(baq), ptr(bqv), ptr(A))
         ctx.save_for_backward(fb, fw, fs, hbar, Wq, Wk, qmask, lmask, Qb, Kb, P, baq, bqv, A)
         ctx.layout = layout
+        if keep_p:
+            Pk = P.clone()
+            ctx.mark_non_differentiable(Pk)
+            return out, Pk
         return out
 
     @staticmethod
-    def backward(ctx, dout):
+    def backward(ctx, dout, dP=None):
         fb, fw, fs, hbar, Wq, Wk, qmask, lmask, Qb, Kb, P, baq, bqv, A = ctx.saved_tensors
         layout = ctx.layout
         B, L, D = fb.shape
@@ -465,7 +510,7 @@ class BoundaryUnitFn(Function):
         call("smin_boundary_unit_bwd", stream(), ptr(dout), ptr(fb), ptr(fw), ptr(fs), ptr(hbar), ptr(layout.cells), ptr(layout.row_ptr),
              layout.N, B, L, Nq, D, ptr(WqT), ptr(WkT), ptr(qmask), ptr(lmask), ptr(Qb), ptr(Kb), ptr(P), ptr(baq), ptr(bqv), ptr(A),
              ptr(dfb), ptr(dfw), ptr(dfs), ptr(dhbar), ptr(dWq), ptr(dbq), ptr(dWk), ptr(dbk), wp, wn)
-        return dfb, dfw, dfs, dhbar, dWq, dbq, dWk, dbk, None, None, None
+        return dfb, dfw, dfs, dhbar, dWq, dbq, dWk, dbk, None, None, None, None
 
 
 class MomentUnitFn(Function):

@@ -24,7 +24,7 @@ from ._lib import SminHipError
 
 from .cells import CellLayout
 from .functional import (VideoFuseFn, WordPrepFn, BiLstmLayerFn, BoundaryUnitFn, ClipWindowMeansFn, ContentAttnFn, ContentUnitFn, GateFn, LinearRowsFn, MomentUnitFn,
-                         ProposalMapFn, ProposalMeansFn, ScoreMapFn)
+                         ProposalMapFn, ProposalMeansFn, ScoreMapFn, attn_maps_gather, content_attn_maps_dense)
 
 
 def _hip_forward(fn):
@@ -214,6 +214,15 @@ class ProposalGeneration(nn.Module):
         return layout.unpack(fc), layout.unpack(fm), fb
 
 
+class _AttnMaps(list):
+    """Per-layer (content map, boundary map) pairs a forward fills; mode "dense": content maps (B, L, L, C, Nq), "packed": rows
+    [N*C, Nq] of the cell list, whose cellmap (B, L, L) is kept beside them."""
+
+    def __init__(self, mode):
+        super().__init__()
+        self.mode, self.cellmap = mode, None
+
+
 def _word_attention(W_q, W_k, query, key, value, mask, scale_dim):
     q, k = W_q(query), W_k(key)
     s = torch.matmul(q, k.transpose(-1, -2)) / math.sqrt(scale_dim)
@@ -226,7 +235,10 @@ def _word_attention(W_q, W_k, query, key, value, mask, scale_dim):
 
 
 class Attention(nn.Module):
-    """reference models.py:128-154 (boundary <-> word attention; O(B L Nq D), library GEMMs)."""
+    """reference models.py:128-154 (boundary <-> word attention; O(B L Nq D), library GEMMs).  ``attn_weights`` (B, Lq, Nq) is
+    recorded (detached) when ``keep_weights`` is set -- by this forward, or by SMIN.forward under SMIN.keep_attention."""
+
+    keep_weights = False
 
     def __init__(self, D):
         super().__init__()
@@ -236,7 +248,9 @@ class Attention(nn.Module):
 
     @_hip_forward
     def forward(self, query, key, value, mask=None):
-        out, _ = _word_attention(self.W_q, self.W_k, query, key, value, mask, self.D)
+        out, p = _word_attention(self.W_q, self.W_k, query, key, value, mask, self.D)
+        if self.keep_weights:
+            self.attn_weights = p.detach()
         return out
 
 
@@ -248,10 +262,11 @@ class BoundaryUnit(nn.Module):
         self.D = D
         self.attn_layer = Attention(D)
 
-    def forward_packed(self, f_b, f_w, f_s, hbar, query_mask, length_mask, layout):
+    def forward_packed(self, f_b, f_w, f_s, hbar, query_mask, length_mask, layout, keep_map=False):
+        """keep_map=True: returns (out, the word-attention map P (B, L, Nq), detached)."""
         at = self.attn_layer
         return BoundaryUnitFn.apply(f_b, f_w, f_s, hbar, at.W_q.weight, at.W_q.bias, at.W_k.weight, at.W_k.bias,
-                                    _rows(query_mask), length_mask.float(), layout)
+                                    _rows(query_mask), length_mask.float(), layout, keep_map)
 
     @_hip_forward
     def forward(self, f_b, f_w, f_s, f_m, query_mask, length_mask):
@@ -263,7 +278,10 @@ class BoundaryUnit(nn.Module):
 
 class ContentAttention(nn.Module):
     """reference models.py:198-226.  Inside ContentUnit this attention is fused into the HIP content
-    kernels (W_q/W_k folded per sample); this stand-alone forward serves the 5-D module seam only."""
+    kernels (W_q/W_k folded per sample); this stand-alone forward serves the 5-D module seam only.  ``attn_weights``
+    (B, L, L, C, Nq) is recorded (detached) when ``keep_weights`` is set, as Attention's."""
+
+    keep_weights = False
 
     def __init__(self, D):
         super().__init__()
@@ -275,7 +293,9 @@ class ContentAttention(nn.Module):
     def forward(self, query, key, value, mask=None):
         B = query.shape[0]
         q = query.reshape(B, -1, query.shape[-1])
-        out, _ = _word_attention(self.W_q, self.W_k, q, key, value, mask, self.D)
+        out, p = _word_attention(self.W_q, self.W_k, q, key, value, mask, self.D)
+        if self.keep_weights:
+            self.attn_weights = p.detach().reshape(query.shape[:-1] + (p.shape[-1],))
         return out.reshape(query.shape[:-1] + (value.shape[-1],))
 
 
@@ -436,8 +456,12 @@ class SMIN(nn.Module):
     content_stream = True          # dl < D: keep the content stream in the dl-dimensional space (see _forward_stream)
     overlap_boundary = True        # boundary unit on a second HIP stream beside the content stream
     overlap_prep = True            # parameter-only work (word-side operands, weight products) on that stream as well
+    keep_attention = False         # a forward also records every layer's word-attention maps, as the reference's modules do:
+                                   # smis[k].content_unit.attn_layer.attn_weights (B, L, L, C, Nq) and
+                                   # smis[k].boundary_unit.attn_layer.attn_weights (B, L, Nq), detached (INTEGRATION.md 3d;
+                                   # B*L*L*C*Nq*4 bytes per layer for the content maps)
 
-    def _forward_stream(self, f, fs, fw, query_mask, length_mask, layout):
+    def _forward_stream(self, f, fs, fw, query_mask, length_mask, layout, maps=None):
         """The same network with the content unit's two linear maps re-associated (exact in real arithmetic).
 
         The unit output  f_c' = cc Wc^T + bc + f_c + hbar  (models.py:269-276) is consumed only by the next unit's
@@ -447,7 +471,10 @@ class SMIN(nn.Module):
             mean_c f_c^k = mean_c f_c^{k-1} + (mean_c cc_k) Wc_k^T + bc_k + hbar_k
         and the (N*C) x D tensors f_c never exist: every contraction over N*C rows is dl x dl instead of D x dl.
         The parameter products (Wch_k Wc_l, Wch_k bc_l, g_k) are tiny and stay in torch, which also routes their
-        gradients back to the reference's parameters."""
+        gradients back to the reference's parameters.
+
+        maps: None, or a list that receives per layer (content map, boundary map): "dense" (B, L, L, C, Nq) / "packed" [N*C, Nq]
+        content maps as the list's ``mode`` attribute says (_AttnMaps)."""
         T, L, C, dl = self.T, self.L, self.C, self.dl
         N = layout.N
         nl = len(self.smis)
@@ -505,7 +532,9 @@ class SMIN(nn.Module):
             # LDS free) and joins before the moment unit; autograd replays its backward on the same stream.
             side.wait_stream(cur)
             with torch.cuda.stream(side):
-                bu = smi.boundary_unit.forward_packed(fb, fw, fs, hbar_b, query_mask, length_mask, layout)
+                bu = smi.boundary_unit.forward_packed(fb, fw, fs, hbar_b, query_mask, length_mask, layout, maps is not None)
+                if maps is not None:
+                    bu, bmap = bu
             if side is not cur:
                 fb.record_stream(side)
                 hbar_b.record_stream(side)
@@ -516,7 +545,13 @@ class SMIN(nn.Module):
                 hp = LinearRowsFn.apply(Wch, None, None, None, 1, H) if lo == 0 else None   # (sum_l hbar_l) Wch^T, per cell
                 chat = LinearRowsFn.apply(Pcats[k][n_part], consts[k] if lo == 0 else None, chat, hp, C, *[cc_l for cc_l, _, _ in part])
             Mq, uq, what, shat, qm = words[k]
-            cc, ccmean = ContentAttnFn.apply(chat, Mq, uq, what, shat, qm, layout, C, not last)
+            if maps is None:
+                cc, ccmean = ContentAttnFn.apply(chat, Mq, uq, what, shat, qm, layout, C, not last)
+            else:
+                cc, ccmean, probs = ContentAttnFn.apply(chat, Mq, uq, what, shat, qm, layout, C, not last, True)
+                if maps.mode == "dense":                                     # behind the layer's attention, on the main stream
+                    probs = content_attn_maps_dense(probs, layout, uq, qm, C, self.dl)
+                maps.append((probs, bmap))
             cumean = LinearRowsFn.apply(cu.linear_c.weight, cu.linear_c.bias, cumean, hbar_c, 1, ccmean)
             if not last:
                 if H is None:
@@ -529,6 +564,8 @@ class SMIN(nn.Module):
             cur.wait_stream(side)
             if side is not cur:
                 bu.record_stream(cur)
+                if maps is not None:
+                    bmap.record_stream(cur)
             fm, cumean = MomentUnitFn.apply(cumean, fm_res, bu, mu_w[k][0], mu_w[k][1], layout)
             fb = bu
         return self.localization.forward_packed(fm, fb, length_mask, layout)
@@ -579,17 +616,50 @@ class SMIN(nn.Module):
                 and video_features.shape[1] == self.T and video_features.shape[1] <= ve.pe.weight.shape[0])
 
     def localize(self, video_features, video_mask, query_features, query_mask, length_mask, moment_mask, k=5, nms_thresh=0.5,
-                 duration=None):
+                 duration=None, attention=False):
         """The k best moments per sample: the forward under torch.no_grad(), then moments.top_moments of its (pm, ps, pe) -- greedy
         temporal NMS at ``nms_thresh`` over the valid cells of ``moment_mask``.  Returns top_moments' dict (``idx`` (B, k, 2) start
-        / end clip, ``score``, ``count``; with ``duration`` (B,) seconds also ``times`` (B, k, 2) in seconds)."""
+        / end clip, ``score``, ``count``; with ``duration`` (B,) seconds also ``times`` (B, k, 2) in seconds).
+
+        attention=True: also ``content_attention`` (B, k, layers, C, Nq), the content unit's word weights of each clip of each kept
+        moment, and ``boundary_attention`` (B, k, layers, 2, Nq), the boundary unit's word weights of its start and end rows (empty
+        slots 0): gathered on the device from the packed maps, no dense map is formed."""
         from .moments import top_moments
         with torch.no_grad():
-            pm, ps, pe, _ = self(video_features, video_mask, query_features, query_mask, length_mask, moment_mask)
-        return top_moments(pm, ps, pe, moment_mask, k=k, nms_thresh=nms_thresh, duration=duration)
+            if attention:
+                maps = _AttnMaps("packed")
+                pm, ps, pe, _ = self._forward(video_features, video_mask, query_features, query_mask, length_mask, moment_mask, maps)
+            else:
+                pm, ps, pe, _ = self(video_features, video_mask, query_features, query_mask, length_mask, moment_mask)
+            r = top_moments(pm, ps, pe, moment_mask, k=k, nms_thresh=nms_thresh, duration=duration)
+            if attention:
+                r["content_attention"], r["boundary_attention"] = attn_maps_gather([c for c, _ in maps], [b for _, b in maps], maps.cellmap,
+                                                                                   r["idx"], self.C)
+        return r
+
+    def _stream_ok(self):
+        """The Python host's content stream (_forward_stream) applies (else: the units as written, ContentUnitFn)."""
+        return self.content_stream and self.dl < self.D and 2 <= self.C <= 4 and len(self.smis) <= 8 and len(self.smis) * self.dl <= 2048
+
+    def _record_attention(self, maps):
+        for smi, (cmap, bmap) in zip(self.smis, maps):
+            smi.content_unit.attn_layer.attn_weights = cmap
+            smi.boundary_unit.attn_layer.attn_weights = bmap
 
     @_hip_forward
     def forward(self, video_features, video_mask, query_features, query_mask, length_mask, moment_mask):
+        maps = None
+        if self.keep_attention:
+            for smi in self.smis:                                 # the stand-alone seams record theirs too
+                smi.content_unit.attn_layer.keep_weights = smi.boundary_unit.attn_layer.keep_weights = True
+            maps = _AttnMaps("dense")
+        out = self._forward(video_features, video_mask, query_features, query_mask, length_mask, moment_mask, maps)
+        if maps is not None:
+            self._record_attention(maps)
+        return out
+
+    @_hip_forward
+    def _forward(self, video_features, video_mask, query_features, query_mask, length_mask, moment_mask, maps):
         # the reference's dataset pads queries and their mask to max_query_length (dataset.py:35, 173); a batch cut to its longest query is taken
         # too: the encoder pads f_w as models.py:58-59 does, and the mask is padded here (every kernel reads max_query_length mask columns)
         query_mask = query_mask.reshape(query_features.shape[0], -1)
@@ -609,14 +679,30 @@ class SMIN(nn.Module):
                    int(self.overlap_boundary), int(self.overlap_prep and (self._streams_allowed("torch") or self._prep_is_library_code())), int(self.fused_core),
                    int(self.async_weights), int(self.bf16_operand_storage), int(self.grad_sync and torch.is_grad_enabled()),
                    -1 if self.known_cell_count is None else int(self.known_cell_count), int(self.tail_split)]
-            return _lib.load_torch().smin_forward(video_features, video_mask, query_features, query_mask, length_mask, moment_mask,
-                                                  self._native_params(), cfg)
+            if maps is None:
+                return _lib.load_torch().smin_forward(video_features, video_mask, query_features, query_mask, length_mask, moment_mask,
+                                                      self._native_params(), cfg)
+            packed = maps.mode == "packed"
+            pm, ps, pe, pa, content, boundary = _lib.load_torch().smin_forward_with_attention(
+                video_features, video_mask, query_features, query_mask, length_mask, moment_mask, self._native_params(), cfg + [int(packed)])
+            if packed:
+                maps.cellmap, content = content[-1], content[:-1]
+            maps.extend(zip(content, boundary))
+            return pm, ps, pe, pa
+        if maps is not None and not self._stream_ok():
+            raise RuntimeError("SMIN.keep_attention / localize(attention=True): the word-attention maps come out of the content stream's attention "
+                               "core; this configuration runs the content units as written (ContentUnitFn, see SMIN._stream_ok), which cannot "
+                               "deliver them")
         pending = CellLayout.begin(moment_mask)                    # work is driven by moment_mask (SURVEY 8a-0 caveat)
         f, fs, fw = self.backbone(video_features, video_mask, query_features, query_mask)
         layout = pending.finish()                                  # the only host sync of a step; hidden behind the backbone
         if (self.content_stream and self.dl < self.D and 2 <= self.C <= 4 and layout.all_valid
                 and len(self.smis) <= 8 and len(self.smis) * self.dl <= 2048):    # limits of the clip-window-means launch
-            return self._forward_stream(f, fs, fw, query_mask, length_mask, layout)
+            if maps is not None:
+                maps.cellmap = layout.cellmap
+            return self._forward_stream(f, fs, fw, query_mask, length_mask, layout, maps)
+        if maps is not None:
+            raise RuntimeError("SMIN.keep_attention: this batch runs the content units as written (ContentUnitFn), which cannot deliver the maps")
         fc, fm, fb = self.pgm.forward_packed(f, layout)
         fcmean = fm                                                # mean_c fc: the map's f_m, then each layer's clip mean
         for k, smi in enumerate(self.smis):

@@ -145,6 +145,9 @@ class CapturedStep:
         return loss, out
 
     def __call__(self, batch):
+        if getattr(self.model, "keep_attention", False):
+            raise RuntimeError("CapturedStep cannot deliver the word-attention maps (SMIN.keep_attention): a replayed graph sets no module "
+                               "attribute; run the step eagerly to record them")
         dev = batch["moment_mask"].device
         _require_hip(batch["moment_mask"], "CapturedStep")
         from . import _lib
