@@ -155,7 +155,8 @@ int smin_boundary_unit_fwd(void* stream, const float* fb, const float* fw, const
                            const float* qmask, const float* lmask,
                            float* out, float* Qb, float* Kb, float* P, float* baq, float* bqv, float* A);
 /* WqT, WkT: transposed weights.  Gradients: dfb, dfw, dfs, dhbar [N][D], dWq, dbq, dWk, dbk.
- * ws_bytes >= 4 * (2*B*L*L + 3*B*L*D + B*L*Nq + B*Nq*D + 2*64*(D*D + D)). */
+ * ws_bytes >= smin_boundary_unit_bwd_ws_bytes(B, L, Nq, D).  Forward and backward take 1 <= L <= 8192. */
+size_t smin_boundary_unit_bwd_ws_bytes(int B, int L, int Nq, int D);   /* 0 = arguments rejected */
 int smin_boundary_unit_bwd(void* stream, const float* dout, const float* fb, const float* fw, const float* fs, const float* hbar,
                            const int32_t* cells, const int32_t* row_ptr, int N, int B, int L, int Nq, int D,
                            const float* WqT, const float* WkT, const float* qmask, const float* lmask,

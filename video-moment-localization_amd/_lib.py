@@ -40,6 +40,7 @@ SIGNATURES = {
     "smin_boundary_reduce_fwd": [_vp] * 5 + [_i] * 4 + [_vp],
     "smin_boundary_reduce_bwd": [_vp] * 6 + [_i] * 4 + [_vp] * 2,
     "smin_boundary_unit_fwd": [_vp] * 7 + [_i] * 5 + [_vp] * 6 + [_vp] * 7,
+    "smin_boundary_unit_bwd_ws_bytes": [_i] * 4,
     "smin_boundary_unit_bwd": [_vp] * 8 + [_i] * 5 + [_vp] * 4 + [_vp] * 6 + [_vp] * 8 + [_vp, _sz],
     "smin_moment_unit_fwd": [_vp] * 5 + [_i] * 4 + [_vp] * 3 + [_vp],
     "smin_pair_product": [_vp] * 3 + [_i] * 3 + [_vp],
@@ -102,7 +103,7 @@ SIGNATURES = {
 _RESTYPE = {"smin_target_arch": ctypes.c_char_p, "smin_workspace_bytes": _sz,
             "smin_content_attn_bwd_workspace_bytes": _sz, "smin_linear_rows_bwd_workspace_bytes": _sz,
             "smin_bilstm_layer_bwd_workspace_bytes": _sz, "smin_video_encoder_bwd_workspace_bytes": _sz, "smin_word_prep_bwd_workspace_bytes": _sz,
-            "smin_col_sum_workspace_bytes": _sz, "smin_top_moments_ws_bytes": _sz, "smin_compute_ious_nms_ws_bytes": _sz}
+            "smin_col_sum_workspace_bytes": _sz, "smin_top_moments_ws_bytes": _sz, "smin_boundary_unit_bwd_ws_bytes": _sz, "smin_compute_ious_nms_ws_bytes": _sz}
 
 _lib = None
 _ws = {}

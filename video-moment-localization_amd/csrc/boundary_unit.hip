@@ -351,10 +351,36 @@ extern "C" int smin_boundary_reduce_bwd(void* stream, const float* dfbm, const f
 
 
 // ---- whole BoundaryUnit -------------------------------------------------------------------------------------------
+// Longest map both directions take: boundary_self_bwd_cols_kernel holds 2L + 64 floats of LDS (65.8 KB at L = 8192, opted in below).
+constexpr int BU_MAX_L = 8192;
+
 static size_t bu_fwd_saved_floats(int B, int L, int Nq, int D)
 {
     return (size_t)B * L * D * 3 + (size_t)B * Nq * D + (size_t)B * L * Nq + (size_t)B * L * L;
 }
+
+// The backward's workspace, as float offsets (16-byte aligned pieces); smin_boundary_unit_bwd_ws_bytes reports `end`.
+struct BuBwdWs {
+    int sp1, sp2, slices;
+    size_t dAbm, draw, dbaq_lm, dfs_part, dQK, dQb, dKb, mid, slab1, bslab1, slab2, bslab2, end;
+    BuBwdWs(int B, int L, int Nq, int D)
+        : sp1(tn_splits(B * L, D, D)), sp2(tn_splits(B * Nq, D, D)), slices(L > 96 ? cdiv(L, 32) : 1)
+    {
+        size_t off = 0;
+        auto take = [&](size_t n) { const size_t o = off; off += (n + 3) & ~(size_t)3; return o; };
+        dAbm = take((size_t)B * L * L);
+        draw = take((size_t)B * L * L);
+        dbaq_lm = take((size_t)B * L * D);
+        dfs_part = take((size_t)B * L * D);
+        dQK = take((size_t)B * L * Nq);
+        dQb = take((size_t)B * L * D);
+        dKb = take((size_t)B * Nq * D);
+        mid = take(slices > 1 ? (size_t)B * slices * D : 0);          // first pass of the two-pass rows_reduce
+        slab1 = take((size_t)sp1 * D * D); bslab1 = take((size_t)sp1 * D);
+        slab2 = take((size_t)sp2 * D * D); bslab2 = take((size_t)sp2 * D);
+        end = off;
+    }
+};
 
 extern "C" int smin_boundary_unit_fwd(void* stream, const float* fb, const float* fw, const float* fs, const float* hbar,
                                       const int32_t* cells, const int32_t* row_ptr, int N, int B, int L, int Nq, int D,
@@ -364,7 +390,7 @@ extern "C" int smin_boundary_unit_fwd(void* stream, const float* fb, const float
 {
     (void)N;
     hipStream_t st = (hipStream_t)stream;
-    SMIN_REQUIRE(D % 4 == 0 && Nq >= 1 && Nq <= 64 && L >= 1 && L <= 8192);
+    SMIN_REQUIRE(D % 4 == 0 && Nq >= 1 && Nq <= 64 && L >= 1 && L <= BU_MAX_L);
     const float scale = 1.0f / sqrtf((float)D);
     int rc = launch_gemm_nt(st, PlainMat{fb, D}, PlainMat{Wq, D}, EpBias{bq, Qb}, B * L, D, D);
     if (rc) return rc;
@@ -380,6 +406,12 @@ extern "C" int smin_boundary_unit_fwd(void* stream, const float* fb, const float
     return 0;
 }
 
+extern "C" size_t smin_boundary_unit_bwd_ws_bytes(int B, int L, int Nq, int D)
+{
+    if (B < 1 || L < 1 || L > BU_MAX_L || Nq < 1 || Nq > 64 || D < 4 || D % 4 != 0) return 0;
+    return BuBwdWs(B, L, Nq, D).end * sizeof(float);
+}
+
 extern "C" int smin_boundary_unit_bwd(void* stream, const float* dout, const float* fb, const float* fw, const float* fs, const float* hbar,
                                       const int32_t* cells, const int32_t* row_ptr, int N, int B, int L, int Nq, int D,
                                       const float* WqT, const float* WkT, const float* qmask, const float* lmask,
@@ -389,37 +421,39 @@ extern "C" int smin_boundary_unit_bwd(void* stream, const float* dout, const flo
 {
     (void)N;
     hipStream_t st = (hipStream_t)stream;
-    SMIN_REQUIRE(D % 4 == 0 && Nq >= 1 && Nq <= 64);
+    SMIN_REQUIRE(D % 4 == 0 && Nq >= 1 && Nq <= 64 && L >= 1 && L <= BU_MAX_L);
     const float scale = 1.0f / sqrtf((float)D);
+    const BuBwdWs lay(B, L, Nq, D);
+    SMIN_REQUIRE(lay.end * sizeof(float) <= ws_bytes);
     float* w = reinterpret_cast<float*>(ws);
-    size_t off = 0;
-    auto take = [&](size_t n) { float* p = w + off; off += (n + 3) & ~(size_t)3; return p; };
-    float* dAbm = take((size_t)B * L * L);
-    float* draw = take((size_t)B * L * L);
-    float* dbaq_lm = take((size_t)B * L * D);
-    float* dfs_part = take((size_t)B * L * D);
-    float* dQK = take((size_t)B * L * Nq);
-    float* dQb = take((size_t)B * L * D);
-    float* dKb = take((size_t)B * Nq * D);
-    const int sp1 = tn_splits(B * L, D, D), sp2 = tn_splits(B * Nq, D, D);
-    float* slab1 = take((size_t)sp1 * D * D); float* bslab1 = take((size_t)sp1 * D);
-    float* slab2 = take((size_t)sp2 * D * D); float* bslab2 = take((size_t)sp2 * D);
-    SMIN_REQUIRE(off * sizeof(float) <= ws_bytes);
+    float* dAbm = w + lay.dAbm;
+    float* draw = w + lay.draw;
+    float* dbaq_lm = w + lay.dbaq_lm;
+    float* dfs_part = w + lay.dfs_part;
+    float* dQK = w + lay.dQK;
+    float* dQb = w + lay.dQb;
+    float* dKb = w + lay.dKb;
+    const int sp1 = lay.sp1, sp2 = lay.sp2;
+    float* slab1 = w + lay.slab1; float* bslab1 = w + lay.bslab1;
+    float* slab2 = w + lay.slab2; float* bslab2 = w + lay.bslab2;
+    const size_t cols_lds = sizeof(float) * (2 * (size_t)L + 64);
+    if (cols_lds > 48 * 1024)
+        if (int e = lds_optin(reinterpret_cast<const void*>(boundary_self_bwd_cols_kernel), cols_lds)) return e;
 
     // f_bm = sum_j A hbar :  dA (map term), dhbar
     hipLaunchKernelGGL(boundary_reduce_bwd_kernel, dim3(L, B), dim3(256), 0, st, dout, A, hbar, cells, row_ptr, L, D, dAbm, dhbar);
     SMIN_LAUNCH_CHECK();
     hipLaunchKernelGGL(boundary_self_bwd_rows_kernel, dim3(L, B), dim3(256), sizeof(float) * L, st, dout, dAbm, A, fb, lmask, L, D, scale, draw);
     SMIN_LAUNCH_CHECK();
-    hipLaunchKernelGGL(boundary_self_bwd_cols_kernel, dim3(L, B), dim3(256), sizeof(float) * (2 * L + 64), st, dout, draw, A, bqv, baq, fb, fs, fw, Kb,
+    hipLaunchKernelGGL(boundary_self_bwd_cols_kernel, dim3(L, B), dim3(256), cols_lds, st, dout, draw, A, bqv, baq, fb, fs, fw, Kb,
                        P, qmask, lmask, L, Nq, D, scale, dfb, dbaq_lm, dfs_part, dQK, dQb);
     SMIN_LAUNCH_CHECK();
     {
-        const int slices = L > 96 ? cdiv(L, 32) : 1;                    // D % 4 == 0
+        const int slices = lay.slices;                                  // D % 4 == 0
         if (slices == 1) {
             hipLaunchKernelGGL(rows_reduce_kernel, dim3(cdiv(D, 256), 1, B), dim3(256), 0, st, dfs_part, L, L, D, dfs);
         } else {
-            float* mid = draw;                                          // [B][slices][D] <= [B][L][L] (D <= 2048 < 32 L); draw was consumed by the kernel above
+            float* mid = w + lay.mid;                                   // [B][slices][D], a piece of its own: any D the forward takes
             hipLaunchKernelGGL(rows_reduce_kernel, dim3(cdiv(D, 256), slices, B), dim3(256), 0, st, dfs_part, L, 32, D, mid);
             SMIN_LAUNCH_CHECK();
             hipLaunchKernelGGL(rows_reduce_kernel, dim3(cdiv(D, 256), 1, B), dim3(256), 0, st, mid, slices, slices, D, dfs);

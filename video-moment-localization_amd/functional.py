@@ -505,8 +505,7 @@ class BoundaryUnitFn(Function):
         WqT, WkT = Wq.t().contiguous(), Wk.t().contiguous()
         dfb, dfw, dfs, dhbar = torch.empty_like(fb), torch.empty_like(fw), torch.empty_like(fs), torch.empty_like(hbar)
         dWq, dbq, dWk, dbk = torch.empty_like(Wq), fb.new_empty((D,)), torch.empty_like(Wk), fb.new_empty((D,))
-        nbytes = 4 * (2 * B * L * L + 3 * B * L * D + B * L * Nq + B * Nq * D + 2 * 64 * (D * D + D)) + 4096
-        _, wp, wn = _ws(nbytes, fb.device)
+        _, wp, wn = _ws(_lib.load().smin_boundary_unit_bwd_ws_bytes(B, L, Nq, D), fb.device)
         call("smin_boundary_unit_bwd", stream(), ptr(dout), ptr(fb), ptr(fw), ptr(fs), ptr(hbar), ptr(layout.cells), ptr(layout.row_ptr),
              layout.N, B, L, Nq, D, ptr(WqT), ptr(WkT), ptr(qmask), ptr(lmask), ptr(Qb), ptr(Kb), ptr(P), ptr(baq), ptr(bqv), ptr(A),
              ptr(dfb), ptr(dfw), ptr(dfs), ptr(dhbar), ptr(dWq), ptr(dbq), ptr(dWk), ptr(dbk), wp, wn)
