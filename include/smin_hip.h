@@ -36,6 +36,10 @@ extern "C" {
  * A, boundary dout), smin_moment_unit_bwd[_x1h] (dfb_acc) and smin_build_targets; smin_score_map_bwd may be issued as two halves;
  * content attention requires dl % 16 == 0; round-2 changes that were not versioned: smin_linear_rows_bwd accepts dW == NULL,
  * smin_video_encoder_bwd / smin_bilstm_layer_bwd may be issued as two halves */
+/* additions within 2 (new entry points only; no existing signature or behaviour changed, so a caller built against 2 is unaffected
+ * and the number stays): gradients of the model's inputs -- smin_video_encoder_bwd_input (dx of the video features from the inputs
+ * half's workspace), smin_sample_clips_bwd, smin_embed_tokens_bwd and smin_embed_tokens_bwd_workspace_bytes (deterministic backward
+ * passes of the device feeding path) */
 #define SMIN_HIP_ABI_VERSION 2
 
 int smin_abi_version(void);
@@ -245,6 +249,12 @@ int smin_build_targets(void* stream, const float* times, const float* duration, 
  *   Rows t >= min(n, T) are zero (dataset.py:72-73).  Requires Din % 4 == 0, B <= 65535.  No host read; B = 0 is a no-op. */
 int smin_sample_clips(void* stream, const float* raw, const int64_t* offsets, const int32_t* spos, int B, int T, int Din, int mode,
                       float* video_features, int32_t* nfeats);
+/* its backward: dout [B][T][Din] -> draw [rows][Din] (rows = raw's row count), with the forward's offsets, spos and mode.  pick: a raw
+ * row gets the sum of every dout[b, t] whose output row read it, added in ascending t (rows repeat once clipped at n - 1); mean: a raw
+ * row gets dout[b, t] / cnt_t of its one window.  Rows no output row read (and rows outside every sample) are zero.  Deterministic
+ * (no atomics); 16-byte aligned dout / draw. */
+int smin_sample_clips_bwd(void* stream, const float* dout, const int64_t* offsets, const int32_t* spos, int B, int T, int Din, int mode,
+                          int64_t rows, float* draw);
 
 /* ---- query word vectors from token ids (reference dataset.py:32-38 get_query_features, dataset.py:173 query mask).
  * tokens [B][Nq] int32, table [V][E] (e.g. GloVe with <unk> and <pad> appended; 16-byte aligned, E % 4 == 0).
@@ -252,6 +262,13 @@ int smin_sample_clips(void* stream, const float* raw, const int64_t* offsets, co
  * (bytes 0/1; an out-of-range id gives 0), qlen [B] = sum of the mask.  No host read; B = 0 is a no-op. */
 int smin_embed_tokens(void* stream, const int32_t* tokens, const float* table, int B, int Nq, int V, int E, int pad_id,
                       float* query_features, uint8_t* query_mask, int32_t* qlen);
+/* its backward: dqf [B][Nq][E] -> dtable [V][E] (dense, as nn.Embedding(sparse=False)): row v = sum of dqf[b, w] over the positions
+ * holding id v, added in ascending (b, w) order; ids outside [0, V) contribute nothing; untouched rows are zero (the zero fill of the
+ * whole table is part of the cost).  Deterministic (no atomics): the (id, position) pairs are sorted in one workgroup, then one
+ * workgroup per distinct id.  Requires B * Nq <= 4096; ws of smin_embed_tokens_bwd_workspace_bytes (8-byte aligned). */
+size_t smin_embed_tokens_bwd_workspace_bytes(int B, int Nq);
+int smin_embed_tokens_bwd(void* stream, const int32_t* tokens, const float* dqf, int B, int Nq, int V, int E, float* dtable,
+                          void* ws, size_t ws_bytes);
 
 /* ---- compute_ious (reference utils.py:10-31): counts [8] = number of samples with a hit for
  * R@1 x IoU {0.1, 0.3, 0.5, 0.7} then R@5 x the same; ws [B][8] scratch.  Any L with L*L >= 5 (the reference's topk(5) needs as many). */
@@ -387,6 +404,11 @@ size_t smin_video_encoder_bwd_workspace_bytes(int B, int T, int Din, int D);
  * second ordered behind the first): dW == NULL -> inputs half (dfs; the masked gradient stays in ws); df == NULL -> weights half. */
 int smin_video_encoder_bwd(void* stream, const float* df, const float* fv, const float* fs, const float* vmask, const float* x,
                            int B, int T, int Din, int D, float* dW, float* dbias, float* dpe, float* dfs, void* ws, size_t ws_bytes);
+/* the input feature's gradient dx [B*T][Din] = dv W, dv = df * fs * vmask the masked gradient that the inputs half above left in ws
+ * (the same ws; issue it behind that half, before or beside the weights half, which only reads ws as well).  WT = W^T [Din][D].
+ * Rows of padded frames (vmask = 0) are exactly zero.  Requires Din % 4 == 0, D % 4 == 0. */
+int smin_video_encoder_bwd_input(void* stream, const float* WT, const float* vmask, int B, int T, int Din, int D, float* dx,
+                                 const void* ws, size_t ws_bytes);
 
 /* ---- QueryEncoder's bidirectional LSTM layer (models.py:38-64: nn.LSTM over a packed, padded batch), one layer per
  * call, both directions.  X [B*Nq][In]; Wih_cat [8H][In] = [W_ih; W_ih_reverse]; bias_cat [8H] = b_ih + b_hh per

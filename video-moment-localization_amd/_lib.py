@@ -60,6 +60,9 @@ SIGNATURES = {
     "smin_build_targets": [_vp] * 5 + [_i] * 4 + [_vp] * 12,
     "smin_sample_clips": [_vp] * 4 + [_i] * 4 + [_vp] * 2,
     "smin_embed_tokens": [_vp] * 3 + [_i] * 5 + [_vp] * 3,
+    "smin_sample_clips_bwd": [_vp] * 4 + [_i] * 4 + [ctypes.c_int64, _vp],
+    "smin_embed_tokens_bwd_workspace_bytes": [_i, _i],
+    "smin_embed_tokens_bwd": [_vp] * 3 + [_i] * 4 + [_vp, _vp, _sz],
     "smin_word_prep_fwd": [_vp] * 5 + [_i] * 5 + [_vp] * 5,
     "smin_word_prep_bwd_workspace_bytes": [_i] * 5,
     "smin_word_prep_bwd": [_vp] * 11 + [_i] * 5 + [_vp] * 3 + [_vp, _sz],
@@ -89,6 +92,7 @@ SIGNATURES = {
     "smin_video_encoder_gate": [_vp] * 3 + [_i] * 3 + [_vp],
     "smin_video_encoder_bwd_workspace_bytes": [_i] * 4,
     "smin_video_encoder_bwd": [_vp] * 6 + [_i] * 4 + [_vp] * 4 + [_vp, _sz],
+    "smin_video_encoder_bwd_input": [_vp] * 3 + [_i] * 4 + [_vp, _vp, _sz],
     "smin_bilstm_layer_fwd": [_vp] * 6 + [_i] * 4 + [_vp] * 3,
     "smin_lstm_pack": [_vp, _vp, _i, _i] + [_vp] * 4,
     "smin_lstm_pack_layers": [_vp, _i, _vp, _vp, _i] + [_vp] * 4,
@@ -102,7 +106,8 @@ SIGNATURES = {
 }
 _RESTYPE = {"smin_target_arch": ctypes.c_char_p, "smin_workspace_bytes": _sz,
             "smin_content_attn_bwd_workspace_bytes": _sz, "smin_linear_rows_bwd_workspace_bytes": _sz,
-            "smin_bilstm_layer_bwd_workspace_bytes": _sz, "smin_video_encoder_bwd_workspace_bytes": _sz, "smin_word_prep_bwd_workspace_bytes": _sz,
+            "smin_bilstm_layer_bwd_workspace_bytes": _sz, "smin_video_encoder_bwd_workspace_bytes": _sz, "smin_embed_tokens_bwd_workspace_bytes": _sz,
+            "smin_word_prep_bwd_workspace_bytes": _sz,
             "smin_col_sum_workspace_bytes": _sz, "smin_top_moments_ws_bytes": _sz, "smin_boundary_unit_bwd_ws_bytes": _sz, "smin_compute_ious_nms_ws_bytes": _sz}
 
 _lib = None

@@ -6,7 +6,7 @@
 // HIP entry points, so the backward pass runs on the autograd engine's thread without the interpreter (DistributedDataParallel
 // hooks fire as usual).  The Python host (video-moment-localization_amd/functional.py, modules.py) binds the same C ABI with
 // ctypes, a node per module; it serves the stand-alone sub-module seams and every in-model call this binding refuses
-// (SMIN.native_host = False, inputs that require grad, configurations outside the limits of SMIN._native_ok).
+// (SMIN.native_host = False, inputs that require grad without the input_grads opt-in, configurations outside the limits of SMIN._native_ok).
 // torch types appear only in this file; libsmin_hip.so knows pointers and sizes.
 //
 // Only the in-model fast path lives here: the content stream on a mask-driven cell list.
@@ -336,7 +336,9 @@ struct SminCore : torch::autograd::Function<SminCore> {
     // F_KEEP_ATTENTION: every layer's word-attention maps leave as extra outputs (not differentiable; the backward ignores them):
     // the content maps dense (B, L, L, C, Nq), or with F_ATTN_PACKED as packed rows [N*C][Nq] followed by the cellmap; the boundary maps (B, L, Nq)
     enum { F_OVERLAP_BOUNDARY = 1, F_OVERLAP_PREP = 2, F_ASYNC_WEIGHTS = 4, F_BF16_OPERANDS = 8, F_GRAD_SYNC = 16, F_NO_TAIL_SPLIT = 32, F_KEEP_ATTENTION = 64,
-           F_ATTN_PACKED = 128 };
+           F_ATTN_PACKED = 128, F_INPUT_GRADS = 256 };
+    // F_INPUT_GRADS: video_features / query_features may require grad; the backward then returns their gradients in slots 0 and 2
+    // (each formed only when autograd asks for it)
     enum { N_FIXED = 13 };          // forward arguments ahead of the parameter list (tensors and scalars alike take one gradient slot)
 
     static variable_list forward(AutogradContext* ctx, Tensor video_features, Tensor video_mask, Tensor query_features, Tensor query_mask, Tensor length_mask,
@@ -703,6 +705,8 @@ struct SminCore : torch::autograd::Function<SminCore> {
         GradSync sync;
         sync.on = (flags & F_GRAD_SYNC) != 0;
         TORCH_CHECK(!sync.on || prep_kernel, "smin_forward: the in-node gradient exchange needs the parameter-product kernel (D % 32 == 0, D <= 1056, dl % 32 == 0, <= 8 layers)");
+        // the inputs' gradients (F_INPUT_GRADS): d video_features = the video encoder's dx, d query_features = LSTM layer 0's dX
+        const bool want_dx = (flags & F_INPUT_GRADS) && ctx->needs_input_grad(0), want_dX = (flags & F_INPUT_GRADS) && ctx->needs_input_grad(2);
         TORCH_CHECK(!sync.on || !grad_sync_config().group.empty(), "smin_forward: grad_sync requested but no process group was set (smin_hip::set_grad_sync)");
         std::vector<Tensor> dprm(prm.size());
         auto dlp = [&](int64_t k, int which) -> Tensor& { return dprm[k * L_COUNT + which]; };
@@ -716,8 +720,10 @@ struct SminCore : torch::autograd::Function<SminCore> {
         }
         const size_t tr_pcat0 = tr_in.size();
         for (int64_t k = 0; k < nl; ++k) for (auto& p : st.layer[k].Pcat) tr_in.push_back(p);
+        const size_t tr_tail = tr_in.size();
         tr_in.push_back(st.Wch_all);
         tr_in.push_back(st.lstm[0].Wih); tr_in.push_back(st.lstm[1].Wih);
+        if (want_dx) tr_in.push_back(all[P_VE_W]);
         // (on the boundary stream, as the boundary heads' backward below: beside the score map's backward on the main stream, which
         //  otherwise opens the backward pass with four short launches in a row in front of the first contraction)
         HStream early = (side != curs && (flags & F_OVERLAP_PREP)) ? side : curs;
@@ -731,7 +737,7 @@ struct SminCore : torch::autograd::Function<SminCore> {
         auto trk = [&](int64_t k, int which) -> const Tensor& { return tr[k * TR_PER_LAYER + which]; };
         std::vector<std::vector<Tensor>> PcatT(nl);
         { size_t i = tr_pcat0; for (int64_t k = 0; k < nl; ++k) for (size_t p = 0; p < st.layer[k].Pcat.size(); ++p) PcatT[k].push_back(tr[i++]); }
-        const Tensor &Wch_allT = tr[tr.size() - 3], *WihT = &tr[tr.size() - 2];
+        const Tensor &Wch_allT = tr[tr_tail], *WihT = &tr[tr_tail + 1];
 
         // ---- Localization
         const Tensor& bu_last = st.layer[nl - 1].bu;
@@ -1106,6 +1112,7 @@ struct SminCore : torch::autograd::Function<SminCore> {
 
         // ---- backbone on the main stream: video encoder, sentence / word features, the two LSTM layers (models.py:38-83)
         std::vector<Tensor> dbb(P_LAYER0), lstm_bufs;
+        Tensor dvideo, dquery;
         // the backbone's weight halves: on the word stream (idle by now) when there is one -- the weight stream still holds layer 0's
         // moment-unit contraction, and these short kernels close the step
         HStream bstr = (tail_split && wordst != curs && wstr != curs) ? wordst : wstr;
@@ -1141,7 +1148,7 @@ struct SminCore : torch::autograd::Function<SminCore> {
             for (int layer = 1; layer >= 0; --layer) {
                 LstmState& ls = st.lstm[layer];
                 const int In = i32(ls.x.size(2)), Hh = i32(H);
-                Tensor dX = layer > 0 ? at::empty_like(ls.x) : Tensor();
+                Tensor dX = layer > 0 || want_dX ? at::empty_like(ls.x) : Tensor();
                 Tensor dWih = at::empty_like(ls.Wih), dbias = at::empty({8 * H}, opt), dWhh = at::empty_like(ls.Whh);
                 lstm_bufs.push_back(dWih); lstm_bufs.push_back(dbias); lstm_bufs.push_back(dWhh);
                 Tensor wsl = own(smin_bilstm_layer_bwd_workspace_bytes(B, i32(Nq_in), In, Hh));
@@ -1169,6 +1176,13 @@ struct SminCore : torch::autograd::Function<SminCore> {
                 o[4] = dWih.slice(0, H4); o[5] = dWhh[1]; o[6] = dbias.slice(0, H4); o[7] = dbias2.slice(0, H4);
                 dH = dX;
             }
+            dquery = dH;
+            // the video features' gradient behind the last recurrence, on the main stream: the cluster recurrences need every CU's LDS
+            // co-resident, and here only the layer-0 weight pieces are left beside it (measured against the weight stream: DESIGN 6)
+            if (want_dx) {
+                dvideo = at::empty_like(st.vx);
+                SMIN_CK(smin_video_encoder_bwd_input(cur(), fp(tr[tr_tail + 3]), fp(st.vmaskf), B, Ti, Din, D, fpm(dvideo), wsv.data_ptr(), (size_t)wsv.numel()));
+            }
         }
         wait_stream(curs, tail);
         wait_stream(curs, wstr);
@@ -1181,6 +1195,8 @@ struct SminCore : torch::autograd::Function<SminCore> {
         }
 
         variable_list out(N_FIXED + all.size());
+        if (want_dx) out[0] = dvideo;
+        if (want_dX) out[2] = dquery;
         for (size_t i = 0; i < all.size(); ++i) out[N_FIXED + i] = i < (size_t)P_LAYER0 ? dbb[i] : dprm[i - P_LAYER0];
         return out;
     }
@@ -1192,12 +1208,14 @@ variable_list smin_forward_impl(const Tensor& video_features, const Tensor& vide
                                 const Tensor& length_mask, const Tensor& moment_mask, at::TensorList prm, at::IntArrayRef cfg, int64_t extra_flags)
 {
     TORCH_CHECK(video_features.is_cuda(), "smin_forward runs on a HIP device only (there is no CPU fallback)");
-    TORCH_CHECK(cfg.size() == 16, "smin_forward: cfg = [T, L, C, D, dl, layers, max_query_length, H, overlap_boundary, overlap_prep, fused_core, async_weights, "
-                "bf16_operand_storage, grad_sync, known_cell_count or -1, tail_split], got ", cfg.size(), " entries");
+    TORCH_CHECK(cfg.size() == 16 || cfg.size() == 17, "smin_forward: cfg = [T, L, C, D, dl, layers, max_query_length, H, overlap_boundary, overlap_prep, fused_core, "
+                "async_weights, bf16_operand_storage, grad_sync, known_cell_count or -1, tail_split] [+ input_grads 0 / 1], got ", cfg.size(), " entries");
+    const bool input_grads = cfg.size() == 17 && cfg[16] != 0;
     TORCH_CHECK(cfg[10] != 0, "smin_forward builds the whole model as one autograd node (cfg[10] = fused_core = 1); a node per module is built by the "
                 "Python host (SMIN.native_host = False)");
-    TORCH_CHECK(!video_features.requires_grad() && !query_features.requires_grad(), "smin_forward forms no gradients of video_features / query_features; "
-                "inputs that require grad go through the Python host (SMIN.native_host = False)");
+    TORCH_CHECK(input_grads || (!video_features.requires_grad() && !query_features.requires_grad()), "smin_forward forms no gradients of video_features / "
+                "query_features unless cfg[16] = input_grads = 1 (SMIN.input_grads = True); otherwise inputs that require grad go through the Python host "
+                "(SMIN.native_host = False)");
     // The reference's dataset pads queries and their mask to max_query_length (dataset.py:35, 173); a batch cut to its longest query is
     // taken too: the word features are padded in the node as models.py:58-59 does, and the mask here, since every kernel reads max_query_length columns.
     TORCH_CHECK(query_features.dim() == 3, "smin_forward: query_features (B, words, dim)");
@@ -1210,6 +1228,7 @@ variable_list smin_forward_impl(const Tensor& video_features, const Tensor& vide
     c10::hip::HIPGuard device_guard(video_features.device().index());
     const int64_t flags = (cfg[8] != 0 ? SminCore::F_OVERLAP_BOUNDARY : 0) | (cfg[9] != 0 ? SminCore::F_OVERLAP_PREP : 0) | (cfg[11] != 0 ? SminCore::F_ASYNC_WEIGHTS : 0) |
                           (cfg[12] != 0 ? SminCore::F_BF16_OPERANDS : 0) | (cfg[13] != 0 ? SminCore::F_GRAD_SYNC : 0) | (cfg[15] == 0 ? SminCore::F_NO_TAIL_SPLIT : 0) |
+                          (input_grads ? SminCore::F_INPUT_GRADS : 0) |
                           (cfg[14] >= 0 ? ((cfg[14] + 1) << 16) : 0) | extra_flags;      // cfg[14]: the number of valid cells, when the caller knows it
     return SminCore::apply(video_features, video_mask, query_features, query_mask, length_mask, moment_mask, T, L, C, nl, maxq, H, flags, prm);
 }
@@ -1223,15 +1242,18 @@ std::tuple<Tensor, Tensor, Tensor, Tensor> smin_forward(const Tensor& video_feat
 
 // smin_forward that also returns every layer's word-attention maps (detached): content[k] = ContentAttention.attn_weights (B, L, L, C, Nq)
 // (models.py:207-226), boundary[k] = Attention.attn_weights (B, L, Nq) (models.py:137-154).  cfg: smin_forward's 16 entries, optionally a 17th:
-// 1 = the content maps packed, content = [probs_0 [N*C, Nq], .., probs_{layers-1}, cellmap (B, L, L) int32] (what SMIN.localize gathers from)
+// 1 = the content maps packed, content = [probs_0 [N*C, Nq], .., probs_{layers-1}, cellmap (B, L, L) int32] (what SMIN.localize gathers from),
+// and an 18th: smin_forward's input_grads
 std::tuple<Tensor, Tensor, Tensor, Tensor, std::vector<Tensor>, std::vector<Tensor>> smin_forward_with_attention(
     const Tensor& video_features, const Tensor& video_mask, const Tensor& query_features, const Tensor& query_mask, const Tensor& length_mask,
     const Tensor& moment_mask, at::TensorList prm, at::IntArrayRef cfg)
 {
-    TORCH_CHECK(cfg.size() == 16 || cfg.size() == 17, "smin_forward_with_attention: cfg = smin_forward's 16 entries [+ packed content maps 0 / 1], got ",
-                cfg.size(), " entries");
-    const bool packed = cfg.size() == 17 && cfg[16] != 0;
-    auto out = smin_forward_impl(video_features, video_mask, query_features, query_mask, length_mask, moment_mask, prm, cfg.slice(0, 16),
+    TORCH_CHECK(cfg.size() >= 16 && cfg.size() <= 18, "smin_forward_with_attention: cfg = smin_forward's 16 entries [+ packed content maps 0 / 1 "
+                "[+ input_grads 0 / 1]], got ", cfg.size(), " entries");
+    const bool packed = cfg.size() >= 17 && cfg[16] != 0;
+    std::vector<int64_t> cfg_core(cfg.begin(), cfg.begin() + 16);
+    if (cfg.size() == 18) cfg_core.push_back(cfg[17]);
+    auto out = smin_forward_impl(video_features, video_mask, query_features, query_mask, length_mask, moment_mask, prm, cfg_core,
                                  SminCore::F_KEEP_ATTENTION | (packed ? SminCore::F_ATTN_PACKED : 0));
     const int64_t nl = cfg[5], nc = nl + (packed ? 1 : 0);
     TORCH_CHECK((int64_t)out.size() == 4 + nc + nl, "smin_forward_with_attention: ", out.size(), " outputs");
@@ -1253,7 +1275,8 @@ TORCH_LIBRARY(smin_hip, m)
 {
     // SMIN.forward (reference models.py:367-377): the six forward arguments, the parameters in SMIN._native_params order and
     // cfg = [T, L, C, D, dl, num_smi_layers, max_query_length, lstm_hidden_size, overlap_boundary, overlap_prep, fused_core (must be 1),
-    //        async_weights, bf16_operand_storage, grad_sync, known_cell_count or -1, tail_split]  
+    //        async_weights, bf16_operand_storage, grad_sync, known_cell_count or -1, tail_split] and optionally input_grads: 1 = video_features /
+    //        query_features may require grad and receive their gradients
     m.def("smin_forward(Tensor video_features, Tensor video_mask, Tensor query_features, Tensor query_mask, Tensor length_mask, Tensor moment_mask, "
           "Tensor[] params, int[] cfg) -> (Tensor, Tensor, Tensor, Tensor)", &smin_forward);
     // the same node with every layer's word-attention maps as extra, non-differentiable outputs

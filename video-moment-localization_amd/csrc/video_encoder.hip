@@ -100,7 +100,7 @@ extern "C" size_t smin_video_encoder_bwd_workspace_bytes(int B, int T, int Din, 
     return sizeof(float) * ((size_t)B * T * D + sp * ((size_t)D * Din + D) + 256);
 }
 
-// df [B*T][D] -> dW [D][Din], dbias [D], dpe [T][D], dfs [B][D]   (x receives no gradient: it is the input feature).
+// df [B*T][D] -> dW [D][Din], dbias [D], dpe [T][D], dfs [B][D]   (x's gradient, when wanted: smin_video_encoder_bwd_input below).
 // In two calls on the same ws: dW == NULL -> the inputs half only (dfs; the masked gradient stays in ws); df == NULL -> the weights half
 // (dW, dbias, dpe from ws as the inputs half left it).
 extern "C" int smin_video_encoder_bwd(void* stream, const float* df, const float* fv, const float* fs, const float* vmask, const float* x,
@@ -123,4 +123,27 @@ extern "C" int smin_video_encoder_bwd(void* stream, const float* df, const float
     SMIN_LAUNCH_CHECK();
     int rc = launch_gemm_tn(st, PlainMat{dv, D}, PlainMat{x, Din}, slab, bslab, R, D, Din, sp); if (rc) return rc;
     return launch_reduce_slabs2(st, slab, dW, D * Din, bslab, dbias, D, sp);
+}
+
+// dx[b][t][:] = dv[b][t][:] W  -- the gradient of the input feature, from the masked gradient dv that the inputs half of
+// smin_video_encoder_bwd left in ws.  NT contraction with W^T [Din][D] as the B operand; rows of padded frames are stored as exact
+// zeros (their dv rows are zero already; the select keeps them zero whatever W holds).
+namespace smin {
+struct EpVideoDx {
+    const float* vmask; float* dx;
+    __device__ __forceinline__ void chunk(const float* Ws, int row0, int col0, int ncols, int M, int N, int lane) const {
+        chunk_rows_f4(Ws, row0, col0, ncols, M, N, lane, [&](int row, int col, float4 v) {
+            stg4(dx + (size_t)row * N + col, vmask[row] != 0.f ? v : f4zero());
+        });
+    }
+};
+}  // namespace smin
+
+extern "C" int smin_video_encoder_bwd_input(void* stream, const float* WT, const float* vmask, int B, int T, int Din, int D, float* dx,
+                                            const void* ws, size_t ws_bytes)
+{
+    SMIN_REQUIRE(Din % 4 == 0 && D % 4 == 0 && B >= 1 && T >= 1 && WT != nullptr && dx != nullptr);
+    SMIN_REQUIRE(ws_bytes >= smin_video_encoder_bwd_workspace_bytes(B, T, Din, D));
+    const float* dv = reinterpret_cast<const float*>(ws);
+    return launch_gemm_nt((hipStream_t)stream, PlainMat{dv, D}, PlainMat{WT, D}, EpVideoDx{vmask, dx}, B * T, Din, D);
 }

@@ -317,22 +317,23 @@ class WordPrepFn(Function):
 
 class VideoFuseFn(Function):
     """f = ((x W^T + b + pe[t]) * vmask) * f_s  -- VideoEncoder.forward and the backbone's Hadamard product (reference
-    models.py:25-36, 81-83) as one contraction with a fused epilogue.  x [B, T, Din] (no gradient), pe [T_emb, D]."""
+    models.py:25-36, 81-83) as one contraction with a fused epilogue.  x [B, T, Din], pe [T_emb, D].  x receives a gradient only with
+    input_grad=True (SMIN.input_grads), then from smin_video_encoder_bwd_input; otherwise none, as before."""
 
     @staticmethod
-    def forward(ctx, x, W, bias, pe, vmask, fs):
+    def forward(ctx, x, W, bias, pe, vmask, fs, input_grad=False):
         x, W, bias, pe, vmask, fs = map(_c, (x, W, bias, pe, vmask, fs))
         B, T, Din = x.shape
         D = W.shape[0]
         fv, f = x.new_empty((B, T, D)), x.new_empty((B, T, D))
         call("smin_video_encoder_fwd", stream(), ptr(x), ptr(W), ptr(bias), ptr(pe), ptr(vmask), ptr(fs), B, T, Din, D, ptr(fv), ptr(f))
-        ctx.save_for_backward(x, fv, fs, vmask)
-        ctx.dims, ctx.pe_rows = (B, T, Din, D), pe.shape[0]
+        ctx.save_for_backward(x, fv, fs, vmask, *((W,) if input_grad else ()))
+        ctx.dims, ctx.pe_rows, ctx.input_grad = (B, T, Din, D), pe.shape[0], input_grad
         return f
 
     @staticmethod
     def backward(ctx, df):
-        x, fv, fs, vmask = ctx.saved_tensors
+        x, fv, fs, vmask, *W = ctx.saved_tensors
         B, T, Din, D = ctx.dims
         df = _c(df)
         dW, dbias = x.new_empty((D, Din)), x.new_empty((D,))
@@ -341,7 +342,11 @@ class VideoFuseFn(Function):
         _, wp, wn = _ws(_lib.load().smin_video_encoder_bwd_workspace_bytes(B, T, Din, D), x.device)
         call("smin_video_encoder_bwd", stream(), ptr(df), ptr(fv), ptr(fs), ptr(vmask), ptr(x), B, T, Din, D,
              ptr(dW), ptr(dbias), ptr(dpe), ptr(dfs), wp, wn)
-        return None, dW, dbias, dpe, None, dfs
+        dx = None
+        if ctx.input_grad and ctx.needs_input_grad[0]:                     # dx = dv W from the masked gradient dv the call above left in ws
+            dx = torch.empty_like(x)
+            call("smin_video_encoder_bwd_input", stream(), ptr(W[0].t().contiguous()), ptr(vmask), B, T, Din, D, ptr(dx), wp, wn)
+        return dx, dW, dbias, dpe, None, dfs, None
 
 
 class BiLstmLayerFn(Function):

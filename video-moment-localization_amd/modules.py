@@ -167,14 +167,16 @@ class Backbone(nn.Module):
         self.queryencoder = QueryEncoder(max_query_length, lstm_hidden_size)
 
     @_hip_forward
-    def forward(self, video_features, video_mask, query_features, query_mask):
+    def forward(self, video_features, video_mask, query_features, query_mask, input_grads=False):
+        """input_grads: the fused video encoder also forms video_features' gradient (SMIN.input_grads); the query encoder forms
+        query_features' gradient either way."""
         fs, fw = self.queryencoder(query_features, query_mask)
         ve = self.videoencoder
         if (video_features.dtype == torch.float32 and ve.d0 % 4 == 0 and ve.d % 4 == 0
                 and video_features.shape[1] <= ve.pe.weight.shape[0]):
             # projection + position embedding + mask + Hadamard product with f_s in one contraction (video_encoder.hip)
             B, T, _ = video_features.shape
-            f = VideoFuseFn.apply(video_features, ve.ve.weight, ve.ve.bias, ve.pe.weight, video_mask.reshape(B * T).float(), fs)
+            f = VideoFuseFn.apply(video_features, ve.ve.weight, ve.ve.bias, ve.pe.weight, video_mask.reshape(B * T).float(), fs, input_grads)
             return f, fs, fw
         fv = ve(video_features, video_mask)
         return fv * fs.unsqueeze(1), fs, fw
@@ -460,6 +462,10 @@ class SMIN(nn.Module):
                                    # smis[k].content_unit.attn_layer.attn_weights (B, L, L, C, Nq) and
                                    # smis[k].boundary_unit.attn_layer.attn_weights (B, L, Nq), detached (INTEGRATION.md 3d;
                                    # B*L*L*C*Nq*4 bytes per layer for the content maps)
+    input_grads = False            # video_features / query_features that require grad receive their gradients, as under the reference's
+                                   # autograd: the one-node path serves them (torch_binding.cpp F_INPUT_GRADS) and the Python host's fused
+                                   # video encoder forms video_features.grad too.  False: such inputs run the Python host, which forms
+                                   # query_features.grad only (video_features.grad stays None) -- INTEGRATION.md 3e
 
     def _forward_stream(self, f, fs, fw, query_mask, length_mask, layout, maps=None):
         """The same network with the content unit's two linear maps re-associated (exact in real arithmetic).
@@ -607,9 +613,10 @@ class SMIN(nn.Module):
     def _native_ok(self, video_features, query_features):
         """The torch-extension path (one autograd node) covers the production configuration: content stream on a mask-driven cell
         list, fused BiLSTM and video encoder kernels, inputs that need no gradient.  Anything else (fused_core = False, dl >= D, C outside
-        2..4, > 8 layers, H > 256, odd widths, video / query features that require grad) runs the same kernels from the Python host below."""
+        2..4, > 8 layers, H > 256, odd widths, video / query features that require grad unless input_grads) runs the same kernels from the
+        Python host below."""
         H, ve, nl = self.lstm_hidden_size, self.backbone.videoencoder, len(self.smis)
-        return (self.native_host and self.fused_core and not video_features.requires_grad and not query_features.requires_grad
+        return (self.native_host and self.fused_core and (self.input_grads or not (video_features.requires_grad or query_features.requires_grad))
                 and self.content_stream and self.dl < self.D and 2 <= self.C <= 4 and 1 <= nl <= 8 and nl * self.dl <= 2048
                 and self.backbone.queryencoder.fused_lstm and H <= 256 and H % 4 == 0
                 and video_features.dtype == torch.float32 and query_features.dtype == torch.float32 and ve.d0 % 4 == 0 and ve.d % 4 == 0
@@ -679,12 +686,13 @@ class SMIN(nn.Module):
                    int(self.overlap_boundary), int(self.overlap_prep and (self._streams_allowed("torch") or self._prep_is_library_code())), int(self.fused_core),
                    int(self.async_weights), int(self.bf16_operand_storage), int(self.grad_sync and torch.is_grad_enabled()),
                    -1 if self.known_cell_count is None else int(self.known_cell_count), int(self.tail_split)]
+            opt_in = [1] if self.input_grads else []
             if maps is None:
                 return _lib.load_torch().smin_forward(video_features, video_mask, query_features, query_mask, length_mask, moment_mask,
-                                                      self._native_params(), cfg)
+                                                      self._native_params(), cfg + opt_in)
             packed = maps.mode == "packed"
             pm, ps, pe, pa, content, boundary = _lib.load_torch().smin_forward_with_attention(
-                video_features, video_mask, query_features, query_mask, length_mask, moment_mask, self._native_params(), cfg + [int(packed)])
+                video_features, video_mask, query_features, query_mask, length_mask, moment_mask, self._native_params(), cfg + [int(packed)] + opt_in)
             if packed:
                 maps.cellmap, content = content[-1], content[:-1]
             maps.extend(zip(content, boundary))
@@ -694,7 +702,7 @@ class SMIN(nn.Module):
                                "core; this configuration runs the content units as written (ContentUnitFn, see SMIN._stream_ok), which cannot "
                                "deliver them")
         pending = CellLayout.begin(moment_mask)                    # work is driven by moment_mask (SURVEY 8a-0 caveat)
-        f, fs, fw = self.backbone(video_features, video_mask, query_features, query_mask)
+        f, fs, fw = self.backbone(video_features, video_mask, query_features, query_mask, input_grads=self.input_grads)
         layout = pending.finish()                                  # the only host sync of a step; hidden behind the backbone
         if (self.content_stream and self.dl < self.D and 2 <= self.C <= 4 and layout.all_valid
                 and len(self.smis) <= 8 and len(self.smis) * self.dl <= 2048):    # limits of the clip-window-means launch

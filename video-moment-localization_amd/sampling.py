@@ -17,7 +17,12 @@ double and ``a_T = n``, summed in fp32 in ascending row order and divided once i
 
 ``sample_clips`` / ``embed_tokens`` are the product entry points (HIP tensors only, no host read, capturable in a graph);
 ``sample_clips_torch`` / ``clip_indices`` are the plain numpy / torch restatement the tests compare against -- nothing routes to
-them silently."""
+them silently.
+
+With ``differentiable=True`` and grad mode on, a ``raw`` / ``table`` that requires grad receives its gradient through an autograd
+node backed by deterministic HIP backward kernels (``smin_sample_clips_bwd`` / ``smin_embed_tokens_bwd``: fixed summation order, no
+atomics); ``nfeats``, ``query_mask`` and ``qlen`` are never differentiable.  By default both functions detach their inputs."""
+from torch.autograd import Function
 import numpy as np
 import torch
 
@@ -91,14 +96,45 @@ def _pack(raw, offsets_or_lengths):
     return raw, _lengths_host(offsets_or_lengths), None
 
 
-def sample_clips(raw, offsets_or_lengths, T, spos=None, mode="pick"):
+class _SampleClipsFn(Function):
+    """sample_clips' resampling as an autograd node: raw (rows, Din) -> video_features (B, T, Din); backward smin_sample_clips_bwd."""
+
+    @staticmethod
+    def forward(ctx, raw, offsets, sp, B, T, mode):
+        from ._lib import call, ptr, stream
+        Din = raw.shape[1]
+        out = torch.empty((B, T, Din), dtype=torch.float32, device=raw.device)
+        nfeats = torch.empty((B,), dtype=torch.int32, device=raw.device)
+        call("smin_sample_clips", stream(), ptr(raw), ptr(offsets), ptr(sp), B, T, Din, mode, ptr(out), ptr(nfeats))
+        ctx.mark_non_differentiable(nfeats)
+        ctx.save_for_backward(offsets, sp)
+        ctx.dims = (B, T, Din, mode, raw.shape[0])
+        return out, nfeats
+
+    @staticmethod
+    def backward(ctx, dout, _dnfeats):
+        from ._lib import call, ptr, stream
+        offsets, sp = ctx.saved_tensors
+        B, T, Din, mode, rows = ctx.dims
+        dout = dout.float().contiguous()
+        if dout.data_ptr() % 16:
+            dout = dout.clone()
+        draw = torch.empty((rows, Din), dtype=torch.float32, device=dout.device)
+        call("smin_sample_clips_bwd", stream(), ptr(dout), ptr(offsets), ptr(sp), B, T, Din, mode, rows, ptr(draw))
+        return draw, None, None, None, None, None
+
+
+def sample_clips(raw, offsets_or_lengths, T, spos=None, mode="pick", differentiable=False):
     """Resample a batch of ragged raw feature sequences to ``(B, T, Din)`` on the device (module docstring).
 
     ``raw``: one packed HIP tensor ``(sum n_b, Din)`` with ``offsets_or_lengths`` either host lengths ``(B,)`` (list, numpy or CPU
     tensor: validated here) or device offsets ``(B + 1,)`` int64 (nothing is read back: graph-capturable; they must be non-decreasing
     and within ``raw``, which is not checked); or a list of ``B`` HIP tensors ``(n_b, Din)`` with ``offsets_or_lengths=None``.
     ``spos``: ``None`` (all 0, the eval split), host values (validated against the reference's range: ValueError) or a device int
-    tensor ``(B,)``.  Returns ``(video_features (B, T, Din) float32, nfeats (B,) int32)`` with ``nfeats = min(n_b, T)``."""
+    tensor ``(B,)``.  Returns ``(video_features (B, T, Din) float32, nfeats (B,) int32)`` with ``nfeats = min(n_b, T)``.
+    ``differentiable=True``: when ``raw`` (or a tensor of the list) requires grad under grad mode, ``video_features`` carries an
+    autograd node whose backward gives each raw row the sum of the output rows' gradients that read it (ascending ``t``; mean mode:
+    its window's gradient over the window's row count); rows never sampled get 0.  Default: ``raw`` is detached."""
     from ._lib import SminHipError, call, ptr, stream
     if mode not in MODES:
         raise ValueError(f"mode must be one of {sorted(MODES)} (got {mode!r})")
@@ -113,7 +149,8 @@ def sample_clips(raw, offsets_or_lengths, T, spos=None, mode="pick"):
     dev, Din, T = raw.device, raw.shape[1], int(T)
     if T < 1:
         raise ValueError(f"T must be >= 1 (got {T})")
-    raw = raw.detach().float().contiguous()
+    grad = differentiable and raw.requires_grad and torch.is_grad_enabled()
+    raw = (raw if grad else raw.detach()).float().contiguous()
     if raw.data_ptr() % 16:
         raw = raw.clone()
     if lengths is not None:
@@ -136,6 +173,11 @@ def sample_clips(raw, offsets_or_lengths, T, spos=None, mode="pick"):
             sp = torch.from_numpy(s).to(dev) if mode == "pick" else None
         else:
             raise ValueError("host spos needs host lengths to be checked against (pass lengths, or spos as a device tensor)")
+    if grad:
+        if B > 65535:
+            raise ValueError(f"sample_clips: at most 65535 videos per call (got {B})")
+        with torch.cuda.device(dev):
+            return _SampleClipsFn.apply(raw, offsets.contiguous(), sp, B, T, MODES[mode])
     out = torch.empty((B, T, Din), dtype=torch.float32, device=dev)
     nfeats = torch.empty((B,), dtype=torch.int32, device=dev)
     with torch.cuda.device(dev):
@@ -179,12 +221,49 @@ def sample_clips_torch(raw, offsets_or_lengths, T, spos=None, mode="pick"):
     return torch.from_numpy(out), torch.from_numpy(np.minimum(lengths, T).astype(np.int32))
 
 
-def embed_tokens(tokens, table, pad_id=None):
+class _EmbedTokensFn(Function):
+    """embed_tokens' lookup as an autograd node: table (V, E) -> query_features (B, Nq, E); backward smin_embed_tokens_bwd."""
+
+    @staticmethod
+    def forward(ctx, tok, table, pad_id):
+        from ._lib import call, ptr, stream
+        (B, Nq), (V, E) = tok.shape, table.shape
+        qf = torch.empty((B, Nq, E), dtype=torch.float32, device=tok.device)
+        qm = torch.empty((B, Nq), dtype=torch.uint8, device=tok.device)
+        ql = torch.empty((B,), dtype=torch.int32, device=tok.device)
+        call("smin_embed_tokens", stream(), ptr(tok), ptr(table), B, Nq, V, E, pad_id, ptr(qf), ptr(qm), ptr(ql))
+        ctx.mark_non_differentiable(qm, ql)
+        ctx.save_for_backward(tok)
+        ctx.V = V
+        return qf, qm, ql
+
+    @staticmethod
+    def backward(ctx, dqf, _dqm, _dql):
+        from ._lib import call, load, ptr, stream, workspace
+        (tok,) = ctx.saved_tensors
+        B, Nq = tok.shape
+        E = dqf.shape[2]
+        dqf = dqf.float().contiguous()
+        if dqf.data_ptr() % 16:
+            dqf = dqf.clone()
+        dtable = torch.empty((ctx.V, E), dtype=torch.float32, device=dqf.device)
+        ws = workspace(load().smin_embed_tokens_bwd_workspace_bytes(B, Nq), dqf.device)
+        call("smin_embed_tokens_bwd", stream(), ptr(tok), ptr(dqf), B, Nq, ctx.V, E, ptr(dtable), ptr(ws), ws.numel())
+        return None, dtable, None
+
+
+EMBED_BWD_MAX = 4096                 # B * Nq of one differentiable embed_tokens call (the backward sorts the positions in one workgroup)
+
+
+def embed_tokens(tokens, table, pad_id=None, differentiable=False):
     """Query word vectors from token ids on the device (dataset.py:32-38, 173).  ``tokens`` (B, Nq) integer HIP tensor, ``table``
     (V, E) float32 HIP tensor (E % 4 == 0), ``pad_id`` default ``V - 1`` (the reference's ``<pad>``, appended last).
 
     Returns ``(query_features (B, Nq, E) float32 = table[tokens], query_mask (B, Nq) uint8 = tokens < pad_id, qlen (B,) int32 = sum
-    of the mask)``.  An id outside ``[0, V)`` gives a zero row and mask 0; it is never read."""
+    of the mask)``.  An id outside ``[0, V)`` gives a zero row and mask 0; it is never read.
+    ``differentiable=True``: when ``table`` requires grad under grad mode, ``query_features`` carries an autograd node whose backward
+    forms the dense ``table.grad`` (as ``nn.Embedding(sparse=False)``): row ``v`` = the sum of the gradient rows at the positions
+    holding ``v``, in ascending ``(b, w)`` order, other rows 0; ``B * Nq <= 4096``.  Default: ``table`` is detached."""
     from ._lib import SminHipError, call, ptr, stream
     if not (tokens.is_cuda and table.is_cuda):
         raise SminHipError("embed_tokens runs on a HIP device only (got a CPU tensor); there is no CPU fallback")
@@ -193,10 +272,16 @@ def embed_tokens(tokens, table, pad_id=None):
     (B, Nq), (V, E) = tokens.shape, table.shape
     pad_id = V - 1 if pad_id is None else int(pad_id)
     tok = tokens.to(torch.int32).contiguous()
-    tab = table.detach().float().contiguous()
+    grad = differentiable and table.requires_grad and torch.is_grad_enabled()
+    tab = (table if grad else table.detach()).float().contiguous()
     if tab.data_ptr() % 16:
         tab = tab.clone()
     dev = tokens.device
+    if grad:
+        if B * Nq > EMBED_BWD_MAX:
+            raise ValueError(f"embed_tokens(differentiable=True): B * Nq = {B * Nq} positions, at most {EMBED_BWD_MAX} per call")
+        with torch.cuda.device(dev):
+            return _EmbedTokensFn.apply(tok, tab, pad_id)
     qf = torch.empty((B, Nq, E), dtype=torch.float32, device=dev)
     qm = torch.empty((B, Nq), dtype=torch.uint8, device=dev)
     ql = torch.empty((B,), dtype=torch.int32, device=dev)
