@@ -39,7 +39,9 @@ extern "C" {
 /* additions within 2 (new entry points only; no existing signature or behaviour changed, so a caller built against 2 is unaffected
  * and the number stays): gradients of the model's inputs -- smin_video_encoder_bwd_input (dx of the video features from the inputs
  * half's workspace), smin_sample_clips_bwd, smin_embed_tokens_bwd and smin_embed_tokens_bwd_workspace_bytes (deterministic backward
- * passes of the device feeding path) */
+ * passes of the device feeding path); long-video retrieval over overlapping windows -- smin_sample_windows (clip resampling of
+ * arbitrary, possibly overlapping row ranges), smin_merge_window_moments (greedy NMS of per-window top-k moments in absolute
+ * time), and a masks-only use of smin_build_targets (sm == NULL) */
 #define SMIN_HIP_ABI_VERSION 2
 
 int smin_abi_version(void);
@@ -235,6 +237,8 @@ int smin_build_targets(void* stream, const float* times, const float* duration, 
                        float* ss, uint8_t* ys, float* se, uint8_t* ye, uint8_t* ya,
                        const float* two_sigma_sq /* [B] or NULL: 2 sigma^2 of the boundary Gaussians as computed in double from the unrounded
                                                     annotation times (dataset.py:116-119); NULL: formed in double from the fp32 times */);
+/* masks only: with sm == NULL (and ym, ss, ys, se, ye, ya NULL as well) only video_mask, query_mask, length_mask and moment_mask are
+ * written; times, duration and two_sigma_sq are not read and may be NULL. */
 
 /* ---- clip resampling of raw per-video features (reference dataset.py:40-74, AbstractDataset.get_fixed_length_features, per
  * sample in numpy on the host there; csrc/sampling.hip).  raw [sum n_b][Din] (16-byte aligned), offsets [B+1] int64: sample b owns
@@ -255,6 +259,12 @@ int smin_sample_clips(void* stream, const float* raw, const int64_t* offsets, co
  * (no atomics); 16-byte aligned dout / draw. */
 int smin_sample_clips_bwd(void* stream, const float* dout, const int64_t* offsets, const int32_t* spos, int B, int T, int Din, int mode,
                           int64_t rows, float* draw);
+/* clip resampling of arbitrary row ranges (the windows of a long video): output sample w owns raw rows row_begin[w] ..
+ * row_begin[w] + len[w] (int64 / int32 [W]; ranges may overlap and repeat, nothing is copied) and is exactly what smin_sample_clips
+ * gives for a sample owning those rows with spos = 0, in either mode.  video_features [W][T][Din], nfeats [W] = min(len, T).  The
+ * ranges must lie within raw (not checked).  Requires Din % 4 == 0, W <= 65535; no host read; W = 0 is a no-op. */
+int smin_sample_windows(void* stream, const float* raw, const int64_t* row_begin, const int32_t* len, int W, int T, int Din, int mode,
+                        float* video_features, int32_t* nfeats);
 
 /* ---- query word vectors from token ids (reference dataset.py:32-38 get_query_features, dataset.py:173 query mask).
  * tokens [B][Nq] int32, table [V][E] (e.g. GloVe with <unk> and <pad> appended; 16-byte aligned, E % 4 == 0).
@@ -289,6 +299,26 @@ int smin_compute_ious(void* stream, const float* pm, const float* ps, const floa
 size_t smin_top_moments_ws_bytes(int B, int L, int k);
 int smin_top_moments(void* stream, const float* pm, const float* ps, const float* pe, const uint8_t* mm, int B, int L, int k,
                      float nms_thresh, long long* idx, float* score, int* count, void* ws, size_t ws_bytes);
+
+/* ---- merge of per-window top-k moments across the windows of a long video (csrc/moments.hip; SMIN.localize_windows).
+ * Inputs: smin_top_moments' outputs of G windows at k_window: idx [G][k_window][2] int64, score [G][k_window], count [G]; each
+ * window's first raw row start [G] int64 (relative to its video) and row count len [G] int32; pair_ptr [B+1] int64: pair b owns
+ * windows pair_ptr[b] .. pair_ptr[b+1] (ordinal g - pair_ptr[b] within the pair).  All arithmetic fp32, in this order:
+ *   span of kept cell (i, j) of window (s, len), in raw rows:  u = (float)max(len, T) / (float)L;  st = (float)s + (float)i * u;
+ *     en = fminf((float)s + (float)(j + 1) * u, (float)(s + len))   (each operation rounded once, no contraction);
+ *   candidates of pair b: the first count[g] slots of each of its windows;
+ *   order: higher score first (-0 equals +0), ties -> lower window ordinal, then lower slot;
+ *   IoU of two spans: inter = fmaxf(0, fminf(en1, en2) - fmaxf(st1, st2)), uni = fmaxf(en1, en2) - fminf(st1, st2),
+ *     iou = inter / uni (one correctly rounded division);
+ *   greedy NMS: walk the candidates in order, keep one unless its IoU with a kept one is > nms_thresh; stop after k kept.
+ *     nms_thresh >= 1: no suppression.
+ * Outputs: span [B][k][2] fp32 (NaN for empty slots), out_score [B][k] (the candidate's score; 0), window [B][k] int64 (ordinal
+ * within the pair; -1), cell [B][k][2] int64 ((i, j); -1), out_count [B] (kept).
+ * Limits: 1 <= k, k_window <= 64, G * k_window < 2^31, T >= 1, L >= 1 (else a negative code, nothing launched); B = 0 is a no-op;
+ * pointers may be NULL only for B = 0 (inputs: for G = 0).  Deterministic, no scratch, no host synchronisation. */
+int smin_merge_window_moments(void* stream, const int64_t* idx, const float* score, const int32_t* count, const int64_t* start,
+                              const int32_t* len, const int64_t* pair_ptr, int G, int B, int T, int L, int k_window, int k,
+                              float nms_thresh, float* span, float* out_score, int64_t* window, int64_t* cell, int32_t* out_count);
 
 /* ---- R@n, IoU=m over the NMS-kept moments: the top-k moments above with k = max(n_list), then for each pair (a, c)
  * counts[a * nm + c] = number of samples with sm[b] > m_list[c] at any of the first n_list[a] kept cells (an empty slot

@@ -55,12 +55,14 @@ SIGNATURES = {
     "smin_compute_ious": [_vp] * 6 + [_i] * 2 + [_vp] * 2,
     "smin_top_moments_ws_bytes": [_i] * 3,
     "smin_top_moments": [_vp] * 5 + [_i] * 3 + [_f] + [_vp] * 4 + [_sz],
+    "smin_merge_window_moments": [_vp] * 7 + [_i] * 6 + [_f] + [_vp] * 5,
     "smin_compute_ious_nms_ws_bytes": [_i] * 5,
     "smin_compute_ious_nms": [_vp] * 6 + [_i] * 3 + [_f, _vp, _i, _vp, _i] + [_vp, _vp, _sz],
     "smin_build_targets": [_vp] * 5 + [_i] * 4 + [_vp] * 12,
     "smin_sample_clips": [_vp] * 4 + [_i] * 4 + [_vp] * 2,
     "smin_embed_tokens": [_vp] * 3 + [_i] * 5 + [_vp] * 3,
     "smin_sample_clips_bwd": [_vp] * 4 + [_i] * 4 + [ctypes.c_int64, _vp],
+    "smin_sample_windows": [_vp] * 4 + [_i] * 4 + [_vp] * 2,
     "smin_embed_tokens_bwd_workspace_bytes": [_i, _i],
     "smin_embed_tokens_bwd": [_vp] * 3 + [_i] * 4 + [_vp, _vp, _sz],
     "smin_word_prep_fwd": [_vp] * 5 + [_i] * 5 + [_vp] * 5,

@@ -4,7 +4,8 @@
 //   sm [B][L][L] = IoU of the window (snippet i .. snippet j) with the ground truth, ym = sm > 0.5      (dataset.py:95-110, 151)
 //   ss, se [B][L] = unnormalised Gaussians around the true boundaries, sigma = (te - ts) / 5; ys, ye    (dataset.py:112-120, 154-155)
 //   ya [B][L] = snippet fully inside the ground-truth window                                            (dataset.py:122-126)
-// so that a data-parallel job ships features and five scalars per sample instead of eleven tensors.  fp32 arithmetic in the
+// so that a data-parallel job ships features and five scalars per sample instead of eleven tensors.  With sm == NULL (and the other
+// targets NULL) only the masks are written, and times / duration are not read (SMIN.localize_windows builds its windows' masks so).  fp32 arithmetic in the
 // reference's order of operations (s_i = i * dur / L, e_j = (j + 1) * dur / L).
 #include "common.h"
 #include "smin_hip.h"
@@ -18,11 +19,17 @@ void build_targets_kernel(const float* __restrict__ times, const float* __restri
                           float* __restrict__ se, uint8_t* __restrict__ ye, uint8_t* __restrict__ ya, const float* __restrict__ two_sigma_sq)
 {
     const int b = blockIdx.y;
-    const float ts = times[2 * b], te = times[2 * b + 1], dur = duration[b], Lf = (float)L;
+    const bool targets = sm != nullptr;                                     // NULL: the masks only (nothing of the annotation is read)
+    const float ts = targets ? times[2 * b] : 0.f, te = targets ? times[2 * b + 1] : 0.f, dur = targets ? duration[b] : 0.f, Lf = (float)L;
     const int nf = min(nfeats[b], T);
     const int n_len = (int)ceil((double)nf / ((double)T / (double)L));      // dataset.py:145: ceil(nfeats / (T / L))
     const int k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k < L * L) {
+        const int i = k / L, j = k - i * L;
+        const size_t o = (size_t)b * L * L + k;
+        moment_mask[o] = (j >= i) && i < n_len && j < n_len;
+    }
+    if (targets && k < L * L) {
         const int i = k / L, j = k - i * L;
         const float s_i = (float)i * dur / Lf, e_j = ((float)j + 1.0f) * dur / Lf;
         const float inter = fmaxf(0.0f, fminf(e_j, te) - fmaxf(s_i, ts));
@@ -31,9 +38,9 @@ void build_targets_kernel(const float* __restrict__ times, const float* __restri
         const size_t o = (size_t)b * L * L + k;
         sm[o] = iou;
         ym[o] = iou > 0.5f;
-        moment_mask[o] = (j >= i) && i < n_len && j < n_len;
     }
-    if (k < L) {
+    if (k < L) length_mask[(size_t)b * L + k] = k < n_len;
+    if (targets && k < L) {
         const float s_t = (float)k * dur / Lf, e_t = ((float)k + 1.0f) * dur / Lf;
         // dataset.py:116-119 forms sigma = (te - ts) / 5 and 2 sigma^2 in Python doubles from the annotation times and rounds once, at the
         // tensor division: a caller that still has those doubles hands the rounded denominator in (two_sigma_sq); otherwise it is
@@ -46,7 +53,6 @@ void build_targets_kernel(const float* __restrict__ times, const float* __restri
         ss[o] = vs; ys[o] = vs > 0.5f;
         se[o] = ve; ye[o] = ve > 0.5f;
         ya[o] = (s_t >= ts) && (e_t <= te);
-        length_mask[o] = k < n_len;
     }
     for (int t = k; t < T; t += gridDim.x * blockDim.x) video_mask[(size_t)b * T + t] = t < nf;
     if (query_mask) for (int w = k; w < Nq; w += gridDim.x * blockDim.x) query_mask[(size_t)b * Nq + w] = w < qlen[b];
@@ -59,6 +65,7 @@ extern "C" int smin_build_targets(void* stream, const float* times, const float*
                                   float* ss, uint8_t* ys, float* se, uint8_t* ye, uint8_t* ya, const float* two_sigma_sq)
 {
     SMIN_REQUIRE(B >= 0 && T >= 1 && L >= 1 && T % L == 0 && (query_mask == nullptr || (qlen != nullptr && Nq >= 1)));
+    SMIN_REQUIRE(sm != nullptr || (ym == nullptr && ss == nullptr && ys == nullptr && se == nullptr && ye == nullptr && ya == nullptr));
     if (B == 0) return 0;
     hipLaunchKernelGGL(smin::build_targets_kernel, dim3(cdiv(L * L, 256), B), dim3(256), 0, (hipStream_t)stream, times, duration, nfeats, qlen, T, L, Nq,
                        video_mask, query_mask, length_mask, moment_mask, sm, ym, ss, ys, se, ye, ya, two_sigma_sq);

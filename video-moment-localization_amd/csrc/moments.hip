@@ -413,6 +413,106 @@ int launch_top(hipStream_t st, const float* pm, const float* ps, const float* pe
     return 0;
 }
 
+
+// ---- cross-window merge (smin_merge_window_moments): one workgroup per pair, k rounds of "the best candidate that no kept span
+// suppresses" (a block argmax of order keys strictly below the previous pick), the kept spans in LDS.  Suppression only grows
+// with the kept set, so round r's pick is the r-th moment the greedy walk keeps; no sort, no atomics, any candidate count.
+
+struct MergeIn {
+    const long long* idx; const float* score; const int* count; const long long* start; const int* len;
+    int G, T, L, kw;
+};
+
+// span in raw rows of cell (i, j) of window g (include/smin_hip.h, in this order, fp32; contraction off: a product and a sum are
+// rounded one by one, never fused into an fma)
+__device__ __forceinline__ void window_span(const MergeIn& in, int g, long long i, long long j, float& st, float& en)
+{
+#pragma clang fp contract(off)
+    const long long s = in.start[g];
+    const int n = in.len[g];
+    const float u = (float)max(n, in.T) / (float)in.L;
+    st = (float)s + (float)i * u;
+    en = fminf((float)s + (float)(j + 1) * u, (float)(s + n));
+}
+
+__device__ __forceinline__ bool span_suppressed(float st, float en, const float* kst, const float* ken, int nk, float thr)
+{
+    for (int r = 0; r < nk; ++r) {
+        const float inter = fmaxf(0.f, fminf(en, ken[r]) - fmaxf(st, kst[r]));
+        const float uni = fmaxf(en, ken[r]) - fminf(st, kst[r]);
+        if (inter / uni > thr) return true;
+    }
+    return false;
+}
+
+__device__ __forceinline__ u64 block_max(u64 v, u64* red)
+{
+    for (int o = 32; o >= 1; o >>= 1) {
+        const u64 x = __shfl_xor(v, o);
+        v = x > v ? x : v;
+    }
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    u64 m = red[0];
+#pragma unroll
+    for (int w = 1; w < MT / 64; ++w) m = red[w] > m ? red[w] : m;
+    return m;
+}
+
+__global__ __launch_bounds__(MT)
+void merge_windows_kernel(MergeIn in, const long long* __restrict__ pair_ptr, int k, float thr,
+                          float* __restrict__ span /* [B][k][2] */, float* __restrict__ out_score /* [B][k] */,
+                          long long* __restrict__ window /* [B][k] */, long long* __restrict__ cell /* [B][k][2] */, int* __restrict__ out_count)
+{
+    __shared__ float kst[MAX_K], ken[MAX_K];
+    __shared__ u64 red[MT / 64];
+    const int b = blockIdx.x, t = threadIdx.x, kw = in.kw;
+    const long long g0 = min(max(pair_ptr[b], 0LL), (long long)in.G);
+    const long long g1 = min(max(pair_ptr[b + 1], g0), (long long)in.G);
+    const int nslot = (int)(g1 - g0) * kw;                       // candidate q = window ordinal * kw + slot (< 2^31: checked on the host)
+    u64 cursor = ~0ull;
+    int nk = 0;
+    for (; nk < k; ++nk) {
+        u64 best = 0;
+        for (int q = t; q < nslot; q += MT) {
+            const int w = q / kw, slot = q - w * kw;
+            const long long g = g0 + w;
+            if (slot >= in.count[g]) continue;
+            const u64 key = make_key(score_ord(in.score[g * kw + slot]), q);
+            if (key >= cursor || key <= best) continue;
+            float st, en;
+            window_span(in, (int)g, in.idx[2 * (g * kw + slot)], in.idx[2 * (g * kw + slot) + 1], st, en);
+            if (!span_suppressed(st, en, kst, ken, nk, thr)) best = key;
+        }
+        best = block_max(best, red);
+        if (best == 0) break;                                    // every candidate is taken or suppressed
+        cursor = best;
+        if (t == 0) {
+            const int q = key_cell(best), w = q / kw, slot = q - w * kw;
+            const long long g = g0 + w, c = g * kw + slot;
+            const long long i = in.idx[2 * c], j = in.idx[2 * c + 1];
+            float st, en;
+            window_span(in, (int)g, i, j, st, en);
+            kst[nk] = st; ken[nk] = en;
+            const size_t o = (size_t)b * k + nk;
+            span[2 * o] = st; span[2 * o + 1] = en;
+            out_score[o] = in.score[c];
+            window[o] = w;
+            cell[2 * o] = i; cell[2 * o + 1] = j;
+        }
+        __syncthreads();
+    }
+    for (int r = nk + t; r < k; r += MT) {
+        const size_t o = (size_t)b * k + r;
+        span[2 * o] = span[2 * o + 1] = __int_as_float(0x7fc00000);
+        out_score[o] = 0.f;
+        window[o] = -1;
+        cell[2 * o] = cell[2 * o + 1] = -1;
+    }
+    if (t == 0) out_count[b] = nk;
+}
+
 }  // namespace
 }  // namespace smin
 
@@ -462,6 +562,22 @@ extern "C" int smin_compute_ious_nms(void* stream, const float* pm, const float*
     hipLaunchKernelGGL(moments_hits_kernel, dim3(B), dim3(MT), 0, st, idx, sm, L, k, pr, hits);
     SMIN_LAUNCH_CHECK();
     hipLaunchKernelGGL(moments_hits_sum_kernel, dim3((npairs + 63) / 64), dim3(64), 0, st, hits, B, npairs, counts);
+    SMIN_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int smin_merge_window_moments(void* stream, const int64_t* idx, const float* score, const int32_t* count, const int64_t* start,
+                                         const int32_t* len, const int64_t* pair_ptr, int G, int B, int T, int L, int k_window, int k,
+                                         float nms_thresh, float* span, float* out_score, int64_t* window, int64_t* cell, int32_t* out_count)
+{
+    SMIN_REQUIRE(k >= 1 && k <= MAX_K && k_window >= 1 && k_window <= MAX_K && G >= 0 && B >= 0 && T >= 1 && L >= 1);
+    SMIN_REQUIRE((long long)G * k_window < 0x7fffffffLL);
+    if (B == 0) return 0;
+    SMIN_REQUIRE(pair_ptr != nullptr && span != nullptr && out_score != nullptr && window != nullptr && cell != nullptr && out_count != nullptr);
+    SMIN_REQUIRE(G == 0 || (idx != nullptr && score != nullptr && count != nullptr && start != nullptr && len != nullptr));
+    const MergeIn in{(const long long*)idx, score, count, (const long long*)start, len, G, T, L, k_window};
+    hipLaunchKernelGGL(merge_windows_kernel, dim3(B), dim3(MT), 0, (hipStream_t)stream, in, (const long long*)pair_ptr, k, nms_thresh, span,
+                       out_score, (long long*)window, (long long*)cell, out_count);
     SMIN_LAUNCH_CHECK();
     return 0;
 }

@@ -10,6 +10,8 @@
 //   mean (mode 1, spos = 0): n <= T as pick; n > T: out[b, t] = mean of raw rows [a_t, a_{t+1}), a_t = rint(t * n / T) in double,
 //     a_T = n; fp32 sum in ascending row order, then one fp32 division by the row count.
 //   rows t >= min(n, T) are zero.  Memory: one copy (pick) or one streaming read (mean); float4 along Din, 64-bit addressing.
+// smin_sample_windows -- the same kernel (a template on how a sample finds its rows) for samples that each own an arbitrary row
+//   range row_begin[w] .. row_begin[w] + len[w] of raw (ranges may overlap or repeat; nothing is copied); spos = 0 (eval split).
 // smin_embed_tokens -- out[b, w] = table[tokens[b, w]] (zero row for an id outside [0, V)), mask = 0 <= id < pad_id, qlen = sum mask.
 // Backward (deterministic, no atomics): smin_sample_clips_bwd gives each raw row the sum, in ascending t, of the output rows that read it
 // (pick) or its window's output row over the window's row count (mean); smin_embed_tokens_bwd sorts the (id, position) pairs of the
@@ -21,15 +23,36 @@ namespace smin {
 
 constexpr int SAMPLE_ROWS = 16;          // output rows per workgroup
 
+// How output sample b finds its raw rows: base = its first row, n = its row count.
+struct OffsetRows {                      // smin_sample_clips: consecutive samples, rows offsets[b] .. offsets[b+1]
+    const long long* offsets;
+    __device__ __forceinline__ void operator()(int b, long long& base, long long& n) const
+    {
+        base = offsets[b];
+        n = max(offsets[b + 1] - base, 0LL);
+    }
+};
+
+struct RangeRows {                       // smin_sample_windows: rows begin[b] .. begin[b] + len[b] (ranges may overlap and repeat)
+    const long long* begin;
+    const int* len;
+    __device__ __forceinline__ void operator()(int b, long long& base, long long& n) const
+    {
+        base = begin[b];
+        n = max((long long)len[b], 0LL);
+    }
+};
+
+template <typename Rows>
 __global__ __launch_bounds__(256)
-void sample_clips_kernel(const float* __restrict__ raw, const long long* __restrict__ offsets, const int* __restrict__ spos_in, int mode,
+void sample_clips_kernel(const float* __restrict__ raw, Rows rows_of, const int* __restrict__ spos_in, int mode,
                          int T, int D4, float* __restrict__ out, int* __restrict__ nfeats)
 {
     __shared__ long long s_first[SAMPLE_ROWS];    // first raw row (absolute) of output row t, or -1: a zero row
     __shared__ int s_count[SAMPLE_ROWS];          // rows averaged (1 = a copy)
     const int b = blockIdx.y, t0 = blockIdx.x * SAMPLE_ROWS;
-    const long long base = offsets[b];
-    const long long n = max(offsets[b + 1] - base, 0LL);
+    long long base, n;
+    rows_of(b, base, n);
     const int nf = (int)min(n, (long long)T);
     if (threadIdx.x < SAMPLE_ROWS) {
         const int t = t0 + threadIdx.x;
@@ -260,8 +283,21 @@ extern "C" int smin_sample_clips(void* stream, const float* raw, const int64_t* 
     SMIN_REQUIRE(B >= 0 && B <= 65535 && T >= 1 && Din >= 4 && Din % 4 == 0 && (mode == 0 || (mode == 1 && spos == nullptr)));
     SMIN_REQUIRE(((uintptr_t)raw & 15) == 0 && ((uintptr_t)video_features & 15) == 0);
     if (B == 0) return 0;
-    hipLaunchKernelGGL(smin::sample_clips_kernel, dim3(cdiv(T, smin::SAMPLE_ROWS), B), dim3(256), 0, (hipStream_t)stream, raw,
-                       (const long long*)offsets, spos, mode, T, Din / 4, video_features, nfeats);
+    hipLaunchKernelGGL(smin::sample_clips_kernel<smin::OffsetRows>, dim3(cdiv(T, smin::SAMPLE_ROWS), B), dim3(256), 0, (hipStream_t)stream, raw,
+                       smin::OffsetRows{(const long long*)offsets}, spos, mode, T, Din / 4, video_features, nfeats);
+    SMIN_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int smin_sample_windows(void* stream, const float* raw, const int64_t* row_begin, const int32_t* len, int W, int T, int Din, int mode,
+                                   float* video_features, int32_t* nfeats)
+{
+    SMIN_REQUIRE(W >= 0 && W <= 65535 && T >= 1 && Din >= 4 && Din % 4 == 0 && (mode == 0 || mode == 1));
+    SMIN_REQUIRE(((uintptr_t)raw & 15) == 0 && ((uintptr_t)video_features & 15) == 0);
+    if (W == 0) return 0;
+    SMIN_REQUIRE(raw != nullptr && row_begin != nullptr && len != nullptr && video_features != nullptr && nfeats != nullptr);
+    hipLaunchKernelGGL(smin::sample_clips_kernel<smin::RangeRows>, dim3(cdiv(T, smin::SAMPLE_ROWS), W), dim3(256), 0, (hipStream_t)stream, raw,
+                       smin::RangeRows{(const long long*)row_begin, len}, nullptr, mode, T, Din / 4, video_features, nfeats);
     SMIN_LAUNCH_CHECK();
     return 0;
 }

@@ -51,6 +51,22 @@ def build_targets_hip(times, duration, nfeats, qlen, T, L, Nq, stream=None):
     return out
 
 
+def build_masks_hip(nfeats, T, L):
+    """The masks of build_targets_hip alone (smin_build_targets with no targets): nfeats (B,) device int -> dict video_mask uint8
+    (B, T, 1), length_mask bool (B, L), moment_mask bool (B, L, L).  No annotation is needed; no host read."""
+    if not nfeats.is_cuda:
+        raise _lib.SminHipError("build_masks_hip runs on a HIP device only (got a CPU tensor); there is no CPU fallback")
+    dev, B = nfeats.device, nfeats.shape[0]
+    out = dict(video_mask=torch.empty((B, T, 1), dtype=torch.uint8, device=dev), length_mask=torch.empty((B, L), dtype=torch.uint8, device=dev),
+               moment_mask=torch.empty((B, L, L), dtype=torch.uint8, device=dev))
+    nf = nfeats.to(torch.int32).contiguous()
+    with torch.cuda.device(dev):
+        call("smin_build_targets", _lib.stream(), None, None, ptr(nf), None, B, T, L, 1, ptr(out["video_mask"]), None, ptr(out["length_mask"]),
+             ptr(out["moment_mask"]), *([None] * 8))
+    out["length_mask"], out["moment_mask"] = out["length_mask"].view(torch.bool), out["moment_mask"].view(torch.bool)
+    return out
+
+
 class BatchFeeder:
     """Double-buffered host -> device feeder.  ``feed(sample_batches)`` takes an iterable of host batches
     ``dict(video_features (B,T,Din) float32, query_features (B,Nq,300) float32, nfeats (B,), qlen (B,), times (B,2), duration (B,))``

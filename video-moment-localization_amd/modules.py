@@ -17,6 +17,7 @@ import math
 
 import os
 
+import numpy as np
 import torch
 import torch.nn as nn
 
@@ -642,6 +643,109 @@ class SMIN(nn.Module):
             if attention:
                 r["content_attention"], r["boundary_attention"] = attn_maps_gather([c for c, _ in maps], [b for _, b in maps], maps.cellmap,
                                                                                    r["idx"], self.C)
+        return r
+
+    def localize_windows(self, raw, lengths, query_features, query_mask, video_index=None, window=None, stride=None, k=5, k_window=None,
+                         nms_thresh=0.5, mode="pick", duration=None, max_batch=64):
+        """The k best moments of (video, query) pairs over videos of any length: overlapping windows of ``window`` raw rows (default
+        T: one row per clip) every ``stride`` rows (default window // 2) are each resampled to T clips, scored by the model and cut to
+        their ``k_window`` (default k) best moments, which are then merged per pair by greedy NMS in raw-row time.
+
+        ``raw`` (R, Din) HIP float32 tensor of V videos' rows back to back, ``lengths`` their V row counts (host); ``query_features``
+        (B, Nq, E) / ``query_mask`` the B pairs' queries, ``video_index`` (B,) host ints (default arange(V), B == V) maps a pair to
+        its video (the rows are not copied per pair).  Windows are processed in chunks of ``max_batch``: sample_windows, the masks
+        from nfeats, one forward under no_grad, top_moments; then one merge (moments.merge_window_moments).  The plan is host
+        arithmetic, so each chunk's valid-cell count is handed to the forward (``known_cell_count``) and nothing is read back.
+
+        Returns a dict: ``span`` (B, k, 2) float32 raw rows of the video (NaN for empty slots), ``score`` (B, k), ``window`` (B, k)
+        int64 window ordinal within the pair (-1), ``cell`` (B, k, 2) int64 cell of that window (-1), ``count`` (B,) int32 and
+        ``n_windows`` (B,) int64; with ``duration`` (B,) seconds also ``times`` = (span * duration) / n (fp32; n = the video's rows)."""
+        from .moments import MAX_K, merge_window_moments
+        from .sampling import MAX_ROWS, MODES, sample_windows, window_plan
+        from .feeder import build_masks_hip
+        from . import _lib
+        T, L = self.T, self.L
+        k_window = k if k_window is None else k_window
+        window = T if window is None else window
+        stride = max(int(window) // 2, 1) if stride is None else stride
+        for name, v, lo, hi in (("k", k, 1, MAX_K), ("k_window", k_window, 1, MAX_K), ("window", window, 1, MAX_ROWS),
+                                ("stride", stride, 1, MAX_ROWS), ("max_batch", max_batch, 1, 65535)):
+            if not (isinstance(v, (int, np.integer)) and lo <= v <= hi):
+                raise ValueError(f"localize_windows: {name} must be an integer in [{lo}, {hi}] (got {v!r})")
+        if mode not in MODES:
+            raise ValueError(f"localize_windows: mode must be one of {sorted(MODES)} (got {mode!r})")
+        for name, t in (("raw", raw), ("query_features", query_features), ("query_mask", query_mask)):
+            if not (isinstance(t, torch.Tensor) and t.is_cuda):
+                raise SminHipError(f"localize_windows: {name} must be a HIP tensor (there is no CPU fallback)")
+        if raw.dim() != 2 or raw.dtype != torch.float32 or raw.shape[1] % 4 != 0 or raw.shape[1] != self.input_video_dim:
+            raise ValueError(f"localize_windows: raw must be float32 (R, Din = {self.input_video_dim}) with Din % 4 == 0 (got "
+                             f"{tuple(raw.shape)} {raw.dtype})")
+        n = np.asarray(lengths.cpu() if isinstance(lengths, torch.Tensor) else lengths, dtype=np.int64).reshape(-1)
+        if n.size and n.min() < 0 or int(n.sum()) != raw.shape[0]:
+            raise ValueError(f"localize_windows: lengths must be >= 0 and sum to raw's {raw.shape[0]} rows (got {int(n.sum())})")
+        V, B = n.shape[0], query_features.shape[0]
+        if video_index is None:
+            if B != V:
+                raise ValueError(f"localize_windows: without video_index the B = {B} queries pair with the V = {V} videos one to one")
+            vi = np.arange(V, dtype=np.int64)
+        else:
+            vi = np.asarray(video_index.cpu() if isinstance(video_index, torch.Tensor) else video_index, dtype=np.int64).reshape(-1)
+            if vi.shape[0] != B or (B and (vi.min() < 0 or vi.max() >= V)):
+                raise ValueError(f"localize_windows: video_index must hold B = {B} indices in [0, {V}) (got {vi.tolist()[:8]})")
+        if query_mask.shape[0] != B:
+            raise ValueError(f"localize_windows: query_mask has {query_mask.shape[0]} rows for B = {B} queries")
+        if duration is not None and tuple(duration.shape) != (B,):
+            raise ValueError(f"localize_windows: duration must be (B,) = ({B},) seconds (got {tuple(duration.shape)})")
+        starts, lens, vptr = (x.numpy() for x in window_plan(n, window, stride))
+        dev = raw.device
+        # per pair: its video's windows, in global window order (pair, then start)
+        nw = (vptr[1:] - vptr[:-1])[vi] if B else np.zeros(0, np.int64)
+        pair_ptr = np.concatenate([[0], np.cumsum(nw)]).astype(np.int64)
+        G = int(pair_ptr[-1])
+        if G * k_window >= 2 ** 31:
+            raise ValueError(f"localize_windows: {G} windows of {k_window} moments exceed the merge's 2**31 candidates")
+        wsel = np.concatenate([np.arange(vptr[v], vptr[v + 1]) for v in vi]).astype(np.int64) if G else np.zeros(0, np.int64)
+        offs = np.concatenate([[0], np.cumsum(n)]).astype(np.int64)
+        pair_of = np.repeat(np.arange(B, dtype=np.int64), nw)
+        w_start, w_len = starts[wsel], lens[wsel].astype(np.int64)
+        nf = np.minimum(w_len, T)
+        n_len = np.array([math.ceil(int(x) / (T / L)) for x in nf], dtype=np.int64)              # as csrc/labels.hip forms it
+        cells = n_len * (n_len + 1) // 2
+        # the whole plan in one pinned buffer, one asynchronous copy (the call never waits for the device)
+        host = np.concatenate([offs[vi[pair_of]] + w_start if G else np.zeros(0, np.int64), w_start, w_len, pair_of, pair_ptr, nw,
+                               n[vi]]).astype(np.int64)
+        plan = torch.from_numpy(host).pin_memory().to(dev, non_blocking=True)
+        cut = np.cumsum([0, G, G, G, G, B + 1, B, B])
+        rb_d, st_d, ln_d, po_d, pp_d, nw_d, nr_d = (plan[cut[q]:cut[q + 1]] for q in range(7))
+        ln_d = ln_d.to(torch.int32)
+        idx = torch.empty((G, k_window, 2), dtype=torch.int64, device=dev)
+        score = torch.empty((G, k_window), dtype=torch.float32, device=dev)
+        count = torch.empty((G,), dtype=torch.int32, device=dev)
+        known = self.known_cell_count
+        try:
+            with torch.no_grad(), torch.cuda.device(dev):
+                for c0 in range(0, G, max_batch):
+                    c1 = min(c0 + max_batch, G)
+                    g = c1 - c0
+                    vf, nfeats = sample_windows(raw, rb_d[c0:c1], ln_d[c0:c1], T, mode=mode)
+                    m = build_masks_hip(nfeats, T, L)
+                    rows = po_d[c0:c1]
+                    qf, qm = query_features.index_select(0, rows), query_mask.index_select(0, rows)
+                    self.known_cell_count = int(cells[c0:c1].sum())
+                    pm, ps, pe, _ = self(vf, m["video_mask"], qf, qm, m["length_mask"], m["moment_mask"])
+                    mm = m["moment_mask"]
+                    nbytes = _lib.load().smin_top_moments_ws_bytes(g, L, k_window)
+                    ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+                    _lib.call("smin_top_moments", _lib.stream(), _lib.ptr(pm.contiguous()), _lib.ptr(ps.contiguous()), _lib.ptr(pe.contiguous()),
+                              _lib.ptr(mm), g, L, k_window, float(nms_thresh), _lib.ptr(idx[c0:c1]), _lib.ptr(score[c0:c1]),
+                              _lib.ptr(count[c0:c1]), _lib.ptr(ws), nbytes)
+        finally:
+            self.known_cell_count = known
+        r = merge_window_moments(idx, score, count, st_d, ln_d, pp_d, T, L, k=k, nms_thresh=nms_thresh)
+        r["n_windows"] = nw_d
+        if duration is not None:
+            d = duration.to(device=dev, dtype=torch.float32).reshape(B, 1, 1)
+            r["times"] = (r["span"] * d) / nr_d.to(torch.float32).reshape(B, 1, 1)
         return r
 
     def _stream_ok(self):

@@ -185,3 +185,118 @@ def compute_ious_nms_torch(pm, ps, pe, moment_mask, sm, n, m, nms_thresh):
     ious = torch.where(flat >= 0, ious, torch.zeros_like(ious))
     counts = torch.stack([((ious[:, :n_] > m_).sum(dim=1) > 0).sum() for n_ in n for m_ in m]).tolist()
     return {k_: float(v) for k_, v in zip(keys, counts)}
+
+
+# ---------------------------------------------------------------- merge across the windows of long videos (SMIN.localize_windows)
+def _merge_check(idx, score, count, start, lens, pair_ptr, T, L, k):
+    if idx.dim() != 3 or idx.shape[2] != 2:
+        raise ValueError(f"merge_window_moments: idx must be (G, k_window, 2), got {tuple(idx.shape)}")
+    G, kw = idx.shape[0], idx.shape[1]
+    if tuple(score.shape) != (G, kw) or tuple(count.shape) != (G,) or tuple(start.shape) != (G,) or tuple(lens.shape) != (G,):
+        raise ValueError(f"merge_window_moments: score must be (G, k_window) = {(G, kw)}, count / start / lens (G,); got "
+                         f"{tuple(score.shape)}, {tuple(count.shape)}, {tuple(start.shape)}, {tuple(lens.shape)}")
+    if pair_ptr.dim() != 1 or pair_ptr.shape[0] < 1:
+        raise ValueError("merge_window_moments: pair_ptr must be (B + 1,)")
+    if not (isinstance(k, int) and 1 <= k <= MAX_K) or not 1 <= kw <= MAX_K:
+        raise ValueError(f"merge_window_moments needs integers 1 <= k, k_window <= {MAX_K} (got k={k!r}, k_window={kw})")
+    if int(T) < 1 or int(L) < 1 or G * kw >= 2 ** 31:
+        raise ValueError(f"merge_window_moments needs T >= 1, L >= 1 and G * k_window < 2**31 (T={T}, L={L}, G={G}, k_window={kw})")
+    return G, kw, pair_ptr.shape[0] - 1
+
+
+def merge_window_moments(idx, score, count, start, lens, pair_ptr, T, L, k=5, nms_thresh=0.5):
+    """Greedy temporal NMS, in raw-row time, of the per-window top moments of long videos (include/smin_hip.h,
+    smin_merge_window_moments): one workgroup per (video, query) pair picks k times the best candidate that no kept span suppresses.
+
+    ``idx (G, k_window, 2)`` int64, ``score (G, k_window)``, ``count (G,)``: top_moments' outputs for G windows; ``start (G,)`` each
+    window's first row relative to its video, ``lens (G,)`` its row count; ``pair_ptr (B + 1,)``: pair b owns windows
+    ``pair_ptr[b] .. pair_ptr[b + 1]``.  HIP tensors only; no host synchronisation.  Returns a dict: ``span (B, k, 2)`` float32 raw
+    rows (NaN for empty slots), ``score (B, k)`` (0), ``window (B, k)`` int64 ordinal within the pair (-1), ``cell (B, k, 2)`` int64
+    (-1), ``count (B,)`` int32."""
+    from .training import _require_hip
+    from ._lib import call, ptr, stream
+    _require_hip(idx, "merge_window_moments")
+    G, kw, B = _merge_check(idx, score, count, start, lens, pair_ptr, T, L, k)
+    dev = idx.device
+    args = [idx.to(torch.int64), score.detach().float(), count.to(torch.int32), start.to(torch.int64), lens.to(torch.int32),
+            pair_ptr.to(torch.int64)]
+    args = [a.contiguous() for a in args]
+    span = torch.empty((B, k, 2), dtype=torch.float32, device=dev)
+    out_score = torch.empty((B, k), dtype=torch.float32, device=dev)
+    window = torch.empty((B, k), dtype=torch.int64, device=dev)
+    cell = torch.empty((B, k, 2), dtype=torch.int64, device=dev)
+    out_count = torch.empty((B,), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        call("smin_merge_window_moments", stream(), *[ptr(a) for a in args], G, B, int(T), int(L), kw, k, float(nms_thresh),
+             ptr(span), ptr(out_score), ptr(window), ptr(cell), ptr(out_count))
+    return {"span": span, "score": out_score, "window": window, "cell": cell, "count": out_count}
+
+
+def _div32(a, b):
+    return (a.float().double() / b.float().double()).float()
+
+
+def _add32(a, b):
+    return (a.float().double() + b.float().double()).float()
+
+
+def window_spans(cell, start, lens, T, L):
+    """Spans in raw rows of cells (i, j) (..., 2) of windows (start, lens) (...,), fp32 in the order of include/smin_hip.h."""
+    s = start.to(torch.int64)
+    n = lens.to(torch.int64)
+    u = _div32(torch.clamp_min(n, int(T)).to(torch.float32), torch.full_like(n, int(L), dtype=torch.float32))
+    sf = s.to(torch.float32)
+    st = _add32(sf, _mul32(cell[..., 0].to(torch.float32), u))
+    en = torch.minimum(_add32(sf, _mul32((cell[..., 1] + 1).to(torch.float32), u)), (s + n).to(torch.float32))
+    return st, en
+
+
+def _span_iou(st1, en1, st2, en2):
+    inter = (torch.minimum(en1, en2) - torch.maximum(st1, st2)).clamp_min(0)
+    uni = torch.maximum(en1, en2) - torch.minimum(st1, st2)
+    return _div32(inter, uni)
+
+
+def merge_window_moments_torch(idx, score, count, start, lens, pair_ptr, T, L, k=5, nms_thresh=0.5):
+    """``merge_window_moments`` as plain torch + Python on any device (same result, bit for bit): each pair's candidates sorted by
+    (score, window, slot), then the greedy walk."""
+    G, kw, B = _merge_check(idx, score, count, start, lens, pair_ptr, T, L, k)
+    dev = idx.device
+    score = score.detach().float()
+    sc = torch.where(score == 0, torch.zeros_like(score), score)                                 # -0 -> +0
+    u = sc.view(torch.int32).to(torch.int64) & 0xFFFFFFFF
+    o = torch.where(u >= 0x80000000, u ^ 0xFFFFFFFF, u | 0x80000000).clamp_min(1).reshape(-1)   # the order word of top_moments_torch
+    st_all, en_all = window_spans(idx, start.unsqueeze(1), lens.unsqueeze(1), T, L)              # (G, kw)
+    st_all, en_all = st_all.reshape(-1), en_all.reshape(-1)
+    slot_ok = (torch.arange(kw, device=dev).unsqueeze(0) < count.to(torch.int64).unsqueeze(1)).reshape(-1)
+    thr = torch.tensor(float(nms_thresh), dtype=torch.float32, device=dev)
+    span = torch.full((B, k, 2), float("nan"), dtype=torch.float32, device=dev)
+    out_score = torch.zeros((B, k), dtype=torch.float32, device=dev)
+    window = torch.full((B, k), -1, dtype=torch.int64, device=dev)
+    cell = torch.full((B, k, 2), -1, dtype=torch.int64, device=dev)
+    out_count = torch.zeros((B,), dtype=torch.int32, device=dev)
+    pp = pair_ptr.to(torch.int64).tolist()
+    for b in range(B):
+        g0 = min(max(pp[b], 0), G)
+        g1 = min(max(pp[b + 1], g0), G)
+        q = torch.arange(g0 * kw, g1 * kw, device=dev)
+        q = q[slot_ok[q]]
+        order = torch.sort(o[q], descending=True, stable=True).indices                             # ties keep (window, slot) order
+        kept = []
+        for c in q[order].tolist():
+            if len(kept) >= k:
+                break
+            if kept:
+                ks = torch.tensor(kept, dtype=torch.int64, device=dev)
+                if bool((_span_iou(st_all[c], en_all[c], st_all[ks], en_all[ks]) > thr).any()):
+                    continue
+            kept.append(c)
+        n = len(kept)
+        if n:
+            ks = torch.tensor(kept, dtype=torch.int64, device=dev)
+            span[b, :n, 0], span[b, :n, 1] = st_all[ks], en_all[ks]
+            out_score[b, :n] = score.reshape(-1)[ks]
+            window[b, :n] = ks // kw - g0
+            cell[b, :n] = idx.reshape(-1, 2)[ks].to(torch.int64)
+        out_count[b] = n
+    return {"span": span, "score": out_score, "window": window, "cell": cell, "count": out_count}

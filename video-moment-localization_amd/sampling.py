@@ -300,3 +300,95 @@ def embed_tokens_torch(tokens, table, pad_id=None):
     qf = torch.where(ok.unsqueeze(-1), qf, torch.zeros_like(qf))
     qm = (ok & (t < pad_id)).to(torch.uint8)
     return qf, qm, qm.sum(1, dtype=torch.int32)
+
+
+# ---------------------------------------------------------------- overlapping windows of long videos (SMIN.localize_windows)
+MAX_ROWS = 1 << 24                   # rows per video: a window start is then exact in fp32 (the merge's spans, moments.py)
+
+
+def window_plan(lengths, window, stride):
+    """Overlapping windows over V videos of ``lengths`` raw rows (host sequence or CPU tensor), pure host arithmetic.
+
+    A video of ``n`` rows gets no window for ``n == 0``; one window ``(start 0, len n)`` for ``n <= window``; otherwise windows of
+    ``len = window`` at starts ``0, stride, 2 * stride, ...`` while ``start + window <= n``, plus one at ``n - window`` when the last of
+    those ends before ``n``.  Windows are ordered by video, then by start.  Returns CPU tensors ``(starts (W,) int64`` relative to the
+    video, ``lens (W,) int32, ptr (V + 1,) int64)``: video ``v`` owns windows ``ptr[v] .. ptr[v + 1]``.  Needs ``window >= 1``,
+    ``stride >= 1`` and ``0 <= n < 2**24``."""
+    n = _lengths_host(lengths)
+    window, stride = int(window), int(stride)
+    if window < 1:
+        raise ValueError(f"window_plan: window must be >= 1 (got {window})")
+    if stride < 1:
+        raise ValueError(f"window_plan: stride must be >= 1 (got {stride})")
+    if n.size and (n.min() < 0 or n.max() >= MAX_ROWS):
+        raise ValueError(f"window_plan: every length must be in [0, 2**24) so that a start is exact in fp32 (got {n.min()} .. {n.max()})")
+    starts, lens, ptr = [], [], [0]
+    for v in n.tolist():
+        if v == 0:
+            pass
+        elif v <= window:
+            starts.append(np.zeros(1, np.int64))
+            lens.append(np.full(1, v, np.int32))
+        else:
+            s = np.arange(0, v - window + 1, stride, dtype=np.int64)
+            if s[-1] + window < v:
+                s = np.append(s, v - window)
+            starts.append(s)
+            lens.append(np.full(s.shape[0], window, np.int32))
+        ptr.append(ptr[-1] + (starts[-1].shape[0] if v else 0))
+    cat = lambda xs, dt: np.concatenate(xs).astype(dt) if xs else np.zeros(0, dt)
+    return (torch.from_numpy(cat(starts, np.int64)), torch.from_numpy(cat(lens, np.int32)),
+            torch.from_numpy(np.asarray(ptr, dtype=np.int64)))
+
+
+def sample_windows(raw, row_begin, lens, T, mode="pick"):
+    """Resample W row ranges of ``raw`` to ``(W, T, Din)`` on the device: sample ``w`` is exactly ``sample_clips`` of a video made
+    of rows ``row_begin[w] .. row_begin[w] + lens[w]`` (eval split, ``spos = 0``), in either mode; ranges may overlap and repeat,
+    and no row is copied to form them (csrc/sampling.hip, smin_sample_windows).  ``raw``: HIP tensor ``(R, Din)``, Din % 4 == 0.
+    ``row_begin`` / ``lens``: host sequences (checked to lie within ``raw``: ValueError) or device int tensors ``(W,)`` (not
+    checked, nothing read back).  Returns ``(video_features (W, T, Din) float32, nfeats (W,) int32 = min(lens, T))``."""
+    from ._lib import SminHipError, call, ptr, stream
+    if mode not in MODES:
+        raise ValueError(f"mode must be one of {sorted(MODES)} (got {mode!r})")
+    if not (isinstance(raw, torch.Tensor) and raw.is_cuda):
+        raise SminHipError("sample_windows runs on a HIP device only (got a CPU tensor); there is no CPU fallback -- "
+                           "the plain restatement is available under the explicit name sample_windows_torch")
+    if raw.dim() != 2 or raw.shape[1] % 4 != 0 or raw.shape[1] < 4:
+        raise ValueError(f"raw must be (rows, Din) with Din % 4 == 0 (got {tuple(raw.shape)})")
+    T, dev, Din = int(T), raw.device, raw.shape[1]
+    if T < 1:
+        raise ValueError(f"T must be >= 1 (got {T})")
+    on_dev = [isinstance(x, torch.Tensor) and x.is_cuda for x in (row_begin, lens)]
+    if all(on_dev):
+        rb, ln = row_begin.to(torch.int64).contiguous(), lens.to(torch.int32).contiguous()
+    elif any(on_dev):
+        raise ValueError("row_begin and lens must both be device tensors or both host values")
+    else:
+        b, n = _lengths_host(row_begin), _lengths_host(lens)
+        if b.shape != n.shape:
+            raise ValueError(f"row_begin has {b.shape[0]} entries, lens {n.shape[0]}")
+        if b.size and (b.min() < 0 or n.min() < 0 or n.max() >= 2 ** 31 or (b + n).max() > raw.shape[0]):
+            raise ValueError(f"sample_windows: every range must lie within raw's {raw.shape[0]} rows")
+        rb, ln = torch.from_numpy(b).to(dev), torch.from_numpy(n.astype(np.int32)).to(dev)
+    W = rb.shape[0]
+    if ln.shape[0] != W or W > 65535:
+        raise ValueError(f"sample_windows: row_begin and lens must have the same length, at most 65535 (got {W}, {ln.shape[0]})")
+    raw = raw.detach().float().contiguous()
+    if raw.data_ptr() % 16:
+        raw = raw.clone()
+    out = torch.empty((W, T, Din), dtype=torch.float32, device=dev)
+    nfeats = torch.empty((W,), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        call("smin_sample_windows", stream(), ptr(raw), ptr(rb), ptr(ln), W, T, Din, MODES[mode], ptr(out), ptr(nfeats))
+    return out, nfeats
+
+
+def sample_windows_torch(raw, row_begin, lens, T, mode="pick"):
+    """``sample_windows`` restated: ``sample_clips_torch`` of each row range on its own (CPU tensors out)."""
+    packed = raw.detach().cpu() if isinstance(raw, torch.Tensor) else torch.as_tensor(np.asarray(raw, np.float32))
+    b, n = _lengths_host(row_begin), _lengths_host(lens)
+    Din = packed.shape[1]
+    if b.shape[0] == 0:
+        return torch.zeros((0, T, Din), dtype=torch.float32), torch.zeros((0,), dtype=torch.int32)
+    parts = [sample_clips_torch(packed[s:s + m], [m], T, mode=mode) for s, m in zip(b.tolist(), n.tolist())]
+    return torch.cat([p[0] for p in parts]), torch.cat([p[1] for p in parts])
