@@ -3,12 +3,14 @@
 backward [-> RCCL gradient all-reduce over xGMI when N > 1] -> Adam step) on synthetic
 ActivityNet-Captions-shaped input (BASELINE.json configs[2]: activitynet.yml with T=256, batch 64 per GPU).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
 Rank 0 prints ONE JSON line (contract in the task statement).  `value` = dense proposals (B_total * L * L)
-per second of the full train step (Adam included) with all inputs resident in HBM; `ms_fwd_bwd` is the same step
+per second of the full train step (Adam included) with all inputs resident in HBM.  A plain run does only what that
+figure needs: set-up, W warm-up steps, K timed steps, the --dump-outputs arrays and the line.  The rest is measured with
+--full alone, after the timed steps: `other_arithmetic` (the bf16-core contraction modes) and what follows.  `ms_fwd_bwd` is the same step
 without the optimizer (SURVEY 8d's metric definition), timed right after.  `roofline` is measured live with HIP
 events recorded by the library on the launch stream (smin_prof_*) around the three moment-unit contractions
 (forward / input gradient / weight gradient) and the attention core inside the timed steps; `roofline.step` prices
@@ -157,10 +159,13 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--workload", default="activitynet_t256", choices=sorted(WORKLOADS))
     ap.add_argument("--batch", type=int, default=0, help="per-GPU batch (default: the workload's)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure ms_fwd_bwd, the roofline and per-kernel figures, the bf16-core contraction modes "
+                         "and the CPU baseline (a plain run measures the headline alone)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-optimizer", action="store_true", help="time fwd+bwd only")
     ap.add_argument("--graph", action="store_true", help="replay the step as one HIP graph (training.CapturedStep; the host-bound small workloads)")
-    ap.add_argument("--no-other-modes", action="store_true", help="skip the extra timings of the bf16-core contraction modes")
+    ap.add_argument("--no-other-modes", action="store_true", help="with --full: skip the extra timings of the bf16-core contraction modes")
     ap.add_argument("--gemm", "--dtype", dest="gemm", default=os.environ.get("SMIN_GEMM_MODE", "f32"), choices=["f32", "f32e", "bf16x3", "bf16"],
                     help="arithmetic of the dense contractions (f32 = the reference's, the headline; bf16 = BASELINE.json configs[1])")
     ap.add_argument("--feed", default="resident", choices=["resident", "host"],
@@ -253,7 +258,8 @@ def main():
     lib = models.vml_amd._lib
     for _ in range(args.warmup):
         step()
-    lib.prof_enable(True)                                    # HIP events around the tagged launches, on their launch stream
+    # HIP events around the tagged launches, on their launch stream; on with or without --full, so that the timed steps are the same
+    lib.prof_enable(True)
     fence()
     t0 = time.perf_counter()
     for _ in range(args.steps):
@@ -265,184 +271,184 @@ def main():
     if args.dump_outputs and rank == 0:                       # before any later step overwrites the scores or the gradients
         dump_outputs(args.dump_outputs, {"loss": loss, **dict(zip(("pm", "ps", "pe", "pa"), scores)),
                                          **{"grad." + k: p.grad for k, p in model.named_parameters() if p.grad is not None}})
-    if captured:                                              # a replay runs no host code, so no launch is bracketed: kernel timings from eager steps
-        lib.prof_enable(True)
-        for _ in range(5):
-            step(with_opt=False, eager=True)
-        fence()
-        lib.prof_enable(False)
-        prof = lib.prof_read()
     elapsed = dp.max_over_ranks(elapsed, dev)                  # slowest rank defines the step
-    # the same K steps without the optimizer: SURVEY 8d defines the metric on zero_grad + fwd + loss + bwd (+ all-reduce)
-    if captured:
-        step(with_opt=False)                                  # (captures that variant's graph outside the timed region)
-    fence()
-    t0 = time.perf_counter()
-    for _ in range(args.steps):
-        step(with_opt=False)
-    fence()
-    elapsed_fb = dp.max_over_ranks(time.perf_counter() - t0, dev)
-    # kernel-quality timings of the backward kernels: in the timed region they share the chip with the weight-gradient stream, so
-    # their event durations there measure the overlap, not the kernel; a short pass with that stream folded into the main one
-    prof_serial = {}
-    if getattr(model, "async_weights", False) and getattr(model, "fused_core", False):
-        model.async_weights = False
-        step(with_opt=False, eager=True)
-        lib.prof_enable(True)
-        for _ in range(max(2, args.steps // 4)):
-            step(with_opt=False, eager=True)
-        fence()
-        lib.prof_enable(False)
-        prof_serial = lib.prof_read()
-        model.async_weights = True
     n_valid_total = int(dp.sum_over_ranks(n_valid, dev))
+    elapsed_fb, roofline, other = None, None, {}
+    if args.full:                                              # what the headline does not need, measured after it
+        if captured:                                          # a replay runs no host code, so no launch is bracketed: kernel timings from eager steps
+            lib.prof_enable(True)
+            for _ in range(5):
+                step(with_opt=False, eager=True)
+            fence()
+            lib.prof_enable(False)
+            prof = lib.prof_read()
+        # the same K steps without the optimizer: SURVEY 8d defines the metric on zero_grad + fwd + loss + bwd (+ all-reduce)
+        if captured:
+            step(with_opt=False)                              # (captures that variant's graph outside the timed region)
+        fence()
+        t0 = time.perf_counter()
+        for _ in range(args.steps):
+            step(with_opt=False)
+        fence()
+        elapsed_fb = dp.max_over_ranks(time.perf_counter() - t0, dev)
+        # kernel-quality timings of the backward kernels: in the timed region they share the chip with the weight-gradient stream, so
+        # their event durations there measure the overlap, not the kernel; a short pass with that stream folded into the main one
+        prof_serial = {}
+        if getattr(model, "async_weights", False) and getattr(model, "fused_core", False):
+            model.async_weights = False
+            step(with_opt=False, eager=True)
+            lib.prof_enable(True)
+            for _ in range(max(2, args.steps // 4)):
+                step(with_opt=False, eager=True)
+            fence()
+            lib.prof_enable(False)
+            prof_serial = lib.prof_read()
+            model.async_weights = True
 
-    # the same step with the contractions on the bf16 matrix cores (never the headline: `value` above is the exact-fp32 run)
-    other = {}
-    # (not under the in-node gradient exchange: it is limited to the exact-fp32 mode, distributed.wrap would have to be redone per mode)
-    if args.gemm == "f32" and not args.no_other_modes and not getattr(model, "grad_sync", False):
-        def scores():
-            with torch.no_grad():
-                return [o.float().clone() for o in net(batch["video_features"], batch["video_mask"], batch["query_features"], batch["query_mask"],
-                                                         batch["length_mask"], batch["moment_mask"])]
-        notes = {"f32e": "fp32 emulated: exact 3-way bf16 split of each operand, 6 products, fp32 accumulate (error vs fp64 at the exact-fp32 engine's level)",
-                 "bf16x3": "2-way bf16 split, 3 products, fp32 accumulate (~1e-5 relative on a dot product)"}
-        for mode in ("f32e", "bf16x3"):
-            ref_scores = scores()                              # exact fp32, current weights
-            models.vml_amd.set_gemm_mode(mode)
+        # the same step with the contractions on the bf16 matrix cores (never the headline: `value` above is the exact-fp32 run)
+        # (not under the in-node gradient exchange: it is limited to the exact-fp32 mode, distributed.wrap would have to be redone per mode)
+        if args.gemm == "f32" and not args.no_other_modes and not getattr(model, "grad_sync", False):
+            def scores():
+                with torch.no_grad():
+                    return [o.float().clone() for o in net(batch["video_features"], batch["video_mask"], batch["query_features"], batch["query_mask"],
+                                                             batch["length_mask"], batch["moment_mask"])]
+            notes = {"f32e": "fp32 emulated: exact 3-way bf16 split of each operand, 6 products, fp32 accumulate (error vs fp64 at the exact-fp32 engine's level)",
+                     "bf16x3": "2-way bf16 split, 3 products, fp32 accumulate (~1e-5 relative on a dot product)"}
+            for mode in ("f32e", "bf16x3"):
+                ref_scores = scores()                              # exact fp32, current weights
+                models.vml_amd.set_gemm_mode(mode)
+                try:
+                    dev_max = max(float((a - b).abs().max()) for a, b in zip(scores(), ref_scores))
+                    for _ in range(3):
+                        step()
+                    fence()
+                    t0 = time.perf_counter()
+                    for _ in range(args.steps):
+                        step()
+                    fence()
+                    el = dp.max_over_ranks(time.perf_counter() - t0, dev)
+                finally:
+                    models.vml_amd.set_gemm_mode("f32")
+                other[mode] = {"ms_per_step": el / args.steps * 1e3, "value": B * world * L * L / (el / args.steps), "unit": "proposals/s",
+                               "max_score_deviation_from_f32": dev_max, "arithmetic": notes[mode]}
+
+        def moment_kernels_alone():
+            """The three moment-unit contractions at this step's size, each alone on an otherwise idle device (after a warm-up pass):
+            what the kernels reach without the rest of the step around them (cache state, clocks under sustained mixed load)."""
+            from vml_amd._lib import call, ptr, stream
+            libc = lib.load()
+            lay = models.vml_amd.CellLayout.begin(batch["moment_mask"]).finish()
+            N = lay.N
+            gd = torch.Generator(device=dev).manual_seed(0)
+            r = lambda *sh: torch.randn(*sh, generator=gd, device=dev)
+            fcm, fm_, fb_, x1, dmu = r(N, D), r(N, D), r(B, L, D), r(N, D), r(N, D)
+            W, bvec = r(D, 2 * D) * 0.03, r(D)
+            WT = W.t().contiguous()
+            mu, dfc, dfb = torch.empty(N, D, device=dev), torch.empty(N, D, device=dev), torch.empty(B, L, D, device=dev)
+            dW, db = torch.empty_like(W), torch.empty(D, device=dev)
+            ws = torch.empty(libc.smin_workspace_bytes(N, B, 4, D, 4, 1), dtype=torch.uint8, device=dev)
+            fns = {"moment_fwd": lambda: call("smin_moment_unit_fwd", stream(), ptr(fcm), ptr(fm_), ptr(fb_), ptr(lay.cells), N, B, L, D, ptr(W), ptr(bvec), ptr(mu), ptr(x1)),
+                   "moment_dx": lambda: call("smin_moment_unit_bwd", stream(), ptr(dmu), ptr(fcm), ptr(fb_), ptr(lay.cells), ptr(lay.row_ptr), ptr(lay.cellmap), N, B, L, D,
+                                             ptr(WT), ptr(dfc), ptr(dfb), None, None, ptr(ws), ws.numel(), 1, None, ptr(x1), None),
+                   "moment_dw": lambda: call("smin_moment_unit_bwd", stream(), ptr(dmu), ptr(fcm), ptr(fb_), ptr(lay.cells), ptr(lay.row_ptr), ptr(lay.cellmap), N, B, L, D,
+                                             ptr(WT), None, None, ptr(dW), ptr(db), ptr(ws), ws.numel(), 1, None, ptr(x1), None)}
+            for _ in range(12):                                     # warm-up of all three, interleaved: ~35 ms of matrix work (the first
+                for f in fns.values():                              # launches after a pause run ~15 % slow, tools/nt_tail.py)
+                    f()
+            out = {}
+            lib.prof_enable(True)
+            for f in fns.values():
+                for _ in range(10):
+                    f()
+            torch.cuda.synchronize()
+            lib.prof_enable(False)
+            rec = lib.prof_read()
+            for k in fns:
+                durs = rec.get(k, [])
+                if durs:
+                    out[k] = sum(durs) / len(durs)
+            return out
+
+        alone_ms = {}
+        if rank == 0 and world == 1 and args.workload != "longvideo":
             try:
-                dev_max = max(float((a - b).abs().max()) for a, b in zip(scores(), ref_scores))
-                for _ in range(3):
-                    step()
-                fence()
-                t0 = time.perf_counter()
-                for _ in range(args.steps):
-                    step()
-                fence()
-                el = dp.max_over_ranks(time.perf_counter() - t0, dev)
-            finally:
-                models.vml_amd.set_gemm_mode("f32")
-            other[mode] = {"ms_per_step": el / args.steps * 1e3, "value": B * world * L * L / (el / args.steps), "unit": "proposals/s",
-                           "max_score_deviation_from_f32": dev_max, "arithmetic": notes[mode]}
+                alone_ms = moment_kernels_alone()
+            except Exception as e:                                   # a diagnostic, never fatal
+                alone_ms = {}
+                print(f"# moment_kernels_alone failed: {e}", file=sys.stderr)
 
-    def moment_kernels_alone():
-        """The three moment-unit contractions at this step's size, each alone on an otherwise idle device (after a warm-up pass):
-        what the kernels reach without the rest of the step around them (cache state, clocks under sustained mixed load)."""
-        from vml_amd._lib import call, ptr, stream
-        libc = lib.load()
-        lay = models.vml_amd.CellLayout.begin(batch["moment_mask"]).finish()
-        N = lay.N
-        gd = torch.Generator(device=dev).manual_seed(0)
-        r = lambda *sh: torch.randn(*sh, generator=gd, device=dev)
-        fcm, fm_, fb_, x1, dmu = r(N, D), r(N, D), r(B, L, D), r(N, D), r(N, D)
-        W, bvec = r(D, 2 * D) * 0.03, r(D)
-        WT = W.t().contiguous()
-        mu, dfc, dfb = torch.empty(N, D, device=dev), torch.empty(N, D, device=dev), torch.empty(B, L, D, device=dev)
-        dW, db = torch.empty_like(W), torch.empty(D, device=dev)
-        ws = torch.empty(libc.smin_workspace_bytes(N, B, 4, D, 4, 1), dtype=torch.uint8, device=dev)
-        fns = {"moment_fwd": lambda: call("smin_moment_unit_fwd", stream(), ptr(fcm), ptr(fm_), ptr(fb_), ptr(lay.cells), N, B, L, D, ptr(W), ptr(bvec), ptr(mu), ptr(x1)),
-               "moment_dx": lambda: call("smin_moment_unit_bwd", stream(), ptr(dmu), ptr(fcm), ptr(fb_), ptr(lay.cells), ptr(lay.row_ptr), ptr(lay.cellmap), N, B, L, D,
-                                         ptr(WT), ptr(dfc), ptr(dfb), None, None, ptr(ws), ws.numel(), 1, None, ptr(x1), None),
-               "moment_dw": lambda: call("smin_moment_unit_bwd", stream(), ptr(dmu), ptr(fcm), ptr(fb_), ptr(lay.cells), ptr(lay.row_ptr), ptr(lay.cellmap), N, B, L, D,
-                                         ptr(WT), None, None, ptr(dW), ptr(db), ptr(ws), ws.numel(), 1, None, ptr(x1), None)}
-        for _ in range(12):                                     # warm-up of all three, interleaved: ~35 ms of matrix work (the first
-            for f in fns.values():                              # launches after a pause run ~15 % slow, tools/nt_tail.py)
-                f()
-        out = {}
-        lib.prof_enable(True)
-        for f in fns.values():
-            for _ in range(10):
-                f()
-        torch.cuda.synchronize()
-        lib.prof_enable(False)
-        rec = lib.prof_read()
-        for k in fns:
-            durs = rec.get(k, [])
-            if durs:
-                out[k] = sum(durs) / len(durs)
-        return out
+        def kernel_line(tag, name, flops):
+            durs = prof.get(tag, [])
+            if not durs:
+                return None
+            in_step_ms = sum(durs) / len(durs)
+            alone = prof_serial.get(tag, []) if tag != "moment_fwd" else []      # the forward contraction runs alone in the timed region
+            avg_ms = sum(alone) / len(alone) if alone else in_step_ms
+            ach = flops / (avg_ms * 1e-3) / 1e12
+            line = {"kernel": name, "achieved": ach, "frac": ach / PEAK_F32_MFMA_TFLOPS, "avg_launch_ms": avg_ms, "launches_timed": len(alone) if alone else len(durs),
+                    "flops_per_launch": flops}
+            if tag in alone_ms:
+                line["alone_ms"] = alone_ms[tag]
+                line["alone_tflops"] = flops / (alone_ms[tag] * 1e-3) / 1e12
+            if alone:
+                line["avg_launch_ms_in_timed_region"] = in_step_ms
+                line["note"] = "avg_launch_ms: pass without the concurrent weight-gradient stream; in the timed region the two streams share the chip"
+            return line
 
-    alone_ms = {}
-    if rank == 0 and world == 1 and args.workload != "longvideo":
-        try:
-            alone_ms = moment_kernels_alone()
-        except Exception as e:                                   # a diagnostic, never fatal
-            alone_ms = {}
-            print(f"# moment_kernels_alone failed: {e}", file=sys.stderr)
-
-    def kernel_line(tag, name, flops):
-        durs = prof.get(tag, [])
-        if not durs:
-            return None
-        in_step_ms = sum(durs) / len(durs)
-        alone = prof_serial.get(tag, []) if tag != "moment_fwd" else []      # the forward contraction runs alone in the timed region
-        avg_ms = sum(alone) / len(alone) if alone else in_step_ms
-        ach = flops / (avg_ms * 1e-3) / 1e12
-        line = {"kernel": name, "achieved": ach, "frac": ach / PEAK_F32_MFMA_TFLOPS, "avg_launch_ms": avg_ms, "launches_timed": len(alone) if alone else len(durs),
-                "flops_per_launch": flops}
-        if tag in alone_ms:
-            line["alone_ms"] = alone_ms[tag]
-            line["alone_tflops"] = flops / (alone_ms[tag] * 1e-3) / 1e12
-        if alone:
-            line["avg_launch_ms_in_timed_region"] = in_step_ms
-            line["note"] = "avg_launch_ms: pass without the concurrent weight-gradient stream; in the timed region the two streams share the chip"
-        return line
-
-    # dominant kernels: the three moment-unit contractions (one launch each per layer per step), 4*D^2 FLOP per valid cell each
-    mu_flops = 2.0 * n_valid * D * (2 * D)
-    gemms = {"moment_fwd": kernel_line("moment_fwd", "gemm_nt_kernel<CatMat,PlainMat,EpMomentOut>  mu = [x1|mean_c f_c] Wcat^T", mu_flops),
-             "moment_dx": kernel_line("moment_dx", "gemm_nt_kernel<PlainMat,PlainMat,EpSplitStore>  dX = dmu Wcat", mu_flops),
-             "moment_dw": kernel_line("moment_dw", "gemm_tn_kernel<PlainMat,CatMat>  dWcat = dmu^T [x1|mean_c f_c]", mu_flops)}
-    pmc = {}
-    pmc_path = os.path.join(ROOT, "profiles", "pmc_moment.json")
-    if os.path.exists(pmc_path) and args.workload == "activitynet_t256" and B == cfg[-1] and args.gemm == "f32":
-        try:                                                # PMC traffic (rocprofv3 --pmc, gfx950 corrections) of exactly this workload
-            pmc = json.load(open(pmc_path))
-            import hashlib                                   # ... measured on the GEMM engine as built from these sources: stale -> no traffic figure
-            csrc = os.path.join(ROOT, "video-moment-localization_amd", "csrc")
-            stamp = pmc.get("sources_sha256") or {}
-            if not stamp or any(hashlib.sha256(open(os.path.join(csrc, f), "rb").read()).hexdigest() != h for f, h in stamp.items()):
-                pmc = {"stale": "profiles/pmc_moment.json was measured on other gemm.h / moment_unit.hip sources (or carries no stamp): traffic omitted; "
-                                "regenerate with profiles/run_pmc.sh + profiles/make_pmc_moment.py"}
-        except Exception:
-            pmc = {}
-    roofline = None
-    if gemms["moment_fwd"]:
-        g = gemms["moment_fwd"]
-        roofline = {"bound": "mfma", "kernel": g["kernel"], "achieved": g["achieved"], "peak": PEAK_F32_MFMA_TFLOPS, "unit": "TFLOP/s",
-                    "frac": g["frac"], "traffic": pmc.get("moment_fwd", {}).get("hbm_bytes_per_launch"), "avg_launch_ms": g["avg_launch_ms"],
-                    "launches_timed": g["launches_timed"], "flops_per_launch": mu_flops, "valid_cells_per_launch": n_valid,
-                    "algorithmic_bytes_per_launch": 4.0 * n_valid * 4 * D}
-        if "stale" in pmc:
-            roofline["traffic_note"] = pmc["stale"]
-        if args.gemm == "bf16":                                # bf16 products run at 16x the fp32 matrix rate: the contraction is bound by its operand traffic
-            ach = roofline["algorithmic_bytes_per_launch"] / (g["avg_launch_ms"] * 1e-3) / 1e9
-            roofline.update({"bound": "hbm", "achieved": ach, "peak": PEAK_HBM_GBS, "unit": "GB/s", "frac": ach / PEAK_HBM_GBS, "traffic": None,
-                             "tflops": g["achieved"]})
-        for k in ("moment_dx", "moment_dw"):
-            if gemms[k]:
-                gemms[k]["traffic"] = pmc.get(k, {}).get("hbm_bytes_per_launch")
-        roofline["moment_gemms"] = {k: v for k, v in gemms.items() if v}
-        attn = {}
-        # attention core: HBM-side view.  fwd reads chat, writes cc (+ mean); bwd reads chat + 1-2 gradients, writes dchat
-        rows = n_valid * C
-        for tag, nbytes in (("attn_fwd", 4.0 * dl * (2 * rows + n_valid)), ("attn_bwd", 4.0 * dl * (3 * rows + n_valid))):
-            durs = prof_serial.get(tag, []) if tag == "attn_bwd" and prof_serial.get(tag) else prof.get(tag, [])
-            if durs:
-                avg_ms = sum(durs) / len(durs)
-                attn[tag] = {"avg_launch_ms": avg_ms, "launches_timed": len(durs), "algorithmic_bytes_per_launch": nbytes,
-                             "achieved_GBs": nbytes / (avg_ms * 1e-3) / 1e9, "frac_hbm": nbytes / (avg_ms * 1e-3) / 1e9 / PEAK_HBM_GBS}
-        roofline["attention_core"] = attn
-        fa, fe, ba = step_work(C, D, dl, Nq, layers)
-        t_fb = elapsed_fb / args.steps
-        per_rank_valid = n_valid_total / world
-        roofline["step"] = {"valid_cells": n_valid_total, "flops_algorithmic_per_cell": fa, "flops_executed_per_cell": fe,
-                            "bytes_algorithmic_per_cell": ba, "timed_on": "ms_fwd_bwd",
-                            "frac_mfma": per_rank_valid * fa / t_fb / 1e12 / PEAK_F32_MFMA_TFLOPS,
-                            "frac_mfma_executed": per_rank_valid * fe / t_fb / 1e12 / PEAK_F32_MFMA_TFLOPS,
-                            "frac_hbm": per_rank_valid * ba / t_fb / 1e9 / PEAK_HBM_GBS,
-                            "bound": "mfma (fp32: ~110 FLOP/B is above the 20 FLOP/B ridge)" if args.gemm != "bf16"
-                                     else "hbm (bf16 products: the 312 FLOP/B ridge is above the path's ~110 FLOP/B)"}
+        # dominant kernels: the three moment-unit contractions (one launch each per layer per step), 4*D^2 FLOP per valid cell each
+        mu_flops = 2.0 * n_valid * D * (2 * D)
+        gemms = {"moment_fwd": kernel_line("moment_fwd", "gemm_nt_kernel<CatMat,PlainMat,EpMomentOut>  mu = [x1|mean_c f_c] Wcat^T", mu_flops),
+                 "moment_dx": kernel_line("moment_dx", "gemm_nt_kernel<PlainMat,PlainMat,EpSplitStore>  dX = dmu Wcat", mu_flops),
+                 "moment_dw": kernel_line("moment_dw", "gemm_tn_kernel<PlainMat,CatMat>  dWcat = dmu^T [x1|mean_c f_c]", mu_flops)}
+        pmc = {}
+        pmc_path = os.path.join(ROOT, "profiles", "pmc_moment.json")
+        if os.path.exists(pmc_path) and args.workload == "activitynet_t256" and B == cfg[-1] and args.gemm == "f32":
+            try:                                                # PMC traffic (rocprofv3 --pmc, gfx950 corrections) of exactly this workload
+                pmc = json.load(open(pmc_path))
+                import hashlib                                   # ... measured on the GEMM engine as built from these sources: stale -> no traffic figure
+                csrc = os.path.join(ROOT, "video-moment-localization_amd", "csrc")
+                stamp = pmc.get("sources_sha256") or {}
+                if not stamp or any(hashlib.sha256(open(os.path.join(csrc, f), "rb").read()).hexdigest() != h for f, h in stamp.items()):
+                    pmc = {"stale": "profiles/pmc_moment.json was measured on other gemm.h / moment_unit.hip sources (or carries no stamp): traffic omitted; "
+                                    "regenerate with profiles/run_pmc.sh + profiles/make_pmc_moment.py"}
+            except Exception:
+                pmc = {}
+        if gemms["moment_fwd"]:
+            g = gemms["moment_fwd"]
+            roofline = {"bound": "mfma", "kernel": g["kernel"], "achieved": g["achieved"], "peak": PEAK_F32_MFMA_TFLOPS, "unit": "TFLOP/s",
+                        "frac": g["frac"], "traffic": pmc.get("moment_fwd", {}).get("hbm_bytes_per_launch"), "avg_launch_ms": g["avg_launch_ms"],
+                        "launches_timed": g["launches_timed"], "flops_per_launch": mu_flops, "valid_cells_per_launch": n_valid,
+                        "algorithmic_bytes_per_launch": 4.0 * n_valid * 4 * D}
+            if "stale" in pmc:
+                roofline["traffic_note"] = pmc["stale"]
+            if args.gemm == "bf16":                                # bf16 products run at 16x the fp32 matrix rate: the contraction is bound by its operand traffic
+                ach = roofline["algorithmic_bytes_per_launch"] / (g["avg_launch_ms"] * 1e-3) / 1e9
+                roofline.update({"bound": "hbm", "achieved": ach, "peak": PEAK_HBM_GBS, "unit": "GB/s", "frac": ach / PEAK_HBM_GBS, "traffic": None,
+                                 "tflops": g["achieved"]})
+            for k in ("moment_dx", "moment_dw"):
+                if gemms[k]:
+                    gemms[k]["traffic"] = pmc.get(k, {}).get("hbm_bytes_per_launch")
+            roofline["moment_gemms"] = {k: v for k, v in gemms.items() if v}
+            attn = {}
+            # attention core: HBM-side view.  fwd reads chat, writes cc (+ mean); bwd reads chat + 1-2 gradients, writes dchat
+            rows = n_valid * C
+            for tag, nbytes in (("attn_fwd", 4.0 * dl * (2 * rows + n_valid)), ("attn_bwd", 4.0 * dl * (3 * rows + n_valid))):
+                durs = prof_serial.get(tag, []) if tag == "attn_bwd" and prof_serial.get(tag) else prof.get(tag, [])
+                if durs:
+                    avg_ms = sum(durs) / len(durs)
+                    attn[tag] = {"avg_launch_ms": avg_ms, "launches_timed": len(durs), "algorithmic_bytes_per_launch": nbytes,
+                                 "achieved_GBs": nbytes / (avg_ms * 1e-3) / 1e9, "frac_hbm": nbytes / (avg_ms * 1e-3) / 1e9 / PEAK_HBM_GBS}
+            roofline["attention_core"] = attn
+            fa, fe, ba = step_work(C, D, dl, Nq, layers)
+            t_fb = elapsed_fb / args.steps
+            per_rank_valid = n_valid_total / world
+            roofline["step"] = {"valid_cells": n_valid_total, "flops_algorithmic_per_cell": fa, "flops_executed_per_cell": fe,
+                                "bytes_algorithmic_per_cell": ba, "timed_on": "ms_fwd_bwd",
+                                "frac_mfma": per_rank_valid * fa / t_fb / 1e12 / PEAK_F32_MFMA_TFLOPS,
+                                "frac_mfma_executed": per_rank_valid * fe / t_fb / 1e12 / PEAK_F32_MFMA_TFLOPS,
+                                "frac_hbm": per_rank_valid * ba / t_fb / 1e9 / PEAK_HBM_GBS,
+                                "bound": "mfma (fp32: ~110 FLOP/B is above the 20 FLOP/B ridge)" if args.gemm != "bf16"
+                                         else "hbm (bf16 products: the 312 FLOP/B ridge is above the path's ~110 FLOP/B)"}
 
     if rank == 0:
         total_B = B * world
@@ -456,7 +462,7 @@ def main():
         out = {
             "metric": "proposals/sec (fwd+bwd)", "value": total_B * L * L / (elapsed / args.steps), "unit": "proposals/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms, "ms_with_adam": None if args.no_optimizer else ms,
-            "ms_fwd_bwd": elapsed_fb / args.steps * 1e3, "higher_is_better": True,
+            "higher_is_better": True,
             "scaling": "weak", "vs_baseline": None,
             "dtype": {"f32": "f32", "f32e": "f32 (emulated on the bf16 matrix cores: exact 3-way split, 6 products, fp32 accumulate)", "bf16x3": "f32 (split-bf16 products, fp32 accumulate)", "bf16": "bf16 (products, and storage of the contraction-only tensors: pair product, attention outputs; fp32 accumulate, fp32 storage of everything an element-wise kernel reads)"}[args.gemm],
             "data": "synthetic" if args.feed == "resident" else "synthetic, fed from pinned host memory every step (BatchFeeder: async H2D + device-side targets)",
@@ -468,11 +474,13 @@ def main():
                        "valid_cells_per_s": n_valid_total / (elapsed / args.steps), "parallelism": f"dp{world}", "dist_backend": backend, "dist_world_size": world_seen,
                        "ddp_overrides": getattr(model, "ddp_overrides", None), "grad_exchange": getattr(model, "grad_exchange", None),
                        "final_loss": float(loss.item())},
-            "roofline": roofline,
         }
+        if args.full:
+            out["ms_fwd_bwd"] = elapsed_fb / args.steps * 1e3
+            out["roofline"] = roofline
         if other:
             out["other_arithmetic"] = other
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(cfg)
         print(json.dumps(out), flush=True)
     if torch.distributed.is_initialized():

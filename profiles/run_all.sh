@@ -9,7 +9,7 @@ cd /tmp && export TMPDIR=/tmp
 rm -rf /tmp/prof_ks
 cd $ROOT
 # SMIN_SYNC_WEIGHTS=1: the weight-gradient stream folded into the main one, so that a kernel's duration is the kernel's
-SMIN_SYNC_WEIGHTS=1 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_ks -- python3 bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-other-modes > $OUT/bench_under_rocprof_$SFX.log 2>&1
+SMIN_SYNC_WEIGHTS=1 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_ks -- python3 bench.py --steps 20 --warmup 3 --full --no-cpu-baseline --no-other-modes > $OUT/bench_under_rocprof_$SFX.log 2>&1
 f=$(find /tmp/prof_ks -name "*kernel_stats.csv" | head -1)
 cp $f $OUT/bench_kernel_stats_$SFX.csv
 python profiles/summarize.py $f 23 70 > $OUT/bench_kernel_stats_$SFX.txt
@@ -25,7 +25,7 @@ rm -rf $OUT/pmc_$SFX
 # long-video stress (BASELINE configs[4] at one GPU's share): kernel stats
 rm -rf /tmp/prof_lv
 cd /tmp
-SMIN_SYNC_WEIGHTS=1 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_lv -- python3 $ROOT/bench.py --workload longvideo --steps 4 --warmup 2 --no-cpu-baseline --no-other-modes > $ROOT/$OUT/longvideo_under_rocprof_$SFX.log 2>&1
+SMIN_SYNC_WEIGHTS=1 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_lv -- python3 $ROOT/bench.py --workload longvideo --steps 4 --warmup 2 --full --no-cpu-baseline --no-other-modes > $ROOT/$OUT/longvideo_under_rocprof_$SFX.log 2>&1
 cd $ROOT
 python profiles/summarize.py $(find /tmp/prof_lv -name "*kernel_stats.csv" | head -1) 6 40 > $OUT/longvideo_kernel_stats_$SFX.txt
-python bench.py --workload longvideo --steps 5 --warmup 2 --no-cpu-baseline > $OUT/longvideo_bench_$SFX.json 2>/dev/null
+python bench.py --workload longvideo --steps 5 --warmup 2 --full --no-cpu-baseline > $OUT/longvideo_bench_$SFX.json 2>/dev/null

@@ -1383,20 +1383,42 @@ def test_degenerate_samples_and_empty_batch(dev):
     assert all(p.grad is None or bool(torch.isfinite(p.grad).all()) for p in m.parameters())
 
 
-def test_bench_contract_line(dev, tmp_path):
-    """bench.py prints one JSON line with the keys the driver reads (short run of a small workload), and --dump-outputs writes
-    what the last timed step computed."""
-    import glob
+def _run_bench(*args):
     import json
     import os
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "2", "--warmup", "1", "--no-cpu-baseline",
-                          "--workload", "charadessta", "--dump-outputs", str(tmp_path / "dump")], capture_output=True, text=True, timeout=300, cwd=root)
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), *args], capture_output=True, text=True, timeout=300, cwd=root)
     assert out.returncode == 0, out.stderr[-2000:]
     line = [ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1]
-    j = json.loads(line)
+    return json.loads(line)
+
+
+def _check_bench_dump(dump, j):
+    """The dump of a charadessta run: scores, loss and every parameter gradient of the last timed step, as float arrays, at most
+    64 MB in all."""
+    import glob
+    import os
+    import models
+    files = glob.glob(str(dump / "*.npy"))
+    names = {os.path.basename(f)[:-4] for f in files}
+    B, L = 32, 16
+    params = [k for k, _ in models.SMIN(64, 16, 4, 512, 128, 3, 1024, 13, 256).named_parameters()]
+    assert names == {"loss", "pm", "ps", "pe", "pa"} | {"grad." + k for k in params}
+    assert sum(os.path.getsize(f) for f in files) <= 64e6
+    d = {n: np.load(str(dump / (n + ".npy"))) for n in names}
+    assert all(a.dtype in (np.float32, np.float64) and np.isfinite(a).all() for a in d.values())
+    assert d["pm"].shape == (B, L, L) and d["ps"].shape == d["pe"].shape == d["pa"].shape == (B, L)
+    assert float(d["loss"]) == j["config"]["final_loss"]
+    assert any(np.abs(d["grad." + k]).max() > 0 for k in params)
+
+
+def test_bench_contract_line(dev, tmp_path):
+    """bench.py --full prints one JSON line with the keys the driver reads (short run of a small workload) and the figures --full
+    adds, and --dump-outputs writes what the last timed step computed."""
+    import os
+    j = _run_bench("--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--workload", "charadessta", "--dump-outputs", str(tmp_path / "dump"))
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
               "dtype", "data", "config", "roofline"):
         assert k in j, k
@@ -1408,19 +1430,22 @@ def test_bench_contract_line(dev, tmp_path):
     if default_mode == "f32":
         oa = j["other_arithmetic"]
         assert set(oa) == {"f32e", "bf16x3"} and oa["f32e"]["max_score_deviation_from_f32"] < 5e-6 and oa["bf16x3"]["max_score_deviation_from_f32"] < 1e-4
-    # the dump: scores, loss and every parameter gradient of the last timed step, as float arrays, at most 64 MB in all
-    import models
-    files = glob.glob(str(tmp_path / "dump" / "*.npy"))
-    names = {os.path.basename(f)[:-4] for f in files}
-    B, L = 32, 16
-    params = [k for k, _ in models.SMIN(64, 16, 4, 512, 128, 3, 1024, 13, 256).named_parameters()]
-    assert names == {"loss", "pm", "ps", "pe", "pa"} | {"grad." + k for k in params}
-    assert sum(os.path.getsize(f) for f in files) <= 64e6
-    d = {n: np.load(str(tmp_path / "dump" / (n + ".npy"))) for n in names}
-    assert all(a.dtype in (np.float32, np.float64) and np.isfinite(a).all() for a in d.values())
-    assert d["pm"].shape == (B, L, L) and d["ps"].shape == d["pe"].shape == d["pa"].shape == (B, L)
-    assert float(d["loss"]) == j["config"]["final_loss"]
-    assert any(np.abs(d["grad." + k]).max() > 0 for k in params)
+    _check_bench_dump(tmp_path / "dump", j)
+
+
+def test_bench_plain_line(dev, tmp_path):
+    """A plain bench.py run prints the same headline keys, measures nothing that --full adds, and dumps the same arrays."""
+    import os
+    j = _run_bench("--steps", "2", "--warmup", "1", "--workload", "charadessta", "--dump-outputs", str(tmp_path / "dump"))
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
+              "dtype", "data", "config"):
+        assert k in j, k
+    default_mode = os.environ.get("SMIN_GEMM_MODE", "f32")
+    assert j["metric"] == "proposals/sec (fwd+bwd)" and j["unit"] == "proposals/s" and j["higher_is_better"] is True
+    assert j["n_gpus"] == 1 and j["steps"] == 2 and j["warmup"] == 1 and j["dtype"].startswith("f32" if default_mode != "bf16" else "bf16")
+    assert j["value"] > 0 and abs(j["value"] - 32 * 16 * 16 / (j["ms_per_step"] * 1e-3)) <= 1e-6 * j["value"]
+    assert not {"ms_fwd_bwd", "roofline", "other_arithmetic", "cpu_baseline"} & set(j)
+    _check_bench_dump(tmp_path / "dump", j)
 
 
 def test_layout_build_kernels(dev):
