@@ -17,6 +17,19 @@ FULL = {
 }
 IN_KEYS = ["video_features", "video_mask", "query_features", "query_mask", "length_mask", "moment_mask"]
 
+GEMM_SLOTS = 768                  # csrc/gemm.h: resident workgroups of the contraction engines (256 CUs x 3)
+
+
+def cdiv(a, b):
+    return -(-a // b)
+
+
+def tn_splits(Mrows, I, J):
+    """gemm.h tn_splits: row splits of a weight-gradient contraction [I, J] over Mrows rows."""
+    s = cdiv(GEMM_SLOTS, cdiv(I, 128) * cdiv(J, 128))
+    s = min(s, cdiv(Mrows, 256))
+    return min(max(s, 1), GEMM_SLOTS)
+
 
 def load_npz(name):
     return np.load(os.path.join(GOLDEN, name + ".npz"), allow_pickle=False)

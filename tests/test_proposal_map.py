@@ -273,7 +273,7 @@ def test_moment_and_score_refs_match_oracle(layout):
 
 # ---------------------------------------------------------------- mirrors of the launch arithmetic
 
-GEMM_SLOTS = 768                  # csrc/gemm.h
+GEMM_SLOTS = H.GEMM_SLOTS
 EV_ROUND = 2 * 512                # proposal_map_bwd_events2_kernel: 2 waves x EV_CAP table entries per round
 
 
@@ -321,9 +321,7 @@ def rows_reduce_slices(L):
     return cdiv(L, 32) if L > 96 else 1
 
 
-def tn_splits(M, I, J):
-    s = cdiv(GEMM_SLOTS, cdiv(I, 128) * cdiv(J, 128))
-    return max(1, min(s, cdiv(M, 256), GEMM_SLOTS))
+tn_splits = H.tn_splits            # gemm.h tn_splits (one mirror for every test file)
 
 
 def parent_bu_ws_floats(B, L, Nq, D):

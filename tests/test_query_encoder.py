@@ -11,6 +11,8 @@ import math
 import pytest
 import torch
 
+from tests.helpers import tn_splits      # gemm.h tn_splits (one mirror for every test file)
+
 FWD_TOL = 1e-5          # max |got - ref| / max |ref|, per output and case (as test_query_encoder_matches_packed_lstm)
 GRAD_TOL = 2e-4
 CUS = 256               # MI355X; the GPU tests read the real count
@@ -105,13 +107,6 @@ def nt_splitk_splits(M, N, K, gemm_mode=0):
     while s > 1 and (K % (16 * s) != 0 or K // s < 256):
         s -= 1
     return min(s, 16)
-
-
-def tn_splits(Mrows, I, J):
-    """gemm.h tn_splits: row splits of a weight-gradient contraction."""
-    s = cdiv(GEMM_SLOTS, cdiv(I, 128) * cdiv(J, 128))
-    s = min(s, cdiv(Mrows, 256))
-    return min(max(s, 1), GEMM_SLOTS)
 
 
 def regimes(case, cus=CUS, gemm_mode=0):
