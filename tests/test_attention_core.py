@@ -569,7 +569,7 @@ def test_python_host_step_at_h384(dev):
     m = m.to(dev)
     b = {k: v.to(dev) for k, v in batch.items()}
     xs = H.model_inputs(b)
-    assert not m._native_ok(xs[0], xs[2])
+    assert m._plan(xs[0], xs[2]) == "stream"
     out = m(*xs)
     for got, want in zip(out, ref):
         assert (got.detach().cpu() - want.detach()).abs().max().item() < 2e-5

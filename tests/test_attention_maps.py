@@ -59,7 +59,7 @@ def _model(cfg, sd, dev, native):
     m = models.SMIN(c["T"], c["L"], c["C"], c["D"], c["dl"], c["layers"], c["Din"], c["Nq"], c["H"], dev)
     m.load_state_dict(sd)
     m = m.to(dev)
-    m.native_host = native
+    m.fused_core = native
     return m
 
 
@@ -92,9 +92,9 @@ def test_fixtures_hold_the_reference_maps():
 def test_forward_with_attention_operator_is_registered():
     import models
     ops = models.vml_amd._lib.load_torch()
-    schema = str(ops.smin_forward_with_attention.default._schema)
-    assert "Tensor[]" in schema.split("->")[1], schema
-    assert "int[] cfg" in schema, schema
+    schema = str(ops.smin_forward.default._schema)
+    assert schema.split("->")[1].count("Tensor[]") == 2, schema
+    assert "str? attention" in schema, schema
 
 
 def test_captured_step_refuses_keep_attention():

@@ -248,7 +248,7 @@ def test_against_oracle_random(dev, T, L, C, D, dl, layers, Din, Nq, Hh, B):
     b = {k: v.to(dev) for k, v in batch.items()}
     xs = H.model_inputs(b)
     if (T, L, C, D, dl, layers, Din, Nq, Hh, B) in NATIVE_ROWS:
-        assert m._native_ok(xs[0], xs[2])
+        assert m._plan(xs[0], xs[2]) == "node"
     pm, ps, pe, pa = m(*xs)
     for got, ref in ((pm, pm0), (ps, ps0), (pe, pe0), (pa, pa0)):
         assert (got.detach().cpu() - ref.detach()).abs().max().item() < SCORE_TOL
@@ -349,7 +349,7 @@ def test_native_host_equals_python_host(dev):
         res = []
         for native in (True, False):
             m = build_model(dict(T=T, L=L, C=C, D=D, dl=dl, layers=layers, Din=Din, Nq=Nq, H=Hh), sd, dev)
-            m.native_host = native
+            m.fused_core = native
             TR.NATIVE_LOSS = native
             try:
                 out = m(*H.model_inputs(b))
@@ -387,7 +387,7 @@ def test_inputs_that_require_grad_take_the_python_host(dev):
     """The one-node step forms no gradients of its inputs: SMIN.forward with video_features / query_features that require grad runs
     the Python host.  Scores and parameter gradients hold the tolerances of test_against_oracle_random, query_features.grad the same
     2e-3 relative bound against the oracle's autograd (video_features.grad stays None: neither host forms it).  The extension itself
-    refuses such inputs, and a cfg asking for a node per module (cfg[10] = 0), pointing to the Python host."""
+    refuses such inputs, pointing to the Python host, and takes no fused_core option (a node per module is the Python host's)."""
     from oracle import smin_oracle as O
     from vml_amd import loss_fn
     import models
@@ -405,7 +405,7 @@ def test_inputs_that_require_grad_take_the_python_host(dev):
     inp = list(H.model_inputs(b))
     inp[0] = inp[0].clone().requires_grad_(True)
     inp[2] = inp[2].clone().requires_grad_(True)
-    assert not m._native_ok(inp[0], inp[2])
+    assert m._plan(inp[0], inp[2]) == "stream"
     streams = []
     python_host = m._forward_stream
     m._forward_stream = lambda *a: streams.append(1) or python_host(*a)
@@ -421,13 +421,13 @@ def test_inputs_that_require_grad_take_the_python_host(dev):
     g0, err = inp0[2].grad, (inp[2].grad.cpu() - inp0[2].grad).abs().max().item()
     print("query_features.grad: max abs err", err, "relative", err / g0.abs().max().item())
     assert err <= 2e-3 * g0.abs().max().item() + 1e-7, err
-    # the extension refuses both cases before it launches anything
+    # the extension refuses such inputs before it launches anything, and it has no option for a node per module
     ops = models.vml_amd._lib.load_torch()
-    cfg = [T, L, C, D, dl, layers, Nq, Hh, 1, 1, 1, 1, 1, 0, -1, 1]
-    with pytest.raises(RuntimeError, match=r"cfg\[10\].*SMIN\.native_host = False"):
-        ops.smin_forward(*H.model_inputs(b), m._native_params(), cfg[:10] + [0] + cfg[11:])
-    with pytest.raises(RuntimeError, match=r"require grad.*SMIN\.native_host = False"):
-        ops.smin_forward(*inp, m._native_params(), cfg)
+    shape = (T, L, C, layers, Nq, Hh)
+    with pytest.raises(RuntimeError, match=r"expected at most \d+ argument"):         # a schema error: no such option
+        ops.smin_forward(*H.model_inputs(b), m._native_params(), *shape, fused_core=False, **m._node_options())
+    with pytest.raises(RuntimeError, match=r"require grad.*SMIN\.fused_core = False"):
+        ops.smin_forward(*inp, m._native_params(), *shape, **m._node_options())
 
 def test_target_kernel_and_feeder(dev):
     """csrc/labels.hip (one launch for every mask / target of a batch) against the per-sample restatement of dataset.py:95-155
@@ -1273,7 +1273,7 @@ def test_short_query_batch_is_padded_to_max_query_length(dev, cut):
     res = []
     for native in (True, False):
         m = build_model(dict(T=T, L=L, C=C, D=D, dl=dl, layers=layers, Din=Din, Nq=Nq, H=Hh), sd, dev)
-        m.native_host = native
+        m.fused_core = native
         out = m(*H.model_inputs(b))
         loss_fn(out[0], b["ym"], b["sm"], b["moment_mask"], out[1], b["ys"], b["ss"], out[2], b["ye"], b["se"], out[3], b["ya"], b["length_mask"]).backward()
         res.append(([o.detach().clone() for o in out], {k: p.grad.clone() for k, p in m.named_parameters()}))

@@ -79,20 +79,25 @@ def test_library_exports_every_declared_symbol():
 
 def test_torch_extension_registers_operators():
     """csrc/torch_binding.cpp: TORCH_LIBRARY(smin_hip) loads without a GPU, exposes the two operators with the documented
-    schemas, and refuses CPU tensors (no CPU fallback behind the extension either)."""
+    schemas, and refuses CPU tensors (no CPU fallback behind the extension either) -- called with SMIN's own options, which
+    therefore bind to the schema."""
     import models
     ops = models.vml_amd._lib.load_torch()
     assert ops.abi_version() == 2
     schema = str(torch.ops.smin_hip.smin_forward.default._schema)
-    for name in ("video_features", "video_mask", "query_features", "query_mask", "length_mask", "moment_mask", "Tensor[] params", "int[] cfg"):
+    for name in ("video_features", "video_mask", "query_features", "query_mask", "length_mask", "moment_mask", "Tensor[] params", "int T", "int L",
+                 "int C", "int num_smi_layers", "int max_query_length", "int lstm_hidden_size", "*, bool overlap_boundary", "bool overlap_prep",
+                 "bool param_prep_kernel", "bool async_weights", "bool bf16_operand_storage", "bool grad_sync", "int? known_cell_count",
+                 "bool tail_split", "bool input_grads", "str? attention"):
         assert name in schema, schema
+    assert "cfg" not in schema, schema
     m = models.SMIN(16, 8, 4, 32, 16, 2, 24, 5, 16)
     ps = m._native_params()
     assert len(ps) == len(list(m.parameters())) == 19 + 20 * 2 + 8
     assert {id(p) for p in ps} == {id(p) for p in m.parameters()}
     with pytest.raises(RuntimeError, match="no CPU fallback"):
         ops.smin_forward(torch.zeros(2, 16, 24), torch.ones(2, 16, 1, dtype=torch.uint8), torch.zeros(2, 5, 300), torch.ones(2, 5, 1, dtype=torch.uint8),
-                         torch.ones(2, 8, dtype=torch.bool), torch.ones(2, 8, 8, dtype=torch.bool), ps, [16, 8, 4, 32, 16, 2, 5, 16, 1, 1])
+                         torch.ones(2, 8, dtype=torch.bool), torch.ones(2, 8, 8, dtype=torch.bool), ps, 16, 8, 4, 2, 5, 16, **m._node_options())
     with pytest.raises(RuntimeError, match="no CPU fallback"):
         ops.smin_loss(*[torch.zeros(2, 8, 8)] * 4, *[torch.zeros(2, 8)] * 9)
 
@@ -256,3 +261,82 @@ def test_constructor_names_the_kernel_limits():
         with pytest.raises(ValueError, match="limits of the HIP kernels") as e:
             models.SMIN(**{**ok, key: val})
         assert word in str(e.value)
+
+
+# (T, L, C, D, dl, layers, Din, Nq, H) -> the path SMIN._plan picks for float32 inputs of T frames that need no gradient: every row of
+# test_hip_parity.test_against_oracle_random, then shapes at the edges of the node and of the content stream
+PLAN_ROWS = [
+    ((64, 16, 4, 64, 32, 2, 40, 9, 32), "node"),
+    ((48, 24, 4, 128, 64, 1, 32, 20, 64), "node"),
+    ((64, 32, 2, 64, 16, 2, 16, 3, 32), "node"),
+    ((96, 32, 3, 128, 128, 3, 24, 32, 64), "units"),       # dl == D
+    ((16, 16, 4, 64, 32, 2, 24, 6, 32), "node"),
+    ((32, 8, 4, 64, 16, 5, 24, 6, 32), "node"),
+    ((32, 8, 4, 64, 16, 9, 24, 6, 32), "units"),           # 9 layers: beyond the clip-window-means launch
+    ((64, 16, 4, 128, 64, 2, 40, 9, 64), "node"),
+    ((32, 16, 4, 64, 32, 1, 24, 17, 32), "node"),
+    ((32, 8, 4, 64, 16, 2, 24, 32, 32), "node"),
+    ((64, 16, 4, 256, 128, 2, 40, 23, 128), "node"),
+    ((32, 8, 4, 192, 128, 2, 24, 29, 96), "node"),
+    ((64, 16, 4, 104, 48, 2, 24, 18, 52), "node"),
+    ((32, 8, 4, 32, 48, 2, 24, 5, 16), "units"),           # dl > D
+    ((32, 8, 4, 256, 128, 17, 24, 5, 128), "units"),       # 17 layers, layers * dl > 2048
+    ((32, 8, 4, 256, 128, 8, 24, 5, 128), "node"),
+    ((32, 8, 4, 528, 64, 2, 24, 5, 264), "stream"),        # H > 256: the BiLSTM kernels do not hold it
+    ((32, 8, 4, 36, 16, 2, 24, 5, 18), "stream"),          # H % 4 != 0
+    ((32, 8, 4, 64, 16, 2, 26, 5, 32), "stream"),          # Din % 4 != 0: torch's projection
+]
+
+
+def test_plan_picks_the_path():
+    """SMIN._plan, the one decision of a forward's path, on the table above and on the switches and inputs that leave the node."""
+    import models
+    for shape, want in PLAN_ROWS:
+        T, Din, Nq = shape[0], shape[6], shape[7]
+        m = models.SMIN(*shape)
+        assert m._plan(torch.zeros(2, T, Din), torch.zeros(2, Nq, 300)) == want, shape
+    m = models.SMIN(64, 16, 4, 64, 32, 2, 40, 9, 32)
+
+    def plan(v_dtype=torch.float32, q_dtype=torch.float32, frames=64, v_grad=False, q_grad=False):
+        return m._plan(torch.zeros(2, frames, 40, dtype=v_dtype, requires_grad=v_grad), torch.zeros(2, 9, 300, dtype=q_dtype, requires_grad=q_grad))
+    assert plan() == "node"
+    assert plan(torch.float64, torch.float64) == plan(torch.float64) == plan(q_dtype=torch.float64) == "stream"
+    assert plan(frames=32) == "stream"                                                  # T mismatch
+    assert plan(v_grad=True) == plan(q_grad=True) == plan(v_grad=True, q_grad=True) == "stream"
+    m.input_grads = True
+    assert plan(v_grad=True) == plan(v_grad=True, q_grad=True) == "node"
+    m.input_grads = False
+    for obj, name, want in ((m, "fused_core", "stream"), (m, "content_stream", "units"), (m.backbone.queryencoder, "fused_lstm", "stream")):
+        setattr(obj, name, False)
+        assert plan() == want, name
+        setattr(obj, name, True)
+    assert plan() == "node"
+
+
+def test_node_options_name_the_op_arguments():
+    """SMIN._node_options: the keywords of smin_hip::smin_forward.  The parameter products run in csrc/param_prep.hip where its limits
+    hold; the second stream takes the parameter-only work when that is library code or when torch may run beside the contractions
+    (f32 mode only)."""
+    import models
+    lib = models.vml_amd._lib
+    schema = lib.load_torch().smin_forward.default._schema
+    m = models.SMIN(64, 16, 4, 128, 64, 2, 40, 9, 64)
+    assert list(m._node_options()) == [a.name for a in schema.arguments if a.kwarg_only]
+    m.known_cell_count, m.tail_split = 17, False
+    assert m._node_options("packed") == dict(overlap_boundary=True, overlap_prep=True, param_prep_kernel=True, async_weights=True,
+                                             bf16_operand_storage=True, grad_sync=False, known_cell_count=17, tail_split=False,
+                                             input_grads=False, attention="packed")
+    m.grad_sync = True
+    assert m._node_options()["grad_sync"]
+    with torch.no_grad():
+        assert not m._node_options()["grad_sync"]
+    torch_prep = models.SMIN(64, 16, 4, 104, 48, 2, 24, 18, 52)                        # D % 32 != 0: torch forms the products
+    try:
+        for mode, beside in (("f32", True), ("f32e", False)):
+            lib.set_gemm_mode(mode)
+            assert models.SMIN._torch_beside_contractions() == beside, mode
+            assert m._param_prep_kernel() and m._node_options()["overlap_prep"]
+            o = torch_prep._node_options()
+            assert not o["param_prep_kernel"] and o["overlap_prep"] == beside, mode
+    finally:
+        lib.set_gemm_mode("f32")

@@ -68,7 +68,7 @@ def test_input_grads_match_the_reference(dev, case):
     one_node_only(m)
     inp[0].requires_grad_(True)
     inp[2].requires_grad_(True)
-    assert m._native_ok(inp[0], inp[2])
+    assert m._plan(inp[0], inp[2]) == "node"
     pm, ps, pe, pa = m(*inp)
     ((w["wm"] * pm).sum() + (w["ws"] * ps).sum() + (w["we"] * pe).sum() + (w["wa"] * pa).sum()).backward()
     assert cluster_error() == 0
@@ -154,11 +154,11 @@ def test_input_grads_move_nothing_else(dev):
     m.input_grads = False
     inp = [x.clone() for x in H.model_inputs(b)]
     inp[0].requires_grad_(True)
-    assert not m._native_ok(inp[0], inp[2])
+    assert m._plan(inp[0], inp[2]) == "stream"
 
 
 def test_python_host_forms_the_video_gradient(dev):
-    """input_grads with native_host = False: the Python host's fused video encoder returns video_features.grad through
+    """input_grads with fused_core = False: the Python host's fused video encoder returns video_features.grad through
     smin_video_encoder_bwd_input, equal to the one-node step's within 1e-5 relative."""
     from oracle import smin_oracle as O
     T, L, C, D, dl, layers, Din, Nq, Hh, B = 64, 16, 4, 128, 32, 2, 40, 9, 64, 5
@@ -168,7 +168,7 @@ def test_python_host_forms_the_video_gradient(dev):
     grads = []
     for native in (True, False):
         m = build_model(dict(T=T, L=L, C=C, D=D, dl=dl, layers=layers, Din=Din, Nq=Nq, H=Hh), sd, dev)
-        m.input_grads, m.native_host = True, native
+        m.input_grads, m.fused_core = True, native
         inp = H.model_inputs(b)
         inp[0] = inp[0].clone().requires_grad_(True)
         inp[2] = inp[2].clone().requires_grad_(True)

@@ -11,7 +11,7 @@ T, L, C, D, dl, layers, Din, Nq, Hh, B = bench.WORKLOADS[os.environ.get("WL", "l
 B = int(os.environ.get("B", 2))
 torch.manual_seed(43)
 model = models.SMIN(T, L, C, D, dl, layers, Din, Nq, Hh, dev).to(dev)
-model.native_host = False
+model.fused_core = False
 model.overlap_prep = False
 batch = bench.make_batch(B, T, L, Nq, Din, seed=1000, device=dev)
 models.vml_amd.set_gemm_mode(os.environ.get("MODE", "f32e"))

@@ -165,7 +165,7 @@ def load_torch():
     if not os.path.exists(TORCH_LIB_PATH):
         raise SminHipError(
             f"{TORCH_LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
-            "(or set SMIN.native_host = False to drive the same kernels from the Python host)")
+            "(or set SMIN.fused_core = False to drive the same kernels from the Python host)")
     torch.ops.load_library(TORCH_LIB_PATH)
     ops = torch.ops.smin_hip
     if ops.abi_version() != ABI_VERSION:

@@ -2,11 +2,11 @@
 //
 // The reference's operator boundary is the nn.Module surface of models.py; below it the drop-in runs as
 // ONE library call per forward: smin_hip::smin_forward takes the six forward arguments of SMIN.forward
-// (reference models.py:367) plus the module's parameters and runs the whole model as ONE autograd node (SminCore) around the
-// HIP entry points, so the backward pass runs on the autograd engine's thread without the interpreter (DistributedDataParallel
-// hooks fire as usual).  The Python host (video-moment-localization_amd/functional.py, modules.py) binds the same C ABI with
-// ctypes, a node per module; it serves the stand-alone sub-module seams and every in-model call this binding refuses
-// (SMIN.native_host = False, inputs that require grad without the input_grads opt-in, configurations outside the limits of SMIN._native_ok).
+// (reference models.py:367) plus the module's parameters, shape and switches (by name) and runs the whole model as ONE autograd node
+// (SminCore) around the HIP entry points, so the backward pass runs on the autograd engine's thread without the interpreter
+// (DistributedDataParallel hooks fire as usual).  The Python host (video-moment-localization_amd/functional.py, modules.py) binds the
+// same C ABI with ctypes, a node per module; it serves the stand-alone sub-module seams and every in-model call that SMIN._plan does not
+// send here (SMIN.fused_core = False, inputs that require grad without input_grads, configurations outside the node's limits).
 // torch types appear only in this file; libsmin_hip.so knows pointers and sizes.
 //
 // Only the in-model fast path lives here: the content stream on a mask-driven cell list.
@@ -20,7 +20,6 @@
 #include <ATen/core/stack.h>
 
 #include <cmath>
-#include <functional>
 #include <map>
 #include <mutex>
 #include <tuple>
@@ -333,16 +332,19 @@ Tensor sum_list(const std::vector<Tensor>& ts)
 }
 
 struct SminCore : torch::autograd::Function<SminCore> {
+    // The boolean options of smin_forward (the op's keyword arguments, named as the SMIN attributes), built in smin_forward only.
     // F_KEEP_ATTENTION: every layer's word-attention maps leave as extra outputs (not differentiable; the backward ignores them):
     // the content maps dense (B, L, L, C, Nq), or with F_ATTN_PACKED as packed rows [N*C][Nq] followed by the cellmap; the boundary maps (B, L, Nq)
-    enum { F_OVERLAP_BOUNDARY = 1, F_OVERLAP_PREP = 2, F_ASYNC_WEIGHTS = 4, F_BF16_OPERANDS = 8, F_GRAD_SYNC = 16, F_NO_TAIL_SPLIT = 32, F_KEEP_ATTENTION = 64,
-           F_ATTN_PACKED = 128, F_INPUT_GRADS = 256 };
+    enum { F_OVERLAP_BOUNDARY = 1, F_OVERLAP_PREP = 2, F_ASYNC_WEIGHTS = 4, F_BF16_OPERANDS = 8, F_GRAD_SYNC = 16, F_TAIL_SPLIT = 32, F_KEEP_ATTENTION = 64,
+           F_ATTN_PACKED = 128, F_INPUT_GRADS = 256, F_PARAM_PREP_KERNEL = 512 };
     // F_INPUT_GRADS: video_features / query_features may require grad; the backward then returns their gradients in slots 0 and 2
     // (each formed only when autograd asks for it)
-    enum { N_FIXED = 13 };          // forward arguments ahead of the parameter list (tensors and scalars alike take one gradient slot)
+    enum { N_FIXED = 14 };          // forward arguments ahead of the parameter list (tensors and scalars alike take one gradient slot)
 
+    // n_known: the number of valid cells of moment_mask when the caller knows it, else -1
     static variable_list forward(AutogradContext* ctx, Tensor video_features, Tensor video_mask, Tensor query_features, Tensor query_mask, Tensor length_mask,
-                                 Tensor moment_mask, int64_t T, int64_t L, int64_t C, int64_t nl, int64_t maxq, int64_t H, int64_t flags, at::TensorList prm_in)
+                                 Tensor moment_mask, int64_t T, int64_t L, int64_t C, int64_t nl, int64_t maxq, int64_t H, int64_t flags, int64_t n_known,
+                                 at::TensorList prm_in)
     {
         std::vector<Tensor> all;
         for (const Tensor& p : prm_in) all.push_back(cont(p));
@@ -367,7 +369,7 @@ struct SminCore : torch::autograd::Function<SminCore> {
         std::vector<Tensor> bcat(nl);
         Tensor bb;
         hipEvent_t products_ready;
-        const bool prep_kernel = D % 32 == 0 && D <= 1056 && dl % 32 == 0 && nl <= 8;   // limits of csrc/param_prep.hip (else: torch calls)
+        const bool prep_kernel = (flags & F_PARAM_PREP_KERNEL) != 0;                // csrc/param_prep.hip (else: torch calls)
         wait_stream(prep, curs);                                                    // (the optimizer's update of the parameters)
         {
             StreamScope sc(prep);
@@ -408,7 +410,6 @@ struct SminCore : torch::autograd::Function<SminCore> {
         }
         // ---- masks as fp32, query lengths, the cell count, the boundary heads' parameters side by side: one launch (csrc/layout.hip);
         // as torch calls (masks that are not one byte per element) eight launches in front of the query encoder
-        const int64_t n_known = (flags >> 16) - 1;
         Tensor qm = query_mask.reshape({Bq, -1});
         auto bytes = [](const Tensor& t) { return t.element_size() == 1 && t.is_contiguous(); };
         const bool fast_prologue = bytes(video_mask) && bytes(qm) && bytes(length_mask) && bytes(moment_mask) && qm.size(1) == maxq && video_mask.numel() == Bq * Tn &&
@@ -433,7 +434,7 @@ struct SminCore : torch::autograd::Function<SminCore> {
             st.wb = at::stack({loc[2].view({D}), loc[4].view({D}), loc[6].view({D})});
             bb = at::cat({loc[3], loc[5], loc[7]});
             // ---- layout, part 1: the cell count leaves for the host now and is waited for after the backbone is queued -- unless the
-            // caller already knows it (flags >> 16 = count + 1; a captured step: nothing inside may wait for the device)
+            // caller already knows it (n_known; a captured step: nothing inside may wait for the device)
             mm = moment_mask.scalar_type() == at::kBool ? moment_mask : moment_mask.ne(0);
             if (n_known < 0) {
                 host_n = at::empty({1}, at::TensorOptions().dtype(at::kLong).pinned_memory(true));
@@ -666,7 +667,7 @@ struct SminCore : torch::autograd::Function<SminCore> {
         visit_state(st, [&](Tensor& t) { flat.push_back(t); });
         for (auto& p : all) flat.push_back(p);
         ctx->save_for_backward(flat);
-        ctx->saved_data["d"] = std::vector<int64_t>{N, T, L, C, nl, flags, H, Nq_in, prep_kernel ? 1 : 0};
+        ctx->saved_data["d"] = std::vector<int64_t>{N, T, L, C, nl, flags, H, Nq_in};
         // ps / pe / pa leave as three outputs of the node (rows of one buffer), not as selections of one output: the selections'
         // backward nodes cost three zero fills, three copies and two adds between the loss and this node's backward
         if (!keep_maps) return {pm, psea[0], psea[1], psea[2]};
@@ -682,7 +683,7 @@ struct SminCore : torch::autograd::Function<SminCore> {
     {
         auto d = ctx->saved_data["d"].toIntVector();
         const int64_t N = d[0], T = d[1], L = d[2], C = d[3], nl = d[4], flags = d[5], H = d[6], Nq_in = d[7];
-        const bool prep_kernel = d[8] != 0;
+        const bool prep_kernel = (flags & F_PARAM_PREP_KERNEL) != 0;
         auto sv = ctx->get_saved_variables();
         CoreState st;
         size_state(st, nl);
@@ -704,7 +705,7 @@ struct SminCore : torch::autograd::Function<SminCore> {
         std::vector<Tensor> keep;                                                  // main-stream tensors read on wstr: alive until the streams join
         GradSync sync;
         sync.on = (flags & F_GRAD_SYNC) != 0;
-        TORCH_CHECK(!sync.on || prep_kernel, "smin_forward: the in-node gradient exchange needs the parameter-product kernel (D % 32 == 0, D <= 1056, dl % 32 == 0, <= 8 layers)");
+        TORCH_CHECK(!sync.on || prep_kernel, "smin_forward: the in-node gradient exchange needs param_prep_kernel (SMIN._param_prep_kernel)");
         // the inputs' gradients (F_INPUT_GRADS): d video_features = the video encoder's dx, d query_features = LSTM layer 0's dX
         const bool want_dx = (flags & F_INPUT_GRADS) && ctx->needs_input_grad(0), want_dX = (flags & F_INPUT_GRADS) && ctx->needs_input_grad(2);
         TORCH_CHECK(!sync.on || !grad_sync_config().group.empty(), "smin_forward: grad_sync requested but no process group was set (smin_hip::set_grad_sync)");
@@ -798,38 +799,29 @@ struct SminCore : torch::autograd::Function<SminCore> {
         auto mark_on = [](HStream on) { hipEvent_t e = next_event(); TORCH_CHECK(hipEventRecord(e, on.stream()) == hipSuccess, "hipEventRecord failed"); return e; };
         hipEvent_t attn0_done = nullptr;
         hipEvent_t boundary_done = nullptr;                                        // the previous iteration's boundary-unit backward (side stream)
-        static const bool defer_dw0 = std::getenv("SMIN_DEFER_DW0") && std::atoi(std::getenv("SMIN_DEFER_DW0")) != 0;
-        Tensor deferred_dfm;
-        std::function<void(const Tensor&)> deferred_weights;
         for (int64_t k = nl - 1; k >= 0; --k) {
             LayerState& ls = st.layer[k];
             // moment unit: dmu -> d cum (its chain gradient folded in), d bu, weight gradients; the residual gradient is dmu itself
             Tensor dcum = at::empty({N, D}, opt), dfb_mu = at::empty({B, L, D}, opt);
             keep.push_back(dfm); keep.push_back(dcum);
             // (measured: the weight half queued ahead of the input half 21.39 -> 21.15 ms/step, behind it 21.7 -> 21.6)
-            // SMIN_DEFER_DW0=1 (experiment, off): layer 0's (the last one of the loop) held back until the proposal map's gradient is
-            // queued, so that it does not stretch the HBM-bound closing kernels.  Measured WORSE (17.8 vs 17.6 ms): it then runs beside
-            // the cluster LSTM, whose workgroups need a CU's whole LDS and wait for CUs this contraction has drained (177 -> 1225 us).
-            auto moment_weights = [&, k](const Tensor& dfm_in) {
-                LayerState& lsk = st.layer[k];
+            {
                 wait_stream(wstr, curs);
                 StreamScope sc(wstr);
-                Tensor dWcat = prep_kernel ? dWcat_all[k] : at::empty_like(lsk.Wcat), dbcat = prep_kernel ? dbcat_all[k] : at::empty({D}, opt);
+                Tensor dWcat = prep_kernel ? dWcat_all[k] : at::empty_like(ls.Wcat), dbcat = prep_kernel ? dbcat_all[k] : at::empty({D}, opt);
                 auto ws = scratch(smin_workspace_bytes(n, B, 4, D, 4, 1), dev);
-                if (lsk.x1.scalar_type() == at::kBFloat16)
-                    SMIN_CK(smin_moment_unit_bwd_x1h(cur(), fp(dfm_in), fp(lsk.cum), fp(lsk.bu), ip(cells), ip(row_ptr), ip(cellmap), n, B, Li, D, fp(trk(k, TR_CAT)), nullptr, nullptr,
-                                                     fpm(dWcat), fpm(dbcat), ws.p, ws.n, 1, nullptr, reinterpret_cast<const uint16_t*>(lsk.x1.const_data_ptr()), nullptr));
+                if (ls.x1.scalar_type() == at::kBFloat16)
+                    SMIN_CK(smin_moment_unit_bwd_x1h(cur(), fp(dfm), fp(ls.cum), fp(ls.bu), ip(cells), ip(row_ptr), ip(cellmap), n, B, Li, D, fp(trk(k, TR_CAT)), nullptr, nullptr,
+                                                     fpm(dWcat), fpm(dbcat), ws.p, ws.n, 1, nullptr, reinterpret_cast<const uint16_t*>(ls.x1.const_data_ptr()), nullptr));
                 else
-                    SMIN_CK(smin_moment_unit_bwd(cur(), fp(dfm_in), fp(lsk.cum), fp(lsk.bu), ip(cells), ip(row_ptr), ip(cellmap), n, B, Li, D, fp(trk(k, TR_CAT)), nullptr, nullptr,
-                                                 fpm(dWcat), fpm(dbcat), ws.p, ws.n, 1, nullptr, fp(lsk.x1), nullptr));
+                    SMIN_CK(smin_moment_unit_bwd(cur(), fp(dfm), fp(ls.cum), fp(ls.bu), ip(cells), ip(row_ptr), ip(cellmap), n, B, Li, D, fp(trk(k, TR_CAT)), nullptr, nullptr,
+                                                 fpm(dWcat), fpm(dbcat), ws.p, ws.n, 1, nullptr, fp(ls.x1), nullptr));
                 if (!prep_kernel) {
                     dlp(k, L_FB_W) = dWcat.slice(1, 0, D).contiguous().view_as(lp(k, L_FB_W)); dlp(k, L_FC_W) = dWcat.slice(1, D).contiguous().view_as(lp(k, L_FC_W));
                     dlp(k, L_FB_B) = dbcat; dlp(k, L_FC_B) = dbcat;
                 }
                 sync.reduce({dWcat, dbcat}, wstr);                                   // inputs of the parameter-product kernel
-            };
-            if (k == 0 && defer_dw0 && wstr != curs) { deferred_dfm = dfm; deferred_weights = moment_weights; }
-            else moment_weights(dfm);
+            }
             // the previous layer's boundary-unit backward (second stream) is awaited HERE, where its dfb is first read -- not in front of
             // that layer's gate backward, which reads nothing of it any more (it forms the unit's dhbar itself): the main stream sat
             // ~0.6 ms behind the unit's weight contractions at the end of layer 0 (tools/gantt.sh)
@@ -966,13 +958,12 @@ struct SminCore : torch::autograd::Function<SminCore> {
         //   main   : layer 0's gate backward (already queued above), the proposal map's gradient -> df, video encoder, LSTM layers
         // (before: the first two waited for the gate backward and the clip-window pass sat between it and the proposal map on the
         //  main stream -- 0.5 ms longer, tools/gantt.sh)
-        // F_NO_TAIL_SPLIT / SMIN_TAIL_SPLIT=0: the round-2 placement (words on the boundary stream, clip-window gradients on the main
-        // stream).  training.CapturedStep asks for it: a replayed graph pays for the extra streams (tacos.yml captured: 3.5 ms/step
-        // once the process has used them, 2.5 without; eager 2.2) -- and never inside a stream capture.
-        static const bool tail_split_env = !(std::getenv("SMIN_TAIL_SPLIT") && std::atoi(std::getenv("SMIN_TAIL_SPLIT")) == 0);
+        // Without F_TAIL_SPLIT: the round-2 placement (words on the boundary stream, clip-window gradients on the main stream).
+        // training.CapturedStep asks for it: a replayed graph pays for the extra streams (tacos.yml captured: 3.5 ms/step once the
+        // process has used them, 2.5 without; eager 2.2) -- and never inside a stream capture.
         hipStreamCaptureStatus capture = hipStreamCaptureStatusNone;
         TORCH_CHECK(hipStreamIsCapturing(curs.stream(), &capture) == hipSuccess, "hipStreamIsCapturing failed");
-        const bool tail_split = tail_split_env && !(flags & F_NO_TAIL_SPLIT) && capture == hipStreamCaptureStatusNone;
+        const bool tail_split = (flags & F_TAIL_SPLIT) && capture == hipStreamCaptureStatusNone;
         HStream tail = (flags & F_OVERLAP_PREP) ? side_stream(dev.index()) : curs;
         HStream wordst = !(flags & F_OVERLAP_PREP) ? curs : tail_split ? side_stream(dev.index(), 1) : tail;
         HStream cw = tail_split ? tail : curs;                                      // stream of the clip-window gradients
@@ -1054,7 +1045,6 @@ struct SminCore : torch::autograd::Function<SminCore> {
             auto ws3 = scratch((size_t)4 * B * T * std::max<int64_t>(D, nl * dl), dev);
             SMIN_CK(smin_proposal_map_bwd(cur(), nullptr, fp(dfm), fp(dfb_next), ip(cells), ip(row_ptr), ip(cellmap), n, B, Ti, Li, Ci, D, fpm(df), ws3.p, ws3.n, ip(tab.first),
                                           tab.second.data_ptr()));
-            if (deferred_weights) { deferred_weights(deferred_dfm); deferred_weights = nullptr; }
             weights_done = mark(wstr);
             float* dxs[1] = {fpm(df)};
             if (cw != curs) await(curs, dg_done);
@@ -1204,59 +1194,42 @@ struct SminCore : torch::autograd::Function<SminCore> {
 
 // ---------------------------------------------------------------- the model
 
-variable_list smin_forward_impl(const Tensor& video_features, const Tensor& video_mask, const Tensor& query_features, const Tensor& query_mask_in,
-                                const Tensor& length_mask, const Tensor& moment_mask, at::TensorList prm, at::IntArrayRef cfg, int64_t extra_flags)
+// SMIN.forward (reference models.py:367-377): the six forward arguments, the parameters in SMIN._native_params order, the model's
+// shape and, by name, SMIN's switches (SMIN._node_options).  attention: None, or every layer's word-attention maps as well (detached):
+// content[k] = ContentAttention.attn_weights (B, L, L, C, Nq) (models.py:207-226) under "dense", or under "packed" the rows [N*C, Nq] of the
+// cell list followed by the cellmap (B, L, L) int32 (what SMIN.localize gathers from); boundary[k] = Attention.attn_weights (B, L, Nq)
+// (models.py:137-154).  Without attention both lists are empty.
+std::tuple<Tensor, Tensor, Tensor, Tensor, std::vector<Tensor>, std::vector<Tensor>> smin_forward(
+    const Tensor& video_features, const Tensor& video_mask, const Tensor& query_features, const Tensor& query_mask_in, const Tensor& length_mask,
+    const Tensor& moment_mask, at::TensorList prm, int64_t T, int64_t L, int64_t C, int64_t num_smi_layers, int64_t max_query_length, int64_t lstm_hidden_size,
+    bool overlap_boundary, bool overlap_prep, bool param_prep_kernel, bool async_weights, bool bf16_operand_storage, bool grad_sync,
+    std::optional<int64_t> known_cell_count, bool tail_split, bool input_grads, std::optional<c10::string_view> attention)
 {
     TORCH_CHECK(video_features.is_cuda(), "smin_forward runs on a HIP device only (there is no CPU fallback)");
-    TORCH_CHECK(cfg.size() == 16 || cfg.size() == 17, "smin_forward: cfg = [T, L, C, D, dl, layers, max_query_length, H, overlap_boundary, overlap_prep, fused_core, "
-                "async_weights, bf16_operand_storage, grad_sync, known_cell_count or -1, tail_split] [+ input_grads 0 / 1], got ", cfg.size(), " entries");
-    const bool input_grads = cfg.size() == 17 && cfg[16] != 0;
-    TORCH_CHECK(cfg[10] != 0, "smin_forward builds the whole model as one autograd node (cfg[10] = fused_core = 1); a node per module is built by the "
-                "Python host (SMIN.native_host = False)");
     TORCH_CHECK(input_grads || (!video_features.requires_grad() && !query_features.requires_grad()), "smin_forward forms no gradients of video_features / "
-                "query_features unless cfg[16] = input_grads = 1 (SMIN.input_grads = True); otherwise inputs that require grad go through the Python host "
-                "(SMIN.native_host = False)");
+                "query_features unless input_grads = True (SMIN.input_grads); otherwise inputs that require grad go through the Python host "
+                "(SMIN.fused_core = False)");
+    const bool packed = attention && *attention == "packed";
+    TORCH_CHECK(!attention || packed || *attention == "dense", "smin_forward: attention is None, \"dense\" or \"packed\" (got \"", *attention, "\")");
     // The reference's dataset pads queries and their mask to max_query_length (dataset.py:35, 173); a batch cut to its longest query is
     // taken too: the word features are padded in the node as models.py:58-59 does, and the mask here, since every kernel reads max_query_length columns.
     TORCH_CHECK(query_features.dim() == 3, "smin_forward: query_features (B, words, dim)");
+    const int64_t nl = num_smi_layers, maxq = max_query_length;
     Tensor query_mask = query_mask_in.reshape({query_features.size(0), -1});
-    TORCH_CHECK((query_mask.size(1) == query_features.size(1) || query_mask.size(1) == cfg[6]) && query_features.size(1) <= cfg[6], "smin_forward: query_mask has ", query_mask.size(1),
-                " columns for ", query_features.size(1), " words (max_query_length ", cfg[6], ")");
-    if (query_mask.size(1) < cfg[6]) query_mask = at::constant_pad_nd(query_mask, {0, cfg[6] - query_mask.size(1)}, 0);
-    const int64_t T = cfg[0], L = cfg[1], C = cfg[2], nl = cfg[5], maxq = cfg[6], H = cfg[7];
+    TORCH_CHECK((query_mask.size(1) == query_features.size(1) || query_mask.size(1) == maxq) && query_features.size(1) <= maxq, "smin_forward: query_mask has ",
+                query_mask.size(1), " columns for ", query_features.size(1), " words (max_query_length ", maxq, ")");
+    if (query_mask.size(1) < maxq) query_mask = at::constant_pad_nd(query_mask, {0, maxq - query_mask.size(1)}, 0);
     TORCH_CHECK((int64_t)prm.size() == P_LAYER0 + nl * L_COUNT + 8, "smin_forward: expected ", P_LAYER0 + nl * L_COUNT + 8, " parameters, got ", prm.size());
     c10::hip::HIPGuard device_guard(video_features.device().index());
-    const int64_t flags = (cfg[8] != 0 ? SminCore::F_OVERLAP_BOUNDARY : 0) | (cfg[9] != 0 ? SminCore::F_OVERLAP_PREP : 0) | (cfg[11] != 0 ? SminCore::F_ASYNC_WEIGHTS : 0) |
-                          (cfg[12] != 0 ? SminCore::F_BF16_OPERANDS : 0) | (cfg[13] != 0 ? SminCore::F_GRAD_SYNC : 0) | (cfg[15] == 0 ? SminCore::F_NO_TAIL_SPLIT : 0) |
-                          (input_grads ? SminCore::F_INPUT_GRADS : 0) |
-                          (cfg[14] >= 0 ? ((cfg[14] + 1) << 16) : 0) | extra_flags;      // cfg[14]: the number of valid cells, when the caller knows it
-    return SminCore::apply(video_features, video_mask, query_features, query_mask, length_mask, moment_mask, T, L, C, nl, maxq, H, flags, prm);
-}
-
-std::tuple<Tensor, Tensor, Tensor, Tensor> smin_forward(const Tensor& video_features, const Tensor& video_mask, const Tensor& query_features, const Tensor& query_mask,
-                                                        const Tensor& length_mask, const Tensor& moment_mask, at::TensorList prm, at::IntArrayRef cfg)
-{
-    auto out = smin_forward_impl(video_features, video_mask, query_features, query_mask, length_mask, moment_mask, prm, cfg, 0);
-    return std::make_tuple(out[0], out[1], out[2], out[3]);
-}
-
-// smin_forward that also returns every layer's word-attention maps (detached): content[k] = ContentAttention.attn_weights (B, L, L, C, Nq)
-// (models.py:207-226), boundary[k] = Attention.attn_weights (B, L, Nq) (models.py:137-154).  cfg: smin_forward's 16 entries, optionally a 17th:
-// 1 = the content maps packed, content = [probs_0 [N*C, Nq], .., probs_{layers-1}, cellmap (B, L, L) int32] (what SMIN.localize gathers from),
-// and an 18th: smin_forward's input_grads
-std::tuple<Tensor, Tensor, Tensor, Tensor, std::vector<Tensor>, std::vector<Tensor>> smin_forward_with_attention(
-    const Tensor& video_features, const Tensor& video_mask, const Tensor& query_features, const Tensor& query_mask, const Tensor& length_mask,
-    const Tensor& moment_mask, at::TensorList prm, at::IntArrayRef cfg)
-{
-    TORCH_CHECK(cfg.size() >= 16 && cfg.size() <= 18, "smin_forward_with_attention: cfg = smin_forward's 16 entries [+ packed content maps 0 / 1 "
-                "[+ input_grads 0 / 1]], got ", cfg.size(), " entries");
-    const bool packed = cfg.size() >= 17 && cfg[16] != 0;
-    std::vector<int64_t> cfg_core(cfg.begin(), cfg.begin() + 16);
-    if (cfg.size() == 18) cfg_core.push_back(cfg[17]);
-    auto out = smin_forward_impl(video_features, video_mask, query_features, query_mask, length_mask, moment_mask, prm, cfg_core,
-                                 SminCore::F_KEEP_ATTENTION | (packed ? SminCore::F_ATTN_PACKED : 0));
-    const int64_t nl = cfg[5], nc = nl + (packed ? 1 : 0);
-    TORCH_CHECK((int64_t)out.size() == 4 + nc + nl, "smin_forward_with_attention: ", out.size(), " outputs");
+    const int64_t flags = (overlap_boundary ? SminCore::F_OVERLAP_BOUNDARY : 0) | (overlap_prep ? SminCore::F_OVERLAP_PREP : 0) |
+                          (param_prep_kernel ? SminCore::F_PARAM_PREP_KERNEL : 0) | (async_weights ? SminCore::F_ASYNC_WEIGHTS : 0) |
+                          (bf16_operand_storage ? SminCore::F_BF16_OPERANDS : 0) | (grad_sync ? SminCore::F_GRAD_SYNC : 0) |
+                          (tail_split ? SminCore::F_TAIL_SPLIT : 0) | (input_grads ? SminCore::F_INPUT_GRADS : 0) |
+                          (attention ? SminCore::F_KEEP_ATTENTION : 0) | (packed ? SminCore::F_ATTN_PACKED : 0);
+    auto out = SminCore::apply(video_features, video_mask, query_features, query_mask, length_mask, moment_mask, T, L, C, nl, maxq, lstm_hidden_size, flags,
+                               known_cell_count.value_or(-1), prm);
+    const int64_t nc = attention ? nl + (packed ? 1 : 0) : 0, nb = attention ? nl : 0;
+    TORCH_CHECK((int64_t)out.size() == 4 + nc + nb, "smin_forward: ", out.size(), " outputs");
     std::vector<Tensor> content(out.begin() + 4, out.begin() + 4 + nc), boundary(out.begin() + 4 + nc, out.end());
     return std::make_tuple(out[0], out[1], out[2], out[3], content, boundary);
 }
@@ -1273,23 +1246,19 @@ Tensor smin_loss(const Tensor& pm, const Tensor& ym, const Tensor& sm, const Ten
 
 TORCH_LIBRARY(smin_hip, m)
 {
-    // SMIN.forward (reference models.py:367-377): the six forward arguments, the parameters in SMIN._native_params order and
-    // cfg = [T, L, C, D, dl, num_smi_layers, max_query_length, lstm_hidden_size, overlap_boundary, overlap_prep, fused_core (must be 1),
-    //        async_weights, bf16_operand_storage, grad_sync, known_cell_count or -1, tail_split] and optionally input_grads: 1 = video_features /
-    //        query_features may require grad and receive their gradients
+    // SMIN.forward as one autograd node (see smin_forward above)
     m.def("smin_forward(Tensor video_features, Tensor video_mask, Tensor query_features, Tensor query_mask, Tensor length_mask, Tensor moment_mask, "
-          "Tensor[] params, int[] cfg) -> (Tensor, Tensor, Tensor, Tensor)", &smin_forward);
-    // the same node with every layer's word-attention maps as extra, non-differentiable outputs
-    m.def("smin_forward_with_attention(Tensor video_features, Tensor video_mask, Tensor query_features, Tensor query_mask, Tensor length_mask, "
-          "Tensor moment_mask, Tensor[] params, int[] cfg) -> (Tensor, Tensor, Tensor, Tensor, Tensor[], Tensor[])", &smin_forward_with_attention);
+          "Tensor[] params, int T, int L, int C, int num_smi_layers, int max_query_length, int lstm_hidden_size, *, bool overlap_boundary, "
+          "bool overlap_prep, bool param_prep_kernel, bool async_weights, bool bf16_operand_storage, bool grad_sync, int? known_cell_count, "
+          "bool tail_split, bool input_grads, str? attention) -> (Tensor, Tensor, Tensor, Tensor, Tensor[], Tensor[])", &smin_forward);
     // restated loss_fn of the reference's train loop (main.py:110-116), same argument order
     m.def("smin_loss(Tensor pm, Tensor ym, Tensor sm, Tensor moment_mask, Tensor ps, Tensor ys, Tensor ss, Tensor pe, Tensor ye, Tensor se, Tensor pa, Tensor ya, "
           "Tensor length_mask) -> Tensor", &smin_loss);
     m.def("abi_version() -> int", []() -> int64_t { return smin_abi_version(); });
-    // the status word of smin_build_cells_n on a device (non-zero after a step whose cfg[14] cell count did not match its mask)
+    // the status word of smin_build_cells_n on a device (non-zero after a step whose known_cell_count did not match its mask)
     m.def("layout_status(Device device) -> Tensor", [](c10::Device dev) { return layout_status(dev); });
     // data parallel: the process group (c10d group name) the one-node backward averages its gradients over, see GradSync;
-    // cfg[13] of smin_forward switches the exchange on per call.  coalesced_avg: the backend takes grouped "avg" all-reduces (RCCL)
+    // smin_forward's grad_sync switches the exchange on per call.  coalesced_avg: the backend takes grouped "avg" all-reduces (RCCL)
     m.def("set_grad_sync(str group_name, int world, bool coalesced_avg) -> ()", [](std::string group, int64_t world, bool coalesced_avg) {
         GradSyncConfig& c = grad_sync_config();
         c.group = std::move(group); c.world = (int)world; c.coalesced_avg = coalesced_avg;

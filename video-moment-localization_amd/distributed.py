@@ -74,8 +74,9 @@ def wrap(model, device=None, bucket_cap_mb=8):
         # gloo stages every bucket through the host and synchronises the streams a gradient touched: with the two-stream
         # step that serialises the whole backward pass (8x slower, measured); RCCL is unaffected
         model.overlap_boundary = changed["overlap_boundary"] = False
-    one_node = getattr(model, "fused_core", False) and getattr(model, "native_host", False) and not os.environ.get("SMIN_DDP_NO_PREP_OVERLAP")
-    if getattr(model, "overlap_prep", False) and (gloo_on_gpu or not one_node):
+    from .modules import SMIN
+    one_node = isinstance(model, SMIN) and model.fused_core
+    if getattr(model, "overlap_prep", False) and (gloo_on_gpu or not one_node or os.environ.get("SMIN_DDP_NO_PREP_OVERLAP")):
         # a node per module (the Python host): DDP creates every parameter's gradient accumulator on the stream it is constructed on;
         # parameters that the step touches only on the second stream then make the main stream wait at each accumulation (measured +0.7 ms
         # over keeping that work on the main stream; the boundary unit's overlap still pays).  The one-node step hands every
@@ -88,10 +89,7 @@ def wrap(model, device=None, bucket_cap_mb=8):
     # The bf16-core contraction modes keep torch DDP (its all-reduce starts after the node has joined its streams): RCCL's
     # reduction kernels are not built under this library's no-packed-fp32 rule (csrc/Makefile) and have not been
     # checked beside the bf16 contraction kernels on a multi-GPU node, so they do not run beside them.
-    from . import _lib
-    in_node = (getattr(model, "fused_core", False) and getattr(model, "native_host", False) and hasattr(model, "_prep_is_library_code")
-               and model._prep_is_library_code() and not os.environ.get("SMIN_TORCH_DDP")
-               and (_lib.get_gemm_mode() == "f32" or bool(os.environ.get("SMIN_STREAMS_IN_ALL_MODES"))))
+    in_node = one_node and model._param_prep_kernel() and SMIN._torch_beside_contractions() and not os.environ.get("SMIN_TORCH_DDP")
     model.grad_exchange = "in_node" if in_node else "torch_ddp"
     if in_node:
         return InNodeDataParallel(model)

@@ -58,11 +58,16 @@ class VideoEncoder(nn.Module):
         self.ve = nn.Linear(self.d0, self.d)
         self.pe = nn.Embedding(self.T, self.d)
 
+    def fused(self, video_features):
+        """The projection runs on the library's kernels (LinearRowsFn here, VideoFuseFn in Backbone and the one-node step)."""
+        return (video_features.dtype == torch.float32 and self.d0 % 4 == 0 and self.d % 4 == 0
+                and video_features.shape[1] <= self.pe.weight.shape[0])
+
     @_hip_forward
     def forward(self, video_features, video_mask):
         vm = video_mask.float()
         pos = torch.arange(video_mask.shape[1], device=video_features.device)
-        if self.d0 % 4 == 0 and self.d % 4 == 0 and video_features.dtype == torch.float32:
+        if self.fused(video_features):
             B, T, _ = video_features.shape                          # the projection on the library's MFMA engine
             y = LinearRowsFn.apply(self.ve.weight, self.ve.bias, None, None, 1, video_features.reshape(B * T, self.d0)).view(B, T, self.d)
         else:
@@ -96,6 +101,11 @@ class QueryEncoder(nn.Module):
         self.max_query_length, self.lstm_hidden_size = max_query_length, lstm_hidden_size
         self.lstm = nn.LSTM(input_size=300, hidden_size=lstm_hidden_size, num_layers=2, bidirectional=True, batch_first=True)
 
+    def fused(self):
+        """The recurrence runs on the library's BiLSTM layer kernels (csrc/bilstm.hip holds H <= 256, H % 4 == 0)."""
+        H = self.lstm_hidden_size
+        return self.fused_lstm and H <= 256 and H % 4 == 0
+
     @_hip_forward
     def forward(self, query_features, query_mask):
         """Same result as the reference's pack_padded_sequence / pad_packed_sequence round trip, but on padded
@@ -106,7 +116,7 @@ class QueryEncoder(nn.Module):
         B, Nq, _ = query_features.shape
         H = self.lstm_hidden_size
         length = query_mask.reshape(B, -1).sum(1).long()
-        if self.fused_lstm and H <= 256 and H % 4 == 0:
+        if self.fused():
             # one HIP launch per layer runs the whole recurrence, both directions, lengths honoured in-kernel
             # (bilstm.hip): the library path below is ~600 launches of a few microseconds each per train step
             x, len32 = query_features, length.to(torch.int32)
@@ -173,8 +183,7 @@ class Backbone(nn.Module):
         query_features' gradient either way."""
         fs, fw = self.queryencoder(query_features, query_mask)
         ve = self.videoencoder
-        if (video_features.dtype == torch.float32 and ve.d0 % 4 == 0 and ve.d % 4 == 0
-                and video_features.shape[1] <= ve.pe.weight.shape[0]):
+        if ve.fused(video_features):
             # projection + position embedding + mask + Hadamard product with f_s in one contraction (video_encoder.hip)
             B, T, _ = video_features.shape
             f = VideoFuseFn.apply(video_features, ve.ve.weight, ve.ve.bias, ve.pe.weight, video_mask.reshape(B * T).float(), fs, input_grads)
@@ -445,7 +454,8 @@ class SMIN(nn.Module):
         self.smis = nn.ModuleList([SMI(D, dl) for _ in range(num_smi_layers)])
         self.localization = Localization(D)
 
-    native_host = True             # run the in-model path as ONE torch-extension call (csrc/torch_binding.cpp); False: Python host
+    fused_core = True              # run the in-model path as ONE torch-extension call, the whole model one autograd node (False: the Python
+                                   # host, a node per module; _plan says which path a call takes)
     async_weights = True           # ... whose weight-gradient contractions run on a low-priority stream of their own
     known_cell_count = None        # number of valid cells of the next batches' moment_mask, when the caller knows it: the forward then
                                    # asks the device nothing (training.CapturedStep); a wrong value is flagged, see csrc/layout.hip
@@ -454,8 +464,6 @@ class SMIN(nn.Module):
     grad_sync = False              # data parallel: the one-node backward averages its gradients over the process group itself, group by
                                    # group as they become final (set by distributed.wrap; torch_binding.cpp GradSync)
     bf16_operand_storage = True    # under set_gemm_mode("bf16"): tensors that only feed contractions are stored as bf16 (no bit of the step changes)
-    fused_core = True              # ... with proposal map + SMI layers + localization as one autograd node (False: a node per module,
-                                   # which only the Python host builds)
     content_stream = True          # dl < D: keep the content stream in the dl-dimensional space (see _forward_stream)
     overlap_boundary = True        # boundary unit on a second HIP stream beside the content stream
     overlap_prep = True            # parameter-only work (word-side operands, weight products) on that stream as well
@@ -464,9 +472,9 @@ class SMIN(nn.Module):
                                    # smis[k].boundary_unit.attn_layer.attn_weights (B, L, Nq), detached (INTEGRATION.md 3d;
                                    # B*L*L*C*Nq*4 bytes per layer for the content maps)
     input_grads = False            # video_features / query_features that require grad receive their gradients, as under the reference's
-                                   # autograd: the one-node path serves them (torch_binding.cpp F_INPUT_GRADS) and the Python host's fused
-                                   # video encoder forms video_features.grad too.  False: such inputs run the Python host, which forms
-                                   # query_features.grad only (video_features.grad stays None) -- INTEGRATION.md 3e
+                                   # autograd: the one-node path serves them and the Python host's fused video encoder forms
+                                   # video_features.grad too.  False: such inputs run the Python host, which forms query_features.grad only
+                                   # (video_features.grad stays None) -- INTEGRATION.md 3e
 
     def _forward_stream(self, f, fs, fw, query_mask, length_mask, layout, maps=None):
         """The same network with the content unit's two linear maps re-associated (exact in real arithmetic).
@@ -492,7 +500,7 @@ class SMIN(nn.Module):
         # the dl x dl weight products, constants and concatenations: ~100 tiny launches forward, more backward -- is
         # formed up front on the second stream.  Their backward nodes then run there too, off the main stream's chain
         # (nothing on the critical path waits for a parameter gradient).
-        prep = side if (self.overlap_prep and self._streams_allowed("torch")) else cur
+        prep = side if (self.overlap_prep and self._torch_beside_contractions()) else cur
         prep.wait_stream(cur)
         with torch.cuda.stream(prep):
             consts, bsum = [], None
@@ -595,33 +603,45 @@ class SMIN(nn.Module):
         return ps
 
     @staticmethod
-    def _streams_allowed(kind="library"):
-        """Which work may run on the second / third HIP stream beside the main one.
+    def _torch_beside_contractions():
+        """Whether torch's kernels may run on a second HIP stream beside this library's contractions.
 
         Measured on gfx950 (tools/bu_concurrent_probe.py): a wave executing PACKED fp32 arithmetic (v_pk_fma_f32 ...) on
         a SIMD where a wave of another kernel runs v_mfma_f32_32x32x16_bf16 occasionally gets a wrong lane result.  This library is
         built without packed fp32 arithmetic (csrc/Makefile), so its own kernels may overlap in every contraction mode.  torch's
-        kernels (element-wise ops, hipBLASLt, the optimizer) are outside that guarantee: with the bf16-core contraction modes
-        (f32e / bf16x3 / bf16) the parameter-only torch work (kind="torch") stays on the main stream, where nothing runs beside it."""
+        kernels (element-wise ops, hipBLASLt, the optimizer, RCCL) are outside that guarantee: with the bf16-core contraction modes
+        (f32e / bf16x3 / bf16) they stay on the main stream, where nothing runs beside them."""
         from . import _lib
-        return kind == "library" or _lib.get_gemm_mode() == "f32" or bool(os.environ.get("SMIN_STREAMS_IN_ALL_MODES"))
+        return _lib.get_gemm_mode() == "f32" or bool(os.environ.get("SMIN_STREAMS_IN_ALL_MODES"))
 
-    def _prep_is_library_code(self):
-        """The one-node step forms the parameter products with csrc/param_prep.hip when its shape limits hold (torch_binding.cpp):
-        then nothing of torch runs on the second stream and the overlap is safe in every contraction mode."""
-        return self.fused_core and self.D % 32 == 0 and self.D <= 1056 and self.dl % 32 == 0 and len(self.smis) <= 8
+    def _param_prep_kernel(self):
+        """The shape limits of csrc/param_prep.hip, where the one-node step forms the parameter products (else with torch calls): then
+        nothing of torch runs on the second stream and the overlap is safe in every contraction mode."""
+        return self.D % 32 == 0 and self.D <= 1056 and self.dl % 32 == 0 and len(self.smis) <= 8
 
-    def _native_ok(self, video_features, query_features):
-        """The torch-extension path (one autograd node) covers the production configuration: content stream on a mask-driven cell
-        list, fused BiLSTM and video encoder kernels, inputs that need no gradient.  Anything else (fused_core = False, dl >= D, C outside
-        2..4, > 8 layers, H > 256, odd widths, video / query features that require grad unless input_grads) runs the same kernels from the
-        Python host below."""
-        H, ve, nl = self.lstm_hidden_size, self.backbone.videoencoder, len(self.smis)
-        return (self.native_host and self.fused_core and (self.input_grads or not (video_features.requires_grad or query_features.requires_grad))
-                and self.content_stream and self.dl < self.D and 2 <= self.C <= 4 and 1 <= nl <= 8 and nl * self.dl <= 2048
-                and self.backbone.queryencoder.fused_lstm and H <= 256 and H % 4 == 0
-                and video_features.dtype == torch.float32 and query_features.dtype == torch.float32 and ve.d0 % 4 == 0 and ve.d % 4 == 0
-                and video_features.shape[1] == self.T and video_features.shape[1] <= ve.pe.weight.shape[0])
+    def _plan(self, video_features, query_features):
+        """The path of a forward: "node", the one-node torch extension (csrc/torch_binding.cpp); "stream", the Python host with the
+        content stream (_forward_stream); "units", the Python host with the content units as written (ContentUnitFn).
+
+        The node covers the production configuration: the content stream, fused BiLSTM and video encoder kernels, float32 inputs of T
+        frames that need no gradient unless input_grads.  The content stream needs dl < D and the limits of the clip-window-means
+        launch.  (The constructor's limits hold throughout.)"""
+        nl = len(self.smis)
+        if not (self.content_stream and self.dl < self.D and nl <= 8 and nl * self.dl <= 2048):
+            return "units"
+        node = (self.fused_core and (self.input_grads or not (video_features.requires_grad or query_features.requires_grad))
+                and self.backbone.queryencoder.fused() and query_features.dtype == torch.float32
+                and self.backbone.videoencoder.fused(video_features) and video_features.shape[1] == self.T)
+        return "node" if node else "stream"
+
+    def _node_options(self, attention=None):
+        """The keyword arguments of smin_hip::smin_forward for this module's switches; attention: None, "dense" or "packed"."""
+        prep_kernel = self._param_prep_kernel()
+        return dict(overlap_boundary=self.overlap_boundary, overlap_prep=self.overlap_prep and (prep_kernel or self._torch_beside_contractions()),
+                    param_prep_kernel=prep_kernel, async_weights=self.async_weights, bf16_operand_storage=self.bf16_operand_storage,
+                    grad_sync=self.grad_sync and torch.is_grad_enabled(),
+                    known_cell_count=None if self.known_cell_count is None else int(self.known_cell_count), tail_split=self.tail_split,
+                    input_grads=self.input_grads, attention=attention)
 
     def localize(self, video_features, video_mask, query_features, query_mask, length_mask, moment_mask, k=5, nms_thresh=0.5,
                  duration=None, attention=False):
@@ -748,10 +768,6 @@ class SMIN(nn.Module):
             r["times"] = (r["span"] * d) / nr_d.to(torch.float32).reshape(B, 1, 1)
         return r
 
-    def _stream_ok(self):
-        """The Python host's content stream (_forward_stream) applies (else: the units as written, ContentUnitFn)."""
-        return self.content_stream and self.dl < self.D and 2 <= self.C <= 4 and len(self.smis) <= 8 and len(self.smis) * self.dl <= 2048
-
     def _record_attention(self, maps):
         for smi, (cmap, bmap) in zip(self.smis, maps):
             smi.content_unit.attn_layer.attn_weights = cmap
@@ -778,43 +794,34 @@ class SMIN(nn.Module):
             raise ValueError(f"query_mask has {query_mask.shape[1]} columns for {query_features.shape[1]} words (max_query_length {self.max_query_length})")
         if query_mask.shape[1] < self.max_query_length:
             query_mask = torch.nn.functional.pad(query_mask, (0, self.max_query_length - query_mask.shape[1]))
-        if self.grad_sync and not self._streams_allowed("torch"):
+        plan = self._plan(video_features, query_features)
+        if self.grad_sync and not self._torch_beside_contractions():
             raise RuntimeError("SMIN.grad_sync: the in-node gradient exchange runs RCCL beside the contraction kernels and is limited to the exact "
                                "fp32 mode; call distributed.wrap after set_gemm_mode (it then uses torch DDP)")
-        if self.grad_sync and not self._native_ok(video_features, query_features):
+        if self.grad_sync and plan != "node":
             raise RuntimeError("SMIN.grad_sync (distributed.wrap's in-node gradient exchange) needs the one-node extension path; this "
-                               "call does not qualify (see SMIN._native_ok) -- wrap the model with SMIN_TORCH_DDP=1 instead")
-        if self._native_ok(video_features, query_features):
+                               "call does not qualify (see SMIN._plan) -- wrap the model with SMIN_TORCH_DDP=1 instead")
+        if plan == "node":
             from . import _lib
-            cfg = [self.T, self.L, self.C, self.D, self.dl, len(self.smis), self.max_query_length, self.lstm_hidden_size,
-                   int(self.overlap_boundary), int(self.overlap_prep and (self._streams_allowed("torch") or self._prep_is_library_code())), int(self.fused_core),
-                   int(self.async_weights), int(self.bf16_operand_storage), int(self.grad_sync and torch.is_grad_enabled()),
-                   -1 if self.known_cell_count is None else int(self.known_cell_count), int(self.tail_split)]
-            opt_in = [1] if self.input_grads else []
-            if maps is None:
-                return _lib.load_torch().smin_forward(video_features, video_mask, query_features, query_mask, length_mask, moment_mask,
-                                                      self._native_params(), cfg + opt_in)
-            packed = maps.mode == "packed"
-            pm, ps, pe, pa, content, boundary = _lib.load_torch().smin_forward_with_attention(
-                video_features, video_mask, query_features, query_mask, length_mask, moment_mask, self._native_params(), cfg + [int(packed)] + opt_in)
-            if packed:
-                maps.cellmap, content = content[-1], content[:-1]
-            maps.extend(zip(content, boundary))
+            pm, ps, pe, pa, content, boundary = _lib.load_torch().smin_forward(
+                video_features, video_mask, query_features, query_mask, length_mask, moment_mask, self._native_params(), self.T, self.L, self.C,
+                len(self.smis), self.max_query_length, self.lstm_hidden_size, **self._node_options(None if maps is None else maps.mode))
+            if maps is not None:
+                if maps.mode == "packed":
+                    maps.cellmap, content = content[-1], content[:-1]
+                maps.extend(zip(content, boundary))
             return pm, ps, pe, pa
-        if maps is not None and not self._stream_ok():
+        if maps is not None and plan == "units":
             raise RuntimeError("SMIN.keep_attention / localize(attention=True): the word-attention maps come out of the content stream's attention "
-                               "core; this configuration runs the content units as written (ContentUnitFn, see SMIN._stream_ok), which cannot "
+                               "core; this configuration runs the content units as written (ContentUnitFn, see SMIN._plan), which cannot "
                                "deliver them")
         pending = CellLayout.begin(moment_mask)                    # work is driven by moment_mask (SURVEY 8a-0 caveat)
         f, fs, fw = self.backbone(video_features, video_mask, query_features, query_mask, input_grads=self.input_grads)
         layout = pending.finish()                                  # the only host sync of a step; hidden behind the backbone
-        if (self.content_stream and self.dl < self.D and 2 <= self.C <= 4 and layout.all_valid
-                and len(self.smis) <= 8 and len(self.smis) * self.dl <= 2048):    # limits of the clip-window-means launch
+        if plan == "stream":
             if maps is not None:
                 maps.cellmap = layout.cellmap
             return self._forward_stream(f, fs, fw, query_mask, length_mask, layout, maps)
-        if maps is not None:
-            raise RuntimeError("SMIN.keep_attention: this batch runs the content units as written (ContentUnitFn), which cannot deliver the maps")
         fc, fm, fb = self.pgm.forward_packed(f, layout)
         fcmean = fm                                                # mean_c fc: the map's f_m, then each layer's clip mean
         for k, smi in enumerate(self.smis):
