@@ -41,7 +41,8 @@ extern "C" {
  * half's workspace), smin_sample_clips_bwd, smin_embed_tokens_bwd and smin_embed_tokens_bwd_workspace_bytes (deterministic backward
  * passes of the device feeding path); long-video retrieval over overlapping windows -- smin_sample_windows (clip resampling of
  * arbitrary, possibly overlapping row ranges), smin_merge_window_moments (greedy NMS of per-window top-k moments in absolute
- * time), and a masks-only use of smin_build_targets (sm == NULL) */
+ * time), and a masks-only use of smin_build_targets (sm == NULL); forward-only scoring -- smin_score_tail_fwd and
+ * smin_score_tail_ws_bytes (the last layer's moment unit and the map's score head as row dots) */
 #define SMIN_HIP_ABI_VERSION 2
 
 int smin_abi_version(void);
@@ -207,6 +208,23 @@ int smin_moment_unit_bwd_x1h(void* stream, const float* dmu, const float* fcmean
 int smin_score_map_fwd(void* stream, const float* fm, const float* fb, const int32_t* cells, int N, int B, int L, int D,
                        const float* wm, const float* bm, const float* wb, const float* bb, const float* lmask,
                        float* pm, float* psea);
+/* Forward-only tail of a scorer: the LAST layer's content-stream sum, its moment unit (models.py:288-303) and the map's score head
+ * (models.py:337) multiplied out -- nobody but the score head reads the last mu.  With Wcat = [Wfb | Wfc] [D][2D], bcat = bias_fb + bias_fc,
+ * Wc [D][dl], bc = content_unit.linear_c, wm, bm = conv_layer_pm:
+ *   a = Wfb^T wm   c = Wfc^T wm   u = Wc^T c   k0 = bc.c + wm.bcat + bm
+ *   pm[b,i,j] = sigmoid(sum_d a[d] bu[b,i,d] bu[b,j,d] + ccmean[n].u + (cumean[n] + hbar[n]).c + fm[n].wm + k0)   at the listed cells, 0 elsewhere
+ * ccmean [N][dl] the attention core's clip-mean output, cumean [N][D] the clip mean entering the layer, hbar [N][D] the gate's output
+ * (NULL: re-formed from fm and fs [B][D] as smin_gate_fwd does), fm [N][D] the layer's input, bu [B][L][D] its boundary output.
+ * Writes what smin_score_map_fwd writes: pm dense [B][L][L], psea [3][B][L] (the same launch: bit-identical).  The list must be mask-driven
+ * (every listed cell valid).  fp32 FMAs in every gemm mode; summation orders are fixed.  Requires D % 4 == 0, dl % 4 == 0, ws 16-byte
+ * aligned with smin_score_tail_ws_bytes(B, L, D, dl) bytes.  Two stages that share nothing but ws (a, c, u, k0): the vectors, from
+ * the parameters alone, and the cells.  pm == psea == NULL forms the vectors only; Wc == bc == Wcat == bcat == NULL scores the cells
+ * with the vectors an earlier call left in ws (wm is read by both) -- so a host may form the vectors early, on another stream. */
+size_t smin_score_tail_ws_bytes(int B, int L, int D, int dl);
+int smin_score_tail_fwd(void* stream, const float* ccmean, const float* cumean, const float* hbar /* nullable */, const float* fm, const float* fs,
+                        const float* bu, const int32_t* cells, int N, int B, int L, int D, int dl, const float* Wc, const float* bc,
+                        const float* Wcat, const float* bcat, const float* wm, const float* bm, const float* wb /* [3][D] */,
+                        const float* bb /* [3] */, const float* lmask, float* pm, float* psea, void* ws, size_t ws_bytes);
 /* dpm [B][L][L], dpsea [3][B][L] -> dfm [N][D], dfb [B][L][D], dwm [D], dbm [1], dwb [3][D], dbb [3].  Two independent halves
  * (map score: dpm -> dfm, dwm, dbm; boundary heads: dpsea -> dfb, dwb, dbb): dpm == NULL or dpsea == NULL skips one (two streams). */
 int smin_score_map_bwd(void* stream, const float* dpm, const float* dpsea, const float* pm, const float* psea,

@@ -4,7 +4,7 @@ one 2-hour video of 7 200 feature rows, 16 queries on it, default window (T rows
 Prints one JSON line: windows per second of the whole call (planning, resampling, masks, forward, per-window top-k, merge) and
 the merge kernel's own time (HIP events around repeated launches on the final candidate buffers).
 
-    python tools/window_localize_bench.py [--rows 7200] [--queries 16] [--max-batch 64] [--reps 5]
+    python tools/window_localize_bench.py [--rows 7200] [--queries 16] [--max-batch 64] [--reps 5] [--forward-only-scoring]
 """
 import argparse
 import json
@@ -24,6 +24,7 @@ def main():
     ap.add_argument("--max-batch", type=int, default=64)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--k", type=int, default=5)
+    ap.add_argument("--forward-only-scoring", action="store_true", help="SMIN.forward_only_scoring: the windows are scored by SMIN.score")
     a = ap.parse_args()
     import models
     api = models.vml_amd
@@ -31,6 +32,7 @@ def main():
     dev = torch.device("cuda:0")
     torch.manual_seed(0)
     m = models.SMIN(T, L, C, D, dl, layers, Din, Nq, Hh, dev).to(dev).eval()
+    m.forward_only_scoring = a.forward_only_scoring
     raw = torch.randn(a.rows, Din, device=dev)
     qf = torch.randn(a.queries, Nq, 300, device=dev)
     qm = torch.ones(a.queries, Nq, dtype=torch.uint8, device=dev)
@@ -71,7 +73,7 @@ def main():
     torch.cuda.synchronize()
     merge_us = e0.elapsed_time(e1) / nrep * 1e3
     print(json.dumps({"tool": "window_localize_bench", "shape": dict(T=T, L=L, D=D, dl=dl, layers=layers, Din=Din, Nq=Nq),
-                      "rows": a.rows, "queries": a.queries, "windows": windows, "max_batch": a.max_batch, "k": a.k,
+                      "forward_only_scoring": a.forward_only_scoring, "rows": a.rows, "queries": a.queries, "windows": windows, "max_batch": a.max_batch, "k": a.k,
                       "call_s_best": round(best, 4), "call_s_all": [round(x, 4) for x in times],
                       "windows_per_s": round(windows / best, 1), "merge_us_per_call": round(merge_us, 2),
                       "merge_candidates": G * kw, "layout_status": int(api._lib.load_torch().layout_status(dev)[0])}))

@@ -50,6 +50,8 @@ SIGNATURES = {
     "smin_moment_unit_bwd_x1h": [_vp] * 7 + [_i] * 4 + [_vp] * 5 + [_vp, _sz, _i, _vp, _vp, _vp],
     "smin_score_map_fwd": [_vp] * 4 + [_i] * 4 + [_vp] * 7,
     "smin_score_map_bwd": [_vp] * 8 + [_i] * 4 + [_vp] * 3 + [_vp] * 6 + [_vp, _sz],
+    "smin_score_tail_ws_bytes": [_i] * 4,
+    "smin_score_tail_fwd": [_vp] * 8 + [_i] * 5 + [_vp] * 11 + [_vp, _sz],
     "smin_loss_fwd": [_vp] * 14 + [_i] * 2 + [_vp] * 2,
     "smin_loss_bwd": [_vp] * 16 + [_i] * 2 + [_vp] * 4,
     "smin_compute_ious": [_vp] * 6 + [_i] * 2 + [_vp] * 2,
@@ -109,7 +111,7 @@ SIGNATURES = {
 _RESTYPE = {"smin_target_arch": ctypes.c_char_p, "smin_workspace_bytes": _sz,
             "smin_content_attn_bwd_workspace_bytes": _sz, "smin_linear_rows_bwd_workspace_bytes": _sz,
             "smin_bilstm_layer_bwd_workspace_bytes": _sz, "smin_video_encoder_bwd_workspace_bytes": _sz, "smin_embed_tokens_bwd_workspace_bytes": _sz,
-            "smin_word_prep_bwd_workspace_bytes": _sz,
+            "smin_word_prep_bwd_workspace_bytes": _sz, "smin_score_tail_ws_bytes": _sz,
             "smin_col_sum_workspace_bytes": _sz, "smin_top_moments_ws_bytes": _sz, "smin_boundary_unit_bwd_ws_bytes": _sz, "smin_compute_ious_nms_ws_bytes": _sz}
 
 _lib = None
@@ -156,8 +158,8 @@ _torch_ops = None
 
 
 def load_torch():
-    """The torch-extension binding (csrc/torch_binding.cpp): registers torch.ops.smin_hip.{smin_forward, smin_loss} -- the
-    whole forward as one library call with its autograd graph built in C++.  Raises if the library is missing."""
+    """The torch-extension binding (csrc/torch_binding.cpp): registers torch.ops.smin_hip.{smin_forward, smin_score, smin_loss} -- the
+    whole forward as one library call with its autograd graph built in C++, and its forward-only scoring twin.  Raises if the library is missing."""
     global _torch_ops
     if _torch_ops is not None:
         return _torch_ops

@@ -31,6 +31,8 @@ struct ProfScope {
 // already on this device (never lowered; returns the hipError_t of hipFuncSetAttribute, 0 when nothing had to be set)
 int device_cus();
 int lds_optin(const void* kernel, size_t bytes);
+// score_map.hip: the three boundary heads of f_b [B][L][D] into psea [3][B][L], and the dense score map pm [B][L][L] cleared
+int launch_score_heads(hipStream_t st, const float* fb, int B, int L, int D, const float* wb, const float* bb, const float* lmask, float* psea, float* pm);
 }  // namespace smin
 
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }

@@ -121,6 +121,14 @@ void score_heads_bwd_kernel(const float* __restrict__ dpsea, const float* __rest
     if (threadIdx.x == 0) { bpartial[chunk * 3] = bs0; bpartial[chunk * 3 + 1] = bs1; bpartial[chunk * 3 + 2] = bs2; }
 }
 
+// the boundary heads' launch, shared with the forward-only tail (score_tail.hip): psea, and pm cleared
+int launch_score_heads(hipStream_t st, const float* fb, int B, int L, int D, const float* wb, const float* bb, const float* lmask, float* psea, float* pm)
+{
+    hipLaunchKernelGGL(score_heads_fwd_kernel, dim3(cdiv(B * L, 4)), dim3(256), 0, st, fb, B * L, D, wb, bb, lmask, psea, pm, L);
+    SMIN_LAUNCH_CHECK();
+    return 0;
+}
+
 }  // namespace smin
 
 using namespace smin;
@@ -131,8 +139,7 @@ extern "C" int smin_score_map_fwd(void* stream, const float* fm, const float* fb
 {
     hipStream_t st = (hipStream_t)stream;
     SMIN_REQUIRE(D % 4 == 0);
-    hipLaunchKernelGGL(score_heads_fwd_kernel, dim3(cdiv(B * L, 4)), dim3(256), 0, st, fb, B * L, D, wb, bb, lmask, psea, pm, L);
-    SMIN_LAUNCH_CHECK();
+    { int rc = launch_score_heads(st, fb, B, L, D, wb, bb, lmask, psea, pm); if (rc) return rc; }
     if (N > 0) {
         hipLaunchKernelGGL(score_map_fwd_kernel, dim3(cdiv(N, 4)), dim3(256), 0, st, fm, cells, N, L, D, wm, bm, pm);
         SMIN_LAUNCH_CHECK();

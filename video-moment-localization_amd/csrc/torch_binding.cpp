@@ -4,7 +4,8 @@
 // ONE library call per forward: smin_hip::smin_forward takes the six forward arguments of SMIN.forward
 // (reference models.py:367) plus the module's parameters, shape and switches (by name) and runs the whole model as ONE autograd node
 // (SminCore) around the HIP entry points, so the backward pass runs on the autograd engine's thread without the interpreter
-// (DistributedDataParallel hooks fire as usual).  The Python host (video-moment-localization_amd/functional.py, modules.py) binds the
+// (DistributedDataParallel hooks fire as usual); smin_hip::smin_score is the same forward without a node, for callers that only rank
+// (SMIN.score).  The Python host (video-moment-localization_amd/functional.py, modules.py) binds the
 // same C ABI with ctypes, a node per module; it serves the stand-alone sub-module seams and every in-model call that SMIN._plan does not
 // send here (SMIN.fused_core = False, inputs that require grad without input_grads, configurations outside the node's limits).
 // torch types appear only in this file; libsmin_hip.so knows pointers and sizes.
@@ -280,6 +281,7 @@ struct LayerState {
 struct LstmState { Tensor x, Hout, G, Cs, Wih, Whh; };
 struct CoreState {
     Tensor vx, fv, vmaskf, len32, last, f, fw, fs, qmf, lmf, cells, row_ptr, cellmap, Wch_all, what, kb, Mq, uq, shat, pm, psea, fm_out, wb;
+    Tensor tailv;                                              // smin_score only: the tail's vectors (not among the saved tensors)
     LstmState lstm[2];
     std::vector<LayerState> layer;
 };
@@ -341,12 +343,15 @@ struct SminCore : torch::autograd::Function<SminCore> {
     // (each formed only when autograd asks for it)
     enum { N_FIXED = 14 };          // forward arguments ahead of the parameter list (tensors and scalars alike take one gradient slot)
 
+    // The forward pass as a sequence of launches, for the node's forward (scoring = false: every tensor the backward reads stays in `st`)
+    // and for smin_score (scoring = true: forward only -- a layer's tensors are dropped once their last reader is queued, and the last
+    // layer ends in smin_score_tail_fwd instead of its content-stream sum, pair product, moment unit and smin_score_map_fwd).
+    // Fills st.pm / st.psea, the contiguous parameters `all` and the attention maps; returns the number of cells.
     // n_known: the number of valid cells of moment_mask when the caller knows it, else -1
-    static variable_list forward(AutogradContext* ctx, Tensor video_features, Tensor video_mask, Tensor query_features, Tensor query_mask, Tensor length_mask,
-                                 Tensor moment_mask, int64_t T, int64_t L, int64_t C, int64_t nl, int64_t maxq, int64_t H, int64_t flags, int64_t n_known,
-                                 at::TensorList prm_in)
+    static int64_t run(CoreState& st, std::vector<Tensor>& all, std::vector<Tensor>& cmaps, std::vector<Tensor>& bmaps, bool scoring, const Tensor& video_features,
+                       const Tensor& video_mask, const Tensor& query_features, const Tensor& query_mask, const Tensor& length_mask, const Tensor& moment_mask, int64_t T,
+                       int64_t L, int64_t C, int64_t nl, int64_t maxq, int64_t H, int64_t flags, int64_t n_known, at::TensorList prm_in)
     {
-        std::vector<Tensor> all;
         for (const Tensor& p : prm_in) all.push_back(cont(p));
         std::vector<Tensor> prm(all.begin() + P_LAYER0, all.end());                // the SMI layers' and the localization head's parameters
         const at::Device dev = video_features.device();
@@ -359,7 +364,6 @@ struct SminCore : torch::autograd::Function<SminCore> {
         HStream curs = c10::hip::getCurrentHIPStream(dev.index());
         HStream side = (flags & F_OVERLAP_BOUNDARY) ? side_stream(dev.index()) : curs;
         HStream prep = (flags & F_OVERLAP_PREP) ? side : curs;
-        CoreState st;
         size_state(st, nl);
 
         // ---- parameter-only work (weight products, constants, concatenations: ~25 tiny launches) on the second stream from the first
@@ -405,6 +409,14 @@ struct SminCore : torch::autograd::Function<SminCore> {
                     bcat[k] = lp(k, L_FB_B) + lp(k, L_FC_B);
                 }
                 st.Wch_all = nl == 1 ? wch[0] : at::cat(wch);
+            }
+            if (scoring) {
+                // the forward-only tail's vectors (csrc/score_tail.hip): parameters only, so here, beside the LSTM, not in front of the tail
+                const int64_t k = nl - 1;
+                st.tailv = at::empty({(int64_t)smin_score_tail_ws_bytes(B, Li, D, dl)}, opt.dtype(at::kByte));
+                SMIN_CK(smin_score_tail_fwd(cur(), nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, B, Li, D, dl, fp(lp(k, L_C_W)), fp(lp(k, L_C_B)),
+                                            fp(st.layer[k].Wcat), fp(bcat[k]), fp(loc[0]), fp(loc[1]), nullptr, nullptr, nullptr, nullptr, nullptr, st.tailv.data_ptr(),
+                                            (size_t)st.tailv.numel()));
             }
             products_ready = mark(prep);
         }
@@ -490,6 +502,8 @@ struct SminCore : torch::autograd::Function<SminCore> {
             SMIN_CK(smin_bilstm_layer_fwd(cur(), fp(x), fp(ls.Wih), fp(bias), fp(W4), ip(st.len32), B, i32(Nq_in), In, Hh, fpm(ls.G), fpm(ls.Hout), fpm(ls.Cs)));
             x = ls.Hout;
         }
+        if (scoring)                                                               // (main-stream tensors that only the backward reads)
+            for (auto& l : st.lstm) { l.G = Tensor(); l.Cs = Tensor(); }
         Tensor fw = x;
         if (Nq_in < maxq) fw = at::constant_pad_nd(fw, {0, 0, 0, maxq - Nq_in}, 0);
         fw = fw.contiguous();
@@ -543,6 +557,9 @@ struct SminCore : torch::autograd::Function<SminCore> {
         // the main stream waits for every other stream before forward / backward return; (2) no tensor that another stream has
         // touched is released before that final wait (saved for backward, returned, or held in a function-scope list).  A block
         // therefore returns to its stream's pool only after all streams have met, and its next user is ordered behind that.
+        // (scoring releases a layer's tensors earlier, but only behind that layer's join of the two streams and with every reader
+        // queued: a block then goes back to the main stream's pool behind the join, or to the second stream's, whose next stretch
+        // opens with a wait for the main stream.)
 
         // ---- proposal map (f_m, f_b) and every layer's clip-window term of chat
         Tensor fm = at::empty({N, D}, opt), fb = at::empty({B, L, D}, opt);
@@ -565,7 +582,7 @@ struct SminCore : torch::autograd::Function<SminCore> {
         const bool bf16_operands = (flags & F_BF16_OPERANDS) && smin_get_gemm_mode() == 2;
         const bool cc_bf16 = bf16_operands && dl % 8 == 0;
         const bool keep_maps = (flags & F_KEEP_ATTENTION) != 0;
-        std::vector<Tensor> cmaps, bmaps;                                          // the attention maps (F_KEEP_ATTENTION)
+        TORCH_CHECK(!(scoring && keep_maps), "smin_score keeps no attention maps");
         for (int64_t k = 0; k < nl; ++k) {
             LayerState& ls = st.layer[k];
             const bool lastl = k == nl - 1;
@@ -638,17 +655,31 @@ struct SminCore : torch::autograd::Function<SminCore> {
             else
                 SMIN_CK(smin_content_attn_fwd(cur(), fp(chat), ip(cells), ip(row_ptr), n, B, Li, Ci, dl, Nq, fp(st.Mq[k]), fp(st.uq[k]), fp(st.what[k]), fp(st.shat[k]), fp(qmf),
                                               lastl ? nullptr : fpm(ls.cc), fpm(ls.ccmean)));
+            if (scoring && lastl) {
+                // forward only: nobody but the score head reads the last mu, so the content-stream sum, the moment unit and the head
+                // collapse to row dots (csrc/score_tail.hip): no cum, no x1, no mu
+                wait_stream(curs, side);
+                st.pm = at::empty({B, L, L}, opt); st.psea = at::empty({3, B, L}, opt);
+                // (its vectors were formed with the parameter products; hbar is re-formed from fm and fs: measured faster than read)
+                SMIN_CK(smin_score_tail_fwd(cur(), fp(ls.ccmean), fp(cumean), nullptr, fp(fm), fp(fs), fp(ls.bu), ip(cells), n, B, Li, D, dl, nullptr, nullptr, nullptr,
+                                            nullptr, fp(loc[0]), nullptr, fp(st.wb), fp(bb), fp(lmf), fpm(st.pm), fpm(st.psea), st.tailv.data_ptr(),
+                                            (size_t)st.tailv.numel()));
+                break;
+            }
             ls.cum = at::empty({N, D}, opt);
             {
                 const float* xs[1] = {fp(ls.ccmean)};
                 SMIN_CK(smin_linear_rows_fwd(cur(), xs, 1, fp(lp(k, L_C_W)), fp(lp(k, L_C_B)), fp(cumean), fp(ls.hbar), 1, n, D, dl, fpm(ls.cum)));
             }
             wait_stream(curs, side);
-            // f_b[i] * f_b[j], kept for the weight gradient (bf16 under bf16_operands: the layer's largest saved tensor)
+            // f_b[i] * f_b[j], kept for the weight gradient (bf16 under bf16_operands: the layer's largest saved tensor); a scorer has
+            // no use for it and lets the contraction form the product as it loads (measured faster there)
             const bool x1h = bf16_operands;
-            ls.x1 = x1h ? at::empty({N, D}, opt.dtype(at::kBFloat16)) : at::empty_like(fm);
             Tensor mu = at::empty_like(fm);
-            if (x1h) {
+            if (!scoring) ls.x1 = x1h ? at::empty({N, D}, opt.dtype(at::kBFloat16)) : at::empty_like(fm);
+            if (scoring) {
+                SMIN_CK(smin_moment_unit_fwd(cur(), fp(ls.cum), fp(fm), fp(ls.bu), ip(cells), n, B, Li, D, fp(ls.Wcat), fp(bcat[k]), fpm(mu), nullptr));
+            } else if (x1h) {
                 uint16_t* xh = reinterpret_cast<uint16_t*>(ls.x1.data_ptr());
                 SMIN_CK(smin_pair_product_bf16(cur(), fp(ls.bu), ip(cells), n, Li, D, xh));
                 SMIN_CK(smin_moment_unit_fwd_x1h(cur(), fp(ls.cum), fp(fm), fp(ls.bu), ip(cells), n, B, Li, D, fp(ls.Wcat), fp(bcat[k]), fpm(mu), xh));
@@ -657,11 +688,33 @@ struct SminCore : torch::autograd::Function<SminCore> {
                 SMIN_CK(smin_moment_unit_fwd(cur(), fp(ls.cum), fp(fm), fp(ls.bu), ip(cells), n, B, Li, D, fp(ls.Wcat), fp(bcat[k]), fpm(mu), fp(ls.x1)));
             }
             fm = mu; cumean = ls.cum; fb = ls.bu;
+            if (scoring) {
+                // The streams have met (the join above) and every reader of this layer's tensors is queued: all of them go except what the
+                // later layers read -- its attention output cc (in `st`), mu, cum and bu (held by fm, cumean, fb), the running gate sum
+                LayerState keep;
+                keep.cc = ls.cc;
+                ls = keep;
+            }
         }
+        if (scoring) return N;
         // Localization (models.py:335-344)
         Tensor pm = at::empty({B, L, L}, opt), psea = at::empty({3, B, L}, opt);
         SMIN_CK(smin_score_map_fwd(cur(), fp(fm), fp(fb), ip(cells), n, B, Li, D, fp(loc[0]), fp(loc[1]), fp(st.wb), fp(bb), fp(lmf), fpm(pm), fpm(psea)));
         st.pm = pm; st.psea = psea; st.fm_out = fm;
+        return N;
+    }
+
+    static variable_list forward(AutogradContext* ctx, Tensor video_features, Tensor video_mask, Tensor query_features, Tensor query_mask, Tensor length_mask,
+                                 Tensor moment_mask, int64_t T, int64_t L, int64_t C, int64_t nl, int64_t maxq, int64_t H, int64_t flags, int64_t n_known,
+                                 at::TensorList prm_in)
+    {
+        CoreState st;
+        std::vector<Tensor> all, cmaps, bmaps;                                     // the parameters; the attention maps (F_KEEP_ATTENTION)
+        const int64_t N = run(st, all, cmaps, bmaps, false, video_features, video_mask, query_features, query_mask, length_mask, moment_mask, T, L, C, nl, maxq, H, flags,
+                              n_known, prm_in);
+        const bool keep_maps = (flags & F_KEEP_ATTENTION) != 0;
+        const int64_t Nq_in = query_features.size(1);
+        const Tensor &pm = st.pm, &psea = st.psea, &cellmap = st.cellmap;
 
         variable_list flat;
         visit_state(st, [&](Tensor& t) { flat.push_back(t); });
@@ -1194,6 +1247,18 @@ struct SminCore : torch::autograd::Function<SminCore> {
 
 // ---------------------------------------------------------------- the model
 
+// The reference's dataset pads queries and their mask to max_query_length (dataset.py:35, 173); a batch cut to its longest query is
+// taken too: the word features are padded in the node as models.py:58-59 does, and the mask here, since every kernel reads max_query_length columns.
+Tensor padded_query_mask(const char* op, const Tensor& query_features, const Tensor& query_mask_in, int64_t maxq)
+{
+    TORCH_CHECK(query_features.dim() == 3, op, ": query_features (B, words, dim)");
+    Tensor query_mask = query_mask_in.reshape({query_features.size(0), -1});
+    TORCH_CHECK((query_mask.size(1) == query_features.size(1) || query_mask.size(1) == maxq) && query_features.size(1) <= maxq, op, ": query_mask has ",
+                query_mask.size(1), " columns for ", query_features.size(1), " words (max_query_length ", maxq, ")");
+    if (query_mask.size(1) < maxq) query_mask = at::constant_pad_nd(query_mask, {0, maxq - query_mask.size(1)}, 0);
+    return query_mask;
+}
+
 // SMIN.forward (reference models.py:367-377): the six forward arguments, the parameters in SMIN._native_params order, the model's
 // shape and, by name, SMIN's switches (SMIN._node_options).  attention: None, or every layer's word-attention maps as well (detached):
 // content[k] = ContentAttention.attn_weights (B, L, L, C, Nq) (models.py:207-226) under "dense", or under "packed" the rows [N*C, Nq] of the
@@ -1211,14 +1276,8 @@ std::tuple<Tensor, Tensor, Tensor, Tensor, std::vector<Tensor>, std::vector<Tens
                 "(SMIN.fused_core = False)");
     const bool packed = attention && *attention == "packed";
     TORCH_CHECK(!attention || packed || *attention == "dense", "smin_forward: attention is None, \"dense\" or \"packed\" (got \"", *attention, "\")");
-    // The reference's dataset pads queries and their mask to max_query_length (dataset.py:35, 173); a batch cut to its longest query is
-    // taken too: the word features are padded in the node as models.py:58-59 does, and the mask here, since every kernel reads max_query_length columns.
-    TORCH_CHECK(query_features.dim() == 3, "smin_forward: query_features (B, words, dim)");
     const int64_t nl = num_smi_layers, maxq = max_query_length;
-    Tensor query_mask = query_mask_in.reshape({query_features.size(0), -1});
-    TORCH_CHECK((query_mask.size(1) == query_features.size(1) || query_mask.size(1) == maxq) && query_features.size(1) <= maxq, "smin_forward: query_mask has ",
-                query_mask.size(1), " columns for ", query_features.size(1), " words (max_query_length ", maxq, ")");
-    if (query_mask.size(1) < maxq) query_mask = at::constant_pad_nd(query_mask, {0, maxq - query_mask.size(1)}, 0);
+    Tensor query_mask = padded_query_mask("smin_forward", query_features, query_mask_in, maxq);
     TORCH_CHECK((int64_t)prm.size() == P_LAYER0 + nl * L_COUNT + 8, "smin_forward: expected ", P_LAYER0 + nl * L_COUNT + 8, " parameters, got ", prm.size());
     c10::hip::HIPGuard device_guard(video_features.device().index());
     const int64_t flags = (overlap_boundary ? SminCore::F_OVERLAP_BOUNDARY : 0) | (overlap_prep ? SminCore::F_OVERLAP_PREP : 0) |
@@ -1232,6 +1291,28 @@ std::tuple<Tensor, Tensor, Tensor, Tensor, std::vector<Tensor>, std::vector<Tens
     TORCH_CHECK((int64_t)out.size() == 4 + nc + nb, "smin_forward: ", out.size(), " outputs");
     std::vector<Tensor> content(out.begin() + 4, out.begin() + 4 + nc), boundary(out.begin() + 4 + nc, out.end());
     return std::make_tuple(out[0], out[1], out[2], out[3], content, boundary);
+}
+
+// SMIN.score: the same model forward only, not an autograd node.  The launches of smin_forward in the same order on
+// the same two streams up to the last layer's attention core; then smin_score_tail_fwd.  Outputs as smin_forward's first four.
+std::tuple<Tensor, Tensor, Tensor, Tensor> smin_score(
+    const Tensor& video_features, const Tensor& video_mask, const Tensor& query_features, const Tensor& query_mask_in, const Tensor& length_mask,
+    const Tensor& moment_mask, at::TensorList prm, int64_t T, int64_t L, int64_t C, int64_t num_smi_layers, int64_t max_query_length, int64_t lstm_hidden_size,
+    bool overlap_boundary, bool overlap_prep, bool param_prep_kernel, bool bf16_operand_storage, std::optional<int64_t> known_cell_count)
+{
+    TORCH_CHECK(video_features.is_cuda(), "smin_score runs on a HIP device only (there is no CPU fallback)");
+    at::NoGradGuard no_grad;
+    const int64_t nl = num_smi_layers;
+    Tensor query_mask = padded_query_mask("smin_score", query_features, query_mask_in, max_query_length);
+    TORCH_CHECK((int64_t)prm.size() == P_LAYER0 + nl * L_COUNT + 8, "smin_score: expected ", P_LAYER0 + nl * L_COUNT + 8, " parameters, got ", prm.size());
+    c10::hip::HIPGuard device_guard(video_features.device().index());
+    const int64_t flags = (overlap_boundary ? SminCore::F_OVERLAP_BOUNDARY : 0) | (overlap_prep ? SminCore::F_OVERLAP_PREP : 0) |
+                          (param_prep_kernel ? SminCore::F_PARAM_PREP_KERNEL : 0) | (bf16_operand_storage ? SminCore::F_BF16_OPERANDS : 0);
+    CoreState st;
+    std::vector<Tensor> all, cmaps, bmaps;
+    SminCore::run(st, all, cmaps, bmaps, true, video_features.detach(), video_mask, query_features.detach(), query_mask, length_mask, moment_mask, T, L, C, nl,
+                  max_query_length, lstm_hidden_size, flags, known_cell_count.value_or(-1), prm);
+    return std::make_tuple(st.pm, st.psea[0], st.psea[1], st.psea[2]);
 }
 
 Tensor smin_loss(const Tensor& pm, const Tensor& ym, const Tensor& sm, const Tensor& moment_mask, const Tensor& ps, const Tensor& ys, const Tensor& ss, const Tensor& pe,
@@ -1251,6 +1332,10 @@ TORCH_LIBRARY(smin_hip, m)
           "Tensor[] params, int T, int L, int C, int num_smi_layers, int max_query_length, int lstm_hidden_size, *, bool overlap_boundary, "
           "bool overlap_prep, bool param_prep_kernel, bool async_weights, bool bf16_operand_storage, bool grad_sync, int? known_cell_count, "
           "bool tail_split, bool input_grads, str? attention) -> (Tensor, Tensor, Tensor, Tensor, Tensor[], Tensor[])", &smin_forward);
+    // SMIN.score: the forward-only scoring path, the last layer collapsed to row dots (see smin_score above)
+    m.def("smin_score(Tensor video_features, Tensor video_mask, Tensor query_features, Tensor query_mask, Tensor length_mask, Tensor moment_mask, "
+          "Tensor[] params, int T, int L, int C, int num_smi_layers, int max_query_length, int lstm_hidden_size, *, bool overlap_boundary, "
+          "bool overlap_prep, bool param_prep_kernel, bool bf16_operand_storage, int? known_cell_count) -> (Tensor, Tensor, Tensor, Tensor)", &smin_score);
     // restated loss_fn of the reference's train loop (main.py:110-116), same argument order
     m.def("smin_loss(Tensor pm, Tensor ym, Tensor sm, Tensor moment_mask, Tensor ps, Tensor ys, Tensor ss, Tensor pe, Tensor ye, Tensor se, Tensor pa, Tensor ya, "
           "Tensor length_mask) -> Tensor", &smin_loss);

@@ -620,3 +620,38 @@ def gemm_nt(a, b):
     c = a.new_empty((M, N))
     call("smin_gemm_nt", stream(), ptr(a), ptr(b), ptr(c), M, N, K)
     return c
+
+
+# ---------------------------------------------------------------- forward-only scoring tail (csrc/score_tail.hip)
+def score_tail_torch(ccmean, cumean, hbar, fm, bu, b_idx, i_idx, j_idx, Wc, bc, Wfb, Wfc, bcat, wm, bm):
+    """The last layer's content-stream sum, moment unit and the map's score head collapsed to row dots, as csrc/score_tail.hip forms
+    them (a torch restatement in the dtype of its arguments): the logits of the listed cells n = (b_idx, i_idx, j_idx).
+
+    a = Wfb^T w, c = Wfc^T w, u = Wc^T c, k0 = bc.c + w.bcat + beta;
+    logit[n] = sum_d a[d] bu[b,i,d] bu[b,j,d] + ccmean[n].u + (cumean[n] + hbar[n]).c + fm[n].w + k0."""
+    a, c = Wfb.t() @ wm, Wfc.t() @ wm
+    u = Wc.t() @ c
+    k0 = bc @ c + wm @ bcat + bm.reshape(())
+    pair = ((bu[b_idx, i_idx] * a) * bu[b_idx, j_idx]).sum(-1)
+    return pair + ccmean @ u + (cumean + hbar) @ c + fm @ wm + k0
+
+
+def score_tail(ccmean, cumean, hbar, fm, fs, bu, cells, Wc, bc, Wcat, bcat, wm, bm, wb, bb, lmask, split=False):
+    """smin_score_tail_fwd through the C ABI: (pm [B][L][L], psea [3][B][L]).  hbar None: re-formed from fm and fs.  split: issued as
+    its two stages, the vectors first (pm == psea == NULL), then the cells without the unit's parameters."""
+    B, L, D = bu.shape
+    N, dl = ccmean.shape
+    pm = torch.empty((B, L, L), dtype=torch.float32, device=bu.device)
+    psea = torch.empty((3, B, L), dtype=torch.float32, device=bu.device)
+    nbytes = _lib.load().smin_score_tail_ws_bytes(B, L, D, dl)
+    ws = _lib.workspace(nbytes, bu.device)
+
+    def issue(Wc, bc, Wcat, bcat, pm, psea):
+        call("smin_score_tail_fwd", stream(), ptr(ccmean), ptr(cumean), ptr(hbar), ptr(fm), ptr(fs), ptr(bu), ptr(cells), N, B, L, D, dl, ptr(Wc), ptr(bc),
+             ptr(Wcat), ptr(bcat), ptr(wm), ptr(bm), ptr(wb), ptr(bb), ptr(lmask), ptr(pm), ptr(psea), ptr(ws), ws.numel())
+    if split:
+        issue(Wc, bc, Wcat, bcat, None, None)
+        issue(None, None, None, None, pm, psea)
+    else:
+        issue(Wc, bc, Wcat, bcat, pm, psea)
+    return pm, psea

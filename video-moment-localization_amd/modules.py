@@ -471,6 +471,8 @@ class SMIN(nn.Module):
                                    # smis[k].content_unit.attn_layer.attn_weights (B, L, L, C, Nq) and
                                    # smis[k].boundary_unit.attn_layer.attn_weights (B, L, Nq), detached (INTEGRATION.md 3d;
                                    # B*L*L*C*Nq*4 bytes per layer for the content maps)
+    forward_only_scoring = False   # localize (without attention=True) and localize_windows take their scores from score(): the forward-only
+                                   # path whose last layer is collapsed to row dots.  False: they run forward under no_grad
     input_grads = False            # video_features / query_features that require grad receive their gradients, as under the reference's
                                    # autograd: the one-node path serves them and the Python host's fused video encoder forms
                                    # video_features.grad too.  False: such inputs run the Python host, which forms query_features.grad only
@@ -643,9 +645,40 @@ class SMIN(nn.Module):
                     known_cell_count=None if self.known_cell_count is None else int(self.known_cell_count), tail_split=self.tail_split,
                     input_grads=self.input_grads, attention=attention)
 
+    def _score_options(self):
+        """The keyword arguments of smin_hip::smin_score for this module's switches."""
+        prep_kernel = self._param_prep_kernel()
+        return dict(overlap_boundary=self.overlap_boundary, overlap_prep=self.overlap_prep and (prep_kernel or self._torch_beside_contractions()),
+                    param_prep_kernel=prep_kernel, bf16_operand_storage=self.bf16_operand_storage,
+                    known_cell_count=None if self.known_cell_count is None else int(self.known_cell_count))
+
+    @_hip_forward
+    def score(self, video_features, video_mask, query_features, query_mask, length_mask, moment_mask):
+        """(pm, ps, pe, pa) as forward returns them, without a graph: detached, same shapes, dtypes and contiguity.
+
+        Where a forward would take the one-node path (_plan) and keep_attention is off, this is smin_hip::smin_score: the same
+        launches on the same two streams, every layer's tensors dropped once their last reader is queued, and the last layer's
+        content-stream sum, moment unit and score head collapsed to row dots (csrc/score_tail.hip; exact in real arithmetic, so
+        the scores agree with forward's to fp32 rounding, not bit for bit).  Every other configuration scores as forward does
+        under torch.no_grad(), bit for bit."""
+        with torch.no_grad():
+            if self.keep_attention or self._plan(video_features, query_features) != "node":
+                return self(video_features, video_mask, query_features, query_mask, length_mask, moment_mask)
+            query_mask = query_mask.reshape(query_features.shape[0], -1)
+            if query_mask.shape[1] != query_features.shape[1] or query_mask.shape[1] > self.max_query_length:
+                raise ValueError(f"query_mask has {query_mask.shape[1]} columns for {query_features.shape[1]} words (max_query_length {self.max_query_length})")
+            from . import _lib
+            return _lib.load_torch().smin_score(
+                video_features, video_mask, query_features, query_mask, length_mask, moment_mask, self._native_params(), self.T, self.L, self.C,
+                len(self.smis), self.max_query_length, self.lstm_hidden_size, **self._score_options())
+
+    def _scores(self, *inputs):
+        """The scores retrieval ranks (under no_grad): score() with forward_only_scoring, else the forward."""
+        return self.score(*inputs) if self.forward_only_scoring else self(*inputs)
+
     def localize(self, video_features, video_mask, query_features, query_mask, length_mask, moment_mask, k=5, nms_thresh=0.5,
                  duration=None, attention=False):
-        """The k best moments per sample: the forward under torch.no_grad(), then moments.top_moments of its (pm, ps, pe) -- greedy
+        """The k best moments per sample: the forward under torch.no_grad() (score() with forward_only_scoring), then moments.top_moments of its (pm, ps, pe) -- greedy
         temporal NMS at ``nms_thresh`` over the valid cells of ``moment_mask``.  Returns top_moments' dict (``idx`` (B, k, 2) start
         / end clip, ``score``, ``count``; with ``duration`` (B,) seconds also ``times`` (B, k, 2) in seconds).
 
@@ -658,7 +691,7 @@ class SMIN(nn.Module):
                 maps = _AttnMaps("packed")
                 pm, ps, pe, _ = self._forward(video_features, video_mask, query_features, query_mask, length_mask, moment_mask, maps)
             else:
-                pm, ps, pe, _ = self(video_features, video_mask, query_features, query_mask, length_mask, moment_mask)
+                pm, ps, pe, _ = self._scores(video_features, video_mask, query_features, query_mask, length_mask, moment_mask)
             r = top_moments(pm, ps, pe, moment_mask, k=k, nms_thresh=nms_thresh, duration=duration)
             if attention:
                 r["content_attention"], r["boundary_attention"] = attn_maps_gather([c for c, _ in maps], [b for _, b in maps], maps.cellmap,
@@ -674,7 +707,7 @@ class SMIN(nn.Module):
         ``raw`` (R, Din) HIP float32 tensor of V videos' rows back to back, ``lengths`` their V row counts (host); ``query_features``
         (B, Nq, E) / ``query_mask`` the B pairs' queries, ``video_index`` (B,) host ints (default arange(V), B == V) maps a pair to
         its video (the rows are not copied per pair).  Windows are processed in chunks of ``max_batch``: sample_windows, the masks
-        from nfeats, one forward under no_grad, top_moments; then one merge (moments.merge_window_moments).  The plan is host
+        from nfeats, one forward under no_grad (score() with forward_only_scoring), top_moments; then one merge (moments.merge_window_moments).  The plan is host
         arithmetic, so each chunk's valid-cell count is handed to the forward (``known_cell_count``) and nothing is read back.
 
         Returns a dict: ``span`` (B, k, 2) float32 raw rows of the video (NaN for empty slots), ``score`` (B, k), ``window`` (B, k)
@@ -752,7 +785,7 @@ class SMIN(nn.Module):
                     rows = po_d[c0:c1]
                     qf, qm = query_features.index_select(0, rows), query_mask.index_select(0, rows)
                     self.known_cell_count = int(cells[c0:c1].sum())
-                    pm, ps, pe, _ = self(vf, m["video_mask"], qf, qm, m["length_mask"], m["moment_mask"])
+                    pm, ps, pe, _ = self._scores(vf, m["video_mask"], qf, qm, m["length_mask"], m["moment_mask"])
                     mm = m["moment_mask"]
                     nbytes = _lib.load().smin_top_moments_ws_bytes(g, L, k_window)
                     ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
