@@ -42,7 +42,8 @@ extern "C" {
  * passes of the device feeding path); long-video retrieval over overlapping windows -- smin_sample_windows (clip resampling of
  * arbitrary, possibly overlapping row ranges), smin_merge_window_moments (greedy NMS of per-window top-k moments in absolute
  * time), and a masks-only use of smin_build_targets (sm == NULL); forward-only scoring -- smin_score_tail_fwd and
- * smin_score_tail_ws_bytes (the last layer's moment unit and the map's score head as row dots) */
+ * smin_score_tail_ws_bytes (the last layer's moment unit and the map's score head as row dots); an epoch's metric and loss totals
+ * kept on the device -- smin_epoch_meter_update and smin_epoch_meter_ws_bytes */
 #define SMIN_HIP_ABI_VERSION 2
 
 int smin_abi_version(void);
@@ -346,6 +347,26 @@ size_t smin_compute_ious_nms_ws_bytes(int B, int L, int k, int nn, int nm);
 int smin_compute_ious_nms(void* stream, const float* pm, const float* ps, const float* pe, const uint8_t* mm, const float* sm,
                           int B, int L, int k, float nms_thresh, const int* n_list, int nn, const float* m_list, int nm,
                           float* counts, void* ws, size_t ws_bytes);
+
+/* ---- epoch meter (csrc/metrics.hip): the two metrics above, accumulated over the batches of an epoch in device memory, with no
+ * host read per batch.  acc [4 + nn * nm] doubles, zeroed by the caller before the first update:
+ *   [0] samples seen;  [1] sum of (double)loss[0] * B over the updates that passed a loss;  [2] samples of those updates;
+ *   [3] sum of the top-1 IoU;  [4 + a * nm + c] samples with a hit for (n_list[a], m_list[c]).
+ * rule 0: the reference's rule, exactly smin_compute_ious (score times mask, top five of all L*L cells); accepted only with
+ *   k = 5, n_list = {1, 5}, m_list = {0.1f, 0.3f, 0.5f, 0.7f} and L*L >= 5; nms_thresh is not read.
+ * rule 1: valid cells with greedy temporal NMS, exactly smin_compute_ious_nms (k >= max(n_list), k <= 64, nn <= 64, nm <= 16;
+ *   nms_thresh >= 1: plain top-k).
+ * Top-1 IoU of a sample, both rules: sm at its first kept cell, 0 if it keeps none.
+ * Arithmetic: the per-sample stage is the one of the two entry points above (one workgroup per sample; fp32 hit flags 0 / 1 and the
+ * top-1 IoU per sample in ws).  One closing wave then forms, for each slot, s = 0.0; for b = 0 .. B-1: s += (double)x[b]; and adds
+ * acc[slot] += s (slots 0 and 2: x[b] = 1); the loss slot is acc[1] += (double)loss[0] * (double)B.  loss: device [1] or NULL (then
+ * slots 1 and 2 stay).  No atomics, no host read: everything is ordered by the stream, so ALL UPDATES OF ONE acc MUST BE ISSUED ON
+ * ONE STREAM (or be ordered by events), and a reader of acc must be ordered behind the last update.  n_list / m_list: host arrays.
+ * _ws_bytes returns 0 when the arguments are rejected. */
+size_t smin_epoch_meter_ws_bytes(int B, int L, int rule, int k, int nn, int nm);
+int smin_epoch_meter_update(void* stream, const float* pm, const float* ps, const float* pe, const uint8_t* mm, const float* sm,
+                            int B, int L, int rule, int k, float nms_thresh, const int* n_list, int nn, const float* m_list, int nm,
+                            const float* loss, double* acc, void* ws, size_t ws_bytes);
 
 /* ---- content stream (reference models.py:242-276 + 115-119, re-associated): the content unit's output
  *   f_c' = m*(cc Wc^T + bc) + f_c + hbar   (models.py:269-276)

@@ -3,6 +3,10 @@
 // One workgroup per sample: per-thread running top-5 over the streamed scores, then five rounds of block arg-max over the
 // candidates (ties -> lowest flat index; torch.topk leaves tie order unspecified, so ties are "parity unpinned"), then the
 // 2 x 4 hit flags; a second pass sums the samples.  One host read per call.  No limit on L.
+//
+// The epoch meter (smin_epoch_meter_update, include/smin_hip.h) runs the same per-sample stage -- this file's for the reference's
+// rule, moments.hip's for the NMS rule -- and closes with one wave that adds the batch's sums to an fp64 accumulator in device
+// memory: no host read per batch, no atomics, the order of every sum fixed.
 #include "common.h"
 #include "smin_hip.h"
 
@@ -13,7 +17,7 @@ __device__ __forceinline__ bool better(float v, int k, float bv, int bi) { retur
 
 __global__ __launch_bounds__(256)
 void ious_kernel(const float* __restrict__ pm, const float* __restrict__ ps, const float* __restrict__ pe, const uint8_t* __restrict__ mm,
-                 const float* __restrict__ sm, int L, float* __restrict__ hits /* [B][8] */)
+                 const float* __restrict__ sm, int L, float* __restrict__ hits /* [B][8] */, float* __restrict__ top1 /* [B] or null */)
 {
     // Any L: each thread streams its share of the L*L scores keeping its own five best in registers (no score buffer, so
     // the 512 x 512 long-video map costs the same LDS as a 16 x 16 one); the 256 x 5 candidates then go through five rounds
@@ -67,6 +71,7 @@ void ious_kernel(const float* __restrict__ pm, const float* __restrict__ ps, con
         for (int r = 0; r < nn; ++r) hit = hit || top[r] > thr;
         hits[(size_t)b * 8 + t] = hit ? 1.f : 0.f;
     }
+    if (t == 0 && top1) top1[b] = top[0];                       // the meter's top-1 IoU: sm at the best cell
 }
 
 __global__ void ious_sum_kernel(const float* __restrict__ hits, int B, float* __restrict__ out)
@@ -78,6 +83,37 @@ __global__ void ious_sum_kernel(const float* __restrict__ hits, int B, float* __
     out[t] = s;
 }
 
+// Closing pass of the epoch meter: one wave, thread per slot of acc [4 + npairs].  Each slot's batch sum is formed in fp64 over
+// the samples in order, then added to the accumulator once (include/smin_hip.h gives the layout and the order).
+__global__ __launch_bounds__(64)
+void meter_close_kernel(const float* __restrict__ hits /* [B][npairs] */, const float* __restrict__ top1 /* [B] */, int B, int npairs,
+                        const float* __restrict__ loss /* [1] or null */, double* __restrict__ acc)
+{
+#pragma clang fp contract(off)
+    for (int slot = threadIdx.x; slot < 4 + npairs; slot += 64) {
+        double s = 0.0;
+        if (slot == 0) {
+            s = (double)B;
+        } else if (slot == 1 || slot == 2) {
+            if (!loss) continue;
+            s = slot == 1 ? (double)loss[0] * (double)B : (double)B;
+        } else if (slot == 3) {
+            for (int b = 0; b < B; ++b) s += (double)top1[b];
+        } else {
+            for (int b = 0; b < B; ++b) s += (double)hits[(size_t)b * npairs + (slot - 4)];
+        }
+        acc[slot] += s;
+    }
+}
+
+static size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
+
+// rule 0 is the reference's metric as this file computes it: n = {1, 5}, m = {0.1, 0.3, 0.5, 0.7}, topk(5) over all L*L cells
+static bool rule0_shape_ok(int B, int L, int k, int nn, int nm)
+{
+    return B >= 1 && L >= 1 && (size_t)L * L >= 5 && (size_t)L * L < 0x7fffffff && k == 5 && nn == 2 && nm == 4;
+}
+
 }  // namespace smin
 
 using namespace smin;
@@ -87,9 +123,44 @@ extern "C" int smin_compute_ious(void* stream, const float* pm, const float* ps,
 {
     hipStream_t st = (hipStream_t)stream;
     SMIN_REQUIRE(B >= 1 && L >= 1 && (size_t)L * L >= 5 && (size_t)L * L < 0x7fffffff);
-    hipLaunchKernelGGL(ious_kernel, dim3(B), dim3(256), 0, st, pm, ps, pe, mm, sm, L, ws);
+    hipLaunchKernelGGL(ious_kernel, dim3(B), dim3(256), 0, st, pm, ps, pe, mm, sm, L, ws, (float*)nullptr);
     SMIN_LAUNCH_CHECK();
     hipLaunchKernelGGL(ious_sum_kernel, dim3(1), dim3(64), 0, st, ws, B, counts);
+    SMIN_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" size_t smin_epoch_meter_ws_bytes(int B, int L, int rule, int k, int nn, int nm)
+{
+    if (rule == 0) return rule0_shape_ok(B, L, k, nn, nm) ? align256((size_t)B * 8 * sizeof(float)) + align256((size_t)B * sizeof(float)) : 0;
+    if (rule != 1) return 0;
+    const size_t stage = nms_hits_stage_bytes(B, L, k, nn, nm);
+    return stage ? stage + align256((size_t)B * sizeof(float)) : 0;
+}
+
+extern "C" int smin_epoch_meter_update(void* stream, const float* pm, const float* ps, const float* pe, const uint8_t* mm, const float* sm,
+                                       int B, int L, int rule, int k, float nms_thresh, const int* n_list, int nn, const float* m_list, int nm,
+                                       const float* loss, double* acc, void* ws, size_t ws_bytes)
+{
+    hipStream_t st = (hipStream_t)stream;
+    SMIN_REQUIRE(rule == 0 || rule == 1);
+    SMIN_REQUIRE(n_list != nullptr && m_list != nullptr && acc != nullptr && ws != nullptr);
+    const size_t need = smin_epoch_meter_ws_bytes(B, L, rule, k, nn, nm);
+    SMIN_REQUIRE(need != 0 && ws_bytes >= need);
+    float* hits = nullptr;
+    float* top1 = nullptr;
+    if (rule == 0) {
+        SMIN_REQUIRE(n_list[0] == 1 && n_list[1] == 5 && m_list[0] == 0.1f && m_list[1] == 0.3f && m_list[2] == 0.5f && m_list[3] == 0.7f);
+        hits = (float*)ws;
+        top1 = (float*)((char*)ws + align256((size_t)B * 8 * sizeof(float)));
+        hipLaunchKernelGGL(ious_kernel, dim3(B), dim3(256), 0, st, pm, ps, pe, mm, sm, L, hits, top1);
+        SMIN_LAUNCH_CHECK();
+    } else {
+        top1 = (float*)((char*)ws + nms_hits_stage_bytes(B, L, k, nn, nm));
+        const int rc = nms_hits_stage(st, pm, ps, pe, mm, sm, B, L, k, nms_thresh, n_list, nn, m_list, nm, ws, &hits, top1);
+        if (rc) return rc;
+    }
+    hipLaunchKernelGGL(meter_close_kernel, dim3(1), dim3(64), 0, st, hits, top1, B, nn * nm, loss, acc);
     SMIN_LAUNCH_CHECK();
     return 0;
 }

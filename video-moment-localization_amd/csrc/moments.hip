@@ -344,7 +344,7 @@ struct Pairs { int n[MAX_N]; float m[MAX_M]; int nn, nm; };
 
 __global__ __launch_bounds__(MT)
 void moments_hits_kernel(const long long* __restrict__ idx, const float* __restrict__ sm, int L, int k, Pairs pr,
-                         float* __restrict__ hits /* [B][nn * nm] */)
+                         float* __restrict__ hits /* [B][nn * nm] */, float* __restrict__ top1 /* [B] or null */)
 {
     __shared__ float iou[MAX_K];
     const int b = blockIdx.x, t = threadIdx.x;
@@ -360,6 +360,7 @@ void moments_hits_kernel(const long long* __restrict__ idx, const float* __restr
         for (int r = 0; r < pr.n[a]; ++r) hit = hit || iou[r] > pr.m[mc];
         hits[(size_t)b * npairs + q] = hit ? 1.f : 0.f;
     }
+    if (t == 0 && top1) top1[b] = iou[0];                        // the epoch meter's top-1 IoU: sm at the first kept cell, 0 if none
 }
 
 __global__ void moments_hits_sum_kernel(const float* __restrict__ hits, int B, int npairs, float* __restrict__ out)
@@ -532,12 +533,40 @@ extern "C" int smin_top_moments(void* stream, const float* pm, const float* ps, 
     return launch_top((hipStream_t)stream, pm, ps, pe, mm, B, L, k, nms_thresh, idx, score, count, (char*)ws);
 }
 
-extern "C" size_t smin_compute_ious_nms_ws_bytes(int B, int L, int k, int nn, int nm)
+// ---- per-sample stage of the NMS metric, shared by smin_compute_ious_nms and the epoch meter (metrics.hip): the top-k launches and the
+// hit flags [B][nn * nm] (and, for the meter, the top-1 IoU per sample) in the caller's scratch
+size_t smin::nms_hits_stage_bytes(int B, int L, int k, int nn, int nm)
 {
     if (!args_ok(B, L, k) || nn < 1 || nn > MAX_N || nm < 1 || nm > MAX_M) return 0;
     const size_t npairs = (size_t)nn * nm;
     const size_t top = align256((size_t)B * k * 2 * sizeof(long long)) + align256((size_t)B * k * sizeof(float)) + align256((size_t)B * sizeof(int));
     return ws_layout(B, L).total + top + align256((size_t)B * npairs * sizeof(float));
+}
+
+int smin::nms_hits_stage(hipStream_t st, const float* pm, const float* ps, const float* pe, const uint8_t* mm, const float* sm, int B, int L, int k,
+                         float nms_thresh, const int* n_list, int nn, const float* m_list, int nm, void* ws, float** hits_out, float* top1)
+{
+    SMIN_REQUIRE(args_ok(B, L, k) && nn >= 1 && nn <= MAX_N && nm >= 1 && nm <= MAX_M && n_list && m_list);
+    Pairs pr{};
+    pr.nn = nn; pr.nm = nm;
+    for (int a = 0; a < nn; ++a) { SMIN_REQUIRE(n_list[a] >= 1 && n_list[a] <= k); pr.n[a] = n_list[a]; }
+    for (int c = 0; c < nm; ++c) pr.m[c] = m_list[c];
+    char* p = (char*)ws + ws_layout(B, L).total;
+    long long* idx = (long long*)p;   p += align256((size_t)B * k * 2 * sizeof(long long));
+    float* score = (float*)p;         p += align256((size_t)B * k * sizeof(float));
+    int* count = (int*)p;             p += align256((size_t)B * sizeof(int));
+    float* hits = (float*)p;
+    const int rc = launch_top(st, pm, ps, pe, mm, B, L, k, nms_thresh, idx, score, count, (char*)ws);
+    if (rc) return rc;
+    hipLaunchKernelGGL(moments_hits_kernel, dim3(B), dim3(MT), 0, st, idx, sm, L, k, pr, hits, top1);
+    SMIN_LAUNCH_CHECK();
+    *hits_out = hits;
+    return 0;
+}
+
+extern "C" size_t smin_compute_ious_nms_ws_bytes(int B, int L, int k, int nn, int nm)
+{
+    return nms_hits_stage_bytes(B, L, k, nn, nm);
 }
 
 extern "C" int smin_compute_ious_nms(void* stream, const float* pm, const float* ps, const float* pe, const uint8_t* mm, const float* sm,
@@ -546,21 +575,11 @@ extern "C" int smin_compute_ious_nms(void* stream, const float* pm, const float*
 {
     SMIN_REQUIRE(args_ok(B, L, k) && nn >= 1 && nn <= MAX_N && nm >= 1 && nm <= MAX_M && n_list && m_list);
     SMIN_REQUIRE(ws != nullptr && ws_bytes >= smin_compute_ious_nms_ws_bytes(B, L, k, nn, nm));
-    Pairs pr{};
-    pr.nn = nn; pr.nm = nm;
-    for (int a = 0; a < nn; ++a) { SMIN_REQUIRE(n_list[a] >= 1 && n_list[a] <= k); pr.n[a] = n_list[a]; }
-    for (int c = 0; c < nm; ++c) pr.m[c] = m_list[c];
     const int npairs = nn * nm;
     hipStream_t st = (hipStream_t)stream;
-    char* p = (char*)ws + ws_layout(B, L).total;
-    long long* idx = (long long*)p;   p += align256((size_t)B * k * 2 * sizeof(long long));
-    float* score = (float*)p;         p += align256((size_t)B * k * sizeof(float));
-    int* count = (int*)p;             p += align256((size_t)B * sizeof(int));
-    float* hits = (float*)p;
-    const int rc = launch_top(st, pm, ps, pe, mm, B, L, k, nms_thresh, idx, score, count, (char*)ws);
+    float* hits = nullptr;
+    const int rc = nms_hits_stage(st, pm, ps, pe, mm, sm, B, L, k, nms_thresh, n_list, nn, m_list, nm, ws, &hits, nullptr);
     if (rc) return rc;
-    hipLaunchKernelGGL(moments_hits_kernel, dim3(B), dim3(MT), 0, st, idx, sm, L, k, pr, hits);
-    SMIN_LAUNCH_CHECK();
     hipLaunchKernelGGL(moments_hits_sum_kernel, dim3((npairs + 63) / 64), dim3(64), 0, st, hits, B, npairs, counts);
     SMIN_LAUNCH_CHECK();
     return 0;

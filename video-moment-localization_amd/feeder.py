@@ -11,6 +11,8 @@ A loader may instead hand over each video's raw feature rows and the query's tok
 docstring): the clip resampling of dataset.py:40-74 and the word-vector lookup of dataset.py:32-38 then run on the copy stream
 as well (csrc/sampling.hip), and the host only packs the ragged rows into a pinned buffer.
 """
+import math
+
 import numpy as np
 import torch
 
@@ -19,6 +21,24 @@ from ._lib import call, ptr
 
 _BATCH_KEYS = ("video_features", "video_mask", "query_features", "query_mask", "length_mask", "moment_mask",
                "sm", "ym", "ss", "ys", "se", "ye", "ya")
+
+
+def cell_count(nfeats, T, L):
+    """Number of valid cells of the moment masks of samples with ``nfeats`` sampled frames (an int or a sequence), by host arithmetic:
+    the sum of ``n_len * (n_len + 1) / 2`` with ``n_len = ceil(nfeats / (T / L))`` (dataset.py:145-147, as csrc/labels.hip forms it).
+    It equals ``int(moment_mask.sum())`` of the batch, so a forward can be handed the count (``SMIN.known_cell_count``) and read
+    nothing back."""
+    total = 0
+    for x in np.asarray(nfeats).reshape(-1).tolist():
+        n_len = min(max(math.ceil(int(x) / (T / L)), 0), L)
+        total += n_len * (n_len + 1) // 2
+    return total
+
+
+class FedBatch(dict):
+    """A fed batch: the dict of the thirteen device tensors main.py's loop reads, plus ``cell_count``, the number of valid cells of
+    its ``moment_mask`` computed on the host (``cell_count`` above)."""
+    cell_count = None
 
 
 def build_targets_hip(times, duration, nfeats, qlen, T, L, Nq, stream=None):
@@ -71,7 +91,8 @@ class BatchFeeder:
     """Double-buffered host -> device feeder.  ``feed(sample_batches)`` takes an iterable of host batches
     ``dict(video_features (B,T,Din) float32, query_features (B,Nq,300) float32, nfeats (B,), qlen (B,), times (B,2), duration (B,))``
     (numpy arrays or CPU tensors) and yields device batches with the thirteen entries main.py's loop reads, one batch ahead of
-    the consumer.
+    the consumer.  Each yielded batch is a ``FedBatch``: its int attribute ``cell_count`` is the number of valid cells of its
+    ``moment_mask``, from the host's ``nfeats`` (raw form: ``min(raw length, T)``) -- nothing is read back for it.
 
     Raw batch form (chosen by its keys): ``dict(raw_features, tokens (B,Nq) int, times (B,2), duration (B,), spos (B,) optional)``
     with ``raw_features`` a list of B arrays ``(n_b, Din)`` or one packed ``(sum n_b, Din)`` array plus ``raw_lengths (B,)``.  The
@@ -122,7 +143,8 @@ class BatchFeeder:
             tg = build_targets_hip(d["times"], d["duration"], d["nfeats"], d["qlen"], self.T, self.L, self.Nq)
             batch = dict(video_features=d["video_features"], query_features=d["query_features"], **tg)
             slot["ready"].record(self.copy_stream)
-        slot["batch"] = {k: batch[k] for k in _BATCH_KEYS}
+        slot["batch"] = FedBatch((k, batch[k]) for k in _BATCH_KEYS)
+        slot["batch"].cell_count = cell_count(t["nfeats"].numpy(), self.T, self.L)
         return B
 
     def _stage_raw(self, slot, hb):
@@ -187,7 +209,8 @@ class BatchFeeder:
             tg = build_targets_hip(d["times"], d["duration"], nfeats, None, self.T, self.L, self.Nq)
             batch = dict(video_features=vf, query_features=qf, query_mask=qm.view(B, self.Nq, 1), **tg)
             slot["ready"].record(self.copy_stream)
-        slot["batch"] = {k: batch[k] for k in _BATCH_KEYS}
+        slot["batch"] = FedBatch((k, batch[k]) for k in _BATCH_KEYS)
+        slot["batch"].cell_count = cell_count(np.minimum(lengths, self.T), self.T, self.L)
         return B
 
     def feed(self, host_batches):

@@ -1,0 +1,178 @@
+"""An epoch's loss and retrieval metrics accumulated on the device: one host read per epoch instead of two per batch.
+
+The reference's loops (main.py:135-211) read ``loss.item()`` and the counts of ``compute_ious`` back on every batch, so the host
+cannot enqueue step n + 1 while step n runs.  ``EpochMeter.update`` enqueues the same per-sample metric stage as ``compute_ious``
+(csrc/metrics.hip, csrc/moments.hip) followed by one closing wave that adds the batch's sums to an fp64 accumulator in device
+memory; ``result()`` is the only read.
+
+State ``acc`` (fp64, ``4 + len(n) * len(m)`` values; include/smin_hip.h, smin_epoch_meter_update):
+  ``[0]`` samples seen; ``[1]`` sum of ``float64(loss) * B`` over the updates that carried a loss; ``[2]`` samples of those updates;
+  ``[3]`` sum of the top-1 IoU (``sm`` at the sample's first kept cell, 0 if it keeps none);
+  ``[4 + a * len(m) + c]`` samples with a hit for ``(n[a], m[c])``.
+Every batch sum is ``s = 0.0; for b in range(B): s += float64(x[b])``, then ``acc[slot] += s``: a fixed order, so
+``EpochMeterTorch`` -- the same class as plain torch ops on any device, the restatement the tests compare against; nothing routes
+to it -- reproduces ``EpochMeter.state`` bit for bit.
+
+All updates of one meter must be issued on one stream (the accumulator is ordered by the stream alone, no atomics)."""
+import ctypes
+
+import torch
+
+from .moments import MAX_K, _check, _mask_u8, _mul32, _nm_check, _sqrt32
+
+_REF_N, _REF_M = (1, 5), (0.1, 0.3, 0.5, 0.7)
+
+
+def _status_word(device):
+    """The device's ``layout_status`` word (set by a forward whose ``known_cell_count`` did not match its mask) as a (1,) int32
+    tensor, or None where no forward of the one-node path can have run (CPU, or the extension was never loaded)."""
+    from . import _lib
+    if torch.device(device).type != "cuda" or _lib._torch_ops is None:
+        return None
+    return _lib._torch_ops.layout_status(torch.device(device))
+
+
+def _lstm_cluster_error(device):
+    """1 once a poll of the cluster LSTM has expired since the last call (smin_lstm_cluster_error; clears the word), else 0."""
+    from . import _lib
+    if torch.device(device).type != "cuda":
+        return 0
+    with torch.cuda.device(device):
+        return int(_lib.load().smin_lstm_cluster_error())
+
+
+class _Meter:
+    def __init__(self, n=_REF_N, m=_REF_M, nms_thresh=None, device=None):
+        self.n, self.m = tuple(n), tuple(m)
+        self.keys = [f"R@{n_}, IoU={m_}" for n_ in self.n for m_ in self.m]
+        if nms_thresh is None:
+            if self.n != _REF_N or self.m != _REF_M:
+                raise ValueError(f"the meter's reference rule (nms_thresh=None) takes n = {_REF_N} and m = {_REF_M} only (got n={self.n}, "
+                                 f"m={self.m}); pass nms_thresh (>= 1 for plain top-k over the valid cells) for other lists")
+            self.rule, self.nms_thresh = 0, None
+            self._n, self._m, self.k = list(_REF_N), list(_REF_M), 5
+        else:
+            self.rule, self.nms_thresh = 1, float(nms_thresh)
+            self._n, self._m = _nm_check(self.n, self.m)                 # ValueError: more than 64 n / 16 m, or an n outside 1..64
+            self.k = max(self._n)
+            assert self.k <= MAX_K
+        self.device = torch.device(self._default_device() if device is None else device)
+        self.state = torch.zeros(4 + len(self.keys), dtype=torch.float64, device=self.device)
+
+    def reset(self):
+        self.state.zero_()
+
+    def result(self, group=None):
+        """The one host read: ``{"R@n, IoU=m": hits / samples, ..., "mIoU": ..., "num_samples": ...}`` plus ``"loss"`` when an
+        update carried one (the divisions of main.py:162-163, 188-189).  ``group``: a torch.distributed process group whose
+        ranks' states are summed first (the meter's own state is left as it is).  Raises RuntimeError, naming the word, when the
+        device's ``layout_status`` word (a batch's ``cell_count`` did not match its ``moment_mask``; cleared here) or the cluster
+        LSTM's poll-expiry word is set: the epoch's numbers are then meaningless."""
+        st = self.state
+        if group is not None:
+            st = st.clone()
+            torch.distributed.all_reduce(st, op=torch.distributed.ReduceOp.SUM, group=group)
+        status = _status_word(self.device)
+        if status is None:
+            acc, bad = st.tolist(), 0
+        else:
+            vals = torch.cat([st, status.to(device=st.device, dtype=torch.float64)]).tolist()
+            acc, bad = vals[:-1], int(vals[-1])
+        expired = _lstm_cluster_error(self.device)
+        if bad:
+            status.zero_()
+        if bad or expired:
+            what = ["layout_status (a batch ran with a cell count that did not match its moment_mask)"] * bool(bad) \
+                + ["smin_lstm_cluster_error (a poll of the cluster LSTM expired)"] * bool(expired)
+            raise RuntimeError("EpochMeter.result: " + " and ".join(what) + " was set during the epoch; its results are meaningless")
+        num = acc[0]
+        out = {k: acc[4 + q] / num for q, k in enumerate(self.keys)}
+        out["mIoU"] = acc[3] / num
+        out["num_samples"] = int(num)
+        if acc[2] > 0:
+            out["loss"] = acc[1] / acc[2]
+        return out
+
+
+class EpochMeter(_Meter):
+    """``EpochMeter(n=(1, 5), m=(0.1, 0.3, 0.5, 0.7), nms_thresh=None, device=...)``: ``nms_thresh=None`` is the reference's rule
+    (``compute_ious``'s kernel; only the reference's n / m -- ``compute_ious`` sends other lists to its torch form, which the meter
+    does not offer); a number selects greedy temporal NMS over the valid cells (``compute_ious(..., nms_thresh=t)``, same limits).
+
+    ``update(pm, ps, pe, moment_mask, sm, loss=None)`` enqueues the kernels on the current stream and returns nothing; ``loss``
+    is the device scalar ``loss_fn`` returned.  HIP tensors only.  ``result()`` reads, ``reset()`` zeroes, ``state`` is the fp64
+    device tensor."""
+
+    @staticmethod
+    def _default_device():
+        return "cuda"
+
+    def update(self, pm, ps, pe, moment_mask, sm, loss=None):
+        from ._lib import SminHipError, call, load, ptr, stream
+        for t in (pm, ps, pe, moment_mask, sm) + (() if loss is None else (loss,)):
+            if not t.is_cuda:
+                raise SminHipError("EpochMeter.update runs on a HIP device only (got a CPU tensor); there is no CPU fallback -- the plain-torch "
+                                   "restatement is available under the explicit name EpochMeterTorch")
+        if pm.device != self.state.device:
+            raise ValueError(f"EpochMeter on {self.state.device} got tensors on {pm.device}")
+        B, L = _check(pm, ps, pe, moment_mask, 1)
+        if self.rule == 0 and L * L < 5:
+            raise ValueError("the meter's reference rule takes the top five of L*L cells: L*L >= 5")
+        if tuple(sm.shape) != (B, L, L) or (loss is not None and loss.numel() != 1):
+            raise ValueError(f"sm must be (B, L, L) = {(B, L, L)} and loss a scalar (got {tuple(sm.shape)}, "
+                             f"{None if loss is None else tuple(loss.shape)})")
+        pm_, ps_, pe_, sm_ = (x.detach().float().contiguous() for x in (pm, ps, pe, sm))
+        mm_ = _mask_u8(moment_mask)
+        loss_ = None if loss is None else loss.detach().float().reshape(1).contiguous()
+        nl, ml = (ctypes.c_int * len(self._n))(*self._n), (ctypes.c_float * len(self._m))(*self._m)
+        with torch.cuda.device(pm.device):
+            nbytes = load().smin_epoch_meter_ws_bytes(B, L, self.rule, self.k, len(self._n), len(self._m))
+            if nbytes == 0:
+                raise SminHipError(f"smin_epoch_meter_ws_bytes rejected B={B}, L={L}, rule={self.rule}, k={self.k}")
+            ws = torch.empty((nbytes,), dtype=torch.uint8, device=pm.device)
+            call("smin_epoch_meter_update", stream(), ptr(pm_), ptr(ps_), ptr(pe_), ptr(mm_), ptr(sm_), B, L, self.rule, self.k,
+                 1.0 if self.nms_thresh is None else self.nms_thresh, ctypes.cast(nl, ctypes.c_void_p), len(self._n),
+                 ctypes.cast(ml, ctypes.c_void_p), len(self._m), ptr(loss_), ptr(self.state), ptr(ws), nbytes)
+
+
+class EpochMeterTorch(_Meter):
+    """``EpochMeter`` as plain torch ops and Python float64 sums on any device (module docstring): built on
+    ``compute_ious_torch`` and ``top_moments_torch``; reads the host on every update."""
+
+    @staticmethod
+    def _default_device():
+        return "cpu"
+
+    def _top1(self, pm, ps, pe, moment_mask, sm):
+        """(B,) fp32: sm at each sample's first kept cell, 0 if it keeps none."""
+        B, L = pm.shape[0], pm.shape[1]
+        smf = sm.detach().float().reshape(B, -1)
+        if self.rule == 1:
+            from .moments import top_moments_torch
+            idx = top_moments_torch(pm, ps, pe, moment_mask, k=1, nms_thresh=self.nms_thresh)["idx"][:, 0]
+            flat = idx[:, 0] * L + idx[:, 1]
+            iou = torch.gather(smf, 1, flat.clamp_min(0).unsqueeze(1)).squeeze(1)
+            return torch.where(flat >= 0, iou, torch.zeros_like(iou))
+        # the reference's rule as csrc/metrics.hip forms it: ((pm * sqrtf(ps_i)) * sqrtf(pe_j)) * mask over all cells, ties -> lower index
+        score = _mul32(_mul32(pm.detach(), _sqrt32(ps.detach()).unsqueeze(2)), _sqrt32(pe.detach()).unsqueeze(1))
+        score = _mul32(score, (_mask_u8(moment_mask) != 0).float()).reshape(B, -1)
+        cell = torch.arange(L * L, device=score.device).unsqueeze(0)
+        best = torch.where(score == score.max(dim=1, keepdim=True).values, cell, torch.full_like(cell, L * L)).min(dim=1).values
+        return torch.gather(smf, 1, best.unsqueeze(1)).squeeze(1)
+
+    def update(self, pm, ps, pe, moment_mask, sm, loss=None):
+        from .training import compute_ious_torch
+        B, L = _check(pm, ps, pe, moment_mask, 1)
+        counts = compute_ious_torch(pm.detach(), ps.detach(), pe.detach(), moment_mask, sm, self.n, self.m, nms_thresh=self.nms_thresh)
+        delta = [0.0] * self.state.numel()
+        delta[0] = float(B)
+        if loss is not None:
+            delta[1] = float(loss.detach().float().reshape(1)[0]) * float(B)     # fp32 value, widened: the product is exact in fp64
+            delta[2] = float(B)
+        s = 0.0
+        for v in self._top1(pm, ps, pe, moment_mask, sm).tolist():               # float64 sum over the samples in order
+            s += v
+        delta[3] = s
+        for q, k in enumerate(self.keys):
+            delta[4 + q] = float(counts[k])                                       # a sum of 0 / 1 flags: exact in any order
+        self.state += torch.tensor(delta, dtype=torch.float64).to(self.state.device)

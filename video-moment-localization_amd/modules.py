@@ -715,7 +715,7 @@ class SMIN(nn.Module):
         ``n_windows`` (B,) int64; with ``duration`` (B,) seconds also ``times`` = (span * duration) / n (fp32; n = the video's rows)."""
         from .moments import MAX_K, merge_window_moments
         from .sampling import MAX_ROWS, MODES, sample_windows, window_plan
-        from .feeder import build_masks_hip
+        from .feeder import build_masks_hip, cell_count
         from . import _lib
         T, L = self.T, self.L
         k_window = k if k_window is None else k_window
@@ -762,8 +762,7 @@ class SMIN(nn.Module):
         pair_of = np.repeat(np.arange(B, dtype=np.int64), nw)
         w_start, w_len = starts[wsel], lens[wsel].astype(np.int64)
         nf = np.minimum(w_len, T)
-        n_len = np.array([math.ceil(int(x) / (T / L)) for x in nf], dtype=np.int64)              # as csrc/labels.hip forms it
-        cells = n_len * (n_len + 1) // 2
+        cells = np.array([cell_count(x, T, L) for x in nf], dtype=np.int64)                      # per window, as csrc/labels.hip forms it
         # the whole plan in one pinned buffer, one asynchronous copy (the call never waits for the device)
         host = np.concatenate([offs[vi[pair_of]] + w_start if G else np.zeros(0, np.int64), w_start, w_len, pair_of, pair_ptr, nw,
                                n[vi]]).astype(np.int64)

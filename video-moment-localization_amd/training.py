@@ -194,3 +194,88 @@ class CapturedStep:
         e = dict(graph=g, static=static, loss=loss, outputs=out, used=self.clock)
         self.entries[key] = e
         return e
+
+
+# ---------------------------------------------------------------- the reference's three loops with no host read per batch
+def _inputs(batch):
+    return [batch[k] for k in MODEL_INPUTS]
+
+
+class _handed_count:
+    """For one call of the model: the batch's host-computed cell count (feeder.FedBatch.cell_count) as ``model.known_cell_count``,
+    so the forward sizes its per-cell tensors without asking the device; the previous value is restored afterwards.  A count that
+    does not match the mask sets the device's layout_status word, which EpochMeter.result() reads."""
+
+    def __init__(self, model, batch):
+        self.model, self.count = model, getattr(batch, "cell_count", None)
+
+    def __enter__(self):
+        if self.count is not None:
+            self.known = self.model.known_cell_count
+            self.model.known_cell_count = int(self.count)
+
+    def __exit__(self, *exc):
+        if self.count is not None:
+            self.model.known_cell_count = self.known
+
+
+def _meter_for(meter, batch):
+    if meter is None:
+        from .meter import EpochMeter
+        meter = EpochMeter(device=batch["moment_mask"].device)
+    return meter
+
+
+def _loss_of(out, b):
+    pm, ps, pe, pa = out
+    return loss_fn(pm, b["ym"], b["sm"], b["moment_mask"], ps, b["ys"], b["ss"], pe, b["ye"], b["se"], pa, b["ya"], b["length_mask"])
+
+
+def train_epoch(model, optimizer, batches, meter=None):
+    """reference main.py:135-165, statement for statement, over device batches (dicts with MODEL_INPUTS + LOSS_TARGETS, e.g. what
+    BatchFeeder.feed yields), with no host read per batch: a batch that carries ``cell_count`` hands it to the forward, the loss
+    and the metric go to ``meter`` (meter.EpochMeter; a default one is made if none is given) in place of ``loss.item()`` and
+    ``compute_ious``, and the one ``meter.result()`` at the end gives ``(train_loss, iou_metrics)``: the epoch's mean loss and the
+    meter's dict (R@n, IoU=m rates, mIoU, num_samples, loss).  The meter is not reset here."""
+    model.train()
+    for batch in batches:
+        meter = _meter_for(meter, batch)
+        optimizer.zero_grad()
+        with _handed_count(model, batch):
+            out = model(*_inputs(batch))
+        loss = _loss_of(out, batch)
+        meter.update(out[0], out[1], out[2], batch["moment_mask"], batch["sm"], loss=loss.detach())
+        loss.backward()
+        optimizer.step()
+    metrics = meter.result()
+    return metrics["loss"], metrics
+
+
+def eval_epoch(model, batches, meter=None):
+    """reference main.py:167-191 in the same way, under torch.no_grad(); the scores come from ``model.score`` when
+    ``model.forward_only_scoring`` is set, else from ``model(...)``.  Returns ``(eval_loss, iou_metrics)``."""
+    model.eval()
+    with torch.no_grad():
+        for batch in batches:
+            meter = _meter_for(meter, batch)
+            with _handed_count(model, batch):
+                out = model.score(*_inputs(batch)) if getattr(model, "forward_only_scoring", False) else model(*_inputs(batch))
+            loss = _loss_of(out, batch)
+            meter.update(out[0], out[1], out[2], batch["moment_mask"], batch["sm"], loss=loss)
+    metrics = meter.result()
+    return metrics["loss"], metrics
+
+
+def test_model(model, batches, meter=None):
+    """reference main.py:193-211 in the same way (no loss; the batches need MODEL_INPUTS and ``sm`` only).  Returns iou_metrics."""
+    model.eval()
+    with torch.no_grad():
+        for batch in batches:
+            meter = _meter_for(meter, batch)
+            with _handed_count(model, batch):
+                out = model.score(*_inputs(batch)) if getattr(model, "forward_only_scoring", False) else model(*_inputs(batch))
+            meter.update(out[0], out[1], out[2], batch["moment_mask"], batch["sm"])
+    return meter.result()
+
+
+test_model.__test__ = False                                       # a loop of the reference, not a pytest test
