@@ -43,7 +43,8 @@ extern "C" {
  * arbitrary, possibly overlapping row ranges), smin_merge_window_moments (greedy NMS of per-window top-k moments in absolute
  * time), and a masks-only use of smin_build_targets (sm == NULL); forward-only scoring -- smin_score_tail_fwd and
  * smin_score_tail_ws_bytes (the last layer's moment unit and the map's score head as row dots); an epoch's metric and loss totals
- * kept on the device -- smin_epoch_meter_update and smin_epoch_meter_ws_bytes */
+ * kept on the device -- smin_epoch_meter_update and smin_epoch_meter_ws_bytes; the metric of merged spans against ground-truth
+ * spans -- smin_span_ious, smin_span_meter_update and smin_span_meter_ws_bytes */
 #define SMIN_HIP_ABI_VERSION 2
 
 int smin_abi_version(void);
@@ -367,6 +368,29 @@ size_t smin_epoch_meter_ws_bytes(int B, int L, int rule, int k, int nn, int nm);
 int smin_epoch_meter_update(void* stream, const float* pm, const float* ps, const float* pe, const uint8_t* mm, const float* sm,
                             int B, int L, int rule, int k, float nms_thresh, const int* n_list, int nn, const float* m_list, int nm,
                             const float* loss, double* acc, void* ws, size_t ws_bytes);
+
+/* ---- span metric (csrc/metrics.hip): IoU, R@n, IoU=m and top-1 IoU of continuous spans -- smin_merge_window_moments' output --
+ * against one ground-truth span per pair, and their accumulation into the epoch meter's acc.
+ * Inputs: span [B][k][2] fp32 (st, en) and count [B] (slots s >= count[b] are empty; their span, NaN, is never used), gt [B][2]
+ * fp32 (gs, ge) in the same unit (raw rows of the pair's video, as the merge returns them; seconds work equally).
+ * All arithmetic fp32, in this order, each operation rounded once:
+ *   IoU of slot s < count[b]:  inter = fmaxf(0, fminf(en, ge) - fmaxf(st, gs));  uni = fmaxf(en, ge) - fminf(st, gs);
+ *     iou = uni > 0 ? inter / uni : 0   (one correctly rounded division; the operation order of the merge's IoU);
+ *   a slot s >= count[b] has IoU exactly 0 (the rule of smin_compute_ious_nms: an empty slot counts as IoU 0);
+ *   count[b] is read clamped to [0, k] by both entry points: a negative count is 0 filled slots, a count above k is k;
+ *   hit for (n_list[a], m_list[c]): some slot s < min(n_list[a], count[b]) with iou > m_list[c] (strict);
+ *   top-1 IoU: the IoU of slot 0, 0 when count[b] == 0.
+ * smin_span_ious writes iou [B][k].  smin_span_meter_update adds to acc [4 + nn * nm] doubles, the accumulator of
+ * smin_epoch_meter_update with the same slots: [0] += B, [3] += the sum of the top-1 IoU, [4 + a * nm + c] += the hits; [1] and [2]
+ * are not touched.  The per-pair stage (one lane per pair; fp32 hit flags 0 / 1 and the top-1 IoU in ws) is followed by the
+ * meter's closing wave: s = 0.0; for b = 0 .. B-1: s += (double)x[b]; acc[slot] += s.  No atomics, no host read: ALL UPDATES OF
+ * ONE acc, of either kind, MUST BE ISSUED ON ONE STREAM (or be ordered by events).  n_list / m_list: host arrays.
+ * Limits: 1 <= k <= 64, 1 <= nn <= 64, 1 <= nm <= 16, every n_list[a] in [1, k], B >= 0 (else a negative code, nothing launched);
+ * B = 0 is a no-op.  ws: device scratch of at least the _ws_bytes size; _ws_bytes returns 0 when B < 1 or nn / nm are rejected. */
+int smin_span_ious(void* stream, const float* span, const int32_t* count, const float* gt, int B, int k, float* iou);
+size_t smin_span_meter_ws_bytes(int B, int nn, int nm);
+int smin_span_meter_update(void* stream, const float* span, const int32_t* count, const float* gt, int B, int k,
+                           const int* n_list, int nn, const float* m_list, int nm, double* acc, void* ws, size_t ws_bytes);
 
 /* ---- content stream (reference models.py:242-276 + 115-119, re-associated): the content unit's output
  *   f_c' = m*(cc Wc^T + bc) + f_c + hbar   (models.py:269-276)

@@ -62,6 +62,9 @@ SIGNATURES = {
     "smin_compute_ious_nms": [_vp] * 6 + [_i] * 3 + [_f, _vp, _i, _vp, _i] + [_vp, _vp, _sz],
     "smin_epoch_meter_ws_bytes": [_i] * 6,
     "smin_epoch_meter_update": [_vp] * 6 + [_i] * 4 + [_f, _vp, _i, _vp, _i] + [_vp, _vp, _vp, _sz],
+    "smin_span_ious": [_vp] * 4 + [_i] * 2 + [_vp],
+    "smin_span_meter_ws_bytes": [_i] * 3,
+    "smin_span_meter_update": [_vp] * 4 + [_i] * 2 + [_vp, _i, _vp, _i] + [_vp, _vp, _sz],
     "smin_build_targets": [_vp] * 5 + [_i] * 4 + [_vp] * 12,
     "smin_sample_clips": [_vp] * 4 + [_i] * 4 + [_vp] * 2,
     "smin_embed_tokens": [_vp] * 3 + [_i] * 5 + [_vp] * 3,
@@ -115,7 +118,7 @@ _RESTYPE = {"smin_target_arch": ctypes.c_char_p, "smin_workspace_bytes": _sz,
             "smin_bilstm_layer_bwd_workspace_bytes": _sz, "smin_video_encoder_bwd_workspace_bytes": _sz, "smin_embed_tokens_bwd_workspace_bytes": _sz,
             "smin_word_prep_bwd_workspace_bytes": _sz, "smin_score_tail_ws_bytes": _sz,
             "smin_col_sum_workspace_bytes": _sz, "smin_top_moments_ws_bytes": _sz, "smin_boundary_unit_bwd_ws_bytes": _sz, "smin_compute_ious_nms_ws_bytes": _sz,
-            "smin_epoch_meter_ws_bytes": _sz}
+            "smin_epoch_meter_ws_bytes": _sz, "smin_span_meter_ws_bytes": _sz}
 
 _lib = None
 _ws = {}

@@ -106,6 +106,59 @@ void meter_close_kernel(const float* __restrict__ hits /* [B][npairs] */, const 
     }
 }
 
+// ---- span metric (smin_span_ious / smin_span_meter_update, include/smin_hip.h): R@n, IoU=m and the top-1 IoU of continuous spans
+// (SMIN.localize_windows' merged output) against one ground-truth span per pair.  One lane per pair (k <= 64 slots), workgroups
+// of one wave; the meter's per-pair stage keeps the lane's IoUs in an LDS column and the batch sums go through meter_close_kernel.
+
+// IoU of slot (st, en) with (gs, ge): fp32, each operation rounded once; NaN operands leave through fminf / fmaxf and the uni > 0 test
+__device__ __forceinline__ float span_iou(float st, float en, float gs, float ge)
+{
+    const float inter = fmaxf(0.f, fminf(en, ge) - fmaxf(st, gs));
+    const float uni = fmaxf(en, ge) - fminf(st, gs);
+    return uni > 0.f ? inter / uni : 0.f;
+}
+
+__global__ __launch_bounds__(64)
+void span_ious_kernel(const float* __restrict__ span, const int* __restrict__ count, const float* __restrict__ gt, int B, int k,
+                      float* __restrict__ iou /* [B][k] */)
+{
+    const int b = blockIdx.x * 64 + threadIdx.x;
+    if (b >= B) return;
+    const float gs = gt[2 * (size_t)b], ge = gt[2 * (size_t)b + 1];
+    const int cnt = min(max(count[b], 0), k);
+    for (int s = 0; s < k; ++s) {
+        const size_t o = (size_t)b * k + s;
+        iou[o] = s < cnt ? span_iou(span[2 * o], span[2 * o + 1], gs, ge) : 0.f;       // an empty slot's NaN span is never read
+    }
+}
+
+struct SpanRule { int n[64]; float m[16]; int nn, nm; };
+
+__global__ __launch_bounds__(64)
+void span_hits_kernel(const float* __restrict__ span, const int* __restrict__ count, const float* __restrict__ gt, int B, int k, SpanRule pr,
+                      float* __restrict__ hits /* [B][nn * nm] */, float* __restrict__ top1 /* [B] */)
+{
+    __shared__ float col[64][64];                                // col[s][lane]: the lane's IoU of slot s (a column per lane: no bank conflict)
+    const int t = threadIdx.x, b = blockIdx.x * 64 + t;
+    if (b >= B) return;                                          // no barrier below: a lane reads its own column only
+    const float gs = gt[2 * (size_t)b], ge = gt[2 * (size_t)b + 1];
+    const int cnt = min(max(count[b], 0), k);
+    for (int s = 0; s < cnt; ++s) {
+        const size_t o = (size_t)b * k + s;
+        col[s][t] = span_iou(span[2 * o], span[2 * o + 1], gs, ge);
+    }
+    top1[b] = cnt > 0 ? col[0][t] : 0.f;
+    const int npairs = pr.nn * pr.nm;
+    for (int a = 0; a < pr.nn; ++a) {
+        const int e = min(pr.n[a], cnt);                         // slots past count[b] are empty: never a hit
+        for (int c = 0; c < pr.nm; ++c) {
+            bool hit = false;
+            for (int s = 0; s < e; ++s) hit = hit || col[s][t] > pr.m[c];
+            hits[(size_t)b * npairs + a * pr.nm + c] = hit ? 1.f : 0.f;
+        }
+    }
+}
+
 static size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 // rule 0 is the reference's metric as this file computes it: n = {1, 5}, m = {0.1, 0.3, 0.5, 0.7}, topk(5) over all L*L cells
@@ -161,6 +214,43 @@ extern "C" int smin_epoch_meter_update(void* stream, const float* pm, const floa
         if (rc) return rc;
     }
     hipLaunchKernelGGL(meter_close_kernel, dim3(1), dim3(64), 0, st, hits, top1, B, nn * nm, loss, acc);
+    SMIN_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int smin_span_ious(void* stream, const float* span, const int32_t* count, const float* gt, int B, int k, float* iou)
+{
+    SMIN_REQUIRE(B >= 0 && k >= 1 && k <= 64);
+    if (B == 0) return 0;
+    SMIN_REQUIRE(span != nullptr && count != nullptr && gt != nullptr && iou != nullptr);
+    hipLaunchKernelGGL(span_ious_kernel, dim3(cdiv(B, 64)), dim3(64), 0, (hipStream_t)stream, span, count, gt, B, k, iou);
+    SMIN_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" size_t smin_span_meter_ws_bytes(int B, int nn, int nm)
+{
+    if (B < 1 || nn < 1 || nn > 64 || nm < 1 || nm > 16) return 0;
+    return align256((size_t)B * nn * nm * sizeof(float)) + align256((size_t)B * sizeof(float));
+}
+
+extern "C" int smin_span_meter_update(void* stream, const float* span, const int32_t* count, const float* gt, int B, int k,
+                                      const int* n_list, int nn, const float* m_list, int nm, double* acc, void* ws, size_t ws_bytes)
+{
+    hipStream_t st = (hipStream_t)stream;
+    SMIN_REQUIRE(B >= 0 && k >= 1 && k <= 64 && nn >= 1 && nn <= 64 && nm >= 1 && nm <= 16 && n_list != nullptr && m_list != nullptr);
+    SpanRule pr{};
+    pr.nn = nn; pr.nm = nm;
+    for (int a = 0; a < nn; ++a) { SMIN_REQUIRE(n_list[a] >= 1 && n_list[a] <= k); pr.n[a] = n_list[a]; }
+    for (int c = 0; c < nm; ++c) pr.m[c] = m_list[c];
+    if (B == 0) return 0;
+    SMIN_REQUIRE(span != nullptr && count != nullptr && gt != nullptr && acc != nullptr && ws != nullptr);
+    SMIN_REQUIRE(ws_bytes >= smin_span_meter_ws_bytes(B, nn, nm));
+    float* hits = (float*)ws;
+    float* top1 = (float*)((char*)ws + align256((size_t)B * nn * nm * sizeof(float)));
+    hipLaunchKernelGGL(span_hits_kernel, dim3(cdiv(B, 64)), dim3(64), 0, st, span, count, gt, B, k, pr, hits, top1);
+    SMIN_LAUNCH_CHECK();
+    hipLaunchKernelGGL(meter_close_kernel, dim3(1), dim3(64), 0, st, hits, top1, B, nn * nm, (const float*)nullptr, acc);
     SMIN_LAUNCH_CHECK();
     return 0;
 }

@@ -87,6 +87,22 @@ def build_masks_hip(nfeats, T, L):
     return out
 
 
+def _raw_parts(hb):
+    """A raw batch's ``raw_features`` as ``(parts, lengths (B,) int64)``: the list's arrays, or the one packed array with its
+    ``raw_lengths`` checked against its rows (ValueError)."""
+    raw = hb["raw_features"]
+    if isinstance(raw, (list, tuple)):
+        parts = [r if isinstance(r, torch.Tensor) else np.asarray(r) for r in raw]
+        return parts, np.array([p.shape[0] for p in parts], dtype=np.int64)
+    parts = [raw if isinstance(raw, torch.Tensor) else np.asarray(raw)]
+    if "raw_lengths" not in hb:
+        raise ValueError("a packed raw_features array needs raw_lengths (B,)")
+    lengths = np.asarray(hb["raw_lengths"], dtype=np.int64).reshape(-1)
+    if (lengths < 0).any() or int(lengths.sum()) != parts[0].shape[0]:
+        raise ValueError(f"raw_lengths must be >= 0 and sum to the {parts[0].shape[0]} rows of raw_features")
+    return parts, lengths
+
+
 class BatchFeeder:
     """Double-buffered host -> device feeder.  ``feed(sample_batches)`` takes an iterable of host batches
     ``dict(video_features (B,T,Din) float32, query_features (B,Nq,300) float32, nfeats (B,), qlen (B,), times (B,2), duration (B,))``
@@ -99,7 +115,13 @@ class BatchFeeder:
     device resamples the rows to T clips (``pool``: "pick", the reference's rule, with start offsets ``spos``, default 0; or "mean",
     sampling.py) and looks the ids up in ``embedding`` (a device ``(V, E)`` table, required for this form) with ``pad_id``
     (default ``V - 1``); nfeats and qlen come from those kernels' outputs and query_mask is ``tokens < pad_id`` (dataset.py:173).
-    Token ids and ``spos`` are validated on the host (ValueError).  The yielded batch has the same thirteen entries."""
+    Token ids and ``spos`` are validated on the host (ValueError).  The yielded batch has the same thirteen entries.
+
+    Window form (a raw batch that also carries ``win_start (B,)`` and ``win_len (B,)``, e.g. from ``sampling.draw_windows``):
+    ``raw_features`` holds whole videos as above, ``times`` / ``duration`` the annotations in seconds; only rows
+    ``win_start[b] .. win_start[b] + win_len[b]`` of each video are packed into the pinned buffer, and the batch is then exactly the
+    raw form of those rows with ``sampling.window_annotations``' ``(times_w, duration_w)``: ``spos`` is validated against
+    ``win_len``, ``cell_count`` comes from ``min(win_len, T)``.  A window outside its video raises ValueError before staging."""
 
     def __init__(self, T, L, Nq, device, depth=3, embedding=None, pad_id=None, pool="pick"):
         from .sampling import MODES
@@ -153,17 +175,9 @@ class BatchFeeder:
         from .sampling import embed_tokens, sample_clips, _check_spos
         if self.embedding is None:
             raise ValueError("a raw batch (tokens) needs BatchFeeder(embedding=<(V, E) device table>)")
-        raw = hb["raw_features"]
-        if isinstance(raw, (list, tuple)):
-            parts = [r if isinstance(r, torch.Tensor) else np.asarray(r) for r in raw]
-            lengths = np.array([p.shape[0] for p in parts], dtype=np.int64)
-        else:
-            parts = [raw if isinstance(raw, torch.Tensor) else np.asarray(raw)]
-            if "raw_lengths" not in hb:
-                raise ValueError("a packed raw_features array needs raw_lengths (B,)")
-            lengths = np.asarray(hb["raw_lengths"], dtype=np.int64).reshape(-1)
-            if (lengths < 0).any() or int(lengths.sum()) != parts[0].shape[0]:
-                raise ValueError(f"raw_lengths must be >= 0 and sum to the {parts[0].shape[0]} rows of raw_features")
+        if "win_start" in hb:
+            hb = self._cut_windows(hb)
+        parts, lengths = _raw_parts(hb)
         B = lengths.shape[0]
         Din = parts[0].shape[1] if parts and parts[0].ndim == 2 else -1
         if B < 1 or Din < 4 or Din % 4 or any(p.ndim != 2 or p.shape[1] != Din for p in parts):
@@ -212,6 +226,30 @@ class BatchFeeder:
         slot["batch"] = FedBatch((k, batch[k]) for k in _BATCH_KEYS)
         slot["batch"].cell_count = cell_count(np.minimum(lengths, self.T), self.T, self.L)
         return B
+
+    def _cut_windows(self, hb):
+        """Window form -> the raw batch of the windows' rows: views of rows win_start .. win_start + win_len of each video (nothing is
+        copied here; the raw path packs them) and the annotations in window time."""
+        from .sampling import window_annotations
+        parts, n = _raw_parts(hb)
+        if isinstance(hb["raw_features"], (list, tuple)):
+            videos = parts
+        else:
+            o = np.concatenate([[0], np.cumsum(n)])
+            videos = [parts[0][o[b]:o[b + 1]] for b in range(n.shape[0])]
+        to_i64 = lambda x: np.asarray(x.cpu() if isinstance(x, torch.Tensor) else x, dtype=np.int64).reshape(-1)
+        ws, wl = to_i64(hb["win_start"]), to_i64(hb["win_len"])
+        if ws.shape != n.shape or wl.shape != n.shape:
+            raise ValueError(f"win_start and win_len must be (B,) = {n.shape} (got {ws.shape}, {wl.shape})")
+        bad = np.nonzero((ws < 0) | (wl < 0) | (ws + wl > n))[0]
+        if bad.size:
+            b = int(bad[0])
+            raise ValueError(f"window {b} (rows {int(ws[b])} .. {int(ws[b] + wl[b])}) lies outside its video of {int(n[b])} rows")
+        times_w, duration_w = window_annotations(hb["times"], hb["duration"], n, ws, wl, self.T)
+        out = dict(raw_features=[v[int(s):int(s + w)] for v, s, w in zip(videos, ws, wl)], tokens=hb["tokens"], times=times_w, duration=duration_w)
+        if hb.get("spos") is not None:
+            out["spos"] = hb["spos"]
+        return out
 
     def feed(self, host_batches):
         """Generator of device batches.  A worker thread does the host side of every batch (pinned staging copy, enqueueing the

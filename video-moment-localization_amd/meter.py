@@ -13,12 +13,16 @@ Every batch sum is ``s = 0.0; for b in range(B): s += float64(x[b])``, then ``ac
 ``EpochMeterTorch`` -- the same class as plain torch ops on any device, the restatement the tests compare against; nothing routes
 to it -- reproduces ``EpochMeter.state`` bit for bit.
 
+``update_spans(span, count, gt)`` adds a batch of merged spans (``SMIN.localize_windows`` / ``merge_window_moments`` output) measured
+against ground-truth spans instead (include/smin_hip.h, smin_span_meter_update): slot 0, the top-1 IoU sum and the hit slots, with the
+meter's own n / m; the rule (``nms_thresh``) plays no part, and a meter may mix both kinds of update.
+
 All updates of one meter must be issued on one stream (the accumulator is ordered by the stream alone, no atomics)."""
 import ctypes
 
 import torch
 
-from .moments import MAX_K, _check, _mask_u8, _mul32, _nm_check, _sqrt32
+from .moments import MAX_K, _check, _mask_u8, _mul32, _nm_check, _span_check, _span_meter_call, _sqrt32
 
 _REF_N, _REF_M = (1, 5), (0.1, 0.3, 0.5, 0.7)
 
@@ -61,6 +65,12 @@ class _Meter:
 
     def reset(self):
         self.state.zero_()
+
+    def _spans_check(self, span, count, gt):
+        B, k = _span_check(span, count, gt)                                  # ValueError: shapes, or more than 64 slots
+        if k < max(self._n):
+            raise ValueError(f"update_spans: the meter's R@{max(self._n)} needs at least {max(self._n)} slots per pair (span has k = {k})")
+        return B, k
 
     def result(self, group=None):
         """The one host read: ``{"R@n, IoU=m": hits / samples, ..., "mIoU": ..., "num_samples": ...}`` plus ``"loss"`` when an
@@ -134,6 +144,20 @@ class EpochMeter(_Meter):
                  1.0 if self.nms_thresh is None else self.nms_thresh, ctypes.cast(nl, ctypes.c_void_p), len(self._n),
                  ctypes.cast(ml, ctypes.c_void_p), len(self._m), ptr(loss_), ptr(self.state), ptr(ws), nbytes)
 
+    def update_spans(self, span, count, gt):
+        """Adds B pairs' merged spans ``span (B, k, 2)`` / ``count (B,)`` against ``gt (B, 2)`` (same unit) to the state: samples,
+        top-1 IoU and the hits of the meter's n / m (module docstring).  Enqueues on the current stream, returns nothing."""
+        from ._lib import SminHipError
+        for t in (span, count, gt):
+            if not t.is_cuda:
+                raise SminHipError("EpochMeter.update_spans runs on a HIP device only (got a CPU tensor); there is no CPU fallback -- the "
+                                   "plain-torch restatement is available under the explicit name EpochMeterTorch")
+        if span.device != self.state.device:
+            raise ValueError(f"EpochMeter on {self.state.device} got tensors on {span.device}")
+        B, k = self._spans_check(span, count, gt)
+        if B:
+            _span_meter_call(span, count, gt, self._n, self._m, self.state)
+
 
 class EpochMeterTorch(_Meter):
     """``EpochMeter`` as plain torch ops and Python float64 sums on any device (module docstring): built on
@@ -175,4 +199,19 @@ class EpochMeterTorch(_Meter):
         delta[3] = s
         for q, k in enumerate(self.keys):
             delta[4 + q] = float(counts[k])                                       # a sum of 0 / 1 flags: exact in any order
+        self.state += torch.tensor(delta, dtype=torch.float64).to(self.state.device)
+
+    def update_spans(self, span, count, gt):
+        from .moments import _span_hits_torch, span_ious_torch
+        B, k = self._spans_check(span, count, gt)
+        ious = span_ious_torch(span, count, gt)
+        delta = [0.0] * self.state.numel()
+        delta[0] = float(B)
+        s = 0.0
+        for v in (ious[:, 0].tolist() if B else []):                             # slot 0's IoU (0 when empty), float64 sum in order
+            s += v
+        delta[3] = s
+        if B:
+            for q, v in enumerate(_span_hits_torch(ious, count, self._n, self._m).tolist()):
+                delta[4 + q] = float(v)
         self.state += torch.tensor(delta, dtype=torch.float64).to(self.state.device)

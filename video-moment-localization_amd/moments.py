@@ -300,3 +300,101 @@ def merge_window_moments_torch(idx, score, count, start, lens, pair_ptr, T, L, k
             cell[b, :n] = idx.reshape(-1, 2)[ks].to(torch.int64)
         out_count[b] = n
     return {"span": span, "score": out_score, "window": window, "cell": cell, "count": out_count}
+
+
+# ---------------------------------------------------------------- metric of merged spans against ground-truth spans
+def _span_check(span, count, gt):
+    if span.dim() != 3 or span.shape[2] != 2:
+        raise ValueError(f"span must be (B, k, 2), got {tuple(span.shape)}")
+    B, k = span.shape[0], span.shape[1]
+    if tuple(count.shape) != (B,) or tuple(gt.shape) != (B, 2):
+        raise ValueError(f"count must be (B,) = {(B,)} and gt (B, 2) = {(B, 2)}; got {tuple(count.shape)}, {tuple(gt.shape)}")
+    if not 1 <= k <= MAX_K:
+        raise ValueError(f"the span metric takes 1 <= k <= {MAX_K} slots per pair (got k = {k})")
+    return B, k
+
+
+def _span_nm_check(n, m, k):
+    keys = [f"R@{n_}, IoU={m_}" for n_ in n for m_ in m]
+    n, m = _nm_check(n, m)
+    if max(n) > k:
+        raise ValueError(f"R@{max(n)} needs at least {max(n)} slots per pair (span has k = {k})")
+    return keys, n, m
+
+
+def span_ious(span, count, gt):
+    """IoU of every slot of ``span (B, k, 2)`` (``merge_window_moments`` / ``SMIN.localize_windows`` output, ``count (B,)`` filled
+    slots) with the pair's ground truth ``gt (B, 2)`` in the same unit, on the device (include/smin_hip.h, smin_span_ious):
+    ``(B, k)`` float32, exactly 0 for the empty slots (their NaN span does not propagate).  HIP tensors only; no host read."""
+    from .training import _require_hip
+    from ._lib import call, ptr, stream
+    _require_hip(span, "span_ious")
+    B, k = _span_check(span, count, gt)
+    span_, gt_, count_ = span.detach().float().contiguous(), gt.detach().float().contiguous(), count.to(torch.int32).contiguous()
+    iou = torch.empty((B, k), dtype=torch.float32, device=span.device)
+    with torch.cuda.device(span.device):
+        call("smin_span_ious", stream(), ptr(span_), ptr(count_), ptr(gt_), B, k, ptr(iou))
+    return iou
+
+
+def _valid_slots(count, k):
+    """(B, k) bool: slot s < count[b], the count clamped to [0, k] as the kernels read it."""
+    return torch.arange(k, device=count.device).unsqueeze(0) < count.to(torch.int64).clamp(0, k).unsqueeze(1)
+
+
+def span_ious_torch(span, count, gt):
+    """``span_ious`` as plain torch on any device (same result, bit for bit): fminf / fmaxf as ``torch.fmin`` / ``torch.fmax``, the
+    fp32 differences as torch forms them (IEEE), the division rounded once."""
+    B, k = _span_check(span, count, gt)
+    span, gt = span.detach().float(), gt.detach().float()
+    st, en = span[..., 0], span[..., 1]
+    gs, ge = gt[:, 0:1], gt[:, 1:2]
+    inter = torch.fmax(torch.fmin(en, ge) - torch.fmax(st, gs), torch.zeros_like(st))
+    uni = torch.fmax(en, ge) - torch.fmin(st, gs)
+    pos = uni > 0
+    iou = torch.where(pos, _div32(inter, torch.where(pos, uni, torch.ones_like(uni))), torch.zeros_like(uni))
+    return torch.where(_valid_slots(count, k), iou, torch.zeros_like(iou))
+
+
+def _span_meter_call(span, count, gt, n, m, acc):
+    """smin_span_meter_update of B >= 1 checked pairs into ``acc`` (fp64, 4 + len(n) * len(m)) on the current stream."""
+    from ._lib import SminHipError, call, load, ptr, stream
+    B, k = span.shape[0], span.shape[1]
+    span_, gt_, count_ = span.detach().float().contiguous(), gt.detach().float().contiguous(), count.to(torch.int32).contiguous()
+    nl, ml = (ctypes.c_int * len(n))(*n), (ctypes.c_float * len(m))(*m)
+    with torch.cuda.device(span.device):
+        nbytes = load().smin_span_meter_ws_bytes(B, len(n), len(m))
+        if nbytes == 0:
+            raise SminHipError(f"smin_span_meter_ws_bytes rejected B={B}, nn={len(n)}, nm={len(m)}")
+        ws = torch.empty((nbytes,), dtype=torch.uint8, device=span.device)
+        call("smin_span_meter_update", stream(), ptr(span_), ptr(count_), ptr(gt_), B, k, ctypes.cast(nl, ctypes.c_void_p), len(n),
+             ctypes.cast(ml, ctypes.c_void_p), len(m), ptr(acc), ptr(ws), nbytes)
+
+
+def compute_span_ious(span, count, gt, n=(1, 5), m=(0.1, 0.3, 0.5, 0.7)):
+    """R@n, IoU=m of merged spans on the device, mirroring ``compute_ious``: ``{"R@n, IoU=m": pairs with some slot
+    s < min(n, count) whose IoU with gt is > m}`` (strict, as utils.py:29), summed over the pairs by the device
+    (smin_span_meter_update into a fresh accumulator).  One host read.  HIP tensors only."""
+    from .training import _require_hip
+    _require_hip(span, "compute_span_ious")
+    B, k = _span_check(span, count, gt)
+    keys, n, m = _span_nm_check(n, m, k)
+    acc = torch.zeros((4 + len(keys),), dtype=torch.float64, device=span.device)
+    if B:
+        _span_meter_call(span, count, gt, n, m, acc)
+    return dict(zip(keys, acc[4:].tolist()))
+
+
+def _span_hits_torch(ious, count, n, m):
+    """(len(n) * len(m),) int64: pairs with a hit for each (n, m), thresholds converted to fp32 once."""
+    valid = _valid_slots(count, ious.shape[1])
+    thr = torch.tensor(m, dtype=torch.float32, device=ious.device)
+    return torch.stack([((ious[:, :n_] > thr[c]) & valid[:, :n_]).any(dim=1).sum() for n_ in n for c in range(len(m))])
+
+
+def compute_span_ious_torch(span, count, gt, n=(1, 5), m=(0.1, 0.3, 0.5, 0.7)):
+    """``compute_span_ious`` through ``span_ious_torch`` (any device)."""
+    B, k = _span_check(span, count, gt)
+    keys, n, m = _span_nm_check(n, m, k)
+    counts = _span_hits_torch(span_ious_torch(span, count, gt), count, n, m).tolist()
+    return {k_: float(v) for k_, v in zip(keys, counts)}

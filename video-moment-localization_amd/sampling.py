@@ -341,6 +341,53 @@ def window_plan(lengths, window, stride):
             torch.from_numpy(np.asarray(ptr, dtype=np.int64)))
 
 
+def window_annotations(times, duration, lengths, win_start, win_len, T):
+    """Annotations of B samples re-expressed in the time of one window each, for training on windows (host, float64; unit: raw rows).
+
+    ``times (B, 2)`` / ``duration (B,)`` in seconds, ``lengths (B,)`` the videos' row counts, ``win_start`` / ``win_len (B,)`` the
+    chosen window of each.  With ``g = times / duration * n`` (the ground truth in rows): ``times_w = g - win_start`` and
+    ``duration_w = max(win_len, T)``.  This is the geometry of the merge (``moments.window_spans``): a cell of the window spans
+    ``max(len, T) / L`` rows, which is what the target kernel forms from ``duration_w``.  The ground truth is not clipped to the
+    window: a window holding part of a long moment gets IoUs below 1, one that misses it ``sm = 0`` everywhere, and sigma comes
+    from the whole moment.  The targets are then those of dataset.py:95-126 for ``(times_w, duration_w, nfeats = min(win_len, T))``.
+    Returns ``(times_w (B, 2), duration_w (B,))`` float64 numpy arrays."""
+    t = np.asarray(times.cpu() if isinstance(times, torch.Tensor) else times, dtype=np.float64).reshape(-1, 2)
+    d = np.asarray(duration.cpu() if isinstance(duration, torch.Tensor) else duration, dtype=np.float64).reshape(-1)
+    n, s, w = _lengths_host(lengths), _lengths_host(win_start), _lengths_host(win_len)
+    B = t.shape[0]
+    if not (d.shape[0] == n.shape[0] == s.shape[0] == w.shape[0] == B):
+        raise ValueError(f"window_annotations: times (B, 2) with duration, lengths, win_start, win_len (B,) (got B = {B} and "
+                         f"{d.shape[0]}, {n.shape[0]}, {s.shape[0]}, {w.shape[0]})")
+    g = t / d[:, None] * n.astype(np.float64)[:, None]
+    return g - s.astype(np.float64)[:, None], np.maximum(w, int(T)).astype(np.float64)
+
+
+def draw_windows(lengths, gt_rows, window, stride, rng, p_overlap):
+    """One training window per sample, drawn on the host from a ``numpy.random.Generator`` (reproducible from its seed).
+
+    The candidates of sample b are ``window_plan([n_b], window, stride)``: the grid ``SMIN.localize_windows`` scores.  Per sample, in
+    order: ``u = rng.random()``; the overlapping candidates are those with ``min(s + len, ge) - max(s, gs) > 0`` for the ground
+    truth ``gt_rows[b] = (gs, ge)`` in rows; if ``u < p_overlap`` and there is one, the choice is among them, else among all
+    candidates; one ``rng.integers(0, len(set))`` picks it.  ``p_overlap`` is the training policy (1: always a window that sees the
+    moment where one exists; 0: uniform over the grid).  Returns ``(win_start (B,) int64, win_len (B,) int32)``; a video of 0 rows
+    raises ValueError."""
+    n = _lengths_host(lengths)
+    gt = np.asarray(gt_rows.cpu() if isinstance(gt_rows, torch.Tensor) else gt_rows, dtype=np.float64).reshape(-1, 2)
+    if gt.shape[0] != n.shape[0]:
+        raise ValueError(f"draw_windows: gt_rows must be (B, 2) for B = {n.shape[0]} videos (got {gt.shape})")
+    win_start, win_len = np.zeros(n.shape[0], np.int64), np.zeros(n.shape[0], np.int32)
+    for b, v in enumerate(n.tolist()):
+        if v == 0:
+            raise ValueError(f"draw_windows: video {b} has no rows")
+        starts, lens, _ = (x.numpy() for x in window_plan([v], window, stride))
+        u = rng.random()
+        over = np.flatnonzero(np.minimum(starts + lens, gt[b, 1]) - np.maximum(starts, gt[b, 0]) > 0)
+        cand = over if (u < p_overlap and over.size) else np.arange(starts.shape[0])
+        c = cand[int(rng.integers(0, cand.shape[0]))]
+        win_start[b], win_len[b] = starts[c], lens[c]
+    return win_start, win_len
+
+
 def sample_windows(raw, row_begin, lens, T, mode="pick"):
     """Resample W row ranges of ``raw`` to ``(W, T, Din)`` on the device: sample ``w`` is exactly ``sample_clips`` of a video made
     of rows ``row_begin[w] .. row_begin[w] + lens[w]`` (eval split, ``spos = 0``), in either mode; ranges may overlap and repeat,

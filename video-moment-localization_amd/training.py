@@ -279,3 +279,39 @@ def test_model(model, batches, meter=None):
 
 
 test_model.__test__ = False                                       # a loop of the reference, not a pytest test
+
+
+def test_model_windows(model, groups, meter=None, *, window=None, stride=None, k=5, k_window=None, nms_thresh=0.5, mode="pick", max_batch=64):
+    """The test loop over videos of any length: R@n, IoU=m and mIoU of ``model.localize_windows``' merged spans against the ground
+    truth, with no host read per group.  Each group is a dict with the arguments of ``localize_windows`` -- ``raw``, ``lengths``,
+    ``query_features``, ``query_mask``, optionally ``video_index`` -- plus the pairs' annotations as host values in seconds,
+    ``times (B, 2)`` and ``duration (B,)``.  Per group: the retrieval (score() with ``model.forward_only_scoring``, as
+    ``localize_windows`` decides), the ground truth in rows ``times / duration * n[video_index]`` formed on the host in float64,
+    rounded once to fp32 and sent in one pinned asynchronous copy, then ``meter.update_spans`` (a default ``EpochMeter`` is made if
+    none is given; ``k`` must reach its largest n).  The one ``meter.result()`` at the end is returned.  The meter is not reset here."""
+    import numpy as np
+    model.eval()
+    for group in groups:
+        raw = group["raw"]
+        if meter is None:
+            from .meter import EpochMeter
+            meter = EpochMeter(device=raw.device)
+        if k < max(meter.n):                                              # before any retrieval runs, not at the first update_spans
+            raise ValueError(f"test_model_windows: k = {k} moments per pair cannot give the meter's R@{max(meter.n)}")
+        out = model.localize_windows(raw, group["lengths"], group["query_features"], group["query_mask"], video_index=group.get("video_index"),
+                                     window=window, stride=stride, k=k, k_window=k_window, nms_thresh=nms_thresh, mode=mode, max_batch=max_batch)
+        host = lambda x, dt: np.asarray(x.cpu() if isinstance(x, torch.Tensor) else x, dtype=dt)
+        n = host(group["lengths"], np.int64).reshape(-1)
+        vi = group.get("video_index")
+        rows = n if vi is None else n[host(vi, np.int64).reshape(-1)]
+        times, duration = host(group["times"], np.float64).reshape(-1, 2), host(group["duration"], np.float64).reshape(-1)
+        if times.shape[0] != rows.shape[0] or duration.shape[0] != rows.shape[0]:
+            raise ValueError(f"test_model_windows: times (B, 2) and duration (B,) must cover the group's B = {rows.shape[0]} pairs "
+                             f"(got {times.shape}, {duration.shape})")
+        gt = (times / duration[:, None] * rows.astype(np.float64)[:, None]).astype(np.float32)
+        gt = torch.from_numpy(gt).pin_memory().to(raw.device, non_blocking=True)
+        meter.update_spans(out["span"], out["count"], gt)
+    return meter.result()
+
+
+test_model_windows.__test__ = False
