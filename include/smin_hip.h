@@ -44,7 +44,8 @@ extern "C" {
  * time), and a masks-only use of smin_build_targets (sm == NULL); forward-only scoring -- smin_score_tail_fwd and
  * smin_score_tail_ws_bytes (the last layer's moment unit and the map's score head as row dots); an epoch's metric and loss totals
  * kept on the device -- smin_epoch_meter_update and smin_epoch_meter_ws_bytes; the metric of merged spans against ground-truth
- * spans -- smin_span_ious, smin_span_meter_update and smin_span_meter_ws_bytes */
+ * spans -- smin_span_ious, smin_span_meter_update and smin_span_meter_ws_bytes; the optimizer update -- smin_adam_step, smin_grad_norm
+ * and smin_adam_ws_bytes */
 #define SMIN_HIP_ABI_VERSION 2
 
 int smin_abi_version(void);
@@ -589,6 +590,35 @@ int smin_sum_lists(void* stream, const float* const* srcs, int n, size_t numel, 
  * to ride on (content stream: layer 0's constant).  Two fixed-order stages. */
 size_t smin_col_sum_workspace_bytes(int R, int W);
 int smin_col_sum(void* stream, const float* x, int R, int W, float* out, void* ws, size_t ws_bytes);
+
+/* ---- Adam / AdamW update of a parameter list with the gradients' global norm on the device (csrc/optimizer.hip).
+ * param / grad / numel / moment_offset: HOST arrays of n entries (device pointers, element counts, first element of the tensor's segment
+ * in the two flat fp32 moment buffers exp_avg / exp_avg_sq).  Tensors need no alignment: 16-byte loads and stores where param, grad and
+ * both segments are 16-byte aligned, 4-byte ones otherwise and for a tensor's last numel % 4 elements.  grad is never written.
+ *   state: 8 doubles on the device -- [0] t, completed steps; [1] beta1^t; [2] beta2^t (running products, one multiplication per
+ *   step); [3] learning rate; [4] total gradient norm of the last step; [5] the clip coefficient it used (an fp32 value); [6] skipped
+ *   steps; [7] non-finite flag of the last step.  The update reads the state; one closing wave behind it advances [0..2], or [6].
+ * Per element, every fp32 operation rounded on its own, with B1 = state[1] * beta1, B2 = state[2] * beta2, step_size =
+ * (float)(lr / (1 - B1)), sbc2 = (float)sqrt(1 - B2) formed in double and the constants rounded once to fp32:
+ *   g = grad * c                       (only when the norm ran; c = state[5])
+ *   g = g + wd * p                     (weight_decay != 0, decoupled == 0)          p = p - (float)(lr * wd) * p   (decoupled != 0)
+ *   m = beta1 * m + (1 - beta1) * g    v = beta2 * v + ((1 - beta2) * g) * g        p = p - step_size * (m / (sqrtf(v) / sbc2 + eps))
+ * Launches: ceil(non-empty tensors / 96) updates + 1 closing wave; none when n == 0 or every tensor is empty.
+ * The norm entry, issued before the step on the same stream when clipping or the guard is wanted: per 4096-element chunk a partial sum of
+ * (double)g * (double)g, the partials added in a fixed order by one workgroup (no atomics: the same bits every run); it writes
+ * state[4] = sqrt(sum), state[5] = (float)min(1, max_norm / (norm + 1e-6)) -- 1 when max_norm < 0: guard only -- and state[7] = 1 when
+ * the sum is inf or NaN.  ws: the partials, sized by the query below from the list's total element count.
+ * The step entry with norm_ws != NULL scales by state[5]; with skip_nonfinite != 0 (which needs norm_ws) and state[7] set it writes
+ * nothing and the closing wave adds 1 to state[6] instead of advancing t.  With norm_ws == NULL the closing wave sets [4] = NaN (not
+ * formed), [5] = 1, [7] = 0.
+ * Rejected before any launch: n < 0, a negative count or offset, a NULL pointer with a positive count, betas outside [0, 1), eps < 0,
+ * weight_decay < 0, a NaN max_norm, a workspace that is too small. */
+size_t smin_adam_ws_bytes(int64_t total_numel, int n);
+int smin_grad_norm(void* stream, const float* const* grad, const int64_t* numel, int n, double max_norm, double* state, void* ws,
+                   size_t ws_bytes);
+int smin_adam_step(void* stream, float* const* param, const float* const* grad, const int64_t* numel, const int64_t* moment_offset, int n,
+                   float* exp_avg, float* exp_avg_sq, double* state, double beta1, double beta2, double eps, double weight_decay,
+                   int decoupled, int skip_nonfinite, const void* norm_ws);
 
 /* ---- stand-alone fp32 MFMA GEMM  C[M][N] = A[M][K] * B[N][K]^T  (used by tests and bench.py's
  * roofline probe; same engine as every contraction above). */

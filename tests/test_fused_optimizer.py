@@ -1,0 +1,611 @@
+"""FusedAdam (csrc/optimizer.hip, optim.py): the Adam / AdamW update of a whole parameter list with the gradient norm, clipping and the
+non-finite guard on the device, against FusedAdamTorch -- the same arithmetic as plain torch ops -- bit for bit, and FusedAdamTorch against
+torch's own optimizers.
+
+"The set": element counts 1, 1, 3, 4, 5, 1023, 4096, 4097, 8193, a (64, 129) matrix, and two 4097-element parameters that are views
+at a 4-byte and an 8-byte offset into larger buffers (these take the kernels' scalar path).  Gradients are randn * 10**randint(-6, 2),
+elementwise, from a seeded CPU generator; the two views' gradients are views at the same offsets."""
+import copy
+import ctypes
+import functools
+import math
+
+import pytest
+import torch
+
+from tests import helpers as H
+
+SET_COUNTS = (1, 1, 3, 4, 5, 1023, 4096, 4097, 8193)
+VIEW_N = 4097
+VARIANTS = {                        # name -> (our keywords, torch class name, torch keywords, max_norm)
+    "plain": (dict(), "Adam", dict(), None),
+    "l2": (dict(weight_decay=1e-2), "Adam", dict(weight_decay=1e-2), None),
+    "decoupled": (dict(weight_decay=1e-2, decoupled=True), "AdamW", dict(weight_decay=1e-2), None),
+    "clipped": (dict(max_norm=1.0), "Adam", dict(), 1.0),
+}
+
+
+def set_values(seed=0, extra=()):
+    """the set's initial values: a list of (tensor, view offset or None)"""
+    g = torch.Generator().manual_seed(seed)
+    vals = [(torch.randn(n, generator=g), None) for n in SET_COUNTS]
+    vals.append((torch.randn(64, 129, generator=g), None))
+    vals += [(torch.randn(VIEW_N, generator=g), 1), (torch.randn(VIEW_N, generator=g), 2)]
+    vals += [(torch.randn(n, generator=g), None) for n in extra]
+    return vals
+
+
+def _placed(x, off, device, dtype):
+    """x on `device`; with `off`, as a view `off` elements into a larger buffer"""
+    x = x.to(dtype)
+    if off is None:
+        return x.clone().to(device)
+    buf = torch.zeros(x.numel() + 8, dtype=dtype, device=device)
+    buf[off:off + x.numel()].copy_(x.reshape(-1))
+    return buf[off:off + x.numel()].view(x.shape)
+
+
+def make_params(vals, device="cpu", dtype=torch.float32):
+    return [torch.nn.Parameter(_placed(x, off, device, dtype)) for x, off in vals]
+
+
+def draw_grads(vals, g):
+    return [torch.randn(x.shape, generator=g) * 10.0 ** torch.randint(-6, 3, x.shape, generator=g).float() for x, _ in vals]
+
+
+def set_grads(params, vals, grads, shift=0):
+    """assign clones of `grads` (a view's gradient is a view at the same offset; `shift` moves every gradient off 16-byte alignment)"""
+    for p, (_, off), gr in zip(params, vals, grads):
+        p.grad = _placed(gr, (off or 0) + shift if (off or shift) else None, p.device, p.dtype)
+
+
+def bits(t):
+    return t.detach().cpu().contiguous().view(torch.int32)
+
+
+def same_bits(a, b):
+    return torch.equal(bits(a), bits(b))
+
+
+def assert_same_state(opt_a, ps_a, opt_b, ps_b, what=""):
+    for i, (a, b) in enumerate(zip(ps_a, ps_b)):
+        assert same_bits(a, b), (what, i, "p")
+        for key in ("exp_avg", "exp_avg_sq"):
+            assert same_bits(opt_a.state[a][key], opt_b.state[b][key]), (what, i, key)
+
+
+def FA():
+    import models
+    return models.vml_amd
+
+
+# ================================================================ CPU
+@functools.lru_cache(maxsize=None)
+def variant_errors(name, steps=10):
+    """(E, ours): the largest absolute parameter error of torch's fp32 optimizer (foreach=False) and of FusedAdamTorch after `steps`
+    steps on the set, both against torch's optimizer in fp64 on the same fp32-valued inputs."""
+    ours_kw, cls, torch_kw, max_norm = VARIANTS[name]
+    vals = set_values(0)
+    p_o, p_t, p_d = make_params(vals), make_params(vals), make_params(vals, dtype=torch.float64)
+    ours = FA().FusedAdamTorch(p_o, **ours_kw)
+    t32 = getattr(torch.optim, cls)(p_t, foreach=False, **torch_kw)
+    t64 = getattr(torch.optim, cls)(p_d, foreach=False, **torch_kw)
+    g = torch.Generator().manual_seed(1)
+    for _ in range(steps):
+        grads = draw_grads(vals, g)
+        for ps in (p_o, p_t, p_d):
+            set_grads(ps, vals, grads)
+        if max_norm is not None:
+            torch.nn.utils.clip_grad_norm_(p_t, max_norm, foreach=False)
+            torch.nn.utils.clip_grad_norm_(p_d, max_norm, foreach=False)
+        ours.step(), t32.step(), t64.step()
+    err = lambda ps: max((p.detach().double() - d.detach()).abs().max().item() for p, d in zip(ps, p_d))
+    return err(p_t), err(p_o)
+
+
+@pytest.mark.parametrize("name", list(VARIANTS))
+def test_restatement_is_adam(name):
+    """10 steps of FusedAdamTorch on the set against torch.optim.Adam / AdamW in fp64; the yardstick E is torch's own fp32 optimizer
+    against that run, and the restatement must stay within 2 E (two fp32 roundings of one formula in another operation order).
+    Measured E (largest absolute parameter error), torch fp32 / FusedAdamTorch:
+        plain 8.2e-07 / 8.2e-07, l2 6.8e-07 / 6.8e-07, decoupled 2.0e-06 / 1.5e-06, clipped 8.8e-07 / 8.8e-07."""
+    E, ours = variant_errors(name)
+    print(f"{name}: torch fp32 E = {E:.3e}, FusedAdamTorch = {ours:.3e}")
+    assert 0.0 < E < 1e-4
+    assert ours <= 2.0 * E, (name, ours, E)
+
+
+def _run_torch_side(steps, vals, seed=1):
+    """FusedAdamTorch on the set for `steps` steps; returns (params, optimizer, generator)"""
+    ps = make_params(vals)
+    opt = FA().FusedAdamTorch(ps, weight_decay=1e-2, max_norm=1.0)
+    g = torch.Generator().manual_seed(seed)
+    for _ in range(steps):
+        set_grads(ps, vals, draw_grads(vals, g))
+        opt.step()
+    return ps, opt, g
+
+
+def test_state_dict_round_trips_with_torch():
+    A = FA()
+    vals = set_values(0)
+    # ours -> ours: 5 steps, save, load into a fresh optimizer on a copy of the parameters, 5 more == 10 uninterrupted
+    p10, _, _ = _run_torch_side(10, vals)
+    p5, o5, g = _run_torch_side(5, vals)
+    sd = copy.deepcopy(o5.state_dict())
+    assert sorted(sd["state"][0]) == ["exp_avg", "exp_avg_sq", "step"]
+    assert sd["state"][0]["step"].dtype == torch.float32 and sd["state"][0]["step"].device.type == "cpu" and float(sd["state"][0]["step"]) == 5.0
+    want_keys = {"lr", "betas", "eps", "weight_decay", "amsgrad", "maximize", "foreach", "capturable", "differentiable", "fused", "decoupled",
+                 "max_norm", "skip_nonfinite", "params"}
+    assert want_keys <= set(sd["param_groups"][0]) and len(sd["param_groups"]) == 1
+    pr = [torch.nn.Parameter(_placed(p.detach(), off, "cpu", torch.float32)) for p, (_, off) in zip(p5, vals)]
+    fresh = A.FusedAdamTorch(pr)                                   # other hyperparameters: the loaded group brings them
+    fresh.load_state_dict(sd)
+    assert fresh.param_groups[0]["weight_decay"] == 1e-2 and fresh.param_groups[0]["max_norm"] == 1.0
+    o0 = fresh.state[pr[0]]["exp_avg"]
+    assert o0.data_ptr() == fresh._exp_avg.data_ptr()              # loading copied into the flat buffer: the views stay views
+    for _ in range(5):
+        set_grads(pr, vals, draw_grads(vals, g))
+        fresh.step()
+    for i, (a, b) in enumerate(zip(pr, p10)):
+        assert same_bits(a, b), i
+
+    # torch -> ours: Adam's dict after 5 steps loads, and the sixth step stays within 2 E of the fp64 run
+    E, _ = variant_errors("plain")
+    p_t, p_d = make_params(vals), make_params(vals, dtype=torch.float64)
+    t32, t64 = torch.optim.Adam(p_t, foreach=False), torch.optim.Adam(p_d, foreach=False)
+    g = torch.Generator().manual_seed(1)
+    for _ in range(5):
+        grads = draw_grads(vals, g)
+        set_grads(p_t, vals, grads), set_grads(p_d, vals, grads)
+        t32.step(), t64.step()
+    mine = A.FusedAdamTorch(p_t)
+    mine.load_state_dict(copy.deepcopy(t32.state_dict()))
+    assert mine._state[:3].tolist() == [5.0, A.optim._beta_power(0.9, 5), A.optim._beta_power(0.999, 5)]
+    grads = draw_grads(vals, g)
+    set_grads(p_t, vals, grads), set_grads(p_d, vals, grads)
+    mine.step(), t64.step()
+    err = max((p.detach().double() - d.detach()).abs().max().item() for p, d in zip(p_t, p_d))
+    print(f"sixth step after loading torch's dict: {err:.3e} (2 E = {2 * E:.3e})")
+    assert err <= 2.0 * E
+    # AdamW's dict carries decoupled_weight_decay
+    w = torch.optim.AdamW(make_params(vals), weight_decay=0.05)
+    mine.load_state_dict(w.state_dict())
+    assert mine.param_groups[0]["decoupled"] is True and mine.param_groups[0]["weight_decay"] == 0.05 and float(mine._state[0]) == 0.0
+
+    # ours -> torch: accepted, and steps
+    p_x = [torch.nn.Parameter(p.detach().clone()) for p in p5]
+    t = torch.optim.Adam(p_x)
+    t.load_state_dict(copy.deepcopy(o5.state_dict()))
+    assert float(t.state[p_x[0]]["step"]) == 5.0 and t.param_groups[0]["weight_decay"] == 1e-2
+    before = [p.detach().clone() for p in p_x]
+    for p, gr in zip(p_x, draw_grads(vals, g)):
+        p.grad = gr
+    t.step()
+    assert float(t.state[p_x[0]]["step"]) == 6.0 and all(not torch.equal(a, b) for a, b in zip(before, p_x))
+
+    # refused
+    bad = copy.deepcopy(o5.state_dict())
+    bad["state"][3]["step"] = torch.tensor(4.0)
+    with pytest.raises(ValueError, match="step counts differ"):
+        fresh.load_state_dict(bad)
+    two = copy.deepcopy(o5.state_dict())
+    two["param_groups"] = [dict(two["param_groups"][0], params=[0]), dict(two["param_groups"][0], params=list(range(1, len(vals))))]
+    with pytest.raises(ValueError, match="one parameter group"):
+        fresh.load_state_dict(two)
+    with pytest.raises(ValueError, match="one parameter group"):
+        A.FusedAdamTorch([{"params": make_params(vals[:2])}, {"params": make_params(vals[2:4]), "lr": 1e-4}])
+    with pytest.raises(ValueError, match="amsgrad"):
+        A.FusedAdamTorch(make_params(vals), amsgrad=True)
+    with pytest.raises(ValueError, match="amsgrad"):
+        fresh.load_state_dict(torch.optim.Adam(make_params(vals), amsgrad=True).state_dict())
+    with pytest.raises(ValueError, match="maximize"):
+        A.FusedAdamTorch(make_params(vals), maximize=True)
+    with pytest.raises(ValueError, match="closure"):
+        fresh.step(lambda: 0.0)
+    with pytest.raises(ValueError, match="one parameter group"):          # ... and none can be added later
+        fresh.add_param_group({"params": make_params(vals[:1])})
+    assert len(fresh.param_groups) == 1
+    fresh.param_groups.append(dict(fresh.param_groups[0], params=make_params(vals[:1])))
+    with pytest.raises(ValueError, match="one parameter group"):          # (nor slipped in: step() looks)
+        fresh.step()
+    fresh.param_groups.pop()
+    for i, (a, b) in enumerate(zip(pr, p10)):                      # a refused load changed nothing
+        assert same_bits(a, b), i
+
+
+def test_load_hooks_fire_and_the_skip_counter_travels():
+    A = FA()
+    vals = set_values(0)[:5]
+    ps = make_params(vals)
+    opt = A.FusedAdamTorch(ps, skip_nonfinite=True)
+    g = torch.Generator().manual_seed(6)
+    set_grads(ps, vals, draw_grads(vals, g))
+    opt.step()
+    ps[1].grad[0] = math.nan
+    opt.step()
+    sd = copy.deepcopy(opt.state_dict())
+    assert sd["param_groups"][0]["skipped_steps"] == 1 and float(sd["state"][0]["step"]) == 1.0
+    fresh = A.FusedAdamTorch(make_params(vals))
+    seen = []
+    fresh.register_load_state_dict_pre_hook(lambda o, d: seen.append("pre"))
+    fresh.register_load_state_dict_post_hook(lambda o: seen.append("post"))
+    fresh.load_state_dict(sd)
+    assert seen == ["pre", "post"]
+    assert float(fresh.skipped_steps) == 1.0 and float(fresh._state[0]) == 1.0 and fresh.param_groups[0]["skip_nonfinite"] is True
+    assert "skipped_steps" not in fresh.param_groups[0]
+    fresh.load_state_dict(torch.optim.Adam(make_params(vals)).state_dict())
+    assert float(fresh.skipped_steps) == 0.0
+
+
+def test_restatement_sqrt_is_correctly_rounded_and_records_the_coefficient_it_used():
+    """The restatement takes sqrtf through fp64 (53 >= 2 * 24 + 2 bits: the second rounding cannot move the result).  torch's own fp32
+    sqrt is not held to that: for x = 0x1.2452ccp-24 a CPU build returned 0x1.118f3ap-12 where the correctly rounded root is
+    0x1.118f3cp-12 (672 of 100 000 random inputs differed there); what it returns here is printed, not asserted."""
+    x = float.fromhex("0x1.2452ccp-24")
+    want = torch.tensor(math.sqrt(x), dtype=torch.float64).float().item()      # math.sqrt is correctly rounded in fp64
+    assert want == float.fromhex("0x1.118f3cp-12")
+    t = torch.tensor([x], dtype=torch.float32)
+    assert t.double().sqrt().to(torch.float32).item() == want
+    print("torch fp32 sqrt:", t.sqrt().item().hex(), "correctly rounded:", want.hex())
+    # state[5] is the coefficient the step used, also when it is handed over
+    A = FA()
+    vals = set_values(0)[:5]
+    ps = make_params(vals)
+    opt = A.FusedAdamTorch(ps, max_norm=1.0)
+    set_grads(ps, vals, draw_grads(vals, torch.Generator().manual_seed(8)))
+    opt.step(clip_coef=0.25)
+    assert float(opt.clip_coef) == 0.25
+    opt.step()
+    assert float(opt.clip_coef) == A.optim.clip_coefficient(float(opt.grad_norm), 1.0) != 0.25
+    with pytest.raises(ValueError, match="fp32 value"):
+        opt.step(clip_coef=0.1)
+
+
+def test_restatement_skips_and_schedules_like_the_device_class():
+    """The restatement's own guard and learning-rate path (the GPU tests lean on them): a non-finite step changes nothing and is
+    counted, torch's schedulers drive param_groups[0]["lr"], and a tensor without a gradient is left alone."""
+    A = FA()
+    vals = set_values(0)[:6]
+    ps = make_params(vals)
+    opt = A.FusedAdamTorch(ps, lr=1e-2, skip_nonfinite=True)
+    sched = torch.optim.lr_scheduler.StepLR(opt, step_size=1, gamma=0.5)
+    g = torch.Generator().manual_seed(2)
+    set_grads(ps, vals, draw_grads(vals, g))
+    opt.step(), sched.step()
+    assert opt.param_groups[0]["lr"] == 5e-3 and float(opt._state[0]) == 1.0 and float(opt.clip_coef) == 1.0
+    keep = [p.detach().clone() for p in ps]
+    ps[0].grad[0] = math.inf
+    opt.step()
+    assert float(opt.skipped_steps) == 1.0 and float(opt._state[0]) == 1.0 and float(opt._state[7]) == 1.0
+    assert all(same_bits(a, b) for a, b in zip(keep, ps))
+    set_grads(ps, vals, draw_grads(vals, g))
+    ps[2].grad = None
+    opt.step()
+    assert float(opt._state[3]) == 5e-3 and float(opt._state[0]) == 2.0 and same_bits(keep[2], ps[2]) and not same_bits(keep[1], ps[1])
+
+
+# ================================================================ GPU
+@pytest.fixture(scope="module")
+def dev():
+    assert torch.cuda.is_available(), "GPU tests need a HIP device"
+    FA()._lib.load_torch()
+    return torch.device("cuda:0")
+
+
+def _pair(vals, dev, **kw):
+    """the device optimizer and the restatement on equal copies of `vals`"""
+    A = FA()
+    pd, pc = make_params(vals, dev), make_params(vals)
+    return pd, A.FusedAdam(pd, **kw), pc, A.FusedAdamTorch(pc, **kw)
+
+
+def _both_step(vals, grads, pd, od, pc, oc, shift=0, what=""):
+    """one step on both sides with the same gradients; the restatement gets the device's coefficient when the norm ran"""
+    set_grads(pd, vals, grads, shift)
+    set_grads(pc, vals, grads)
+    od.step()
+    use_norm = od._needs_norm(od.param_groups[0])
+    oc.step(clip_coef=float(od.clip_coef) if use_norm else None)
+    assert_same_state(od, pd, oc, pc, what)
+    for i, (p, gr) in enumerate(zip(pd, grads)):
+        assert same_bits(p.grad, gr), (what, i, "grad was written")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", list(VARIANTS))
+def test_update_bit_for_bit(dev, name):
+    """6 steps on the set: p, exp_avg and exp_avg_sq of every tensor equal FusedAdamTorch's on the CPU bit for bit after every step, and
+    grad is unchanged.  The restatement gets the same gradients and, clipped, the coefficient the device used."""
+    vals = set_values(0)
+    pd, od, pc, oc = _pair(vals, dev, lr=1e-3, **VARIANTS[name][0])
+    g = torch.Generator().manual_seed(1)
+    for it in range(6):
+        _both_step(vals, draw_grads(vals, g), pd, od, pc, oc, what=(name, it))
+    assert od._state[:3].tolist() == oc._state[:3].tolist() and float(od._state[0]) == 6.0
+    if name == "clipped":
+        assert 0.0 < float(od.clip_coef) < 1.0                     # (the set's gradients reach 1e2: clipping was active)
+
+
+@pytest.mark.gpu
+def test_norm_and_coefficient(dev):
+    A = FA()
+    vals = set_values(0, extra=(1_000_003,))
+    g = torch.Generator().manual_seed(3)
+    grads = draw_grads(vals, g)
+    n = sum(gr.numel() for gr in grads)
+    exact = math.fsum(x for gr in grads for x in (gr.double() * gr.double()).flatten().tolist())   # the squares are exact in fp64
+    norms = []
+    for shift in (0, 0, 1, 3):                                     # two equal runs, then every gradient off 16-byte alignment
+        pd = make_params(vals, dev)
+        od = A.FusedAdam(pd, max_norm=1.0)
+        set_grads(pd, vals, grads, shift)
+        od.step()
+        norm, coef, flag = float(od.grad_norm), float(od.clip_coef), float(od._state[7])
+        rel = abs(norm * norm - exact) / exact
+        print(f"shift {shift}: norm {norm!r}, relative error of norm^2 {rel:.3e} (bound {(n - 1) * 2.0 ** -53:.3e}), coefficient {coef!r}")
+        assert rel <= (n - 1) * 2.0 ** -53
+        assert coef == A.optim.clip_coefficient(norm, 1.0) and flag == 0.0
+        assert coef == torch.tensor(min(1.0, 1.0 / (norm + 1e-6)), dtype=torch.float64).float().item()
+        norms.append(norm)
+    assert len({x.hex() for x in norms}) == 1, norms               # the same bits: run to run, and on either load path
+    # max_norm far above the norm: the coefficient is exactly 1 and the update is the unclipped one
+    vals = set_values(0)
+    grads = draw_grads(vals, g)
+    p1, p2 = make_params(vals, dev), make_params(vals, dev)
+    o1, o2 = A.FusedAdam(p1, max_norm=1e30), A.FusedAdam(p2)
+    for _ in range(2):
+        set_grads(p1, vals, grads), set_grads(p2, vals, grads)
+        o1.step(), o2.step()
+    assert float(o1.clip_coef) == 1.0 and float(o1.grad_norm) > 1.0
+    assert o2._ws is None and math.isnan(float(o2.grad_norm)) and float(o2.clip_coef) == 1.0
+    assert_same_state(o1, p1, o2, p2, "max_norm = 1e30")
+
+
+@pytest.mark.gpu
+def test_nonfinite_guard(dev):
+    """One inf in the 1-element tensor, then one NaN in the last element of the 8193 tensor: with skip_nonfinite every p, m, v and
+    state[0:3] keep their bits and skipped_steps counts; clean steps around them equal the restatement's.  With the guard off and no
+    clipping no norm kernel runs (no workspace) and the NaN propagates as under torch."""
+    A = FA()
+    vals = set_values(0)
+    i8193 = SET_COUNTS.index(8193)
+    pd, od, pc, oc = _pair(vals, dev, skip_nonfinite=True, max_norm=5.0)
+    g = torch.Generator().manual_seed(4)
+    _both_step(vals, draw_grads(vals, g), pd, od, pc, oc, what="clean 0")
+    keep_p = [p.detach().clone() for p in pd]
+    keep_m, keep_v, keep_s = od._exp_avg.clone(), od._exp_avg_sq.clone(), od._state.clone()
+    for k, (idx, val) in enumerate(((0, math.inf), (i8193, math.nan))):
+        grads = draw_grads(vals, g)
+        grads[idx].view(-1)[-1] = val
+        set_grads(pd, vals, grads)
+        od.step()
+        assert float(od.skipped_steps) == k + 1.0 and float(od._state[7]) == 1.0
+        assert not (float(od.grad_norm) < math.inf)
+        assert all(same_bits(a, b) for a, b in zip(keep_p, pd))
+        assert same_bits(keep_m, od._exp_avg) and same_bits(keep_v, od._exp_avg_sq)
+        assert od._state[:3].tolist() == keep_s[:3].tolist()
+    _both_step(vals, draw_grads(vals, g), pd, od, pc, oc, what="clean 1")
+    assert float(od._state[0]) == 2.0 and float(od._state[7]) == 0.0 and float(od.skipped_steps) == 2.0
+
+    # guard off, no clipping: no norm, and the NaN goes where torch's goes
+    p1, p2 = make_params(vals, dev), make_params(vals, dev)
+    o1, o2 = A.FusedAdam(p1), torch.optim.Adam(p2)
+    grads = draw_grads(vals, g)
+    grads[i8193].view(-1)[-1] = math.nan
+    set_grads(p1, vals, grads), set_grads(p2, vals, grads)
+    o1.step(), o2.step()
+    assert o1._ws is None and float(o1.skipped_steps) == 0.0 and float(o1._state[0]) == 1.0
+    for a, b in zip(p1, p2):
+        assert torch.equal(torch.isnan(a), torch.isnan(b))
+    assert int(torch.isnan(p1[i8193]).sum()) == 1 and bool(torch.isnan(p1[i8193][-1]))
+    # guard off, clipping on: the flag is only reported
+    o3 = A.FusedAdam(make_params(vals, dev), max_norm=1.0)
+    set_grads(o3.param_groups[0]["params"], vals, grads)
+    o3.step()
+    assert float(o3._state[7]) == 1.0 and float(o3.skipped_steps) == 0.0 and float(o3._state[0]) == 1.0
+
+
+@pytest.mark.gpu
+def test_table_edges(dev):
+    A = FA()
+    g = torch.Generator().manual_seed(5)
+    # 300 tensors of 1..7 elements: more than one launch's capacity, for the update and for the norm
+    vals = [(torch.randn(int(n), generator=g), None) for n in torch.randint(1, 8, (300,), generator=g)]
+    pd, od, pc, oc = _pair(vals, dev, max_norm=1.0, weight_decay=1e-2)
+    for it in range(2):
+        _both_step(vals, draw_grads(vals, g), pd, od, pc, oc, what=("300", it))
+    # a zero-element tensor, and three parameters whose .grad is None: those keep p, m, v; the rest match
+    vals = [(torch.randn(n, generator=g), None) for n in (0, 5, 7, 4096, 9, 130)]
+    pd, od, pc, oc = _pair(vals, dev, max_norm=1.0)
+    _both_step(vals, draw_grads(vals, g), pd, od, pc, oc, what="all grads")
+    none = (2, 3, 4)
+    keep = [(pd[i].detach().clone(), od.state[pd[i]]["exp_avg"].clone(), od.state[pd[i]]["exp_avg_sq"].clone()) for i in none]
+    grads = draw_grads(vals, g)
+    set_grads(pd, vals, grads), set_grads(pc, vals, grads)
+    for i in none:
+        pd[i].grad = pc[i].grad = None
+    od.step()
+    oc.step(clip_coef=float(od.clip_coef))
+    assert_same_state(od, pd, oc, pc, "three without grad")
+    for i, (p, m, v) in zip(none, keep):
+        assert same_bits(p, pd[i]) and same_bits(m, od.state[pd[i]]["exp_avg"]) and same_bits(v, od.state[pd[i]]["exp_avg_sq"])
+    assert float(od._state[0]) == 2.0
+    # n == 0: nothing is launched (the closing wave would have advanced t)
+    for p in pd:
+        p.grad = None
+    before = [p.detach().clone() for p in pd]
+    od.step()
+    assert float(od._state[0]) == 2.0 and all(same_bits(a, b) for a, b in zip(before, pd))
+    # Python refuses what the kernels do not take
+    with pytest.raises(ValueError, match="fp32 only"):
+        A.FusedAdam([torch.nn.Parameter(torch.zeros(8, dtype=torch.float16, device=dev))])
+    with pytest.raises(ValueError, match="not contiguous"):
+        A.FusedAdam([torch.nn.Parameter(torch.zeros(4, 6, device=dev).t())])
+    with pytest.raises(A._lib.SminHipError, match="no CPU fallback"):
+        A.FusedAdam([torch.nn.Parameter(torch.zeros(8))])
+    ops = A._lib.load_torch()
+    z = torch.zeros(8, device=dev)
+    state = torch.zeros(8, dtype=torch.float64, device=dev)
+    with pytest.raises(RuntimeError, match="not fp32"):
+        ops.adam_step([z.half()], [z.half()], z, z.clone(), [0], state, None, 0.9, 0.999, 1e-8, 0.0, False, -1.0, False)
+    with pytest.raises(RuntimeError, match="shape"):
+        ops.adam_step([z], [z[:4]], z, z.clone(), [0], state, None, 0.9, 0.999, 1e-8, 0.0, False, -1.0, False)
+    with pytest.raises(RuntimeError, match="outside the flat buffers"):
+        ops.adam_step([z], [z.clone()], z.clone(), z.clone(), [4], state, None, 0.9, 0.999, 1e-8, 0.0, False, -1.0, False)
+    with pytest.raises(RuntimeError, match="workspace"):
+        ops.adam_step([z], [z.clone()], z.clone(), z.clone(), [0], state, None, 0.9, 0.999, 1e-8, 0.0, False, 1.0, False)
+
+
+@pytest.mark.gpu
+def test_c_entries_refuse_bad_arguments(dev):
+    """smin_adam_step / smin_grad_norm through ctypes with valid small buffers: each refusal is a negative code and nothing is launched
+    (state and parameters keep their bits); the same call with good arguments returns 0 and steps."""
+    A = FA()
+    lib = A._lib.load()
+    n = 2
+    p = [torch.ones(16, device=dev), torch.ones(5, device=dev)]
+    gr = [torch.full((16,), 0.5, device=dev), torch.full((5,), 0.25, device=dev)]
+    m, v = torch.zeros(24, device=dev), torch.zeros(24, device=dev)
+    state = torch.tensor([0.0, 1.0, 1.0, 1e-3, 0.0, 1.0, 0.0, 0.0], dtype=torch.float64, device=dev)
+    ws_bytes = lib.smin_adam_ws_bytes(21, n)
+    assert ws_bytes >= 3 * 8 and lib.smin_adam_ws_bytes(-1, n) == 0 and lib.smin_adam_ws_bytes(21, -1) == 0
+    ws = torch.zeros(ws_bytes, dtype=torch.uint8, device=dev)
+    arr = lambda ty, xs: (ty * len(xs))(*xs)
+    ptrs = lambda ts: arr(ctypes.c_void_p, [t.data_ptr() for t in ts])
+    st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    P, G, N, O = ptrs(p), ptrs(gr), arr(ctypes.c_int64, [16, 5]), arr(ctypes.c_int64, [0, 16])
+
+    def step(P=P, G=G, N=N, O=O, n=n, b1=0.9, b2=0.999, eps=1e-8, wd=0.0, skip=0, nws=None):
+        return lib.smin_adam_step(st, P, G, N, O, n, m.data_ptr(), v.data_ptr(), state.data_ptr(), b1, b2, eps, wd, 0, skip, nws)
+
+    def norm(G=G, N=N, n=n, max_norm=1.0, wsb=ws_bytes):
+        return lib.smin_grad_norm(st, G, N, n, max_norm, state.data_ptr(), ws.data_ptr(), wsb)
+
+    null0 = arr(ctypes.c_void_p, [None, p[1].data_ptr()])
+    refused = [step(n=-1), step(N=arr(ctypes.c_int64, [16, -5])), step(P=null0), step(G=null0), step(b1=1.0), step(b1=-0.1), step(b2=1.0),
+               step(b2=-0.5), step(eps=-1e-8), step(O=arr(ctypes.c_int64, [0, -4])), step(skip=1, nws=None),
+               norm(n=-1), norm(N=arr(ctypes.c_int64, [-16, 5])), norm(G=null0), norm(wsb=8), norm(max_norm=math.nan)]
+    torch.cuda.synchronize()
+    assert all(rc < 0 for rc in refused), refused
+    assert state.tolist() == [0.0, 1.0, 1.0, 1e-3, 0.0, 1.0, 0.0, 0.0] and all(bool((x == 1).all()) for x in p) and not bool(m.any())
+    # legal and launching nothing: n == 0 and empty tensors
+    assert step(n=0) == 0 and norm(n=0) == 0 and step(N=arr(ctypes.c_int64, [0, 0]), P=arr(ctypes.c_void_p, [None, None])) == 0
+    torch.cuda.synchronize()
+    assert state.tolist()[:3] == [0.0, 1.0, 1.0]
+    # the good call: the restatement's step on the same values
+    assert norm() == 0 and step(nws=ws.data_ptr()) == 0
+    torch.cuda.synchronize()
+    pc = [torch.nn.Parameter(torch.ones(16)), torch.nn.Parameter(torch.ones(5))]
+    oc = A.FusedAdamTorch(pc, max_norm=1.0)
+    for q, x in zip(pc, gr):
+        q.grad = x.cpu()
+    oc.step(clip_coef=float(state[5]))
+    assert all(same_bits(a, b) for a, b in zip(p, pc))
+    assert same_bits(m[:16], oc.state[pc[0]]["exp_avg"]) and same_bits(v[16:21], oc.state[pc[1]]["exp_avg_sq"])
+    assert state.tolist()[:3] == oc._state.tolist()[:3] and float(state[4]) == math.sqrt(16 * 0.25 + 5 * 0.0625)
+
+
+# ---------------------------------------------------------------- the model's own step
+CHEAP = dict(T=64, L=16, C=4, D=128, dl=32, layers=2, Din=64, Nq=8, H=64)
+CHEAP_B = 5
+
+
+def _cheap(dev, seed=31):
+    from oracle import smin_oracle as O                            # seeded weights and inputs only
+    c = CHEAP
+    sd = O.formula_state_dict(H.smin_shapes(c["T"], c["L"], c["C"], c["D"], c["dl"], c["layers"], c["Din"], c["Nq"], c["H"]), gain=1.2)
+    batch = {k: v.to(dev) for k, v in O.synthetic_batch(CHEAP_B, c["T"], c["L"], c["Nq"], c["Din"], seed=seed).items()}   # ragged lengths
+    return sd, batch
+
+
+def _model(sd, dev):
+    import models
+    c = CHEAP
+    m = models.SMIN(c["T"], c["L"], c["C"], c["D"], c["dl"], c["layers"], c["Din"], c["Nq"], c["H"], dev)
+    m.load_state_dict(sd, strict=True)
+    return m.to(dev)
+
+
+def _train_step(m, opt, b):
+    opt.zero_grad(set_to_none=True)
+    out = m(*H.model_inputs(b))
+    loss = FA().loss_fn(out[0], b["ym"], b["sm"], b["moment_mask"], out[1], b["ys"], b["ss"], out[2], b["ye"], b["se"], out[3], b["ya"], b["length_mask"])
+    loss.backward()
+    opt.step()
+
+
+@pytest.mark.gpu
+def test_model_step_matches_restatement(dev):
+    """SMIN at the suite's cheap shape, one-node path, max_norm = 1, the guard on: after each of 3 steps every parameter (67 at two
+    layers) equals the restatement's, stepped on the CPU with the step's gradients and the device's coefficient."""
+    A = FA()
+    sd, b = _cheap(dev)
+    m = _model(sd, dev)
+    assert m._plan(b["video_features"], b["query_features"]) == "node"
+    pd = list(m.parameters())
+    od = A.FusedAdam(pd, lr=1e-3, max_norm=1.0, skip_nonfinite=True)
+    pc = [torch.nn.Parameter(p.detach().cpu().clone()) for p in pd]
+    oc = A.FusedAdamTorch(pc, lr=1e-3, max_norm=1.0, skip_nonfinite=True)
+    for it in range(3):
+        _train_step(m, od, b)
+        assert all(p.grad is not None for p in pd)
+        for q, p in zip(pc, pd):
+            q.grad = p.grad.cpu()
+        c = float(od.clip_coef)
+        assert 0.0 < c <= 1.0 and float(od._state[7]) == 0.0
+        oc.step(clip_coef=c)
+        assert_same_state(od, pd, oc, pc, it)
+        with torch.no_grad():
+            for q, p in zip(pc, pd):
+                p.copy_(q)                                         # both sides continue from equal bits
+    assert float(od._state[0]) == 3.0 and float(od.skipped_steps) == 0.0
+
+
+@pytest.mark.gpu
+def test_resume_on_the_device(dev):
+    """state_dict() after 2 steps, loaded into a fresh FusedAdam on a copy of the model, then one more step on the same batch: the
+    parameters equal the uninterrupted third step's bit for bit."""
+    A = FA()
+    sd, b = _cheap(dev)
+    m = _model(sd, dev)
+    kw = dict(lr=1e-3, weight_decay=1e-2, decoupled=True, max_norm=1.0, skip_nonfinite=True)
+    od = A.FusedAdam(m.parameters(), **kw)
+    for _ in range(2):
+        _train_step(m, od, b)
+    saved = copy.deepcopy(od.state_dict())
+    m2 = _model({k: v.detach().clone() for k, v in m.state_dict().items()}, dev)
+    o2 = A.FusedAdam(m2.parameters())
+    o2.load_state_dict(saved)
+    assert o2._state[:4].tolist() == od._state[:4].tolist() and o2.param_groups[0]["decoupled"] is True
+    _train_step(m, od, b)
+    _train_step(m2, o2, b)
+    assert_same_state(od, list(m.parameters()), o2, list(m2.parameters()), "resumed")
+
+
+@pytest.mark.gpu
+def test_captured_step_and_pushed_learning_rate(dev):
+    """CapturedStep(model, FusedAdam(...)) with no capturable flag anywhere: after each of four calls on one batch (the first is three
+    warm-up steps and one replay) the parameters equal the eager steps of a twin model bit for bit; then a new learning rate sent with
+    push_lr() reaches the next replay of the same graph."""
+    A = FA()
+    sd, b = _cheap(dev)
+    m_e, m_c = _model(sd, dev), _model(sd, dev)
+    o_e, o_c = A.FusedAdam(m_e.parameters(), lr=5e-4), A.FusedAdam(m_c.parameters(), lr=5e-4)
+    step = A.CapturedStep(m_c, o_c)
+    m_e.tail_split = m_c.tail_split                                # (placement only: no bit of the step depends on it)
+    for it in range(4):
+        step(b)
+        for _ in range(4 if it == 0 else 1):
+            _train_step(m_e, o_e, b)
+        torch.cuda.synchronize()
+        assert_same_state(o_e, list(m_e.parameters()), o_c, list(m_c.parameters()), it)
+    assert len(step.entries) == 1
+    for o in (o_e, o_c):
+        o.param_groups[0]["lr"] = 1e-4
+    o_c.push_lr()
+    step(b)
+    _train_step(m_e, o_e, b)
+    torch.cuda.synchronize()
+    assert len(step.entries) == 1 and float(o_c._state[3]) == 1e-4 and float(o_c._state[0]) == 8.0
+    assert_same_state(o_e, list(m_e.parameters()), o_c, list(m_c.parameters()), "lr 1e-4")

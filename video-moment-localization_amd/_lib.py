@@ -12,6 +12,7 @@ TORCH_LIB_PATH = os.path.join(_HERE, "libsmin_torch.so")        # TORCH_LIBRARY(
 CSRC = os.path.join(_HERE, "csrc")
 
 _vp, _i, _sz, _f = ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t, ctypes.c_float
+_i64, _d = ctypes.c_int64, ctypes.c_double
 ABI_VERSION = 2                                                 # include/smin_hip.h SMIN_HIP_ABI_VERSION
 
 # name -> argtypes (restype is int unless listed in _RESTYPE); mirrors include/smin_hip.h one to one
@@ -112,13 +113,16 @@ SIGNATURES = {
     "smin_bilstm_layer_bwd": [_vp] * 9 + [_i] * 4 + [_vp] * 4 + [_vp, _sz],
     "smin_step_prologue": [_vp] * 7 + [_i] * 5 + [_vp] * 8,
     "smin_bilstm_layer_bwd_weights": [_vp, _i, _vp, _vp] + [_i] * 4 + [_vp] * 4 + [_vp, _sz],
+    "smin_adam_ws_bytes": [_i64, _i],
+    "smin_grad_norm": [_vp, _vp, _vp, _i, _d, _vp, _vp, _sz],
+    "smin_adam_step": [_vp] * 5 + [_i] + [_vp] * 3 + [_d] * 4 + [_i, _i, _vp],
 }
 _RESTYPE = {"smin_target_arch": ctypes.c_char_p, "smin_workspace_bytes": _sz,
             "smin_content_attn_bwd_workspace_bytes": _sz, "smin_linear_rows_bwd_workspace_bytes": _sz,
             "smin_bilstm_layer_bwd_workspace_bytes": _sz, "smin_video_encoder_bwd_workspace_bytes": _sz, "smin_embed_tokens_bwd_workspace_bytes": _sz,
             "smin_word_prep_bwd_workspace_bytes": _sz, "smin_score_tail_ws_bytes": _sz,
             "smin_col_sum_workspace_bytes": _sz, "smin_top_moments_ws_bytes": _sz, "smin_boundary_unit_bwd_ws_bytes": _sz, "smin_compute_ious_nms_ws_bytes": _sz,
-            "smin_epoch_meter_ws_bytes": _sz, "smin_span_meter_ws_bytes": _sz}
+            "smin_epoch_meter_ws_bytes": _sz, "smin_span_meter_ws_bytes": _sz, "smin_adam_ws_bytes": _sz}
 
 _lib = None
 _ws = {}
@@ -164,8 +168,9 @@ _torch_ops = None
 
 
 def load_torch():
-    """The torch-extension binding (csrc/torch_binding.cpp): registers torch.ops.smin_hip.{smin_forward, smin_score, smin_loss} -- the
-    whole forward as one library call with its autograd graph built in C++, and its forward-only scoring twin.  Raises if the library is missing."""
+    """The torch-extension binding (csrc/torch_binding.cpp): registers torch.ops.smin_hip.{smin_forward, smin_score, smin_loss, adam_step} --
+    the whole forward as one library call with its autograd graph built in C++, its forward-only scoring twin, and the optimizer step over
+    a parameter list.  Raises if the library is missing."""
     global _torch_ops
     if _torch_ops is not None:
         return _torch_ops

@@ -1323,6 +1323,57 @@ Tensor smin_loss(const Tensor& pm, const Tensor& ym, const Tensor& sm, const Ten
     return LossNode::apply(pm, ps, pe, pa, ym, sm, moment_mask, ys, ss, ye, se, ya, length_mask);
 }
 
+// FusedAdam.step (optim.py): the pointers of the parameters and their gradients are gathered here -- with
+// zero_grad(set_to_none=True) the gradients move every step -- and handed to smin_grad_norm (when clipping or the guard is on) and
+// smin_adam_step on the current stream.  No host read: capturable as it stands, the pointers baked into the graph as for torch's own
+// fused Adam.  max_norm < 0: no clipping.  ws: the norm's partials (uint8, smin_adam_ws_bytes), required when the norm runs.
+void adam_step(at::TensorList params, at::TensorList grads, const Tensor& exp_avg_flat, const Tensor& exp_avg_sq_flat, at::IntArrayRef offsets,
+               const Tensor& state, const std::optional<Tensor>& ws, double beta1, double beta2, double eps, double weight_decay, bool decoupled,
+               double max_norm, bool skip_nonfinite)
+{
+    const size_t n = params.size();
+    TORCH_CHECK(grads.size() == n && offsets.size() == n, "adam_step: ", n, " parameters, ", grads.size(), " gradients, ", offsets.size(), " offsets");
+    TORCH_CHECK(exp_avg_flat.is_cuda(), "adam_step runs on a HIP device only (there is no CPU fallback)");
+    const auto dev = exp_avg_flat.device();
+    auto flat_ok = [&](const Tensor& t, at::ScalarType ty) { return t.device() == dev && t.scalar_type() == ty && t.is_contiguous(); };
+    TORCH_CHECK(flat_ok(exp_avg_flat, at::kFloat) && flat_ok(exp_avg_sq_flat, at::kFloat) && exp_avg_flat.numel() == exp_avg_sq_flat.numel(),
+                "adam_step: the moment buffers must be contiguous fp32 tensors of one size on one HIP device");
+    TORCH_CHECK(flat_ok(state, at::kDouble) && state.numel() == 8, "adam_step: state must be 8 contiguous doubles on the parameters' device");
+    std::vector<float*> pp(n);
+    std::vector<const float*> gp(n);
+    std::vector<int64_t> ne(n), mo(n);
+    int64_t total = 0;
+    for (size_t i = 0; i < n; ++i) {
+        const Tensor &p = params[i], &g = grads[i];
+        TORCH_CHECK(p.is_cuda() && g.is_cuda(), "adam_step runs on a HIP device only (there is no CPU fallback): parameter ", i);
+        TORCH_CHECK(p.device() == dev && g.device() == dev, "adam_step: parameter ", i, " or its gradient is on another device");
+        TORCH_CHECK(p.scalar_type() == at::kFloat && g.scalar_type() == at::kFloat, "adam_step: parameter ", i, " or its gradient is not fp32");
+        TORCH_CHECK(p.is_contiguous() && g.is_contiguous(), "adam_step: parameter ", i, " or its gradient is not contiguous");
+        TORCH_CHECK(p.sizes() == g.sizes(), "adam_step: gradient ", i, " has not its parameter's shape");
+        ne[i] = p.numel();
+        mo[i] = offsets[i];
+        TORCH_CHECK(mo[i] >= 0 && mo[i] + ne[i] <= exp_avg_flat.numel(), "adam_step: moment segment ", i, " lies outside the flat buffers");
+        pp[i] = p.numel() ? p.data_ptr<float>() : nullptr;
+        gp[i] = g.numel() ? g.const_data_ptr<float>() : nullptr;
+        total += ne[i];
+        torch::autograd::impl::bump_version(p);                   // written in place below, as far as autograd's saved tensors are concerned
+    }
+    const bool norm = max_norm >= 0.0 || skip_nonfinite;
+    c10::hip::HIPGuard device_guard(dev.index());
+    void* wsp = nullptr;
+    if (norm) {
+        const size_t need = smin_adam_ws_bytes(total, i32((int64_t)n));
+        TORCH_CHECK(ws && ws->defined() && ws->device() == dev && ws->scalar_type() == at::kByte && ws->is_contiguous() && (size_t)ws->numel() >= need,
+                    "adam_step: the norm needs a uint8 workspace of ", need, " bytes on the parameters' device");
+        wsp = ws->data_ptr();
+        SMIN_CK(smin_grad_norm(cur(), gp.data(), ne.data(), i32((int64_t)n), max_norm >= 0.0 ? max_norm : -1.0, state.data_ptr<double>(), wsp,
+                               (size_t)ws->numel()));
+    }
+    SMIN_CK(smin_adam_step(cur(), pp.data(), gp.data(), ne.data(), mo.data(), i32((int64_t)n), exp_avg_flat.data_ptr<float>(),
+                           exp_avg_sq_flat.data_ptr<float>(), state.data_ptr<double>(), beta1, beta2, eps, weight_decay, decoupled ? 1 : 0,
+                           skip_nonfinite ? 1 : 0, wsp));
+}
+
 }  // namespace
 
 TORCH_LIBRARY(smin_hip, m)
@@ -1339,6 +1390,9 @@ TORCH_LIBRARY(smin_hip, m)
     // restated loss_fn of the reference's train loop (main.py:110-116), same argument order
     m.def("smin_loss(Tensor pm, Tensor ym, Tensor sm, Tensor moment_mask, Tensor ps, Tensor ys, Tensor ss, Tensor pe, Tensor ye, Tensor se, Tensor pa, Tensor ya, "
           "Tensor length_mask) -> Tensor", &smin_loss);
+    // FusedAdam.step: Adam / AdamW over a parameter list, gradient norm, clipping and the non-finite guard on the device (see adam_step above)
+    m.def("adam_step(Tensor[] params, Tensor[] grads, Tensor exp_avg_flat, Tensor exp_avg_sq_flat, int[] offsets, Tensor state, Tensor? ws, float beta1, "
+          "float beta2, float eps, float weight_decay, bool decoupled, float max_norm, bool skip_nonfinite) -> ()", &adam_step);
     m.def("abi_version() -> int", []() -> int64_t { return smin_abi_version(); });
     // the status word of smin_build_cells_n on a device (non-zero after a step whose known_cell_count did not match its mask)
     m.def("layout_status(Device device) -> Tensor", [](c10::Device dev) { return layout_status(dev); });

@@ -103,7 +103,8 @@ class CapturedStep:
     count) and kept (``max_graphs``, least recently used evicted).  Batches of full-length videos -- the common case: the
     reference's dataset resamples every video longer than T to exactly T frames (dataset.py:40-74) -- share one count; a batch
     with a count not seen before is captured on first sight (three eager steps + the capture).  Limits: the optimizer must be
-    capturable (``torch.optim.Adam(..., capturable=True)``); not combined with data parallel (collectives inside a captured
+    capturable (``torch.optim.Adam(..., capturable=True)``, or ``FusedAdam``, which is capturable as it stands and takes a new learning
+    rate between replays through ``push_lr()``); not combined with data parallel (collectives inside a captured
     step are not handled here).  Opt-in: results are bit-identical to the eager step (tests/test_hip_parity.py).
 
         step = CapturedStep(model, optimizer)
