@@ -45,7 +45,8 @@ extern "C" {
  * smin_score_tail_ws_bytes (the last layer's moment unit and the map's score head as row dots); an epoch's metric and loss totals
  * kept on the device -- smin_epoch_meter_update and smin_epoch_meter_ws_bytes; the metric of merged spans against ground-truth
  * spans -- smin_span_ious, smin_span_meter_update and smin_span_meter_ws_bytes; the optimizer update -- smin_adam_step, smin_grad_norm
- * and smin_adam_ws_bytes */
+ * and smin_adam_ws_bytes; row-sparse training of the word table -- smin_embed_tokens_bwd_rows, smin_embed_tokens_bwd_rows_workspace_bytes
+ * (the table gradient as its distinct rows) and smin_row_adam_step (a lazy Adam step over those rows) */
 #define SMIN_HIP_ABI_VERSION 2
 
 int smin_abi_version(void);
@@ -300,6 +301,16 @@ int smin_embed_tokens(void* stream, const int32_t* tokens, const float* table, i
 size_t smin_embed_tokens_bwd_workspace_bytes(int B, int Nq);
 int smin_embed_tokens_bwd(void* stream, const int32_t* tokens, const float* dqf, int B, int Nq, int V, int E, float* dtable,
                           void* ws, size_t ws_bytes);
+/* the same gradient as its distinct rows (csrc/row_sparse.hip), for a table too large to sweep: with n = B * Nq <= 4096,
+ * ids [n] int32, rows [n][E], count [1] int32, sqnorm [1] double.  Slots s < count hold the distinct ids in [0, V) in strictly ascending
+ * order; rows[s] = sum of dqf[b, w] over the positions holding ids[s], added in ascending (b, w) order -- the additions of the dense
+ * entry above, so rows[s] has the bits of dtable[ids[s]].  Slots s >= count get ids[s] = -1 and their rows are not written.  sqnorm = the
+ * sum of squares of the count rows, accumulated in double in a fixed order.  B = 0 or no id in range gives count = 0, sqnorm = 0.
+ * Deterministic (no atomics); three launches sized by n that exit early on the device-side count: no host read, no pass over V * E.
+ * Requires 16-byte aligned dqf / rows, E % 4 == 0; ws of the query below (8-byte aligned). */
+size_t smin_embed_tokens_bwd_rows_workspace_bytes(int B, int Nq);
+int smin_embed_tokens_bwd_rows(void* stream, const int32_t* tokens, const float* dqf, int B, int Nq, int V, int E, int32_t* ids, float* rows,
+                               int32_t* count, double* sqnorm, void* ws, size_t ws_bytes);
 
 /* ---- compute_ious (reference utils.py:10-31): counts [8] = number of samples with a hit for
  * R@1 x IoU {0.1, 0.3, 0.5, 0.7} then R@5 x the same; ws [B][8] scratch.  Any L with L*L >= 5 (the reference's topk(5) needs as many). */
@@ -619,6 +630,21 @@ int smin_grad_norm(void* stream, const float* const* grad, const int64_t* numel,
 int smin_adam_step(void* stream, float* const* param, const float* const* grad, const int64_t* numel, const int64_t* moment_offset, int n,
                    float* exp_avg, float* exp_avg_sq, double* state, double beta1, double beta2, double eps, double weight_decay,
                    int decoupled, int skip_nonfinite, const void* norm_ws);
+
+/* ---- lazy Adam over the rows of a table listed by the rows entry of the token lookup's backward (csrc/row_sparse.hip).
+ * table / exp_avg / exp_avg_sq [V][E] (16-byte aligned, E % 4 == 0); ids [n], rows [n][E], count [1], sqnorm [1] as that entry writes
+ * them (n <= 4096 is the capacity of ids / rows; sqnorm may be NULL: norm unknown).  state: the 8 doubles of the step entry above, same
+ * layout and rules; [4] = sqrt(sqnorm) (NaN without sqnorm), [5] = the scale used.  scale: NULL, or one double on the device (e.g.
+ * state[5] of the model's optimizer), cast once to fp32.  One workgroup per slot s < count applies to row ids[s], every fp32 operation
+ * rounded on its own and the scalars formed as above:
+ *   g = rows[s] * (float)scale         (only when scale is given)
+ *   m = beta1 * m + (1 - beta1) * g    v = beta2 * v + ((1 - beta2) * g) * g        p = p - step_size * (m / (sqrtf(v) / sbc2 + eps))
+ * Rows not listed (and a slot whose id lies outside [0, V)) are neither read nor written; there is no weight decay.  One closing wave
+ * advances t and the powers once per call, also when count == 0.  With skip_nonfinite != 0, an inf or NaN sqnorm or scale writes
+ * nothing, leaves t alone and adds 1 to state[6]; state[7] is that flag either way.  Two launches (one when n == 0); no host read. */
+int smin_row_adam_step(void* stream, float* table, float* exp_avg, float* exp_avg_sq, const int32_t* ids, const float* rows,
+                       const int32_t* count, const double* sqnorm, int n, int V, int E, double* state, const double* scale, double beta1,
+                       double beta2, double eps, int skip_nonfinite);
 
 /* ---- stand-alone fp32 MFMA GEMM  C[M][N] = A[M][K] * B[N][K]^T  (used by tests and bench.py's
  * roofline probe; same engine as every contraction above). */

@@ -73,6 +73,8 @@ SIGNATURES = {
     "smin_sample_windows": [_vp] * 4 + [_i] * 4 + [_vp] * 2,
     "smin_embed_tokens_bwd_workspace_bytes": [_i, _i],
     "smin_embed_tokens_bwd": [_vp] * 3 + [_i] * 4 + [_vp, _vp, _sz],
+    "smin_embed_tokens_bwd_rows_workspace_bytes": [_i, _i],
+    "smin_embed_tokens_bwd_rows": [_vp] * 3 + [_i] * 4 + [_vp] * 4 + [_vp, _sz],
     "smin_word_prep_fwd": [_vp] * 5 + [_i] * 5 + [_vp] * 5,
     "smin_word_prep_bwd_workspace_bytes": [_i] * 5,
     "smin_word_prep_bwd": [_vp] * 11 + [_i] * 5 + [_vp] * 3 + [_vp, _sz],
@@ -116,10 +118,12 @@ SIGNATURES = {
     "smin_adam_ws_bytes": [_i64, _i],
     "smin_grad_norm": [_vp, _vp, _vp, _i, _d, _vp, _vp, _sz],
     "smin_adam_step": [_vp] * 5 + [_i] + [_vp] * 3 + [_d] * 4 + [_i, _i, _vp],
+    "smin_row_adam_step": [_vp] * 8 + [_i] * 3 + [_vp] * 2 + [_d] * 3 + [_i],
 }
 _RESTYPE = {"smin_target_arch": ctypes.c_char_p, "smin_workspace_bytes": _sz,
             "smin_content_attn_bwd_workspace_bytes": _sz, "smin_linear_rows_bwd_workspace_bytes": _sz,
             "smin_bilstm_layer_bwd_workspace_bytes": _sz, "smin_video_encoder_bwd_workspace_bytes": _sz, "smin_embed_tokens_bwd_workspace_bytes": _sz,
+            "smin_embed_tokens_bwd_rows_workspace_bytes": _sz,
             "smin_word_prep_bwd_workspace_bytes": _sz, "smin_score_tail_ws_bytes": _sz,
             "smin_col_sum_workspace_bytes": _sz, "smin_top_moments_ws_bytes": _sz, "smin_boundary_unit_bwd_ws_bytes": _sz, "smin_compute_ious_nms_ws_bytes": _sz,
             "smin_epoch_meter_ws_bytes": _sz, "smin_span_meter_ws_bytes": _sz, "smin_adam_ws_bytes": _sz}

@@ -17,6 +17,7 @@
 // (pick) or its window's output row over the window's row count (mean); smin_embed_tokens_bwd sorts the (id, position) pairs of the
 // batch in one workgroup, then one workgroup per distinct id adds its positions' rows in ascending position order.
 #include "common.h"
+#include "embed_sort.h"
 #include "smin_hip.h"
 
 namespace smin {
@@ -222,37 +223,13 @@ void sample_clips_bwd_kernel(const float* __restrict__ dout, const long long* __
 }
 
 // ---- backward of smin_embed_tokens
-constexpr int EMBED_BWD_MAX = 4096;      // positions B * Nq sorted in LDS (32 KB of keys)
-
-// keys[i] = (id << 32 | position) sorted ascending (bitonic sort in LDS, one workgroup); positions with an id outside [0, V) are
-// given the largest key and never read.  Equal ids end up adjacent, in ascending position order.
+// keys[i] = (id << 32 | position) sorted ascending (embed_sort.h, one workgroup); positions with an id outside [0, V) are given the
+// largest key and never read.  Equal ids end up adjacent, in ascending position order.
 __global__ __launch_bounds__(1024)
 void embed_tokens_sort_kernel(const int* __restrict__ tokens, int n, int V, unsigned long long* __restrict__ keys)
 {
     __shared__ unsigned long long s[EMBED_BWD_MAX];
-    int np = 1;
-    while (np < n) np <<= 1;
-    for (int i = threadIdx.x; i < np; i += blockDim.x) {
-        unsigned long long k = ~0ull;
-        if (i < n) {
-            const int id = tokens[i];
-            if (id >= 0 && id < V) k = ((unsigned long long)(unsigned)id << 32) | (unsigned)i;
-        }
-        s[i] = k;
-    }
-    __syncthreads();
-    for (int size = 2; size <= np; size <<= 1)
-        for (int stride = size >> 1; stride > 0; stride >>= 1) {
-            for (int i = threadIdx.x; i < np; i += blockDim.x) {
-                const int partner = i ^ stride;
-                if (partner > i) {
-                    const bool up = (i & size) == 0;
-                    const unsigned long long a = s[i], c = s[partner];
-                    if ((a > c) == up) { s[i] = c; s[partner] = a; }
-                }
-            }
-            __syncthreads();
-        }
+    embed_sort_keys(tokens, n, V, s);
     for (int i = threadIdx.x; i < n; i += blockDim.x) keys[i] = s[i];
 }
 

@@ -53,6 +53,8 @@ def clip_coefficient(norm, max_norm):
 
 
 class _FusedAdamBase(torch.optim.Optimizer):
+    _label = "FusedAdam"                  # what the messages call the optimizer
+
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, decoupled=False, max_norm=None, skip_nonfinite=False,
                  **torch_keys):
         unknown = set(torch_keys) - set(_TORCH_KEYS)
@@ -84,7 +86,7 @@ class _FusedAdamBase(torch.optim.Optimizer):
     def add_param_group(self, param_group):
         """Refused once constructed: the moment buffers are laid out for the one group the constructor got."""
         if getattr(self, "_constructed", False):
-            raise ValueError("FusedAdam: one parameter group only; its parameters are fixed at construction")
+            raise ValueError(f"{self._label}: one parameter group only; its parameters are fixed at construction")
         super().add_param_group(param_group)
 
     def _the_group(self):
@@ -92,32 +94,32 @@ class _FusedAdamBase(torch.optim.Optimizer):
         return self.param_groups[0]
 
     # ---- what is refused
-    @staticmethod
-    def _check_group_values(g):
+    @classmethod
+    def _check_group_values(cls, g):
         if g.get("amsgrad", False) or g.get("maximize", False):
-            raise ValueError("FusedAdam: amsgrad and maximize are not supported")
+            raise ValueError(f"{cls._label}: amsgrad and maximize are not supported")
         b1, b2 = g["betas"]
         if not (0.0 <= b1 < 1.0 and 0.0 <= b2 < 1.0):
-            raise ValueError(f"FusedAdam: betas must lie in [0, 1) (got {g['betas']})")
+            raise ValueError(f"{cls._label}: betas must lie in [0, 1) (got {g['betas']})")
         if not g["lr"] >= 0.0 or not g["eps"] >= 0.0 or not g["weight_decay"] >= 0.0:
-            raise ValueError("FusedAdam: lr, eps and weight_decay must be >= 0")
+            raise ValueError(f"{cls._label}: lr, eps and weight_decay must be >= 0")
         if g.get("max_norm") is not None and not g["max_norm"] >= 0.0:
-            raise ValueError("FusedAdam: max_norm must be None or >= 0")
+            raise ValueError(f"{cls._label}: max_norm must be None or >= 0")
 
     @classmethod
     def _check_groups(cls, groups):
         if len(groups) != 1:
-            raise ValueError(f"FusedAdam: one parameter group only (got {len(groups)})")
+            raise ValueError(f"{cls._label}: one parameter group only (got {len(groups)})")
         cls._check_group_values(groups[0])
 
     def _check_params(self, ps):
         for i, p in enumerate(ps):
             if p.dtype != torch.float32:
-                raise ValueError(f"FusedAdam: parameter {i} is {p.dtype}; fp32 only")
+                raise ValueError(f"{self._label}: parameter {i} is {p.dtype}; fp32 only")
             if not p.is_contiguous():
-                raise ValueError(f"FusedAdam: parameter {i} is not contiguous")
+                raise ValueError(f"{self._label}: parameter {i} is not contiguous")
             if p.device != ps[0].device:
-                raise ValueError(f"FusedAdam: parameter {i} is on {p.device}, parameter 0 on {ps[0].device}; one device only")
+                raise ValueError(f"{self._label}: parameter {i} is on {p.device}, parameter 0 on {ps[0].device}; one device only")
 
     # ---- device views for logging without a host read
     @property
@@ -143,7 +145,7 @@ class _FusedAdamBase(torch.optim.Optimizer):
         lr = float(self.param_groups[0]["lr"])
         if lr != self._lr_sent:
             if self._state.is_cuda and torch.cuda.is_current_stream_capturing():
-                raise RuntimeError("FusedAdam: the learning rate changed inside a graph capture; call push_lr() before capturing")
+                raise RuntimeError(f"{self._label}: the learning rate changed inside a graph capture; call push_lr() before capturing")
             self._state[3:4].fill_(lr)
             self._lr_sent = lr
 
@@ -177,7 +179,7 @@ class _FusedAdamBase(torch.optim.Optimizer):
         ids = list(g.pop("params"))
         ps = self.param_groups[0]["params"]
         if len(ids) != len(ps):
-            raise ValueError(f"FusedAdam: the loaded group has {len(ids)} parameters, this optimizer {len(ps)}")
+            raise ValueError(f"{self._label}: the loaded group has {len(ids)} parameters, this optimizer {len(ps)}")
         if "decoupled" not in g:
             g["decoupled"] = bool(g.get("decoupled_weight_decay", self.param_groups[0]["decoupled"]))
         g.pop("decoupled_weight_decay", None)
@@ -189,15 +191,15 @@ class _FusedAdamBase(torch.optim.Optimizer):
         saved = state_dict["state"]
         steps = {float(st["step"]) for st in saved.values()}
         if len(steps) > 1:
-            raise ValueError(f"FusedAdam: per-tensor step counts differ ({sorted(steps)}); the step count here is global")
+            raise ValueError(f"{self._label}: per-tensor step counts differ ({sorted(steps)}); the step count here is global")
         t = steps.pop() if steps else 0.0
         if t != int(t) or t < 0:
-            raise ValueError(f"FusedAdam: step count {t}")
+            raise ValueError(f"{self._label}: step count {t}")
         for i, p in zip(ids, ps):
             st = saved.get(i)
             for key in ("exp_avg", "exp_avg_sq"):
                 if st is not None and tuple(st[key].shape) != tuple(p.shape):
-                    raise ValueError(f"FusedAdam: {key} of parameter {i} has shape {tuple(st[key].shape)}, the parameter {tuple(p.shape)}")
+                    raise ValueError(f"{self._label}: {key} of parameter {i} has shape {tuple(st[key].shape)}, the parameter {tuple(p.shape)}")
         self.param_groups[0].update(merged)
         with torch.no_grad():
             for i, p in zip(ids, ps):
@@ -319,3 +321,151 @@ class FusedAdam(_FusedAdamBase):
         _lib.load_torch().adam_step(params, grads, self._exp_avg, self._exp_avg_sq, offsets, self._state, ws, float(beta1), float(beta2),
                                     float(g["eps"]), float(g["weight_decay"]), bool(g["decoupled"]),
                                     float(g["max_norm"]) if g["max_norm"] is not None else -1.0, bool(g["skip_nonfinite"]))
+
+
+# ---------------------------------------------------------------- lazy Adam over the rows of a word table
+class _RowSparseAdamBase(_FusedAdamBase):
+    """Adam over one ``(V, E)`` table whose gradient arrives as a ``sampling.RowSparseGrad``: only the rows a batch touched are read or
+    written (lazy Adam, the rule of ``torch.optim.SparseAdam``: an untouched row keeps p, m and v), with ``FusedAdam``'s state, arithmetic
+    and checkpoint format (``torch.optim.Adam``'s: ``step``, dense ``exp_avg`` / ``exp_avg_sq``).  t and the powers of the betas are global
+    and advance once per consumed gradient.  No weight decay (it would move every row), amsgrad or maximize."""
+
+    def __init__(self, table, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, skip_nonfinite=False, **torch_keys):
+        if not isinstance(table, torch.Tensor):
+            raise TypeError(f"{type(self).__name__}: exactly one table, a tensor (got {type(table).__name__})")
+        wd = torch_keys.pop("weight_decay", 0.0)
+        if wd != 0.0:
+            raise ValueError(f"{type(self).__name__}: weight_decay is not supported (it would touch every row of the table)")
+        super().__init__([table], lr, betas, eps, 0.0, False, None, skip_nonfinite, **torch_keys)
+
+    _label = "RowSparseAdam"
+
+    @classmethod
+    def _check_group_values(cls, g):
+        if g.get("weight_decay", 0.0) != 0.0 or g.get("max_norm") is not None:
+            raise ValueError("RowSparseAdam: weight_decay and max_norm are not supported (pass the model's coefficient as step(scale=...))")
+        super()._check_group_values(g)
+
+    def _check_params(self, ps):
+        super()._check_params(ps)
+        if ps[0].dim() != 2 or ps[0].shape[0] < 1 or ps[0].shape[1] < 4 or ps[0].shape[1] % 4:
+            raise ValueError(f"RowSparseAdam: the table must be (V >= 1, E) with E % 4 == 0 (got {tuple(ps[0].shape)})")
+
+    @property
+    def table(self):
+        return self.param_groups[0]["params"][0]
+
+    def _pending(self):
+        rg = getattr(self.table, "row_grad", None)
+        return rg if rg is not None and rg.pending else None
+
+    def zero_grad(self, set_to_none=True):
+        rg = getattr(self.table, "row_grad", None)
+        if rg is not None:
+            rg.clear()
+            if set_to_none:
+                self.table.row_grad = None
+        super().zero_grad(set_to_none)
+
+
+def _scale_f32(scale):
+    """the scale as the update uses it: cast once to fp32 (a Python float; reads a device value)"""
+    x = scale.detach().reshape(-1)[0].item() if isinstance(scale, torch.Tensor) else float(scale)
+    return _f32(x)
+
+
+class RowSparseAdamTorch(_RowSparseAdamBase):
+    """The arithmetic of ``RowSparseAdam`` as plain torch ops on any device, written as ``FusedAdamTorch`` is: each fp32 operation one by
+    one, the scalars in Python floats.  ``step(grad)`` takes a ``RowSparseGrad`` or a pair ``(ids, rows)`` of distinct row indices (an id
+    outside ``[0, V)`` is ignored, as the -1 of an unused slot) and their gradient rows.  Nothing routes to it."""
+
+    @torch.no_grad()
+    def step(self, grad=None, scale=None, closure=None):
+        if closure is not None:
+            raise ValueError("RowSparseAdam takes no closure")
+        g = self._the_group()
+        self.push_lr()
+        if grad is None:
+            grad = self._pending()
+            if grad is None:
+                return
+        p, V = self.table, self.table.shape[0]
+        if isinstance(grad, (tuple, list)):
+            ids, rows = grad
+            ids = torch.as_tensor(ids, device=p.device).to(torch.int64)
+            rows = torch.as_tensor(rows, device=p.device).to(torch.float32).reshape(ids.shape[0], -1)
+            keep = (ids >= 0) & (ids < V)
+            ids, rows = ids[keep], rows[keep]
+            total = float((rows.double() * rows.double()).sum())
+        else:
+            ids = grad.ids.to(device=p.device, dtype=torch.int64)
+            keep = (ids >= 0) & (ids < V)
+            ids, rows = ids[keep], grad.rows.to(p.device)[keep]
+            total = float(grad.sq_norm.reshape(-1)[0])
+            grad.clear()
+        lr, (beta1, beta2), eps = float(g["lr"]), g["betas"], float(g["eps"])
+        t, b1p, b2p = self._state[:3].tolist()
+        c = None if scale is None else _scale_f32(scale)
+        flag = not (total < math.inf) or (c is not None and not (abs(c) < math.inf))
+        self._state[4], self._state[5], self._state[7] = (math.sqrt(total) if total >= 0.0 else math.nan), 1.0 if c is None else c, float(flag)
+        if g["skip_nonfinite"] and flag:
+            self._state[6] += 1.0
+            return
+        B1, B2 = b1p * beta1, b2p * beta2
+        step_size, sbc2 = _f32(lr / (1.0 - B1)), _f32(math.sqrt(1.0 - B2))
+        b1f, omb1f, b2f, omb2f, epsf = _f32(beta1), _f32(1.0 - beta1), _f32(beta2), _f32(1.0 - beta2), _f32(eps)
+        st = self.state[p]
+        m, v = st["exp_avg"], st["exp_avg_sq"]
+        gr = rows * c if c is not None else rows
+        m_r = m[ids] * b1f + gr * omb1f
+        v_r = v[ids] * b2f + (gr * omb2f) * gr
+        p_r = p[ids] - (m_r / (v_r.double().sqrt().to(torch.float32) / sbc2 + epsf)) * step_size
+        m[ids], v[ids], p[ids] = m_r, v_r, p_r
+        self._state[0], self._state[1], self._state[2] = t + 1.0, B1, B2
+
+
+class RowSparseAdam(_RowSparseAdamBase):
+    """``RowSparseAdam(table, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, skip_nonfinite=False)``: lazy Adam over one fp32, contiguous HIP
+    ``(V, E)`` table trained through ``embed_tokens(..., differentiable=True, sparse_grad=True)``.  ``step(scale=None)`` consumes
+    ``table.row_grad`` in two launches sized by the batch (``smin_row_adam_step``): the rows listed there get ``FusedAdam``'s update, every
+    other row of the table and of the moments is neither read nor written; without a pending gradient it does nothing and t stays.
+    ``scale``: a device fp64 value (or a float) the gradient rows are multiplied by, e.g. ``FusedAdam.clip_coef`` of the model's optimizer
+    after its step.  With ``skip_nonfinite`` a gradient whose ``sq_norm``, or a ``scale`` that, is inf or NaN changes nothing and is
+    counted in ``skipped_steps``.  ``grad_norm`` is the row gradient's own norm.  No host read; ``push_lr``, ``zero_grad``,
+    ``state_dict`` / ``load_state_dict`` and ``torch.optim.lr_scheduler.*`` as for ``FusedAdam``."""
+
+    def _check_params(self, ps):
+        from ._lib import SminHipError
+        if not ps[0].is_cuda:
+            raise SminHipError("RowSparseAdam runs on a HIP device only (the table is a CPU tensor); there is no CPU fallback -- the "
+                               "plain-torch restatement is available under the explicit name RowSparseAdamTorch")
+        super()._check_params(ps)
+        if ps[0].data_ptr() % 16:
+            raise ValueError("RowSparseAdam: the table must be 16-byte aligned")
+
+    @torch.no_grad()
+    def step(self, scale=None, closure=None):
+        if closure is not None:
+            raise ValueError("RowSparseAdam takes no closure")
+        from ._lib import call, ptr, stream
+        g = self._the_group()
+        self.push_lr()
+        rg = self._pending()
+        if rg is None:
+            return
+        p = self.table
+        V, E = p.shape
+        if rg.shape != (V, E) or rg.rows.device != p.device:
+            raise ValueError(f"RowSparseAdam: row_grad is of a {rg.shape} table on {rg.rows.device}, the table {(V, E)} on {p.device}")
+        if scale is not None:
+            if not isinstance(scale, torch.Tensor):
+                scale = torch.full((1,), float(scale), dtype=torch.float64).to(p.device, non_blocking=True)
+            if scale.dtype != torch.float64 or scale.numel() != 1 or scale.device != p.device:
+                raise ValueError("RowSparseAdam: scale must be one fp64 value on the table's device (or a float)")
+            scale = scale.detach().contiguous()
+        beta1, beta2 = g["betas"]
+        with torch.cuda.device(p.device):
+            call("smin_row_adam_step", stream(), ptr(p.detach()), ptr(self._exp_avg), ptr(self._exp_avg_sq), ptr(rg.ids), ptr(rg.rows),
+                 ptr(rg.count), ptr(rg.sq_norm), rg.ids.shape[0], V, E, ptr(self._state), ptr(scale), float(beta1), float(beta2),
+                 float(g["eps"]), int(bool(g["skip_nonfinite"])))
+        rg.clear()

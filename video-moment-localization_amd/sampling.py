@@ -21,7 +21,11 @@ them silently.
 
 With ``differentiable=True`` and grad mode on, a ``raw`` / ``table`` that requires grad receives its gradient through an autograd
 node backed by deterministic HIP backward kernels (``smin_sample_clips_bwd`` / ``smin_embed_tokens_bwd``: fixed summation order, no
-atomics); ``nfeats``, ``query_mask`` and ``qlen`` are never differentiable.  By default both functions detach their inputs."""
+atomics); ``nfeats``, ``query_mask`` and ``qlen`` are never differentiable.  By default both functions detach their inputs.
+
+``embed_tokens(..., differentiable=True, sparse_grad=True)`` leaves the table's gradient as its distinct rows instead (a
+``RowSparseGrad`` on ``table.row_grad``, from ``smin_embed_tokens_bwd_rows``: no ``(V, E)`` tensor is formed), for
+``optim.RowSparseAdam`` to consume."""
 from torch.autograd import Function
 import numpy as np
 import torch
@@ -252,10 +256,79 @@ class _EmbedTokensFn(Function):
         return None, dtable, None
 
 
+class RowSparseGrad:
+    """The gradient of a ``(V, E)`` table as the rows a batch touched, all on the device (``smin_embed_tokens_bwd_rows``):
+
+    ``ids (n,) int32``: slots ``s < count`` hold the distinct ids in ``[0, V)``, strictly ascending; later slots hold -1.
+    ``rows (n, E) float32``: ``rows[s]`` = row ``ids[s]`` of the dense gradient, bit for bit; rows of later slots are unspecified.
+    ``count (1,) int32``; ``sq_norm (1,) float64`` = the sum of squares of the ``count`` rows (a fixed summation order).
+    ``n = B * Nq`` of the batch; ``shape = (V, E)``.  ``pending`` (host side) is set by the backward that made it and cleared by
+    ``clear()``, which the optimizer's ``step()`` / ``zero_grad()`` call: a backward into a table whose gradient is still pending is
+    refused, since row lists of two batches do not add up in place."""
+
+    def __init__(self, ids, rows, count, sq_norm, shape):
+        self.ids, self.rows, self.count, self.sq_norm, self.shape = ids, rows, count, sq_norm, tuple(shape)
+        self.pending = True
+
+    def clear(self):
+        self.pending = False
+
+    def to_dense(self):
+        """The ``(V, E)`` gradient, formed on the device without a host read: slots with id -1 are ignored."""
+        V, E = self.shape
+        idx = self.ids.to(torch.int64)
+        used = (idx >= 0) & (idx < V)
+        # the rows of unused slots were never written: they are replaced by zeros and added to row 0, which adding zero leaves as it is;
+        # every other row receives exactly one listed row, so the sum is that row whatever the order of the additions
+        rows = torch.where(used.unsqueeze(1), self.rows, torch.zeros_like(self.rows))
+        dense = torch.zeros((V, E), dtype=self.rows.dtype, device=self.rows.device)
+        return dense.index_add_(0, torch.where(used, idx, torch.zeros_like(idx)), rows)
+
+    def to_sparse_coo(self):
+        """A coalesced ``torch.sparse_coo_tensor`` of shape ``(V, E)`` (reads ``count``: one host read)."""
+        c = int(self.count.item())
+        return torch.sparse_coo_tensor(self.ids[:c].to(torch.int64).unsqueeze(0), self.rows[:c], self.shape, is_coalesced=True)
+
+
+class _EmbedTokensRowsFn(Function):
+    """embed_tokens' lookup with a row-sparse backward: smin_embed_tokens_bwd_rows deposits a RowSparseGrad on ``holder[0].row_grad`` (the
+    caller's table); the node itself returns no gradient, so ``table.grad`` stays None."""
+
+    @staticmethod
+    def forward(ctx, tok, table, pad_id, holder):
+        out = _EmbedTokensFn.forward(ctx, tok, table, pad_id)
+        ctx.E, ctx.holder = table.shape[1], holder
+        return out
+
+    @staticmethod
+    def backward(ctx, dqf, _dqm, _dql):
+        from ._lib import call, load, ptr, stream, workspace
+        (tok,) = ctx.saved_tensors
+        table = ctx.holder[0]
+        old = getattr(table, "row_grad", None)
+        if old is not None and old.pending:
+            raise RuntimeError("embed_tokens(sparse_grad=True): the table's row_grad of an earlier backward is still pending; consume it "
+                               "with RowSparseAdam.step(), or drop it with zero_grad() / table.row_grad.clear()")
+        B, Nq = tok.shape
+        n, E, dev = B * Nq, ctx.E, dqf.device
+        dqf = dqf.float().contiguous()
+        if dqf.data_ptr() % 16:
+            dqf = dqf.clone()
+        ids = torch.empty((n,), dtype=torch.int32, device=dev)
+        rows = torch.empty((n, E), dtype=torch.float32, device=dev)
+        count = torch.empty((1,), dtype=torch.int32, device=dev)
+        sq_norm = torch.empty((1,), dtype=torch.float64, device=dev)
+        ws = workspace(load().smin_embed_tokens_bwd_rows_workspace_bytes(B, Nq), dev)
+        call("smin_embed_tokens_bwd_rows", stream(), ptr(tok), ptr(dqf), B, Nq, ctx.V, E, ptr(ids), ptr(rows), ptr(count), ptr(sq_norm),
+             ptr(ws), ws.numel())
+        table.row_grad = RowSparseGrad(ids, rows, count, sq_norm, (ctx.V, E))
+        return None, None, None, None
+
+
 EMBED_BWD_MAX = 4096                 # B * Nq of one differentiable embed_tokens call (the backward sorts the positions in one workgroup)
 
 
-def embed_tokens(tokens, table, pad_id=None, differentiable=False):
+def embed_tokens(tokens, table, pad_id=None, differentiable=False, sparse_grad=False):
     """Query word vectors from token ids on the device (dataset.py:32-38, 173).  ``tokens`` (B, Nq) integer HIP tensor, ``table``
     (V, E) float32 HIP tensor (E % 4 == 0), ``pad_id`` default ``V - 1`` (the reference's ``<pad>``, appended last).
 
@@ -263,8 +336,14 @@ def embed_tokens(tokens, table, pad_id=None, differentiable=False):
     of the mask)``.  An id outside ``[0, V)`` gives a zero row and mask 0; it is never read.
     ``differentiable=True``: when ``table`` requires grad under grad mode, ``query_features`` carries an autograd node whose backward
     forms the dense ``table.grad`` (as ``nn.Embedding(sparse=False)``): row ``v`` = the sum of the gradient rows at the positions
-    holding ``v``, in ascending ``(b, w)`` order, other rows 0; ``B * Nq <= 4096``.  Default: ``table`` is detached."""
+    holding ``v``, in ascending ``(b, w)`` order, other rows 0; ``B * Nq <= 4096``.  Default: ``table`` is detached.
+    ``sparse_grad=True`` (needs ``differentiable=True``: ValueError otherwise; ``table`` fp32, contiguous, 16-byte aligned): the same
+    forward, but the backward deposits the gradient's distinct rows as a ``RowSparseGrad`` on ``table.row_grad`` -- the same sums, bit
+    for bit, with no ``(V, E)`` tensor -- and ``table.grad`` stays None.  A second backward while that gradient is pending raises
+    RuntimeError (``RowSparseAdam.step()`` / ``zero_grad()`` or ``table.row_grad.clear()`` release it)."""
     from ._lib import SminHipError, call, ptr, stream
+    if sparse_grad and not differentiable:
+        raise ValueError("embed_tokens: sparse_grad=True needs differentiable=True")
     if not (tokens.is_cuda and table.is_cuda):
         raise SminHipError("embed_tokens runs on a HIP device only (got a CPU tensor); there is no CPU fallback")
     if tokens.dim() != 2 or table.dim() != 2 or table.shape[1] % 4 != 0 or table.shape[1] < 4 or tokens.shape[1] < 1:
@@ -273,6 +352,9 @@ def embed_tokens(tokens, table, pad_id=None, differentiable=False):
     pad_id = V - 1 if pad_id is None else int(pad_id)
     tok = tokens.to(torch.int32).contiguous()
     grad = differentiable and table.requires_grad and torch.is_grad_enabled()
+    if sparse_grad and (table.dtype != torch.float32 or not table.is_contiguous() or table.data_ptr() % 16):
+        raise ValueError(f"embed_tokens(sparse_grad=True): the table must be fp32, contiguous and 16-byte aligned, since its rows are updated "
+                         f"in place (got {table.dtype}, contiguous = {table.is_contiguous()})")
     tab = (table if grad else table.detach()).float().contiguous()
     if tab.data_ptr() % 16:
         tab = tab.clone()
@@ -280,6 +362,9 @@ def embed_tokens(tokens, table, pad_id=None, differentiable=False):
     if grad:
         if B * Nq > EMBED_BWD_MAX:
             raise ValueError(f"embed_tokens(differentiable=True): B * Nq = {B * Nq} positions, at most {EMBED_BWD_MAX} per call")
+        if sparse_grad:
+            with torch.cuda.device(dev):
+                return _EmbedTokensRowsFn.apply(tok, tab, pad_id, [table])
         with torch.cuda.device(dev):
             return _EmbedTokensFn.apply(tok, tab, pad_id)
     qf = torch.empty((B, Nq, E), dtype=torch.float32, device=dev)
