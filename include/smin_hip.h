@@ -46,7 +46,9 @@ extern "C" {
  * kept on the device -- smin_epoch_meter_update and smin_epoch_meter_ws_bytes; the metric of merged spans against ground-truth
  * spans -- smin_span_ious, smin_span_meter_update and smin_span_meter_ws_bytes; the optimizer update -- smin_adam_step, smin_grad_norm
  * and smin_adam_ws_bytes; row-sparse training of the word table -- smin_embed_tokens_bwd_rows, smin_embed_tokens_bwd_rows_workspace_bytes
- * (the table gradient as its distinct rows) and smin_row_adam_step (a lazy Adam step over those rows) */
+ * (the table gradient as its distinct rows) and smin_row_adam_step (a lazy Adam step over those rows); the merge of several such row
+ * lists into one -- smin_row_lists_merge and smin_row_lists_merge_workspace_bytes (data-parallel ranks, micro-batches); with it
+ * smin_row_adam_step takes lists of up to 65536 slots where it took 4096 (it rejected longer ones before any launch) */
 #define SMIN_HIP_ABI_VERSION 2
 
 int smin_abi_version(void);
@@ -633,7 +635,7 @@ int smin_adam_step(void* stream, float* const* param, const float* const* grad, 
 
 /* ---- lazy Adam over the rows of a table listed by the rows entry of the token lookup's backward (csrc/row_sparse.hip).
  * table / exp_avg / exp_avg_sq [V][E] (16-byte aligned, E % 4 == 0); ids [n], rows [n][E], count [1], sqnorm [1] as that entry writes
- * them (n <= 4096 is the capacity of ids / rows; sqnorm may be NULL: norm unknown).  state: the 8 doubles of the step entry above, same
+ * them, or as smin_row_lists_merge does (n <= 65536 is the capacity of ids / rows; sqnorm may be NULL: norm unknown).  state: the 8 doubles of the step entry above, same
  * layout and rules; [4] = sqrt(sqnorm) (NaN without sqnorm), [5] = the scale used.  scale: NULL, or one double on the device (e.g.
  * state[5] of the model's optimizer), cast once to fp32.  One workgroup per slot s < count applies to row ids[s], every fp32 operation
  * rounded on its own and the scalars formed as above:
@@ -645,6 +647,31 @@ int smin_adam_step(void* stream, float* const* param, const float* const* grad, 
 int smin_row_adam_step(void* stream, float* table, float* exp_avg, float* exp_avg_sq, const int32_t* ids, const float* rows,
                        const int32_t* count, const double* sqnorm, int n, int V, int E, double* state, const double* scale, double beta1,
                        double beta2, double eps, int skip_nonfinite);
+
+/* ---- merge of R row lists of one [V][E] table into one (csrc/row_sparse.hip): the gradients of data-parallel ranks
+ * or of micro-batches.  ids / rows / count are HOST arrays of R device pointers, n a HOST array with the capacity of each list; scale is
+ * NULL or one double on the device; the outputs have capacity N = the sum of n[r]; ws of the query below (8-byte aligned).
+ * Inputs.  List r is as smin_embed_tokens_bwd_rows writes it: slots s < c_r hold strictly ascending ids in [0, V), with
+ *   c_r = min(count_r[0], n[r]) clamped on the device.  rows_r[s] for s >= c_r is never read.  Limits: 1 <= R <= 16, n[r] >= 0,
+ *   N <= 65536, E >= 4, E % 4 == 0, rows 16-byte aligned.  A list with n[r] == 0 is not read at all (its pointers may be NULL).
+ * Ids.  out_ids[0 .. out_count) is the strictly ascending union of the listed ids; out_ids[out_count .. N) is -1; out_count[0] is the
+ *   size of the union.
+ * Rows.  out_rows[s] = ((rows_r0[.] + rows_r1[.]) + ...) over the lists that hold out_ids[s], in ascending r; every fp32 addition is
+ *   rounded on its own.  When scale != NULL the row is then multiplied by (float)scale[0], cast once, with one more rounding.  Rows of
+ *   slots >= out_count are not written.
+ * Squared norm.  out_sqnorm[0] is the sum of squares of the out_count output rows in double, accumulated in the order of the rows entry
+ *   above (per row: each thread over its quads in index order, then a fixed tree; then the rows in a fixed order).  With R = 1 and no
+ *   scale the call therefore reproduces ids, rows, count and sqnorm of its input bit for bit.
+ * Determinism.  The same bits every run (no atomics); four launches sized by N that exit early on device-side counts (N == 0: count
+ *   and sqnorm are cleared, nothing is launched).  No host read.  No pass over V * E.
+ * Malformed lists.  Every index formed from list contents is bounded before it is used: a list that breaks the ordering contract gives
+ *   unspecified rows but no access outside the buffers.
+ * Rejection.  A nonzero status is returned before any launch for: R outside [1, 16], a negative n[r], N > 65536, bad E, a NULL pointer
+ *   with N > 0 (a list's own pointers only when n[r] > 0), misaligned rows, or a workspace that is too small. */
+size_t smin_row_lists_merge_workspace_bytes(int R, int N);
+int smin_row_lists_merge(void* stream, const int32_t* const* ids, const float* const* rows, const int32_t* const* count, const int* n,
+                         int R, int V, int E, const double* scale, int32_t* out_ids, float* out_rows, int32_t* out_count,
+                         double* out_sqnorm, void* ws, size_t ws_bytes);
 
 /* ---- stand-alone fp32 MFMA GEMM  C[M][N] = A[M][K] * B[N][K]^T  (used by tests and bench.py's
  * roofline probe; same engine as every contraction above). */

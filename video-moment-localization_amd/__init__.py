@@ -24,6 +24,7 @@ from .moments import top_moments, top_moments_torch, merge_window_moments, merge
 from .moments import span_ious, span_ious_torch, compute_span_ious, compute_span_ious_torch  # noqa: F401
 from .feeder import BatchFeeder, FedBatch, build_targets_hip, build_masks_hip, cell_count  # noqa: F401
 from .sampling import (  # noqa: F401
-    sample_clips, sample_clips_torch, embed_tokens, embed_tokens_torch, RowSparseGrad, clip_indices, draw_offsets, spos_high,
+    sample_clips, sample_clips_torch, embed_tokens, embed_tokens_torch, RowSparseGrad, merge_row_grads, merge_row_grads_torch,
+    clip_indices, draw_offsets, spos_high,
     window_plan, sample_windows, sample_windows_torch, window_annotations, draw_windows,
 )

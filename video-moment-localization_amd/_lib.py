@@ -119,6 +119,8 @@ SIGNATURES = {
     "smin_grad_norm": [_vp, _vp, _vp, _i, _d, _vp, _vp, _sz],
     "smin_adam_step": [_vp] * 5 + [_i] + [_vp] * 3 + [_d] * 4 + [_i, _i, _vp],
     "smin_row_adam_step": [_vp] * 8 + [_i] * 3 + [_vp] * 2 + [_d] * 3 + [_i],
+    "smin_row_lists_merge_workspace_bytes": [_i, _i],
+    "smin_row_lists_merge": [_vp] * 5 + [_i] * 3 + [_vp] * 5 + [_vp, _sz],
 }
 _RESTYPE = {"smin_target_arch": ctypes.c_char_p, "smin_workspace_bytes": _sz,
             "smin_content_attn_bwd_workspace_bytes": _sz, "smin_linear_rows_bwd_workspace_bytes": _sz,
@@ -126,7 +128,8 @@ _RESTYPE = {"smin_target_arch": ctypes.c_char_p, "smin_workspace_bytes": _sz,
             "smin_embed_tokens_bwd_rows_workspace_bytes": _sz,
             "smin_word_prep_bwd_workspace_bytes": _sz, "smin_score_tail_ws_bytes": _sz,
             "smin_col_sum_workspace_bytes": _sz, "smin_top_moments_ws_bytes": _sz, "smin_boundary_unit_bwd_ws_bytes": _sz, "smin_compute_ious_nms_ws_bytes": _sz,
-            "smin_epoch_meter_ws_bytes": _sz, "smin_span_meter_ws_bytes": _sz, "smin_adam_ws_bytes": _sz}
+            "smin_epoch_meter_ws_bytes": _sz, "smin_span_meter_ws_bytes": _sz, "smin_adam_ws_bytes": _sz,
+            "smin_row_lists_merge_workspace_bytes": _sz}
 
 _lib = None
 _ws = {}

@@ -1,5 +1,6 @@
 // Row-sparse training of a word-vector table: the compact gradient of smin_embed_tokens and a lazy Adam step over its rows
-// (smin_embed_tokens_bwd_rows / smin_row_adam_step, include/smin_hip.h).
+// (smin_embed_tokens_bwd_rows / smin_row_adam_step, include/smin_hip.h), and the merge of several such gradients into
+// one (smin_row_lists_merge; INTEGRATION.md 3l: described where its kernels start).
 //
 //   sort     one workgroup: the (id, position) keys of the batch sorted in LDS (embed_sort.h, the dense backward's sort), then the run
 //            heads (a valid key whose predecessor holds another id) counted by a prefix scan in the same workgroup: the head of slot s
@@ -133,6 +134,193 @@ void embed_rows_sqnorm_kernel(const double* __restrict__ partial, const int* __r
     if (threadIdx.x == 0) sqnorm[0] = sum;
 }
 
+// ---- merge of several row lists of one table (smin_row_lists_merge)
+//   rank     one thread per input slot (r, s < c_r): a lower-bound binary search of its id in every list r' gives lt_r' and present_r';
+//            merged position = sum of lt_r' + #{r' < r : present_r'}, a run head iff no r' < r holds the id.  The positions of M = sum of
+//            c_r elements are a permutation of [0, M): equal ids adjacent, in ascending r.  entry[position] = head | r << 16 | s.
+//   scan     one workgroup: exclusive prefix of the head flags over [0, M) in chunks of 4096 with a carried base; the head of slot q
+//            writes ids[q] and start[q]; start[count] = M, ids[q >= count] = -1.
+//   rows     one workgroup per output slot (grid N, early exit on the device-side count): the run's rows added in entry order (ascending
+//            r), scaled, stored, and the row's sum of squares in fp64 as embed_rows_kernel forms it.
+//   sqnorm   embed_rows_sqnorm_kernel.
+// Every index formed from list contents (an entry's r and s, a position, a run's bounds) is bounded before it is used, so lists that
+// break the ordering contract give unspecified rows and no access outside the buffers.
+constexpr int MERGE_MAX_LISTS = 16;
+constexpr int MERGE_MAX = 65536;         // N = the sum of the lists' capacities: s < 65536 fits an entry's low 16 bits
+constexpr int MERGE_RANK_THREADS = 256;
+constexpr unsigned MERGE_HEAD = 0x80000000u;
+
+struct MergeLists {                      // by value: 16 * 28 + 4 bytes of kernel arguments
+    const int* ids[MERGE_MAX_LISTS];
+    const float* rows[MERGE_MAX_LISTS];
+    const int* count[MERGE_MAX_LISTS];
+    int n[MERGE_MAX_LISTS];              // capacity of list r
+    int off[MERGE_MAX_LISTS + 1];        // off[r] = n[0] + .. + n[r - 1]; off[R] = N
+};
+
+// Workspace of smin_row_lists_merge for N slots: partial [N] f64 | entry [N] u32 | start [N + 1] i32.
+struct MergeWs {
+    double* partial;
+    unsigned* entry;
+    int* start;
+};
+__host__ __device__ inline MergeWs merge_ws(void* ws, int N)
+{
+    MergeWs w;
+    w.partial = reinterpret_cast<double*>(ws);
+    w.entry = reinterpret_cast<unsigned*>(w.partial + N);
+    w.start = reinterpret_cast<int*>(w.entry + N);
+    return w;
+}
+
+// c_r = min(count_r[0], n[r]), never negative; a list of capacity 0 is not read at all
+__device__ __forceinline__ int merge_len(const MergeLists& L, int r)
+{
+    const int cap = L.n[r];
+    if (cap <= 0) return 0;
+    const int c = L.count[r][0];
+    return c < 0 ? 0 : (c > cap ? cap : c);
+}
+
+// first index in ids[0 .. c) whose id is not below `id` (c when none): at most 17 steps, every probe inside [0, c)
+__device__ __forceinline__ int merge_lower_bound(const int* __restrict__ ids, int c, int id)
+{
+    int lo = 0, hi = c;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (ids[mid] < id) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+
+__global__ __launch_bounds__(MERGE_RANK_THREADS)
+void merge_rank_kernel(const MergeLists L, int R, int N, unsigned* __restrict__ entry)
+{
+    const int g = blockIdx.x * MERGE_RANK_THREADS + threadIdx.x;
+    if (g >= N) return;
+    int r = 0;
+    while (r + 1 < R && g >= L.off[r + 1]) ++r;
+    const int s = g - L.off[r];
+    if (s < 0 || s >= merge_len(L, r)) return;
+    const int id = L.ids[r][s];
+    int p = 0, before = 0;
+    for (int q = 0; q < R; ++q) {
+        const int c = merge_len(L, q);
+        const int lb = merge_lower_bound(L.ids[q], c, id);
+        p += lb;
+        if (q < r && lb < c && L.ids[q][lb] == id) ++before;
+    }
+    p += before;
+    if (p < N) entry[p] = (before == 0 ? MERGE_HEAD : 0u) | ((unsigned)r << 16) | (unsigned)s;
+}
+
+// the slot of list r an entry names, or -1 for an entry that names none (possible only behind lists that break the contract)
+__device__ __forceinline__ int merge_entry_slot(const MergeLists& L, int R, unsigned e, int& r)
+{
+    r = (int)((e >> 16) & 15u);
+    const int s = (int)(e & 0xffffu);
+    return (r < R && s < merge_len(L, r)) ? s : -1;
+}
+
+__global__ __launch_bounds__(SORT_THREADS)
+void merge_scan_kernel(const MergeLists L, int R, int N, const unsigned* __restrict__ entry, int* __restrict__ start, int* __restrict__ ids,
+                       int* __restrict__ count)
+{
+    __shared__ int wave_heads[SORT_WAVES];
+    int M = 0;
+    for (int r = 0; r < R; ++r) M += merge_len(L, r);
+    if (M > N) M = N;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int carried = 0;                                                  // heads before this chunk
+    for (int base = 0; base < M; base += EMBED_BWD_MAX) {             // M is the same in every thread: no divergent barrier
+        const int i0 = base + 4 * (int)threadIdx.x;
+        int heads = 0, id[4] = {0, 0, 0, 0};
+        bool head[4];
+        for (int q = 0; q < 4; ++q) {
+            const int i = i0 + q;
+            head[q] = false;
+            if (i < M) {
+                const unsigned e = entry[i];
+                int r;
+                const int s = merge_entry_slot(L, R, e, r);
+                if ((e & MERGE_HEAD) && s >= 0) { head[q] = true; id[q] = L.ids[r][s]; ++heads; }
+            }
+        }
+        int hs = heads;                                               // inclusive scan inside the wave
+        for (int o = 1; o < 64; o <<= 1) {
+            const int h = __shfl_up(hs, o);
+            if (lane >= o) hs += h;
+        }
+        if (lane == 63) wave_heads[wave] = hs;
+        __syncthreads();
+        int hbase = 0, total = 0;
+        for (int w = 0; w < SORT_WAVES; ++w) {
+            if (w < wave) hbase += wave_heads[w];
+            total += wave_heads[w];
+        }
+        int slot = carried + hbase + hs - heads;                      // heads before position i0: at most i0 < N
+        for (int q = 0; q < 4; ++q)
+            if (head[q]) {
+                ids[slot] = id[q];
+                start[slot] = i0 + q;
+                ++slot;
+            }
+        carried += total;
+        __syncthreads();                                              // wave_heads is rewritten by the next chunk
+    }
+    for (int i = carried + (int)threadIdx.x; i < N; i += SORT_THREADS) ids[i] = -1;
+    if (threadIdx.x == 0) { start[carried] = M; count[0] = carried; }  // carried <= M <= N: start has N + 1 entries
+}
+
+__global__ __launch_bounds__(ROWS_THREADS)
+void merge_rows_kernel(const MergeLists L, int R, int N, const unsigned* __restrict__ entry, const int* __restrict__ start,
+                       const int* __restrict__ count, const double* __restrict__ scale, int E4, float* __restrict__ rows,
+                       double* __restrict__ partial)
+{
+#pragma clang fp contract(off)
+    __shared__ double red[4];
+    __shared__ const float* src[MERGE_MAX_LISTS];
+    const int sl = blockIdx.x;
+    if (sl >= count[0]) return;
+    const size_t E = (size_t)E4 * 4;
+    const int i = start[sl];
+    int len = start[sl + 1] - i;                                      // a run holds one element per list at most
+    if (i < 0 || len < 0) len = 0;
+    if (len > R) len = R;
+    if (len > N - i) len = N - i;
+    if ((int)threadIdx.x < MERGE_MAX_LISTS) {
+        const float* p = nullptr;
+        if ((int)threadIdx.x < len) {
+            int r;
+            const int s = merge_entry_slot(L, R, entry[i + (int)threadIdx.x], r);
+            if (s >= 0) p = L.rows[r] + (size_t)s * E;
+        }
+        src[threadIdx.x] = p;
+    }
+    __syncthreads();
+    const bool scaled = scale != nullptr;
+    const float cf = scaled ? (float)scale[0] : 1.0f;
+    double acc = 0.0;
+    for (int c = threadIdx.x; c < E4; c += blockDim.x) {
+        float4 v = f4zero();
+        bool have = false;
+        for (int k = 0; k < len; ++k) {
+            if (src[k] == nullptr) continue;
+            const float4 x = ldg4(src[k] + 4 * (size_t)c);
+            v = have ? f4add(v, x) : x;
+            have = true;
+        }
+        if (scaled) v = f4scale(v, cf);
+        stg4(rows + (size_t)sl * E + 4 * (size_t)c, v);
+        acc += (double)v.x * (double)v.x;
+        acc += (double)v.y * (double)v.y;
+        acc += (double)v.z * (double)v.z;
+        acc += (double)v.w * (double)v.w;
+    }
+    const double sum = rows_block_sum(acc, red);
+    if (threadIdx.x == 0) partial[sl] = sum;
+}
+
 // ---- lazy Adam over the listed rows
 struct RowAdamHyper {
     double beta1, beta2;
@@ -247,11 +435,65 @@ extern "C" int smin_embed_tokens_bwd_rows(void* stream, const int32_t* tokens, c
     return 0;
 }
 
+extern "C" size_t smin_row_lists_merge_workspace_bytes(int R, int N)
+{
+    (void)R;
+    const size_t n = (size_t)(N > 0 ? N : 0);
+    return (sizeof(double) + sizeof(unsigned)) * n + sizeof(int) * (n + 1) + 256;
+}
+
+extern "C" int smin_row_lists_merge(void* stream, const int32_t* const* ids, const float* const* rows, const int32_t* const* count, const int* n,
+                                    int R, int V, int E, const double* scale, int32_t* out_ids, float* out_rows, int32_t* out_count,
+                                    double* out_sqnorm, void* ws, size_t ws_bytes)
+{
+    SMIN_REQUIRE(R >= 1 && R <= MERGE_MAX_LISTS && V >= 1 && E >= 4 && E % 4 == 0 && n != nullptr);
+    MergeLists L;
+    long long total = 0;
+    for (int r = 0; r < MERGE_MAX_LISTS; ++r) {
+        L.ids[r] = nullptr; L.rows[r] = nullptr; L.count[r] = nullptr; L.n[r] = 0;
+        L.off[r] = (int)total;
+        if (r < R) {
+            SMIN_REQUIRE(n[r] >= 0 && n[r] <= MERGE_MAX);
+            L.n[r] = n[r];
+            total += n[r];
+            SMIN_REQUIRE(total <= MERGE_MAX);
+        }
+    }
+    const int N = (int)total;
+    L.off[MERGE_MAX_LISTS] = N;
+    SMIN_REQUIRE(((uintptr_t)scale & 7) == 0 && ((uintptr_t)out_sqnorm & 7) == 0 && ((uintptr_t)out_rows & 15) == 0 && ((uintptr_t)ws & 7) == 0);
+    hipStream_t st = (hipStream_t)stream;
+    if (N == 0) {                                                     // nothing listed: count = 0 and sqnorm = 0 where they are asked for
+        if (out_count && hipMemsetAsync(out_count, 0, sizeof(int32_t), st) != hipSuccess) return (int)hipGetLastError();
+        if (out_sqnorm && hipMemsetAsync(out_sqnorm, 0, sizeof(double), st) != hipSuccess) return (int)hipGetLastError();
+        return 0;
+    }
+    SMIN_REQUIRE(ids != nullptr && rows != nullptr && count != nullptr);
+    SMIN_REQUIRE(out_ids != nullptr && out_rows != nullptr && out_count != nullptr && out_sqnorm != nullptr && ws != nullptr);
+    SMIN_REQUIRE(ws_bytes >= smin_row_lists_merge_workspace_bytes(R, N));
+    for (int r = 0; r < R; ++r) {
+        if (n[r] == 0) continue;                                      // a list without capacity is never read
+        SMIN_REQUIRE(ids[r] != nullptr && rows[r] != nullptr && count[r] != nullptr && ((uintptr_t)rows[r] & 15) == 0);
+        L.ids[r] = ids[r]; L.rows[r] = rows[r]; L.count[r] = count[r];
+    }
+    const MergeWs w = merge_ws(ws, N);
+    hipLaunchKernelGGL(merge_rank_kernel, dim3(cdiv(N, MERGE_RANK_THREADS)), dim3(MERGE_RANK_THREADS), 0, st, L, R, N, w.entry);
+    SMIN_LAUNCH_CHECK();
+    hipLaunchKernelGGL(merge_scan_kernel, dim3(1), dim3(SORT_THREADS), 0, st, L, R, N, (const unsigned*)w.entry, w.start, out_ids, out_count);
+    SMIN_LAUNCH_CHECK();
+    hipLaunchKernelGGL(merge_rows_kernel, dim3(N), dim3(ROWS_THREADS), 0, st, L, R, N, (const unsigned*)w.entry, (const int*)w.start,
+                       (const int*)out_count, scale, E / 4, out_rows, w.partial);
+    SMIN_LAUNCH_CHECK();
+    hipLaunchKernelGGL(embed_rows_sqnorm_kernel, dim3(1), dim3(ROWS_THREADS), 0, st, (const double*)w.partial, (const int*)out_count, out_sqnorm);
+    SMIN_LAUNCH_CHECK();
+    return 0;
+}
+
 extern "C" int smin_row_adam_step(void* stream, float* table, float* exp_avg, float* exp_avg_sq, const int32_t* ids, const float* rows,
                                   const int32_t* count, const double* sqnorm, int n, int V, int E, double* state, const double* scale,
                                   double beta1, double beta2, double eps, int skip_nonfinite)
 {
-    SMIN_REQUIRE(n >= 0 && n <= EMBED_BWD_MAX && V >= 1 && E >= 4 && E % 4 == 0);
+    SMIN_REQUIRE(n >= 0 && n <= MERGE_MAX && V >= 1 && E >= 4 && E % 4 == 0);   // a merged list may hold 16 lists' slots
     SMIN_REQUIRE(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0 && eps >= 0.0);
     SMIN_REQUIRE(state != nullptr && ((uintptr_t)state & 7) == 0 && ((uintptr_t)scale & 7) == 0 && ((uintptr_t)sqnorm & 7) == 0);
     SMIN_REQUIRE(n == 0 || (table != nullptr && exp_avg != nullptr && exp_avg_sq != nullptr && ids != nullptr && rows != nullptr && count != nullptr));

@@ -98,6 +98,44 @@ def wrap(model, device=None, bucket_cap_mb=8):
     return DDP(model, device_ids=ids, bucket_cap_mb=bucket_cap_mb, gradient_as_bucket_view=True)
 
 
+def exchange_row_grad(table, group=None, average=True, merge=None):
+    """Give every data-parallel rank the same row-sparse gradient of ``table``: each rank's pending
+    ``table.row_grad`` (``embed_tokens(..., sparse_grad=True)``) is gathered -- ``ids``, ``count`` and ``rows``, n * (E + 1) + 1 words a
+    rank instead of the V * E of a dense all-reduce -- and ``table.row_grad`` is replaced by ``merge(lists in rank order, scale)``
+    with ``scale = 1 / world size`` if ``average`` (what the model's gradients get) else ``None``.  ``merge`` defaults to
+    ``sampling.merge_row_grads`` (HIP); ``sampling.merge_row_grads_torch`` is the restatement for CPU groups.  Every rank ends with the
+    same list, bit for bit, so the ``RowSparseAdam`` steps that follow keep the replicas of the table identical.
+    Without an initialised process group, or at world size 1, nothing is touched.  Otherwise every rank must call it: a table without
+    a pending ``row_grad`` raises RuntimeError (a rank must not skip a collective silently), and ranks whose gradients differ in
+    capacity n or in ``(V, E)`` raise ValueError on every rank (checked through one small gather read on the host)."""
+    if not dist.is_initialized():
+        return
+    world = dist.get_world_size(group)
+    if world == 1:
+        return
+    from .sampling import RowSparseGrad, merge_row_grads
+    rg = getattr(table, "row_grad", None)
+    if rg is None or not rg.pending:
+        raise RuntimeError("exchange_row_grad: the table has no pending row_grad (every rank of the group takes part in the gather: run "
+                           "the backward of embed_tokens(..., sparse_grad=True) on each before calling it)")
+    (V, E), n, dev = rg.shape, int(rg.ids.shape[0]), rg.rows.device
+    mine = torch.tensor([n, V, E], dtype=torch.int64, device=dev)
+    dims = torch.empty((world, 3), dtype=torch.int64, device=dev)
+    dist.all_gather([dims[r] for r in range(world)], mine, group=group)
+    if not bool((dims == mine).all()):
+        raise ValueError(f"exchange_row_grad: every rank's row_grad must have the same capacity and table shape (n, V, E); got {dims.tolist()}")
+    if n == 0:
+        return
+    ids = torch.empty((world, n), dtype=torch.int32, device=dev)
+    count = torch.empty((world, 1), dtype=torch.int32, device=dev)
+    rows = torch.empty((world, n, E), dtype=torch.float32, device=dev)
+    for buf, own in ((ids, rg.ids), (count, rg.count), (rows, rg.rows)):
+        dist.all_gather([buf[r] for r in range(world)], own.reshape(buf.shape[1:]).contiguous(), group=group)
+    # the merge recomputes the squared norm, so the lists' own are not gathered
+    lists = [RowSparseGrad(ids[r], rows[r], count[r], None, (V, E)) for r in range(world)]
+    table.row_grad = (merge or merge_row_grads)(lists, scale=1.0 / world if average else None)
+
+
 def describe():
     """(backend, world size) of the default process group as the collective library reports them -- what a benchmark
     line may claim about its gradient exchange."""

@@ -25,7 +25,9 @@ atomics); ``nfeats``, ``query_mask`` and ``qlen`` are never differentiable.  By 
 
 ``embed_tokens(..., differentiable=True, sparse_grad=True)`` leaves the table's gradient as its distinct rows instead (a
 ``RowSparseGrad`` on ``table.row_grad``, from ``smin_embed_tokens_bwd_rows``: no ``(V, E)`` tensor is formed), for
-``optim.RowSparseAdam`` to consume."""
+``optim.RowSparseAdam`` to consume.  ``merge_row_grads`` merges several such gradients of one table into one
+(``smin_row_lists_merge``: data-parallel ranks through ``distributed.exchange_row_grad``, micro-batches through
+``embed_tokens(..., accumulate=True)``); ``merge_row_grads_torch`` restates it."""
 from torch.autograd import Function
 import numpy as np
 import torch
@@ -262,9 +264,10 @@ class RowSparseGrad:
     ``ids (n,) int32``: slots ``s < count`` hold the distinct ids in ``[0, V)``, strictly ascending; later slots hold -1.
     ``rows (n, E) float32``: ``rows[s]`` = row ``ids[s]`` of the dense gradient, bit for bit; rows of later slots are unspecified.
     ``count (1,) int32``; ``sq_norm (1,) float64`` = the sum of squares of the ``count`` rows (a fixed summation order).
-    ``n = B * Nq`` of the batch; ``shape = (V, E)``.  ``pending`` (host side) is set by the backward that made it and cleared by
-    ``clear()``, which the optimizer's ``step()`` / ``zero_grad()`` call: a backward into a table whose gradient is still pending is
-    refused, since row lists of two batches do not add up in place."""
+    ``n = B * Nq`` of the batch (the sum of its inputs' ``n`` for a merged gradient); ``shape = (V, E)``.  ``pending`` (host side) is set
+    by the backward or merge that made it and cleared by ``clear()``, which the optimizer's ``step()`` / ``zero_grad()`` call: a backward
+    into a table whose gradient is still pending is refused unless ``embed_tokens`` was called with ``accumulate=True``, which merges
+    the two (``merge_row_grads``)."""
 
     def __init__(self, ids, rows, count, sq_norm, shape):
         self.ids, self.rows, self.count, self.sq_norm, self.shape = ids, rows, count, sq_norm, tuple(shape)
@@ -290,14 +293,105 @@ class RowSparseGrad:
         return torch.sparse_coo_tensor(self.ids[:c].to(torch.int64).unsqueeze(0), self.rows[:c], self.shape, is_coalesced=True)
 
 
+MERGE_MAX_LISTS = 16                 # row lists per merge_row_grads call
+MERGE_MAX_SLOTS = 65536              # the sum of their capacities (and the longest list RowSparseAdam.step() takes)
+
+
+def _merge_args(grads, who):
+    """-> (list of RowSparseGrad, (V, E), device, N = the sum of the capacities), or ValueError"""
+    grads = list(grads)
+    if not 1 <= len(grads) <= MERGE_MAX_LISTS:
+        raise ValueError(f"{who}: 1 to {MERGE_MAX_LISTS} row gradients per call (got {len(grads)})")
+    shape, dev = tuple(grads[0].shape), grads[0].rows.device
+    for g in grads:
+        if tuple(g.shape) != shape or g.rows.device != dev or g.ids.device != dev or g.count.device != dev:
+            raise ValueError(f"{who}: every row gradient must be of the same (V, E) table on one device (got {tuple(g.shape)} on "
+                             f"{g.rows.device} beside {shape} on {dev})")
+        if g.ids.dim() != 1 or g.rows.shape != (g.ids.shape[0], shape[1]) or g.count.numel() != 1:
+            raise ValueError(f"{who}: ids (n,), rows (n, E) and count (1,) expected (got {tuple(g.ids.shape)}, {tuple(g.rows.shape)}, "
+                             f"{tuple(g.count.shape)})")
+    N = sum(int(g.ids.shape[0]) for g in grads)
+    if N > MERGE_MAX_SLOTS:
+        raise ValueError(f"{who}: the capacities add up to {N} slots, at most {MERGE_MAX_SLOTS} per call")
+    return grads, shape, dev, N
+
+
+def merge_row_grads(grads, scale=None):
+    """Merge 1 to 16 ``RowSparseGrad`` of the same ``(V, E)`` table on one HIP device into one, on the device and without a host read
+    (``smin_row_lists_merge``, csrc/row_sparse.hip).  The result has capacity ``N`` = the sum of the inputs'
+    capacities (at most 65536): ``ids[:count]`` is the strictly ascending union of the listed ids, ``ids[count:]`` is -1; ``rows[s]`` is
+    ``((rows_a + rows_b) + ...)`` over the inputs that list ``ids[s]``, in the order of ``grads``, every fp32 addition rounded on its own,
+    then -- when ``scale`` is given: a float, or one fp64 value on the device -- multiplied by the scale cast once to fp32; ``sq_norm``
+    is the fp64 sum of squares of the result's rows in the order of ``smin_embed_tokens_bwd_rows``, so one gradient merged alone comes
+    back bit for bit.  The same bits every run.  Returns a pending ``RowSparseGrad``; the inputs are left as they are.
+    ValueError: mismatched ``(V, E)`` or devices, more than 16 gradients, more than 65536 slots; SminHipError: CPU tensors."""
+    import ctypes
+    from ._lib import SminHipError, call, load, ptr, stream, workspace
+    grads, (V, E), dev, N = _merge_args(grads, "merge_row_grads")
+    if dev.type != "cuda":
+        raise SminHipError("merge_row_grads runs on a HIP device only (got CPU tensors); there is no CPU fallback -- the plain restatement "
+                           "is available under the explicit name merge_row_grads_torch")
+    for g in grads:
+        if (g.ids.dtype != torch.int32 or g.count.dtype != torch.int32 or g.rows.dtype != torch.float32
+                or not (g.ids.is_contiguous() and g.rows.is_contiguous()) or g.rows.data_ptr() % 16):
+            raise ValueError("merge_row_grads: ids and count must be int32, rows fp32, contiguous and 16-byte aligned")
+    if scale is not None:
+        if not isinstance(scale, torch.Tensor):
+            scale = torch.full((1,), float(scale), dtype=torch.float64).to(dev, non_blocking=True)
+        if scale.dtype != torch.float64 or scale.numel() != 1 or scale.device != dev:
+            raise ValueError("merge_row_grads: scale must be one fp64 value on the gradients' device (or a float)")
+        scale = scale.detach().contiguous()
+    R = len(grads)
+    ids = torch.empty((N,), dtype=torch.int32, device=dev)
+    rows = torch.empty((N, E), dtype=torch.float32, device=dev)
+    count = torch.empty((1,), dtype=torch.int32, device=dev)
+    sq_norm = torch.empty((1,), dtype=torch.float64, device=dev)
+    pointers = lambda ts: (ctypes.c_void_p * R)(*[t.data_ptr() if t.numel() else None for t in ts])
+    caps = (ctypes.c_int * R)(*[int(g.ids.shape[0]) for g in grads])
+    with torch.cuda.device(dev):
+        ws = workspace(load().smin_row_lists_merge_workspace_bytes(R, N), dev)
+        call("smin_row_lists_merge", stream(), pointers([g.ids for g in grads]), pointers([g.rows for g in grads]),
+             pointers([g.count for g in grads]), caps, R, V, E, ptr(scale), ptr(ids), ptr(rows), ptr(count), ptr(sq_norm), ptr(ws), ws.numel())
+    return RowSparseGrad(ids, rows, count, sq_norm, (V, E))
+
+
+def merge_row_grads_torch(grads, scale=None):
+    """``merge_row_grads`` as plain torch ops on any device (the restatement; reads the counts on the host): the same order of
+    additions, one fp32 operation at a time, the same -1 tail; rows of slots ``>= count`` are zero; ``sq_norm`` is the fp64 sum of
+    squares of ``rows[:count]`` (``torch.sum``: the kernel's value to a few ulps, not to the bit).  Nothing routes to it."""
+    grads, (V, E), dev, N = _merge_args(grads, "merge_row_grads_torch")
+    lists = []
+    for g in grads:
+        c = min(max(int(g.count.reshape(-1)[0]), 0), int(g.ids.shape[0]))
+        lists.append((g.ids[:c].to(torch.int64), g.rows[:c].to(torch.float32)))
+    union = torch.unique(torch.cat([i for i, _ in lists]))           # sorted
+    K = int(union.numel())
+    acc = torch.zeros((K, E), dtype=torch.float32, device=dev)
+    have = torch.zeros((K,), dtype=torch.bool, device=dev)
+    for i, r in lists:                                                # a list's ids are distinct: every slot receives one row per list at most
+        slot = torch.searchsorted(union, i)
+        acc[slot] = torch.where(have[slot].unsqueeze(1), acc[slot] + r, r)
+        have[slot] = True
+    if scale is not None:
+        c = scale.detach().reshape(-1)[0].to(torch.float64) if isinstance(scale, torch.Tensor) else torch.tensor(float(scale), dtype=torch.float64)
+        acc = acc * c.to(device=dev, dtype=torch.float32)             # cast once to fp32, one rounding per element
+    ids = torch.full((N,), -1, dtype=torch.int32, device=dev)
+    ids[:K] = union.to(torch.int32)
+    rows = torch.zeros((N, E), dtype=torch.float32, device=dev)
+    rows[:K] = acc
+    count = torch.tensor([K], dtype=torch.int32, device=dev)
+    sq_norm = (acc.double() * acc.double()).sum().reshape(1)
+    return RowSparseGrad(ids, rows, count, sq_norm, (V, E))
+
+
 class _EmbedTokensRowsFn(Function):
     """embed_tokens' lookup with a row-sparse backward: smin_embed_tokens_bwd_rows deposits a RowSparseGrad on ``holder[0].row_grad`` (the
     caller's table); the node itself returns no gradient, so ``table.grad`` stays None."""
 
     @staticmethod
-    def forward(ctx, tok, table, pad_id, holder):
+    def forward(ctx, tok, table, pad_id, holder, accumulate):
         out = _EmbedTokensFn.forward(ctx, tok, table, pad_id)
-        ctx.E, ctx.holder = table.shape[1], holder
+        ctx.E, ctx.holder, ctx.accumulate = table.shape[1], holder, accumulate
         return out
 
     @staticmethod
@@ -306,9 +400,11 @@ class _EmbedTokensRowsFn(Function):
         (tok,) = ctx.saved_tensors
         table = ctx.holder[0]
         old = getattr(table, "row_grad", None)
-        if old is not None and old.pending:
+        old = old if old is not None and old.pending else None
+        if old is not None and not ctx.accumulate:
             raise RuntimeError("embed_tokens(sparse_grad=True): the table's row_grad of an earlier backward is still pending; consume it "
-                               "with RowSparseAdam.step(), or drop it with zero_grad() / table.row_grad.clear()")
+                               "with RowSparseAdam.step(), drop it with zero_grad() / table.row_grad.clear(), or pass accumulate=True to "
+                               "add this backward's rows to it")
         B, Nq = tok.shape
         n, E, dev = B * Nq, ctx.E, dqf.device
         dqf = dqf.float().contiguous()
@@ -321,14 +417,15 @@ class _EmbedTokensRowsFn(Function):
         ws = workspace(load().smin_embed_tokens_bwd_rows_workspace_bytes(B, Nq), dev)
         call("smin_embed_tokens_bwd_rows", stream(), ptr(tok), ptr(dqf), B, Nq, ctx.V, E, ptr(ids), ptr(rows), ptr(count), ptr(sq_norm),
              ptr(ws), ws.numel())
-        table.row_grad = RowSparseGrad(ids, rows, count, sq_norm, (ctx.V, E))
-        return None, None, None, None
+        new = RowSparseGrad(ids, rows, count, sq_norm, (ctx.V, E))
+        table.row_grad = new if old is None else merge_row_grads([old, new])   # old + new, as the dense path's table.grad += new
+        return None, None, None, None, None
 
 
 EMBED_BWD_MAX = 4096                 # B * Nq of one differentiable embed_tokens call (the backward sorts the positions in one workgroup)
 
 
-def embed_tokens(tokens, table, pad_id=None, differentiable=False, sparse_grad=False):
+def embed_tokens(tokens, table, pad_id=None, differentiable=False, sparse_grad=False, accumulate=False):
     """Query word vectors from token ids on the device (dataset.py:32-38, 173).  ``tokens`` (B, Nq) integer HIP tensor, ``table``
     (V, E) float32 HIP tensor (E % 4 == 0), ``pad_id`` default ``V - 1`` (the reference's ``<pad>``, appended last).
 
@@ -340,10 +437,15 @@ def embed_tokens(tokens, table, pad_id=None, differentiable=False, sparse_grad=F
     ``sparse_grad=True`` (needs ``differentiable=True``: ValueError otherwise; ``table`` fp32, contiguous, 16-byte aligned): the same
     forward, but the backward deposits the gradient's distinct rows as a ``RowSparseGrad`` on ``table.row_grad`` -- the same sums, bit
     for bit, with no ``(V, E)`` tensor -- and ``table.grad`` stays None.  A second backward while that gradient is pending raises
-    RuntimeError (``RowSparseAdam.step()`` / ``zero_grad()`` or ``table.row_grad.clear()`` release it)."""
+    RuntimeError (``RowSparseAdam.step()`` / ``zero_grad()`` or ``table.row_grad.clear()`` release it), unless
+    ``accumulate=True`` (needs ``sparse_grad=True``: ValueError otherwise): the backward then replaces a pending ``row_grad`` by
+    ``merge_row_grads([pending, new])``, whose ``to_dense()`` is what the dense path's ``table.grad += ...`` gives, bit for bit; the
+    capacities add up, at most 65536 slots in all."""
     from ._lib import SminHipError, call, ptr, stream
     if sparse_grad and not differentiable:
         raise ValueError("embed_tokens: sparse_grad=True needs differentiable=True")
+    if accumulate and not sparse_grad:
+        raise ValueError("embed_tokens: accumulate=True needs sparse_grad=True (the dense path accumulates into table.grad by itself)")
     if not (tokens.is_cuda and table.is_cuda):
         raise SminHipError("embed_tokens runs on a HIP device only (got a CPU tensor); there is no CPU fallback")
     if tokens.dim() != 2 or table.dim() != 2 or table.shape[1] % 4 != 0 or table.shape[1] < 4 or tokens.shape[1] < 1:
@@ -364,7 +466,7 @@ def embed_tokens(tokens, table, pad_id=None, differentiable=False, sparse_grad=F
             raise ValueError(f"embed_tokens(differentiable=True): B * Nq = {B * Nq} positions, at most {EMBED_BWD_MAX} per call")
         if sparse_grad:
             with torch.cuda.device(dev):
-                return _EmbedTokensRowsFn.apply(tok, tab, pad_id, [table])
+                return _EmbedTokensRowsFn.apply(tok, tab, pad_id, [table], bool(accumulate))
         with torch.cuda.device(dev):
             return _EmbedTokensFn.apply(tok, tab, pad_id)
     qf = torch.empty((B, Nq, E), dtype=torch.float32, device=dev)
