@@ -48,7 +48,9 @@ extern "C" {
  * and smin_adam_ws_bytes; row-sparse training of the word table -- smin_embed_tokens_bwd_rows, smin_embed_tokens_bwd_rows_workspace_bytes
  * (the table gradient as its distinct rows) and smin_row_adam_step (a lazy Adam step over those rows); the merge of several such row
  * lists into one -- smin_row_lists_merge and smin_row_lists_merge_workspace_bytes (data-parallel ranks, micro-batches); with it
- * smin_row_adam_step takes lists of up to 65536 slots where it took 4096 (it rejected longer ones before any launch) */
+ * smin_row_adam_step takes lists of up to 65536 slots where it took 4096 (it rejected longer ones before any launch); corpus search
+ * over banks of encoded videos and queries -- smin_pair_assemble (the backbone's outputs of indexed pairs) and smin_corpus_topk (one
+ * ranked list per query across videos) */
 #define SMIN_HIP_ABI_VERSION 2
 
 int smin_abi_version(void);
@@ -672,6 +674,45 @@ size_t smin_row_lists_merge_workspace_bytes(int R, int N);
 int smin_row_lists_merge(void* stream, const int32_t* const* ids, const float* const* rows, const int32_t* const* count, const int* n,
                          int R, int V, int E, const double* scale, int32_t* out_ids, float* out_rows, int32_t* out_count,
                          double* out_sqnorm, void* ws, size_t ws_bytes);
+
+/* ---- corpus search (csrc/corpus.hip): Q queries against a bank of V videos, each encoded once.  Scoring only:
+ * neither entry has a backward.
+ *
+ * smin_pair_assemble: the backbone's outputs of P (video, query) pairs from the banks, one launch.
+ * Inputs.  fv [V][T][D]: the video encoder's projection with position embedding and mask (smin_video_encoder_fwd with fs == NULL);
+ *   fs_bank [Q][D], fw_bank [Q][Nq][D]: the query encoder's sentence and word features; video_index, query_index: [P] int32 on the
+ *   device, any lists, repeats included.
+ * Outputs.  f [P][T][D]: f[p][t][:] = fv[vi[p]][t][:] * fs_bank[qi[p]][:]; fw [P][Nq][D] = fw_bank[qi[p]]; fs [P][D] = fs_bank[qi[p]].
+ * Arithmetic.  One fp32 multiplication per element of f, so its bits are those of smin_video_encoder_gate on expanded copies of the
+ *   operands; the two gathers are bit copies.  16-byte loads and stores throughout.
+ * Bounds.  An index outside [0, V) or [0, Q) is clamped into the range before it forms an address: the call cannot leave the buffers
+ *   (the Python host refuses such an index before it gets here).
+ * Limits.  D >= 4, D % 4 == 0, P, V, Q, T, Nq >= 1, buffers 16-byte aligned.  The outputs must not overlap the inputs.
+ * Determinism.  The same bits every run (no atomics); no host read; capturable.
+ * Rejection.  A nonzero status is returned before the launch for a bad D, a size below 1 or a NULL pointer. */
+int smin_pair_assemble(void* stream, const float* fv, const float* fs_bank, const float* fw_bank, const int32_t* video_index,
+                       const int32_t* query_index, int P, int V, int Q, int T, int Nq, int D, float* f, float* fw, float* fs);
+
+/* smin_corpus_topk: the K best moments of each query over all of its videos, one launch, one workgroup per query; no workspace.
+ * Inputs.  The per-pair lists exactly as smin_top_moments writes them for P pairs at k = k_video: pair_score [P][k_video] fp32,
+ *   pair_idx [P][k_video][2] int64, pair_count [P] int32; pair_video [P] int32: each pair's video; pair_ptr [Q + 1] int32: query q owns
+ *   pairs pair_ptr[q] .. pair_ptr[q + 1] (ascending, within [0, P]: P itself is not an argument and the range is trusted; a negative
+ *   or descending entry gives an empty range).  A query may have no pairs, and the number of pairs per query is not limited.
+ * Candidates.  The first min(pair_count[p], k_video) slots of each of the query's pairs, the count clamped on the device (a negative
+ *   one lists nothing).  Slots past the count are never read.
+ * Order.  Higher score first; ties go to the lower video index, then to the lower slot, then (two pairs of one query that name the
+ *   same video) to the earlier pair.  A score of -0 counts as +0.  No suppression across videos: moments of different videos do not
+ *   overlap, and within a video smin_top_moments has already applied the NMS.
+ * Outputs.  The first K candidates in that order: out_video [Q][K] int64, out_idx [Q][K][2] int64 and out_score [Q][K] fp32 (idx and
+ *   score copied bit for bit), out_count [Q] int32 = the number listed.  Empty slots: video -1, idx -1, score 0.
+ * Limits.  1 <= K <= 64, 1 <= k_video <= 64, Q >= 0 (Q == 0: nothing is launched).
+ * Determinism.  The same bits every run (no atomics); no host read; capturable.
+ * Rejection.  A nonzero status is returned before the launch for a bad K or k_video, a negative Q, or, with Q > 0, a NULL pair_ptr or
+ *   output.  Whether a query has pairs is known on the device only: with a NULL pair_score, pair_idx, pair_count or pair_video none of
+ *   the four is read and every query comes out empty. */
+int smin_corpus_topk(void* stream, const float* pair_score, const int64_t* pair_idx, const int32_t* pair_count, const int32_t* pair_video,
+                     const int32_t* pair_ptr, int Q, int k_video, int K, int64_t* out_video, int64_t* out_idx, float* out_score,
+                     int32_t* out_count);
 
 /* ---- stand-alone fp32 MFMA GEMM  C[M][N] = A[M][K] * B[N][K]^T  (used by tests and bench.py's
  * roofline probe; same engine as every contraction above). */

@@ -1,0 +1,471 @@
+"""Corpus search: csrc/corpus.hip (smin_pair_assemble, smin_corpus_topk), the operators smin_hip::smin_encode_videos /
+smin_encode_queries / smin_score_pairs and SMIN.encode_videos / encode_queries / score_pairs / search.
+
+Host: the C ABI and operator surface, moments.corpus_topk_torch on hand-made lists, the refusals.
+GPU: the two kernels bit for bit against torch indexing and the restated merge; score_pairs on identity banks against SMIN.score
+(same bits) and on shared banks against the CPU oracle, gated by the error of SMIN.score on the expanded batch; search end to end
+against search_torch, without host reads, on the fall-back path, repeatably, and without moving anything else."""
+import ctypes
+import os
+import re
+
+import numpy as np
+import pytest
+import torch
+
+from tests import helpers as H
+
+SCORE_TOL = 2e-5                                       # test_score_path.SCORE_TOL
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+TINY_SHAPE = (16, 8, 4, 32, 16, 2, 24, 5, 16)          # T, L, C, D, dl, layers, Din, Nq, H
+OPTIONS = ("bool overlap_boundary", "bool overlap_prep", "bool param_prep_kernel", "bool bf16_operand_storage", "int? known_cell_count")
+
+
+def V():
+    import models
+    return models.vml_amd
+
+
+def tiny_model(dev=None):
+    import models
+    from oracle import smin_oracle as O
+    sd = O.formula_state_dict(H.smin_shapes(*TINY_SHAPE), gain=1.2)
+    m = models.SMIN(*TINY_SHAPE) if dev is None else models.SMIN(*TINY_SHAPE, dev)
+    m.load_state_dict(sd, strict=True)
+    return (m if dev is None else m.to(dev)), sd
+
+
+def corpus_inputs(snips=(8, 1, 5, 8, 3), words=(5, 1, 3, 4), seed=3):
+    """V videos with the given numbers of valid snippets of L and Q queries with the given numbers of words, as host tensors in the
+    layout of oracle.synthetic_batch."""
+    T, L, _, _, _, _, Din, Nq, _ = TINY_SHAPE
+    g = torch.Generator().manual_seed(seed)
+    nv, nq = len(snips), len(words)
+    vf, qf = torch.randn(nv, T, Din, generator=g), torch.randn(nq, Nq, 300, generator=g)
+    vmask, qmask = torch.zeros(nv, T, 1, dtype=torch.uint8), torch.zeros(nq, Nq, 1, dtype=torch.uint8)
+    lmask = torch.zeros(nv, L, dtype=torch.bool)
+    for v, s in enumerate(snips):
+        nf = s * (T // L) - (v % 2)                    # odd videos end inside their last snippet
+        vf[v, nf:] = 0
+        vmask[v, :nf] = 1
+        lmask[v, :s] = True
+    for q, w in enumerate(words):
+        qf[q, w:] = 0
+        qmask[q, :w] = 1
+    mmask = torch.triu(lmask.unsqueeze(2) & lmask.unsqueeze(1))
+    return dict(video_features=vf, video_mask=vmask, length_mask=lmask, moment_mask=mmask), dict(query_features=qf, query_mask=qmask)
+
+
+def expand(vid, qry, vi, qi):
+    """the six forward inputs of the pairs (vi[p], qi[p])"""
+    vi, qi = torch.as_tensor(vi, dtype=torch.int64), torch.as_tensor(qi, dtype=torch.int64)
+    vi, qi = vi.to(vid["video_features"].device), qi.to(vid["video_features"].device)
+    return [vid["video_features"][vi], vid["video_mask"][vi], qry["query_features"][qi], qry["query_mask"][qi], vid["length_mask"][vi],
+            vid["moment_mask"][vi]]
+
+
+def host_banks():
+    vid, qry = corpus_inputs()
+    A = V()
+    counts = vid["moment_mask"].reshape(5, -1).sum(1).tolist()
+    vb = A.VideoBank(None, vid["video_features"], vid["video_mask"], vid["length_mask"], vid["moment_mask"], counts)
+    qb = A.QueryBank(None, None, qry["query_features"], qry["query_mask"].reshape(4, -1))
+    return vb, qb
+
+
+# ---------------------------------------------------------------- host: surface
+def test_header_and_table_declare_the_corpus_kernels():
+    text = open(os.path.join(ROOT, "include", "smin_hip.h")).read()
+    for name in ("smin_pair_assemble", "smin_corpus_topk"):
+        assert re.search(r"\bint\s+" + name + r"\s*\(", text), name
+        assert name in V()._lib.SIGNATURES, name
+        assert hasattr(V()._lib.load(), name)
+    assert "#define SMIN_HIP_ABI_VERSION 2" in text
+    assert "corpus.hip" in open(os.path.join(ROOT, "video-moment-localization_amd", "csrc", "Makefile")).read()
+
+
+def test_operators_are_registered_and_refuse_cpu():
+    ops = V()._lib.load_torch()
+    for name in ("smin_encode_videos", "smin_encode_queries", "smin_score_pairs"):
+        assert hasattr(ops, name), name
+    schema = str(torch.ops.smin_hip.smin_score_pairs.default._schema)
+    score_schema = str(torch.ops.smin_hip.smin_score.default._schema)
+    for name in ("Tensor fv", "Tensor fw", "Tensor fs", "Tensor video_index", "Tensor query_index", "Tensor[] params", "*, bool overlap_boundary") + OPTIONS:
+        assert name in schema, schema
+    for name in OPTIONS:
+        assert name in score_schema
+    for name in ("async_weights", "grad_sync", "tail_split", "input_grads", "attention"):
+        assert name not in schema, schema
+    m, _ = tiny_model()
+    vid, qry = corpus_inputs()
+    with pytest.raises(RuntimeError, match="no CPU fallback"):
+        ops.smin_encode_videos(vid["video_features"], vid["video_mask"], m._native_params())
+    with pytest.raises(RuntimeError, match="no CPU fallback"):
+        ops.smin_encode_queries(qry["query_features"], qry["query_mask"], m._native_params(), 5, 16)
+    with pytest.raises(RuntimeError, match="no CPU fallback"):
+        ops.smin_score_pairs(torch.zeros(5, 16, 32), torch.zeros(4, 5, 32), torch.zeros(4, 32), vid["video_mask"], qry["query_mask"], vid["length_mask"],
+                             vid["moment_mask"], torch.zeros(2, dtype=torch.int32), torch.zeros(2, dtype=torch.int32), m._native_params(), 16, 8, 4, 2, 5, 16,
+                             **m._score_options())
+
+
+def test_methods_fail_loudly_on_cpu():
+    m, _ = tiny_model()
+    vid, qry = corpus_inputs()
+    err = V()._lib.SminHipError
+    with pytest.raises(err, match="no CPU fallback"):
+        m.encode_videos(vid["video_features"], vid["video_mask"], vid["length_mask"], vid["moment_mask"])
+    with pytest.raises(err, match="no CPU fallback"):
+        m.encode_queries(qry["query_features"], qry["query_mask"])
+    vb, qb = host_banks()
+    with pytest.raises(err, match="no CPU fallback"):
+        m.score_pairs(vb, qb, [0, 1], [1, 0])
+    with pytest.raises(err, match="no CPU fallback"):
+        m.search(vb, qb)
+    with pytest.raises(err, match="no CPU fallback"):
+        V().corpus_topk(torch.zeros(1, 2), torch.zeros(1, 2, 2, dtype=torch.int64), torch.zeros(1, dtype=torch.int32), torch.zeros(1, dtype=torch.int32),
+                        torch.tensor([0, 1], dtype=torch.int32))
+
+
+def test_refusals():
+    m, _ = tiny_model()
+    vb, qb = host_banks()
+    with pytest.raises(ValueError, match="video_index must lie"):
+        m.score_pairs(vb, qb, [0, 5], [0, 0])
+    with pytest.raises(ValueError, match="video_index must lie"):
+        m.score_pairs(vb, qb, [0, 1], [0, -1])
+    with pytest.raises(ValueError, match="video_index must lie"):
+        m.search(vb, qb, pairs=[(4, 0)])
+    with pytest.raises(ValueError, match="one length"):
+        m.score_pairs(vb, qb, [0, 1, 2], [0, 1])
+    with pytest.raises(ValueError, match="more than once"):
+        m.search(vb, qb, pairs=[(0, 1), (2, 3), (0, 1)])
+    for kw in (dict(k=0), dict(k=65), dict(k_video=0), dict(k_video=65), dict(max_batch=0), dict(k=2.0)):
+        with pytest.raises(ValueError, match="must be an integer"):
+            m.search(vb, qb, **kw)
+    with pytest.raises(ValueError, match="duration must be"):
+        m.search(vb, qb, duration=torch.ones(4))
+    with pytest.raises(ValueError, match="duration must be"):
+        m.search_torch(vb, qb, duration=torch.ones(5, 1))
+
+
+# ---------------------------------------------------------------- host: the restated merge on hand-made lists
+def lists(score, count, video, ptr, kv):
+    P = len(video)
+    score = torch.tensor(score, dtype=torch.float32).reshape(P, kv)
+    idx = torch.arange(P * kv * 2, dtype=torch.int64).reshape(P, kv, 2)
+    return (score, idx, torch.tensor(count, dtype=torch.int32), torch.tensor(video, dtype=torch.int32), torch.tensor(ptr, dtype=torch.int32))
+
+
+def test_corpus_topk_torch_by_hand():
+    f = V().corpus_topk_torch
+    # query 0: videos 7 and 2 (ties across videos and within a pair, -0 against +0, garbage behind the count);
+    # query 1: no pairs; query 2: one pair with count 0
+    score = [0.5, 0.25, 0.25,   0.5, -0.0, 9.0,   0.0, 0.5, 0.5,   9.0, 9.0, 9.0]
+    a = lists(score, [3, 2, 3, 0], [7, 2, 4, 1], [0, 3, 3, 4], 3)
+    r = f(*a, k=5)
+    assert r["count"].tolist() == [5, 0, 0]
+    # 0.5: video 2 (pair 1 slot 0), video 4 slot 1, slot 2, video 7 slot 0; then 0.25: video 7 slot 1
+    assert r["video"].tolist() == [[2, 4, 4, 7, 7], [-1] * 5, [-1] * 5]
+    flat = lambda p, s: [2 * (3 * p + s), 2 * (3 * p + s) + 1]
+    assert r["idx"][0].tolist() == [flat(1, 0), flat(2, 1), flat(2, 2), flat(0, 0), flat(0, 1)]
+    assert r["score"][0].tolist() == [0.5, 0.5, 0.5, 0.5, 0.25]
+    assert r["idx"][1:].eq(-1).all() and r["score"][1:].eq(0).all()
+    # K larger than the candidates: all 8 in order, -0 (video 2) ahead of +0 (video 4) as equals, by video; the rest empty
+    r = f(*a, k=64)
+    assert r["count"].tolist() == [8, 0, 0]
+    assert r["video"][0, :8].tolist() == [2, 4, 4, 7, 7, 7, 2, 4] and r["video"][0, 8:].eq(-1).all()
+    assert r["score"][0, 6:8].view(torch.int32).tolist() == [-2 ** 31, 0]            # the scores leave as stored: -0 stays -0
+    assert r["score"][0, 8:].eq(0).all() and r["idx"][0, 8:].eq(-1).all()
+    r = f(*a, k=1)
+    assert r["video"].tolist() == [[2], [-1], [-1]] and r["count"].tolist() == [1, 0, 0]
+    # a count above k_video is clamped; a negative one lists nothing
+    r = f(*lists([1.0, 2.0, 3.0, 4.0], [9, -1], [0, 1], [0, 2], 2), k=5)
+    assert r["count"].tolist() == [2] and r["score"][0, :2].tolist() == [2.0, 1.0]
+    for bad in (0, 65, 2.0):
+        with pytest.raises(ValueError):
+            f(*a, k=bad)
+
+
+# ---------------------------------------------------------------- GPU
+@pytest.fixture(scope="module")
+def dev():
+    assert torch.cuda.is_available(), "GPU tests need a HIP device"
+    V()._lib.load()
+    return torch.device("cuda:0")
+
+
+def bits(t):
+    return t.detach().cpu().contiguous().view(torch.int32)
+
+
+SENTINEL = 0x5A5A5A5A
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("nv,nq,P,T,Nq,D", [(3, 4, 17, 16, 5, 32), (2, 2, 1, 1, 1, 4), (5, 3, 9, 7, 5, 104)])
+def test_pair_assemble_bit_exact(dev, nv, nq, P, T, Nq, D):
+    L_ = V()._lib
+    g = torch.Generator().manual_seed(nv * 100 + P)
+    fv, fsb, fwb = torch.randn(nv, T, D, generator=g), torch.randn(nq, D, generator=g), torch.randn(nq, Nq, D, generator=g)
+    vi = torch.randint(0, nv, (P,), generator=g, dtype=torch.int64)
+    qi = torch.randint(0, nq, (P,), generator=g, dtype=torch.int64)
+    if P > 2:
+        vi[1], qi[1] = vi[0], qi[0]                                                  # a repeated pair
+        assert len(set(vi.tolist())) < P
+    want = [fv[vi] * fsb[qi].unsqueeze(1), fwb[qi], fsb[qi]]
+    outs = [torch.full((w.numel() + 4,), SENTINEL, dtype=torch.int32, device=dev).view(torch.float32) for w in want]
+    ins = [x.to(dev) for x in (fv, fsb, fwb)] + [vi.to(dev, torch.int32), qi.to(dev, torch.int32)]
+    L_.call("smin_pair_assemble", L_.stream(), *[L_.ptr(x) for x in ins], P, nv, nq, T, Nq, D, *[L_.ptr(o) for o in outs])
+    torch.cuda.synchronize()
+    for name, o, w in zip(("f", "fw", "fs"), outs, want):
+        assert torch.equal(bits(o[:w.numel()]), bits(w.reshape(-1))), name
+        assert bits(o[w.numel():]).eq(SENTINEL).all(), name + ": sentinel overwritten"
+    # rejected before any launch
+    lib = L_.load()
+    args = [L_.ptr(x) for x in ins]
+    assert lib.smin_pair_assemble(L_.stream(), *args, P, nv, nq, T, Nq, D + 2, *[L_.ptr(o) for o in outs]) != 0
+    assert lib.smin_pair_assemble(L_.stream(), *args, 0, nv, nq, T, Nq, D, *[L_.ptr(o) for o in outs]) != 0
+    assert lib.smin_pair_assemble(L_.stream(), None, *args[1:], P, nv, nq, T, Nq, D, *[L_.ptr(o) for o in outs]) != 0
+
+
+def random_lists(per_query, kv, seed, garbage):
+    """top_moments-shaped lists of sum(per_query) pairs: scores from eight values (both zeros among them), counts in [0, kv], distinct
+    videos within a query, `garbage` in the slots behind each count"""
+    g = torch.Generator().manual_seed(seed)
+    P = sum(per_query)
+    values = torch.tensor([0.9, 0.5, 0.25, 0.125, 0.0, -0.0, 0.75, 1e-3])
+    score = values[torch.randint(0, 8, (P, kv), generator=g)]
+    idx = torch.randint(0, 64, (P, kv, 2), generator=g, dtype=torch.int64)
+    count = torch.randint(0, kv + 1, (P,), generator=g, dtype=torch.int32)
+    if P:
+        count[0] = kv
+    video = torch.cat([torch.randperm(max(n, 1) + 5, generator=g)[:n] for n in per_query]).to(torch.int32) if P else torch.zeros(0, dtype=torch.int32)
+    ptr = torch.tensor(np.concatenate([[0], np.cumsum(per_query)]), dtype=torch.int32)
+    unused = torch.arange(kv).unsqueeze(0) >= count.unsqueeze(1)
+    score = torch.where(unused, torch.full_like(score, garbage), score)
+    idx = torch.where(unused.unsqueeze(2), torch.full_like(idx, 777 if garbage == garbage else -5), idx)
+    return score, idx, count, video, ptr
+
+
+def same_merge(got, want, what=""):
+    for key in ("video", "idx", "count"):
+        assert torch.equal(got[key].cpu(), want[key]), (what, key)
+    assert torch.equal(bits(got["score"]), bits(want["score"])), (what, "score")
+    assert got["video"].dtype == torch.int64 and got["idx"].dtype == torch.int64 and got["count"].dtype == torch.int32
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("K", [1, 5, 64])
+def test_corpus_topk_small(dev, K):
+    A = V()
+    a = random_lists([0, 1, 7, 3], 3, seed=11, garbage=float("nan"))
+    b = random_lists([0, 1, 7, 3], 3, seed=11, garbage=1e30)
+    assert (a[2] < 3).any() and (a[2] == 3).any()
+    want = A.corpus_topk_torch(*a, k=K)
+    assert want["count"].tolist() == [min(K, int(a[2][a[4][q]:a[4][q + 1]].sum())) for q in range(4)]
+    for name, x in (("nan", a), ("huge", b)):
+        got = A.corpus_topk(*[t.to(dev) for t in x], k=K)
+        same_merge(got, want, name)                                                  # the garbage behind the counts does not matter
+
+
+@pytest.mark.gpu
+def test_corpus_topk_many_pairs_and_none(dev):
+    A = V()
+    a = random_lists([700], 5, seed=5, garbage=float("nan"))
+    assert int(a[2].sum()) > 1024
+    same_merge(A.corpus_topk(*[t.to(dev) for t in a], k=64), A.corpus_topk_torch(*a, k=64), "700 pairs")
+    e = random_lists([0], 5, seed=1, garbage=0.0)
+    assert e[0].shape == (0, 5)
+    got = A.corpus_topk(*[t.to(dev) for t in e], k=5)
+    same_merge(got, A.corpus_topk_torch(*e, k=5), "no pairs")
+    assert got["count"].tolist() == [0] and got["video"].eq(-1).all() and got["idx"].eq(-1).all() and got["score"].eq(0).all()
+    # rejected before any launch
+    L_ = A._lib
+    t = [x.to(dev) for x in a]
+    outs = [torch.empty(1, 64, dtype=torch.int64, device=dev), torch.empty(1, 64, 2, dtype=torch.int64, device=dev),
+            torch.empty(1, 64, device=dev), torch.empty(1, dtype=torch.int32, device=dev)]
+    p = [L_.ptr(x) for x in t]
+    o = [L_.ptr(x) for x in outs]
+    lib = L_.load()
+    assert lib.smin_corpus_topk(L_.stream(), *p, 1, 5, 65, *o) != 0
+    assert lib.smin_corpus_topk(L_.stream(), *p, 1, 0, 5, *o) != 0
+    assert lib.smin_corpus_topk(L_.stream(), *p, -1, 5, 5, *o) != 0
+    assert lib.smin_corpus_topk(L_.stream(), *p[:4], None, 1, 5, 5, *o) != 0
+    assert lib.smin_corpus_topk(L_.stream(), *p, 1, 5, 5, None, *o[1:]) != 0
+
+
+def build_model(cfg, sd, dev):
+    import models
+    m = models.SMIN(cfg["T"], cfg["L"], cfg["C"], cfg["D"], cfg["dl"], cfg["layers"], cfg["Din"], cfg["Nq"], cfg["H"], dev)
+    m.load_state_dict(sd, strict=True)
+    return m.to(dev)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", H.TINY)
+def test_identity_banks_are_score(dev, name):
+    cfg, sd, batch, _, _, _ = H.split_tiny(H.load_npz(name))
+    m = build_model(cfg, sd, dev)
+    xs = H.model_inputs({k: v.to(dev) for k, v in batch.items()})
+    B = xs[0].shape[0]
+    want = m.score(*xs)
+    vb = m.encode_videos(xs[0], xs[1], xs[4], xs[5])
+    qb = m.encode_queries(xs[2], xs[3])
+    assert vb.cell_counts == tuple(batch["moment_mask"].reshape(B, -1).sum(1).tolist()) and len(vb) == len(qb) == B
+    print(name, "plan", m._plan(xs[0], xs[2]), "bank", None if vb.fv is None else tuple(vb.fv.shape))
+    got = m.score_pairs(vb, qb, list(range(B)), list(range(B)))
+    for key, g, w in zip(("pm", "ps", "pe", "pa"), got, want):
+        assert g.shape == w.shape and g.dtype == torch.float32 and g.is_contiguous() and not g.requires_grad
+        assert torch.equal(bits(g), bits(w)), key
+    assert int(V()._lib.load_torch().layout_status(dev)[0]) == 0
+
+
+@pytest.fixture(scope="module")
+def corpus(dev):
+    """the tiny model, V = 5 / Q = 4 banks, all 20 pairs query-major, the oracle's scores of the expanded batch (computed once)"""
+    from oracle import smin_oracle as O
+    m, sd = tiny_model(dev)
+    vid, qry = corpus_inputs()
+    qi, vi = np.repeat(np.arange(4), 5), np.tile(np.arange(5), 4)
+    with torch.no_grad():
+        ref = O.smin_forward(sd, dict(T=16, L=8, C=4), *expand(vid, qry, vi, qi))
+    vid_d, qry_d = {k: v.to(dev) for k, v in vid.items()}, {k: v.to(dev) for k, v in qry.items()}
+    vb = m.encode_videos(vid_d["video_features"], vid_d["video_mask"], vid_d["length_mask"], vid_d["moment_mask"])
+    qb = m.encode_queries(qry_d["query_features"], qry_d["query_mask"])
+    return dict(m=m, vid=vid, qry=qry, vid_d=vid_d, qry_d=qry_d, vb=vb, qb=qb, vi=vi, qi=qi, ref=[r.detach() for r in ref])
+
+
+@pytest.mark.gpu
+def test_shared_banks_against_oracle(dev, corpus):
+    c = corpus
+    m = c["m"]
+    assert m._plan(c["vid_d"]["video_features"], c["qry_d"]["query_features"]) == "node" and c["vb"].fv is not None
+    assert tuple(c["vb"].fv.shape) == (5, 16, 32) and tuple(c["qb"].fw.shape) == (4, 5, 32) and tuple(c["qb"].fs.shape) == (4, 32)
+    assert c["vb"].cell_counts == (36, 1, 15, 36, 6)
+    got = m.score_pairs(c["vb"], c["qb"], c["vi"], c["qi"])
+    base = m.score(*expand(c["vid_d"], c["qry_d"], c["vi"], c["qi"]))
+    mm = c["vid"]["moment_mask"][torch.as_tensor(c["vi"])]
+    for key, g, b, r in zip(("pm", "ps", "pe", "pa"), got, base, c["ref"]):
+        err, err_score = (g.cpu() - r).abs().max().item(), (b.cpu() - r).abs().max().item()
+        print(V().get_gemm_mode(), key, "score_pairs vs oracle", err, "score on the expanded batch vs oracle", err_score)
+        assert g.shape == r.shape
+        assert err < max(SCORE_TOL, 2 * err_score), (key, err, err_score)
+    assert got[0].cpu()[~mm].abs().max().item() == 0.0
+    assert m.known_cell_count is None
+
+
+def searched(c, **kw):
+    m = c["m"]
+    scorer = lambda vi, qi: m.score_pairs(c["vb"], c["qb"], vi, qi)
+    return m.search(c["vb"], c["qb"], **kw), m.search_torch(c["vb"], c["qb"], scorer=scorer, **kw)
+
+
+def same_search(got, want, Q, k):
+    assert set(got) == set(want)
+    assert got["video"].shape == (Q, k) and got["idx"].shape == (Q, k, 2) and got["score"].shape == (Q, k) and got["count"].shape == (Q,)
+    same_merge(got, {key: v.cpu() for key, v in want.items()})
+    if "times" in want:
+        assert torch.equal(torch.isnan(got["times"]).cpu(), torch.isnan(want["times"]).cpu())
+        assert torch.equal(bits(torch.nan_to_num(got["times"])), bits(torch.nan_to_num(want["times"])))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("max_batch", [7, 64])
+def test_search_end_to_end(dev, corpus, max_batch):
+    c = corpus
+    duration = torch.tensor([10.0, 3.5, 60.0, 7.25, 100.0])
+    got, want = searched(c, k=5, k_video=3, duration=duration, max_batch=max_batch)
+    same_search(got, want, 4, 5)
+    assert got["count"].tolist() == [5, 5, 5, 5]
+    # the times follow top_moments' formula on the moment's own video
+    vid, idx = got["video"].cpu(), got["idx"].cpu()
+    edge = idx.to(torch.float32) + torch.tensor([0.0, 1.0])
+    t = edge * duration[vid.clamp_min(0)].reshape(4, 5, 1) / 8
+    assert torch.equal(got["times"].cpu(), t)
+    # every listed moment is a kept moment of its pair, and the list is ordered
+    s = got["score"].cpu()
+    assert (s[:, :-1] >= s[:, 1:]).all()
+    # ... and equals the plain restatement on score()'s own scores of the expanded pairs up to their rounding
+    plain = c["m"].search_torch(c["vb"], c["qb"], k=5, k_video=3, max_batch=max_batch)
+    assert (plain["score"].cpu() - s).abs().max().item() < 2 * SCORE_TOL
+
+
+@pytest.mark.gpu
+def test_search_listed_pairs(dev, corpus):
+    c = corpus
+    pairs = np.array([(3, 4), (0, 2), (3, 0), (2, 1), (0, 0)])                      # query 1 has no pair; video 1 has one valid cell
+    got, want = searched(c, pairs=pairs, k=5, k_video=3, duration=torch.arange(1.0, 6.0), max_batch=2)
+    same_search(got, want, 4, 5)
+    assert got["count"].tolist()[1] == 0 and got["count"].tolist()[2] == 1
+    assert got["video"][1].eq(-1).all() and got["idx"][1].eq(-1).all() and got["score"][1].eq(0).all() and torch.isnan(got["times"][1]).all()
+    assert got["video"][2].tolist() == [1, -1, -1, -1, -1] and torch.isnan(got["times"][2, 1:]).all()
+    assert set(got["video"][0].tolist()) <= {0, 2} and set(got["video"][3].tolist()) <= {0, 4}
+    empty = c["m"].search(c["vb"], c["qb"], pairs=np.zeros((0, 2), dtype=np.int64), k=2)
+    assert empty["count"].tolist() == [0] * 4 and empty["video"].eq(-1).all()
+
+
+@pytest.mark.gpu
+def test_search_reads_nothing_back(dev, corpus):
+    c = corpus
+    m = c["m"]
+    kw = dict(k=5, k_video=3, max_batch=7, duration=torch.ones(5, device=dev))
+    first = m.search(c["vb"], c["qb"], **kw)                                         # first use outside the checked region
+    torch.cuda.synchronize()
+    mode = torch.cuda.get_sync_debug_mode()
+    torch.cuda.set_sync_debug_mode("error")
+    try:
+        second = m.search(c["vb"], c["qb"], **kw)
+        m.score_pairs(c["vb"], c["qb"], [0, 4, 4], [3, 3, 0])
+    finally:
+        torch.cuda.set_sync_debug_mode(mode)
+    same_merge(second, {k: v.cpu() for k, v in first.items()})
+    assert int(V()._lib.load_torch().layout_status(dev)[0]) == 0
+
+
+@pytest.mark.gpu
+def test_search_falls_back_with_keep_attention(dev, corpus):
+    c = corpus
+    m = c["m"]
+    m.keep_attention = True
+    try:
+        got, want = searched(c, k=5, k_video=3, max_batch=7, duration=torch.ones(5))
+        pm = m.score_pairs(c["vb"], c["qb"], c["vi"], c["qi"])[0]
+        assert tuple(m.smis[0].content_unit.attn_layer.attn_weights.shape) == (20, 8, 8, 4, 5)       # the forward ran, on the expanded pairs
+    finally:
+        m.keep_attention = False
+    same_search(got, want, 4, 5)
+    assert set(got) == {"video", "idx", "score", "count", "times"}
+    err = (pm.cpu() - c["ref"][0]).abs().max().item()
+    print("fall-back pm vs oracle", err)
+    assert err < SCORE_TOL
+
+
+@pytest.mark.gpu
+def test_search_repeats_bit_for_bit(dev, corpus):
+    c = corpus
+    runs = [c["m"].search(c["vb"], c["qb"], k=5, k_video=3, max_batch=7) for _ in range(5)]
+    for r in runs[1:]:
+        same_merge(r, {k: v.cpu() for k, v in runs[0].items()})
+
+
+@pytest.mark.gpu
+def test_nothing_else_moved(dev):
+    A = V()
+    cfg, sd, batch, _, _, _ = H.split_tiny(H.load_npz(H.TINY[0]))
+    m = build_model(cfg, sd, dev)
+    b = {k: v.to(dev) for k, v in batch.items()}
+    xs = H.model_inputs(b)
+
+    def step():
+        m.zero_grad(set_to_none=True)
+        out = m(*xs)
+        A.loss_fn(out[0], b["ym"], b["sm"], b["moment_mask"], out[1], b["ys"], b["ss"], out[2], b["ye"], b["se"], out[3], b["ya"], b["length_mask"]).backward()
+        torch.cuda.synchronize()
+        return [bits(t) for t in m.score(*xs)] + [bits(t) for t in out] + [bits(p.grad) for p in m.parameters()]
+
+    before = step()
+    vb, qb = m.encode_videos(xs[0], xs[1], xs[4], xs[5]), m.encode_queries(xs[2], xs[3])
+    r = m.search(vb, qb, k=3, max_batch=3)
+    assert r["count"].shape == (xs[0].shape[0],)
+    after = step()
+    assert len(before) == len(after) and all(torch.equal(x, y) for x, y in zip(before, after))

@@ -121,6 +121,8 @@ SIGNATURES = {
     "smin_row_adam_step": [_vp] * 8 + [_i] * 3 + [_vp] * 2 + [_d] * 3 + [_i],
     "smin_row_lists_merge_workspace_bytes": [_i, _i],
     "smin_row_lists_merge": [_vp] * 5 + [_i] * 3 + [_vp] * 5 + [_vp, _sz],
+    "smin_pair_assemble": [_vp] * 6 + [_i] * 6 + [_vp] * 3,
+    "smin_corpus_topk": [_vp] * 6 + [_i] * 3 + [_vp] * 4,
 }
 _RESTYPE = {"smin_target_arch": ctypes.c_char_p, "smin_workspace_bytes": _sz,
             "smin_content_attn_bwd_workspace_bytes": _sz, "smin_linear_rows_bwd_workspace_bytes": _sz,
@@ -175,9 +177,10 @@ _torch_ops = None
 
 
 def load_torch():
-    """The torch-extension binding (csrc/torch_binding.cpp): registers torch.ops.smin_hip.{smin_forward, smin_score, smin_loss, adam_step} --
-    the whole forward as one library call with its autograd graph built in C++, its forward-only scoring twin, and the optimizer step over
-    a parameter list.  Raises if the library is missing."""
+    """The torch-extension binding (csrc/torch_binding.cpp): registers torch.ops.smin_hip.{smin_forward, smin_score, smin_loss, adam_step,
+    smin_encode_videos, smin_encode_queries, smin_score_pairs} -- the whole forward as one library call with its autograd graph built in
+    C++, its forward-only scoring twin, the optimizer step over a parameter list, and the corpus-search operators (the two encoders
+    alone and the scorer over indexed pairs of their banks).  Raises if the library is missing."""
     global _torch_ops
     if _torch_ops is not None:
         return _torch_ops

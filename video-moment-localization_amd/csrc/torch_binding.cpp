@@ -333,6 +333,54 @@ Tensor sum_list(const std::vector<Tensor>& ts)
     return out;
 }
 
+// smin_score_pairs: the backbone's outputs of V videos and Q queries, each encoded once (smin_encode_videos / smin_encode_queries), and
+// the P (video, query) pairs to score: vi / qi [P] int32 on the device
+struct PairBank { Tensor fv, fw, fs, vi, qi; };
+
+// The query encoder (models.py:38-62): both BiLSTM layers' operand layouts in one launch, the two recurrences, f_w padded to
+// max_query_length and the sentence feature f_s.  The layers' tensors that a backward reads stay in `lstm` (scoring: dropped).
+std::pair<Tensor, Tensor> query_encoder(LstmState (&lstm)[2], const std::vector<Tensor>& all, const Tensor& query_features, const Tensor& len32, int64_t maxq,
+                                        int64_t H, bool scoring)
+{
+    const auto opt = query_features.options();
+    Tensor x = cont(query_features);
+    const int64_t Bq = x.size(0), Nq_in = x.size(1);
+    const int B = i32(Bq);
+    // both layers' operand layouts in one launch, ahead of the first recurrence (a launch per layer sat between the two)
+    Tensor lstm_bias[2], lstm_W4[2];
+    {
+        const float* raw[16]; int ins[2]; float *wih[2], *bs[2], *whh[2], *w4[2];
+        for (int layer = 0; layer < 2; ++layer) {
+            LstmState& ls = lstm[layer];
+            const int64_t In = layer == 0 ? x.size(2) : 2 * H;
+            ls.Wih = at::empty({8 * H, In}, opt);                              // [w_ih; w_ih_reverse]
+            lstm_bias[layer] = at::empty({8 * H}, opt);                        // b_ih + b_hh per direction
+            ls.Whh = at::empty({2, 4 * H, H}, opt);
+            lstm_W4[layer] = at::empty({2, H, H, 4}, opt);                     // [d, k, u, gate]
+            for (int q = 0; q < 8; ++q) raw[8 * layer + q] = fp(all[P_LSTM + 8 * layer + q]);
+            ins[layer] = i32(In); wih[layer] = fpm(ls.Wih); bs[layer] = fpm(lstm_bias[layer]); whh[layer] = fpm(ls.Whh); w4[layer] = fpm(lstm_W4[layer]);
+        }
+        SMIN_CK(smin_lstm_pack_layers(cur(), 2, raw, ins, i32(H), wih, bs, whh, w4));
+    }
+    for (int layer = 0; layer < 2; ++layer) {
+        LstmState& ls = lstm[layer];
+        const int In = i32(x.size(2)), Hh = i32(H);
+        ls.x = x;
+        const Tensor &bias = lstm_bias[layer], &W4 = lstm_W4[layer];
+        ls.G = at::empty({Bq, Nq_in, 2, 4 * H}, opt); ls.Hout = at::empty({Bq, Nq_in, 2 * H}, opt); ls.Cs = at::empty({Bq, Nq_in, 2, H}, opt);
+        SMIN_CK(smin_bilstm_layer_fwd(cur(), fp(x), fp(ls.Wih), fp(bias), fp(W4), ip(len32), B, i32(Nq_in), In, Hh, fpm(ls.G), fpm(ls.Hout), fpm(ls.Cs)));
+        x = ls.Hout;
+    }
+    if (scoring)                                                               // (main-stream tensors that only the backward reads)
+        for (auto& l : lstm) { l.G = Tensor(); l.Cs = Tensor(); }
+    Tensor fw = x;
+    if (Nq_in < maxq) fw = at::constant_pad_nd(fw, {0, 0, 0, maxq - Nq_in}, 0);
+    fw = fw.contiguous();
+    Tensor fs = at::empty({Bq, 2 * H}, opt);                                    // [h_fwd at the last word | h_bwd at the first word]
+    SMIN_CK(smin_sentence_feature_fwd(cur(), fp(fw), ip(len32), B, i32(fw.size(1)), i32(H), fpm(fs)));
+    return {fw, fs};
+}
+
 struct SminCore : torch::autograd::Function<SminCore> {
     // The boolean options of smin_forward (the op's keyword arguments, named as the SMIN attributes), built in smin_forward only.
     // F_KEEP_ATTENTION: every layer's word-attention maps leave as extra outputs (not differentiable; the backward ignores them):
@@ -348,15 +396,18 @@ struct SminCore : torch::autograd::Function<SminCore> {
     // layer ends in smin_score_tail_fwd instead of its content-stream sum, pair product, moment unit and smin_score_map_fwd).
     // Fills st.pm / st.psea, the contiguous parameters `all` and the attention maps; returns the number of cells.
     // n_known: the number of valid cells of moment_mask when the caller knows it, else -1
+    // bank (scoring only): the backbone's outputs come from the banks through smin_pair_assemble instead of the two encoders --
+    // video_features / query_features are unused and the four masks are the pairs' (gathered by the caller)
     static int64_t run(CoreState& st, std::vector<Tensor>& all, std::vector<Tensor>& cmaps, std::vector<Tensor>& bmaps, bool scoring, const Tensor& video_features,
                        const Tensor& video_mask, const Tensor& query_features, const Tensor& query_mask, const Tensor& length_mask, const Tensor& moment_mask, int64_t T,
-                       int64_t L, int64_t C, int64_t nl, int64_t maxq, int64_t H, int64_t flags, int64_t n_known, at::TensorList prm_in)
+                       int64_t L, int64_t C, int64_t nl, int64_t maxq, int64_t H, int64_t flags, int64_t n_known, at::TensorList prm_in, const PairBank* bank = nullptr)
     {
+        TORCH_CHECK(!bank || scoring, "banks are scored, not trained through");
         for (const Tensor& p : prm_in) all.push_back(cont(p));
         std::vector<Tensor> prm(all.begin() + P_LAYER0, all.end());                // the SMI layers' and the localization head's parameters
-        const at::Device dev = video_features.device();
-        const auto opt = video_features.options();
-        const int64_t Bq = video_features.size(0), Tn = video_features.size(1), Nq_in = query_features.size(1);
+        const at::Device dev = bank ? bank->fv.device() : video_features.device();
+        const auto opt = bank ? bank->fv.options() : video_features.options();
+        const int64_t Bq = bank ? bank->vi.size(0) : video_features.size(0), Tn = bank ? bank->fv.size(1) : video_features.size(1);
         TORCH_CHECK(Tn == T, "ProposalGeneration was built for T=", T, " but got ", Tn, " frames");
         const int B = i32(Bq), D = i32(all[P_VE_W].size(0)), Nq = i32(maxq), dl = i32(prm[L_CH_W].size(0)), Li = i32(L), Ci = i32(C), Ti = i32(T);
         auto lp = [&](int64_t k, int which) -> const Tensor& { return prm[k * L_COUNT + which]; };
@@ -463,11 +514,13 @@ struct SminCore : torch::autograd::Function<SminCore> {
         // sentence feature (models.py:81-83) waits for the LSTM layers (the fused call sat behind them: ~90 us of the step's opening chain).
         // Queued behind the parameter products: ahead of them it runs beside the LSTM operand packing and the first recurrence and
         // stretches both (pack 20 -> 84 us, recurrence 87 -> 130 us: the opening chain 45 us longer, tools/gantt.sh).
-        st.vx = cont(video_features);
-        st.fv = at::empty({Bq, T, (int64_t)D}, opt);
-        Tensor f = at::empty({Bq, T, (int64_t)D}, opt);
+        if (!bank) {
+            st.vx = cont(video_features);
+            st.fv = at::empty({Bq, T, (int64_t)D}, opt);
+        }
+        Tensor f = at::empty({Bq, T, (int64_t)D}, opt), fw, fs;
         hipEvent_t projection_ready = nullptr;
-        if (prep != curs) {
+        if (!bank && prep != curs) {
             await(prep, count_ready);                                              // (vmaskf)
             StreamScope sc(prep);
             SMIN_CK(smin_video_encoder_fwd(cur(), fp(st.vx), fp(all[P_VE_W]), fp(all[P_VE_B]), fp(all[P_PE]), fp(st.vmaskf), nullptr, B, Ti, i32(st.vx.size(2)), D, fpm(st.fv),
@@ -476,44 +529,19 @@ struct SminCore : torch::autograd::Function<SminCore> {
         }
 
         // ---- backbone (models.py:38-83): BiLSTM x 2, sentence feature, fused video encoder
-        Tensor x = cont(query_features);
-        // both layers' operand layouts in one launch, ahead of the first recurrence (a launch per layer sat between the two)
-        Tensor lstm_bias[2], lstm_W4[2];
-        {
-            const float* raw[16]; int ins[2]; float *wih[2], *bs[2], *whh[2], *w4[2];
-            for (int layer = 0; layer < 2; ++layer) {
-                LstmState& ls = st.lstm[layer];
-                const int64_t In = layer == 0 ? x.size(2) : 2 * H;
-                ls.Wih = at::empty({8 * H, In}, opt);                              // [w_ih; w_ih_reverse]
-                lstm_bias[layer] = at::empty({8 * H}, opt);                        // b_ih + b_hh per direction
-                ls.Whh = at::empty({2, 4 * H, H}, opt);
-                lstm_W4[layer] = at::empty({2, H, H, 4}, opt);                     // [d, k, u, gate]
-                for (int q = 0; q < 8; ++q) raw[8 * layer + q] = fp(all[P_LSTM + 8 * layer + q]);
-                ins[layer] = i32(In); wih[layer] = fpm(ls.Wih); bs[layer] = fpm(lstm_bias[layer]); whh[layer] = fpm(ls.Whh); w4[layer] = fpm(lstm_W4[layer]);
-            }
-            SMIN_CK(smin_lstm_pack_layers(cur(), 2, raw, ins, i32(H), wih, bs, whh, w4));
-        }
-        for (int layer = 0; layer < 2; ++layer) {
-            LstmState& ls = st.lstm[layer];
-            const int In = i32(x.size(2)), Hh = i32(H);
-            ls.x = x;
-            const Tensor &bias = lstm_bias[layer], &W4 = lstm_W4[layer];
-            ls.G = at::empty({Bq, Nq_in, 2, 4 * H}, opt); ls.Hout = at::empty({Bq, Nq_in, 2 * H}, opt); ls.Cs = at::empty({Bq, Nq_in, 2, H}, opt);
-            SMIN_CK(smin_bilstm_layer_fwd(cur(), fp(x), fp(ls.Wih), fp(bias), fp(W4), ip(st.len32), B, i32(Nq_in), In, Hh, fpm(ls.G), fpm(ls.Hout), fpm(ls.Cs)));
-            x = ls.Hout;
-        }
-        if (scoring)                                                               // (main-stream tensors that only the backward reads)
-            for (auto& l : st.lstm) { l.G = Tensor(); l.Cs = Tensor(); }
-        Tensor fw = x;
-        if (Nq_in < maxq) fw = at::constant_pad_nd(fw, {0, 0, 0, maxq - Nq_in}, 0);
-        fw = fw.contiguous();
-        Tensor fs = at::empty({Bq, 2 * H}, opt);                                    // [h_fwd at the last word | h_bwd at the first word]
-        SMIN_CK(smin_sentence_feature_fwd(cur(), fp(fw), ip(st.len32), B, i32(fw.size(1)), i32(H), fpm(fs)));
-        if (projection_ready) {
-            await(curs, projection_ready);
-            SMIN_CK(smin_video_encoder_gate(cur(), fp(st.fv), fp(fs), B, Ti, D, fpm(f)));
+        if (bank) {
+            // both encoders ran once per video and per query: the pairs' f = f_v * f_s, f_w and f_s in one launch (csrc/corpus.hip)
+            fw = at::empty({Bq, maxq, (int64_t)D}, opt); fs = at::empty({Bq, (int64_t)D}, opt);
+            SMIN_CK(smin_pair_assemble(cur(), fp(bank->fv), fp(bank->fs), fp(bank->fw), ip(bank->vi), ip(bank->qi), B, i32(bank->fv.size(0)), i32(bank->fs.size(0)), Ti, Nq,
+                                       D, fpm(f), fpm(fw), fpm(fs)));
         } else {
-            SMIN_CK(smin_video_encoder_fwd(cur(), fp(st.vx), fp(all[P_VE_W]), fp(all[P_VE_B]), fp(all[P_PE]), fp(st.vmaskf), fp(fs), B, Ti, i32(st.vx.size(2)), D, fpm(st.fv), fpm(f)));
+            std::tie(fw, fs) = query_encoder(st.lstm, all, query_features, st.len32, maxq, H, scoring);
+            if (projection_ready) {
+                await(curs, projection_ready);
+                SMIN_CK(smin_video_encoder_gate(cur(), fp(st.fv), fp(fs), B, Ti, D, fpm(f)));
+            } else {
+                SMIN_CK(smin_video_encoder_fwd(cur(), fp(st.vx), fp(all[P_VE_W]), fp(all[P_VE_B]), fp(all[P_PE]), fp(st.vmaskf), fp(fs), B, Ti, i32(st.vx.size(2)), D, fpm(st.fv), fpm(f)));
+            }
         }
 
         // ---- layout, part 2
@@ -1315,6 +1343,86 @@ std::tuple<Tensor, Tensor, Tensor, Tensor> smin_score(
     return std::make_tuple(st.pm, st.psea[0], st.psea[1], st.psea[2]);
 }
 
+// ---- corpus search (SMIN.encode_videos / encode_queries / score_pairs): the two encoders once per video and per
+// query, then the model from the Hadamard product on for any list of (video, query) pairs.  Forward only.
+
+// f_v (V, T, D) = the projection with position embedding and mask (models.py:25-36): smin_forward's call with fs == NULL
+Tensor smin_encode_videos(const Tensor& video_features, const Tensor& video_mask, at::TensorList prm)
+{
+    TORCH_CHECK(video_features.is_cuda() && video_mask.is_cuda(), "smin_encode_videos runs on a HIP device only (there is no CPU fallback)");
+    at::NoGradGuard no_grad;
+    TORCH_CHECK(video_features.dim() == 3 && video_features.scalar_type() == at::kFloat, "smin_encode_videos: video_features float32 (V, T, Din)");
+    TORCH_CHECK((int64_t)prm.size() >= P_LSTM, "smin_encode_videos: the parameter list starts with the video encoder's three");
+    const int64_t V = video_features.size(0), T = video_features.size(1), Din = video_features.size(2);
+    Tensor W = cont(prm[P_VE_W].detach()), bias = cont(prm[P_VE_B].detach()), pe = cont(prm[P_PE].detach());
+    const int64_t D = W.size(0);
+    TORCH_CHECK(W.dim() == 2 && W.size(1) == Din && bias.numel() == D && pe.dim() == 2 && pe.size(1) == D && pe.size(0) >= T && video_mask.numel() == V * T,
+                "smin_encode_videos: shapes of the video encoder's parameters or of video_mask do not fit video_features");
+    c10::hip::HIPGuard device_guard(video_features.device().index());
+    Tensor vx = cont(video_features.detach());
+    Tensor vm = video_mask.reshape({V * T});
+    Tensor vmaskf = cont(vm.is_floating_point() ? fl(vm) : vm.ne(0).to(at::kFloat));
+    Tensor fv = at::empty({V, T, D}, vx.options());
+    SMIN_CK(smin_video_encoder_fwd(cur(), fp(vx), fp(W), fp(bias), fp(pe), fp(vmaskf), nullptr, i32(V), i32(T), i32(Din), i32(D), fpm(fv), nullptr));
+    return fv;
+}
+
+// (f_w (Q, max_query_length, D), f_s (Q, D)): pack, the two smin_bilstm_layer_fwd calls and smin_sentence_feature_fwd, as smin_forward issues them
+std::tuple<Tensor, Tensor> smin_encode_queries(const Tensor& query_features, const Tensor& query_mask_in, at::TensorList prm, int64_t max_query_length,
+                                               int64_t lstm_hidden_size)
+{
+    TORCH_CHECK(query_features.is_cuda() && query_mask_in.is_cuda(), "smin_encode_queries runs on a HIP device only (there is no CPU fallback)");
+    at::NoGradGuard no_grad;
+    TORCH_CHECK(query_features.scalar_type() == at::kFloat, "smin_encode_queries: query_features float32 (Q, words, dim)");
+    TORCH_CHECK((int64_t)prm.size() >= P_LAYER0, "smin_encode_queries: the parameter list starts with the video encoder's three and the LSTM's sixteen");
+    Tensor query_mask = padded_query_mask("smin_encode_queries", query_features, query_mask_in, max_query_length);
+    c10::hip::HIPGuard device_guard(query_features.device().index());
+    std::vector<Tensor> all;
+    for (int64_t i = 0; i < P_LAYER0; ++i) all.push_back(cont(prm[i].detach()));
+    Tensor len32 = query_mask.ne(0).sum(1).to(at::kInt).contiguous();
+    LstmState lstm[2];
+    auto out = query_encoder(lstm, all, query_features.detach(), len32, max_query_length, lstm_hidden_size, true);
+    return std::make_tuple(out.first, out.second);
+}
+
+// SMIN.score_pairs: smin_score for the P pairs (video_index[p], query_index[p]) of banks fv / fw / fs.  The four byte masks are gathered
+// per pair, smin_step_prologue runs on the gathered masks, smin_pair_assemble stands where smin_score has its backbone, and from
+// "layout, part 2" on it is the code smin_score runs (SminCore::run).  Outputs as smin_score's, one row per pair.
+std::tuple<Tensor, Tensor, Tensor, Tensor> smin_score_pairs(
+    const Tensor& fv, const Tensor& fw, const Tensor& fs, const Tensor& video_mask, const Tensor& query_mask_in, const Tensor& length_mask, const Tensor& moment_mask,
+    const Tensor& video_index, const Tensor& query_index, at::TensorList prm, int64_t T, int64_t L, int64_t C, int64_t num_smi_layers, int64_t max_query_length,
+    int64_t lstm_hidden_size, bool overlap_boundary, bool overlap_prep, bool param_prep_kernel, bool bf16_operand_storage, std::optional<int64_t> known_cell_count)
+{
+    for (const Tensor* t : {&fv, &fw, &fs, &video_mask, &query_mask_in, &length_mask, &moment_mask, &video_index, &query_index})
+        TORCH_CHECK(t->is_cuda(), "smin_score_pairs runs on a HIP device only (there is no CPU fallback)");
+    at::NoGradGuard no_grad;
+    const int64_t nl = num_smi_layers, maxq = max_query_length;
+    TORCH_CHECK((int64_t)prm.size() == P_LAYER0 + nl * L_COUNT + 8, "smin_score_pairs: expected ", P_LAYER0 + nl * L_COUNT + 8, " parameters, got ", prm.size());
+    TORCH_CHECK(fv.dim() == 3 && fw.dim() == 3 && fs.dim() == 2 && fv.scalar_type() == at::kFloat && fw.scalar_type() == at::kFloat && fs.scalar_type() == at::kFloat,
+                "smin_score_pairs: fv (V, T, D), fw (Q, max_query_length, D), fs (Q, D) float32");
+    const int64_t V = fv.size(0), Q = fs.size(0), D = fv.size(2);
+    TORCH_CHECK(V >= 1 && Q >= 1 && fv.size(1) == T && fw.size(0) == Q && fw.size(1) == maxq && fw.size(2) == D && fs.size(1) == D && D == 2 * lstm_hidden_size,
+                "smin_score_pairs: the banks do not fit each other or the model (T = ", T, ", max_query_length = ", maxq, ", D = ", 2 * lstm_hidden_size, ")");
+    TORCH_CHECK(video_index.dim() == 1 && query_index.dim() == 1 && video_index.size(0) == query_index.size(0) && video_index.size(0) >= 1,
+                "smin_score_pairs: video_index and query_index are (P,) with P >= 1");
+    TORCH_CHECK(video_mask.size(0) == V && length_mask.size(0) == V && moment_mask.size(0) == V && query_mask_in.size(0) == Q,
+                "smin_score_pairs: video_mask, length_mask and moment_mask have a row per video, query_mask a row per query");
+    Tensor query_mask = query_mask_in.reshape({Q, -1});
+    TORCH_CHECK(query_mask.size(1) == maxq, "smin_score_pairs: query_mask (Q, max_query_length) as the query bank keeps it");
+    c10::hip::HIPGuard device_guard(fv.device().index());
+    PairBank bank{cont(fv.detach()), cont(fw.detach()), cont(fs.detach()), cont(video_index.to(at::kInt)), cont(query_index.to(at::kInt))};
+    // the byte masks per pair: P * (T + Nq + L + L * L) bytes
+    Tensor vm = video_mask.index_select(0, bank.vi), qm = query_mask.index_select(0, bank.qi), lm = length_mask.index_select(0, bank.vi),
+           mm = moment_mask.index_select(0, bank.vi);
+    const int64_t flags = (overlap_boundary ? SminCore::F_OVERLAP_BOUNDARY : 0) | (overlap_prep ? SminCore::F_OVERLAP_PREP : 0) |
+                          (param_prep_kernel ? SminCore::F_PARAM_PREP_KERNEL : 0) | (bf16_operand_storage ? SminCore::F_BF16_OPERANDS : 0);
+    CoreState st;
+    std::vector<Tensor> all, cmaps, bmaps;
+    SminCore::run(st, all, cmaps, bmaps, true, Tensor(), vm, Tensor(), qm, lm, mm, T, L, C, nl, maxq, lstm_hidden_size, flags, known_cell_count.value_or(-1), prm,
+                  &bank);
+    return std::make_tuple(st.pm, st.psea[0], st.psea[1], st.psea[2]);
+}
+
 Tensor smin_loss(const Tensor& pm, const Tensor& ym, const Tensor& sm, const Tensor& moment_mask, const Tensor& ps, const Tensor& ys, const Tensor& ss, const Tensor& pe,
                  const Tensor& ye, const Tensor& se, const Tensor& pa, const Tensor& ya, const Tensor& length_mask)
 {
@@ -1387,6 +1495,13 @@ TORCH_LIBRARY(smin_hip, m)
     m.def("smin_score(Tensor video_features, Tensor video_mask, Tensor query_features, Tensor query_mask, Tensor length_mask, Tensor moment_mask, "
           "Tensor[] params, int T, int L, int C, int num_smi_layers, int max_query_length, int lstm_hidden_size, *, bool overlap_boundary, "
           "bool overlap_prep, bool param_prep_kernel, bool bf16_operand_storage, int? known_cell_count) -> (Tensor, Tensor, Tensor, Tensor)", &smin_score);
+    // corpus search: the two encoders alone, and smin_score over indexed pairs of their banks
+    m.def("smin_encode_videos(Tensor video_features, Tensor video_mask, Tensor[] params) -> Tensor", &smin_encode_videos);
+    m.def("smin_encode_queries(Tensor query_features, Tensor query_mask, Tensor[] params, int max_query_length, int lstm_hidden_size) -> (Tensor, Tensor)",
+          &smin_encode_queries);
+    m.def("smin_score_pairs(Tensor fv, Tensor fw, Tensor fs, Tensor video_mask, Tensor query_mask, Tensor length_mask, Tensor moment_mask, Tensor video_index, "
+          "Tensor query_index, Tensor[] params, int T, int L, int C, int num_smi_layers, int max_query_length, int lstm_hidden_size, *, bool overlap_boundary, "
+          "bool overlap_prep, bool param_prep_kernel, bool bf16_operand_storage, int? known_cell_count) -> (Tensor, Tensor, Tensor, Tensor)", &smin_score_pairs);
     // restated loss_fn of the reference's train loop (main.py:110-116), same argument order
     m.def("smin_loss(Tensor pm, Tensor ym, Tensor sm, Tensor moment_mask, Tensor ps, Tensor ys, Tensor ss, Tensor pe, Tensor ye, Tensor se, Tensor pa, Tensor ya, "
           "Tensor length_mask) -> Tensor", &smin_loss);

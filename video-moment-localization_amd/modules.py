@@ -44,6 +44,11 @@ def _hip_forward(fn):
     return wrapper
 
 
+def _byte_mask(mask):
+    """A mask as one byte per element (bool / uint8 as they are), contiguous: what the banks keep and the kernels gather."""
+    return (mask if mask.dtype in (torch.bool, torch.uint8) else mask != 0).contiguous()
+
+
 def _rows(mask):
     """(B, N, 1) / (B, N) 0-1 mask -> float (B, N); unlike the reference's .squeeze() this is B=1 safe."""
     return mask.reshape(mask.shape[0], -1).float()
@@ -428,6 +433,36 @@ class Localization(nn.Module):
         return self.forward_packed(layout.pack(f_m), f_b, length_mask, layout)
 
 
+class VideoBank:
+    """V videos encoded once (SMIN.encode_videos): ``fv (V, T, D)``, the video encoder's projection with position embedding and mask --
+    everything of a video the model computes before the video meets a query (f = fv * fs, reference models.py:81) --, the videos'
+    ``video_mask``, ``length_mask`` and ``moment_mask`` and ``cell_counts``, each video's number of valid cells as host ints (what
+    lets SMIN.search hand every chunk's ``known_cell_count`` to the scorer without a device read).  ``video_features`` is the input
+    itself (not a copy), kept for the configurations that score through SMIN.score.
+
+    A bank is detached and is a snapshot of the parameters at the time of the call: a parameter update (an optimizer step,
+    load_state_dict) makes it stale -- encode again.  ``fv`` is None when the call would not take the one-node path (SMIN._plan)."""
+
+    def __init__(self, fv, video_features, video_mask, length_mask, moment_mask, cell_counts):
+        self.fv, self.video_features, self.video_mask, self.length_mask, self.moment_mask = fv, video_features, video_mask, length_mask, moment_mask
+        self.cell_counts = tuple(int(c) for c in cell_counts)
+
+    def __len__(self):
+        return self.video_features.shape[0]
+
+
+class QueryBank:
+    """Q queries encoded once (SMIN.encode_queries): the query encoder's word features ``fw (Q, max_query_length, D)`` and sentence
+    features ``fs (Q, D)``, and ``query_mask (Q, max_query_length)`` padded as the kernels read it.  ``query_features`` is the input
+    itself, kept for the configurations that score through SMIN.score.  Detached; stale after a parameter update, as VideoBank."""
+
+    def __init__(self, fw, fs, query_features, query_mask):
+        self.fw, self.fs, self.query_features, self.query_mask = fw, fs, query_features, query_mask
+
+    def __len__(self):
+        return self.query_features.shape[0]
+
+
 class SMIN(nn.Module):
     """reference models.py:346-377 -- the drop-in boundary (ctor called positionally from main.py:71)."""
 
@@ -799,6 +834,217 @@ class SMIN(nn.Module):
             d = duration.to(device=dev, dtype=torch.float32).reshape(B, 1, 1)
             r["times"] = (r["span"] * d) / nr_d.to(torch.float32).reshape(B, 1, 1)
         return r
+
+    # ---------------------------------------------------------------- corpus search
+    def _bank_plan(self, video_features, query_features):
+        """Whether pairs of these inputs score on the one-node path from banks (as score(): _plan == "node" and no keep_attention)."""
+        return not self.keep_attention and self._plan(video_features, query_features) == "node"
+
+    def encode_videos(self, video_features, video_mask, length_mask, moment_mask):
+        """A VideoBank of V videos: the projection with position embedding and mask runs once per video (smin_hip::smin_encode_videos),
+        not once per (video, query) pair.  ``video_features (V, T, Din)`` and the three masks as forward takes them.  One host read
+        (the videos' valid-cell counts); under torch.no_grad().  The bank is stale after a parameter update."""
+        for name, t in (("video_features", video_features), ("video_mask", video_mask), ("length_mask", length_mask), ("moment_mask", moment_mask)):
+            if not (isinstance(t, torch.Tensor) and t.is_cuda):
+                raise SminHipError(f"encode_videos: {name} must be a HIP tensor (there is no CPU fallback)")
+        V = video_features.shape[0]
+        if video_features.dim() != 3 or V < 1 or video_mask.shape[0] != V or tuple(length_mask.shape) != (V, self.L) or tuple(moment_mask.shape) != (V, self.L, self.L):
+            raise ValueError(f"encode_videos: video_features (V, T, Din) with V >= 1, video_mask (V, T[, 1]), length_mask (V, L) and moment_mask (V, L, L); got "
+                             f"{tuple(video_features.shape)}, {tuple(video_mask.shape)}, {tuple(length_mask.shape)}, {tuple(moment_mask.shape)}")
+        from . import _lib
+        with torch.no_grad(), torch.cuda.device(video_features.device):
+            vf = video_features.detach()
+            masks = [_byte_mask(t) for t in (video_mask, length_mask, moment_mask)]
+            fv = None
+            if self.fused_core and self.backbone.videoencoder.fused(vf) and vf.shape[1] == self.T:
+                fv = _lib.load_torch().smin_encode_videos(vf, masks[0], self._native_params()[:3])
+            counts = masks[2].reshape(V, -1).ne(0).sum(dim=1).tolist()             # the bank's only host read
+        return VideoBank(fv, vf, masks[0], masks[1], masks[2], counts)
+
+    def encode_queries(self, query_features, query_mask):
+        """A QueryBank of Q queries: the two BiLSTM layers and the sentence feature run once per query
+        (smin_hip::smin_encode_queries).  ``query_features (Q, words, E)`` / ``query_mask`` as forward takes them.  No host read;
+        under torch.no_grad().  The bank is stale after a parameter update."""
+        for name, t in (("query_features", query_features), ("query_mask", query_mask)):
+            if not (isinstance(t, torch.Tensor) and t.is_cuda):
+                raise SminHipError(f"encode_queries: {name} must be a HIP tensor (there is no CPU fallback)")
+        if query_features.dim() != 3 or query_features.shape[0] < 1:
+            raise ValueError(f"encode_queries: query_features (Q, words, E) with Q >= 1 (got {tuple(query_features.shape)})")
+        qm = query_mask.reshape(query_features.shape[0], -1)
+        if qm.shape[1] != query_features.shape[1] or qm.shape[1] > self.max_query_length:
+            raise ValueError(f"query_mask has {qm.shape[1]} columns for {query_features.shape[1]} words (max_query_length {self.max_query_length})")
+        from . import _lib
+        with torch.no_grad(), torch.cuda.device(query_features.device):
+            qf = query_features.detach()
+            qm = _byte_mask(qm)
+            fw = fs = None
+            if self.fused_core and self.backbone.queryencoder.fused() and qf.dtype == torch.float32:
+                fw, fs = _lib.load_torch().smin_encode_queries(qf, qm, self._native_params()[:19], self.max_query_length, self.lstm_hidden_size)
+            if qm.shape[1] < self.max_query_length:
+                qm = torch.nn.functional.pad(qm, (0, self.max_query_length - qm.shape[1]))
+        return QueryBank(fw, fs, qf, qm)
+
+    @staticmethod
+    def _pair_lists(what, videos, queries, video_index, query_index):
+        if not isinstance(videos, VideoBank) or not isinstance(queries, QueryBank):
+            raise TypeError(f"{what}: videos is a VideoBank (encode_videos) and queries a QueryBank (encode_queries)")
+        vi = np.asarray(video_index.cpu() if isinstance(video_index, torch.Tensor) else video_index, dtype=np.int64).reshape(-1)
+        qi = np.asarray(query_index.cpu() if isinstance(query_index, torch.Tensor) else query_index, dtype=np.int64).reshape(-1)
+        if vi.shape[0] != qi.shape[0]:
+            raise ValueError(f"{what}: video_index and query_index must have one length (got {vi.shape[0]} and {qi.shape[0]})")
+        V, Q = len(videos), len(queries)
+        if vi.size and (vi.min() < 0 or vi.max() >= V or qi.min() < 0 or qi.max() >= Q):
+            raise ValueError(f"{what}: video_index must lie in [0, {V}) and query_index in [0, {Q})")
+        return vi, qi
+
+    @staticmethod
+    def _require_hip_banks(what, videos, queries):
+        for name, t in (("videos", videos.video_features), ("queries", queries.query_features)):
+            if not t.is_cuda:
+                raise SminHipError(f"{what}: {name} must hold HIP tensors (there is no CPU fallback)")
+
+    def _score_pairs(self, videos, queries, vi, qi, vi_d, qi_d):
+        """score_pairs of checked host lists vi / qi (P >= 1) whose int32 device copies are vi_d / qi_d.  No host read."""
+        known = self.known_cell_count
+        self.known_cell_count = int(sum(videos.cell_counts[v] for v in vi))       # host arithmetic: the scorer asks the device nothing
+        try:
+            with torch.no_grad(), torch.cuda.device(vi_d.device):
+                if not self._bank_plan(videos.video_features, queries.query_features):
+                    # as score(): configurations off the one-node path (and keep_attention) run the forward, here on expanded pairs
+                    qm = queries.query_mask[:, :queries.query_features.shape[1]]
+                    return self.score(videos.video_features.index_select(0, vi_d), videos.video_mask.index_select(0, vi_d),
+                                      queries.query_features.index_select(0, qi_d), qm.index_select(0, qi_d),
+                                      videos.length_mask.index_select(0, vi_d), videos.moment_mask.index_select(0, vi_d))
+                if videos.fv is None or queries.fw is None:
+                    raise ValueError("score_pairs: a bank was encoded while the module was off the one-node path (SMIN._plan); encode it again")
+                from . import _lib
+                return _lib.load_torch().smin_score_pairs(
+                    videos.fv, queries.fw, queries.fs, videos.video_mask, queries.query_mask, videos.length_mask, videos.moment_mask, vi_d, qi_d,
+                    self._native_params(), self.T, self.L, self.C, len(self.smis), self.max_query_length, self.lstm_hidden_size, **self._score_options())
+        finally:
+            self.known_cell_count = known
+
+    def score_pairs(self, videos, queries, video_index, query_index):
+        """(pm, ps, pe, pa) as score() returns them for the P pairs (videos[video_index[p]], queries[query_index[p]]) of a VideoBank
+        and a QueryBank: neither encoder runs again, and no pair carries a copy of its video's features.  ``video_index`` /
+        ``query_index``: host int sequences of one length P >= 1, any lists, repeats included; an index out of range raises
+        ValueError.  On the one-node path this is smin_hip::smin_score_pairs: the pairs' masks gathered (bytes), smin_pair_assemble
+        where smin_score has its backbone, then smin_score's own code -- the bits of score() on the expanded batch.  Where score()
+        would run the forward instead (_plan != "node", keep_attention) the pairs are expanded and scored by score().  The valid-cell
+        count comes from the bank, so nothing is read back."""
+        vi, qi = self._pair_lists("score_pairs", videos, queries, video_index, query_index)
+        if vi.shape[0] < 1:
+            raise ValueError("score_pairs: at least one pair")
+        self._require_hip_banks("score_pairs", videos, queries)
+        dev = videos.video_features.device
+        idx = torch.from_numpy(np.concatenate([vi, qi]).astype(np.int32)).pin_memory().to(dev, non_blocking=True)
+        return self._score_pairs(videos, queries, vi, qi, idx[:vi.shape[0]], idx[vi.shape[0]:])
+
+    def _search_plan(self, what, videos, queries, pairs, k, k_video, max_batch, duration):
+        from .moments import MAX_K
+        k_video = k if k_video is None else k_video
+        for name, v, lo, hi in (("k", k, 1, MAX_K), ("k_video", k_video, 1, MAX_K), ("max_batch", max_batch, 1, 65535)):
+            if not (isinstance(v, (int, np.integer)) and lo <= v <= hi):
+                raise ValueError(f"{what}: {name} must be an integer in [{lo}, {hi}] (got {v!r})")
+        if not isinstance(videos, VideoBank) or not isinstance(queries, QueryBank):
+            raise TypeError(f"{what}: videos is a VideoBank (encode_videos) and queries a QueryBank (encode_queries)")
+        V, Q = len(videos), len(queries)
+        if pairs is None:
+            qi, vi = np.repeat(np.arange(Q, dtype=np.int64), V), np.tile(np.arange(V, dtype=np.int64), Q)
+        else:
+            pr = np.asarray(pairs.cpu() if isinstance(pairs, torch.Tensor) else pairs, dtype=np.int64)
+            if pr.size == 0:
+                pr = pr.reshape(0, 2)
+            if pr.ndim != 2 or pr.shape[1] != 2:
+                raise ValueError(f"{what}: pairs must be (P, 2) rows of (query, video) (got {pr.shape})")
+            order = np.lexsort((pr[:, 1], pr[:, 0]))                               # by (query, video)
+            qi, vi = pr[order, 0], pr[order, 1]
+        vi, qi = self._pair_lists(what, videos, queries, vi, qi)
+        if vi.size > 1 and bool(((qi[1:] == qi[:-1]) & (vi[1:] == vi[:-1])).any()):
+            raise ValueError(f"{what}: a (query, video) pair is listed more than once")
+        if duration is not None and tuple(duration.shape) != (V,):
+            raise ValueError(f"{what}: duration must be (V,) = ({V},) seconds (got {tuple(duration.shape)})")
+        self._require_hip_banks(what, videos, queries)
+        pair_ptr = np.concatenate([[0], np.cumsum(np.bincount(qi, minlength=Q))]).astype(np.int64)
+        return int(k), int(k_video), vi, qi, pair_ptr
+
+    @staticmethod
+    def _search_result(r, duration, L):
+        if duration is not None:
+            # moments._times' formula on each moment's own video: (i * duration / L, (j + 1) * duration / L) in fp32, NaN for empty slots
+            # (formed without a constant from the host: the call reads and writes no host memory)
+            Q, k = r["video"].shape
+            d = duration.to(device=r["video"].device, dtype=torch.float32)[r["video"].clamp_min(0)].reshape(Q, k, 1)
+            edge = r["idx"].to(torch.float32)
+            edge[..., 1] += 1.0
+            t = edge * d / L
+            r["times"] = torch.where(r["idx"] >= 0, t, torch.full_like(t, float("nan")))
+        return r
+
+    def search(self, videos, queries, pairs=None, k=5, k_video=None, nms_thresh=0.5, duration=None, max_batch=64):
+        """Which video, and where: the k best moments of each of the Q queries of a QueryBank over the videos of a VideoBank.
+
+        ``pairs``: None -- every query against every video --, or a host (P, 2) array of (query, video) rows, in any order (sorted
+        here by (query, video)); a repeated pair raises ValueError.  The pairs are scored in chunks of at most ``max_batch``
+        (score_pairs: from the banks, no encoder runs again; each chunk's valid-cell count is the sum of the bank's cell_counts,
+        nothing is read back), each chunk is cut to its ``k_video`` (default k) best moments per pair by top_moments' kernels
+        (greedy NMS at ``nms_thresh``), and one smin_corpus_topk ranks each query's moments across its videos: higher score first,
+        ties -> lower video, then lower slot.  Every listed pair is scored by the full model.
+
+        Returns a dict: ``video (Q, k)`` int64 (-1 for empty slots), ``idx (Q, k, 2)`` int64 start / end clip (-1), ``score (Q, k)``
+        (0), ``count (Q,)`` int32; with ``duration`` (V,) seconds also ``times (Q, k, 2)``: top_moments' formula on
+        ``duration[video]``, NaN for empty slots.  Scores come from score_pairs (forward_only_scoring or not: a bank has no graph),
+        in the contraction mode of set_gemm_mode.  No host synchronisation."""
+        from .moments import corpus_topk
+        from . import _lib
+        k, k_video, vi, qi, pair_ptr = self._search_plan("search", videos, queries, pairs, k, k_video, max_batch, duration)
+        dev, L, P = videos.video_features.device, self.L, vi.shape[0]
+        # the whole plan in one pinned buffer, one asynchronous copy (the call never waits for the device)
+        plan = torch.from_numpy(np.concatenate([vi, qi, pair_ptr]).astype(np.int32)).pin_memory().to(dev, non_blocking=True)
+        vi_d, qi_d, pp_d = plan[:P], plan[P:2 * P], plan[2 * P:]
+        idx = torch.empty((P, k_video, 2), dtype=torch.int64, device=dev)
+        score = torch.empty((P, k_video), dtype=torch.float32, device=dev)
+        count = torch.empty((P,), dtype=torch.int32, device=dev)
+        with torch.no_grad(), torch.cuda.device(dev):
+            for c0 in range(0, P, max_batch):
+                c1 = min(c0 + max_batch, P)
+                pm, ps, pe, _ = self._score_pairs(videos, queries, vi[c0:c1], qi[c0:c1], vi_d[c0:c1], qi_d[c0:c1])
+                mm = videos.moment_mask.index_select(0, vi_d[c0:c1])
+                nbytes = _lib.load().smin_top_moments_ws_bytes(c1 - c0, L, k_video)
+                ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+                _lib.call("smin_top_moments", _lib.stream(), _lib.ptr(pm.contiguous()), _lib.ptr(ps.contiguous()), _lib.ptr(pe.contiguous()),
+                          _lib.ptr(mm), c1 - c0, L, k_video, float(nms_thresh), _lib.ptr(idx[c0:c1]), _lib.ptr(score[c0:c1]),
+                          _lib.ptr(count[c0:c1]), _lib.ptr(ws), nbytes)
+            r = corpus_topk(score, idx, count, vi_d, pp_d, k=k)
+        return self._search_result(r, duration, L)
+
+    def search_torch(self, videos, queries, pairs=None, k=5, k_video=None, nms_thresh=0.5, duration=None, max_batch=64, scorer=None):
+        """``search`` restated: the same plan and chunking, each chunk's pairs expanded and scored by score(), cut by top_moments and
+        merged by moments.corpus_topk_torch.  Kept under its own name as what the tests compare against -- nothing routes here.
+        ``scorer(video_index, query_index) -> (pm, ps, pe, pa)`` replaces score() on the expanded pairs (the tests feed it
+        score_pairs, to compare the ranking on equal scores)."""
+        from .moments import corpus_topk_torch, top_moments
+        k, k_video, vi, qi, pair_ptr = self._search_plan("search_torch", videos, queries, pairs, k, k_video, max_batch, duration)
+        dev, L, P = videos.video_features.device, self.L, vi.shape[0]
+        idx = torch.empty((P, k_video, 2), dtype=torch.int64, device=dev)
+        score = torch.empty((P, k_video), dtype=torch.float32, device=dev)
+        count = torch.empty((P,), dtype=torch.int32, device=dev)
+        with torch.no_grad():
+            for c0 in range(0, P, max_batch):
+                c1 = min(c0 + max_batch, P)
+                vi_d, qi_d = (torch.from_numpy(x[c0:c1].copy()).to(dev) for x in (vi, qi))
+                mm = videos.moment_mask.index_select(0, vi_d)
+                if scorer is not None:
+                    pm, ps, pe, _ = scorer(vi[c0:c1], qi[c0:c1])
+                else:
+                    qm = queries.query_mask[:, :queries.query_features.shape[1]]
+                    pm, ps, pe, _ = self.score(videos.video_features.index_select(0, vi_d), videos.video_mask.index_select(0, vi_d),
+                                               queries.query_features.index_select(0, qi_d), qm.index_select(0, qi_d),
+                                               videos.length_mask.index_select(0, vi_d), mm)
+                t = top_moments(pm, ps, pe, mm, k=k_video, nms_thresh=nms_thresh)
+                idx[c0:c1], score[c0:c1], count[c0:c1] = t["idx"], t["score"], t["count"]
+        r = corpus_topk_torch(score, idx, count, torch.from_numpy(vi).to(dev), torch.from_numpy(pair_ptr).to(dev), k=k)
+        return self._search_result(r, duration, L)
 
     def _record_attention(self, maps):
         for smi, (cmap, bmap) in zip(self.smis, maps):

@@ -398,3 +398,76 @@ def compute_span_ious_torch(span, count, gt, n=(1, 5), m=(0.1, 0.3, 0.5, 0.7)):
     keys, n, m = _span_nm_check(n, m, k)
     counts = _span_hits_torch(span_ious_torch(span, count, gt), count, n, m).tolist()
     return {k_: float(v) for k_, v in zip(keys, counts)}
+
+
+# ---------------------------------------------------------------- merge across the videos of a corpus (SMIN.search)
+def _corpus_check(pair_score, pair_idx, pair_count, pair_video, pair_ptr, k):
+    if pair_idx.dim() != 3 or pair_idx.shape[2] != 2:
+        raise ValueError(f"corpus_topk: pair_idx must be (P, k_video, 2), got {tuple(pair_idx.shape)}")
+    P, kv = pair_idx.shape[0], pair_idx.shape[1]
+    if tuple(pair_score.shape) != (P, kv) or tuple(pair_count.shape) != (P,) or tuple(pair_video.shape) != (P,):
+        raise ValueError(f"corpus_topk: pair_score must be (P, k_video) = {(P, kv)}, pair_count / pair_video (P,); got "
+                         f"{tuple(pair_score.shape)}, {tuple(pair_count.shape)}, {tuple(pair_video.shape)}")
+    if pair_ptr.dim() != 1 or pair_ptr.shape[0] < 1:
+        raise ValueError("corpus_topk: pair_ptr must be (Q + 1,)")
+    if not (isinstance(k, int) and 1 <= k <= MAX_K) or not 1 <= kv <= MAX_K:
+        raise ValueError(f"corpus_topk needs integers 1 <= k, k_video <= {MAX_K} (got k={k!r}, k_video={kv})")
+    if P >= 2 ** 31:
+        raise ValueError(f"corpus_topk: {P} pairs exceed the int32 pair_ptr")
+    return P, kv, pair_ptr.shape[0] - 1
+
+
+def corpus_topk(pair_score, pair_idx, pair_count, pair_video, pair_ptr, k=5):
+    """One ranked list per query over all of its videos (include/smin_hip.h, smin_corpus_topk): one workgroup per query picks k
+    times the best remaining candidate of the query's pairs.
+
+    ``pair_score (P, k_video)``, ``pair_idx (P, k_video, 2)`` int64, ``pair_count (P,)``: top_moments' outputs for P (video, query)
+    pairs; ``pair_video (P,)`` each pair's video; ``pair_ptr (Q + 1,)``: query q owns pairs ``pair_ptr[q] .. pair_ptr[q + 1]``
+    (ascending, within [0, P]).  Order: higher score first, ties -> lower video, then lower slot, then the earlier pair; -0 counts as
+    +0.  HIP tensors only; no host synchronisation.  Returns a dict: ``video (Q, k)`` int64 (-1 for empty slots), ``idx (Q, k, 2)``
+    int64 (-1), ``score (Q, k)`` float32 (0), ``count (Q,)`` int32."""
+    from .training import _require_hip
+    from ._lib import call, ptr, stream
+    _require_hip(pair_ptr, "corpus_topk")
+    P, kv, Q = _corpus_check(pair_score, pair_idx, pair_count, pair_video, pair_ptr, k)
+    dev = pair_ptr.device
+    args = [pair_score.detach().float(), pair_idx.to(torch.int64), pair_count.to(torch.int32), pair_video.to(torch.int32), pair_ptr.to(torch.int32)]
+    args = [a.contiguous() for a in args]
+    video = torch.empty((Q, k), dtype=torch.int64, device=dev)
+    idx = torch.empty((Q, k, 2), dtype=torch.int64, device=dev)
+    score = torch.empty((Q, k), dtype=torch.float32, device=dev)
+    count = torch.empty((Q,), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        call("smin_corpus_topk", stream(), *[ptr(a) if a.numel() else None for a in args], Q, kv, k, ptr(video), ptr(idx), ptr(score), ptr(count))
+    return {"video": video, "idx": idx, "score": score, "count": count}
+
+
+def corpus_topk_torch(pair_score, pair_idx, pair_count, pair_video, pair_ptr, k=5):
+    """``corpus_topk`` as plain torch + Python on any device (same result, bit for bit): each query's candidates sorted by
+    (score, video, slot, pair)."""
+    P, kv, Q = _corpus_check(pair_score, pair_idx, pair_count, pair_video, pair_ptr, k)
+    dev = pair_ptr.device
+    score = pair_score.detach().float()
+    sc = torch.where(score == 0, torch.zeros_like(score), score)                                 # -0 -> +0
+    u = sc.contiguous().view(torch.int32).to(torch.int64) & 0xFFFFFFFF
+    o = torch.where(u >= 0x80000000, u ^ 0xFFFFFFFF, u | 0x80000000).clamp_min(1).reshape(-1).tolist()   # the order word of top_moments_torch
+    cnt = pair_count.to(torch.int64).clamp(max=kv).tolist()
+    vid = pair_video.to(torch.int64).tolist()
+    pp = pair_ptr.to(torch.int64).tolist()
+    video = torch.full((Q, k), -1, dtype=torch.int64, device=dev)
+    idx = torch.full((Q, k, 2), -1, dtype=torch.int64, device=dev)
+    out_score = torch.zeros((Q, k), dtype=torch.float32, device=dev)
+    count = torch.zeros((Q,), dtype=torch.int32, device=dev)
+    for q in range(Q):
+        g0 = max(pp[q], 0)
+        g1 = max(pp[q + 1], g0)
+        cand = [(-o[g * kv + s], vid[g], s, g) for g in range(g0, g1) for s in range(max(cnt[g], 0))]
+        cand.sort()
+        n = min(len(cand), k)
+        if n:
+            flat = torch.tensor([g * kv + s for _, _, s, g in cand[:n]], dtype=torch.int64, device=dev)
+            video[q, :n] = torch.tensor([v for _, v, _, _ in cand[:n]], dtype=torch.int64, device=dev)
+            idx[q, :n] = pair_idx.to(torch.int64).reshape(-1, 2)[flat]
+            out_score[q, :n] = score.reshape(-1)[flat]
+        count[q] = n
+    return {"video": video, "idx": idx, "score": out_score, "count": count}
