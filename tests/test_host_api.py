@@ -340,3 +340,30 @@ def test_node_options_name_the_op_arguments():
             assert not o["param_prep_kernel"] and o["overlap_prep"] == beside, mode
     finally:
         lib.set_gemm_mode("f32")
+
+
+def test_known_cells_sets_and_restores():
+    """_host.known_cells, what localize_windows, score_pairs and the epoch loops hand a host-computed valid-cell count through: set
+    for the body, the previous value back afterwards (exceptions included, nested uses in order), the attribute left alone for None."""
+    import types
+    import models
+    known_cells = models.vml_amd._host.known_cells
+    for before in (None, 11):
+        m = types.SimpleNamespace(known_cell_count=before)
+        with known_cells(m, 7):
+            assert m.known_cell_count == 7
+        assert m.known_cell_count == before                          # normal exit
+        with pytest.raises(KeyError):
+            with known_cells(m, 7):
+                assert m.known_cell_count == 7
+                raise KeyError("body")
+        assert m.known_cell_count == before                          # exit by exception
+        with known_cells(m, 3):
+            with known_cells(m, 5):
+                assert m.known_cell_count == 5
+            assert m.known_cell_count == 3                           # the inner one unwinds to the outer one's value
+        assert m.known_cell_count == before
+        with known_cells(m, None):
+            assert m.known_cell_count == before
+            m.known_cell_count = 99                                  # None: no-op, so nothing is put back either
+        assert m.known_cell_count == 99

@@ -17,6 +17,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._host import host_array
 from ._lib import call, ptr
 
 _BATCH_KEYS = ("video_features", "video_mask", "query_features", "query_mask", "length_mask", "moment_mask",
@@ -182,7 +183,7 @@ class BatchFeeder:
         Din = parts[0].shape[1] if parts and parts[0].ndim == 2 else -1
         if B < 1 or Din < 4 or Din % 4 or any(p.ndim != 2 or p.shape[1] != Din for p in parts):
             raise ValueError("raw_features must be (n_b, Din) arrays with one Din, Din % 4 == 0, and at least one sample")
-        tok = np.asarray(hb["tokens"].cpu() if isinstance(hb["tokens"], torch.Tensor) else hb["tokens"])
+        tok = host_array(hb["tokens"], None, None)
         V = self.embedding.shape[0]
         if tok.dtype.kind not in "iu" or tok.shape != (B, self.Nq):
             raise ValueError(f"tokens must be an integer array of shape (B, Nq) = {(B, self.Nq)} (got {tok.dtype}, {tok.shape})")
@@ -237,8 +238,7 @@ class BatchFeeder:
         else:
             o = np.concatenate([[0], np.cumsum(n)])
             videos = [parts[0][o[b]:o[b + 1]] for b in range(n.shape[0])]
-        to_i64 = lambda x: np.asarray(x.cpu() if isinstance(x, torch.Tensor) else x, dtype=np.int64).reshape(-1)
-        ws, wl = to_i64(hb["win_start"]), to_i64(hb["win_len"])
+        ws, wl = host_array(hb["win_start"]), host_array(hb["win_len"])
         if ws.shape != n.shape or wl.shape != n.shape:
             raise ValueError(f"win_start and win_len must be (B,) = {n.shape} (got {ws.shape}, {wl.shape})")
         bad = np.nonzero((ws < 0) | (wl < 0) | (ws + wl > n))[0]

@@ -22,7 +22,8 @@ import ctypes
 
 import torch
 
-from .moments import MAX_K, _check, _mask_u8, _mul32, _nm_check, _span_check, _span_meter_call, _sqrt32
+from ._host import byte_mask
+from .moments import MAX_K, _check, _mul32, _nm_check, _span_check, _span_meter_call, _sqrt32
 
 _REF_N, _REF_M = (1, 5), (0.1, 0.3, 0.5, 0.7)
 
@@ -132,7 +133,7 @@ class EpochMeter(_Meter):
             raise ValueError(f"sm must be (B, L, L) = {(B, L, L)} and loss a scalar (got {tuple(sm.shape)}, "
                              f"{None if loss is None else tuple(loss.shape)})")
         pm_, ps_, pe_, sm_ = (x.detach().float().contiguous() for x in (pm, ps, pe, sm))
-        mm_ = _mask_u8(moment_mask)
+        mm_ = byte_mask(moment_mask)
         loss_ = None if loss is None else loss.detach().float().reshape(1).contiguous()
         nl, ml = (ctypes.c_int * len(self._n))(*self._n), (ctypes.c_float * len(self._m))(*self._m)
         with torch.cuda.device(pm.device):
@@ -179,7 +180,7 @@ class EpochMeterTorch(_Meter):
             return torch.where(flat >= 0, iou, torch.zeros_like(iou))
         # the reference's rule as csrc/metrics.hip forms it: ((pm * sqrtf(ps_i)) * sqrtf(pe_j)) * mask over all cells, ties -> lower index
         score = _mul32(_mul32(pm.detach(), _sqrt32(ps.detach()).unsqueeze(2)), _sqrt32(pe.detach()).unsqueeze(1))
-        score = _mul32(score, (_mask_u8(moment_mask) != 0).float()).reshape(B, -1)
+        score = _mul32(score, (byte_mask(moment_mask) != 0).float()).reshape(B, -1)
         cell = torch.arange(L * L, device=score.device).unsqueeze(0)
         best = torch.where(score == score.max(dim=1, keepdim=True).values, cell, torch.full_like(cell, L * L)).min(dim=1).values
         return torch.gather(smf, 1, best.unsqueeze(1)).squeeze(1)

@@ -10,22 +10,25 @@ Inside ``SMIN.forward`` the L x L map lives in the packed valid-cell layout (cel
 (B, L, L, ...) tensors of the reference appear only at the stand-alone sub-module seams
 (``ContentUnit.forward`` etc.), which convert at the boundary and accept arbitrary dense inputs.
 Per-cell work and the whole boundary unit run in HIP (functional.py); the O(B*Nq*dl) word-side projections of the
-content unit and the backbone stay plain torch library calls.
+content unit and the backbone stay plain torch library calls.  What ``SMIN`` has beyond the reference -- localize, localize_windows, the
+banks and corpus search -- is in retrieval.py: a mixin that ``SMIN`` inherits; ``VideoBank`` and ``QueryBank`` are re-exported here.
 """
 import functools
 import math
 
 import os
 
-import numpy as np
 import torch
 import torch.nn as nn
 
+from . import _lib
+from ._host import _AttnMaps, query_mask_rows
 from ._lib import SminHipError
 
 from .cells import CellLayout
 from .functional import (VideoFuseFn, WordPrepFn, BiLstmLayerFn, BoundaryUnitFn, ClipWindowMeansFn, ContentAttnFn, ContentUnitFn, GateFn, LinearRowsFn, MomentUnitFn,
-                         ProposalMapFn, ProposalMeansFn, ScoreMapFn, attn_maps_gather, content_attn_maps_dense)
+                         ProposalMapFn, ProposalMeansFn, ScoreMapFn, content_attn_maps_dense)
+from .retrieval import QueryBank, VideoBank, _Retrieval  # noqa: F401  (the package namespace takes the banks from here)
 
 
 def _hip_forward(fn):
@@ -42,11 +45,6 @@ def _hip_forward(fn):
                 return fn(self, x, *args, **kwargs)
         return fn(self, x, *args, **kwargs)
     return wrapper
-
-
-def _byte_mask(mask):
-    """A mask as one byte per element (bool / uint8 as they are), contiguous: what the banks keep and the kernels gather."""
-    return (mask if mask.dtype in (torch.bool, torch.uint8) else mask != 0).contiguous()
 
 
 def _rows(mask):
@@ -229,15 +227,6 @@ class ProposalGeneration(nn.Module):
         layout = CellLayout.from_mask(moment_mask)
         fc, fm, fb = self.forward_packed(f, layout)
         return layout.unpack(fc), layout.unpack(fm), fb
-
-
-class _AttnMaps(list):
-    """Per-layer (content map, boundary map) pairs a forward fills; mode "dense": content maps (B, L, L, C, Nq), "packed": rows
-    [N*C, Nq] of the cell list, whose cellmap (B, L, L) is kept beside them."""
-
-    def __init__(self, mode):
-        super().__init__()
-        self.mode, self.cellmap = mode, None
 
 
 def _word_attention(W_q, W_k, query, key, value, mask, scale_dim):
@@ -433,38 +422,9 @@ class Localization(nn.Module):
         return self.forward_packed(layout.pack(f_m), f_b, length_mask, layout)
 
 
-class VideoBank:
-    """V videos encoded once (SMIN.encode_videos): ``fv (V, T, D)``, the video encoder's projection with position embedding and mask --
-    everything of a video the model computes before the video meets a query (f = fv * fs, reference models.py:81) --, the videos'
-    ``video_mask``, ``length_mask`` and ``moment_mask`` and ``cell_counts``, each video's number of valid cells as host ints (what
-    lets SMIN.search hand every chunk's ``known_cell_count`` to the scorer without a device read).  ``video_features`` is the input
-    itself (not a copy), kept for the configurations that score through SMIN.score.
-
-    A bank is detached and is a snapshot of the parameters at the time of the call: a parameter update (an optimizer step,
-    load_state_dict) makes it stale -- encode again.  ``fv`` is None when the call would not take the one-node path (SMIN._plan)."""
-
-    def __init__(self, fv, video_features, video_mask, length_mask, moment_mask, cell_counts):
-        self.fv, self.video_features, self.video_mask, self.length_mask, self.moment_mask = fv, video_features, video_mask, length_mask, moment_mask
-        self.cell_counts = tuple(int(c) for c in cell_counts)
-
-    def __len__(self):
-        return self.video_features.shape[0]
-
-
-class QueryBank:
-    """Q queries encoded once (SMIN.encode_queries): the query encoder's word features ``fw (Q, max_query_length, D)`` and sentence
-    features ``fs (Q, D)``, and ``query_mask (Q, max_query_length)`` padded as the kernels read it.  ``query_features`` is the input
-    itself, kept for the configurations that score through SMIN.score.  Detached; stale after a parameter update, as VideoBank."""
-
-    def __init__(self, fw, fs, query_features, query_mask):
-        self.fw, self.fs, self.query_features, self.query_mask = fw, fs, query_features, query_mask
-
-    def __len__(self):
-        return self.query_features.shape[0]
-
-
-class SMIN(nn.Module):
-    """reference models.py:346-377 -- the drop-in boundary (ctor called positionally from main.py:71)."""
+class SMIN(nn.Module, _Retrieval):
+    """reference models.py:346-377 -- the drop-in boundary (ctor called positionally from main.py:71).  What the reference does not
+    have -- localize, localize_windows, encode_videos / encode_queries, score_pairs, search -- is inherited from retrieval.py."""
 
     def __init__(self, T, L, C, D, dl, num_smi_layers, input_video_dim, max_query_length, lstm_hidden_size, device='cpu'):
         super().__init__()
@@ -648,7 +608,6 @@ class SMIN(nn.Module):
         built without packed fp32 arithmetic (csrc/Makefile), so its own kernels may overlap in every contraction mode.  torch's
         kernels (element-wise ops, hipBLASLt, the optimizer, RCCL) are outside that guarantee: with the bf16-core contraction modes
         (f32e / bf16x3 / bf16) they stay on the main stream, where nothing runs beside them."""
-        from . import _lib
         return _lib.get_gemm_mode() == "f32" or bool(os.environ.get("SMIN_STREAMS_IN_ALL_MODES"))
 
     def _param_prep_kernel(self):
@@ -673,12 +632,10 @@ class SMIN(nn.Module):
 
     def _node_options(self, attention=None):
         """The keyword arguments of smin_hip::smin_forward for this module's switches; attention: None, "dense" or "packed"."""
-        prep_kernel = self._param_prep_kernel()
-        return dict(overlap_boundary=self.overlap_boundary, overlap_prep=self.overlap_prep and (prep_kernel or self._torch_beside_contractions()),
-                    param_prep_kernel=prep_kernel, async_weights=self.async_weights, bf16_operand_storage=self.bf16_operand_storage,
-                    grad_sync=self.grad_sync and torch.is_grad_enabled(),
-                    known_cell_count=None if self.known_cell_count is None else int(self.known_cell_count), tail_split=self.tail_split,
-                    input_grads=self.input_grads, attention=attention)
+        o = self._score_options()                                  # the scorer's five and the node's own five, in the order of the op's schema
+        bf16, known = o.pop("bf16_operand_storage"), o.pop("known_cell_count")
+        return dict(**o, async_weights=self.async_weights, bf16_operand_storage=bf16, grad_sync=self.grad_sync and torch.is_grad_enabled(),
+                    known_cell_count=known, tail_split=self.tail_split, input_grads=self.input_grads, attention=attention)
 
     def _score_options(self):
         """The keyword arguments of smin_hip::smin_score for this module's switches."""
@@ -699,352 +656,10 @@ class SMIN(nn.Module):
         with torch.no_grad():
             if self.keep_attention or self._plan(video_features, query_features) != "node":
                 return self(video_features, video_mask, query_features, query_mask, length_mask, moment_mask)
-            query_mask = query_mask.reshape(query_features.shape[0], -1)
-            if query_mask.shape[1] != query_features.shape[1] or query_mask.shape[1] > self.max_query_length:
-                raise ValueError(f"query_mask has {query_mask.shape[1]} columns for {query_features.shape[1]} words (max_query_length {self.max_query_length})")
-            from . import _lib
+            query_mask = query_mask_rows(query_features, query_mask, self.max_query_length)
             return _lib.load_torch().smin_score(
                 video_features, video_mask, query_features, query_mask, length_mask, moment_mask, self._native_params(), self.T, self.L, self.C,
                 len(self.smis), self.max_query_length, self.lstm_hidden_size, **self._score_options())
-
-    def _scores(self, *inputs):
-        """The scores retrieval ranks (under no_grad): score() with forward_only_scoring, else the forward."""
-        return self.score(*inputs) if self.forward_only_scoring else self(*inputs)
-
-    def localize(self, video_features, video_mask, query_features, query_mask, length_mask, moment_mask, k=5, nms_thresh=0.5,
-                 duration=None, attention=False):
-        """The k best moments per sample: the forward under torch.no_grad() (score() with forward_only_scoring), then moments.top_moments of its (pm, ps, pe) -- greedy
-        temporal NMS at ``nms_thresh`` over the valid cells of ``moment_mask``.  Returns top_moments' dict (``idx`` (B, k, 2) start
-        / end clip, ``score``, ``count``; with ``duration`` (B,) seconds also ``times`` (B, k, 2) in seconds).
-
-        attention=True: also ``content_attention`` (B, k, layers, C, Nq), the content unit's word weights of each clip of each kept
-        moment, and ``boundary_attention`` (B, k, layers, 2, Nq), the boundary unit's word weights of its start and end rows (empty
-        slots 0): gathered on the device from the packed maps, no dense map is formed."""
-        from .moments import top_moments
-        with torch.no_grad():
-            if attention:
-                maps = _AttnMaps("packed")
-                pm, ps, pe, _ = self._forward(video_features, video_mask, query_features, query_mask, length_mask, moment_mask, maps)
-            else:
-                pm, ps, pe, _ = self._scores(video_features, video_mask, query_features, query_mask, length_mask, moment_mask)
-            r = top_moments(pm, ps, pe, moment_mask, k=k, nms_thresh=nms_thresh, duration=duration)
-            if attention:
-                r["content_attention"], r["boundary_attention"] = attn_maps_gather([c for c, _ in maps], [b for _, b in maps], maps.cellmap,
-                                                                                   r["idx"], self.C)
-        return r
-
-    def localize_windows(self, raw, lengths, query_features, query_mask, video_index=None, window=None, stride=None, k=5, k_window=None,
-                         nms_thresh=0.5, mode="pick", duration=None, max_batch=64):
-        """The k best moments of (video, query) pairs over videos of any length: overlapping windows of ``window`` raw rows (default
-        T: one row per clip) every ``stride`` rows (default window // 2) are each resampled to T clips, scored by the model and cut to
-        their ``k_window`` (default k) best moments, which are then merged per pair by greedy NMS in raw-row time.
-
-        ``raw`` (R, Din) HIP float32 tensor of V videos' rows back to back, ``lengths`` their V row counts (host); ``query_features``
-        (B, Nq, E) / ``query_mask`` the B pairs' queries, ``video_index`` (B,) host ints (default arange(V), B == V) maps a pair to
-        its video (the rows are not copied per pair).  Windows are processed in chunks of ``max_batch``: sample_windows, the masks
-        from nfeats, one forward under no_grad (score() with forward_only_scoring), top_moments; then one merge (moments.merge_window_moments).  The plan is host
-        arithmetic, so each chunk's valid-cell count is handed to the forward (``known_cell_count``) and nothing is read back.
-
-        Returns a dict: ``span`` (B, k, 2) float32 raw rows of the video (NaN for empty slots), ``score`` (B, k), ``window`` (B, k)
-        int64 window ordinal within the pair (-1), ``cell`` (B, k, 2) int64 cell of that window (-1), ``count`` (B,) int32 and
-        ``n_windows`` (B,) int64; with ``duration`` (B,) seconds also ``times`` = (span * duration) / n (fp32; n = the video's rows)."""
-        from .moments import MAX_K, merge_window_moments
-        from .sampling import MAX_ROWS, MODES, sample_windows, window_plan
-        from .feeder import build_masks_hip, cell_count
-        from . import _lib
-        T, L = self.T, self.L
-        k_window = k if k_window is None else k_window
-        window = T if window is None else window
-        stride = max(int(window) // 2, 1) if stride is None else stride
-        for name, v, lo, hi in (("k", k, 1, MAX_K), ("k_window", k_window, 1, MAX_K), ("window", window, 1, MAX_ROWS),
-                                ("stride", stride, 1, MAX_ROWS), ("max_batch", max_batch, 1, 65535)):
-            if not (isinstance(v, (int, np.integer)) and lo <= v <= hi):
-                raise ValueError(f"localize_windows: {name} must be an integer in [{lo}, {hi}] (got {v!r})")
-        if mode not in MODES:
-            raise ValueError(f"localize_windows: mode must be one of {sorted(MODES)} (got {mode!r})")
-        for name, t in (("raw", raw), ("query_features", query_features), ("query_mask", query_mask)):
-            if not (isinstance(t, torch.Tensor) and t.is_cuda):
-                raise SminHipError(f"localize_windows: {name} must be a HIP tensor (there is no CPU fallback)")
-        if raw.dim() != 2 or raw.dtype != torch.float32 or raw.shape[1] % 4 != 0 or raw.shape[1] != self.input_video_dim:
-            raise ValueError(f"localize_windows: raw must be float32 (R, Din = {self.input_video_dim}) with Din % 4 == 0 (got "
-                             f"{tuple(raw.shape)} {raw.dtype})")
-        n = np.asarray(lengths.cpu() if isinstance(lengths, torch.Tensor) else lengths, dtype=np.int64).reshape(-1)
-        if n.size and n.min() < 0 or int(n.sum()) != raw.shape[0]:
-            raise ValueError(f"localize_windows: lengths must be >= 0 and sum to raw's {raw.shape[0]} rows (got {int(n.sum())})")
-        V, B = n.shape[0], query_features.shape[0]
-        if video_index is None:
-            if B != V:
-                raise ValueError(f"localize_windows: without video_index the B = {B} queries pair with the V = {V} videos one to one")
-            vi = np.arange(V, dtype=np.int64)
-        else:
-            vi = np.asarray(video_index.cpu() if isinstance(video_index, torch.Tensor) else video_index, dtype=np.int64).reshape(-1)
-            if vi.shape[0] != B or (B and (vi.min() < 0 or vi.max() >= V)):
-                raise ValueError(f"localize_windows: video_index must hold B = {B} indices in [0, {V}) (got {vi.tolist()[:8]})")
-        if query_mask.shape[0] != B:
-            raise ValueError(f"localize_windows: query_mask has {query_mask.shape[0]} rows for B = {B} queries")
-        if duration is not None and tuple(duration.shape) != (B,):
-            raise ValueError(f"localize_windows: duration must be (B,) = ({B},) seconds (got {tuple(duration.shape)})")
-        starts, lens, vptr = (x.numpy() for x in window_plan(n, window, stride))
-        dev = raw.device
-        # per pair: its video's windows, in global window order (pair, then start)
-        nw = (vptr[1:] - vptr[:-1])[vi] if B else np.zeros(0, np.int64)
-        pair_ptr = np.concatenate([[0], np.cumsum(nw)]).astype(np.int64)
-        G = int(pair_ptr[-1])
-        if G * k_window >= 2 ** 31:
-            raise ValueError(f"localize_windows: {G} windows of {k_window} moments exceed the merge's 2**31 candidates")
-        wsel = np.concatenate([np.arange(vptr[v], vptr[v + 1]) for v in vi]).astype(np.int64) if G else np.zeros(0, np.int64)
-        offs = np.concatenate([[0], np.cumsum(n)]).astype(np.int64)
-        pair_of = np.repeat(np.arange(B, dtype=np.int64), nw)
-        w_start, w_len = starts[wsel], lens[wsel].astype(np.int64)
-        nf = np.minimum(w_len, T)
-        cells = np.array([cell_count(x, T, L) for x in nf], dtype=np.int64)                      # per window, as csrc/labels.hip forms it
-        # the whole plan in one pinned buffer, one asynchronous copy (the call never waits for the device)
-        host = np.concatenate([offs[vi[pair_of]] + w_start if G else np.zeros(0, np.int64), w_start, w_len, pair_of, pair_ptr, nw,
-                               n[vi]]).astype(np.int64)
-        plan = torch.from_numpy(host).pin_memory().to(dev, non_blocking=True)
-        cut = np.cumsum([0, G, G, G, G, B + 1, B, B])
-        rb_d, st_d, ln_d, po_d, pp_d, nw_d, nr_d = (plan[cut[q]:cut[q + 1]] for q in range(7))
-        ln_d = ln_d.to(torch.int32)
-        idx = torch.empty((G, k_window, 2), dtype=torch.int64, device=dev)
-        score = torch.empty((G, k_window), dtype=torch.float32, device=dev)
-        count = torch.empty((G,), dtype=torch.int32, device=dev)
-        known = self.known_cell_count
-        try:
-            with torch.no_grad(), torch.cuda.device(dev):
-                for c0 in range(0, G, max_batch):
-                    c1 = min(c0 + max_batch, G)
-                    g = c1 - c0
-                    vf, nfeats = sample_windows(raw, rb_d[c0:c1], ln_d[c0:c1], T, mode=mode)
-                    m = build_masks_hip(nfeats, T, L)
-                    rows = po_d[c0:c1]
-                    qf, qm = query_features.index_select(0, rows), query_mask.index_select(0, rows)
-                    self.known_cell_count = int(cells[c0:c1].sum())
-                    pm, ps, pe, _ = self._scores(vf, m["video_mask"], qf, qm, m["length_mask"], m["moment_mask"])
-                    mm = m["moment_mask"]
-                    nbytes = _lib.load().smin_top_moments_ws_bytes(g, L, k_window)
-                    ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
-                    _lib.call("smin_top_moments", _lib.stream(), _lib.ptr(pm.contiguous()), _lib.ptr(ps.contiguous()), _lib.ptr(pe.contiguous()),
-                              _lib.ptr(mm), g, L, k_window, float(nms_thresh), _lib.ptr(idx[c0:c1]), _lib.ptr(score[c0:c1]),
-                              _lib.ptr(count[c0:c1]), _lib.ptr(ws), nbytes)
-        finally:
-            self.known_cell_count = known
-        r = merge_window_moments(idx, score, count, st_d, ln_d, pp_d, T, L, k=k, nms_thresh=nms_thresh)
-        r["n_windows"] = nw_d
-        if duration is not None:
-            d = duration.to(device=dev, dtype=torch.float32).reshape(B, 1, 1)
-            r["times"] = (r["span"] * d) / nr_d.to(torch.float32).reshape(B, 1, 1)
-        return r
-
-    # ---------------------------------------------------------------- corpus search (INTEGRATION.md 3m)
-    def _bank_plan(self, video_features, query_features):
-        """Whether pairs of these inputs score on the one-node path from banks (as score(): _plan == "node" and no keep_attention)."""
-        return not self.keep_attention and self._plan(video_features, query_features) == "node"
-
-    def encode_videos(self, video_features, video_mask, length_mask, moment_mask):
-        """A VideoBank of V videos: the projection with position embedding and mask runs once per video (smin_hip::smin_encode_videos),
-        not once per (video, query) pair.  ``video_features (V, T, Din)`` and the three masks as forward takes them.  One host read
-        (the videos' valid-cell counts); under torch.no_grad().  The bank is stale after a parameter update."""
-        for name, t in (("video_features", video_features), ("video_mask", video_mask), ("length_mask", length_mask), ("moment_mask", moment_mask)):
-            if not (isinstance(t, torch.Tensor) and t.is_cuda):
-                raise SminHipError(f"encode_videos: {name} must be a HIP tensor (there is no CPU fallback)")
-        V = video_features.shape[0]
-        if video_features.dim() != 3 or V < 1 or video_mask.shape[0] != V or tuple(length_mask.shape) != (V, self.L) or tuple(moment_mask.shape) != (V, self.L, self.L):
-            raise ValueError(f"encode_videos: video_features (V, T, Din) with V >= 1, video_mask (V, T[, 1]), length_mask (V, L) and moment_mask (V, L, L); got "
-                             f"{tuple(video_features.shape)}, {tuple(video_mask.shape)}, {tuple(length_mask.shape)}, {tuple(moment_mask.shape)}")
-        from . import _lib
-        with torch.no_grad(), torch.cuda.device(video_features.device):
-            vf = video_features.detach()
-            masks = [_byte_mask(t) for t in (video_mask, length_mask, moment_mask)]
-            fv = None
-            if self.fused_core and self.backbone.videoencoder.fused(vf) and vf.shape[1] == self.T:
-                fv = _lib.load_torch().smin_encode_videos(vf, masks[0], self._native_params()[:3])
-            counts = masks[2].reshape(V, -1).ne(0).sum(dim=1).tolist()             # the bank's only host read
-        return VideoBank(fv, vf, masks[0], masks[1], masks[2], counts)
-
-    def encode_queries(self, query_features, query_mask):
-        """A QueryBank of Q queries: the two BiLSTM layers and the sentence feature run once per query
-        (smin_hip::smin_encode_queries).  ``query_features (Q, words, E)`` / ``query_mask`` as forward takes them.  No host read;
-        under torch.no_grad().  The bank is stale after a parameter update."""
-        for name, t in (("query_features", query_features), ("query_mask", query_mask)):
-            if not (isinstance(t, torch.Tensor) and t.is_cuda):
-                raise SminHipError(f"encode_queries: {name} must be a HIP tensor (there is no CPU fallback)")
-        if query_features.dim() != 3 or query_features.shape[0] < 1:
-            raise ValueError(f"encode_queries: query_features (Q, words, E) with Q >= 1 (got {tuple(query_features.shape)})")
-        qm = query_mask.reshape(query_features.shape[0], -1)
-        if qm.shape[1] != query_features.shape[1] or qm.shape[1] > self.max_query_length:
-            raise ValueError(f"query_mask has {qm.shape[1]} columns for {query_features.shape[1]} words (max_query_length {self.max_query_length})")
-        from . import _lib
-        with torch.no_grad(), torch.cuda.device(query_features.device):
-            qf = query_features.detach()
-            qm = _byte_mask(qm)
-            fw = fs = None
-            if self.fused_core and self.backbone.queryencoder.fused() and qf.dtype == torch.float32:
-                fw, fs = _lib.load_torch().smin_encode_queries(qf, qm, self._native_params()[:19], self.max_query_length, self.lstm_hidden_size)
-            if qm.shape[1] < self.max_query_length:
-                qm = torch.nn.functional.pad(qm, (0, self.max_query_length - qm.shape[1]))
-        return QueryBank(fw, fs, qf, qm)
-
-    @staticmethod
-    def _pair_lists(what, videos, queries, video_index, query_index):
-        if not isinstance(videos, VideoBank) or not isinstance(queries, QueryBank):
-            raise TypeError(f"{what}: videos is a VideoBank (encode_videos) and queries a QueryBank (encode_queries)")
-        vi = np.asarray(video_index.cpu() if isinstance(video_index, torch.Tensor) else video_index, dtype=np.int64).reshape(-1)
-        qi = np.asarray(query_index.cpu() if isinstance(query_index, torch.Tensor) else query_index, dtype=np.int64).reshape(-1)
-        if vi.shape[0] != qi.shape[0]:
-            raise ValueError(f"{what}: video_index and query_index must have one length (got {vi.shape[0]} and {qi.shape[0]})")
-        V, Q = len(videos), len(queries)
-        if vi.size and (vi.min() < 0 or vi.max() >= V or qi.min() < 0 or qi.max() >= Q):
-            raise ValueError(f"{what}: video_index must lie in [0, {V}) and query_index in [0, {Q})")
-        return vi, qi
-
-    @staticmethod
-    def _require_hip_banks(what, videos, queries):
-        for name, t in (("videos", videos.video_features), ("queries", queries.query_features)):
-            if not t.is_cuda:
-                raise SminHipError(f"{what}: {name} must hold HIP tensors (there is no CPU fallback)")
-
-    def _score_pairs(self, videos, queries, vi, qi, vi_d, qi_d):
-        """score_pairs of checked host lists vi / qi (P >= 1) whose int32 device copies are vi_d / qi_d.  No host read."""
-        known = self.known_cell_count
-        self.known_cell_count = int(sum(videos.cell_counts[v] for v in vi))       # host arithmetic: the scorer asks the device nothing
-        try:
-            with torch.no_grad(), torch.cuda.device(vi_d.device):
-                if not self._bank_plan(videos.video_features, queries.query_features):
-                    # as score(): configurations off the one-node path (and keep_attention) run the forward, here on expanded pairs
-                    qm = queries.query_mask[:, :queries.query_features.shape[1]]
-                    return self.score(videos.video_features.index_select(0, vi_d), videos.video_mask.index_select(0, vi_d),
-                                      queries.query_features.index_select(0, qi_d), qm.index_select(0, qi_d),
-                                      videos.length_mask.index_select(0, vi_d), videos.moment_mask.index_select(0, vi_d))
-                if videos.fv is None or queries.fw is None:
-                    raise ValueError("score_pairs: a bank was encoded while the module was off the one-node path (SMIN._plan); encode it again")
-                from . import _lib
-                return _lib.load_torch().smin_score_pairs(
-                    videos.fv, queries.fw, queries.fs, videos.video_mask, queries.query_mask, videos.length_mask, videos.moment_mask, vi_d, qi_d,
-                    self._native_params(), self.T, self.L, self.C, len(self.smis), self.max_query_length, self.lstm_hidden_size, **self._score_options())
-        finally:
-            self.known_cell_count = known
-
-    def score_pairs(self, videos, queries, video_index, query_index):
-        """(pm, ps, pe, pa) as score() returns them for the P pairs (videos[video_index[p]], queries[query_index[p]]) of a VideoBank
-        and a QueryBank: neither encoder runs again, and no pair carries a copy of its video's features.  ``video_index`` /
-        ``query_index``: host int sequences of one length P >= 1, any lists, repeats included; an index out of range raises
-        ValueError.  On the one-node path this is smin_hip::smin_score_pairs: the pairs' masks gathered (bytes), smin_pair_assemble
-        where smin_score has its backbone, then smin_score's own code -- the bits of score() on the expanded batch.  Where score()
-        would run the forward instead (_plan != "node", keep_attention) the pairs are expanded and scored by score().  The valid-cell
-        count comes from the bank, so nothing is read back."""
-        vi, qi = self._pair_lists("score_pairs", videos, queries, video_index, query_index)
-        if vi.shape[0] < 1:
-            raise ValueError("score_pairs: at least one pair")
-        self._require_hip_banks("score_pairs", videos, queries)
-        dev = videos.video_features.device
-        idx = torch.from_numpy(np.concatenate([vi, qi]).astype(np.int32)).pin_memory().to(dev, non_blocking=True)
-        return self._score_pairs(videos, queries, vi, qi, idx[:vi.shape[0]], idx[vi.shape[0]:])
-
-    def _search_plan(self, what, videos, queries, pairs, k, k_video, max_batch, duration):
-        from .moments import MAX_K
-        k_video = k if k_video is None else k_video
-        for name, v, lo, hi in (("k", k, 1, MAX_K), ("k_video", k_video, 1, MAX_K), ("max_batch", max_batch, 1, 65535)):
-            if not (isinstance(v, (int, np.integer)) and lo <= v <= hi):
-                raise ValueError(f"{what}: {name} must be an integer in [{lo}, {hi}] (got {v!r})")
-        if not isinstance(videos, VideoBank) or not isinstance(queries, QueryBank):
-            raise TypeError(f"{what}: videos is a VideoBank (encode_videos) and queries a QueryBank (encode_queries)")
-        V, Q = len(videos), len(queries)
-        if pairs is None:
-            qi, vi = np.repeat(np.arange(Q, dtype=np.int64), V), np.tile(np.arange(V, dtype=np.int64), Q)
-        else:
-            pr = np.asarray(pairs.cpu() if isinstance(pairs, torch.Tensor) else pairs, dtype=np.int64)
-            if pr.size == 0:
-                pr = pr.reshape(0, 2)
-            if pr.ndim != 2 or pr.shape[1] != 2:
-                raise ValueError(f"{what}: pairs must be (P, 2) rows of (query, video) (got {pr.shape})")
-            order = np.lexsort((pr[:, 1], pr[:, 0]))                               # by (query, video)
-            qi, vi = pr[order, 0], pr[order, 1]
-        vi, qi = self._pair_lists(what, videos, queries, vi, qi)
-        if vi.size > 1 and bool(((qi[1:] == qi[:-1]) & (vi[1:] == vi[:-1])).any()):
-            raise ValueError(f"{what}: a (query, video) pair is listed more than once")
-        if duration is not None and tuple(duration.shape) != (V,):
-            raise ValueError(f"{what}: duration must be (V,) = ({V},) seconds (got {tuple(duration.shape)})")
-        self._require_hip_banks(what, videos, queries)
-        pair_ptr = np.concatenate([[0], np.cumsum(np.bincount(qi, minlength=Q))]).astype(np.int64)
-        return int(k), int(k_video), vi, qi, pair_ptr
-
-    @staticmethod
-    def _search_result(r, duration, L):
-        if duration is not None:
-            # moments._times' formula on each moment's own video: (i * duration / L, (j + 1) * duration / L) in fp32, NaN for empty slots
-            # (formed without a constant from the host: the call reads and writes no host memory)
-            Q, k = r["video"].shape
-            d = duration.to(device=r["video"].device, dtype=torch.float32)[r["video"].clamp_min(0)].reshape(Q, k, 1)
-            edge = r["idx"].to(torch.float32)
-            edge[..., 1] += 1.0
-            t = edge * d / L
-            r["times"] = torch.where(r["idx"] >= 0, t, torch.full_like(t, float("nan")))
-        return r
-
-    def search(self, videos, queries, pairs=None, k=5, k_video=None, nms_thresh=0.5, duration=None, max_batch=64):
-        """Which video, and where: the k best moments of each of the Q queries of a QueryBank over the videos of a VideoBank.
-
-        ``pairs``: None -- every query against every video --, or a host (P, 2) array of (query, video) rows, in any order (sorted
-        here by (query, video)); a repeated pair raises ValueError.  The pairs are scored in chunks of at most ``max_batch``
-        (score_pairs: from the banks, no encoder runs again; each chunk's valid-cell count is the sum of the bank's cell_counts,
-        nothing is read back), each chunk is cut to its ``k_video`` (default k) best moments per pair by top_moments' kernels
-        (greedy NMS at ``nms_thresh``), and one smin_corpus_topk ranks each query's moments across its videos: higher score first,
-        ties -> lower video, then lower slot.  Every listed pair is scored by the full model.
-
-        Returns a dict: ``video (Q, k)`` int64 (-1 for empty slots), ``idx (Q, k, 2)`` int64 start / end clip (-1), ``score (Q, k)``
-        (0), ``count (Q,)`` int32; with ``duration`` (V,) seconds also ``times (Q, k, 2)``: top_moments' formula on
-        ``duration[video]``, NaN for empty slots.  Scores come from score_pairs (forward_only_scoring or not: a bank has no graph),
-        in the contraction mode of set_gemm_mode.  No host synchronisation."""
-        from .moments import corpus_topk
-        from . import _lib
-        k, k_video, vi, qi, pair_ptr = self._search_plan("search", videos, queries, pairs, k, k_video, max_batch, duration)
-        dev, L, P = videos.video_features.device, self.L, vi.shape[0]
-        # the whole plan in one pinned buffer, one asynchronous copy (the call never waits for the device)
-        plan = torch.from_numpy(np.concatenate([vi, qi, pair_ptr]).astype(np.int32)).pin_memory().to(dev, non_blocking=True)
-        vi_d, qi_d, pp_d = plan[:P], plan[P:2 * P], plan[2 * P:]
-        idx = torch.empty((P, k_video, 2), dtype=torch.int64, device=dev)
-        score = torch.empty((P, k_video), dtype=torch.float32, device=dev)
-        count = torch.empty((P,), dtype=torch.int32, device=dev)
-        with torch.no_grad(), torch.cuda.device(dev):
-            for c0 in range(0, P, max_batch):
-                c1 = min(c0 + max_batch, P)
-                pm, ps, pe, _ = self._score_pairs(videos, queries, vi[c0:c1], qi[c0:c1], vi_d[c0:c1], qi_d[c0:c1])
-                mm = videos.moment_mask.index_select(0, vi_d[c0:c1])
-                nbytes = _lib.load().smin_top_moments_ws_bytes(c1 - c0, L, k_video)
-                ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
-                _lib.call("smin_top_moments", _lib.stream(), _lib.ptr(pm.contiguous()), _lib.ptr(ps.contiguous()), _lib.ptr(pe.contiguous()),
-                          _lib.ptr(mm), c1 - c0, L, k_video, float(nms_thresh), _lib.ptr(idx[c0:c1]), _lib.ptr(score[c0:c1]),
-                          _lib.ptr(count[c0:c1]), _lib.ptr(ws), nbytes)
-            r = corpus_topk(score, idx, count, vi_d, pp_d, k=k)
-        return self._search_result(r, duration, L)
-
-    def search_torch(self, videos, queries, pairs=None, k=5, k_video=None, nms_thresh=0.5, duration=None, max_batch=64, scorer=None):
-        """``search`` restated: the same plan and chunking, each chunk's pairs expanded and scored by score(), cut by top_moments and
-        merged by moments.corpus_topk_torch.  Kept under its own name as what the tests compare against -- nothing routes here.
-        ``scorer(video_index, query_index) -> (pm, ps, pe, pa)`` replaces score() on the expanded pairs (the tests feed it
-        score_pairs, to compare the ranking on equal scores)."""
-        from .moments import corpus_topk_torch, top_moments
-        k, k_video, vi, qi, pair_ptr = self._search_plan("search_torch", videos, queries, pairs, k, k_video, max_batch, duration)
-        dev, L, P = videos.video_features.device, self.L, vi.shape[0]
-        idx = torch.empty((P, k_video, 2), dtype=torch.int64, device=dev)
-        score = torch.empty((P, k_video), dtype=torch.float32, device=dev)
-        count = torch.empty((P,), dtype=torch.int32, device=dev)
-        with torch.no_grad():
-            for c0 in range(0, P, max_batch):
-                c1 = min(c0 + max_batch, P)
-                vi_d, qi_d = (torch.from_numpy(x[c0:c1].copy()).to(dev) for x in (vi, qi))
-                mm = videos.moment_mask.index_select(0, vi_d)
-                if scorer is not None:
-                    pm, ps, pe, _ = scorer(vi[c0:c1], qi[c0:c1])
-                else:
-                    qm = queries.query_mask[:, :queries.query_features.shape[1]]
-                    pm, ps, pe, _ = self.score(videos.video_features.index_select(0, vi_d), videos.video_mask.index_select(0, vi_d),
-                                               queries.query_features.index_select(0, qi_d), qm.index_select(0, qi_d),
-                                               videos.length_mask.index_select(0, vi_d), mm)
-                t = top_moments(pm, ps, pe, mm, k=k_video, nms_thresh=nms_thresh)
-                idx[c0:c1], score[c0:c1], count[c0:c1] = t["idx"], t["score"], t["count"]
-        r = corpus_topk_torch(score, idx, count, torch.from_numpy(vi).to(dev), torch.from_numpy(pair_ptr).to(dev), k=k)
-        return self._search_result(r, duration, L)
 
     def _record_attention(self, maps):
         for smi, (cmap, bmap) in zip(self.smis, maps):
@@ -1067,9 +682,7 @@ class SMIN(nn.Module):
     def _forward(self, video_features, video_mask, query_features, query_mask, length_mask, moment_mask, maps):
         # the reference's dataset pads queries and their mask to max_query_length (dataset.py:35, 173); a batch cut to its longest query is taken
         # too: the encoder pads f_w as models.py:58-59 does, and the mask is padded here (every kernel reads max_query_length mask columns)
-        query_mask = query_mask.reshape(query_features.shape[0], -1)
-        if query_mask.shape[1] != query_features.shape[1] or query_mask.shape[1] > self.max_query_length:
-            raise ValueError(f"query_mask has {query_mask.shape[1]} columns for {query_features.shape[1]} words (max_query_length {self.max_query_length})")
+        query_mask = query_mask_rows(query_features, query_mask, self.max_query_length)
         if query_mask.shape[1] < self.max_query_length:
             query_mask = torch.nn.functional.pad(query_mask, (0, self.max_query_length - query_mask.shape[1]))
         plan = self._plan(video_features, query_features)
@@ -1080,7 +693,6 @@ class SMIN(nn.Module):
             raise RuntimeError("SMIN.grad_sync (distributed.wrap's in-node gradient exchange) needs the one-node extension path; this "
                                "call does not qualify (see SMIN._plan) -- wrap the model with SMIN_TORCH_DDP=1 instead")
         if plan == "node":
-            from . import _lib
             pm, ps, pe, pa, content, boundary = _lib.load_torch().smin_forward(
                 video_features, video_mask, query_features, query_mask, length_mask, moment_mask, self._native_params(), self.T, self.L, self.C,
                 len(self.smis), self.max_query_length, self.lstm_hidden_size, **self._node_options(None if maps is None else maps.mode))

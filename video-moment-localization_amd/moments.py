@@ -21,6 +21,9 @@ import ctypes
 
 import torch
 
+from ._host import _require_hip, byte_mask
+from ._lib import SminHipError, call, load, ptr, stream
+
 MAX_K = 64
 MAX_N, MAX_M = 64, 16               # compute_ious(..., nms_thresh=t): at most 64 values of n and 16 thresholds m
 
@@ -54,8 +57,18 @@ def _result(idx, score, count, duration, L):
     return out
 
 
-def _mask_u8(moment_mask):
-    return (moment_mask if moment_mask.dtype in (torch.bool, torch.uint8) else moment_mask != 0).contiguous()
+def _top_moments_into(pm, ps, pe, moment_mask, k, nms_thresh, idx, score, count):
+    """smin_top_moments of B checked samples on ``pm``'s device into the caller's contiguous ``idx (B, k, 2)`` int64, ``score (B, k)``
+    float32 and ``count (B,)`` int32 (e.g. a chunk's rows of larger buffers): the workspace query, its allocation and the call.
+    Detached fp32 contiguous scores and a contiguous byte mask are passed as they are: no launch or copy beside the kernels'."""
+    B, L = pm.shape[0], pm.shape[1]
+    pm_, ps_, pe_ = (x.detach().float().contiguous() for x in (pm, ps, pe))
+    mm_ = byte_mask(moment_mask)
+    with torch.cuda.device(pm.device):
+        nbytes = load().smin_top_moments_ws_bytes(B, L, k)
+        ws = torch.empty((nbytes,), dtype=torch.uint8, device=pm.device)
+        call("smin_top_moments", stream(), ptr(pm_), ptr(ps_), ptr(pe_), ptr(mm_), B, L, k, float(nms_thresh),
+             ptr(idx), ptr(score), ptr(count), ptr(ws), nbytes)
 
 
 def top_moments(pm, ps, pe, moment_mask, k=5, nms_thresh=0.5, duration=None):
@@ -65,20 +78,12 @@ def top_moments(pm, ps, pe, moment_mask, k=5, nms_thresh=0.5, duration=None):
     Returns a dict: ``idx`` (B, k, 2) int64 start / end clip (-1 for empty slots), ``score`` (B, k) float32 (0 for empty
     slots), ``count`` (B,) int32; with ``duration`` (B,) seconds also ``times`` (B, k, 2) float32:
     ``(i * duration / L, (j + 1) * duration / L)``, NaN for empty slots."""
-    from .training import _require_hip
-    from ._lib import call, ptr, stream, load
     _require_hip(pm, "top_moments")
     B, L = _check(pm, ps, pe, moment_mask, k)
-    pm_, ps_, pe_ = (x.detach().float().contiguous() for x in (pm, ps, pe))
-    mm_ = _mask_u8(moment_mask)
     idx = torch.empty((B, k, 2), dtype=torch.int64, device=pm.device)
     score = torch.empty((B, k), dtype=torch.float32, device=pm.device)
     count = torch.empty((B,), dtype=torch.int32, device=pm.device)
-    with torch.cuda.device(pm.device):
-        nbytes = load().smin_top_moments_ws_bytes(B, L, k)
-        ws = torch.empty((nbytes,), dtype=torch.uint8, device=pm.device)
-        call("smin_top_moments", stream(), ptr(pm_), ptr(ps_), ptr(pe_), ptr(mm_), B, L, k, float(nms_thresh),
-             ptr(idx), ptr(score), ptr(count), ptr(ws), nbytes)
+    _top_moments_into(pm, ps, pe, moment_mask, k, nms_thresh, idx, score, count)
     return _result(idx, score, count, duration, L)
 
 
@@ -108,7 +113,7 @@ def top_moments_torch(pm, ps, pe, moment_mask, k=5, nms_thresh=0.5, duration=Non
     score = torch.where(score == 0, torch.zeros_like(score), score).reshape(B, -1)              # -0 -> +0
     u = score.view(torch.int32).to(torch.int64) & 0xFFFFFFFF                                     # fp32 bits -> unsigned order word
     o = torch.where(u >= 0x80000000, u ^ 0xFFFFFFFF, u | 0x80000000).clamp_min(1)
-    valid = _mask_u8(moment_mask).reshape(B, -1) != 0
+    valid = byte_mask(moment_mask).reshape(B, -1) != 0
     o = torch.where(valid, o, torch.zeros_like(o))
     order = torch.sort(o, dim=1, descending=True, stable=True).indices                          # ties keep index order
     nvalid = valid.sum(dim=1).tolist()
@@ -157,13 +162,12 @@ def _nm_check(n, m):
 def compute_ious_nms(pm, ps, pe, moment_mask, sm, n, m, nms_thresh):
     """R@n, IoU=m over the NMS-kept moments on the device (training.compute_ious(..., nms_thresh=t)): top-k with k = max(n), then
     sm gathered at the kept cells (empty slot = IoU 0) and the hits summed over the samples by the device.  One host read."""
-    from ._lib import call, ptr, stream, load
     B, L = _check(pm, ps, pe, moment_mask, 1)
     keys = [f"R@{n_}, IoU={m_}" for n_ in n for m_ in m]
     n, m = _nm_check(n, m)
     k = max(n)
     pm_, ps_, pe_, sm_ = (x.detach().float().contiguous() for x in (pm, ps, pe, sm))
-    mm_ = _mask_u8(moment_mask)
+    mm_ = byte_mask(moment_mask)
     nl, ml = (ctypes.c_int * len(n))(*n), (ctypes.c_float * len(m))(*m)
     counts = torch.empty((len(n) * len(m),), dtype=torch.float32, device=pm.device)
     with torch.cuda.device(pm.device):
@@ -213,8 +217,6 @@ def merge_window_moments(idx, score, count, start, lens, pair_ptr, T, L, k=5, nm
     ``pair_ptr[b] .. pair_ptr[b + 1]``.  HIP tensors only; no host synchronisation.  Returns a dict: ``span (B, k, 2)`` float32 raw
     rows (NaN for empty slots), ``score (B, k)`` (0), ``window (B, k)`` int64 ordinal within the pair (-1), ``cell (B, k, 2)`` int64
     (-1), ``count (B,)`` int32."""
-    from .training import _require_hip
-    from ._lib import call, ptr, stream
     _require_hip(idx, "merge_window_moments")
     G, kw, B = _merge_check(idx, score, count, start, lens, pair_ptr, T, L, k)
     dev = idx.device
@@ -326,8 +328,6 @@ def span_ious(span, count, gt):
     """IoU of every slot of ``span (B, k, 2)`` (``merge_window_moments`` / ``SMIN.localize_windows`` output, ``count (B,)`` filled
     slots) with the pair's ground truth ``gt (B, 2)`` in the same unit, on the device (include/smin_hip.h, smin_span_ious):
     ``(B, k)`` float32, exactly 0 for the empty slots (their NaN span does not propagate).  HIP tensors only; no host read."""
-    from .training import _require_hip
-    from ._lib import call, ptr, stream
     _require_hip(span, "span_ious")
     B, k = _span_check(span, count, gt)
     span_, gt_, count_ = span.detach().float().contiguous(), gt.detach().float().contiguous(), count.to(torch.int32).contiguous()
@@ -358,7 +358,6 @@ def span_ious_torch(span, count, gt):
 
 def _span_meter_call(span, count, gt, n, m, acc):
     """smin_span_meter_update of B >= 1 checked pairs into ``acc`` (fp64, 4 + len(n) * len(m)) on the current stream."""
-    from ._lib import SminHipError, call, load, ptr, stream
     B, k = span.shape[0], span.shape[1]
     span_, gt_, count_ = span.detach().float().contiguous(), gt.detach().float().contiguous(), count.to(torch.int32).contiguous()
     nl, ml = (ctypes.c_int * len(n))(*n), (ctypes.c_float * len(m))(*m)
@@ -375,7 +374,6 @@ def compute_span_ious(span, count, gt, n=(1, 5), m=(0.1, 0.3, 0.5, 0.7)):
     """R@n, IoU=m of merged spans on the device, mirroring ``compute_ious``: ``{"R@n, IoU=m": pairs with some slot
     s < min(n, count) whose IoU with gt is > m}`` (strict, as utils.py:29), summed over the pairs by the device
     (smin_span_meter_update into a fresh accumulator).  One host read.  HIP tensors only."""
-    from .training import _require_hip
     _require_hip(span, "compute_span_ious")
     B, k = _span_check(span, count, gt)
     keys, n, m = _span_nm_check(n, m, k)
@@ -426,8 +424,6 @@ def corpus_topk(pair_score, pair_idx, pair_count, pair_video, pair_ptr, k=5):
     (ascending, within [0, P]).  Order: higher score first, ties -> lower video, then lower slot, then the earlier pair; -0 counts as
     +0.  HIP tensors only; no host synchronisation.  Returns a dict: ``video (Q, k)`` int64 (-1 for empty slots), ``idx (Q, k, 2)``
     int64 (-1), ``score (Q, k)`` float32 (0), ``count (Q,)`` int32."""
-    from .training import _require_hip
-    from ._lib import call, ptr, stream
     _require_hip(pair_ptr, "corpus_topk")
     P, kv, Q = _corpus_check(pair_score, pair_idx, pair_count, pair_video, pair_ptr, k)
     dev = pair_ptr.device

@@ -1,0 +1,341 @@
+"""Retrieval on top of SMIN's scores, which the reference does not have: the best moments of a sample (``localize``), of videos of
+any length over overlapping windows (``localize_windows``) and of a corpus encoded once (``encode_videos`` / ``encode_queries`` ->
+``score_pairs`` / ``search``): host code around the library's kernels and the model's own ``score`` / ``forward``, which
+``modules.SMIN`` inherits through the stateless mixin ``_Retrieval``."""
+import numpy as np
+import torch
+
+from . import _lib
+from ._host import _AttnMaps, byte_mask, host_array, known_cells, query_mask_rows, require_hip_tensors, require_ints
+from .feeder import build_masks_hip, cell_count
+from .functional import attn_maps_gather
+from .moments import MAX_K, _top_moments_into, corpus_topk, corpus_topk_torch, merge_window_moments, top_moments
+from .sampling import MAX_ROWS, MODES, sample_windows, window_plan
+
+
+class VideoBank:
+    """V videos encoded once (SMIN.encode_videos): ``fv (V, T, D)``, the video encoder's projection with position embedding and mask --
+    everything of a video the model computes before the video meets a query (f = fv * fs, reference models.py:81) --, the videos'
+    ``video_mask``, ``length_mask`` and ``moment_mask`` and ``cell_counts``, each video's number of valid cells as host ints (what
+    lets SMIN.search hand every chunk's ``known_cell_count`` to the scorer without a device read).  ``video_features`` is the input
+    itself (not a copy), kept for the configurations that score through SMIN.score.
+
+    A bank is detached and is a snapshot of the parameters at the time of the call: a parameter update (an optimizer step,
+    load_state_dict) makes it stale -- encode again.  ``fv`` is None when the call would not take the one-node path (SMIN._plan)."""
+
+    def __init__(self, fv, video_features, video_mask, length_mask, moment_mask, cell_counts):
+        self.fv, self.video_features, self.video_mask, self.length_mask, self.moment_mask = fv, video_features, video_mask, length_mask, moment_mask
+        self.cell_counts = tuple(int(c) for c in cell_counts)
+
+    def __len__(self):
+        return self.video_features.shape[0]
+
+
+class QueryBank:
+    """Q queries encoded once (SMIN.encode_queries): the query encoder's word features ``fw (Q, max_query_length, D)`` and sentence
+    features ``fs (Q, D)``, and ``query_mask (Q, max_query_length)`` padded as the kernels read it.  ``query_features`` is the input
+    itself, kept for the configurations that score through SMIN.score.  Detached; stale after a parameter update, as VideoBank."""
+
+    def __init__(self, fw, fs, query_features, query_mask):
+        self.fw, self.fs, self.query_features, self.query_mask = fw, fs, query_features, query_mask
+
+    def __len__(self):
+        return self.query_features.shape[0]
+
+
+def _require_banks(what, videos, queries):
+    if not isinstance(videos, VideoBank) or not isinstance(queries, QueryBank):
+        raise TypeError(f"{what}: videos is a VideoBank (encode_videos) and queries a QueryBank (encode_queries)")
+
+
+def _chunk_buffers(n, k, max_batch, dev):
+    """Where the chunks of n windows / pairs leave their k best moments: top_moments' ``idx (n, k, 2)``, ``score (n, k)`` and
+    ``count (n,)`` on ``dev``, and the chunks' bounds [(c0, c1), ...] of at most ``max_batch`` rows."""
+    idx = torch.empty((n, k, 2), dtype=torch.int64, device=dev)
+    score = torch.empty((n, k), dtype=torch.float32, device=dev)
+    count = torch.empty((n,), dtype=torch.int32, device=dev)
+    return idx, score, count, [(c0, min(c0 + max_batch, n)) for c0 in range(0, n, max_batch)]
+
+
+class _Retrieval:
+    """SMIN's retrieval methods, inherited by modules.SMIN: no constructor and no state of its own."""
+
+    def _scores(self, *inputs):
+        """The scores retrieval ranks (under no_grad): score() with forward_only_scoring, else the forward."""
+        return self.score(*inputs) if self.forward_only_scoring else self(*inputs)
+
+    def localize(self, video_features, video_mask, query_features, query_mask, length_mask, moment_mask, k=5, nms_thresh=0.5,
+                 duration=None, attention=False):
+        """The k best moments per sample: the forward under torch.no_grad() (score() with forward_only_scoring), then moments.top_moments of its (pm, ps, pe) -- greedy
+        temporal NMS at ``nms_thresh`` over the valid cells of ``moment_mask``.  Returns top_moments' dict (``idx`` (B, k, 2) start
+        / end clip, ``score``, ``count``; with ``duration`` (B,) seconds also ``times`` (B, k, 2) in seconds).
+
+        attention=True: also ``content_attention`` (B, k, layers, C, Nq), the content unit's word weights of each clip of each kept
+        moment, and ``boundary_attention`` (B, k, layers, 2, Nq), the boundary unit's word weights of its start and end rows (empty
+        slots 0): gathered on the device from the packed maps, no dense map is formed."""
+        with torch.no_grad():
+            if attention:
+                maps = _AttnMaps("packed")
+                pm, ps, pe, _ = self._forward(video_features, video_mask, query_features, query_mask, length_mask, moment_mask, maps)
+            else:
+                pm, ps, pe, _ = self._scores(video_features, video_mask, query_features, query_mask, length_mask, moment_mask)
+            r = top_moments(pm, ps, pe, moment_mask, k=k, nms_thresh=nms_thresh, duration=duration)
+            if attention:
+                r["content_attention"], r["boundary_attention"] = attn_maps_gather([c for c, _ in maps], [b for _, b in maps], maps.cellmap,
+                                                                                   r["idx"], self.C)
+        return r
+
+    def localize_windows(self, raw, lengths, query_features, query_mask, video_index=None, window=None, stride=None, k=5, k_window=None,
+                         nms_thresh=0.5, mode="pick", duration=None, max_batch=64):
+        """The k best moments of (video, query) pairs over videos of any length: overlapping windows of ``window`` raw rows (default
+        T: one row per clip) every ``stride`` rows (default window // 2) are each resampled to T clips, scored by the model and cut to
+        their ``k_window`` (default k) best moments, which are then merged per pair by greedy NMS in raw-row time.
+
+        ``raw`` (R, Din) HIP float32 tensor of V videos' rows back to back, ``lengths`` their V row counts (host); ``query_features``
+        (B, Nq, E) / ``query_mask`` the B pairs' queries, ``video_index`` (B,) host ints (default arange(V), B == V) maps a pair to
+        its video (the rows are not copied per pair).  Windows are processed in chunks of ``max_batch``: sample_windows, the masks
+        from nfeats, one forward under no_grad (score() with forward_only_scoring), top_moments; then one merge (moments.merge_window_moments).  The plan is host
+        arithmetic, so each chunk's valid-cell count is handed to the forward (``known_cell_count``) and nothing is read back.
+
+        Returns a dict: ``span`` (B, k, 2) float32 raw rows of the video (NaN for empty slots), ``score`` (B, k), ``window`` (B, k)
+        int64 window ordinal within the pair (-1), ``cell`` (B, k, 2) int64 cell of that window (-1), ``count`` (B,) int32 and
+        ``n_windows`` (B,) int64; with ``duration`` (B,) seconds also ``times`` = (span * duration) / n (fp32; n = the video's rows)."""
+        T, L = self.T, self.L
+        k_window = k if k_window is None else k_window
+        window = T if window is None else window
+        stride = max(int(window) // 2, 1) if stride is None else stride
+        require_ints("localize_windows", ("k", k, 1, MAX_K), ("k_window", k_window, 1, MAX_K), ("window", window, 1, MAX_ROWS),
+                     ("stride", stride, 1, MAX_ROWS), ("max_batch", max_batch, 1, 65535))
+        if mode not in MODES:
+            raise ValueError(f"localize_windows: mode must be one of {sorted(MODES)} (got {mode!r})")
+        require_hip_tensors("localize_windows", dict(raw=raw, query_features=query_features, query_mask=query_mask))
+        if raw.dim() != 2 or raw.dtype != torch.float32 or raw.shape[1] % 4 != 0 or raw.shape[1] != self.input_video_dim:
+            raise ValueError(f"localize_windows: raw must be float32 (R, Din = {self.input_video_dim}) with Din % 4 == 0 (got "
+                             f"{tuple(raw.shape)} {raw.dtype})")
+        n = host_array(lengths)
+        if n.size and n.min() < 0 or int(n.sum()) != raw.shape[0]:
+            raise ValueError(f"localize_windows: lengths must be >= 0 and sum to raw's {raw.shape[0]} rows (got {int(n.sum())})")
+        V, B = n.shape[0], query_features.shape[0]
+        if video_index is None:
+            if B != V:
+                raise ValueError(f"localize_windows: without video_index the B = {B} queries pair with the V = {V} videos one to one")
+            vi = np.arange(V, dtype=np.int64)
+        else:
+            vi = host_array(video_index)
+            if vi.shape[0] != B or (B and (vi.min() < 0 or vi.max() >= V)):
+                raise ValueError(f"localize_windows: video_index must hold B = {B} indices in [0, {V}) (got {vi.tolist()[:8]})")
+        if query_mask.shape[0] != B:
+            raise ValueError(f"localize_windows: query_mask has {query_mask.shape[0]} rows for B = {B} queries")
+        if duration is not None and tuple(duration.shape) != (B,):
+            raise ValueError(f"localize_windows: duration must be (B,) = ({B},) seconds (got {tuple(duration.shape)})")
+        starts, lens, vptr = (x.numpy() for x in window_plan(n, window, stride))
+        dev = raw.device
+        # per pair: its video's windows, in global window order (pair, then start)
+        nw = (vptr[1:] - vptr[:-1])[vi] if B else np.zeros(0, np.int64)
+        pair_ptr = np.concatenate([[0], np.cumsum(nw)]).astype(np.int64)
+        G = int(pair_ptr[-1])
+        if G * k_window >= 2 ** 31:
+            raise ValueError(f"localize_windows: {G} windows of {k_window} moments exceed the merge's 2**31 candidates")
+        wsel = np.concatenate([np.arange(vptr[v], vptr[v + 1]) for v in vi]).astype(np.int64) if G else np.zeros(0, np.int64)
+        offs = np.concatenate([[0], np.cumsum(n)]).astype(np.int64)
+        pair_of = np.repeat(np.arange(B, dtype=np.int64), nw)
+        w_start, w_len = starts[wsel], lens[wsel].astype(np.int64)
+        nf = np.minimum(w_len, T)
+        cells = np.array([cell_count(x, T, L) for x in nf], dtype=np.int64)                      # per window, as csrc/labels.hip forms it
+        # the whole plan in one pinned buffer, one asynchronous copy (the call never waits for the device)
+        host = np.concatenate([offs[vi[pair_of]] + w_start if G else np.zeros(0, np.int64), w_start, w_len, pair_of, pair_ptr, nw,
+                               n[vi]]).astype(np.int64)
+        plan = torch.from_numpy(host).pin_memory().to(dev, non_blocking=True)
+        cut = np.cumsum([0, G, G, G, G, B + 1, B, B])
+        rb_d, st_d, ln_d, po_d, pp_d, nw_d, nr_d = (plan[cut[q]:cut[q + 1]] for q in range(7))
+        ln_d = ln_d.to(torch.int32)
+        idx, score, count, chunks = _chunk_buffers(G, k_window, max_batch, dev)
+        with torch.no_grad(), torch.cuda.device(dev):
+            for c0, c1 in chunks:
+                vf, nfeats = sample_windows(raw, rb_d[c0:c1], ln_d[c0:c1], T, mode=mode)
+                m = build_masks_hip(nfeats, T, L)
+                rows = po_d[c0:c1]
+                qf, qm = query_features.index_select(0, rows), query_mask.index_select(0, rows)
+                with known_cells(self, int(cells[c0:c1].sum())):
+                    pm, ps, pe, _ = self._scores(vf, m["video_mask"], qf, qm, m["length_mask"], m["moment_mask"])
+                _top_moments_into(pm, ps, pe, m["moment_mask"], k_window, nms_thresh, idx[c0:c1], score[c0:c1], count[c0:c1])
+        r = merge_window_moments(idx, score, count, st_d, ln_d, pp_d, T, L, k=k, nms_thresh=nms_thresh)
+        r["n_windows"] = nw_d
+        if duration is not None:
+            d = duration.to(device=dev, dtype=torch.float32).reshape(B, 1, 1)
+            r["times"] = (r["span"] * d) / nr_d.to(torch.float32).reshape(B, 1, 1)
+        return r
+
+    # ---------------------------------------------------------------- corpus search
+    def _bank_plan(self, video_features, query_features):
+        """Whether pairs of these inputs score on the one-node path from banks (as score(): _plan == "node" and no keep_attention)."""
+        return not self.keep_attention and self._plan(video_features, query_features) == "node"
+
+    def encode_videos(self, video_features, video_mask, length_mask, moment_mask):
+        """A VideoBank of V videos: the projection with position embedding and mask runs once per video (smin_hip::smin_encode_videos),
+        not once per (video, query) pair.  ``video_features (V, T, Din)`` and the three masks as forward takes them.  One host read
+        (the videos' valid-cell counts); under torch.no_grad().  The bank is stale after a parameter update."""
+        require_hip_tensors("encode_videos", dict(video_features=video_features, video_mask=video_mask, length_mask=length_mask, moment_mask=moment_mask))
+        V = video_features.shape[0]
+        if video_features.dim() != 3 or V < 1 or video_mask.shape[0] != V or tuple(length_mask.shape) != (V, self.L) or tuple(moment_mask.shape) != (V, self.L, self.L):
+            raise ValueError(f"encode_videos: video_features (V, T, Din) with V >= 1, video_mask (V, T[, 1]), length_mask (V, L) and moment_mask (V, L, L); got "
+                             f"{tuple(video_features.shape)}, {tuple(video_mask.shape)}, {tuple(length_mask.shape)}, {tuple(moment_mask.shape)}")
+        with torch.no_grad(), torch.cuda.device(video_features.device):
+            vf = video_features.detach()
+            masks = [byte_mask(t) for t in (video_mask, length_mask, moment_mask)]
+            fv = None
+            if self.fused_core and self.backbone.videoencoder.fused(vf) and vf.shape[1] == self.T:
+                fv = _lib.load_torch().smin_encode_videos(vf, masks[0], self._native_params()[:3])
+            counts = masks[2].reshape(V, -1).ne(0).sum(dim=1).tolist()             # the bank's only host read
+        return VideoBank(fv, vf, masks[0], masks[1], masks[2], counts)
+
+    def encode_queries(self, query_features, query_mask):
+        """A QueryBank of Q queries: the two BiLSTM layers and the sentence feature run once per query
+        (smin_hip::smin_encode_queries).  ``query_features (Q, words, E)`` / ``query_mask`` as forward takes them.  No host read;
+        under torch.no_grad().  The bank is stale after a parameter update."""
+        require_hip_tensors("encode_queries", dict(query_features=query_features, query_mask=query_mask))
+        if query_features.dim() != 3 or query_features.shape[0] < 1:
+            raise ValueError(f"encode_queries: query_features (Q, words, E) with Q >= 1 (got {tuple(query_features.shape)})")
+        qm = query_mask_rows(query_features, query_mask, self.max_query_length)
+        with torch.no_grad(), torch.cuda.device(query_features.device):
+            qf = query_features.detach()
+            qm = byte_mask(qm)
+            fw = fs = None
+            if self.fused_core and self.backbone.queryencoder.fused() and qf.dtype == torch.float32:
+                fw, fs = _lib.load_torch().smin_encode_queries(qf, qm, self._native_params()[:19], self.max_query_length, self.lstm_hidden_size)
+            if qm.shape[1] < self.max_query_length:
+                qm = torch.nn.functional.pad(qm, (0, self.max_query_length - qm.shape[1]))
+        return QueryBank(fw, fs, qf, qm)
+
+    @staticmethod
+    def _pair_lists(what, videos, queries, video_index, query_index):
+        _require_banks(what, videos, queries)
+        vi, qi = host_array(video_index), host_array(query_index)
+        if vi.shape[0] != qi.shape[0]:
+            raise ValueError(f"{what}: video_index and query_index must have one length (got {vi.shape[0]} and {qi.shape[0]})")
+        V, Q = len(videos), len(queries)
+        if vi.size and (vi.min() < 0 or vi.max() >= V or qi.min() < 0 or qi.max() >= Q):
+            raise ValueError(f"{what}: video_index must lie in [0, {V}) and query_index in [0, {Q})")
+        return vi, qi
+
+    def _score_pairs(self, videos, queries, vi, qi, vi_d, qi_d):
+        """score_pairs of checked host lists vi / qi (P >= 1) whose int32 device copies are vi_d / qi_d.  No host read."""
+        cells = sum(videos.cell_counts[v] for v in vi)                            # host arithmetic: the scorer asks the device nothing
+        with known_cells(self, cells), torch.no_grad(), torch.cuda.device(vi_d.device):
+            if not self._bank_plan(videos.video_features, queries.query_features):
+                # as score(): configurations off the one-node path (and keep_attention) run the forward, here on expanded pairs
+                qm = queries.query_mask[:, :queries.query_features.shape[1]]
+                return self.score(videos.video_features.index_select(0, vi_d), videos.video_mask.index_select(0, vi_d),
+                                  queries.query_features.index_select(0, qi_d), qm.index_select(0, qi_d),
+                                  videos.length_mask.index_select(0, vi_d), videos.moment_mask.index_select(0, vi_d))
+            if videos.fv is None or queries.fw is None:
+                raise ValueError("score_pairs: a bank was encoded while the module was off the one-node path (SMIN._plan); encode it again")
+            return _lib.load_torch().smin_score_pairs(
+                videos.fv, queries.fw, queries.fs, videos.video_mask, queries.query_mask, videos.length_mask, videos.moment_mask, vi_d, qi_d,
+                self._native_params(), self.T, self.L, self.C, len(self.smis), self.max_query_length, self.lstm_hidden_size, **self._score_options())
+
+    def score_pairs(self, videos, queries, video_index, query_index):
+        """(pm, ps, pe, pa) as score() returns them for the P pairs (videos[video_index[p]], queries[query_index[p]]) of a VideoBank
+        and a QueryBank: neither encoder runs again, and no pair carries a copy of its video's features.  ``video_index`` /
+        ``query_index``: host int sequences of one length P >= 1, any lists, repeats included; an index out of range raises
+        ValueError.  On the one-node path this is smin_hip::smin_score_pairs: the pairs' masks gathered (bytes), smin_pair_assemble
+        where smin_score has its backbone, then smin_score's own code -- the bits of score() on the expanded batch.  Where score()
+        would run the forward instead (_plan != "node", keep_attention) the pairs are expanded and scored by score().  The valid-cell
+        count comes from the bank, so nothing is read back."""
+        vi, qi = self._pair_lists("score_pairs", videos, queries, video_index, query_index)
+        if vi.shape[0] < 1:
+            raise ValueError("score_pairs: at least one pair")
+        require_hip_tensors("score_pairs", dict(videos=videos.video_features, queries=queries.query_features), must="hold HIP tensors")
+        dev = videos.video_features.device
+        idx = torch.from_numpy(np.concatenate([vi, qi]).astype(np.int32)).pin_memory().to(dev, non_blocking=True)
+        return self._score_pairs(videos, queries, vi, qi, idx[:vi.shape[0]], idx[vi.shape[0]:])
+
+    def _search_plan(self, what, videos, queries, pairs, k, k_video, max_batch, duration):
+        k_video = k if k_video is None else k_video
+        require_ints(what, ("k", k, 1, MAX_K), ("k_video", k_video, 1, MAX_K), ("max_batch", max_batch, 1, 65535))
+        _require_banks(what, videos, queries)
+        V, Q = len(videos), len(queries)
+        if pairs is None:
+            qi, vi = np.repeat(np.arange(Q, dtype=np.int64), V), np.tile(np.arange(V, dtype=np.int64), Q)
+        else:
+            pr = host_array(pairs, shape=None)
+            if pr.size == 0:
+                pr = pr.reshape(0, 2)
+            if pr.ndim != 2 or pr.shape[1] != 2:
+                raise ValueError(f"{what}: pairs must be (P, 2) rows of (query, video) (got {pr.shape})")
+            order = np.lexsort((pr[:, 1], pr[:, 0]))                               # by (query, video)
+            qi, vi = pr[order, 0], pr[order, 1]
+        vi, qi = self._pair_lists(what, videos, queries, vi, qi)
+        if vi.size > 1 and bool(((qi[1:] == qi[:-1]) & (vi[1:] == vi[:-1])).any()):
+            raise ValueError(f"{what}: a (query, video) pair is listed more than once")
+        if duration is not None and tuple(duration.shape) != (V,):
+            raise ValueError(f"{what}: duration must be (V,) = ({V},) seconds (got {tuple(duration.shape)})")
+        require_hip_tensors(what, dict(videos=videos.video_features, queries=queries.query_features), must="hold HIP tensors")
+        pair_ptr = np.concatenate([[0], np.cumsum(np.bincount(qi, minlength=Q))]).astype(np.int64)
+        return int(k), int(k_video), vi, qi, pair_ptr
+
+    @staticmethod
+    def _search_result(r, duration, L):
+        if duration is not None:
+            # moments._times' formula on each moment's own video: (i * duration / L, (j + 1) * duration / L) in fp32, NaN for empty slots
+            # (formed without a constant from the host: the call reads and writes no host memory)
+            Q, k = r["video"].shape
+            d = duration.to(device=r["video"].device, dtype=torch.float32)[r["video"].clamp_min(0)].reshape(Q, k, 1)
+            edge = r["idx"].to(torch.float32)
+            edge[..., 1] += 1.0
+            t = edge * d / L
+            r["times"] = torch.where(r["idx"] >= 0, t, torch.full_like(t, float("nan")))
+        return r
+
+    def search(self, videos, queries, pairs=None, k=5, k_video=None, nms_thresh=0.5, duration=None, max_batch=64):
+        """Which video, and where: the k best moments of each of the Q queries of a QueryBank over the videos of a VideoBank.
+
+        ``pairs``: None -- every query against every video --, or a host (P, 2) array of (query, video) rows, in any order (sorted
+        here by (query, video)); a repeated pair raises ValueError.  The pairs are scored in chunks of at most ``max_batch``
+        (score_pairs: from the banks, no encoder runs again; each chunk's valid-cell count is the sum of the bank's cell_counts,
+        nothing is read back), each chunk is cut to its ``k_video`` (default k) best moments per pair by top_moments' kernels
+        (greedy NMS at ``nms_thresh``), and one smin_corpus_topk ranks each query's moments across its videos: higher score first,
+        ties -> lower video, then lower slot.  Every listed pair is scored by the full model.
+
+        Returns a dict: ``video (Q, k)`` int64 (-1 for empty slots), ``idx (Q, k, 2)`` int64 start / end clip (-1), ``score (Q, k)``
+        (0), ``count (Q,)`` int32; with ``duration`` (V,) seconds also ``times (Q, k, 2)``: top_moments' formula on
+        ``duration[video]``, NaN for empty slots.  Scores come from score_pairs (forward_only_scoring or not: a bank has no graph),
+        in the contraction mode of set_gemm_mode.  No host synchronisation."""
+        k, k_video, vi, qi, pair_ptr = self._search_plan("search", videos, queries, pairs, k, k_video, max_batch, duration)
+        dev, L, P = videos.video_features.device, self.L, vi.shape[0]
+        # the whole plan in one pinned buffer, one asynchronous copy (the call never waits for the device)
+        plan = torch.from_numpy(np.concatenate([vi, qi, pair_ptr]).astype(np.int32)).pin_memory().to(dev, non_blocking=True)
+        vi_d, qi_d, pp_d = plan[:P], plan[P:2 * P], plan[2 * P:]
+        idx, score, count, chunks = _chunk_buffers(P, k_video, max_batch, dev)
+        with torch.no_grad(), torch.cuda.device(dev):
+            for c0, c1 in chunks:
+                pm, ps, pe, _ = self._score_pairs(videos, queries, vi[c0:c1], qi[c0:c1], vi_d[c0:c1], qi_d[c0:c1])
+                mm = videos.moment_mask.index_select(0, vi_d[c0:c1])
+                _top_moments_into(pm, ps, pe, mm, k_video, nms_thresh, idx[c0:c1], score[c0:c1], count[c0:c1])
+            r = corpus_topk(score, idx, count, vi_d, pp_d, k=k)
+        return self._search_result(r, duration, L)
+
+    def search_torch(self, videos, queries, pairs=None, k=5, k_video=None, nms_thresh=0.5, duration=None, max_batch=64, scorer=None):
+        """``search`` restated: the same plan and chunking, each chunk's pairs expanded and scored by score(), cut by top_moments and
+        merged by moments.corpus_topk_torch.  Kept under its own name as what the tests compare against -- nothing routes here.
+        ``scorer(video_index, query_index) -> (pm, ps, pe, pa)`` replaces score() on the expanded pairs (the tests feed it
+        score_pairs, to compare the ranking on equal scores)."""
+        k, k_video, vi, qi, pair_ptr = self._search_plan("search_torch", videos, queries, pairs, k, k_video, max_batch, duration)
+        dev, L, P = videos.video_features.device, self.L, vi.shape[0]
+        idx, score, count, chunks = _chunk_buffers(P, k_video, max_batch, dev)
+        with torch.no_grad():
+            for c0, c1 in chunks:
+                vi_d, qi_d = (torch.from_numpy(x[c0:c1].copy()).to(dev) for x in (vi, qi))
+                mm = videos.moment_mask.index_select(0, vi_d)
+                if scorer is not None:
+                    pm, ps, pe, _ = scorer(vi[c0:c1], qi[c0:c1])
+                else:
+                    qm = queries.query_mask[:, :queries.query_features.shape[1]]
+                    pm, ps, pe, _ = self.score(videos.video_features.index_select(0, vi_d), videos.video_mask.index_select(0, vi_d),
+                                               queries.query_features.index_select(0, qi_d), qm.index_select(0, qi_d),
+                                               videos.length_mask.index_select(0, vi_d), mm)
+                t = top_moments(pm, ps, pe, mm, k=k_video, nms_thresh=nms_thresh)
+                idx[c0:c1], score[c0:c1], count[c0:c1] = t["idx"], t["score"], t["count"]
+        r = corpus_topk_torch(score, idx, count, torch.from_numpy(vi).to(dev), torch.from_numpy(pair_ptr).to(dev), k=k)
+        return self._search_result(r, duration, L)
+

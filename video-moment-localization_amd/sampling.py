@@ -32,6 +32,8 @@ from torch.autograd import Function
 import numpy as np
 import torch
 
+from ._host import host_array
+
 MODES = {"pick": 0, "mean": 1}
 
 
@@ -68,13 +70,9 @@ def mean_windows(n, T):
     return a
 
 
-def _lengths_host(x):
-    return np.asarray(x.cpu() if isinstance(x, torch.Tensor) else x, dtype=np.int64).reshape(-1)
-
-
 def _check_spos(spos, lengths, T, mode):
     """Host-side validation of start offsets against the reference's range (ValueError)."""
-    s = np.asarray(spos.cpu() if isinstance(spos, torch.Tensor) else spos, dtype=np.int64).reshape(-1)
+    s = host_array(spos)
     if s.shape[0] != lengths.shape[0]:
         raise ValueError(f"spos has {s.shape[0]} entries for {lengths.shape[0]} samples")
     if mode == "mean" and s.any():
@@ -99,7 +97,7 @@ def _pack(raw, offsets_or_lengths):
         return torch.cat([r.reshape(-1, r.shape[-1]) for r in raw], 0), lengths, None
     if isinstance(offsets_or_lengths, torch.Tensor) and offsets_or_lengths.is_cuda:
         return raw, None, offsets_or_lengths
-    return raw, _lengths_host(offsets_or_lengths), None
+    return raw, host_array(offsets_or_lengths), None
 
 
 class _SampleClipsFn(Function):
@@ -203,7 +201,7 @@ def sample_clips_torch(raw, offsets_or_lengths, T, spos=None, mode="pick"):
         packed = np.concatenate(rows, 0) if rows else np.zeros((0, Din), np.float32)
     else:
         packed = np.asarray(raw.detach().cpu() if isinstance(raw, torch.Tensor) else raw, dtype=np.float32)
-        lengths = _lengths_host(offsets_or_lengths)
+        lengths = host_array(offsets_or_lengths)
         if isinstance(offsets_or_lengths, torch.Tensor) and offsets_or_lengths.is_cuda:
             lengths = np.diff(lengths)                                        # device offsets -> lengths
         Din = packed.shape[1]
@@ -501,7 +499,7 @@ def window_plan(lengths, window, stride):
     those ends before ``n``.  Windows are ordered by video, then by start.  Returns CPU tensors ``(starts (W,) int64`` relative to the
     video, ``lens (W,) int32, ptr (V + 1,) int64)``: video ``v`` owns windows ``ptr[v] .. ptr[v + 1]``.  Needs ``window >= 1``,
     ``stride >= 1`` and ``0 <= n < 2**24``."""
-    n = _lengths_host(lengths)
+    n = host_array(lengths)
     window, stride = int(window), int(stride)
     if window < 1:
         raise ValueError(f"window_plan: window must be >= 1 (got {window})")
@@ -538,9 +536,9 @@ def window_annotations(times, duration, lengths, win_start, win_len, T):
     window: a window holding part of a long moment gets IoUs below 1, one that misses it ``sm = 0`` everywhere, and sigma comes
     from the whole moment.  The targets are then those of dataset.py:95-126 for ``(times_w, duration_w, nfeats = min(win_len, T))``.
     Returns ``(times_w (B, 2), duration_w (B,))`` float64 numpy arrays."""
-    t = np.asarray(times.cpu() if isinstance(times, torch.Tensor) else times, dtype=np.float64).reshape(-1, 2)
-    d = np.asarray(duration.cpu() if isinstance(duration, torch.Tensor) else duration, dtype=np.float64).reshape(-1)
-    n, s, w = _lengths_host(lengths), _lengths_host(win_start), _lengths_host(win_len)
+    t = host_array(times, np.float64, (-1, 2))
+    d = host_array(duration, np.float64)
+    n, s, w = host_array(lengths), host_array(win_start), host_array(win_len)
     B = t.shape[0]
     if not (d.shape[0] == n.shape[0] == s.shape[0] == w.shape[0] == B):
         raise ValueError(f"window_annotations: times (B, 2) with duration, lengths, win_start, win_len (B,) (got B = {B} and "
@@ -558,8 +556,8 @@ def draw_windows(lengths, gt_rows, window, stride, rng, p_overlap):
     candidates; one ``rng.integers(0, len(set))`` picks it.  ``p_overlap`` is the training policy (1: always a window that sees the
     moment where one exists; 0: uniform over the grid).  Returns ``(win_start (B,) int64, win_len (B,) int32)``; a video of 0 rows
     raises ValueError."""
-    n = _lengths_host(lengths)
-    gt = np.asarray(gt_rows.cpu() if isinstance(gt_rows, torch.Tensor) else gt_rows, dtype=np.float64).reshape(-1, 2)
+    n = host_array(lengths)
+    gt = host_array(gt_rows, np.float64, (-1, 2))
     if gt.shape[0] != n.shape[0]:
         raise ValueError(f"draw_windows: gt_rows must be (B, 2) for B = {n.shape[0]} videos (got {gt.shape})")
     win_start, win_len = np.zeros(n.shape[0], np.int64), np.zeros(n.shape[0], np.int32)
@@ -598,7 +596,7 @@ def sample_windows(raw, row_begin, lens, T, mode="pick"):
     elif any(on_dev):
         raise ValueError("row_begin and lens must both be device tensors or both host values")
     else:
-        b, n = _lengths_host(row_begin), _lengths_host(lens)
+        b, n = host_array(row_begin), host_array(lens)
         if b.shape != n.shape:
             raise ValueError(f"row_begin has {b.shape[0]} entries, lens {n.shape[0]}")
         if b.size and (b.min() < 0 or n.min() < 0 or n.max() >= 2 ** 31 or (b + n).max() > raw.shape[0]):
@@ -620,7 +618,7 @@ def sample_windows(raw, row_begin, lens, T, mode="pick"):
 def sample_windows_torch(raw, row_begin, lens, T, mode="pick"):
     """``sample_windows`` restated: ``sample_clips_torch`` of each row range on its own (CPU tensors out)."""
     packed = raw.detach().cpu() if isinstance(raw, torch.Tensor) else torch.as_tensor(np.asarray(raw, np.float32))
-    b, n = _lengths_host(row_begin), _lengths_host(lens)
+    b, n = host_array(row_begin), host_array(lens)
     Din = packed.shape[1]
     if b.shape[0] == 0:
         return torch.zeros((0, T, Din), dtype=torch.float32), torch.zeros((0,), dtype=torch.int32)

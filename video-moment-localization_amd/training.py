@@ -5,6 +5,8 @@ own names as a second restatement the tests compare against -- nothing routes to
 import torch
 import torch.nn.functional as F
 
+from ._host import _require_hip, host_array, known_cells
+
 
 def bce_loss(p, y, s, mask):
     """reference main.py:89-108.  The reference builds BCELoss(reduction=None), which raises on every torch
@@ -28,13 +30,6 @@ def loss_fn_torch(pm, ym, sm, moment_mask, ps, ys, ss, pe, ye, se, pa, ya, lengt
 
 
 NATIVE_LOSS = True          # loss through the torch-extension binding (False: the ctypes / Python autograd host, same kernels)
-
-
-def _require_hip(t, what):
-    if not t.is_cuda:
-        from ._lib import SminHipError
-        raise SminHipError(f"{what} runs on a HIP device only (got a CPU tensor); there is no CPU fallback -- "
-                           f"the plain-torch restatement is available under the explicit name {what}_torch")
 
 
 def loss_fn(pm, ym, sm, moment_mask, ps, ys, ss, pe, ye, se, pa, ya, length_mask):
@@ -202,24 +197,6 @@ def _inputs(batch):
     return [batch[k] for k in MODEL_INPUTS]
 
 
-class _handed_count:
-    """For one call of the model: the batch's host-computed cell count (feeder.FedBatch.cell_count) as ``model.known_cell_count``,
-    so the forward sizes its per-cell tensors without asking the device; the previous value is restored afterwards.  A count that
-    does not match the mask sets the device's layout_status word, which EpochMeter.result() reads."""
-
-    def __init__(self, model, batch):
-        self.model, self.count = model, getattr(batch, "cell_count", None)
-
-    def __enter__(self):
-        if self.count is not None:
-            self.known = self.model.known_cell_count
-            self.model.known_cell_count = int(self.count)
-
-    def __exit__(self, *exc):
-        if self.count is not None:
-            self.model.known_cell_count = self.known
-
-
 def _meter_for(meter, batch):
     if meter is None:
         from .meter import EpochMeter
@@ -242,7 +219,7 @@ def train_epoch(model, optimizer, batches, meter=None):
     for batch in batches:
         meter = _meter_for(meter, batch)
         optimizer.zero_grad()
-        with _handed_count(model, batch):
+        with known_cells(model, getattr(batch, "cell_count", None)):
             out = model(*_inputs(batch))
         loss = _loss_of(out, batch)
         meter.update(out[0], out[1], out[2], batch["moment_mask"], batch["sm"], loss=loss.detach())
@@ -259,7 +236,7 @@ def eval_epoch(model, batches, meter=None):
     with torch.no_grad():
         for batch in batches:
             meter = _meter_for(meter, batch)
-            with _handed_count(model, batch):
+            with known_cells(model, getattr(batch, "cell_count", None)):
                 out = model.score(*_inputs(batch)) if getattr(model, "forward_only_scoring", False) else model(*_inputs(batch))
             loss = _loss_of(out, batch)
             meter.update(out[0], out[1], out[2], batch["moment_mask"], batch["sm"], loss=loss)
@@ -273,7 +250,7 @@ def test_model(model, batches, meter=None):
     with torch.no_grad():
         for batch in batches:
             meter = _meter_for(meter, batch)
-            with _handed_count(model, batch):
+            with known_cells(model, getattr(batch, "cell_count", None)):
                 out = model.score(*_inputs(batch)) if getattr(model, "forward_only_scoring", False) else model(*_inputs(batch))
             meter.update(out[0], out[1], out[2], batch["moment_mask"], batch["sm"])
     return meter.result()
@@ -301,11 +278,10 @@ def test_model_windows(model, groups, meter=None, *, window=None, stride=None, k
             raise ValueError(f"test_model_windows: k = {k} moments per pair cannot give the meter's R@{max(meter.n)}")
         out = model.localize_windows(raw, group["lengths"], group["query_features"], group["query_mask"], video_index=group.get("video_index"),
                                      window=window, stride=stride, k=k, k_window=k_window, nms_thresh=nms_thresh, mode=mode, max_batch=max_batch)
-        host = lambda x, dt: np.asarray(x.cpu() if isinstance(x, torch.Tensor) else x, dtype=dt)
-        n = host(group["lengths"], np.int64).reshape(-1)
+        n = host_array(group["lengths"])
         vi = group.get("video_index")
-        rows = n if vi is None else n[host(vi, np.int64).reshape(-1)]
-        times, duration = host(group["times"], np.float64).reshape(-1, 2), host(group["duration"], np.float64).reshape(-1)
+        rows = n if vi is None else n[host_array(vi)]
+        times, duration = host_array(group["times"], np.float64, (-1, 2)), host_array(group["duration"], np.float64)
         if times.shape[0] != rows.shape[0] or duration.shape[0] != rows.shape[0]:
             raise ValueError(f"test_model_windows: times (B, 2) and duration (B,) must cover the group's B = {rows.shape[0]} pairs "
                              f"(got {times.shape}, {duration.shape})")
