@@ -50,7 +50,9 @@ extern "C" {
  * lists into one -- smin_row_lists_merge and smin_row_lists_merge_workspace_bytes (data-parallel ranks, micro-batches); with it
  * smin_row_adam_step takes lists of up to 65536 slots where it took 4096 (it rejected longer ones before any launch); corpus search
  * over banks of encoded videos and queries -- smin_pair_assemble (the backbone's outputs of indexed pairs) and smin_corpus_topk (one
- * ranked list per query across videos) */
+ * ranked list per query across videos); evaluation of corpus search -- smin_search_merge (ranked lists of disjoint video shards into
+ * one list per query) and smin_corpus_meter_update with smin_corpus_meter_ws_bytes (VCMR and VR recall into the epoch meter's kind of
+ * accumulator) */
 #define SMIN_HIP_ABI_VERSION 2
 
 int smin_abi_version(void);
@@ -408,6 +410,28 @@ size_t smin_span_meter_ws_bytes(int B, int nn, int nm);
 int smin_span_meter_update(void* stream, const float* span, const int32_t* count, const float* gt, int B, int k,
                            const int* n_list, int nn, const float* m_list, int nm, double* acc, void* ws, size_t ws_bytes);
 
+/* ---- corpus metric (csrc/metrics.hip): video-corpus moment retrieval (VCMR) recall R@n, IoU=m, video retrieval
+ * (VR) recall R@n and the top-1 IoU of ranked lists over a corpus -- SMIN.search / smin_search_merge output -- against one ground-truth
+ * moment of one ground-truth video per query, accumulated as the span metric accumulates.
+ * Inputs: video [Q][k] int64, span [Q][k][2] fp32 (st, en), count [Q] int32 (read clamped to [0, k]; entries r >= count[q] are empty
+ * and never read), gt_video [Q] int64, gt [Q][2] fp32 (gs, ge) in span's unit: seconds, or clip edges (i, j + 1).
+ * Per query, over the entries r < cnt = clamp(count[q], 0, k):
+ *   iou[r] = the span metric's IoU of span[r] with gt (fp32, each operation rounded once) if video[r] == gt_video[q], else 0;
+ *   top-1 IoU: iou[0], 0 when cnt == 0;
+ *   VCMR hit for (n_list[a], m_list[c]): some r < min(n_list[a], cnt) with iou[r] > m_list[c] (strict);
+ *   VR hit for n_list[a]: some entry has video[r] == gt_video[q] and, for the first such r, the number of distinct videos among the
+ *     entries 0 .. r-1 is < n_list[a] (the ground-truth video is among the first n distinct videos of the list);
+ *   a query whose ground-truth video is not listed is a miss everywhere.
+ * acc [4 + nn * nm + nn] doubles: [0] += Q, [1] and [2] are not touched, [3] += the sum of the top-1 IoU, [4 + a * nm + c] += the VCMR
+ * hits, [4 + nn * nm + a] += the VR hits; every sum is s = 0.0; for q = 0 .. Q-1: s += (double)x[q]; acc[slot] += s (the epoch
+ * meter's closing wave over nn * nm + nn slots).  No atomics, no host read: ALL UPDATES OF ONE acc MUST BE ISSUED ON ONE STREAM.
+ * Limits: 1 <= k <= 64, 1 <= nn <= 64, 1 <= nm <= 16, every n_list[a] in [1, k], Q >= 0 (else a negative code, nothing launched);
+ * Q = 0 is a no-op.  n_list / m_list: host arrays.  ws: device scratch of at least the _ws_bytes size (0: Q < 1 or nn / nm rejected). */
+size_t smin_corpus_meter_ws_bytes(int Q, int nn, int nm);
+int smin_corpus_meter_update(void* stream, const int64_t* video, const float* span, const int32_t* count, const int64_t* gt_video,
+                             const float* gt, int Q, int k, const int* n_list, int nn, const float* m_list, int nm, double* acc,
+                             void* ws, size_t ws_bytes);
+
 /* ---- content stream (reference models.py:242-276 + 115-119, re-associated): the content unit's output
  *   f_c' = m*(cc Wc^T + bc) + f_c + hbar   (models.py:269-276)
  * is consumed only by the next unit's linear_c_hat (models.py:247) and, through mean_c, by the moment unit
@@ -713,6 +737,25 @@ int smin_pair_assemble(void* stream, const float* fv, const float* fs_bank, cons
 int smin_corpus_topk(void* stream, const float* pair_score, const int64_t* pair_idx, const int32_t* pair_count, const int32_t* pair_video,
                      const int32_t* pair_ptr, int Q, int k_video, int K, int64_t* out_video, int64_t* out_idx, float* out_score,
                      int32_t* out_count);
+
+/* smin_search_merge: S ranked lists per query, each over its own shard of the videos, into the K best of all shards; one launch, one
+ * workgroup per query, no workspace, no host read; capturable.
+ * Inputs.  video, idx, score, count: HOST tables of S device pointers, read before the call returns (they travel to the kernel by
+ *   value); list s is smin_corpus_topk's output at K = k_list[s]: video [Q][k_s] int64, idx [Q][k_s][2] int64, score [Q][k_s] fp32,
+ *   count [Q] int32.  k_list, video_offset: host [S]; video_offset[s] is added to list s's video ids (the shard's first global id).
+ * Candidates.  Position p of list s for query q iff p < clamp(count_s[q], 0, k_s); what lies behind the counts is never read.
+ * Order.  Higher score first (-0 counts as +0); ties go to the lower global video video_s[q][p] + video_offset[s], then to the lower
+ *   s, then to the lower p.  EACH LIST IS ASSUMED ORDERED AS smin_corpus_topk ORDERS IT (not checked): then, for shards of disjoint
+ *   videos given in ascending offset, the result is bit for bit smin_corpus_topk's list of the whole corpus, merged at once or folded
+ *   one shard after another.  Global video ids must lie in [0, 2^31): the order key holds them as int32.
+ * Outputs.  As smin_corpus_topk: out_video [Q][K] int64 global ids, out_idx [Q][K][2], out_score [Q][K] (idx and score copied bit for
+ *   bit), out_count [Q]; empty slots -1 / -1 / 0.
+ * Limits.  1 <= S <= 16, 1 <= K <= 64, 1 <= k_list[s] <= 64, 0 <= video_offset[s] < 2^31, Q >= 0 (Q == 0: returns 0, nothing launched).
+ * Rejection.  A nonzero status before any launch for S, K or a k out of range, Q < 0, and with Q > 0 a NULL table, table entry or
+ *   output, an offset out of range, or an output that is one of the input pointers. */
+int smin_search_merge(void* stream, int S, const int64_t* const* video, const int64_t* const* idx, const float* const* score,
+                      const int32_t* const* count, const int32_t* k_list, const int64_t* video_offset, int Q, int K,
+                      int64_t* out_video, int64_t* out_idx, float* out_score, int32_t* out_count);
 
 /* ---- stand-alone fp32 MFMA GEMM  C[M][N] = A[M][K] * B[N][K]^T  (used by tests and bench.py's
  * roofline probe; same engine as every contraction above). */

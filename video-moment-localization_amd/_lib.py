@@ -123,6 +123,9 @@ SIGNATURES = {
     "smin_row_lists_merge": [_vp] * 5 + [_i] * 3 + [_vp] * 5 + [_vp, _sz],
     "smin_pair_assemble": [_vp] * 6 + [_i] * 6 + [_vp] * 3,
     "smin_corpus_topk": [_vp] * 6 + [_i] * 3 + [_vp] * 4,
+    "smin_search_merge": [_vp, _i] + [_vp] * 6 + [_i] * 2 + [_vp] * 4,
+    "smin_corpus_meter_ws_bytes": [_i] * 3,
+    "smin_corpus_meter_update": [_vp] * 6 + [_i] * 2 + [_vp, _i, _vp, _i] + [_vp, _vp, _sz],
 }
 _RESTYPE = {"smin_target_arch": ctypes.c_char_p, "smin_workspace_bytes": _sz,
             "smin_content_attn_bwd_workspace_bytes": _sz, "smin_linear_rows_bwd_workspace_bytes": _sz,
@@ -131,7 +134,7 @@ _RESTYPE = {"smin_target_arch": ctypes.c_char_p, "smin_workspace_bytes": _sz,
             "smin_word_prep_bwd_workspace_bytes": _sz, "smin_score_tail_ws_bytes": _sz,
             "smin_col_sum_workspace_bytes": _sz, "smin_top_moments_ws_bytes": _sz, "smin_boundary_unit_bwd_ws_bytes": _sz, "smin_compute_ious_nms_ws_bytes": _sz,
             "smin_epoch_meter_ws_bytes": _sz, "smin_span_meter_ws_bytes": _sz, "smin_adam_ws_bytes": _sz,
-            "smin_row_lists_merge_workspace_bytes": _sz}
+            "smin_row_lists_merge_workspace_bytes": _sz, "smin_corpus_meter_ws_bytes": _sz}
 
 _lib = None
 _ws = {}

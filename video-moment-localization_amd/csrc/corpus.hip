@@ -2,8 +2,11 @@
 // video and once per query; the first place where a video and a query meet is the Hadamard product f = f_v * f_s (reference
 // models.py:81), so a scored (video, query) pair starts here:
 //   smin_pair_assemble  forms f, f_w, f_s of P pairs from the banks through two index lists, in one launch;
-//   smin_corpus_topk    merges the pairs' top_moments lists into one ranked list per query across videos.
-// Neither has a backward: the path only scores.
+//   smin_corpus_topk    merges the pairs' top_moments lists into one ranked list per query across videos;
+//   smin_search_merge   merges up to 16 such ranked lists of disjoint video shards into one: the same K-round
+//                       selection (topk_rounds) over another way of reading candidate c, so a merge of the shards' lists is the list
+//                       smin_corpus_topk gives on the whole corpus.
+// None has a backward: the path only scores.
 #include "common.h"
 #include "smin_hip.h"
 
@@ -81,28 +84,23 @@ __device__ __forceinline__ Key block_max_key(Key v, Key* red)
     return m;
 }
 
-__global__ __launch_bounds__(CT)
-void corpus_topk_kernel(const float* __restrict__ pair_score, const long long* __restrict__ pair_idx, const int* __restrict__ pair_count,
-                        const int* __restrict__ pair_video, const int* __restrict__ pair_ptr, int kv, int K,
-                        long long* __restrict__ out_video /* [Q][K] */, long long* __restrict__ out_idx /* [Q][K][2] */,
-                        float* __restrict__ out_score /* [Q][K] */, int* __restrict__ out_count)
+// The K rounds over a source of candidates.  Src::read(c, slot, w, score, video) says whether candidate c < ncand exists and gives
+// its key parts (slot < 64 and w < 2^56: the key's two low fields, lower first); Src::emit(slot, w, ...) copies the picked one out.
+template <class Src>
+__device__ __forceinline__ void topk_rounds(const Src& src, long long ncand, int K, long long* __restrict__ out_video /* [Q][K] */,
+                                            long long* __restrict__ out_idx /* [Q][K][2] */, float* __restrict__ out_score /* [Q][K] */,
+                                            int* __restrict__ out_count)
 {
     __shared__ Key red[CT / 64];
     const int b = blockIdx.x, t = threadIdx.x;
-    const long long g0 = max(pair_ptr[b], 0);
-    const long long g1 = max((long long)pair_ptr[b + 1], g0);
-    const bool lists = pair_score && pair_idx && pair_count && pair_video;     // (NULL lists: no query may have a pair, none is read)
-    const long long nslot = lists ? (g1 - g0) * kv : 0;          // candidate c = pair ordinal * kv + slot
     Key cursor; cursor.hi = ~0ull; cursor.lo = ~0ull;
     int nk = 0;
     for (; nk < K; ++nk) {
         Key best; best.hi = 0; best.lo = 0;
-        for (long long c = t; c < nslot; c += CT) {
-            const long long w = c / kv;
-            const int slot = (int)(c - w * kv);
-            const long long g = g0 + w;
-            if (slot >= min(pair_count[g], kv)) continue;        // (a negative count lists nothing)
-            const Key key = make_key(pair_score[g * kv + slot], pair_video[g], slot, w);
+        for (long long c = t; c < ncand; c += CT) {
+            int slot, video; long long w; float score;
+            if (!src.read(c, slot, w, score, video)) continue;
+            const Key key = make_key(score, video, slot, w);
             if (!key_less(key, cursor) || !key_less(best, key)) continue;
             best = key;
         }
@@ -112,11 +110,8 @@ void corpus_topk_kernel(const float* __restrict__ pair_score, const long long* _
         if (t == 0) {
             const long long w = (long long)(0x00ffffffffffffffull - (best.lo & 0x00ffffffffffffffull));
             const int slot = CORPUS_MAX_K - 1 - (int)(best.lo >> 56);
-            const long long g = g0 + w, c = g * kv + slot;
             const size_t o = (size_t)b * K + nk;
-            out_video[o] = pair_video[g];
-            out_idx[2 * o] = pair_idx[2 * c]; out_idx[2 * o + 1] = pair_idx[2 * c + 1];
-            out_score[o] = pair_score[c];
+            src.emit(slot, w, out_video + o, out_idx + 2 * o, out_score + o);
         }
         __syncthreads();
     }
@@ -127,6 +122,80 @@ void corpus_topk_kernel(const float* __restrict__ pair_score, const long long* _
         out_score[o] = 0.f;
     }
     if (t == 0) out_count[b] = nk;
+}
+
+// smin_corpus_topk's candidates: c = pair ordinal * kv + slot over the query's pairs g0 .. ; key parts (slot, pair ordinal)
+struct PairLists {
+    const float* score; const long long* idx; const int* count; const int* video;
+    long long g0; int kv;
+    __device__ __forceinline__ bool read(long long c, int& slot, long long& w, float& sc, int& vid) const
+    {
+        w = c / kv;
+        slot = (int)(c - w * kv);
+        const long long g = g0 + w;
+        if (slot >= min(count[g], kv)) return false;             // (a negative count lists nothing)
+        sc = score[g * kv + slot];
+        vid = video[g];
+        return true;
+    }
+    __device__ __forceinline__ void emit(int slot, long long w, long long* ov, long long* oi, float* os) const
+    {
+        const long long g = g0 + w, c = g * kv + slot;
+        *ov = video[g];
+        oi[0] = idx[2 * c]; oi[1] = idx[2 * c + 1];
+        *os = score[c];
+    }
+};
+
+__global__ __launch_bounds__(CT)
+void corpus_topk_kernel(const float* __restrict__ pair_score, const long long* __restrict__ pair_idx, const int* __restrict__ pair_count,
+                        const int* __restrict__ pair_video, const int* __restrict__ pair_ptr, int kv, int K,
+                        long long* __restrict__ out_video, long long* __restrict__ out_idx, float* __restrict__ out_score, int* __restrict__ out_count)
+{
+    const int b = blockIdx.x;
+    const long long g0 = max(pair_ptr[b], 0);
+    const long long g1 = max((long long)pair_ptr[b + 1], g0);
+    const bool lists = pair_score && pair_idx && pair_count && pair_video;     // (NULL lists: no query may have a pair, none is read)
+    const PairLists src{pair_score, pair_idx, pair_count, pair_video, g0, kv};
+    topk_rounds(src, lists ? (g1 - g0) * kv : 0, K, out_video, out_idx, out_score, out_count);
+}
+
+// smin_search_merge's candidates: S ranked lists of k[s] slots per query, c = base[s] + p (base: the exclusive prefix of k); key
+// parts (list s <= 15, position p).  Passed to the kernel by value: the host tables need no copy of their own.
+constexpr int MERGE_MAX_S = 16;
+struct RankedTables {
+    const long long* video[MERGE_MAX_S]; const long long* idx[MERGE_MAX_S]; const float* score[MERGE_MAX_S]; const int* count[MERGE_MAX_S];
+    long long offset[MERGE_MAX_S];
+    int k[MERGE_MAX_S], base[MERGE_MAX_S + 1], S;
+};
+struct RankedLists {
+    const RankedTables& tb; long long q;
+    __device__ __forceinline__ bool read(long long c, int& slot, long long& w, float& sc, int& vid) const
+    {
+        int s = 0;
+        while (s + 1 < tb.S && c >= tb.base[s + 1]) ++s;
+        const int p = (int)c - tb.base[s], ks = tb.k[s];
+        if (p >= min(tb.count[s][q], ks)) return false;          // behind the count: never read
+        slot = s; w = p;
+        sc = tb.score[s][q * ks + p];
+        vid = (int)(tb.video[s][q * ks + p] + tb.offset[s]);     // the key's field: global ids lie in [0, 2^31)
+        return true;
+    }
+    __device__ __forceinline__ void emit(int s, long long p, long long* ov, long long* oi, float* os) const
+    {
+        const long long c = q * tb.k[s] + p;
+        *ov = tb.video[s][c] + tb.offset[s];
+        oi[0] = tb.idx[s][2 * c]; oi[1] = tb.idx[s][2 * c + 1];
+        *os = tb.score[s][c];
+    }
+};
+
+__global__ __launch_bounds__(CT)
+void search_merge_kernel(const RankedTables tb, int K, long long* __restrict__ out_video, long long* __restrict__ out_idx,
+                         float* __restrict__ out_score, int* __restrict__ out_count)
+{
+    const RankedLists src{tb, (long long)blockIdx.x};
+    topk_rounds(src, tb.base[tb.S], K, out_video, out_idx, out_score, out_count);
 }
 
 }  // namespace
@@ -158,6 +227,38 @@ extern "C" int smin_corpus_topk(void* stream, const float* pair_score, const int
     // (whether a query has pairs is known on the device only: with a NULL pair list the kernel reads none of the four and every query comes out empty)
     hipLaunchKernelGGL(corpus_topk_kernel, dim3(Q), dim3(CT), 0, (hipStream_t)stream, pair_score, (const long long*)pair_idx, pair_count, pair_video,
                        pair_ptr, k_video, K, (long long*)out_video, (long long*)out_idx, out_score, out_count);
+    SMIN_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int smin_search_merge(void* stream, int S, const int64_t* const* video, const int64_t* const* idx, const float* const* score,
+                                 const int32_t* const* count, const int32_t* k_list, const int64_t* video_offset, int Q, int K,
+                                 int64_t* out_video, int64_t* out_idx, float* out_score, int32_t* out_count)
+{
+    SMIN_REQUIRE(S >= 1 && S <= MERGE_MAX_S && K >= 1 && K <= CORPUS_MAX_K && Q >= 0);
+    RankedTables tb{};
+    tb.S = S;
+    if (k_list) {
+        for (int s = 0; s < S; ++s) {
+            SMIN_REQUIRE(k_list[s] >= 1 && k_list[s] <= CORPUS_MAX_K);
+            tb.k[s] = k_list[s];
+            tb.base[s + 1] = tb.base[s] + k_list[s];
+        }
+    }
+    if (Q == 0) return 0;
+    SMIN_REQUIRE(video != nullptr && idx != nullptr && score != nullptr && count != nullptr && k_list != nullptr && video_offset != nullptr);
+    SMIN_REQUIRE(out_video != nullptr && out_idx != nullptr && out_score != nullptr && out_count != nullptr);
+    for (int s = 0; s < S; ++s) {
+        SMIN_REQUIRE(video[s] != nullptr && idx[s] != nullptr && score[s] != nullptr && count[s] != nullptr);
+        SMIN_REQUIRE(video_offset[s] >= 0 && video_offset[s] <= 0x7fffffffll);
+        const void* in[4] = {video[s], idx[s], score[s], count[s]};
+        for (const void* p : in)                                 // the rounds read the lists while thread 0 writes the result
+            SMIN_REQUIRE(p != (const void*)out_video && p != (const void*)out_idx && p != (const void*)out_score && p != (const void*)out_count);
+        tb.video[s] = (const long long*)video[s]; tb.idx[s] = (const long long*)idx[s]; tb.score[s] = score[s]; tb.count[s] = count[s];
+        tb.offset[s] = video_offset[s];
+    }
+    hipLaunchKernelGGL(search_merge_kernel, dim3(Q), dim3(CT), 0, (hipStream_t)stream, tb, K, (long long*)out_video, (long long*)out_idx, out_score,
+                       out_count);
     SMIN_LAUNCH_CHECK();
     return 0;
 }

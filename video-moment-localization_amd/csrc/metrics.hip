@@ -159,6 +159,48 @@ void span_hits_kernel(const float* __restrict__ span, const int* __restrict__ co
     }
 }
 
+// ---- corpus metric (smin_corpus_meter_update, include/smin_hip.h): VCMR R@n, IoU=m, VR R@n and the top-1 IoU of SMIN.search-style
+// ranked lists over a corpus against one ground-truth (video, span) per query.  The per-query stage of span_hits_kernel with the
+// entry's video in the test: an entry of another video has IoU 0.
+__global__ __launch_bounds__(64)
+void corpus_hits_kernel(const long long* __restrict__ video, const float* __restrict__ span, const int* __restrict__ count,
+                        const long long* __restrict__ gt_video, const float* __restrict__ gt, int Q, int k, SpanRule pr,
+                        float* __restrict__ hits /* [Q][nn * nm + nn] */, float* __restrict__ top1 /* [Q] */)
+{
+    __shared__ float col[64][64];                                // col[r][lane]: the lane's IoU of entry r
+    const int t = threadIdx.x, b = blockIdx.x * 64 + t;
+    if (b >= Q) return;                                          // no barrier below: a lane reads its own column only
+    const float gs = gt[2 * (size_t)b], ge = gt[2 * (size_t)b + 1];
+    const long long gv = gt_video[b];
+    const long long* vb = video + (size_t)b * k;
+    const int cnt = min(max(count[b], 0), k);
+    int first = -1;                                              // the first entry of the ground-truth video
+    for (int r = 0; r < cnt; ++r) {
+        const size_t o = (size_t)b * k + r;
+        const bool same = vb[r] == gv;
+        col[r][t] = same ? span_iou(span[2 * o], span[2 * o + 1], gs, ge) : 0.f;
+        if (same && first < 0) first = r;
+    }
+    top1[b] = cnt > 0 ? col[0][t] : 0.f;
+    const int npairs = pr.nn * pr.nm + pr.nn;
+    float* hb = hits + (size_t)b * npairs;
+    for (int a = 0; a < pr.nn; ++a) {
+        const int e = min(pr.n[a], cnt);
+        for (int c = 0; c < pr.nm; ++c) {
+            bool hit = false;
+            for (int r = 0; r < e; ++r) hit = hit || col[r][t] > pr.m[c];
+            hb[a * pr.nm + c] = hit ? 1.f : 0.f;
+        }
+    }
+    int distinct = 0;                                            // distinct videos ranked ahead of the ground-truth video
+    for (int r = 0; r < first; ++r) {
+        bool seen = false;
+        for (int u = 0; u < r; ++u) seen = seen || vb[u] == vb[r];
+        distinct += seen ? 0 : 1;
+    }
+    for (int a = 0; a < pr.nn; ++a) hb[pr.nn * pr.nm + a] = (first >= 0 && distinct < pr.n[a]) ? 1.f : 0.f;
+}
+
 static size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 // rule 0 is the reference's metric as this file computes it: n = {1, 5}, m = {0.1, 0.3, 0.5, 0.7}, topk(5) over all L*L cells
@@ -251,6 +293,36 @@ extern "C" int smin_span_meter_update(void* stream, const float* span, const int
     hipLaunchKernelGGL(span_hits_kernel, dim3(cdiv(B, 64)), dim3(64), 0, st, span, count, gt, B, k, pr, hits, top1);
     SMIN_LAUNCH_CHECK();
     hipLaunchKernelGGL(meter_close_kernel, dim3(1), dim3(64), 0, st, hits, top1, B, nn * nm, (const float*)nullptr, acc);
+    SMIN_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" size_t smin_corpus_meter_ws_bytes(int Q, int nn, int nm)
+{
+    if (Q < 1 || nn < 1 || nn > 64 || nm < 1 || nm > 16) return 0;
+    return align256((size_t)Q * (nn * nm + nn) * sizeof(float)) + align256((size_t)Q * sizeof(float));
+}
+
+extern "C" int smin_corpus_meter_update(void* stream, const int64_t* video, const float* span, const int32_t* count, const int64_t* gt_video,
+                                        const float* gt, int Q, int k, const int* n_list, int nn, const float* m_list, int nm, double* acc,
+                                        void* ws, size_t ws_bytes)
+{
+    hipStream_t st = (hipStream_t)stream;
+    SMIN_REQUIRE(Q >= 0 && k >= 1 && k <= 64 && nn >= 1 && nn <= 64 && nm >= 1 && nm <= 16 && n_list != nullptr && m_list != nullptr);
+    SpanRule pr{};
+    pr.nn = nn; pr.nm = nm;
+    for (int a = 0; a < nn; ++a) { SMIN_REQUIRE(n_list[a] >= 1 && n_list[a] <= k); pr.n[a] = n_list[a]; }
+    for (int c = 0; c < nm; ++c) pr.m[c] = m_list[c];
+    if (Q == 0) return 0;
+    SMIN_REQUIRE(video != nullptr && span != nullptr && count != nullptr && gt_video != nullptr && gt != nullptr && acc != nullptr && ws != nullptr);
+    SMIN_REQUIRE(ws_bytes >= smin_corpus_meter_ws_bytes(Q, nn, nm));
+    const int npairs = nn * nm + nn;
+    float* hits = (float*)ws;
+    float* top1 = (float*)((char*)ws + align256((size_t)Q * npairs * sizeof(float)));
+    hipLaunchKernelGGL(corpus_hits_kernel, dim3(cdiv(Q, 64)), dim3(64), 0, st, (const long long*)video, span, count, (const long long*)gt_video, gt, Q, k,
+                       pr, hits, top1);
+    SMIN_LAUNCH_CHECK();
+    hipLaunchKernelGGL(meter_close_kernel, dim3(1), dim3(64), 0, st, hits, top1, Q, npairs, (const float*)nullptr, acc);
     SMIN_LAUNCH_CHECK();
     return 0;
 }

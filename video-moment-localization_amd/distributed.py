@@ -136,6 +136,40 @@ def exchange_row_grad(table, group=None, average=True, merge=None):
     table.row_grad = (merge or merge_row_grads)(lists, scale=1.0 / world if average else None)
 
 
+def gather_search(result, num_videos, group=None, k=None, merge=None):
+    """One global ranked list on every rank out of each rank's ``SMIN.search`` over its own shard of the videos (the same queries on
+    every rank): the ranks gather ``video``, ``idx``, ``score`` and ``count`` -- Q * k_s * 4 + Q words a rank -- and
+    their ``num_videos``, and each merges the lists in rank order with ``video_offset`` the exclusive prefix sum of ``num_videos``, so
+    rank r's video v becomes global video ``sum(num_videos[:r]) + v``.  ``k``: entries per query of the merged list (default: the
+    lists' own).  ``merge`` defaults to ``moments.merge_search`` (HIP); ``moments.merge_search_torch`` is the restatement for CPU
+    groups.  More than 16 ranks are folded in groups of 16, which gives the same list.  Every rank returns the same dict, bit for bit
+    (``video``, ``idx``, ``score``, ``count``; times follow from ``moments.search_times`` and the global durations).
+    Without an initialised process group, or at world size 1, the rank's own list is merged alone.  Ranks whose lists differ in Q or
+    in entries per query, or that pass different ``k``, raise ValueError on every rank (one small gather read on the host)."""
+    from .moments import fold_search, merge_search
+    merge = merge or merge_search
+    video = result["video"]
+    Q, ks = video.shape
+    k = ks if k is None else int(k)
+    if not dist.is_initialized() or dist.get_world_size(group) == 1:
+        return merge([result], [0], k=k)
+    world, dev = dist.get_world_size(group), video.device
+    mine = torch.tensor([Q, ks, k, int(num_videos)], dtype=torch.int64, device=dev)
+    dims = torch.empty((world, 4), dtype=torch.int64, device=dev)
+    dist.all_gather([dims[r] for r in range(world)], mine, group=group)
+    dims = dims.tolist()
+    if any(d[:3] != dims[0][:3] for d in dims) or min(d[3] for d in dims) < 0:
+        raise ValueError(f"gather_search: every rank's list must have the same queries, entries per query and k, and num_videos >= 0; got "
+                         f"(Q, k_list, k, num_videos) = {dims}")
+    bufs = {"video": torch.empty((world, Q, ks), dtype=torch.int64, device=dev), "idx": torch.empty((world, Q, ks, 2), dtype=torch.int64, device=dev),
+            "score": torch.empty((world, Q, ks), dtype=torch.float32, device=dev), "count": torch.empty((world, Q), dtype=torch.int32, device=dev)}
+    for key, buf in bufs.items():
+        dist.all_gather([buf[r] for r in range(world)], result[key].detach().to(buf.dtype).contiguous(), group=group)
+    lists = [{key: buf[r] for key, buf in bufs.items()} for r in range(world)]
+    offsets = [sum(d[3] for d in dims[:r]) for r in range(world)]
+    return fold_search(lists, offsets, k, merge)
+
+
 def describe():
     """(backend, world size) of the default process group as the collective library reports them -- what a benchmark
     line may claim about its gradient exchange."""

@@ -17,13 +17,20 @@ to it -- reproduces ``EpochMeter.state`` bit for bit.
 against ground-truth spans instead (include/smin_hip.h, smin_span_meter_update): slot 0, the top-1 IoU sum and the hit slots, with the
 meter's own n / m; the rule (``nms_thresh``) plays no part, and a meter may mix both kinds of update.
 
+``CorpusMeter`` / ``CorpusMeterTorch`` keep the numbers of corpus search the same way (include/smin_hip.h,
+smin_corpus_meter_update): ``update(result, gt_video, gt)`` takes a ranked list over a corpus (``SMIN.search`` /
+``merge_search`` output) and one ground-truth moment of one ground-truth video per query.  State: ``4 + len(n) * len(m) + len(n)``
+values -- ``[0]`` queries, ``[1]`` / ``[2]`` unused, ``[3]`` the top-1 IoU sum (an entry of another video has IoU 0),
+``[4 + a * len(m) + c]`` VCMR hits (the moment of the right video among the top n[a] with IoU > m[c]), ``[4 + len(n) * len(m) + a]`` VR
+hits (the right video among the first n[a] distinct videos of the list).
+
 All updates of one meter must be issued on one stream (the accumulator is ordered by the stream alone, no atomics)."""
 import ctypes
 
 import torch
 
 from ._host import byte_mask
-from .moments import MAX_K, _check, _mul32, _nm_check, _span_check, _span_meter_call, _sqrt32
+from .moments import MAX_K, _check, _mul32, _nm_check, _span_check, _span_meter_call, _sqrt32, _valid_slots, span_ious_torch
 
 _REF_N, _REF_M = (1, 5), (0.1, 0.3, 0.5, 0.7)
 
@@ -215,4 +222,102 @@ class EpochMeterTorch(_Meter):
         if B:
             for q, v in enumerate(_span_hits_torch(ious, count, self._n, self._m).tolist()):
                 delta[4 + q] = float(v)
+        self.state += torch.tensor(delta, dtype=torch.float64).to(self.state.device)
+
+
+class _CorpusMeter(_Meter):
+    def __init__(self, n=_REF_N, m=_REF_M, device=None):
+        self.n, self.m = tuple(n), tuple(m)
+        self._n, self._m = _nm_check(self.n, self.m)                         # ValueError: more than 64 n / 16 m, or an n outside 1..64
+        self.keys = [f"R@{n_}, IoU={m_}" for n_ in self.n for m_ in self.m] + [f"VR@{n_}" for n_ in self.n]
+        self.device = torch.device(self._default_device() if device is None else device)
+        self.state = torch.zeros(4 + len(self.keys), dtype=torch.float64, device=self.device)
+
+    def _lists(self, result, gt_video, gt):
+        """The checked update: ``video (Q, k)`` int64, ``span (Q, k, 2)`` fp32 -- ``result["times"]`` when present, else the clip edges
+        ``(i, j + 1)`` of ``result["idx"]`` --, ``count (Q,)``, ``gt_video (Q,)`` int64 and ``gt (Q, 2)`` fp32."""
+        video, count = result["video"], result["count"]
+        if video.dim() != 2:
+            raise ValueError(f"{type(self).__name__}.update: result['video'] must be (Q, k), got {tuple(video.shape)}")
+        Q, k = video.shape
+        if not 1 <= k <= MAX_K or k < max(self._n):
+            raise ValueError(f"{type(self).__name__}.update: the meter's R@{max(self._n)} needs lists of {max(self._n)}..{MAX_K} entries "
+                             f"per query (result has k = {k})")
+        if "times" in result:
+            span = result["times"].detach().float()
+        else:
+            span = result["idx"].to(torch.float32)                            # a copy: idx is int64
+            span[..., 1] += 1.0
+        if tuple(span.shape) != (Q, k, 2) or tuple(count.shape) != (Q,) or tuple(gt_video.shape) != (Q,) or tuple(gt.shape) != (Q, 2):
+            raise ValueError(f"{type(self).__name__}.update: times / idx must be (Q, k, 2) = {(Q, k, 2)}, count and gt_video (Q,) and gt "
+                             f"(Q, 2); got {tuple(span.shape)}, {tuple(count.shape)}, {tuple(gt_video.shape)}, {tuple(gt.shape)}")
+        return video.to(torch.int64), span, count.to(torch.int32), gt_video.to(torch.int64), gt.detach().float(), Q, k
+
+
+class CorpusMeter(_CorpusMeter):
+    """``CorpusMeter(n=(1, 5), m=(0.1, 0.3, 0.5, 0.7), device=...)``: VCMR R@n, IoU=m, VR R@n and the mean top-1 IoU of corpus search,
+    in fp64 on the device (module docstring).  ``update(result, gt_video, gt)`` enqueues two kernels on the current stream and returns
+    nothing: ``result`` is ``SMIN.search`` / ``merge_search`` output with at least max(n) entries per query, ``gt_video (Q,)`` the
+    ground-truth video in ``result["video"]``'s numbering, ``gt (Q, 2)`` the ground-truth moment in the unit of ``result["times"]``
+    (seconds) or, without times, in clip edges ``(i, j + 1)``.  HIP tensors only.  ``result()`` reads (keys ``"R@n, IoU=m"``, ``"VR@n"``,
+    ``"mIoU"``, ``"num_samples"``), ``reset()`` zeroes, ``state`` is the fp64 device tensor."""
+
+    @staticmethod
+    def _default_device():
+        return "cuda"
+
+    def update(self, result, gt_video, gt):
+        from ._lib import SminHipError, call, load, ptr, stream
+        video, span, count, gt_video, gt, Q, k = self._lists(result, gt_video, gt)
+        for t in (video, span, count, gt_video, gt):
+            if not t.is_cuda:
+                raise SminHipError("CorpusMeter.update runs on a HIP device only (got a CPU tensor); there is no CPU fallback -- the plain-torch "
+                                   "restatement is available under the explicit name CorpusMeterTorch")
+        if video.device != self.state.device:
+            raise ValueError(f"CorpusMeter on {self.state.device} got tensors on {video.device}")
+        if Q == 0:
+            return
+        args = [t.contiguous() for t in (video, span, count, gt_video, gt)]
+        nn, nm = len(self._n), len(self._m)
+        nl, ml = (ctypes.c_int * nn)(*self._n), (ctypes.c_float * nm)(*self._m)
+        with torch.cuda.device(video.device):
+            nbytes = load().smin_corpus_meter_ws_bytes(Q, nn, nm)
+            if nbytes == 0:
+                raise SminHipError(f"smin_corpus_meter_ws_bytes rejected Q={Q}, nn={nn}, nm={nm}")
+            ws = torch.empty((nbytes,), dtype=torch.uint8, device=video.device)
+            call("smin_corpus_meter_update", stream(), *[ptr(a) for a in args], Q, k, ctypes.cast(nl, ctypes.c_void_p), nn,
+                 ctypes.cast(ml, ctypes.c_void_p), nm, ptr(self.state), ptr(ws), nbytes)
+
+
+class CorpusMeterTorch(_CorpusMeter):
+    """``CorpusMeter`` as plain torch ops and Python float64 sums on any device: reads the host on every update."""
+
+    @staticmethod
+    def _default_device():
+        return "cpu"
+
+    def update(self, result, gt_video, gt):
+        video, span, count, gt_video, gt, Q, k = self._lists(result, gt_video, gt)
+        delta = [0.0] * self.state.numel()
+        delta[0] = float(Q)
+        if Q:
+            valid = _valid_slots(count, k)
+            same = (video == gt_video.unsqueeze(1)) & valid
+            iou = span_ious_torch(span, count, gt)                            # fp32, each operation rounded once; 0 behind the counts
+            iou = torch.where(same, iou, torch.zeros_like(iou))
+            s = 0.0
+            for v in iou[:, 0].tolist():                                      # float64 sum over the queries in order
+                s += v
+            delta[3] = s
+            thr = torch.tensor(self._m, dtype=torch.float32, device=iou.device)
+            hits = [((iou[:, :n_] > thr[c]) & valid[:, :n_]).any(dim=1).sum() for n_ in self._n for c in range(len(self._m))]
+            # VR: the distinct videos ranked ahead of the first entry of the ground-truth video
+            rank = torch.arange(k, device=video.device)
+            first = torch.where(same, rank.unsqueeze(0), torch.full_like(video, k)).min(dim=1).values
+            earlier = (video.unsqueeze(2) == video.unsqueeze(1)) & (rank.unsqueeze(0) < rank.unsqueeze(1)).unsqueeze(0)     # [q, r, u]: u < r, same video
+            fresh = ~earlier.any(dim=2)
+            distinct = (fresh & (rank.unsqueeze(0) < first.unsqueeze(1))).sum(dim=1)
+            hits += [((first < k) & (distinct < n_)).sum() for n_ in self._n]
+            for q, v in enumerate(torch.stack(hits).tolist()):
+                delta[4 + q] = float(v)                                       # sums of 0 / 1 flags: exact in any order
         self.state += torch.tensor(delta, dtype=torch.float64).to(self.state.device)

@@ -467,3 +467,128 @@ def corpus_topk_torch(pair_score, pair_idx, pair_count, pair_video, pair_ptr, k=
             out_score[q, :n] = score.reshape(-1)[flat]
         count[q] = n
     return {"video": video, "idx": idx, "score": out_score, "count": count}
+
+
+def search_times(video, idx, duration, L):
+    """``times (Q, k, 2)`` of a ranked corpus list: top_moments' formula on each moment's own video, ``(i * duration[video] / L,
+    (j + 1) * duration[video] / L)`` in fp32, NaN for empty slots.  ``duration``: the (V,) seconds of the videos ``video`` indexes.
+    Formed without a constant from the host: the call reads and writes no host memory."""
+    Q, k = video.shape
+    d = duration.to(device=video.device, dtype=torch.float32)[video.clamp_min(0)].reshape(Q, k, 1)
+    edge = idx.to(torch.float32)
+    edge[..., 1] += 1.0
+    t = edge * d / L
+    return torch.where(idx >= 0, t, torch.full_like(t, float("nan")))
+
+
+# ---------------------------------------------------------------- merge of ranked lists of disjoint video shards (INTEGRATION.md 3n)
+MAX_LISTS = 16
+
+
+def _merge_search_check(what, results, video_offset, k, duration, L):
+    results = list(results)
+    S = len(results)
+    if not 1 <= S <= MAX_LISTS:
+        raise ValueError(f"{what}: takes 1..{MAX_LISTS} ranked lists at a time (got {S}); fold longer sequences")
+    if not (isinstance(k, int) and 1 <= k <= MAX_K):
+        raise ValueError(f"{what} needs an integer 1 <= k <= {MAX_K} (got {k!r})")
+    Q = results[0]["video"].shape[0] if results[0]["video"].dim() == 2 else -1
+    for s, r in enumerate(results):
+        v = r["video"]
+        if v.dim() != 2 or v.shape[0] != Q:
+            raise ValueError(f"{what}: every list's video must be (Q, k_s) with one Q = {Q} (list {s}: {tuple(v.shape)})")
+        ks = v.shape[1]
+        if not 1 <= ks <= MAX_K:
+            raise ValueError(f"{what}: a list holds 1..{MAX_K} slots per query (list {s}: k = {ks})")
+        if tuple(r["idx"].shape) != (Q, ks, 2) or tuple(r["score"].shape) != (Q, ks) or tuple(r["count"].shape) != (Q,):
+            raise ValueError(f"{what}: list {s} must hold idx (Q, k_s, 2) = {(Q, ks, 2)}, score (Q, k_s) and count (Q,); got "
+                             f"{tuple(r['idx'].shape)}, {tuple(r['score'].shape)}, {tuple(r['count'].shape)}")
+        if r["video"].device != results[0]["video"].device:
+            raise ValueError(f"{what}: the lists must be on one device")
+    off = [0] * S if video_offset is None else [int(x) for x in video_offset]
+    if len(off) != S or min(off) < 0 or max(off) >= 2 ** 31:
+        raise ValueError(f"{what}: video_offset must hold one offset in [0, 2**31) per list (got {off})")
+    if duration is not None and L is None:
+        raise ValueError(f"{what}: times need L, the number of clips per video, beside duration")
+    return results, off, Q
+
+
+def merge_search(results, video_offset=None, k=5, duration=None, L=None):
+    """One ranked list per query out of 1..16 ``SMIN.search``-style lists, each over its own shard of the videos (include/smin_hip.h,
+    smin_search_merge): one launch, one workgroup per query picks k times the best remaining candidate of all lists.
+
+    ``results``: dicts with ``video (Q, k_s)`` int64, ``idx (Q, k_s, 2)`` int64, ``score (Q, k_s)`` and ``count (Q,)`` on one HIP device
+    with one Q; ``video_offset``: host ints, list s's first global video (default all 0).  Order: higher score first (-0 counts as
+    +0), ties -> lower global video, then lower list, then lower position.  Each list is assumed ordered as ``search`` orders it; then
+    the merge of the lists of disjoint shards in ascending offset is, bit for bit, the list ``search`` / ``corpus_topk`` give on the
+    whole corpus at equal pair scores, all at once or folded (``merge_search([carry, next], [0, seen])``).  No host synchronisation.
+
+    Returns ``search``'s dict with global ids in ``video``; with ``duration`` (the global (V,) seconds) and ``L`` also ``times``."""
+    results, off, Q = _merge_search_check("merge_search", results, video_offset, k, duration, L)
+    for r in results:
+        for key in ("video", "idx", "score", "count"):
+            _require_hip(r[key], "merge_search")
+    dev, S = results[0]["video"].device, len(results)
+    cols = [[r["video"].to(torch.int64).contiguous() for r in results], [r["idx"].to(torch.int64).contiguous() for r in results],
+            [r["score"].detach().float().contiguous() for r in results], [r["count"].to(torch.int32).contiguous() for r in results]]
+    tables = [(ctypes.c_void_p * S)(*[t.data_ptr() for t in col]) for col in cols]
+    k_list = (ctypes.c_int32 * S)(*[t.shape[1] for t in cols[0]])
+    offsets = (ctypes.c_int64 * S)(*off)
+    video = torch.empty((Q, k), dtype=torch.int64, device=dev)
+    idx = torch.empty((Q, k, 2), dtype=torch.int64, device=dev)
+    score = torch.empty((Q, k), dtype=torch.float32, device=dev)
+    count = torch.empty((Q,), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        call("smin_search_merge", stream(), S, *[ctypes.cast(t, ctypes.c_void_p) for t in tables], ctypes.cast(k_list, ctypes.c_void_p),
+             ctypes.cast(offsets, ctypes.c_void_p), Q, k, ptr(video), ptr(idx), ptr(score), ptr(count))
+    out = {"video": video, "idx": idx, "score": score, "count": count}
+    if duration is not None:
+        out["times"] = search_times(video, idx, duration, L)
+    return out
+
+
+def merge_search_torch(results, video_offset=None, k=5, duration=None, L=None):
+    """``merge_search`` as plain torch + Python on any device (same result, bit for bit): each query's candidates sorted by
+    (score, global video, list, position)."""
+    results, off, Q = _merge_search_check("merge_search_torch", results, video_offset, k, duration, L)
+    dev = results[0]["video"].device
+    per = []
+    for r in results:
+        score = r["score"].detach().float()
+        sc = torch.where(score == 0, torch.zeros_like(score), score)                             # -0 -> +0
+        u = sc.contiguous().view(torch.int32).to(torch.int64) & 0xFFFFFFFF
+        o = torch.where(u >= 0x80000000, u ^ 0xFFFFFFFF, u | 0x80000000).clamp_min(1).tolist()  # the order word of top_moments_torch
+        ks = score.shape[1]
+        per.append((o, r["video"].to(torch.int64).tolist(), r["count"].to(torch.int64).clamp(0, ks).tolist()))
+    base = [0]
+    for r in results:
+        base.append(base[-1] + r["score"].shape[1])
+    all_video = torch.cat([r["video"].to(torch.int64) + off[s] for s, r in enumerate(results)], dim=1)       # (Q, sum k_s), list after list
+    all_idx = torch.cat([r["idx"].to(torch.int64) for r in results], dim=1)
+    all_score = torch.cat([r["score"].detach().float() for r in results], dim=1)
+    video = torch.full((Q, k), -1, dtype=torch.int64, device=dev)
+    idx = torch.full((Q, k, 2), -1, dtype=torch.int64, device=dev)
+    out_score = torch.zeros((Q, k), dtype=torch.float32, device=dev)
+    count = torch.zeros((Q,), dtype=torch.int32, device=dev)
+    for q in range(Q):
+        cand = [(-o[q][p], vid[q][p] + off[s], s, p) for s, (o, vid, cnt) in enumerate(per) for p in range(cnt[q])]
+        cand.sort()
+        n = min(len(cand), k)
+        if n:
+            flat = torch.tensor([base[s] + p for _, _, s, p in cand[:n]], dtype=torch.int64, device=dev)
+            video[q, :n], idx[q, :n], out_score[q, :n] = all_video[q, flat], all_idx[q, flat], all_score[q, flat]
+        count[q] = n
+    out = {"video": video, "idx": idx, "score": out_score, "count": count}
+    if duration is not None:
+        out["times"] = search_times(video, idx, duration, L)
+    return out
+
+
+def fold_search(lists, offsets, k, merge):
+    """``merge`` (merge_search or merge_search_torch) over any number of lists in ascending offset: the first 16 at once, then the carry
+    -- which holds global ids already, so its offset is 0 -- with the next 15, and so on; the same list as one merge of all
+    (INTEGRATION.md 3n)."""
+    carry = merge(lists[:MAX_LISTS], offsets[:MAX_LISTS], k=k)
+    for r0 in range(MAX_LISTS, len(lists), MAX_LISTS - 1):
+        carry = merge([carry] + list(lists[r0:r0 + MAX_LISTS - 1]), [0] + list(offsets[r0:r0 + MAX_LISTS - 1]), k=k)
+    return carry

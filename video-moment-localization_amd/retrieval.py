@@ -9,7 +9,7 @@ from . import _lib
 from ._host import _AttnMaps, byte_mask, host_array, known_cells, query_mask_rows, require_hip_tensors, require_ints
 from .feeder import build_masks_hip, cell_count
 from .functional import attn_maps_gather
-from .moments import MAX_K, _top_moments_into, corpus_topk, corpus_topk_torch, merge_window_moments, top_moments
+from .moments import MAX_K, _top_moments_into, corpus_topk, corpus_topk_torch, merge_window_moments, search_times, top_moments
 from .sampling import MAX_ROWS, MODES, sample_windows, window_plan
 
 
@@ -277,14 +277,7 @@ class _Retrieval:
     @staticmethod
     def _search_result(r, duration, L):
         if duration is not None:
-            # moments._times' formula on each moment's own video: (i * duration / L, (j + 1) * duration / L) in fp32, NaN for empty slots
-            # (formed without a constant from the host: the call reads and writes no host memory)
-            Q, k = r["video"].shape
-            d = duration.to(device=r["video"].device, dtype=torch.float32)[r["video"].clamp_min(0)].reshape(Q, k, 1)
-            edge = r["idx"].to(torch.float32)
-            edge[..., 1] += 1.0
-            t = edge * d / L
-            r["times"] = torch.where(r["idx"] >= 0, t, torch.full_like(t, float("nan")))
+            r["times"] = search_times(r["video"], r["idx"], duration, L)          # moments._times' formula on each moment's own video
         return r
 
     def search(self, videos, queries, pairs=None, k=5, k_video=None, nms_thresh=0.5, duration=None, max_batch=64):

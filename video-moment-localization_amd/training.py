@@ -292,3 +292,71 @@ def test_model_windows(model, groups, meter=None, *, window=None, stride=None, k
 
 
 test_model_windows.__test__ = False
+
+
+def search_shards(model, video_shards, queries, *, k=25, k_video=5, nms_thresh=0.5, max_batch=64):
+    """``model.search`` over a corpus that comes in shards: ``queries`` is a QueryBank (``model.encode_queries``), ``video_shards`` an
+    iterable of dicts with ``encode_videos``' four arguments and a host ``duration (V_s,)``.  Per shard: ``encode_videos``, ``search``
+    at (k, k_video), then ``carry = merge_search([carry, r], [0, videos seen], k=k)`` -- at equal pair scores the list ``search`` gives
+    on one bank of all the videos.  One shard's bank is alive at a time.  Returns ``(carry, duration)``: the
+    ranked list with global video ids in shard order, and the shards' durations concatenated as a host float64 array.  Host reads:
+    ``encode_videos``' own count read per shard."""
+    import numpy as np
+    from .moments import merge_search
+    carry, seen, durations = None, 0, []
+    for shard in video_shards:
+        bank = model.encode_videos(shard["video_features"], shard["video_mask"], shard["length_mask"], shard["moment_mask"])
+        d = host_array(shard["duration"], np.float64)
+        if d.shape[0] != len(bank):
+            raise ValueError(f"search_shards: duration must cover the shard's {len(bank)} videos (got {d.shape[0]})")
+        r = model.search(bank, queries, k=k, k_video=k_video, nms_thresh=nms_thresh, max_batch=max_batch)
+        carry = r if carry is None else merge_search([carry, r], [0, seen], k=k)
+        seen += len(bank)
+        durations.append(d)
+    if carry is None:
+        raise ValueError("search_shards: at least one shard of videos")
+    return carry, np.concatenate(durations)
+
+
+def test_model_corpus(model, video_shards, queries, gt_video, gt_times, meter=None, *, k=25, k_video=5, nms_thresh=0.5, max_batch=64):
+    """The test loop of corpus search: VCMR R@n, IoU=m, VR R@n and mIoU of ``model.search`` over a corpus in shards, with no host
+    read beside ``encode_videos``' own and the meter's one at the end.  ``video_shards``: an iterable of dicts with
+    ``encode_videos``' four arguments and a host ``duration (V_s,)`` in seconds; ``queries``: a dict with ``query_features`` and
+    ``query_mask``, encoded once; ``gt_video (Q,)``: each query's video as a global index in shard order, ``gt_times (Q, 2)`` its
+    moment in seconds, both host values.  The shards are searched and folded by ``search_shards``; the merged list gets ``times``
+    from the concatenated durations, which travel with ``gt_video`` and ``gt_times`` in one pinned asynchronous copy; one
+    ``meter.update`` (meter.CorpusMeter; a default one is made if none is given) and the one ``meter.result()``, which is returned.
+    The meter is not reset here.
+
+    VR@n is exact when ``k >= max(n) * k_video`` -- the first n distinct videos of a list occupy at most that many entries --;
+    anything less, like ``k < max(n)``, raises ValueError before any retrieval runs."""
+    import numpy as np
+    from .moments import search_times
+    n_max = 5 if meter is None else max(meter.n)
+    if k < n_max or k < n_max * k_video:
+        raise ValueError(f"test_model_corpus: k = {k} entries per query cannot give an exact R@{n_max} / VR@{n_max} at k_video = {k_video}: "
+                         f"needs k >= max(n) * k_video = {n_max * k_video}")
+    gv, gt = host_array(gt_video), host_array(gt_times, np.float64, (-1, 2))
+    Q = queries["query_features"].shape[0]
+    if gv.shape[0] != Q or gt.shape[0] != Q:
+        raise ValueError(f"test_model_corpus: gt_video (Q,) and gt_times (Q, 2) must cover the Q = {Q} queries (got {gv.shape}, {gt.shape})")
+    model.eval()
+    bank = model.encode_queries(queries["query_features"], queries["query_mask"])
+    dev = queries["query_features"].device
+    if meter is None:
+        from .meter import CorpusMeter
+        meter = CorpusMeter(device=dev)
+    carry, duration = search_shards(model, video_shards, bank, k=k, k_video=k_video, nms_thresh=nms_thresh, max_batch=max_batch)
+    if Q and (gv.min() < 0 or gv.max() >= duration.shape[0]):
+        raise ValueError(f"test_model_corpus: gt_video must lie in [0, {duration.shape[0]}), the videos of the shards")
+    # gt_video (int64, first: 8-byte aligned), then the durations and gt_times (fp32), as bytes of one pinned buffer: one asynchronous copy
+    V_all = duration.shape[0]
+    host = np.concatenate([gv.astype(np.int64).view(np.uint8), np.concatenate([duration, gt.reshape(-1)]).astype(np.float32).view(np.uint8)])
+    buf = torch.from_numpy(host).pin_memory().to(dev, non_blocking=True)
+    gv_d, f32 = buf[:8 * Q].view(torch.int64), buf[8 * Q:].view(torch.float32)
+    carry["times"] = search_times(carry["video"], carry["idx"], f32[:V_all], model.L)
+    meter.update(carry, gv_d, f32[V_all:].reshape(Q, 2))
+    return meter.result()
+
+
+test_model_corpus.__test__ = False
