@@ -52,7 +52,8 @@ extern "C" {
  * over banks of encoded videos and queries -- smin_pair_assemble (the backbone's outputs of indexed pairs) and smin_corpus_topk (one
  * ranked list per query across videos); evaluation of corpus search -- smin_search_merge (ranked lists of disjoint video shards into
  * one list per query) and smin_corpus_meter_update with smin_corpus_meter_ws_bytes (VCMR and VR recall into the epoch meter's kind of
- * accumulator) */
+ * accumulator); training through shared banks -- smin_pair_assemble_bwd and smin_pair_assemble_bwd_workspace_bytes (the adjoint of
+ * smin_pair_assemble: the pairs' gradients summed onto their videos and queries in a fixed order) */
 #define SMIN_HIP_ABI_VERSION 2
 
 int smin_abi_version(void);
@@ -699,8 +700,9 @@ int smin_row_lists_merge(void* stream, const int32_t* const* ids, const float* c
                          int R, int V, int E, const double* scale, int32_t* out_ids, float* out_rows, int32_t* out_count,
                          double* out_sqnorm, void* ws, size_t ws_bytes);
 
-/* ---- corpus search (csrc/corpus.hip): Q queries against a bank of V videos, each encoded once.  Scoring only:
- * neither entry has a backward.
+/* ---- corpus search (csrc/corpus.hip): Q queries against a bank of V videos, each encoded once.
+ * smin_pair_assemble has a backward, smin_pair_assemble_bwd below (training through shared banks); the two merges
+ * (smin_corpus_topk, smin_search_merge) only rank and have none.
  *
  * smin_pair_assemble: the backbone's outputs of P (video, query) pairs from the banks, one launch.
  * Inputs.  fv [V][T][D]: the video encoder's projection with position embedding and mask (smin_video_encoder_fwd with fs == NULL);
@@ -716,6 +718,38 @@ int smin_row_lists_merge(void* stream, const int32_t* const* ids, const float* c
  * Rejection.  A nonzero status is returned before the launch for a bad D, a size below 1 or a NULL pointer. */
 int smin_pair_assemble(void* stream, const float* fv, const float* fs_bank, const float* fw_bank, const int32_t* video_index,
                        const int32_t* query_index, int P, int V, int Q, int T, int Nq, int D, float* f, float* fw, float* fs);
+
+/* smin_pair_assemble_bwd: the adjoint of smin_pair_assemble -- the gradients of the P pairs' f, f_w, f_s summed back onto the V videos
+ * and Q queries they were gathered from.  Two launches, no atomics.
+ * Inputs.  df [P][T][D], dfw [P][Nq][D], dfs [P][D]: the gradients of smin_pair_assemble's three outputs; dfw and dfs may each be NULL
+ *   (= zeros, bit for bit).  fv [V][T][D], fs_bank [Q][D]: the forward's operands.  video_index, query_index: [P] int32 on the device,
+ *   the forward's lists.  The same pairs grouped by video and by query, CSR, int32 on the device: v_ptr [V + 1] / v_pairs [P] -- video v
+ *   owns v_pairs[v_ptr[v] .. v_ptr[v + 1]) --, q_ptr [Q + 1] / q_pairs [P]; each segment lists its pairs p in ascending order.  A
+ *   segment names its video, so the kernels read fv[v] for the pairs of segment v and never read video_index (it is part of the
+ *   signature as the list the segments were built from).
+ * Outputs, every element written (nothing needs zeroing first).
+ *   dfv [V][T][D]:       dfv[v][t][:]  = sum_{p in seg_v} df[p][t][:] * fs_bank[qi[p]][:]
+ *   dfw_bank [Q][Nq][D]: dfw_bank[q]   = sum_{p in seg_q} dfw[p]
+ *   dfs_bank [Q][D]:     dfs_bank[q][:] = sum_{p in seg_q} ( dfs[p][:] + sum_t df[p][t][:] * fv[vi[p]][t][:] )
+ *   A video or a query with no pair gets exact zeros.
+ * Order.  fp32; every sum starts at +0 and runs over the segment in list order.  dfv: one fused multiply-add per pair.  dfs_bank: a
+ *   pair's dot over t is formed in chunks of 4 consecutive frames, each a chain of fused multiply-adds in ascending t from +0; chunk
+ *   c belongs to lane c % 8; lane j adds, pair after pair in list order, its chunks in ascending c (lane 0 adds dfs[p] ahead of the
+ *   pair's chunks); the eight lanes are then added in ascending j.  A function of the arguments only.
+ * Traffic.  df is read once, fv once (not once per pair), fs_bank once per pair; the chunk dots pass through ws: P * ceil(T / 4) * D
+ *   floats written and read.  16-byte loads and stores throughout.
+ * Bounds.  Every value read from v_ptr, q_ptr (into [0, P], ascending), v_pairs, q_pairs (into [0, P)) and query_index (into [0, Q)) is
+ *   clamped before it forms an address: malformed lists give unspecified sums, never an access outside the buffers.
+ * Limits.  D >= 4, D % 4 == 0, P, V, Q, T, Nq >= 1, buffers 16-byte aligned; outputs and ws must not overlap the inputs or each other.
+ * Workspace.  ws_bytes >= smin_pair_assemble_bwd_workspace_bytes(P, T, D), exactly P * ceil(T / 4) * D * 4.
+ * Determinism.  The same bits every run; no host read; capturable.
+ * Rejection.  A nonzero status before any launch for a bad D, a size below 1, a NULL pointer other than dfw / dfs, or a workspace that
+ *   is too small; the outputs are then untouched. */
+size_t smin_pair_assemble_bwd_workspace_bytes(int P, int T, int D);
+int smin_pair_assemble_bwd(void* stream, const float* df, const float* dfw, const float* dfs, const float* fv, const float* fs_bank,
+                           const int32_t* video_index, const int32_t* query_index, const int32_t* v_ptr, const int32_t* v_pairs,
+                           const int32_t* q_ptr, const int32_t* q_pairs, int P, int V, int Q, int T, int Nq, int D, float* dfv,
+                           float* dfw_bank, float* dfs_bank, void* ws, size_t ws_bytes);
 
 /* smin_corpus_topk: the K best moments of each query over all of its videos, one launch, one workgroup per query; no workspace.
  * Inputs.  The per-pair lists exactly as smin_top_moments writes them for P pairs at k = k_video: pair_score [P][k_video] fp32,

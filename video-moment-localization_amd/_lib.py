@@ -122,6 +122,8 @@ SIGNATURES = {
     "smin_row_lists_merge_workspace_bytes": [_i, _i],
     "smin_row_lists_merge": [_vp] * 5 + [_i] * 3 + [_vp] * 5 + [_vp, _sz],
     "smin_pair_assemble": [_vp] * 6 + [_i] * 6 + [_vp] * 3,
+    "smin_pair_assemble_bwd_workspace_bytes": [_i] * 3,
+    "smin_pair_assemble_bwd": [_vp] * 12 + [_i] * 6 + [_vp] * 3 + [_vp, _sz],
     "smin_corpus_topk": [_vp] * 6 + [_i] * 3 + [_vp] * 4,
     "smin_search_merge": [_vp, _i] + [_vp] * 6 + [_i] * 2 + [_vp] * 4,
     "smin_corpus_meter_ws_bytes": [_i] * 3,
@@ -134,7 +136,8 @@ _RESTYPE = {"smin_target_arch": ctypes.c_char_p, "smin_workspace_bytes": _sz,
             "smin_word_prep_bwd_workspace_bytes": _sz, "smin_score_tail_ws_bytes": _sz,
             "smin_col_sum_workspace_bytes": _sz, "smin_top_moments_ws_bytes": _sz, "smin_boundary_unit_bwd_ws_bytes": _sz, "smin_compute_ious_nms_ws_bytes": _sz,
             "smin_epoch_meter_ws_bytes": _sz, "smin_span_meter_ws_bytes": _sz, "smin_adam_ws_bytes": _sz,
-            "smin_row_lists_merge_workspace_bytes": _sz, "smin_corpus_meter_ws_bytes": _sz}
+            "smin_row_lists_merge_workspace_bytes": _sz, "smin_corpus_meter_ws_bytes": _sz,
+            "smin_pair_assemble_bwd_workspace_bytes": _sz}
 
 _lib = None
 _ws = {}
@@ -181,7 +184,7 @@ _torch_ops = None
 
 def load_torch():
     """The torch-extension binding (csrc/torch_binding.cpp): registers torch.ops.smin_hip.{smin_forward, smin_score, smin_loss, adam_step,
-    smin_encode_videos, smin_encode_queries, smin_score_pairs} -- the whole forward as one library call with its autograd graph built in
+    smin_encode_videos, smin_encode_queries, smin_score_pairs, smin_forward_pairs} -- the whole forward as one library call with its autograd graph built in
     C++, its forward-only scoring twin, the optimizer step over a parameter list, and the corpus-search operators (the two encoders
     alone and the scorer over indexed pairs of their banks).  Raises if the library is missing."""
     global _torch_ops

@@ -6,7 +6,10 @@
 //   smin_search_merge   merges up to 16 such ranked lists of disjoint video shards into one: the same K-round
 //                       selection (topk_rounds) over another way of reading candidate c, so a merge of the shards' lists is the list
 //                       smin_corpus_topk gives on the whole corpus.
-// None has a backward: the path only scores.
+// smin_pair_assemble has an adjoint, which is what lets a model train through shared banks:
+//   smin_pair_assemble_bwd  sums the pairs' gradients of f, f_w, f_s back onto the videos and queries they came from, through the
+//                           pairs grouped by video and by query (two CSR lists from the host): no atomics, a fixed order.
+// The two merges have no backward.
 #include "common.h"
 #include "smin_hip.h"
 
@@ -41,6 +44,115 @@ void pair_assemble_kernel(const float* __restrict__ fv, const float* __restrict_
         stg4(fw + ((p * Nq + w) * D4 + d4) * 4, ldg4(fw_bank + ((q * Nq + w) * D4 + d4) * 4));
     } else {
         stg4(fs + (p * D4 + d4) * 4, s);
+    }
+}
+
+// ---- the adjoint of pair_assemble_kernel.  df [P][T][D] is by far the largest operand and is read ONCE: a thread owns one float4
+// column d4 of BWD_TC consecutive frames of one video v and walks v's pairs in segment order; per pair it reads its BWD_TC quads of df,
+// adds df * fs_bank[qi[p]] to the frames' running sums (dfv, kept in registers) and writes the pair's partial dot with its own quads of
+// fv (registers as well, so fv is read once in all) to part [P][TC][D], TC = ceil(T / BWD_TC).  pair_bwd_query_kernel then sums, per
+// query, its pairs' partials and dfs in a fixed order (below).  The remaining threads of the first launch sum dfw.
+// Every value read from a list is clamped before it forms an address.
+constexpr int BWD_TC = 4;
+
+__device__ __forceinline__ float4 f4fma(float4 a, float4 b, float4 c)
+{
+    return make_float4(fmaf(a.x, b.x, c.x), fmaf(a.y, b.y, c.y), fmaf(a.z, b.z, c.z), fmaf(a.w, b.w, c.w));
+}
+__device__ __forceinline__ void segment(const int* __restrict__ ptr, int g, int P, int& s0, int& s1)
+{
+    s0 = min(max(ptr[g], 0), P);
+    s1 = min(max(ptr[g + 1], s0), P);
+}
+
+__global__ __launch_bounds__(256)
+void pair_bwd_video_kernel(const float* __restrict__ df, const float* __restrict__ dfw, const float* __restrict__ fv, const float* __restrict__ fs_bank,
+                           const int* __restrict__ query_index, const int* __restrict__ v_ptr, const int* __restrict__ v_pairs,
+                           const int* __restrict__ q_ptr, const int* __restrict__ q_pairs, int P, int V, int Q, int T, int TC, int Nq, int D4,
+                           size_t n_video, size_t total, float* __restrict__ dfv, float* __restrict__ dfw_bank, float* __restrict__ part)
+{
+    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= total) return;
+    const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (idx < n_video) {                                         // (v, frame chunk c, d4)
+        const int d4 = (int)(idx % D4);
+        const size_t vc = idx / D4;
+        const size_t v = vc / TC;
+        const int c = (int)(vc - v * TC), t0 = c * BWD_TC;
+        float4 x[BWD_TC], acc[BWD_TC];
+#pragma unroll
+        for (int j = 0; j < BWD_TC; ++j) {
+            x[j] = t0 + j < T ? ldg4(fv + ((v * T + t0 + j) * D4 + d4) * 4) : zero;
+            acc[j] = zero;
+        }
+        int s0, s1;
+        segment(v_ptr, (int)v, P, s0, s1);
+        for (int s = s0; s < s1; ++s) {
+            const size_t p = (size_t)min(max(v_pairs[s], 0), P - 1);
+            const size_t q = (size_t)min(max(query_index[p], 0), Q - 1);
+            const float4 g = ldg4(fs_bank + (q * D4 + d4) * 4);
+            float4 dot = zero;
+#pragma unroll
+            for (int j = 0; j < BWD_TC; ++j) {
+                if (t0 + j < T) {
+                    const float4 d = ldg4(df + ((p * T + t0 + j) * D4 + d4) * 4);
+                    acc[j] = f4fma(d, g, acc[j]);
+                    dot = f4fma(d, x[j], dot);
+                }
+            }
+            stg4(part + ((p * TC + c) * D4 + d4) * 4, dot);
+        }
+#pragma unroll
+        for (int j = 0; j < BWD_TC; ++j)
+            if (t0 + j < T) stg4(dfv + ((v * T + t0 + j) * D4 + d4) * 4, acc[j]);
+    } else {                                                     // (q, word w, d4)
+        const size_t i = idx - n_video;
+        const int d4 = (int)(i % D4);
+        const size_t qw = i / D4;
+        const size_t q = qw / Nq;
+        const int w = (int)(qw - q * Nq);
+        float4 acc = zero;
+        int s0, s1;
+        segment(q_ptr, (int)q, P, s0, s1);
+        for (int s = s0; s < s1; ++s) {
+            const size_t p = (size_t)min(max(q_pairs[s], 0), P - 1);
+            acc = f4add(acc, dfw ? ldg4(dfw + ((p * Nq + w) * D4 + d4) * 4) : zero);
+        }
+        stg4(dfw_bank + ((q * Nq + w) * D4 + d4) * 4, acc);
+    }
+}
+
+// One workgroup per (query, tile of BWD_QD quads): BWD_QJ lanes share the chunks of a pair, lane j taking c = j, j + BWD_QJ, ... (the
+// loads of a lane are independent: a single thread walking all chunks of all pairs is one latency chain).  Lane j sums over the
+// segment's pairs in list order, within a pair over its chunks in ascending c; dfs[p] joins lane 0; the lanes are then added in
+// ascending j.  A fixed order, a function of the arguments only.
+constexpr int BWD_QD = 32, BWD_QJ = 8;
+
+__global__ __launch_bounds__(BWD_QD * BWD_QJ)
+void pair_bwd_query_kernel(const float* __restrict__ dfs, const float* __restrict__ part, const int* __restrict__ q_ptr, const int* __restrict__ q_pairs,
+                           int P, int TC, int D4, float* __restrict__ dfs_bank)
+{
+    __shared__ float4 red[BWD_QJ][BWD_QD];
+    const int lane = threadIdx.x % BWD_QD, j = threadIdx.x / BWD_QD;
+    const int d4 = blockIdx.x * BWD_QD + lane;
+    const size_t q = blockIdx.y;
+    const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
+    float4 acc = zero;
+    if (d4 < D4) {
+        int s0, s1;
+        segment(q_ptr, (int)q, P, s0, s1);
+        for (int s = s0; s < s1; ++s) {
+            const size_t p = (size_t)min(max(q_pairs[s], 0), P - 1);
+            if (j == 0) acc = f4add(acc, dfs ? ldg4(dfs + (p * D4 + d4) * 4) : zero);
+            for (int c = j; c < TC; c += BWD_QJ) acc = f4add(acc, ldg4(part + ((p * TC + c) * D4 + d4) * 4));
+        }
+    }
+    red[j][lane] = acc;
+    __syncthreads();
+    if (j == 0 && d4 < D4) {
+#pragma unroll
+        for (int k = 1; k < BWD_QJ; ++k) acc = f4add(acc, red[k][lane]);
+        stg4(dfs_bank + (q * D4 + d4) * 4, acc);
     }
 }
 
@@ -213,6 +325,35 @@ extern "C" int smin_pair_assemble(void* stream, const float* fv, const float* fs
     SMIN_REQUIRE((total + 255) / 256 <= 0x7fffffffull);
     hipLaunchKernelGGL(pair_assemble_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, fv, fs_bank, fw_bank, video_index,
                        query_index, V, Q, T, Nq, D / 4, total, f, fw, fs);
+    SMIN_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" size_t smin_pair_assemble_bwd_workspace_bytes(int P, int T, int D)
+{
+    if (P < 1 || T < 1 || D < 4) return 0;
+    return (size_t)P * ((T + BWD_TC - 1) / BWD_TC) * D * sizeof(float);
+}
+
+extern "C" int smin_pair_assemble_bwd(void* stream, const float* df, const float* dfw, const float* dfs, const float* fv, const float* fs_bank,
+                                      const int32_t* video_index, const int32_t* query_index, const int32_t* v_ptr, const int32_t* v_pairs,
+                                      const int32_t* q_ptr, const int32_t* q_pairs, int P, int V, int Q, int T, int Nq, int D, float* dfv,
+                                      float* dfw_bank, float* dfs_bank, void* ws, size_t ws_bytes)
+{
+    SMIN_REQUIRE(D >= 4 && D % 4 == 0 && P >= 1 && V >= 1 && Q >= 1 && T >= 1 && Nq >= 1);
+    SMIN_REQUIRE(df != nullptr && fv != nullptr && fs_bank != nullptr && video_index != nullptr && query_index != nullptr);
+    SMIN_REQUIRE(v_ptr != nullptr && v_pairs != nullptr && q_ptr != nullptr && q_pairs != nullptr);
+    SMIN_REQUIRE(dfv != nullptr && dfw_bank != nullptr && dfs_bank != nullptr);
+    SMIN_REQUIRE(ws != nullptr && ws_bytes >= smin_pair_assemble_bwd_workspace_bytes(P, T, D));
+    const int D4 = D / 4, TC = (T + BWD_TC - 1) / BWD_TC;
+    const size_t n_video = (size_t)V * TC * D4, total = n_video + (size_t)Q * Nq * D4;
+    SMIN_REQUIRE((total + 255) / 256 <= 0x7fffffffull && (size_t)P * TC <= 0x7fffffffull && Q <= 65535);
+    float* part = static_cast<float*>(ws);
+    hipLaunchKernelGGL(pair_bwd_video_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, df, dfw, fv, fs_bank, query_index, v_ptr,
+                       v_pairs, q_ptr, q_pairs, P, V, Q, T, TC, Nq, D4, n_video, total, dfv, dfw_bank, part);
+    SMIN_LAUNCH_CHECK();
+    hipLaunchKernelGGL(pair_bwd_query_kernel, dim3((unsigned)((D4 + BWD_QD - 1) / BWD_QD), (unsigned)Q), dim3(BWD_QD * BWD_QJ), 0, (hipStream_t)stream, dfs, part, q_ptr,
+                       q_pairs, P, TC, D4, dfs_bank);
     SMIN_LAUNCH_CHECK();
     return 0;
 }

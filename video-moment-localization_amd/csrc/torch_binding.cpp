@@ -282,6 +282,9 @@ struct LstmState { Tensor x, Hout, G, Cs, Wih, Whh; };
 struct CoreState {
     Tensor vx, fv, vmaskf, len32, last, f, fw, fs, qmf, lmf, cells, row_ptr, cellmap, Wch_all, what, kb, Mq, uq, shat, pm, psea, fm_out, wb;
     Tensor tailv;                                              // smin_score only: the tail's vectors (not among the saved tensors)
+    // smin_forward_pairs only (undefined otherwise): the query bank's sentence features, the pair lists and their CSR groupings.  There
+    // fv, vx, vmaskf have a row per video, len32 and the LSTM state a row per query, everything else a row per pair.
+    Tensor fs_bank, vi, qi, v_ptr, v_pairs, q_ptr, q_pairs;
     LstmState lstm[2];
     std::vector<LayerState> layer;
 };
@@ -289,7 +292,7 @@ template <class F>
 void visit_state(CoreState& s, F&& fn)
 {
     for (Tensor* t : {&s.vx, &s.fv, &s.vmaskf, &s.len32, &s.last, &s.f, &s.fw, &s.fs, &s.qmf, &s.lmf, &s.cells, &s.row_ptr, &s.cellmap, &s.Wch_all, &s.what, &s.kb, &s.Mq,
-                      &s.uq, &s.shat, &s.pm, &s.psea, &s.fm_out, &s.wb})
+                      &s.uq, &s.shat, &s.pm, &s.psea, &s.fm_out, &s.wb, &s.fs_bank, &s.vi, &s.qi, &s.v_ptr, &s.v_pairs, &s.q_ptr, &s.q_pairs})
         fn(*t);
     for (auto& l : s.lstm)
         for (Tensor* t : {&l.x, &l.Hout, &l.G, &l.Cs, &l.Wih, &l.Whh}) fn(*t);
@@ -334,8 +337,15 @@ Tensor sum_list(const std::vector<Tensor>& ts)
 }
 
 // smin_score_pairs: the backbone's outputs of V videos and Q queries, each encoded once (smin_encode_videos / smin_encode_queries), and
-// the P (video, query) pairs to score: vi / qi [P] int32 on the device
-struct PairBank { Tensor fv, fw, fs, vi, qi; };
+// the P (video, query) pairs to score: vi / qi [P] int32 on the device.
+// smin_forward_pairs (train): no encoded banks -- the run encodes the V videos and Q queries itself (video_features / query_features
+// then have a row per video / per query) from the per-video and per-query masks vmask_v / qmask_q, and keeps what the backward needs:
+// the CSR groupings of the pairs by video and by query (smin_pair_assemble_bwd).
+struct PairBank {
+    Tensor fv, fw, fs, vi, qi;
+    bool train = false;
+    Tensor vmask_v, qmask_q, v_ptr, v_pairs, q_ptr, q_pairs;
+};
 
 // The query encoder (models.py:38-62): both BiLSTM layers' operand layouts in one launch, the two recurrences, f_w padded to
 // max_query_length and the sentence feature f_s.  The layers' tensors that a backward reads stay in `lstm` (scoring: dropped).
@@ -396,18 +406,21 @@ struct SminCore : torch::autograd::Function<SminCore> {
     // layer ends in smin_score_tail_fwd instead of its content-stream sum, pair product, moment unit and smin_score_map_fwd).
     // Fills st.pm / st.psea, the contiguous parameters `all` and the attention maps; returns the number of cells.
     // n_known: the number of valid cells of moment_mask when the caller knows it, else -1
-    // bank (scoring only): the backbone's outputs come from the banks through smin_pair_assemble instead of the two encoders --
-    // video_features / query_features are unused and the four masks are the pairs' (gathered by the caller)
+    // bank: the backbone's outputs of the pairs come from banks through smin_pair_assemble and the four masks are the pairs' (gathered
+    // by the caller).  Scoring: the banks are given and video_features / query_features are unused.  Training (bank->train): the two
+    // encoders run here, once per row of video_features (V, T, Din) and of query_features (Q, words, E), and their state is kept.
     static int64_t run(CoreState& st, std::vector<Tensor>& all, std::vector<Tensor>& cmaps, std::vector<Tensor>& bmaps, bool scoring, const Tensor& video_features,
                        const Tensor& video_mask, const Tensor& query_features, const Tensor& query_mask, const Tensor& length_mask, const Tensor& moment_mask, int64_t T,
                        int64_t L, int64_t C, int64_t nl, int64_t maxq, int64_t H, int64_t flags, int64_t n_known, at::TensorList prm_in, const PairBank* bank = nullptr)
     {
-        TORCH_CHECK(!bank || scoring, "banks are scored, not trained through");
+        TORCH_CHECK(!bank || scoring != bank->train, "given banks are scored; a training run encodes its own");
+        const bool own_bank = bank && bank->train;
         for (const Tensor& p : prm_in) all.push_back(cont(p));
         std::vector<Tensor> prm(all.begin() + P_LAYER0, all.end());                // the SMI layers' and the localization head's parameters
-        const at::Device dev = bank ? bank->fv.device() : video_features.device();
-        const auto opt = bank ? bank->fv.options() : video_features.options();
-        const int64_t Bq = bank ? bank->vi.size(0) : video_features.size(0), Tn = bank ? bank->fv.size(1) : video_features.size(1);
+        const Tensor& like = bank && !own_bank ? bank->fv : video_features;
+        const at::Device dev = like.device();
+        const auto opt = like.options();
+        const int64_t Bq = bank ? bank->vi.size(0) : video_features.size(0), Tn = like.size(1);
         TORCH_CHECK(Tn == T, "ProposalGeneration was built for T=", T, " but got ", Tn, " frames");
         const int B = i32(Bq), D = i32(all[P_VE_W].size(0)), Nq = i32(maxq), dl = i32(prm[L_CH_W].size(0)), Li = i32(L), Ci = i32(C), Ti = i32(T);
         auto lp = [&](int64_t k, int which) -> const Tensor& { return prm[k * L_COUNT + which]; };
@@ -514,9 +527,9 @@ struct SminCore : torch::autograd::Function<SminCore> {
         // sentence feature (models.py:81-83) waits for the LSTM layers (the fused call sat behind them: ~90 us of the step's opening chain).
         // Queued behind the parameter products: ahead of them it runs beside the LSTM operand packing and the first recurrence and
         // stretches both (pack 20 -> 84 us, recurrence 87 -> 130 us: the opening chain 45 us longer, tools/gantt.sh).
-        if (!bank) {
+        if (!bank || own_bank) {
             st.vx = cont(video_features);
-            st.fv = at::empty({Bq, T, (int64_t)D}, opt);
+            st.fv = at::empty({st.vx.size(0), T, (int64_t)D}, opt);
         }
         Tensor f = at::empty({Bq, T, (int64_t)D}, opt), fw, fs;
         hipEvent_t projection_ready = nullptr;
@@ -530,10 +543,25 @@ struct SminCore : torch::autograd::Function<SminCore> {
 
         // ---- backbone (models.py:38-83): BiLSTM x 2, sentence feature, fused video encoder
         if (bank) {
+            Tensor bfv = bank->fv, bfw = bank->fw, bfs = bank->fs;
+            if (own_bank) {
+                // the two encoders once per video and once per query, on the main stream (as smin_encode_videos / smin_encode_queries);
+                // the prologue's vmaskf and len32 above are per pair and are replaced by the encoders' own rows, which the backward reads
+                const int64_t V = st.vx.size(0), Qn = query_features.size(0);
+                Tensor vm = bank->vmask_v.reshape({V * Tn});
+                st.vmaskf = cont(vm.is_floating_point() ? fl(vm) : vm.ne(0).to(at::kFloat));
+                st.len32 = bank->qmask_q.reshape({Qn, -1}).ne(0).sum(1).to(at::kInt).contiguous();
+                SMIN_CK(smin_video_encoder_fwd(cur(), fp(st.vx), fp(all[P_VE_W]), fp(all[P_VE_B]), fp(all[P_PE]), fp(st.vmaskf), nullptr, i32(V), Ti, i32(st.vx.size(2)), D,
+                                               fpm(st.fv), nullptr));
+                std::tie(bfw, bfs) = query_encoder(st.lstm, all, query_features, st.len32, maxq, H, false);
+                bfv = st.fv;
+                st.fs_bank = bfs; st.vi = bank->vi; st.qi = bank->qi;
+                st.v_ptr = bank->v_ptr; st.v_pairs = bank->v_pairs; st.q_ptr = bank->q_ptr; st.q_pairs = bank->q_pairs;
+            }
             // both encoders ran once per video and per query: the pairs' f = f_v * f_s, f_w and f_s in one launch (csrc/corpus.hip)
             fw = at::empty({Bq, maxq, (int64_t)D}, opt); fs = at::empty({Bq, (int64_t)D}, opt);
-            SMIN_CK(smin_pair_assemble(cur(), fp(bank->fv), fp(bank->fs), fp(bank->fw), ip(bank->vi), ip(bank->qi), B, i32(bank->fv.size(0)), i32(bank->fs.size(0)), Ti, Nq,
-                                       D, fpm(f), fpm(fw), fpm(fs)));
+            SMIN_CK(smin_pair_assemble(cur(), fp(bfv), fp(bfs), fp(bfw), ip(bank->vi), ip(bank->qi), B, i32(bfv.size(0)), i32(bfs.size(0)), Ti, Nq, D, fpm(f), fpm(fw),
+                                       fpm(fs)));
         } else {
             std::tie(fw, fs) = query_encoder(st.lstm, all, query_features, st.len32, maxq, H, scoring);
             if (projection_ready) {
@@ -732,6 +760,16 @@ struct SminCore : torch::autograd::Function<SminCore> {
         return N;
     }
 
+    // what backward_from reads: every tensor of the state, the contiguous parameters, the shape
+    static void save_state(AutogradContext* ctx, CoreState& st, const std::vector<Tensor>& all, std::vector<int64_t> d)
+    {
+        variable_list flat;
+        visit_state(st, [&](Tensor& t) { flat.push_back(t); });
+        for (auto& p : all) flat.push_back(p);
+        ctx->save_for_backward(flat);
+        ctx->saved_data["d"] = std::move(d);
+    }
+
     static variable_list forward(AutogradContext* ctx, Tensor video_features, Tensor video_mask, Tensor query_features, Tensor query_mask, Tensor length_mask,
                                  Tensor moment_mask, int64_t T, int64_t L, int64_t C, int64_t nl, int64_t maxq, int64_t H, int64_t flags, int64_t n_known,
                                  at::TensorList prm_in)
@@ -744,11 +782,7 @@ struct SminCore : torch::autograd::Function<SminCore> {
         const int64_t Nq_in = query_features.size(1);
         const Tensor &pm = st.pm, &psea = st.psea, &cellmap = st.cellmap;
 
-        variable_list flat;
-        visit_state(st, [&](Tensor& t) { flat.push_back(t); });
-        for (auto& p : all) flat.push_back(p);
-        ctx->save_for_backward(flat);
-        ctx->saved_data["d"] = std::vector<int64_t>{N, T, L, C, nl, flags, H, Nq_in};
+        save_state(ctx, st, all, {N, T, L, C, nl, flags, H, Nq_in});
         // ps / pe / pa leave as three outputs of the node (rows of one buffer), not as selections of one output: the selections'
         // backward nodes cost three zero fills, three copies and two adds between the loss and this node's backward
         if (!keep_maps) return {pm, psea[0], psea[1], psea[2]};
@@ -760,7 +794,13 @@ struct SminCore : torch::autograd::Function<SminCore> {
         return out;
     }
 
-    static variable_list backward(AutogradContext* ctx, variable_list g)
+    static variable_list backward(AutogradContext* ctx, variable_list g) { return backward_from(ctx, g, N_FIXED); }
+
+    // The backward pass of a state run() left (this node's and SminPairCore's): the parameters' gradients in slots n_fixed .. of the
+    // result, the inputs' (F_INPUT_GRADS) in slots 0 and 2.  With the pair lists in the state (smin_forward_pairs) everything down to
+    // df, dfs_parts and dfw_parts runs at batch P as it stands; smin_pair_assemble_bwd then sums the pairs onto their videos and
+    // queries, and the backbone's backward runs at batch V (video encoder) and Q (sentence feature, LSTM layers).
+    static variable_list backward_from(AutogradContext* ctx, variable_list g, int64_t n_fixed)
     {
         auto d = ctx->saved_data["d"].toIntVector();
         const int64_t N = d[0], T = d[1], L = d[2], C = d[3], nl = d[4], flags = d[5], H = d[6], Nq_in = d[7];
@@ -1190,7 +1230,9 @@ struct SminCore : torch::autograd::Function<SminCore> {
         {
             const int Din = i32(st.vx.size(2));
             const int64_t pe_rows = all[P_PE].size(0);
-            Tensor dfs_video = at::empty_like(fs);
+            const bool pairs = st.vi.defined();
+            const int Bv = i32(st.vx.size(0)), Bw = i32(st.lstm[0].x.size(0));     // rows of the video encoder and of the query encoder (B unless pairs)
+            Tensor dfs_video = at::empty({(int64_t)Bv, (int64_t)D}, opt);
             dbb[P_VE_W] = at::empty({D, Din}, opt); dbb[P_VE_B] = at::empty({D}, opt);
             dbb[P_PE] = pe_rows != T ? at::zeros({pe_rows, D}, opt) : at::empty({T, D}, opt);
             // every call below is split into its inputs half (main stream, the dependent chain) and its weights half (weight stream); the
@@ -1200,21 +1242,41 @@ struct SminCore : torch::autograd::Function<SminCore> {
                 keep.push_back(t);
                 return t;
             };
-            Tensor wsv = own(smin_video_encoder_bwd_workspace_bytes(B, Ti, Din, D));
-            SMIN_CK(smin_video_encoder_bwd(cur(), fp(df), fp(st.fv), fp(fs), fp(st.vmaskf), fp(st.vx), B, Ti, Din, D, nullptr, nullptr, nullptr, fpm(dfs_video), wsv.data_ptr(),
-                                           (size_t)wsv.numel()));
-            dfs_parts.push_back(dfs_video);
-            if (wordst != curs) await(curs, words_done);
-            Tensor dfs_total = sum_list(dfs_parts), dfw_total = sum_list(dfw_parts);
+            Tensor wsv = own(smin_video_encoder_bwd_workspace_bytes(Bv, Ti, Din, D));
+            Tensor dfs_total, dfw_total, venc_fs = fs;
+            if (pairs) {
+                // the pairs' gradients onto their videos and queries (csrc/corpus.hip): df -> dfv, the per-pair sums of dfw / dfs and the
+                // product's gradient of f_s -> the query bank's rows.  The video encoder's backward has no fs == NULL mode: it takes dfv as
+                // its df and ones as fs (a multiplication by 1.0f is exact; its dfs output is not used).
+                if (wordst != curs) await(curs, words_done);
+                Tensor dfs_p = sum_list(dfs_parts), dfw_p = sum_list(dfw_parts);
+                Tensor dfv = at::empty_like(st.fv);
+                dfw_total = at::empty({(int64_t)Bw, (int64_t)Nq, (int64_t)D}, opt); dfs_total = at::empty({(int64_t)Bw, (int64_t)D}, opt);
+                Tensor wsp = own(smin_pair_assemble_bwd_workspace_bytes(B, Ti, D));
+                SMIN_CK(smin_pair_assemble_bwd(cur(), fp(df), fp(dfw_p), fp(dfs_p), fp(st.fv), fp(st.fs_bank), ip(st.vi), ip(st.qi), ip(st.v_ptr), ip(st.v_pairs),
+                                               ip(st.q_ptr), ip(st.q_pairs), B, Bv, Bw, Ti, Nq, D, fpm(dfv), fpm(dfw_total), fpm(dfs_total), wsp.data_ptr(),
+                                               (size_t)wsp.numel()));
+                keep.push_back(dfs_p); keep.push_back(dfw_p);
+                venc_fs = at::ones({(int64_t)Bv, (int64_t)D}, opt);
+                keep.push_back(venc_fs);
+                df = dfv;
+            }
+            SMIN_CK(smin_video_encoder_bwd(cur(), fp(df), fp(st.fv), fp(venc_fs), fp(st.vmaskf), fp(st.vx), Bv, Ti, Din, D, nullptr, nullptr, nullptr, fpm(dfs_video),
+                                           wsv.data_ptr(), (size_t)wsv.numel()));
+            if (!pairs) {
+                dfs_parts.push_back(dfs_video);
+                if (wordst != curs) await(curs, words_done);
+                dfs_total = sum_list(dfs_parts); dfw_total = sum_list(dfw_parts);
+            }
             // f_s = [f_w[b, len_b - 1, :H] | f_w[b, 0, H:]] (models.py:60-62)
-            SMIN_CK(smin_sentence_feature_bwd(cur(), fp(dfs_total), ip(st.len32), B, Nq, i32(H), fpm(dfw_total)));
+            SMIN_CK(smin_sentence_feature_bwd(cur(), fp(dfs_total), ip(st.len32), Bw, Nq, i32(H), fpm(dfw_total)));
             Tensor dH = Nq_in < Nq ? dfw_total.slice(1, 0, Nq_in).contiguous() : dfw_total;
-            keep.push_back(dfs_total); keep.push_back(dfw_total); keep.push_back(dH); keep.push_back(df);
+            keep.push_back(dfs_total); keep.push_back(dfw_total); keep.push_back(dH); keep.push_back(df); keep.push_back(dfs_video);
             wait_stream(bstr, curs);
             {
                 StreamScope sc(bstr);
-                SMIN_CK(smin_video_encoder_bwd(cur(), nullptr, fp(st.fv), fp(fs), fp(st.vmaskf), fp(st.vx), B, Ti, Din, D, fpm(dbb[P_VE_W]), fpm(dbb[P_VE_B]), fpm(dbb[P_PE]),
-                                               nullptr, wsv.data_ptr(), (size_t)wsv.numel()));
+                SMIN_CK(smin_video_encoder_bwd(cur(), nullptr, fp(st.fv), fp(venc_fs), fp(st.vmaskf), fp(st.vx), Bv, Ti, Din, D, fpm(dbb[P_VE_W]), fpm(dbb[P_VE_B]),
+                                               fpm(dbb[P_PE]), nullptr, wsv.data_ptr(), (size_t)wsv.numel()));
             }
             for (int layer = 1; layer >= 0; --layer) {
                 LstmState& ls = st.lstm[layer];
@@ -1222,8 +1284,8 @@ struct SminCore : torch::autograd::Function<SminCore> {
                 Tensor dX = layer > 0 || want_dX ? at::empty_like(ls.x) : Tensor();
                 Tensor dWih = at::empty_like(ls.Wih), dbias = at::empty({8 * H}, opt), dWhh = at::empty_like(ls.Whh);
                 lstm_bufs.push_back(dWih); lstm_bufs.push_back(dbias); lstm_bufs.push_back(dWhh);
-                Tensor wsl = own(smin_bilstm_layer_bwd_workspace_bytes(B, i32(Nq_in), In, Hh));
-                SMIN_CK(smin_bilstm_layer_bwd(cur(), fp(dH), fp(ls.x), fp(ls.Hout), fp(ls.G), fp(ls.Cs), fp(WihT[layer]), fp(ls.Whh), ip(st.len32), B, i32(Nq_in), In, Hh,
+                Tensor wsl = own(smin_bilstm_layer_bwd_workspace_bytes(Bw, i32(Nq_in), In, Hh));
+                SMIN_CK(smin_bilstm_layer_bwd(cur(), fp(dH), fp(ls.x), fp(ls.Hout), fp(ls.G), fp(ls.Cs), fp(WihT[layer]), fp(ls.Whh), ip(st.len32), Bw, i32(Nq_in), In, Hh,
                                               fpm(dX), nullptr, nullptr, nullptr, wsl.data_ptr(), (size_t)wsl.numel()));
                 // the weight gradients: three independent pieces; the last layer's (nothing else is left to run by then) on three streams,
                 // pieces that share a stream in one call.  b_ih and b_hh get the same gradient in two tensors (dbias2: one tensor handed
@@ -1237,7 +1299,7 @@ struct SminCore : torch::autograd::Function<SminCore> {
                     while (pc + 1 < 3 && piece[pc + 1] == piece[pc]) which |= 1 << ++pc;
                     wait_stream(piece[pc], curs);
                     StreamScope sc(piece[pc]);
-                    SMIN_CK(smin_bilstm_layer_bwd_weights(cur(), which, fp(ls.x), fp(ls.Hout), B, i32(Nq_in), In, Hh, fpm(dWih), fpm(dbias), fpm(dbias2), fpm(dWhh),
+                    SMIN_CK(smin_bilstm_layer_bwd_weights(cur(), which, fp(ls.x), fp(ls.Hout), Bw, i32(Nq_in), In, Hh, fpm(dWih), fpm(dbias), fpm(dbias2), fpm(dWhh),
                                                           wsl.data_ptr(), (size_t)wsl.numel()));
                 }
                 if (dX.defined()) keep.push_back(dX);
@@ -1252,7 +1314,7 @@ struct SminCore : torch::autograd::Function<SminCore> {
             // co-resident, and here only the layer-0 weight pieces are left beside it (measured against the weight stream: DESIGN 6)
             if (want_dx) {
                 dvideo = at::empty_like(st.vx);
-                SMIN_CK(smin_video_encoder_bwd_input(cur(), fp(tr[tr_tail + 3]), fp(st.vmaskf), B, Ti, Din, D, fpm(dvideo), wsv.data_ptr(), (size_t)wsv.numel()));
+                SMIN_CK(smin_video_encoder_bwd_input(cur(), fp(tr[tr_tail + 3]), fp(st.vmaskf), Bv, Ti, Din, D, fpm(dvideo), wsv.data_ptr(), (size_t)wsv.numel()));
             }
         }
         wait_stream(curs, tail);
@@ -1265,12 +1327,36 @@ struct SminCore : torch::autograd::Function<SminCore> {
             sync.join(curs);
         }
 
-        variable_list out(N_FIXED + all.size());
+        variable_list out(n_fixed + all.size());
         if (want_dx) out[0] = dvideo;
         if (want_dX) out[2] = dquery;
-        for (size_t i = 0; i < all.size(); ++i) out[N_FIXED + i] = i < (size_t)P_LAYER0 ? dbb[i] : dprm[i - P_LAYER0];
+        for (size_t i = 0; i < all.size(); ++i) out[n_fixed + i] = i < (size_t)P_LAYER0 ? dbb[i] : dprm[i - P_LAYER0];
         return out;
     }
+};
+
+// smin_forward_pairs' node: SminCore's run on the pairs of banks it encodes itself, and SminCore's backward (backward_from).
+struct SminPairCore : torch::autograd::Function<SminPairCore> {
+    enum { N_FIXED = 20 };          // forward arguments ahead of the parameter list
+    static variable_list forward(AutogradContext* ctx, Tensor video_features, Tensor video_mask, Tensor query_features, Tensor query_mask, Tensor length_mask,
+                                 Tensor moment_mask, Tensor video_index, Tensor query_index, Tensor v_ptr, Tensor v_pairs, Tensor q_ptr, Tensor q_pairs, int64_t T, int64_t L,
+                                 int64_t C, int64_t nl, int64_t maxq, int64_t H, int64_t flags, int64_t n_known, at::TensorList prm_in)
+    {
+        PairBank bank;
+        bank.train = true;
+        bank.vi = video_index; bank.qi = query_index;
+        bank.vmask_v = video_mask; bank.qmask_q = query_mask;
+        bank.v_ptr = v_ptr; bank.v_pairs = v_pairs; bank.q_ptr = q_ptr; bank.q_pairs = q_pairs;
+        // the byte masks per pair, as smin_score_pairs gathers them: P * (T + Nq + L + L * L) bytes
+        Tensor vm = video_mask.index_select(0, bank.vi), qm = query_mask.index_select(0, bank.qi), lm = length_mask.index_select(0, bank.vi),
+               mm = moment_mask.index_select(0, bank.vi);
+        CoreState st;
+        std::vector<Tensor> all, cmaps, bmaps;
+        const int64_t N = SminCore::run(st, all, cmaps, bmaps, false, video_features, vm, query_features, qm, lm, mm, T, L, C, nl, maxq, H, flags, n_known, prm_in, &bank);
+        SminCore::save_state(ctx, st, all, {N, T, L, C, nl, flags, H, query_features.size(1)});
+        return {st.pm, st.psea[0], st.psea[1], st.psea[2]};
+    }
+    static variable_list backward(AutogradContext* ctx, variable_list g) { return SminCore::backward_from(ctx, g, N_FIXED); }
 };
 
 // ---------------------------------------------------------------- the model
@@ -1423,6 +1509,46 @@ std::tuple<Tensor, Tensor, Tensor, Tensor> smin_score_pairs(
     return std::make_tuple(st.pm, st.psea[0], st.psea[1], st.psea[2]);
 }
 
+// SMIN.forward_pairs: smin_forward for the P pairs (video_index[p], query_index[p]) of V videos and Q queries that
+// are each encoded once -- one autograd node, differentiable with respect to the parameters.  video_features (V, T, Din) and the three
+// video-side masks have a row per video, query_features (Q, words, E) and query_mask a row per query; video_index / query_index (P,)
+// int32 on the device, and the same pairs grouped by video (v_ptr (V + 1,), v_pairs (P,)) and by query (q_ptr (Q + 1,), q_pairs (P,)),
+// each segment in ascending p -- what smin_pair_assemble_bwd sums over.  Outputs as smin_forward's first four, one row per pair.
+// The node has no in-node gradient exchange, forms no input gradients and keeps no attention maps: those options are not in the schema.
+std::tuple<Tensor, Tensor, Tensor, Tensor> smin_forward_pairs(
+    const Tensor& video_features, const Tensor& video_mask, const Tensor& query_features, const Tensor& query_mask_in, const Tensor& length_mask,
+    const Tensor& moment_mask, const Tensor& video_index, const Tensor& query_index, const Tensor& v_ptr, const Tensor& v_pairs, const Tensor& q_ptr,
+    const Tensor& q_pairs, at::TensorList prm, int64_t T, int64_t L, int64_t C, int64_t num_smi_layers, int64_t max_query_length, int64_t lstm_hidden_size,
+    bool overlap_boundary, bool overlap_prep, bool param_prep_kernel, bool async_weights, bool bf16_operand_storage, std::optional<int64_t> known_cell_count,
+    bool tail_split)
+{
+    for (const Tensor* t : {&video_features, &video_mask, &query_features, &query_mask_in, &length_mask, &moment_mask, &video_index, &query_index, &v_ptr, &v_pairs,
+                            &q_ptr, &q_pairs})
+        TORCH_CHECK(t->is_cuda(), "smin_forward_pairs runs on a HIP device only (there is no CPU fallback)");
+    TORCH_CHECK(!video_features.requires_grad() && !query_features.requires_grad(), "smin_forward_pairs forms no gradients of video_features / query_features");
+    const int64_t nl = num_smi_layers, maxq = max_query_length;
+    TORCH_CHECK((int64_t)prm.size() == P_LAYER0 + nl * L_COUNT + 8, "smin_forward_pairs: expected ", P_LAYER0 + nl * L_COUNT + 8, " parameters, got ", prm.size());
+    TORCH_CHECK(video_features.dim() == 3 && video_features.scalar_type() == at::kFloat && query_features.dim() == 3 && query_features.scalar_type() == at::kFloat,
+                "smin_forward_pairs: video_features (V, T, Din) and query_features (Q, words, E) float32");
+    const int64_t V = video_features.size(0), Q = query_features.size(0), P = video_index.numel();
+    TORCH_CHECK(V >= 1 && Q >= 1 && P >= 1 && video_index.dim() == 1 && query_index.dim() == 1 && query_index.size(0) == P,
+                "smin_forward_pairs: at least one video, one query and one pair; video_index and query_index are (P,)");
+    TORCH_CHECK(video_mask.size(0) == V && video_mask.numel() == V * T && length_mask.size(0) == V && moment_mask.size(0) == V,
+                "smin_forward_pairs: video_mask (V, T), length_mask and moment_mask have a row per video");
+    auto i32list = [](const Tensor& t, int64_t n) { return t.dim() == 1 && t.size(0) == n && t.scalar_type() == at::kInt; };
+    TORCH_CHECK(i32list(video_index, P) && i32list(query_index, P) && i32list(v_ptr, V + 1) && i32list(v_pairs, P) && i32list(q_ptr, Q + 1) && i32list(q_pairs, P),
+                "smin_forward_pairs: video_index, query_index, v_pairs, q_pairs (P,), v_ptr (V + 1,) and q_ptr (Q + 1,) are int32");
+    Tensor query_mask = padded_query_mask("smin_forward_pairs", query_features, query_mask_in, maxq);
+    c10::hip::HIPGuard device_guard(video_features.device().index());
+    const int64_t flags = (overlap_boundary ? SminCore::F_OVERLAP_BOUNDARY : 0) | (overlap_prep ? SminCore::F_OVERLAP_PREP : 0) |
+                          (param_prep_kernel ? SminCore::F_PARAM_PREP_KERNEL : 0) | (async_weights ? SminCore::F_ASYNC_WEIGHTS : 0) |
+                          (bf16_operand_storage ? SminCore::F_BF16_OPERANDS : 0) | (tail_split ? SminCore::F_TAIL_SPLIT : 0);
+    auto out = SminPairCore::apply(video_features, video_mask, query_features, query_mask, length_mask, moment_mask, cont(video_index), cont(query_index), cont(v_ptr),
+                                   cont(v_pairs), cont(q_ptr), cont(q_pairs), T, L, C, nl, maxq, lstm_hidden_size, flags, known_cell_count.value_or(-1), prm);
+    TORCH_CHECK(out.size() == 4, "smin_forward_pairs: ", out.size(), " outputs");
+    return std::make_tuple(out[0], out[1], out[2], out[3]);
+}
+
 Tensor smin_loss(const Tensor& pm, const Tensor& ym, const Tensor& sm, const Tensor& moment_mask, const Tensor& ps, const Tensor& ys, const Tensor& ss, const Tensor& pe,
                  const Tensor& ye, const Tensor& se, const Tensor& pa, const Tensor& ya, const Tensor& length_mask)
 {
@@ -1502,6 +1628,11 @@ TORCH_LIBRARY(smin_hip, m)
     m.def("smin_score_pairs(Tensor fv, Tensor fw, Tensor fs, Tensor video_mask, Tensor query_mask, Tensor length_mask, Tensor moment_mask, Tensor video_index, "
           "Tensor query_index, Tensor[] params, int T, int L, int C, int num_smi_layers, int max_query_length, int lstm_hidden_size, *, bool overlap_boundary, "
           "bool overlap_prep, bool param_prep_kernel, bool bf16_operand_storage, int? known_cell_count) -> (Tensor, Tensor, Tensor, Tensor)", &smin_score_pairs);
+    // SMIN.forward_pairs: smin_forward over indexed pairs of videos and queries encoded once each, one autograd node
+    m.def("smin_forward_pairs(Tensor video_features, Tensor video_mask, Tensor query_features, Tensor query_mask, Tensor length_mask, Tensor moment_mask, "
+          "Tensor video_index, Tensor query_index, Tensor v_ptr, Tensor v_pairs, Tensor q_ptr, Tensor q_pairs, Tensor[] params, int T, int L, int C, "
+          "int num_smi_layers, int max_query_length, int lstm_hidden_size, *, bool overlap_boundary, bool overlap_prep, bool param_prep_kernel, "
+          "bool async_weights, bool bf16_operand_storage, int? known_cell_count, bool tail_split) -> (Tensor, Tensor, Tensor, Tensor)", &smin_forward_pairs);
     // restated loss_fn of the reference's train loop (main.py:110-116), same argument order
     m.def("smin_loss(Tensor pm, Tensor ym, Tensor sm, Tensor moment_mask, Tensor ps, Tensor ys, Tensor ss, Tensor pe, Tensor ye, Tensor se, Tensor pa, Tensor ya, "
           "Tensor length_mask) -> Tensor", &smin_loss);

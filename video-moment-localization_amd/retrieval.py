@@ -1,7 +1,8 @@
 """Retrieval on top of SMIN's scores, which the reference does not have: the best moments of a sample (``localize``), of videos of
 any length over overlapping windows (``localize_windows``) and of a corpus encoded once (``encode_videos`` / ``encode_queries`` ->
-``score_pairs`` / ``search``): host code around the library's kernels and the model's own ``score`` / ``forward``, which
-``modules.SMIN`` inherits through the stateless mixin ``_Retrieval``."""
+``score_pairs`` / ``search``), and the training counterpart of the last, ``forward_pairs`` over (video, query) pairs that share their
+encoders: host code around the library's kernels and the model's own ``score`` / ``forward``, which ``modules.SMIN`` inherits
+through the stateless mixin ``_Retrieval``."""
 import numpy as np
 import torch
 
@@ -46,6 +47,48 @@ class QueryBank:
 def _require_banks(what, videos, queries):
     if not isinstance(videos, VideoBank) or not isinstance(queries, QueryBank):
         raise TypeError(f"{what}: videos is a VideoBank (encode_videos) and queries a QueryBank (encode_queries)")
+
+
+class PairPlan:
+    """The index lists of P (video, query) pairs over V videos and Q queries as forward_pairs and training.pair_targets read them:
+    the checked host lists ``vi`` / ``qi`` (int64 numpy) and, on ``device`` as int32, ``video_index`` / ``query_index (P,)`` and the
+    same pairs grouped by video -- ``v_ptr (V + 1,)``, ``v_pairs (P,)`` -- and by query -- ``q_ptr (Q + 1,)``, ``q_pairs (P,)`` --,
+    each segment in ascending p (smin_pair_assemble_bwd sums in that order).  With ``gt_video`` (Q host ints, each query's own video)
+    also ``positive (P,)`` int32, 1 where ``video_index[p] == gt_video[query_index[p]]``, and ``positive_rows``, the ordinals of
+    those pairs (int64).  Everything is formed on the host and travels in ONE pinned asynchronous copy (a plain copy on the CPU)."""
+
+    def __init__(self, video_index, query_index, V, Q, device, gt_video=None, what="pair_plan"):
+        vi, qi = host_array(video_index), host_array(query_index)
+        if vi.shape[0] != qi.shape[0]:
+            raise ValueError(f"{what}: video_index and query_index must have one length (got {vi.shape[0]} and {qi.shape[0]})")
+        P = vi.shape[0]
+        if P < 1:
+            raise ValueError(f"{what}: at least one pair")
+        if vi.min() < 0 or vi.max() >= V or qi.min() < 0 or qi.max() >= Q:
+            raise ValueError(f"{what}: video_index must lie in [0, {V}) and query_index in [0, {Q})")
+        parts = [vi, qi]
+        for idx, n in ((vi, V), (qi, Q)):
+            parts += [np.concatenate([[0], np.cumsum(np.bincount(idx, minlength=n))]), np.argsort(idx, kind="stable")]
+        rows = None
+        if gt_video is not None:
+            gv = host_array(gt_video)
+            if gv.shape[0] != Q:
+                raise ValueError(f"{what}: gt_video must name a video for each of the Q = {Q} queries (got {gv.shape[0]})")
+            pos = vi == gv[qi]
+            rows = np.flatnonzero(pos)
+            parts += [pos, rows]
+        host = torch.from_numpy(np.concatenate(parts).astype(np.int32))
+        device = torch.device(device)
+        buf = host.pin_memory().to(device, non_blocking=True) if device.type == "cuda" else host
+        cut = np.cumsum([0, P, P, V + 1, P, Q + 1, P] + ([P, rows.shape[0]] if rows is not None else []))
+        cuts = [buf[cut[k]:cut[k + 1]] for k in range(len(cut) - 1)]
+        self.vi, self.qi, self.V, self.Q, self.P, self.device = vi, qi, V, Q, P, device
+        self.video_index, self.query_index, self.v_ptr, self.v_pairs, self.q_ptr, self.q_pairs = cuts[:6]
+        self.positive, self.positive_rows = (cuts[6], cuts[7].to(torch.int64)) if rows is not None else (None, None)
+        self.num_positive = None if rows is None else int(rows.shape[0])
+
+    def fits(self, V, Q, device):
+        return self.V == V and self.Q == Q and self.device == torch.device(device)
 
 
 def _chunk_buffers(n, k, max_batch, dev):
@@ -249,6 +292,59 @@ class _Retrieval:
         dev = videos.video_features.device
         idx = torch.from_numpy(np.concatenate([vi, qi]).astype(np.int32)).pin_memory().to(dev, non_blocking=True)
         return self._score_pairs(videos, queries, vi, qi, idx[:vi.shape[0]], idx[vi.shape[0]:])
+
+    # ---------------------------------------------------------------- training through shared banks
+    def forward_pairs(self, video_features, video_mask, query_features, query_mask, length_mask, moment_mask, video_index, query_index,
+                      cell_counts=None, plan=None):
+        """(pm, ps, pe, pa) as forward returns them for the P pairs (video video_index[p], query query_index[p]) of V videos and Q
+        queries, differentiable with respect to the parameters: the video encoder runs once per video and the query encoder once per
+        query, in the forward and in the backward, and no pair carries a copy of its video's features.  ``video_features (V, T, Din)``,
+        ``video_mask``, ``length_mask`` and ``moment_mask`` have a row per video, ``query_features (Q, words, E)`` and ``query_mask`` a
+        row per query; ``video_index`` / ``query_index``: host int sequences of one length P >= 1, any lists, repeats included; an
+        index out of range or an empty list raises ValueError.  ``cell_counts``: the V videos' valid-cell counts as host ints
+        (feeder.cell_count); with them the pairs' count is host arithmetic and the step reads nothing back, without them the node
+        reads the count once, as forward does.  ``plan``: a PairPlan already built from these lists (training.train_epoch_pairs
+        shares one with pair_targets: one copy for both).
+
+        On the one-node path this is smin_hip::smin_forward_pairs, one autograd node: smin_pair_assemble where smin_forward has the
+        product f = f_v * f_s, the layers at batch P, and in the backward smin_pair_assemble_bwd -- a sum over the pairs that share a
+        video or a query, in list order, the same bits every run -- in front of the encoders' backward at batch V and Q.  Where
+        forward would not take that path (_plan != "node", keep_attention) the pairs are expanded with index_select and go through
+        forward: bit for bit that route.  Not with grad_sync (data-parallel training through this node is out of scope)."""
+        V, Q = video_features.shape[0], query_features.shape[0]
+        if plan is None:
+            plan = PairPlan(video_index, query_index, V, Q, video_features.device, what="forward_pairs")
+        elif not plan.fits(V, Q, video_features.device):
+            raise ValueError(f"forward_pairs: the plan was built for {plan.V} videos and {plan.Q} queries on {plan.device}")
+        require_hip_tensors("forward_pairs", dict(video_features=video_features, video_mask=video_mask, query_features=query_features, query_mask=query_mask,
+                                                  length_mask=length_mask, moment_mask=moment_mask))
+        if video_features.dim() != 3 or query_features.dim() != 3 or V < 1 or Q < 1 or video_mask.shape[0] != V or length_mask.shape[0] != V \
+                or moment_mask.shape[0] != V or query_mask.shape[0] != Q:
+            raise ValueError("forward_pairs: video_features (V, T, Din), video_mask, length_mask and moment_mask with a row per video; "
+                             "query_features (Q, words, E) and query_mask with a row per query")
+        if self.grad_sync:
+            raise RuntimeError("forward_pairs: not combined with the in-node gradient exchange (SMIN.grad_sync)")
+        cells = None
+        if cell_counts is not None:
+            cc = host_array(cell_counts)
+            if cc.shape[0] != V:
+                raise ValueError(f"forward_pairs: cell_counts must hold the V = {V} videos' counts (got {cc.shape[0]})")
+            cells = int(cc[plan.vi].sum())
+        vi_d, qi_d = plan.video_index, plan.query_index
+        with known_cells(self, cells), torch.cuda.device(video_features.device):
+            if not self._bank_plan(video_features, query_features):
+                # as score_pairs: configurations off the one-node path (and keep_attention) run the forward on expanded pairs
+                return self.forward(video_features.index_select(0, vi_d), video_mask.index_select(0, vi_d), query_features.index_select(0, qi_d),
+                                    query_mask.index_select(0, qi_d), length_mask.index_select(0, vi_d), moment_mask.index_select(0, vi_d))
+            qm = query_mask_rows(query_features, query_mask, self.max_query_length)
+            if qm.shape[1] < self.max_query_length:
+                qm = torch.nn.functional.pad(qm, (0, self.max_query_length - qm.shape[1]))
+            o = self._node_options()
+            for refused in ("grad_sync", "input_grads", "attention"):
+                o.pop(refused)
+            return _lib.load_torch().smin_forward_pairs(
+                video_features, video_mask, query_features, qm, length_mask, moment_mask, vi_d, qi_d, plan.v_ptr, plan.v_pairs, plan.q_ptr, plan.q_pairs,
+                self._native_params(), self.T, self.L, self.C, len(self.smis), self.max_query_length, self.lstm_hidden_size, **o)
 
     def _search_plan(self, what, videos, queries, pairs, k, k_video, max_batch, duration):
         k_video = k if k_video is None else k_video

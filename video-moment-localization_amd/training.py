@@ -229,6 +229,61 @@ def train_epoch(model, optimizer, batches, meter=None):
     return metrics["loss"], metrics
 
 
+def pair_targets(video_masks, query_targets, video_index, query_index, gt_video, plan=None):
+    """The masks and loss targets of P (video, query) pairs, as forward_pairs pairs them, from per-video and per-query tensors:
+    ``video_masks``: a dict with ``video_mask``, ``length_mask``, ``moment_mask`` (a row per video); ``query_targets``: a dict with
+    LOSS_TARGETS (a row per query: query q's targets against its ground-truth video ``gt_video[q]``, as build_targets_hip made
+    them).  Returns a dict with the three masks gathered per pair and LOSS_TARGETS per pair: query ``query_index[p]``'s own where
+    ``video_index[p] == gt_video[query_index[p]]`` (a positive pair), all-zero otherwise -- with ym = 0 and sm = 0 loss_fn pushes a
+    negative pair's whole map, and its boundary scores, towards 0.  ``video_index`` / ``query_index`` / ``gt_video``: host ints; the
+    positive flags are host arithmetic and travel with the lists (retrieval.PairPlan; ``plan``: one already built with gt_video, as
+    train_epoch_pairs shares with forward_pairs).  Torch indexing on the tensors' device; no host read."""
+    from .retrieval import PairPlan
+    mm = video_masks["moment_mask"]
+    V, Q = mm.shape[0], query_targets["sm"].shape[0]
+    if plan is None:
+        plan = PairPlan(video_index, query_index, V, Q, mm.device, gt_video=gt_video, what="pair_targets")
+    elif plan.positive is None or not plan.fits(V, Q, mm.device):
+        raise ValueError("pair_targets: the plan must be built with gt_video for these videos and queries")
+    out = {k: video_masks[k].index_select(0, plan.video_index) for k in ("video_mask", "length_mask", "moment_mask")}
+    keep = plan.positive != 0
+    for k in LOSS_TARGETS:
+        t = query_targets[k].index_select(0, plan.query_index)
+        out[k] = torch.where(keep.reshape((-1,) + (1,) * (t.dim() - 1)), t, torch.zeros((), dtype=t.dtype, device=t.device))
+    return out
+
+
+def train_epoch_pairs(model, optimizer, groups, meter=None):
+    """train_epoch over groups of V videos and Q queries that share their encoders (SMIN.forward_pairs).  A group
+    is a dict with ``video_features``, ``video_mask``, ``length_mask``, ``moment_mask`` (a row per video), ``query_features``,
+    ``query_mask`` and LOSS_TARGETS (a row per query, against its own video), the host lists ``video_index``, ``query_index`` (the
+    pairs) and ``gt_video`` (Q,), and optionally ``cell_counts`` (V host ints: the step then reads nothing back).  Per group: one
+    PairPlan (one pinned copy), forward_pairs, pair_targets, loss_fn over all the pairs, backward, optimizer.step; ``meter.update``
+    runs over the positive pairs only, their rows gathered by the plan's device index list, so ``num_samples`` counts queries with
+    their own video listed, not pairs (a group without a positive pair raises ValueError).  One host read, ``meter.result()`` at
+    the end; returns ``(train_loss, iou_metrics)``.  The meter is not reset here."""
+    from .retrieval import PairPlan
+    model.train()
+    for g in groups:
+        meter = _meter_for(meter, g)
+        mm = g["moment_mask"]
+        plan = PairPlan(g["video_index"], g["query_index"], mm.shape[0], g["query_features"].shape[0], mm.device, gt_video=g["gt_video"],
+                        what="train_epoch_pairs")
+        if plan.num_positive < 1:
+            raise ValueError("train_epoch_pairs: a group must list at least one query with its own video (the metric runs over those pairs)")
+        optimizer.zero_grad()
+        out = model.forward_pairs(*_inputs(g), None, None, cell_counts=g.get("cell_counts"), plan=plan)
+        tg = pair_targets(g, g, None, None, None, plan=plan)
+        loss = _loss_of(out, tg)
+        rows = plan.positive_rows
+        meter.update(out[0].detach().index_select(0, rows), out[1].detach().index_select(0, rows), out[2].detach().index_select(0, rows),
+                     tg["moment_mask"].index_select(0, rows), tg["sm"].index_select(0, rows), loss=loss.detach())
+        loss.backward()
+        optimizer.step()
+    metrics = meter.result()
+    return metrics["loss"], metrics
+
+
 def eval_epoch(model, batches, meter=None):
     """reference main.py:167-191 in the same way, under torch.no_grad(); the scores come from ``model.score`` when
     ``model.forward_only_scoring`` is set, else from ``model(...)``.  Returns ``(eval_loss, iou_metrics)``."""
