@@ -367,3 +367,52 @@ def test_known_cells_sets_and_restores():
             assert m.known_cell_count == before
             m.known_cell_count = 99                                  # None: no-op, so nothing is put back either
         assert m.known_cell_count == 99
+
+
+def test_ctypes_table_rows_match_the_header():
+    """_lib.SIGNATURES / _lib._RESTYPE are parsed from include/smin_hip.h.  These rows are written out by hand from the header; between
+    them they hold every C type it uses: an empty list, a char* return, a size_t return, float, double, a leading int64_t,
+    pointer-to-pointer, a void* + size_t workspace pair."""
+    import ctypes
+    import models
+    _lib = models.vml_amd._lib
+    vp, i, sz, f, d, i64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t, ctypes.c_float, ctypes.c_double, ctypes.c_int64
+    rows = {
+        "smin_abi_version": ([], i),
+        "smin_target_arch": ([], ctypes.c_char_p),
+        "smin_workspace_bytes": ([i, i, i, i, i, i], sz),
+        "smin_top_moments": ([vp, vp, vp, vp, vp, i, i, i, f, vp, vp, vp, vp, sz], i),
+        "smin_adam_step": ([vp, vp, vp, vp, vp, i, vp, vp, vp, d, d, d, d, i, i, vp], i),
+        "smin_adam_ws_bytes": ([i64, i], sz),
+        "smin_gate_bwd": ([vp, vp, i, vp, i, vp, vp, vp, i, i, i, i, vp, vp, vp, sz, vp, vp, vp], i),
+        "smin_linear_rows_fwd": ([vp, vp, i, vp, vp, vp, vp, i, i, i, i, vp], i),
+    }
+    for name, (args, ret) in rows.items():
+        assert _lib.SIGNATURES[name] == args, name
+        assert _lib._RESTYPE.get(name, i) is ret, name
+    assert all(_lib._RESTYPE[n] in (sz, ctypes.c_char_p) for n in _lib._RESTYPE) and set(_lib._RESTYPE) <= set(_lib.SIGNATURES)
+
+
+def test_header_parser_reads_c_prototypes():
+    import ctypes
+    import models
+    _lib = models.vml_amd._lib
+    vp, i, sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t
+    text = """
+    #define SMIN_X 3   // int smin_in_a_line_comment(int a);
+    /* int smin_in_a_block_comment(int a); */
+    int smin_broken(void* stream, const float* const* xs,
+                    int n, /* nullable */ const float* bias,
+                    double scale, int64_t total,
+                    void* ws, size_t ws_bytes /* >= 8 * (n + 1) */);
+    size_t
+    smin_broken_ws_bytes(int n);
+    const char *smin_name(void);
+    static int helper(int a);
+    """
+    sig, ret = _lib._parse_header(text)
+    assert sig == {"smin_broken": [vp, vp, i, vp, ctypes.c_double, ctypes.c_int64, vp, sz], "smin_broken_ws_bytes": [i], "smin_name": []}
+    assert ret == {"smin_broken_ws_bytes": sz, "smin_name": ctypes.c_char_p}
+    for bad in ("int smin_odd(void* stream, unsigned flags);", "int smin_odd(short a);", "int smin_odd(int);"):
+        with pytest.raises(_lib.SminHipError, match="smin_odd"):
+            _lib._parse_header(bad)

@@ -2,6 +2,7 @@
 raises if the library is missing or a tensor is not on a HIP device."""
 import ctypes
 import os
+import re
 import subprocess
 
 import torch
@@ -11,140 +12,47 @@ LIB_PATH = os.path.join(_HERE, "libsmin_hip.so")
 TORCH_LIB_PATH = os.path.join(_HERE, "libsmin_torch.so")        # TORCH_LIBRARY(smin_hip, ...): csrc/torch_binding.cpp
 CSRC = os.path.join(_HERE, "csrc")
 
-_vp, _i, _sz, _f = ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t, ctypes.c_float
-_i64, _d = ctypes.c_int64, ctypes.c_double
+HEADER_PATH = os.path.join(_HERE, os.pardir, "include", "smin_hip.h")  # where csrc/Makefile finds it (-I../../include)
 ABI_VERSION = 2                                                 # include/smin_hip.h SMIN_HIP_ABI_VERSION
 
-# name -> argtypes (restype is int unless listed in _RESTYPE); mirrors include/smin_hip.h one to one
-SIGNATURES = {
-    "smin_abi_version": [],
-    "smin_target_arch": [],
-    "smin_set_gemm_mode": [_i],
-    "smin_get_gemm_mode": [],
-    "smin_prof_enable": [_i],
-    "smin_prof_read": [_vp, _vp, _i],
-    "smin_workspace_bytes": [_i] * 6,
-    "smin_transpose_batch": [_vp] * 5 + [_i],
-    "smin_param_prep_fwd": [_vp, _vp, _i, _i, _i] + [_vp] * 5,
-    "smin_param_prep_bwd": [_vp, _vp, _i, _i, _i] + [_vp] * 9,
-    "smin_sum_lists": [_vp, _vp, _i, _sz, _vp],
-    "smin_col_sum_workspace_bytes": [_i, _i],
-    "smin_col_sum": [_vp, _vp, _i, _i, _vp, _vp, _sz],
-    "smin_proposal_map_fwd": [_vp, _vp, _vp] + [_i] * 6 + [_vp] * 3 + [_vp, _sz],
-    "smin_proposal_map_bwd": [_vp] * 7 + [_i] * 6 + [_vp, _vp, _sz, _vp, _vp],
-    "smin_clip_event_table": [_vp] + [_i] * 3 + [_vp] * 3,
-    "smin_gate_fwd": [_vp] * 4 + [_i] * 2 + [_vp],
-    "smin_gate_fwd_sum": [_vp] * 4 + [_i] * 2 + [_vp] * 3,
-    "smin_gate_bwd": [_vp, _vp, _i, _vp, _i, _vp, _vp, _vp] + [_i] * 4 + [_vp] * 2 + [_vp, _sz] + [_vp] * 3,
-    "smin_content_unit_fwd": [_vp] * 5 + [_i] * 7 + [_vp] * 9 + [_vp, _i] + [_vp] * 4,
-    "smin_content_unit_bwd": [_vp] * 6 + [_i] * 7 + [_vp] * 9 + [_vp] * 10 + [_vp, _sz, _i],
-    "smin_boundary_reduce_fwd": [_vp] * 5 + [_i] * 4 + [_vp],
-    "smin_boundary_reduce_bwd": [_vp] * 6 + [_i] * 4 + [_vp] * 2,
-    "smin_boundary_unit_fwd": [_vp] * 7 + [_i] * 5 + [_vp] * 6 + [_vp] * 7,
-    "smin_boundary_unit_bwd_ws_bytes": [_i] * 4,
-    "smin_boundary_unit_bwd": [_vp] * 8 + [_i] * 5 + [_vp] * 4 + [_vp] * 6 + [_vp] * 8 + [_vp, _sz],
-    "smin_moment_unit_fwd": [_vp] * 5 + [_i] * 4 + [_vp] * 3 + [_vp],
-    "smin_pair_product": [_vp] * 3 + [_i] * 3 + [_vp],
-    "smin_moment_unit_bwd": [_vp] * 7 + [_i] * 4 + [_vp] * 5 + [_vp, _sz, _i, _vp, _vp, _vp],
-    "smin_pair_product_bf16": [_vp] * 3 + [_i] * 3 + [_vp],
-    "smin_moment_unit_fwd_x1h": [_vp] * 5 + [_i] * 4 + [_vp] * 3 + [_vp],
-    "smin_moment_unit_bwd_x1h": [_vp] * 7 + [_i] * 4 + [_vp] * 5 + [_vp, _sz, _i, _vp, _vp, _vp],
-    "smin_score_map_fwd": [_vp] * 4 + [_i] * 4 + [_vp] * 7,
-    "smin_score_map_bwd": [_vp] * 8 + [_i] * 4 + [_vp] * 3 + [_vp] * 6 + [_vp, _sz],
-    "smin_score_tail_ws_bytes": [_i] * 4,
-    "smin_score_tail_fwd": [_vp] * 8 + [_i] * 5 + [_vp] * 11 + [_vp, _sz],
-    "smin_loss_fwd": [_vp] * 14 + [_i] * 2 + [_vp] * 2,
-    "smin_loss_bwd": [_vp] * 16 + [_i] * 2 + [_vp] * 4,
-    "smin_compute_ious": [_vp] * 6 + [_i] * 2 + [_vp] * 2,
-    "smin_top_moments_ws_bytes": [_i] * 3,
-    "smin_top_moments": [_vp] * 5 + [_i] * 3 + [_f] + [_vp] * 4 + [_sz],
-    "smin_merge_window_moments": [_vp] * 7 + [_i] * 6 + [_f] + [_vp] * 5,
-    "smin_compute_ious_nms_ws_bytes": [_i] * 5,
-    "smin_compute_ious_nms": [_vp] * 6 + [_i] * 3 + [_f, _vp, _i, _vp, _i] + [_vp, _vp, _sz],
-    "smin_epoch_meter_ws_bytes": [_i] * 6,
-    "smin_epoch_meter_update": [_vp] * 6 + [_i] * 4 + [_f, _vp, _i, _vp, _i] + [_vp, _vp, _vp, _sz],
-    "smin_span_ious": [_vp] * 4 + [_i] * 2 + [_vp],
-    "smin_span_meter_ws_bytes": [_i] * 3,
-    "smin_span_meter_update": [_vp] * 4 + [_i] * 2 + [_vp, _i, _vp, _i] + [_vp, _vp, _sz],
-    "smin_build_targets": [_vp] * 5 + [_i] * 4 + [_vp] * 12,
-    "smin_sample_clips": [_vp] * 4 + [_i] * 4 + [_vp] * 2,
-    "smin_embed_tokens": [_vp] * 3 + [_i] * 5 + [_vp] * 3,
-    "smin_sample_clips_bwd": [_vp] * 4 + [_i] * 4 + [ctypes.c_int64, _vp],
-    "smin_sample_windows": [_vp] * 4 + [_i] * 4 + [_vp] * 2,
-    "smin_embed_tokens_bwd_workspace_bytes": [_i, _i],
-    "smin_embed_tokens_bwd": [_vp] * 3 + [_i] * 4 + [_vp, _vp, _sz],
-    "smin_embed_tokens_bwd_rows_workspace_bytes": [_i, _i],
-    "smin_embed_tokens_bwd_rows": [_vp] * 3 + [_i] * 4 + [_vp] * 4 + [_vp, _sz],
-    "smin_word_prep_fwd": [_vp] * 5 + [_i] * 5 + [_vp] * 5,
-    "smin_word_prep_bwd_workspace_bytes": [_i] * 5,
-    "smin_word_prep_bwd": [_vp] * 11 + [_i] * 5 + [_vp] * 3 + [_vp, _sz],
-    "smin_build_cells": [_vp, _vp, _i, _i, _i, _vp, _vp, _vp],
-    "smin_build_cells_n": [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp],
-    "smin_pack_cells": [_vp, _vp, _vp, _i, _i, _i, _vp],
-    "smin_unpack_cells": [_vp, _vp, _vp, _i, _i, _i, _vp],
-    "smin_gemm_nt": [_vp] * 4 + [_i] * 3,
-    "smin_gemm_nt_acc": [_vp] * 4 + [_i] * 3,
-    "smin_clip_window_means_fwd": [_vp] * 3 + [_i, _vp] + [_i] * 7 + [_vp, _vp, _sz],
-    "smin_clip_window_means_bwd": [_vp] * 5 + [_i] * 7 + [_vp, _vp, _sz, _vp, _vp],
-    "smin_content_attn_fwd": [_vp] * 4 + [_i] * 6 + [_vp] * 7,
-    "smin_content_attn_fwd_cch": [_vp] * 4 + [_i] * 6 + [_vp] * 7,
-    "smin_content_attn_fwd_probs": [_vp] * 4 + [_i] * 6 + [_vp] * 6 + [_i, _vp, _vp],
-    "smin_content_attn_maps_dense": [_vp] * 4 + [_i] * 5 + [_vp] * 3,
-    "smin_attn_maps_gather": [_vp] * 3 + [_i] + [_vp] * 2 + [_i] * 5 + [_vp] * 2,
-    "smin_content_attn_bwd_workspace_bytes": [_i] * 4,
-    "smin_content_attn_bwd": [_vp] * 6 + [_i] * 6 + [_vp] * 10 + [_vp, _sz],
-    "smin_linear_rows_fwd": [_vp, _vp, _i] + [_vp] * 4 + [_i] * 4 + [_vp],
-    "smin_linear_rows_fwd_xh": [_vp, _vp, _i] + [_vp] * 4 + [_i] * 4 + [_vp],
-    "smin_linear_rows_bwd_xh": [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _sz],
-    "smin_linear_rows_bwd_workspace_bytes": [_i] * 3,
-    "smin_linear_rows_bwd": [_vp, _vp, _vp, _i, _vp] + [_i] * 3 + [_vp] * 3 + [_vp, _sz],
-    "smin_linear_rows_dx_acc": [_vp, _vp, _i, _vp] + [_i] * 3 + [_vp],
-    "smin_group_sum": [_vp, _vp, _i, _i, _i, _vp],
-    "smin_video_encoder_fwd": [_vp] * 7 + [_i] * 4 + [_vp] * 2,
-    "smin_video_encoder_gate": [_vp] * 3 + [_i] * 3 + [_vp],
-    "smin_video_encoder_bwd_workspace_bytes": [_i] * 4,
-    "smin_video_encoder_bwd": [_vp] * 6 + [_i] * 4 + [_vp] * 4 + [_vp, _sz],
-    "smin_video_encoder_bwd_input": [_vp] * 3 + [_i] * 4 + [_vp, _vp, _sz],
-    "smin_bilstm_layer_fwd": [_vp] * 6 + [_i] * 4 + [_vp] * 3,
-    "smin_lstm_pack": [_vp, _vp, _i, _i] + [_vp] * 4,
-    "smin_lstm_pack_layers": [_vp, _i, _vp, _vp, _i] + [_vp] * 4,
-    "smin_lstm_cluster_error": [],
-    "smin_sentence_feature_fwd": [_vp, _vp, _vp, _i, _i, _i, _vp],
-    "smin_sentence_feature_bwd": [_vp, _vp, _vp, _i, _i, _i, _vp],
-    "smin_bilstm_layer_bwd_workspace_bytes": [_i] * 4,
-    "smin_bilstm_layer_bwd": [_vp] * 9 + [_i] * 4 + [_vp] * 4 + [_vp, _sz],
-    "smin_step_prologue": [_vp] * 7 + [_i] * 5 + [_vp] * 8,
-    "smin_bilstm_layer_bwd_weights": [_vp, _i, _vp, _vp] + [_i] * 4 + [_vp] * 4 + [_vp, _sz],
-    "smin_adam_ws_bytes": [_i64, _i],
-    "smin_grad_norm": [_vp, _vp, _vp, _i, _d, _vp, _vp, _sz],
-    "smin_adam_step": [_vp] * 5 + [_i] + [_vp] * 3 + [_d] * 4 + [_i, _i, _vp],
-    "smin_row_adam_step": [_vp] * 8 + [_i] * 3 + [_vp] * 2 + [_d] * 3 + [_i],
-    "smin_row_lists_merge_workspace_bytes": [_i, _i],
-    "smin_row_lists_merge": [_vp] * 5 + [_i] * 3 + [_vp] * 5 + [_vp, _sz],
-    "smin_pair_assemble": [_vp] * 6 + [_i] * 6 + [_vp] * 3,
-    "smin_pair_assemble_bwd_workspace_bytes": [_i] * 3,
-    "smin_pair_assemble_bwd": [_vp] * 12 + [_i] * 6 + [_vp] * 3 + [_vp, _sz],
-    "smin_corpus_topk": [_vp] * 6 + [_i] * 3 + [_vp] * 4,
-    "smin_search_merge": [_vp, _i] + [_vp] * 6 + [_i] * 2 + [_vp] * 4,
-    "smin_corpus_meter_ws_bytes": [_i] * 3,
-    "smin_corpus_meter_update": [_vp] * 6 + [_i] * 2 + [_vp, _i, _vp, _i] + [_vp, _vp, _sz],
-}
-_RESTYPE = {"smin_target_arch": ctypes.c_char_p, "smin_workspace_bytes": _sz,
-            "smin_content_attn_bwd_workspace_bytes": _sz, "smin_linear_rows_bwd_workspace_bytes": _sz,
-            "smin_bilstm_layer_bwd_workspace_bytes": _sz, "smin_video_encoder_bwd_workspace_bytes": _sz, "smin_embed_tokens_bwd_workspace_bytes": _sz,
-            "smin_embed_tokens_bwd_rows_workspace_bytes": _sz,
-            "smin_word_prep_bwd_workspace_bytes": _sz, "smin_score_tail_ws_bytes": _sz,
-            "smin_col_sum_workspace_bytes": _sz, "smin_top_moments_ws_bytes": _sz, "smin_boundary_unit_bwd_ws_bytes": _sz, "smin_compute_ious_nms_ws_bytes": _sz,
-            "smin_epoch_meter_ws_bytes": _sz, "smin_span_meter_ws_bytes": _sz, "smin_adam_ws_bytes": _sz,
-            "smin_row_lists_merge_workspace_bytes": _sz, "smin_corpus_meter_ws_bytes": _sz,
-            "smin_pair_assemble_bwd_workspace_bytes": _sz}
-
-_lib = None
-_ws = {}
+_SCALARS = {"int": ctypes.c_int, "size_t": ctypes.c_size_t, "float": ctypes.c_float, "double": ctypes.c_double, "int64_t": ctypes.c_int64}
 
 
 class SminHipError(RuntimeError):
     pass
+
+
+def _parse_header(text):
+    """({name: argtypes}, {name: restype, where it is not int}) of every `int | size_t | const char* smin_*(...);` prototype of a
+    C header: any pointer is a c_void_p, the scalars are _SCALARS, (void) is no argument."""
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    text = re.sub(r"//[^\n]*", " ", text)
+    signatures, restypes = {}, {}
+    for ret, name, args in re.findall(r"\b(int|size_t|const\s+char\s*\*)(?:(?<=\*)|\s)\s*(smin_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", text):
+        row = []
+        for arg in ([] if args.strip() in ("", "void") else args.split(",")):
+            ty = " ".join(re.sub(r"\bconst\b", " ", arg).split()[:-1])     # the last word is the argument's name
+            if "*" not in arg and ty not in _SCALARS:
+                raise SminHipError(f"{name}: no ctypes type for the argument `{' '.join(arg.split())}`")
+            row.append(ctypes.c_void_p if "*" in arg else _SCALARS[ty])
+        signatures[name] = row
+        if ret != "int":
+            restypes[name] = ctypes.c_size_t if ret == "size_t" else ctypes.c_char_p
+    return signatures, restypes
+
+
+def _header_table():
+    if not os.path.exists(HEADER_PATH):
+        raise SminHipError(f"{HEADER_PATH} is missing: the ctypes table is read from the C header")
+    with open(HEADER_PATH) as f:
+        return _parse_header(f.read())
+
+
+# name -> argtypes (restype is int unless listed in _RESTYPE): include/smin_hip.h, read at import
+SIGNATURES, _RESTYPE = _header_table()
+
+_lib = None
+_ws = {}
 
 
 def build(verbose=False):
@@ -170,7 +78,7 @@ def load():
     for name, args in SIGNATURES.items():
         fn = getattr(lib, name)          # AttributeError here == header/library mismatch
         fn.argtypes = args
-        fn.restype = _RESTYPE.get(name, _i)
+        fn.restype = _RESTYPE.get(name, ctypes.c_int)
     if lib.smin_abi_version() != ABI_VERSION:
         raise SminHipError("libsmin_hip.so ABI version mismatch")
     _lib = lib

@@ -5,7 +5,8 @@
 // (reference models.py:367) plus the module's parameters, shape and switches (by name) and runs the whole model as ONE autograd node
 // (SminCore) around the HIP entry points, so the backward pass runs on the autograd engine's thread without the interpreter
 // (DistributedDataParallel hooks fire as usual); smin_hip::smin_score is the same forward without a node, for callers that only rank
-// (SMIN.score).  The Python host (video-moment-localization_amd/functional.py, modules.py) binds the
+// (SMIN.score).  smin_forward_pairs and smin_score_pairs are the same two over indexed pairs of videos and queries: every run is
+// described by one CoreCall value, and SminCore is the only node (the pair lists travel in the call).  The Python host (video-moment-localization_amd/functional.py, modules.py) binds the
 // same C ABI with ctypes, a node per module; it serves the stand-alone sub-module seams and every in-model call that SMIN._plan does not
 // send here (SMIN.fused_core = False, inputs that require grad without input_grads, configurations outside the node's limits).
 // torch types appear only in this file; libsmin_hip.so knows pointers and sizes.
@@ -47,6 +48,7 @@ inline const float* fp(const Tensor& t) { return t.defined() ? t.const_data_ptr<
 inline float* fpm(const Tensor& t) { return t.defined() ? t.data_ptr<float>() : nullptr; }
 inline const uint16_t* hp16(const Tensor& t) { return reinterpret_cast<const uint16_t*>(t.const_data_ptr()); }     // bf16 tensors as bit patterns
 inline const int32_t* ip(const Tensor& t) { return t.const_data_ptr<int32_t>(); }
+inline const uint8_t* u8(const Tensor& t) { return static_cast<const uint8_t*>(t.const_data_ptr()); }             // one-byte masks
 inline void* cur() { return (void*)c10::hip::getCurrentHIPStream().stream(); }
 inline Tensor cont(const Tensor& t) { return t.defined() ? t.contiguous() : t; }
 inline Tensor fl(const Tensor& t) { return t.scalar_type() == at::kFloat ? t : t.to(at::kFloat); }
@@ -74,7 +76,7 @@ struct Cache {
 };
 
 // Events for stream joins: a ring per device (an event is bound to the device it was created on), created under that device's
-// guard.  A draw is consumed (recorded and waited for by hipStreamWaitEvent, or synchronised by the host) within the call that
+// guard.  A draw is consumed (marked and awaited by a stream, or waited for by the host) within the call that
 // drew it; the ring is far longer than the draws of one forward + backward pass (~60 at three layers), so no event is
 // re-recorded while a wait on its previous record is still being enqueued.
 hipEvent_t next_event()
@@ -91,13 +93,20 @@ hipEvent_t next_event()
     }
     return ring.first[ring.second++ % RING];
 }
+// The two verbs of every hand-off between streams (the rules that make them safe: DESIGN.md 6, "Stream rules"):
+// mark: an event behind everything queued on `on` so far; await: `waiter` runs nothing further until `e` has happened
+hipEvent_t mark(HStream on)
+{
+    hipEvent_t e = next_event();
+    TORCH_CHECK(hipEventRecord(e, on.stream()) == hipSuccess, "hipEventRecord failed");
+    return e;
+}
+void await(HStream waiter, hipEvent_t e) { TORCH_CHECK(hipStreamWaitEvent(waiter.stream(), e, 0) == hipSuccess, "hipStreamWaitEvent failed"); }
+void host_wait(hipEvent_t e) { TORCH_CHECK(hipEventSynchronize(e) == hipSuccess, "hipEventSynchronize failed"); }
 // `waiter` waits for everything queued on `on` so far (stream.wait_stream)
 void wait_stream(HStream waiter, HStream on)
 {
-    if (waiter == on) return;
-    hipEvent_t e = next_event();
-    TORCH_CHECK(hipEventRecord(e, on.stream()) == hipSuccess, "hipEventRecord failed");
-    TORCH_CHECK(hipStreamWaitEvent(waiter.stream(), e, 0) == hipSuccess, "hipStreamWaitEvent failed");
+    if (waiter != on) await(waiter, mark(on));
 }
 HStream side_stream(c10::DeviceIndex dev, int which = 0)
 {
@@ -230,7 +239,24 @@ struct GradSync {
 enum { P_VE_W = 0, P_VE_B, P_PE, P_LSTM = 3, P_LAYER0 = 19 };
 enum { L_CH_W = 0, L_CH_B, L_WH_W, L_WH_B, L_SH_W, L_SH_B, L_C_W, L_C_B, L_AQ_W, L_AQ_B, L_AK_W, L_AK_B, L_BQ_W, L_BQ_B, L_BK_W, L_BK_B, L_FB_W, L_FB_B, L_FC_W,
        L_FC_B, L_COUNT };
-
+// a layer's parameters that meet in the parameter products (csrc/param_prep.hip), and its word-side ones (csrc/word_prep.hip)
+constexpr int L_PRODUCTS[] = {L_CH_W, L_CH_B, L_C_W, L_C_B, L_FB_W, L_FB_B, L_FC_W, L_FC_B}, L_WORD_SIDE[] = {L_WH_W, L_WH_B, L_SH_W, L_SH_B, L_AK_W, L_AK_B, L_AQ_W, L_AQ_B};
+// The contiguous parameters of a run, or their gradients (ParamList(nl): undefined until formed), under one index arithmetic.
+struct ParamList {
+    std::vector<Tensor> all;
+    int64_t nl = 0;
+    static int64_t expected(int64_t nl) { return P_LAYER0 + nl * L_COUNT + 8; }
+    ParamList() = default;
+    explicit ParamList(int64_t nl) : all(expected(nl)), nl(nl) {}
+    ParamList(std::vector<Tensor> ts, int64_t nl) : all(std::move(ts)), nl(nl) {}
+    ParamList(at::TensorList ts, size_t count, int64_t nl) : nl(nl) { for (size_t i = 0; i < count; ++i) all.push_back(cont(ts[i])); }
+    const Tensor& backbone(int which) const { return all[which]; }                       // P_VE_W .. P_LSTM + 15
+    Tensor& backbone(int which) { return all[which]; }
+    const Tensor& layer(int64_t k, int which) const { return all[P_LAYER0 + k * L_COUNT + which]; }
+    Tensor& layer(int64_t k, int which) { return all[P_LAYER0 + k * L_COUNT + which]; }
+    const Tensor& loc(int i) const { return all[P_LAYER0 + nl * L_COUNT + i]; }           // the localization head's 8
+    Tensor& loc(int i) { return all[P_LAYER0 + nl * L_COUNT + i]; }
+};
 
 // restated loss of the reference's train loop (main.py:89-116): one forward and one backward kernel
 struct LossNode : torch::autograd::Function<LossNode> {
@@ -243,7 +269,6 @@ struct LossNode : torch::autograd::Function<LossNode> {
         ym = b(ym); mm = b(mm); ys = b(ys); ye = b(ye); ya = b(ya); lm = b(lm);
         const int B = i32(ps.size(0)), L = i32(ps.size(1));
         Tensor loss = at::empty({1}, pm.options()), part = at::empty({B, 6}, pm.options());
-        auto u8 = [](const Tensor& t) { return static_cast<const uint8_t*>(t.const_data_ptr()); };
         SMIN_CK(smin_loss_fwd(cur(), fp(pm), u8(ym), fp(sm), u8(mm), fp(ps), u8(ys), fp(ss), fp(pe), u8(ye), fp(se), fp(pa), u8(ya), u8(lm), B, L, fpm(loss), fpm(part)));
         ctx->save_for_backward({pm, ps, pe, pa, ym, sm, mm, ys, ss, ye, se, ya, lm, part});
         return loss.reshape({});
@@ -258,7 +283,6 @@ struct LossNode : torch::autograd::Function<LossNode> {
         // the three score gradients are rows of one buffer: the model's node takes them as they are (no gather)
         Tensor dpm = at::empty_like(pm), d3 = at::empty({3, (int64_t)B, (int64_t)L}, ps.options());
         Tensor dps = d3[0], dpe = d3[1], dpa = d3[2];
-        auto u8 = [](const Tensor& t) { return static_cast<const uint8_t*>(t.const_data_ptr()); };
         SMIN_CK(smin_loss_bwd(cur(), fp(dloss), fp(part), fp(pm), u8(ym), fp(sm), u8(mm), fp(ps), u8(ys), fp(ss), fp(pe), u8(ye), fp(se), fp(pa), u8(ya), u8(lm), B, L,
                               fpm(dpm), fpm(dps), fpm(dpe), fpm(dpa)));
         variable_list out{dpm, dps, dpe, dpa};
@@ -281,7 +305,10 @@ struct LayerState {
 struct LstmState { Tensor x, Hout, G, Cs, Wih, Whh; };
 struct CoreState {
     Tensor vx, fv, vmaskf, len32, last, f, fw, fs, qmf, lmf, cells, row_ptr, cellmap, Wch_all, what, kb, Mq, uq, shat, pm, psea, fm_out, wb;
-    Tensor tailv;                                              // smin_score only: the tail's vectors (not among the saved tensors)
+    // not among the saved tensors: the tail's vectors (smin_score only), the parameters (saved behind them), the attention maps (outputs)
+    Tensor tailv;
+    ParamList prm;
+    std::vector<Tensor> cmaps, bmaps;
     // smin_forward_pairs only (undefined otherwise): the query bank's sentence features, the pair lists and their CSR groupings.  There
     // fv, vx, vmaskf have a row per video, len32 and the LSTM state a row per query, everything else a row per pair.
     Tensor fs_bank, vi, qi, v_ptr, v_pairs, q_ptr, q_pairs;
@@ -347,9 +374,73 @@ struct PairBank {
     Tensor vmask_v, qmask_q, v_ptr, v_pairs, q_ptr, q_pairs;
 };
 
+// The boolean options of the operators (their keyword arguments, named as the SMIN attributes) as one word.
+// F_KEEP_ATTENTION: every layer's word-attention maps leave as extra outputs (not differentiable; the backward ignores them):
+// the content maps dense (B, L, L, C, Nq), or with F_ATTN_PACKED as packed rows [N*C][Nq] followed by the cellmap; the boundary maps (B, L, Nq)
+// F_INPUT_GRADS: video_features / query_features may require grad; the backward then returns their gradients in slots 0 and 1
+// (each formed only when autograd asks for it)
+enum { F_OVERLAP_BOUNDARY = 1, F_OVERLAP_PREP = 2, F_ASYNC_WEIGHTS = 4, F_BF16_OPERANDS = 8, F_GRAD_SYNC = 16, F_TAIL_SPLIT = 32, F_KEEP_ATTENTION = 64,
+       F_ATTN_PACKED = 128, F_INPUT_GRADS = 256, F_PARAM_PREP_KERNEL = 512 };
+int64_t flag_word(bool overlap_boundary, bool overlap_prep, bool param_prep_kernel, bool bf16_operand_storage, bool async_weights = false, bool tail_split = false,
+                  bool grad_sync = false, bool input_grads = false, bool keep_attention = false, bool attn_packed = false)
+{
+    return (overlap_boundary ? F_OVERLAP_BOUNDARY : 0) | (overlap_prep ? F_OVERLAP_PREP : 0) | (param_prep_kernel ? F_PARAM_PREP_KERNEL : 0) |
+           (bf16_operand_storage ? F_BF16_OPERANDS : 0) | (async_weights ? F_ASYNC_WEIGHTS : 0) | (tail_split ? F_TAIL_SPLIT : 0) | (grad_sync ? F_GRAD_SYNC : 0) |
+           (input_grads ? F_INPUT_GRADS : 0) | (keep_attention ? F_KEEP_ATTENTION : 0) | (attn_packed ? F_ATTN_PACKED : 0);
+}
+
+// What a run of the core is given, beside video_features, query_features and the parameter list: one value from the operator to
+// SminCore::run, through SminCore::apply as a single argument.
+struct CoreCall {
+    Tensor video_mask, query_mask, length_mask, moment_mask;    // a row per sample; with a bank: per pair (gathered by run_call)
+    int64_t T = 0, L = 0, C = 0, nl = 0, maxq = 0, H = 0;
+    int64_t flags = 0;
+    int64_t n_known = -1;                                       // the number of valid cells of moment_mask when the caller knows it, else -1
+    bool scoring = false;                                       // true: forward only (smin_score, smin_score_pairs)
+    std::optional<PairBank> bank;
+};
+
+// the shape a backward needs beside the saved tensors: every field under its name in ctx->saved_data
+struct SavedShape {
+    int64_t N, T, L, C, nl, flags, H, Nq_in;
+    template <class Self, class F> static void each(Self& s, F fn)
+    {
+        fn("N", s.N); fn("T", s.T); fn("L", s.L); fn("C", s.C); fn("nl", s.nl); fn("flags", s.flags); fn("H", s.H); fn("Nq_in", s.Nq_in);
+    }
+    void put(AutogradContext* ctx) const { each(*this, [&](const char* key, int64_t v) { ctx->saved_data[key] = v; }); }
+    static SavedShape get(AutogradContext* ctx)
+    {
+        SavedShape s;
+        each(s, [&](const char* key, int64_t& v) { v = ctx->saved_data[key].toInt(); });
+        return s;
+    }
+};
+
+// What both passes derive from a tensor of the batch, the parameters, the shape and the flags
+struct Dims {
+    at::Device dev;
+    at::TensorOptions opt;
+    int B, D, Nq, dl, Li, Ci, Ti;
+    HStream curs, side;                                         // the caller's stream; the boundary unit's (F_OVERLAP_BOUNDARY, else the caller's)
+    Dims(const Tensor& like, int64_t batch, const ParamList& P, int64_t T, int64_t L, int64_t C, int64_t maxq, int64_t flags)
+        : dev(like.device()), opt(like.options()), B(i32(batch)), D(i32(P.backbone(P_VE_W).size(0))), Nq(i32(maxq)), dl(i32(P.layer(0, L_CH_W).size(0))), Li(i32(L)),
+          Ci(i32(C)), Ti(i32(T)), curs(c10::hip::getCurrentHIPStream(dev.index())), side((flags & F_OVERLAP_BOUNDARY) ? side_stream(dev.index()) : curs) {}
+};
+
+// What smin_encode_queries / smin_encode_videos and a training run over pairs (SminCore::run) both do: the lengths of a (Q, words) mask;
+// a (V * T) video mask as fp32 (returned) and the video encoder's projection f_v (models.py:25-36) of the V videos into `fv`
+Tensor query_lengths(const Tensor& query_mask) { return query_mask.ne(0).sum(1).to(at::kInt).contiguous(); }
+Tensor project_videos(const ParamList& P, const Tensor& vx, const Tensor& video_mask, const Tensor& fv)
+{
+    Tensor vmaskf = cont(video_mask.is_floating_point() ? fl(video_mask) : video_mask.ne(0).to(at::kFloat));
+    SMIN_CK(smin_video_encoder_fwd(cur(), fp(vx), fp(P.backbone(P_VE_W)), fp(P.backbone(P_VE_B)), fp(P.backbone(P_PE)), fp(vmaskf), nullptr, i32(vx.size(0)), i32(vx.size(1)),
+                                   i32(vx.size(2)), i32(fv.size(2)), fpm(fv), nullptr));
+    return vmaskf;
+}
+
 // The query encoder (models.py:38-62): both BiLSTM layers' operand layouts in one launch, the two recurrences, f_w padded to
 // max_query_length and the sentence feature f_s.  The layers' tensors that a backward reads stay in `lstm` (scoring: dropped).
-std::pair<Tensor, Tensor> query_encoder(LstmState (&lstm)[2], const std::vector<Tensor>& all, const Tensor& query_features, const Tensor& len32, int64_t maxq,
+std::pair<Tensor, Tensor> query_encoder(LstmState (&lstm)[2], const ParamList& P, const Tensor& query_features, const Tensor& len32, int64_t maxq,
                                         int64_t H, bool scoring)
 {
     const auto opt = query_features.options();
@@ -367,7 +458,7 @@ std::pair<Tensor, Tensor> query_encoder(LstmState (&lstm)[2], const std::vector<
             lstm_bias[layer] = at::empty({8 * H}, opt);                        // b_ih + b_hh per direction
             ls.Whh = at::empty({2, 4 * H, H}, opt);
             lstm_W4[layer] = at::empty({2, H, H, 4}, opt);                     // [d, k, u, gate]
-            for (int q = 0; q < 8; ++q) raw[8 * layer + q] = fp(all[P_LSTM + 8 * layer + q]);
+            for (int q = 0; q < 8; ++q) raw[8 * layer + q] = fp(P.backbone(P_LSTM + 8 * layer + q));
             ins[layer] = i32(In); wih[layer] = fpm(ls.Wih); bs[layer] = fpm(lstm_bias[layer]); whh[layer] = fpm(ls.Whh); w4[layer] = fpm(lstm_W4[layer]);
         }
         SMIN_CK(smin_lstm_pack_layers(cur(), 2, raw, ins, i32(H), wih, bs, whh, w4));
@@ -392,48 +483,31 @@ std::pair<Tensor, Tensor> query_encoder(LstmState (&lstm)[2], const std::vector<
 }
 
 struct SminCore : torch::autograd::Function<SminCore> {
-    // The boolean options of smin_forward (the op's keyword arguments, named as the SMIN attributes), built in smin_forward only.
-    // F_KEEP_ATTENTION: every layer's word-attention maps leave as extra outputs (not differentiable; the backward ignores them):
-    // the content maps dense (B, L, L, C, Nq), or with F_ATTN_PACKED as packed rows [N*C][Nq] followed by the cellmap; the boundary maps (B, L, Nq)
-    enum { F_OVERLAP_BOUNDARY = 1, F_OVERLAP_PREP = 2, F_ASYNC_WEIGHTS = 4, F_BF16_OPERANDS = 8, F_GRAD_SYNC = 16, F_TAIL_SPLIT = 32, F_KEEP_ATTENTION = 64,
-           F_ATTN_PACKED = 128, F_INPUT_GRADS = 256, F_PARAM_PREP_KERNEL = 512 };
-    // F_INPUT_GRADS: video_features / query_features may require grad; the backward then returns their gradients in slots 0 and 2
-    // (each formed only when autograd asks for it)
-    enum { N_FIXED = 14 };          // forward arguments ahead of the parameter list (tensors and scalars alike take one gradient slot)
+    enum { N_FIXED = 3 };           // forward arguments ahead of the parameter list: video_features, query_features, the call (one gradient slot each)
 
     // The forward pass as a sequence of launches, for the node's forward (scoring = false: every tensor the backward reads stays in `st`)
     // and for smin_score (scoring = true: forward only -- a layer's tensors are dropped once their last reader is queued, and the last
     // layer ends in smin_score_tail_fwd instead of its content-stream sum, pair product, moment unit and smin_score_map_fwd).
-    // Fills st.pm / st.psea, the contiguous parameters `all` and the attention maps; returns the number of cells.
-    // n_known: the number of valid cells of moment_mask when the caller knows it, else -1
-    // bank: the backbone's outputs of the pairs come from banks through smin_pair_assemble and the four masks are the pairs' (gathered
-    // by the caller).  Scoring: the banks are given and video_features / query_features are unused.  Training (bank->train): the two
+    // Fills st.pm / st.psea, the contiguous parameters st.prm and the attention maps; returns the number of cells.
+    // call.bank: the backbone's outputs of the pairs come from banks through smin_pair_assemble and the four masks are the pairs'.
+    // Scoring: the banks are given and video_features / query_features are unused.  Training (bank->train): the two
     // encoders run here, once per row of video_features (V, T, Din) and of query_features (Q, words, E), and their state is kept.
-    static int64_t run(CoreState& st, std::vector<Tensor>& all, std::vector<Tensor>& cmaps, std::vector<Tensor>& bmaps, bool scoring, const Tensor& video_features,
-                       const Tensor& video_mask, const Tensor& query_features, const Tensor& query_mask, const Tensor& length_mask, const Tensor& moment_mask, int64_t T,
-                       int64_t L, int64_t C, int64_t nl, int64_t maxq, int64_t H, int64_t flags, int64_t n_known, at::TensorList prm_in, const PairBank* bank = nullptr)
+    static int64_t run(CoreState& st, const CoreCall& call, const Tensor& video_features, const Tensor& query_features, at::TensorList prm_in)
     {
+        const auto& [video_mask, query_mask, length_mask, moment_mask, T, L, C, nl, maxq, H, flags, n_known, scoring, given_bank] = call;
+        const PairBank* bank = given_bank ? &*given_bank : nullptr;
         TORCH_CHECK(!bank || scoring != bank->train, "given banks are scored; a training run encodes its own");
         const bool own_bank = bank && bank->train;
-        for (const Tensor& p : prm_in) all.push_back(cont(p));
-        std::vector<Tensor> prm(all.begin() + P_LAYER0, all.end());                // the SMI layers' and the localization head's parameters
+        const ParamList& P = st.prm = ParamList(prm_in, prm_in.size(), nl);
         const Tensor& like = bank && !own_bank ? bank->fv : video_features;
-        const at::Device dev = like.device();
-        const auto opt = like.options();
         const int64_t Bq = bank ? bank->vi.size(0) : video_features.size(0), Tn = like.size(1);
         TORCH_CHECK(Tn == T, "ProposalGeneration was built for T=", T, " but got ", Tn, " frames");
-        const int B = i32(Bq), D = i32(all[P_VE_W].size(0)), Nq = i32(maxq), dl = i32(prm[L_CH_W].size(0)), Li = i32(L), Ci = i32(C), Ti = i32(T);
-        auto lp = [&](int64_t k, int which) -> const Tensor& { return prm[k * L_COUNT + which]; };
-        const Tensor* loc = &prm[nl * L_COUNT];
-        HStream curs = c10::hip::getCurrentHIPStream(dev.index());
-        HStream side = (flags & F_OVERLAP_BOUNDARY) ? side_stream(dev.index()) : curs;
+        const auto [dev, opt, B, D, Nq, dl, Li, Ci, Ti, curs, side] = Dims(like, Bq, P, T, L, C, maxq, flags);
         HStream prep = (flags & F_OVERLAP_PREP) ? side : curs;
         size_state(st, nl);
 
         // ---- parameter-only work (weight products, constants, concatenations: ~25 tiny launches) on the second stream from the first
         // moment of the step, beside the LSTM recurrence that opens the critical path; the main stream waits for it before the proposal map
-        auto mark = [](HStream on) { hipEvent_t e = next_event(); TORCH_CHECK(hipEventRecord(e, on.stream()) == hipSuccess, "hipEventRecord failed"); return e; };
-        auto await = [](HStream waiter, hipEvent_t e) { TORCH_CHECK(hipStreamWaitEvent(waiter.stream(), e, 0) == hipSuccess, "hipStreamWaitEvent failed"); };
         std::vector<Tensor> bcat(nl);
         Tensor bb;
         hipEvent_t products_ready;
@@ -447,7 +521,7 @@ struct SminCore : torch::autograd::Function<SminCore> {
                 std::vector<const float*> pp;
                 std::vector<float*> pc(nl * 2, nullptr);
                 for (int64_t k = 0; k < nl; ++k) {
-                    for (int which : {L_CH_W, L_CH_B, L_C_W, L_C_B, L_FB_W, L_FB_B, L_FC_W, L_FC_B}) pp.push_back(fp(lp(k, which)));
+                    for (int which : L_PRODUCTS) pp.push_back(fp(P.layer(k, which)));
                     LayerState& ls = st.layer[k];
                     for (int64_t lo = 0; lo < k; lo += 4) {
                         ls.Pcat[lo / 4] = at::empty({dl, std::min<int64_t>(4, k - lo) * dl}, opt);
@@ -461,16 +535,16 @@ struct SminCore : torch::autograd::Function<SminCore> {
                 std::vector<Tensor> wch;
                 for (int64_t k = 0; k < nl; ++k) {
                     LayerState& ls = st.layer[k];
-                    ls.consts = bsum.defined() ? lp(k, L_CH_B) + at::mv(lp(k, L_CH_W), bsum) : lp(k, L_CH_B);
-                    bsum = bsum.defined() ? bsum + lp(k, L_C_B) : lp(k, L_C_B);
-                    wch.push_back(lp(k, L_CH_W));
+                    ls.consts = bsum.defined() ? P.layer(k, L_CH_B) + at::mv(P.layer(k, L_CH_W), bsum) : P.layer(k, L_CH_B);
+                    bsum = bsum.defined() ? bsum + P.layer(k, L_C_B) : P.layer(k, L_C_B);
+                    wch.push_back(P.layer(k, L_CH_W));
                     for (int64_t lo = 0; lo < k; lo += 4) {
                         std::vector<Tensor> parts;
-                        for (int64_t l = lo; l < std::min(lo + 4, k); ++l) parts.push_back(at::matmul(lp(k, L_CH_W), lp(l, L_C_W)));
+                        for (int64_t l = lo; l < std::min(lo + 4, k); ++l) parts.push_back(at::matmul(P.layer(k, L_CH_W), P.layer(l, L_C_W)));
                         ls.Pcat[lo / 4] = parts.size() == 1 ? parts[0] : at::cat(parts, 1);
                     }
-                    ls.Wcat = at::cat({lp(k, L_FB_W).view({D, D}), lp(k, L_FC_W).view({D, D})}, 1);
-                    bcat[k] = lp(k, L_FB_B) + lp(k, L_FC_B);
+                    ls.Wcat = at::cat({P.layer(k, L_FB_W).view({D, D}), P.layer(k, L_FC_W).view({D, D})}, 1);
+                    bcat[k] = P.layer(k, L_FB_B) + P.layer(k, L_FC_B);
                 }
                 st.Wch_all = nl == 1 ? wch[0] : at::cat(wch);
             }
@@ -478,8 +552,8 @@ struct SminCore : torch::autograd::Function<SminCore> {
                 // the forward-only tail's vectors (csrc/score_tail.hip): parameters only, so here, beside the LSTM, not in front of the tail
                 const int64_t k = nl - 1;
                 st.tailv = at::empty({(int64_t)smin_score_tail_ws_bytes(B, Li, D, dl)}, opt.dtype(at::kByte));
-                SMIN_CK(smin_score_tail_fwd(cur(), nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, B, Li, D, dl, fp(lp(k, L_C_W)), fp(lp(k, L_C_B)),
-                                            fp(st.layer[k].Wcat), fp(bcat[k]), fp(loc[0]), fp(loc[1]), nullptr, nullptr, nullptr, nullptr, nullptr, st.tailv.data_ptr(),
+                SMIN_CK(smin_score_tail_fwd(cur(), nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, B, Li, D, dl, fp(P.layer(k, L_C_W)), fp(P.layer(k, L_C_B)),
+                                            fp(st.layer[k].Wcat), fp(bcat[k]), fp(P.loc(0)), fp(P.loc(1)), nullptr, nullptr, nullptr, nullptr, nullptr, st.tailv.data_ptr(),
                                             (size_t)st.tailv.numel()));
             }
             products_ready = mark(prep);
@@ -496,9 +570,8 @@ struct SminCore : torch::autograd::Function<SminCore> {
             st.len32 = at::empty({Bq}, opt.dtype(at::kInt));
             qmf = at::empty({Bq, maxq}, opt); lmf = at::empty({Bq, L}, opt); st.vmaskf = at::empty({Bq * Tn}, opt);
             Tensor count = at::empty({1}, opt.dtype(at::kLong));
-            const float* w3[3] = {fp(loc[2]), fp(loc[4]), fp(loc[6])};
-            const float* b3[3] = {fp(loc[3]), fp(loc[5]), fp(loc[7])};
-            auto u8 = [](const Tensor& t) { return static_cast<const uint8_t*>(t.const_data_ptr()); };
+            const float* w3[3] = {fp(P.loc(2)), fp(P.loc(4)), fp(P.loc(6))};
+            const float* b3[3] = {fp(P.loc(3)), fp(P.loc(5)), fp(P.loc(7))};
             SMIN_CK(smin_step_prologue(cur(), u8(qm), u8(video_mask), u8(length_mask), u8(moment_mask), w3, b3, B, Nq, Ti, Li, D, st.len32.data_ptr<int32_t>(), fpm(qmf),
                                        fpm(st.vmaskf), fpm(lmf), fpm(st.wb), fpm(bb), count.data_ptr<int64_t>(), prologue_words(dev).data_ptr()));
             mm = moment_mask;
@@ -507,8 +580,8 @@ struct SminCore : torch::autograd::Function<SminCore> {
                 host_n.copy_(count, /*non_blocking=*/true);
             }
         } else {
-            st.wb = at::stack({loc[2].view({D}), loc[4].view({D}), loc[6].view({D})});
-            bb = at::cat({loc[3], loc[5], loc[7]});
+            st.wb = at::stack({P.loc(2).view({D}), P.loc(4).view({D}), P.loc(6).view({D})});
+            bb = at::cat({P.loc(3), P.loc(5), P.loc(7)});
             // ---- layout, part 1: the cell count leaves for the host now and is waited for after the backbone is queued -- unless the
             // caller already knows it (n_known; a captured step: nothing inside may wait for the device)
             mm = moment_mask.scalar_type() == at::kBool ? moment_mask : moment_mask.ne(0);
@@ -520,8 +593,7 @@ struct SminCore : torch::autograd::Function<SminCore> {
             st.vmaskf = cont(fl(video_mask.reshape({Bq * Tn})));
             qmf = cont(fl(qm)); lmf = cont(fl(length_mask));
         }
-        hipEvent_t count_ready = next_event();
-        TORCH_CHECK(hipEventRecord(count_ready, curs.stream()) == hipSuccess, "hipEventRecord failed");
+        hipEvent_t count_ready = mark(curs);
 
         // ---- the video encoder's projection (models.py:25-36) on the second stream, beside the query encoder: only its product with the
         // sentence feature (models.py:81-83) waits for the LSTM layers (the fused call sat behind them: ~90 us of the step's opening chain).
@@ -536,8 +608,8 @@ struct SminCore : torch::autograd::Function<SminCore> {
         if (!bank && prep != curs) {
             await(prep, count_ready);                                              // (vmaskf)
             StreamScope sc(prep);
-            SMIN_CK(smin_video_encoder_fwd(cur(), fp(st.vx), fp(all[P_VE_W]), fp(all[P_VE_B]), fp(all[P_PE]), fp(st.vmaskf), nullptr, B, Ti, i32(st.vx.size(2)), D, fpm(st.fv),
-                                           nullptr));
+            SMIN_CK(smin_video_encoder_fwd(cur(), fp(st.vx), fp(P.backbone(P_VE_W)), fp(P.backbone(P_VE_B)), fp(P.backbone(P_PE)), fp(st.vmaskf), nullptr, B, Ti,
+                                           i32(st.vx.size(2)), D, fpm(st.fv), nullptr));
             projection_ready = mark(prep);
         }
 
@@ -547,13 +619,9 @@ struct SminCore : torch::autograd::Function<SminCore> {
             if (own_bank) {
                 // the two encoders once per video and once per query, on the main stream (as smin_encode_videos / smin_encode_queries);
                 // the prologue's vmaskf and len32 above are per pair and are replaced by the encoders' own rows, which the backward reads
-                const int64_t V = st.vx.size(0), Qn = query_features.size(0);
-                Tensor vm = bank->vmask_v.reshape({V * Tn});
-                st.vmaskf = cont(vm.is_floating_point() ? fl(vm) : vm.ne(0).to(at::kFloat));
-                st.len32 = bank->qmask_q.reshape({Qn, -1}).ne(0).sum(1).to(at::kInt).contiguous();
-                SMIN_CK(smin_video_encoder_fwd(cur(), fp(st.vx), fp(all[P_VE_W]), fp(all[P_VE_B]), fp(all[P_PE]), fp(st.vmaskf), nullptr, i32(V), Ti, i32(st.vx.size(2)), D,
-                                               fpm(st.fv), nullptr));
-                std::tie(bfw, bfs) = query_encoder(st.lstm, all, query_features, st.len32, maxq, H, false);
+                st.len32 = query_lengths(bank->qmask_q.reshape({query_features.size(0), -1}));
+                st.vmaskf = project_videos(P, st.vx, bank->vmask_v.reshape({st.vx.size(0) * Tn}), st.fv);
+                std::tie(bfw, bfs) = query_encoder(st.lstm, P, query_features, st.len32, maxq, H, false);
                 bfv = st.fv;
                 st.fs_bank = bfs; st.vi = bank->vi; st.qi = bank->qi;
                 st.v_ptr = bank->v_ptr; st.v_pairs = bank->v_pairs; st.q_ptr = bank->q_ptr; st.q_pairs = bank->q_pairs;
@@ -563,17 +631,18 @@ struct SminCore : torch::autograd::Function<SminCore> {
             SMIN_CK(smin_pair_assemble(cur(), fp(bfv), fp(bfs), fp(bfw), ip(bank->vi), ip(bank->qi), B, i32(bfv.size(0)), i32(bfs.size(0)), Ti, Nq, D, fpm(f), fpm(fw),
                                        fpm(fs)));
         } else {
-            std::tie(fw, fs) = query_encoder(st.lstm, all, query_features, st.len32, maxq, H, scoring);
+            std::tie(fw, fs) = query_encoder(st.lstm, P, query_features, st.len32, maxq, H, scoring);
             if (projection_ready) {
                 await(curs, projection_ready);
                 SMIN_CK(smin_video_encoder_gate(cur(), fp(st.fv), fp(fs), B, Ti, D, fpm(f)));
             } else {
-                SMIN_CK(smin_video_encoder_fwd(cur(), fp(st.vx), fp(all[P_VE_W]), fp(all[P_VE_B]), fp(all[P_PE]), fp(st.vmaskf), fp(fs), B, Ti, i32(st.vx.size(2)), D, fpm(st.fv), fpm(f)));
+                SMIN_CK(smin_video_encoder_fwd(cur(), fp(st.vx), fp(P.backbone(P_VE_W)), fp(P.backbone(P_VE_B)), fp(P.backbone(P_PE)), fp(st.vmaskf), fp(fs), B, Ti,
+                                               i32(st.vx.size(2)), D, fpm(st.fv), fpm(f)));
             }
         }
 
         // ---- layout, part 2
-        if (n_known < 0) TORCH_CHECK(hipEventSynchronize(count_ready) == hipSuccess, "hipEventSynchronize failed");
+        if (n_known < 0) host_wait(count_ready);
         const int64_t N = n_known < 0 ? host_n.const_data_ptr<int64_t>()[0] : n_known;
         const int n = i32(N);
         Tensor cells, row_ptr, cellmap;
@@ -585,11 +654,10 @@ struct SminCore : torch::autograd::Function<SminCore> {
             auto io = at::TensorOptions().dtype(at::kInt).device(dev);
             cells = at::empty({N, 4}, io); row_ptr = at::empty({Bq * L + 1}, io); cellmap = at::empty({Bq, L, L}, io);
             if (n_known < 0)
-                SMIN_CK(smin_build_cells(cur(), static_cast<const uint8_t*>(mask8.const_data_ptr()), B, Li, 0, cells.data_ptr<int32_t>(), row_ptr.data_ptr<int32_t>(),
-                                         cellmap.data_ptr<int32_t>()));
+                SMIN_CK(smin_build_cells(cur(), u8(mask8), B, Li, 0, cells.data_ptr<int32_t>(), row_ptr.data_ptr<int32_t>(), cellmap.data_ptr<int32_t>()));
             else
-                SMIN_CK(smin_build_cells_n(cur(), static_cast<const uint8_t*>(mask8.const_data_ptr()), B, Li, 0, n, cells.data_ptr<int32_t>(), row_ptr.data_ptr<int32_t>(),
-                                           cellmap.data_ptr<int32_t>(), layout_status(dev).data_ptr<int32_t>()));
+                SMIN_CK(smin_build_cells_n(cur(), u8(mask8), B, Li, 0, n, cells.data_ptr<int32_t>(), row_ptr.data_ptr<int32_t>(), cellmap.data_ptr<int32_t>(),
+                                           layout_status(dev).data_ptr<int32_t>()));
             layout_ready = mark(prep);
         }
         st.f = f; st.fw = fw; st.fs = fs; st.qmf = qmf; st.lmf = lmf; st.cells = cells; st.row_ptr = row_ptr; st.cellmap = cellmap;
@@ -601,21 +669,15 @@ struct SminCore : torch::autograd::Function<SminCore> {
             StreamScope sc(prep);
             std::vector<const float*> pp;
             for (int64_t k = 0; k < nl; ++k)
-                for (int which : {L_WH_W, L_WH_B, L_SH_W, L_SH_B, L_AK_W, L_AK_B, L_AQ_W, L_AQ_B}) pp.push_back(fp(lp(k, which)));
+                for (int which : L_WORD_SIDE) pp.push_back(fp(P.layer(k, which)));
             st.what = at::empty({nl, B, Nq, dl}, opt); st.kb = at::empty({nl, B, Nq, dl}, opt); st.Mq = at::empty({nl, B, Nq, dl}, opt);
             st.shat = at::empty({nl, B, dl}, opt); st.uq = at::empty({nl, B, Nq}, opt);
             SMIN_CK(smin_word_prep_fwd(cur(), fp(fw), fp(fs), fp(qmf), pp.data(), i32(nl), B, Nq, D, dl, fpm(st.what), fpm(st.shat), fpm(st.kb), fpm(st.Mq), fpm(st.uq)));
             words_ready = mark(prep);
         }
         if (prep != curs) { await(curs, products_ready); await(curs, layout_ready); }
-        // Tensors cross streams here without recordStream bookkeeping (an event record and queries per tensor and step: ~0.3 ms of
-        // host time).  What makes that safe: (1) every stretch of work on another stream starts with a wait for the main stream and
-        // the main stream waits for every other stream before forward / backward return; (2) no tensor that another stream has
-        // touched is released before that final wait (saved for backward, returned, or held in a function-scope list).  A block
-        // therefore returns to its stream's pool only after all streams have met, and its next user is ordered behind that.
-        // (scoring releases a layer's tensors earlier, but only behind that layer's join of the two streams and with every reader
-        // queued: a block then goes back to the main stream's pool behind the join, or to the second stream's, whose next stretch
-        // opens with a wait for the main stream.)
+        // Tensors cross streams here without recordStream bookkeeping: DESIGN.md 6, "Stream rules" (4) says what makes that safe, for
+        // scoring's early release of a layer's tensors too.
 
         // ---- proposal map (f_m, f_b) and every layer's clip-window term of chat
         Tensor fm = at::empty({N, D}, opt), fb = at::empty({B, L, D}, opt);
@@ -660,14 +722,14 @@ struct SminCore : torch::autograd::Function<SminCore> {
                 StreamScope sc(side);
                 ls.bu = at::empty_like(fb); ls.Qb = at::empty_like(fb); ls.baq = at::empty_like(fb); ls.bqv = at::empty_like(fb); ls.Kb = at::empty_like(fw);
                 ls.P = at::empty({B, L, Nq}, opt); ls.A = at::empty({B, L, L}, opt);
-                SMIN_CK(smin_boundary_unit_fwd(cur(), fp(fb), fp(fw), fp(fs), fp(ls.hbar), ip(cells), ip(row_ptr), n, B, Li, Nq, D, fp(lp(k, L_BQ_W)), fp(lp(k, L_BQ_B)),
-                                               fp(lp(k, L_BK_W)), fp(lp(k, L_BK_B)), fp(qmf), fp(lmf), fpm(ls.bu), fpm(ls.Qb), fpm(ls.Kb), fpm(ls.P), fpm(ls.baq),
+                SMIN_CK(smin_boundary_unit_fwd(cur(), fp(fb), fp(fw), fp(fs), fp(ls.hbar), ip(cells), ip(row_ptr), n, B, Li, Nq, D, fp(P.layer(k, L_BQ_W)), fp(P.layer(k, L_BQ_B)),
+                                               fp(P.layer(k, L_BK_W)), fp(P.layer(k, L_BK_B)), fp(qmf), fp(lmf), fpm(ls.bu), fpm(ls.Qb), fpm(ls.Kb), fpm(ls.P), fpm(ls.baq),
                                                fpm(ls.bqv), fpm(ls.A)));
                 if (keep_maps)                                                     // Attention.attn_weights (models.py:153) is P as written
                     TORCH_CHECK(hipMemcpyAsync(bmap.data_ptr(), ls.P.const_data_ptr(), sizeof(float) * ls.P.numel(), hipMemcpyDeviceToDevice, side.stream()) == hipSuccess,
                                 "hipMemcpyAsync failed");
             }
-            if (keep_maps) bmaps.push_back(bmap);
+            if (keep_maps) st.bmaps.push_back(bmap);
             // chat_k = clip-window term + [cc_0 | ..] Pcat^T + const_k + (Hs Wch^T per cell)
             Tensor chat = pgs[k];
             const Tensor& Hs_k = ls.Hs;
@@ -676,7 +738,7 @@ struct SminCore : torch::autograd::Function<SminCore> {
                 if (lo == 0) {
                     hp = at::empty({N, dl}, opt);
                     const float* xs[1] = {fp(Hs_k)};
-                    SMIN_CK(smin_linear_rows_fwd(cur(), xs, 1, fp(lp(k, L_CH_W)), nullptr, nullptr, nullptr, 1, n, dl, D, fpm(hp)));
+                    SMIN_CK(smin_linear_rows_fwd(cur(), xs, 1, fp(P.layer(k, L_CH_W)), nullptr, nullptr, nullptr, 1, n, dl, D, fpm(hp)));
                 }
                 const int nseg = i32(std::min<int64_t>(4, k - lo));
                 Tensor y = at::empty({N * C, dl}, opt);
@@ -699,11 +761,11 @@ struct SminCore : torch::autograd::Function<SminCore> {
                 SMIN_CK(smin_content_attn_fwd_probs(cur(), fp(chat), ip(cells), ip(row_ptr), n, B, Li, Ci, dl, Nq, fp(st.Mq[k]), fp(st.uq[k]), fp(st.what[k]),
                                                     fp(st.shat[k]), fp(qmf), lastl ? nullptr : ls.cc.data_ptr(), cc_bf16 && !lastl ? 1 : 0, fpm(ls.ccmean), fpm(probs)));
                 if (flags & F_ATTN_PACKED) {
-                    cmaps.push_back(probs);
+                    st.cmaps.push_back(probs);
                 } else {                                                           // ContentAttention.attn_weights in the reference's layout
                     Tensor dense = at::empty({Bq, L, L, C, (int64_t)Nq}, opt);
                     SMIN_CK(smin_content_attn_maps_dense(cur(), fp(probs), ip(cellmap), ip(cells), B, Li, Ci, dl, Nq, fp(st.uq[k]), fp(qmf), fpm(dense)));
-                    cmaps.push_back(dense);
+                    st.cmaps.push_back(dense);
                 }
             } else if (cc_bf16 && !lastl)
                 SMIN_CK(smin_content_attn_fwd_cch(cur(), fp(chat), ip(cells), ip(row_ptr), n, B, Li, Ci, dl, Nq, fp(st.Mq[k]), fp(st.uq[k]), fp(st.what[k]), fp(st.shat[k]),
@@ -718,14 +780,14 @@ struct SminCore : torch::autograd::Function<SminCore> {
                 st.pm = at::empty({B, L, L}, opt); st.psea = at::empty({3, B, L}, opt);
                 // (its vectors were formed with the parameter products; hbar is re-formed from fm and fs: measured faster than read)
                 SMIN_CK(smin_score_tail_fwd(cur(), fp(ls.ccmean), fp(cumean), nullptr, fp(fm), fp(fs), fp(ls.bu), ip(cells), n, B, Li, D, dl, nullptr, nullptr, nullptr,
-                                            nullptr, fp(loc[0]), nullptr, fp(st.wb), fp(bb), fp(lmf), fpm(st.pm), fpm(st.psea), st.tailv.data_ptr(),
+                                            nullptr, fp(P.loc(0)), nullptr, fp(st.wb), fp(bb), fp(lmf), fpm(st.pm), fpm(st.psea), st.tailv.data_ptr(),
                                             (size_t)st.tailv.numel()));
                 break;
             }
             ls.cum = at::empty({N, D}, opt);
             {
                 const float* xs[1] = {fp(ls.ccmean)};
-                SMIN_CK(smin_linear_rows_fwd(cur(), xs, 1, fp(lp(k, L_C_W)), fp(lp(k, L_C_B)), fp(cumean), fp(ls.hbar), 1, n, D, dl, fpm(ls.cum)));
+                SMIN_CK(smin_linear_rows_fwd(cur(), xs, 1, fp(P.layer(k, L_C_W)), fp(P.layer(k, L_C_B)), fp(cumean), fp(ls.hbar), 1, n, D, dl, fpm(ls.cum)));
             }
             wait_stream(curs, side);
             // f_b[i] * f_b[j], kept for the weight gradient (bf16 under bf16_operands: the layer's largest saved tensor); a scorer has
@@ -755,71 +817,50 @@ struct SminCore : torch::autograd::Function<SminCore> {
         if (scoring) return N;
         // Localization (models.py:335-344)
         Tensor pm = at::empty({B, L, L}, opt), psea = at::empty({3, B, L}, opt);
-        SMIN_CK(smin_score_map_fwd(cur(), fp(fm), fp(fb), ip(cells), n, B, Li, D, fp(loc[0]), fp(loc[1]), fp(st.wb), fp(bb), fp(lmf), fpm(pm), fpm(psea)));
+        SMIN_CK(smin_score_map_fwd(cur(), fp(fm), fp(fb), ip(cells), n, B, Li, D, fp(P.loc(0)), fp(P.loc(1)), fp(st.wb), fp(bb), fp(lmf), fpm(pm), fpm(psea)));
         st.pm = pm; st.psea = psea; st.fm_out = fm;
         return N;
     }
 
-    // what backward_from reads: every tensor of the state, the contiguous parameters, the shape
-    static void save_state(AutogradContext* ctx, CoreState& st, const std::vector<Tensor>& all, std::vector<int64_t> d)
-    {
-        variable_list flat;
-        visit_state(st, [&](Tensor& t) { flat.push_back(t); });
-        for (auto& p : all) flat.push_back(p);
-        ctx->save_for_backward(flat);
-        ctx->saved_data["d"] = std::move(d);
-    }
-
-    static variable_list forward(AutogradContext* ctx, Tensor video_features, Tensor video_mask, Tensor query_features, Tensor query_mask, Tensor length_mask,
-                                 Tensor moment_mask, int64_t T, int64_t L, int64_t C, int64_t nl, int64_t maxq, int64_t H, int64_t flags, int64_t n_known,
-                                 at::TensorList prm_in)
+    static variable_list forward(AutogradContext* ctx, Tensor video_features, Tensor query_features, const CoreCall& call, at::TensorList prm_in)
     {
         CoreState st;
-        std::vector<Tensor> all, cmaps, bmaps;                                     // the parameters; the attention maps (F_KEEP_ATTENTION)
-        const int64_t N = run(st, all, cmaps, bmaps, false, video_features, video_mask, query_features, query_mask, length_mask, moment_mask, T, L, C, nl, maxq, H, flags,
-                              n_known, prm_in);
-        const bool keep_maps = (flags & F_KEEP_ATTENTION) != 0;
-        const int64_t Nq_in = query_features.size(1);
-        const Tensor &pm = st.pm, &psea = st.psea, &cellmap = st.cellmap;
-
-        save_state(ctx, st, all, {N, T, L, C, nl, flags, H, Nq_in});
+        const int64_t N = run(st, call, video_features, query_features, prm_in);
+        // what backward reads: every tensor of the state, the contiguous parameters, the shape
+        variable_list flat;
+        visit_state(st, [&](Tensor& t) { flat.push_back(t); });
+        for (auto& p : st.prm.all) flat.push_back(p);
+        ctx->save_for_backward(flat);
+        SavedShape{N, call.T, call.L, call.C, call.nl, call.flags, call.H, query_features.size(1)}.put(ctx);
         // ps / pe / pa leave as three outputs of the node (rows of one buffer), not as selections of one output: the selections'
         // backward nodes cost three zero fills, three copies and two adds between the loss and this node's backward
-        if (!keep_maps) return {pm, psea[0], psea[1], psea[2]};
-        if (flags & F_ATTN_PACKED) cmaps.push_back(cellmap.clone());
-        variable_list out{pm, psea[0], psea[1], psea[2]};
-        for (auto& t : cmaps) out.push_back(t);
-        for (auto& t : bmaps) out.push_back(t);
+        variable_list out{st.pm, st.psea[0], st.psea[1], st.psea[2]};
+        if (!(call.flags & F_KEEP_ATTENTION)) return out;
+        if (call.flags & F_ATTN_PACKED) st.cmaps.push_back(st.cellmap.clone());
+        for (auto& t : st.cmaps) out.push_back(t);
+        for (auto& t : st.bmaps) out.push_back(t);
         ctx->mark_non_differentiable(variable_list(out.begin() + 4, out.end()));
         return out;
     }
 
-    static variable_list backward(AutogradContext* ctx, variable_list g) { return backward_from(ctx, g, N_FIXED); }
-
-    // The backward pass of a state run() left (this node's and SminPairCore's): the parameters' gradients in slots n_fixed .. of the
-    // result, the inputs' (F_INPUT_GRADS) in slots 0 and 2.  With the pair lists in the state (smin_forward_pairs) everything down to
+    // The backward pass of the state run() left: the parameters' gradients in slots N_FIXED .. of the result, the inputs'
+    // (F_INPUT_GRADS) in slots 0 and 1.  With the pair lists in the state (smin_forward_pairs) everything down to
     // df, dfs_parts and dfw_parts runs at batch P as it stands; smin_pair_assemble_bwd then sums the pairs onto their videos and
     // queries, and the backbone's backward runs at batch V (video encoder) and Q (sentence feature, LSTM layers).
-    static variable_list backward_from(AutogradContext* ctx, variable_list g, int64_t n_fixed)
+    static variable_list backward(AutogradContext* ctx, variable_list g)
     {
-        auto d = ctx->saved_data["d"].toIntVector();
-        const int64_t N = d[0], T = d[1], L = d[2], C = d[3], nl = d[4], flags = d[5], H = d[6], Nq_in = d[7];
+        const auto [N, T, L, C, nl, flags, H, Nq_in] = SavedShape::get(ctx);
         const bool prep_kernel = (flags & F_PARAM_PREP_KERNEL) != 0;
         auto sv = ctx->get_saved_variables();
         CoreState st;
         size_state(st, nl);
         size_t cursor = 0;
         visit_state(st, [&](Tensor& t) { t = sv[cursor++]; });
-        std::vector<Tensor> all(sv.begin() + cursor, sv.end());
-        std::vector<Tensor> prm(all.begin() + P_LAYER0, all.end());
-        auto lp = [&](int64_t k, int which) -> const Tensor& { return prm[k * L_COUNT + which]; };
-        const Tensor* loc = &prm[nl * L_COUNT];
+        const ParamList P(std::vector<Tensor>(sv.begin() + cursor, sv.end()), nl);
+        ParamList dprm(nl);                                                        // the gradients, slot for slot
         const Tensor &f = st.f, &fw = st.fw, &fs = st.fs, &qmf = st.qmf, &lmf = st.lmf, &cells = st.cells, &row_ptr = st.row_ptr, &cellmap = st.cellmap;
-        const at::Device dev = f.device();
-        const auto opt = f.options();
-        const int B = i32(f.size(0)), D = i32(f.size(2)), Nq = i32(fw.size(1)), dl = i32(prm[L_CH_W].size(0)), n = i32(N), Li = i32(L), Ci = i32(C), Ti = i32(T);
-        HStream curs = c10::hip::getCurrentHIPStream(dev.index());
-        HStream side = (flags & F_OVERLAP_BOUNDARY) ? side_stream(dev.index()) : curs;
+        const auto [dev, opt, B, D, Nq, dl, Li, Ci, Ti, curs, side] = Dims(f, f.size(0), P, T, L, C, fw.size(1), flags);
+        const int n = i32(N);
         // weight-gradient contractions: nothing waits for them before the end of the step, so they go to a low-priority stream
         // of their own and fill the chip beside the bandwidth-bound kernels of the main chain
         HStream wstr = (flags & F_ASYNC_WEIGHTS) ? weight_stream(dev.index()) : curs;
@@ -828,28 +869,25 @@ struct SminCore : torch::autograd::Function<SminCore> {
         sync.on = (flags & F_GRAD_SYNC) != 0;
         TORCH_CHECK(!sync.on || prep_kernel, "smin_forward: the in-node gradient exchange needs param_prep_kernel (SMIN._param_prep_kernel)");
         // the inputs' gradients (F_INPUT_GRADS): d video_features = the video encoder's dx, d query_features = LSTM layer 0's dX
-        const bool want_dx = (flags & F_INPUT_GRADS) && ctx->needs_input_grad(0), want_dX = (flags & F_INPUT_GRADS) && ctx->needs_input_grad(2);
+        const bool want_dx = (flags & F_INPUT_GRADS) && ctx->needs_input_grad(0), want_dX = (flags & F_INPUT_GRADS) && ctx->needs_input_grad(1);
         TORCH_CHECK(!sync.on || !grad_sync_config().group.empty(), "smin_forward: grad_sync requested but no process group was set (smin_hip::set_grad_sync)");
-        std::vector<Tensor> dprm(prm.size());
-        auto dlp = [&](int64_t k, int which) -> Tensor& { return dprm[k * L_COUNT + which]; };
         auto acc = [](Tensor& into, const Tensor& t) { if (into.defined()) into.add_(t); else into = t; };
 
         // ---- W^T of every contraction weight, one launch
         enum { TR_CH = 0, TR_C, TR_CAT, TR_BQ, TR_BK, TR_PER_LAYER };
         std::vector<Tensor> tr_in;
         for (int64_t k = 0; k < nl; ++k) {
-            tr_in.push_back(lp(k, L_CH_W)); tr_in.push_back(lp(k, L_C_W)); tr_in.push_back(st.layer[k].Wcat); tr_in.push_back(lp(k, L_BQ_W)); tr_in.push_back(lp(k, L_BK_W));
+            for (const Tensor& w : {P.layer(k, L_CH_W), P.layer(k, L_C_W), st.layer[k].Wcat, P.layer(k, L_BQ_W), P.layer(k, L_BK_W)}) tr_in.push_back(w);
         }
         const size_t tr_pcat0 = tr_in.size();
         for (int64_t k = 0; k < nl; ++k) for (auto& p : st.layer[k].Pcat) tr_in.push_back(p);
         const size_t tr_tail = tr_in.size();
         tr_in.push_back(st.Wch_all);
         tr_in.push_back(st.lstm[0].Wih); tr_in.push_back(st.lstm[1].Wih);
-        if (want_dx) tr_in.push_back(all[P_VE_W]);
+        if (want_dx) tr_in.push_back(P.backbone(P_VE_W));
         // (on the boundary stream, as the boundary heads' backward below: beside the score map's backward on the main stream, which
         //  otherwise opens the backward pass with four short launches in a row in front of the first contraction)
         HStream early = (side != curs && (flags & F_OVERLAP_PREP)) ? side : curs;
-        auto mark0 = [](HStream on) { hipEvent_t e = next_event(); TORCH_CHECK(hipEventRecord(e, on.stream()) == hipSuccess, "hipEventRecord failed"); return e; };
         wait_stream(early, curs);
         std::vector<Tensor> tr;
         {
@@ -882,27 +920,26 @@ struct SminCore : torch::autograd::Function<SminCore> {
         {
             Tensor dwm = at::empty({D}, opt), dbm = at::empty({1}, opt), dwb = at::empty({3, D}, opt), dbb = at::empty({3}, opt);
             if (early != curs) {
-                wait_stream(early, curs);                                          // (behind the allocations above: see "the backward's tail", lesson 2)
+                wait_stream(early, curs);                                          // (behind the allocations above: "Stream rules" (2))
                 {
                     StreamScope sc(early);
                     auto ws = scratch(smin_workspace_bytes(n, B, 4, D, 4, 1), dev);
-                    SMIN_CK(smin_score_map_bwd(cur(), nullptr, fp(dpsea), fp(st.pm), fp(st.psea), fp(st.fm_out), fp(bu_last), ip(cells), n, B, Li, D, fp(loc[0]), fp(st.wb),
+                    SMIN_CK(smin_score_map_bwd(cur(), nullptr, fp(dpsea), fp(st.pm), fp(st.psea), fp(st.fm_out), fp(bu_last), ip(cells), n, B, Li, D, fp(P.loc(0)), fp(st.wb),
                                                fp(lmf), nullptr, fpm(dfb_next), nullptr, nullptr, fpm(dwb), fpm(dbb), ws.p, ws.n));
                 }
-                hipEvent_t early_done = mark0(early);
+                hipEvent_t early_done = mark(early);
                 auto ws = scratch(smin_workspace_bytes(n, B, 4, D, 4, 1), dev);
-                SMIN_CK(smin_score_map_bwd(cur(), fp(dpm), nullptr, fp(st.pm), fp(st.psea), fp(st.fm_out), fp(bu_last), ip(cells), n, B, Li, D, fp(loc[0]), fp(st.wb), fp(lmf),
+                SMIN_CK(smin_score_map_bwd(cur(), fp(dpm), nullptr, fp(st.pm), fp(st.psea), fp(st.fm_out), fp(bu_last), ip(cells), n, B, Li, D, fp(P.loc(0)), fp(st.wb), fp(lmf),
                                            fpm(dfm), nullptr, fpm(dwm), fpm(dbm), nullptr, nullptr, ws.p, ws.n));
-                TORCH_CHECK(hipStreamWaitEvent(curs.stream(), early_done, 0) == hipSuccess, "hipStreamWaitEvent failed");    // W^T and dfb_next
+                await(curs, early_done);                                           // W^T and dfb_next
             } else {
                 auto ws = scratch(smin_workspace_bytes(n, B, 4, D, 4, 1), dev);
-                SMIN_CK(smin_score_map_bwd(cur(), fp(dpm), fp(dpsea), fp(st.pm), fp(st.psea), fp(st.fm_out), fp(bu_last), ip(cells), n, B, Li, D, fp(loc[0]), fp(st.wb), fp(lmf),
+                SMIN_CK(smin_score_map_bwd(cur(), fp(dpm), fp(dpsea), fp(st.pm), fp(st.psea), fp(st.fm_out), fp(bu_last), ip(cells), n, B, Li, D, fp(P.loc(0)), fp(st.wb), fp(lmf),
                                            fpm(dfm), fpm(dfb_next), fpm(dwm), fpm(dbm), fpm(dwb), fpm(dbb), ws.p, ws.n));
             }
-            Tensor* dloc = &dprm[nl * L_COUNT];
             loc_bufs = {dwm, dbm, dwb, dbb};
-            dloc[0] = dwm.view_as(loc[0]); dloc[1] = dbm.view_as(loc[1]);
-            for (int h = 0; h < 3; ++h) { dloc[2 + 2 * h] = dwb[h].view_as(loc[2 + 2 * h]); dloc[3 + 2 * h] = dbb.slice(0, h, h + 1).view_as(loc[3 + 2 * h]); }
+            dprm.loc(0) = dwm.view_as(P.loc(0)); dprm.loc(1) = dbm.view_as(P.loc(1));
+            for (int h = 0; h < 3; ++h) { dprm.loc(2 + 2 * h) = dwb[h].view_as(P.loc(2 + 2 * h)); dprm.loc(3 + 2 * h) = dbb.slice(0, h, h + 1).view_as(P.loc(3 + 2 * h)); }
         }
 
         std::vector<Tensor> dcc(nl), dHs(nl), dchat(nl), dconsts(nl), dfs_parts, dfw_parts;
@@ -917,7 +954,6 @@ struct SminCore : torch::autograd::Function<SminCore> {
         Tensor dwhat = at::empty_like(st.what), dshat = at::empty_like(st.shat), dMq = at::empty_like(st.Mq), duq = at::empty_like(st.uq);
         if (N == 0) { dwhat.zero_(); dshat.zero_(); dMq.zero_(); duq.zero_(); }
         Tensor dcum_next;                                                          // gradient of cum_k from layer k+1's clip-mean chain
-        auto mark_on = [](HStream on) { hipEvent_t e = next_event(); TORCH_CHECK(hipEventRecord(e, on.stream()) == hipSuccess, "hipEventRecord failed"); return e; };
         hipEvent_t attn0_done = nullptr;
         hipEvent_t boundary_done = nullptr;                                        // the previous iteration's boundary-unit backward (side stream)
         for (int64_t k = nl - 1; k >= 0; --k) {
@@ -938,15 +974,16 @@ struct SminCore : torch::autograd::Function<SminCore> {
                     SMIN_CK(smin_moment_unit_bwd(cur(), fp(dfm), fp(ls.cum), fp(ls.bu), ip(cells), ip(row_ptr), ip(cellmap), n, B, Li, D, fp(trk(k, TR_CAT)), nullptr, nullptr,
                                                  fpm(dWcat), fpm(dbcat), ws.p, ws.n, 1, nullptr, fp(ls.x1), nullptr));
                 if (!prep_kernel) {
-                    dlp(k, L_FB_W) = dWcat.slice(1, 0, D).contiguous().view_as(lp(k, L_FB_W)); dlp(k, L_FC_W) = dWcat.slice(1, D).contiguous().view_as(lp(k, L_FC_W));
-                    dlp(k, L_FB_B) = dbcat; dlp(k, L_FC_B) = dbcat;
+                    dprm.layer(k, L_FB_W) = dWcat.slice(1, 0, D).contiguous().view_as(P.layer(k, L_FB_W));
+                    dprm.layer(k, L_FC_W) = dWcat.slice(1, D).contiguous().view_as(P.layer(k, L_FC_W));
+                    dprm.layer(k, L_FB_B) = dbcat; dprm.layer(k, L_FC_B) = dbcat;
                 }
                 sync.reduce({dWcat, dbcat}, wstr);                                   // inputs of the parameter-product kernel
             }
             // the previous layer's boundary-unit backward (second stream) is awaited HERE, where its dfb is first read -- not in front of
             // that layer's gate backward, which reads nothing of it any more (it forms the unit's dhbar itself): the main stream sat
             // ~0.6 ms behind the unit's weight contractions at the end of layer 0 (tools/gantt.sh)
-            if (boundary_done) { TORCH_CHECK(hipStreamWaitEvent(curs.stream(), boundary_done, 0) == hipSuccess, "hipStreamWaitEvent failed"); boundary_done = nullptr; }
+            if (boundary_done) { await(curs, boundary_done); boundary_done = nullptr; }
             {
                 auto ws = scratch(smin_workspace_bytes(n, B, 4, D, 4, 1), dev);
                 SMIN_CK(smin_moment_unit_bwd(cur(), fp(dfm), fp(ls.cum), fp(ls.bu), ip(cells), ip(row_ptr), ip(cellmap), n, B, Li, D, fp(trk(k, TR_CAT)), fpm(dcum), fpm(dfb_mu),
@@ -967,12 +1004,12 @@ struct SminCore : torch::autograd::Function<SminCore> {
                 SMIN_CK(smin_boundary_unit_bwd(cur(), fp(dbu), fp(ls.fb), fp(fw), fp(fs), fp(ls.hbar), ip(cells), ip(row_ptr), n, B, Li, Nq, D, fp(trk(k, TR_BQ)), fp(trk(k, TR_BK)),
                                                fp(qmf), fp(lmf), fp(ls.Qb), fp(ls.Kb), fp(ls.P), fp(ls.baq), fp(ls.bqv), fp(ls.A), fpm(dfb_k), fpm(dfw), fpm(dfs), nullptr,
                                                fpm(dWq), fpm(dbq), fpm(dWk), fpm(dbk), ws.p, ws.n));
-                dlp(k, L_BQ_W) = dWq; dlp(k, L_BQ_B) = dbq; dlp(k, L_BK_W) = dWk; dlp(k, L_BK_B) = dbk;
+                dprm.layer(k, L_BQ_W) = dWq; dprm.layer(k, L_BQ_B) = dbq; dprm.layer(k, L_BK_W) = dWk; dprm.layer(k, L_BK_B) = dbk;
                 sync.reduce({dWq, dbq, dWk, dbk}, side);
                 dfs_parts.push_back(dfs); dfw_parts.push_back(dfw);
                 keep.push_back(dfb_next); keep.push_back(dfb_mu); keep.push_back(dbu);
             }
-            if (side != curs) boundary_done = mark_on(side);
+            if (side != curs) boundary_done = mark(side);
             // clip-mean update cum = ccmean Wc^T + b + cumean + hbar: d ccmean, weight gradients; d cumean = d hbar = dcum
             Tensor dccmean = at::empty({N, dl}, opt);
             {
@@ -987,7 +1024,7 @@ struct SminCore : torch::autograd::Function<SminCore> {
                 SMIN_CK(smin_content_attn_bwd(cur(), fp(dcc[k]), fp(dccmean), fp(ls.chat), ip(cells), ip(row_ptr), n, B, Li, Ci, dl, Nq, fp(st.Mq[k]), fp(st.uq[k]), fp(st.what[k]),
                                               fp(st.shat[k]), fp(qmf), fpm(dchat[k]), fpm(dMq[k]), fpm(duq[k]), fpm(dwhat[k]), fpm(dshat[k]), ws.p, ws.n));
             }
-            if (k == 0) attn0_done = mark_on(curs);                                // every dchat / word-side gradient is final from here on
+            if (k == 0) attn0_done = mark(curs);                                // every dchat / word-side gradient is final from here on
             // chat_k's contraction over the earlier layers' attention outputs, and its per-cell gate term: input gradients
             Tensor dhp;
             for (int64_t part = 0, lo = 0; lo < k; ++part, lo += 4) {
@@ -1023,12 +1060,12 @@ struct SminCore : torch::autograd::Function<SminCore> {
             {
                 StreamScope sc(wstr);
                 {
-                    Tensor dWc = at::empty_like(lp(k, L_C_W)), dbc = at::empty({D}, opt);
+                    Tensor dWc = at::empty_like(P.layer(k, L_C_W)), dbc = at::empty({D}, opt);
                     const float* xs[1] = {fp(ls.ccmean)};
                     auto ws = scratch(smin_linear_rows_bwd_workspace_bytes(n, D, dl), dev);
                     SMIN_CK(smin_linear_rows_bwd(cur(), fp(dcum), xs, 1, nullptr, n, D, dl, nullptr, fpm(dWc), fpm(dbc), ws.p, ws.n));
                     if (prep_kernel) { base_c[k] = dWc; base_bc[k] = dbc; }
-                    else { acc(dlp(k, L_C_W), dWc); acc(dlp(k, L_C_B), dbc); }
+                    else { acc(dprm.layer(k, L_C_W), dWc); acc(dprm.layer(k, L_C_B), dbc); }
                 }
                 for (int64_t part = 0, lo = 0; lo < k; ++part, lo += 4) {
                     const int nseg = i32(std::min<int64_t>(4, k - lo));
@@ -1047,11 +1084,11 @@ struct SminCore : torch::autograd::Function<SminCore> {
                     dPcat[k].push_back(dP);
                 }
                 if (k > 0) {
-                    Tensor dWch = at::empty_like(lp(k, L_CH_W));
+                    Tensor dWch = at::empty_like(P.layer(k, L_CH_W));
                     const float* xs[1] = {fp(ls.Hs)};
                     auto ws = scratch(smin_linear_rows_bwd_workspace_bytes(n, dl, D), dev);
                     SMIN_CK(smin_linear_rows_bwd(cur(), fp(dhp), xs, 1, nullptr, n, dl, D, nullptr, fpm(dWch), nullptr, ws.p, ws.n));
-                    if (prep_kernel) base_ch[k] = dWch; else acc(dlp(k, L_CH_W), dWch);
+                    if (prep_kernel) base_ch[k] = dWch; else acc(dprm.layer(k, L_CH_W), dWch);
                 }
             }
             // gate: every consumer of hbar_k (clip-mean update, boundary unit, the later layers' running sums) and of f_m (residual; layer 0: the clip-mean chain)
@@ -1088,8 +1125,6 @@ struct SminCore : torch::autograd::Function<SminCore> {
         HStream tail = (flags & F_OVERLAP_PREP) ? side_stream(dev.index()) : curs;
         HStream wordst = !(flags & F_OVERLAP_PREP) ? curs : tail_split ? side_stream(dev.index(), 1) : tail;
         HStream cw = tail_split ? tail : curs;                                      // stream of the clip-window gradients
-        auto mark = mark_on;
-        auto await = [](HStream waiter, hipEvent_t e) { TORCH_CHECK(hipStreamWaitEvent(waiter.stream(), e, 0) == hipSuccess, "hipStreamWaitEvent failed"); };
         if (!attn0_done) attn0_done = mark(curs);
         hipEvent_t words_done;
         if (!tail_split) wait_stream(wordst, curs);
@@ -1100,10 +1135,10 @@ struct SminCore : torch::autograd::Function<SminCore> {
             std::vector<float*> dp;
             for (int64_t k = 0; k < nl; ++k) {
                 gp[0].push_back(fp(dwhat[k])); gp[1].push_back(fp(dshat[k])); gp[2].push_back(fp(dMq[k])); gp[3].push_back(fp(duq[k]));
-                for (int which : {L_WH_W, L_WH_B, L_SH_W, L_SH_B, L_AK_W, L_AK_B, L_AQ_W, L_AQ_B}) {
-                    pp.push_back(fp(lp(k, which)));
-                    dlp(k, which) = at::empty_like(lp(k, which));
-                    dp.push_back(fpm(dlp(k, which)));
+                for (int which : L_WORD_SIDE) {
+                    pp.push_back(fp(P.layer(k, which)));
+                    dprm.layer(k, which) = at::empty_like(P.layer(k, which));
+                    dp.push_back(fpm(dprm.layer(k, which)));
                 }
             }
             Tensor dfw = at::empty_like(fw), dfs = at::empty_like(fs);
@@ -1115,7 +1150,7 @@ struct SminCore : torch::autograd::Function<SminCore> {
             if (sync.on) {
                 std::vector<Tensor> ws_grads = loc_bufs;
                 for (int64_t k = 0; k < nl; ++k)
-                    for (int which : {L_WH_W, L_WH_B, L_SH_W, L_SH_B, L_AK_W, L_AK_B, L_AQ_W, L_AQ_B}) ws_grads.push_back(dlp(k, which));
+                    for (int which : L_WORD_SIDE) ws_grads.push_back(dprm.layer(k, which));
                 sync.reduce(ws_grads, wordst);
             }
         }
@@ -1125,7 +1160,7 @@ struct SminCore : torch::autograd::Function<SminCore> {
         hipEvent_t weights_done;
         bool tab_built = false;
         auto tab = clip_event_table(dev, Ti, Li, Ci, &tab_built);
-        if (tab_built) wait_stream(cw, curs);                                    // first backward of this geometry only
+        if (tab_built) wait_stream(cw, curs);                                    // first backward of this geometry only ("Stream rules" (1))
         {
             std::vector<const float*> ptrs;
             for (int64_t k = 0; k < nl; ++k) ptrs.push_back(fp(dchat[k]));
@@ -1134,8 +1169,7 @@ struct SminCore : torch::autograd::Function<SminCore> {
             Tensor dg;
             {
                 StreamScope sc(cw);
-                // allocated under THIS stream: a block from the main stream's pool may still be read by main-stream kernels queued behind
-                // attn0_done (the allocator only orders reuse within the stream a block was allocated on)
+                // allocated under THIS stream ("Stream rules" (2)): main-stream kernels are queued behind attn0_done
                 dg = at::empty({(int64_t)B * T, nl * dl}, opt);
                 keep.push_back(dg);
                 auto ws = scratch((size_t)4 * B * T * std::max<int64_t>(D, nl * dl), dev);
@@ -1147,14 +1181,13 @@ struct SminCore : torch::autograd::Function<SminCore> {
             {
                 StreamScope sc(tail_split ? tail : wstr);
                 // the weight gradient of the clip-window contraction stays on this stream (its only consumer is the parameter-product kernel
-                // queued here below).  NOT on the weight stream: that stream would wait for this one and this one for it, and two forked
-                // streams that wait for each other's events send hipStreamEndCapture into an endless recursion (captured step).
+                // queued here below).  NOT on the weight stream: that stream would wait for this one and this one for it ("Stream rules" (3)).
                 if (!prep_kernel) dconsts[0] = at::empty({dl}, opt);
                 const float* xs[1] = {fp(f)};
                 dWch_all = at::empty_like(st.Wch_all);
                 auto wsw = scratch(smin_linear_rows_bwd_workspace_bytes(i32(B * T), i32(nl * dl), D), dev);
                 SMIN_CK(smin_linear_rows_bwd(cur(), fp(dg), xs, 1, nullptr, i32(B * T), i32(nl * dl), D, nullptr, fpm(dWch_all), nullptr, wsw.p, wsw.n));
-                if (!prep_kernel) for (int64_t k = 0; k < nl; ++k) acc(dlp(k, L_CH_W), dWch_all.slice(0, k * dl, (k + 1) * dl));
+                if (!prep_kernel) for (int64_t k = 0; k < nl; ++k) acc(dprm.layer(k, L_CH_W), dWch_all.slice(0, k * dl, (k + 1) * dl));
                 // layer 0's constant: its gradient is the column sum of dchat_0 (the later layers' ride on their weight-gradient passes)
                 auto wsc = scratch(smin_col_sum_workspace_bytes(i32(N * C), dl), dev);
                 SMIN_CK(smin_col_sum(cur(), fp(dchat[0]), i32(N * C), dl, fpm(dconsts[0]), wsc.p, wsc.n));
@@ -1162,7 +1195,7 @@ struct SminCore : torch::autograd::Function<SminCore> {
             // df = gradient through the proposal map (f_m, f_b) + gradient through the clip-window terms, the second accumulated by its
             // contraction's epilogue
             df = at::empty({B, T, D}, opt);
-            if (boundary_done) { TORCH_CHECK(hipStreamWaitEvent(curs.stream(), boundary_done, 0) == hipSuccess, "hipStreamWaitEvent failed"); boundary_done = nullptr; }   // layer 0's dfb
+            if (boundary_done) { await(curs, boundary_done); boundary_done = nullptr; }   // layer 0's dfb
             auto ws3 = scratch((size_t)4 * B * T * std::max<int64_t>(D, nl * dl), dev);
             SMIN_CK(smin_proposal_map_bwd(cur(), nullptr, fp(dfm), fp(dfb_next), ip(cells), ip(row_ptr), ip(cellmap), n, B, Ti, Li, Ci, D, fpm(df), ws3.p, ws3.n, ip(tab.first),
                                           tab.second.data_ptr()));
@@ -1188,10 +1221,10 @@ struct SminCore : torch::autograd::Function<SminCore> {
             std::vector<const float*> pp, dpc(nl * 2, nullptr), bch(nl, nullptr), bc(nl), bbc(nl);
             std::vector<float*> gp;
             for (int64_t k = 0; k < nl; ++k) {
-                for (int which : {L_CH_W, L_CH_B, L_C_W, L_C_B, L_FB_W, L_FB_B, L_FC_W, L_FC_B}) {
-                    pp.push_back(fp(lp(k, which)));
-                    dlp(k, which) = at::empty_like(lp(k, which));
-                    gp.push_back(fpm(dlp(k, which)));
+                for (int which : L_PRODUCTS) {
+                    pp.push_back(fp(P.layer(k, which)));
+                    dprm.layer(k, which) = at::empty_like(P.layer(k, which));
+                    gp.push_back(fpm(dprm.layer(k, which)));
                 }
                 for (size_t part = 0; part < dPcat[k].size(); ++part) dpc[k * 2 + part] = fp(dPcat[k][part]);
                 bch[k] = fp(base_ch[k]); bc[k] = fp(base_c[k]); bbc[k] = fp(base_bc[k]);
@@ -1202,39 +1235,39 @@ struct SminCore : torch::autograd::Function<SminCore> {
             StreamScope sc(tail);
             Tensor bsum;
             std::vector<Tensor> bsums(nl);
-            for (int64_t k = 0; k < nl; ++k) { bsums[k] = bsum; bsum = bsum.defined() ? bsum + lp(k, L_C_B) : lp(k, L_C_B); }
+            for (int64_t k = 0; k < nl; ++k) { bsums[k] = bsum; bsum = bsum.defined() ? bsum + P.layer(k, L_C_B) : P.layer(k, L_C_B); }
             Tensor dbsum_run;                                                       // sum_{k' > l} Wch_k'^T dconst_k'
             for (int64_t k = nl - 1; k >= 0; --k) {
-                dlp(k, L_CH_B) = dconsts[k];
-                if (dbsum_run.defined()) dlp(k, L_C_B).add_(dbsum_run);           // in place: the buffer was allocated on the main stream and must outlive this launch
+                dprm.layer(k, L_CH_B) = dconsts[k];
+                if (dbsum_run.defined()) dprm.layer(k, L_C_B).add_(dbsum_run);           // in place: the buffer was allocated on the main stream and must outlive this launch
                 if (k > 0) {
-                    dlp(k, L_CH_W).addr_(dconsts[k], bsums[k]);
+                    dprm.layer(k, L_CH_W).addr_(dconsts[k], bsums[k]);
                     Tensor dbs = at::mv(trk(k, TR_CH), dconsts[k]);
                     dbsum_run = dbsum_run.defined() ? dbsum_run + dbs : dbs;
                 }
                 for (size_t part = 0; part < dPcat[k].size(); ++part)
                     for (int64_t l = (int64_t)part * 4; l < std::min<int64_t>((int64_t)part * 4 + 4, k); ++l) {
                         Tensor dP = dPcat[k][part].slice(1, (l - (int64_t)part * 4) * dl, (l - (int64_t)part * 4 + 1) * dl);
-                        dlp(k, L_CH_W).addmm_(dP, trk(l, TR_C));                   // dWch_k += dP_kl Wc_l^T
-                        dlp(l, L_C_W).addmm_(trk(k, TR_CH), dP);                   // dWc_l  += Wch_k^T dP_kl
+                        dprm.layer(k, L_CH_W).addmm_(dP, trk(l, TR_C));                   // dWch_k += dP_kl Wc_l^T
+                        dprm.layer(l, L_C_W).addmm_(trk(k, TR_CH), dP);                   // dWc_l  += Wch_k^T dP_kl
                     }
             }
         }
 
         // ---- backbone on the main stream: video encoder, sentence / word features, the two LSTM layers (models.py:38-83)
-        std::vector<Tensor> dbb(P_LAYER0), lstm_bufs;
+        std::vector<Tensor> lstm_bufs;
         Tensor dvideo, dquery;
         // the backbone's weight halves: on the word stream (idle by now) when there is one -- the weight stream still holds layer 0's
         // moment-unit contraction, and these short kernels close the step
         HStream bstr = (tail_split && wordst != curs && wstr != curs) ? wordst : wstr;
         {
             const int Din = i32(st.vx.size(2));
-            const int64_t pe_rows = all[P_PE].size(0);
+            const int64_t pe_rows = P.backbone(P_PE).size(0);
             const bool pairs = st.vi.defined();
             const int Bv = i32(st.vx.size(0)), Bw = i32(st.lstm[0].x.size(0));     // rows of the video encoder and of the query encoder (B unless pairs)
             Tensor dfs_video = at::empty({(int64_t)Bv, (int64_t)D}, opt);
-            dbb[P_VE_W] = at::empty({D, Din}, opt); dbb[P_VE_B] = at::empty({D}, opt);
-            dbb[P_PE] = pe_rows != T ? at::zeros({pe_rows, D}, opt) : at::empty({T, D}, opt);
+            dprm.backbone(P_VE_W) = at::empty({D, Din}, opt); dprm.backbone(P_VE_B) = at::empty({D}, opt);
+            dprm.backbone(P_PE) = pe_rows != T ? at::zeros({pe_rows, D}, opt) : at::empty({T, D}, opt);
             // every call below is split into its inputs half (main stream, the dependent chain) and its weights half (weight stream); the
             // intermediate of a pair lives in a buffer of its own (the per-stream scratch is reused by the next call on that stream)
             auto own = [&](size_t nbytes) {
@@ -1275,8 +1308,8 @@ struct SminCore : torch::autograd::Function<SminCore> {
             wait_stream(bstr, curs);
             {
                 StreamScope sc(bstr);
-                SMIN_CK(smin_video_encoder_bwd(cur(), nullptr, fp(st.fv), fp(venc_fs), fp(st.vmaskf), fp(st.vx), Bv, Ti, Din, D, fpm(dbb[P_VE_W]), fpm(dbb[P_VE_B]),
-                                               fpm(dbb[P_PE]), nullptr, wsv.data_ptr(), (size_t)wsv.numel()));
+                SMIN_CK(smin_video_encoder_bwd(cur(), nullptr, fp(st.fv), fp(venc_fs), fp(st.vmaskf), fp(st.vx), Bv, Ti, Din, D, fpm(dprm.backbone(P_VE_W)), fpm(dprm.backbone(P_VE_B)),
+                                               fpm(dprm.backbone(P_PE)), nullptr, wsv.data_ptr(), (size_t)wsv.numel()));
             }
             for (int layer = 1; layer >= 0; --layer) {
                 LstmState& ls = st.lstm[layer];
@@ -1304,7 +1337,7 @@ struct SminCore : torch::autograd::Function<SminCore> {
                 }
                 if (dX.defined()) keep.push_back(dX);
                 const int64_t H4 = 4 * H;
-                Tensor* o = &dbb[P_LSTM + 8 * layer];
+                Tensor* o = &dprm.backbone(P_LSTM + 8 * layer);
                 o[0] = dWih.slice(0, 0, H4); o[1] = dWhh[0]; o[2] = dbias.slice(0, 0, H4); o[3] = dbias2.slice(0, 0, H4);
                 o[4] = dWih.slice(0, H4); o[5] = dWhh[1]; o[6] = dbias.slice(0, H4); o[7] = dbias2.slice(0, H4);
                 dH = dX;
@@ -1321,42 +1354,18 @@ struct SminCore : torch::autograd::Function<SminCore> {
         wait_stream(curs, wstr);
         wait_stream(curs, wordst);
         if (sync.on) {
-            std::vector<Tensor> late{dbb[P_VE_W], dbb[P_VE_B], dbb[P_PE]};
+            std::vector<Tensor> late{dprm.backbone(P_VE_W), dprm.backbone(P_VE_B), dprm.backbone(P_PE)};
             for (auto& t : lstm_bufs) late.push_back(t);
             sync.reduce(late, curs);
             sync.join(curs);
         }
 
-        variable_list out(n_fixed + all.size());
+        variable_list out(N_FIXED + dprm.all.size());
         if (want_dx) out[0] = dvideo;
-        if (want_dX) out[2] = dquery;
-        for (size_t i = 0; i < all.size(); ++i) out[n_fixed + i] = i < (size_t)P_LAYER0 ? dbb[i] : dprm[i - P_LAYER0];
+        if (want_dX) out[1] = dquery;
+        std::copy(dprm.all.begin(), dprm.all.end(), out.begin() + N_FIXED);
         return out;
     }
-};
-
-// smin_forward_pairs' node: SminCore's run on the pairs of banks it encodes itself, and SminCore's backward (backward_from).
-struct SminPairCore : torch::autograd::Function<SminPairCore> {
-    enum { N_FIXED = 20 };          // forward arguments ahead of the parameter list
-    static variable_list forward(AutogradContext* ctx, Tensor video_features, Tensor video_mask, Tensor query_features, Tensor query_mask, Tensor length_mask,
-                                 Tensor moment_mask, Tensor video_index, Tensor query_index, Tensor v_ptr, Tensor v_pairs, Tensor q_ptr, Tensor q_pairs, int64_t T, int64_t L,
-                                 int64_t C, int64_t nl, int64_t maxq, int64_t H, int64_t flags, int64_t n_known, at::TensorList prm_in)
-    {
-        PairBank bank;
-        bank.train = true;
-        bank.vi = video_index; bank.qi = query_index;
-        bank.vmask_v = video_mask; bank.qmask_q = query_mask;
-        bank.v_ptr = v_ptr; bank.v_pairs = v_pairs; bank.q_ptr = q_ptr; bank.q_pairs = q_pairs;
-        // the byte masks per pair, as smin_score_pairs gathers them: P * (T + Nq + L + L * L) bytes
-        Tensor vm = video_mask.index_select(0, bank.vi), qm = query_mask.index_select(0, bank.qi), lm = length_mask.index_select(0, bank.vi),
-               mm = moment_mask.index_select(0, bank.vi);
-        CoreState st;
-        std::vector<Tensor> all, cmaps, bmaps;
-        const int64_t N = SminCore::run(st, all, cmaps, bmaps, false, video_features, vm, query_features, qm, lm, mm, T, L, C, nl, maxq, H, flags, n_known, prm_in, &bank);
-        SminCore::save_state(ctx, st, all, {N, T, L, C, nl, flags, H, query_features.size(1)});
-        return {st.pm, st.psea[0], st.psea[1], st.psea[2]};
-    }
-    static variable_list backward(AutogradContext* ctx, variable_list g) { return SminCore::backward_from(ctx, g, N_FIXED); }
 };
 
 // ---------------------------------------------------------------- the model
@@ -1373,34 +1382,53 @@ Tensor padded_query_mask(const char* op, const Tensor& query_features, const Ten
     return query_mask;
 }
 
+// What the four operators over the core share: the device check (`inputs`: every tensor that has to be on the device; the first names
+// it), the parameter count, the device guard, the query mask padded to max_query_length, the pairs' masks gathered (call.bank: the
+// masks arrive with a row per video / per query), and the run itself -- forward only (call.scoring), else as the node.
+variable_list run_call(const char* op, std::initializer_list<const Tensor*> inputs, CoreCall call, const Tensor& video_features, const Tensor& query_features,
+                       at::TensorList prm)
+{
+    for (const Tensor* t : inputs) TORCH_CHECK(t->is_cuda(), op, " runs on a HIP device only (there is no CPU fallback)");
+    TORCH_CHECK((int64_t)prm.size() == ParamList::expected(call.nl), op, ": expected ", ParamList::expected(call.nl), " parameters, got ", prm.size());
+    c10::hip::HIPGuard device_guard((*inputs.begin())->device().index());
+    c10::AutoGradMode grad_mode(!call.scoring && c10::GradMode::is_enabled());
+    if (query_features.defined()) call.query_mask = padded_query_mask(op, query_features, call.query_mask, call.maxq);
+    if (call.bank) {
+        PairBank& bank = *call.bank;
+        if (bank.train) { bank.vmask_v = call.video_mask; bank.qmask_q = call.query_mask; }
+        // the byte masks per pair: P * (T + Nq + L + L * L) bytes
+        call.video_mask = call.video_mask.index_select(0, bank.vi); call.query_mask = call.query_mask.index_select(0, bank.qi);
+        call.length_mask = call.length_mask.index_select(0, bank.vi); call.moment_mask = call.moment_mask.index_select(0, bank.vi);
+    }
+    if (!call.scoring) return SminCore::apply(video_features, query_features, call, prm);
+    CoreState st;
+    SminCore::run(st, call, video_features, query_features, prm);
+    return {st.pm, st.psea[0], st.psea[1], st.psea[2]};
+}
+using Scores = std::tuple<Tensor, Tensor, Tensor, Tensor>;
+Scores scores(const variable_list& out) { return std::make_tuple(out[0], out[1], out[2], out[3]); }
+
 // SMIN.forward (reference models.py:367-377): the six forward arguments, the parameters in SMIN._native_params order, the model's
 // shape and, by name, SMIN's switches (SMIN._node_options).  attention: None, or every layer's word-attention maps as well (detached):
 // content[k] = ContentAttention.attn_weights (B, L, L, C, Nq) (models.py:207-226) under "dense", or under "packed" the rows [N*C, Nq] of the
 // cell list followed by the cellmap (B, L, L) int32 (what SMIN.localize gathers from); boundary[k] = Attention.attn_weights (B, L, Nq)
 // (models.py:137-154).  Without attention both lists are empty.
 std::tuple<Tensor, Tensor, Tensor, Tensor, std::vector<Tensor>, std::vector<Tensor>> smin_forward(
-    const Tensor& video_features, const Tensor& video_mask, const Tensor& query_features, const Tensor& query_mask_in, const Tensor& length_mask,
+    const Tensor& video_features, const Tensor& video_mask, const Tensor& query_features, const Tensor& query_mask, const Tensor& length_mask,
     const Tensor& moment_mask, at::TensorList prm, int64_t T, int64_t L, int64_t C, int64_t num_smi_layers, int64_t max_query_length, int64_t lstm_hidden_size,
     bool overlap_boundary, bool overlap_prep, bool param_prep_kernel, bool async_weights, bool bf16_operand_storage, bool grad_sync,
     std::optional<int64_t> known_cell_count, bool tail_split, bool input_grads, std::optional<c10::string_view> attention)
 {
-    TORCH_CHECK(video_features.is_cuda(), "smin_forward runs on a HIP device only (there is no CPU fallback)");
-    TORCH_CHECK(input_grads || (!video_features.requires_grad() && !query_features.requires_grad()), "smin_forward forms no gradients of video_features / "
-                "query_features unless input_grads = True (SMIN.input_grads); otherwise inputs that require grad go through the Python host "
-                "(SMIN.fused_core = False)");
+    TORCH_CHECK(input_grads || (!video_features.requires_grad() && !query_features.requires_grad()),
+                "smin_forward forms no gradients of video_features / query_features unless input_grads = True (SMIN.input_grads); otherwise inputs that "
+                "require grad go through the Python host (SMIN.fused_core = False)");
     const bool packed = attention && *attention == "packed";
     TORCH_CHECK(!attention || packed || *attention == "dense", "smin_forward: attention is None, \"dense\" or \"packed\" (got \"", *attention, "\")");
-    const int64_t nl = num_smi_layers, maxq = max_query_length;
-    Tensor query_mask = padded_query_mask("smin_forward", query_features, query_mask_in, maxq);
-    TORCH_CHECK((int64_t)prm.size() == P_LAYER0 + nl * L_COUNT + 8, "smin_forward: expected ", P_LAYER0 + nl * L_COUNT + 8, " parameters, got ", prm.size());
-    c10::hip::HIPGuard device_guard(video_features.device().index());
-    const int64_t flags = (overlap_boundary ? SminCore::F_OVERLAP_BOUNDARY : 0) | (overlap_prep ? SminCore::F_OVERLAP_PREP : 0) |
-                          (param_prep_kernel ? SminCore::F_PARAM_PREP_KERNEL : 0) | (async_weights ? SminCore::F_ASYNC_WEIGHTS : 0) |
-                          (bf16_operand_storage ? SminCore::F_BF16_OPERANDS : 0) | (grad_sync ? SminCore::F_GRAD_SYNC : 0) |
-                          (tail_split ? SminCore::F_TAIL_SPLIT : 0) | (input_grads ? SminCore::F_INPUT_GRADS : 0) |
-                          (attention ? SminCore::F_KEEP_ATTENTION : 0) | (packed ? SminCore::F_ATTN_PACKED : 0);
-    auto out = SminCore::apply(video_features, video_mask, query_features, query_mask, length_mask, moment_mask, T, L, C, nl, maxq, lstm_hidden_size, flags,
-                               known_cell_count.value_or(-1), prm);
+    const int64_t nl = num_smi_layers;
+    const int64_t flags = flag_word(overlap_boundary, overlap_prep, param_prep_kernel, bf16_operand_storage, async_weights, tail_split, grad_sync, input_grads,
+                                    attention.has_value(), packed);
+    CoreCall call{video_mask, query_mask, length_mask, moment_mask, T, L, C, nl, max_query_length, lstm_hidden_size, flags, known_cell_count.value_or(-1)};
+    auto out = run_call("smin_forward", {&video_features}, std::move(call), video_features, query_features, prm);
     const int64_t nc = attention ? nl + (packed ? 1 : 0) : 0, nb = attention ? nl : 0;
     TORCH_CHECK((int64_t)out.size() == 4 + nc + nb, "smin_forward: ", out.size(), " outputs");
     std::vector<Tensor> content(out.begin() + 4, out.begin() + 4 + nc), boundary(out.begin() + 4 + nc, out.end());
@@ -1409,24 +1437,13 @@ std::tuple<Tensor, Tensor, Tensor, Tensor, std::vector<Tensor>, std::vector<Tens
 
 // SMIN.score: the same model forward only, not an autograd node.  The launches of smin_forward in the same order on
 // the same two streams up to the last layer's attention core; then smin_score_tail_fwd.  Outputs as smin_forward's first four.
-std::tuple<Tensor, Tensor, Tensor, Tensor> smin_score(
-    const Tensor& video_features, const Tensor& video_mask, const Tensor& query_features, const Tensor& query_mask_in, const Tensor& length_mask,
-    const Tensor& moment_mask, at::TensorList prm, int64_t T, int64_t L, int64_t C, int64_t num_smi_layers, int64_t max_query_length, int64_t lstm_hidden_size,
-    bool overlap_boundary, bool overlap_prep, bool param_prep_kernel, bool bf16_operand_storage, std::optional<int64_t> known_cell_count)
+Scores smin_score(const Tensor& video_features, const Tensor& video_mask, const Tensor& query_features, const Tensor& query_mask, const Tensor& length_mask,
+                  const Tensor& moment_mask, at::TensorList prm, int64_t T, int64_t L, int64_t C, int64_t num_smi_layers, int64_t max_query_length, int64_t lstm_hidden_size,
+                  bool overlap_boundary, bool overlap_prep, bool param_prep_kernel, bool bf16_operand_storage, std::optional<int64_t> known_cell_count)
 {
-    TORCH_CHECK(video_features.is_cuda(), "smin_score runs on a HIP device only (there is no CPU fallback)");
-    at::NoGradGuard no_grad;
-    const int64_t nl = num_smi_layers;
-    Tensor query_mask = padded_query_mask("smin_score", query_features, query_mask_in, max_query_length);
-    TORCH_CHECK((int64_t)prm.size() == P_LAYER0 + nl * L_COUNT + 8, "smin_score: expected ", P_LAYER0 + nl * L_COUNT + 8, " parameters, got ", prm.size());
-    c10::hip::HIPGuard device_guard(video_features.device().index());
-    const int64_t flags = (overlap_boundary ? SminCore::F_OVERLAP_BOUNDARY : 0) | (overlap_prep ? SminCore::F_OVERLAP_PREP : 0) |
-                          (param_prep_kernel ? SminCore::F_PARAM_PREP_KERNEL : 0) | (bf16_operand_storage ? SminCore::F_BF16_OPERANDS : 0);
-    CoreState st;
-    std::vector<Tensor> all, cmaps, bmaps;
-    SminCore::run(st, all, cmaps, bmaps, true, video_features.detach(), video_mask, query_features.detach(), query_mask, length_mask, moment_mask, T, L, C, nl,
-                  max_query_length, lstm_hidden_size, flags, known_cell_count.value_or(-1), prm);
-    return std::make_tuple(st.pm, st.psea[0], st.psea[1], st.psea[2]);
+    const int64_t flags = flag_word(overlap_boundary, overlap_prep, param_prep_kernel, bf16_operand_storage);
+    CoreCall call{video_mask, query_mask, length_mask, moment_mask, T, L, C, num_smi_layers, max_query_length, lstm_hidden_size, flags, known_cell_count.value_or(-1), true};
+    return scores(run_call("smin_score", {&video_features}, std::move(call), video_features, query_features, prm));
 }
 
 // ---- corpus search (SMIN.encode_videos / encode_queries / score_pairs): the two encoders once per video and per
@@ -1440,16 +1457,15 @@ Tensor smin_encode_videos(const Tensor& video_features, const Tensor& video_mask
     TORCH_CHECK(video_features.dim() == 3 && video_features.scalar_type() == at::kFloat, "smin_encode_videos: video_features float32 (V, T, Din)");
     TORCH_CHECK((int64_t)prm.size() >= P_LSTM, "smin_encode_videos: the parameter list starts with the video encoder's three");
     const int64_t V = video_features.size(0), T = video_features.size(1), Din = video_features.size(2);
-    Tensor W = cont(prm[P_VE_W].detach()), bias = cont(prm[P_VE_B].detach()), pe = cont(prm[P_PE].detach());
+    const ParamList P(prm, P_LSTM, 0);
+    const Tensor &W = P.backbone(P_VE_W), &bias = P.backbone(P_VE_B), &pe = P.backbone(P_PE);
     const int64_t D = W.size(0);
     TORCH_CHECK(W.dim() == 2 && W.size(1) == Din && bias.numel() == D && pe.dim() == 2 && pe.size(1) == D && pe.size(0) >= T && video_mask.numel() == V * T,
                 "smin_encode_videos: shapes of the video encoder's parameters or of video_mask do not fit video_features");
     c10::hip::HIPGuard device_guard(video_features.device().index());
     Tensor vx = cont(video_features.detach());
-    Tensor vm = video_mask.reshape({V * T});
-    Tensor vmaskf = cont(vm.is_floating_point() ? fl(vm) : vm.ne(0).to(at::kFloat));
     Tensor fv = at::empty({V, T, D}, vx.options());
-    SMIN_CK(smin_video_encoder_fwd(cur(), fp(vx), fp(W), fp(bias), fp(pe), fp(vmaskf), nullptr, i32(V), i32(T), i32(Din), i32(D), fpm(fv), nullptr));
+    project_videos(P, vx, video_mask.reshape({V * T}), fv);
     return fv;
 }
 
@@ -1463,27 +1479,20 @@ std::tuple<Tensor, Tensor> smin_encode_queries(const Tensor& query_features, con
     TORCH_CHECK((int64_t)prm.size() >= P_LAYER0, "smin_encode_queries: the parameter list starts with the video encoder's three and the LSTM's sixteen");
     Tensor query_mask = padded_query_mask("smin_encode_queries", query_features, query_mask_in, max_query_length);
     c10::hip::HIPGuard device_guard(query_features.device().index());
-    std::vector<Tensor> all;
-    for (int64_t i = 0; i < P_LAYER0; ++i) all.push_back(cont(prm[i].detach()));
-    Tensor len32 = query_mask.ne(0).sum(1).to(at::kInt).contiguous();
     LstmState lstm[2];
-    auto out = query_encoder(lstm, all, query_features.detach(), len32, max_query_length, lstm_hidden_size, true);
+    auto out = query_encoder(lstm, ParamList(prm, P_LAYER0, 0), query_features.detach(), query_lengths(query_mask), max_query_length, lstm_hidden_size, true);
     return std::make_tuple(out.first, out.second);
 }
 
 // SMIN.score_pairs: smin_score for the P pairs (video_index[p], query_index[p]) of banks fv / fw / fs.  The four byte masks are gathered
 // per pair, smin_step_prologue runs on the gathered masks, smin_pair_assemble stands where smin_score has its backbone, and from
 // "layout, part 2" on it is the code smin_score runs (SminCore::run).  Outputs as smin_score's, one row per pair.
-std::tuple<Tensor, Tensor, Tensor, Tensor> smin_score_pairs(
-    const Tensor& fv, const Tensor& fw, const Tensor& fs, const Tensor& video_mask, const Tensor& query_mask_in, const Tensor& length_mask, const Tensor& moment_mask,
-    const Tensor& video_index, const Tensor& query_index, at::TensorList prm, int64_t T, int64_t L, int64_t C, int64_t num_smi_layers, int64_t max_query_length,
-    int64_t lstm_hidden_size, bool overlap_boundary, bool overlap_prep, bool param_prep_kernel, bool bf16_operand_storage, std::optional<int64_t> known_cell_count)
+Scores smin_score_pairs(const Tensor& fv, const Tensor& fw, const Tensor& fs, const Tensor& video_mask, const Tensor& query_mask_in, const Tensor& length_mask,
+                        const Tensor& moment_mask, const Tensor& video_index, const Tensor& query_index, at::TensorList prm, int64_t T, int64_t L, int64_t C,
+                        int64_t num_smi_layers, int64_t max_query_length, int64_t lstm_hidden_size, bool overlap_boundary, bool overlap_prep, bool param_prep_kernel,
+                        bool bf16_operand_storage, std::optional<int64_t> known_cell_count)
 {
-    for (const Tensor* t : {&fv, &fw, &fs, &video_mask, &query_mask_in, &length_mask, &moment_mask, &video_index, &query_index})
-        TORCH_CHECK(t->is_cuda(), "smin_score_pairs runs on a HIP device only (there is no CPU fallback)");
-    at::NoGradGuard no_grad;
-    const int64_t nl = num_smi_layers, maxq = max_query_length;
-    TORCH_CHECK((int64_t)prm.size() == P_LAYER0 + nl * L_COUNT + 8, "smin_score_pairs: expected ", P_LAYER0 + nl * L_COUNT + 8, " parameters, got ", prm.size());
+    const int64_t maxq = max_query_length;
     TORCH_CHECK(fv.dim() == 3 && fw.dim() == 3 && fs.dim() == 2 && fv.scalar_type() == at::kFloat && fw.scalar_type() == at::kFloat && fs.scalar_type() == at::kFloat,
                 "smin_score_pairs: fv (V, T, D), fw (Q, max_query_length, D), fs (Q, D) float32");
     const int64_t V = fv.size(0), Q = fs.size(0), D = fv.size(2);
@@ -1495,39 +1504,26 @@ std::tuple<Tensor, Tensor, Tensor, Tensor> smin_score_pairs(
                 "smin_score_pairs: video_mask, length_mask and moment_mask have a row per video, query_mask a row per query");
     Tensor query_mask = query_mask_in.reshape({Q, -1});
     TORCH_CHECK(query_mask.size(1) == maxq, "smin_score_pairs: query_mask (Q, max_query_length) as the query bank keeps it");
-    c10::hip::HIPGuard device_guard(fv.device().index());
-    PairBank bank{cont(fv.detach()), cont(fw.detach()), cont(fs.detach()), cont(video_index.to(at::kInt)), cont(query_index.to(at::kInt))};
-    // the byte masks per pair: P * (T + Nq + L + L * L) bytes
-    Tensor vm = video_mask.index_select(0, bank.vi), qm = query_mask.index_select(0, bank.qi), lm = length_mask.index_select(0, bank.vi),
-           mm = moment_mask.index_select(0, bank.vi);
-    const int64_t flags = (overlap_boundary ? SminCore::F_OVERLAP_BOUNDARY : 0) | (overlap_prep ? SminCore::F_OVERLAP_PREP : 0) |
-                          (param_prep_kernel ? SminCore::F_PARAM_PREP_KERNEL : 0) | (bf16_operand_storage ? SminCore::F_BF16_OPERANDS : 0);
-    CoreState st;
-    std::vector<Tensor> all, cmaps, bmaps;
-    SminCore::run(st, all, cmaps, bmaps, true, Tensor(), vm, Tensor(), qm, lm, mm, T, L, C, nl, maxq, lstm_hidden_size, flags, known_cell_count.value_or(-1), prm,
-                  &bank);
-    return std::make_tuple(st.pm, st.psea[0], st.psea[1], st.psea[2]);
+    const int64_t flags = flag_word(overlap_boundary, overlap_prep, param_prep_kernel, bf16_operand_storage);
+    CoreCall call{video_mask, query_mask, length_mask, moment_mask, T, L, C, num_smi_layers, maxq, lstm_hidden_size, flags, known_cell_count.value_or(-1), true};
+    call.bank = PairBank{cont(fv.detach()), cont(fw.detach()), cont(fs.detach()), cont(video_index.to(at::kInt)), cont(query_index.to(at::kInt))};
+    return scores(run_call("smin_score_pairs", {&fv, &fw, &fs, &video_mask, &query_mask_in, &length_mask, &moment_mask, &video_index, &query_index}, std::move(call),
+                           Tensor(), Tensor(), prm));
 }
 
 // SMIN.forward_pairs: smin_forward for the P pairs (video_index[p], query_index[p]) of V videos and Q queries that
-// are each encoded once -- one autograd node, differentiable with respect to the parameters.  video_features (V, T, Din) and the three
+// are each encoded once -- the same autograd node, differentiable with respect to the parameters.  video_features (V, T, Din) and the three
 // video-side masks have a row per video, query_features (Q, words, E) and query_mask a row per query; video_index / query_index (P,)
 // int32 on the device, and the same pairs grouped by video (v_ptr (V + 1,), v_pairs (P,)) and by query (q_ptr (Q + 1,), q_pairs (P,)),
 // each segment in ascending p -- what smin_pair_assemble_bwd sums over.  Outputs as smin_forward's first four, one row per pair.
-// The node has no in-node gradient exchange, forms no input gradients and keeps no attention maps: those options are not in the schema.
-std::tuple<Tensor, Tensor, Tensor, Tensor> smin_forward_pairs(
-    const Tensor& video_features, const Tensor& video_mask, const Tensor& query_features, const Tensor& query_mask_in, const Tensor& length_mask,
-    const Tensor& moment_mask, const Tensor& video_index, const Tensor& query_index, const Tensor& v_ptr, const Tensor& v_pairs, const Tensor& q_ptr,
-    const Tensor& q_pairs, at::TensorList prm, int64_t T, int64_t L, int64_t C, int64_t num_smi_layers, int64_t max_query_length, int64_t lstm_hidden_size,
-    bool overlap_boundary, bool overlap_prep, bool param_prep_kernel, bool async_weights, bool bf16_operand_storage, std::optional<int64_t> known_cell_count,
-    bool tail_split)
+// No in-node gradient exchange, no input gradients and no attention maps here: those options are not in the schema.
+Scores smin_forward_pairs(const Tensor& video_features, const Tensor& video_mask, const Tensor& query_features, const Tensor& query_mask, const Tensor& length_mask,
+                          const Tensor& moment_mask, const Tensor& video_index, const Tensor& query_index, const Tensor& v_ptr, const Tensor& v_pairs, const Tensor& q_ptr,
+                          const Tensor& q_pairs, at::TensorList prm, int64_t T, int64_t L, int64_t C, int64_t num_smi_layers, int64_t max_query_length,
+                          int64_t lstm_hidden_size, bool overlap_boundary, bool overlap_prep, bool param_prep_kernel, bool async_weights, bool bf16_operand_storage,
+                          std::optional<int64_t> known_cell_count, bool tail_split)
 {
-    for (const Tensor* t : {&video_features, &video_mask, &query_features, &query_mask_in, &length_mask, &moment_mask, &video_index, &query_index, &v_ptr, &v_pairs,
-                            &q_ptr, &q_pairs})
-        TORCH_CHECK(t->is_cuda(), "smin_forward_pairs runs on a HIP device only (there is no CPU fallback)");
     TORCH_CHECK(!video_features.requires_grad() && !query_features.requires_grad(), "smin_forward_pairs forms no gradients of video_features / query_features");
-    const int64_t nl = num_smi_layers, maxq = max_query_length;
-    TORCH_CHECK((int64_t)prm.size() == P_LAYER0 + nl * L_COUNT + 8, "smin_forward_pairs: expected ", P_LAYER0 + nl * L_COUNT + 8, " parameters, got ", prm.size());
     TORCH_CHECK(video_features.dim() == 3 && video_features.scalar_type() == at::kFloat && query_features.dim() == 3 && query_features.scalar_type() == at::kFloat,
                 "smin_forward_pairs: video_features (V, T, Din) and query_features (Q, words, E) float32");
     const int64_t V = video_features.size(0), Q = query_features.size(0), P = video_index.numel();
@@ -1538,15 +1534,14 @@ std::tuple<Tensor, Tensor, Tensor, Tensor> smin_forward_pairs(
     auto i32list = [](const Tensor& t, int64_t n) { return t.dim() == 1 && t.size(0) == n && t.scalar_type() == at::kInt; };
     TORCH_CHECK(i32list(video_index, P) && i32list(query_index, P) && i32list(v_ptr, V + 1) && i32list(v_pairs, P) && i32list(q_ptr, Q + 1) && i32list(q_pairs, P),
                 "smin_forward_pairs: video_index, query_index, v_pairs, q_pairs (P,), v_ptr (V + 1,) and q_ptr (Q + 1,) are int32");
-    Tensor query_mask = padded_query_mask("smin_forward_pairs", query_features, query_mask_in, maxq);
-    c10::hip::HIPGuard device_guard(video_features.device().index());
-    const int64_t flags = (overlap_boundary ? SminCore::F_OVERLAP_BOUNDARY : 0) | (overlap_prep ? SminCore::F_OVERLAP_PREP : 0) |
-                          (param_prep_kernel ? SminCore::F_PARAM_PREP_KERNEL : 0) | (async_weights ? SminCore::F_ASYNC_WEIGHTS : 0) |
-                          (bf16_operand_storage ? SminCore::F_BF16_OPERANDS : 0) | (tail_split ? SminCore::F_TAIL_SPLIT : 0);
-    auto out = SminPairCore::apply(video_features, video_mask, query_features, query_mask, length_mask, moment_mask, cont(video_index), cont(query_index), cont(v_ptr),
-                                   cont(v_pairs), cont(q_ptr), cont(q_pairs), T, L, C, nl, maxq, lstm_hidden_size, flags, known_cell_count.value_or(-1), prm);
+    const int64_t flags = flag_word(overlap_boundary, overlap_prep, param_prep_kernel, bf16_operand_storage, async_weights, tail_split);
+    CoreCall call{video_mask, query_mask, length_mask, moment_mask, T, L, C, num_smi_layers, max_query_length, lstm_hidden_size, flags, known_cell_count.value_or(-1)};
+    call.bank = PairBank{Tensor(), Tensor(), Tensor(), cont(video_index), cont(query_index), /*train=*/true, Tensor(), Tensor(), cont(v_ptr), cont(v_pairs), cont(q_ptr),
+                         cont(q_pairs)};
+    auto out = run_call("smin_forward_pairs", {&video_features, &video_mask, &query_features, &query_mask, &length_mask, &moment_mask, &video_index, &query_index, &v_ptr,
+                                               &v_pairs, &q_ptr, &q_pairs}, std::move(call), video_features, query_features, prm);
     TORCH_CHECK(out.size() == 4, "smin_forward_pairs: ", out.size(), " outputs");
-    return std::make_tuple(out[0], out[1], out[2], out[3]);
+    return scores(out);
 }
 
 Tensor smin_loss(const Tensor& pm, const Tensor& ym, const Tensor& sm, const Tensor& moment_mask, const Tensor& ps, const Tensor& ys, const Tensor& ss, const Tensor& pe,

@@ -599,6 +599,10 @@ class SMIN(nn.Module, _Retrieval):
             ps += [m.weight, m.bias]
         return ps
 
+    def _core_args(self):
+        """The positional tail every core operator of csrc/torch_binding.cpp takes behind its tensors: the parameters and the model's shape."""
+        return self._native_params(), self.T, self.L, self.C, len(self.smis), self.max_query_length, self.lstm_hidden_size
+
     @staticmethod
     def _torch_beside_contractions():
         """Whether torch's kernels may run on a second HIP stream beside this library's contractions.
@@ -658,8 +662,7 @@ class SMIN(nn.Module, _Retrieval):
                 return self(video_features, video_mask, query_features, query_mask, length_mask, moment_mask)
             query_mask = query_mask_rows(query_features, query_mask, self.max_query_length)
             return _lib.load_torch().smin_score(
-                video_features, video_mask, query_features, query_mask, length_mask, moment_mask, self._native_params(), self.T, self.L, self.C,
-                len(self.smis), self.max_query_length, self.lstm_hidden_size, **self._score_options())
+                video_features, video_mask, query_features, query_mask, length_mask, moment_mask, *self._core_args(), **self._score_options())
 
     def _record_attention(self, maps):
         for smi, (cmap, bmap) in zip(self.smis, maps):
@@ -694,8 +697,8 @@ class SMIN(nn.Module, _Retrieval):
                                "call does not qualify (see SMIN._plan) -- wrap the model with SMIN_TORCH_DDP=1 instead")
         if plan == "node":
             pm, ps, pe, pa, content, boundary = _lib.load_torch().smin_forward(
-                video_features, video_mask, query_features, query_mask, length_mask, moment_mask, self._native_params(), self.T, self.L, self.C,
-                len(self.smis), self.max_query_length, self.lstm_hidden_size, **self._node_options(None if maps is None else maps.mode))
+                video_features, video_mask, query_features, query_mask, length_mask, moment_mask, *self._core_args(),
+                **self._node_options(None if maps is None else maps.mode))
             if maps is not None:
                 if maps.mode == "packed":
                     maps.cellmap, content = content[-1], content[:-1]

@@ -275,7 +275,7 @@ class _Retrieval:
                 raise ValueError("score_pairs: a bank was encoded while the module was off the one-node path (SMIN._plan); encode it again")
             return _lib.load_torch().smin_score_pairs(
                 videos.fv, queries.fw, queries.fs, videos.video_mask, queries.query_mask, videos.length_mask, videos.moment_mask, vi_d, qi_d,
-                self._native_params(), self.T, self.L, self.C, len(self.smis), self.max_query_length, self.lstm_hidden_size, **self._score_options())
+                *self._core_args(), **self._score_options())
 
     def score_pairs(self, videos, queries, video_index, query_index):
         """(pm, ps, pe, pa) as score() returns them for the P pairs (videos[video_index[p]], queries[query_index[p]]) of a VideoBank
@@ -344,7 +344,7 @@ class _Retrieval:
                 o.pop(refused)
             return _lib.load_torch().smin_forward_pairs(
                 video_features, video_mask, query_features, qm, length_mask, moment_mask, vi_d, qi_d, plan.v_ptr, plan.v_pairs, plan.q_ptr, plan.q_pairs,
-                self._native_params(), self.T, self.L, self.C, len(self.smis), self.max_query_length, self.lstm_hidden_size, **o)
+                *self._core_args(), **o)
 
     def _search_plan(self, what, videos, queries, pairs, k, k_video, max_batch, duration):
         k_video = k if k_video is None else k_video
