@@ -53,7 +53,9 @@ extern "C" {
  * ranked list per query across videos); evaluation of corpus search -- smin_search_merge (ranked lists of disjoint video shards into
  * one list per query) and smin_corpus_meter_update with smin_corpus_meter_ws_bytes (VCMR and VR recall into the epoch meter's kind of
  * accumulator); training through shared banks -- smin_pair_assemble_bwd and smin_pair_assemble_bwd_workspace_bytes (the adjoint of
- * smin_pair_assemble: the pairs' gradients summed onto their videos and queries in a fixed order) */
+ * smin_pair_assemble: the pairs' gradients summed onto their videos and queries in a fixed order); hard-negative mining on the device
+ * -- smin_mine_pairs and smin_mine_pairs_ws_bytes (each query's own video and its highest-scoring wrong ones as the pair lists and both
+ * groupings smin_pair_assemble_bwd reads) */
 #define SMIN_HIP_ABI_VERSION 2
 
 int smin_abi_version(void);
@@ -702,7 +704,7 @@ int smin_row_lists_merge(void* stream, const int32_t* const* ids, const float* c
 
 /* ---- corpus search (csrc/corpus.hip): Q queries against a bank of V videos, each encoded once.
  * smin_pair_assemble has a backward, smin_pair_assemble_bwd below (training through shared banks); the two merges
- * (smin_corpus_topk, smin_search_merge) only rank and have none.
+ * (smin_corpus_topk, smin_search_merge) only rank and have none; smin_mine_pairs picks the pairs to train on.
  *
  * smin_pair_assemble: the backbone's outputs of P (video, query) pairs from the banks, one launch.
  * Inputs.  fv [V][T][D]: the video encoder's projection with position embedding and mask (smin_video_encoder_fwd with fs == NULL);
@@ -790,6 +792,34 @@ int smin_corpus_topk(void* stream, const float* pair_score, const int64_t* pair_
 int smin_search_merge(void* stream, int S, const int64_t* const* video, const int64_t* const* idx, const float* const* score,
                       const int32_t* const* count, const int32_t* k_list, const int64_t* video_offset, int Q, int K,
                       int64_t* out_video, int64_t* out_idx, float* out_score, int32_t* out_count);
+
+/* smin_mine_pairs: the pair plan of hard-negative mining -- for each of Q queries its own video and the N
+ * highest-scoring wrong videos, as smin_pair_assemble's two lists and smin_pair_assemble_bwd's two groupings, formed on the device.
+ * Four launches (select, count, scan, fill), no atomics.  P = Q * (1 + N); pair p = q * (1 + N) + s is slot s of query q.
+ * Inputs.  score [Q][V] fp32: each (query, video) pair's score, expected finite (SMIN.pair_scores: the best fused moment score);
+ *   gt_video [Q] int32 on the device: each query's own video, clamped into [0, V) before it forms an address or a comparison.
+ *   skip: the number of hardest negatives left out (in moment retrieval those are often unlabelled true matches).
+ * Order.  Among the videos v != gt_video[q]: higher score[q][v] first, ties go to the lower v, a score of -0 counts as +0 -- the
+ *   order of smin_corpus_topk, found by the same rounds (one workgroup per query, skip + N block argmaxes of order keys).  With a
+ *   NaN in the row the order is unspecified; the picks stay distinct, within [0, V) and != gt_video[q].
+ * Outputs, all int32, every element written.
+ *   query_index [P]:  query_index[p] = q.
+ *   video_index [P]:  slot 0 = gt_video[q] (the positive pair); slots 1 .. N = the negatives of ranks skip .. skip + N - 1, in rank
+ *     order.  A query's 1 + N videos are distinct.
+ *   q_ptr [Q + 1], q_pairs [P]: the pairs grouped by query: q_ptr[q] = q * (1 + N), q_pairs[p] = p.
+ *   v_ptr [V + 1], v_pairs [P]: the pairs grouped by video, each segment in ascending p; a segment holds at most Q pairs, a video no
+ *     query picked an empty one.  Exactly the arrays a stable sort of video_index gives (bincount, cumsum, argsort).
+ * Limits.  Q >= 1, V >= 2, N >= 1, skip >= 0, skip + N <= 64, skip + N <= V - 1, Q * (1 + N) < 2^31.  The outputs and ws must not
+ *   overlap the inputs or each other.
+ * Workspace.  ws_bytes >= smin_mine_pairs_ws_bytes(Q, V, N), exactly V * 4 (the videos' pair counts between the launches); the
+ *   query returns 0 for Q < 1, V < 2 or N < 1.
+ * Determinism.  The same bits every run: the outputs are a function of score and gt_video alone, placed with plain stores in a
+ *   fixed order (no atomics, no library sort); no host read; capturable.
+ * Rejection.  A nonzero status is returned before any launch, the outputs untouched, for a limit broken, a NULL pointer, or a
+ *   workspace that is too small. */
+size_t smin_mine_pairs_ws_bytes(int Q, int V, int N);
+int smin_mine_pairs(void* stream, const float* score, const int32_t* gt_video, int Q, int V, int N, int skip, int32_t* video_index,
+                    int32_t* query_index, int32_t* v_ptr, int32_t* v_pairs, int32_t* q_ptr, int32_t* q_pairs, void* ws, size_t ws_bytes);
 
 /* ---- stand-alone fp32 MFMA GEMM  C[M][N] = A[M][K] * B[N][K]^T  (used by tests and bench.py's
  * roofline probe; same engine as every contraction above). */

@@ -10,6 +10,10 @@
 //   smin_pair_assemble_bwd  sums the pairs' gradients of f, f_w, f_s back onto the videos and queries they came from, through the
 //                           pairs grouped by video and by query (two CSR lists from the host): no atomics, a fixed order.
 // The two merges have no backward.
+// The training-side counterpart of the search:
+//   smin_mine_pairs         picks, per query, its own video and the N highest-scoring wrong ones -- topk_rounds over a third way of
+//                           reading candidate c, a row of pair scores without the query's own video -- and groups the picked pairs by
+//                           video and by query on the device: the pair plan smin_pair_assemble_bwd reads, with no host in between.
 #include "common.h"
 #include "smin_hip.h"
 
@@ -197,14 +201,13 @@ __device__ __forceinline__ Key block_max_key(Key v, Key* red)
 }
 
 // The K rounds over a source of candidates.  Src::read(c, slot, w, score, video) says whether candidate c < ncand exists and gives
-// its key parts (slot < 64 and w < 2^56: the key's two low fields, lower first); Src::emit(slot, w, ...) copies the picked one out.
+// its key parts (slot < 64 and w < 2^56: the key's two low fields, lower first); Src::emit(r, slot, w) copies the r-th pick out, to
+// wherever the source keeps its result.  Returns the number of picks (< K when the candidates ran out), the same in every thread.
 template <class Src>
-__device__ __forceinline__ void topk_rounds(const Src& src, long long ncand, int K, long long* __restrict__ out_video /* [Q][K] */,
-                                            long long* __restrict__ out_idx /* [Q][K][2] */, float* __restrict__ out_score /* [Q][K] */,
-                                            int* __restrict__ out_count)
+__device__ __forceinline__ int topk_rounds(const Src& src, long long ncand, int K)
 {
     __shared__ Key red[CT / 64];
-    const int b = blockIdx.x, t = threadIdx.x;
+    const int t = threadIdx.x;
     Key cursor; cursor.hi = ~0ull; cursor.lo = ~0ull;
     int nk = 0;
     for (; nk < K; ++nk) {
@@ -222,24 +225,34 @@ __device__ __forceinline__ void topk_rounds(const Src& src, long long ncand, int
         if (t == 0) {
             const long long w = (long long)(0x00ffffffffffffffull - (best.lo & 0x00ffffffffffffffull));
             const int slot = CORPUS_MAX_K - 1 - (int)(best.lo >> 56);
-            const size_t o = (size_t)b * K + nk;
-            src.emit(slot, w, out_video + o, out_idx + 2 * o, out_score + o);
+            src.emit(nk, slot, w);
         }
         __syncthreads();
     }
-    for (int r = nk + t; r < K; r += CT) {
-        const size_t o = (size_t)b * K + r;
-        out_video[o] = -1;
-        out_idx[2 * o] = out_idx[2 * o + 1] = -1;
-        out_score[o] = 0.f;
-    }
-    if (t == 0) out_count[b] = nk;
+    return nk;
 }
+
+// Where the two merges leave query blockIdx.x's ranked list: entry r of K, and the empty slots behind the nk listed ones.
+struct RankedOut {
+    long long* video /* [Q][K] */; long long* idx /* [Q][K][2] */; float* score /* [Q][K] */; int* count /* [Q] */;
+    int K;
+    __device__ __forceinline__ size_t at(int r) const { return (size_t)blockIdx.x * K + r; }
+    __device__ __forceinline__ void finish(int nk) const
+    {
+        for (int r = nk + threadIdx.x; r < K; r += CT) {
+            const size_t o = at(r);
+            video[o] = -1;
+            idx[2 * o] = idx[2 * o + 1] = -1;
+            score[o] = 0.f;
+        }
+        if (threadIdx.x == 0) count[blockIdx.x] = nk;
+    }
+};
 
 // smin_corpus_topk's candidates: c = pair ordinal * kv + slot over the query's pairs g0 .. ; key parts (slot, pair ordinal)
 struct PairLists {
     const float* score; const long long* idx; const int* count; const int* video;
-    long long g0; int kv;
+    long long g0; int kv; RankedOut out;
     __device__ __forceinline__ bool read(long long c, int& slot, long long& w, float& sc, int& vid) const
     {
         w = c / kv;
@@ -250,12 +263,13 @@ struct PairLists {
         vid = video[g];
         return true;
     }
-    __device__ __forceinline__ void emit(int slot, long long w, long long* ov, long long* oi, float* os) const
+    __device__ __forceinline__ void emit(int r, int slot, long long w) const
     {
         const long long g = g0 + w, c = g * kv + slot;
-        *ov = video[g];
-        oi[0] = idx[2 * c]; oi[1] = idx[2 * c + 1];
-        *os = score[c];
+        const size_t o = out.at(r);
+        out.video[o] = video[g];
+        out.idx[2 * o] = idx[2 * c]; out.idx[2 * o + 1] = idx[2 * c + 1];
+        out.score[o] = score[c];
     }
 };
 
@@ -268,8 +282,8 @@ void corpus_topk_kernel(const float* __restrict__ pair_score, const long long* _
     const long long g0 = max(pair_ptr[b], 0);
     const long long g1 = max((long long)pair_ptr[b + 1], g0);
     const bool lists = pair_score && pair_idx && pair_count && pair_video;     // (NULL lists: no query may have a pair, none is read)
-    const PairLists src{pair_score, pair_idx, pair_count, pair_video, g0, kv};
-    topk_rounds(src, lists ? (g1 - g0) * kv : 0, K, out_video, out_idx, out_score, out_count);
+    const PairLists src{pair_score, pair_idx, pair_count, pair_video, g0, kv, {out_video, out_idx, out_score, out_count, K}};
+    src.out.finish(topk_rounds(src, lists ? (g1 - g0) * kv : 0, K));
 }
 
 // smin_search_merge's candidates: S ranked lists of k[s] slots per query, c = base[s] + p (base: the exclusive prefix of k); key
@@ -281,7 +295,7 @@ struct RankedTables {
     int k[MERGE_MAX_S], base[MERGE_MAX_S + 1], S;
 };
 struct RankedLists {
-    const RankedTables& tb; long long q;
+    const RankedTables& tb; long long q; RankedOut out;
     __device__ __forceinline__ bool read(long long c, int& slot, long long& w, float& sc, int& vid) const
     {
         int s = 0;
@@ -293,12 +307,13 @@ struct RankedLists {
         vid = (int)(tb.video[s][q * ks + p] + tb.offset[s]);     // the key's field: global ids lie in [0, 2^31)
         return true;
     }
-    __device__ __forceinline__ void emit(int s, long long p, long long* ov, long long* oi, float* os) const
+    __device__ __forceinline__ void emit(int r, int s, long long p) const
     {
         const long long c = q * tb.k[s] + p;
-        *ov = tb.video[s][c] + tb.offset[s];
-        oi[0] = tb.idx[s][2 * c]; oi[1] = tb.idx[s][2 * c + 1];
-        *os = tb.score[s][c];
+        const size_t o = out.at(r);
+        out.video[o] = tb.video[s][c] + tb.offset[s];
+        out.idx[2 * o] = tb.idx[s][2 * c]; out.idx[2 * o + 1] = tb.idx[s][2 * c + 1];
+        out.score[o] = tb.score[s][c];
     }
 };
 
@@ -306,8 +321,140 @@ __global__ __launch_bounds__(CT)
 void search_merge_kernel(const RankedTables tb, int K, long long* __restrict__ out_video, long long* __restrict__ out_idx,
                          float* __restrict__ out_score, int* __restrict__ out_count)
 {
-    const RankedLists src{tb, (long long)blockIdx.x};
-    topk_rounds(src, tb.base[tb.S], K, out_video, out_idx, out_score, out_count);
+    const RankedLists src{tb, (long long)blockIdx.x, {out_video, out_idx, out_score, out_count, K}};
+    src.out.finish(topk_rounds(src, tb.base[tb.S], K));
+}
+
+// ---- hard-negative mining (smin_mine_pairs).  Query q owns the pairs q * S .. q * S + S - 1, S = 1 + N: slot 0 its own video, slots
+// 1 .. N the negatives of ranks skip .. skip + N - 1.  smin_mine_pairs' candidates: c = video over row q of the pair scores, the
+// query's own video left out; key parts (slot 0, w = the video, which emit reads back as its pick).
+struct ScoreRow {
+    const float* row /* [V] */; int gt, skip; int* picks /* the query's S entries of video_index */;
+    __device__ __forceinline__ bool read(long long c, int& slot, long long& w, float& sc, int& vid) const
+    {
+        if ((int)c == gt) return false;
+        slot = 0; w = c;
+        sc = row[c];
+        vid = (int)c;
+        return true;
+    }
+    __device__ __forceinline__ void emit(int r, int, long long w) const
+    {
+        if (r >= skip) picks[1 + r - skip] = (int)w;
+    }
+};
+
+// One workgroup per query: the lists and the grouping by query, which is the identity.  Every candidate has a nonzero key below the
+// first cursor and skip + N <= V - 1, so the rounds never run dry and all N negatives are written.
+__global__ __launch_bounds__(CT)
+void mine_select_kernel(const float* __restrict__ score, const int* __restrict__ gt_video, int Q, int V, int N, int skip,
+                        int* __restrict__ video_index, int* __restrict__ query_index, int* __restrict__ q_ptr, int* __restrict__ q_pairs)
+{
+    const int q = blockIdx.x, S = 1 + N, t = threadIdx.x;
+    const int gt = min(max(gt_video[q], 0), V - 1);
+    const ScoreRow src{score + (size_t)q * V, gt, skip, video_index + (size_t)q * S};
+    topk_rounds(src, V, skip + N);
+    for (int s = t; s < S; s += CT) {
+        const int p = q * S + s;
+        query_index[p] = q;
+        q_pairs[p] = p;
+    }
+    if (t == 0) {
+        video_index[(size_t)q * S] = gt;
+        q_ptr[q] = q * S;
+        if (q == Q - 1) q_ptr[Q] = Q * S;
+    }
+}
+
+// The pair of query q that names video v, or -1: a query's S picks are distinct videos, so there is at most one.
+__device__ __forceinline__ int pair_of(const int* __restrict__ video_index, int q, int S, int v)
+{
+    int p = -1;
+    for (int s = 0; s < S; ++s) if (video_index[(size_t)q * S + s] == v) p = q * S + s;
+    return p;
+}
+
+__device__ __forceinline__ int block_sum(int v, int* red /* [CT / 64] */)
+{
+    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    int s = 0;
+#pragma unroll
+    for (int w = 0; w < CT / 64; ++w) s += red[w];
+    return s;
+}
+
+// One workgroup per video: the number of pairs that name it.
+__global__ __launch_bounds__(CT)
+void mine_count_kernel(const int* __restrict__ video_index, int Q, int S, int* __restrict__ counts /* [V] */)
+{
+    __shared__ int red[CT / 64];
+    const int v = blockIdx.x;
+    int n = 0;
+    for (int q = threadIdx.x; q < Q; q += CT) n += pair_of(video_index, q, S, v) >= 0;
+    n = block_sum(n, red);
+    if (threadIdx.x == 0) counts[v] = n;
+}
+
+// One workgroup: v_ptr = the exclusive prefix of the counts, CT videos at a time in ascending v (integer sums: any order gives the
+// same bits; this one needs a single pass).
+__global__ __launch_bounds__(CT)
+void mine_scan_kernel(const int* __restrict__ counts, int V, int* __restrict__ v_ptr /* [V + 1] */)
+{
+    __shared__ int wave_sum[CT / 64];
+    const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
+    int base = 0;
+    for (int v0 = 0; v0 < V; v0 += CT) {
+        const int v = v0 + t;
+        const int c = v < V ? counts[v] : 0;
+        int incl = c;
+        for (int o = 1; o < 64; o <<= 1) {
+            const int x = __shfl_up(incl, o);
+            if (lane >= o) incl += x;
+        }
+        __syncthreads();                                         // (the previous chunk's reads of wave_sum are done)
+        if (lane == 63) wave_sum[wv] = incl;
+        __syncthreads();
+        int before = 0, total = 0;
+#pragma unroll
+        for (int w = 0; w < CT / 64; ++w) {
+            if (w < wv) before += wave_sum[w];
+            total += wave_sum[w];
+        }
+        if (v < V) v_ptr[v] = base + before + incl - c;
+        base += total;
+    }
+    if (t == 0) v_ptr[V] = base;
+}
+
+// One workgroup per video: its pairs in ascending p, which is ascending q -- CT queries at a time, each chunk's pairs placed by a
+// ballot prefix within the wave and the waves' totals in order.  Plain stores, no atomics: the same bits every run.
+__global__ __launch_bounds__(CT)
+void mine_fill_kernel(const int* __restrict__ video_index, const int* __restrict__ v_ptr, int Q, int S, int* __restrict__ v_pairs /* [P] */)
+{
+    __shared__ int wave_sum[CT / 64];
+    const int v = blockIdx.x, t = threadIdx.x, lane = t & 63, wv = t >> 6;
+    const long long P = (long long)Q * S;
+    long long base = v_ptr[v];
+    for (int q0 = 0; q0 < Q; q0 += CT) {
+        const int q = q0 + t;
+        const int p = q < Q ? pair_of(video_index, q, S, v) : -1;
+        const u64 hits = __ballot(p >= 0);
+        __syncthreads();
+        if (lane == 0) wave_sum[wv] = __popcll(hits);
+        __syncthreads();
+        int before = 0, total = 0;
+#pragma unroll
+        for (int w = 0; w < CT / 64; ++w) {
+            if (w < wv) before += wave_sum[w];
+            total += wave_sum[w];
+        }
+        const long long o = base + before + __popcll(hits & ((1ull << lane) - 1ull));
+        if (p >= 0 && o >= 0 && o < P) v_pairs[o] = p;
+        base += total;
+    }
 }
 
 }  // namespace
@@ -400,6 +547,33 @@ extern "C" int smin_search_merge(void* stream, int S, const int64_t* const* vide
     }
     hipLaunchKernelGGL(search_merge_kernel, dim3(Q), dim3(CT), 0, (hipStream_t)stream, tb, K, (long long*)out_video, (long long*)out_idx, out_score,
                        out_count);
+    SMIN_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" size_t smin_mine_pairs_ws_bytes(int Q, int V, int N)
+{
+    if (Q < 1 || V < 2 || N < 1) return 0;
+    return (size_t)V * sizeof(int);                              // the videos' pair counts
+}
+
+extern "C" int smin_mine_pairs(void* stream, const float* score, const int32_t* gt_video, int Q, int V, int N, int skip, int32_t* video_index,
+                               int32_t* query_index, int32_t* v_ptr, int32_t* v_pairs, int32_t* q_ptr, int32_t* q_pairs, void* ws, size_t ws_bytes)
+{
+    SMIN_REQUIRE(Q >= 1 && V >= 2 && N >= 1 && skip >= 0 && skip <= CORPUS_MAX_K && N <= CORPUS_MAX_K);
+    SMIN_REQUIRE(skip + N <= CORPUS_MAX_K && skip + N <= V - 1 && (long long)Q * (1 + N) < 0x80000000ll);
+    SMIN_REQUIRE(score != nullptr && gt_video != nullptr && video_index != nullptr && query_index != nullptr);
+    SMIN_REQUIRE(v_ptr != nullptr && v_pairs != nullptr && q_ptr != nullptr && q_pairs != nullptr);
+    SMIN_REQUIRE(ws != nullptr && ws_bytes >= smin_mine_pairs_ws_bytes(Q, V, N));
+    const hipStream_t st = (hipStream_t)stream;
+    int* counts = static_cast<int*>(ws);
+    hipLaunchKernelGGL(mine_select_kernel, dim3(Q), dim3(CT), 0, st, score, gt_video, Q, V, N, skip, video_index, query_index, q_ptr, q_pairs);
+    SMIN_LAUNCH_CHECK();
+    hipLaunchKernelGGL(mine_count_kernel, dim3(V), dim3(CT), 0, st, video_index, Q, 1 + N, counts);
+    SMIN_LAUNCH_CHECK();
+    hipLaunchKernelGGL(mine_scan_kernel, dim3(1), dim3(CT), 0, st, counts, V, v_ptr);
+    SMIN_LAUNCH_CHECK();
+    hipLaunchKernelGGL(mine_fill_kernel, dim3(V), dim3(CT), 0, st, video_index, v_ptr, Q, 1 + N, v_pairs);
     SMIN_LAUNCH_CHECK();
     return 0;
 }

@@ -19,9 +19,10 @@ Semantics (csrc/moments.hip, include/smin_hip.h), for each sample b:
 the tests compare against -- nothing routes to it silently."""
 import ctypes
 
+import numpy as np
 import torch
 
-from ._host import _require_hip, byte_mask
+from ._host import _require_hip, byte_mask, host_array, require_ints
 from ._lib import SminHipError, call, load, ptr, stream
 
 MAX_K = 64
@@ -467,6 +468,82 @@ def corpus_topk_torch(pair_score, pair_idx, pair_count, pair_video, pair_ptr, k=
             out_score[q, :n] = score.reshape(-1)[flat]
         count[q] = n
     return {"video": video, "idx": idx, "score": out_score, "count": count}
+
+
+# ---------------------------------------------------------------- hard-negative mining (SMIN.mine_pairs)
+def _mine_check(what, score, gt_video, negatives, skip):
+    if score.dim() != 2:
+        raise ValueError(f"{what}: score must be (Q, V), got {tuple(score.shape)}")
+    Q, V = score.shape
+    gt = host_array(gt_video)
+    if gt.shape[0] != Q:
+        raise ValueError(f"{what}: gt_video must name a video for each of the Q = {Q} queries of score (Q, V) = {tuple(score.shape)} (got {gt.shape[0]})")
+    if Q < 1 or V < 2:
+        raise ValueError(f"{what}: needs Q >= 1 queries and V >= 2 videos (score is {tuple(score.shape)})")
+    if gt.min() < 0 or gt.max() >= V:
+        raise ValueError(f"{what}: gt_video must lie in [0, {V})")
+    require_ints(what, ("negatives", negatives, 1, MAX_K), ("skip", skip, 0, MAX_K))
+    if skip + negatives > MAX_K or skip + negatives > V - 1:
+        raise ValueError(f"{what}: skip + negatives = {skip + negatives} must not exceed {MAX_K} nor the V - 1 = {V - 1} wrong videos of a query")
+    if Q * (1 + negatives) >= 2 ** 31:
+        raise ValueError(f"{what}: {Q * (1 + negatives)} pairs exceed the int32 lists")
+    return Q, V, gt
+
+
+def mine_pairs(score, gt_video, negatives, skip=0):
+    """The pair plan of hard-negative mining, built on the device (include/smin_hip.h, smin_mine_pairs): for each query its own
+    video and its ``negatives`` highest-scoring wrong videos after the ``skip`` hardest (often unlabelled true matches).
+
+    ``score (Q, V)`` fp32 HIP tensor: each (query, video) pair's score (SMIN.pair_scores); ``gt_video``: Q host ints in [0, V).
+    Order among the videos v != gt_video[q]: higher score first, ties -> lower v, -0 counts as +0 (corpus_topk's order).  Limits:
+    negatives >= 1, skip >= 0, skip + negatives <= min(64, V - 1).  Returns a retrieval.PairPlan of P = Q * (1 + negatives) pairs
+    whose lists and groupings were formed by the kernels (``PairPlan.from_device``: its host lists ``vi`` / ``qi`` are None): pair
+    q * (1 + negatives) is query q's positive, the next ``negatives`` its negatives in rank order.  gt_video and the positive flags
+    (host arithmetic: the layout is fixed) travel in one pinned asynchronous copy; one call into the library; no host read."""
+    _require_hip(score, "mine_pairs")
+    Q, V, gt = _mine_check("mine_pairs", score, gt_video, negatives, skip)
+    from .retrieval import PairPlan
+    N, dev = int(negatives), score.device
+    S, P = 1 + N, Q * (1 + N)
+    rows = np.arange(Q, dtype=np.int64) * S
+    host = torch.from_numpy(np.concatenate([gt, np.arange(P) % S == 0, rows]).astype(np.int32))
+    sc = score.detach().float().contiguous()
+    with torch.cuda.device(dev):
+        buf = host.pin_memory().to(dev, non_blocking=True)
+        out = torch.empty((4 * P + V + Q + 2,), dtype=torch.int32, device=dev)
+        cut = np.cumsum([0, P, P, V + 1, P, Q + 1, P])
+        lists = [out[cut[k]:cut[k + 1]] for k in range(6)]
+        nbytes = load().smin_mine_pairs_ws_bytes(Q, V, N)
+        ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+        call("smin_mine_pairs", stream(), ptr(sc), ptr(buf[:Q]), Q, V, N, int(skip), *[ptr(a) for a in lists], ptr(ws), nbytes)
+        return PairPlan.from_device(*lists, V, Q, positive=buf[Q:Q + P], positive_rows=buf[Q + P:].to(torch.int64), num_positive=Q)
+
+
+def mine_pairs_torch(score, gt_video, negatives, skip=0):
+    """``mine_pairs`` as plain torch + Python on any device (same result, bit for bit): each query's wrong videos sorted by
+    (score, video), then the pairs sorted by (video, pair).  Returns the six int32 arrays ``(video_index, query_index, v_ptr,
+    v_pairs, q_ptr, q_pairs)`` on ``score``'s device."""
+    Q, V, gt = _mine_check("mine_pairs_torch", score, gt_video, negatives, skip)
+    N, S = int(negatives), 1 + int(negatives)
+    sc = score.detach().float()
+    sc = torch.where(sc == 0, torch.zeros_like(sc), sc)                                          # -0 -> +0
+    u = sc.contiguous().view(torch.int32).to(torch.int64) & 0xFFFFFFFF
+    o = torch.where(u >= 0x80000000, u ^ 0xFFFFFFFF, u | 0x80000000).clamp_min(1).tolist()      # the order word of top_moments_torch
+    vi, qi = [], []
+    for q in range(Q):
+        g = int(gt[q])
+        ranked = sorted((-o[q][v], v) for v in range(V) if v != g)
+        vi += [g] + [v for _, v in ranked[skip:skip + N]]
+        qi += [q] * S
+    P = Q * S
+    v_pairs = sorted(range(P), key=lambda p: (vi[p], p))
+    v_ptr = [0] * (V + 1)
+    for v in vi:
+        v_ptr[v + 1] += 1
+    for v in range(V):
+        v_ptr[v + 1] += v_ptr[v]
+    arrays = (vi, qi, v_ptr, v_pairs, [q * S for q in range(Q + 1)], list(range(P)))
+    return tuple(torch.tensor(a, dtype=torch.int32, device=score.device) for a in arrays)
 
 
 def search_times(video, idx, duration, L):

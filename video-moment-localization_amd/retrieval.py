@@ -10,7 +10,7 @@ from . import _lib
 from ._host import _AttnMaps, byte_mask, host_array, known_cells, query_mask_rows, require_hip_tensors, require_ints
 from .feeder import build_masks_hip, cell_count
 from .functional import attn_maps_gather
-from .moments import MAX_K, _top_moments_into, corpus_topk, corpus_topk_torch, merge_window_moments, search_times, top_moments
+from .moments import MAX_K, _top_moments_into, corpus_topk, corpus_topk_torch, merge_window_moments, mine_pairs, search_times, top_moments
 from .sampling import MAX_ROWS, MODES, sample_windows, window_plan
 
 
@@ -55,7 +55,10 @@ class PairPlan:
     same pairs grouped by video -- ``v_ptr (V + 1,)``, ``v_pairs (P,)`` -- and by query -- ``q_ptr (Q + 1,)``, ``q_pairs (P,)`` --,
     each segment in ascending p (smin_pair_assemble_bwd sums in that order).  With ``gt_video`` (Q host ints, each query's own video)
     also ``positive (P,)`` int32, 1 where ``video_index[p] == gt_video[query_index[p]]``, and ``positive_rows``, the ordinals of
-    those pairs (int64).  Everything is formed on the host and travels in ONE pinned asynchronous copy (a plain copy on the CPU)."""
+    those pairs (int64).  Everything is formed on the host and travels in ONE pinned asynchronous copy (a plain copy on the CPU).
+
+    ``PairPlan.from_device`` wraps the same arrays where the device formed them (moments.mine_pairs): there are no host lists then,
+    ``vi`` and ``qi`` are None, and nothing that takes a plan may read them."""
 
     def __init__(self, video_index, query_index, V, Q, device, gt_video=None, what="pair_plan"):
         vi, qi = host_array(video_index), host_array(query_index)
@@ -86,6 +89,21 @@ class PairPlan:
         self.video_index, self.query_index, self.v_ptr, self.v_pairs, self.q_ptr, self.q_pairs = cuts[:6]
         self.positive, self.positive_rows = (cuts[6], cuts[7].to(torch.int64)) if rows is not None else (None, None)
         self.num_positive = None if rows is None else int(rows.shape[0])
+
+    @classmethod
+    def from_device(cls, video_index, query_index, v_ptr, v_pairs, q_ptr, q_pairs, V, Q, positive=None, positive_rows=None, num_positive=None):
+        """A plan over int32 arrays that are on their device already (smin_mine_pairs' outputs): nothing is copied, checked against
+        the ranges or read back.  ``positive (P,)`` int32, ``positive_rows`` int64 and ``num_positive`` (a host int) as the
+        constructor forms them from gt_video, where the caller knows them (pair_targets and train_epoch_pairs need them)."""
+        P = video_index.shape[0]
+        if P < 1 or any(tuple(a.shape) != (n,) for a, n in ((query_index, P), (v_pairs, P), (q_pairs, P), (v_ptr, V + 1), (q_ptr, Q + 1))):
+            raise ValueError(f"PairPlan.from_device: four (P,) arrays with P >= 1, v_ptr (V + 1,) = ({V + 1},) and q_ptr (Q + 1,) = ({Q + 1},)")
+        self = cls.__new__(cls)
+        self.vi = self.qi = None
+        self.V, self.Q, self.P, self.device = V, Q, P, video_index.device
+        self.video_index, self.query_index, self.v_ptr, self.v_pairs, self.q_ptr, self.q_pairs = video_index, query_index, v_ptr, v_pairs, q_ptr, q_pairs
+        self.positive, self.positive_rows, self.num_positive = positive, positive_rows, num_positive
+        return self
 
     def fits(self, V, Q, device):
         return self.V == V and self.Q == Q and self.device == torch.device(device)
@@ -214,10 +232,11 @@ class _Retrieval:
         """Whether pairs of these inputs score on the one-node path from banks (as score(): _plan == "node" and no keep_attention)."""
         return not self.keep_attention and self._plan(video_features, query_features) == "node"
 
-    def encode_videos(self, video_features, video_mask, length_mask, moment_mask):
+    def encode_videos(self, video_features, video_mask, length_mask, moment_mask, cell_counts=None):
         """A VideoBank of V videos: the projection with position embedding and mask runs once per video (smin_hip::smin_encode_videos),
         not once per (video, query) pair.  ``video_features (V, T, Din)`` and the three masks as forward takes them.  One host read
-        (the videos' valid-cell counts); under torch.no_grad().  The bank is stale after a parameter update."""
+        (the videos' valid-cell counts), none with ``cell_counts``, the V counts as host ints (feeder.cell_count); under
+        torch.no_grad().  The bank is stale after a parameter update."""
         require_hip_tensors("encode_videos", dict(video_features=video_features, video_mask=video_mask, length_mask=length_mask, moment_mask=moment_mask))
         V = video_features.shape[0]
         if video_features.dim() != 3 or V < 1 or video_mask.shape[0] != V or tuple(length_mask.shape) != (V, self.L) or tuple(moment_mask.shape) != (V, self.L, self.L):
@@ -229,7 +248,12 @@ class _Retrieval:
             fv = None
             if self.fused_core and self.backbone.videoencoder.fused(vf) and vf.shape[1] == self.T:
                 fv = _lib.load_torch().smin_encode_videos(vf, masks[0], self._native_params()[:3])
-            counts = masks[2].reshape(V, -1).ne(0).sum(dim=1).tolist()             # the bank's only host read
+            if cell_counts is None:
+                counts = masks[2].reshape(V, -1).ne(0).sum(dim=1).tolist()         # the bank's only host read
+            else:
+                counts = host_array(cell_counts)
+                if counts.shape[0] != V:
+                    raise ValueError(f"encode_videos: cell_counts must hold the V = {V} videos' counts (got {counts.shape[0]})")
         return VideoBank(fv, vf, masks[0], masks[1], masks[2], counts)
 
     def encode_queries(self, query_features, query_mask):
@@ -304,7 +328,10 @@ class _Retrieval:
         index out of range or an empty list raises ValueError.  ``cell_counts``: the V videos' valid-cell counts as host ints
         (feeder.cell_count); with them the pairs' count is host arithmetic and the step reads nothing back, without them the node
         reads the count once, as forward does.  ``plan``: a PairPlan already built from these lists (training.train_epoch_pairs
-        shares one with pair_targets: one copy for both).
+        shares one with pair_targets: one copy for both).  A device-built plan (SMIN.mine_pairs; ``plan.vi is None``) has no host list
+        to sum the counts over: with ``cell_counts`` whose V entries are all one value c -- the common case, every longer video is
+        resampled to T -- the pairs' count is P * c and the step reads nothing back; with unequal counts, or none, no
+        count is handed over and the node reads it once.
 
         On the one-node path this is smin_hip::smin_forward_pairs, one autograd node: smin_pair_assemble where smin_forward has the
         product f = f_v * f_s, the layers at batch P, and in the backward smin_pair_assemble_bwd -- a sum over the pairs that share a
@@ -329,7 +356,10 @@ class _Retrieval:
             cc = host_array(cell_counts)
             if cc.shape[0] != V:
                 raise ValueError(f"forward_pairs: cell_counts must hold the V = {V} videos' counts (got {cc.shape[0]})")
-            cells = int(cc[plan.vi].sum())
+            if plan.vi is not None:
+                cells = int(cc[plan.vi].sum())
+            elif (cc == cc[0]).all():
+                cells = plan.P * int(cc[0])
         vi_d, qi_d = plan.video_index, plan.query_index
         with known_cells(self, cells), torch.cuda.device(video_features.device):
             if not self._bank_plan(video_features, query_features):
@@ -395,14 +425,39 @@ class _Retrieval:
         # the whole plan in one pinned buffer, one asynchronous copy (the call never waits for the device)
         plan = torch.from_numpy(np.concatenate([vi, qi, pair_ptr]).astype(np.int32)).pin_memory().to(dev, non_blocking=True)
         vi_d, qi_d, pp_d = plan[:P], plan[P:2 * P], plan[2 * P:]
-        idx, score, count, chunks = _chunk_buffers(P, k_video, max_batch, dev)
         with torch.no_grad(), torch.cuda.device(dev):
-            for c0, c1 in chunks:
-                pm, ps, pe, _ = self._score_pairs(videos, queries, vi[c0:c1], qi[c0:c1], vi_d[c0:c1], qi_d[c0:c1])
-                mm = videos.moment_mask.index_select(0, vi_d[c0:c1])
-                _top_moments_into(pm, ps, pe, mm, k_video, nms_thresh, idx[c0:c1], score[c0:c1], count[c0:c1])
+            idx, score, count = self._pair_moments(videos, queries, vi, qi, vi_d, qi_d, k_video, nms_thresh, max_batch)
             r = corpus_topk(score, idx, count, vi_d, pp_d, k=k)
         return self._search_result(r, duration, L)
+
+    def _pair_moments(self, videos, queries, vi, qi, vi_d, qi_d, k_video, nms_thresh, max_batch):
+        """search's chunk loop: top_moments' ``idx (P, k_video, 2)``, ``score (P, k_video)`` and ``count (P,)`` of the P pairs of the
+        checked host lists vi / qi (int32 device copies vi_d / qi_d), scored in chunks of at most ``max_batch``.  No host read."""
+        idx, score, count, chunks = _chunk_buffers(vi.shape[0], k_video, max_batch, vi_d.device)
+        for c0, c1 in chunks:
+            pm, ps, pe, _ = self._score_pairs(videos, queries, vi[c0:c1], qi[c0:c1], vi_d[c0:c1], qi_d[c0:c1])
+            mm = videos.moment_mask.index_select(0, vi_d[c0:c1])
+            _top_moments_into(pm, ps, pe, mm, k_video, nms_thresh, idx[c0:c1], score[c0:c1], count[c0:c1])
+        return idx, score, count
+
+    # ---------------------------------------------------------------- hard-negative mining (INTEGRATION.md 3p)
+    def pair_scores(self, videos, queries, max_batch=64):
+        """``(Q, V)`` float32: the best fused moment score of every (query, video) pair of a QueryBank and a VideoBank -- search's chunk
+        loop over all pairs at one moment per pair, so the bits of ``top_moments(*score_pairs(all pairs)[:3], moment_mask, k=1)``'s
+        slot 0; 0 for a pair without a valid cell.  Under torch.no_grad(); no host read."""
+        _, _, vi, qi, _ = self._search_plan("pair_scores", videos, queries, None, 1, 1, max_batch, None)
+        dev = videos.video_features.device
+        with torch.no_grad(), torch.cuda.device(dev):
+            vi_d, qi_d = torch.from_numpy(np.concatenate([vi, qi]).astype(np.int32)).pin_memory().to(dev, non_blocking=True).split(vi.shape[0])
+            _, score, _ = self._pair_moments(videos, queries, vi, qi, vi_d, qi_d, 1, 1.0, max_batch)   # (an empty slot's score is 0)
+        return score.reshape(len(queries), len(videos))
+
+    def mine_pairs(self, videos, queries, gt_video, negatives, skip=0, max_batch=64):
+        """The pairs to train on, chosen by the model: for each query of the QueryBank its own video ``gt_video[q]`` (Q host ints) and
+        the ``negatives`` wrong videos of the VideoBank it scores highest after the ``skip`` hardest -- ``pair_scores``, then
+        moments.mine_pairs.  Returns a device-built PairPlan of Q * (1 + negatives) pairs for ``forward_pairs(plan=...)`` and
+        training.pair_targets.  The banks are a snapshot of the parameters, and so is the choice.  No host read."""
+        return mine_pairs(self.pair_scores(videos, queries, max_batch), gt_video, negatives, skip)
 
     def search_torch(self, videos, queries, pairs=None, k=5, k_video=None, nms_thresh=0.5, duration=None, max_batch=64, scorer=None):
         """``search`` restated: the same plan and chunking, each chunk's pairs expanded and scored by score(), cut by top_moments and

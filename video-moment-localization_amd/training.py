@@ -253,33 +253,67 @@ def pair_targets(video_masks, query_targets, video_index, query_index, gt_video,
     return out
 
 
+def _pair_step(model, optimizer, g, plan, meter):
+    """One step of train_epoch_pairs on group ``g`` through ``plan`` (built with its positive flags): forward_pairs, pair_targets,
+    loss_fn over all the pairs, the meter over the positive ones, backward, optimizer.step.  No host read with ``cell_counts``."""
+    optimizer.zero_grad()
+    out = model.forward_pairs(*_inputs(g), None, None, cell_counts=g.get("cell_counts"), plan=plan)
+    tg = pair_targets(g, g, None, None, None, plan=plan)
+    loss = _loss_of(out, tg)
+    rows = plan.positive_rows
+    meter.update(out[0].detach().index_select(0, rows), out[1].detach().index_select(0, rows), out[2].detach().index_select(0, rows),
+                 tg["moment_mask"].index_select(0, rows), tg["sm"].index_select(0, rows), loss=loss.detach())
+    loss.backward()
+    optimizer.step()
+
+
 def train_epoch_pairs(model, optimizer, groups, meter=None):
     """train_epoch over groups of V videos and Q queries that share their encoders (SMIN.forward_pairs).  A group
     is a dict with ``video_features``, ``video_mask``, ``length_mask``, ``moment_mask`` (a row per video), ``query_features``,
     ``query_mask`` and LOSS_TARGETS (a row per query, against its own video), the host lists ``video_index``, ``query_index`` (the
-    pairs) and ``gt_video`` (Q,), and optionally ``cell_counts`` (V host ints: the step then reads nothing back).  Per group: one
-    PairPlan (one pinned copy), forward_pairs, pair_targets, loss_fn over all the pairs, backward, optimizer.step; ``meter.update``
-    runs over the positive pairs only, their rows gathered by the plan's device index list, so ``num_samples`` counts queries with
-    their own video listed, not pairs (a group without a positive pair raises ValueError).  One host read, ``meter.result()`` at
-    the end; returns ``(train_loss, iou_metrics)``.  The meter is not reset here."""
+    pairs) and ``gt_video`` (Q,), and optionally ``cell_counts`` (V host ints: the step then reads nothing back).  In place of the
+    three lists a group may carry ``plan``, a PairPlan with its positive flags for these videos and queries -- a device-built one
+    (SMIN.mine_pairs) of a caller who mines from banks refreshed on their own schedule; it reads nothing back when the V
+    ``cell_counts`` are equal (forward_pairs).  Per group: one PairPlan (one pinned copy), forward_pairs, pair_targets, loss_fn over
+    all the pairs, backward, optimizer.step; ``meter.update`` runs over the positive pairs only, their rows gathered by the plan's
+    device index list, so ``num_samples`` counts queries with their own video listed, not pairs (a group without a positive pair
+    raises ValueError).  One host read, ``meter.result()`` at the end; returns ``(train_loss, iou_metrics)``.  The meter is not
+    reset here."""
     from .retrieval import PairPlan
     model.train()
     for g in groups:
         meter = _meter_for(meter, g)
         mm = g["moment_mask"]
-        plan = PairPlan(g["video_index"], g["query_index"], mm.shape[0], g["query_features"].shape[0], mm.device, gt_video=g["gt_video"],
-                        what="train_epoch_pairs")
+        plan = g.get("plan")
+        if plan is None:
+            plan = PairPlan(g["video_index"], g["query_index"], mm.shape[0], g["query_features"].shape[0], mm.device, gt_video=g["gt_video"],
+                            what="train_epoch_pairs")
+        elif not isinstance(plan, PairPlan) or plan.num_positive is None or not plan.fits(mm.shape[0], g["query_features"].shape[0], mm.device):
+            raise ValueError("train_epoch_pairs: a group's plan must be a PairPlan with its positive flags for the group's videos and queries")
         if plan.num_positive < 1:
             raise ValueError("train_epoch_pairs: a group must list at least one query with its own video (the metric runs over those pairs)")
-        optimizer.zero_grad()
-        out = model.forward_pairs(*_inputs(g), None, None, cell_counts=g.get("cell_counts"), plan=plan)
-        tg = pair_targets(g, g, None, None, None, plan=plan)
-        loss = _loss_of(out, tg)
-        rows = plan.positive_rows
-        meter.update(out[0].detach().index_select(0, rows), out[1].detach().index_select(0, rows), out[2].detach().index_select(0, rows),
-                     tg["moment_mask"].index_select(0, rows), tg["sm"].index_select(0, rows), loss=loss.detach())
-        loss.backward()
-        optimizer.step()
+        _pair_step(model, optimizer, g, plan, meter)
+    metrics = meter.result()
+    return metrics["loss"], metrics
+
+
+def train_epoch_mined(model, optimizer, groups, negatives, skip=0, meter=None, max_batch=64):
+    """train_epoch_pairs with the pairs chosen by the model (hard-negative mining).  A group is train_epoch_pairs'
+    dict without the two lists: the tensors, ``gt_video`` (Q host ints) and optionally ``cell_counts``.  Per group, under
+    torch.no_grad(): encode_videos / encode_queries with the current parameters and ``model.mine_pairs`` -- every query against every
+    video of the group at the price of a scoring pass, then each query's own video and its ``negatives`` highest-scoring wrong ones
+    after the ``skip`` hardest, as a pair plan formed on the device --; then train_epoch_pairs' step on that plan, Q * (1 +
+    negatives) pairs.  With ``cell_counts`` of one value per group nothing is read back before the one ``meter.result()`` at the
+    end; with unequal counts the node reads the pairs' cell count once per step, and without them encode_videos reads the videos'
+    counts as well.  ``num_samples`` counts the queries.  Returns ``(train_loss, iou_metrics)``.  The meter is not reset here."""
+    model.train()
+    for g in groups:
+        meter = _meter_for(meter, g)
+        with torch.no_grad():
+            videos = model.encode_videos(g["video_features"], g["video_mask"], g["length_mask"], g["moment_mask"], cell_counts=g.get("cell_counts"))
+            queries = model.encode_queries(g["query_features"], g["query_mask"])
+            plan = model.mine_pairs(videos, queries, g["gt_video"], negatives, skip=skip, max_batch=max_batch)
+        _pair_step(model, optimizer, g, plan, meter)
     metrics = meter.result()
     return metrics["loss"], metrics
 
