@@ -55,7 +55,8 @@ extern "C" {
  * accumulator); training through shared banks -- smin_pair_assemble_bwd and smin_pair_assemble_bwd_workspace_bytes (the adjoint of
  * smin_pair_assemble: the pairs' gradients summed onto their videos and queries in a fixed order); hard-negative mining on the device
  * -- smin_mine_pairs and smin_mine_pairs_ws_bytes (each query's own video and its highest-scoring wrong ones as the pair lists and both
- * groupings smin_pair_assemble_bwd reads) */
+ * groupings smin_pair_assemble_bwd reads); a contrastive loss over a pair plan -- smin_pair_rank_fwd, smin_pair_rank_bwd and
+ * smin_pair_rank_ws_bytes (each query's own video ranked above the wrong ones it was paired with) */
 #define SMIN_HIP_ABI_VERSION 2
 
 int smin_abi_version(void);
@@ -820,6 +821,63 @@ int smin_search_merge(void* stream, int S, const int64_t* const* video, const in
 size_t smin_mine_pairs_ws_bytes(int Q, int V, int N);
 int smin_mine_pairs(void* stream, const float* score, const int32_t* gt_video, int Q, int V, int N, int skip, int32_t* video_index,
                     int32_t* query_index, int32_t* v_ptr, int32_t* v_pairs, int32_t* q_ptr, int32_t* q_pairs, void* ws, size_t ws_bytes);
+
+/* ---- video-level contrastive loss over a pair plan (csrc/pair_rank.hip): each query's own video ranked above the
+ * wrong ones it was paired with.  All arithmetic fp32.
+ *
+ * smin_pair_rank_fwd: three launches (pool, queries, total), no atomics.
+ * Inputs.  pm [P][L][L], ps [P][L], pe [P][L] fp32: the P pairs' scores (forward_pairs); mm [P][L][L] one byte per cell: the pairs'
+ *   moment_mask (nonzero = valid).  q_ptr [Q + 1], q_pairs [P] int32: the pairs grouped by query, CSR, query q owns
+ *   q_pairs[q_ptr[q] .. q_ptr[q + 1]), in list order (a PairPlan's).  positive [P] int32: nonzero where the pair's video is its query's
+ *   own.  tau: the temperature that pools a pair's cells, gamma: the one across a query's videos.
+ * Cell score.  f[p][i][j] = (pm[p][i][j] * sqrtf(max(ps[p][i], 1e-12f))) * sqrtf(max(pe[p][j], 1e-12f)), smin_top_moments' order.
+ * Pair score.  Over the pair's n_p valid cells, m_p their maximum: s_p = m_p + tau * logf((sum_valid expf((f - m_p) / tau)) / n_p);
+ *   n_p == 0: s_p = 0, a constant that still takes part in its query's sums.
+ * Query loss.  S_q the query's segment, S_q+ its pairs with positive != 0, M_q = max_{S_q} s:
+ *   l_q = logf(sum_{S_q} expf((s_p - M_q) / gamma)) - logf(sum_{S_q+} expf((s_p - M_q) / gamma)).
+ *   A query with S_q+ empty (a query without a pair among them) is not counted.
+ * Outputs, every element written.
+ *   loss [1] = (sum of l_q over the Nc counted queries) / Nc, exactly 0 when Nc == 0.
+ *   stats [2] = { Nc, hits }: a counted query is a hit when max_{S_q+} s >= max_{S_q \ S_q+} s (always, without a negative).
+ *   pair_score [P] = s_p.
+ *   coef [P]: (softmax_{S_q}(p) - [p in S_q+] softmax_{S_q+}(p)) / gamma, the derivative of l_q by s_p, 0 for the pairs of a query that
+ *     is not counted (and for a pair no segment lists);  pool [P][2] = { m_p, the sum over the valid cells } (0, 0 when n_p == 0).
+ *     stats, coef and pool are what smin_pair_rank_bwd reads.
+ * Order.  Pool: one workgroup of 256 per pair; thread t takes cells t, t + 256, ... of the row-major map in ascending order, the 64
+ *   lanes of a wave are added by wave_sum (DPP), the four waves as (w0 + w1) + (w2 + w3); the maximum first, then the sum.  Queries:
+ *   one wave64 per query; lane l takes entries l, l + 64, ... of the segment in ascending order, then wave_sum.  Total: one thread
+ *   adds l_q, the counted flags and the hits in ascending q.
+ * Bounds.  Every value read from q_ptr (into [0, P], ascending) and q_pairs (into [0, P)) is clamped before it forms an address:
+ *   malformed lists give unspecified sums, never an access outside the buffers.
+ * Limits.  P, Q >= 1, 1 <= L <= 4096 (cells are counted in fp32), tau and gamma finite and > 0; ws 16-byte aligned; the outputs and
+ *   ws must not overlap the inputs or each other.
+ * Workspace.  ws_bytes >= smin_pair_rank_ws_bytes(P, Q, L), exactly Q * 16 (l_q and the two flags between the launches); the
+ *   query returns 0 for a size out of range.
+ * Determinism.  The same bits every run; no host read; no allocation; capturable.
+ * Rejection.  A nonzero status before any launch, the outputs untouched, for a size out of range, a NULL pointer, a tau or gamma that
+ *   is not finite and positive, or a workspace that is too small. */
+size_t smin_pair_rank_ws_bytes(int P, int Q, int L);
+int smin_pair_rank_fwd(void* stream, const float* pm, const float* ps, const float* pe, const uint8_t* mm, const int32_t* q_ptr,
+                       const int32_t* q_pairs, const int32_t* positive, int P, int Q, int L, float tau, float gamma, float* loss,
+                       float* stats, float* pair_score, float* coef, float* pool, void* ws, size_t ws_bytes);
+
+/* smin_pair_rank_bwd: the gradients of smin_pair_rank_fwd's loss by pm, ps and pe; one launch, one workgroup of 256 per pair, no
+ * atomics, no workspace.  f and the exponentials are recomputed from the inputs, not stored.
+ * Inputs.  dloss [1]: the upstream gradient; stats, coef, pool: the forward's; pm, ps, pe, mm, tau: the forward's.
+ * Outputs, every element written.  With g_p = dloss * coef[p] / Nc and df = g_p * expf((f - m_p) / tau) / pool[p][1] on the valid cells,
+ *   a_i = sqrtf(max(ps[p][i], 1e-12f)), b_j likewise of pe, and a', b' their derivatives with torch.clamp_min's gradient (0.5 / a where
+ *   ps >= 1e-12f, else 0):
+ *   dpm [P][L][L] = (df * a_i) * b_j, 0 in a masked cell;
+ *   dps [P][L]    = (sum_j (df * pm) * b_j) * a'_i;    dpe [P][L] = (sum_i (df * pm) * a_i) * b'_j;  0 for a row or column without a
+ *   valid cell.  A pair with g_p == 0 (its query not counted, Nc == 0) or without a valid cell gets zeros throughout.
+ * Order.  dps: wave w takes rows w, w + 4, ...; lane l adds the columns l, l + 64, ... in ascending order, then wave_sum.  dpe: columns
+ *   in chunks of 64, lane l has column chunk + l; wave w adds rows w, w + 4, ... in ascending order, and the four waves are added as
+ *   (w0 + w1) + (w2 + w3).  A function of the arguments only.
+ * Limits.  P >= 1, 1 <= L <= 4096, tau finite and > 0.  The outputs must not overlap the inputs or each other.
+ * Determinism.  The same bits every run; no host read; no allocation; capturable.
+ * Rejection.  A nonzero status before the launch, the outputs untouched, for a size out of range, a NULL pointer or a bad tau. */
+int smin_pair_rank_bwd(void* stream, const float* dloss, const float* stats, const float* coef, const float* pool, const float* pm,
+                       const float* ps, const float* pe, const uint8_t* mm, int P, int L, float tau, float* dpm, float* dps, float* dpe);
 
 /* ---- stand-alone fp32 MFMA GEMM  C[M][N] = A[M][K] * B[N][K]^T  (used by tests and bench.py's
  * roofline probe; same engine as every contraction above). */

@@ -17,7 +17,7 @@ from .modules import (  # noqa: F401
 )
 from .training import loss_fn, loss_fn_torch, bce_loss, compute_ious, compute_ious_torch, CapturedStep  # noqa: F401
 from .training import train_epoch, eval_epoch, test_model, test_model_windows, test_model_corpus  # noqa: F401
-from .training import pair_targets, train_epoch_pairs, train_epoch_mined  # noqa: F401
+from .training import pair_targets, train_epoch_pairs, train_epoch_mined, pair_rank_loss, pair_rank_loss_torch  # noqa: F401
 from .retrieval import PairPlan  # noqa: F401
 from .meter import EpochMeter, EpochMeterTorch, CorpusMeter, CorpusMeterTorch  # noqa: F401
 from .optim import FusedAdam, FusedAdamTorch, RowSparseAdam, RowSparseAdamTorch  # noqa: F401

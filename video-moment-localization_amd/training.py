@@ -44,6 +44,84 @@ def loss_fn(pm, ym, sm, moment_mask, ps, ys, ss, pe, ye, se, pa, ya, length_mask
         return LossFn.apply(pm, ps, pe, pa, ym, sm, moment_mask, ys, ss, ye, se, ya, length_mask)
 
 
+def _temperatures(what, tau, gamma):
+    for name, v in (("tau", tau), ("gamma", gamma)):
+        if not (isinstance(v, (int, float)) and 0.0 < float(v) < float("inf")):
+            raise ValueError(f"{what}: {name} must be a finite positive number (got {v!r})")
+
+
+def _pair_rank_check(what, pm, plan, tau, gamma):
+    from .retrieval import PairPlan
+    if not isinstance(plan, PairPlan) or plan.positive is None:
+        raise ValueError(f"{what}: the plan must be a PairPlan with its positive flags (built with gt_video, or SMIN.mine_pairs)")
+    if pm.dim() != 3 or plan.P != pm.shape[0]:
+        raise ValueError(f"{what}: the plan lists {plan.P} pairs and pm is {tuple(pm.shape)}: pm must be (P, L, L) of the plan's pairs")
+    _temperatures(what, tau, gamma)
+
+
+def pair_rank_loss_torch(pm, ps, pe, moment_mask, plan, tau=0.1, gamma=0.1, return_stats=False):
+    """``pair_rank_loss`` as plain torch ops on any device and in any float dtype, differentiable by autograd: the tests' reference;
+    nothing routes here.  The plan's ``q_ptr`` / ``q_pairs`` / ``positive`` are read once on the host to form the loop over the
+    queries, so on a device this call waits for it: not for the training path."""
+    _pair_rank_check("pair_rank_loss_torch", pm, plan, tau, gamma)
+    P, Q = plan.P, plan.Q
+    lists = torch.cat([plan.q_ptr.reshape(-1), plan.q_pairs.reshape(-1), plan.positive.reshape(-1)]).tolist()     # the one host read
+    q_ptr, q_pairs, positive = lists[:Q + 1], lists[Q + 1:Q + 1 + P], lists[Q + 1 + P:]
+    valid = moment_mask != 0
+    f = (pm * torch.sqrt(ps.clamp_min(1e-12)).unsqueeze(2)) * torch.sqrt(pe.clamp_min(1e-12)).unsqueeze(1)
+    n = valid.reshape(P, -1).sum(dim=1)
+    some = n > 0
+    m = torch.where(valid, f.detach(), torch.full_like(f, float("-inf"))).reshape(P, -1).max(dim=1).values
+    m = torch.where(some, m, torch.zeros_like(m)).reshape(P, 1, 1)
+    # a masked cell stands at the maximum (exponent 0) and is multiplied away: nothing infinite reaches autograd
+    e = torch.exp((torch.where(valid, f, m) - m) / tau) * valid.to(f.dtype)
+    z = e.reshape(P, -1).sum(dim=1)
+    one = torch.ones_like(z)
+    s = torch.where(some, m.reshape(P) + tau * torch.log(torch.where(some, z, one) / torch.where(some, n.to(f.dtype), one)), torch.zeros_like(z))
+    sd = s.detach()
+    total, counted, hits = s.new_zeros(()), 0, 0
+    for q in range(Q):
+        seg = q_pairs[q_ptr[q]:q_ptr[q + 1]]
+        pos = [p for p in seg if positive[p] != 0]
+        if not pos:
+            continue
+        neg = [p for p in seg if positive[p] == 0]
+        x = (s[seg] - sd[seg].max()) / gamma
+        total = total + (torch.log(torch.exp(x).sum()) - torch.log(torch.exp(x[[k for k, p in enumerate(seg) if positive[p] != 0]]).sum()))
+        counted += 1
+        hits += int(not neg or bool(sd[pos].max() >= sd[neg].max()))
+    loss = total / counted if counted else (s.sum() * 0.0)
+    if not return_stats:
+        return loss
+    return loss, torch.tensor([counted, hits], dtype=torch.float32, device=pm.device), sd
+
+
+def pair_rank_loss(pm, ps, pe, moment_mask, plan, tau=0.1, gamma=0.1, return_stats=False):
+    """A video-level contrastive term beside ``loss_fn``: for each query of a pair plan, its own video's pair score
+    against those of all the videos it was paired with.  ``pm (P, L, L)``, ``ps``, ``pe (P, L)``: forward_pairs' outputs;
+    ``moment_mask (P, L, L)``: the pairs' mask (pair_targets); ``plan``: the PairPlan of these pairs with its positive flags, host-built
+    with gt_video or device-built (SMIN.mine_pairs).  A pair's score is the log-mean-exp at temperature ``tau`` of its valid cells'
+    fused scores ``pm * sqrt(ps_i) * sqrt(pe_j)`` (between their mean and their maximum; tau -> 0: SMIN.pair_scores); a query's loss is
+    ``log sum_all exp(s / gamma) - log sum_positive exp(s / gamma)`` over its pairs, softmax cross-entropy with one positive; the loss
+    is the mean over the queries that have a positive pair (0, with zero gradients, if none has).  HIP kernels forward and backward
+    (csrc/pair_rank.hip), fp32, the same bits every run, no host read; HIP tensors only.  Gradients go to pm, ps and pe.
+
+    Returns ``loss``; with ``return_stats`` ``(loss, stats, pair_score)``: ``stats = [counted queries, hits]`` fp32 on the device -- a
+    hit: the query's best positive scores at least its best negative, the in-group video-retrieval accuracy -- and ``pair_score (P,)``,
+    detached."""
+    _pair_rank_check("pair_rank_loss", pm, plan, tau, gamma)
+    _require_hip(pm, "pair_rank_loss")
+    from . import _lib
+    tau, gamma = float(tau), float(gamma)
+    if NATIVE_LOSS:
+        out = _lib.load_torch().smin_pair_rank_loss(pm, ps, pe, moment_mask, plan.q_ptr, plan.q_pairs, plan.positive, tau, gamma)
+    else:
+        from .functional import PairRankFn
+        with torch.cuda.device(pm.device):
+            out = PairRankFn.apply(pm, ps, pe, moment_mask, plan.q_ptr, plan.q_pairs, plan.positive, tau, gamma)
+    return tuple(out) if return_stats else out[0]
+
+
 def compute_ious_torch(pm, ps, pe, moment_mask, sm, n=(1, 5), m=(0.1, 0.3, 0.5, 0.7), nms_thresh=None):
     """reference utils.py:10-31 as plain torch ops with a single host sync (the reference syncs once per (n, m) pair).
     ``nms_thresh`` set: R@n, IoU=m over the moments kept by greedy temporal NMS (moments.top_moments_torch) instead."""
@@ -253,13 +331,24 @@ def pair_targets(video_masks, query_targets, video_index, query_index, gt_video,
     return out
 
 
-def _pair_step(model, optimizer, g, plan, meter):
+def _rank_weight(what, rank_weight, tau, gamma):
+    """The loops' check of their contrastive term's arguments, ahead of the first step."""
+    if not (isinstance(rank_weight, (int, float)) and 0.0 <= float(rank_weight) < float("inf")):
+        raise ValueError(f"{what}: rank_weight must be a finite number >= 0 (got {rank_weight!r})")
+    _temperatures(what, tau, gamma)
+    return float(rank_weight)
+
+
+def _pair_step(model, optimizer, g, plan, meter, rank_weight=0.0, tau=0.1, gamma=0.1):
     """One step of train_epoch_pairs on group ``g`` through ``plan`` (built with its positive flags): forward_pairs, pair_targets,
-    loss_fn over all the pairs, the meter over the positive ones, backward, optimizer.step.  No host read with ``cell_counts``."""
+    loss_fn over all the pairs -- plus ``rank_weight * pair_rank_loss`` over the plan when the weight is not 0 --, the meter over the
+    positive ones, backward, optimizer.step.  No host read with ``cell_counts``."""
     optimizer.zero_grad()
     out = model.forward_pairs(*_inputs(g), None, None, cell_counts=g.get("cell_counts"), plan=plan)
     tg = pair_targets(g, g, None, None, None, plan=plan)
     loss = _loss_of(out, tg)
+    if rank_weight != 0.0:
+        loss = loss + rank_weight * pair_rank_loss(out[0], out[1], out[2], tg["moment_mask"], plan, tau, gamma)
     rows = plan.positive_rows
     meter.update(out[0].detach().index_select(0, rows), out[1].detach().index_select(0, rows), out[2].detach().index_select(0, rows),
                  tg["moment_mask"].index_select(0, rows), tg["sm"].index_select(0, rows), loss=loss.detach())
@@ -267,7 +356,7 @@ def _pair_step(model, optimizer, g, plan, meter):
     optimizer.step()
 
 
-def train_epoch_pairs(model, optimizer, groups, meter=None):
+def train_epoch_pairs(model, optimizer, groups, meter=None, rank_weight=0.0, tau=0.1, gamma=0.1):
     """train_epoch over groups of V videos and Q queries that share their encoders (SMIN.forward_pairs).  A group
     is a dict with ``video_features``, ``video_mask``, ``length_mask``, ``moment_mask`` (a row per video), ``query_features``,
     ``query_mask`` and LOSS_TARGETS (a row per query, against its own video), the host lists ``video_index``, ``query_index`` (the
@@ -278,8 +367,14 @@ def train_epoch_pairs(model, optimizer, groups, meter=None):
     all the pairs, backward, optimizer.step; ``meter.update`` runs over the positive pairs only, their rows gathered by the plan's
     device index list, so ``num_samples`` counts queries with their own video listed, not pairs (a group without a positive pair
     raises ValueError).  One host read, ``meter.result()`` at the end; returns ``(train_loss, iou_metrics)``.  The meter is not
-    reset here."""
+    reset here.
+
+    ``rank_weight`` > 0: the step's loss is ``loss_fn(...) + rank_weight * pair_rank_loss(pm, ps, pe, moment_mask, plan, tau, gamma)``,
+    formed on the device -- the contrastive term that ranks a query's own video above the wrong ones of its pairs
+    --, and the meter records that total.  At 0 (the default) the term is not computed and the step is unchanged, bit for bit; a
+    negative weight raises ValueError."""
     from .retrieval import PairPlan
+    rank_weight = _rank_weight("train_epoch_pairs", rank_weight, tau, gamma)
     model.train()
     for g in groups:
         meter = _meter_for(meter, g)
@@ -292,12 +387,12 @@ def train_epoch_pairs(model, optimizer, groups, meter=None):
             raise ValueError("train_epoch_pairs: a group's plan must be a PairPlan with its positive flags for the group's videos and queries")
         if plan.num_positive < 1:
             raise ValueError("train_epoch_pairs: a group must list at least one query with its own video (the metric runs over those pairs)")
-        _pair_step(model, optimizer, g, plan, meter)
+        _pair_step(model, optimizer, g, plan, meter, rank_weight, tau, gamma)
     metrics = meter.result()
     return metrics["loss"], metrics
 
 
-def train_epoch_mined(model, optimizer, groups, negatives, skip=0, meter=None, max_batch=64):
+def train_epoch_mined(model, optimizer, groups, negatives, skip=0, meter=None, max_batch=64, rank_weight=0.0, tau=0.1, gamma=0.1):
     """train_epoch_pairs with the pairs chosen by the model (hard-negative mining).  A group is train_epoch_pairs'
     dict without the two lists: the tensors, ``gt_video`` (Q host ints) and optionally ``cell_counts``.  Per group, under
     torch.no_grad(): encode_videos / encode_queries with the current parameters and ``model.mine_pairs`` -- every query against every
@@ -305,7 +400,9 @@ def train_epoch_mined(model, optimizer, groups, negatives, skip=0, meter=None, m
     after the ``skip`` hardest, as a pair plan formed on the device --; then train_epoch_pairs' step on that plan, Q * (1 +
     negatives) pairs.  With ``cell_counts`` of one value per group nothing is read back before the one ``meter.result()`` at the
     end; with unequal counts the node reads the pairs' cell count once per step, and without them encode_videos reads the videos'
-    counts as well.  ``num_samples`` counts the queries.  Returns ``(train_loss, iou_metrics)``.  The meter is not reset here."""
+    counts as well.  ``num_samples`` counts the queries.  Returns ``(train_loss, iou_metrics)``.  The meter is not reset here.
+    ``rank_weight``, ``tau``, ``gamma``: train_epoch_pairs' contrastive term over the mined plan -- what a hard negative is mined for."""
+    rank_weight = _rank_weight("train_epoch_mined", rank_weight, tau, gamma)
     model.train()
     for g in groups:
         meter = _meter_for(meter, g)
@@ -313,7 +410,7 @@ def train_epoch_mined(model, optimizer, groups, negatives, skip=0, meter=None, m
             videos = model.encode_videos(g["video_features"], g["video_mask"], g["length_mask"], g["moment_mask"], cell_counts=g.get("cell_counts"))
             queries = model.encode_queries(g["query_features"], g["query_mask"])
             plan = model.mine_pairs(videos, queries, g["gt_video"], negatives, skip=skip, max_batch=max_batch)
-        _pair_step(model, optimizer, g, plan, meter)
+        _pair_step(model, optimizer, g, plan, meter, rank_weight, tau, gamma)
     metrics = meter.result()
     return metrics["loss"], metrics
 
