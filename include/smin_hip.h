@@ -56,7 +56,8 @@ extern "C" {
  * smin_pair_assemble: the pairs' gradients summed onto their videos and queries in a fixed order); hard-negative mining on the device
  * -- smin_mine_pairs and smin_mine_pairs_ws_bytes (each query's own video and its highest-scoring wrong ones as the pair lists and both
  * groupings smin_pair_assemble_bwd reads); a contrastive loss over a pair plan -- smin_pair_rank_fwd, smin_pair_rank_bwd and
- * smin_pair_rank_ws_bytes (each query's own video ranked above the wrong ones it was paired with) */
+ * smin_pair_rank_ws_bytes (each query's own video ranked above the wrong ones it was paired with); corpus search over
+ * banks of windows of long videos -- smin_corpus_span_topk (one ranked list of span-valued moments per query across videos) */
 #define SMIN_HIP_ABI_VERSION 2
 
 int smin_abi_version(void);
@@ -793,6 +794,30 @@ int smin_corpus_topk(void* stream, const float* pair_score, const int64_t* pair_
 int smin_search_merge(void* stream, int S, const int64_t* const* video, const int64_t* const* idx, const float* const* score,
                       const int32_t* const* count, const int32_t* k_list, const int64_t* video_offset, int Q, int K,
                       int64_t* out_video, int64_t* out_idx, float* out_score, int32_t* out_count);
+
+/* smin_corpus_span_topk: the K best span-valued moments of each query over all of its videos (SMIN.search_windows):
+ * smin_corpus_topk for lists whose moments are spans in raw rows of long videos.  One launch, one workgroup per query; no workspace.
+ * Inputs.  The per-group lists exactly as smin_merge_window_moments writes them for G2 (query, video) groups at k = k_video:
+ *   span [G2][k_video][2] fp32, score [G2][k_video] fp32, window [G2][k_video] int64, cell [G2][k_video][2] int64, count [G2] int32;
+ *   group_video [G2] int32: each group's video; group_ptr [Q + 1] int32: query q owns groups group_ptr[q] .. group_ptr[q + 1]
+ *   (ascending, within [0, G2]: G2 itself is not an argument and the range is trusted; a negative or descending entry gives an empty
+ *   range).  A query may have no groups, and the number of groups per query is not limited.
+ * Candidates.  The first clamp(count[g], 0, k_video) slots of each of the query's groups, the count clamped on the device.  What lies
+ *   behind the counts (NaN spans, -1) is never read.
+ * Order.  smin_corpus_topk's, through the same order word: higher score first (-0 counts as +0); ties go to the lower video, then to
+ *   the lower slot, then to the earlier group.  No suppression across videos; within a video smin_merge_window_moments has applied it.
+ * Outputs.  The first K candidates in that order: out_video [Q][K] int64, out_span [Q][K][2] fp32, out_score [Q][K] fp32, out_window
+ *   [Q][K] int64 and out_cell [Q][K][2] int64 (span, score, window and cell copied bit for bit), out_count [Q] int32 = the number
+ *   listed.  Every element of every output is written; empty slots: video -1, span NaN (0x7fc00000), score 0, window -1, cell -1.
+ * Limits.  1 <= K <= 64, 1 <= k_video <= 64, Q >= 0 (Q == 0: nothing is launched).  The outputs must not overlap the inputs.
+ * Determinism.  The same bits every run (no atomics); no host read; capturable.
+ * Rejection.  A nonzero status is returned before the launch for a bad K or k_video, a negative Q, or, with Q > 0, a NULL group_ptr or
+ *   output.  Whether a query has groups is known on the device only: with a NULL span, score, window, cell, count or group_video none
+ *   of the six is read and every query comes out empty. */
+int smin_corpus_span_topk(void* stream, const float* span, const float* score, const int64_t* window, const int64_t* cell,
+                          const int32_t* count, const int32_t* group_video, const int32_t* group_ptr, int Q, int k_video, int K,
+                          int64_t* out_video, float* out_span, float* out_score, int64_t* out_window, int64_t* out_cell,
+                          int32_t* out_count);
 
 /* smin_mine_pairs: the pair plan of hard-negative mining -- for each of Q queries its own video and the N
  * highest-scoring wrong videos, as smin_pair_assemble's two lists and smin_pair_assemble_bwd's two groupings, formed on the device.

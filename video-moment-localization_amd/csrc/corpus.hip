@@ -5,7 +5,9 @@
 //   smin_corpus_topk    merges the pairs' top_moments lists into one ranked list per query across videos;
 //   smin_search_merge   merges up to 16 such ranked lists of disjoint video shards into one: the same K-round
 //                       selection (topk_rounds) over another way of reading candidate c, so a merge of the shards' lists is the list
-//                       smin_corpus_topk gives on the whole corpus.
+//                       smin_corpus_topk gives on the whole corpus;
+//   smin_corpus_span_topk  ranks, per query, the span-valued moments of its videos (smin_merge_window_moments' lists of a bank of
+//                       windows over long videos): the same rounds over the same key, five fields per entry.
 // smin_pair_assemble has an adjoint, which is what lets a model train through shared banks:
 //   smin_pair_assemble_bwd  sums the pairs' gradients of f, f_w, f_s back onto the videos and queries they came from, through the
 //                           pairs grouped by video and by query (two CSR lists from the host): no atomics, a fixed order.
@@ -325,6 +327,68 @@ void search_merge_kernel(const RankedTables tb, int K, long long* __restrict__ o
     src.out.finish(topk_rounds(src, tb.base[tb.S], K));
 }
 
+// smin_corpus_span_topk: the lists are smin_merge_window_moments' -- a (query, video) group's moments as spans in
+// raw rows, with the window and the cell each came from -- so an entry is five fields wide and has an output writer of its own.
+struct SpanOut {
+    long long* video /* [Q][K] */; float* span /* [Q][K][2] */; float* score /* [Q][K] */; long long* window /* [Q][K] */;
+    long long* cell /* [Q][K][2] */; int* count /* [Q] */;
+    int K;
+    __device__ __forceinline__ size_t at(int r) const { return (size_t)blockIdx.x * K + r; }
+    __device__ __forceinline__ void finish(int nk) const
+    {
+        for (int r = nk + threadIdx.x; r < K; r += CT) {
+            const size_t o = at(r);
+            video[o] = -1;
+            span[2 * o] = span[2 * o + 1] = __uint_as_float(0x7fc00000u);
+            score[o] = 0.f;
+            window[o] = -1;
+            cell[2 * o] = cell[2 * o + 1] = -1;
+        }
+        if (threadIdx.x == 0) count[blockIdx.x] = nk;
+    }
+};
+
+// Its candidates: c = group ordinal * kv + slot over the query's groups g0 .. ; key parts (slot, group ordinal), as PairLists
+struct SpanLists {
+    const float* span; const float* score; const long long* window; const long long* cell; const int* count; const int* video;
+    long long g0; int kv; SpanOut out;
+    __device__ __forceinline__ bool read(long long c, int& slot, long long& w, float& sc, int& vid) const
+    {
+        w = c / kv;
+        slot = (int)(c - w * kv);
+        const long long g = g0 + w;
+        if (slot >= min(count[g], kv)) return false;             // behind the count (NaN spans, -1): never read
+        sc = score[g * kv + slot];
+        vid = video[g];
+        return true;
+    }
+    __device__ __forceinline__ void emit(int r, int slot, long long w) const
+    {
+        const long long g = g0 + w, c = g * kv + slot;
+        const size_t o = out.at(r);
+        out.video[o] = video[g];
+        out.span[2 * o] = span[2 * c]; out.span[2 * o + 1] = span[2 * c + 1];          // plain moves: the bits leave as they came
+        out.score[o] = score[c];
+        out.window[o] = window[c];
+        out.cell[2 * o] = cell[2 * c]; out.cell[2 * o + 1] = cell[2 * c + 1];
+    }
+};
+
+__global__ __launch_bounds__(CT)
+void corpus_span_topk_kernel(const float* __restrict__ span, const float* __restrict__ score, const long long* __restrict__ window,
+                             const long long* __restrict__ cell, const int* __restrict__ count, const int* __restrict__ group_video,
+                             const int* __restrict__ group_ptr, int kv, int K, long long* __restrict__ out_video, float* __restrict__ out_span,
+                             float* __restrict__ out_score, long long* __restrict__ out_window, long long* __restrict__ out_cell,
+                             int* __restrict__ out_count)
+{
+    const int b = blockIdx.x;
+    const long long g0 = max(group_ptr[b], 0);
+    const long long g1 = max((long long)group_ptr[b + 1], g0);
+    const bool lists = span && score && window && cell && count && group_video;   // (NULL lists: no query may have a group, none is read)
+    const SpanLists src{span, score, window, cell, count, group_video, g0, kv, {out_video, out_span, out_score, out_window, out_cell, out_count, K}};
+    src.out.finish(topk_rounds(src, lists ? (g1 - g0) * kv : 0, K));
+}
+
 // ---- hard-negative mining (smin_mine_pairs).  Query q owns the pairs q * S .. q * S + S - 1, S = 1 + N: slot 0 its own video, slots
 // 1 .. N the negatives of ranks skip .. skip + N - 1.  smin_mine_pairs' candidates: c = video over row q of the pair scores, the
 // query's own video left out; key parts (slot 0, w = the video, which emit reads back as its pick).
@@ -547,6 +611,23 @@ extern "C" int smin_search_merge(void* stream, int S, const int64_t* const* vide
     }
     hipLaunchKernelGGL(search_merge_kernel, dim3(Q), dim3(CT), 0, (hipStream_t)stream, tb, K, (long long*)out_video, (long long*)out_idx, out_score,
                        out_count);
+    SMIN_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int smin_corpus_span_topk(void* stream, const float* span, const float* score, const int64_t* window, const int64_t* cell,
+                                     const int32_t* count, const int32_t* group_video, const int32_t* group_ptr, int Q, int k_video, int K,
+                                     int64_t* out_video, float* out_span, float* out_score, int64_t* out_window, int64_t* out_cell,
+                                     int32_t* out_count)
+{
+    SMIN_REQUIRE(K >= 1 && K <= CORPUS_MAX_K && k_video >= 1 && k_video <= CORPUS_MAX_K && Q >= 0);
+    if (Q == 0) return 0;
+    SMIN_REQUIRE(group_ptr != nullptr && out_video != nullptr && out_span != nullptr && out_score != nullptr && out_window != nullptr);
+    SMIN_REQUIRE(out_cell != nullptr && out_count != nullptr);
+    // (as smin_corpus_topk: with a NULL list the kernel reads none of the six and every query comes out empty)
+    hipLaunchKernelGGL(corpus_span_topk_kernel, dim3(Q), dim3(CT), 0, (hipStream_t)stream, span, score, (const long long*)window, (const long long*)cell,
+                       count, group_video, group_ptr, k_video, K, (long long*)out_video, out_span, out_score, (long long*)out_window,
+                       (long long*)out_cell, out_count);
     SMIN_LAUNCH_CHECK();
     return 0;
 }

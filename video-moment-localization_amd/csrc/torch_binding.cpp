@@ -1548,6 +1548,40 @@ Scores smin_score_pairs(const Tensor& fv, const Tensor& fw, const Tensor& fs, co
                            Tensor(), Tensor(), prm));
 }
 
+// moments.corpus_span_topk (SMIN.search_windows' last stage): smin_corpus_span_topk over smin_merge_window_moments'
+// lists of G2 (query, video) groups at k_video -- span (G2, k_video, 2) fp32, score (G2, k_video) fp32, window (G2, k_video) int64,
+// cell (G2, k_video, 2) int64, count (G2,) int32 --, group_video (G2,) and group_ptr (Q + 1,) int32.  Returns (video (Q, k) int64,
+// span (Q, k, 2), score (Q, k), window (Q, k) int64, cell (Q, k, 2) int64, count (Q,) int32), every element written by the kernel.
+std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> corpus_span_topk_op(const Tensor& span, const Tensor& score, const Tensor& window, const Tensor& cell,
+                                                                                 const Tensor& count, const Tensor& group_video, const Tensor& group_ptr, int64_t k)
+{
+    for (const Tensor* t : {&span, &score, &window, &cell, &count, &group_video, &group_ptr})
+        TORCH_CHECK(t->is_cuda(), "smin_corpus_span_topk runs on a HIP device only (there is no CPU fallback)");
+    for (const Tensor* t : {&span, &score, &window, &cell, &count, &group_video})
+        TORCH_CHECK(t->device() == group_ptr.device(), "smin_corpus_span_topk: every tensor on one device");
+    const int64_t G2 = span.dim() == 3 ? span.size(0) : -1, kv = span.dim() == 3 ? span.size(1) : -1;
+    TORCH_CHECK(G2 >= 0 && G2 < (int64_t(1) << 31) && kv >= 1 && kv <= 64 && span.size(2) == 2 && score.sizes() == at::IntArrayRef({G2, kv}) && window.sizes() == score.sizes() &&
+                    cell.sizes() == at::IntArrayRef({G2, kv, 2}) && count.sizes() == at::IntArrayRef({G2}) && group_video.sizes() == count.sizes(),
+                "smin_corpus_span_topk: span (G2, k_video, 2), score and window (G2, k_video), cell (G2, k_video, 2), count and group_video (G2,) with 1 <= k_video <= 64");
+    TORCH_CHECK(group_ptr.dim() == 1 && group_ptr.size(0) >= 1 && k >= 1 && k <= 64, "smin_corpus_span_topk: group_ptr (Q + 1,) and 1 <= k <= 64");
+    TORCH_CHECK(span.scalar_type() == at::kFloat && score.scalar_type() == at::kFloat && window.scalar_type() == at::kLong && cell.scalar_type() == at::kLong &&
+                    count.scalar_type() == at::kInt && group_video.scalar_type() == at::kInt && group_ptr.scalar_type() == at::kInt,
+                "smin_corpus_span_topk: span and score float32, window and cell int64, count, group_video and group_ptr int32");
+    at::NoGradGuard no_grad;
+    c10::hip::HIPGuard device_guard(group_ptr.device().index());
+    const int64_t Q = group_ptr.size(0) - 1;
+    const Tensor sp = cont(span.detach()), sc = cont(score.detach()), wi = cont(window), ce = cont(cell), cn = cont(count), gv = cont(group_video), gp = cont(group_ptr);
+    const auto f32 = sp.options(), i64 = wi.options();
+    Tensor out_video = at::empty({Q, k}, i64), out_span = at::empty({Q, k, 2}, f32), out_score = at::empty({Q, k}, f32), out_window = at::empty({Q, k}, i64),
+           out_cell = at::empty({Q, k, 2}, i64), out_count = at::empty({Q}, cn.options());
+    const bool some = G2 > 0;                                   // (no groups: NULL lists, every query comes out empty)
+    SMIN_CK(smin_corpus_span_topk(cur(), some ? fp(sp) : nullptr, some ? fp(sc) : nullptr, some ? wi.const_data_ptr<int64_t>() : nullptr,
+                                  some ? ce.const_data_ptr<int64_t>() : nullptr, some ? ip(cn) : nullptr, some ? ip(gv) : nullptr, ip(gp), i32(Q), i32(kv), i32(k),
+                                  out_video.data_ptr<int64_t>(), fpm(out_span), fpm(out_score), out_window.data_ptr<int64_t>(), out_cell.data_ptr<int64_t>(),
+                                  out_count.data_ptr<int32_t>()));
+    return std::make_tuple(out_video, out_span, out_score, out_window, out_cell, out_count);
+}
+
 // SMIN.forward_pairs: smin_forward for the P pairs (video_index[p], query_index[p]) of V videos and Q queries that
 // are each encoded once -- the same autograd node, differentiable with respect to the parameters.  video_features (V, T, Din) and the three
 // video-side masks have a row per video, query_features (Q, words, E) and query_mask a row per query; video_index / query_index (P,)
@@ -1679,6 +1713,9 @@ TORCH_LIBRARY(smin_hip, m)
     m.def("smin_score_pairs(Tensor fv, Tensor fw, Tensor fs, Tensor video_mask, Tensor query_mask, Tensor length_mask, Tensor moment_mask, Tensor video_index, "
           "Tensor query_index, Tensor[] params, int T, int L, int C, int num_smi_layers, int max_query_length, int lstm_hidden_size, *, bool overlap_boundary, "
           "bool overlap_prep, bool param_prep_kernel, bool bf16_operand_storage, int? known_cell_count) -> (Tensor, Tensor, Tensor, Tensor)", &smin_score_pairs);
+    // SMIN.search_windows' ranking across videos: span-valued moments of (query, video) groups into one list per query
+    m.def("smin_corpus_span_topk(Tensor span, Tensor score, Tensor window, Tensor cell, Tensor count, Tensor group_video, Tensor group_ptr, int k) -> "
+          "(Tensor video, Tensor span, Tensor score, Tensor window, Tensor cell, Tensor count)", &corpus_span_topk_op);
     // SMIN.forward_pairs: smin_forward over indexed pairs of videos and queries encoded once each, one autograd node
     m.def("smin_forward_pairs(Tensor video_features, Tensor video_mask, Tensor query_features, Tensor query_mask, Tensor length_mask, Tensor moment_mask, "
           "Tensor video_index, Tensor query_index, Tensor v_ptr, Tensor v_pairs, Tensor q_ptr, Tensor q_pairs, Tensor[] params, int T, int L, int C, "

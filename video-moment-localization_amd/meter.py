@@ -257,7 +257,8 @@ class _CorpusMeter(_Meter):
 class CorpusMeter(_CorpusMeter):
     """``CorpusMeter(n=(1, 5), m=(0.1, 0.3, 0.5, 0.7), device=...)``: VCMR R@n, IoU=m, VR R@n and the mean top-1 IoU of corpus search,
     in fp64 on the device (module docstring).  ``update(result, gt_video, gt)`` enqueues two kernels on the current stream and returns
-    nothing: ``result`` is ``SMIN.search`` / ``merge_search`` output with at least max(n) entries per query, ``gt_video (Q,)`` the
+    nothing: ``result`` is ``SMIN.search`` / ``merge_search`` / ``SMIN.search_windows`` output (``video``, ``count`` and ``times``, or
+    ``idx`` where there are no times) with at least max(n) entries per query, ``gt_video (Q,)`` the
     ground-truth video in ``result["video"]``'s numbering, ``gt (Q, 2)`` the ground-truth moment in the unit of ``result["times"]``
     (seconds) or, without times, in clip edges ``(i, j + 1)``.  HIP tensors only.  ``result()`` reads (keys ``"R@n, IoU=m"``, ``"VR@n"``,
     ``"mIoU"``, ``"num_samples"``), ``reset()`` zeroes, ``state`` is the fp64 device tensor."""

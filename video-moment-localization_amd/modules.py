@@ -424,7 +424,7 @@ class Localization(nn.Module):
 
 class SMIN(nn.Module, _Retrieval):
     """reference models.py:346-377 -- the drop-in boundary (ctor called positionally from main.py:71).  What the reference does not
-    have -- localize, localize_windows, encode_videos / encode_queries, score_pairs, search, forward_pairs, pair_scores, mine_pairs -- is inherited from retrieval.py."""
+    have -- localize, localize_windows, encode_videos / encode_queries, score_pairs, search, encode_windows, search_windows, forward_pairs, pair_scores, mine_pairs -- is inherited from retrieval.py."""
 
     def __init__(self, T, L, C, D, dl, num_smi_layers, input_video_dim, max_query_length, lstm_hidden_size, device='cpu'):
         super().__init__()

@@ -470,6 +470,82 @@ def corpus_topk_torch(pair_score, pair_idx, pair_count, pair_video, pair_ptr, k=
     return {"video": video, "idx": idx, "score": out_score, "count": count}
 
 
+# ---------------------------------------------------------------- merge of span lists across videos (SMIN.search_windows)
+def _corpus_span_check(what, span, score, window, cell, count, group_video, group_ptr, k):
+    if span.dim() != 3 or span.shape[2] != 2:
+        raise ValueError(f"{what}: span must be (G2, k_video, 2), got {tuple(span.shape)}")
+    G2, kv = span.shape[0], span.shape[1]
+    if tuple(score.shape) != (G2, kv) or tuple(window.shape) != (G2, kv) or tuple(cell.shape) != (G2, kv, 2) or tuple(count.shape) != (G2,) \
+            or tuple(group_video.shape) != (G2,):
+        raise ValueError(f"{what}: score and window must be (G2, k_video) = {(G2, kv)}, cell (G2, k_video, 2), count / group_video (G2,); got "
+                         f"{tuple(score.shape)}, {tuple(window.shape)}, {tuple(cell.shape)}, {tuple(count.shape)}, {tuple(group_video.shape)}")
+    if group_ptr.dim() != 1 or group_ptr.shape[0] < 1:
+        raise ValueError(f"{what}: group_ptr must be (Q + 1,)")
+    if not (isinstance(k, int) and 1 <= k <= MAX_K) or not 1 <= kv <= MAX_K:
+        raise ValueError(f"{what} needs integers 1 <= k, k_video <= {MAX_K} (got k={k!r}, k_video={kv})")
+    if G2 >= 2 ** 31:
+        raise ValueError(f"{what}: {G2} groups exceed the int32 group_ptr")
+    return G2, kv, group_ptr.shape[0] - 1
+
+
+_SPAN_KEYS = ("video", "span", "score", "window", "cell", "count")
+
+
+def corpus_span_topk(span, score, window, cell, count, group_video, group_ptr, k=5):
+    """One ranked list of span-valued moments per query over all of its videos (include/smin_hip.h, smin_corpus_span_topk; the operator
+    smin_hip::smin_corpus_span_topk): one workgroup per query picks k times the best remaining candidate of the query's groups.
+
+    ``span (G2, k_video, 2)`` fp32, ``score (G2, k_video)``, ``window (G2, k_video)`` int64, ``cell (G2, k_video, 2)`` int64 and
+    ``count (G2,)``: merge_window_moments' outputs for G2 (query, video) groups; ``group_video (G2,)`` each group's video;
+    ``group_ptr (Q + 1,)``: query q owns groups ``group_ptr[q] .. group_ptr[q + 1]`` (ascending, within [0, G2]).  Order: corpus_topk's
+    -- higher score first, ties -> lower video, then lower slot, then the earlier group; -0 counts as +0.  HIP tensors only; no host
+    synchronisation.  Returns a dict: ``video (Q, k)`` int64 (-1 for empty slots), ``span (Q, k, 2)`` fp32 (NaN), ``score (Q, k)`` (0),
+    ``window (Q, k)`` int64 (-1), ``cell (Q, k, 2)`` int64 (-1), ``count (Q,)`` int32; span, score, window and cell are copied bit
+    for bit."""
+    _require_hip(group_ptr, "corpus_span_topk")
+    _corpus_span_check("corpus_span_topk", span, score, window, cell, count, group_video, group_ptr, k)
+    from ._lib import load_torch
+    out = load_torch().smin_corpus_span_topk(span.detach().float(), score.detach().float(), window.to(torch.int64), cell.to(torch.int64),
+                                             count.to(torch.int32), group_video.to(torch.int32), group_ptr.to(torch.int32), k)
+    return dict(zip(_SPAN_KEYS, out))
+
+
+def corpus_span_topk_torch(span, score, window, cell, count, group_video, group_ptr, k=5):
+    """``corpus_span_topk`` as plain torch + Python on any device (same result, bit for bit): each query's candidates sorted by
+    (score, video, slot, group)."""
+    G2, kv, Q = _corpus_span_check("corpus_span_topk_torch", span, score, window, cell, count, group_video, group_ptr, k)
+    dev = group_ptr.device
+    span, score = span.detach().float(), score.detach().float()
+    sc = torch.where(score == 0, torch.zeros_like(score), score)                                 # -0 -> +0
+    u = sc.contiguous().view(torch.int32).to(torch.int64) & 0xFFFFFFFF
+    o = torch.where(u >= 0x80000000, u ^ 0xFFFFFFFF, u | 0x80000000).clamp_min(1).reshape(-1).tolist()   # the order word of top_moments_torch
+    cnt = count.to(torch.int64).clamp(0, kv).tolist()
+    vid = group_video.to(torch.int64).tolist()
+    gp = group_ptr.to(torch.int64).tolist()
+    out = {"video": torch.full((Q, k), -1, dtype=torch.int64, device=dev),
+           "span": torch.full((Q, k, 2), 0x7FC00000, dtype=torch.int32, device=dev).view(torch.float32),    # the kernel's NaN
+           "score": torch.zeros((Q, k), dtype=torch.float32, device=dev),
+           "window": torch.full((Q, k), -1, dtype=torch.int64, device=dev),
+           "cell": torch.full((Q, k, 2), -1, dtype=torch.int64, device=dev),
+           "count": torch.zeros((Q,), dtype=torch.int32, device=dev)}
+    span_bits = span.contiguous().view(torch.int32).reshape(-1, 2)                               # moved as integers: a NaN keeps its payload
+    for q in range(Q):
+        g0 = max(gp[q], 0)
+        g1 = max(gp[q + 1], g0)
+        cand = [(-o[g * kv + s], vid[g], s, g) for g in range(g0, g1) for s in range(cnt[g])]
+        cand.sort()
+        n = min(len(cand), k)
+        if n:
+            flat = torch.tensor([g * kv + s for _, _, s, g in cand[:n]], dtype=torch.int64, device=dev)
+            out["video"][q, :n] = torch.tensor([v for _, v, _, _ in cand[:n]], dtype=torch.int64, device=dev)
+            out["span"].view(torch.int32)[q, :n] = span_bits[flat]
+            out["score"].view(torch.int32)[q, :n] = score.contiguous().view(torch.int32).reshape(-1)[flat]
+            out["window"][q, :n] = window.to(torch.int64).reshape(-1)[flat]
+            out["cell"][q, :n] = cell.to(torch.int64).reshape(-1, 2)[flat]
+        out["count"][q] = n
+    return out
+
+
 # ---------------------------------------------------------------- hard-negative mining (SMIN.mine_pairs; INTEGRATION.md 3p)
 def _mine_check(what, score, gt_video, negatives, skip):
     if score.dim() != 2:

@@ -1,6 +1,7 @@
 """Retrieval on top of SMIN's scores, which the reference does not have: the best moments of a sample (``localize``), of videos of
 any length over overlapping windows (``localize_windows``) and of a corpus encoded once (``encode_videos`` / ``encode_queries`` ->
-``score_pairs`` / ``search``), and the training counterpart of the last, ``forward_pairs`` over (video, query) pairs that share their
+``score_pairs`` / ``search``; a corpus of videos of any length: ``encode_windows`` -> ``search_windows``), and the training counterpart
+of ``score_pairs``, ``forward_pairs`` over (video, query) pairs that share their
 encoders: host code around the library's kernels and the model's own ``score`` / ``forward``, which ``modules.SMIN`` inherits
 through the stateless mixin ``_Retrieval``."""
 import numpy as np
@@ -10,7 +11,8 @@ from . import _lib
 from ._host import _AttnMaps, byte_mask, host_array, known_cells, query_mask_rows, require_hip_tensors, require_ints
 from .feeder import build_masks_hip, cell_count
 from .functional import attn_maps_gather
-from .moments import MAX_K, _top_moments_into, corpus_topk, corpus_topk_torch, merge_window_moments, mine_pairs, search_times, top_moments
+from .moments import (MAX_K, _top_moments_into, corpus_span_topk, corpus_span_topk_torch, corpus_topk, corpus_topk_torch, merge_window_moments,
+                      merge_window_moments_torch, mine_pairs, search_times, top_moments, top_moments_torch)
 from .sampling import MAX_ROWS, MODES, sample_windows, window_plan
 
 
@@ -29,7 +31,43 @@ class VideoBank:
         self.cell_counts = tuple(int(c) for c in cell_counts)
 
     def __len__(self):
-        return self.video_features.shape[0]
+        return (self.video_mask if self.video_features is None else self.video_features).shape[0]
+
+    @property
+    def device(self):
+        return self.video_mask.device
+
+    @property
+    def plan_features(self):
+        """What SMIN._plan reads of the bank's features (dtype, T, no gradient): the features themselves where the bank keeps them."""
+        return self.video_features
+
+
+class WindowBank(VideoBank):
+    """The W windows of V videos of any length, encoded once (SMIN.encode_windows): a VideoBank whose rows are the
+    windows in global window order (video, then start) -- ``fv (W, T, D)``, the three masks and ``cell_counts`` per window --, and the
+    plan they came from: ``start (W,)`` int64 and ``len (W,)`` int32 on the device (each window's first raw row relative to its video
+    and its row count), ``video_ptr (V + 1,)`` on the host (numpy int64) and ``video_ptr_d`` on the device (int64) -- video v owns
+    windows ``video_ptr[v] .. video_ptr[v + 1]`` --, ``n_rows (V,)`` the videos' row counts and ``starts`` / ``lens (W,)`` (host, numpy
+    int64), ``window``, ``stride`` and ``mode``.  ``len(bank)`` is W; ``n_videos`` is V.
+
+    ``video_features`` is None on the one-node path: the sampled ``(W, T, Din)`` features are several times ``fv``'s size (Din against
+    D) and nothing reads them there; ``plan_features`` then is an empty ``(0, T, Din)`` tensor of their dtype and device.  They are kept
+    only where pairs are scored through SMIN.score on expanded pairs (off the one-node path, keep_attention).  A snapshot of the
+    parameters, as every bank."""
+
+    def __init__(self, fv, video_features, video_mask, length_mask, moment_mask, cell_counts, starts, lens, video_ptr, n_rows, start, len,
+                 video_ptr_d, window, stride, mode="pick", plan_features=None):
+        super().__init__(fv, video_features, video_mask, length_mask, moment_mask, cell_counts)
+        self.starts, self.lens, self.video_ptr, self.n_rows = (host_array(x) for x in (starts, lens, video_ptr, n_rows))     # host values
+        self.start, self.len, self.video_ptr_d = start, len, video_ptr_d                                                    # their device copies
+        self.window, self.stride, self.mode = int(window), int(stride), mode
+        self.n_videos = self.n_rows.shape[0]
+        self._plan_features = plan_features
+
+    @property
+    def plan_features(self):
+        return self._plan_features if self.video_features is None else self.video_features
 
 
 class QueryBank:
@@ -280,7 +318,10 @@ class _Retrieval:
         vi, qi = host_array(video_index), host_array(query_index)
         if vi.shape[0] != qi.shape[0]:
             raise ValueError(f"{what}: video_index and query_index must have one length (got {vi.shape[0]} and {qi.shape[0]})")
-        V, Q = len(videos), len(queries)
+        return _Retrieval._check_range(what, vi, qi, len(videos), len(queries))
+
+    @staticmethod
+    def _check_range(what, vi, qi, V, Q):
         if vi.size and (vi.min() < 0 or vi.max() >= V or qi.min() < 0 or qi.max() >= Q):
             raise ValueError(f"{what}: video_index must lie in [0, {V}) and query_index in [0, {Q})")
         return vi, qi
@@ -289,8 +330,10 @@ class _Retrieval:
         """score_pairs of checked host lists vi / qi (P >= 1) whose int32 device copies are vi_d / qi_d.  No host read."""
         cells = sum(videos.cell_counts[v] for v in vi)                            # host arithmetic: the scorer asks the device nothing
         with known_cells(self, cells), torch.no_grad(), torch.cuda.device(vi_d.device):
-            if not self._bank_plan(videos.video_features, queries.query_features):
+            if not self._bank_plan(videos.plan_features, queries.query_features):
                 # as score(): configurations off the one-node path (and keep_attention) run the forward, here on expanded pairs
+                if videos.video_features is None:
+                    raise ValueError("score_pairs: the window bank was encoded on the one-node path and keeps no features to expand; encode it again")
                 qm = queries.query_mask[:, :queries.query_features.shape[1]]
                 return self.score(videos.video_features.index_select(0, vi_d), videos.video_mask.index_select(0, vi_d),
                                   queries.query_features.index_select(0, qi_d), qm.index_select(0, qi_d),
@@ -312,8 +355,8 @@ class _Retrieval:
         vi, qi = self._pair_lists("score_pairs", videos, queries, video_index, query_index)
         if vi.shape[0] < 1:
             raise ValueError("score_pairs: at least one pair")
-        require_hip_tensors("score_pairs", dict(videos=videos.video_features, queries=queries.query_features), must="hold HIP tensors")
-        dev = videos.video_features.device
+        require_hip_tensors("score_pairs", dict(videos=videos.video_mask, queries=queries.query_features), must="hold HIP tensors")
+        dev = videos.device
         idx = torch.from_numpy(np.concatenate([vi, qi]).astype(np.int32)).pin_memory().to(dev, non_blocking=True)
         return self._score_pairs(videos, queries, vi, qi, idx[:vi.shape[0]], idx[vi.shape[0]:])
 
@@ -381,6 +424,17 @@ class _Retrieval:
         require_ints(what, ("k", k, 1, MAX_K), ("k_video", k_video, 1, MAX_K), ("max_batch", max_batch, 1, 65535))
         _require_banks(what, videos, queries)
         V, Q = len(videos), len(queries)
+        vi, qi, pair_ptr = self._listed_pairs(what, pairs, V, Q)
+        if duration is not None and tuple(duration.shape) != (V,):
+            raise ValueError(f"{what}: duration must be (V,) = ({V},) seconds (got {tuple(duration.shape)})")
+        require_hip_tensors(what, dict(videos=videos.video_mask, queries=queries.query_features), must="hold HIP tensors")
+        return int(k), int(k_video), vi, qi, pair_ptr
+
+    @staticmethod
+    def _listed_pairs(what, pairs, V, Q):
+        """The checked (query, video) pairs of a search over V videos and Q queries, sorted by (query, video): host lists ``vi``, ``qi``
+        and ``pair_ptr (Q + 1,)``, query q owning pairs ``pair_ptr[q] .. pair_ptr[q + 1]``.  ``pairs`` None: every query against every
+        video.  ValueError for a malformed list, an index out of range or a repeated pair."""
         if pairs is None:
             qi, vi = np.repeat(np.arange(Q, dtype=np.int64), V), np.tile(np.arange(V, dtype=np.int64), Q)
         else:
@@ -391,14 +445,11 @@ class _Retrieval:
                 raise ValueError(f"{what}: pairs must be (P, 2) rows of (query, video) (got {pr.shape})")
             order = np.lexsort((pr[:, 1], pr[:, 0]))                               # by (query, video)
             qi, vi = pr[order, 0], pr[order, 1]
-        vi, qi = self._pair_lists(what, videos, queries, vi, qi)
+        vi, qi = _Retrieval._check_range(what, host_array(vi), host_array(qi), V, Q)
         if vi.size > 1 and bool(((qi[1:] == qi[:-1]) & (vi[1:] == vi[:-1])).any()):
             raise ValueError(f"{what}: a (query, video) pair is listed more than once")
-        if duration is not None and tuple(duration.shape) != (V,):
-            raise ValueError(f"{what}: duration must be (V,) = ({V},) seconds (got {tuple(duration.shape)})")
-        require_hip_tensors(what, dict(videos=videos.video_features, queries=queries.query_features), must="hold HIP tensors")
         pair_ptr = np.concatenate([[0], np.cumsum(np.bincount(qi, minlength=Q))]).astype(np.int64)
-        return int(k), int(k_video), vi, qi, pair_ptr
+        return vi, qi, pair_ptr
 
     @staticmethod
     def _search_result(r, duration, L):
@@ -421,7 +472,7 @@ class _Retrieval:
         ``duration[video]``, NaN for empty slots.  Scores come from score_pairs (forward_only_scoring or not: a bank has no graph),
         in the contraction mode of set_gemm_mode.  No host synchronisation."""
         k, k_video, vi, qi, pair_ptr = self._search_plan("search", videos, queries, pairs, k, k_video, max_batch, duration)
-        dev, L, P = videos.video_features.device, self.L, vi.shape[0]
+        dev, L, P = videos.device, self.L, vi.shape[0]
         # the whole plan in one pinned buffer, one asynchronous copy (the call never waits for the device)
         plan = torch.from_numpy(np.concatenate([vi, qi, pair_ptr]).astype(np.int32)).pin_memory().to(dev, non_blocking=True)
         vi_d, qi_d, pp_d = plan[:P], plan[P:2 * P], plan[2 * P:]
@@ -439,6 +490,161 @@ class _Retrieval:
             mm = videos.moment_mask.index_select(0, vi_d[c0:c1])
             _top_moments_into(pm, ps, pe, mm, k_video, nms_thresh, idx[c0:c1], score[c0:c1], count[c0:c1])
         return idx, score, count
+
+    # ---------------------------------------------------------------- corpus search over long videos
+    def encode_windows(self, raw, lengths, window=None, stride=None, mode="pick", max_batch=64):
+        """A WindowBank of the W windows of V videos of any length: sampling.window_plan's overlapping windows of ``window`` raw rows
+        (default T: one row per clip) every ``stride`` rows (default window // 2), each resampled to T clips and encoded once --
+        chunk by chunk, at most ``max_batch`` windows each: sample_windows, build_masks_hip, encode_videos (smin_hip::smin_encode_videos).
+        ``raw (R, Din)`` HIP float32 tensor of the videos' rows back to back and ``lengths`` their V row counts (host), as
+        localize_windows takes them.  A video of 0 rows has no window.  The windows' valid-cell counts come from the host plan
+        (feeder.cell_count of min(len, T)) and the plan travels in one pinned asynchronous copy: nothing is read back.  The sampled
+        features are dropped chunk by chunk on the one-node path (WindowBank).  Under torch.no_grad(); stale after a parameter update."""
+        T, L = self.T, self.L
+        window = T if window is None else window
+        stride = max(int(window) // 2, 1) if stride is None else stride
+        require_ints("encode_windows", ("window", window, 1, MAX_ROWS), ("stride", stride, 1, MAX_ROWS), ("max_batch", max_batch, 1, 65535))
+        if mode not in MODES:
+            raise ValueError(f"encode_windows: mode must be one of {sorted(MODES)} (got {mode!r})")
+        require_hip_tensors("encode_windows", dict(raw=raw))
+        if raw.dim() != 2 or raw.dtype != torch.float32 or raw.shape[1] % 4 != 0 or raw.shape[1] != self.input_video_dim:
+            raise ValueError(f"encode_windows: raw must be float32 (R, Din = {self.input_video_dim}) with Din % 4 == 0 (got "
+                             f"{tuple(raw.shape)} {raw.dtype})")
+        n = host_array(lengths)
+        if n.size and n.min() < 0 or int(n.sum()) != raw.shape[0]:
+            raise ValueError(f"encode_windows: lengths must be >= 0 and sum to raw's {raw.shape[0]} rows (got {int(n.sum())})")
+        starts, lens, vptr = (x.numpy() for x in window_plan(n, window, stride))
+        V, W, dev, Din = n.shape[0], starts.shape[0], raw.device, raw.shape[1]
+        offs = np.concatenate([[0], np.cumsum(n)]).astype(np.int64)
+        row_begin = offs[np.repeat(np.arange(V), vptr[1:] - vptr[:-1])] + starts
+        cells = [cell_count(x, T, L) for x in np.minimum(lens, T)]                              # per window, as csrc/labels.hip forms it
+        probe = raw.new_empty((0, T, Din))                                                     # what SMIN._plan reads of the windows' features
+        keep = not self._bank_plan(probe, probe)                                               # (the query side's dtype is checked when pairs are scored)
+        with torch.no_grad(), torch.cuda.device(dev):
+            # the whole plan in one pinned buffer, one asynchronous copy (the call never waits for the device)
+            plan = torch.from_numpy(np.concatenate([row_begin, starts, lens, vptr]).astype(np.int64)).pin_memory().to(dev, non_blocking=True)
+            rb_d, st_d, ln_d, vp_d = plan[:W], plan[W:2 * W], plan[2 * W:3 * W].to(torch.int32), plan[3 * W:]
+            vmask = torch.empty((W, T, 1), dtype=torch.uint8, device=dev)
+            lmask = torch.empty((W, L), dtype=torch.bool, device=dev)
+            mmask = torch.empty((W, L, L), dtype=torch.bool, device=dev)
+            feats = torch.empty((W, T, Din), dtype=torch.float32, device=dev) if keep else None
+            fv = None
+            for c0 in range(0, W, max_batch):
+                c1 = min(c0 + max_batch, W)
+                vf, nfeats = sample_windows(raw, rb_d[c0:c1], ln_d[c0:c1], T, mode=mode)
+                m = build_masks_hip(nfeats, T, L)
+                part = self.encode_videos(vf, m["video_mask"], m["length_mask"], m["moment_mask"], cell_counts=cells[c0:c1])
+                vmask[c0:c1], lmask[c0:c1], mmask[c0:c1] = part.video_mask, part.length_mask, part.moment_mask
+                if part.fv is not None:
+                    fv = torch.empty((W,) + tuple(part.fv.shape[1:]), dtype=torch.float32, device=dev) if fv is None else fv
+                    fv[c0:c1] = part.fv
+                if keep:
+                    feats[c0:c1] = vf
+        return WindowBank(fv, feats, vmask, lmask, mmask, cells, starts, lens, vptr, n, st_d, ln_d, vp_d, window, stride, mode, plan_features=probe)
+
+    def _window_search_plan(self, what, windows, queries, pairs, k, k_video, k_window, max_batch, duration):
+        """search_windows' checked arguments and its expansion, host arithmetic only: ``(k, k_video, k_window, plan)`` with ``plan`` a dict
+        of numpy int64 arrays -- ``vi`` / ``qi (G2,)`` the (query, video) groups sorted by (query, video), ``wi`` / ``wq (G,)`` the
+        (query, window) list (each group's windows in start order, ``wi`` a global window of the bank), ``group_ptr (G2 + 1,)`` over that
+        list and ``query_ptr (Q + 1,)`` over the groups."""
+        k_video = k if k_video is None else k_video
+        k_window = k_video if k_window is None else k_window
+        require_ints(what, ("k", k, 1, MAX_K), ("k_video", k_video, 1, MAX_K), ("k_window", k_window, 1, MAX_K), ("max_batch", max_batch, 1, 65535))
+        if not isinstance(windows, WindowBank) or not isinstance(queries, QueryBank):
+            raise ValueError(f"{what}: windows is a WindowBank (encode_windows) and queries a QueryBank (encode_queries)")
+        V, Q = windows.n_videos, len(queries)
+        vi, qi, query_ptr = self._listed_pairs(what, pairs, V, Q)
+        if duration is not None and tuple(duration.shape) != (V,):
+            raise ValueError(f"{what}: duration must be (V,) = ({V},) seconds (got {tuple(duration.shape)})")
+        vptr = windows.video_ptr
+        nw = (vptr[1:] - vptr[:-1])[vi]                                                        # windows per group; 0 for a video without rows
+        group_ptr = np.concatenate([[0], np.cumsum(nw)]).astype(np.int64)
+        G2, G = vi.shape[0], int(group_ptr[-1])
+        if G * int(k_window) >= 2 ** 31 or G2 >= 2 ** 31:
+            raise ValueError(f"{what}: {G} (query, window) pairs of {k_window} moments in {G2} groups exceed the merges' 2**31 candidates / groups")
+        wi = np.concatenate([np.arange(vptr[v], vptr[v + 1]) for v in vi]).astype(np.int64) if G else np.zeros(0, np.int64)
+        plan = dict(vi=vi, qi=qi, wi=wi, wq=np.repeat(qi, nw), group_ptr=group_ptr, query_ptr=query_ptr)
+        return int(k), int(k_video), int(k_window), plan
+
+    @staticmethod
+    def _window_times(r, duration, n_rows):
+        """``times = (span * duration[video]) / n_rows[video]`` in fp32 -- localize_windows' formula on each entry's own video; the NaN
+        span of an empty slot carries through."""
+        v = r["video"].clamp_min(0)
+        d = duration.to(device=v.device, dtype=torch.float32)[v].unsqueeze(-1)
+        r["times"] = (r["span"] * d) / n_rows.to(torch.float32)[v].unsqueeze(-1)
+        return r
+
+    def search_windows(self, windows, queries, pairs=None, k=5, k_video=None, k_window=None, nms_thresh=0.5, duration=None, max_batch=64):
+        """Which video, and where, over videos of any length: the k best moments of each of the Q queries of a QueryBank over the videos
+        of a WindowBank, at the windows' native resolution.
+
+        ``pairs``: None -- every query against every video --, or a host (P, 2) array of (query, video) rows, in any order (sorted here
+        by (query, video)); a repeated pair raises ValueError.  Each pair expands to its video's windows in start order (a video
+        without rows: none).  The (query, window) list is scored in chunks of at most ``max_batch`` -- score_pairs from the banks, no
+        encoder runs again, each chunk's valid-cell count the sum of the bank's cell_counts -- and each chunk is cut to ``k_window``
+        (default k_video) moments per window by top_moments' kernels.  One smin_merge_window_moments then merges each (query, video)
+        group's windows by greedy NMS in raw-row time into ``k_video`` (default k) moments, and one smin_corpus_span_topk ranks each
+        query's moments across its videos: higher score first, ties -> lower video, then lower slot.
+
+        Returns a dict: ``video (Q, k)`` int64 (-1 for empty slots), ``span (Q, k, 2)`` float32 raw rows of that video (NaN),
+        ``score (Q, k)`` (0), ``window (Q, k)`` int64 the window's ordinal within its video (-1), ``cell (Q, k, 2)`` int64 (-1),
+        ``count (Q,)`` int32; with ``duration (V,)`` seconds also ``times (Q, k, 2) = (span * duration[video]) / n_rows[video]`` (fp32, NaN
+        for empty slots).  The whole plan travels in one pinned asynchronous copy.  No host synchronisation."""
+        k, k_video, k_window, p = self._window_search_plan("search_windows", windows, queries, pairs, k, k_video, k_window, max_batch, duration)
+        require_hip_tensors("search_windows", dict(windows=windows.video_mask, queries=queries.query_features), must="hold HIP tensors")
+        dev, G, G2, Q, V = windows.device, p["wi"].shape[0], p["vi"].shape[0], len(queries), windows.n_videos
+        host = np.concatenate([p["wi"], p["wq"], p["group_ptr"], p["vi"], p["query_ptr"], windows.n_rows]).astype(np.int64)
+        with torch.no_grad(), torch.cuda.device(dev):
+            plan = torch.from_numpy(host).pin_memory().to(dev, non_blocking=True)
+            cut = np.cumsum([0, G, G, G2 + 1, G2, Q + 1, V])
+            wi_d, wq_d, gp_d, gv_d, qp_d, nr_d = (plan[cut[j]:cut[j + 1]] for j in range(6))
+            wi32, wq32 = wi_d.to(torch.int32), wq_d.to(torch.int32)
+            idx, score, count = self._pair_moments(windows, queries, p["wi"], p["wq"], wi32, wq32, k_window, nms_thresh, max_batch)
+            g = merge_window_moments(idx, score, count, windows.start.index_select(0, wi_d), windows.len.index_select(0, wi_d), gp_d,
+                                     self.T, self.L, k=k_video, nms_thresh=nms_thresh)
+            r = corpus_span_topk(g["span"], g["score"], g["window"], g["cell"], g["count"], gv_d.to(torch.int32), qp_d.to(torch.int32), k=k)
+            return r if duration is None else self._window_times(r, duration, nr_d)
+
+    def search_windows_torch(self, windows, queries, raw=None, pairs=None, k=5, k_video=None, k_window=None, nms_thresh=0.5, duration=None,
+                             max_batch=64, scorer=None):
+        """``search_windows`` restated: the same expansion and chunking, each chunk's windows sampled from ``raw`` (encode_windows'
+        ``raw``) and scored with their queries by localize_windows' own route (sample_windows, build_masks_hip, score() / the forward),
+        cut by top_moments, merged per group by moments.merge_window_moments_torch and ranked by moments.corpus_span_topk_torch.  Kept
+        under its own name as what the tests compare against -- nothing routes here.  ``scorer(window_index, query_index) -> (pm, ps,
+        pe, pa)`` replaces the sampling and the model on a chunk's (window, query) pairs (the tests feed it score_pairs, to compare the
+        selection on equal scores; with it ``raw`` is not read, and on CPU banks the cut is top_moments_torch)."""
+        what = "search_windows_torch"
+        k, k_video, k_window, p = self._window_search_plan(what, windows, queries, pairs, k, k_video, k_window, max_batch, duration)
+        if scorer is None and raw is None:
+            raise ValueError(f"{what}: needs raw, the rows the bank was encoded from, or a scorer")
+        dev, T, L, G = windows.device, self.T, self.L, p["wi"].shape[0]
+        cut_moments = top_moments if dev.type == "cuda" else top_moments_torch
+        idx, score, count, chunks = _chunk_buffers(G, k_window, max_batch, dev)
+        offs = np.concatenate([[0], np.cumsum(windows.n_rows)]).astype(np.int64)
+        video_of = np.repeat(np.arange(windows.n_videos), windows.video_ptr[1:] - windows.video_ptr[:-1])
+        qm = queries.query_mask[:, :queries.query_features.shape[1]]
+        with torch.no_grad():
+            for c0, c1 in chunks:
+                wi, wq = p["wi"][c0:c1], p["wq"][c0:c1]
+                if scorer is not None:
+                    pm, ps, pe, _ = scorer(wi, wq)
+                    mm = windows.moment_mask.index_select(0, torch.from_numpy(wi).to(dev))
+                else:
+                    vf, nfeats = sample_windows(raw, (offs[video_of[wi]] + windows.starts[wi]).tolist(), windows.lens[wi].tolist(), T, mode=windows.mode)
+                    m = build_masks_hip(nfeats, T, L)
+                    wq_d = torch.from_numpy(wq).to(dev)
+                    mm = m["moment_mask"]
+                    pm, ps, pe, _ = self._scores(vf, m["video_mask"], queries.query_features.index_select(0, wq_d), qm.index_select(0, wq_d),
+                                                 m["length_mask"], mm)
+                t = cut_moments(pm, ps, pe, mm, k=k_window, nms_thresh=nms_thresh)
+                idx[c0:c1], score[c0:c1], count[c0:c1] = t["idx"], t["score"], t["count"]
+            on = lambda a, dt=torch.int64: torch.from_numpy(np.ascontiguousarray(a)).to(device=dev, dtype=dt)
+            g = merge_window_moments_torch(idx, score, count, on(windows.starts[p["wi"]]), on(windows.lens[p["wi"]], torch.int32), on(p["group_ptr"]),
+                                           T, L, k=k_video, nms_thresh=nms_thresh)
+            r = corpus_span_topk_torch(g["span"], g["score"], g["window"], g["cell"], g["count"], on(p["vi"], torch.int32),
+                                       on(p["query_ptr"], torch.int32), k=k)
+            return r if duration is None else self._window_times(r, duration, on(windows.n_rows))
 
     # ---------------------------------------------------------------- hard-negative mining (INTEGRATION.md 3p)
     def pair_scores(self, videos, queries, max_batch=64):

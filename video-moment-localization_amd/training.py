@@ -546,3 +546,44 @@ def test_model_corpus(model, video_shards, queries, gt_video, gt_times, meter=No
 
 
 test_model_corpus.__test__ = False
+
+
+def test_model_corpus_windows(model, raw, lengths, queries, gt_video, gt_times, duration, meter=None, *, window=None, stride=None, k=25,
+                              k_video=5, k_window=None, nms_thresh=0.5, max_batch=64):
+    """The test loop of corpus search over videos of any length: VCMR R@n, IoU=m, VR R@n and mIoU of
+    ``model.search_windows``, with no host read beside the meter's one at the end.  ``raw (R, Din)`` / ``lengths``: the V videos' rows
+    back to back and their row counts, as ``encode_windows`` takes them; ``queries``: a dict with ``query_features`` and
+    ``query_mask``, encoded once; ``gt_video (Q,)``: each query's video, ``gt_times (Q, 2)`` its moment in seconds and ``duration (V,)``
+    the videos' lengths in seconds, all host values, which travel in one pinned asynchronous copy.  One ``encode_queries``, one
+    ``encode_windows``, one ``search_windows`` with the durations, one ``meter.update`` (meter.CorpusMeter; a default one is made if
+    none is given) and the one ``meter.result()``, which is returned.  The meter is not reset here.
+
+    VR@n is exact when ``k >= max(n) * k_video``, as in ``test_model_corpus``; anything less raises ValueError before any retrieval runs."""
+    import numpy as np
+    n_max = 5 if meter is None else max(meter.n)
+    if k < n_max or k < n_max * k_video:
+        raise ValueError(f"test_model_corpus_windows: k = {k} entries per query cannot give an exact R@{n_max} / VR@{n_max} at k_video = {k_video}: "
+                         f"needs k >= max(n) * k_video = {n_max * k_video}")
+    gv, gt, dur = host_array(gt_video), host_array(gt_times, np.float64, (-1, 2)), host_array(duration, np.float64)
+    Q, V = queries["query_features"].shape[0], host_array(lengths).shape[0]
+    if gv.shape[0] != Q or gt.shape[0] != Q:
+        raise ValueError(f"test_model_corpus_windows: gt_video (Q,) and gt_times (Q, 2) must cover the Q = {Q} queries (got {gv.shape}, {gt.shape})")
+    if dur.shape[0] != V or (Q and (gv.min() < 0 or gv.max() >= V)):
+        raise ValueError(f"test_model_corpus_windows: duration must be (V,) = ({V},) seconds and gt_video lie in [0, {V}) (got {dur.shape})")
+    model.eval()
+    dev = queries["query_features"].device
+    if meter is None:
+        from .meter import CorpusMeter
+        meter = CorpusMeter(device=dev)
+    # gt_video (int64, first: 8-byte aligned), then the durations and gt_times (fp32), as bytes of one pinned buffer: one asynchronous copy
+    host = np.concatenate([gv.astype(np.int64).view(np.uint8), np.concatenate([dur, gt.reshape(-1)]).astype(np.float32).view(np.uint8)])
+    buf = torch.from_numpy(host).pin_memory().to(dev, non_blocking=True)
+    gv_d, f32 = buf[:8 * Q].view(torch.int64), buf[8 * Q:].view(torch.float32)
+    bank = model.encode_queries(queries["query_features"], queries["query_mask"])
+    windows = model.encode_windows(raw, lengths, window=window, stride=stride, max_batch=max_batch)
+    r = model.search_windows(windows, bank, k=k, k_video=k_video, k_window=k_window, nms_thresh=nms_thresh, duration=f32[:V], max_batch=max_batch)
+    meter.update(r, gv_d, f32[V:].reshape(Q, 2))
+    return meter.result()
+
+
+test_model_corpus_windows.__test__ = False
