@@ -591,8 +591,11 @@ int smin_lstm_cluster_error(void);
 int smin_build_cells(void* stream, const uint8_t* mask, int B, int L, int all_cells,
                      int32_t* cells, int32_t* row_ptr, int32_t* cellmap);
 /* The same for a caller that already knows the number of listed cells (a captured step replays with the count it was captured
- * for: no device -> host round trip inside the step).  cells holds exactly n_expected entries; nothing is written past it, and
- * *status (device int32, cleared once by the caller) is set to 1 if the mask lists a different number of cells. */
+ * for: no device -> host round trip inside the step).  cells holds exactly n_expected entries and nothing is written past it.
+ * The caller gets the layout of the mask's first n_expected listed cells in (b, i, j) order: no row_ptr entry exceeds n_expected,
+ * a listed cell past the cut has cellmap -1, and where the mask lists fewer cells, entries total .. n_expected - 1 of cells are
+ * {0, 0, 0, 0} and belong to no row.  *status (device int32, cleared once by the caller) is set to 1 if the mask lists a
+ * different number of cells, and is left as found otherwise. */
 int smin_build_cells_n(void* stream, const uint8_t* mask, int B, int L, int all_cells, int n_expected,
                        int32_t* cells, int32_t* row_ptr, int32_t* cellmap, int32_t* status);
 

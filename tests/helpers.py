@@ -80,3 +80,37 @@ def smin_shapes(T, L, C, D, dl, layers, Din, Nq, H):
         s[f"localization.conv_layer_{n}.weight"] = (1, D, 1)
         s[f"localization.conv_layer_{n}.bias"] = (1,)
     return s
+
+
+LAYOUT_GUARD, LAYOUT_SENTINEL = 8, -777
+
+
+def build_cells(dev, mask_d, all_cells, n, n_expected=None, status=None):
+    """smin_build_cells (n_expected None) or smin_build_cells_n through the C ABI, on a uint8 (B, L, L) device mask, into outputs of n
+    cells with LAYOUT_GUARD sentinel entries behind each; returns (cells, row_ptr, cellmap) with their guards, on the device."""
+    import models
+    lib = models.vml_amd._lib
+    B, L, _ = mask_d.shape
+    cells = torch.full((n + LAYOUT_GUARD, 4), LAYOUT_SENTINEL, dtype=torch.int32, device=dev)
+    row_ptr = torch.full((B * L + 1 + LAYOUT_GUARD,), LAYOUT_SENTINEL, dtype=torch.int32, device=dev)
+    cellmap = torch.full((B * L * L + LAYOUT_GUARD,), LAYOUT_SENTINEL, dtype=torch.int32, device=dev)
+    if n_expected is None:
+        lib.call("smin_build_cells", lib.stream(), lib.ptr(mask_d), B, L, int(all_cells), lib.ptr(cells), lib.ptr(row_ptr), lib.ptr(cellmap))
+    else:
+        lib.call("smin_build_cells_n", lib.stream(), lib.ptr(mask_d), B, L, int(all_cells), int(n_expected), lib.ptr(cells), lib.ptr(row_ptr),
+                 lib.ptr(cellmap), lib.ptr(status))
+    return cells, row_ptr, cellmap
+
+
+def fail_unless_row_ptr_is_clamped(dev, moment_mask, n):
+    """The guard in front of every model-level run with a wrong cell count: the layout of the batch's own mask under that count, built
+    alone (that call is in bounds by itself).  Fails the test, before the model runs, if a row_ptr entry exceeds the count; returns
+    the call's status word."""
+    import pytest
+    mask_d = (moment_mask != 0).contiguous().view(torch.uint8)
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    _, row_ptr, _ = build_cells(dev, mask_d, 0, n, n, status)
+    worst = int(row_ptr[:mask_d.shape[0] * mask_d.shape[1] + 1].max())
+    if worst > n:
+        pytest.fail(f"smin_build_cells_n leaves row_ptr at {worst} for a count of {n}: the model is not run on that layout")
+    return int(status)

@@ -496,3 +496,31 @@ def test_overcounted_batch_makes_result_raise(dev):
     batches[1].cell_count -= 7
     meter.reset()
     assert api.eval_epoch(m, batches, meter)[1]["num_samples"] == 7
+
+
+@pytest.mark.gpu
+def test_undercounted_batch_makes_result_raise(dev):
+    """A cell_count lowered by 7: the forward runs on the layout of the mask's first count cells (csrc/layout.hip clamps row_ptr to the
+    count, so every per-cell index stays in bounds), the status word is set, result() raises naming it and clears it.  The layout of
+    that mask under that count is built alone first, and the epoch is not run if a row_ptr entry exceeds the count."""
+    api = V()
+    T, L, Nq, Din = 64, 16, 9, 40
+    batches = fed_copies(api, dev, T, L, Nq, Din, (4, 3), seed=14)
+    n = batches[1].cell_count - 7
+    assert n > 0
+    assert H.fail_unless_row_ptr_is_clamped(dev, batches[1]["moment_mask"], n) == 1
+    _, m = twin_models(dev, T, L, Din, Nq)
+    meter = api.EpochMeter(device=dev)
+    api.eval_epoch(m, batches, meter)                                            # clean epoch first
+    assert status_word(api, dev) == 0
+    batches[1].cell_count -= 7
+    meter.reset()
+    try:
+        with pytest.raises(RuntimeError, match="layout_status"):
+            api.eval_epoch(m, batches, meter)
+        assert status_word(api, dev) == 0 and m.known_cell_count is None
+    finally:
+        api._lib.load_torch().layout_status(dev).zero_()
+    batches[1].cell_count += 7
+    meter.reset()
+    assert api.eval_epoch(m, batches, meter)[1]["num_samples"] == 7

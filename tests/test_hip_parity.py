@@ -1530,6 +1530,8 @@ def test_captured_step_bit_identical_to_eager(dev):
     step = CapturedStep(m, None)
     for b in (b1, b2, b3, b1):
         want = eager(b)
+        for p in m.parameters():
+            p.grad = None                                          # the gradients below are the step's own, not eager's left in place
         loss, out = step(b)
         torch.cuda.synchronize()
         assert torch.equal(loss.detach(), want[0])

@@ -12,9 +12,9 @@
 // relaxed agent-scope atomic store (global_store_dwordx2 sc1) and polled with relaxed agent-scope atomic loads (sc1: served past
 // the L1) -- no flags, no fences, no L2 write-back.  Two granule buffers alternate by step parity: a workgroup writes step s + 2
 // only after it has read every other workgroup's step s + 1, which they publish only after reading all of step s -- so the
-// buffer it overwrites has been read by everyone.  The exchange buffer is cleared by a memset node ahead of each launch (tags
-// start at 1), so replays of a captured step see no stale tags.  Every poll is bounded: on expiry an error word is set and the
-// launch finishes with wrong values instead of hanging.
+// buffer it overwrites has been read by everyone.  The exchange buffer is cleared by a kernel of this file ahead of each launch
+// (cl_clear_kernel; tags start at 1), so replays of a captured step see no stale tags.  Every poll is bounded: on expiry an error
+// word is set and the launch finishes with wrong values instead of hanging.
 // Residency: the grid never exceeds one workgroup per CU (clusters loop over their sample groups), so every workgroup of a
 // cluster becomes resident without waiting for another workgroup of this launch to exit.  The grid is padded to whole groups of
 // 8 clusters (cluster_of), so the cluster count is capped at (CUs / (8 P)) * 8, not CUs / P: at P = 5, 6, 7 the latter padded
@@ -424,6 +424,28 @@ void bilstm_cluster_bwd_kernel(const float* __restrict__ dHout, const float* __r
     }
 }
 
+// Clears the exchange buffer ahead of a recurrence: every launch uses the same tags, so a granule left by the launch before would
+// pass for this launch's.  A kernel, where this used to be hipMemsetAsync.  Observed, cause not established: with the memset, a
+// captured step replayed after a replay of another batch's graph delivered wrong gradients for every LSTM parameter (the reverse
+// direction first; scores and all other gradients exact, the poll-expiry word clear), as the backward recurrence would from the
+// other batch's partial sums under valid tags; with this kernel in its place the same tests pass (tests/test_step_variants.py, the
+// replay tests).  Left unexplained: the forward recurrence cleared its buffer the same way and its scores stayed exact, and the
+// step's other memsets (linear_rows.hip, moment_unit.hip, score_map.hip) replay without trouble.  A clear that fails goes unseen
+// while one batch is replayed: the stale granules then are bit for bit the fresh ones.  n is a multiple of 16 (16-byte stores).
+__global__ __launch_bounds__(256)
+void cl_clear_kernel(unsigned long long* __restrict__ xch, size_t n)
+{
+    ulonglong2* x2 = reinterpret_cast<ulonglong2*>(xch);
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n / 2; i += (size_t)gridDim.x * 256) x2[i] = make_ulonglong2(0ull, 0ull);
+}
+static int cl_clear(hipStream_t st, unsigned long long* xch, size_t gran)
+{
+    const size_t blocks = (gran / 2 + 255) / 256;
+    hipLaunchKernelGGL(cl_clear_kernel, dim3((unsigned)(blocks < 1024 ? (blocks < 1 ? 1 : blocks) : 1024)), dim3(256), 0, st, xch, gran);
+    SMIN_LAUNCH_CHECK();
+    return 0;
+}
+
 // ---- launchers ----------------------------------------------------------------------------------------------------------------
 // Exchange buffers, one per (device, direction), allocated ONCE at the size the largest geometry needs on this device (the cluster
 // count is capped by the CU count, so the bound does not depend on the batch): forward <= 256 CUs + 64 H granules, backward
@@ -492,7 +514,7 @@ int launch_bilstm_cluster_fwd(hipStream_t st, float* G, const float* W4, const i
     unsigned long long* xch = cl_exchange(0, gran);
     if (!xch) return -2;
     if (cl_turn(st, false)) return -4;
-    if (P > 1 && hipMemsetAsync(xch, 0, gran * sizeof(unsigned long long), st) != hipSuccess) return -3;
+    if (P > 1 && cl_clear(st, xch, gran)) return -3;
     hipLaunchKernelGGL(bilstm_cluster_fwd_kernel, dim3(grid), dim3(256), lds, st, G, W4, len, B, Nq, H, P, nclus, Hout, Cs, xch);
     SMIN_LAUNCH_CHECK();
     return cl_turn(st, true);
@@ -509,7 +531,7 @@ int launch_bilstm_cluster_bwd(hipStream_t st, const float* dHout, const float* G
     unsigned long long* xch = cl_exchange(1, gran);
     if (!xch) return -2;
     if (cl_turn(st, false)) return -4;
-    if (P > 1 && hipMemsetAsync(xch, 0, gran * sizeof(unsigned long long), st) != hipSuccess) return -3;
+    if (P > 1 && cl_clear(st, xch, gran)) return -3;
     hipLaunchKernelGGL(bilstm_cluster_bwd_kernel, dim3(grid), dim3(256), lds, st, dHout, G, Cs, Whh, len, B, Nq, H, P, nclus, dG, xch);
     SMIN_LAUNCH_CHECK();
     return cl_turn(st, true);

@@ -9,8 +9,12 @@ namespace smin {
 
 // row_ptr[r + 1] = inclusive running count of listed cells over rows r = b*L + i; one workgroup, rows in chunks of 1024.
 // all_cells: every (b, i, j) is listed (count = L per row).
+// n_cap >= 0: the caller keeps the first n_cap listed cells only (layout_fill_kernel), so every entry is clamped to n_cap -- no
+// consumer that walks row_ptr[r] .. row_ptr[r + 1] leaves the n_cap entries of the per-cell tensors -- and *status becomes 1 when
+// the unclamped total is another number (the one place that still sees it).  n_cap < 0: the plain counts, status is not read.
 __global__ __launch_bounds__(1024)
-void layout_rows_kernel(const uint8_t* __restrict__ mask, int rows, int L, int all_cells, int* __restrict__ row_ptr)
+void layout_rows_kernel(const uint8_t* __restrict__ mask, int rows, int L, int all_cells, int* __restrict__ row_ptr, int n_cap,
+                        int* __restrict__ status)
 {
     __shared__ int part[1024];
     __shared__ int carry;
@@ -47,24 +51,29 @@ void layout_rows_kernel(const uint8_t* __restrict__ mask, int rows, int L, int a
             part[t] += v;
             __syncthreads();
         }
-        if (r < rows) row_ptr[r + 1] = carry + part[t];
+        if (r < rows) {
+            const int upto = carry + part[t];
+            row_ptr[r + 1] = n_cap >= 0 && upto > n_cap ? n_cap : upto;
+        }
         __syncthreads();
         if (t == 1023) carry += part[1023];
         __syncthreads();
     }
+    if (t == 0 && n_cap >= 0 && carry != n_cap) *status = 1;
 }
 
 // one wave per row (b, i): compacts the listed j's by ballot rank
 // n_cap >= 0: the caller sized `cells` for exactly n_cap entries without asking the device (a captured step replays with the count
-// it was captured for): nothing is written past n_cap, entries the mask does not fill are set to an inert in-range cell, and
-// *status becomes 1 when the mask lists a different number of cells -- the step's results are then meaningless, but in bounds.
+// it was captured for) and row_ptr is clamped to n_cap (layout_rows_kernel, which also raises the status word): the first n_cap
+// listed cells are kept, the others get cellmap -1 like any cell the mask leaves out, nothing is written past n_cap, and entries
+// the mask does not fill are set to an inert in-range cell that no row owns.  What comes out is the layout of the mask's first
+// n_cap cells: with a wrong count the step's results are those of another mask, but every index stays in bounds.
 __global__ __launch_bounds__(256)
 void layout_fill_kernel(const uint8_t* __restrict__ mask, const int* __restrict__ row_ptr, int rows, int L, int all_cells,
-                        int* __restrict__ cells, int* __restrict__ cellmap, int n_cap, int* __restrict__ status)
+                        int* __restrict__ cells, int* __restrict__ cellmap, int n_cap)
 {
     if (n_cap >= 0 && blockIdx.x == 0) {
-        const int total = row_ptr[rows];
-        if (threadIdx.x == 0 && total != n_cap) *status = 1;
+        const int total = row_ptr[rows];                                    // min(listed cells, n_cap)
         for (int id = total + (int)threadIdx.x; id < n_cap; id += 256) *reinterpret_cast<int4*>(cells + 4 * (size_t)id) = make_int4(0, 0, 0, 0);
     }
     const int r = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
@@ -100,25 +109,28 @@ extern "C" int smin_build_cells(void* stream, const uint8_t* mask, int B, int L,
     hipStream_t st = (hipStream_t)stream;
     SMIN_REQUIRE(B >= 1 && L >= 1);
     const int rows = B * L;
-    hipLaunchKernelGGL(layout_rows_kernel, dim3(1), dim3(1024), 0, st, mask, rows, L, all_cells, row_ptr);
+    hipLaunchKernelGGL(layout_rows_kernel, dim3(1), dim3(1024), 0, st, mask, rows, L, all_cells, row_ptr, -1, (int*)nullptr);
     SMIN_LAUNCH_CHECK();
-    hipLaunchKernelGGL(layout_fill_kernel, dim3(cdiv(rows, 4)), dim3(256), 0, st, mask, row_ptr, rows, L, all_cells, cells, cellmap, -1, (int*)nullptr);
+    hipLaunchKernelGGL(layout_fill_kernel, dim3(cdiv(rows, 4)), dim3(256), 0, st, mask, row_ptr, rows, L, all_cells, cells, cellmap, -1);
     SMIN_LAUNCH_CHECK();
     return 0;
 }
 
 // The same for a caller that knows the number of listed cells already (n_expected, e.g. a captured step: no device -> host round
-// trip inside the step).  `cells` holds exactly n_expected entries; *status (device, int32) is set to 1 if the mask lists another
-// number -- see layout_fill_kernel.  The caller clears *status once and reads it when convenient.
+// trip inside the step).  `cells` holds exactly n_expected entries.  The caller gets the layout of the mask's first n_expected
+// listed cells in (b, i, j) order: row_ptr never exceeds n_expected, a listed cell past the cut has cellmap -1, and where the mask
+// lists fewer, entries total .. n_expected - 1 of `cells` are {0, 0, 0, 0} and belong to no row.  *status (device, int32) is set to
+// 1 if the mask lists another number than n_expected and is left as found otherwise: the caller clears it once and reads it when
+// convenient.
 extern "C" int smin_build_cells_n(void* stream, const uint8_t* mask, int B, int L, int all_cells, int n_expected,
                                   int32_t* cells, int32_t* row_ptr, int32_t* cellmap, int32_t* status)
 {
     hipStream_t st = (hipStream_t)stream;
     SMIN_REQUIRE(B >= 1 && L >= 1 && n_expected >= 0 && status != nullptr);
     const int rows = B * L;
-    hipLaunchKernelGGL(layout_rows_kernel, dim3(1), dim3(1024), 0, st, mask, rows, L, all_cells, row_ptr);
+    hipLaunchKernelGGL(layout_rows_kernel, dim3(1), dim3(1024), 0, st, mask, rows, L, all_cells, row_ptr, n_expected, status);
     SMIN_LAUNCH_CHECK();
-    hipLaunchKernelGGL(layout_fill_kernel, dim3(cdiv(rows, 4)), dim3(256), 0, st, mask, row_ptr, rows, L, all_cells, cells, cellmap, n_expected, status);
+    hipLaunchKernelGGL(layout_fill_kernel, dim3(cdiv(rows, 4)), dim3(256), 0, st, mask, row_ptr, rows, L, all_cells, cells, cellmap, n_expected);
     SMIN_LAUNCH_CHECK();
     return 0;
 }
