@@ -10,7 +10,8 @@
  * Conventions
  *   - every pointer is a DEVICE pointer to contiguous fp32 unless stated; `stream` is a hipStream_t.
  *   - all calls are asynchronous on `stream`, allocate nothing and never synchronise (graph-capturable);
- *     scratch comes from the caller-provided workspace `ws` (size from smin_workspace_bytes).
+ *     scratch comes from the caller-provided workspace `ws`; each entry point that takes one names the query for its size
+ *     (smin_<entry>_ws_bytes or _workspace_bytes: a pure host function of the entry point's own shape arguments).
  *   - return 0 on success, a positive hipError_t, or a negative code for a rejected argument.
  *   - requirements: D % 4 == 0, dl % 16 == 0, 16 <= dl <= 128, 2 <= C <= 4, Nq <= 32.
  *
@@ -57,7 +58,10 @@ extern "C" {
  * -- smin_mine_pairs and smin_mine_pairs_ws_bytes (each query's own video and its highest-scoring wrong ones as the pair lists and both
  * groupings smin_pair_assemble_bwd reads); a contrastive loss over a pair plan -- smin_pair_rank_fwd, smin_pair_rank_bwd and
  * smin_pair_rank_ws_bytes (each query's own video ranked above the wrong ones it was paired with); corpus search over
- * banks of windows of long videos -- smin_corpus_span_topk (one ranked list of span-valued moments per query across videos) */
+ * banks of windows of long videos -- smin_corpus_span_topk (one ranked list of span-valued moments per query across videos); an exact
+ * workspace size query for each entry point that had none -- smin_proposal_map_fwd_ws_bytes, smin_proposal_map_bwd_ws_bytes,
+ * smin_clip_window_means_fwd_ws_bytes, smin_clip_window_means_bwd_ws_bytes, smin_gate_bwd_ws_bytes, smin_moment_unit_bwd_ws_bytes,
+ * smin_score_map_bwd_ws_bytes and smin_content_unit_bwd_ws_bytes (smin_workspace_bytes is now their maximum) */
 #define SMIN_HIP_ABI_VERSION 2
 
 int smin_abi_version(void);
@@ -85,22 +89,30 @@ int smin_prof_enable(int on);
 int smin_prof_read(int32_t* tags, float* ms, int cap);
 /* "gfx950" -- the only code object in the library */
 const char* smin_target_arch(void);
-/* bytes of scratch any single call below may need for N cells (C, D, dl, Nq, B as given) */
+/* The old catch-all scratch size, kept for callers built against it; new code asks the entry point's own query.  It is the largest
+ * of smin_content_unit_bwd_ws_bytes(N, B, C, D, dl, 0), smin_moment_unit_bwd_ws_bytes(N, B, L, D) and smin_score_map_bwd_ws_bytes(N, B,
+ * L, D); a query that rejects the arguments contributes nothing.  It was never given the map side and takes L = 64: that matters to the
+ * score map's term alone, and a list of N >= B * L cells is covered at any L by the moment unit's term.  (Nq is not used.) */
 size_t smin_workspace_bytes(int N, int B, int C, int D, int dl, int Nq);
 
 /* ---- ProposalGeneration.forward (models.py:115-126) with compute_content_matrix (models.py:88-98)
  * as index arithmetic: fc[n,c,:] = mean of f[b, start..start+cs) per clip, fm = mean_c fc (divides by C),
- * fb = AvgPool1d(T/L) over time.  f [B][T][D]; fc [N][C][D]; fm [N][D]; fb [B][L][D]. */
+ * fb = AvgPool1d(T/L) over time.  f [B][T][D]; fc [N][C][D]; fm [N][D]; fb [B][L][D].
+ * ws_bytes >= smin_proposal_map_fwd_ws_bytes(B, T, D) (0 = arguments rejected: D % 4, D > 2048). */
+size_t smin_proposal_map_fwd_ws_bytes(int B, int T, int D);
 int smin_proposal_map_fwd(void* stream, const float* f, const int32_t* cells, int N, int B, int T, int L, int C, int D,
-                          float* fc, float* fm, float* fb, void* ws, size_t ws_bytes /* >= 8*B*(T+1)*D */);
+                          float* fc, float* fm, float* fb, void* ws, size_t ws_bytes);
 /* (any of fc/fm/fb may be NULL = not wanted) */
 /* The clip-boundary table of a geometry (T, L, C): which clip of which (i, j) starts / ends at each frame -- the
  * sparsity pattern of the reference's cached content matrix (models.py:88-98, 110).  Build once per geometry: call
  * with table == NULL to get counts [T]; form the exclusive prefix offsets [T+1]; call with counts == NULL to fill
  * table (8 bytes per entry, offsets[T] entries). */
 int smin_clip_event_table(void* stream, int T, int L, int C, int32_t* counts, const int32_t* offsets, void* table);
-/* df [B][T][D] = d/df of the three outputs (any of dfc/dfm/dfb may be NULL = zero).  ws_bytes >= 4*B*T*D.
+/* df [B][T][D] = d/df of the three outputs (any of dfc/dfm/dfb may be NULL = zero).
+ * ws_bytes >= smin_proposal_map_bwd_ws_bytes(B, T, D) (0 = arguments rejected: D % 4, D > 2048); the workspace is neither read nor
+ * checked when N == 0 or dfc == dfm == NULL.
  * ev_offsets / ev_table: the geometry's clip-boundary table (NULL, NULL = derive the boundaries in-kernel, slower). */
+size_t smin_proposal_map_bwd_ws_bytes(int B, int T, int D);
 int smin_proposal_map_bwd(void* stream, const float* dfc, const float* dfm, const float* dfb,
                           const int32_t* cells, const int32_t* row_ptr, const int32_t* cellmap,
                           int N, int B, int T, int L, int C, int D, float* df, void* ws, size_t ws_bytes,
@@ -117,7 +129,9 @@ int smin_gate_fwd_sum(void* stream, const float* fm, const float* fs, const int3
                       float* hsum_out);
 /* boundary_A [B][L][L], boundary_dout [B][L][D] (both or neither; cells [N][4] then required): the boundary unit's consumer of hbar,
  * f_bm[b,i] = sum_j A[b,i,j] hbar[b,i,j] (models.py:191-194), enters as A[b,i,j] * boundary_dout[b,i,:] formed on the fly -- pass the
- * unit's saved attention A and the gradient of its output, and call smin_boundary_unit_bwd with dhbar == NULL. */
+ * unit's saved attention A and the gradient of its output, and call smin_boundary_unit_bwd with dhbar == NULL.
+ * ws_bytes >= smin_gate_bwd_ws_bytes(B, L, D) (0 = arguments rejected: D % 4). */
+size_t smin_gate_bwd_ws_bytes(int B, int L, int D);
 int smin_gate_bwd(void* stream, const float* const* dhbar, int n_dhbar, const float* const* dres, int n_dres,
                   const float* fm, const float* fs, const int32_t* row_ptr,
                   int N, int B, int L, int D, float* dfm, float* dfs, void* ws, size_t ws_bytes,
@@ -144,7 +158,10 @@ int smin_content_unit_fwd(void* stream, const float* fc, const float* hbar, cons
  * same `last` as in forward (then dfc_out must be NULL and cchat is the [N][dl] clip mean).
  * WcT [dl][D] and WchT [D][dl] are transposed copies of the weights.
  * Gradients: dfc [N][C][D], dhbar [N][D], dWch [dl][D], dbch [dl], dMq [B][Nq][dl], duq [B][Nq],
- * dwhat [B][Nq][dl], dshat [B][dl], dWc [D][dl], dbc [D]. */
+ * dwhat [B][Nq][dl], dshat [B][dl], dWc [D][dl], dbc [D].
+ * ws_bytes >= smin_content_unit_bwd_ws_bytes(N, B, C, D, dl, last) (0 = arguments rejected: D % 4, dl % 16, dl outside 16..128,
+ * C outside 2..4); N == 0 is a no-op that reads no workspace. */
+size_t smin_content_unit_bwd_ws_bytes(int N, int B, int C, int D, int dl, int last);
 int smin_content_unit_bwd(void* stream, const float* dfc_out, const float* dfcmean,
                           const float* fc, const int32_t* cells, const int32_t* row_ptr,
                           int N, int B, int L, int C, int D, int dl, int Nq,
@@ -198,7 +215,10 @@ int smin_pair_product(void* stream, const float* fb, const int32_t* cells, int N
 /* WcatT [2D][D].  dfcmean [N][D], dfb [B][L][D], dWcat [D][2D], dbcat [D]; the residual gradient
  * d mu / d fm is the identity and is left to the caller (dfm += dmu).  Either half may be skipped: dfcmean == dfb == NULL
  * computes only the weight gradients, dWcat == dbcat == NULL only the input gradients (the halves share nothing but
- * dmu, so a host may run them on two streams; each call needs its own workspace). */
+ * dmu, so a host may run them on two streams; each call needs its own workspace).
+ * ws_bytes >= smin_moment_unit_bwd_ws_bytes(N, B, L, D) (0 = arguments rejected: D % 4, D > 2048): one layout for either half, for
+ * the whole, and for smin_moment_unit_bwd_x1h. */
+size_t smin_moment_unit_bwd_ws_bytes(int N, int B, int L, int D);
 int smin_moment_unit_bwd(void* stream, const float* dmu, const float* fcmean, const float* fb, const int32_t* cells,
                          const int32_t* row_ptr, const int32_t* cellmap, int N, int B, int L, int D, const float* WcatT,
                          float* dfcmean, float* dfb, float* dWcat, float* dbcat, void* ws, size_t ws_bytes,
@@ -241,7 +261,9 @@ int smin_score_tail_fwd(void* stream, const float* ccmean, const float* cumean, 
                         const float* Wcat, const float* bcat, const float* wm, const float* bm, const float* wb /* [3][D] */,
                         const float* bb /* [3] */, const float* lmask, float* pm, float* psea, void* ws, size_t ws_bytes);
 /* dpm [B][L][L], dpsea [3][B][L] -> dfm [N][D], dfb [B][L][D], dwm [D], dbm [1], dwb [3][D], dbb [3].  Two independent halves
- * (map score: dpm -> dfm, dwm, dbm; boundary heads: dpsea -> dfb, dwb, dbb): dpm == NULL or dpsea == NULL skips one (two streams). */
+ * (map score: dpm -> dfm, dwm, dbm; boundary heads: dpsea -> dfb, dwb, dbb): dpm == NULL or dpsea == NULL skips one (two streams).
+ * ws_bytes >= smin_score_map_bwd_ws_bytes(N, B, L, D) (0 = arguments rejected: D % 4), which covers both halves. */
+size_t smin_score_map_bwd_ws_bytes(int N, int B, int L, int D);
 int smin_score_map_bwd(void* stream, const float* dpm, const float* dpsea, const float* pm, const float* psea,
                        const float* fm, const float* fb, const int32_t* cells, int N, int B, int L, int D,
                        const float* wm, const float* wb, const float* lmask,
@@ -447,11 +469,15 @@ int smin_corpus_meter_update(void* stream, const int64_t* video, const float* sp
  * (modules.py: SMIN.forward) composes them under autograd.  Requires a mask-driven cell list (m == 1 everywhere). */
 
 /* out[s][n*C + c][:] = m * (mean over clip c of cell n of g[b][t][s*W:(s+1)*W] + bias[s*W:(s+1)*W])
- * g [B][T][nseg*W] (nseg <= 8: one segment per layer), out [nseg][N*C][W]; ws >= 8*B*(T+1)*nseg*W bytes. */
+ * g [B][T][nseg*W] (nseg <= 8: one segment per layer), out [nseg][N*C][W];
+ * ws_bytes >= smin_clip_window_means_fwd_ws_bytes(B, T, W, nseg) (0 = arguments rejected: W % 4, nseg outside 1..8, nseg*W > 2048). */
+size_t smin_clip_window_means_fwd_ws_bytes(int B, int T, int W, int nseg);
 int smin_clip_window_means_fwd(void* stream, const float* g, const float* bias /* [bias_len], first features only */, int bias_len,
                                const int32_t* cells, int N, int B, int T, int L, int C,
                                int W, int nseg, float* out, void* ws, size_t ws_bytes);
-/* dout: HOST array of nseg device pointers, dout[s] [N*C][W] -> dg [B][T][nseg*W]; ws >= 4*B*T*nseg*W bytes. */
+/* dout: HOST array of nseg device pointers, dout[s] [N*C][W] -> dg [B][T][nseg*W];
+ * ws_bytes >= smin_clip_window_means_bwd_ws_bytes(B, T, W, nseg) (0 = rejected, as above); neither read nor checked when N == 0. */
+size_t smin_clip_window_means_bwd_ws_bytes(int B, int T, int W, int nseg);
 int smin_clip_window_means_bwd(void* stream, const float* const* dout, const int32_t* cells, const int32_t* row_ptr,
                                const int32_t* cellmap, int N, int B, int T, int L, int C, int W, int nseg, float* dg,
                                void* ws, size_t ws_bytes, const int32_t* ev_offsets, const void* ev_table);

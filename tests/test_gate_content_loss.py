@@ -722,7 +722,7 @@ def _run_content_unit(dev, case, label):
         if not last:
             assert torch.equal(fc_out[dead], (d["fc"] + d["hbar"].unsqueeze(1))[dead]), (label, "fc_out of a masked cell is fc + hbar")
 
-    nbytes = models.vml_amd._lib.load().smin_workspace_bytes(N, B, C, D, dl, Nq)
+    nbytes = models.vml_amd._lib.load().smin_content_unit_bwd_ws_bytes(N, B, C, D, dl, int(last))
     WchT, WcT = d["Wch"].t().contiguous(), d["Wc"].t().contiguous()
     dfc_out = G_out.float().to(dev) if variant == "dfc" else None
     dfcmean = G_mean.float().to(dev)
@@ -747,7 +747,7 @@ def _run_content_unit(dev, case, label):
 @pytest.mark.parametrize("case", CU_CASES, ids=[_cu_id(c) for c in CU_CASES])
 def test_content_unit_against_fp64(dev, case):
     """smin_content_unit_fwd / _bwd: chat, cchat (the clip mean when last), fc_out, fcmean and all ten gradients, on a workspace of
-    exactly smin_workspace_bytes.  EpLastMean on 128-row main tiles would need more than 32 768 cells and is left to the engine
+    exactly its query (smin_content_unit_bwd_ws_bytes).  EpLastMean on 128-row main tiles would need more than 32 768 cells and is left to the engine
     tests (tests/test_gemm_engine.py): the last form of the first large case runs its final GEMM as a mini launch on N rows."""
     _run_content_unit(dev, case, _cu_id(case))
 

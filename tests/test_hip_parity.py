@@ -1110,7 +1110,7 @@ def test_step_helpers_through_the_c_abi(dev):
     r = lambda *s: torch.randn(*s, generator=g).to(dev)
     dmu, fcm, fb, x1, acc = r(N, D), r(N, D), r(B, L, D), r(N, D), r(N, D)
     WT = (r(2 * D, D) * 0.1).contiguous()
-    nb = lib.smin_workspace_bytes(N, B, 4, D, 4, 1)
+    nb = max(lib.smin_moment_unit_bwd_ws_bytes(N, B, L, D), lib.smin_score_map_bwd_ws_bytes(N, B, L, D))   # one buffer serves both below
     ws = torch.empty(nb, dtype=torch.uint8, device=dev)
 
     def mu_bwd(want_in, want_w):

@@ -77,6 +77,54 @@ def test_library_exports_every_declared_symbol():
     assert loaded.smin_workspace_bytes(1000, 2, 4, 512, 128, 20) > 0
 
 
+# (B, T, L, C, D, dl, Nq): the small, split and empty lists of the workspace tests (tests/test_workspace_queries.py) and the five
+# BASELINE workloads (bench.py WORKLOADS); N is the upper-triangular count unless given
+_WS_SHAPES = [(2, 16, 8, 3, 64, 16, 5), (5, 32, 16, 2, 64, 16, 5), (64, 256, 64, 4, 512, 128, 20), (64, 128, 64, 4, 512, 128, 20),
+              (32, 64, 16, 4, 512, 128, 13), (2, 128, 32, 4, 512, 128, 14), (16, 1024, 512, 4, 512, 128, 20)]
+_WS_COMPAT_L = 64                                          # include/smin_hip.h: the map side smin_workspace_bytes assumes
+
+
+def _ws_cell_counts(B, L):
+    full = B * L * (L + 1) // 2
+    return sorted({0, 1, full - L // 2, full})              # empty, one cell, ragged (one sample's last rows cut), every valid cell
+
+
+def test_workspace_bytes_is_the_maximum_of_the_unit_queries():
+    """smin_workspace_bytes, the old catch-all, has no arithmetic of its own: it is the largest of the three unit backwards' queries,
+    the content unit's at last == 0 and the score map's at L = 64 (it was never given L); a rejecting query contributes nothing.
+    Any list with N >= B * L cells is covered at its own L as well."""
+    import models
+    lib = models.vml_amd._lib.load()
+    for B, T, L, C, D, dl, Nq in _WS_SHAPES:
+        for N in _ws_cell_counts(B, L):
+            content = [lib.smin_content_unit_bwd_ws_bytes(N, B, C, D, dl, last) for last in (0, 1)]
+            moment, score = lib.smin_moment_unit_bwd_ws_bytes(N, B, L, D), lib.smin_score_map_bwd_ws_bytes(N, B, L, D)
+            assert content[0] >= content[1] > 0 and moment > 0 and score > 0
+            got = lib.smin_workspace_bytes(N, B, C, D, dl, Nq)
+            assert got == max(content[0], moment, lib.smin_score_map_bwd_ws_bytes(N, B, _WS_COMPAT_L, D)), (B, L, N)
+            if N >= B * L or L <= _WS_COMPAT_L:
+                assert got >= max(content[0], moment, score), (B, L, N)
+    # a rejecting query contributes nothing: the moment unit refuses D > 2048, the content unit dl = 8, both D % 4 != 0
+    assert lib.smin_moment_unit_bwd_ws_bytes(100, 2, 8, 2052) == 0
+    assert lib.smin_workspace_bytes(100, 2, 4, 2052, 16, 5) == max(lib.smin_content_unit_bwd_ws_bytes(100, 2, 4, 2052, 16, 0),
+                                                                     lib.smin_score_map_bwd_ws_bytes(100, 2, _WS_COMPAT_L, 2052))
+    assert lib.smin_workspace_bytes(100, 2, 4, 64, 8, 5) == max(lib.smin_moment_unit_bwd_ws_bytes(100, 2, 8, 64),
+                                                                 lib.smin_score_map_bwd_ws_bytes(100, 2, _WS_COMPAT_L, 64))
+    assert lib.smin_workspace_bytes(100, 2, 4, 66, 16, 5) == 0
+
+
+def test_workspace_bytes_covers_the_benchmarks_moment_unit_call():
+    """bench.py sizes smin_moment_unit_bwd's workspace with smin_workspace_bytes(N, B, 4, D, 4, 1): at the headline workload and for
+    L up to 512 that is no less than the unit's own query."""
+    import models
+    lib = models.vml_amd._lib.load()
+    D = 512
+    for B, L in [(64, 64)] + [(b, l) for l in (8, 16, 32, 64, 128, 256, 512) for b in (1, 16)]:
+        for N in _ws_cell_counts(B, L):
+            need = lib.smin_moment_unit_bwd_ws_bytes(N, B, L, D)
+            assert 0 < need <= lib.smin_workspace_bytes(N, B, 4, D, 4, 1), (B, L, N)
+
+
 def test_torch_extension_registers_operators():
     """csrc/torch_binding.cpp: TORCH_LIBRARY(smin_hip) loads without a GPU, exposes the two operators with the documented
     schemas, and refuses CPU tensors (no CPU fallback behind the extension either) -- called with SMIN's own options, which
@@ -386,6 +434,14 @@ def test_ctypes_table_rows_match_the_header():
         "smin_adam_ws_bytes": ([i64, i], sz),
         "smin_gate_bwd": ([vp, vp, i, vp, i, vp, vp, vp, i, i, i, i, vp, vp, vp, sz, vp, vp, vp], i),
         "smin_linear_rows_fwd": ([vp, vp, i, vp, vp, vp, vp, i, i, i, i, vp], i),
+        "smin_proposal_map_fwd_ws_bytes": ([i, i, i], sz),
+        "smin_proposal_map_bwd_ws_bytes": ([i, i, i], sz),
+        "smin_clip_window_means_fwd_ws_bytes": ([i, i, i, i], sz),
+        "smin_clip_window_means_bwd_ws_bytes": ([i, i, i, i], sz),
+        "smin_gate_bwd_ws_bytes": ([i, i, i], sz),
+        "smin_moment_unit_bwd_ws_bytes": ([i, i, i, i], sz),
+        "smin_score_map_bwd_ws_bytes": ([i, i, i, i], sz),
+        "smin_content_unit_bwd_ws_bytes": ([i, i, i, i, i, i], sz),
     }
     for name, (args, ret) in rows.items():
         assert _lib.SIGNATURES[name] == args, name

@@ -882,7 +882,7 @@ def test_moment_unit_against_fp64(dev, case):
     _check(label, "mu", mu, mu0, FWD_TOL, worst, "f")
 
     WcatT = d["Wcat"].t().contiguous()
-    nbytes = models.vml_amd._lib.load().smin_workspace_bytes(N, B, 4, D, 4, 1)
+    nbytes = models.vml_amd._lib.load().smin_moment_unit_bwd_ws_bytes(N, B, L, D)
     G_d, am_d, ab_d = G.float().to(dev), acc_m.float().to(dev), acc_b.float().to(dev)
     fn = "smin_moment_unit_bwd_x1h" if operand == "x1h" else "smin_moment_unit_bwd"
 
@@ -947,7 +947,7 @@ def test_score_map_against_fp64(dev, case):
     _check(label, "pm", pm, pm0, FWD_TOL, worst, "f")
     _check(label, "psea", psea, psea0, FWD_TOL, worst, "f")
     assert torch.all(pm.cpu()[lay.cellmap < 0] == 0), (label, "a cell absent from the list must score 0")
-    nbytes = models.vml_amd._lib.load().smin_workspace_bytes(N, B, 4, D, 4, 1)
+    nbytes = models.vml_amd._lib.load().smin_score_map_bwd_ws_bytes(N, B, L, D)
     Gm_d, Gs_d = Gm.float().to(dev), Gs.float().to(dev)
 
     def run(with_pm, with_sea):

@@ -130,7 +130,11 @@ def stream():
 
 def workspace(nbytes, device):
     """Persistent scratch buffer per (device, stream), grown on demand: calls on one stream are stream-ordered, and
-    units running side by side on two streams never share scratch."""
+    units running side by side on two streams never share scratch.  Inside a stream capture the scratch is a fresh tensor of the
+    graph's own memory pool: a captured graph keeps the pointer it is given, and the persistent buffer is replaced by the next larger
+    request."""
+    if device.type == "cuda" and torch.cuda.is_current_stream_capturing():
+        return torch.empty(max(int(nbytes), 16), dtype=torch.uint8, device=device)
     key = (device.type, device.index, torch.cuda.current_stream(device).cuda_stream if device.type == "cuda" else 0)
     buf = _ws.get(key)
     if buf is None or buf.numel() < nbytes:

@@ -168,6 +168,31 @@ extern "C" int smin_content_unit_fwd(void* stream, const float* fc, const float*
     return 0;
 }
 
+// The backward's workspace, as float offsets (16-byte aligned pieces); smin_content_unit_bwd_ws_bytes reports `end`.
+struct CuBwdWs {
+    int sp1, sp2;
+    size_t dcchat, dchat, slab1, bslab1, slab2, bslab2, aws, end;
+    CuBwdWs(int N, int B, int C, int D, int dl, int last) : sp1(tn_splits(last ? N : N * C, D, dl)), sp2(tn_splits(N * C, dl, D))
+    {
+        const size_t M = (size_t)N * C;
+        size_t off = 0;
+        auto take = [&](size_t n) { const size_t o = off; off += (n + 3) & ~(size_t)3; return o; };
+        dcchat = take(M * dl);
+        dchat = take(M * dl);
+        slab1 = take((size_t)sp1 * D * dl); bslab1 = take((size_t)sp1 * D);
+        slab2 = take((size_t)sp2 * dl * D); bslab2 = take((size_t)sp2 * dl);
+        aws = take(content_attn_bwd_ws_floats(N, B, dl));
+        end = off;
+    }
+};
+static bool cu_shape_ok(int C, int D, int dl) { return D % 4 == 0 && dl % 16 == 0 && dl >= 16 && dl <= 128 && C >= 2 && C <= 4; }
+
+extern "C" size_t smin_content_unit_bwd_ws_bytes(int N, int B, int C, int D, int dl, int last)
+{
+    if (!cu_shape_ok(C, D, dl)) return 0;
+    return CuBwdWs(N, B, C, D, dl, last).end * sizeof(float);
+}
+
 template <bool HAS_DFC>
 static int content_unit_bwd_impl(hipStream_t st, const float* dfc_out, const float* dfcmean,
                                  const float* fc, const int32_t* cells, const int32_t* row_ptr,
@@ -180,16 +205,15 @@ static int content_unit_bwd_impl(hipStream_t st, const float* dfc_out, const flo
 {
     const int M = N * C;
     const float invC = 1.0f / C;
+    const CuBwdWs lay(N, B, C, D, dl, last);
+    SMIN_REQUIRE(lay.end * sizeof(float) <= ws_bytes);
     float* w = reinterpret_cast<float*>(ws);
-    size_t off = 0;
-    auto take = [&](size_t n) { float* p = w + off; off += (n + 3) & ~(size_t)3; return p; };
-    float* dcchat = take((size_t)M * dl);
-    float* dchat = take((size_t)M * dl);
-    const int sp1 = tn_splits(last ? N : M, D, dl), sp2 = tn_splits(M, dl, D);
-    float* slab1 = take((size_t)sp1 * D * dl); float* bslab1 = take((size_t)sp1 * D);
-    float* slab2 = take((size_t)sp2 * dl * D); float* bslab2 = take((size_t)sp2 * dl);
-    float* aws = take(content_attn_bwd_ws_floats(N, B, dl));
-    SMIN_REQUIRE(off * sizeof(float) <= ws_bytes);
+    float* dcchat = w + lay.dcchat;
+    float* dchat = w + lay.dchat;
+    const int sp1 = lay.sp1, sp2 = lay.sp2;
+    float* slab1 = w + lay.slab1; float* bslab1 = w + lay.bslab1;
+    float* slab2 = w + lay.slab2; float* bslab2 = w + lay.bslab2;
+    float* aws = w + lay.aws;
     const DoutEffMat<true, HAS_DFC> dout{dfc_out, dfcmean, cells, C, D, invC};
 
     int rc;
@@ -241,7 +265,7 @@ extern "C" int smin_content_unit_bwd(void* stream, const float* dfc_out, const f
 {
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     SMIN_REQUIRE(!(last && dfc_out));                           // "last" means nothing consumed fc_out itself
-    SMIN_REQUIRE(D % 4 == 0 && dl % 16 == 0 && dl >= 16 && dl <= 128 && C >= 2 && C <= 4 && Nq >= 1 && Nq <= 32);
+    SMIN_REQUIRE(cu_shape_ok(C, D, dl) && Nq >= 1 && Nq <= 32);
     if (N == 0) return 0;
     if (dfc_out)
         return content_unit_bwd_impl<true>(st, dfc_out, dfcmean, fc, cells, row_ptr, N, B, L, C, D, dl, Nq, WchT, Mq, uq, what, shat, qmask,

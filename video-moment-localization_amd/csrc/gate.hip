@@ -142,6 +142,20 @@ extern "C" int smin_gate_fwd_sum(void* stream, const float* fm, const float* fs,
     return 0;
 }
 
+// The backward's workspace, one piece at offset 0: the chunks' partial sums of dfs, partial [B][mc][D]; the size query and the entry
+// point both read this.
+struct GateBwdWs {
+    int cpc, mc;
+    size_t end;                                        // floats
+    GateBwdWs(int B, int L, int D) { chunking_fine(L, &cpc, &mc); end = (size_t)B * mc * D; }
+};
+
+extern "C" size_t smin_gate_bwd_ws_bytes(int B, int L, int D)
+{
+    if (D % 4 != 0) return 0;
+    return GateBwdWs(B, L, D).end * sizeof(float);
+}
+
 extern "C" int smin_gate_bwd(void* stream, const float* const* dhbar, int n_dhbar, const float* const* dres, int n_dres,
                              const float* fm, const float* fs, const int32_t* row_ptr,
                              int N, int B, int L, int D, float* dfm, float* dfs, void* ws, size_t ws_bytes,
@@ -150,8 +164,9 @@ extern "C" int smin_gate_bwd(void* stream, const float* const* dhbar, int n_dhba
     SMIN_REQUIRE((boundary_A == nullptr) == (boundary_dout == nullptr) && (boundary_A == nullptr || cells != nullptr || N == 0));
     hipStream_t st = (hipStream_t)stream;
     SMIN_REQUIRE(D % 4 == 0 && n_dhbar >= 1 && n_dhbar <= 4 && n_dres >= 0 && n_dres <= 4);
-    int cpc, mc; chunking_fine(L, &cpc, &mc);
-    SMIN_REQUIRE(ws_bytes >= sizeof(float) * (size_t)B * mc * D);
+    const GateBwdWs lay(B, L, D);
+    SMIN_REQUIRE(lay.end * sizeof(float) <= ws_bytes);
+    const int cpc = lay.cpc, mc = lay.mc;
     float* partial = reinterpret_cast<float*>(ws);
     GradList gh, gr;
     for (int k = 0; k < 4; ++k) { gh.p[k] = dhbar[k < n_dhbar ? k : 0]; gr.p[k] = n_dres > 0 ? dres[k < n_dres ? k : 0] : nullptr; }

@@ -151,19 +151,42 @@ extern "C" int smin_pair_product(void* stream, const float* fb, const int32_t* c
     return 0;
 }
 
+// The backward's workspace, as float offsets (16-byte aligned pieces), one layout for either half and both entry points;
+// smin_moment_unit_bwd_ws_bytes reports `end`.
+struct MuBwdWs {
+    int sp;
+    size_t dx1, slab, bslab, end;
+    MuBwdWs(int N, int D) : sp(N > 0 ? tn_splits(N, D, 2 * D) : 1)
+    {
+        dx1 = 0;                                                   // [N][D]: the pair half of dX, read by moment_dfb_kernel
+        slab = dx1 + (((size_t)N * D + 3) & ~(size_t)3);           // [sp][D][2D]
+        bslab = slab + (size_t)sp * D * 2 * D;                     // [sp][D]
+        end = bslab + (size_t)sp * D;
+    }
+};
+static bool mu_bwd_width_ok(int D) { return D % 4 == 0 && D <= 2048; }
+
+extern "C" size_t smin_moment_unit_bwd_ws_bytes(int N, int B, int L, int D)
+{
+    (void)B; (void)L;
+    if (!mu_bwd_width_ok(D)) return 0;
+    return MuBwdWs(N, D).end * sizeof(float);
+}
+
 static int moment_unit_bwd(void* stream, const float* dmu, const float* fcmean, const float* fb, const int32_t* cells,
                            const int32_t* row_ptr, const int32_t* cellmap, int N, int B, int L, int D, const float* WcatT,
                            float* dfcmean, float* dfb, float* dWcat, float* dbcat, void* ws, size_t ws_bytes, int all_valid,
                            const float* dfcmean_acc, const float* x1, const unsigned short* x1h, const float* dfb_acc)
 {
     hipStream_t st = (hipStream_t)stream;
-    SMIN_REQUIRE(D % 4 == 0 && D <= 2048);
+    SMIN_REQUIRE(mu_bwd_width_ok(D));
+    const MuBwdWs lay(N, D);
+    SMIN_REQUIRE(lay.end * sizeof(float) <= ws_bytes);
     float* w = reinterpret_cast<float*>(ws);
-    const int sp = N > 0 ? tn_splits(N, D, 2 * D) : 1;
-    float* dx1 = w;
-    float* slab = dx1 + (((size_t)N * D + 3) & ~(size_t)3);
-    float* bslab = slab + (size_t)sp * D * 2 * D;
-    SMIN_REQUIRE((size_t)((bslab + (size_t)sp * D) - w) * sizeof(float) <= ws_bytes);
+    const int sp = lay.sp;
+    float* dx1 = w + lay.dx1;
+    float* slab = w + lay.slab;
+    float* bslab = w + lay.bslab;
     // either half may be skipped (NULL outputs): the two halves share only dmu, so a host can run them on two streams
     const bool want_in = dfb != nullptr, want_w = dWcat != nullptr;      // (dfcmean [N][D] is legitimately NULL when N == 0)
     SMIN_REQUIRE(!want_in || N == 0 || dfcmean != nullptr);

@@ -430,13 +430,30 @@ __global__ void proposal_map_bwd_scan_kernel(const float* __restrict__ E, const 
 
 using namespace smin;
 
+// The two workspaces of this file, each one piece at offset 0: the forward's fp64 time prefix Pf [B][T + 1][D] and the backward's
+// per-frame event sums E [B][T][D].  The size queries and the entry points both read these.
+static size_t prefix_ws_bytes(int B, int T, int D) { return sizeof(double) * (size_t)B * (T + 1) * D; }
+static size_t events_ws_bytes(int B, int T, int D) { return sizeof(float) * (size_t)B * T * D; }
+static bool map_width_ok(int D) { return D % 4 == 0 && D <= 2048; }
+static bool window_width_ok(int W, int nseg) { return W % 4 == 0 && nseg >= 1 && nseg <= 8 && W * nseg <= 2048; }
+
+extern "C" size_t smin_proposal_map_fwd_ws_bytes(int B, int T, int D) { return map_width_ok(D) ? prefix_ws_bytes(B, T, D) : 0; }
+extern "C" size_t smin_proposal_map_bwd_ws_bytes(int B, int T, int D) { return map_width_ok(D) ? events_ws_bytes(B, T, D) : 0; }
+extern "C" size_t smin_clip_window_means_fwd_ws_bytes(int B, int T, int W, int nseg)
+{
+    return window_width_ok(W, nseg) ? prefix_ws_bytes(B, T, W * nseg) : 0;
+}
+extern "C" size_t smin_clip_window_means_bwd_ws_bytes(int B, int T, int W, int nseg)
+{
+    return window_width_ok(W, nseg) ? events_ws_bytes(B, T, W * nseg) : 0;
+}
+
 extern "C" int smin_proposal_map_fwd(void* stream, const float* f, const int32_t* cells, int N, int B, int T, int L, int C, int D,
                                         float* fc, float* fm, float* fb, void* ws, size_t ws_bytes)
 {
     hipStream_t st = (hipStream_t)stream;
-    SMIN_REQUIRE(D % 4 == 0 && L >= 1 && T >= L && T % L == 0 && C >= 1);
-    SMIN_REQUIRE(D <= 2048);
-    SMIN_REQUIRE(ws_bytes >= sizeof(double) * (size_t)B * (T + 1) * D);
+    SMIN_REQUIRE(map_width_ok(D) && L >= 1 && T >= L && T % L == 0 && C >= 1);
+    SMIN_REQUIRE(ws_bytes >= prefix_ws_bytes(B, T, D));
     double* Pf = reinterpret_cast<double*>(ws);
     hipLaunchKernelGGL((time_scan_kernel<true>), dim3(cdiv(D, 64), B), dim3(1024), 0, st, f, (const float*)nullptr, T, L, D, Pf, (float*)nullptr);
     SMIN_LAUNCH_CHECK();
@@ -507,10 +524,10 @@ extern "C" int smin_proposal_map_bwd(void* stream, const float* dfc, const float
 {
     (void)row_ptr;
     hipStream_t st = (hipStream_t)stream;
-    SMIN_REQUIRE(D % 4 == 0 && L >= 1 && T >= L && T % L == 0 && C >= 1 && D <= 2048);
+    SMIN_REQUIRE(map_width_ok(D) && L >= 1 && T >= L && T % L == 0 && C >= 1);
     float* E = nullptr;
     if (N > 0 && (dfc || dfm)) {
-        SMIN_REQUIRE(ws_bytes >= sizeof(float) * (size_t)B * T * D);
+        SMIN_REQUIRE(ws_bytes >= events_ws_bytes(B, T, D));
         E = reinterpret_cast<float*>(ws);
         size_t lds;
         if (ev_table && ev_offsets && events2_ok(N, T, L, C, &lds)) {
@@ -570,9 +587,9 @@ extern "C" int smin_clip_window_means_fwd(void* stream, const float* g, const fl
 {
     hipStream_t st = (hipStream_t)stream;
     const int D = W * nseg;
-    SMIN_REQUIRE(W % 4 == 0 && nseg >= 1 && nseg <= 8 && L >= 1 && T >= L && T % L == 0 && C >= 1 && D <= 2048);
+    SMIN_REQUIRE(window_width_ok(W, nseg) && L >= 1 && T >= L && T % L == 0 && C >= 1);
     SMIN_REQUIRE(bias_len % 4 == 0 && bias_len >= 0 && bias_len <= D);
-    SMIN_REQUIRE(ws_bytes >= sizeof(double) * (size_t)B * (T + 1) * D);
+    SMIN_REQUIRE(ws_bytes >= prefix_ws_bytes(B, T, D));
     if (N == 0) return 0;
     double* Pf = reinterpret_cast<double*>(ws);
     hipLaunchKernelGGL((time_scan_kernel<true>), dim3(cdiv(D, 64), B), dim3(1024), 0, st, g, (const float*)nullptr, T, L, D, Pf, (float*)nullptr);
@@ -591,10 +608,10 @@ extern "C" int smin_clip_window_means_bwd(void* stream, const float* const* dout
     (void)row_ptr;
     hipStream_t st = (hipStream_t)stream;
     const int D = W * nseg;
-    SMIN_REQUIRE(W % 4 == 0 && nseg >= 1 && nseg <= 8 && L >= 1 && T >= L && T % L == 0 && C >= 1 && D <= 2048);
+    SMIN_REQUIRE(window_width_ok(W, nseg) && L >= 1 && T >= L && T % L == 0 && C >= 1);
     float* E = nullptr;
     if (N > 0) {
-        SMIN_REQUIRE(ws_bytes >= sizeof(float) * (size_t)B * T * D);
+        SMIN_REQUIRE(ws_bytes >= events_ws_bytes(B, T, D));
         E = reinterpret_cast<float*>(ws);
         size_t lds;
         SegClipGrad src;

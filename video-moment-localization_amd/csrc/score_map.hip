@@ -147,6 +147,27 @@ extern "C" int smin_score_map_fwd(void* stream, const float* fm, const float* fb
     return 0;
 }
 
+// The backward's workspace, as float offsets: each half has its own two pieces, so the halves may run side by side in one buffer;
+// smin_score_map_bwd_ws_bytes reports `end`.
+struct ScoreBwdWs {
+    int nch, hch;
+    size_t part, bpart, hpart, hbpart, end;
+    ScoreBwdWs(int N, int B, int L, int D) : nch(cdiv(N > 0 ? N : 1, 64)), hch(cdiv(B * L, HEAD_ROWS))
+    {
+        part = 0;                                      // [nch][D]
+        bpart = part + (size_t)nch * D;                // [nch]  (padded to 4)
+        hpart = bpart + ((nch + 3) & ~3);              // [hch][3][D]
+        hbpart = hpart + (size_t)hch * 3 * D;          // [hch][3]
+        end = hbpart + (size_t)hch * 3;
+    }
+};
+
+extern "C" size_t smin_score_map_bwd_ws_bytes(int N, int B, int L, int D)
+{
+    if (D % 4 != 0) return 0;
+    return ScoreBwdWs(N, B, L, D).end * sizeof(float);
+}
+
 extern "C" int smin_score_map_bwd(void* stream, const float* dpm, const float* dpsea, const float* pm, const float* psea,
                                   const float* fm, const float* fb, const int32_t* cells, int N, int B, int L, int D,
                                   const float* wm, const float* wb, const float* lmask,
@@ -155,13 +176,14 @@ extern "C" int smin_score_map_bwd(void* stream, const float* dpm, const float* d
     hipStream_t st = (hipStream_t)stream;
     SMIN_REQUIRE(D % 4 == 0);
     const int BL = B * L;
-    const int nch = cdiv(N > 0 ? N : 1, 64), hch = cdiv(BL, HEAD_ROWS);
+    const ScoreBwdWs lay(N, B, L, D);
+    SMIN_REQUIRE(lay.end * sizeof(float) <= ws_bytes);
+    const int nch = lay.nch, hch = lay.hch;
     float* w = reinterpret_cast<float*>(ws);
-    float* part = w;                                   // [nch][D]
-    float* bpart = part + (size_t)nch * D;             // [nch]  (padded to 4)
-    float* hpart = bpart + ((nch + 3) & ~3);           // [hch][3][D]
-    float* hbpart = hpart + (size_t)hch * 3 * D;       // [hch][3]
-    SMIN_REQUIRE((size_t)((hbpart + (size_t)hch * 3) - w) * sizeof(float) <= ws_bytes);
+    float* part = w + lay.part;
+    float* bpart = w + lay.bpart;
+    float* hpart = w + lay.hpart;
+    float* hbpart = w + lay.hbpart;
     // two independent halves (the map's score: dpm -> dfm, dwm, dbm; the boundary heads: dpsea -> dfb, dwb, dbb), each with its own part
     // of ws: dpm == NULL or dpsea == NULL skips a half, so that a host can issue them on two streams
     SMIN_REQUIRE(dpm != nullptr || dpsea != nullptr);

@@ -132,18 +132,36 @@ HStream weight_stream(c10::DeviceIndex dev)
     });
 }
 
-// persistent scratch per (device, stream): calls on one stream are stream-ordered, two streams never share scratch
+// persistent scratch per (device, stream): calls on one stream are stream-ordered, two streams never share scratch.
+// .n is the size that was asked for, not the buffer's capacity: an entry point's own check then sees an under-sized request on
+// every call, not only on a fresh stream.
 struct Scratch { void* p; size_t n; Tensor hold; };
 Scratch scratch(size_t nbytes, const at::Device& dev)
 {
     static Cache<std::pair<int, int64_t>, Tensor> bufs;                 // (an entry grows: locked here)
     const auto st = c10::hip::getCurrentHIPStream(dev.index());
+    // A captured graph keeps the pointer it is given, and the persistent buffer is replaced (and freed) by the next larger request:
+    // inside a capture the scratch comes from the graph's own memory pool, like every other tensor of the captured step.
+    hipStreamCaptureStatus capture = hipStreamCaptureStatusNone;
+    TORCH_CHECK(hipStreamIsCapturing(st.stream(), &capture) == hipSuccess, "hipStreamIsCapturing failed");
+    if (capture != hipStreamCaptureStatusNone) {
+        Tensor t = at::empty({(int64_t)std::max<size_t>(nbytes, 16)}, at::TensorOptions().dtype(at::kByte).device(dev));
+        return Scratch{t.data_ptr(), nbytes, t};
+    }
     std::lock_guard<std::mutex> lk(bufs.mu);
     Tensor& b = bufs.m[{(int)dev.index(), (int64_t)st.id()}];
     if (!b.defined() || (size_t)b.numel() < nbytes)
         b = at::empty({(int64_t)(nbytes + nbytes / 4 + 4096)}, at::TensorOptions().dtype(at::kByte).device(dev));
-    return Scratch{b.data_ptr(), (size_t)b.numel(), b};
+    return Scratch{b.data_ptr(), nbytes, b};
 }
+// scratch of the size an entry point's own query returns (0 = the entry point would reject these shape arguments):
+// SMIN_WS(smin_gate_bwd_ws_bytes(B, L, D), dev)
+Scratch scratch_for(size_t need, const char* query, const at::Device& dev)
+{
+    TORCH_CHECK(need > 0, query, " rejected its arguments");
+    return scratch(need, dev);
+}
+#define SMIN_WS(query_call, dev) scratch_for(query_call, #query_call, dev)
 
 // the geometry's clip-boundary table, built once per (device, T, L, C)
 std::pair<Tensor, Tensor> clip_event_table(const at::Device& dev, int T, int L, int C, bool* built_now = nullptr)
@@ -719,7 +737,7 @@ struct SminCore : torch::autograd::Function<SminCore> {
         // ---- proposal map (f_m, f_b) and every layer's clip-window term of chat
         Tensor fm = at::empty({N, D}, opt), fb = at::empty({B, L, D}, opt);
         {
-            auto ws = scratch((size_t)8 * B * (T + 1) * std::max<int64_t>(D, nl * dl), dev);
+            auto ws = SMIN_WS(smin_proposal_map_fwd_ws_bytes(B, Ti, D), dev);
             SMIN_CK(smin_proposal_map_fwd(cur(), fp(f), ip(cells), n, B, Ti, Li, Ci, D, nullptr, fpm(fm), fpm(fb), ws.p, ws.n));
         }
         Tensor pgs = at::empty({nl, N * C, dl}, opt);
@@ -727,7 +745,7 @@ struct SminCore : torch::autograd::Function<SminCore> {
             Tensor g_all = at::empty({(int64_t)B * T, nl * dl}, opt);
             const float* xs[1] = {fp(f)};
             SMIN_CK(smin_linear_rows_fwd(cur(), xs, 1, fp(st.Wch_all), nullptr, nullptr, nullptr, 1, i32(B * T), i32(nl * dl), D, fpm(g_all)));
-            auto ws = scratch((size_t)8 * B * (T + 1) * std::max<int64_t>(D, nl * dl), dev);
+            auto ws = SMIN_WS(smin_clip_window_means_fwd_ws_bytes(B, Ti, dl, i32(nl)), dev);
             SMIN_CK(smin_clip_window_means_fwd(cur(), fp(g_all), fp(st.layer[0].consts), dl, ip(cells), n, B, Ti, Li, Ci, dl, i32(nl), fpm(pgs), ws.p, ws.n));
         }
 
@@ -960,17 +978,17 @@ struct SminCore : torch::autograd::Function<SminCore> {
                 wait_stream(early, curs);                                          // (behind the allocations above: "Stream rules" (2))
                 {
                     StreamScope sc(early);
-                    auto ws = scratch(smin_workspace_bytes(n, B, 4, D, 4, 1), dev);
+                    auto ws = SMIN_WS(smin_score_map_bwd_ws_bytes(n, B, Li, D), dev);
                     SMIN_CK(smin_score_map_bwd(cur(), nullptr, fp(dpsea), fp(st.pm), fp(st.psea), fp(st.fm_out), fp(bu_last), ip(cells), n, B, Li, D, fp(P.loc(0)), fp(st.wb),
                                                fp(lmf), nullptr, fpm(dfb_next), nullptr, nullptr, fpm(dwb), fpm(dbb), ws.p, ws.n));
                 }
                 hipEvent_t early_done = mark(early);
-                auto ws = scratch(smin_workspace_bytes(n, B, 4, D, 4, 1), dev);
+                auto ws = SMIN_WS(smin_score_map_bwd_ws_bytes(n, B, Li, D), dev);
                 SMIN_CK(smin_score_map_bwd(cur(), fp(dpm), nullptr, fp(st.pm), fp(st.psea), fp(st.fm_out), fp(bu_last), ip(cells), n, B, Li, D, fp(P.loc(0)), fp(st.wb), fp(lmf),
                                            fpm(dfm), nullptr, fpm(dwm), fpm(dbm), nullptr, nullptr, ws.p, ws.n));
                 await(curs, early_done);                                           // W^T and dfb_next
             } else {
-                auto ws = scratch(smin_workspace_bytes(n, B, 4, D, 4, 1), dev);
+                auto ws = SMIN_WS(smin_score_map_bwd_ws_bytes(n, B, Li, D), dev);
                 SMIN_CK(smin_score_map_bwd(cur(), fp(dpm), fp(dpsea), fp(st.pm), fp(st.psea), fp(st.fm_out), fp(bu_last), ip(cells), n, B, Li, D, fp(P.loc(0)), fp(st.wb), fp(lmf),
                                            fpm(dfm), fpm(dfb_next), fpm(dwm), fpm(dbm), fpm(dwb), fpm(dbb), ws.p, ws.n));
             }
@@ -1003,7 +1021,7 @@ struct SminCore : torch::autograd::Function<SminCore> {
                 wait_stream(wstr, curs);
                 StreamScope sc(wstr);
                 Tensor dWcat = prep_kernel ? dWcat_all[k] : at::empty_like(ls.Wcat), dbcat = prep_kernel ? dbcat_all[k] : at::empty({D}, opt);
-                auto ws = scratch(smin_workspace_bytes(n, B, 4, D, 4, 1), dev);
+                auto ws = SMIN_WS(smin_moment_unit_bwd_ws_bytes(n, B, Li, D), dev);
                 if (ls.x1.scalar_type() == at::kBFloat16)
                     SMIN_CK(smin_moment_unit_bwd_x1h(cur(), fp(dfm), fp(ls.cum), fp(ls.bu), ip(cells), ip(row_ptr), ip(cellmap), n, B, Li, D, fp(trk(k, TR_CAT)), nullptr, nullptr,
                                                      fpm(dWcat), fpm(dbcat), ws.p, ws.n, 1, nullptr, reinterpret_cast<const uint16_t*>(ls.x1.const_data_ptr()), nullptr));
@@ -1022,7 +1040,7 @@ struct SminCore : torch::autograd::Function<SminCore> {
             // ~0.6 ms behind the unit's weight contractions at the end of layer 0 (tools/gantt.sh)
             if (boundary_done) { await(curs, boundary_done); boundary_done = nullptr; }
             {
-                auto ws = scratch(smin_workspace_bytes(n, B, 4, D, 4, 1), dev);
+                auto ws = SMIN_WS(smin_moment_unit_bwd_ws_bytes(n, B, Li, D), dev);
                 SMIN_CK(smin_moment_unit_bwd(cur(), fp(dfm), fp(ls.cum), fp(ls.bu), ip(cells), ip(row_ptr), ip(cellmap), n, B, Li, D, fp(trk(k, TR_CAT)), fpm(dcum), fpm(dfb_mu),
                                              nullptr, nullptr, ws.p, ws.n, 1, fp(dcum_next), nullptr, fp(dfb_next)));   // (the pair product feeds the weight half only)
             }                                                                      // dfb_mu = this unit's gradient of bu + the later consumer's (dfb_next): dbu
@@ -1037,7 +1055,7 @@ struct SminCore : torch::autograd::Function<SminCore> {
                 dfb_k = at::empty({B, L, D}, opt);
                 Tensor dfw = at::empty_like(fw), dfs = at::empty_like(fs);
                 Tensor dWq = at::empty({D, D}, opt), dbq = at::empty({D}, opt), dWk = at::empty({D, D}, opt), dbk = at::empty({D}, opt);
-                auto ws = scratch(smin_boundary_unit_bwd_ws_bytes(B, Li, Nq, D), dev);
+                auto ws = SMIN_WS(smin_boundary_unit_bwd_ws_bytes(B, Li, Nq, D), dev);
                 SMIN_CK(smin_boundary_unit_bwd(cur(), fp(dbu), fp(ls.fb), fp(fw), fp(fs), fp(ls.hbar), ip(cells), ip(row_ptr), n, B, Li, Nq, D, fp(trk(k, TR_BQ)), fp(trk(k, TR_BK)),
                                                fp(qmf), fp(lmf), fp(ls.Qb), fp(ls.Kb), fp(ls.P), fp(ls.baq), fp(ls.bqv), fp(ls.A), fpm(dfb_k), fpm(dfw), fpm(dfs), nullptr,
                                                fpm(dWq), fpm(dbq), fpm(dWk), fpm(dbk), ws.p, ws.n));
@@ -1138,7 +1156,7 @@ struct SminCore : torch::autograd::Function<SminCore> {
                 else { later_sum = sum_list(later); dh.push_back(fp(later_sum)); }
                 if (k == 0) dr.push_back(fp(dcum));
                 Tensor dfm_k = at::empty({N, D}, opt), dfs = at::empty_like(fs);
-                auto ws = scratch((size_t)4 * B * 512 * D + 4096, dev);
+                auto ws = SMIN_WS(smin_gate_bwd_ws_bytes(B, Li, D), dev);
                 SMIN_CK(smin_gate_bwd(cur(), dh.data(), i32(dh.size()), dr.data(), i32(dr.size()), fp(ls.fm), fp(fs), ip(row_ptr), n, B, Li, D, fpm(dfm_k), fpm(dfs), ws.p, ws.n,
                                       ip(cells), fp(ls.A), fp(dbu)));
                 dfs_parts.push_back(dfs);
@@ -1209,7 +1227,7 @@ struct SminCore : torch::autograd::Function<SminCore> {
                 // allocated under THIS stream ("Stream rules" (2)): main-stream kernels are queued behind attn0_done
                 dg = at::empty({(int64_t)B * T, nl * dl}, opt);
                 keep.push_back(dg);
-                auto ws = scratch((size_t)4 * B * T * std::max<int64_t>(D, nl * dl), dev);
+                auto ws = SMIN_WS(smin_clip_window_means_bwd_ws_bytes(B, Ti, dl, i32(nl)), dev);
                 SMIN_CK(smin_clip_window_means_bwd(cur(), ptrs.data(), ip(cells), ip(row_ptr), ip(cellmap), n, B, Ti, Li, Ci, dl, i32(nl), fpm(dg), ws.p, ws.n, ip(tab.first),
                                                    tab.second.data_ptr()));
                 dg_done = mark(cw);
@@ -1233,7 +1251,7 @@ struct SminCore : torch::autograd::Function<SminCore> {
             // contraction's epilogue
             df = at::empty({B, T, D}, opt);
             if (boundary_done) { await(curs, boundary_done); boundary_done = nullptr; }   // layer 0's dfb
-            auto ws3 = scratch((size_t)4 * B * T * std::max<int64_t>(D, nl * dl), dev);
+            auto ws3 = SMIN_WS(smin_proposal_map_bwd_ws_bytes(B, Ti, D), dev);
             SMIN_CK(smin_proposal_map_bwd(cur(), nullptr, fp(dfm), fp(dfb_next), ip(cells), ip(row_ptr), ip(cellmap), n, B, Ti, Li, Ci, D, fpm(df), ws3.p, ws3.n, ip(tab.first),
                                           tab.second.data_ptr()));
             weights_done = mark(wstr);

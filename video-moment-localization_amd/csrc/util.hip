@@ -2,6 +2,7 @@
 #include "gemm.h"
 #include "smin_hip.h"
 #include <stdlib.h>
+#include <algorithm>
 #include <map>
 #include <mutex>
 #include <utility>
@@ -244,22 +245,17 @@ extern "C" int smin_prof_read(int32_t* tags, float* ms, int cap)
     return n;
 }
 
+// the map side smin_workspace_bytes assumes for the score map's boundary heads, as the bound it replaces did (include/smin_hip.h)
+constexpr int WS_COMPAT_L = 64;
+
 extern "C" size_t smin_workspace_bytes(int N, int B, int C, int D, int dl, int Nq)
 {
+    // the old catch-all, kept for callers built against it: the largest of the three unit backwards' own queries (a query that
+    // rejects the arguments returns 0 and so contributes nothing).  It was never given the map side: the score map's term is taken
+    // at WS_COMPAT_L, the content unit's with last == 0 (the larger of its two layouts).
     (void)Nq;
-    const size_t M = (size_t)N * C;
-    // content unit bwd: 2 x [M][dl] + TN slabs + attention slabs + gate partials
-    const size_t sp_c = (size_t)(M > 0 ? tn_splits((int)M, D, dl) + tn_splits((int)M, dl, D) : 2);
-    size_t content = 3 * M * dl + 2 * M * 32 + sp_c * ((size_t)D * dl + D + dl) + (size_t)B * 64 * ((size_t)64 * dl + dl + 32) + (size_t)B * 512 * D;
-    // moment unit bwd: dX1 [N][D] + TN slabs + bias slabs
-    size_t moment = (size_t)N * D + (size_t)(N > 0 ? tn_splits(N, D, 2 * D) : 1) * ((size_t)D * 2 * D + D);
-    // boundary / score: per-row partials
-    size_t other = (size_t)N + 8 * (size_t)B * 64 * D + (size_t)N * 4 + (size_t)(N / 32 + 1) * (D + 4);
-    // boundary unit bwd (L <= 64 assumed here; the host adds 2*B*L*L + 3*B*L*D for longer maps)
-    other += (size_t)B * 64 * 64 * 2 + (size_t)B * 64 * D * 3 + (size_t)B * 64 * 64 + (size_t)B * 64 * D + 2 * (size_t)64 * ((size_t)D * D + D);
-    size_t fl = content > moment ? content : moment;
-    if (other > fl) fl = other;
-    return (fl + 1024) * sizeof(float);
+    return std::max({smin_content_unit_bwd_ws_bytes(N, B, C, D, dl, 0), smin_moment_unit_bwd_ws_bytes(N, B, WS_COMPAT_L, D),
+                     smin_score_map_bwd_ws_bytes(N, B, WS_COMPAT_L, D)});
 }
 
 extern "C" int smin_pack_cells(void* stream, const float* dense, const int32_t* cells, int N, int L, int W, float* packed)

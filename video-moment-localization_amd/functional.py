@@ -15,13 +15,17 @@ def _c(t):
 
 
 def _ws(nbytes, device):
+    """(buffer, pointer, the size that was asked for): the entry point's own check sees the request, not the buffer's capacity."""
     buf = _lib.workspace(nbytes, device)
-    return buf, ptr(buf), buf.numel()
+    return buf, ptr(buf), nbytes
 
 
-def _unit_ws(layout, C, D, dl, Nq, device):
-    n = _lib.load().smin_workspace_bytes(layout.N, layout.B, C, D, dl, Nq)
-    return _ws(n, device)
+def _ws_for(query, device, *shape):
+    """Scratch of the size an entry point's own query returns for its shape arguments (0 = the entry point would reject them)."""
+    nbytes = getattr(_lib.load(), query)(*shape)
+    if nbytes == 0:
+        raise _lib.SminHipError(f"{query}{shape} rejected its arguments")
+    return _ws(nbytes, device)
 
 
 _EVENT_TABLES = {}
@@ -56,7 +60,7 @@ class ProposalMapFn(Function):
         fc = f.new_empty((layout.N, C, D))
         fm = f.new_empty((layout.N, D))
         fb = f.new_empty((B, L, D))
-        _, wp, wn = _ws(8 * B * (T + 1) * D, f.device)
+        _, wp, wn = _ws_for("smin_proposal_map_fwd_ws_bytes", f.device, B, T, D)
         call("smin_proposal_map_fwd", stream(), ptr(f), ptr(layout.cells), layout.N, B, T, L, C, D, ptr(fc), ptr(fm), ptr(fb), wp, wn)
         ctx.layout, ctx.dims = layout, (B, T, L, C, D)
         return fc, fm, fb
@@ -68,7 +72,7 @@ class ProposalMapFn(Function):
         dfc, dfm, dfb = _c(dfc), _c(dfm), _c(dfb)
         ref = dfc if dfc is not None else dfm if dfm is not None else dfb
         df = ref.new_empty((B, T, D))
-        _, wp, wn = _ws(4 * B * T * D, df.device)
+        _, wp, wn = _ws_for("smin_proposal_map_bwd_ws_bytes", df.device, B, T, D)
         eo, et = clip_event_table(df.device, T, L, C)
         call("smin_proposal_map_bwd", stream(), ptr(dfc), ptr(dfm), ptr(dfb), ptr(layout.cells), ptr(layout.row_ptr), ptr(layout.cellmap),
              layout.N, B, T, L, C, D, ptr(df), wp, wn, ptr(eo), ptr(et))
@@ -86,7 +90,7 @@ class ProposalMeansFn(Function):
             raise ValueError(f"ProposalGeneration was built for T={T} but got {Tn} frames")
         fm = f.new_empty((layout.N, D))
         fb = f.new_empty((B, L, D))
-        _, wp, wn = _ws(8 * B * (T + 1) * D, f.device)
+        _, wp, wn = _ws_for("smin_proposal_map_fwd_ws_bytes", f.device, B, T, D)
         call("smin_proposal_map_fwd", stream(), ptr(f), ptr(layout.cells), layout.N, B, T, L, C, D, None, ptr(fm), ptr(fb), wp, wn)
         ctx.layout, ctx.dims = layout, (B, T, L, C, D)
         return fm, fb
@@ -98,7 +102,7 @@ class ProposalMeansFn(Function):
         dfm, dfb = _c(dfm), _c(dfb)
         ref = dfm if dfm is not None else dfb
         df = ref.new_empty((B, T, D))
-        _, wp, wn = _ws(4 * B * T * D, df.device)
+        _, wp, wn = _ws_for("smin_proposal_map_bwd_ws_bytes", df.device, B, T, D)
         eo, et = clip_event_table(df.device, T, L, C)
         call("smin_proposal_map_bwd", stream(), None, ptr(dfm), ptr(dfb), ptr(layout.cells), ptr(layout.row_ptr), ptr(layout.cellmap),
              layout.N, B, T, L, C, D, ptr(df), wp, wn, ptr(eo), ptr(et))
@@ -117,7 +121,7 @@ class ClipWindowMeansFn(Function):
         B, Tn, D = g.shape
         W = D // nseg
         out = g.new_empty((nseg, layout.N * C, W))
-        _, wp, wn = _ws(8 * B * (T + 1) * D, g.device)
+        _, wp, wn = _ws_for("smin_clip_window_means_fwd_ws_bytes", g.device, B, T, W, nseg)
         nb = 0 if bias is None else bias.numel()                     # bias may cover only the first segments
         call("smin_clip_window_means_fwd", stream(), ptr(g), ptr(bias), nb, ptr(layout.cells), layout.N, B, T, L, C, W, nseg, ptr(out), wp, wn)
         ctx.layout, ctx.dims, ctx.nb = layout, (B, T, L, C, W, nseg), nb
@@ -131,7 +135,7 @@ class ClipWindowMeansFn(Function):
         ref = next(d for d in douts if d is not None)
         douts = [_c(d) if d is not None else ref.new_zeros((layout.N * C, W)) for d in douts]
         dg = ref.new_empty((B, T, W * nseg))
-        _, wp, wn = _ws(4 * B * T * W * nseg, ref.device)
+        _, wp, wn = _ws_for("smin_clip_window_means_bwd_ws_bytes", ref.device, B, T, W, nseg)
         arr = (ctypes.c_void_p * nseg)(*[d.data_ptr() for d in douts])
         eo, et = clip_event_table(ref.device, T, L, C)
         call("smin_clip_window_means_bwd", stream(), arr, ptr(layout.cells), ptr(layout.row_ptr), ptr(layout.cellmap),
@@ -414,7 +418,7 @@ class GateFn(Function):
         for g in dh + dr:
             ptr(g)
         dfm, dfs = torch.empty_like(fm), torch.empty_like(fs)
-        _, wp, wn = _ws(4 * layout.B * 512 * D + 4096, fm.device)
+        _, wp, wn = _ws_for("smin_gate_bwd_ws_bytes", fm.device, layout.B, layout.L, D)
         call("smin_gate_bwd", stream(), _ptr_array(dh), len(dh), _ptr_array(dr) if dr else None, len(dr), ptr(fm), ptr(fs),
              ptr(layout.row_ptr), N, layout.B, layout.L, D, ptr(dfm), ptr(dfs), wp, wn, None, None, None)
         return dfm, dfs, None, None, None
@@ -466,7 +470,7 @@ class ContentUnitFn(Function):
             for t in (dWch, dbch, dMq, duq, dwhat, dshat, dWc, dbc):
                 t.zero_()
         else:
-            _, wp, wn = _unit_ws(layout, C, D, dl, Nq, fc.device)
+            _, wp, wn = _ws_for("smin_content_unit_bwd_ws_bytes", fc.device, N, B, C, D, dl, int(ctx.last))
             call("smin_content_unit_bwd", stream(), ptr(dfc_out), ptr(dfcmean), ptr(fc), ptr(layout.cells), ptr(layout.row_ptr),
                  N, B, layout.L, C, D, dl, Nq, ptr(WchT), ptr(Mq), ptr(uq), ptr(what), ptr(shat), ptr(qmask), ptr(WcT),
                  ptr(chat), ptr(cchat), ptr(dfc), ptr(dhbar), ptr(dWch), ptr(dbch), ptr(dMq), ptr(duq), ptr(dwhat), ptr(dshat),
@@ -547,7 +551,7 @@ class MomentUnitFn(Function):
         WcatT = Wcat.t().contiguous()
         dfcmean, dfb = torch.empty_like(fcmean), torch.empty_like(fb)
         dWcat, dbcat = torch.empty_like(Wcat), fb.new_empty((D,))
-        _, wp, wn = _unit_ws(layout, 4, D, 4, 1, fb.device)
+        _, wp, wn = _ws_for("smin_moment_unit_bwd_ws_bytes", fb.device, N, B, L, D)
         call("smin_moment_unit_bwd", stream(), ptr(dmu), ptr(fcmean), ptr(fb), ptr(layout.cells), ptr(layout.row_ptr), ptr(layout.cellmap),
              N, B, L, D, ptr(WcatT), ptr(dfcmean), ptr(dfb), ptr(dWcat), ptr(dbcat), wp, wn, int(layout.all_valid), ptr(dacc), ptr(x1), None)
         return dfcmean, dmu, dfb, dWcat, dbcat, None
@@ -580,7 +584,7 @@ class ScoreMapFn(Function):
         dfm, dfb = torch.empty_like(fm), torch.empty_like(fb)
         dwm, dbm = torch.empty_like(wm), fm.new_empty((1,))
         dwb, dbb = torch.empty_like(wb), fm.new_empty((3,))
-        _, wp, wn = _unit_ws(layout, 4, D, 4, 1, fm.device)
+        _, wp, wn = _ws_for("smin_score_map_bwd_ws_bytes", fm.device, N, B, L, D)
         call("smin_score_map_bwd", stream(), ptr(dpm), ptr(dpsea), ptr(pm), ptr(psea), ptr(fm), ptr(fb), ptr(layout.cells), N, B, L, D,
              ptr(wm), ptr(wb), ptr(lmask), ptr(dfm), ptr(dfb), ptr(dwm), ptr(dbm), ptr(dwb), ptr(dbb), wp, wn)
         return dfm, dfb, dwm, dbm, dwb, dbb, None, None
