@@ -61,7 +61,8 @@ extern "C" {
  * banks of windows of long videos -- smin_corpus_span_topk (one ranked list of span-valued moments per query across videos); an exact
  * workspace size query for each entry point that had none -- smin_proposal_map_fwd_ws_bytes, smin_proposal_map_bwd_ws_bytes,
  * smin_clip_window_means_fwd_ws_bytes, smin_clip_window_means_bwd_ws_bytes, smin_gate_bwd_ws_bytes, smin_moment_unit_bwd_ws_bytes,
- * smin_score_map_bwd_ws_bytes and smin_content_unit_bwd_ws_bytes (smin_workspace_bytes is now their maximum) */
+ * smin_score_map_bwd_ws_bytes and smin_content_unit_bwd_ws_bytes (smin_workspace_bytes is now their maximum); merging the span lists
+ * of sharded window banks -- smin_span_search_merge (smin_search_merge for smin_corpus_span_topk's lists, as a one-pass rank) */
 #define SMIN_HIP_ABI_VERSION 2
 
 int smin_abi_version(void);
@@ -847,6 +848,34 @@ int smin_corpus_span_topk(void* stream, const float* span, const float* score, c
                           const int32_t* count, const int32_t* group_video, const int32_t* group_ptr, int Q, int k_video, int K,
                           int64_t* out_video, float* out_span, float* out_score, int64_t* out_window, int64_t* out_cell,
                           int32_t* out_count);
+
+/* smin_span_search_merge: S ranked lists of span-valued moments per query, each over its own shard of a corpus of long videos, into
+ * the K best of all shards: smin_search_merge for smin_corpus_span_topk's lists.  One launch, one workgroup per
+ * query, no workspace, no copy, no atomics, no host read; capturable.
+ * Inputs.  video, span, score, window, cell, count: HOST tables of S device pointers, read before the call returns (they travel to the
+ *   kernel by value); list s is smin_corpus_span_topk's output at K = k_list[s]: video [Q][k_s] int64 (shard-local), span [Q][k_s][2]
+ *   fp32, score [Q][k_s] fp32, window [Q][k_s] int64, cell [Q][k_s][2] int64, count [Q] int32.  k_list, video_offset: host [S];
+ *   video_offset[s] is added to list s's video ids (the shard's first global id).
+ * Candidates.  Position p of list s for query q iff p < clamp(count_s[q], 0, k_s); what lies behind the counts (NaN spans, -1) is
+ *   never read.
+ * Order.  smin_search_merge's: higher score first (-0 counts as +0); ties go to the lower global video video_s[q][p] +
+ *   video_offset[s], then to the lower s, then to the lower p.  EACH LIST IS ASSUMED ORDERED AS smin_corpus_span_topk ORDERS IT (not
+ *   checked): a candidate's rank is then p plus, over the other lists, the number of entries that go ahead of it (a binary search
+ *   each: one pass, not K rounds), the ranks of a query are a permutation, and for shards of whole, disjoint videos given in
+ *   ascending offset the result is bit for bit smin_corpus_span_topk's list of the whole corpus, merged at once or folded one shard
+ *   after another.  For lists not so ordered the content is unspecified; every write stays in bounds and every element is written.
+ *   Global video ids must lie in [0, 2^31): the order word holds them as int32.
+ * Outputs.  As smin_corpus_span_topk: out_video [Q][K] int64 global ids, out_span [Q][K][2], out_score [Q][K], out_window [Q][K],
+ *   out_cell [Q][K][2] (span, score, window and cell copied bit for bit), out_count [Q] = min(sum of the clamped counts, K).  Every
+ *   element of every output is written; empty slots: video -1, span NaN (0x7fc00000), score 0, window -1, cell -1.
+ * Limits.  1 <= S <= 16, 1 <= K <= 64, 1 <= k_list[s] <= 64, 0 <= video_offset[s] < 2^31, Q >= 0 (Q == 0: returns 0, nothing launched).
+ * Determinism.  The same bits every run: each slot's last writer is fixed by the ranks.
+ * Rejection.  A nonzero status before any launch for S, K or a k out of range, Q < 0, and with Q > 0 a NULL table, table entry or
+ *   output, an offset out of range, or an output that is one of the input pointers. */
+int smin_span_search_merge(void* stream, int S, const int64_t* const* video, const float* const* span, const float* const* score,
+                           const int64_t* const* window, const int64_t* const* cell, const int32_t* const* count,
+                           const int32_t* k_list, const int64_t* video_offset, int Q, int K, int64_t* out_video, float* out_span,
+                           float* out_score, int64_t* out_window, int64_t* out_cell, int32_t* out_count);
 
 /* smin_mine_pairs: the pair plan of hard-negative mining -- for each of Q queries its own video and the N
  * highest-scoring wrong videos, as smin_pair_assemble's two lists and smin_pair_assemble_bwd's two groupings, formed on the device.

@@ -7,11 +7,13 @@
 //                       selection (topk_rounds) over another way of reading candidate c, so a merge of the shards' lists is the list
 //                       smin_corpus_topk gives on the whole corpus;
 //   smin_corpus_span_topk  ranks, per query, the span-valued moments of its videos (smin_merge_window_moments' lists of a bank of
-//                       windows over long videos): the same rounds over the same key, five fields per entry.
+//                       windows over long videos): the same rounds over the same key, five fields per entry;
+//   smin_span_search_merge  merges up to 16 such span lists of shards of whole videos into one: the same order,
+//                       found without the rounds -- the lists are sorted, so each candidate's rank is a sum of binary searches.
 // smin_pair_assemble has an adjoint, which is what lets a model train through shared banks:
 //   smin_pair_assemble_bwd  sums the pairs' gradients of f, f_w, f_s back onto the videos and queries they came from, through the
 //                           pairs grouped by video and by query (two CSR lists from the host): no atomics, a fixed order.
-// The two merges have no backward.
+// The merges have no backward.
 // The training-side counterpart of the search:
 //   smin_mine_pairs         picks, per query, its own video and the N highest-scoring wrong ones -- topk_rounds over a third way of
 //                           reading candidate c, a row of pair scores without the query's own video -- and groups the picked pairs by
@@ -389,6 +391,78 @@ void corpus_span_topk_kernel(const float* __restrict__ span, const float* __rest
     src.out.finish(topk_rounds(src, lists ? (g1 - g0) * kv : 0, K));
 }
 
+// smin_span_search_merge: S ranked span lists of disjoint video shards into one, in ONE pass instead of K rounds.
+// Each list is sorted, so a candidate's place in the merge is its own position plus, for every other list, the number of entries
+// that go ahead of it -- a binary search over that list's order words.  Only Key::hi (score order, inverted global video) takes part:
+// the two low fields of smin_search_merge's key are (list, position), which the rank spells out as ">=" for the lists before s, ">"
+// for those after, and p itself.  Passed to the kernel by value, as RankedTables.
+struct SpanTables {
+    const long long* video[MERGE_MAX_S]; const float* span[MERGE_MAX_S]; const float* score[MERGE_MAX_S]; const long long* window[MERGE_MAX_S];
+    const long long* cell[MERGE_MAX_S]; const int* count[MERGE_MAX_S];
+    long long offset[MERGE_MAX_S];
+    int k[MERGE_MAX_S], base[MERGE_MAX_S + 1], S;
+};
+
+// The number of the n words at a (descending) that go ahead of `mine`: those >= mine (or_equal) or > mine.  n <= CORPUS_MAX_K, so
+// seven halvings; every index read is < n whatever the words hold.
+__device__ __forceinline__ int count_ahead(const u64* a, int n, u64 mine, bool or_equal)
+{
+    int lo = 0;
+#pragma unroll
+    for (int step = CORPUS_MAX_K; step >= 1; step >>= 1) {
+        const int m = lo + step;
+        if (m <= n && (or_equal ? a[m - 1] >= mine : a[m - 1] > mine)) lo = m;
+    }
+    return lo;
+}
+
+// One workgroup per query.  The order words of all candidates go to LDS (list s at base[s], 8 KB at most), every output slot is set
+// to the empty pattern, and after one barrier each candidate whose rank is below nk moves its five fields to that slot.  For lists
+// ordered as assumed the ranks are a permutation of 0 .. sum(cnt) - 1: each slot below nk is written once more, by one thread.  For
+// any other input rank <= p + the other lists' counts < sum(cnt), so a write stays inside the query's K slots.
+__global__ __launch_bounds__(CT)
+void span_search_merge_kernel(const SpanTables tb, const SpanOut out)
+{
+    __shared__ u64 hi[MERGE_MAX_S * CORPUS_MAX_K];
+    __shared__ int cnt[MERGE_MAX_S];
+    const int t = threadIdx.x, S = tb.S;
+    const long long q = blockIdx.x;
+    if (t < S) cnt[t] = min(max(tb.count[t][q], 0), tb.k[t]);
+    out.finish(0);                                               // all K slots empty (and count 0, which thread 0 overwrites below)
+    __syncthreads();
+    for (int c = t; c < tb.base[S]; c += CT) {
+        int s = 0;
+        while (s + 1 < S && c >= tb.base[s + 1]) ++s;
+        const int p = c - tb.base[s];
+        if (p >= cnt[s]) continue;                               // behind the count: never read
+        const long long i = q * tb.k[s] + p;
+        hi[c] = make_key(tb.score[s][i], (int)(tb.video[s][i] + tb.offset[s]), 0, 0).hi;
+    }
+    __syncthreads();
+    int total = 0;
+    for (int s = 0; s < S; ++s) total += cnt[s];
+    const int nk = min(total, out.K);
+    for (int c = t; c < tb.base[S]; c += CT) {
+        int s = 0;
+        while (s + 1 < S && c >= tb.base[s + 1]) ++s;
+        const int p = c - tb.base[s];
+        if (p >= cnt[s]) continue;
+        const u64 mine = hi[c];
+        int rank = p;
+        for (int o = 0; o < S; ++o)
+            if (o != s) rank += count_ahead(hi + tb.base[o], cnt[o], mine, o < s);
+        if (rank >= nk) continue;
+        const long long i = q * tb.k[s] + p;
+        const size_t r = out.at(rank);
+        out.video[r] = tb.video[s][i] + tb.offset[s];
+        out.span[2 * r] = tb.span[s][2 * i]; out.span[2 * r + 1] = tb.span[s][2 * i + 1];      // plain moves: the bits leave as they came
+        out.score[r] = tb.score[s][i];
+        out.window[r] = tb.window[s][i];
+        out.cell[2 * r] = tb.cell[s][2 * i]; out.cell[2 * r + 1] = tb.cell[s][2 * i + 1];
+    }
+    if (t == 0) out.count[q] = nk;
+}
+
 // ---- hard-negative mining (smin_mine_pairs).  Query q owns the pairs q * S .. q * S + S - 1, S = 1 + N: slot 0 its own video, slots
 // 1 .. N the negatives of ranks skip .. skip + N - 1.  smin_mine_pairs' candidates: c = video over row q of the pair scores, the
 // query's own video left out; key parts (slot 0, w = the video, which emit reads back as its pick).
@@ -628,6 +702,43 @@ extern "C" int smin_corpus_span_topk(void* stream, const float* span, const floa
     hipLaunchKernelGGL(corpus_span_topk_kernel, dim3(Q), dim3(CT), 0, (hipStream_t)stream, span, score, (const long long*)window, (const long long*)cell,
                        count, group_video, group_ptr, k_video, K, (long long*)out_video, out_span, out_score, (long long*)out_window,
                        (long long*)out_cell, out_count);
+    SMIN_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int smin_span_search_merge(void* stream, int S, const int64_t* const* video, const float* const* span, const float* const* score,
+                                      const int64_t* const* window, const int64_t* const* cell, const int32_t* const* count,
+                                      const int32_t* k_list, const int64_t* video_offset, int Q, int K, int64_t* out_video, float* out_span,
+                                      float* out_score, int64_t* out_window, int64_t* out_cell, int32_t* out_count)
+{
+    SMIN_REQUIRE(S >= 1 && S <= MERGE_MAX_S && K >= 1 && K <= CORPUS_MAX_K && Q >= 0);
+    SpanTables tb{};
+    tb.S = S;
+    if (k_list) {
+        for (int s = 0; s < S; ++s) {
+            SMIN_REQUIRE(k_list[s] >= 1 && k_list[s] <= CORPUS_MAX_K);
+            tb.k[s] = k_list[s];
+            tb.base[s + 1] = tb.base[s] + k_list[s];
+        }
+    }
+    if (Q == 0) return 0;
+    SMIN_REQUIRE(video != nullptr && span != nullptr && score != nullptr && window != nullptr && cell != nullptr && count != nullptr);
+    SMIN_REQUIRE(k_list != nullptr && video_offset != nullptr);
+    const void* outs[6] = {out_video, out_span, out_score, out_window, out_cell, out_count};
+    for (const void* o : outs) SMIN_REQUIRE(o != nullptr);
+    for (int s = 0; s < S; ++s) {
+        SMIN_REQUIRE(video_offset[s] >= 0 && video_offset[s] <= 0x7fffffffll);
+        const void* in[6] = {video[s], span[s], score[s], window[s], cell[s], count[s]};
+        for (const void* p : in) {
+            SMIN_REQUIRE(p != nullptr);
+            for (const void* o : outs) SMIN_REQUIRE(p != o);     // the candidates read the lists while others write the result
+        }
+        tb.video[s] = (const long long*)video[s]; tb.span[s] = span[s]; tb.score[s] = score[s]; tb.window[s] = (const long long*)window[s];
+        tb.cell[s] = (const long long*)cell[s]; tb.count[s] = count[s];
+        tb.offset[s] = video_offset[s];
+    }
+    const SpanOut out{(long long*)out_video, out_span, out_score, (long long*)out_window, (long long*)out_cell, out_count, K};
+    hipLaunchKernelGGL(span_search_merge_kernel, dim3(Q), dim3(CT), 0, (hipStream_t)stream, tb, out);
     SMIN_LAUNCH_CHECK();
     return 0;
 }

@@ -146,8 +146,26 @@ def gather_search(result, num_videos, group=None, k=None, merge=None):
     (``video``, ``idx``, ``score``, ``count``; times follow from ``moments.search_times`` and the global durations).
     Without an initialised process group, or at world size 1, the rank's own list is merged alone.  Ranks whose lists differ in Q or
     in entries per query, or that pass different ``k``, raise ValueError on every rank (one small gather read on the host)."""
-    from .moments import fold_search, merge_search
-    merge = merge or merge_search
+    from .moments import merge_search
+    return _gather_lists("gather_search", result, {"idx": (torch.int64, (2,)), "score": (torch.float32, ())}, num_videos, group, k, merge or merge_search)
+
+
+def gather_search_windows(result, num_videos, group=None, k=None, merge=None):
+    """``gather_search`` for ``SMIN.search_windows`` lists: each rank searched the window bank of its own shard of
+    whole videos with the same queries; the ranks gather ``video``, ``span``, ``score``, ``window``, ``cell`` and ``count`` and their
+    ``num_videos`` by the same protocol -- the one small dims gather with its ValueError on every rank, rank order, offsets the
+    exclusive prefix sum, more than 16 ranks folded -- and each merges them with ``moments.merge_search_windows`` (HIP; ``merge``:
+    ``moments.merge_search_windows_torch`` is the restatement for CPU groups).  Every rank returns the same dict, bit for bit, without
+    ``times``: they follow from ``moments.window_times`` and the global durations and row counts."""
+    from .moments import merge_search_windows
+    fields = {"span": (torch.float32, (2,)), "score": (torch.float32, ()), "window": (torch.int64, ()), "cell": (torch.int64, (2,))}
+    return _gather_lists("gather_search_windows", result, fields, num_videos, group, k, merge or merge_search_windows)
+
+
+def _gather_lists(what, result, fields, num_videos, group, k, merge):
+    """The protocol of gather_search and gather_search_windows: ``fields`` names a list's tensors beside ``video (Q, k_s)`` int64 and
+    ``count (Q,)`` int32 -- name -> (dtype, the shape behind (Q, k_s))."""
+    from .moments import fold_search
     video = result["video"]
     Q, ks = video.shape
     k = ks if k is None else int(k)
@@ -159,10 +177,11 @@ def gather_search(result, num_videos, group=None, k=None, merge=None):
     dist.all_gather([dims[r] for r in range(world)], mine, group=group)
     dims = dims.tolist()
     if any(d[:3] != dims[0][:3] for d in dims) or min(d[3] for d in dims) < 0:
-        raise ValueError(f"gather_search: every rank's list must have the same queries, entries per query and k, and num_videos >= 0; got "
+        raise ValueError(f"{what}: every rank's list must have the same queries, entries per query and k, and num_videos >= 0; got "
                          f"(Q, k_list, k, num_videos) = {dims}")
-    bufs = {"video": torch.empty((world, Q, ks), dtype=torch.int64, device=dev), "idx": torch.empty((world, Q, ks, 2), dtype=torch.int64, device=dev),
-            "score": torch.empty((world, Q, ks), dtype=torch.float32, device=dev), "count": torch.empty((world, Q), dtype=torch.int32, device=dev)}
+    bufs = {"video": torch.empty((world, Q, ks), dtype=torch.int64, device=dev)}
+    bufs.update({key: torch.empty((world, Q, ks) + tail, dtype=dt, device=dev) for key, (dt, tail) in fields.items()})
+    bufs["count"] = torch.empty((world, Q), dtype=torch.int32, device=dev)
     for key, buf in bufs.items():
         dist.all_gather([buf[r] for r in range(world)], result[key].detach().to(buf.dtype).contiguous(), group=group)
     lists = [{key: buf[r] for key, buf in bufs.items()} for r in range(world)]

@@ -634,11 +634,25 @@ def search_times(video, idx, duration, L):
     return torch.where(idx >= 0, t, torch.full_like(t, float("nan")))
 
 
+def window_times(video, span, duration, n_rows):
+    """``times (Q, k, 2)`` of a ranked list of spans: ``(span * duration[video]) / n_rows[video]`` in fp32 -- localize_windows' formula
+    on each entry's own video; the NaN span of an empty slot carries through.  ``duration`` / ``n_rows``: the (V,) seconds and row
+    counts of the videos ``video`` indexes."""
+    v = video.clamp_min(0)
+    d = duration.to(device=v.device, dtype=torch.float32)[v].unsqueeze(-1)
+    return (span * d) / n_rows.to(device=v.device, dtype=torch.float32)[v].unsqueeze(-1)
+
+
 # ---------------------------------------------------------------- merge of ranked lists of disjoint video shards (INTEGRATION.md 3n)
 MAX_LISTS = 16
 
 
-def _merge_search_check(what, results, video_offset, k, duration, L):
+_SEARCH_FIELDS = {"idx": (2,), "score": ()}                                       # a list's tensors beside video (Q, k_s) and count (Q,):
+_SPAN_FIELDS = {"span": (2,), "score": (), "window": (), "cell": (2,)}           # name -> the shape behind (Q, k_s)
+
+
+def _ranked_lists_check(what, results, video_offset, k, fields):
+    """What the merges of ranked lists check alike, whatever an entry holds: the lists, their offsets and Q."""
     results = list(results)
     S = len(results)
     if not 1 <= S <= MAX_LISTS:
@@ -653,17 +667,22 @@ def _merge_search_check(what, results, video_offset, k, duration, L):
         ks = v.shape[1]
         if not 1 <= ks <= MAX_K:
             raise ValueError(f"{what}: a list holds 1..{MAX_K} slots per query (list {s}: k = {ks})")
-        if tuple(r["idx"].shape) != (Q, ks, 2) or tuple(r["score"].shape) != (Q, ks) or tuple(r["count"].shape) != (Q,):
-            raise ValueError(f"{what}: list {s} must hold idx (Q, k_s, 2) = {(Q, ks, 2)}, score (Q, k_s) and count (Q,); got "
-                             f"{tuple(r['idx'].shape)}, {tuple(r['score'].shape)}, {tuple(r['count'].shape)}")
+        if any(tuple(r[key].shape) != (Q, ks) + tail for key, tail in fields.items()) or tuple(r["count"].shape) != (Q,):
+            raise ValueError(f"{what}: list {s} must hold " + ", ".join(f"{key} {(Q, ks) + tail}" for key, tail in fields.items()) +
+                             f" and count {(Q,)}; got " + ", ".join(str(tuple(r[key].shape)) for key in list(fields) + ["count"]))
         if r["video"].device != results[0]["video"].device:
             raise ValueError(f"{what}: the lists must be on one device")
     off = [0] * S if video_offset is None else [int(x) for x in video_offset]
     if len(off) != S or min(off) < 0 or max(off) >= 2 ** 31:
         raise ValueError(f"{what}: video_offset must hold one offset in [0, 2**31) per list (got {off})")
+    return results, off, Q
+
+
+def _merge_search_check(what, results, video_offset, k, duration, L):
+    checked = _ranked_lists_check(what, results, video_offset, k, _SEARCH_FIELDS)
     if duration is not None and L is None:
         raise ValueError(f"{what}: times need L, the number of clips per video, beside duration")
-    return results, off, Q
+    return checked
 
 
 def merge_search(results, video_offset=None, k=5, duration=None, L=None):
@@ -745,3 +764,90 @@ def fold_search(lists, offsets, k, merge):
     for r0 in range(MAX_LISTS, len(lists), MAX_LISTS - 1):
         carry = merge([carry] + list(lists[r0:r0 + MAX_LISTS - 1]), [0] + list(offsets[r0:r0 + MAX_LISTS - 1]), k=k)
     return carry
+
+
+# ---------------------------------------------------------------- merge of span lists of sharded window banks
+def _merge_span_check(what, results, video_offset, k, duration, n_rows):
+    checked = _ranked_lists_check(what, results, video_offset, k, _SPAN_FIELDS)
+    if (duration is None) != (n_rows is None):
+        raise ValueError(f"{what}: times need both duration and n_rows, the global (V,) seconds and row counts of the videos")
+    return checked
+
+
+def _with_window_times(out, duration, n_rows):
+    if duration is not None:
+        out["times"] = window_times(out["video"], out["span"], torch.as_tensor(duration), torch.as_tensor(n_rows))
+    return out
+
+
+def merge_search_windows(results, video_offset=None, k=5, duration=None, n_rows=None):
+    """One ranked list of span-valued moments per query out of 1..16 ``SMIN.search_windows``-style lists, each over its own shard of a
+    corpus of long videos (include/smin_hip.h, smin_span_search_merge): one launch, one workgroup per query; each candidate finds its
+    rank in the merge by a binary search over every other list and moves its fields there -- one pass, not k rounds.
+
+    ``results``: dicts with ``video (Q, k_s)`` int64, ``span (Q, k_s, 2)`` fp32, ``score (Q, k_s)``, ``window (Q, k_s)`` int64,
+    ``cell (Q, k_s, 2)`` int64 and ``count (Q,)`` on one HIP device with one Q (their ``times``, if any, are not read);
+    ``video_offset``: host ints, list s's first global video (default all 0).  Order: merge_search's -- higher score first (-0 counts
+    as +0), ties -> lower global video, then lower list, then lower position.  Each list is assumed ordered as ``search_windows``
+    orders it; then the merge of the lists of shards of whole, disjoint videos in ascending offset is, bit for bit, the list
+    ``search_windows`` / ``corpus_span_topk`` give on the whole corpus at equal pair scores, all at once or folded
+    (``merge_search_windows([carry, next], [0, seen])``; any number of lists: ``fold_search``).  No host synchronisation.
+
+    Returns ``search_windows``' dict with global ids in ``video``; with ``duration`` and ``n_rows`` (the global (V,) seconds and row
+    counts) also ``times``, by ``window_times``."""
+    results, off, Q = _merge_span_check("merge_search_windows", results, video_offset, k, duration, n_rows)
+    for r in results:
+        for key in _SPAN_KEYS:
+            _require_hip(r[key], "merge_search_windows")
+    dev, S = results[0]["video"].device, len(results)
+    dtypes = dict(video=torch.int64, span=torch.float32, score=torch.float32, window=torch.int64, cell=torch.int64, count=torch.int32)
+    cols = [[r[key].detach().to(dtypes[key]).contiguous() for r in results] for key in _SPAN_KEYS]
+    tables = [(ctypes.c_void_p * S)(*[t.data_ptr() for t in col]) for col in cols]
+    k_list = (ctypes.c_int32 * S)(*[t.shape[1] for t in cols[0]])
+    offsets = (ctypes.c_int64 * S)(*off)
+    out = {"video": torch.empty((Q, k), dtype=torch.int64, device=dev), "span": torch.empty((Q, k, 2), dtype=torch.float32, device=dev),
+           "score": torch.empty((Q, k), dtype=torch.float32, device=dev), "window": torch.empty((Q, k), dtype=torch.int64, device=dev),
+           "cell": torch.empty((Q, k, 2), dtype=torch.int64, device=dev), "count": torch.empty((Q,), dtype=torch.int32, device=dev)}
+    with torch.cuda.device(dev):
+        call("smin_span_search_merge", stream(), S, *[ctypes.cast(t, ctypes.c_void_p) for t in tables], ctypes.cast(k_list, ctypes.c_void_p),
+             ctypes.cast(offsets, ctypes.c_void_p), Q, k, *[ptr(out[key]) for key in _SPAN_KEYS])
+    return _with_window_times(out, duration, n_rows)
+
+
+def merge_search_windows_torch(results, video_offset=None, k=5, duration=None, n_rows=None):
+    """``merge_search_windows`` as plain torch + Python on any device (same result, bit for bit): each query's candidates sorted by
+    (score, global video, list, position)."""
+    results, off, Q = _merge_span_check("merge_search_windows_torch", results, video_offset, k, duration, n_rows)
+    dev = results[0]["video"].device
+    per, base = [], [0]
+    for r in results:
+        score = r["score"].detach().float()
+        sc = torch.where(score == 0, torch.zeros_like(score), score)                             # -0 -> +0
+        u = sc.contiguous().view(torch.int32).to(torch.int64) & 0xFFFFFFFF
+        o = torch.where(u >= 0x80000000, u ^ 0xFFFFFFFF, u | 0x80000000).clamp_min(1).tolist()  # the order word of top_moments_torch
+        ks = score.shape[1]
+        per.append((o, r["video"].to(torch.int64).tolist(), r["count"].to(torch.int64).clamp(0, ks).tolist()))
+        base.append(base[-1] + ks)
+    # list after list, (Q, sum k_s); span and score as integers, so a NaN keeps its payload and -0 its sign
+    everything = {"video": torch.cat([r["video"].to(torch.int64) + off[s] for s, r in enumerate(results)], dim=1),
+                  "span": torch.cat([r["span"].detach().float().contiguous().view(torch.int32) for r in results], dim=1),
+                  "score": torch.cat([r["score"].detach().float().contiguous().view(torch.int32) for r in results], dim=1),
+                  "window": torch.cat([r["window"].to(torch.int64) for r in results], dim=1),
+                  "cell": torch.cat([r["cell"].to(torch.int64) for r in results], dim=1)}
+    out = {"video": torch.full((Q, k), -1, dtype=torch.int64, device=dev),
+           "span": torch.full((Q, k, 2), 0x7FC00000, dtype=torch.int32, device=dev).view(torch.float32),    # the kernel's NaN
+           "score": torch.zeros((Q, k), dtype=torch.float32, device=dev),
+           "window": torch.full((Q, k), -1, dtype=torch.int64, device=dev),
+           "cell": torch.full((Q, k, 2), -1, dtype=torch.int64, device=dev),
+           "count": torch.zeros((Q,), dtype=torch.int32, device=dev)}
+    for q in range(Q):
+        cand = [(-o[q][p], vid[q][p] + off[s], s, p) for s, (o, vid, cnt) in enumerate(per) for p in range(cnt[q])]
+        cand.sort()
+        n = min(len(cand), k)
+        if n:
+            flat = torch.tensor([base[s] + p for _, _, s, p in cand[:n]], dtype=torch.int64, device=dev)
+            for key, src in everything.items():
+                dst = out[key].view(torch.int32) if key in ("span", "score") else out[key]
+                dst[q, :n] = src[q, flat]
+        out["count"][q] = n
+    return _with_window_times(out, duration, n_rows)

@@ -12,7 +12,7 @@ from ._host import _AttnMaps, byte_mask, host_array, known_cells, query_mask_row
 from .feeder import build_masks_hip, cell_count
 from .functional import attn_maps_gather
 from .moments import (MAX_K, _top_moments_into, corpus_span_topk, corpus_span_topk_torch, corpus_topk, corpus_topk_torch, merge_window_moments,
-                      merge_window_moments_torch, mine_pairs, search_times, top_moments, top_moments_torch)
+                      merge_window_moments_torch, mine_pairs, search_times, top_moments, top_moments_torch, window_times)
 from .sampling import MAX_ROWS, MODES, sample_windows, window_plan
 
 
@@ -568,11 +568,7 @@ class _Retrieval:
 
     @staticmethod
     def _window_times(r, duration, n_rows):
-        """``times = (span * duration[video]) / n_rows[video]`` in fp32 -- localize_windows' formula on each entry's own video; the NaN
-        span of an empty slot carries through."""
-        v = r["video"].clamp_min(0)
-        d = duration.to(device=v.device, dtype=torch.float32)[v].unsqueeze(-1)
-        r["times"] = (r["span"] * d) / n_rows.to(torch.float32)[v].unsqueeze(-1)
+        r["times"] = window_times(r["video"], r["span"], duration, n_rows)           # moments' one formula, on each entry's own video
         return r
 
     def search_windows(self, windows, queries, pairs=None, k=5, k_video=None, k_window=None, nms_thresh=0.5, duration=None, max_batch=64):

@@ -596,3 +596,76 @@ def test_model_corpus_windows(model, raw, lengths, queries, gt_video, gt_times, 
 
 
 test_model_corpus_windows.__test__ = False
+
+
+def search_window_shards(model, shards, queries, *, window=None, stride=None, k=25, k_video=5, k_window=None, nms_thresh=0.5, max_batch=64):
+    """``model.search_windows`` over a corpus of long videos that comes in shards: ``queries`` is a QueryBank
+    (``model.encode_queries``), ``shards`` an iterable of dicts with ``encode_windows``' ``raw (R_s, Din)`` and ``lengths (V_s,)`` and a
+    host ``duration (V_s,)``.  Per shard: ``encode_windows``, ``search_windows`` at (k, k_video, k_window) without durations, then
+    ``carry = merge_search_windows([carry, r], [0, videos seen], k=k)`` -- at equal pair scores the list ``search_windows`` gives on one
+    bank of all the videos.  A SHARD MUST HOLD WHOLE VIDEOS: the NMS of a (query, video) group runs within one bank.  One shard's bank
+    is alive at a time.  Returns ``(carry, duration, n_rows)``: the ranked list with global video ids in shard order, and the shards'
+    durations (float64) and row counts (int64) concatenated as host arrays.  No host read."""
+    import numpy as np
+    from .moments import merge_search_windows
+    carry, seen, durations, rows = None, 0, [], []
+    for shard in shards:
+        n, d = host_array(shard["lengths"]), host_array(shard["duration"], np.float64)
+        if d.shape[0] != n.shape[0]:
+            raise ValueError(f"search_window_shards: duration must cover the shard's {n.shape[0]} videos (got {d.shape[0]})")
+        bank = model.encode_windows(shard["raw"], n, window=window, stride=stride, max_batch=max_batch)
+        r = model.search_windows(bank, queries, k=k, k_video=k_video, k_window=k_window, nms_thresh=nms_thresh, max_batch=max_batch)
+        carry = r if carry is None else merge_search_windows([carry, r], [0, seen], k=k)
+        seen += n.shape[0]
+        durations.append(d)
+        rows.append(n)
+    if carry is None:
+        raise ValueError("search_window_shards: at least one shard of videos")
+    return carry, np.concatenate(durations), np.concatenate(rows)
+
+
+def test_model_corpus_window_shards(model, shards, queries, gt_video, gt_times, meter=None, *, window=None, stride=None, k=25, k_video=5,
+                                    k_window=None, nms_thresh=0.5, max_batch=64):
+    """``test_model_corpus_windows`` over a corpus that comes in shards of whole videos: VCMR R@n, IoU=m, VR R@n
+    and mIoU of ``model.search_windows``, with no host read beside the meter's one at the end.  ``shards``: an iterable of dicts with
+    ``raw``, ``lengths`` and a host ``duration (V_s,)`` in seconds; ``queries``: a dict with ``query_features`` and ``query_mask``,
+    encoded once; ``gt_video (Q,)``: each query's video as a global index in shard order, ``gt_times (Q, 2)`` its moment in seconds,
+    both host values.  The shards are searched and folded by ``search_window_shards``; the merged list gets ``times`` from the
+    concatenated durations and row counts, which travel with ``gt_video`` and ``gt_times`` in one pinned asynchronous copy; one
+    ``meter.update`` (meter.CorpusMeter; a default one is made if none is given) and the one ``meter.result()``, which is returned.
+    The meter is not reset here.
+
+    VR@n is exact when ``k >= max(n) * k_video``, as in ``test_model_corpus``; anything less raises ValueError before any retrieval runs."""
+    import numpy as np
+    from .moments import window_times
+    n_max = 5 if meter is None else max(meter.n)
+    if k < n_max or k < n_max * k_video:
+        raise ValueError(f"test_model_corpus_window_shards: k = {k} entries per query cannot give an exact R@{n_max} / VR@{n_max} at k_video = "
+                         f"{k_video}: needs k >= max(n) * k_video = {n_max * k_video}")
+    gv, gt = host_array(gt_video), host_array(gt_times, np.float64, (-1, 2))
+    Q = queries["query_features"].shape[0]
+    if gv.shape[0] != Q or gt.shape[0] != Q:
+        raise ValueError(f"test_model_corpus_window_shards: gt_video (Q,) and gt_times (Q, 2) must cover the Q = {Q} queries (got {gv.shape}, {gt.shape})")
+    model.eval()
+    bank = model.encode_queries(queries["query_features"], queries["query_mask"])
+    dev = queries["query_features"].device
+    if meter is None:
+        from .meter import CorpusMeter
+        meter = CorpusMeter(device=dev)
+    carry, duration, n_rows = search_window_shards(model, shards, bank, window=window, stride=stride, k=k, k_video=k_video, k_window=k_window,
+                                                   nms_thresh=nms_thresh, max_batch=max_batch)
+    V_all = duration.shape[0]
+    if Q and (gv.min() < 0 or gv.max() >= V_all):
+        raise ValueError(f"test_model_corpus_window_shards: gt_video must lie in [0, {V_all}), the videos of the shards")
+    # gt_video and the row counts (int64, first: 8-byte aligned), then the durations and gt_times (fp32), as bytes of one pinned buffer:
+    # one asynchronous copy
+    host = np.concatenate([np.concatenate([gv, n_rows]).astype(np.int64).view(np.uint8),
+                           np.concatenate([duration, gt.reshape(-1)]).astype(np.float32).view(np.uint8)])
+    buf = torch.from_numpy(host).pin_memory().to(dev, non_blocking=True)
+    i64, f32 = buf[:8 * (Q + V_all)].view(torch.int64), buf[8 * (Q + V_all):].view(torch.float32)
+    carry["times"] = window_times(carry["video"], carry["span"], f32[:V_all], i64[Q:])
+    meter.update(carry, i64[:Q], f32[V_all:].reshape(Q, 2))
+    return meter.result()
+
+
+test_model_corpus_window_shards.__test__ = False
