@@ -62,7 +62,9 @@ extern "C" {
  * workspace size query for each entry point that had none -- smin_proposal_map_fwd_ws_bytes, smin_proposal_map_bwd_ws_bytes,
  * smin_clip_window_means_fwd_ws_bytes, smin_clip_window_means_bwd_ws_bytes, smin_gate_bwd_ws_bytes, smin_moment_unit_bwd_ws_bytes,
  * smin_score_map_bwd_ws_bytes and smin_content_unit_bwd_ws_bytes (smin_workspace_bytes is now their maximum); merging the span lists
- * of sharded window banks -- smin_span_search_merge (smin_search_merge for smin_corpus_span_topk's lists, as a one-pass rank) */
+ * of sharded window banks -- smin_span_search_merge (smin_search_merge for smin_corpus_span_topk's lists, as a one-pass rank); video ranking
+ * by the pooled pair score -- smin_pair_pool, smin_group_pool, smin_video_rank and smin_moment_reweight (the score the contrastive loss
+ * trains, read at inference: a video ranking, a weight on each video's moments and a cut to the best videos) */
 #define SMIN_HIP_ABI_VERSION 2
 
 int smin_abi_version(void);
@@ -961,6 +963,77 @@ int smin_pair_rank_fwd(void* stream, const float* pm, const float* ps, const flo
  * Rejection.  A nonzero status before the launch, the outputs untouched, for a size out of range, a NULL pointer or a bad tau. */
 int smin_pair_rank_bwd(void* stream, const float* dloss, const float* stats, const float* coef, const float* pool, const float* pm,
                        const float* ps, const float* pe, const uint8_t* mm, int P, int L, float tau, float* dpm, float* dps, float* dpe);
+
+/* ---- video ranking by the pooled pair score (csrc/video_rank.hip): the score smin_pair_rank_fwd contrasts, read
+ * at inference.  All arithmetic fp32; no atomics, plain stores; no workspace; no host read; no allocation; capturable.
+ *
+ * smin_pair_pool: the pooled score of each of P maps; one launch, one workgroup of 256 per map.
+ * Inputs.  pm [P][L][L], ps [P][L], pe [P][L] fp32, mm [P][L][L] one byte per cell (nonzero = valid), tau: as smin_pair_rank_fwd.
+ * Outputs, every element written.  score [P] = s_p of smin_pair_rank_fwd, BIT FOR BIT its pair_score on the same inputs: both entry
+ *   points run one copy of the device code (csrc/pair_pool.h), in smin_pair_rank_fwd's order -- thread t takes cells t, t + 256, ...,
+ *   wave_sum, the four waves as (w0 + w1) + (w2 + w3), the maximum first and the sum second.  pool [P][2] = { m_p, sum_valid expf((f -
+ *   m_p) / tau) }; cells [P] = n_p, the number of valid cells, as fp32 (exact: L <= 4096).  A pair without a valid cell: score 0, pool
+ *   { 0, 0 }, cells 0.
+ * Limits.  P >= 1, 1 <= L <= 4096, tau finite and > 0.  The outputs must not overlap the inputs or each other.
+ * Rejection.  A nonzero status before the launch, the outputs untouched, for a size out of range, a NULL pointer or a bad tau. */
+int smin_pair_pool(void* stream, const float* pm, const float* ps, const float* pe, const uint8_t* mm, int P, int L, float tau,
+                   float* score, float* pool, float* cells);
+
+/* smin_group_pool: the score of each (query, video) group of a window search -- the log-mean-exp over all valid cells of the group's
+ * windows, composed from the windows' pools; one launch, one thread per group.
+ * Inputs.  pool [W][2], cells [W] fp32: smin_pair_pool's outputs for the W (query, window) maps; group_ptr [G2 + 1] int32: group g owns
+ *   windows group_ptr[g] .. group_ptr[g + 1]; every entry is clamped into [0, W] and made ascending before it forms an address.
+ * Score.  Over the group's windows with cells[w] > 0, in ascending w: M = max m_w, then S = sum of sum_w * expf((m_w - M) / tau) and
+ *   N = sum of cells_w; score [G2] = M + tau * logf(S / N), out_cells [G2] = N.  A group without windows or without cells: score 0,
+ *   cells 0.  A CELL IN THE OVERLAP OF TWO WINDOWS COUNTS TWICE: the windows are pooled as they were scored, each over its own map.
+ *   The order of every sum depends on the arguments only.
+ * Limits.  G2 >= 0 (G2 == 0: nothing is launched), W >= 0 (W == 0: pool and cells may be NULL, every group comes out empty), tau
+ *   finite and > 0.  Every element of both outputs is written.
+ * Rejection.  A nonzero status before the launch, the outputs untouched, for a negative size, a bad tau or, with G2 > 0, a NULL
+ *   pointer. */
+int smin_group_pool(void* stream, const float* pool, const float* cells, const int32_t* group_ptr, int G2, int W, float tau, float* score,
+                    float* out_cells);
+
+/* smin_video_rank: per query, its videos ranked by the pair score; one launch, one workgroup of 256 per query.
+ * Inputs.  pair_score [P], pair_cells [P] fp32: smin_pair_pool's (or smin_group_pool's) score and cell count of P (query, video) pairs;
+ *   pair_video [P] int32: each pair's video; pair_ptr [Q + 1] int32: query q owns pairs pair_ptr[q] .. pair_ptr[q + 1], every entry
+ *   clamped into [0, P] and made ascending before it forms an address; the number of pairs per query is not limited.  gt_video [Q]
+ *   int32 or NULL: each query's own video (compared, never an index).  alpha: the weight's exponent scale.
+ * Candidates.  The query's pairs with pair_cells > 0.
+ * Order.  Higher score first (-0 counts as +0); ties go to the lower video, then to the earlier pair: smin_corpus_topk's order word.
+ *   A pair's rank is the number of the query's candidates ahead of it, found by counting against the segment's order words, which go
+ *   through LDS 2048 at a time: no sort, no rounds, any number of pairs.
+ * Outputs, every element written (pair_rank and weight: for an ascending pair_ptr; the pairs in front of the first segment and behind
+ *   the last are written as non-candidates).  A pair_ptr that is not ascending is clamped, so every access stays inside the buffers,
+ *   but the clamped segments may then overlap -- a pair_rank / weight element gets two writers and holds either query's value --
+ *   or leave pairs between them unwritten: the content is unspecified there, and the same bits every run are no longer promised.
+ *   pair_rank [P] int32: the 0-based rank among the query's candidates, -1 for a non-candidate; not limited by n.
+ *   weight [P]: expf(alpha * (s_p - s_max(q))) for a candidate, s_max the query's best candidate score; exactly 1.0f for every
+ *     candidate when alpha == 0; 0 for a non-candidate.  alpha > 0 gives weights in (0, 1], alpha < 0 weights >= 1 (inf once
+ *     alpha * (s_p - s_max) passes fp32's range: the caller's choice).
+ *   out_video [Q][n] int64, out_score [Q][n] fp32 (copied bit for bit), out_count [Q] int32: the first min(n, candidates) candidates;
+ *     empty slots: video -1, score 0.
+ *   gt_rank [Q] int32: the rank of the candidate whose video is gt_video[q] (the best of them, should two pairs name it); -1 if no
+ *     candidate of the query names it or gt_video is NULL.
+ * Limits.  0 <= P <= 0x7fff0000 (P == 0: the four lists and pair_rank / weight may be NULL), Q >= 0 (Q == 0: nothing is launched),
+ *   1 <= n <= 64, alpha finite, of either sign.  The outputs must not overlap the inputs or each other.
+ * Determinism.  The same bits every run: ranks are counts, each output slot has one writer.
+ * Rejection.  A nonzero status before the launch, the outputs untouched, for a size out of range, an alpha that is not finite or,
+ *   with Q > 0, a NULL pointer other than gt_video. */
+int smin_video_rank(void* stream, const float* pair_score, const float* pair_cells, const int32_t* pair_video, const int32_t* pair_ptr,
+                    const int32_t* gt_video, int P, int Q, int n, float alpha, int64_t* out_video, float* out_score, int32_t* out_count,
+                    int32_t* pair_rank, float* weight, int32_t* gt_rank);
+
+/* smin_moment_reweight: the pairs' moment lists weighted by their video and cut to the best videos; one launch, one thread per slot.
+ * Inputs.  score [P][k] fp32, count [P] int32: smin_top_moments' (or smin_merge_window_moments') lists of the P pairs; pair_rank [P],
+ *   weight [P]: smin_video_rank's.
+ * Outputs, every element written.  out_score [P][k] = score * weight[p], one fp32 multiplication (slots behind the count included:
+ *   nothing reads them); out_count [P] = count[p] where max_videos <= 0 (no cut) or 0 <= pair_rank[p] < max_videos, else 0.  The lists
+ *   keep their order (weight >= 0), so smin_corpus_topk and smin_corpus_span_topk rank them unchanged.
+ * Limits.  P >= 0 (P == 0: nothing is launched), 1 <= k <= 64, P * k < 2^39.  The outputs must not overlap the inputs.
+ * Rejection.  A nonzero status before the launch, the outputs untouched, for a size out of range or, with P > 0, a NULL pointer. */
+int smin_moment_reweight(void* stream, const float* score, const int32_t* count, const int32_t* pair_rank, const float* weight, int P, int k,
+                         int max_videos, float* out_score, int32_t* out_count);
 
 /* ---- stand-alone fp32 MFMA GEMM  C[M][N] = A[M][K] * B[N][K]^T  (used by tests and bench.py's
  * roofline probe; same engine as every contraction above). */

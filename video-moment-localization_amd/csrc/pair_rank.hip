@@ -10,76 +10,25 @@
 #include <cmath>
 
 #include "common.h"
+#include "pair_pool.h"
 #include "smin_hip.h"
 
 namespace smin {
 
-constexpr float RANK_CLAMP = 1e-12f;          // under the square roots, as torch.clamp_min: the derivative stays finite
-
-__device__ __forceinline__ float rank_root(float x) { return sqrtf(fmaxf(x, RANK_CLAMP)); }
-// d sqrt(max(x, c)) / dx with clamp_min's gradient (passes where x >= c)
-__device__ __forceinline__ float rank_root_grad(float x, float root) { return x >= RANK_CLAMP ? 0.5f / root : 0.f; }
-__device__ __forceinline__ float rank_cell(float pm, float a, float b) { return (pm * a) * b; }
-__device__ __forceinline__ float rank_exp(float f, float m, float tau) { return expf((f - m) / tau); }
-
-__device__ __forceinline__ float wave_max(float v) {
-    v = fmaxf(v, __shfl_xor(v, 1));
-    v = fmaxf(v, __shfl_xor(v, 2));
-    v = fmaxf(v, __shfl_xor(v, 4));
-    v = fmaxf(v, __shfl_xor(v, 8));
-    v = fmaxf(v, __shfl_xor(v, 16));
-    v = fmaxf(v, __shfl_xor(v, 32));
-    return v;
-}
-// the four waves' totals, ((w0 + w1) + (w2 + w3)): loss.hip's block_sum
-__device__ __forceinline__ float rank_block_sum(float v, float* red) {
-    v = wave_sum(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return (red[0] + red[1]) + (red[2] + red[3]);
-}
-__device__ __forceinline__ float rank_block_max(float v, float* red) {
-    v = wave_max(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-}
-
 // pool[p] = { m_p, sum_valid exp((f - m_p) / tau) } (both 0 for a pair without a valid cell), score[p] = s_p, coef[p] = 0 (the query
-// pass overwrites it for every pair a segment lists).  Thread t takes cells t, t + 256, ... of the row-major map in ascending order.
+// pass overwrites it for every pair a segment lists).  Thread t takes cells t, t + 256, ... of the row-major map in ascending order
+// (pair_pool.h: the pooling smin_pair_pool shares).
 __global__ __launch_bounds__(256)
 void pair_rank_pool_kernel(const float* __restrict__ pm, const float* __restrict__ ps, const float* __restrict__ pe, const uint8_t* __restrict__ mm,
                            int L, float tau, float* __restrict__ score, float* __restrict__ pool, float* __restrict__ coef)
 {
     __shared__ float red[4];
-    const int p = blockIdx.x, t = threadIdx.x;
-    const size_t map = (size_t)p * L * L, row = (size_t)p * L;
-    const int cells = L * L, di = 256 / L, dj = 256 % L;
-    float mx = -INFINITY, cnt = 0.f;
-    for (int k = t, i = t / L, j = t % L; k < cells; k += 256) {
-        if (mm[map + k]) {
-            mx = fmaxf(mx, rank_cell(pm[map + k], rank_root(ps[row + i]), rank_root(pe[row + j])));
-            cnt += 1.f;
-        }
-        i += di; j += dj;
-        if (j >= L) { j -= L; ++i; }
-    }
-    mx = rank_block_max(mx, red);
-    cnt = rank_block_sum(cnt, red);
-    const float m = cnt > 0.f ? mx : 0.f;
-    float sum = 0.f;
-    for (int k = t, i = t / L, j = t % L; k < cells; k += 256) {
-        if (mm[map + k]) sum += rank_exp(rank_cell(pm[map + k], rank_root(ps[row + i]), rank_root(pe[row + j])), m, tau);
-        i += di; j += dj;
-        if (j >= L) { j -= L; ++i; }
-    }
-    sum = rank_block_sum(sum, red);
-    if (t == 0) {
-        score[p] = cnt > 0.f ? m + tau * logf(sum / cnt) : 0.f;
-        pool[2 * (size_t)p] = m;
-        pool[2 * (size_t)p + 1] = cnt > 0.f ? sum : 0.f;
+    const int p = blockIdx.x;
+    const PairPool r = pair_pool_cells(pm, ps, pe, mm, p, L, tau, red);
+    if (threadIdx.x == 0) {
+        score[p] = r.score;
+        pool[2 * (size_t)p] = r.m;
+        pool[2 * (size_t)p + 1] = r.sum;
         coef[p] = 0.f;
     }
 }
@@ -196,9 +145,6 @@ void pair_rank_bwd_kernel(const float* __restrict__ dloss, const float* __restri
         if (w == 0 && j < L) dpe[row + j] = ((col[0][lane] + col[1][lane]) + (col[2][lane] + col[3][lane])) * rank_root_grad(y, b);
     }
 }
-
-static bool rank_temperature(float v) { return std::isfinite(v) && v > 0.f; }
-constexpr int RANK_MAX_L = 4096;              // L * L cells are counted in fp32: exact up to 2^24
 
 }  // namespace smin
 

@@ -322,3 +322,44 @@ class CorpusMeterTorch(_CorpusMeter):
             for q, v in enumerate(torch.stack(hits).tolist()):
                 delta[4 + q] = float(v)                                       # sums of 0 / 1 flags: exact in any order
         self.state += torch.tensor(delta, dtype=torch.float64).to(self.state.device)
+
+
+class VideoRankMeter:
+    """``VideoRankMeter(n=(1, 5, 10, 100), device=...)``: video retrieval measured on the video ranking itself --
+    VR@n for any positive n, the mean reciprocal rank and the number of queries, as fp64 totals in a device tensor.  ``update(gt_rank)``
+    takes ``gt_rank (Q,)`` of ``SMIN.rank_videos`` / ``SMIN.search(video_weight=...)``: the 0-based rank of each query's own video among
+    its ranked videos, -1 where it is not among them.  A query counts for VR@n when ``0 <= gt_rank < n`` and adds ``1 / (gt_rank + 1)``
+    to the MRR sum (0 for -1).  A few torch ops on the tensor's device per update, no host read; ``result()`` is the one read (keys
+    ``"VR@n"``, ``"MRR"``, ``"num_samples"``), ``reset()`` zeroes, ``state`` is ``[queries, sum of reciprocal ranks, hits per n ...]``.
+    ``CorpusMeter``'s VR@n, derived from the videos the best moments lie in, stays as it is."""
+
+    def __init__(self, n=(1, 5, 10, 100), device=None):
+        self.n = tuple(n)
+        if not self.n or any(not isinstance(v, int) or isinstance(v, bool) or v < 1 for v in self.n):
+            raise ValueError(f"VideoRankMeter: n must be positive integers (got {n!r})")
+        self.keys = [f"VR@{v}" for v in self.n]
+        self.device = torch.device("cuda" if device is None else device)
+        self.state = torch.zeros(2 + len(self.n), dtype=torch.float64, device=self.device)
+        self._n = torch.tensor(self.n, dtype=torch.int64).to(self.device, non_blocking=True)
+
+    def reset(self):
+        self.state.zero_()
+
+    def update(self, gt_rank):
+        if gt_rank.dim() != 1 or gt_rank.is_floating_point():
+            raise ValueError(f"VideoRankMeter.update: gt_rank must be an integer (Q,) tensor, got {tuple(gt_rank.shape)} {gt_rank.dtype}")
+        if gt_rank.device != self.state.device:
+            raise ValueError(f"VideoRankMeter on {self.state.device} got a tensor on {gt_rank.device}")
+        r = gt_rank.to(torch.int64)
+        found = r >= 0
+        rr = torch.where(found, 1.0 / (r.clamp_min(0) + 1).to(torch.float64), torch.zeros_like(r, dtype=torch.float64))
+        hits = (found.unsqueeze(1) & (r.unsqueeze(1) < self._n.unsqueeze(0))).sum(dim=0).to(torch.float64)
+        self.state += torch.cat([hits.new_full((1,), float(r.shape[0])), rr.sum().reshape(1), hits])
+
+    def result(self):
+        acc = self.state.tolist()                                              # the one host read
+        num = acc[0]
+        out = {k: (acc[2 + a] / num if num else 0.0) for a, k in enumerate(self.keys)}
+        out["MRR"] = acc[1] / num if num else 0.0
+        out["num_samples"] = int(num)
+        return out

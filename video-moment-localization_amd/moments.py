@@ -622,6 +622,244 @@ def mine_pairs_torch(score, gt_video, negatives, skip=0):
     return tuple(torch.tensor(a, dtype=torch.int32, device=score.device) for a in arrays)
 
 
+# ---------------------------------------------------------------- video ranking by the pooled pair score
+MAX_POOL_L = 4096                   # smin_pair_pool counts a map's cells in fp32
+
+
+def _temperature(what, tau):
+    if not (isinstance(tau, (int, float)) and not isinstance(tau, bool) and 0.0 < float(tau) < float("inf")):
+        raise ValueError(f"{what}: tau must be a finite positive number (got {tau!r})")
+    return float(tau)
+
+
+def _video_weight(what, alpha):
+    if not (isinstance(alpha, (int, float)) and not isinstance(alpha, bool) and float("-inf") < float(alpha) < float("inf")):
+        raise ValueError(f"{what}: the video weight must be a finite number (got {alpha!r})")
+    return float(alpha)
+
+
+def _pool_check(what, pm, ps, pe, moment_mask, tau):
+    if pm.dim() != 3 or pm.shape[1] != pm.shape[2]:
+        raise ValueError(f"{what}: pm must be (P, L, L), got {tuple(pm.shape)}")
+    P, L = pm.shape[0], pm.shape[1]
+    if tuple(ps.shape) != (P, L) or tuple(pe.shape) != (P, L) or tuple(moment_mask.shape) != (P, L, L):
+        raise ValueError(f"{what}: ps / pe must be (P, L) = {(P, L)} and moment_mask (P, L, L); got {tuple(ps.shape)}, {tuple(pe.shape)}, "
+                         f"{tuple(moment_mask.shape)}")
+    if P < 1 or not 1 <= L <= MAX_POOL_L:
+        raise ValueError(f"{what} needs P >= 1 and 1 <= L <= {MAX_POOL_L} (P={P}, L={L})")
+    return P, L, _temperature(what, tau)
+
+
+def _pair_pool_into(pm, ps, pe, moment_mask, tau, score, pool, cells):
+    """smin_pair_pool of P checked maps on ``pm``'s device into the caller's contiguous fp32 ``score (P,)``, ``pool (P, 2)`` and ``cells
+    (P,)`` (e.g. a chunk's rows of larger buffers): one launch, nothing else."""
+    pm_, ps_, pe_ = (x.detach().float().contiguous() for x in (pm, ps, pe))
+    mm_ = byte_mask(moment_mask)
+    with torch.cuda.device(pm.device):
+        call("smin_pair_pool", stream(), ptr(pm_), ptr(ps_), ptr(pe_), ptr(mm_), pm.shape[0], pm.shape[1], float(tau), ptr(score), ptr(pool), ptr(cells))
+
+
+def pair_pool(pm, ps, pe, moment_mask, tau=0.1):
+    """The pooled score of each of P (video, query) maps (include/smin_hip.h, smin_pair_pool): the log-mean-exp at temperature ``tau`` of
+    the valid cells' fused scores ``pm * sqrt(ps_i) * sqrt(pe_j)`` -- the pair score training.pair_rank_loss contrasts, bit for bit.
+    Returns ``(score (P,), pool (P, 2), cells (P,))`` fp32: ``pool = {the maximum m, sum exp((f - m) / tau)}``, ``cells`` the number of
+    valid cells; a pair without one gives 0 throughout.  HIP tensors only; one launch; no host synchronisation."""
+    _require_hip(pm, "pair_pool")
+    P, _, tau = _pool_check("pair_pool", pm, ps, pe, moment_mask, tau)
+    score = torch.empty((P,), dtype=torch.float32, device=pm.device)
+    pool = torch.empty((P, 2), dtype=torch.float32, device=pm.device)
+    cells = torch.empty((P,), dtype=torch.float32, device=pm.device)
+    _pair_pool_into(pm, ps, pe, moment_mask, tau, score, pool, cells)
+    return score, pool, cells
+
+
+def pair_pool_torch(pm, ps, pe, moment_mask, tau=0.1):
+    """``pair_pool`` as plain torch ops on any device, in the dtype of ``pm`` (fp64 inputs give the fp64 reference): the tests'
+    restatement, nothing routes here."""
+    P, _, tau = _pool_check("pair_pool_torch", pm, ps, pe, moment_mask, tau)
+    valid = moment_mask != 0
+    f = (pm * torch.sqrt(ps.clamp_min(1e-12)).unsqueeze(2)) * torch.sqrt(pe.clamp_min(1e-12)).unsqueeze(1)
+    n = valid.reshape(P, -1).sum(dim=1)
+    some = n > 0
+    m = torch.where(valid, f, torch.full_like(f, float("-inf"))).reshape(P, -1).max(dim=1).values
+    m = torch.where(some, m, torch.zeros_like(m))
+    m3 = m.reshape(P, 1, 1)
+    z = (torch.exp((torch.where(valid, f, m3) - m3) / tau) * valid.to(f.dtype)).reshape(P, -1).sum(dim=1)
+    one = torch.ones_like(z)
+    score = torch.where(some, m + tau * torch.log(torch.where(some, z, one) / torch.where(some, n.to(f.dtype), one)), torch.zeros_like(z))
+    return score, torch.stack([m, z], dim=1), n.to(f.dtype)
+
+
+def _group_check(what, pool, cells, group_ptr, tau):
+    if pool.dim() != 2 or pool.shape[1] != 2 or tuple(cells.shape) != (pool.shape[0],):
+        raise ValueError(f"{what}: pool must be (W, 2) and cells (W,), got {tuple(pool.shape)} and {tuple(cells.shape)}")
+    if group_ptr.dim() != 1 or group_ptr.shape[0] < 1:
+        raise ValueError(f"{what}: group_ptr must be (G2 + 1,)")
+    if pool.shape[0] >= 2 ** 31 or group_ptr.shape[0] > 2 ** 31:
+        raise ValueError(f"{what}: {pool.shape[0]} windows in {group_ptr.shape[0] - 1} groups exceed the int32 group_ptr")
+    return pool.shape[0], group_ptr.shape[0] - 1, _temperature(what, tau)
+
+
+def group_pool(pool, cells, group_ptr, tau=0.1):
+    """The pooled score of each (query, video) group of a window search (include/smin_hip.h, smin_group_pool): the log-mean-exp over all
+    valid cells of the group's windows, composed from ``pair_pool``'s ``pool (W, 2)`` and ``cells (W,)`` of the (query, window) maps;
+    ``group_ptr (G2 + 1,)``: group g owns windows ``group_ptr[g] .. group_ptr[g + 1]``.  A cell in the overlap of two windows counts
+    twice.  Returns ``(score (G2,), cells (G2,))`` fp32, 0 and 0 for a group without cells.  HIP tensors only; one launch; no host
+    synchronisation."""
+    _require_hip(group_ptr, "group_pool")
+    W, G2, tau = _group_check("group_pool", pool, cells, group_ptr, tau)
+    dev = group_ptr.device
+    pool_, cells_, gp = pool.detach().float().contiguous(), cells.detach().float().contiguous(), group_ptr.to(torch.int32).contiguous()
+    score = torch.empty((G2,), dtype=torch.float32, device=dev)
+    out_cells = torch.empty((G2,), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        call("smin_group_pool", stream(), ptr(pool_) if W else None, ptr(cells_) if W else None, ptr(gp), G2, W, tau, ptr(score) if G2 else None,
+             ptr(out_cells) if G2 else None)
+    return score, out_cells
+
+
+def group_pool_torch(pool, cells, group_ptr, tau=0.1):
+    """``group_pool`` as plain torch + Python on any device, in the dtype of ``pool``: the tests' restatement (reads the host)."""
+    W, G2, tau = _group_check("group_pool_torch", pool, cells, group_ptr, tau)
+    gp = group_ptr.to(torch.int64).tolist()
+    score, out_cells = pool.new_zeros((G2,)), pool.new_zeros((G2,))
+    for g in range(G2):
+        w0 = min(max(gp[g], 0), W)
+        w1 = min(max(gp[g + 1], w0), W)
+        keep = cells[w0:w1] > 0
+        if not bool(keep.any()):
+            continue
+        m, s = pool[w0:w1, 0][keep], pool[w0:w1, 1][keep]
+        big = m.max()
+        total = cells[w0:w1][keep].sum()
+        score[g] = big + tau * torch.log((s * torch.exp((m - big) / tau)).sum() / total)
+        out_cells[g] = total
+    return score, out_cells
+
+
+_RANK_KEYS = ("video", "score", "count", "pair_rank", "weight", "gt_rank")
+
+
+def _rank_check(what, pair_score, pair_cells, pair_video, pair_ptr, n, alpha, gt_video):
+    if pair_score.dim() != 1 or tuple(pair_cells.shape) != tuple(pair_score.shape) or tuple(pair_video.shape) != tuple(pair_score.shape):
+        raise ValueError(f"{what}: pair_score, pair_cells and pair_video must be (P,); got {tuple(pair_score.shape)}, {tuple(pair_cells.shape)}, "
+                         f"{tuple(pair_video.shape)}")
+    if pair_ptr.dim() != 1 or pair_ptr.shape[0] < 1:
+        raise ValueError(f"{what}: pair_ptr must be (Q + 1,)")
+    P, Q = pair_score.shape[0], pair_ptr.shape[0] - 1
+    if not (isinstance(n, int) and not isinstance(n, bool) and 1 <= n <= MAX_K):
+        raise ValueError(f"{what} needs an integer 1 <= n <= {MAX_K} (got {n!r})")
+    if P > 0x7fff0000:
+        raise ValueError(f"{what}: {P} pairs exceed the int32 pair_ptr")
+    if gt_video is not None and tuple(gt_video.shape) != (Q,):
+        raise ValueError(f"{what}: gt_video must be (Q,) = ({Q},) (got {tuple(gt_video.shape)})")
+    return P, Q, _video_weight(what, alpha)
+
+
+def rank_videos(pair_score, pair_cells, pair_video, pair_ptr, n=5, alpha=0.0, gt_video=None):
+    """Each query's videos ranked by the pooled pair score (include/smin_hip.h, smin_video_rank): one workgroup per query ranks its pairs
+    by counting, any number of pairs per query.
+
+    ``pair_score (P,)`` / ``pair_cells (P,)``: ``pair_pool``'s (or ``group_pool``'s) score and cell count of P (query, video) pairs;
+    ``pair_video (P,)`` each pair's video; ``pair_ptr (Q + 1,)``: query q owns pairs ``pair_ptr[q] .. pair_ptr[q + 1]``; ``gt_video (Q,)``
+    int tensor or None: each query's own video.  Candidates: the pairs with cells > 0.  Order: higher score first, -0 counts as +0,
+    ties -> lower video, then the earlier pair (corpus_topk's).  HIP tensors only; one launch; no host synchronisation.  Returns a
+    dict: ``video (Q, n)`` int64 (-1 for empty slots), ``score (Q, n)`` (0), ``count (Q,)`` int32, ``pair_rank (P,)`` int32 the rank among
+    the query's candidates (-1 for a non-candidate; not limited by n), ``weight (P,)`` = ``exp(alpha * (s_p - the query's best))`` (0
+    for a non-candidate; exactly 1 at alpha = 0) and ``gt_rank (Q,)`` int32 the rank of gt_video's pair (-1: not listed, no candidate,
+    or no gt_video)."""
+    _require_hip(pair_ptr, "rank_videos")
+    P, Q, alpha = _rank_check("rank_videos", pair_score, pair_cells, pair_video, pair_ptr, n, alpha, gt_video)
+    dev = pair_ptr.device
+    args = [pair_score.detach().float(), pair_cells.detach().float(), pair_video.to(torch.int32), pair_ptr.to(torch.int32)]
+    args = [a.contiguous() for a in args]
+    gt = None if gt_video is None or Q == 0 else gt_video.to(torch.int32).contiguous()
+    video = torch.empty((Q, n), dtype=torch.int64, device=dev)
+    score = torch.empty((Q, n), dtype=torch.float32, device=dev)
+    count = torch.empty((Q,), dtype=torch.int32, device=dev)
+    pair_rank = torch.empty((P,), dtype=torch.int32, device=dev)
+    weight = torch.empty((P,), dtype=torch.float32, device=dev)
+    gt_rank = torch.empty((Q,), dtype=torch.int32, device=dev)
+    opt = lambda a: ptr(a) if a.numel() else None
+    with torch.cuda.device(dev):
+        call("smin_video_rank", stream(), *[opt(a) for a in args], ptr(gt), P, Q, n, alpha, opt(video), opt(score), opt(count), opt(pair_rank),
+             opt(weight), opt(gt_rank))
+    return dict(zip(_RANK_KEYS, (video, score, count, pair_rank, weight, gt_rank)))
+
+
+def rank_videos_torch(pair_score, pair_cells, pair_video, pair_ptr, n=5, alpha=0.0, gt_video=None):
+    """``rank_videos`` as plain torch + Python on any device: each query's candidates sorted by (score, video, pair), the same tie
+    rules; ``score`` and ``weight`` in the dtype of ``pair_score`` (fp64 inputs give the fp64 reference).  Reads the host."""
+    P, Q, alpha = _rank_check("rank_videos_torch", pair_score, pair_cells, pair_video, pair_ptr, n, alpha, gt_video)
+    dev, dt = pair_ptr.device, pair_score.dtype
+    s, c, vid, pp = pair_score.detach().tolist(), pair_cells.tolist(), pair_video.to(torch.int64).tolist(), pair_ptr.to(torch.int64).tolist()
+    gt = None if gt_video is None else gt_video.to(torch.int64).tolist()
+    video = torch.full((Q, n), -1, dtype=torch.int64, device=dev)
+    score = torch.zeros((Q, n), dtype=dt, device=dev)
+    count, gt_rank = [0] * Q, [-1] * Q
+    pair_rank, best = [-1] * P, [0.0] * P
+    for q in range(Q):
+        g0 = min(max(pp[q], 0), P)
+        g1 = min(max(pp[q + 1], g0), P)
+        cand = sorted((-(s[e] + 0.0), vid[e], e) for e in range(g0, g1) if c[e] > 0)          # -0 + 0 = +0: -0 counts as +0
+        for r, (_, v, e) in enumerate(cand):
+            pair_rank[e] = r
+            best[e] = s[cand[0][2]]
+            if gt is not None and v == gt[q] and gt_rank[q] < 0:
+                gt_rank[q] = r
+        count[q] = min(len(cand), n)
+        if count[q]:
+            rows = torch.tensor([e for _, _, e in cand[:n]], dtype=torch.int64, device=dev)
+            video[q, :count[q]] = torch.tensor([v for _, v, _ in cand[:n]], dtype=torch.int64, device=dev)
+            score[q, :count[q]] = pair_score.detach()[rows]
+    rank_t = torch.tensor(pair_rank, dtype=torch.int32, device=dev)
+    listed = rank_t >= 0
+    if alpha == 0.0:
+        weight = listed.to(dt)
+    else:
+        top = torch.tensor(best, dtype=dt, device=dev)
+        weight = torch.where(listed, torch.exp(alpha * (torch.where(listed, pair_score.detach(), top) - top)), torch.zeros_like(top))
+    return dict(zip(_RANK_KEYS, (video, score, torch.tensor(count, dtype=torch.int32, device=dev), rank_t, weight,
+                                 torch.tensor(gt_rank, dtype=torch.int32, device=dev))))
+
+
+def _reweight_check(what, score, count, pair_rank, weight, max_videos):
+    if score.dim() != 2 or not 1 <= score.shape[1] <= MAX_K:
+        raise ValueError(f"{what}: score must be (P, k) with 1 <= k <= {MAX_K}, got {tuple(score.shape)}")
+    P = score.shape[0]
+    if tuple(count.shape) != (P,) or tuple(pair_rank.shape) != (P,) or tuple(weight.shape) != (P,):
+        raise ValueError(f"{what}: count, pair_rank and weight must be (P,) = ({P},); got {tuple(count.shape)}, {tuple(pair_rank.shape)}, "
+                         f"{tuple(weight.shape)}")
+    if max_videos is None:
+        return P, 0
+    if not (isinstance(max_videos, int) and not isinstance(max_videos, bool) and 0 <= max_videos < 2 ** 31):
+        raise ValueError(f"{what}: max_videos must be None or an integer >= 0, 0 for no cut (got {max_videos!r})")
+    return P, max_videos
+
+
+def reweight_moments(score, count, pair_rank, weight, max_videos=None):
+    """The pairs' moment lists weighted by their video and cut to each query's best videos (include/smin_hip.h, smin_moment_reweight):
+    ``(score * weight[p], count where 0 <= pair_rank[p] < max_videos else 0)`` for ``score (P, k)`` / ``count (P,)`` of top_moments or
+    merge_window_moments and ``pair_rank`` / ``weight (P,)`` of ``rank_videos``; ``max_videos`` None or 0: no cut.  corpus_topk /
+    corpus_span_topk then rank the lists as they are.  HIP tensors only; one launch; no host synchronisation."""
+    _require_hip(score, "reweight_moments")
+    P, cut = _reweight_check("reweight_moments", score, count, pair_rank, weight, max_videos)
+    args = [score.detach().float(), count.to(torch.int32), pair_rank.to(torch.int32), weight.detach().float()]
+    args = [a.contiguous() for a in args]
+    out_score, out_count = torch.empty_like(args[0]), torch.empty_like(args[1])
+    if P:
+        with torch.cuda.device(score.device):
+            call("smin_moment_reweight", stream(), *[ptr(a) for a in args], P, score.shape[1], cut, ptr(out_score), ptr(out_count))
+    return out_score, out_count
+
+
+def reweight_moments_torch(score, count, pair_rank, weight, max_videos=None):
+    """``reweight_moments`` as plain torch ops on any device, in the dtype of ``score``."""
+    _, cut = _reweight_check("reweight_moments_torch", score, count, pair_rank, weight, max_videos)
+    keep = torch.ones_like(pair_rank, dtype=torch.bool) if cut <= 0 else (pair_rank >= 0) & (pair_rank < cut)
+    return score * weight.to(score.dtype).unsqueeze(1), torch.where(keep, count, torch.zeros_like(count))
+
+
 def search_times(video, idx, duration, L):
     """``times (Q, k, 2)`` of a ranked corpus list: top_moments' formula on each moment's own video, ``(i * duration[video] / L,
     (j + 1) * duration[video] / L)`` in fp32, NaN for empty slots.  ``duration``: the (V,) seconds of the videos ``video`` indexes.

@@ -11,8 +11,9 @@ from . import _lib
 from ._host import _AttnMaps, byte_mask, host_array, known_cells, query_mask_rows, require_hip_tensors, require_ints
 from .feeder import build_masks_hip, cell_count
 from .functional import attn_maps_gather
-from .moments import (MAX_K, _top_moments_into, corpus_span_topk, corpus_span_topk_torch, corpus_topk, corpus_topk_torch, merge_window_moments,
-                      merge_window_moments_torch, mine_pairs, search_times, top_moments, top_moments_torch, window_times)
+from .moments import (MAX_K, _pair_pool_into, _temperature, _top_moments_into, _video_weight, corpus_span_topk, corpus_span_topk_torch, corpus_topk,
+                      corpus_topk_torch, group_pool, merge_window_moments, merge_window_moments_torch, mine_pairs, rank_videos, reweight_moments,
+                      reweight_moments_torch, search_times, top_moments, top_moments_torch, window_times)
 from .sampling import MAX_ROWS, MODES, sample_windows, window_plan
 
 
@@ -154,6 +155,11 @@ def _chunk_buffers(n, k, max_batch, dev):
     score = torch.empty((n, k), dtype=torch.float32, device=dev)
     count = torch.empty((n,), dtype=torch.int32, device=dev)
     return idx, score, count, [(c0, min(c0 + max_batch, n)) for c0 in range(0, n, max_batch)]
+
+
+def _pool_buffers(n, dev):
+    """Where the chunks of n pairs leave pair_pool's ``score (n,)``, ``pool (n, 2)`` and ``cells (n,)`` on ``dev``."""
+    return tuple(torch.empty(shape, dtype=torch.float32, device=dev) for shape in ((n,), (n, 2), (n,)))
 
 
 class _Retrieval:
@@ -457,7 +463,8 @@ class _Retrieval:
             r["times"] = search_times(r["video"], r["idx"], duration, L)          # moments._times' formula on each moment's own video
         return r
 
-    def search(self, videos, queries, pairs=None, k=5, k_video=None, nms_thresh=0.5, duration=None, max_batch=64):
+    def search(self, videos, queries, pairs=None, k=5, k_video=None, nms_thresh=0.5, duration=None, max_batch=64, video_weight=None,
+               max_videos=None, tau=0.1, n_videos=None, gt_video=None):
         """Which video, and where: the k best moments of each of the Q queries of a QueryBank over the videos of a VideoBank.
 
         ``pairs``: None -- every query against every video --, or a host (P, 2) array of (query, video) rows, in any order (sorted
@@ -470,9 +477,31 @@ class _Retrieval:
         Returns a dict: ``video (Q, k)`` int64 (-1 for empty slots), ``idx (Q, k, 2)`` int64 start / end clip (-1), ``score (Q, k)``
         (0), ``count (Q,)`` int32; with ``duration`` (V,) seconds also ``times (Q, k, 2)``: top_moments' formula on
         ``duration[video]``, NaN for empty slots.  Scores come from score_pairs (forward_only_scoring or not: a bank has no graph),
-        in the contraction mode of set_gemm_mode.  No host synchronisation."""
+        in the contraction mode of set_gemm_mode.  No host synchronisation.
+
+        ``video_weight`` / ``max_videos`` (both None: the search above, untouched) bring in the video-level score the contrastive
+        loss trains: each chunk's scores are also pooled into their pair scores at temperature ``tau`` (one
+        pair_pool launch; the model does not run again), one smin_video_rank ranks each query's videos by them, and one
+        smin_moment_reweight multiplies every moment score by ``exp(video_weight * (s_video - the query's best s))`` and, with
+        ``max_videos`` = M, empties the lists of the videos behind the query's best M, before the same smin_corpus_topk.  ``score`` is
+        then the weighted score, and the result gains ``video_rank (Q, n_videos)`` int64 (-1), ``video_score`` (0), ``video_count
+        (Q,)`` and ``gt_rank (Q,)`` int32: the rank of ``gt_video[q]`` (Q host ints) among the query's videos, -1 if it is not listed
+        or no gt_video is given.  ``n_videos`` defaults to min(k, 64)."""
         k, k_video, vi, qi, pair_ptr = self._search_plan("search", videos, queries, pairs, k, k_video, max_batch, duration)
         dev, L, P = videos.device, self.L, vi.shape[0]
+        if video_weight is not None or max_videos is not None:
+            alpha, cut, tau, n_videos, gt = self._video_options("search", video_weight, max_videos, tau, n_videos, gt_video, k, len(queries))
+            parts = [vi, qi, pair_ptr, gt]
+            plan = torch.from_numpy(np.concatenate(parts).astype(np.int32)).pin_memory().to(dev, non_blocking=True)
+            vi_d, qi_d, pp_d, gt_d = plan.split([a.shape[0] for a in parts])
+            with torch.no_grad(), torch.cuda.device(dev):
+                pools = _pool_buffers(P, dev)
+                idx, score, count = self._pair_moments(videos, queries, vi, qi, vi_d, qi_d, k_video, nms_thresh, max_batch, pools=(tau,) + pools)
+                vr = rank_videos(pools[0], pools[2], vi_d, pp_d, n=n_videos, alpha=alpha, gt_video=gt_d if gt.size else None)
+                score, count = reweight_moments(score, count, vr["pair_rank"], vr["weight"], cut)
+                r = corpus_topk(score, idx, count, vi_d, pp_d, k=k)
+            r.update(video_rank=vr["video"], video_score=vr["score"], video_count=vr["count"], gt_rank=vr["gt_rank"])
+            return self._search_result(r, duration, L)
         # the whole plan in one pinned buffer, one asynchronous copy (the call never waits for the device)
         plan = torch.from_numpy(np.concatenate([vi, qi, pair_ptr]).astype(np.int32)).pin_memory().to(dev, non_blocking=True)
         vi_d, qi_d, pp_d = plan[:P], plan[P:2 * P], plan[2 * P:]
@@ -481,15 +510,80 @@ class _Retrieval:
             r = corpus_topk(score, idx, count, vi_d, pp_d, k=k)
         return self._search_result(r, duration, L)
 
-    def _pair_moments(self, videos, queries, vi, qi, vi_d, qi_d, k_video, nms_thresh, max_batch):
+    def _pair_moments(self, videos, queries, vi, qi, vi_d, qi_d, k_video, nms_thresh, max_batch, pools=None):
         """search's chunk loop: top_moments' ``idx (P, k_video, 2)``, ``score (P, k_video)`` and ``count (P,)`` of the P pairs of the
-        checked host lists vi / qi (int32 device copies vi_d / qi_d), scored in chunks of at most ``max_batch``.  No host read."""
+        checked host lists vi / qi (int32 device copies vi_d / qi_d), scored in chunks of at most ``max_batch``.  ``pools``: ``(tau,
+        score (P,), pool (P, 2), cells (P,))`` -- each chunk's scores are then also pooled into these buffers (one pair_pool launch on
+        the scores the chunk already holds).  No host read."""
         idx, score, count, chunks = _chunk_buffers(vi.shape[0], k_video, max_batch, vi_d.device)
         for c0, c1 in chunks:
             pm, ps, pe, _ = self._score_pairs(videos, queries, vi[c0:c1], qi[c0:c1], vi_d[c0:c1], qi_d[c0:c1])
             mm = videos.moment_mask.index_select(0, vi_d[c0:c1])
             _top_moments_into(pm, ps, pe, mm, k_video, nms_thresh, idx[c0:c1], score[c0:c1], count[c0:c1])
+            if pools is not None:
+                _pair_pool_into(pm, ps, pe, mm, pools[0], pools[1][c0:c1], pools[2][c0:c1], pools[3][c0:c1])
         return idx, score, count
+
+    # ---------------------------------------------------------------- video ranking by the pooled pair score (INTEGRATION.md 3t)
+    @staticmethod
+    def _video_options(what, video_weight, max_videos, tau, n_videos, gt_video, k, Q):
+        """The checked video-level options of a search: ``(alpha, max_videos or None, tau, n_videos, gt_video as Q host ints or an empty
+        array)``.  ValueError for a bad value."""
+        alpha = _video_weight(what, 0.0 if video_weight is None else video_weight)
+        if max_videos is not None:
+            require_ints(what, ("max_videos", max_videos, 1, 2 ** 31 - 1))
+        n_videos = min(int(k), MAX_K) if n_videos is None else n_videos
+        require_ints(what, ("n_videos", n_videos, 1, MAX_K))
+        gt = np.zeros(0, np.int64) if gt_video is None else host_array(gt_video)
+        if gt_video is not None and gt.shape[0] != Q:
+            raise ValueError(f"{what}: gt_video must name a video for each of the Q = {Q} queries (got {gt.shape[0]})")
+        return alpha, None if max_videos is None else int(max_videos), _temperature(what, tau), int(n_videos), gt
+
+    def _pair_pools(self, videos, queries, vi, qi, vi_d, qi_d, tau, max_batch):
+        """search's chunk loop with pair_pool where search has the moment cut: ``(score (P,), pool (P, 2), cells (P,))`` of the P pairs of
+        the checked host lists vi / qi.  No host read."""
+        P = vi.shape[0]
+        score, pool, cells = _pool_buffers(P, vi_d.device)
+        for c0 in range(0, P, max_batch):
+            c1 = min(c0 + max_batch, P)
+            pm, ps, pe, _ = self._score_pairs(videos, queries, vi[c0:c1], qi[c0:c1], vi_d[c0:c1], qi_d[c0:c1])
+            _pair_pool_into(pm, ps, pe, videos.moment_mask.index_select(0, vi_d[c0:c1]), tau, score[c0:c1], pool[c0:c1], cells[c0:c1])
+        return score, pool, cells
+
+    def rank_videos(self, videos, queries, pairs=None, n=5, tau=0.1, gt_video=None, max_batch=64):
+        """Which video: each of the Q queries' videos ranked by the pooled pair score, the score training.pair_rank_loss contrasts
+         -- video retrieval only, no moment is cut.  ``videos``: a VideoBank, or a WindowBank of videos of any
+        length; ``pairs`` as ``search`` takes them.  search's chunk loop with one pair_pool per chunk (log-mean-exp of the valid cells'
+        fused scores at temperature ``tau``); for a WindowBank the (query, window) list is pooled and one group_pool composes each
+        (query, video) group's windows (a cell in the overlap of two windows counts twice); then one smin_video_rank: higher score
+        first, ties -> lower video.  A pair without a valid cell (a video without rows) is no candidate.
+
+        Returns a dict: ``video (Q, n)`` int64 (-1 for empty slots), ``score (Q, n)`` (0), ``count (Q,)`` int32, ``pair_score (P,)`` and
+        ``pair_rank (P,)`` int32 (-1 for a non-candidate) over the listed pairs sorted by (query, video), and ``gt_rank (Q,)`` int32, the
+        rank of ``gt_video[q]`` (Q host ints; -1 if it is not listed or no gt_video is given).  The plan travels in one pinned
+        asynchronous copy.  No host synchronisation."""
+        what = "rank_videos"
+        require_ints(what, ("n", n, 1, MAX_K))
+        windowed = isinstance(videos, WindowBank)
+        if windowed:
+            _, _, _, p = self._window_search_plan(what, videos, queries, pairs, 1, 1, 1, max_batch, None)
+            vi, qi, pair_ptr = p["vi"], p["qi"], p["query_ptr"]
+        else:
+            _, _, vi, qi, pair_ptr = self._search_plan(what, videos, queries, pairs, 1, 1, max_batch, None)
+        require_hip_tensors(what, dict(videos=videos.video_mask, queries=queries.query_features), must="hold HIP tensors")
+        Q, P, dev = len(queries), vi.shape[0], videos.device
+        _, _, tau, n, gt = self._video_options(what, None, None, tau, int(n), gt_video, n, Q)
+        parts = [vi, pair_ptr, gt] + ([p["wi"], p["wq"], p["group_ptr"]] if windowed else [qi])
+        with torch.no_grad(), torch.cuda.device(dev):
+            plan = torch.from_numpy(np.concatenate(parts).astype(np.int32)).pin_memory().to(dev, non_blocking=True)
+            vi_d, pp_d, gt_d, *rest = plan.split([a.shape[0] for a in parts])
+            if windowed:
+                _, pool, cells = self._pair_pools(videos, queries, p["wi"], p["wq"], rest[0], rest[1], tau, max_batch)
+                score, cells = group_pool(pool, cells, rest[2], tau)
+            else:
+                score, _, cells = self._pair_pools(videos, queries, vi, qi, vi_d, rest[0], tau, max_batch)
+            vr = rank_videos(score, cells, vi_d, pp_d, n=n, alpha=0.0, gt_video=gt_d if gt.size else None)
+        return dict(video=vr["video"], score=vr["score"], count=vr["count"], pair_score=score, pair_rank=vr["pair_rank"], gt_rank=vr["gt_rank"])
 
     # ---------------------------------------------------------------- corpus search over long videos (INTEGRATION.md 3r)
     def encode_windows(self, raw, lengths, window=None, stride=None, mode="pick", max_batch=64):
@@ -571,7 +665,8 @@ class _Retrieval:
         r["times"] = window_times(r["video"], r["span"], duration, n_rows)           # moments' one formula, on each entry's own video
         return r
 
-    def search_windows(self, windows, queries, pairs=None, k=5, k_video=None, k_window=None, nms_thresh=0.5, duration=None, max_batch=64):
+    def search_windows(self, windows, queries, pairs=None, k=5, k_video=None, k_window=None, nms_thresh=0.5, duration=None, max_batch=64,
+                       video_weight=None, max_videos=None, tau=0.1, n_videos=None, gt_video=None):
         """Which video, and where, over videos of any length: the k best moments of each of the Q queries of a QueryBank over the videos
         of a WindowBank, at the windows' native resolution.
 
@@ -586,10 +681,35 @@ class _Retrieval:
         Returns a dict: ``video (Q, k)`` int64 (-1 for empty slots), ``span (Q, k, 2)`` float32 raw rows of that video (NaN),
         ``score (Q, k)`` (0), ``window (Q, k)`` int64 the window's ordinal within its video (-1), ``cell (Q, k, 2)`` int64 (-1),
         ``count (Q,)`` int32; with ``duration (V,)`` seconds also ``times (Q, k, 2) = (span * duration[video]) / n_rows[video]`` (fp32, NaN
-        for empty slots).  The whole plan travels in one pinned asynchronous copy.  No host synchronisation."""
+        for empty slots).  The whole plan travels in one pinned asynchronous copy.  No host synchronisation.
+
+        ``video_weight`` / ``max_videos`` / ``tau`` / ``n_videos`` / ``gt_video``: as ``search`` takes them (both of the first two None:
+        the search above, untouched).  Each chunk's (query, window) scores are also pooled (pair_pool), one group_pool composes a (query,
+        video) group's windows into the group's score, and smin_video_rank and smin_moment_reweight act on the groups' merged lists in
+        front of the same smin_corpus_span_topk; the result gains ``video_rank``, ``video_score``, ``video_count`` and ``gt_rank``."""
         k, k_video, k_window, p = self._window_search_plan("search_windows", windows, queries, pairs, k, k_video, k_window, max_batch, duration)
+        video_level = video_weight is not None or max_videos is not None
+        if video_level:
+            alpha, cut_v, tau, n_videos, gt = self._video_options("search_windows", video_weight, max_videos, tau, n_videos, gt_video, k, len(queries))
         require_hip_tensors("search_windows", dict(windows=windows.video_mask, queries=queries.query_features), must="hold HIP tensors")
         dev, G, G2, Q, V = windows.device, p["wi"].shape[0], p["vi"].shape[0], len(queries), windows.n_videos
+        if video_level:
+            parts = [p["wi"], p["wq"], p["group_ptr"], p["vi"], p["query_ptr"], windows.n_rows, gt]
+            with torch.no_grad(), torch.cuda.device(dev):
+                plan = torch.from_numpy(np.concatenate(parts).astype(np.int64)).pin_memory().to(dev, non_blocking=True)
+                wi_d, wq_d, gp_d, vid_d, qp_d, nr_d, gt_d = plan.split([a.shape[0] for a in parts])
+                wi32, wq32, vid32, qp32 = (x.to(torch.int32) for x in (wi_d, wq_d, vid_d, qp_d))
+                pools = _pool_buffers(G, dev)
+                idx, score, count = self._pair_moments(windows, queries, p["wi"], p["wq"], wi32, wq32, k_window, nms_thresh, max_batch,
+                                                       pools=(tau,) + pools)
+                g = merge_window_moments(idx, score, count, windows.start.index_select(0, wi_d), windows.len.index_select(0, wi_d), gp_d,
+                                         self.T, self.L, k=k_video, nms_thresh=nms_thresh)
+                gs, gc = group_pool(pools[1], pools[2], gp_d, tau)
+                vr = rank_videos(gs, gc, vid32, qp32, n=n_videos, alpha=alpha, gt_video=gt_d if gt.size else None)
+                g_score, g_count = reweight_moments(g["score"], g["count"], vr["pair_rank"], vr["weight"], cut_v)
+                r = corpus_span_topk(g["span"], g_score, g["window"], g["cell"], g_count, vid32, qp32, k=k)
+                r.update(video_rank=vr["video"], video_score=vr["score"], video_count=vr["count"], gt_rank=vr["gt_rank"])
+                return r if duration is None else self._window_times(r, duration, nr_d)
         host = np.concatenate([p["wi"], p["wq"], p["group_ptr"], p["vi"], p["query_ptr"], windows.n_rows]).astype(np.int64)
         with torch.no_grad(), torch.cuda.device(dev):
             plan = torch.from_numpy(host).pin_memory().to(dev, non_blocking=True)
@@ -603,13 +723,15 @@ class _Retrieval:
             return r if duration is None else self._window_times(r, duration, nr_d)
 
     def search_windows_torch(self, windows, queries, raw=None, pairs=None, k=5, k_video=None, k_window=None, nms_thresh=0.5, duration=None,
-                             max_batch=64, scorer=None):
+                             max_batch=64, scorer=None, pair_rank=None, weight=None, max_videos=None):
         """``search_windows`` restated: the same expansion and chunking, each chunk's windows sampled from ``raw`` (encode_windows'
         ``raw``) and scored with their queries by localize_windows' own route (sample_windows, build_masks_hip, score() / the forward),
         cut by top_moments, merged per group by moments.merge_window_moments_torch and ranked by moments.corpus_span_topk_torch.  Kept
         under its own name as what the tests compare against -- nothing routes here.  ``scorer(window_index, query_index) -> (pm, ps,
         pe, pa)`` replaces the sampling and the model on a chunk's (window, query) pairs (the tests feed it score_pairs, to compare the
-        selection on equal scores; with it ``raw`` is not read, and on CPU banks the cut is top_moments_torch)."""
+        selection on equal scores; with it ``raw`` is not read, and on CPU banks the cut is top_moments_torch).  ``pair_rank`` / ``weight
+        (G2,)`` with ``max_videos``: moments.reweight_moments_torch on the groups' merged lists in front of the ranking (the tests feed it
+        the kernels' ranks and weights of ``search_windows(video_weight=..., max_videos=...)``)."""
         what = "search_windows_torch"
         k, k_video, k_window, p = self._window_search_plan(what, windows, queries, pairs, k, k_video, k_window, max_batch, duration)
         if scorer is None and raw is None:
@@ -638,34 +760,46 @@ class _Retrieval:
             on = lambda a, dt=torch.int64: torch.from_numpy(np.ascontiguousarray(a)).to(device=dev, dtype=dt)
             g = merge_window_moments_torch(idx, score, count, on(windows.starts[p["wi"]]), on(windows.lens[p["wi"]], torch.int32), on(p["group_ptr"]),
                                            T, L, k=k_video, nms_thresh=nms_thresh)
+            if weight is not None:
+                g["score"], g["count"] = reweight_moments_torch(g["score"], g["count"], pair_rank, weight, max_videos)
             r = corpus_span_topk_torch(g["span"], g["score"], g["window"], g["cell"], g["count"], on(p["vi"], torch.int32),
                                        on(p["query_ptr"], torch.int32), k=k)
             return r if duration is None else self._window_times(r, duration, on(windows.n_rows))
 
     # ---------------------------------------------------------------- hard-negative mining
-    def pair_scores(self, videos, queries, max_batch=64):
+    def pair_scores(self, videos, queries, max_batch=64, pool=None, tau=0.1):
         """``(Q, V)`` float32: the best fused moment score of every (query, video) pair of a QueryBank and a VideoBank -- search's chunk
         loop over all pairs at one moment per pair, so the bits of ``top_moments(*score_pairs(all pairs)[:3], moment_mask, k=1)``'s
-        slot 0; 0 for a pair without a valid cell.  Under torch.no_grad(); no host read."""
+        slot 0; 0 for a pair without a valid cell.  ``pool="lme"``: the pooled pair score at temperature ``tau`` instead -- the bits of
+        ``moments.pair_pool`` on the same scores, the score training.pair_rank_loss contrasts.  Under
+        torch.no_grad(); no host read."""
+        if pool not in (None, "lme"):
+            raise ValueError(f"pair_scores: pool must be None (the best moment) or 'lme' (the pooled pair score), got {pool!r}")
         _, _, vi, qi, _ = self._search_plan("pair_scores", videos, queries, None, 1, 1, max_batch, None)
         dev = videos.video_features.device
         with torch.no_grad(), torch.cuda.device(dev):
             vi_d, qi_d = torch.from_numpy(np.concatenate([vi, qi]).astype(np.int32)).pin_memory().to(dev, non_blocking=True).split(vi.shape[0])
+            if pool == "lme":
+                return self._pair_pools(videos, queries, vi, qi, vi_d, qi_d, _temperature("pair_scores", tau), max_batch)[0].reshape(len(queries), len(videos))
             _, score, _ = self._pair_moments(videos, queries, vi, qi, vi_d, qi_d, 1, 1.0, max_batch)   # (an empty slot's score is 0)
         return score.reshape(len(queries), len(videos))
 
-    def mine_pairs(self, videos, queries, gt_video, negatives, skip=0, max_batch=64):
+    def mine_pairs(self, videos, queries, gt_video, negatives, skip=0, max_batch=64, pool=None, tau=0.1):
         """The pairs to train on, chosen by the model: for each query of the QueryBank its own video ``gt_video[q]`` (Q host ints) and
         the ``negatives`` wrong videos of the VideoBank it scores highest after the ``skip`` hardest -- ``pair_scores``, then
         moments.mine_pairs.  Returns a device-built PairPlan of Q * (1 + negatives) pairs for ``forward_pairs(plan=...)`` and
-        training.pair_targets.  The banks are a snapshot of the parameters, and so is the choice.  No host read."""
-        return mine_pairs(self.pair_scores(videos, queries, max_batch), gt_video, negatives, skip)
+        training.pair_targets.  The banks are a snapshot of the parameters, and so is the choice.  ``pool`` / ``tau``: pair_scores' --
+        ``pool="lme"`` mines by the pooled pair score the contrastive term contrasts, None by the best moment.  No host read."""
+        return mine_pairs(self.pair_scores(videos, queries, max_batch, pool=pool, tau=tau), gt_video, negatives, skip)
 
-    def search_torch(self, videos, queries, pairs=None, k=5, k_video=None, nms_thresh=0.5, duration=None, max_batch=64, scorer=None):
+    def search_torch(self, videos, queries, pairs=None, k=5, k_video=None, nms_thresh=0.5, duration=None, max_batch=64, scorer=None,
+                     pair_rank=None, weight=None, max_videos=None):
         """``search`` restated: the same plan and chunking, each chunk's pairs expanded and scored by score(), cut by top_moments and
         merged by moments.corpus_topk_torch.  Kept under its own name as what the tests compare against -- nothing routes here.
         ``scorer(video_index, query_index) -> (pm, ps, pe, pa)`` replaces score() on the expanded pairs (the tests feed it
-        score_pairs, to compare the ranking on equal scores)."""
+        score_pairs, to compare the ranking on equal scores).  ``pair_rank`` / ``weight (P,)`` with ``max_videos``:
+        moments.reweight_moments_torch on the pairs' lists in front of the ranking (the tests feed it the kernels' ranks and weights of
+        ``search(video_weight=..., max_videos=...)``)."""
         k, k_video, vi, qi, pair_ptr = self._search_plan("search_torch", videos, queries, pairs, k, k_video, max_batch, duration)
         dev, L, P = videos.video_features.device, self.L, vi.shape[0]
         idx, score, count, chunks = _chunk_buffers(P, k_video, max_batch, dev)
@@ -682,6 +816,8 @@ class _Retrieval:
                                                videos.length_mask.index_select(0, vi_d), mm)
                 t = top_moments(pm, ps, pe, mm, k=k_video, nms_thresh=nms_thresh)
                 idx[c0:c1], score[c0:c1], count[c0:c1] = t["idx"], t["score"], t["count"]
+        if weight is not None:
+            score, count = reweight_moments_torch(score, count, pair_rank, weight, max_videos)
         r = corpus_topk_torch(score, idx, count, torch.from_numpy(vi).to(dev), torch.from_numpy(pair_ptr).to(dev), k=k)
         return self._search_result(r, duration, L)
 

@@ -401,7 +401,7 @@ def train_epoch_pairs(model, optimizer, groups, meter=None, rank_weight=0.0, tau
     return metrics["loss"], metrics
 
 
-def train_epoch_mined(model, optimizer, groups, negatives, skip=0, meter=None, max_batch=64, rank_weight=0.0, tau=0.1, gamma=0.1):
+def train_epoch_mined(model, optimizer, groups, negatives, skip=0, meter=None, max_batch=64, rank_weight=0.0, tau=0.1, gamma=0.1, mine_pool=None):
     """train_epoch_pairs with the pairs chosen by the model (hard-negative mining).  A group is train_epoch_pairs'
     dict without the two lists: the tensors, ``gt_video`` (Q host ints) and optionally ``cell_counts``.  Per group, under
     torch.no_grad(): encode_videos / encode_queries with the current parameters and ``model.mine_pairs`` -- every query against every
@@ -410,7 +410,9 @@ def train_epoch_mined(model, optimizer, groups, negatives, skip=0, meter=None, m
     negatives) pairs.  With ``cell_counts`` of one value per group nothing is read back before the one ``meter.result()`` at the
     end; with unequal counts the node reads the pairs' cell count once per step, and without them encode_videos reads the videos'
     counts as well.  ``num_samples`` counts the queries.  Returns ``(train_loss, iou_metrics)``.  The meter is not reset here.
-    ``rank_weight``, ``tau``, ``gamma``: train_epoch_pairs' contrastive term over the mined plan -- what a hard negative is mined for."""
+    ``rank_weight``, ``tau``, ``gamma``: train_epoch_pairs' contrastive term over the mined plan -- what a hard negative is mined for.
+    ``mine_pool``: SMIN.mine_pairs' ``pool`` -- ``"lme"`` mines by the pooled pair score at ``tau``, the score that term contrasts
+    (INTEGRATION.md 3t); None by the best moment."""
     rank_weight = _rank_weight("train_epoch_mined", rank_weight, tau, gamma)
     model.train()
     for g in groups:
@@ -418,7 +420,7 @@ def train_epoch_mined(model, optimizer, groups, negatives, skip=0, meter=None, m
         with torch.no_grad():
             videos = model.encode_videos(g["video_features"], g["video_mask"], g["length_mask"], g["moment_mask"], cell_counts=g.get("cell_counts"))
             queries = model.encode_queries(g["query_features"], g["query_mask"])
-            plan = model.mine_pairs(videos, queries, g["gt_video"], negatives, skip=skip, max_batch=max_batch)
+            plan = model.mine_pairs(videos, queries, g["gt_video"], negatives, skip=skip, max_batch=max_batch, pool=mine_pool, tau=tau)
         _pair_step(model, optimizer, g, plan, meter, rank_weight, tau, gamma)
     metrics = meter.result()
     return metrics["loss"], metrics
@@ -513,7 +515,16 @@ def search_shards(model, video_shards, queries, *, k=25, k_video=5, nms_thresh=0
     return carry, np.concatenate(durations)
 
 
-def test_model_corpus(model, video_shards, queries, gt_video, gt_times, meter=None, *, k=25, k_video=5, nms_thresh=0.5, max_batch=64):
+def _video_level(video_weight, max_videos, video_meter):
+    """``(on, video_weight)``: whether a corpus test loop runs with the video-level options, and the weight it hands to
+    the search -- 0.0 where only a meter asks for the video ranking: the neutral setting, at which the moments' list is the plain
+    search's bit for bit."""
+    on = video_weight is not None or max_videos is not None or video_meter is not None
+    return on, 0.0 if on and video_weight is None and max_videos is None else video_weight
+
+
+def test_model_corpus(model, video_shards, queries, gt_video, gt_times, meter=None, *, k=25, k_video=5, nms_thresh=0.5, max_batch=64,
+                      video_weight=None, max_videos=None, tau=0.1, video_meter=None):
     """The test loop of corpus search: VCMR R@n, IoU=m, VR R@n and mIoU of ``model.search`` over a corpus in shards, with no host
     read beside ``encode_videos``' own and the meter's one at the end.  ``video_shards``: an iterable of dicts with
     ``encode_videos``' four arguments and a host ``duration (V_s,)`` in seconds; ``queries``: a dict with ``query_features`` and
@@ -524,9 +535,21 @@ def test_model_corpus(model, video_shards, queries, gt_video, gt_times, meter=No
     The meter is not reset here.
 
     VR@n is exact when ``k >= max(n) * k_video`` -- the first n distinct videos of a list occupy at most that many entries --;
-    anything less, like ``k < max(n)``, raises ValueError before any retrieval runs."""
+    anything less, like ``k < max(n)``, raises ValueError before any retrieval runs.
+
+    ``video_weight`` / ``max_videos`` / ``tau``: ``model.search``'s video-level options; ``video_meter``: a
+    meter.VideoRankMeter, updated with the search's ``gt_rank`` (its ``result()`` is the caller's to read; given alone, the search runs
+    at ``video_weight=0.0``, which leaves the moments' list as it is and adds the video ranking).  With any of them the corpus
+    must come as ONE shard -- the weight needs the corpus-wide best score and rank, which a merge of shard lists does not have;
+    ValueError for more.  The shard may carry ``cell_counts`` (encode_videos'), and the loop then reads nothing but ``meter.result()``."""
     import numpy as np
     from .moments import search_times
+    video_level, video_weight = _video_level(video_weight, max_videos, video_meter)
+    if video_level:
+        video_shards = list(video_shards)
+        if len(video_shards) != 1:
+            raise ValueError(f"test_model_corpus: video_weight / max_videos / video_meter need the corpus as one shard (got {len(video_shards)}): "
+                             "the video weight and rank are corpus-wide, and the shard merges do not carry them")
     n_max = 5 if meter is None else max(meter.n)
     if k < n_max or k < n_max * k_video:
         raise ValueError(f"test_model_corpus: k = {k} entries per query cannot give an exact R@{n_max} / VR@{n_max} at k_video = {k_video}: "
@@ -541,9 +564,23 @@ def test_model_corpus(model, video_shards, queries, gt_video, gt_times, meter=No
     if meter is None:
         from .meter import CorpusMeter
         meter = CorpusMeter(device=dev)
-    carry, duration = search_shards(model, video_shards, bank, k=k, k_video=k_video, nms_thresh=nms_thresh, max_batch=max_batch)
-    if Q and (gv.min() < 0 or gv.max() >= duration.shape[0]):
-        raise ValueError(f"test_model_corpus: gt_video must lie in [0, {duration.shape[0]}), the videos of the shards")
+    if video_level:
+        shard = video_shards[0]
+        videos = model.encode_videos(shard["video_features"], shard["video_mask"], shard["length_mask"], shard["moment_mask"],
+                                     cell_counts=shard.get("cell_counts"))
+        duration = host_array(shard["duration"], np.float64)
+        if duration.shape[0] != len(videos):
+            raise ValueError(f"test_model_corpus: duration must cover the shard's {len(videos)} videos (got {duration.shape[0]})")
+        if Q and (gv.min() < 0 or gv.max() >= duration.shape[0]):
+            raise ValueError(f"test_model_corpus: gt_video must lie in [0, {duration.shape[0]}), the videos of the shard")
+        carry = model.search(videos, bank, k=k, k_video=k_video, nms_thresh=nms_thresh, max_batch=max_batch, video_weight=video_weight,
+                             max_videos=max_videos, tau=tau, gt_video=gv)
+        if video_meter is not None:
+            video_meter.update(carry["gt_rank"])
+    else:
+        carry, duration = search_shards(model, video_shards, bank, k=k, k_video=k_video, nms_thresh=nms_thresh, max_batch=max_batch)
+        if Q and (gv.min() < 0 or gv.max() >= duration.shape[0]):
+            raise ValueError(f"test_model_corpus: gt_video must lie in [0, {duration.shape[0]}), the videos of the shards")
     # gt_video (int64, first: 8-byte aligned), then the durations and gt_times (fp32), as bytes of one pinned buffer: one asynchronous copy
     V_all = duration.shape[0]
     host = np.concatenate([gv.astype(np.int64).view(np.uint8), np.concatenate([duration, gt.reshape(-1)]).astype(np.float32).view(np.uint8)])
@@ -558,7 +595,8 @@ test_model_corpus.__test__ = False
 
 
 def test_model_corpus_windows(model, raw, lengths, queries, gt_video, gt_times, duration, meter=None, *, window=None, stride=None, k=25,
-                              k_video=5, k_window=None, nms_thresh=0.5, max_batch=64):
+                              k_video=5, k_window=None, nms_thresh=0.5, max_batch=64, video_weight=None, max_videos=None, tau=0.1,
+                              video_meter=None):
     """The test loop of corpus search over videos of any length: VCMR R@n, IoU=m, VR R@n and mIoU of
     ``model.search_windows``, with no host read beside the meter's one at the end.  ``raw (R, Din)`` / ``lengths``: the V videos' rows
     back to back and their row counts, as ``encode_windows`` takes them; ``queries``: a dict with ``query_features`` and
@@ -567,7 +605,12 @@ def test_model_corpus_windows(model, raw, lengths, queries, gt_video, gt_times, 
     ``encode_windows``, one ``search_windows`` with the durations, one ``meter.update`` (meter.CorpusMeter; a default one is made if
     none is given) and the one ``meter.result()``, which is returned.  The meter is not reset here.
 
-    VR@n is exact when ``k >= max(n) * k_video``, as in ``test_model_corpus``; anything less raises ValueError before any retrieval runs."""
+    VR@n is exact when ``k >= max(n) * k_video``, as in ``test_model_corpus``; anything less raises ValueError before any retrieval runs.
+
+    ``video_weight`` / ``max_videos`` / ``tau``: ``model.search_windows``' video-level options; ``video_meter``: a
+    meter.VideoRankMeter, updated with the search's ``gt_rank`` (given alone, the search runs at ``video_weight=0.0``: the same moments'
+    list, plus the video ranking).  This loop searches one bank, so there is no shard limit here; the
+    sharded loop (``test_model_corpus_window_shards``) takes none of these."""
     import numpy as np
     n_max = 5 if meter is None else max(meter.n)
     if k < n_max or k < n_max * k_video:
@@ -590,7 +633,14 @@ def test_model_corpus_windows(model, raw, lengths, queries, gt_video, gt_times, 
     gv_d, f32 = buf[:8 * Q].view(torch.int64), buf[8 * Q:].view(torch.float32)
     bank = model.encode_queries(queries["query_features"], queries["query_mask"])
     windows = model.encode_windows(raw, lengths, window=window, stride=stride, max_batch=max_batch)
-    r = model.search_windows(windows, bank, k=k, k_video=k_video, k_window=k_window, nms_thresh=nms_thresh, duration=f32[:V], max_batch=max_batch)
+    video_level, video_weight = _video_level(video_weight, max_videos, video_meter)
+    if video_level:
+        r = model.search_windows(windows, bank, k=k, k_video=k_video, k_window=k_window, nms_thresh=nms_thresh, duration=f32[:V], max_batch=max_batch,
+                                 video_weight=video_weight, max_videos=max_videos, tau=tau, gt_video=gv)
+        if video_meter is not None:
+            video_meter.update(r["gt_rank"])
+    else:
+        r = model.search_windows(windows, bank, k=k, k_video=k_video, k_window=k_window, nms_thresh=nms_thresh, duration=f32[:V], max_batch=max_batch)
     meter.update(r, gv_d, f32[V:].reshape(Q, 2))
     return meter.result()
 
