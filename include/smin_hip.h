@@ -64,7 +64,9 @@ extern "C" {
  * smin_score_map_bwd_ws_bytes and smin_content_unit_bwd_ws_bytes (smin_workspace_bytes is now their maximum); merging the span lists
  * of sharded window banks -- smin_span_search_merge (smin_search_merge for smin_corpus_span_topk's lists, as a one-pass rank); video ranking
  * by the pooled pair score -- smin_pair_pool, smin_group_pool, smin_video_rank and smin_moment_reweight (the score the contrastive loss
- * trains, read at inference: a video ranking, a weight on each video's moments and a cut to the best videos) */
+ * trains, read at inference: a video ranking, a weight on each video's moments and a cut to the best videos); that weight and cut
+ * across shards -- smin_search_merge_weighted and smin_span_search_merge_weighted (shard lists that carry their unweighted scores,
+ * merged under the video weights and ranks of all the shards' videos) */
 #define SMIN_HIP_ABI_VERSION 2
 
 int smin_abi_version(void);
@@ -878,6 +880,41 @@ int smin_span_search_merge(void* stream, int S, const int64_t* const* video, con
                            const int64_t* const* window, const int64_t* const* cell, const int32_t* const* count,
                            const int32_t* k_list, const int64_t* video_offset, int Q, int K, int64_t* out_video, float* out_span,
                            float* out_score, int64_t* out_window, int64_t* out_cell, int32_t* out_count);
+
+/* smin_search_merge_weighted, smin_span_search_merge_weighted: S shard lists that carry their UNWEIGHTED moment scores, merged into
+ * the K best per query under the video weights and ranks of all the shards' videos.  One launch, one workgroup of
+ * 256 per query, 8 KB of LDS, no workspace, no atomics, no host read; capturable.  The two differ in what an entry holds beside video,
+ * raw and score: idx [.][2] int64 (smin_corpus_topk's lists) or span [.][2] fp32, window int64 and cell [.][2] int64
+ * (smin_corpus_span_topk's); one templated kernel body.
+ * Inputs.  video, idx (span, window, cell), raw, count: HOST tables of S device pointers, read before the call returns; list s holds
+ *   video [Q][k_s] int64 (local to the list), the entry fields, raw [Q][k_s] fp32 -- the entry's moment score before any video weight --
+ *   and count [Q] int32.  k_list, video_offset: host [S]; video_offset[s] is added to list s's video ids.  video_rank [Q][V] int32
+ *   (-1: not a candidate video) and video_weight [Q][V] fp32 on the device: smin_video_rank's pair_rank and weight over the V global
+ *   videos (pair_ptr[q] = q * V, pair_video = v).  max_videos <= 0: no cut.
+ * Candidates.  Position p of list s for query q iff p < clamp(count_s[q], 0, k_s); with g = video_s[q][p] + video_offset[s] it drops
+ *   out unless 0 <= g < V (g forms no address before that check), video_rank[q][g] >= 0 and (max_videos <= 0 or video_rank[q][g] <
+ *   max_videos).  Its value is raw * video_weight[q][g], one fp32 multiplication: smin_moment_reweight's expression, the same bits.
+ * Order.  Higher value first (-0 counts as +0); ties go to the lower g, then to the lower s, then to the lower p.  THE LISTS ARE NOT
+ *   ASSUMED SORTED in that order (they were ranked under other weights, and rounding may swap near-ties): the surviving candidates'
+ *   order words are staged in LDS and each counts the words ahead of it, as smin_video_rank does -- a strict total order, so the ranks
+ *   are a permutation and, after the fill with the empty pattern, every slot below out_count has exactly one writer.
+ * Outputs, every element written.  out_video [Q][K] int64 = g; the entry fields and out_raw [Q][K] moved bit for bit; out_score [Q][K]
+ *   the value; out_count [Q] = min(survivors, K).  Empty slots: video -1, idx / window / cell -1, span NaN (0x7fc00000), score and
+ *   raw 0.  The result is a list of the same form over global ids: a later merge takes it at offset 0.
+ * Limits.  1 <= S <= 16, 1 <= K <= 64, 1 <= k_list[s] <= 64, 0 <= video_offset[s] < 2^31, V >= 0 (V == 0: the two video tables may be
+ *   NULL, every query comes out empty), Q >= 0 (Q == 0: returns 0, nothing launched).
+ * Determinism.  The same bits every run: ranks are counts, each slot's last writer is fixed by them.
+ * Rejection.  A nonzero status before any launch, the outputs untouched, for S, K or a k out of range, Q < 0, V < 0, and with Q > 0 a
+ *   NULL table, table entry or output, an offset out of range, or an output that is one of the input pointers. */
+int smin_search_merge_weighted(void* stream, int S, const int64_t* const* video, const int64_t* const* idx, const float* const* raw,
+                               const int32_t* const* count, const int32_t* k_list, const int64_t* video_offset, const int32_t* video_rank,
+                               const float* video_weight, int V, int max_videos, int Q, int K, int64_t* out_video, int64_t* out_idx,
+                               float* out_score, float* out_raw, int32_t* out_count);
+int smin_span_search_merge_weighted(void* stream, int S, const int64_t* const* video, const float* const* span, const float* const* raw,
+                                    const int64_t* const* window, const int64_t* const* cell, const int32_t* const* count,
+                                    const int32_t* k_list, const int64_t* video_offset, const int32_t* video_rank, const float* video_weight,
+                                    int V, int max_videos, int Q, int K, int64_t* out_video, float* out_span, float* out_score,
+                                    float* out_raw, int64_t* out_window, int64_t* out_cell, int32_t* out_count);
 
 /* smin_mine_pairs: the pair plan of hard-negative mining -- for each of Q queries its own video and the N
  * highest-scoring wrong videos, as smin_pair_assemble's two lists and smin_pair_assemble_bwd's two groupings, formed on the device.

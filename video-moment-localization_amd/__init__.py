@@ -18,6 +18,8 @@ from .modules import (  # noqa: F401
 from .training import loss_fn, loss_fn_torch, bce_loss, compute_ious, compute_ious_torch, CapturedStep  # noqa: F401
 from .training import train_epoch, eval_epoch, test_model, test_model_windows, test_model_corpus, test_model_corpus_windows  # noqa: F401
 from .training import test_model_corpus_window_shards  # noqa: F401
+from .training import search_shards_weighted, search_window_shards_weighted  # noqa: F401
+from .training import test_model_corpus_weighted_shards, test_model_corpus_window_shards_weighted  # noqa: F401
 from .training import pair_targets, train_epoch_pairs, train_epoch_mined, pair_rank_loss, pair_rank_loss_torch  # noqa: F401
 from .retrieval import PairPlan, WindowBank  # noqa: F401
 from .meter import EpochMeter, EpochMeterTorch, CorpusMeter, CorpusMeterTorch, VideoRankMeter  # noqa: F401
@@ -28,6 +30,8 @@ from .moments import corpus_span_topk, corpus_span_topk_torch, merge_search_wind
 from .moments import corpus_topk, corpus_topk_torch, merge_search, merge_search_torch, mine_pairs, mine_pairs_torch  # noqa: F401
 from .moments import pair_pool, pair_pool_torch, group_pool, group_pool_torch, rank_videos, rank_videos_torch  # noqa: F401
 from .moments import reweight_moments, reweight_moments_torch  # noqa: F401
+from .moments import merge_search_weighted, merge_search_weighted_torch  # noqa: F401
+from .moments import merge_search_windows_weighted, merge_search_windows_weighted_torch  # noqa: F401
 from .moments import span_ious, span_ious_torch, compute_span_ious, compute_span_ious_torch  # noqa: F401
 from .feeder import BatchFeeder, FedBatch, build_targets_hip, build_masks_hip, cell_count  # noqa: F401
 from .sampling import (  # noqa: F401

@@ -9,7 +9,10 @@
 //   smin_corpus_span_topk  ranks, per query, the span-valued moments of its videos (smin_merge_window_moments' lists of a bank of
 //                       windows over long videos): the same rounds over the same key, five fields per entry;
 //   smin_span_search_merge  merges up to 16 such span lists of shards of whole videos into one: the same order,
-//                       found without the rounds -- the lists are sorted, so each candidate's rank is a sum of binary searches.
+//                       found without the rounds -- the lists are sorted, so each candidate's rank is a sum of binary searches;
+//   smin_search_merge_weighted / smin_span_search_merge_weighted  merge shard lists that carry their unweighted scores, under the
+//                       video weights and ranks of the whole corpus: the lists are not sorted in that order, so
+//                       each candidate counts the order words ahead of it -- one templated body over what an entry holds.
 // smin_pair_assemble has an adjoint, which is what lets a model train through shared banks:
 //   smin_pair_assemble_bwd  sums the pairs' gradients of f, f_w, f_s back onto the videos and queries they came from, through the
 //                           pairs grouped by video and by query (two CSR lists from the host): no atomics, a fixed order.
@@ -595,6 +598,151 @@ void mine_fill_kernel(const int* __restrict__ video_index, const int* __restrict
     }
 }
 
+// ---- merge of shard lists that carry their unweighted scores (smin_search_merge_weighted, smin_span_search_merge_weighted;
+// INTEGRATION.md 3u).  A candidate's value is raw * video_weight[q][g], g its global video, and the videos the corpus-wide rank cuts
+// drop out, so the lists are NOT sorted in the order they are merged in (rounding under the new weight may swap near-ties): no
+// binary search.  One workgroup per query stages the order word of every candidate in LDS (0 for one that dropped out; at most
+// 16 * 64 words, 8 KB) and each candidate counts the words ahead of it, as video_rank_kernel does: a larger word, or an equal one
+// earlier in (list, position) order.  That order is strict and total, so the survivors' ranks are a permutation of 0 .. n - 1 and,
+// after the fill with the empty pattern, each slot below nk = min(n, K) has exactly one writer.  What an entry holds beside video, raw
+// and score is the template parameter: F::In the lists' tables, F::Out the output's, with move() and clear().
+struct IdxFields {                           // SMIN.search: the moment's clips
+    struct In { const long long* idx; };
+    struct Out {
+        long long* idx /* [Q][K][2] */;
+        __device__ __forceinline__ void move(size_t o, const In& in, long long i) const { idx[2 * o] = in.idx[2 * i]; idx[2 * o + 1] = in.idx[2 * i + 1]; }
+        __device__ __forceinline__ void clear(size_t o) const { idx[2 * o] = idx[2 * o + 1] = -1; }
+    };
+};
+struct SpanFields {                          // SMIN.search_windows: span, window, cell (SpanOut's fields and empty pattern)
+    struct In { const float* span; const long long* window; const long long* cell; };
+    struct Out {
+        float* span /* [Q][K][2] */; long long* window /* [Q][K] */; long long* cell /* [Q][K][2] */;
+        __device__ __forceinline__ void move(size_t o, const In& in, long long i) const
+        {
+            span[2 * o] = in.span[2 * i]; span[2 * o + 1] = in.span[2 * i + 1];                  // plain moves: the bits leave as they came
+            window[o] = in.window[i];
+            cell[2 * o] = in.cell[2 * i]; cell[2 * o + 1] = in.cell[2 * i + 1];
+        }
+        __device__ __forceinline__ void clear(size_t o) const
+        {
+            span[2 * o] = span[2 * o + 1] = __uint_as_float(0x7fc00000u);
+            window[o] = -1;
+            cell[2 * o] = cell[2 * o + 1] = -1;
+        }
+    };
+};
+template <class F>
+struct WeightedTables {                      // by value, as RankedTables
+    const long long* video[MERGE_MAX_S]; const float* raw[MERGE_MAX_S]; const int* count[MERGE_MAX_S]; typename F::In in[MERGE_MAX_S];
+    long long offset[MERGE_MAX_S];
+    int k[MERGE_MAX_S], base[MERGE_MAX_S + 1], S;
+};
+template <class F>
+struct WeightedOut {
+    long long* video /* [Q][K] */; float* score /* [Q][K] */; float* raw /* [Q][K] */; int* count /* [Q] */;
+    typename F::Out f;
+    int K;
+};
+constexpr int WM_OWN = MERGE_MAX_S * CORPUS_MAX_K / CT;          // candidates a thread owns at most: c = t, t + CT, ...
+
+template <class F>
+__global__ __launch_bounds__(CT)
+void merge_weighted_kernel(const WeightedTables<F> tb, const int* __restrict__ video_rank, const float* __restrict__ video_weight, int V,
+                           int max_videos, const WeightedOut<F> out)
+{
+    __shared__ u64 word[MERGE_MAX_S * CORPUS_MAX_K];
+    __shared__ int cnt[MERGE_MAX_S];
+    __shared__ int red[CT / 64];
+    const int t = threadIdx.x, S = tb.S, ncand = tb.base[S];
+    const long long q = blockIdx.x;
+    if (t < S) cnt[t] = min(max(tb.count[t][q], 0), tb.k[t]);
+    for (int r = t; r < out.K; r += CT) {                         // all K slots empty
+        const size_t o = (size_t)q * out.K + r;
+        out.video[o] = -1;
+        out.score[o] = 0.f;
+        out.raw[o] = 0.f;
+        out.f.clear(o);
+    }
+    __syncthreads();
+    const int nown = (ncand + CT - 1) / CT;                       // (uniform)
+    u64 mine[WM_OWN];
+    float val[WM_OWN];
+    long long src[WM_OWN];
+    int lst[WM_OWN], gvid[WM_OWN], alive = 0;
+#pragma unroll
+    for (int r = 0; r < WM_OWN; ++r) {
+        const int c = t + r * CT;
+        mine[r] = 0ull; val[r] = 0.f; src[r] = 0; lst[r] = 0; gvid[r] = 0;
+        if (c >= ncand) continue;
+        int s = 0;
+        while (s + 1 < S && c >= tb.base[s + 1]) ++s;
+        const int p = c - tb.base[s];
+        if (p < cnt[s]) {                                        // behind the count: never read
+            const long long i = q * tb.k[s] + p;
+            const long long g = tb.video[s][i] + tb.offset[s];
+            if (g >= 0 && g < V) {                               // (g forms no address before this)
+                const size_t e = (size_t)q * V + (size_t)g;
+                const int vr = video_rank[e];
+                if (vr >= 0 && (max_videos <= 0 || vr < max_videos)) {
+                    val[r] = tb.raw[s][i] * video_weight[e];     // smin_moment_reweight's product
+                    mine[r] = make_key(val[r], (int)g, 0, 0).hi; // >= 2^32: never the 0 of a dropped candidate
+                    src[r] = i; lst[r] = s; gvid[r] = (int)g;
+                    ++alive;
+                }
+            }
+        }
+        word[c] = mine[r];
+    }
+    const int nk = min(block_sum(alive, red), out.K);             // (its barriers also publish the stage)
+    int rank[WM_OWN];
+#pragma unroll
+    for (int r = 0; r < WM_OWN; ++r) rank[r] = 0;
+    for (int j = 0; j < ncand; ++j) {                             // one LDS address for the whole wave: a broadcast
+        const u64 w = word[j];
+#pragma unroll
+        for (int r = 0; r < WM_OWN; ++r)
+            if (r < nown) rank[r] += (w > mine[r]) || (w == mine[r] && j < t + r * CT);
+    }
+#pragma unroll
+    for (int r = 0; r < WM_OWN; ++r) {
+        if (mine[r] == 0ull || rank[r] >= nk) continue;
+        const size_t o = (size_t)q * out.K + rank[r];
+        const int s = lst[r];
+        out.video[o] = gvid[r];
+        out.score[o] = val[r];
+        out.raw[o] = tb.raw[s][src[r]];
+        out.f.move(o, tb.in[s], src[r]);
+    }
+    if (t == 0) out.count[q] = nk;
+}
+
+// What the two weighted merges check and fill alike, in front of their own fields.
+template <class F>
+int weighted_tables(WeightedTables<F>& tb, int S, const int64_t* const* video, const float* const* raw, const int32_t* const* count,
+                    const int32_t* k_list, const int64_t* video_offset, const int32_t* video_rank, const float* video_weight, int V, int Q, int K)
+{
+    SMIN_REQUIRE(S >= 1 && S <= MERGE_MAX_S && K >= 1 && K <= CORPUS_MAX_K && Q >= 0 && V >= 0);
+    tb.S = S;
+    if (k_list) {
+        for (int s = 0; s < S; ++s) {
+            SMIN_REQUIRE(k_list[s] >= 1 && k_list[s] <= CORPUS_MAX_K);
+            tb.k[s] = k_list[s];
+            tb.base[s + 1] = tb.base[s] + k_list[s];
+        }
+    }
+    if (Q == 0) return 0;
+    SMIN_REQUIRE(video != nullptr && raw != nullptr && count != nullptr && k_list != nullptr && video_offset != nullptr);
+    SMIN_REQUIRE(V == 0 || (video_rank != nullptr && video_weight != nullptr));      // (V == 0: every candidate drops out, neither is read)
+    for (int s = 0; s < S; ++s) {
+        SMIN_REQUIRE(video[s] != nullptr && raw[s] != nullptr && count[s] != nullptr);
+        SMIN_REQUIRE(video_offset[s] >= 0 && video_offset[s] <= 0x7fffffffll);
+        tb.video[s] = (const long long*)video[s]; tb.raw[s] = raw[s]; tb.count[s] = count[s];
+        tb.offset[s] = video_offset[s];
+    }
+    return 0;
+}
+
 }  // namespace
 }  // namespace smin
 
@@ -739,6 +887,62 @@ extern "C" int smin_span_search_merge(void* stream, int S, const int64_t* const*
     }
     const SpanOut out{(long long*)out_video, out_span, out_score, (long long*)out_window, (long long*)out_cell, out_count, K};
     hipLaunchKernelGGL(span_search_merge_kernel, dim3(Q), dim3(CT), 0, (hipStream_t)stream, tb, out);
+    SMIN_LAUNCH_CHECK();
+    return 0;
+}
+
+// An output that is one of the inputs (a list's tables or the two video tables): the candidates read while others write.
+static bool weighted_alias(const void* const* ins, int n_in, const void* const* outs, int n_out)
+{
+    for (int i = 0; i < n_in; ++i)
+        for (int o = 0; o < n_out; ++o)
+            if (ins[i] != nullptr && ins[i] == outs[o]) return true;
+    return false;
+}
+
+extern "C" int smin_search_merge_weighted(void* stream, int S, const int64_t* const* video, const int64_t* const* idx, const float* const* raw,
+                                          const int32_t* const* count, const int32_t* k_list, const int64_t* video_offset,
+                                          const int32_t* video_rank, const float* video_weight, int V, int max_videos, int Q, int K,
+                                          int64_t* out_video, int64_t* out_idx, float* out_score, float* out_raw, int32_t* out_count)
+{
+    WeightedTables<IdxFields> tb{};
+    const int rc = weighted_tables(tb, S, video, raw, count, k_list, video_offset, video_rank, video_weight, V, Q, K);
+    if (rc != 0 || Q == 0) return rc;
+    SMIN_REQUIRE(idx != nullptr);
+    const void* outs[5] = {out_video, out_idx, out_score, out_raw, out_count};
+    for (const void* o : outs) SMIN_REQUIRE(o != nullptr);
+    for (int s = 0; s < S; ++s) {
+        SMIN_REQUIRE(idx[s] != nullptr);
+        const void* ins[6] = {video[s], idx[s], raw[s], count[s], video_rank, video_weight};
+        SMIN_REQUIRE(!weighted_alias(ins, 6, outs, 5));
+        tb.in[s].idx = (const long long*)idx[s];
+    }
+    const WeightedOut<IdxFields> out{(long long*)out_video, out_score, out_raw, out_count, {(long long*)out_idx}, K};
+    hipLaunchKernelGGL(merge_weighted_kernel<IdxFields>, dim3(Q), dim3(CT), 0, (hipStream_t)stream, tb, video_rank, video_weight, V, max_videos, out);
+    SMIN_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int smin_span_search_merge_weighted(void* stream, int S, const int64_t* const* video, const float* const* span, const float* const* raw,
+                                               const int64_t* const* window, const int64_t* const* cell, const int32_t* const* count,
+                                               const int32_t* k_list, const int64_t* video_offset, const int32_t* video_rank,
+                                               const float* video_weight, int V, int max_videos, int Q, int K, int64_t* out_video, float* out_span,
+                                               float* out_score, float* out_raw, int64_t* out_window, int64_t* out_cell, int32_t* out_count)
+{
+    WeightedTables<SpanFields> tb{};
+    const int rc = weighted_tables(tb, S, video, raw, count, k_list, video_offset, video_rank, video_weight, V, Q, K);
+    if (rc != 0 || Q == 0) return rc;
+    SMIN_REQUIRE(span != nullptr && window != nullptr && cell != nullptr);
+    const void* outs[7] = {out_video, out_span, out_score, out_raw, out_window, out_cell, out_count};
+    for (const void* o : outs) SMIN_REQUIRE(o != nullptr);
+    for (int s = 0; s < S; ++s) {
+        SMIN_REQUIRE(span[s] != nullptr && window[s] != nullptr && cell[s] != nullptr);
+        const void* ins[8] = {video[s], span[s], raw[s], window[s], cell[s], count[s], video_rank, video_weight};
+        SMIN_REQUIRE(!weighted_alias(ins, 8, outs, 7));
+        tb.in[s].span = span[s]; tb.in[s].window = (const long long*)window[s]; tb.in[s].cell = (const long long*)cell[s];
+    }
+    const WeightedOut<SpanFields> out{(long long*)out_video, out_score, out_raw, out_count, {out_span, (long long*)out_window, (long long*)out_cell}, K};
+    hipLaunchKernelGGL(merge_weighted_kernel<SpanFields>, dim3(Q), dim3(CT), 0, (hipStream_t)stream, tb, video_rank, video_weight, V, max_videos, out);
     SMIN_LAUNCH_CHECK();
     return 0;
 }

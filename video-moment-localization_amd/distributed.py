@@ -162,29 +162,83 @@ def gather_search_windows(result, num_videos, group=None, k=None, merge=None):
     return _gather_lists("gather_search_windows", result, fields, num_videos, group, k, merge or merge_search_windows)
 
 
-def _gather_lists(what, result, fields, num_videos, group, k, merge):
-    """The protocol of gather_search and gather_search_windows: ``fields`` names a list's tensors beside ``video (Q, k_s)`` int64 and
-    ``count (Q,)`` int32 -- name -> (dtype, the shape behind (Q, k_s))."""
+def gather_search_weighted(result, num_videos=None, group=None, k=None, video_weight=0.0, max_videos=None, n_videos=None, gt_video=None, merge=None):
+    """``gather_search`` for ``SMIN.search(..., carry=True)`` lists, merged under the corpus-wide video weights and ranks (INTEGRATION.md
+    3u): ``gather_search``'s protocol with ``raw`` and the two ``(Q, V_r)`` matrices ``pair_score`` / ``pair_cells`` added -- their widths
+    differ from rank to rank, so they travel padded to the widest, the widths taken from the one small dims gather -- and each rank
+    merges the lists in rank order with ``moments.merge_search_weighted`` (HIP; ``merge``: ``moments.merge_search_weighted_torch`` is the
+    restatement for CPU groups).  ``num_videos`` defaults to the width of ``pair_score``, which it must equal.  ``video_weight``,
+    ``max_videos`` and ``n_videos`` must be the same on every rank, and are checked with the dims; ``gt_video``: the queries' global
+    videos, the same on every rank.  Every rank returns the same dict, bit for bit.  A mismatch raises ValueError on every rank."""
+    from .moments import merge_search_weighted
+    fields = {"idx": (torch.int64, (2,)), "score": (torch.float32, ()), "raw": (torch.float32, ())}
+    return _gather_weighted("gather_search_weighted", result, fields, num_videos, group, k, merge or merge_search_weighted, video_weight,
+                            max_videos, n_videos, gt_video)
+
+
+def gather_search_windows_weighted(result, num_videos=None, group=None, k=None, video_weight=0.0, max_videos=None, n_videos=None, gt_video=None,
+                                   merge=None):
+    """``gather_search_weighted`` for ``SMIN.search_windows(..., carry=True)`` lists of shards of whole videos, merged by
+    ``moments.merge_search_windows_weighted`` (``merge``: its ``_torch`` restatement for CPU groups)."""
+    from .moments import merge_search_windows_weighted
+    fields = {"span": (torch.float32, (2,)), "score": (torch.float32, ()), "raw": (torch.float32, ()), "window": (torch.int64, ()),
+              "cell": (torch.int64, (2,))}
+    return _gather_weighted("gather_search_windows_weighted", result, fields, num_videos, group, k, merge or merge_search_windows_weighted,
+                            video_weight, max_videos, n_videos, gt_video)
+
+
+def _gather_weighted(what, result, fields, num_videos, group, k, merge, video_weight, max_videos, n_videos, gt_video):
+    import struct
+    for key in ("raw", "pair_score", "pair_cells"):
+        if key not in result:
+            raise ValueError(f"{what}: the list carries no {key} -- search the shard with carry=True")
+    bound = lambda lists, offsets, k: merge(lists, offsets, k=k, video_weight=video_weight, max_videos=max_videos, n_videos=n_videos, gt_video=gt_video)
+    width = int(result["pair_score"].shape[1])
+    # the options every rank must share, as integers of the dims gather: the weight by its fp64 bits
+    options = [struct.unpack("<q", struct.pack("<d", float(video_weight)))[0], -1 if max_videos is None else int(max_videos),
+               -1 if n_videos is None else int(n_videos)]
+    return _gather_lists(what, result, fields, width if num_videos is None else num_videos, group, k, bound, wide=("pair_score", "pair_cells"),
+                         options=[width] + options)
+
+
+def _gather_lists(what, result, fields, num_videos, group, k, merge, wide=(), options=()):
+    """The protocol of the gathers of ranked lists: ``fields`` names a list's tensors beside ``video (Q, k_s)`` int64 and ``count (Q,)``
+    int32 -- name -> (dtype, the shape behind (Q, k_s)).  ``wide``: the list's fp32 ``(Q, num_videos)`` matrices, gathered padded to the
+    widest rank's; ``options``: further integers of the dims gather -- the first the matrices' width, which must be the rank's
+    num_videos, the others values every rank must share."""
     from .moments import fold_search
     video = result["video"]
     Q, ks = video.shape
     k = ks if k is None else int(k)
     if not dist.is_initialized() or dist.get_world_size(group) == 1:
+        if options and options[0] != int(num_videos):
+            raise ValueError(f"{what}: num_videos = {int(num_videos)} must be the width of the list's (Q, V) matrices ({options[0]})")
         return merge([result], [0], k=k)
     world, dev = dist.get_world_size(group), video.device
-    mine = torch.tensor([Q, ks, k, int(num_videos)], dtype=torch.int64, device=dev)
-    dims = torch.empty((world, 4), dtype=torch.int64, device=dev)
+    mine = torch.tensor([Q, ks, k, int(num_videos)] + list(options), dtype=torch.int64, device=dev)
+    dims = torch.empty((world, mine.shape[0]), dtype=torch.int64, device=dev)
     dist.all_gather([dims[r] for r in range(world)], mine, group=group)
     dims = dims.tolist()
     if any(d[:3] != dims[0][:3] for d in dims) or min(d[3] for d in dims) < 0:
         raise ValueError(f"{what}: every rank's list must have the same queries, entries per query and k, and num_videos >= 0; got "
-                         f"(Q, k_list, k, num_videos) = {dims}")
+                         f"(Q, k_list, k, num_videos) = {[d[:4] for d in dims]}")
+    if options and (any(d[4] != d[3] for d in dims) or any(d[5:] != dims[0][5:] for d in dims)):
+        raise ValueError(f"{what}: every rank's num_videos must be the width of its (Q, V) matrices and the video-level options the same on "
+                         f"every rank; got (num_videos, width, options...) = {[d[3:] for d in dims]}")
     bufs = {"video": torch.empty((world, Q, ks), dtype=torch.int64, device=dev)}
     bufs.update({key: torch.empty((world, Q, ks) + tail, dtype=dt, device=dev) for key, (dt, tail) in fields.items()})
     bufs["count"] = torch.empty((world, Q), dtype=torch.int32, device=dev)
     for key, buf in bufs.items():
         dist.all_gather([buf[r] for r in range(world)], result[key].detach().to(buf.dtype).contiguous(), group=group)
     lists = [{key: buf[r] for key, buf in bufs.items()} for r in range(world)]
+    widest = max(d[3] for d in dims)
+    for key in wide:
+        buf = torch.empty((world, Q, widest), dtype=torch.float32, device=dev)
+        own = torch.zeros((Q, widest), dtype=torch.float32, device=dev)
+        own[:, :dims[dist.get_rank(group)][3]] = result[key].detach().float()
+        dist.all_gather([buf[r] for r in range(world)], own, group=group)
+        for r in range(world):
+            lists[r][key] = buf[r, :, :dims[r][3]]
     offsets = [sum(d[3] for d in dims[:r]) for r in range(world)]
     return fold_search(lists, offsets, k, merge)
 

@@ -1089,3 +1089,260 @@ def merge_search_windows_torch(results, video_offset=None, k=5, duration=None, n
                 dst[q, :n] = src[q, flat]
         out["count"][q] = n
     return _with_window_times(out, duration, n_rows)
+
+
+# ---------------------------------------------------------------- weighted merge of shard lists that carry their video scores
+_WEIGHTED_SEARCH_FIELDS = dict(_SEARCH_FIELDS, raw=())
+_WEIGHTED_SPAN_FIELDS = dict(_SPAN_FIELDS, raw=())
+_CARRY_KEYS = ("raw", "pair_score", "pair_cells")
+_WEIGHTED_DTYPES = dict(video=torch.int64, idx=torch.int64, span=torch.float32, score=torch.float32, raw=torch.float32, window=torch.int64,
+                        cell=torch.int64, count=torch.int32)
+
+
+def carry_slots(k, k_video, max_videos=None):
+    """The entries per query a carry list must hold for the k best of the whole corpus to survive a merge under ``max_videos`` = M:
+    ``min(64, k + (M - 1) * k_video)``, and k without a cut.  A shard (or a carry) cuts its list by the best M of ITS videos; up to
+    M - 1 of those are not among the corpus' best M, the corpus-wide ranking drops their entries -- at most ``k_video`` each -- and
+    until then they occupy slots in front of entries that stay.  With that many slots (or with every entry of the shard's best M
+    videos listed, which 64 slots may already do) no entry of the final k is pushed out."""
+    if not (isinstance(k, int) and 1 <= k <= MAX_K and isinstance(k_video, int) and 1 <= k_video <= MAX_K):
+        raise ValueError(f"carry_slots needs integers 1 <= k, k_video <= {MAX_K} (got {k!r}, {k_video!r})")
+    if not max_videos:
+        return k
+    return min(MAX_K, k + (int(max_videos) - 1) * k_video)
+
+
+_LIST_KEYS = ("video", "idx", "span", "score", "raw", "window", "cell", "times")
+
+
+def truncate_search(result, k):
+    """The first ``k`` entries per query of a ranked list (a search result or a carry): slices of its per-entry tensors, the count
+    limited to k, everything else as it is.  A list is sorted, so this is the list its search or merge gives at ``k``.  No host read."""
+    out = dict(result)
+    for key in _LIST_KEYS:
+        if key in out:
+            out[key] = out[key][:, :k].contiguous()
+    out["count"] = out["count"].clamp(max=k)
+    return out
+
+
+def _weighted_check(what, results, video_offset, k, fields, max_videos, n_videos):
+    """The carry lists of a weighted merge, checked: ``(results, offsets, Q, V, max_videos or 0, n_videos)``.  Beside what every merge of
+    ranked lists checks, each list must carry ``raw`` and its ``pair_score`` / ``pair_cells (Q, V_s)``, and the lists must tile the V global
+    videos in ascending offset: offset 0 first, each next one the sum of the widths before it."""
+    results = list(results)
+    for s, r in enumerate(results):
+        missing = [key for key in _CARRY_KEYS if key not in r]
+        if missing:
+            raise ValueError(f"{what}: list {s} carries no {' / '.join(missing)} -- search the shard with carry=True (a plain list cannot be "
+                             "re-weighted against the other shards' videos)")
+    results, off, Q = _ranked_lists_check(what, results, video_offset, k, fields)
+    seen = 0
+    for s, r in enumerate(results):
+        ps, pc = r["pair_score"], r["pair_cells"]
+        if ps.dim() != 2 or ps.shape[0] != Q or tuple(pc.shape) != tuple(ps.shape):
+            raise ValueError(f"{what}: list {s}'s pair_score and pair_cells must be (Q, V_s) with Q = {Q} (got {tuple(ps.shape)}, {tuple(pc.shape)})")
+        if off[s] != seen:
+            raise ValueError(f"{what}: the lists must tile the videos in ascending offset -- list {s} covers {ps.shape[1]} videos and must "
+                             f"start at {seen} (got offsets {off})")
+        seen += ps.shape[1]
+    if Q * seen > 0x7fff0000:
+        raise ValueError(f"{what}: {Q} queries x {seen} videos exceed the int32 pair list of the video ranking")
+    if not (max_videos is None or (isinstance(max_videos, int) and not isinstance(max_videos, bool) and 0 <= max_videos < 2 ** 31)):
+        raise ValueError(f"{what}: max_videos must be None or an integer >= 0, 0 for no cut (got {max_videos!r})")
+    cut = 0 if max_videos is None else max_videos
+    n_videos = min(k, MAX_K) if n_videos is None else n_videos
+    if not (isinstance(n_videos, int) and not isinstance(n_videos, bool) and 1 <= n_videos <= MAX_K):
+        raise ValueError(f"{what}: n_videos must be an integer in [1, {MAX_K}] (got {n_videos!r})")
+    return results, off, Q, seen, cut, n_videos
+
+
+def _video_tables(results, Q, V, n_videos, alpha, gt_video, rank):
+    """The shards' pooled scores side by side and ``rank`` (rank_videos or rank_videos_torch) over them: ``(pair_score (Q, V), pair_cells
+    (Q, V), rank's dict)`` -- every query against every global video, ``pair_ptr[q] = q * V`` and ``pair_video = v``, so ``pair_rank`` and
+    ``weight`` reshape to the (Q, V) tables of the merge.  ``gt_video``: None, a (Q,) int tensor or Q host ints (which travel in one
+    pinned asynchronous copy)."""
+    dev = results[0]["video"].device
+    ps = torch.cat([r["pair_score"].detach().float() for r in results], dim=1)
+    pc = torch.cat([r["pair_cells"].detach().float() for r in results], dim=1)
+    pair_ptr = torch.arange(Q + 1, dtype=torch.int32, device=dev) * V
+    pair_video = torch.arange(V, dtype=torch.int32, device=dev).repeat(Q)
+    if gt_video is not None and not isinstance(gt_video, torch.Tensor):
+        gt = torch.from_numpy(host_array(gt_video).astype(np.int32))
+        gt_video = gt.pin_memory().to(dev, non_blocking=True) if dev.type == "cuda" else gt
+    return ps, pc, rank(ps.reshape(-1), pc.reshape(-1), pair_video, pair_ptr, n=n_videos, alpha=alpha, gt_video=gt_video)
+
+
+def _weighted_result(out, ps, pc, vr):
+    out.update(pair_score=ps, pair_cells=pc, video_rank=vr["video"], video_score=vr["score"], video_count=vr["count"], gt_rank=vr["gt_rank"])
+    return out
+
+
+def _merge_weighted(what, results, off, Q, k, fields, rank_table, weight_table, V, cut):
+    """One launch of smin_search_merge_weighted (``fields`` with ``idx``) or smin_span_search_merge_weighted over checked lists:
+    ``rank_table`` / ``weight_table (Q, V)`` int32 / fp32 on the lists' device, ``cut`` <= 0 for no cut.  Returns the carry's entry keys."""
+    keys = ["video"] + list(fields) + ["count"]
+    for r in results:
+        for key in keys:
+            _require_hip(r[key], what)
+    dev, S = results[0]["video"].device, len(results)
+    spans = "span" in fields
+    order = ("video", "span", "raw", "window", "cell", "count") if spans else ("video", "idx", "raw", "count")
+    cols = [[r[key].detach().to(_WEIGHTED_DTYPES[key]).contiguous() for r in results] for key in order]
+    tables = [(ctypes.c_void_p * S)(*[t.data_ptr() for t in col]) for col in cols]
+    k_list = (ctypes.c_int32 * S)(*[t.shape[1] for t in cols[0]])
+    offsets = (ctypes.c_int64 * S)(*off)
+    rank_table, weight_table = rank_table.to(torch.int32).contiguous(), weight_table.detach().float().contiguous()
+    out_keys = ("video", "span", "score", "raw", "window", "cell", "count") if spans else ("video", "idx", "score", "raw", "count")
+    out = {key: torch.empty((Q,) if key == "count" else (Q, k) + ((2,) if key in ("idx", "span", "cell") else ()), dtype=_WEIGHTED_DTYPES[key], device=dev)
+           for key in out_keys}
+    with torch.cuda.device(dev):
+        call("smin_span_search_merge_weighted" if spans else "smin_search_merge_weighted", stream(), S,
+             *[ctypes.cast(t, ctypes.c_void_p) for t in tables], ctypes.cast(k_list, ctypes.c_void_p), ctypes.cast(offsets, ctypes.c_void_p),
+             ptr(rank_table) if rank_table.numel() else None, ptr(weight_table) if weight_table.numel() else None, V, cut, Q, k,
+             *[ptr(out[key]) if out[key].numel() else None for key in out_keys])
+    return out
+
+
+def _merge_weighted_torch(results, off, Q, k, fields, rank_table, weight_table, V, cut):
+    """``_merge_weighted`` as plain torch + Python on any device (same result, bit for bit): each query's surviving candidates sorted by
+    (value, global video, list, position), the value ``raw * weight`` rounded once to fp32."""
+    dev = results[0]["video"].device
+    rank_l, per, base = rank_table.to(torch.int64).tolist(), [], [0]
+    everything = {key: [] for key in ["video", "score"] + list(fields)}
+    for s, r in enumerate(results):
+        ks = r["video"].shape[1]
+        g = r["video"].to(torch.int64) + off[s]
+        inside = (g >= 0) & (g < V)
+        w = torch.gather(weight_table.detach().float(), 1, torch.where(inside, g, torch.zeros_like(g))) if V else torch.zeros(g.shape, device=dev)
+        value = _mul32(r["raw"].detach().float(), w)
+        sc = torch.where(value == 0, torch.zeros_like(value), value)                             # -0 -> +0
+        u = sc.contiguous().view(torch.int32).to(torch.int64) & 0xFFFFFFFF
+        o = torch.where(u >= 0x80000000, u ^ 0xFFFFFFFF, u | 0x80000000).clamp_min(1).tolist()  # the order word of top_moments_torch
+        per.append((o, g.tolist(), r["count"].to(torch.int64).clamp(0, ks).tolist()))
+        base.append(base[-1] + ks)
+        for key in everything:                                                                 # floats as integers: a NaN keeps its payload, -0 its sign
+            t = g if key == "video" else value if key == "score" else r[key].detach().to(_WEIGHTED_DTYPES[key])
+            everything[key].append(t.contiguous().view(torch.int32) if t.dtype == torch.float32 else t)
+    everything = {key: torch.cat(ts, dim=1) for key, ts in everything.items()}
+    out = {"video": torch.full((Q, k), -1, dtype=torch.int64, device=dev), "score": torch.zeros((Q, k), dtype=torch.float32, device=dev)}
+    for key, tail in fields.items():
+        if key == "score":
+            continue
+        if key == "span":
+            out[key] = torch.full((Q, k, 2), 0x7FC00000, dtype=torch.int32, device=dev).view(torch.float32)        # the kernel's NaN
+        elif key == "raw":
+            out[key] = torch.zeros((Q, k), dtype=torch.float32, device=dev)
+        else:
+            out[key] = torch.full((Q, k) + tail, -1, dtype=torch.int64, device=dev)
+    out["count"] = torch.zeros((Q,), dtype=torch.int32, device=dev)
+    for q in range(Q):
+        cand = []
+        for s, (o, g, cnt) in enumerate(per):
+            for p in range(cnt[q]):
+                gv = g[q][p]
+                if not 0 <= gv < V:
+                    continue
+                vr = rank_l[q][gv]
+                if vr < 0 or (cut > 0 and vr >= cut):
+                    continue
+                cand.append((-o[q][p], gv, s, p))
+        cand.sort()
+        n = min(len(cand), k)
+        if n:
+            flat = torch.tensor([base[s] + p for _, _, s, p in cand[:n]], dtype=torch.int64, device=dev)
+            for key, src in everything.items():
+                dst = out[key].view(torch.int32) if out[key].dtype == torch.float32 else out[key]
+                dst[q, :n] = src[q, flat]
+        out["count"][q] = n
+    return out
+
+
+def merge_search_weighted(results, video_offset=None, k=5, video_weight=0.0, max_videos=None, n_videos=None, gt_video=None, duration=None, L=None):
+    """One ranked list per query out of 1..16 ``SMIN.search(..., carry=True)`` lists of disjoint video shards, ranked as
+    ``search(video_weight=..., max_videos=...)`` ranks one bank of all their videos.  In order: the lists'
+    ``pair_score`` / ``pair_cells (Q, V_s)`` side by side (one torch.cat each, ascending offset), one ``rank_videos`` over the V videos they
+    cover -- the corpus-wide video rank and weight ``exp(video_weight * (s - the query's best s))`` --, and one launch of
+    smin_search_merge_weighted (include/smin_hip.h): each candidate's value is its ``raw`` score times its video's weight, the videos
+    behind the query's best ``max_videos`` drop out, and each survivor finds its rank by counting -- the lists need not be sorted in the
+    new order.  Order: higher value first (-0 counts as +0), ties -> lower global video, then lower list, then lower position.
+
+    ``results``: dicts with ``video (Q, k_s)`` int64, ``idx (Q, k_s, 2)`` int64, ``score``, ``raw (Q, k_s)``, ``count (Q,)`` and ``pair_score`` /
+    ``pair_cells (Q, V_s)`` on one HIP device with one Q; ``video_offset``: host ints, list s's first global video; the lists must tile
+    [0, V) in ascending offset with their widths V_s (ValueError otherwise, or for a list without ``raw`` / ``pair_score`` /
+    ``pair_cells``).  ``gt_video``: Q host ints or a (Q,) int tensor of global ids, or None.  No host synchronisation.
+
+    Returns a list of the same form over global ids -- ``video``, ``idx``, ``score`` (weighted), ``raw`` (moved bit for bit), ``count``,
+    ``pair_score`` / ``pair_cells (Q, V)`` -- so it merges again at offset 0 (``merge_search_weighted([carry, next], [0, V], ...)``;
+    ``fold_search`` with the options bound), plus ``video_rank (Q, n_videos)``, ``video_score``, ``video_count`` and ``gt_rank (Q,)`` of that
+    one ``rank_videos``; with ``duration`` (the global (V,) seconds) and ``L`` also ``times``.  With the same options in every shard
+    search and every merge, ``k_s >= k`` and -- under a cut -- ``carry_slots(k, k_video, max_videos)`` entries in every list that is
+    merged again (the shard lists, and the carries of a fold, cut to k by ``truncate_search`` at the end), the result is, at equal pair
+    scores and away from fp32 near-ties between a query's candidate values, bit for bit the one-bank search's; the carry costs
+    ``Q * V * 8`` bytes and every merge re-ranks all V videos seen."""
+    what = "merge_search_weighted"
+    alpha = _video_weight(what, video_weight)
+    results, off, Q, V, cut, n_videos = _weighted_check(what, results, video_offset, k, _WEIGHTED_SEARCH_FIELDS, max_videos, n_videos)
+    if duration is not None and L is None:
+        raise ValueError(f"{what}: times need L, the number of clips per video, beside duration")
+    for r in results:
+        for key in ("video", "pair_score", "pair_cells"):
+            _require_hip(r[key], what)
+    ps, pc, vr = _video_tables(results, Q, V, n_videos, alpha, gt_video, rank_videos)
+    out = _merge_weighted(what, results, off, Q, k, _WEIGHTED_SEARCH_FIELDS, vr["pair_rank"].reshape(Q, V), vr["weight"].reshape(Q, V), V, cut)
+    if duration is not None:
+        out["times"] = search_times(out["video"], out["idx"], duration, L)
+    return _weighted_result(out, ps, pc, vr)
+
+
+def merge_search_weighted_torch(results, video_offset=None, k=5, video_weight=0.0, max_videos=None, n_videos=None, gt_video=None, duration=None,
+                                L=None, tables=None):
+    """``merge_search_weighted`` as plain torch + Python on any device: the video ranking by ``rank_videos_torch`` -- or, with ``tables``
+    = ``(pair_rank, weight)`` of shape (Q, V), the rank and weight tables it is given (the tests feed it the kernel's, whose expf is
+    not torch's exp) --, then a Python sort on (value, global video, list, position).  Nothing routes here."""
+    what = "merge_search_weighted_torch"
+    alpha = _video_weight(what, video_weight)
+    results, off, Q, V, cut, n_videos = _weighted_check(what, results, video_offset, k, _WEIGHTED_SEARCH_FIELDS, max_videos, n_videos)
+    if duration is not None and L is None:
+        raise ValueError(f"{what}: times need L, the number of clips per video, beside duration")
+    ps, pc, vr = _video_tables(results, Q, V, n_videos, alpha, gt_video, rank_videos_torch)
+    rank_table, weight_table = (vr["pair_rank"], vr["weight"]) if tables is None else tables
+    out = _merge_weighted_torch(results, off, Q, k, _WEIGHTED_SEARCH_FIELDS, rank_table.reshape(Q, V), weight_table.reshape(Q, V), V, cut)
+    if duration is not None:
+        out["times"] = search_times(out["video"], out["idx"], duration, L)
+    return _weighted_result(out, ps, pc, vr)
+
+
+def merge_search_windows_weighted(results, video_offset=None, k=5, video_weight=0.0, max_videos=None, n_videos=None, gt_video=None, duration=None,
+                                  n_rows=None):
+    """``merge_search_weighted`` for ``SMIN.search_windows(..., carry=True)`` lists of shards of whole videos: the same cat, the same one
+    ``rank_videos`` (the lists' ``pair_score`` / ``pair_cells`` are the groups' ``group_pool`` outputs) and one launch of
+    smin_span_search_merge_weighted -- the same kernel body over entries of ``span``, ``window`` and ``cell``.  Returns the carry form
+    with those fields, plus ``video_rank``, ``video_score``, ``video_count`` and ``gt_rank``; with ``duration`` and ``n_rows`` (the global
+    (V,) seconds and row counts) also ``times``, by ``window_times``."""
+    what = "merge_search_windows_weighted"
+    alpha = _video_weight(what, video_weight)
+    results, off, Q, V, cut, n_videos = _weighted_check(what, results, video_offset, k, _WEIGHTED_SPAN_FIELDS, max_videos, n_videos)
+    if (duration is None) != (n_rows is None):
+        raise ValueError(f"{what}: times need both duration and n_rows, the global (V,) seconds and row counts of the videos")
+    for r in results:
+        for key in ("video", "pair_score", "pair_cells"):
+            _require_hip(r[key], what)
+    ps, pc, vr = _video_tables(results, Q, V, n_videos, alpha, gt_video, rank_videos)
+    out = _merge_weighted(what, results, off, Q, k, _WEIGHTED_SPAN_FIELDS, vr["pair_rank"].reshape(Q, V), vr["weight"].reshape(Q, V), V, cut)
+    return _weighted_result(_with_window_times(out, duration, n_rows), ps, pc, vr)
+
+
+def merge_search_windows_weighted_torch(results, video_offset=None, k=5, video_weight=0.0, max_videos=None, n_videos=None, gt_video=None,
+                                        duration=None, n_rows=None, tables=None):
+    """``merge_search_windows_weighted`` as plain torch + Python on any device; ``tables`` as ``merge_search_weighted_torch`` takes them.
+    Nothing routes here."""
+    what = "merge_search_windows_weighted_torch"
+    alpha = _video_weight(what, video_weight)
+    results, off, Q, V, cut, n_videos = _weighted_check(what, results, video_offset, k, _WEIGHTED_SPAN_FIELDS, max_videos, n_videos)
+    if (duration is None) != (n_rows is None):
+        raise ValueError(f"{what}: times need both duration and n_rows, the global (V,) seconds and row counts of the videos")
+    ps, pc, vr = _video_tables(results, Q, V, n_videos, alpha, gt_video, rank_videos_torch)
+    rank_table, weight_table = (vr["pair_rank"], vr["weight"]) if tables is None else tables
+    out = _merge_weighted_torch(results, off, Q, k, _WEIGHTED_SPAN_FIELDS, rank_table.reshape(Q, V), weight_table.reshape(Q, V), V, cut)
+    return _weighted_result(_with_window_times(out, duration, n_rows), ps, pc, vr)

@@ -17,6 +17,21 @@ from .moments import (MAX_K, _pair_pool_into, _temperature, _top_moments_into, _
 from .sampling import MAX_ROWS, MODES, sample_windows, window_plan
 
 
+def _carry_raw(video, listed, lists, score, count, V):
+    """``raw (Q, k)`` of a ranked list over every (query, video) of a bank of V videos: the unweighted score of each listed entry, taken
+    from its pair's own list (pair q * V + video) at the slot whose integer fields match -- ``listed``: the entry's fields ``(Q, k, n)``,
+    ``lists``: the pairs' ``(P, k_video, n)``, ``score (P, k_video)`` / ``count (P,)`` the pairs' lists before any weight.  A gather: the
+    bits leave as they came; 0 for an empty slot.  A few torch ops, no host read."""
+    Q, kv = video.shape[0], score.shape[1]
+    pair = torch.arange(Q, device=video.device).unsqueeze(1) * V + video.clamp_min(0)                   # (Q, k)
+    match = torch.arange(kv, device=video.device) < count.to(torch.int64).clamp(0, kv)[pair].unsqueeze(-1)
+    for mine, theirs in zip(listed, lists):
+        match = match & (theirs[pair] == mine.unsqueeze(2)).all(dim=-1)                                   # (Q, k, k_video)
+    slot = match.to(torch.int8).argmax(dim=-1, keepdim=True)
+    raw = score.detach().float()[pair].gather(-1, slot).squeeze(-1)
+    return torch.where((video >= 0) & match.any(dim=-1), raw, torch.zeros_like(raw))
+
+
 class VideoBank:
     """V videos encoded once (SMIN.encode_videos): ``fv (V, T, D)``, the video encoder's projection with position embedding and mask --
     everything of a video the model computes before the video meets a query (f = fv * fs, reference models.py:81) --, the videos'
@@ -464,7 +479,7 @@ class _Retrieval:
         return r
 
     def search(self, videos, queries, pairs=None, k=5, k_video=None, nms_thresh=0.5, duration=None, max_batch=64, video_weight=None,
-               max_videos=None, tau=0.1, n_videos=None, gt_video=None):
+               max_videos=None, tau=0.1, n_videos=None, gt_video=None, carry=False):
         """Which video, and where: the k best moments of each of the Q queries of a QueryBank over the videos of a VideoBank.
 
         ``pairs``: None -- every query against every video --, or a host (P, 2) array of (query, video) rows, in any order (sorted
@@ -486,7 +501,18 @@ class _Retrieval:
         ``max_videos`` = M, empties the lists of the videos behind the query's best M, before the same smin_corpus_topk.  ``score`` is
         then the weighted score, and the result gains ``video_rank (Q, n_videos)`` int64 (-1), ``video_score`` (0), ``video_count
         (Q,)`` and ``gt_rank (Q,)`` int32: the rank of ``gt_video[q]`` (Q host ints) among the query's videos, -1 if it is not listed
-        or no gt_video is given.  ``n_videos`` defaults to min(k, 64)."""
+        or no gt_video is given.  ``n_videos`` defaults to min(k, 64).
+
+        ``carry=True`` (with the video-level options; alone it implies ``video_weight=0.0``) makes the result one that
+        moments.merge_search_weighted can merge with other shards' (INTEGRATION.md 3u): ``pairs`` must be None (ValueError otherwise),
+        and the result gains ``raw (Q, k)``, each listed entry's unweighted score -- the bits of its pair's own top_moments list, found
+        by matching (video, idx) against that list with a few torch ops; 0 for empty slots --, and ``pair_score`` / ``pair_cells (Q, V)``,
+        the pooled score and valid-cell count of every (query, video) of the bank, the arrays smin_video_rank was fed.  ``score`` stays
+        the score weighted within this bank and the list stays cut by this bank's ranks.  No host read."""
+        if carry and pairs is not None:
+            raise ValueError("search: carry=True takes pairs=None, every query against every video of the bank (a merge re-ranks all the shard's videos)")
+        if carry and video_weight is None and max_videos is None:
+            video_weight = 0.0
         k, k_video, vi, qi, pair_ptr = self._search_plan("search", videos, queries, pairs, k, k_video, max_batch, duration)
         dev, L, P = videos.device, self.L, vi.shape[0]
         if video_weight is not None or max_videos is not None:
@@ -498,8 +524,12 @@ class _Retrieval:
                 pools = _pool_buffers(P, dev)
                 idx, score, count = self._pair_moments(videos, queries, vi, qi, vi_d, qi_d, k_video, nms_thresh, max_batch, pools=(tau,) + pools)
                 vr = rank_videos(pools[0], pools[2], vi_d, pp_d, n=n_videos, alpha=alpha, gt_video=gt_d if gt.size else None)
-                score, count = reweight_moments(score, count, vr["pair_rank"], vr["weight"], cut)
-                r = corpus_topk(score, idx, count, vi_d, pp_d, k=k)
+                w_score, w_count = reweight_moments(score, count, vr["pair_rank"], vr["weight"], cut)
+                r = corpus_topk(w_score, idx, w_count, vi_d, pp_d, k=k)
+                if carry:
+                    Q, V = len(queries), len(videos)
+                    r["raw"] = _carry_raw(r["video"], (r["idx"],), (idx,), score, count, V)
+                    r["pair_score"], r["pair_cells"] = pools[0].reshape(Q, V), pools[2].reshape(Q, V)
             r.update(video_rank=vr["video"], video_score=vr["score"], video_count=vr["count"], gt_rank=vr["gt_rank"])
             return self._search_result(r, duration, L)
         # the whole plan in one pinned buffer, one asynchronous copy (the call never waits for the device)
@@ -666,7 +696,7 @@ class _Retrieval:
         return r
 
     def search_windows(self, windows, queries, pairs=None, k=5, k_video=None, k_window=None, nms_thresh=0.5, duration=None, max_batch=64,
-                       video_weight=None, max_videos=None, tau=0.1, n_videos=None, gt_video=None):
+                       video_weight=None, max_videos=None, tau=0.1, n_videos=None, gt_video=None, carry=False):
         """Which video, and where, over videos of any length: the k best moments of each of the Q queries of a QueryBank over the videos
         of a WindowBank, at the windows' native resolution.
 
@@ -686,7 +716,16 @@ class _Retrieval:
         ``video_weight`` / ``max_videos`` / ``tau`` / ``n_videos`` / ``gt_video``: as ``search`` takes them (both of the first two None:
         the search above, untouched).  Each chunk's (query, window) scores are also pooled (pair_pool), one group_pool composes a (query,
         video) group's windows into the group's score, and smin_video_rank and smin_moment_reweight act on the groups' merged lists in
-        front of the same smin_corpus_span_topk; the result gains ``video_rank``, ``video_score``, ``video_count`` and ``gt_rank``."""
+        front of the same smin_corpus_span_topk; the result gains ``video_rank``, ``video_score``, ``video_count`` and ``gt_rank``.
+
+        ``carry=True``: as ``search`` takes it (``pairs`` must be None), for moments.merge_search_windows_weighted:
+        ``raw (Q, k)`` holds the bits of the entry's score in its group's merge_window_moments list, matched by (video, window, cell), and
+        ``pair_score`` / ``pair_cells (Q, V)`` are the group_pool outputs."""
+        if carry and pairs is not None:
+            raise ValueError("search_windows: carry=True takes pairs=None, every query against every video of the bank (a merge re-ranks all the "
+                             "shard's videos)")
+        if carry and video_weight is None and max_videos is None:
+            video_weight = 0.0
         k, k_video, k_window, p = self._window_search_plan("search_windows", windows, queries, pairs, k, k_video, k_window, max_batch, duration)
         video_level = video_weight is not None or max_videos is not None
         if video_level:
@@ -708,6 +747,10 @@ class _Retrieval:
                 vr = rank_videos(gs, gc, vid32, qp32, n=n_videos, alpha=alpha, gt_video=gt_d if gt.size else None)
                 g_score, g_count = reweight_moments(g["score"], g["count"], vr["pair_rank"], vr["weight"], cut_v)
                 r = corpus_span_topk(g["span"], g_score, g["window"], g["cell"], g_count, vid32, qp32, k=k)
+                if carry:
+                    r["raw"] = _carry_raw(r["video"], (r["window"].unsqueeze(-1), r["cell"]), (g["window"].unsqueeze(-1), g["cell"]), g["score"],
+                                          g["count"], V)
+                    r["pair_score"], r["pair_cells"] = gs.reshape(Q, V), gc.reshape(Q, V)
                 r.update(video_rank=vr["video"], video_score=vr["score"], video_count=vr["count"], gt_rank=vr["gt_rank"])
                 return r if duration is None else self._window_times(r, duration, nr_d)
         host = np.concatenate([p["wi"], p["wq"], p["group_ptr"], p["vi"], p["query_ptr"], windows.n_rows]).astype(np.int64)

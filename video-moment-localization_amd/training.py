@@ -523,6 +523,21 @@ def _video_level(video_weight, max_videos, video_meter):
     return on, 0.0 if on and video_weight is None and max_videos is None else video_weight
 
 
+def _corpus_result(model, carry, meter, gv, gt, duration, dev):
+    """The end of a corpus test loop over a merged list ``carry``: gt_video (int64, first: 8-byte aligned), then the durations and gt_times
+    (fp32), as bytes of one pinned buffer -- one asynchronous copy --, the list's ``times``, one ``meter.update`` and the one
+    ``meter.result()``."""
+    import numpy as np
+    from .moments import search_times
+    Q, V_all = gv.shape[0], duration.shape[0]
+    host = np.concatenate([gv.astype(np.int64).view(np.uint8), np.concatenate([duration, gt.reshape(-1)]).astype(np.float32).view(np.uint8)])
+    buf = torch.from_numpy(host).pin_memory().to(dev, non_blocking=True)
+    gv_d, f32 = buf[:8 * Q].view(torch.int64), buf[8 * Q:].view(torch.float32)
+    carry["times"] = search_times(carry["video"], carry["idx"], f32[:V_all], model.L)
+    meter.update(carry, gv_d, f32[V_all:].reshape(Q, 2))
+    return meter.result()
+
+
 def test_model_corpus(model, video_shards, queries, gt_video, gt_times, meter=None, *, k=25, k_video=5, nms_thresh=0.5, max_batch=64,
                       video_weight=None, max_videos=None, tau=0.1, video_meter=None):
     """The test loop of corpus search: VCMR R@n, IoU=m, VR R@n and mIoU of ``model.search`` over a corpus in shards, with no host
@@ -540,16 +555,15 @@ def test_model_corpus(model, video_shards, queries, gt_video, gt_times, meter=No
     ``video_weight`` / ``max_videos`` / ``tau``: ``model.search``'s video-level options; ``video_meter``: a
     meter.VideoRankMeter, updated with the search's ``gt_rank`` (its ``result()`` is the caller's to read; given alone, the search runs
     at ``video_weight=0.0``, which leaves the moments' list as it is and adds the video ranking).  With any of them the corpus
-    must come as ONE shard -- the weight needs the corpus-wide best score and rank, which a merge of shard lists does not have;
-    ValueError for more.  The shard may carry ``cell_counts`` (encode_videos'), and the loop then reads nothing but ``meter.result()``."""
+    must come as ONE shard -- the weight needs the corpus-wide best score and rank, which a merge of plain shard lists does not have;
+    ValueError for more (``test_model_corpus_weighted_shards`` is the loop whose shard lists carry them).  The shard may carry ``cell_counts`` (encode_videos'), and the loop then reads nothing but ``meter.result()``."""
     import numpy as np
-    from .moments import search_times
     video_level, video_weight = _video_level(video_weight, max_videos, video_meter)
     if video_level:
         video_shards = list(video_shards)
         if len(video_shards) != 1:
             raise ValueError(f"test_model_corpus: video_weight / max_videos / video_meter need the corpus as one shard (got {len(video_shards)}): "
-                             "the video weight and rank are corpus-wide, and the shard merges do not carry them")
+                             "the video weight and rank are corpus-wide, and the plain shard merges do not carry them (test_model_corpus_weighted_shards does)")
     n_max = 5 if meter is None else max(meter.n)
     if k < n_max or k < n_max * k_video:
         raise ValueError(f"test_model_corpus: k = {k} entries per query cannot give an exact R@{n_max} / VR@{n_max} at k_video = {k_video}: "
@@ -581,14 +595,7 @@ def test_model_corpus(model, video_shards, queries, gt_video, gt_times, meter=No
         carry, duration = search_shards(model, video_shards, bank, k=k, k_video=k_video, nms_thresh=nms_thresh, max_batch=max_batch)
         if Q and (gv.min() < 0 or gv.max() >= duration.shape[0]):
             raise ValueError(f"test_model_corpus: gt_video must lie in [0, {duration.shape[0]}), the videos of the shards")
-    # gt_video (int64, first: 8-byte aligned), then the durations and gt_times (fp32), as bytes of one pinned buffer: one asynchronous copy
-    V_all = duration.shape[0]
-    host = np.concatenate([gv.astype(np.int64).view(np.uint8), np.concatenate([duration, gt.reshape(-1)]).astype(np.float32).view(np.uint8)])
-    buf = torch.from_numpy(host).pin_memory().to(dev, non_blocking=True)
-    gv_d, f32 = buf[:8 * Q].view(torch.int64), buf[8 * Q:].view(torch.float32)
-    carry["times"] = search_times(carry["video"], carry["idx"], f32[:V_all], model.L)
-    meter.update(carry, gv_d, f32[V_all:].reshape(Q, 2))
-    return meter.result()
+    return _corpus_result(model, carry, meter, gv, gt, duration, dev)
 
 
 test_model_corpus.__test__ = False
@@ -719,3 +726,157 @@ def test_model_corpus_window_shards(model, shards, queries, gt_video, gt_times, 
 
 
 test_model_corpus_window_shards.__test__ = False
+
+
+# ---------------------------------------------------------------- sharded search with the video-level score
+def _gt_on_device(gt_video, dev):
+    """Q host ints as an int32 tensor on ``dev`` through one pinned asynchronous copy (None stays None): every merge of a fold reads it."""
+    import numpy as np
+    if gt_video is None:
+        return None
+    return torch.from_numpy(host_array(gt_video).astype(np.int32)).pin_memory().to(dev, non_blocking=True)
+
+
+def search_shards_weighted(model, video_shards, queries, *, k=25, k_video=5, nms_thresh=0.5, max_batch=64, video_weight=0.0, max_videos=None,
+                           tau=0.1, n_videos=None, gt_video=None):
+    """``search_shards`` with ``model.search``'s video-level options (INTEGRATION.md 3u): per shard ``encode_videos`` (with the shard's
+    ``cell_counts``, if it has them), ``search(..., carry=True)`` at (k, k_video) with the options, then ``carry =
+    merge_search_weighted([carry, r], [0, videos seen], ...)`` -- the first shard's list is merged alone, so every carry holds the ranks
+    and weights of all the videos seen.  Every list of the fold holds ``moments.carry_slots(k, k_video, max_videos)`` entries per query
+    -- a shard cuts its list by ITS best ``max_videos`` videos, and those the corpus-wide rank drops later must not have pushed out
+    entries that stay -- and the result is cut to ``k`` at the end.  At equal pair scores (and away from fp32 near-ties of a query's
+    candidate values) it is ``search(video_weight, max_videos)`` on one bank of all the videos, provided ``k + (max_videos - 1) *
+    k_video <= 64`` or 64 entries hold every moment of a shard's best ``max_videos`` videos.  One shard's bank is alive at a time; the carry holds
+    ``Q * videos seen * 8`` bytes of pooled scores.  ``gt_video``: each query's video as a global index in shard order (Q host ints),
+    for ``gt_rank``.  Returns ``(carry, duration)`` as ``search_shards``; the carry also holds ``video_rank``, ``video_score``,
+    ``video_count`` and ``gt_rank`` of the last merge.  Host reads: ``encode_videos``' own per shard without ``cell_counts``, else none."""
+    import numpy as np
+    from .moments import MAX_K, carry_slots, merge_search_weighted, truncate_search
+    slots = carry_slots(k, k_video, max_videos)                  # what every list of the fold holds, so that the cut drops none of the final k
+    n_videos = min(k, MAX_K) if n_videos is None else n_videos
+    carry, seen, durations, gt_d = None, 0, [], None
+    for shard in video_shards:
+        bank = model.encode_videos(shard["video_features"], shard["video_mask"], shard["length_mask"], shard["moment_mask"],
+                                   cell_counts=shard.get("cell_counts"))
+        d = host_array(shard["duration"], np.float64)
+        if d.shape[0] != len(bank):
+            raise ValueError(f"search_shards_weighted: duration must cover the shard's {len(bank)} videos (got {d.shape[0]})")
+        r = model.search(bank, queries, k=slots, k_video=k_video, nms_thresh=nms_thresh, max_batch=max_batch, video_weight=video_weight,
+                         max_videos=max_videos, tau=tau, n_videos=n_videos, carry=True)
+        if carry is None:
+            gt_d = _gt_on_device(gt_video, bank.device)
+        carry = merge_search_weighted([r] if carry is None else [carry, r], [0] if carry is None else [0, seen], k=slots, video_weight=video_weight,
+                                      max_videos=max_videos, n_videos=n_videos, gt_video=gt_d)
+        seen += len(bank)
+        durations.append(d)
+    if carry is None:
+        raise ValueError("search_shards_weighted: at least one shard of videos")
+    return truncate_search(carry, k), np.concatenate(durations)
+
+
+def search_window_shards_weighted(model, shards, queries, *, window=None, stride=None, k=25, k_video=5, k_window=None, nms_thresh=0.5, max_batch=64,
+                                  video_weight=0.0, max_videos=None, tau=0.1, n_videos=None, gt_video=None):
+    """``search_window_shards`` with the video-level options: ``search_shards_weighted`` over window banks of shards of whole videos --
+    ``encode_windows``, ``search_windows(..., carry=True)``, ``merge_search_windows_weighted``.  Returns ``(carry, duration, n_rows)``.  No
+    host read."""
+    import numpy as np
+    from .moments import MAX_K, carry_slots, merge_search_windows_weighted, truncate_search
+    slots = carry_slots(k, k_video, max_videos)
+    n_videos = min(k, MAX_K) if n_videos is None else n_videos
+    carry, seen, durations, rows, gt_d = None, 0, [], [], None
+    for shard in shards:
+        n, d = host_array(shard["lengths"]), host_array(shard["duration"], np.float64)
+        if d.shape[0] != n.shape[0]:
+            raise ValueError(f"search_window_shards_weighted: duration must cover the shard's {n.shape[0]} videos (got {d.shape[0]})")
+        bank = model.encode_windows(shard["raw"], n, window=window, stride=stride, max_batch=max_batch)
+        r = model.search_windows(bank, queries, k=slots, k_video=k_video, k_window=k_window, nms_thresh=nms_thresh, max_batch=max_batch,
+                                 video_weight=video_weight, max_videos=max_videos, tau=tau, n_videos=n_videos, carry=True)
+        if carry is None:
+            gt_d = _gt_on_device(gt_video, bank.device)
+        carry = merge_search_windows_weighted([r] if carry is None else [carry, r], [0] if carry is None else [0, seen], k=slots,
+                                              video_weight=video_weight, max_videos=max_videos, n_videos=n_videos, gt_video=gt_d)
+        seen += n.shape[0]
+        durations.append(d)
+        rows.append(n)
+    if carry is None:
+        raise ValueError("search_window_shards_weighted: at least one shard of videos")
+    return truncate_search(carry, k), np.concatenate(durations), np.concatenate(rows)
+
+
+def _corpus_loop_check(what, meter, k, k_video, queries, gt_video, gt_times):
+    import numpy as np
+    n_max = 5 if meter is None else max(meter.n)
+    if k < n_max or k < n_max * k_video:
+        raise ValueError(f"{what}: k = {k} entries per query cannot give an exact R@{n_max} / VR@{n_max} at k_video = {k_video}: "
+                         f"needs k >= max(n) * k_video = {n_max * k_video}")
+    gv, gt = host_array(gt_video), host_array(gt_times, np.float64, (-1, 2))
+    Q = queries["query_features"].shape[0]
+    if gv.shape[0] != Q or gt.shape[0] != Q:
+        raise ValueError(f"{what}: gt_video (Q,) and gt_times (Q, 2) must cover the Q = {Q} queries (got {gv.shape}, {gt.shape})")
+    return gv, gt, Q
+
+
+def test_model_corpus_weighted_shards(model, video_shards, queries, gt_video, gt_times, meter=None, *, k=25, k_video=5, nms_thresh=0.5,
+                                      max_batch=64, video_weight=None, max_videos=None, tau=0.1, video_meter=None):
+    """``test_model_corpus`` with the video-level options over a corpus in ANY number of shards: the shards are
+    searched with ``carry=True`` and folded by ``search_shards_weighted``, whose merges re-rank the videos seen so far, so the weight and
+    the cut are the corpus-wide ones.  Arguments and result as ``test_model_corpus``; ``video_weight`` None means 0.0; ``video_meter`` (a
+    meter.VideoRankMeter) is updated with the last merge's ``gt_rank``.  With ``cell_counts`` in every shard the loop reads the host once,
+    at ``meter.result()``.  At equal pair scores it gives ``test_model_corpus(one shard of all the videos, same options)``' metrics."""
+    what = "test_model_corpus_weighted_shards"
+    gv, gt, Q = _corpus_loop_check(what, meter, k, k_video, queries, gt_video, gt_times)
+    model.eval()
+    bank = model.encode_queries(queries["query_features"], queries["query_mask"])
+    dev = queries["query_features"].device
+    if meter is None:
+        from .meter import CorpusMeter
+        meter = CorpusMeter(device=dev)
+    carry, duration = search_shards_weighted(model, video_shards, bank, k=k, k_video=k_video, nms_thresh=nms_thresh, max_batch=max_batch,
+                                             video_weight=0.0 if video_weight is None else video_weight, max_videos=max_videos, tau=tau, gt_video=gv)
+    if Q and (gv.min() < 0 or gv.max() >= duration.shape[0]):
+        raise ValueError(f"{what}: gt_video must lie in [0, {duration.shape[0]}), the videos of the shards")
+    if video_meter is not None:
+        video_meter.update(carry["gt_rank"])
+    return _corpus_result(model, carry, meter, gv, gt, duration, dev)
+
+
+test_model_corpus_weighted_shards.__test__ = False
+
+
+def test_model_corpus_window_shards_weighted(model, shards, queries, gt_video, gt_times, meter=None, *, window=None, stride=None, k=25, k_video=5,
+                                             k_window=None, nms_thresh=0.5, max_batch=64, video_weight=None, max_videos=None, tau=0.1,
+                                             video_meter=None):
+    """``test_model_corpus_window_shards`` with the video-level options: shards of whole videos searched with
+    ``carry=True`` and folded by ``search_window_shards_weighted``.  Arguments and result as ``test_model_corpus_window_shards``;
+    ``video_weight`` None means 0.0; ``video_meter`` is updated with the last merge's ``gt_rank``.  One host read, ``meter.result()``.  At
+    equal pair scores it gives ``test_model_corpus_windows(the concatenated corpus, same options)``' metrics."""
+    import numpy as np
+    from .moments import window_times
+    what = "test_model_corpus_window_shards_weighted"
+    gv, gt, Q = _corpus_loop_check(what, meter, k, k_video, queries, gt_video, gt_times)
+    model.eval()
+    bank = model.encode_queries(queries["query_features"], queries["query_mask"])
+    dev = queries["query_features"].device
+    if meter is None:
+        from .meter import CorpusMeter
+        meter = CorpusMeter(device=dev)
+    carry, duration, n_rows = search_window_shards_weighted(model, shards, bank, window=window, stride=stride, k=k, k_video=k_video,
+                                                            k_window=k_window, nms_thresh=nms_thresh, max_batch=max_batch,
+                                                            video_weight=0.0 if video_weight is None else video_weight,
+                                                            max_videos=max_videos, tau=tau, gt_video=gv)
+    V_all = duration.shape[0]
+    if Q and (gv.min() < 0 or gv.max() >= V_all):
+        raise ValueError(f"{what}: gt_video must lie in [0, {V_all}), the videos of the shards")
+    if video_meter is not None:
+        video_meter.update(carry["gt_rank"])
+    # gt_video and the row counts (int64, first: 8-byte aligned), then the durations and gt_times (fp32): one pinned asynchronous copy
+    host = np.concatenate([np.concatenate([gv, n_rows]).astype(np.int64).view(np.uint8),
+                           np.concatenate([duration, gt.reshape(-1)]).astype(np.float32).view(np.uint8)])
+    buf = torch.from_numpy(host).pin_memory().to(dev, non_blocking=True)
+    i64, f32 = buf[:8 * (Q + V_all)].view(torch.int64), buf[8 * (Q + V_all):].view(torch.float32)
+    carry["times"] = window_times(carry["video"], carry["span"], f32[:V_all], i64[Q:])
+    meter.update(carry, i64[:Q], f32[V_all:].reshape(Q, 2))
+    return meter.result()
+
+
+test_model_corpus_window_shards_weighted.__test__ = False
