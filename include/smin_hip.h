@@ -1072,6 +1072,54 @@ int smin_video_rank(void* stream, const float* pair_score, const float* pair_cel
 int smin_moment_reweight(void* stream, const float* score, const int32_t* count, const int32_t* pair_rank, const float* weight, int P, int k,
                          int max_videos, float* out_score, int32_t* out_count);
 
+/* ---- first-stage video score from the banks alone (csrc/prefilter.hip): the model with zero SMI layers -- the score
+ * heads on ProposalGeneration's output --, which is linear in the video bank.  No atomics, plain stores; no host read; no allocation;
+ * capturable.
+ *
+ * smin_prefilter_scores: the first-stage score of every (query, video) of Q queries and V videos; three launches.
+ * Inputs.  fv [V][T][D] fp32: the video bank; fs [Q][D] fp32: the queries' sentence features; w [3][D], b [3] fp32: the weights and
+ *   biases of the heads in the order (pm, ps, pe); lmask [V][L], mm [V][L][L]: one byte per entry (nonzero = valid), as the banks
+ *   hold them; tau: the pooling temperature.
+ * Stage 1.  a_h[q][v][t] = sum_d fv[v][t][d] * (fs[q][d] * w[h][d]): a small kernel forms the operand fs (.) w_h as [3 Q rounded up to
+ *   4][D] rows (row 3 q + h; the padding rows are zero) and ONE contraction [V T][D] x [.][D]^T runs on the fp32 MFMA engine in the
+ *   mode of smin_set_gemm_mode; its epilogue stores the projections transposed ([3 q + h][V T]) into the workspace.
+ * Stage 2.  One workgroup of 256 per (q, v) stages the pair's 3 T projections in LDS.  With r = T / L:
+ *   pm0[i][j] = sigmoid((S * (1.0f / (float)cs)) / (float)C + b[0]) where mm[v][i][j] != 0, else 0;  S = the sum of a_0[t] over t in
+ *     [i r, i r + c cs), n = (j - i + 1) r, cs = max(1, n / C), c = min(C, n) (an empty range under the diagonal): the mean over C of
+ *     the content matrix's clips, with 1 / cs rounded to fp32 as the reference stores it (csrc/proposal_map.hip does the same).  Lane i of wave 0 owns row i and keeps ONE running sum from frame i r on, frames in ascending order (the
+ *     ranges of a row share their start and their ends do not decrease with j): at most T additions per row.
+ *   ps0[i] = sigmoid(S_i / (float)r + b[1]) where lmask[v][i] != 0, else 0;  S_i = a_1[i r] + ... + a_1[i r + r - 1], ascending;  pe0
+ *     likewise of a_2 and b[2].  sigmoid(x) = 1 / (1 + expf(-x)).
+ *   score, pool, cells: smin_pair_pool's of (pm0, ps0, pe0, mm[v]) -- csrc/pair_pool.h, the one copy of that device code, so the bits
+ *     are smin_pair_pool's on the stored maps.  A pair without a valid cell: score 0, pool { 0, 0 }, cells 0.
+ * Outputs, every element written, pair p = q V + v:  score [Q][V], pool [Q][V][2], cells [Q][V] fp32;  pm0 [Q V][L][L], ps0 [Q V][L],
+ *   pe0 [Q V][L] fp32: given together or all NULL (the scores do not depend on it).
+ * Every (q, v) is computed alone: a call on a slice of the videos gives the slice's bits.
+ * Workspace.  ws_bytes >= smin_prefilter_ws_bytes(Q, V, T, D) (0 for sizes out of range): the operand and the projections.
+ * Limits.  1 <= Q <= 65535, V >= 1, 1 <= L <= 64, L <= T <= 2048, 1 <= C <= 65536, D >= 4 with D % 4 == 0, V T <= 0x7fff0000 and
+ *   V T (3 Q + 3) <= 2^34 (call it on slices of the videos beyond that).  LDS per
+ *   workgroup: 4 (3 T + L L + 4 L + 4) bytes.  The outputs and the workspace must not overlap the inputs or each other.
+ * Determinism.  The same bits every run.
+ * Rejection.  A nonzero status before any launch, the outputs untouched, for a size out of range, D % 4 != 0, T < L, a bad tau, a NULL
+ *   pointer (the three maps: only some of them NULL) or a short workspace. */
+size_t smin_prefilter_ws_bytes(int Q, int V, int T, int D);
+int smin_prefilter_scores(void* stream, const float* fv, const float* fs, const float* w, const float* b, const uint8_t* lmask,
+                          const uint8_t* mm, int Q, int V, int T, int L, int C, int D, float tau, float* score, float* pool, float* cells,
+                          float* pm0, float* ps0, float* pe0, void* ws, size_t ws_bytes);
+
+/* smin_prefilter_select: each query's best Ms = min(M, V) videos as the pair lists of a search; one launch, one workgroup of 256 per
+ * query, no workspace.
+ * Inputs.  pair_rank [Q][V] int32: smin_video_rank's pair_rank over the (Q, V) scores with pair_ptr[q] = q V (a candidate's rank among
+ *   its query's candidates, -1 for a non-candidate).
+ * Outputs, every element written.  sel_video [Q][Ms] int32: the videos with 0 <= rank < Ms; a query with fewer than Ms candidates gets
+ *   its lowest-indexed non-candidates as well (they yield empty moment lists); ASCENDING BY VIDEO, the order smin_corpus_topk expects
+ *   of a query's pairs.  sel_query [Q][Ms] int32 = q.  The videos are scanned in tiles of 256 with running counts (ballot and
+ *   popcount, integers only): one writer per slot.  Ranks that are not smin_video_rank's (no permutation of 0 .. candidates - 1) stay
+ *   in bounds; slots that find no video then hold -1.
+ * Limits.  Q >= 1, 1 <= V <= 0x7fff0000, M >= 1.  Determinism.  The same bits every run.
+ * Rejection.  A nonzero status before the launch, the outputs untouched, for a size out of range or a NULL pointer. */
+int smin_prefilter_select(void* stream, const int32_t* pair_rank, int Q, int V, int M, int32_t* sel_video, int32_t* sel_query);
+
 /* ---- stand-alone fp32 MFMA GEMM  C[M][N] = A[M][K] * B[N][K]^T  (used by tests and bench.py's
  * roofline probe; same engine as every contraction above). */
 int smin_gemm_nt(void* stream, const float* A, const float* Bm, float* Cm, int M, int N, int K);

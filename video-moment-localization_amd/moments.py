@@ -18,6 +18,7 @@ Semantics (csrc/moments.hip, include/smin_hip.h), for each sample b:
 ``top_moments_torch`` is the same function as plain torch + Python on any device, kept under its own name as the restatement
 the tests compare against -- nothing routes to it silently."""
 import ctypes
+import functools
 
 import numpy as np
 import torch
@@ -858,6 +859,133 @@ def reweight_moments_torch(score, count, pair_rank, weight, max_videos=None):
     _, cut = _reweight_check("reweight_moments_torch", score, count, pair_rank, weight, max_videos)
     keep = torch.ones_like(pair_rank, dtype=torch.bool) if cut <= 0 else (pair_rank >= 0) & (pair_rank < cut)
     return score * weight.to(score.dtype).unsqueeze(1), torch.where(keep, count, torch.zeros_like(count))
+
+
+# ---------------------------------------------------------------- first-stage video score from the banks alone
+PREFILTER_MAX_L, PREFILTER_MAX_T, PREFILTER_MAX_Q = 64, 2048, 65535        # csrc/prefilter.hip
+PREFILTER_WS_CAP = 256 << 20        # bytes of workspace per call of smin_prefilter_scores: the videos are tiled to stay under it
+
+
+def _prefilter_check(what, fv, fs, w, b, length_mask, moment_mask, T, L, C, tau):
+    if fv.dim() != 3 or fs.dim() != 2 or fv.shape[2] != fs.shape[1] or fv.shape[0] < 1 or fs.shape[0] < 1:
+        raise ValueError(f"{what}: fv must be (V, T, D) and fs (Q, D) with V, Q >= 1; got {tuple(fv.shape)} and {tuple(fs.shape)}")
+    V, D, Q = fv.shape[0], fv.shape[2], fs.shape[0]
+    require_ints(what, ("L", L, 1, PREFILTER_MAX_L), ("T", T, L, PREFILTER_MAX_T), ("C", C, 1, 65536))
+    if fv.shape[1] != T or D % 4 != 0 or Q > PREFILTER_MAX_Q:
+        raise ValueError(f"{what}: fv must hold T = {T} frames of D % 4 == 0 features for at most {PREFILTER_MAX_Q} queries; got "
+                         f"{tuple(fv.shape)} and Q = {Q}")
+    if tuple(w.shape) != (3, D) or tuple(b.shape) != (3,):
+        raise ValueError(f"{what}: w must be (3, D) = (3, {D}) and b (3,), the heads in the order (pm, ps, pe); got {tuple(w.shape)} and "
+                         f"{tuple(b.shape)}")
+    if tuple(length_mask.shape) != (V, L) or tuple(moment_mask.shape) != (V, L, L):
+        raise ValueError(f"{what}: length_mask must be (V, L) = {(V, L)} and moment_mask (V, L, L); got {tuple(length_mask.shape)} and "
+                         f"{tuple(moment_mask.shape)}")
+    return Q, V, D, _temperature(what, tau)
+
+
+def prefilter_scores(fv, fs, w, b, length_mask, moment_mask, T, L, C, tau=0.1, maps=False):
+    """The first-stage score of every (query, video) of a video bank's ``fv (V, T, D)`` and a query bank's ``fs (Q, D)``
+    (include/smin_hip.h, smin_prefilter_scores): the model with zero SMI layers -- the heads ``w (3, D)`` / ``b (3,)``, in the order
+    (pm, ps, pe), on ProposalGeneration's output --, pooled as ``pair_pool`` pools the full model's maps, at temperature ``tau``.  One
+    contraction over D on the fp32 MFMA engine (in the mode of set_gemm_mode) and one workgroup per pair.
+
+    Returns ``(score (Q, V), pool (Q, V, 2), cells (Q, V))`` fp32; with ``maps=True`` also ``pm0 (Q, V, L, L)``, ``ps0`` and ``pe0 (Q, V,
+    L)``.  The videos are processed in tiles whose workspace stays under PREFILTER_WS_CAP; a tile changes no bits, every (q, v) is
+    computed alone.  HIP tensors only; no host synchronisation."""
+    _require_hip(fv, "prefilter_scores")
+    Q, V, D, tau = _prefilter_check("prefilter_scores", fv, fs, w, b, length_mask, moment_mask, T, L, C, tau)
+    dev = fv.device
+    fv_, fs_, w_, b_ = (x.detach().float().contiguous() for x in (fv, fs, w, b))
+    lm_, mm_ = byte_mask(length_mask), byte_mask(moment_mask)
+    lib = load()
+    per_video = max(int(lib.smin_prefilter_ws_bytes(Q, 2, T, D)) - int(lib.smin_prefilter_ws_bytes(Q, 1, T, D)), 1)
+    step = max(1, min(V, 0x7fff0000 // T, PREFILTER_WS_CAP // per_video - 1))
+    new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+    outs = [new(Q, V), new(Q, V, 2), new(Q, V)] + ([new(Q, V, L, L), new(Q, V, L), new(Q, V, L)] if maps else [])
+    with torch.cuda.device(dev):
+        for v0 in range(0, V, step):
+            v1 = min(v0 + step, V)
+            tile = outs if (v0, v1) == (0, V) else [new(Q, v1 - v0, *o.shape[2:]) for o in outs]
+            nbytes = int(lib.smin_prefilter_ws_bytes(Q, v1 - v0, T, D))
+            ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+            call("smin_prefilter_scores", stream(), ptr(fv_[v0:v1]), ptr(fs_), ptr(w_), ptr(b_), ptr(lm_[v0:v1]), ptr(mm_[v0:v1]), Q, v1 - v0,
+                 T, L, C, D, tau, *[ptr(o) for o in tile], *([] if maps else [None] * 3), ptr(ws), nbytes)
+            if tile is not outs:
+                for o, part in zip(outs, tile):
+                    o[:, v0:v1] = part
+    return tuple(outs)
+
+
+@functools.lru_cache(maxsize=8)
+def _prefilter_window_weights(T, L, C):
+    r = T // L
+    weight = np.zeros((L, L, T))
+    for i in range(L):
+        for j in range(i, L):
+            n = (j - i + 1) * r
+            cs, c = max(1, n // C), min(C, n)
+            weight[i, j, i * r:i * r + c * cs] = float(np.float32(1.0) / np.float32(cs))
+    return weight
+
+
+def _prefilter_windows(T, L, C, dtype, device):
+    """``weight (L, L, T)`` of the content matrix's clips summed over C: cell (i, j) weighs the frames [i r, i r + c cs) by 1 / cs rounded
+    to fp32, as the reference stores it, with r = T // L, n = (j - i + 1) r, cs = max(1, n // C), c = min(C, n) (oracle content_windows'
+    arithmetic; an empty range under the diagonal).  Host arithmetic on T, L and C alone (kept per (T, L, C)), one copy to the device."""
+    return torch.from_numpy(_prefilter_window_weights(int(T), int(L), int(C))).to(device=device, dtype=dtype)
+
+
+def prefilter_scores_torch(fv, fs, w, b, length_mask, moment_mask, T, L, C, tau=0.1, maps=False):
+    """``prefilter_scores`` as plain torch ops on any device, in the dtype of ``fv`` (fp64 inputs give the fp64 reference): the tests'
+    restatement, nothing routes here.  Forms the (Q, V, L, L) maps at once."""
+    Q, V, D, tau = _prefilter_check("prefilter_scores_torch", fv, fs, w, b, length_mask, moment_mask, T, L, C, tau)
+    dt, r = fv.dtype, T // L
+    fs, w, b = fs.to(dt), w.to(dt), b.to(dt)
+    a = torch.einsum("vtd,hqd->hqvt", fv, fs.unsqueeze(0) * w.unsqueeze(1))                       # (3, Q, V, T)
+    weight = _prefilter_windows(T, L, C, dt, fv.device)
+    valid = (moment_mask != 0).unsqueeze(0)
+    pm0 = torch.sigmoid(torch.einsum("qvt,ijt->qvij", a[0], weight) / C + b[0]) * valid.to(dt)
+    clip = lambda x: x[..., :L * r].reshape(Q, V, L, r).sum(dim=-1) / r
+    keep = (length_mask != 0).to(dt).unsqueeze(0)
+    ps0, pe0 = torch.sigmoid(clip(a[1]) + b[1]) * keep, torch.sigmoid(clip(a[2]) + b[2]) * keep
+    score, pool, cells = pair_pool_torch(pm0.reshape(Q * V, L, L), ps0.reshape(Q * V, L), pe0.reshape(Q * V, L),
+                                         valid.expand(Q, V, L, L).reshape(Q * V, L, L), tau)
+    out = (score.reshape(Q, V), pool.reshape(Q, V, 2), cells.reshape(Q, V))
+    return out + (pm0, ps0, pe0) if maps else out
+
+
+def _select_check(what, pair_rank, M):
+    if pair_rank.dim() != 2 or pair_rank.shape[0] < 1 or pair_rank.shape[1] < 1:
+        raise ValueError(f"{what}: pair_rank must be (Q, V) with Q, V >= 1, got {tuple(pair_rank.shape)}")
+    require_ints(what, ("M", M, 1, 2 ** 31 - 1))
+    return pair_rank.shape[0], pair_rank.shape[1], min(int(M), pair_rank.shape[1])
+
+
+def prefilter_select(pair_rank, M):
+    """Each query's best ``Ms = min(M, V)`` videos as the pair lists of a search (include/smin_hip.h, smin_prefilter_select).
+    ``pair_rank (Q, V)``: rank_videos' ``pair_rank`` over the (Q, V) first-stage scores with ``pair_ptr[q] = q * V``.  Each query keeps
+    the videos with ``0 <= rank < Ms``; with fewer candidates its lowest-indexed non-candidates fill the list.  Returns ``(video (Q,
+    Ms), query (Q, Ms))`` int32, ``video[q]`` ascending, ``query[q] = q``.  HIP tensors only; one launch; no host synchronisation."""
+    _require_hip(pair_rank, "prefilter_select")
+    Q, V, Ms = _select_check("prefilter_select", pair_rank, M)
+    rank = pair_rank.to(torch.int32).contiguous()
+    video = torch.empty((Q, Ms), dtype=torch.int32, device=rank.device)
+    query = torch.empty((Q, Ms), dtype=torch.int32, device=rank.device)
+    with torch.cuda.device(rank.device):
+        call("smin_prefilter_select", stream(), ptr(rank), Q, V, int(M), ptr(video), ptr(query))
+    return video, query
+
+
+def prefilter_select_torch(pair_rank, M):
+    """``prefilter_select`` as plain torch ops on any device (for ranks that are rank_videos'): the tests' restatement."""
+    Q, V, Ms = _select_check("prefilter_select_torch", pair_rank, M)
+    kept = (pair_rank >= 0) & (pair_rank < Ms)
+    non = pair_rank < 0
+    need = Ms - kept.sum(dim=1, keepdim=True)
+    keep = kept | (non & (non.cumsum(dim=1) <= need))
+    video = torch.sort((~keep).to(torch.int8), dim=1, stable=True).indices[:, :Ms].to(torch.int32)
+    query = torch.arange(Q, dtype=torch.int32, device=pair_rank.device).unsqueeze(1).expand(Q, Ms).contiguous()
+    return video, query
 
 
 def search_times(video, idx, duration, L):

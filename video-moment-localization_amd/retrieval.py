@@ -1,6 +1,7 @@
 """Retrieval on top of SMIN's scores, which the reference does not have: the best moments of a sample (``localize``), of videos of
 any length over overlapping windows (``localize_windows``) and of a corpus encoded once (``encode_videos`` / ``encode_queries`` ->
-``score_pairs`` / ``search``; a corpus of videos of any length: ``encode_windows`` -> ``search_windows``), and the training counterpart
+``score_pairs`` / ``search``, pruned by a first-stage score from the banks alone with ``prefilter_videos`` / ``search(prefilter=M)``; a corpus
+of videos of any length: ``encode_windows`` -> ``search_windows``), and the training counterpart
 of ``score_pairs``, ``forward_pairs`` over (video, query) pairs that share their
 encoders: host code around the library's kernels and the model's own ``score`` / ``forward``, which ``modules.SMIN`` inherits
 through the stateless mixin ``_Retrieval``."""
@@ -12,7 +13,8 @@ from ._host import _AttnMaps, byte_mask, host_array, known_cells, query_mask_row
 from .feeder import build_masks_hip, cell_count
 from .functional import attn_maps_gather
 from .moments import (MAX_K, _pair_pool_into, _temperature, _top_moments_into, _video_weight, corpus_span_topk, corpus_span_topk_torch, corpus_topk,
-                      corpus_topk_torch, group_pool, merge_window_moments, merge_window_moments_torch, mine_pairs, rank_videos, reweight_moments,
+                      corpus_topk_torch, group_pool, merge_window_moments, merge_window_moments_torch, mine_pairs, prefilter_scores, prefilter_select,
+                      rank_videos, reweight_moments,
                       reweight_moments_torch, search_times, top_moments, top_moments_torch, window_times)
 from .sampling import MAX_ROWS, MODES, sample_windows, window_plan
 
@@ -347,9 +349,11 @@ class _Retrieval:
             raise ValueError(f"{what}: video_index must lie in [0, {V}) and query_index in [0, {Q})")
         return vi, qi
 
-    def _score_pairs(self, videos, queries, vi, qi, vi_d, qi_d):
-        """score_pairs of checked host lists vi / qi (P >= 1) whose int32 device copies are vi_d / qi_d.  No host read."""
-        cells = sum(videos.cell_counts[v] for v in vi)                            # host arithmetic: the scorer asks the device nothing
+    def _score_pairs(self, videos, queries, vi, qi, vi_d, qi_d, cells=None):
+        """score_pairs of checked host lists vi / qi (P >= 1) whose int32 device copies are vi_d / qi_d.  No host read.  ``vi`` None: the
+        lists exist on the device only, and ``cells`` is the pairs' valid-cell count where the caller knows it (None: the node reads it)."""
+        if vi is not None:
+            cells = sum(videos.cell_counts[v] for v in vi)                        # host arithmetic: the scorer asks the device nothing
         with known_cells(self, cells), torch.no_grad(), torch.cuda.device(vi_d.device):
             if not self._bank_plan(videos.plan_features, queries.query_features):
                 # as score(): configurations off the one-node path (and keep_attention) run the forward, here on expanded pairs
@@ -479,7 +483,7 @@ class _Retrieval:
         return r
 
     def search(self, videos, queries, pairs=None, k=5, k_video=None, nms_thresh=0.5, duration=None, max_batch=64, video_weight=None,
-               max_videos=None, tau=0.1, n_videos=None, gt_video=None, carry=False):
+               max_videos=None, tau=0.1, n_videos=None, gt_video=None, prefilter=None, carry=False):
         """Which video, and where: the k best moments of each of the Q queries of a QueryBank over the videos of a VideoBank.
 
         ``pairs``: None -- every query against every video --, or a host (P, 2) array of (query, video) rows, in any order (sorted
@@ -508,7 +512,25 @@ class _Retrieval:
         and the result gains ``raw (Q, k)``, each listed entry's unweighted score -- the bits of its pair's own top_moments list, found
         by matching (video, idx) against that list with a few torch ops; 0 for empty slots --, and ``pair_score`` / ``pair_cells (Q, V)``,
         the pooled score and valid-cell count of every (query, video) of the bank, the arrays smin_video_rank was fed.  ``score`` stays
-        the score weighted within this bank and the list stays cut by this bank's ranks.  No host read."""
+        the score weighted within this bank and the list stays cut by this bank's ranks.  No host read.
+
+        ``prefilter=M`` (None: everything above, untouched) prunes the videos before the model runs:
+        ``prefilter_videos`` scores every (query, video) from the banks alone and keeps each query's best ``Ms = min(M, V)`` videos, and
+        the chunk loop and smin_corpus_topk above then run over those Q * Ms pairs, whose lists were built on the device
+        (``pair_ptr[q] = q * Ms``): the full model scores Q * Ms pairs instead of Q * V.  No host list exists to sum the bank's
+        cell_counts over, so the rule ``forward_pairs`` documents for a mined plan applies: when all the bank's ``cell_counts`` are one
+        value c, each chunk's valid-cell count is ``pairs * c`` and the call reads nothing back; otherwise no count is handed over and
+        the node reads it once per chunk.  ``video_weight`` / ``max_videos`` / ``gt_video`` / ``tau`` act as above on the surviving
+        pairs (``tau`` is also the first stage's temperature).  With ``pairs`` or ``carry=True``: ValueError (a carried merge needs
+        every video's pooled score).  The result gains ``prefilter_video (Q, Ms)`` int64 ascending, ``prefilter_score (Q, V)`` and
+        ``prefilter_gt_rank (Q,)`` int32, the first stage's rank of ``gt_video[q]`` (-1 without gt_video or for a non-candidate).  What
+        the pruning loses is not bounded: a video the first stage ranks behind M is never seen by the model."""
+        if prefilter is not None:
+            if pairs is not None or carry:
+                raise ValueError("search: prefilter takes pairs=None and carry=False (it chooses the pairs itself, and a carried merge needs "
+                                 "every video's pooled score)")
+            return self._search_prefiltered(videos, queries, prefilter, k, k_video, nms_thresh, duration, max_batch, video_weight, max_videos, tau,
+                                            n_videos, gt_video)
         if carry and pairs is not None:
             raise ValueError("search: carry=True takes pairs=None, every query against every video of the bank (a merge re-ranks all the shard's videos)")
         if carry and video_weight is None and max_videos is None:
@@ -553,6 +575,106 @@ class _Retrieval:
             if pools is not None:
                 _pair_pool_into(pm, ps, pe, mm, pools[0], pools[1][c0:c1], pools[2][c0:c1], pools[3][c0:c1])
         return idx, score, count
+
+    # ---------------------------------------------------------------- first-stage pruning from the banks alone
+    def prefilter_videos(self, videos, queries, M, tau=0.1, gt_video=None):
+        """Each query's best ``Ms = min(M, V)`` videos by the first-stage score: the model with zero SMI layers -- the score heads on
+        ProposalGeneration's output, pooled as the contrastive loss pools the full model's maps at temperature ``tau`` --, computed from
+        ``videos.fv`` and ``queries.fs`` alone (moments.prefilter_scores: one contraction over D for all Q * V pairs), ranked by the
+        existing smin_video_rank and cut by moments.prefilter_select.  No new weights, no training, and no accuracy claim.
+
+        ``videos``: a VideoBank, or a WindowBank of videos of any length -- the (query, window) pools are then composed by group_pool
+        into per-video scores (a cell in the overlap of two windows counts twice).  ``gt_video``: Q host ints, each
+        query's own video.  Returns a dict: ``video (Q, Ms)`` int64 ascending (a query with fewer than Ms candidates is filled with its
+        lowest-indexed videos without a valid cell), ``score (Q, V)``, ``rank (Q, V)`` int32 the first-stage rank (-1 for a
+        non-candidate), ``gt_rank (Q,)`` int32 as VideoRankMeter.update takes it (-1 without gt_video), and, for a VideoBank,
+        ``video_index`` / ``query_index (Q * Ms,)`` int32, the device pair lists sorted by (query, video).  A bank encoded off the
+        one-node path raises score_pairs' ValueError.  Under torch.no_grad(); the only copy is gt_video's (pinned, asynchronous); no
+        host read."""
+        what = "prefilter_videos"
+        _require_banks(what, videos, queries)
+        require_ints(what, ("M", M, 1, 2 ** 31 - 1))
+        tau = _temperature(what, tau)
+        windowed = isinstance(videos, WindowBank)
+        Q, W, dev = len(queries), len(videos), videos.device
+        V = videos.n_videos if windowed else W
+        gt = None
+        if gt_video is not None:
+            gt = host_array(gt_video)
+            if gt.shape[0] != Q:
+                raise ValueError(f"{what}: gt_video must name a video for each of the Q = {Q} queries (got {gt.shape[0]})")
+        require_hip_tensors(what, dict(videos=videos.video_mask, queries=queries.query_features), must="hold HIP tensors")
+        if videos.fv is None or queries.fs is None:
+            raise ValueError("score_pairs: a bank was encoded while the module was off the one-node path (SMIN._plan); encode it again")
+        if Q * max(V, W) > 0x7fff0000:
+            raise ValueError(f"{what}: {Q} queries over {max(V, W)} videos / windows exceed the int32 pair lists")
+        lo, D = self.localization, videos.fv.shape[2]
+        heads = (lo.conv_layer_pm, lo.conv_layer_ps, lo.conv_layer_pe)
+        with torch.no_grad(), torch.cuda.device(dev):
+            w, b = torch.stack([h.weight.reshape(D) for h in heads]), torch.cat([h.bias.reshape(1) for h in heads])
+            score, pool, cells = prefilter_scores(videos.fv, queries.fs, w, b, videos.length_mask, videos.moment_mask, self.T, self.L, self.C, tau)
+            if windowed:
+                first = torch.arange(Q, device=dev).unsqueeze(1) * W + videos.video_ptr_d[:-1].unsqueeze(0)           # group q * V + v begins here
+                group_ptr = torch.cat([first.reshape(-1), first.new_full((1,), Q * W)])
+                score, cells = (x.reshape(Q, V) for x in group_pool(pool.reshape(Q * W, 2), cells.reshape(Q * W), group_ptr, tau))
+            gt_d = None if gt is None else torch.from_numpy(gt.astype(np.int32)).pin_memory().to(dev, non_blocking=True)
+            video_of = torch.arange(V, dtype=torch.int32, device=dev).repeat(Q)
+            pair_ptr = torch.arange(Q + 1, dtype=torch.int32, device=dev) * V
+            vr = rank_videos(score.reshape(-1), cells.reshape(-1), video_of, pair_ptr, n=1, alpha=0.0, gt_video=gt_d)
+            rank = vr["pair_rank"].reshape(Q, V)
+            video, query = prefilter_select(rank, int(M))
+        r = dict(video=video.to(torch.int64), score=score, rank=rank, gt_rank=vr["gt_rank"])
+        if not windowed:
+            r.update(video_index=video.reshape(-1), query_index=query.reshape(-1))
+        return r
+
+    def _pair_moments_device(self, videos, queries, vi_d, qi_d, cell, k_video, nms_thresh, max_batch, pools=None):
+        """``_pair_moments`` over pair lists that exist on the device only (int32 ``vi_d`` / ``qi_d (P,)``): the same chunks, no host copy
+        of the lists.  ``cell``: every video's valid-cell count where the bank's are all one value -- a chunk's count is then its pairs
+        times it --, else None: no count is handed over and the node reads it once per chunk."""
+        idx, score, count, chunks = _chunk_buffers(vi_d.shape[0], k_video, max_batch, vi_d.device)
+        for c0, c1 in chunks:
+            pm, ps, pe, _ = self._score_pairs(videos, queries, None, None, vi_d[c0:c1], qi_d[c0:c1], cells=None if cell is None else (c1 - c0) * cell)
+            mm = videos.moment_mask.index_select(0, vi_d[c0:c1])
+            _top_moments_into(pm, ps, pe, mm, k_video, nms_thresh, idx[c0:c1], score[c0:c1], count[c0:c1])
+            if pools is not None:
+                _pair_pool_into(pm, ps, pe, mm, pools[0], pools[1][c0:c1], pools[2][c0:c1], pools[3][c0:c1])
+        return idx, score, count
+
+    def _search_prefiltered(self, videos, queries, M, k, k_video, nms_thresh, duration, max_batch, video_weight, max_videos, tau, n_videos, gt_video):
+        """``search(prefilter=M)``: prefilter_videos, then search's chunk loop and ranking over the device-built Q * Ms pair lists."""
+        what = "search"
+        k_video = k if k_video is None else k_video
+        require_ints(what, ("k", k, 1, MAX_K), ("k_video", k_video, 1, MAX_K), ("max_batch", max_batch, 1, 65535))
+        _require_banks(what, videos, queries)
+        if isinstance(videos, WindowBank):
+            raise ValueError("search: prefilter takes a VideoBank (pruning a window search is out of scope: the surviving windows' list has a "
+                             "data-dependent length)")
+        Q, V, dev = len(queries), len(videos), videos.device
+        if duration is not None and tuple(duration.shape) != (V,):
+            raise ValueError(f"{what}: duration must be (V,) = ({V},) seconds (got {tuple(duration.shape)})")
+        video_level = video_weight is not None or max_videos is not None
+        if video_level:
+            alpha, cut, tau, n_videos, gt = self._video_options(what, video_weight, max_videos, tau, n_videos, gt_video, k, Q)
+        pf = self.prefilter_videos(videos, queries, M, tau, gt_video)
+        vi_d, qi_d, Ms = pf["video_index"], pf["query_index"], pf["video"].shape[1]
+        counts = videos.cell_counts
+        cell = counts[0] if all(c == counts[0] for c in counts) else None
+        with torch.no_grad(), torch.cuda.device(dev):
+            pp_d = torch.arange(Q + 1, dtype=torch.int32, device=dev) * Ms
+            if video_level:
+                gt_d = torch.from_numpy(gt.astype(np.int32)).pin_memory().to(dev, non_blocking=True) if gt.size else None
+                pools = _pool_buffers(Q * Ms, dev)
+                idx, score, count = self._pair_moments_device(videos, queries, vi_d, qi_d, cell, int(k_video), nms_thresh, max_batch, pools=(tau,) + pools)
+                vr = rank_videos(pools[0], pools[2], vi_d, pp_d, n=n_videos, alpha=alpha, gt_video=gt_d)
+                w_score, w_count = reweight_moments(score, count, vr["pair_rank"], vr["weight"], cut)
+                r = corpus_topk(w_score, idx, w_count, vi_d, pp_d, k=int(k))
+                r.update(video_rank=vr["video"], video_score=vr["score"], video_count=vr["count"], gt_rank=vr["gt_rank"])
+            else:
+                idx, score, count = self._pair_moments_device(videos, queries, vi_d, qi_d, cell, int(k_video), nms_thresh, max_batch)
+                r = corpus_topk(score, idx, count, vi_d, pp_d, k=int(k))
+        r.update(prefilter_video=pf["video"], prefilter_score=pf["score"], prefilter_gt_rank=pf["gt_rank"])
+        return self._search_result(r, duration, self.L)
 
     # ---------------------------------------------------------------- video ranking by the pooled pair score (INTEGRATION.md 3t)
     @staticmethod
