@@ -1,0 +1,489 @@
+"""Backward passes of the feed kernels against ordered restatements (csrc/sampling.hip smin_sample_clips_bwd and
+smin_embed_tokens_bwd, csrc/embed_sort.h, csrc/row_sparse.hip smin_embed_tokens_bwd_rows and one smin_row_adam_step).
+
+Both backward kernels define their result to the bit: the raw-row gradient is a copy (pick) or one fp32 division (mean), the table
+gradient a fixed-order fp32 sum ("ascending position order inside a run", embed_sort.h).  So each is compared with torch.equal
+against a plain restatement -- table_grad_ordered, raw_grad_scatter -- and the restatements are tied to the definition in fp64 on the
+CPU.  The shapes are the ones at which the kernels change path: the bitonic sort's padding around powers of two and its second and
+fourth key per thread, runs of one and of 4096 equal ids, rows wider than one trip of the 256-thread column loop (E, Din = 1028),
+partial 16-row blocks, empty samples between full ones, device offsets that start past row 0, out-of-range device start offsets,
+and outputs poisoned with NaN before the C entry runs."""
+import functools
+
+import numpy as np
+import pytest
+import torch
+
+from tests.test_input_grads import _sample_clips_ref
+from tests.test_row_sparse_table import backward_dense, backward_rows, batches, same_state
+
+gpu = pytest.mark.gpu
+
+
+def A():
+    import models
+    return models.vml_amd
+
+
+def S():
+    import models  # noqa: F401  (loads the package as vml_amd)
+    from vml_amd import sampling
+    return sampling
+
+
+@pytest.fixture(scope="module")
+def dev():
+    assert torch.cuda.is_available(), "GPU tests need a HIP device"
+    A()._lib.load()
+    return torch.device("cuda:0")
+
+
+# ---------------------------------------------------------------- restatements
+def table_grad_ordered(tok, dqf, V, descending=False):
+    """-> (the dense (V, E) fp32 gradient of embed_tokens, the sorted distinct ids in [0, V)).  Row v = the fp32 sum of dqf at the flat
+    positions holding v, added strictly in ascending position order (descending=True: the same terms in descending order), every
+    addition rounded on its own; ids outside [0, V) contribute nothing, untouched rows are 0.  By rounds: round q adds the q-th
+    occurrence of every id that has one, so the loop runs as often as the longest run is long."""
+    t = tok.reshape(-1).to(torch.int64).cpu()
+    g = dqf.detach().float().cpu().reshape(t.numel(), -1)
+    pos = torch.nonzero((t >= 0) & (t < V)).view(-1)                       # ascending positions of the in-range ids
+    order = torch.argsort(t[pos], stable=True)
+    ids_s, pos_s = t[pos][order], pos[order]                               # by id, inside an id by ascending position
+    distinct, counts = torch.unique_consecutive(ids_s, return_counts=True)
+    first = torch.cumsum(counts, 0) - counts
+    rank = torch.arange(ids_s.numel()) - torch.repeat_interleave(first, counts)
+    if descending:
+        rank = torch.repeat_interleave(counts, counts) - 1 - rank
+    by_round = torch.argsort(rank, stable=True)
+    ids_r, pos_r = ids_s[by_round], pos_s[by_round]
+    out = torch.zeros((V, g.shape[1]), dtype=torch.float32)
+    lo = 0
+    for q, hi in enumerate(torch.cumsum(torch.bincount(rank), 0).tolist()):
+        i, p = ids_r[lo:hi], pos_r[lo:hi]                                  # distinct ids inside a round
+        out[i] = g[p] if q == 0 else out[i] + g[p]
+        lo = hi
+    return out, distinct
+
+
+def table_grad_fp64(tok, dqf, V):
+    """-> (the same gradient by fp64 index_add_, the bound per element on an fp32 sum of those terms in any order:
+    (m - 1) * 2**-24 * sum |terms| with m the run length of the row's id; 0 for m <= 1, where the sum is exact)."""
+    t = tok.reshape(-1).to(torch.int64).cpu()
+    g = dqf.detach().double().cpu().reshape(t.numel(), -1)
+    ok = (t >= 0) & (t < V)
+    ref = torch.zeros((V, g.shape[1]), dtype=torch.float64).index_add_(0, t[ok], g[ok])
+    mag = torch.zeros((V, g.shape[1]), dtype=torch.float64).index_add_(0, t[ok], g[ok].abs())
+    m = torch.bincount(t[ok], minlength=V)
+    return ref, (m - 1).clamp(min=0).double().unsqueeze(1) * 2.0 ** -24 * mag
+
+
+def clamp_spos(spos, lengths, T):
+    """Start offsets clamped into [0, spos_high) per sample, as the kernels clamp a device spos."""
+    hi = S().spos_high(np.asarray(lengths, dtype=np.int64), T)
+    s = np.zeros(len(lengths), np.int64) if spos is None else np.asarray(spos, dtype=np.int64)
+    return np.clip(s, 0, hi - 1)
+
+
+def raw_grad_scatter(dout, offsets, T, spos, mode, rows):
+    """The (rows, Din) fp32 gradient of sample_clips from clip_indices / mean_windows: pick, or n <= T: draw[base + idx[t]] =
+    dout[b, t]; mean with n > T: every row of window t gets dout[b, t] / float32(cnt_t); everything else 0.  offsets: B + 1 host
+    values; a spos outside [0, spos_high) is clamped first."""
+    s = S()
+    dout = dout.detach().float().cpu().numpy()
+    offsets = np.asarray(offsets, dtype=np.int64)
+    lengths = np.diff(offsets)
+    sp = clamp_spos(spos, lengths, T)
+    draw = np.zeros((rows, dout.shape[2]), np.float32)
+    for b, n in enumerate(lengths.tolist()):
+        base = int(offsets[b])
+        if mode == "pick" or n <= T:
+            idx = s.clip_indices(n, T, sp[b] if mode == "pick" else 0)
+            draw[base + idx] = dout[b, :idx.shape[0]]
+        else:
+            a = s.mean_windows(n, T)
+            cnt = a[1:] - a[:-1]
+            draw[base:base + n] = np.repeat(dout[b] / cnt.astype(np.float32)[:, None], cnt, axis=0)
+    return torch.from_numpy(draw)
+
+
+# ---------------------------------------------------------------- cases
+EMBED_CASES = [                      # (B, Nq, V, E, id pattern); n = B * Nq
+    (1, 1, 5, 4, "distinct"),        # n = 1: np = 1, no sort stage
+    (1, 2, 5, 4, "distinct"),        # np = 2
+    (3, 21, 8, 20, "random"),        # 63, 64, 65: padding around a power of two, runs of about 8
+    (1, 64, 8, 20, "random"),
+    (5, 13, 8, 20, "random"),
+    (31, 33, 50, 12, "random"),      # 1023, 1024, 1025: one key per thread of the sort, then two
+    (32, 32, 50, 12, "random"),
+    (25, 41, 50, 12, "random"),
+    (3, 683, 97, 4, "random"),       # 2049: np = 4096, half of it padding
+    (65, 63, 300, 4, "random"),      # 4095
+    (64, 64, 7, 1028, "random"),     # 4096, E / 4 = 257: second trip of the column loop, runs of about 585
+    (128, 32, 1, 4, "zeros"),        # one run of 4096, V = 1
+    (64, 64, 4096, 4, "descending"),  # every stage swaps, all runs of length 1
+    (128, 32, 100000, 4, "random"),  # large ids in the key's high word
+    (25, 41, 11, 20, "mixed"),       # 1025: -1, V and 2**31 - 1 at about 50 %: padding keys between real ones
+    (3, 5, 11, 4, "none"),           # no id in range: an all-zero gradient
+]
+MIXED_CASE = (25, 41, 11, 20, "mixed")
+# With the unshifted seed this case's one run of three ids sums to the same bits in either order, which
+# test_descending_order_changes_the_bits does not accept of a case with a run longer than 2.
+SEED_SHIFT = {(128, 32, 100000, 4, "random"): 2}
+
+
+def case_id(c):
+    return "-".join(str(x) for x in c)
+
+
+@functools.lru_cache(maxsize=None)
+def embed_case(case):
+    """-> (tok (B, Nq) int64, dqf (B, Nq, E), table_grad_ordered's gradient and ids, the fp64 gradient and its bound); computed once
+    per case and shared by the tests, which leave it as it is.  dqf as tests/test_row_sparse_table.py draws it: randn times a power
+    of ten from 1e-3 to 1e2 per position, so that the order of the additions shows in the bits."""
+    B, Nq, V, E, pattern = case
+    n = B * Nq
+    g = torch.Generator().manual_seed(B * 1000 + Nq + V + E + SEED_SHIFT.get(case, 0))
+    if pattern == "distinct":
+        tok = torch.arange(n).view(B, Nq)
+    elif pattern == "zeros":
+        tok = torch.zeros((B, Nq), dtype=torch.int64)
+    elif pattern == "descending":
+        tok = torch.arange(n - 1, -1, -1).view(B, Nq)
+    elif pattern == "none":
+        tok = torch.where(torch.rand(B, Nq, generator=g) < 0.5, torch.tensor(-1), torch.tensor(V + 3)).to(torch.int64)
+    else:
+        tok = torch.randint(0, V, (B, Nq), generator=g)
+        if pattern == "mixed":
+            outside = torch.tensor([-1, V, 2 ** 31 - 1])[torch.randint(0, 3, (B, Nq), generator=g)]
+            tok = torch.where(torch.rand(B, Nq, generator=g) < 0.5, outside, tok)
+    dqf = torch.randn(B, Nq, E, generator=g) * 10.0 ** torch.randint(-3, 3, (B, Nq, 1), generator=g).float()
+    want, ids = table_grad_ordered(tok, dqf, V)
+    ref, bound = table_grad_fp64(tok, dqf, V)
+    return tok, dqf, want, ids, ref, bound
+
+
+def longest_run(tok, V):
+    t = tok.reshape(-1)
+    t = t[(t >= 0) & (t < V)]
+    return int(torch.bincount(t).max()) if t.numel() else 0
+
+
+def clip_lengths(T):
+    """[0, 1, T - 1, T, T + 1, 3T/2 where integral (stride 1.5: the draw range loses one), 2T, 2T + 1, 13T + 7] without negatives and
+    repeats, then two empty samples in a row and a short one."""
+    head = [0, 1, T - 1, T, T + 1] + ([3 * T // 2] if T % 2 == 0 else []) + [2 * T, 2 * T + 1, 13 * T + 7]
+    seen = []
+    for n in head:
+        if n >= 0 and n not in seen:
+            seen.append(n)
+    return tuple(seen + [0, 0, 5])
+
+
+CLIP_SHAPES = [(1, 4), (7, 12), (16, 500), (17, 1028), (64, 4)]     # (T, Din); Din = 1028: 16 * 257 quads per block
+CLIP_SPOS = ["pick-spos0", "pick-top", "mean"]
+LONG = (16, 4, (100003, 3))                                         # deep binary searches, a stride that is no short binary fraction
+DEVICE_OFFSETS = (16, 12, 5, 9)                                     # T, Din, offsets[0], rows of raw past offsets[B]
+
+
+@functools.lru_cache(maxsize=None)
+def clip_case(T, Din, lengths, which, lead=0, tail=0, spos=None):
+    """One sample_clips problem and its expected gradient, computed once: dict(raw, dout, lengths, offsets, spos, mode, rows, want).
+    which: "pick-spos0", "pick-top" (spos = spos_high - 1), "pick-given" (spos as passed: clamped by the restatement) or "mean";
+    raw has `lead` rows before the first sample and `tail` rows behind the last."""
+    n = np.array(lengths, dtype=np.int64)
+    g = torch.Generator().manual_seed(T * 100 + Din + len(lengths) + lead)
+    rows = lead + int(n.sum()) + tail
+    mode = "mean" if which == "mean" else "pick"
+    sp = {"pick-spos0": np.zeros(len(n), np.int64), "pick-top": S().spos_high(n, T) - 1, "mean": None,
+          "pick-given": None if spos is None else np.array(spos, dtype=np.int64)}[which]
+    offsets = lead + np.concatenate([[0], np.cumsum(n)]).astype(np.int64)
+    raw = torch.randn(rows, Din, generator=g)
+    dout = torch.randn(len(n), T, Din, generator=g)
+    return dict(T=T, Din=Din, raw=raw, dout=dout, lengths=n, offsets=offsets, spos=sp, mode=mode, rows=rows,
+                want=raw_grad_scatter(dout, offsets, T, sp, mode, rows))
+
+
+def pick_triples():
+    """Every (n, T, spos) the GPU cases hand to the pick rule, start offsets as the kernels clamp them."""
+    out = set()
+    for T, Din in CLIP_SHAPES + [LONG[:2], DEVICE_OFFSETS[:2]]:
+        lengths = LONG[2] if (T, Din) == LONG[:2] else clip_lengths(T)
+        hi = S().spos_high(np.array(lengths), T)
+        for n, h, c in zip(lengths, hi, clamp_spos(wild_spos(lengths, T), lengths, T)):
+            out |= {(n, T, 0), (n, T, int(h) - 1), (n, T, int(c))}
+    return sorted(out)
+
+
+def wild_spos(lengths, T):
+    """Device start offsets 1000, -3, top of the range, 1000, ...: two of three outside the range the reference draws from."""
+    hi = S().spos_high(np.array(lengths), T)
+    return tuple(int(x) for x in np.where(np.arange(len(lengths)) % 3 == 0, 1000, np.where(np.arange(len(lengths)) % 3 == 1, -3, hi - 1)))
+
+
+# ---------------------------------------------------------------- CPU: the restatements against their definitions
+@pytest.mark.parametrize("case", EMBED_CASES, ids=case_id)
+def test_table_grad_ordered_against_fp64(case):
+    """table_grad_ordered against fp64 index_add_: per element within (m - 1) * 2**-24 * sum |terms|, the bound of a length-m fp32 sum
+    (exact for m <= 1); its ids are torch.unique's; rows of ids that never occur are 0."""
+    B, Nq, V, E, _ = case
+    tok, dqf, want, ids, ref, bound = embed_case(case)
+    err = (want.double() - ref).abs()
+    print(case, "longest run", longest_run(tok, V), "largest error / bound", float((err / bound.clamp(min=1e-300)).max()))
+    assert bool((err <= bound).all())
+    assert torch.equal(ids, torch.unique(tok[(tok >= 0) & (tok < V)]))
+    absent = torch.ones(V, dtype=torch.bool)
+    absent[ids] = False
+    assert bool((want[absent] == 0).all())
+
+
+def test_descending_order_changes_the_bits():
+    """The power of the bitwise comparison: for every embed case with a run longer than 2, the same sums taken in descending
+    position order differ from table_grad_ordered in at least one element (and agree with fp64 within the same bound)."""
+    seen = 0
+    for case in EMBED_CASES:
+        B, Nq, V, E, _ = case
+        tok, dqf, want, _, ref, bound = embed_case(case)
+        if longest_run(tok, V) <= 2:
+            continue
+        seen += 1
+        rev, _ = table_grad_ordered(tok, dqf, V, descending=True)
+        differing = int((rev != want).sum())
+        print(case, "elements that differ in descending order:", differing, "of", want.numel())
+        assert differing > 0, case
+        assert bool(((rev.double() - ref).abs() <= bound).all())
+    assert seen == 12                                                    # all but the distinct, descending and out-of-range cases
+
+
+CPU_CLIP_CASES = [(1, 4, "mean"), (7, 12, "pick-top"), (17, 1028, "mean"), (64, 4, "pick-spos0")]
+
+
+@pytest.mark.parametrize("T,Din,which", CPU_CLIP_CASES, ids=lambda v: str(v))
+def test_raw_grad_scatter_against_fp64_autograd(T, Din, which):
+    """raw_grad_scatter against torch autograd in fp64 through _sample_clips_ref: pick is a copy, so equal after casting the fp64
+    gradient to fp32; mean is one division, so within one fp32 ulp (fp64 rounded to fp32 may round twice)."""
+    p = clip_case(T, Din, clip_lengths(T), which)
+    r64 = p["raw"].double().requires_grad_(True)
+    spos = np.zeros(len(p["lengths"]), np.int64) if p["spos"] is None else p["spos"]
+    _sample_clips_ref(r64, p["lengths"], T, spos, p["mode"]).backward(p["dout"].double())
+    if which != "mean":
+        assert torch.equal(p["want"], r64.grad.float())
+        assert int((p["want"].abs().sum(1) == 0).sum()) > 0              # rows the stride skips
+    else:
+        ref = r64.grad.numpy()
+        ulp = np.spacing(np.abs(ref).astype(np.float32)).astype(np.float64)
+        assert bool((np.abs(p["want"].double().numpy() - ref) <= ulp).all())
+        assert int((p["want"].abs().sum(1) > 0).sum()) == int(p["lengths"].sum())   # every row of a sample is in a window or picked
+
+
+def test_pick_rule_reads_no_row_twice():
+    """Premise of raw_grad_scatter's pick rule (an assignment per output row): for every (n, T, spos) of the GPU cases -- start
+    offsets 0, spos_high - 1 and the clamped out-of-range ones -- clip_indices is strictly increasing and the clip to [0, n - 1]
+    changes nothing.  The same holds for T in {1, 2, 7, 16, 17, 64, 256}, every n up to 10T + 3, n = 100003 and 2**24 + 1 and spos in
+    {0, hi / 2, hi - 1} (9553 cases, checked when these tests were written).  So sample_clips_bwd_kernel's branch that adds several
+    output rows into one raw row in pick mode is reached by no valid input; no test here tries to reach it with offsets that break
+    the contract."""
+    triples = pick_triples()
+    assert len(triples) > 60
+    for n, T, spos in triples:
+        idx = S().clip_indices(n, T, spos)
+        stride = 1.0 if n <= T else n / float(T)
+        delta = (float(spos) + stride) - float(spos)
+        unclipped = np.rint(float(spos) + np.arange(min(n, T), dtype=np.float64) * delta).astype(np.int64)
+        assert idx.shape[0] == min(n, T)
+        assert np.array_equal(idx, unclipped), (n, T, spos)
+        assert bool((np.diff(idx) > 0).all()), (n, T, spos)
+        assert n == 0 or (idx[0] >= 0 and idx[-1] <= n - 1), (n, T, spos)
+
+
+# ---------------------------------------------------------------- GPU: the table gradient
+@gpu
+@pytest.mark.parametrize("case", EMBED_CASES, ids=case_id)
+def test_dense_table_gradient_bitwise(dev, case):
+    """embed_tokens(differentiable=True) -> backward: table.grad is torch.equal to table_grad_ordered (the header's ascending
+    position order inside a run, to the bit), within the fp64 bound of a length-m fp32 sum, and the same bits on a second run."""
+    B, Nq, V, E, _ = case
+    tok, dqf, want, _, ref, bound = embed_case(case)
+    runs = []
+    for _ in range(2):
+        table = torch.zeros(V, E, device=dev).requires_grad_(True)
+        runs.append(backward_dense(tok.to(dev), table, dqf.to(dev)).cpu())
+    assert torch.equal(runs[0], runs[1])
+    err = (runs[0].double() - ref).abs()
+    print(case, "elements off the ordered sum:", int((runs[0] != want).sum()), "largest error / bound",
+          float((err / bound.clamp(min=1e-300)).max()))
+    assert torch.equal(runs[0], want)
+    assert bool((err <= bound).all())
+
+
+@gpu
+@pytest.mark.parametrize("case", EMBED_CASES, ids=case_id)
+def test_row_sparse_gradient_bitwise(dev, case):
+    """embed_tokens(sparse_grad=True) -> backward, against the restatement instead of the dense kernel: ids[:count] = the sorted
+    distinct in-range ids, ids[count:] = -1, rows[:count] torch.equal to those rows of table_grad_ordered, to_dense() torch.equal to
+    the whole of it, sq_norm within 1e-9 relative of the fp64 sum of squares of table_grad_ordered.  The kernel adds count * E
+    squares in fp64 in a fixed order: 7 * 1028 = 7196 additions in the E = 1028 case, where each thread's partial sum covers up to
+    two quads, and at most 4096 * 4 = 16384 in any case here, so its rounding stays below 16384 * 2**-53 = 1.9e-12."""
+    B, Nq, V, E, _ = case
+    tok, dqf, want, ids, _, _ = embed_case(case)
+    table = torch.zeros(V, E, device=dev).requires_grad_(True)
+    rg = backward_rows(tok.to(dev), table, dqf.to(dev))
+    count = int(rg.count.item())
+    assert rg.ids.dtype == torch.int32 and rg.ids.shape == (B * Nq,) and rg.rows.shape == (B * Nq, E) and rg.shape == (V, E)
+    assert count == ids.numel()
+    assert torch.equal(rg.ids[:count].cpu().long(), ids)
+    assert bool((rg.ids[count:] == -1).all())
+    assert torch.equal(rg.rows[:count].cpu(), want[ids])
+    assert torch.equal(rg.to_dense().cpu(), want)
+    ref = float((want.double() * want.double()).sum())
+    got = float(rg.sq_norm.item())
+    print(case, "count", count, "sq_norm", got, "fp64 of the restatement", ref, "rel", abs(got - ref) / max(ref, 1e-300))
+    assert rg.sq_norm.dtype == torch.float64 and abs(got - ref) <= 1e-9 * ref
+
+
+@gpu
+@pytest.mark.parametrize("scaled", [False, True], ids=["unscaled", "scaled"])
+def test_row_adam_step_on_rows_wider_than_one_trip(dev, scaled):
+    """(4, 8, 40, 516): E / 4 = 129 quads for row_adam_update_kernel's 128 threads, so its row loop takes a second trip.  Two steps
+    (the second on non-zero moments), the whole table, both moments and state[:3] against RowSparseAdamTorch on the CPU bit for bit,
+    as tests/test_row_sparse_table.py::test_step_equals_the_torch_restatement_bitwise compares them; the rows that go into the step
+    equal table_grad_ordered."""
+    B, Nq, V, E = 4, 8, 40, 516
+    init = torch.randn(V, E, generator=torch.Generator().manual_seed(3))
+    table = init.clone().to(dev).requires_grad_(True)
+    rtable = init.clone().requires_grad_(True)
+    opt = A().RowSparseAdam(table, lr=3e-3, betas=(0.8, 0.99), eps=1e-7)
+    ref = A().RowSparseAdamTorch(rtable, lr=3e-3, betas=(0.8, 0.99), eps=1e-7)
+    scale = torch.tensor([torch.tensor(0.37, dtype=torch.float32).item()], dtype=torch.float64, device=dev) if scaled else None
+    for k, (tok, dqf) in enumerate(batches(B, Nq, V, E, 2, seed=V)):
+        rg = backward_rows(tok.to(dev), table, dqf.to(dev))
+        assert torch.equal(rg.to_dense().cpu(), table_grad_ordered(tok, dqf, V)[0])
+        opt.step(scale=scale)
+        ref.step((rg.ids.cpu(), rg.rows.cpu()), scale=scale)
+        same_state(opt, ref, table, rtable)
+        assert opt._state[0].item() == k + 1
+    assert not torch.equal(table.detach().cpu(), init)
+
+
+# ---------------------------------------------------------------- GPU: the raw-row gradient
+def clips_backward(dev, p, offsets_or_lengths, spos):
+    """sample_clips(differentiable=True) -> backward of p's dout, twice: the two gradients are bit-equal and equal p's restatement.
+    Returns the forward's (video_features, nfeats) on the host."""
+    for k in range(2):
+        r = p["raw"].to(dev).requires_grad_(True)
+        out, nf = S().sample_clips(r, offsets_or_lengths, p["T"], spos=spos, mode=p["mode"], differentiable=True)
+        assert out.requires_grad and not nf.requires_grad
+        out.backward(p["dout"].to(dev))
+        if k == 0:
+            first = r.grad.cpu()
+    assert torch.equal(first, r.grad.cpu())
+    print("rows off the restatement:", int((first != p["want"]).any(1).sum()), "of", p["rows"])
+    assert torch.equal(first, p["want"])
+    return out.detach().cpu(), nf.cpu()
+
+
+@gpu
+@pytest.mark.parametrize("which", CLIP_SPOS)
+@pytest.mark.parametrize("T,Din", CLIP_SHAPES, ids=lambda v: str(v))
+def test_raw_row_gradient_bitwise(dev, T, Din, which):
+    """Host lengths clip_lengths(T): raw.grad is torch.equal to raw_grad_scatter, pick at both ends of the draw range and mean.
+    T = 7 and 17 leave a partial 16-row block on the forward side, Din = 1028 more than one trip of the column loop per thread,
+    the two empty samples in a row equal offsets in the kernel's search for the sample of a row."""
+    p = clip_case(T, Din, clip_lengths(T), which)
+    out, nf = clips_backward(dev, p, p["lengths"], p["spos"])
+    assert torch.equal(nf, torch.from_numpy(np.minimum(p["lengths"], T).astype(np.int32)))
+    assert int((p["want"].abs().sum(1) == 0).sum()) > 0 or which == "mean"
+
+
+@gpu
+@pytest.mark.parametrize("which", ["pick-top", "mean"])
+def test_raw_row_gradient_of_a_long_sample(dev, which):
+    """T = 16, Din = 4, lengths [100003, 3]: 17 steps of the search over t per raw row and a stride of 6250.1875."""
+    T, Din, lengths = LONG
+    p = clip_case(T, Din, lengths, which)
+    clips_backward(dev, p, p["lengths"], p["spos"])
+    assert int((p["want"].abs().sum(1) > 0).sum()) == (100003 + 3 if which == "mean" else 16 + 3)
+
+
+@gpu
+@pytest.mark.parametrize("which", ["pick-top", "mean"])
+def test_raw_row_gradient_with_device_offsets(dev, which):
+    """The device-offsets form run backward: offsets[0] = 5 and raw has 9 rows past offsets[B]; the rows outside every sample get
+    exact zeros, the others the restatement's values."""
+    T, Din, lead, tail = DEVICE_OFFSETS
+    p = clip_case(T, Din, clip_lengths(T), which, lead, tail)
+    offsets = torch.from_numpy(p["offsets"]).to(dev)
+    spos = None if which == "mean" else torch.from_numpy(p["spos"].astype(np.int32)).to(dev)
+    clips_backward(dev, p, offsets, spos)
+    assert bool((p["want"][:lead] == 0).all()) and bool((p["want"][p["rows"] - tail:] == 0).all())
+    assert bool((p["want"][lead:lead + 1] != 0).any())
+
+
+@gpu
+def test_out_of_range_device_spos_is_clamped_alike(dev):
+    """Device spos = [1000, -3, top, 1000, ...] in pick mode: forward and backward clamp alike -- the forward equals
+    sample_clips_torch with the clamped values, the gradient raw_grad_scatter with them."""
+    T, Din = DEVICE_OFFSETS[:2]
+    lengths = clip_lengths(T)
+    wild = wild_spos(lengths, T)
+    p = clip_case(T, Din, lengths, "pick-given", 0, 0, wild)
+    clamped = clamp_spos(wild, lengths, T)
+    assert bool((np.array(wild) != clamped).sum() >= 6) and int(clamped.max()) > 0
+    out, nf = clips_backward(dev, p, p["lengths"], torch.tensor(wild, dtype=torch.int32, device=dev))
+    ref, rnf = S().sample_clips_torch(p["raw"], p["lengths"], T, spos=clamped, mode="pick")
+    assert torch.equal(out, ref) and torch.equal(nf, rnf)
+
+
+# ---------------------------------------------------------------- GPU: the C entries on poisoned outputs
+@gpu
+@pytest.mark.parametrize("which", ["pick-top", "mean"])
+def test_sample_clips_bwd_writes_every_row(dev, which):
+    """smin_sample_clips_bwd called directly on a draw filled with NaN (the autograd node hands it torch.empty, which cannot show
+    an unwritten row), the device-offsets case: no NaN survives and the result equals the restatement."""
+    from vml_amd._lib import call, ptr, stream
+    T, Din, lead, tail = DEVICE_OFFSETS
+    p = clip_case(T, Din, clip_lengths(T), which, lead, tail)
+    dout = p["dout"].to(dev)
+    offsets = torch.from_numpy(p["offsets"]).to(dev)
+    spos = None if which == "mean" else torch.from_numpy(p["spos"].astype(np.int32)).to(dev)
+    draw = torch.full((p["rows"], Din), float("nan"), device=dev)
+    call("smin_sample_clips_bwd", stream(), ptr(dout), ptr(offsets), ptr(spos), len(p["lengths"]), T, Din, S().MODES[p["mode"]], p["rows"],
+         ptr(draw))
+    assert not bool(torch.isnan(draw).any())
+    assert torch.equal(draw.cpu(), p["want"])
+
+
+@gpu
+def test_embed_tokens_bwd_writes_every_row(dev):
+    """smin_embed_tokens_bwd called directly on a dtable filled with NaN, the mixed-range case: no NaN survives (rows no token
+    touches are zeroed by the entry itself) and the result equals the restatement."""
+    from vml_amd._lib import call, load, ptr, stream, workspace
+    B, Nq, V, E, _ = MIXED_CASE
+    tok, dqf, want, ids, _, _ = embed_case(MIXED_CASE)
+    assert 0 < ids.numel() and longest_run(tok, V) > 2 and int(((tok < 0) | (tok >= V)).sum()) > B * Nq // 3
+    dtable = torch.full((V, E), float("nan"), device=dev)
+    ws = workspace(load().smin_embed_tokens_bwd_workspace_bytes(B, Nq), dev)
+    tok32, g = tok.to(torch.int32).to(dev), dqf.to(dev)                    # held until the call has run
+    call("smin_embed_tokens_bwd", stream(), ptr(tok32), ptr(g), B, Nq, V, E, ptr(dtable), ptr(ws), ws.numel())
+    assert not bool(torch.isnan(dtable).any())
+    assert torch.equal(dtable.cpu(), want)
+
+
+# ---------------------------------------------------------------- GPU: the forward's mask loop past 64 words
+@gpu
+@pytest.mark.parametrize("Nq", [63, 64, 65, 130])
+def test_embed_tokens_forward_beyond_one_ballot(dev, Nq):
+    """embed_tokens_kernel forms mask and length by ballots over 64 words at a time: Nq = 63, 64, 65 and 130 (one, one full, two and
+    three trips), B = 3, V = 50, E = 8, pads from a different word in every row and a few ids outside [0, V): features, mask and
+    qlen bit-equal to embed_tokens_torch."""
+    B, V, E = 3, 50, 8
+    g = torch.Generator().manual_seed(Nq)
+    tok = torch.randint(0, V - 1, (B, Nq), generator=g)
+    for b, keep in enumerate((Nq, Nq - 1, 2 * Nq // 3)):
+        tok[b, keep:] = V - 1                                              # <pad>
+    tok[0, 1], tok[1, Nq // 2], tok[2, 0], tok[0, Nq - 1] = -1, V, V + 7, 2 ** 31 - 1
+    table = torch.randn(V, E, generator=g)
+    qf, qm, ql = S().embed_tokens(tok.to(dev), table.to(dev))
+    rf, rm, rl = S().embed_tokens_torch(tok, table)
+    assert rl.tolist() == [Nq - 2, Nq - 2, 2 * Nq // 3 - 1]
+    assert torch.equal(qf.cpu(), rf) and torch.equal(qm.cpu(), rm) and torch.equal(ql.cpu(), rl)
+    assert qm.dtype == torch.uint8 and ql.dtype == torch.int32
