@@ -1107,6 +1107,42 @@ int smin_prefilter_scores(void* stream, const float* fv, const float* fs, const 
                           const uint8_t* mm, int Q, int V, int T, int L, int C, int D, float tau, float* score, float* pool, float* cells,
                           float* pm0, float* ps0, float* pe0, void* ws, size_t ws_bytes);
 
+/* smin_prefilter_maps_bwd: the gradients of smin_prefilter_scores' maps by the banks and the heads: from dpm0,
+ * dps0, dpe0 to dfv, dfs, dw and db.  Seven launches, the slab reduction among them; no atomics, plain stores; no host read; no allocation;
+ * capturable.
+ * Inputs.  dpm0 [Q V][L][L], dps0, dpe0 [Q V][L] fp32: the gradients on the maps, pair p = q V + v; pm0, ps0, pe0: the forward's stored
+ *   outputs (the sigmoids' slopes y (1 - y) are taken from them); fv, fs, w, lmask, mm, Q, V, T, L, C, D: as smin_prefilter_scores.
+ * Per pair, one workgroup of 256, with r = T / L, n = (j - i + 1) r, cs = max(1, n / C), c = min(C, n):
+ *   g_m[i][j] = dpm0 pm0 (1 - pm0) where mm[v][i][j] != 0, else 0;  g_s[i] = dps0 ps0 (1 - ps0) where lmask[v][i] != 0, else 0;  g_e
+ *     likewise.  (A masked entry's gradient is never used: it may hold anything.)
+ *   dS[i][j] = (g_m[i][j] * (1.0f / (float)cs)) / (float)C for j >= i (1 / cs rounded to fp32 as the forward rounds it), else 0;
+ *   da_m[t] = the sum of dS[i][j] over the cells whose range [i r, i r + c cs) holds frame t: four threads share a row of the map, a
+ *     quarter each, and form the row's suffix sums (the ranges of a row share their start and their ends do not decrease with j), a
+ *     table per (T, L, C) names the first j - i whose range reaches a given offset, and a frame adds ONE suffix sum per row, rows i
+ *     ascending: L T lookups per pair;  da_s[t] = g_s[t / r] / (float)r, da_e likewise;  frames t >= L r: exactly 0.
+ *   The pair's sums of g_m, g_s, g_e go to the workspace in fp64 -- under a contrastive loss the slopes cancel over a query's videos,
+ *     some 300-fold on the tiny test model, and an fp32 running sum would spend its rounding on the partial sums --; a small kernel
+ *     adds them into db over p ascending (lane k of 64 takes p = k, k + 64, ...; then the lanes ascending) and rounds once.
+ * With da [V T][N3] (column 3 q + h; N3 = 3 Q rounded up to 4, the padding columns zero) and op[3 q + h] = fs[q] (.) w[h]:
+ *   dfv = da op (the NT engine against op stored transposed, K = N3);  dop = da^T fv (the TN engine over the V T rows in sp row
+ *   splits, the slabs added in split order);  dfs[q] = sum_h dop[3 q + h] (.) w[h], h ascending;  dw[h] = sum_q dop[3 q + h] (.) fs[q],
+ *   q ascending.  Both contractions run in the mode of smin_set_gemm_mode.
+ * Outputs, every element written.  dfv [V][T][D], dfs [Q][D], dw [3][D], db [3] fp32.
+ * Workspace.  ws_bytes >= smin_prefilter_bwd_ws_bytes(Q, V, T, D) (0 for sizes out of range) = 4 (V T N3 + D N3 + sp N3 D + N3 D + 8 Q V)
+ *   bytes, in that order: da, op transposed, the slabs, dop and the pairs' partial sums of db ([Q V][4] fp64); ws 16-byte aligned;
+ *   sp = max(1, min(ceil(768 / (ceil(N3 / 128) ceil(D / 128))), ceil(V T / 64))).
+ * Limits.  smin_prefilter_scores' (1 <= L <= 64, L <= T <= 2048, D % 4 == 0, ...) and (3 Q + 3) D <= 2^28.  LDS per workgroup:
+ *   4 (L (L | 1) + 4 L + T + 24) bytes, under 26 KB at the limits.  The outputs and the workspace must not overlap the inputs or each
+ *   other.
+ * Determinism.  Every sum runs in an order fixed by the arguments: the same bits every run.
+ * Rejection.  A nonzero status before any launch, the outputs untouched, for a size out of range, a NULL pointer, a short or misaligned workspace or
+ *   an output (the workspace included) that is one of the inputs or another output. */
+size_t smin_prefilter_bwd_ws_bytes(int Q, int V, int T, int D);
+int smin_prefilter_maps_bwd(void* stream, const float* dpm0, const float* dps0, const float* dpe0, const float* pm0, const float* ps0,
+                            const float* pe0, const float* fv, const float* fs, const float* w, const uint8_t* lmask, const uint8_t* mm,
+                            int Q, int V, int T, int L, int C, int D, float* dfv, float* dfs, float* dw, float* db, void* ws,
+                            size_t ws_bytes);
+
 /* smin_prefilter_select: each query's best Ms = min(M, V) videos as the pair lists of a search; one launch, one workgroup of 256 per
  * query, no workspace.
  * Inputs.  pair_rank [Q][V] int32: smin_video_rank's pair_rank over the (Q, V) scores with pair_ptr[q] = q V (a candidate's rank among

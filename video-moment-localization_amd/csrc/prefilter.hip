@@ -6,7 +6,9 @@
 //                          stage 2: one workgroup per (q, v) stages the pair's 3 T projections in LDS, forms every cell's range sum as
 //                          a running sum along its row (one wave), applies the sigmoid heads (all waves) and pools the fused scores through pair_pool.h.
 //   smin_prefilter_select  each query's best M videos of smin_video_rank's ranks, ascending by video, as the pair lists of a search.
+//   smin_prefilter_maps_bwd  the gradients of stage 2's maps by fv, fs and the heads (described where it begins below).
 // No atomics, plain stores, every output element written, every sum in an order that depends on the arguments only.
+#include <algorithm>
 #include <cmath>
 
 #include "common.h"
@@ -235,6 +237,248 @@ extern "C" int smin_prefilter_select(void* stream, const int32_t* pair_rank, int
     SMIN_REQUIRE(pair_rank && sel_video && sel_query);
     const int Ms = M < V ? M : V;
     hipLaunchKernelGGL(prefilter_select_kernel, dim3(Q), dim3(PT), 0, (hipStream_t)stream, pair_rank, V, Ms, sel_video, sel_query);
+    SMIN_LAUNCH_CHECK();
+    return 0;
+}
+
+// ---------------------------------------------------------------- backward of the first-stage maps
+//   smin_prefilter_maps_bwd  from gradients on (pm0, ps0, pe0) to gradients on fv, fs and the heads:
+//     1. the operand transposed, opT [D][N3] (column 3 q + h = fs[q] (.) w[h], the padding columns zero: a small kernel);
+//     2. one workgroup of 256 per (q, v): the heads' sigmoid slopes from the stored outputs, the pair's three partial sums of db, a
+//        suffix sum of dS along every row of the map and the pair's 3 T values of da [V T][N3] (column 3 q + h);
+//     3. db: the pairs' partial sums (fp64: the heads' slopes of a contrastive loss cancel over a query's videos) added over p ascending
+//        and rounded once (a small kernel);
+//     4. dfv = da opT^T (launch_gemm_nt, K = N3) and dop = da^T fv (launch_gemm_tn over the V T rows, slabs reduced in split order),
+//        both in the mode of smin_set_gemm_mode;
+//     5. dfs[q] = sum_h dop[3 q + h] (.) w[h], dw[h] = sum_q dop[3 q + h] (.) fs[q], q ascending (a small kernel).
+namespace smin {
+namespace {
+
+// The workspace of smin_prefilter_maps_bwd as float offsets (every piece a multiple of 4 floats); smin_prefilter_bwd_ws_bytes reports `end`.
+struct PfBwdLayout { int N3, sp; size_t da, opT, slab, dop, dbpart, end; };
+static PfBwdLayout pfb_layout(int Q, int V, int T, int D)
+{
+    PfBwdLayout w;
+    w.N3 = cdiv(3 * Q, 4) * 4;
+    // row splits of the TN contraction: enough workgroups for the chip, at least 64 rows each (the arguments alone decide)
+    w.sp = std::max(1, std::min(cdiv(GEMM_SLOTS, cdiv(w.N3, 128) * cdiv(D, 128)), cdiv(V * T, 64)));
+    w.da = 0;                                                    // [V T][N3]
+    w.opT = w.da + (size_t)V * T * w.N3;                         // [D][N3]
+    w.slab = w.opT + (size_t)D * w.N3;                           // [sp][N3][D]
+    w.dop = w.slab + (size_t)w.sp * w.N3 * D;                    // [N3][D]
+    w.dbpart = w.dop + (size_t)w.N3 * D;                         // [Q V][4] fp64
+    w.end = w.dbpart + (size_t)Q * V * 8;
+    return w;
+}
+static bool pfb_sizes_ok(int Q, int V, int T, int D)
+{
+    return pf_sizes_ok(Q, V, T, D) && (long long)(3 * Q + 3) * D <= (1ll << 28);     // (the slab reduction counts dop's elements in an int)
+}
+
+// butterfly sum over the wave's 64 lanes in fp64 (a fixed order per lane)
+__device__ __forceinline__ double wave_sum_f64(double v)
+{
+    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
+    return v;
+}
+
+// opT [D][N3]: column 3 q + h of row d = fs[q][d] * w[h][d] (the forward's operand, transposed); columns >= 3 Q are zero
+__global__ __launch_bounds__(PT)
+void prefilter_operand_t_kernel(const float* __restrict__ fs, const float* __restrict__ w, int Q, int D, int N3, size_t total, float* __restrict__ opT)
+{
+    const size_t idx = (size_t)blockIdx.x * PT + threadIdx.x;
+    if (idx >= total) return;
+    const int d = (int)(idx / N3), n = (int)(idx % N3), q = n / 3, h = n % 3;
+    opT[idx] = q < Q ? fs[(size_t)q * D + d] * w[(size_t)h * D + d] : 0.f;
+}
+
+// One workgroup per (q, v) = (blockIdx.y, blockIdx.x).  LDS: red [12] fp64, S [L][L | 1] (dS, then its suffix sums along the rows), gs [L],
+// ge [L], inv [L] (1 / cs of a window of d + 1 clips), wlen [L], first [T] (the first d whose wlen[d] exceeds a frame's offset from its
+// row's start; L if none): 4 (L (L | 1) + 4 L + T + 24) bytes.
+// Phase 1.  All threads: first[] by bisection of the non-decreasing wlen[]; the slopes of the three heads from the stored outputs, dS
+// cell by cell, the thread's partial sums of db in fp64; the partial sums meet in wave order.
+// Phase 2.  Thread t owns quarter t & 3 of row t >> 2: the quarter's suffix sums, then the later quarters' totals on top.
+// Phase 3.  All threads, one frame each: the rows i = 0 .. t / r in ascending order, one lookup each -- the cells of row i that hold
+// frame t are those with j - i >= first[t - i r], whose dS the suffix sum holds at that column.
+__global__ __launch_bounds__(PT)
+void prefilter_cell_bwd_kernel(const float* __restrict__ dpm0, const float* __restrict__ dps0, const float* __restrict__ dpe0,
+                               const float* __restrict__ pm0, const float* __restrict__ ps0, const float* __restrict__ pe0,
+                               const uint8_t* __restrict__ lmask, const uint8_t* __restrict__ mm, int Q, int V, int T, int L, int C, int N3,
+                               float* __restrict__ da, double* __restrict__ dbpart)
+{
+    extern __shared__ __attribute__((aligned(16))) float pfb_smem[];
+    const int LS = L | 1;
+    double* red = reinterpret_cast<double*>(pfb_smem);
+    float* S = pfb_smem + 24;
+    float* gs = S + L * LS;
+    float* ge = gs + L;
+    float* inv = ge + L;
+    int* wlen = reinterpret_cast<int*>(inv + L);
+    int* first = wlen + L;
+    const int v = blockIdx.x, q = blockIdx.y, t = threadIdx.x, r = T / L;
+    const size_t p = (size_t)q * V + v;
+    const uint8_t* vmm = mm + (size_t)v * L * L;
+    if (t < L) {
+        const int n = (t + 1) * r, cs = max(1, n / C), c = min(C, n);
+        wlen[t] = c * cs;
+        inv[t] = 1.0f / (float)cs;
+    }
+    __syncthreads();
+    for (int o = t; o < T; o += PT) {
+        int lo = 0, hi = L;                                      // the first d in [0, L] with wlen[d] > o
+        while (lo < hi) {
+            const int mid = (lo + hi) >> 1;
+            if (wlen[mid] > o) hi = mid; else lo = mid + 1;
+        }
+        first[o] = lo;
+    }
+    double accm = 0.0, accs = 0.0, acce = 0.0;
+    for (int k = t; k < L * L; k += PT) {
+        const int i = k / L, j = k - i * L, d = j - i;
+        const float y = pm0[p * L * L + k];
+        const float g = vmm[k] ? dpm0[p * L * L + k] * y * (1.0f - y) : 0.f;
+        accm += (double)g;                                       // (a valid cell under the diagonal holds sigmoid(b[0]): it reaches db alone)
+        S[i * LS + j] = d >= 0 ? (g * inv[d]) / (float)C : 0.f;
+    }
+    if (t < L) {
+        const float ys = ps0[p * L + t], ye = pe0[p * L + t];
+        const bool ok = lmask[(size_t)v * L + t] != 0;
+        const float s = ok ? dps0[p * L + t] * ys * (1.0f - ys) : 0.f;
+        const float e = ok ? dpe0[p * L + t] * ye * (1.0f - ye) : 0.f;
+        gs[t] = s;
+        ge[t] = e;
+        accs = (double)s;
+        acce = (double)e;
+    }
+    accm = wave_sum_f64(accm);
+    accs = wave_sum_f64(accs);
+    acce = wave_sum_f64(acce);
+    if ((t & 63) == 0) { red[3 * (t >> 6)] = accm; red[3 * (t >> 6) + 1] = accs; red[3 * (t >> 6) + 2] = acce; }
+    __syncthreads();
+    if (t < 3) dbpart[4 * p + t] = ((red[t] + red[3 + t]) + red[6 + t]) + red[9 + t];
+    if (t == 3) dbpart[4 * p + 3] = 0.0;
+
+    const int row = t >> 2, seg = t & 3, Lq = (L + 3) / 4, c0 = seg * Lq, c1 = min(L, c0 + Lq);
+    const bool owner = row < L && c0 < c1;
+    if (owner) {
+        float run = 0.f;
+        for (int j = c1 - 1; j >= c0; --j) { run += S[row * LS + j]; S[row * LS + j] = run; }
+    }
+    __syncthreads();
+    float later = 0.f;
+    if (owner)
+        for (int s = 3; s > seg; --s)
+            if (s * Lq < L) later += S[row * LS + s * Lq];
+    __syncthreads();
+    if (owner)
+        for (int j = c0; j < c1; ++j) S[row * LS + j] += later;
+    __syncthreads();
+
+    const int Tr = L * r, pad = N3 - 3 * Q;
+    for (int tt = t; tt < T; tt += PT) {
+        float am = 0.f, as = 0.f, ae = 0.f;
+        if (tt < Tr) {                                           // the frames past L r reach no clip: exactly 0
+            const int ci = tt / r;
+            for (int i = 0; i <= ci; ++i) {
+                const int col = i + first[tt - i * r];
+                if (col < L) am += S[i * LS + col];
+            }
+            as = gs[ci] / (float)r;
+            ae = ge[ci] / (float)r;
+        }
+        float* o = da + ((size_t)v * T + tt) * N3 + 3 * q;
+        o[0] = am; o[1] = as; o[2] = ae;
+        if (q == Q - 1)
+            for (int k = 0; k < pad; ++k) o[3 + k] = 0.f;        // the contraction's padding columns
+    }
+}
+
+// db[h] = the pairs' partial sums in fp64, p ascending within a lane's stride of 64, then the 64 lanes ascending, rounded once
+__global__ __launch_bounds__(192)
+void prefilter_db_kernel(const double* __restrict__ dbpart, size_t P, float* __restrict__ db)
+{
+    __shared__ double part[3][64];
+    const int h = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    double s = 0.0;
+    for (size_t p = lane; p < P; p += 64) s += dbpart[4 * p + h];
+    part[h][lane] = s;
+    __syncthreads();
+    if (lane == 0) {
+        double v = part[h][0];
+        for (int k = 1; k < 64; ++k) v += part[h][k];
+        db[h] = (float)v;
+    }
+}
+
+// dfs [Q][D] and dw [3][D] of dop [N3][D]: elements [0, Q D) are dfs, the next 3 D are dw (q ascending)
+__global__ __launch_bounds__(PT)
+void prefilter_operand_bwd_kernel(const float* __restrict__ dop, const float* __restrict__ fs, const float* __restrict__ w, int Q, int D,
+                                  float* __restrict__ dfs, float* __restrict__ dw)
+{
+    const size_t idx = (size_t)blockIdx.x * PT + threadIdx.x, nq = (size_t)Q * D;
+    if (idx < nq) {
+        const size_t q = idx / D, d = idx % D;
+        float s = dop[(3 * q) * D + d] * w[d];
+        s += dop[(3 * q + 1) * D + d] * w[(size_t)D + d];
+        s += dop[(3 * q + 2) * D + d] * w[2 * (size_t)D + d];
+        dfs[idx] = s;
+    } else if (idx < nq + 3 * (size_t)D) {
+        const size_t h = (idx - nq) / D, d = (idx - nq) % D;
+        float s = 0.f;
+        for (size_t q = 0; q < (size_t)Q; ++q) s += dop[(3 * q + h) * D + d] * fs[q * D + d];
+        dw[idx - nq] = s;
+    }
+}
+
+}  // namespace
+}  // namespace smin
+
+extern "C" size_t smin_prefilter_bwd_ws_bytes(int Q, int V, int T, int D)
+{
+    if (!pfb_sizes_ok(Q, V, T, D)) return 0;
+    return pfb_layout(Q, V, T, D).end * sizeof(float);
+}
+
+extern "C" int smin_prefilter_maps_bwd(void* stream, const float* dpm0, const float* dps0, const float* dpe0, const float* pm0, const float* ps0,
+                                       const float* pe0, const float* fv, const float* fs, const float* w, const uint8_t* lmask,
+                                       const uint8_t* mm, int Q, int V, int T, int L, int C, int D, float* dfv, float* dfs, float* dw, float* db,
+                                       void* ws, size_t ws_bytes)
+{
+    SMIN_REQUIRE(pfb_sizes_ok(Q, V, T, D) && L >= 1 && L <= PF_MAX_L && T >= L && C >= 1 && C <= 0x10000);
+    SMIN_REQUIRE(dpm0 && dps0 && dpe0 && pm0 && ps0 && pe0 && fv && fs && w && lmask && mm && dfv && dfs && dw && db && ws);
+    SMIN_REQUIRE(ws_bytes >= smin_prefilter_bwd_ws_bytes(Q, V, T, D));
+    SMIN_REQUIRE(((uintptr_t)ws & 15) == 0);                     // (the contractions read da in 16-byte pieces)
+    const void* ins[11] = {dpm0, dps0, dpe0, pm0, ps0, pe0, fv, fs, w, lmask, mm};
+    const void* outs[5] = {dfv, dfs, dw, db, ws};
+    for (int o = 0; o < 5; ++o) {                                // an output that is an input or another output
+        for (const void* in : ins) SMIN_REQUIRE(in != outs[o]);
+        for (int k = 0; k < o; ++k) SMIN_REQUIRE(outs[k] != outs[o]);
+    }
+    const hipStream_t st = (hipStream_t)stream;
+    const PfBwdLayout lay = pfb_layout(Q, V, T, D);
+    float* base = static_cast<float*>(ws);
+    float* da = base + lay.da;
+    float* opT = base + lay.opT;
+    float* slab = base + lay.slab;
+    float* dop = base + lay.dop;
+    double* dbpart = reinterpret_cast<double*>(base + lay.dbpart);
+    const size_t total = (size_t)D * lay.N3;
+    hipLaunchKernelGGL(prefilter_operand_t_kernel, dim3((unsigned)((total + PT - 1) / PT)), dim3(PT), 0, st, fs, w, Q, D, lay.N3, total, opT);
+    SMIN_LAUNCH_CHECK();
+    const size_t lds = sizeof(float) * ((size_t)L * (L | 1) + 4 * (size_t)L + T + 24);
+    hipLaunchKernelGGL(prefilter_cell_bwd_kernel, dim3(V, Q), dim3(PT), lds, st, dpm0, dps0, dpe0, pm0, ps0, pe0, lmask, mm, Q, V, T, L, C, lay.N3,
+                       da, dbpart);
+    SMIN_LAUNCH_CHECK();
+    hipLaunchKernelGGL(prefilter_db_kernel, dim3(1), dim3(192), 0, st, dbpart, (size_t)Q * V, db);
+    SMIN_LAUNCH_CHECK();
+    int rc = launch_gemm_nt(st, PlainMat{da, lay.N3}, PlainMat{opT, lay.N3}, EpSlabStore{dfv}, V * T, D, lay.N3);
+    if (rc) return rc;
+    rc = launch_gemm_tn(st, PlainMat{da, lay.N3}, PlainMat{fv, D}, slab, (float*)nullptr, V * T, lay.N3, D, lay.sp);
+    if (rc) return rc;
+    rc = launch_reduce_slabs(st, slab, dop, lay.N3 * D, lay.sp);
+    if (rc) return rc;
+    const size_t nel = ((size_t)Q + 3) * D;
+    hipLaunchKernelGGL(prefilter_operand_bwd_kernel, dim3((unsigned)((nel + PT - 1) / PT)), dim3(PT), 0, st, dop, fs, w, Q, D, dfs, dw);
     SMIN_LAUNCH_CHECK();
     return 0;
 }

@@ -650,6 +650,43 @@ class PairRankFn(Function):
         return (dpm, dps, dpe) + (None,) * 6
 
 
+class PrefilterMapsFn(Function):
+    """The first-stage maps with their backward (csrc/prefilter.hip) on the ctypes route: smin_prefilter_scores
+    with maps in ONE call, smin_prefilter_maps_bwd in the backward.  ``lmask`` / ``mm``: one byte per entry.  Returns (pm0 (Q, V, L,
+    L), ps0, pe0 (Q, V, L), score (Q, V), pool (Q, V, 2), cells (Q, V)); the last three are not differentiable; gradients go to fv, fs,
+    w and b."""
+
+    @staticmethod
+    def forward(ctx, fv, fs, w, b, lmask, mm, T, L, C, tau):
+        fv, fs, w, b = (_c(x.detach().float()) for x in (fv, fs, w, b))
+        lmask, mm = _c(lmask), _c(mm)
+        V, _, D = fv.shape
+        Q = fs.shape[0]
+        new = lambda *shape: fv.new_empty(shape)
+        score, pool, cells = new(Q, V), new(Q, V, 2), new(Q, V)
+        pm0, ps0, pe0 = new(Q, V, L, L), new(Q, V, L), new(Q, V, L)
+        nbytes = _lib.load().smin_prefilter_ws_bytes(Q, V, T, D)
+        ws = _lib.workspace(nbytes, fv.device)
+        call("smin_prefilter_scores", stream(), ptr(fv), ptr(fs), ptr(w), ptr(b), ptr(lmask), ptr(mm), Q, V, T, L, C, D, tau, ptr(score), ptr(pool),
+             ptr(cells), ptr(pm0), ptr(ps0), ptr(pe0), ptr(ws), ws.numel())
+        ctx.save_for_backward(fv, fs, w, lmask, mm, pm0, ps0, pe0)
+        ctx.dims = (Q, V, T, L, C, D)
+        ctx.mark_non_differentiable(score, pool, cells)
+        return pm0, ps0, pe0, score, pool, cells
+
+    @staticmethod
+    def backward(ctx, dpm0, dps0, dpe0, _dscore, _dpool, _dcells):
+        fv, fs, w, lmask, mm, pm0, ps0, pe0 = ctx.saved_tensors
+        Q, V, T, L, C, D = ctx.dims
+        dpm0, dps0, dpe0 = (_c(x.float()) for x in (dpm0, dps0, dpe0))
+        dfv, dfs, dw, db = torch.empty_like(fv), torch.empty_like(fs), torch.empty_like(w), fv.new_empty((3,))
+        nbytes = _lib.load().smin_prefilter_bwd_ws_bytes(Q, V, T, D)
+        ws = _lib.workspace(nbytes, fv.device)
+        call("smin_prefilter_maps_bwd", stream(), ptr(dpm0), ptr(dps0), ptr(dpe0), ptr(pm0), ptr(ps0), ptr(pe0), ptr(fv), ptr(fs), ptr(w), ptr(lmask),
+             ptr(mm), Q, V, T, L, C, D, ptr(dfv), ptr(dfs), ptr(dw), ptr(db), ptr(ws), ws.numel())
+        return (dfv, dfs, dw, db) + (None,) * 6
+
+
 def gemm_nt(a, b):
     """C = A @ B^T on the library's fp32 MFMA engine (tests / bench roofline probe)."""
     a, b = _c(a), _c(b)

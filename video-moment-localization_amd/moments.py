@@ -916,6 +916,31 @@ def prefilter_scores(fv, fs, w, b, length_mask, moment_mask, T, L, C, tau=0.1, m
     return tuple(outs)
 
 
+def prefilter_maps(fv, fs, w, b, length_mask, moment_mask, T, L, C, tau=0.1):
+    """``prefilter_scores(maps=True)`` with a backward (include/smin_hip.h, smin_prefilter_maps_bwd): the first-stage
+    maps of every (query, video), differentiable with respect to ``fv``, ``fs``, ``w`` and ``b`` -- what training the first stage
+    needs.  Returns ``(pm0 (Q, V, L, L), ps0 (Q, V, L), pe0 (Q, V, L), score (Q, V))``: the maps have prefilter_scores' bits, the score
+    is detached.  The backward is HIP kernels and the library's two fp32 contractions (in the mode of set_gemm_mode), every sum in an
+    order fixed by the shapes: the same bits every run.
+
+    One call, never tiled -- a tile would change the summation order of the gradients of ``fs``, ``w`` and ``b`` --: where the
+    forward's and the backward's workspaces together would pass PREFILTER_WS_CAP it raises ValueError.  HIP tensors only; no host
+    synchronisation."""
+    _require_hip(fv, "prefilter_maps")
+    Q, V, D, tau = _prefilter_check("prefilter_maps", fv, fs, w, b, length_mask, moment_mask, T, L, C, tau)
+    if any(x.dtype != torch.float32 for x in (fv, fs, w, b)):
+        raise ValueError("prefilter_maps: fv, fs, w and b must be float32 (the gradients are formed in fp32)")
+    lib = load()
+    nbytes = int(lib.smin_prefilter_ws_bytes(Q, V, T, D)), int(lib.smin_prefilter_bwd_ws_bytes(Q, V, T, D))
+    if min(nbytes) == 0 or sum(nbytes) > PREFILTER_WS_CAP:
+        raise ValueError(f"prefilter_maps: {Q} queries over {V} videos of {T} frames need {nbytes[0]} + {nbytes[1]} bytes of workspace in "
+                         f"one call (0: sizes out of range), the cap is {PREFILTER_WS_CAP}: train on smaller groups (the call is not tiled)")
+    from .functional import PrefilterMapsFn
+    with torch.cuda.device(fv.device):
+        pm0, ps0, pe0, score, _, _ = PrefilterMapsFn.apply(fv, fs, w, b, byte_mask(length_mask), byte_mask(moment_mask), int(T), int(L), int(C), tau)
+    return pm0, ps0, pe0, score
+
+
 @functools.lru_cache(maxsize=8)
 def _prefilter_window_weights(T, L, C):
     r = T // L

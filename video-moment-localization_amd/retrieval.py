@@ -13,7 +13,7 @@ from ._host import _AttnMaps, byte_mask, host_array, known_cells, query_mask_row
 from .feeder import build_masks_hip, cell_count
 from .functional import attn_maps_gather
 from .moments import (MAX_K, _pair_pool_into, _temperature, _top_moments_into, _video_weight, corpus_span_topk, corpus_span_topk_torch, corpus_topk,
-                      corpus_topk_torch, group_pool, merge_window_moments, merge_window_moments_torch, mine_pairs, prefilter_scores, prefilter_select,
+                      corpus_topk_torch, group_pool, merge_window_moments, merge_window_moments_torch, mine_pairs, prefilter_maps, prefilter_scores, prefilter_select,
                       rank_videos, reweight_moments,
                       reweight_moments_torch, search_times, top_moments, top_moments_torch, window_times)
 from .sampling import MAX_ROWS, MODES, sample_windows, window_plan
@@ -627,6 +627,41 @@ class _Retrieval:
         if not windowed:
             r.update(video_index=video.reshape(-1), query_index=query.reshape(-1))
         return r
+
+    def prefilter_forward(self, video_features, video_mask, query_features, query_mask, length_mask, moment_mask, tau=0.1):
+        """The first-stage maps of every (query, video) of V videos and Q queries, with grad: what prefilter_videos
+        ranks by, differentiable with respect to the encoders and the three score heads; no SMI layer runs.  ``fv`` and ``fs`` come
+        from the modules' own encoders (``backbone.videoencoder`` through LinearRowsFn, ``backbone.queryencoder`` through
+        BiLstmLayerFn), the heads' ``w`` / ``b`` are stacked from ``localization.conv_layer_pm / ps / pe`` as prefilter_videos stacks
+        them, and moments.prefilter_maps forms the maps and, in the backward, their gradients.
+
+        Returns ``(pm0 (Q * V, L, L), ps0 (Q * V, L), pe0 (Q * V, L), score (Q, V))``: the maps in pair order ``p = q * V + v`` as
+        training.pair_rank_loss takes them, the score detached (pooled at ``tau``).  Raises ValueError where the fused encoders are
+        unavailable (``fused()`` false, inputs that are not float32, T differing from the model's).  No host read."""
+        what = "prefilter_forward"
+        if video_features.dim() != 3 or query_features.dim() != 3 or video_features.shape[0] < 1 or query_features.shape[0] < 1:
+            raise ValueError(f"{what}: video_features (V, T, Din) and query_features (Q, words, E) with V, Q >= 1; got "
+                             f"{tuple(video_features.shape)} and {tuple(query_features.shape)}")
+        V, Q = video_features.shape[0], query_features.shape[0]
+        if video_mask.shape[0] != V or tuple(length_mask.shape) != (V, self.L) or tuple(moment_mask.shape) != (V, self.L, self.L) or query_mask.shape[0] != Q:
+            raise ValueError(f"{what}: video_mask (V, T[, 1]), length_mask (V, L) and moment_mask (V, L, L) with a row per video, query_mask with a "
+                             f"row per query; got {tuple(video_mask.shape)}, {tuple(length_mask.shape)}, {tuple(moment_mask.shape)}, {tuple(query_mask.shape)}")
+        tau = _temperature(what, tau)
+        ve, qe = self.backbone.videoencoder, self.backbone.queryencoder
+        if not (qe.fused() and query_features.dtype == torch.float32 and ve.fused(video_features) and video_features.shape[1] == self.T):
+            raise ValueError(f"{what}: the first stage trains through the fused encoders (float32 inputs of T = {self.T} frames, "
+                             "VideoEncoder.fused and QueryEncoder.fused); this module or these inputs are off that path")
+        require_hip_tensors(what, dict(video_features=video_features, video_mask=video_mask, query_features=query_features, query_mask=query_mask,
+                                       length_mask=length_mask, moment_mask=moment_mask))
+        lo, D = self.localization, self.D
+        heads = (lo.conv_layer_pm, lo.conv_layer_ps, lo.conv_layer_pe)
+        with torch.cuda.device(video_features.device):
+            fv = ve(video_features, video_mask.reshape(V, -1, 1))
+            fs, _ = qe(query_features, query_mask)
+            w, b = torch.stack([h.weight.reshape(D) for h in heads]), torch.cat([h.bias.reshape(1) for h in heads])
+            pm0, ps0, pe0, score = prefilter_maps(fv, fs, w, b, length_mask, moment_mask, self.T, self.L, self.C, tau)
+        L = self.L
+        return pm0.reshape(Q * V, L, L), ps0.reshape(Q * V, L), pe0.reshape(Q * V, L), score
 
     def _pair_moments_device(self, videos, queries, vi_d, qi_d, cell, k_video, nms_thresh, max_batch, pools=None):
         """``_pair_moments`` over pair lists that exist on the device only (int32 ``vi_d`` / ``qi_d (P,)``): the same chunks, no host copy

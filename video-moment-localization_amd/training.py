@@ -2,6 +2,7 @@
 R@n/IoU metric, restated so that the unmodified training loop becomes runnable.  ``loss_fn`` / ``compute_ious`` are the
 product entry points (HIP kernels, HIP tensors only); ``*_torch`` are the same formulas as plain torch ops, kept under their
 own names as a second restatement the tests compare against -- nothing routes to them silently."""
+import numpy as np
 import torch
 import torch.nn.functional as F
 
@@ -348,16 +349,67 @@ def _rank_weight(what, rank_weight, tau, gamma):
     return float(rank_weight)
 
 
-def _pair_step(model, optimizer, g, plan, meter, rank_weight=0.0, tau=0.1, gamma=0.1):
+def _prefilter_weight(what, prefilter_weight, tau, gamma):
+    """The loops' check of their first-stage term's arguments, ahead of the first step."""
+    if not (isinstance(prefilter_weight, (int, float)) and not isinstance(prefilter_weight, bool) and 0.0 <= float(prefilter_weight) < float("inf")):
+        raise ValueError(f"{what}: prefilter_weight must be a finite number >= 0 (got {prefilter_weight!r})")
+    _temperatures(what, tau, gamma)
+    return float(prefilter_weight)
+
+
+_ALL_PAIRS_PLANS = {}              # (V, Q, gt_video, device) -> the all-pairs PairPlan: a group met again makes no second pinned copy
+
+
+def all_pairs_plan(V, Q, gt_video, device, what="all_pairs_plan"):
+    """The PairPlan of all Q * V pairs of a group, q-major (``p = q * V + v``, so ``q_ptr[q] = q * V``), with its positive flags at
+    ``v == gt_video[q]``: the pair order of SMIN.prefilter_forward's maps.  One plan is kept per (V, Q, gt_video, device) -- the latest
+    16 --, as the loops share a group's plan between forward_pairs and pair_targets: one pinned copy per distinct group at most."""
+    from .retrieval import PairPlan
+    gv = host_array(gt_video)
+    key = (int(V), int(Q), tuple(int(x) for x in gv), str(torch.device(device)))
+    plan = _ALL_PAIRS_PLANS.get(key)
+    if plan is None:
+        if len(_ALL_PAIRS_PLANS) >= 16:
+            _ALL_PAIRS_PLANS.pop(next(iter(_ALL_PAIRS_PLANS)))
+        plan = _ALL_PAIRS_PLANS[key] = PairPlan(np.tile(np.arange(V), Q), np.repeat(np.arange(Q), V), V, Q, device, gt_video=gv, what=what)
+    return plan
+
+
+def prefilter_rank_loss(model, group, tau=0.1, gamma=0.1, return_stats=False):
+    """``pair_rank_loss`` on the FIRST-STAGE maps of a group: each query's own video ranked above all the other
+    videos of the group by the score ``SMIN.search(prefilter=M)`` prunes with -- the model with zero SMI layers.  ``group``:
+    train_epoch_pairs' dict (the tensors and ``gt_video``; its pair lists are not read: the term runs over all Q * V pairs).
+    SMIN.prefilter_forward forms the maps with grad through the modules' encoders and the three score heads, the all-pairs plan
+    (all_pairs_plan) carries the positive flags, ``moment_mask`` is gathered per pair, and the existing pair_rank_loss contrasts them,
+    unchanged.  Gradients reach the encoders and the heads only; no SMI layer runs.  No host read.  Returns pair_rank_loss' value(s)."""
+    what = "prefilter_rank_loss"
+    _temperatures(what, tau, gamma)
+    mm = group["moment_mask"]
+    V, Q = mm.shape[0], group["query_features"].shape[0]
+    if "gt_video" not in group or group["gt_video"] is None:
+        raise ValueError(f"{what}: the group must carry gt_video, each query's own video")
+    gv = host_array(group["gt_video"])
+    if gv.shape[0] != Q or (gv.size and (gv.min() < 0 or gv.max() >= V)):
+        raise ValueError(f"{what}: gt_video must name one of the V = {V} videos for each of the Q = {Q} queries")
+    pm0, ps0, pe0, _ = model.prefilter_forward(*_inputs(group), tau=tau)
+    plan = all_pairs_plan(V, Q, gv, mm.device, what)
+    mm_pairs = mm.index_select(0, plan.video_index)
+    return pair_rank_loss(pm0, ps0, pe0, mm_pairs, plan, tau, gamma, return_stats)
+
+
+def _pair_step(model, optimizer, g, plan, meter, rank_weight=0.0, tau=0.1, gamma=0.1, prefilter_weight=0.0):
     """One step of train_epoch_pairs on group ``g`` through ``plan`` (built with its positive flags): forward_pairs, pair_targets,
     loss_fn over all the pairs -- plus ``rank_weight * pair_rank_loss`` over the plan when the weight is not 0 --, the meter over the
-    positive ones, backward, optimizer.step.  No host read with ``cell_counts``."""
+    positive ones, backward, optimizer.step.  ``prefilter_weight`` not 0: plus ``prefilter_weight * prefilter_rank_loss`` over all
+    the group's pairs.  No host read with ``cell_counts``."""
     optimizer.zero_grad()
     out = model.forward_pairs(*_inputs(g), None, None, cell_counts=g.get("cell_counts"), plan=plan)
     tg = pair_targets(g, g, None, None, None, plan=plan)
     loss = _loss_of(out, tg)
     if rank_weight != 0.0:
         loss = loss + rank_weight * pair_rank_loss(out[0], out[1], out[2], tg["moment_mask"], plan, tau, gamma)
+    if prefilter_weight != 0.0:
+        loss = loss + prefilter_weight * prefilter_rank_loss(model, g, tau, gamma)
     rows = plan.positive_rows
     meter.update(out[0].detach().index_select(0, rows), out[1].detach().index_select(0, rows), out[2].detach().index_select(0, rows),
                  tg["moment_mask"].index_select(0, rows), tg["sm"].index_select(0, rows), loss=loss.detach())
@@ -365,7 +417,7 @@ def _pair_step(model, optimizer, g, plan, meter, rank_weight=0.0, tau=0.1, gamma
     optimizer.step()
 
 
-def train_epoch_pairs(model, optimizer, groups, meter=None, rank_weight=0.0, tau=0.1, gamma=0.1):
+def train_epoch_pairs(model, optimizer, groups, meter=None, rank_weight=0.0, tau=0.1, gamma=0.1, prefilter_weight=0.0):
     """train_epoch over groups of V videos and Q queries that share their encoders (SMIN.forward_pairs).  A group
     is a dict with ``video_features``, ``video_mask``, ``length_mask``, ``moment_mask`` (a row per video), ``query_features``,
     ``query_mask`` and LOSS_TARGETS (a row per query, against its own video), the host lists ``video_index``, ``query_index`` (the
@@ -381,9 +433,16 @@ def train_epoch_pairs(model, optimizer, groups, meter=None, rank_weight=0.0, tau
     ``rank_weight`` > 0: the step's loss is ``loss_fn(...) + rank_weight * pair_rank_loss(pm, ps, pe, moment_mask, plan, tau, gamma)``,
     formed on the device -- the contrastive term that ranks a query's own video above the wrong ones of its pairs
     --, and the meter records that total.  At 0 (the default) the term is not computed and the step is unchanged, bit for bit; a
-    negative weight raises ValueError."""
+    negative weight raises ValueError.
+
+    ``prefilter_weight`` > 0: the loss also gains ``prefilter_weight * prefilter_rank_loss(model, group, tau, gamma)``, the same
+    contrastive term on the first-stage maps over ALL the group's Q * V pairs -- it trains the score that
+    ``search(prefilter=M)`` prunes with; the group must carry ``gt_video``.  The encoders then run a second time in the step, as
+    modules.  At 0 (the default) nothing new is called and the step is unchanged, bit for bit; a negative or non-finite weight
+    raises ValueError ahead of the first step."""
     from .retrieval import PairPlan
     rank_weight = _rank_weight("train_epoch_pairs", rank_weight, tau, gamma)
+    prefilter_weight = _prefilter_weight("train_epoch_pairs", prefilter_weight, tau, gamma)
     model.train()
     for g in groups:
         meter = _meter_for(meter, g)
@@ -396,12 +455,13 @@ def train_epoch_pairs(model, optimizer, groups, meter=None, rank_weight=0.0, tau
             raise ValueError("train_epoch_pairs: a group's plan must be a PairPlan with its positive flags for the group's videos and queries")
         if plan.num_positive < 1:
             raise ValueError("train_epoch_pairs: a group must list at least one query with its own video (the metric runs over those pairs)")
-        _pair_step(model, optimizer, g, plan, meter, rank_weight, tau, gamma)
+        _pair_step(model, optimizer, g, plan, meter, rank_weight, tau, gamma, prefilter_weight)
     metrics = meter.result()
     return metrics["loss"], metrics
 
 
-def train_epoch_mined(model, optimizer, groups, negatives, skip=0, meter=None, max_batch=64, rank_weight=0.0, tau=0.1, gamma=0.1, mine_pool=None):
+def train_epoch_mined(model, optimizer, groups, negatives, skip=0, meter=None, max_batch=64, rank_weight=0.0, tau=0.1, gamma=0.1, mine_pool=None,
+                      prefilter_weight=0.0):
     """train_epoch_pairs with the pairs chosen by the model (hard-negative mining).  A group is train_epoch_pairs'
     dict without the two lists: the tensors, ``gt_video`` (Q host ints) and optionally ``cell_counts``.  Per group, under
     torch.no_grad(): encode_videos / encode_queries with the current parameters and ``model.mine_pairs`` -- every query against every
@@ -412,8 +472,10 @@ def train_epoch_mined(model, optimizer, groups, negatives, skip=0, meter=None, m
     counts as well.  ``num_samples`` counts the queries.  Returns ``(train_loss, iou_metrics)``.  The meter is not reset here.
     ``rank_weight``, ``tau``, ``gamma``: train_epoch_pairs' contrastive term over the mined plan -- what a hard negative is mined for.
     ``mine_pool``: SMIN.mine_pairs' ``pool`` -- ``"lme"`` mines by the pooled pair score at ``tau``, the score that term contrasts
-    (INTEGRATION.md 3t); None by the best moment."""
+    (INTEGRATION.md 3t); None by the best moment.  ``prefilter_weight``: train_epoch_pairs' first-stage term over all the group's
+    pairs; 0, the default, leaves the step unchanged bit for bit."""
     rank_weight = _rank_weight("train_epoch_mined", rank_weight, tau, gamma)
+    prefilter_weight = _prefilter_weight("train_epoch_mined", prefilter_weight, tau, gamma)
     model.train()
     for g in groups:
         meter = _meter_for(meter, g)
@@ -421,9 +483,35 @@ def train_epoch_mined(model, optimizer, groups, negatives, skip=0, meter=None, m
             videos = model.encode_videos(g["video_features"], g["video_mask"], g["length_mask"], g["moment_mask"], cell_counts=g.get("cell_counts"))
             queries = model.encode_queries(g["query_features"], g["query_mask"])
             plan = model.mine_pairs(videos, queries, g["gt_video"], negatives, skip=skip, max_batch=max_batch, pool=mine_pool, tau=tau)
-        _pair_step(model, optimizer, g, plan, meter, rank_weight, tau, gamma)
+        _pair_step(model, optimizer, g, plan, meter, rank_weight, tau, gamma, prefilter_weight)
     metrics = meter.result()
     return metrics["loss"], metrics
+
+
+def train_epoch_prefilter(model, optimizer, groups, tau=0.1, gamma=0.1):
+    """The first stage alone: per group ``prefilter_rank_loss`` over all its Q * V pairs, backward,
+    optimizer.step -- a cheap pre-training or fine-tuning pass of the encoders and the three score heads in which no SMI layer runs
+    (the layers' parameters receive no gradient: give the optimizer the parameters to move, or all of them -- FusedAdam skips a
+    parameter without a gradient).  A group is train_epoch_pairs' dict; only the six model inputs and ``gt_video`` are read.  The
+    losses and pair_rank_loss' stats are summed on the device; ONE host read at the end.  Returns ``(mean loss over the groups,
+    in-group hit rate)``: the share of the counted queries whose own video scores at least as high as every other video of its
+    group by the first-stage score."""
+    _temperatures("train_epoch_prefilter", tau, gamma)
+    model.train()
+    total = stats = None
+    n = 0
+    for g in groups:
+        optimizer.zero_grad()
+        loss, st, _ = prefilter_rank_loss(model, g, tau, gamma, return_stats=True)
+        loss.backward()
+        optimizer.step()
+        total = loss.detach().clone() if total is None else total + loss.detach()
+        stats = st.clone() if stats is None else stats + st
+        n += 1
+    if n == 0:
+        raise ValueError("train_epoch_prefilter: no group")
+    loss_sum, counted, hits = torch.cat([total.reshape(1), stats.reshape(2)]).tolist()          # the one host read
+    return loss_sum / n, (hits / counted if counted else 0.0)
 
 
 def eval_epoch(model, batches, meter=None):
