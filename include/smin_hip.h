@@ -364,7 +364,9 @@ int smin_compute_ious(void* stream, const float* pm, const float* ps, const floa
  *   greedy NMS: walk the candidates in order, keep one unless its IoU with a kept cell is > nms_thresh; stop after k kept or
  *     when the candidates run out.  nms_thresh >= 1: no suppression (plain top-k over the valid cells).
  * Outputs: idx [B][k][2] (start clip i, end clip j; -1 for empty slots), score [B][k] (0 for empty slots), count [B] (kept).
- * Limits: 1 <= k <= 64, B >= 1, L >= 1, L*L < 2^31.  The result is exact and independent of the internal candidate buffers.
+ * Limits: 1 <= k <= 64, 1 <= B <= 65535 (the sample is the y coordinate of the band select's grid), L >= 1, L*L < 2^31; the same
+ * holds for smin_compute_ious_nms and rule 1 of the epoch meter below, which run these launches.  The result is exact and
+ * independent of the internal candidate buffers; fp32 subnormal scores are kept (no flush to zero) and ordered like any other.
  * No host synchronisation (capturable in a HIP graph).  ws: device scratch of at least the _ws_bytes size (0 = arguments rejected). */
 size_t smin_top_moments_ws_bytes(int B, int L, int k);
 int smin_top_moments(void* stream, const float* pm, const float* ps, const float* pe, const uint8_t* mm, int B, int L, int k,

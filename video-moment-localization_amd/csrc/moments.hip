@@ -11,7 +11,7 @@
 //   greedy NMS  walk the candidates in order; keep one unless its IoU with an already kept cell is > nms_thresh (fp32);
 //               stop after k kept or when the candidates run out.  nms_thresh >= 1: no suppression (plain top-k of the valid cells).
 //   empty slots index -1 and score 0; count[b] = number kept.
-//   limits      1 <= k <= 64, B >= 1, L >= 1 with L*L < 2^31.
+//   limits      1 <= k <= 64, 1 <= B <= 65535 (launch 1 puts the sample in the grid's second dimension), L >= 1 with L*L < 2^31.
 //
 // Order key: a 64-bit integer, larger = earlier: the score's fp32 bits mapped to an unsigned total order in the high word, and
 // 0x7fffffff - flat index in the low word.  Keys are distinct per cell and never 0 (0 marks "no cell").
@@ -398,7 +398,9 @@ WsLayout ws_layout(int B, int L)
     return w;
 }
 
-bool args_ok(int B, int L, int k) { return B >= 1 && L >= 1 && (long long)L * L < 0x7fffffffLL && k >= 1 && k <= MAX_K; }
+constexpr int MAX_B = 65535;            // the band select puts the sample in the grid's second dimension
+
+bool args_ok(int B, int L, int k) { return B >= 1 && B <= MAX_B && L >= 1 && (long long)L * L < 0x7fffffffLL && k >= 1 && k <= MAX_K; }
 
 int launch_top(hipStream_t st, const float* pm, const float* ps, const float* pe, const uint8_t* mm, int B, int L, int k, float thr,
                long long* idx, float* score, int* count, char* ws)

@@ -12,7 +12,8 @@ Semantics (csrc/moments.hip, include/smin_hip.h), for each sample b:
     (converted to fp32 once); stop after k kept or when the candidates run out.  ``nms_thresh >= 1``: no suppression,
     i.e. plain top-k over the valid cells;
   * empty slots: index -1 and score 0; ``count[b]`` = number kept;
-  * limits: 1 <= k <= 64, B >= 1, L >= 1 with L*L < 2**31.
+  * limits: 1 <= k <= 64, 1 <= B <= 65535 (the band select puts the sample in the grid's second dimension; larger batches go
+    through in chunks, as retrieval's ``max_batch`` does), L >= 1 with L*L < 2**31.
 
 ``top_moments`` is the product entry point (HIP kernels, HIP tensors only, no host synchronisation, capturable in a graph);
 ``top_moments_torch`` is the same function as plain torch + Python on any device, kept under its own name as the restatement
@@ -27,6 +28,7 @@ from ._host import _require_hip, byte_mask, host_array, require_ints
 from ._lib import SminHipError, call, load, ptr, stream
 
 MAX_K = 64
+MAX_B = 65535                       # csrc/moments.hip: the sample index is the band select's grid y coordinate
 MAX_N, MAX_M = 64, 16               # compute_ious(..., nms_thresh=t): at most 64 values of n and 16 thresholds m
 
 
@@ -37,8 +39,8 @@ def _check(pm, ps, pe, moment_mask, k):
     if tuple(ps.shape) != (B, L) or tuple(pe.shape) != (B, L) or tuple(moment_mask.shape) != (B, L, L):
         raise ValueError(f"ps / pe must be (B, L) = {(B, L)} and moment_mask (B, L, L); got {tuple(ps.shape)}, {tuple(pe.shape)}, "
                          f"{tuple(moment_mask.shape)}")
-    if B < 1 or L < 1 or L * L >= 2 ** 31:
-        raise ValueError(f"top_moments needs B >= 1 and 1 <= L with L*L < 2**31 (B={B}, L={L})")
+    if not 1 <= B <= MAX_B or L < 1 or L * L >= 2 ** 31:
+        raise ValueError(f"top_moments needs 1 <= B <= {MAX_B} and 1 <= L with L*L < 2**31 (B={B}, L={L})")
     if not (isinstance(k, int) and 1 <= k <= MAX_K):
         raise ValueError(f"top_moments needs an integer 1 <= k <= {MAX_K} (got {k!r})")
     return B, L
