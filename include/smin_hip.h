@@ -1158,6 +1158,64 @@ int smin_prefilter_maps_bwd(void* stream, const float* dpm0, const float* dps0, 
  * Rejection.  A nonzero status before the launch, the outputs untouched, for a size out of range or a NULL pointer. */
 int smin_prefilter_select(void* stream, const int32_t* pair_rank, int Q, int V, int M, int32_t* sel_video, int32_t* sel_query);
 
+/* ---- the corpus-wide first-stage cut over shards (csrc/prefilter_fold.hip): smin_prefilter_select's cut of one bank
+ * of all the videos, kept as a running best-M per query while the corpus' shards stream past.  wave64, workgroups of 256; no atomics,
+ * plain stores; no host read; no allocation; capturable.
+ *
+ * The order of the cut, a strict total order over a query's videos by their GLOBAL id: candidates (cells > 0) first, among them the
+ *   higher first-stage score first by smin_video_rank's comparison (-0 counts as +0; ties go to the lower video); then the
+ *   non-candidates in ascending video.  Its first Ms elements are what smin_video_rank + smin_prefilter_select keep of one bank.
+ *
+ * smin_prefilter_fold: folds one shard into the running state; one launch, one workgroup per query, no workspace.
+ * State, read and updated in place, M slots per query:  slot_score [Q][M] fp32, slot_cells [Q][M] fp32 (0: no candidate), slot_video
+ *   [Q][M] int32 the global id, -1 for an empty slot.  Invariant: the filled slots are 0 .. n_old - 1 with n_old = min(M, seen).
+ * Inputs.  score [Q][Vs], cells [Q][Vs] fp32: smin_prefilter_scores' of the shard; seen: the global id of the shard's video 0 (the
+ *   number of videos folded so far); n_old: min(M, seen), stated by the caller and checked.
+ * The fold.  n_new = min(M, seen + Vs).  Every element of the union of the n_old old slots and the Vs shard videos gets a 64-bit order
+ *   word (distinct ids, distinct words); the words go through LDS 2048 at a time and an element's place is the number of words larger
+ *   than its own: no sort, any Vs.  An element stays or is admitted where place < n_new.
+ * Slots.  An incumbent that stays keeps its slot: nothing of it is written.  The evicted slots and the empty slots n_old .. n_new - 1,
+ *   in ascending slot order, receive the admitted shard videos in ascending local index (two scans with running counts: ballot and
+ *   popcount, integers only).  Each slot has one writer.
+ * Outputs.  The state: a slot that receives a video gets its score and cells (copied bit for bit) and seen + its local index; slots
+ *   >= n_new are written empty (score 0, cells 0, video -1); an incumbent that stays is left alone.  copy_src [Q][M] int32, every
+ *   element written: the local index in the shard of the video the slot must receive, -1 to leave the slot alone.
+ *   A state that breaks the invariant stays in bounds; its content is then unspecified.
+ * Limits.  Q >= 1, 1 <= Vs <= 0x7fff0000, 1 <= M <= 2048, seen >= 0, seen + Vs <= 2^31 - 1.  LDS per workgroup: 42 KB (the slots' words
+ *   16 KB, a tile of the shard's 16 KB, the free-slot list 8 KB, the eviction flags 2 KB).  score and cells must not overlap the state
+ *   or copy_src.  Work per query: (n_old + Vs)^2 / 256 word comparisons per thread.
+ * Determinism.  The same bits every run: places are counts, each slot has one writer.
+ * Rejection.  A nonzero status before the launch, the state and copy_src untouched, for a size out of range (M > 2048 among them),
+ *   n_old != min(M, seen), seen + Vs past int32 or a NULL pointer. */
+int smin_prefilter_fold(void* stream, const float* score, const float* cells, int Q, int Vs, int M, int seen, int n_old, float* slot_score,
+                        float* slot_cells, int32_t* slot_video, int32_t* copy_src);
+
+/* smin_survivors_admit: the payload of a fold -- copies the admitted videos of a shard's bank into the bank of survivors; one launch,
+ * one workgroup per (row, 32 KB of its fv row).
+ * Inputs.  copy_src [R] int32: smin_prefilter_fold's, R = Q M rows (row q M + slot); fv [Vs][T][D] fp32, video_mask [Vs][T], length_mask
+ *   [Vs][L], moment_mask [Vs][L][L]: the shard's bank, one byte per mask entry.
+ * Outputs.  For every row with 0 <= copy_src[row] < Vs: out_fv [R][T][D] row = the video's fv row (T D floats as float4),
+ *   out_video_mask [R][T], out_length_mask [R][L], out_moment_mask [R][L][L] rows = its masks, byte by byte (L L need not be a multiple
+ *   of 4), all bit for bit.  Every other row (copy_src -1) is left alone.
+ * Limits.  R >= 1, Vs >= 1, T >= 1, 1 <= L <= 4096, D >= 4 with D % 4 == 0, T D / 4 <= 2048 * 65535; fv and out_fv 16-byte aligned.  The
+ *   outputs must not overlap the inputs or each other.  Determinism.  Copies: the same bits every run.
+ * Rejection.  A nonzero status before the launch, the outputs untouched, for a size out of range, a NULL pointer or a misaligned fv. */
+int smin_survivors_admit(void* stream, const int32_t* copy_src, const float* fv, const uint8_t* video_mask, const uint8_t* length_mask,
+                         const uint8_t* moment_mask, int R, int Vs, int T, int L, int D, float* out_fv, uint8_t* out_video_mask,
+                         uint8_t* out_length_mask, uint8_t* out_moment_mask);
+
+/* smin_prefilter_gt_rank: the first-stage rank of each query's own video over the whole corpus, O(V) per query (smin_video_rank over
+ * the corpus would be O(V^2)); one launch, one workgroup per query.
+ * Inputs.  score [Q][V] fp32: the shards' first-stage scores concatenated; cand [V]: one byte per video, nonzero = it has a valid cell
+ *   (a video's cell count does not depend on the query); gt_video [Q] int32 or NULL: each query's own video.
+ * Output, every element written.  gt_rank [Q] int32: the number of candidates ahead of gt_video[q] in the order above -- the gt_rank
+ *   smin_video_rank gives over the (Q, V) scores --; -1 where gt_video is NULL, out of [0, V) (it forms no address before that check)
+ *   or no candidate.  Counts per thread (v = t, t + 256, ...) are added over the wave and then the four waves: integers, any order
+ *   gives the same value.
+ * Limits.  Q >= 1, 1 <= V <= 0x7fff0000.  Rejection.  A nonzero status before the launch, gt_rank untouched, for a size out of range or
+ *   a NULL pointer other than gt_video. */
+int smin_prefilter_gt_rank(void* stream, const float* score, const uint8_t* cand, const int32_t* gt_video, int Q, int V, int32_t* gt_rank);
+
 /* ---- stand-alone fp32 MFMA GEMM  C[M][N] = A[M][K] * B[N][K]^T  (used by tests and bench.py's
  * roofline probe; same engine as every contraction above). */
 int smin_gemm_nt(void* stream, const float* A, const float* Bm, float* Cm, int M, int N, int K);

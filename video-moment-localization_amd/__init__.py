@@ -22,7 +22,8 @@ from .training import search_shards_weighted, search_window_shards_weighted  # n
 from .training import test_model_corpus_weighted_shards, test_model_corpus_window_shards_weighted  # noqa: F401
 from .training import pair_targets, train_epoch_pairs, train_epoch_mined, pair_rank_loss, pair_rank_loss_torch  # noqa: F401
 from .training import prefilter_rank_loss, train_epoch_prefilter  # noqa: F401
-from .retrieval import PairPlan, WindowBank  # noqa: F401
+from .training import search_shards_prefiltered, test_model_corpus_prefiltered_shards  # noqa: F401
+from .retrieval import PairPlan, SurvivorBank, WindowBank  # noqa: F401
 from .meter import EpochMeter, EpochMeterTorch, CorpusMeter, CorpusMeterTorch, VideoRankMeter  # noqa: F401
 from .optim import FusedAdam, FusedAdamTorch, RowSparseAdam, RowSparseAdamTorch  # noqa: F401
 from .labels import build_targets  # noqa: F401
@@ -32,6 +33,7 @@ from .moments import corpus_topk, corpus_topk_torch, merge_search, merge_search_
 from .moments import pair_pool, pair_pool_torch, group_pool, group_pool_torch, rank_videos, rank_videos_torch  # noqa: F401
 from .moments import reweight_moments, reweight_moments_torch  # noqa: F401
 from .moments import prefilter_scores, prefilter_scores_torch, prefilter_select, prefilter_select_torch, prefilter_maps  # noqa: F401
+from .moments import prefilter_fold, prefilter_fold_torch, survivors_admit, survivors_admit_torch, prefilter_gt_rank, prefilter_gt_rank_torch  # noqa: F401
 from .moments import merge_search_weighted, merge_search_weighted_torch  # noqa: F401
 from .moments import merge_search_windows_weighted, merge_search_windows_weighted_torch  # noqa: F401
 from .moments import span_ious, span_ious_torch, compute_span_ious, compute_span_ious_torch  # noqa: F401

@@ -1015,6 +1015,171 @@ def prefilter_select_torch(pair_rank, M):
     return video, query
 
 
+# ---------------------------------------------------------------- the corpus-wide first-stage cut over shards
+PREFILTER_FOLD_MAX_M = 2048         # csrc/prefilter_fold.hip: a query's slots and their free list stay in LDS
+
+
+def _fold_check(what, slot_score, slot_cells, slot_video, score, cells, seen):
+    if slot_score.dim() != 2 or slot_score.shape[0] < 1 or tuple(slot_cells.shape) != tuple(slot_score.shape) or tuple(slot_video.shape) != tuple(slot_score.shape):
+        raise ValueError(f"{what}: slot_score, slot_cells and slot_video must be (Q, M) with Q >= 1; got {tuple(slot_score.shape)}, "
+                         f"{tuple(slot_cells.shape)}, {tuple(slot_video.shape)}")
+    Q, M = slot_score.shape
+    if score.dim() != 2 or score.shape[0] != Q or score.shape[1] < 1 or tuple(cells.shape) != tuple(score.shape):
+        raise ValueError(f"{what}: score and cells must be (Q, Vs) = ({Q}, Vs >= 1); got {tuple(score.shape)} and {tuple(cells.shape)}")
+    Vs = score.shape[1]
+    if Vs > 0x7fff0000:
+        raise ValueError(f"{what}: {Vs} videos in one shard exceed the int32 video ids")
+    require_ints(what, ("M", M, 1, PREFILTER_FOLD_MAX_M), ("seen", seen, 0, 2 ** 31 - 1 - Vs))
+    return Q, M, Vs, min(M, int(seen)), min(M, int(seen) + Vs)
+
+
+def prefilter_fold(slot_score, slot_cells, slot_video, score, cells, seen, copy_src=None):
+    """One shard folded into the running best-M of every query (include/smin_hip.h, smin_prefilter_fold): the state ``slot_score`` /
+    ``slot_cells (Q, M)`` float32 and ``slot_video (Q, M)`` int32 (the global id, -1 for an empty slot; the filled slots are ``0 ..
+    min(M, seen) - 1``) is UPDATED IN PLACE with the shard's ``score`` / ``cells (Q, Vs)`` of ``prefilter_scores``; ``seen`` (a host
+    int) is the global id of the shard's video 0.  Afterwards the filled slots hold the first ``min(M, seen + Vs)`` of all the videos
+    seen in the order of ``search(prefilter=M)``'s cut: candidates (cells > 0) by higher score, ties to the lower video, then the
+    non-candidates by ascending video.  Incumbents that stay keep their slots; the evicted and the empty slots, ascending, receive the
+    admitted shard videos in ascending local index.  Returns ``copy_src (Q, M)`` int32 (written into the tensor given, if any): the
+    local index of the video a slot must receive (``survivors_admit`` copies it), -1 to leave the slot alone.  HIP tensors only; one
+    launch; no host synchronisation."""
+    _require_hip(slot_score, "prefilter_fold")
+    Q, M, Vs, n_old, _ = _fold_check("prefilter_fold", slot_score, slot_cells, slot_video, score, cells, seen)
+    state = (slot_score, slot_cells, slot_video) + (() if copy_src is None else (copy_src,))
+    if any(not s.is_contiguous() for s in state) or slot_score.dtype != torch.float32 or slot_cells.dtype != torch.float32 \
+            or slot_video.dtype != torch.int32 or (copy_src is not None and (copy_src.dtype != torch.int32 or tuple(copy_src.shape) != (Q, M))):
+        raise ValueError("prefilter_fold: the state is updated in place: contiguous float32 slot_score / slot_cells and int32 slot_video / "
+                         "copy_src (Q, M)")
+    dev = slot_score.device
+    if copy_src is None:
+        copy_src = torch.empty((Q, M), dtype=torch.int32, device=dev)
+    s_, c_ = score.detach().float().contiguous(), cells.detach().float().contiguous()
+    with torch.cuda.device(dev):
+        call("smin_prefilter_fold", stream(), ptr(s_), ptr(c_), Q, Vs, M, int(seen), n_old, ptr(slot_score), ptr(slot_cells), ptr(slot_video),
+             ptr(copy_src))
+    return copy_src
+
+
+def prefilter_fold_torch(slot_score, slot_cells, slot_video, score, cells, seen):
+    """``prefilter_fold`` as plain Python on any device, out of place: ``(slot_score, slot_cells, slot_video, copy_src)`` after the shard,
+    the scores in the dtype of ``slot_score``.  The tests' restatement, nothing routes here.  Reads the host."""
+    Q, M, Vs, n_old, n_new = _fold_check("prefilter_fold_torch", slot_score, slot_cells, slot_video, score, cells, seen)
+    seen = int(seen)
+    out_s, out_c, out_v = slot_score.clone(), slot_cells.clone(), slot_video.clone()
+    copy_src = torch.full((Q, M), -1, dtype=torch.int32, device=slot_score.device)
+    os_, oc, ov, s, c = slot_score.tolist(), slot_cells.tolist(), slot_video.tolist(), score.tolist(), cells.tolist()
+    # the order: candidates first, higher score first (-0 + 0 = +0), then the lower video; non-candidates by ascending video
+    key = lambda sc, ce, vid: (0, -(sc + 0.0), vid) if ce > 0 else (1, 0.0, vid)
+    for q in range(Q):
+        union = [(key(os_[q][j], oc[q][j], ov[q][j]), 0, j) for j in range(n_old)] + [(key(s[q][v], c[q][v], seen + v), 1, v) for v in range(Vs)]
+        first = sorted(union)[:n_new]
+        stay = {j for _, new, j in first if not new}
+        admitted = sorted(v for _, new, v in first if new)
+        free = [j for j in range(n_new) if j >= n_old or j not in stay]
+        for j, v in zip(free, admitted):
+            out_s[q, j], out_c[q, j], out_v[q, j], copy_src[q, j] = score[q, v].to(out_s.dtype), cells[q, v].to(out_c.dtype), seen + v, v
+        if n_new < M:
+            out_s[q, n_new:], out_c[q, n_new:], out_v[q, n_new:] = 0, 0, -1
+    return out_s, out_c, out_v, copy_src
+
+
+_ADMIT_NAMES = ("fv", "video_mask", "length_mask", "moment_mask")
+
+
+def _admit_check(what, copy_src, shard, out):
+    if len(shard) != 4 or len(out) != 4:
+        raise ValueError(f"{what}: shard and out are (fv, video_mask, length_mask, moment_mask)")
+    fv, lm = shard[0], shard[2]
+    if fv.dim() != 3 or fv.shape[0] < 1 or fv.shape[2] % 4 != 0 or fv.shape[2] < 4 or lm.dim() != 2:
+        raise ValueError(f"{what}: the shard's fv must be (Vs, T, D) with Vs >= 1 and D % 4 == 0 and its length_mask (Vs, L); got "
+                         f"{tuple(fv.shape)} and {tuple(lm.shape)}")
+    Vs, T, D = fv.shape
+    L, R = lm.shape[1], copy_src.numel()
+    if R < 1 or R >= 2 ** 31:
+        raise ValueError(f"{what}: copy_src must hold between 1 and 2**31 - 1 rows (got {R})")
+    for name, src, dst, tail in zip(_ADMIT_NAMES, shard, out, ((T, D), (T,), (L,), (L, L))):
+        n = int(np.prod(tail))
+        if src.shape[0] != Vs or src.numel() != Vs * n or dst.numel() != R * n or src.dtype != dst.dtype:
+            raise ValueError(f"{what}: {name} must hold {tail} per video, {Vs} videos in the shard and {R} rows in the survivors, in one "
+                             f"dtype; got {tuple(src.shape)} {src.dtype} and {tuple(dst.shape)} {dst.dtype}")
+    return R, Vs, T, L, D
+
+
+def survivors_admit(copy_src, shard, out):
+    """The payload of a fold (include/smin_hip.h, smin_survivors_admit): for every row r of ``copy_src`` (any shape, R elements, row ``q *
+    M + slot``) with ``copy_src[r] >= 0``, row r of ``out`` -- the survivors' ``(fv (R, T, D), video_mask (R, T[, 1]), length_mask (R,
+    L), moment_mask (R, L, L))``, updated IN PLACE -- becomes video ``copy_src[r]`` of ``shard``, the same four tensors of the
+    shard's bank (float32 fv, one byte per mask entry), bit for bit.  Rows with -1 are not touched.  HIP tensors only; one launch; no
+    host synchronisation."""
+    _require_hip(copy_src, "survivors_admit")
+    R, Vs, T, L, D = _admit_check("survivors_admit", copy_src, shard, out)
+    if shard[0].dtype != torch.float32 or any(m.dtype not in (torch.bool, torch.uint8) for m in shard[1:]):
+        raise ValueError("survivors_admit: float32 fv and bool / uint8 masks (the banks' own)")
+    if any(not t.is_contiguous() for t in out) or copy_src.dtype != torch.int32 or not copy_src.is_contiguous():
+        raise ValueError("survivors_admit: the survivors are updated in place: contiguous tensors, and a contiguous int32 copy_src")
+    src = [t.detach().contiguous() for t in shard]
+    with torch.cuda.device(copy_src.device):
+        call("smin_survivors_admit", stream(), ptr(copy_src), *[ptr(t) for t in src], R, Vs, T, L, D, *[ptr(t) for t in out])
+    return out
+
+
+def survivors_admit_torch(copy_src, shard, out):
+    """``survivors_admit`` as plain torch ops on any device, out of place: the four tensors of ``out`` after the copy, each in its own
+    dtype.  The tests' restatement, nothing routes here."""
+    _admit_check("survivors_admit_torch", copy_src, shard, out)
+    src = copy_src.reshape(-1).to(torch.int64)
+    take = src >= 0
+    res = []
+    for s, d in zip(shard, out):
+        rows = s.reshape(s.shape[0], -1)[src.clamp_min(0)]
+        res.append(torch.where(take.unsqueeze(1), rows, d.reshape(src.shape[0], -1)).reshape(d.shape))
+    return tuple(res)
+
+
+def _gt_rank_check(what, score, cand, gt_video):
+    if score.dim() != 2 or score.shape[0] < 1 or score.shape[1] < 1 or tuple(cand.shape) != (score.shape[1],):
+        raise ValueError(f"{what}: score must be (Q, V) with Q, V >= 1 and cand (V,); got {tuple(score.shape)} and {tuple(cand.shape)}")
+    Q, V = score.shape
+    if V > 0x7fff0000:
+        raise ValueError(f"{what}: {V} videos exceed the int32 video ids")
+    if gt_video is not None and tuple(gt_video.shape) != (Q,):
+        raise ValueError(f"{what}: gt_video must be (Q,) = ({Q},) (got {tuple(gt_video.shape)})")
+    return Q, V
+
+
+def prefilter_gt_rank(score, cand, gt_video=None):
+    """The first-stage rank of each query's own video over the whole corpus (include/smin_hip.h, smin_prefilter_gt_rank): ``score (Q, V)``
+    the first-stage scores of all the videos, ``cand (V,)`` nonzero where a video has a valid cell, ``gt_video (Q,)`` int tensor or
+    None.  Returns ``gt_rank (Q,)`` int32: the number of candidates ahead of the query's own video (higher score, or an equal score and
+    a lower video) -- ``prefilter_videos(...)["gt_rank"]`` on one bank of all the videos, in O(V) per query --; -1 without gt_video,
+    for one out of range or for a non-candidate.  HIP tensors only; one launch; no host synchronisation."""
+    _require_hip(score, "prefilter_gt_rank")
+    Q, V = _gt_rank_check("prefilter_gt_rank", score, cand, gt_video)
+    s_, c_ = score.detach().float().contiguous(), byte_mask(cand)
+    gt = None if gt_video is None else gt_video.to(torch.int32).contiguous()
+    out = torch.empty((Q,), dtype=torch.int32, device=score.device)
+    with torch.cuda.device(score.device):
+        call("smin_prefilter_gt_rank", stream(), ptr(s_), ptr(c_), ptr(gt), Q, V, ptr(out))
+    return out
+
+
+def prefilter_gt_rank_torch(score, cand, gt_video=None):
+    """``prefilter_gt_rank`` as plain torch ops on any device, comparing in the dtype of ``score``: the tests' restatement."""
+    Q, V = _gt_rank_check("prefilter_gt_rank_torch", score, cand, gt_video)
+    dev = score.device
+    if gt_video is None:
+        return torch.full((Q,), -1, dtype=torch.int32, device=dev)
+    gt = gt_video.to(torch.int64)
+    inside = (gt >= 0) & (gt < V)
+    g = torch.where(inside, gt, torch.zeros_like(gt)).unsqueeze(1)
+    c = (cand != 0).unsqueeze(0)
+    own = score.detach().gather(1, g)
+    video = torch.arange(V, device=dev).unsqueeze(0)
+    ahead = c & ((score.detach() > own) | ((score.detach() == own) & (video < g)))
+    ok = inside & c.expand(Q, V).gather(1, g).squeeze(1)
+    return torch.where(ok, ahead.sum(dim=1), torch.full_like(gt, -1)).to(torch.int32)
+
+
 def search_times(video, idx, duration, L):
     """``times (Q, k, 2)`` of a ranked corpus list: top_moments' formula on each moment's own video, ``(i * duration[video] / L,
     (j + 1) * duration[video] / L)`` in fp32, NaN for empty slots.  ``duration``: the (V,) seconds of the videos ``video`` indexes.

@@ -1,6 +1,7 @@
 """Retrieval on top of SMIN's scores, which the reference does not have: the best moments of a sample (``localize``), of videos of
 any length over overlapping windows (``localize_windows``) and of a corpus encoded once (``encode_videos`` / ``encode_queries`` ->
-``score_pairs`` / ``search``, pruned by a first-stage score from the banks alone with ``prefilter_videos`` / ``search(prefilter=M)``; a corpus
+``score_pairs`` / ``search``, pruned by a first-stage score from the banks alone with ``prefilter_videos`` / ``search(prefilter=M)`` and, for a corpus that comes in
+shards, ``new_survivors`` / ``fold_survivors`` / ``search_survivors``; a corpus
 of videos of any length: ``encode_windows`` -> ``search_windows``), and the training counterpart
 of ``score_pairs``, ``forward_pairs`` over (video, query) pairs that share their
 encoders: host code around the library's kernels and the model's own ``score`` / ``forward``, which ``modules.SMIN`` inherits
@@ -12,7 +13,7 @@ from . import _lib
 from ._host import _AttnMaps, byte_mask, host_array, known_cells, query_mask_rows, require_hip_tensors, require_ints
 from .feeder import build_masks_hip, cell_count
 from .functional import attn_maps_gather
-from .moments import (MAX_K, _pair_pool_into, _temperature, _top_moments_into, _video_weight, corpus_span_topk, corpus_span_topk_torch, corpus_topk,
+from .moments import (MAX_K, PREFILTER_FOLD_MAX_M, prefilter_fold, prefilter_gt_rank, survivors_admit, _pair_pool_into, _temperature, _top_moments_into, _video_weight, corpus_span_topk, corpus_span_topk_torch, corpus_topk,
                       corpus_topk_torch, group_pool, merge_window_moments, merge_window_moments_torch, mine_pairs, prefilter_maps, prefilter_scores, prefilter_select,
                       rank_videos, reweight_moments,
                       reweight_moments_torch, search_times, top_moments, top_moments_torch, window_times)
@@ -86,6 +87,57 @@ class WindowBank(VideoBank):
     @property
     def plan_features(self):
         return self._plan_features if self.video_features is None else self.video_features
+
+
+class SurvivorBank(VideoBank):
+    """The running first-stage cut of a corpus that comes in shards (SMIN.new_survivors / fold_survivors / search_survivors;
+    INTEGRATION.md 3x): for each of Q queries the best M videos seen so far by the first-stage score, WITH what the full model needs of
+    them -- a VideoBank of ``Q * M`` rows, row ``q * M + slot``: ``fv (Q M, T, D)`` and the three masks, copied from each shard's bank
+    before it is dropped.  A video kept by several queries is stored once per query.  The rows are allocated by the first fold (they
+    take the shard bank's shapes and mask dtypes); before it ``fv`` and the masks are None.
+
+    Beside the rows: the slot state of smin_prefilter_fold -- ``slot_score`` / ``slot_cells (Q, M)`` float32, ``slot_video (Q, M)``
+    int32 (the global video id in shard order, -1 for an empty slot; the filled slots are ``0 .. min(M, seen) - 1``) and ``copy_src (Q,
+    M)``, the last fold's --, ``tau``, ``seen`` (the videos folded so far, a host int), the kept first-stage scores ``score (Q, seen)``
+    and the candidate flags ``candidate (seen,)`` (a video with a valid cell), both concatenated from the shards on demand.
+    ``cell_count`` is every video's valid-cell count where all the shards' ``cell_counts`` were one value, else None.
+    ``video_features`` is None and ``plan_features`` an empty ``(0, T, Din)`` tensor, as WindowBank gives on the one-node path.
+
+    Memory: ``Q * M * (4 T D + T + L + L * L)`` bytes of rows, fixed by (Q, M), plus ``4 * Q * V`` bytes of kept scores (and V flag
+    bytes) -- the only part that grows with the corpus.  A snapshot of the parameters, as every bank."""
+
+    def __init__(self, Q, M, tau, device, plan_features):
+        super().__init__(None, None, None, None, None, ())
+        self.Q, self.M, self.tau, self.seen = int(Q), int(M), tau, 0
+        self._device, self._plan_features = torch.device(device), plan_features
+        self.slot_score = torch.zeros((Q, M), dtype=torch.float32, device=device)
+        self.slot_cells = torch.zeros((Q, M), dtype=torch.float32, device=device)
+        self.slot_video = torch.full((Q, M), -1, dtype=torch.int32, device=device)
+        self.copy_src = torch.full((Q, M), -1, dtype=torch.int32, device=device)
+        self.shard_scores, self.shard_candidates, self.cell_values = [], [], set()
+
+    def __len__(self):
+        return self.Q * self.M
+
+    @property
+    def device(self):
+        return self._device
+
+    @property
+    def plan_features(self):
+        return self._plan_features
+
+    @property
+    def score(self):
+        return torch.cat(self.shard_scores, dim=1)
+
+    @property
+    def candidate(self):
+        return torch.cat(self.shard_candidates)
+
+    @property
+    def cell_count(self):
+        return next(iter(self.cell_values)) if len(self.cell_values) == 1 else None
 
 
 class QueryBank:
@@ -608,10 +660,8 @@ class _Retrieval:
             raise ValueError("score_pairs: a bank was encoded while the module was off the one-node path (SMIN._plan); encode it again")
         if Q * max(V, W) > 0x7fff0000:
             raise ValueError(f"{what}: {Q} queries over {max(V, W)} videos / windows exceed the int32 pair lists")
-        lo, D = self.localization, videos.fv.shape[2]
-        heads = (lo.conv_layer_pm, lo.conv_layer_ps, lo.conv_layer_pe)
         with torch.no_grad(), torch.cuda.device(dev):
-            w, b = torch.stack([h.weight.reshape(D) for h in heads]), torch.cat([h.bias.reshape(1) for h in heads])
+            w, b = self._first_stage_heads(videos.fv.shape[2])
             score, pool, cells = prefilter_scores(videos.fv, queries.fs, w, b, videos.length_mask, videos.moment_mask, self.T, self.L, self.C, tau)
             if windowed:
                 first = torch.arange(Q, device=dev).unsqueeze(1) * W + videos.video_ptr_d[:-1].unsqueeze(0)           # group q * V + v begins here
@@ -695,20 +745,138 @@ class _Retrieval:
         vi_d, qi_d, Ms = pf["video_index"], pf["query_index"], pf["video"].shape[1]
         counts = videos.cell_counts
         cell = counts[0] if all(c == counts[0] for c in counts) else None
+        r = self._search_survivor_pairs(videos, queries, vi_d, vi_d, qi_d, Ms, cell, int(k), int(k_video), nms_thresh, max_batch,
+                                        (alpha, cut, tau, n_videos, gt) if video_level else None)
+        r.update(prefilter_video=pf["video"], prefilter_score=pf["score"], prefilter_gt_rank=pf["gt_rank"])
+        return self._search_result(r, duration, self.L)
+
+    def _search_survivor_pairs(self, videos, queries, rows_d, video_d, qi_d, Ms, cell, k, k_video, nms_thresh, max_batch, video_level):
+        """The tail ``search(prefilter=M)`` and ``search_survivors`` share: the full model over the Q * Ms surviving pairs, sorted by (query,
+        video), then the ranking.  ``rows_d (Q Ms,)`` int32: each pair's row of the bank ``videos``; ``video_d``: its video id as the
+        ranking reads it (ties go to the lower video) and the result names it -- the same tensor for a VideoBank, the global ids for a
+        SurvivorBank --; ``cell`` as ``_pair_moments_device`` takes it; ``video_level``: None, or ``_video_options``' tuple (INTEGRATION.md
+        3t).  No host read."""
+        Q, dev = len(queries), videos.device
         with torch.no_grad(), torch.cuda.device(dev):
             pp_d = torch.arange(Q + 1, dtype=torch.int32, device=dev) * Ms
-            if video_level:
+            if video_level is not None:
+                alpha, cut, tau, n_videos, gt = video_level
                 gt_d = torch.from_numpy(gt.astype(np.int32)).pin_memory().to(dev, non_blocking=True) if gt.size else None
                 pools = _pool_buffers(Q * Ms, dev)
-                idx, score, count = self._pair_moments_device(videos, queries, vi_d, qi_d, cell, int(k_video), nms_thresh, max_batch, pools=(tau,) + pools)
-                vr = rank_videos(pools[0], pools[2], vi_d, pp_d, n=n_videos, alpha=alpha, gt_video=gt_d)
+                idx, score, count = self._pair_moments_device(videos, queries, rows_d, qi_d, cell, k_video, nms_thresh, max_batch, pools=(tau,) + pools)
+                vr = rank_videos(pools[0], pools[2], video_d, pp_d, n=n_videos, alpha=alpha, gt_video=gt_d)
                 w_score, w_count = reweight_moments(score, count, vr["pair_rank"], vr["weight"], cut)
-                r = corpus_topk(w_score, idx, w_count, vi_d, pp_d, k=int(k))
+                r = corpus_topk(w_score, idx, w_count, video_d, pp_d, k=k)
                 r.update(video_rank=vr["video"], video_score=vr["score"], video_count=vr["count"], gt_rank=vr["gt_rank"])
             else:
-                idx, score, count = self._pair_moments_device(videos, queries, vi_d, qi_d, cell, int(k_video), nms_thresh, max_batch)
-                r = corpus_topk(score, idx, count, vi_d, pp_d, k=int(k))
-        r.update(prefilter_video=pf["video"], prefilter_score=pf["score"], prefilter_gt_rank=pf["gt_rank"])
+                idx, score, count = self._pair_moments_device(videos, queries, rows_d, qi_d, cell, k_video, nms_thresh, max_batch)
+                r = corpus_topk(score, idx, count, video_d, pp_d, k=k)
+        return r
+
+    # ---------------------------------------------------------------- the first-stage cut over a corpus in shards (INTEGRATION.md 3x)
+    def _first_stage_heads(self, D):
+        """The three score heads stacked as prefilter_scores reads them: ``w (3, D)``, ``b (3,)`` in the order (pm, ps, pe)."""
+        lo = self.localization
+        heads = (lo.conv_layer_pm, lo.conv_layer_ps, lo.conv_layer_pe)
+        return torch.stack([h.weight.reshape(D) for h in heads]), torch.cat([h.bias.reshape(1) for h in heads])
+
+    def new_survivors(self, queries, M, tau=0.1):
+        """An empty SurvivorBank for the Q queries of a QueryBank: each query's best ``M`` videos by the first-stage score at
+        temperature ``tau``, to be filled shard by shard with ``fold_survivors`` and searched with ``search_survivors``."""
+        what = "new_survivors"
+        if not isinstance(queries, QueryBank):
+            raise TypeError(f"{what}: queries is a QueryBank (encode_queries)")
+        require_ints(what, ("M", M, 1, PREFILTER_FOLD_MAX_M))
+        tau = _temperature(what, tau)
+        require_hip_tensors(what, dict(queries=queries.query_features), must="hold HIP tensors")
+        dev = queries.query_features.device
+        probe = torch.empty((0, self.T, self.input_video_dim), dtype=torch.float32, device=dev)
+        return SurvivorBank(len(queries), int(M), tau, dev, probe)
+
+    def fold_survivors(self, survivors, videos, queries):
+        """One shard of the corpus folded into a SurvivorBank: on the shard's VideoBank ``videos``, ``prefilter_scores`` (tiled as
+        prefilter_videos tiles it; every (query, video) is computed alone, so these are the bits one bank of all the videos gives),
+        ``prefilter_fold`` -- the running cut: after the call each query's slots hold its best ``min(M, videos seen)`` of ALL the videos
+        seen, in the order of search(prefilter=M)'s cut -- and ``survivors_admit``, which copies the admitted videos' fv rows and masks
+        into the survivors' rows; the shard's bank may then be dropped.  The shard's videos get the global ids ``survivors.seen ..``.
+        ValueError for a WindowBank (or a SurvivorBank), a bank encoded off the one-node path (score_pairs' message), another number of
+        queries than the survivors were made for or a bank of other shapes than the earlier shards'.  Under torch.no_grad(); reads
+        nothing back.  Returns ``survivors``."""
+        what = "fold_survivors"
+        if not isinstance(survivors, SurvivorBank):
+            raise TypeError(f"{what}: survivors is a SurvivorBank (new_survivors)")
+        _require_banks(what, videos, queries)
+        if isinstance(videos, (WindowBank, SurvivorBank)):
+            raise ValueError(f"{what}: a shard is a VideoBank of whole videos (pruning a window search is out of scope: the surviving windows' "
+                             "list has a data-dependent length)")
+        Q, V, M = len(queries), len(videos), survivors.M
+        if Q != survivors.Q:
+            raise ValueError(f"{what}: the survivors were made for Q = {survivors.Q} queries (got {Q})")
+        require_hip_tensors(what, dict(videos=videos.video_mask, queries=queries.query_features), must="hold HIP tensors")
+        if videos.fv is None or queries.fs is None:
+            raise ValueError("score_pairs: a bank was encoded while the module was off the one-node path (SMIN._plan); encode it again")
+        if survivors.seen + V > 0x7fff0000 // max(Q, 1):
+            raise ValueError(f"{what}: {Q} queries over {survivors.seen + V} videos exceed the int32 pair lists")
+        dev, D = videos.device, videos.fv.shape[2]
+        shard = (videos.fv, videos.video_mask, videos.length_mask, videos.moment_mask)
+        if survivors.fv is not None and any(a.shape[1:] != b.shape[1:] or a.dtype != b.dtype
+                                             for a, b in zip(shard, (survivors.fv, survivors.video_mask, survivors.length_mask, survivors.moment_mask))):
+            raise ValueError(f"{what}: the shard's bank differs from the earlier shards' in a shape or a mask's dtype")
+        with torch.no_grad(), torch.cuda.device(dev):
+            if survivors.fv is None:
+                survivors.fv, survivors.video_mask, survivors.length_mask, survivors.moment_mask = (
+                    torch.zeros((Q * M,) + tuple(t.shape[1:]), dtype=t.dtype, device=dev) for t in shard)
+            w, b = self._first_stage_heads(D)
+            score, _, cells = prefilter_scores(videos.fv, queries.fs, w, b, videos.length_mask, videos.moment_mask, self.T, self.L, self.C, survivors.tau)
+            prefilter_fold(survivors.slot_score, survivors.slot_cells, survivors.slot_video, score, cells, survivors.seen, copy_src=survivors.copy_src)
+            survivors_admit(survivors.copy_src, shard, (survivors.fv, survivors.video_mask, survivors.length_mask, survivors.moment_mask))
+            survivors.shard_scores.append(score)
+            survivors.shard_candidates.append(cells[0] > 0)          # (a video's valid cells do not depend on the query)
+        survivors.seen += V
+        survivors.cell_values.update(videos.cell_counts)
+        return survivors
+
+    def search_survivors(self, survivors, queries, k=5, k_video=None, nms_thresh=0.5, duration=None, max_batch=64, video_weight=None,
+                         max_videos=None, n_videos=None, gt_video=None):
+        """``search(prefilter=M)`` of a corpus that came in shards, once its last shard is folded: the full model runs once, over the ``Q *
+        Ms`` pairs of the survivors' rows (``Ms = min(M, videos seen)``).  Each query's filled slots are put in ascending order of
+        their global video (one torch.sort of (Q, Ms) ints), and the tail of search(prefilter=M) runs on them -- the chunk loop over
+        the rows, the video-level options (their ``tau`` is the survivors') and smin_corpus_topk with the global video
+        ids: bit for bit ``search(one bank of all the videos, prefilter=M)``, keys included -- ``prefilter_video (Q, Ms)`` int64
+        ascending, ``prefilter_score (Q, V)`` and ``prefilter_gt_rank (Q,)`` (moments.prefilter_gt_rank over the kept scores: O(V) per
+        query).  ``duration (V,)``, ``gt_video``: over the global ids.  Valid-cell count: when every shard's ``cell_counts`` were one
+        value c, each chunk's count is ``pairs * c`` and nothing is read back; otherwise the node reads it once per chunk."""
+        what = "search_survivors"
+        k_video = k if k_video is None else k_video
+        require_ints(what, ("k", k, 1, MAX_K), ("k_video", k_video, 1, MAX_K), ("max_batch", max_batch, 1, 65535))
+        if not isinstance(survivors, SurvivorBank) or not isinstance(queries, QueryBank):
+            raise TypeError(f"{what}: survivors is a SurvivorBank (new_survivors) and queries a QueryBank (encode_queries)")
+        Q, V, M, dev = len(queries), survivors.seen, survivors.M, survivors.device
+        if Q != survivors.Q:
+            raise ValueError(f"{what}: the survivors were made for Q = {survivors.Q} queries (got {Q})")
+        if V < 1:
+            raise ValueError(f"{what}: no shard has been folded (fold_survivors)")
+        if duration is not None and tuple(duration.shape) != (V,):
+            raise ValueError(f"{what}: duration must be (V,) = ({V},) seconds (got {tuple(duration.shape)})")
+        video_level = None
+        if video_weight is not None or max_videos is not None:
+            video_level = self._video_options(what, video_weight, max_videos, survivors.tau, n_videos, gt_video, k, Q)
+        gt = None
+        if gt_video is not None:
+            gt = host_array(gt_video)
+            if gt.shape[0] != Q:
+                raise ValueError(f"{what}: gt_video must name a video for each of the Q = {Q} queries (got {gt.shape[0]})")
+        Ms = min(M, V)
+        with torch.no_grad(), torch.cuda.device(dev):
+            video, order = torch.sort(survivors.slot_video[:, :Ms], dim=1)
+            rows = (torch.arange(Q, dtype=torch.int32, device=dev) * M).unsqueeze(1) + order.to(torch.int32)
+            qi_d = torch.arange(Q, dtype=torch.int32, device=dev).unsqueeze(1).expand(Q, Ms).reshape(-1)
+            gt_d = None if gt is None else torch.from_numpy(gt.astype(np.int32)).pin_memory().to(dev, non_blocking=True)
+            score = survivors.score
+            gt_rank = prefilter_gt_rank(score, survivors.candidate, gt_d)
+        r = self._search_survivor_pairs(survivors, queries, rows.reshape(-1), video.reshape(-1).contiguous(), qi_d, Ms, survivors.cell_count, int(k),
+                                        int(k_video), nms_thresh, max_batch, video_level)
+        r.update(prefilter_video=video.to(torch.int64), prefilter_score=score, prefilter_gt_rank=gt_rank)
         return self._search_result(r, duration, self.L)
 
     # ---------------------------------------------------------------- video ranking by the pooled pair score (INTEGRATION.md 3t)

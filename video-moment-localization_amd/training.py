@@ -968,3 +968,61 @@ def test_model_corpus_window_shards_weighted(model, shards, queries, gt_video, g
 
 
 test_model_corpus_window_shards_weighted.__test__ = False
+
+
+# ---------------------------------------------------------------- pruned search over a corpus in shards
+def search_shards_prefiltered(model, video_shards, queries, *, prefilter, k=25, k_video=5, nms_thresh=0.5, max_batch=64, video_weight=None,
+                              max_videos=None, tau=0.1, n_videos=None, gt_video=None):
+    """``model.search(prefilter=M)`` over a corpus that comes in shards: ``video_shards`` as ``search_shards`` takes
+    them (a shard may carry ``cell_counts``), ``queries`` a QueryBank.  Per shard: ``encode_videos`` and ``fold_survivors`` -- the
+    first-stage score of the shard's videos and the running corpus-wide cut, whose survivors take their rows along --; one shard's
+    bank is alive at a time.  After the last shard ``search_survivors`` runs the full model once, on each query's best
+    ``min(prefilter, videos)`` videos of the WHOLE corpus: bit for bit ``search(prefilter=M)`` on one bank of all the videos, with
+    ``video_weight`` / ``max_videos`` / ``n_videos`` / ``gt_video`` (global ids in shard order) acting as there; ``tau`` is the first
+    stage's temperature and the video-level one.  Returns ``(result, duration)`` as ``search_shards``; the result also holds
+    ``prefilter_video``, ``prefilter_score`` and ``prefilter_gt_rank``.  Host reads: ``encode_videos``' own per shard without
+    ``cell_counts``; with them, and all of one value, none."""
+    import numpy as np
+    survivors, durations = model.new_survivors(queries, prefilter, tau), []
+    for shard in video_shards:
+        bank = model.encode_videos(shard["video_features"], shard["video_mask"], shard["length_mask"], shard["moment_mask"],
+                                   cell_counts=shard.get("cell_counts"))
+        d = host_array(shard["duration"], np.float64)
+        if d.shape[0] != len(bank):
+            raise ValueError(f"search_shards_prefiltered: duration must cover the shard's {len(bank)} videos (got {d.shape[0]})")
+        model.fold_survivors(survivors, bank, queries)
+        durations.append(d)
+    if not durations:
+        raise ValueError("search_shards_prefiltered: at least one shard of videos")
+    r = model.search_survivors(survivors, queries, k=k, k_video=k_video, nms_thresh=nms_thresh, max_batch=max_batch, video_weight=video_weight,
+                               max_videos=max_videos, n_videos=n_videos, gt_video=gt_video)
+    return r, np.concatenate(durations)
+
+
+def test_model_corpus_prefiltered_shards(model, video_shards, queries, gt_video, gt_times, meter=None, *, prefilter, k=25, k_video=5,
+                                         nms_thresh=0.5, max_batch=64, video_weight=None, max_videos=None, tau=0.1, video_meter=None):
+    """``test_model_corpus`` over a corpus in any number of shards with the first-stage cut: the shards are folded
+    and searched by ``search_shards_prefiltered``, so the full model scores each query's best ``prefilter`` videos of the whole corpus
+    and the metrics are those of ``model.search(one bank of all the videos, prefilter=M)``' list.  Arguments and result as
+    ``test_model_corpus_weighted_shards``; ``video_weight`` / ``max_videos`` both None leave the video-level options off;
+    ``video_meter`` (a meter.VideoRankMeter) is updated with ``prefilter_gt_rank``, the FIRST stage's rank of each query's own video --
+    VR@M of it is the share of queries whose video the cut keeps.  With equal ``cell_counts`` in every shard the loop reads the host
+    once, at ``meter.result()``.  What the pruning loses is not bounded."""
+    what = "test_model_corpus_prefiltered_shards"
+    gv, gt, Q = _corpus_loop_check(what, meter, k, k_video, queries, gt_video, gt_times)
+    model.eval()
+    bank = model.encode_queries(queries["query_features"], queries["query_mask"])
+    dev = queries["query_features"].device
+    if meter is None:
+        from .meter import CorpusMeter
+        meter = CorpusMeter(device=dev)
+    carry, duration = search_shards_prefiltered(model, video_shards, bank, prefilter=prefilter, k=k, k_video=k_video, nms_thresh=nms_thresh,
+                                                max_batch=max_batch, video_weight=video_weight, max_videos=max_videos, tau=tau, gt_video=gv)
+    if Q and (gv.min() < 0 or gv.max() >= duration.shape[0]):
+        raise ValueError(f"{what}: gt_video must lie in [0, {duration.shape[0]}), the videos of the shards")
+    if video_meter is not None:
+        video_meter.update(carry["prefilter_gt_rank"])
+    return _corpus_result(model, carry, meter, gv, gt, duration, dev)
+
+
+test_model_corpus_prefiltered_shards.__test__ = False
