@@ -596,7 +596,7 @@ def test_weighted_window_search_with_the_video_cut(dev, world):
     kw = dict(max_batch=7, **WS.KW)
     r = m.search_windows(wb, qb, video_weight=7.5, max_videos=2, tau=TAU, gt_video=gt, duration=WS.DURATION.to(dev), **kw)
     # the restatement: the same expansion, pools and groups from the public pieces, then search_windows_torch with the kernels' rank and weight
-    _, _, _, p = m._window_search_plan("test", wb, qb, None, 5, 3, 3, 7, None)
+    _, p = m._window_search_plan("test", wb, qb, None, 5, 3, 3, 7, None)
     on = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev).to(torch.int32)
     scorer = lambda wi, wq: m.score_pairs(wb, qb, wi, wq)
     pool, cells = [], []

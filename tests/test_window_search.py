@@ -256,8 +256,8 @@ def test_expansion_plan_by_hand():
     assert [x.tolist() for x in A.window_plan(LENGTHS, WINDOW, STRIDE)] == [STARTS, LENS, VPTR]
     assert wb.cell_counts == tuple(A.cell_count(min(n, T), T, L) for n in LENS) == (36, 36, 36, 36, 36, 15, 36, 36)
     plan = lambda pairs: m._window_search_plan("search_windows", wb, qb, pairs, 5, None, None, 64, None)
-    k, k_video, k_window, p = plan(None)
-    assert (k, k_video, k_window) == (5, 5, 5)
+    o, p = plan(None)
+    assert (o.k, o.k_video, o.k_window) == (5, 5, 5)
     per_video = [[0, 1, 2, 3], [4], [5], [], [6, 7]]
     assert p["qi"].tolist() == [q for q in range(4) for _ in range(5)] and p["vi"].tolist() == [0, 1, 2, 3, 4] * 4
     assert p["wi"].tolist() == [w for _ in range(4) for v in range(5) for w in per_video[v]]
@@ -266,14 +266,14 @@ def test_expansion_plan_by_hand():
     assert p["query_ptr"].tolist() == [0, 5, 10, 15, 20]
     # a shuffled list: query 1 has no pair, query 2 only the video without rows
     pairs = np.array([(3, 4), (0, 2), (3, 0), (2, 3), (0, 0), (0, 4)])
-    _, _, _, p = plan(pairs)
+    _, p = plan(pairs)
     assert p["qi"].tolist() == [0, 0, 0, 2, 3, 3] and p["vi"].tolist() == [0, 2, 4, 3, 0, 4]
     assert p["wi"].tolist() == [0, 1, 2, 3, 5, 6, 7, 0, 1, 2, 3, 6, 7]
     assert p["wq"].tolist() == [0] * 7 + [3] * 6
     assert p["group_ptr"].tolist() == [0, 4, 5, 7, 7, 11, 13]
     assert p["query_ptr"].tolist() == [0, 3, 3, 4, 6]
-    _, k_video, k_window, p = m._window_search_plan("search_windows", wb, qb, np.zeros((0, 2), dtype=np.int64), 7, 3, None, 64, None)
-    assert (k_video, k_window) == (3, 3) and p["wi"].shape == (0,) and p["group_ptr"].tolist() == [0] and p["query_ptr"].tolist() == [0] * 5
+    o, p = m._window_search_plan("search_windows", wb, qb, np.zeros((0, 2), dtype=np.int64), 7, 3, None, 64, None)
+    assert (o.k_video, o.k_window) == (3, 3) and p["wi"].shape == (0,) and p["group_ptr"].tolist() == [0] and p["query_ptr"].tolist() == [0] * 5
 
 
 def fake_scorer(wb):

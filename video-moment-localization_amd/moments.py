@@ -102,6 +102,14 @@ def _mul32(a, b):
     return (a.float().double() * b.float().double()).float()
 
 
+def _order_word(score):
+    """fp32 scores as int64 words in the kernels' order: a higher score has the higher word, -0 counts as +0, and no word is below 1
+    (0 stands for "no candidate")."""
+    score = torch.where(score == 0, torch.zeros_like(score), score)                             # -0 -> +0
+    u = score.contiguous().view(torch.int32).to(torch.int64) & 0xFFFFFFFF                        # fp32 bits -> unsigned order word
+    return torch.where(u >= 0x80000000, u ^ 0xFFFFFFFF, u | 0x80000000).clamp_min(1)
+
+
 def _iou(i1, j1, i2, j2):
     inter = (torch.minimum(j1, j2) + 1 - torch.maximum(i1, i2)).clamp_min(0)
     union = torch.maximum(j1, j2) + 1 - torch.minimum(i1, i2)
@@ -115,8 +123,7 @@ def top_moments_torch(pm, ps, pe, moment_mask, k=5, nms_thresh=0.5, duration=Non
     dev = pm.device
     score = _mul32(_mul32(pm.detach(), _sqrt32(ps.detach()).unsqueeze(2)), _sqrt32(pe.detach()).unsqueeze(1))
     score = torch.where(score == 0, torch.zeros_like(score), score).reshape(B, -1)              # -0 -> +0
-    u = score.view(torch.int32).to(torch.int64) & 0xFFFFFFFF                                     # fp32 bits -> unsigned order word
-    o = torch.where(u >= 0x80000000, u ^ 0xFFFFFFFF, u | 0x80000000).clamp_min(1)
+    o = _order_word(score)
     valid = byte_mask(moment_mask).reshape(B, -1) != 0
     o = torch.where(valid, o, torch.zeros_like(o))
     order = torch.sort(o, dim=1, descending=True, stable=True).indices                          # ties keep index order
@@ -269,9 +276,7 @@ def merge_window_moments_torch(idx, score, count, start, lens, pair_ptr, T, L, k
     G, kw, B = _merge_check(idx, score, count, start, lens, pair_ptr, T, L, k)
     dev = idx.device
     score = score.detach().float()
-    sc = torch.where(score == 0, torch.zeros_like(score), score)                                 # -0 -> +0
-    u = sc.view(torch.int32).to(torch.int64) & 0xFFFFFFFF
-    o = torch.where(u >= 0x80000000, u ^ 0xFFFFFFFF, u | 0x80000000).clamp_min(1).reshape(-1)   # the order word of top_moments_torch
+    o = _order_word(score).reshape(-1)
     st_all, en_all = window_spans(idx, start.unsqueeze(1), lens.unsqueeze(1), T, L)              # (G, kw)
     st_all, en_all = st_all.reshape(-1), en_all.reshape(-1)
     slot_ok = (torch.arange(kw, device=dev).unsqueeze(0) < count.to(torch.int64).unsqueeze(1)).reshape(-1)
@@ -448,9 +453,7 @@ def corpus_topk_torch(pair_score, pair_idx, pair_count, pair_video, pair_ptr, k=
     P, kv, Q = _corpus_check(pair_score, pair_idx, pair_count, pair_video, pair_ptr, k)
     dev = pair_ptr.device
     score = pair_score.detach().float()
-    sc = torch.where(score == 0, torch.zeros_like(score), score)                                 # -0 -> +0
-    u = sc.contiguous().view(torch.int32).to(torch.int64) & 0xFFFFFFFF
-    o = torch.where(u >= 0x80000000, u ^ 0xFFFFFFFF, u | 0x80000000).clamp_min(1).reshape(-1).tolist()   # the order word of top_moments_torch
+    o = _order_word(score).reshape(-1).tolist()
     cnt = pair_count.to(torch.int64).clamp(max=kv).tolist()
     vid = pair_video.to(torch.int64).tolist()
     pp = pair_ptr.to(torch.int64).tolist()
@@ -519,9 +522,7 @@ def corpus_span_topk_torch(span, score, window, cell, count, group_video, group_
     G2, kv, Q = _corpus_span_check("corpus_span_topk_torch", span, score, window, cell, count, group_video, group_ptr, k)
     dev = group_ptr.device
     span, score = span.detach().float(), score.detach().float()
-    sc = torch.where(score == 0, torch.zeros_like(score), score)                                 # -0 -> +0
-    u = sc.contiguous().view(torch.int32).to(torch.int64) & 0xFFFFFFFF
-    o = torch.where(u >= 0x80000000, u ^ 0xFFFFFFFF, u | 0x80000000).clamp_min(1).reshape(-1).tolist()   # the order word of top_moments_torch
+    o = _order_word(score).reshape(-1).tolist()
     cnt = count.to(torch.int64).clamp(0, kv).tolist()
     vid = group_video.to(torch.int64).tolist()
     gp = group_ptr.to(torch.int64).tolist()
@@ -604,10 +605,7 @@ def mine_pairs_torch(score, gt_video, negatives, skip=0):
     v_pairs, q_ptr, q_pairs)`` on ``score``'s device."""
     Q, V, gt = _mine_check("mine_pairs_torch", score, gt_video, negatives, skip)
     N, S = int(negatives), 1 + int(negatives)
-    sc = score.detach().float()
-    sc = torch.where(sc == 0, torch.zeros_like(sc), sc)                                          # -0 -> +0
-    u = sc.contiguous().view(torch.int32).to(torch.int64) & 0xFFFFFFFF
-    o = torch.where(u >= 0x80000000, u ^ 0xFFFFFFFF, u | 0x80000000).clamp_min(1).tolist()      # the order word of top_moments_torch
+    o = _order_word(score.detach().float()).tolist()
     vi, qi = [], []
     for q in range(Q):
         g = int(gt[q])
@@ -1204,9 +1202,27 @@ def window_times(video, span, duration, n_rows):
 # ---------------------------------------------------------------- merge of ranked lists of disjoint video shards
 MAX_LISTS = 16
 
+# What a ranked list holds, described once: field -> (dtype, the shape behind (Q, k_s)), and ``count (Q,)``.  The kernels leave -1 in an
+# empty slot's integers, 0 in its floats and the NaN 0x7FC00000 in its span.
+_ENTRY = dict(video=(torch.int64, ()), idx=(torch.int64, (2,)), span=(torch.float32, (2,)), score=(torch.float32, ()), raw=(torch.float32, ()),
+              window=(torch.int64, ()), cell=(torch.int64, (2,)), count=(torch.int32, None))
 
-_SEARCH_FIELDS = {"idx": (2,), "score": ()}                                       # a list's tensors beside video (Q, k_s) and count (Q,):
-_SPAN_FIELDS = {"span": (2,), "score": (), "window": (), "cell": (2,)}           # name -> the shape behind (Q, k_s)
+
+def _fields(*names):
+    """A kind of entry: its fields beside video, name -> the shape behind (Q, k_s)."""
+    return {name: _ENTRY[name][1] for name in names}
+
+
+_SEARCH_FIELDS, _SPAN_FIELDS = _fields("idx", "score"), _fields("span", "score", "window", "cell")
+_WEIGHTED_SEARCH_FIELDS, _WEIGHTED_SPAN_FIELDS = dict(_SEARCH_FIELDS, raw=()), dict(_SPAN_FIELDS, raw=())          # (INTEGRATION.md 3u)
+
+# The merge kernels (include/smin_hip.h): (span entries, weighted) -> the symbol, its per-list tables and its outputs in argument order
+_MERGE_KERNELS = {
+    (False, False): ("smin_search_merge", ("video", "idx", "score", "count"), ("video", "idx", "score", "count")),
+    (True, False): ("smin_span_search_merge", _SPAN_KEYS, _SPAN_KEYS),
+    (False, True): ("smin_search_merge_weighted", ("video", "idx", "raw", "count"), ("video", "idx", "score", "raw", "count")),
+    (True, True): ("smin_span_search_merge_weighted", ("video", "span", "raw", "window", "cell", "count"),
+                   ("video", "span", "score", "raw", "window", "cell", "count"))}
 
 
 def _ranked_lists_check(what, results, video_offset, k, fields):
@@ -1236,11 +1252,87 @@ def _ranked_lists_check(what, results, video_offset, k, fields):
     return results, off, Q
 
 
-def _merge_search_check(what, results, video_offset, k, duration, L):
-    checked = _ranked_lists_check(what, results, video_offset, k, _SEARCH_FIELDS)
-    if duration is not None and L is None:
+def _times_check(what, fields, duration, scale):
+    """``times`` of a merged list need ``duration`` and ``scale``: L for entries of ``idx``, n_rows for entries of ``span``."""
+    if "span" in fields:
+        if (duration is None) != (scale is None):
+            raise ValueError(f"{what}: times need both duration and n_rows, the global (V,) seconds and row counts of the videos")
+    elif duration is not None and scale is None:
         raise ValueError(f"{what}: times need L, the number of clips per video, beside duration")
-    return checked
+
+
+def _with_times(out, duration, scale):
+    if duration is not None and "span" in out:
+        out["times"] = window_times(out["video"], out["span"], torch.as_tensor(duration), torch.as_tensor(scale))
+    elif duration is not None:
+        out["times"] = search_times(out["video"], out["idx"], duration, scale)
+    return out
+
+
+def _launch_merge(what, results, off, Q, k, fields, weighted=()):
+    """One launch of the merge kernel for entries of ``fields`` over checked lists (_MERGE_KERNELS); ``weighted``: the weighted kernels'
+    arguments between the offsets and Q.  Returns the kernel's outputs by name."""
+    for r in results:
+        for key in ["video"] + list(fields) + ["count"]:
+            _require_hip(r[key], what)
+    dev, S = results[0]["video"].device, len(results)
+    symbol, ins, outs = _MERGE_KERNELS["span" in fields, bool(weighted)]
+    cols = [[r[key].detach().to(_ENTRY[key][0]).contiguous() for r in results] for key in ins]
+    tables = [(ctypes.c_void_p * S)(*[t.data_ptr() for t in col]) for col in cols]
+    k_list = (ctypes.c_int32 * S)(*[t.shape[1] for t in cols[0]])
+    offsets = (ctypes.c_int64 * S)(*off)
+    out = {key: torch.empty((Q,) if key == "count" else (Q, k) + _ENTRY[key][1], dtype=_ENTRY[key][0], device=dev) for key in outs}
+    with torch.cuda.device(dev):
+        call(symbol, stream(), S, *[ctypes.cast(t, ctypes.c_void_p) for t in tables], ctypes.cast(k_list, ctypes.c_void_p),
+             ctypes.cast(offsets, ctypes.c_void_p), *weighted, Q, k, *[ptr(out[key]) if out[key].numel() else None for key in outs])
+    return out
+
+
+def _merge_lists_torch(results, off, Q, k, fields, value=None, keep=None):
+    """The merges of ranked lists as plain torch + Python on any device: each query's candidates -- the first ``count[q]`` entries of
+    every list, of those the ones ``keep[s] (Q, k_s)`` bool admits -- sorted by (value, global video, list, position), and the best k
+    moved bit for bit: floats travel as int32 views, so a NaN keeps its payload and -0 its sign.  ``value[s] (Q, k_s)`` fp32 stands in
+    for list s's score, in the order and in the output.  Empty slots hold the kernels' patterns (_ENTRY)."""
+    dev = results[0]["video"].device
+    per, base, moved = [], [0], {key: [] for key in ["video"] + list(fields)}
+    for s, r in enumerate(results):
+        ks = r["video"].shape[1]
+        g = r["video"].to(torch.int64) + off[s]
+        score = r["score"].detach().float() if value is None else value[s]
+        per.append((_order_word(score).tolist(), g.tolist(), r["count"].to(torch.int64).clamp(0, ks).tolist(),
+                    None if keep is None else keep[s].tolist()))
+        base.append(base[-1] + ks)
+        for key in moved:                                                                      # list after list, (Q, sum k_s)
+            t = g if key == "video" else score if key == "score" else r[key].detach().to(_ENTRY[key][0])
+            moved[key].append(t.contiguous().view(torch.int32) if t.dtype == torch.float32 else t)
+    moved = {key: torch.cat(ts, dim=1) for key, ts in moved.items()}
+    out = {}
+    for key in moved:
+        dtype, tail = _ENTRY[key]
+        if dtype == torch.float32:
+            out[key] = torch.full((Q, k) + tail, 0x7FC00000 if key == "span" else 0, dtype=torch.int32, device=dev).view(torch.float32)
+        else:
+            out[key] = torch.full((Q, k) + tail, -1, dtype=dtype, device=dev)
+    out["count"] = torch.zeros((Q,), dtype=torch.int32, device=dev)
+    for q in range(Q):
+        cand = [(-o[q][p], g[q][p], s, p) for s, (o, g, cnt, ok) in enumerate(per) for p in range(cnt[q]) if ok is None or ok[q][p]]
+        cand.sort()
+        n = min(len(cand), k)
+        if n:
+            flat = torch.tensor([base[s] + p for _, _, s, p in cand[:n]], dtype=torch.int64, device=dev)
+            for key, src in moved.items():
+                dst = out[key].view(torch.int32) if out[key].dtype == torch.float32 else out[key]
+                dst[q, :n] = src[q, flat]
+        out["count"][q] = n
+    return out
+
+
+def _merge(what, results, video_offset, k, fields, duration, scale, restated=False):
+    """The body of the plain merges: the checks, the kernel or its restatement, ``times``."""
+    results, off, Q = _ranked_lists_check(what, results, video_offset, k, fields)
+    _times_check(what, fields, duration, scale)
+    out = _merge_lists_torch(results, off, Q, k, fields) if restated else _launch_merge(what, results, off, Q, k, fields)
+    return _with_times(out, duration, scale)
 
 
 def merge_search(results, video_offset=None, k=5, duration=None, L=None):
@@ -1254,64 +1346,13 @@ def merge_search(results, video_offset=None, k=5, duration=None, L=None):
     whole corpus at equal pair scores, all at once or folded (``merge_search([carry, next], [0, seen])``).  No host synchronisation.
 
     Returns ``search``'s dict with global ids in ``video``; with ``duration`` (the global (V,) seconds) and ``L`` also ``times``."""
-    results, off, Q = _merge_search_check("merge_search", results, video_offset, k, duration, L)
-    for r in results:
-        for key in ("video", "idx", "score", "count"):
-            _require_hip(r[key], "merge_search")
-    dev, S = results[0]["video"].device, len(results)
-    cols = [[r["video"].to(torch.int64).contiguous() for r in results], [r["idx"].to(torch.int64).contiguous() for r in results],
-            [r["score"].detach().float().contiguous() for r in results], [r["count"].to(torch.int32).contiguous() for r in results]]
-    tables = [(ctypes.c_void_p * S)(*[t.data_ptr() for t in col]) for col in cols]
-    k_list = (ctypes.c_int32 * S)(*[t.shape[1] for t in cols[0]])
-    offsets = (ctypes.c_int64 * S)(*off)
-    video = torch.empty((Q, k), dtype=torch.int64, device=dev)
-    idx = torch.empty((Q, k, 2), dtype=torch.int64, device=dev)
-    score = torch.empty((Q, k), dtype=torch.float32, device=dev)
-    count = torch.empty((Q,), dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        call("smin_search_merge", stream(), S, *[ctypes.cast(t, ctypes.c_void_p) for t in tables], ctypes.cast(k_list, ctypes.c_void_p),
-             ctypes.cast(offsets, ctypes.c_void_p), Q, k, ptr(video), ptr(idx), ptr(score), ptr(count))
-    out = {"video": video, "idx": idx, "score": score, "count": count}
-    if duration is not None:
-        out["times"] = search_times(video, idx, duration, L)
-    return out
+    return _merge("merge_search", results, video_offset, k, _SEARCH_FIELDS, duration, L)
 
 
 def merge_search_torch(results, video_offset=None, k=5, duration=None, L=None):
     """``merge_search`` as plain torch + Python on any device (same result, bit for bit): each query's candidates sorted by
     (score, global video, list, position)."""
-    results, off, Q = _merge_search_check("merge_search_torch", results, video_offset, k, duration, L)
-    dev = results[0]["video"].device
-    per = []
-    for r in results:
-        score = r["score"].detach().float()
-        sc = torch.where(score == 0, torch.zeros_like(score), score)                             # -0 -> +0
-        u = sc.contiguous().view(torch.int32).to(torch.int64) & 0xFFFFFFFF
-        o = torch.where(u >= 0x80000000, u ^ 0xFFFFFFFF, u | 0x80000000).clamp_min(1).tolist()  # the order word of top_moments_torch
-        ks = score.shape[1]
-        per.append((o, r["video"].to(torch.int64).tolist(), r["count"].to(torch.int64).clamp(0, ks).tolist()))
-    base = [0]
-    for r in results:
-        base.append(base[-1] + r["score"].shape[1])
-    all_video = torch.cat([r["video"].to(torch.int64) + off[s] for s, r in enumerate(results)], dim=1)       # (Q, sum k_s), list after list
-    all_idx = torch.cat([r["idx"].to(torch.int64) for r in results], dim=1)
-    all_score = torch.cat([r["score"].detach().float() for r in results], dim=1)
-    video = torch.full((Q, k), -1, dtype=torch.int64, device=dev)
-    idx = torch.full((Q, k, 2), -1, dtype=torch.int64, device=dev)
-    out_score = torch.zeros((Q, k), dtype=torch.float32, device=dev)
-    count = torch.zeros((Q,), dtype=torch.int32, device=dev)
-    for q in range(Q):
-        cand = [(-o[q][p], vid[q][p] + off[s], s, p) for s, (o, vid, cnt) in enumerate(per) for p in range(cnt[q])]
-        cand.sort()
-        n = min(len(cand), k)
-        if n:
-            flat = torch.tensor([base[s] + p for _, _, s, p in cand[:n]], dtype=torch.int64, device=dev)
-            video[q, :n], idx[q, :n], out_score[q, :n] = all_video[q, flat], all_idx[q, flat], all_score[q, flat]
-        count[q] = n
-    out = {"video": video, "idx": idx, "score": out_score, "count": count}
-    if duration is not None:
-        out["times"] = search_times(video, idx, duration, L)
-    return out
+    return _merge("merge_search_torch", results, video_offset, k, _SEARCH_FIELDS, duration, L, restated=True)
 
 
 def fold_search(lists, offsets, k, merge):
@@ -1325,19 +1366,6 @@ def fold_search(lists, offsets, k, merge):
 
 
 # ---------------------------------------------------------------- merge of span lists of sharded window banks
-def _merge_span_check(what, results, video_offset, k, duration, n_rows):
-    checked = _ranked_lists_check(what, results, video_offset, k, _SPAN_FIELDS)
-    if (duration is None) != (n_rows is None):
-        raise ValueError(f"{what}: times need both duration and n_rows, the global (V,) seconds and row counts of the videos")
-    return checked
-
-
-def _with_window_times(out, duration, n_rows):
-    if duration is not None:
-        out["times"] = window_times(out["video"], out["span"], torch.as_tensor(duration), torch.as_tensor(n_rows))
-    return out
-
-
 def merge_search_windows(results, video_offset=None, k=5, duration=None, n_rows=None):
     """One ranked list of span-valued moments per query out of 1..16 ``SMIN.search_windows``-style lists, each over its own shard of a
     corpus of long videos (include/smin_hip.h, smin_span_search_merge): one launch, one workgroup per query; each candidate finds its
@@ -1353,70 +1381,17 @@ def merge_search_windows(results, video_offset=None, k=5, duration=None, n_rows=
 
     Returns ``search_windows``' dict with global ids in ``video``; with ``duration`` and ``n_rows`` (the global (V,) seconds and row
     counts) also ``times``, by ``window_times``."""
-    results, off, Q = _merge_span_check("merge_search_windows", results, video_offset, k, duration, n_rows)
-    for r in results:
-        for key in _SPAN_KEYS:
-            _require_hip(r[key], "merge_search_windows")
-    dev, S = results[0]["video"].device, len(results)
-    dtypes = dict(video=torch.int64, span=torch.float32, score=torch.float32, window=torch.int64, cell=torch.int64, count=torch.int32)
-    cols = [[r[key].detach().to(dtypes[key]).contiguous() for r in results] for key in _SPAN_KEYS]
-    tables = [(ctypes.c_void_p * S)(*[t.data_ptr() for t in col]) for col in cols]
-    k_list = (ctypes.c_int32 * S)(*[t.shape[1] for t in cols[0]])
-    offsets = (ctypes.c_int64 * S)(*off)
-    out = {"video": torch.empty((Q, k), dtype=torch.int64, device=dev), "span": torch.empty((Q, k, 2), dtype=torch.float32, device=dev),
-           "score": torch.empty((Q, k), dtype=torch.float32, device=dev), "window": torch.empty((Q, k), dtype=torch.int64, device=dev),
-           "cell": torch.empty((Q, k, 2), dtype=torch.int64, device=dev), "count": torch.empty((Q,), dtype=torch.int32, device=dev)}
-    with torch.cuda.device(dev):
-        call("smin_span_search_merge", stream(), S, *[ctypes.cast(t, ctypes.c_void_p) for t in tables], ctypes.cast(k_list, ctypes.c_void_p),
-             ctypes.cast(offsets, ctypes.c_void_p), Q, k, *[ptr(out[key]) for key in _SPAN_KEYS])
-    return _with_window_times(out, duration, n_rows)
+    return _merge("merge_search_windows", results, video_offset, k, _SPAN_FIELDS, duration, n_rows)
 
 
 def merge_search_windows_torch(results, video_offset=None, k=5, duration=None, n_rows=None):
     """``merge_search_windows`` as plain torch + Python on any device (same result, bit for bit): each query's candidates sorted by
     (score, global video, list, position)."""
-    results, off, Q = _merge_span_check("merge_search_windows_torch", results, video_offset, k, duration, n_rows)
-    dev = results[0]["video"].device
-    per, base = [], [0]
-    for r in results:
-        score = r["score"].detach().float()
-        sc = torch.where(score == 0, torch.zeros_like(score), score)                             # -0 -> +0
-        u = sc.contiguous().view(torch.int32).to(torch.int64) & 0xFFFFFFFF
-        o = torch.where(u >= 0x80000000, u ^ 0xFFFFFFFF, u | 0x80000000).clamp_min(1).tolist()  # the order word of top_moments_torch
-        ks = score.shape[1]
-        per.append((o, r["video"].to(torch.int64).tolist(), r["count"].to(torch.int64).clamp(0, ks).tolist()))
-        base.append(base[-1] + ks)
-    # list after list, (Q, sum k_s); span and score as integers, so a NaN keeps its payload and -0 its sign
-    everything = {"video": torch.cat([r["video"].to(torch.int64) + off[s] for s, r in enumerate(results)], dim=1),
-                  "span": torch.cat([r["span"].detach().float().contiguous().view(torch.int32) for r in results], dim=1),
-                  "score": torch.cat([r["score"].detach().float().contiguous().view(torch.int32) for r in results], dim=1),
-                  "window": torch.cat([r["window"].to(torch.int64) for r in results], dim=1),
-                  "cell": torch.cat([r["cell"].to(torch.int64) for r in results], dim=1)}
-    out = {"video": torch.full((Q, k), -1, dtype=torch.int64, device=dev),
-           "span": torch.full((Q, k, 2), 0x7FC00000, dtype=torch.int32, device=dev).view(torch.float32),    # the kernel's NaN
-           "score": torch.zeros((Q, k), dtype=torch.float32, device=dev),
-           "window": torch.full((Q, k), -1, dtype=torch.int64, device=dev),
-           "cell": torch.full((Q, k, 2), -1, dtype=torch.int64, device=dev),
-           "count": torch.zeros((Q,), dtype=torch.int32, device=dev)}
-    for q in range(Q):
-        cand = [(-o[q][p], vid[q][p] + off[s], s, p) for s, (o, vid, cnt) in enumerate(per) for p in range(cnt[q])]
-        cand.sort()
-        n = min(len(cand), k)
-        if n:
-            flat = torch.tensor([base[s] + p for _, _, s, p in cand[:n]], dtype=torch.int64, device=dev)
-            for key, src in everything.items():
-                dst = out[key].view(torch.int32) if key in ("span", "score") else out[key]
-                dst[q, :n] = src[q, flat]
-        out["count"][q] = n
-    return _with_window_times(out, duration, n_rows)
+    return _merge("merge_search_windows_torch", results, video_offset, k, _SPAN_FIELDS, duration, n_rows, restated=True)
 
 
 # ---------------------------------------------------------------- weighted merge of shard lists that carry their video scores (INTEGRATION.md 3u)
-_WEIGHTED_SEARCH_FIELDS = dict(_SEARCH_FIELDS, raw=())
-_WEIGHTED_SPAN_FIELDS = dict(_SPAN_FIELDS, raw=())
 _CARRY_KEYS = ("raw", "pair_score", "pair_cells")
-_WEIGHTED_DTYPES = dict(video=torch.int64, idx=torch.int64, span=torch.float32, score=torch.float32, raw=torch.float32, window=torch.int64,
-                        cell=torch.int64, count=torch.int32)
 
 
 def carry_slots(k, k_video, max_videos=None):
@@ -1493,88 +1468,46 @@ def _video_tables(results, Q, V, n_videos, alpha, gt_video, rank):
     return ps, pc, rank(ps.reshape(-1), pc.reshape(-1), pair_video, pair_ptr, n=n_videos, alpha=alpha, gt_video=gt_video)
 
 
-def _weighted_result(out, ps, pc, vr):
-    out.update(pair_score=ps, pair_cells=pc, video_rank=vr["video"], video_score=vr["score"], video_count=vr["count"], gt_rank=vr["gt_rank"])
-    return out
-
-
 def _merge_weighted(what, results, off, Q, k, fields, rank_table, weight_table, V, cut):
     """One launch of smin_search_merge_weighted (``fields`` with ``idx``) or smin_span_search_merge_weighted over checked lists:
     ``rank_table`` / ``weight_table (Q, V)`` int32 / fp32 on the lists' device, ``cut`` <= 0 for no cut.  Returns the carry's entry keys."""
-    keys = ["video"] + list(fields) + ["count"]
-    for r in results:
-        for key in keys:
-            _require_hip(r[key], what)
-    dev, S = results[0]["video"].device, len(results)
-    spans = "span" in fields
-    order = ("video", "span", "raw", "window", "cell", "count") if spans else ("video", "idx", "raw", "count")
-    cols = [[r[key].detach().to(_WEIGHTED_DTYPES[key]).contiguous() for r in results] for key in order]
-    tables = [(ctypes.c_void_p * S)(*[t.data_ptr() for t in col]) for col in cols]
-    k_list = (ctypes.c_int32 * S)(*[t.shape[1] for t in cols[0]])
-    offsets = (ctypes.c_int64 * S)(*off)
     rank_table, weight_table = rank_table.to(torch.int32).contiguous(), weight_table.detach().float().contiguous()
-    out_keys = ("video", "span", "score", "raw", "window", "cell", "count") if spans else ("video", "idx", "score", "raw", "count")
-    out = {key: torch.empty((Q,) if key == "count" else (Q, k) + ((2,) if key in ("idx", "span", "cell") else ()), dtype=_WEIGHTED_DTYPES[key], device=dev)
-           for key in out_keys}
-    with torch.cuda.device(dev):
-        call("smin_span_search_merge_weighted" if spans else "smin_search_merge_weighted", stream(), S,
-             *[ctypes.cast(t, ctypes.c_void_p) for t in tables], ctypes.cast(k_list, ctypes.c_void_p), ctypes.cast(offsets, ctypes.c_void_p),
-             ptr(rank_table) if rank_table.numel() else None, ptr(weight_table) if weight_table.numel() else None, V, cut, Q, k,
-             *[ptr(out[key]) if out[key].numel() else None for key in out_keys])
-    return out
+    return _launch_merge(what, results, off, Q, k, fields, (ptr(rank_table) if rank_table.numel() else None,
+                                                            ptr(weight_table) if weight_table.numel() else None, V, cut))
 
 
 def _merge_weighted_torch(results, off, Q, k, fields, rank_table, weight_table, V, cut):
     """``_merge_weighted`` as plain torch + Python on any device (same result, bit for bit): each query's surviving candidates sorted by
-    (value, global video, list, position), the value ``raw * weight`` rounded once to fp32."""
-    dev = results[0]["video"].device
-    rank_l, per, base = rank_table.to(torch.int64).tolist(), [], [0]
-    everything = {key: [] for key in ["video", "score"] + list(fields)}
+    (value, global video, list, position), the value ``raw * weight`` rounded once to fp32.  A candidate survives with a global video in
+    [0, V) whose rank is neither below 0 nor, under a cut, at or behind it."""
+    value, keep = [], []
     for s, r in enumerate(results):
-        ks = r["video"].shape[1]
         g = r["video"].to(torch.int64) + off[s]
         inside = (g >= 0) & (g < V)
-        w = torch.gather(weight_table.detach().float(), 1, torch.where(inside, g, torch.zeros_like(g))) if V else torch.zeros(g.shape, device=dev)
-        value = _mul32(r["raw"].detach().float(), w)
-        sc = torch.where(value == 0, torch.zeros_like(value), value)                             # -0 -> +0
-        u = sc.contiguous().view(torch.int32).to(torch.int64) & 0xFFFFFFFF
-        o = torch.where(u >= 0x80000000, u ^ 0xFFFFFFFF, u | 0x80000000).clamp_min(1).tolist()  # the order word of top_moments_torch
-        per.append((o, g.tolist(), r["count"].to(torch.int64).clamp(0, ks).tolist()))
-        base.append(base[-1] + ks)
-        for key in everything:                                                                 # floats as integers: a NaN keeps its payload, -0 its sign
-            t = g if key == "video" else value if key == "score" else r[key].detach().to(_WEIGHTED_DTYPES[key])
-            everything[key].append(t.contiguous().view(torch.int32) if t.dtype == torch.float32 else t)
-    everything = {key: torch.cat(ts, dim=1) for key, ts in everything.items()}
-    out = {"video": torch.full((Q, k), -1, dtype=torch.int64, device=dev), "score": torch.zeros((Q, k), dtype=torch.float32, device=dev)}
-    for key, tail in fields.items():
-        if key == "score":
-            continue
-        if key == "span":
-            out[key] = torch.full((Q, k, 2), 0x7FC00000, dtype=torch.int32, device=dev).view(torch.float32)        # the kernel's NaN
-        elif key == "raw":
-            out[key] = torch.zeros((Q, k), dtype=torch.float32, device=dev)
-        else:
-            out[key] = torch.full((Q, k) + tail, -1, dtype=torch.int64, device=dev)
-    out["count"] = torch.zeros((Q,), dtype=torch.int32, device=dev)
-    for q in range(Q):
-        cand = []
-        for s, (o, g, cnt) in enumerate(per):
-            for p in range(cnt[q]):
-                gv = g[q][p]
-                if not 0 <= gv < V:
-                    continue
-                vr = rank_l[q][gv]
-                if vr < 0 or (cut > 0 and vr >= cut):
-                    continue
-                cand.append((-o[q][p], gv, s, p))
-        cand.sort()
-        n = min(len(cand), k)
-        if n:
-            flat = torch.tensor([base[s] + p for _, _, s, p in cand[:n]], dtype=torch.int64, device=dev)
-            for key, src in everything.items():
-                dst = out[key].view(torch.int32) if out[key].dtype == torch.float32 else out[key]
-                dst[q, :n] = src[q, flat]
-        out["count"][q] = n
+        at = torch.where(inside, g, torch.zeros_like(g))
+        w = torch.gather(weight_table.detach().float(), 1, at) if V else torch.zeros(g.shape, device=g.device)
+        rank = torch.gather(rank_table.to(torch.int64), 1, at) if V else torch.full_like(g, -1)
+        value.append(_mul32(r["raw"].detach().float(), w))
+        keep.append(inside & (rank >= 0) & ((rank < cut) if cut > 0 else inside))
+    return _merge_lists_torch(results, off, Q, k, fields, value, keep)
+
+
+def _search_merge_weighted(what, results, video_offset, k, video_weight, max_videos, n_videos, gt_video, duration, scale, fields,
+                           restated=False, tables=None):
+    """The body of the four weighted merges: the checks, the shards' pooled scores side by side and one video ranking over them, the
+    kernel (or, ``restated``, the torch ranking -- replaced by ``tables`` where given -- and the sort), ``times`` and the carry's keys."""
+    alpha = _video_weight(what, video_weight)
+    results, off, Q, V, cut, n_videos = _weighted_check(what, results, video_offset, k, fields, max_videos, n_videos)
+    _times_check(what, fields, duration, scale)
+    if not restated:
+        for r in results:
+            for key in ("video", "pair_score", "pair_cells"):
+                _require_hip(r[key], what)
+    ps, pc, vr = _video_tables(results, Q, V, n_videos, alpha, gt_video, rank_videos_torch if restated else rank_videos)
+    rank_table, weight_table = (vr["pair_rank"], vr["weight"]) if tables is None else tables
+    merge = _merge_weighted_torch if restated else functools.partial(_merge_weighted, what)
+    out = _with_times(merge(results, off, Q, k, fields, rank_table.reshape(Q, V), weight_table.reshape(Q, V), V, cut), duration, scale)
+    out.update(pair_score=ps, pair_cells=pc, video_rank=vr["video"], video_score=vr["score"], video_count=vr["count"], gt_rank=vr["gt_rank"])
     return out
 
 
@@ -1600,19 +1533,8 @@ def merge_search_weighted(results, video_offset=None, k=5, video_weight=0.0, max
     merged again (the shard lists, and the carries of a fold, cut to k by ``truncate_search`` at the end), the result is, at equal pair
     scores and away from fp32 near-ties between a query's candidate values, bit for bit the one-bank search's; the carry costs
     ``Q * V * 8`` bytes and every merge re-ranks all V videos seen."""
-    what = "merge_search_weighted"
-    alpha = _video_weight(what, video_weight)
-    results, off, Q, V, cut, n_videos = _weighted_check(what, results, video_offset, k, _WEIGHTED_SEARCH_FIELDS, max_videos, n_videos)
-    if duration is not None and L is None:
-        raise ValueError(f"{what}: times need L, the number of clips per video, beside duration")
-    for r in results:
-        for key in ("video", "pair_score", "pair_cells"):
-            _require_hip(r[key], what)
-    ps, pc, vr = _video_tables(results, Q, V, n_videos, alpha, gt_video, rank_videos)
-    out = _merge_weighted(what, results, off, Q, k, _WEIGHTED_SEARCH_FIELDS, vr["pair_rank"].reshape(Q, V), vr["weight"].reshape(Q, V), V, cut)
-    if duration is not None:
-        out["times"] = search_times(out["video"], out["idx"], duration, L)
-    return _weighted_result(out, ps, pc, vr)
+    return _search_merge_weighted("merge_search_weighted", results, video_offset, k, video_weight, max_videos, n_videos, gt_video, duration, L,
+                                  _WEIGHTED_SEARCH_FIELDS)
 
 
 def merge_search_weighted_torch(results, video_offset=None, k=5, video_weight=0.0, max_videos=None, n_videos=None, gt_video=None, duration=None,
@@ -1620,17 +1542,8 @@ def merge_search_weighted_torch(results, video_offset=None, k=5, video_weight=0.
     """``merge_search_weighted`` as plain torch + Python on any device: the video ranking by ``rank_videos_torch`` -- or, with ``tables``
     = ``(pair_rank, weight)`` of shape (Q, V), the rank and weight tables it is given (the tests feed it the kernel's, whose expf is
     not torch's exp) --, then a Python sort on (value, global video, list, position).  Nothing routes here."""
-    what = "merge_search_weighted_torch"
-    alpha = _video_weight(what, video_weight)
-    results, off, Q, V, cut, n_videos = _weighted_check(what, results, video_offset, k, _WEIGHTED_SEARCH_FIELDS, max_videos, n_videos)
-    if duration is not None and L is None:
-        raise ValueError(f"{what}: times need L, the number of clips per video, beside duration")
-    ps, pc, vr = _video_tables(results, Q, V, n_videos, alpha, gt_video, rank_videos_torch)
-    rank_table, weight_table = (vr["pair_rank"], vr["weight"]) if tables is None else tables
-    out = _merge_weighted_torch(results, off, Q, k, _WEIGHTED_SEARCH_FIELDS, rank_table.reshape(Q, V), weight_table.reshape(Q, V), V, cut)
-    if duration is not None:
-        out["times"] = search_times(out["video"], out["idx"], duration, L)
-    return _weighted_result(out, ps, pc, vr)
+    return _search_merge_weighted("merge_search_weighted_torch", results, video_offset, k, video_weight, max_videos, n_videos, gt_video, duration, L,
+                                  _WEIGHTED_SEARCH_FIELDS, restated=True, tables=tables)
 
 
 def merge_search_windows_weighted(results, video_offset=None, k=5, video_weight=0.0, max_videos=None, n_videos=None, gt_video=None, duration=None,
@@ -1640,29 +1553,13 @@ def merge_search_windows_weighted(results, video_offset=None, k=5, video_weight=
     smin_span_search_merge_weighted -- the same kernel body over entries of ``span``, ``window`` and ``cell``.  Returns the carry form
     with those fields, plus ``video_rank``, ``video_score``, ``video_count`` and ``gt_rank``; with ``duration`` and ``n_rows`` (the global
     (V,) seconds and row counts) also ``times``, by ``window_times``."""
-    what = "merge_search_windows_weighted"
-    alpha = _video_weight(what, video_weight)
-    results, off, Q, V, cut, n_videos = _weighted_check(what, results, video_offset, k, _WEIGHTED_SPAN_FIELDS, max_videos, n_videos)
-    if (duration is None) != (n_rows is None):
-        raise ValueError(f"{what}: times need both duration and n_rows, the global (V,) seconds and row counts of the videos")
-    for r in results:
-        for key in ("video", "pair_score", "pair_cells"):
-            _require_hip(r[key], what)
-    ps, pc, vr = _video_tables(results, Q, V, n_videos, alpha, gt_video, rank_videos)
-    out = _merge_weighted(what, results, off, Q, k, _WEIGHTED_SPAN_FIELDS, vr["pair_rank"].reshape(Q, V), vr["weight"].reshape(Q, V), V, cut)
-    return _weighted_result(_with_window_times(out, duration, n_rows), ps, pc, vr)
+    return _search_merge_weighted("merge_search_windows_weighted", results, video_offset, k, video_weight, max_videos, n_videos, gt_video, duration,
+                                  n_rows, _WEIGHTED_SPAN_FIELDS)
 
 
 def merge_search_windows_weighted_torch(results, video_offset=None, k=5, video_weight=0.0, max_videos=None, n_videos=None, gt_video=None,
                                         duration=None, n_rows=None, tables=None):
     """``merge_search_windows_weighted`` as plain torch + Python on any device; ``tables`` as ``merge_search_weighted_torch`` takes them.
     Nothing routes here."""
-    what = "merge_search_windows_weighted_torch"
-    alpha = _video_weight(what, video_weight)
-    results, off, Q, V, cut, n_videos = _weighted_check(what, results, video_offset, k, _WEIGHTED_SPAN_FIELDS, max_videos, n_videos)
-    if (duration is None) != (n_rows is None):
-        raise ValueError(f"{what}: times need both duration and n_rows, the global (V,) seconds and row counts of the videos")
-    ps, pc, vr = _video_tables(results, Q, V, n_videos, alpha, gt_video, rank_videos_torch)
-    rank_table, weight_table = (vr["pair_rank"], vr["weight"]) if tables is None else tables
-    out = _merge_weighted_torch(results, off, Q, k, _WEIGHTED_SPAN_FIELDS, rank_table.reshape(Q, V), weight_table.reshape(Q, V), V, cut)
-    return _weighted_result(_with_window_times(out, duration, n_rows), ps, pc, vr)
+    return _search_merge_weighted("merge_search_windows_weighted_torch", results, video_offset, k, video_weight, max_videos, n_videos, gt_video,
+                                  duration, n_rows, _WEIGHTED_SPAN_FIELDS, restated=True, tables=tables)

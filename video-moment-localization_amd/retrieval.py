@@ -61,6 +61,11 @@ class VideoBank:
         """What SMIN._plan reads of the bank's features (dtype, T, no gradient): the features themselves where the bank keeps them."""
         return self.video_features
 
+    @property
+    def cell_count(self):
+        """Every video's valid-cell count where all ``cell_counts`` are one value, else None."""
+        return self.cell_counts[0] if len(set(self.cell_counts)) == 1 else None
+
 
 class WindowBank(VideoBank):
     """The W windows of V videos of any length, encoded once (SMIN.encode_windows): a VideoBank whose rows are the
@@ -157,6 +162,57 @@ def _require_banks(what, videos, queries):
         raise TypeError(f"{what}: videos is a VideoBank (encode_videos) and queries a QueryBank (encode_queries)")
 
 
+def _require_node_banks(videos, queries):
+    """ValueError for a bank without the one-node path's encodings (encode_queries leaves ``fw`` and ``fs`` together)."""
+    if videos.fv is None or queries.fw is None or queries.fs is None:
+        raise ValueError("score_pairs: a bank was encoded while the module was off the one-node path (SMIN._plan); encode it again")
+
+
+def _upload(parts, dtype, dev):
+    """Host arrays as views of ONE buffer of ``dtype`` on ``dev``: a pinned asynchronous copy, so the call never waits for the device
+    (a plain tensor on the CPU)."""
+    host = torch.from_numpy(np.concatenate(parts).astype(dtype))
+    buf = host.pin_memory().to(dev, non_blocking=True) if torch.device(dev).type == "cuda" else host
+    return buf.split([a.shape[0] for a in parts])
+
+
+class _Options:
+    """The checked options of a search, as one value: ``k``, ``k_video`` and ``k_window`` with their defaults filled in; after
+    ``video_level`` the options of INTEGRATION.md 3t -- ``ranked`` True, ``alpha``, ``max_videos`` (None: no cut), ``tau``, ``n_videos`` --;
+    ``gt``, each query's own video as Q host ints (empty: none given).  Every check of these has its one source here; an entry point
+    runs them in the order its errors have always come in.  ValueError for a bad value."""
+    ranked, gt = False, np.zeros(0, np.int64)
+
+    def __init__(self, what, k=1, k_video=None, max_batch=1, k_window=None, windows=False):
+        k_video = k if k_video is None else k_video
+        k_window = k_video if k_window is None else k_window
+        require_ints(what, ("k", k, 1, MAX_K), ("k_video", k_video, 1, MAX_K), *([("k_window", k_window, 1, MAX_K)] if windows else []),
+                     ("max_batch", max_batch, 1, 65535))
+        self.what, self.k, self.k_video, self.k_window = what, int(k), int(k_video), int(k_window) if windows else None
+
+    def duration(self, duration, V):
+        if duration is not None and tuple(duration.shape) != (V,):
+            raise ValueError(f"{self.what}: duration must be (V,) = ({V},) seconds (got {tuple(duration.shape)})")
+
+    def gt_video(self, gt_video, Q):
+        if gt_video is not None:
+            self.gt = host_array(gt_video)
+            if self.gt.shape[0] != Q:
+                raise ValueError(f"{self.what}: gt_video must name a video for each of the Q = {Q} queries (got {self.gt.shape[0]})")
+        return self
+
+    def video_level(self, video_weight, max_videos, tau, n_videos, gt_video, Q):
+        self.alpha = _video_weight(self.what, 0.0 if video_weight is None else video_weight)
+        if max_videos is not None:
+            require_ints(self.what, ("max_videos", max_videos, 1, 2 ** 31 - 1))
+        n_videos = min(self.k, MAX_K) if n_videos is None else n_videos
+        require_ints(self.what, ("n_videos", n_videos, 1, MAX_K))
+        self.gt_video(gt_video, Q)
+        self.max_videos, self.n_videos = None if max_videos is None else int(max_videos), int(n_videos)
+        self.ranked, self.tau = True, _temperature(self.what, tau)
+        return self
+
+
 class PairPlan:
     """The index lists of P (video, query) pairs over V videos and Q queries as forward_pairs and training.pair_targets read them:
     the checked host lists ``vi`` / ``qi`` (int64 numpy) and, on ``device`` as int32, ``video_index`` / ``query_index (P,)`` and the
@@ -188,11 +244,8 @@ class PairPlan:
             pos = vi == gv[qi]
             rows = np.flatnonzero(pos)
             parts += [pos, rows]
-        host = torch.from_numpy(np.concatenate(parts).astype(np.int32))
         device = torch.device(device)
-        buf = host.pin_memory().to(device, non_blocking=True) if device.type == "cuda" else host
-        cut = np.cumsum([0, P, P, V + 1, P, Q + 1, P] + ([P, rows.shape[0]] if rows is not None else []))
-        cuts = [buf[cut[k]:cut[k + 1]] for k in range(len(cut) - 1)]
+        cuts = _upload(parts, np.int32, device)
         self.vi, self.qi, self.V, self.Q, self.P, self.device = vi, qi, V, Q, P, device
         self.video_index, self.query_index, self.v_ptr, self.v_pairs, self.q_ptr, self.q_pairs = cuts[:6]
         self.positive, self.positive_rows = (cuts[6], cuts[7].to(torch.int64)) if rows is not None else (None, None)
@@ -229,6 +282,26 @@ def _chunk_buffers(n, k, max_batch, dev):
 def _pool_buffers(n, dev):
     """Where the chunks of n pairs leave pair_pool's ``score (n,)``, ``pool (n, 2)`` and ``cells (n,)`` on ``dev``."""
     return tuple(torch.empty(shape, dtype=torch.float32, device=dev) for shape in ((n,), (n, 2), (n,)))
+
+
+def _rank_lists(o, lists, video_d, ptr_d, gt_d=None, pooled=None):
+    """The ranking tail of every search: each query's ``o.k`` best moments across its videos out of ``lists``, its pairs' top_moments
+    lists (``idx``: one smin_corpus_topk) or its groups' merge_window_moments lists (``span`` / ``window`` / ``cell``: one
+    smin_corpus_span_topk) -- ``video_d``: each pair's or group's video, ``ptr_d (Q + 1,)``: query q owns ``ptr_d[q] .. ptr_d[q + 1]``, both
+    int32.  With the video-level options (``o.ranked``), in front of it one smin_video_rank over ``pooled``, the pairs'
+    or groups' pooled ``(score, cells)``, and one smin_moment_reweight of the lists by it; the result then gains ``video_rank``,
+    ``video_score``, ``video_count`` and ``gt_rank`` (``gt_d``: ``o.gt`` on the device).  ``lists`` is left as it is.  No host read."""
+    score, count = lists["score"], lists["count"]
+    if o.ranked:
+        vr = rank_videos(pooled[0], pooled[1], video_d, ptr_d, n=o.n_videos, alpha=o.alpha, gt_video=gt_d if o.gt.size else None)
+        score, count = reweight_moments(score, count, vr["pair_rank"], vr["weight"], o.max_videos)
+    if "idx" in lists:
+        r = corpus_topk(score, lists["idx"], count, video_d, ptr_d, k=o.k)
+    else:
+        r = corpus_span_topk(lists["span"], score, lists["window"], lists["cell"], count, video_d, ptr_d, k=o.k)
+    if o.ranked:
+        r.update(video_rank=vr["video"], video_score=vr["score"], video_count=vr["count"], gt_rank=vr["gt_rank"])
+    return r
 
 
 class _Retrieval:
@@ -317,11 +390,8 @@ class _Retrieval:
         nf = np.minimum(w_len, T)
         cells = np.array([cell_count(x, T, L) for x in nf], dtype=np.int64)                      # per window, as csrc/labels.hip forms it
         # the whole plan in one pinned buffer, one asynchronous copy (the call never waits for the device)
-        host = np.concatenate([offs[vi[pair_of]] + w_start if G else np.zeros(0, np.int64), w_start, w_len, pair_of, pair_ptr, nw,
-                               n[vi]]).astype(np.int64)
-        plan = torch.from_numpy(host).pin_memory().to(dev, non_blocking=True)
-        cut = np.cumsum([0, G, G, G, G, B + 1, B, B])
-        rb_d, st_d, ln_d, po_d, pp_d, nw_d, nr_d = (plan[cut[q]:cut[q + 1]] for q in range(7))
+        rb_d, st_d, ln_d, po_d, pp_d, nw_d, nr_d = _upload([offs[vi[pair_of]] + w_start if G else np.zeros(0, np.int64), w_start, w_len, pair_of,
+                                                            pair_ptr, nw, n[vi]], np.int64, dev)
         ln_d = ln_d.to(torch.int32)
         idx, score, count, chunks = _chunk_buffers(G, k_window, max_batch, dev)
         with torch.no_grad(), torch.cuda.device(dev):
@@ -415,8 +485,7 @@ class _Retrieval:
                 return self.score(videos.video_features.index_select(0, vi_d), videos.video_mask.index_select(0, vi_d),
                                   queries.query_features.index_select(0, qi_d), qm.index_select(0, qi_d),
                                   videos.length_mask.index_select(0, vi_d), videos.moment_mask.index_select(0, vi_d))
-            if videos.fv is None or queries.fw is None:
-                raise ValueError("score_pairs: a bank was encoded while the module was off the one-node path (SMIN._plan); encode it again")
+            _require_node_banks(videos, queries)
             return _lib.load_torch().smin_score_pairs(
                 videos.fv, queries.fw, queries.fs, videos.video_mask, queries.query_mask, videos.length_mask, videos.moment_mask, vi_d, qi_d,
                 *self._core_args(), **self._score_options())
@@ -433,9 +502,7 @@ class _Retrieval:
         if vi.shape[0] < 1:
             raise ValueError("score_pairs: at least one pair")
         require_hip_tensors("score_pairs", dict(videos=videos.video_mask, queries=queries.query_features), must="hold HIP tensors")
-        dev = videos.device
-        idx = torch.from_numpy(np.concatenate([vi, qi]).astype(np.int32)).pin_memory().to(dev, non_blocking=True)
-        return self._score_pairs(videos, queries, vi, qi, idx[:vi.shape[0]], idx[vi.shape[0]:])
+        return self._score_pairs(videos, queries, vi, qi, *_upload([vi, qi], np.int32, videos.device))
 
     # ---------------------------------------------------------------- training through shared banks
     def forward_pairs(self, video_features, video_mask, query_features, query_mask, length_mask, moment_mask, video_index, query_index,
@@ -497,15 +564,14 @@ class _Retrieval:
                 *self._core_args(), **o)
 
     def _search_plan(self, what, videos, queries, pairs, k, k_video, max_batch, duration):
-        k_video = k if k_video is None else k_video
-        require_ints(what, ("k", k, 1, MAX_K), ("k_video", k_video, 1, MAX_K), ("max_batch", max_batch, 1, 65535))
+        """search's checked arguments and its pair lists: ``(options, vi, qi, pair_ptr)`` (_Options, _listed_pairs)."""
+        o = _Options(what, k, k_video, max_batch)
         _require_banks(what, videos, queries)
         V, Q = len(videos), len(queries)
         vi, qi, pair_ptr = self._listed_pairs(what, pairs, V, Q)
-        if duration is not None and tuple(duration.shape) != (V,):
-            raise ValueError(f"{what}: duration must be (V,) = ({V},) seconds (got {tuple(duration.shape)})")
+        o.duration(duration, V)
         require_hip_tensors(what, dict(videos=videos.video_mask, queries=queries.query_features), must="hold HIP tensors")
-        return int(k), int(k_video), vi, qi, pair_ptr
+        return o, vi, qi, pair_ptr
 
     @staticmethod
     def _listed_pairs(what, pairs, V, Q):
@@ -587,46 +653,45 @@ class _Retrieval:
             raise ValueError("search: carry=True takes pairs=None, every query against every video of the bank (a merge re-ranks all the shard's videos)")
         if carry and video_weight is None and max_videos is None:
             video_weight = 0.0
-        k, k_video, vi, qi, pair_ptr = self._search_plan("search", videos, queries, pairs, k, k_video, max_batch, duration)
-        dev, L, P = videos.device, self.L, vi.shape[0]
+        o, vi, qi, pair_ptr = self._search_plan("search", videos, queries, pairs, k, k_video, max_batch, duration)
         if video_weight is not None or max_videos is not None:
-            alpha, cut, tau, n_videos, gt = self._video_options("search", video_weight, max_videos, tau, n_videos, gt_video, k, len(queries))
-            parts = [vi, qi, pair_ptr, gt]
-            plan = torch.from_numpy(np.concatenate(parts).astype(np.int32)).pin_memory().to(dev, non_blocking=True)
-            vi_d, qi_d, pp_d, gt_d = plan.split([a.shape[0] for a in parts])
-            with torch.no_grad(), torch.cuda.device(dev):
-                pools = _pool_buffers(P, dev)
-                idx, score, count = self._pair_moments(videos, queries, vi, qi, vi_d, qi_d, k_video, nms_thresh, max_batch, pools=(tau,) + pools)
-                vr = rank_videos(pools[0], pools[2], vi_d, pp_d, n=n_videos, alpha=alpha, gt_video=gt_d if gt.size else None)
-                w_score, w_count = reweight_moments(score, count, vr["pair_rank"], vr["weight"], cut)
-                r = corpus_topk(w_score, idx, w_count, vi_d, pp_d, k=k)
-                if carry:
-                    Q, V = len(queries), len(videos)
-                    r["raw"] = _carry_raw(r["video"], (r["idx"],), (idx,), score, count, V)
-                    r["pair_score"], r["pair_cells"] = pools[0].reshape(Q, V), pools[2].reshape(Q, V)
-            r.update(video_rank=vr["video"], video_score=vr["score"], video_count=vr["count"], gt_rank=vr["gt_rank"])
-            return self._search_result(r, duration, L)
+            o.video_level(video_weight, max_videos, tau, n_videos, gt_video, len(queries))
+        dev, Q, V = videos.device, len(queries), len(videos)
         # the whole plan in one pinned buffer, one asynchronous copy (the call never waits for the device)
-        plan = torch.from_numpy(np.concatenate([vi, qi, pair_ptr]).astype(np.int32)).pin_memory().to(dev, non_blocking=True)
-        vi_d, qi_d, pp_d = plan[:P], plan[P:2 * P], plan[2 * P:]
+        vi_d, qi_d, pp_d, gt_d = _upload([vi, qi, pair_ptr, o.gt], np.int32, dev)
         with torch.no_grad(), torch.cuda.device(dev):
-            idx, score, count = self._pair_moments(videos, queries, vi, qi, vi_d, qi_d, k_video, nms_thresh, max_batch)
-            r = corpus_topk(score, idx, count, vi_d, pp_d, k=k)
-        return self._search_result(r, duration, L)
+            lists, pools = self._pair_chunks(videos, queries, vi_d, qi_d, max_batch, host=(vi, qi), cut=(o.k_video, nms_thresh),
+                                             tau=o.tau if o.ranked else None)
+            r = _rank_lists(o, lists, vi_d, pp_d, gt_d, pools and (pools[0], pools[2]))
+            if carry:
+                r["raw"] = _carry_raw(r["video"], (r["idx"],), (lists["idx"],), lists["score"], lists["count"], V)
+                r["pair_score"], r["pair_cells"] = pools[0].reshape(Q, V), pools[2].reshape(Q, V)
+        return self._search_result(r, duration, self.L)
 
-    def _pair_moments(self, videos, queries, vi, qi, vi_d, qi_d, k_video, nms_thresh, max_batch, pools=None):
-        """search's chunk loop: top_moments' ``idx (P, k_video, 2)``, ``score (P, k_video)`` and ``count (P,)`` of the P pairs of the
-        checked host lists vi / qi (int32 device copies vi_d / qi_d), scored in chunks of at most ``max_batch``.  ``pools``: ``(tau,
-        score (P,), pool (P, 2), cells (P,))`` -- each chunk's scores are then also pooled into these buffers (one pair_pool launch on
-        the scores the chunk already holds).  No host read."""
-        idx, score, count, chunks = _chunk_buffers(vi.shape[0], k_video, max_batch, vi_d.device)
-        for c0, c1 in chunks:
-            pm, ps, pe, _ = self._score_pairs(videos, queries, vi[c0:c1], qi[c0:c1], vi_d[c0:c1], qi_d[c0:c1])
+    def _pair_chunks(self, videos, queries, vi_d, qi_d, max_batch, host=None, cell=None, cut=None, tau=None):
+        """search's chunk loop, the only one: the P pairs of the int32 device lists ``vi_d`` / ``qi_d`` scored from the banks in chunks of
+        at most ``max_batch`` (_score_pairs), each chunk's moment masks gathered, and of each chunk's scores what is asked for:
+        ``cut = (k_video, nms_thresh)`` -- top_moments' ``idx (P, k_video, 2)``, ``score (P, k_video)`` and ``count (P,)``, returned as a
+        dict --, ``tau`` -- pair_pool's ``(score (P,), pool (P, 2), cells (P,))`` at that temperature, one launch on the scores the chunk
+        already holds.  Returns ``(lists, pools)``, None for what was not asked for.  A chunk's valid-cell count: with ``host``, the checked
+        host lists ``(vi, qi)`` the device lists were copied from, the sum of the bank's cell_counts; without them the lists exist on the
+        device only, and it is the chunk's pairs times ``cell`` -- every video's count where the bank's are all one value -- or, ``cell``
+        None, not handed over: the node reads it once per chunk.  No host read otherwise."""
+        P, dev = vi_d.shape[0], vi_d.device
+        lists = dict(zip(("idx", "score", "count"), _chunk_buffers(P, cut[0], max_batch, dev))) if cut is not None else None
+        pools = _pool_buffers(P, dev) if tau is not None else None
+        for c0 in range(0, P, max_batch):
+            c1 = min(c0 + max_batch, P)
+            if host is not None:
+                pm, ps, pe, _ = self._score_pairs(videos, queries, host[0][c0:c1], host[1][c0:c1], vi_d[c0:c1], qi_d[c0:c1])
+            else:
+                pm, ps, pe, _ = self._score_pairs(videos, queries, None, None, vi_d[c0:c1], qi_d[c0:c1], cells=None if cell is None else (c1 - c0) * cell)
             mm = videos.moment_mask.index_select(0, vi_d[c0:c1])
-            _top_moments_into(pm, ps, pe, mm, k_video, nms_thresh, idx[c0:c1], score[c0:c1], count[c0:c1])
-            if pools is not None:
-                _pair_pool_into(pm, ps, pe, mm, pools[0], pools[1][c0:c1], pools[2][c0:c1], pools[3][c0:c1])
-        return idx, score, count
+            if cut is not None:
+                _top_moments_into(pm, ps, pe, mm, cut[0], cut[1], lists["idx"][c0:c1], lists["score"][c0:c1], lists["count"][c0:c1])
+            if tau is not None:
+                _pair_pool_into(pm, ps, pe, mm, tau, pools[0][c0:c1], pools[1][c0:c1], pools[2][c0:c1])
+        return lists, pools
 
     # ---------------------------------------------------------------- first-stage pruning from the banks alone (INTEGRATION.md 3v)
     def prefilter_videos(self, videos, queries, M, tau=0.1, gt_video=None):
@@ -650,14 +715,9 @@ class _Retrieval:
         windowed = isinstance(videos, WindowBank)
         Q, W, dev = len(queries), len(videos), videos.device
         V = videos.n_videos if windowed else W
-        gt = None
-        if gt_video is not None:
-            gt = host_array(gt_video)
-            if gt.shape[0] != Q:
-                raise ValueError(f"{what}: gt_video must name a video for each of the Q = {Q} queries (got {gt.shape[0]})")
+        gt = _Options(what).gt_video(gt_video, Q).gt
         require_hip_tensors(what, dict(videos=videos.video_mask, queries=queries.query_features), must="hold HIP tensors")
-        if videos.fv is None or queries.fs is None:
-            raise ValueError("score_pairs: a bank was encoded while the module was off the one-node path (SMIN._plan); encode it again")
+        _require_node_banks(videos, queries)
         if Q * max(V, W) > 0x7fff0000:
             raise ValueError(f"{what}: {Q} queries over {max(V, W)} videos / windows exceed the int32 pair lists")
         with torch.no_grad(), torch.cuda.device(dev):
@@ -667,7 +727,7 @@ class _Retrieval:
                 first = torch.arange(Q, device=dev).unsqueeze(1) * W + videos.video_ptr_d[:-1].unsqueeze(0)           # group q * V + v begins here
                 group_ptr = torch.cat([first.reshape(-1), first.new_full((1,), Q * W)])
                 score, cells = (x.reshape(Q, V) for x in group_pool(pool.reshape(Q * W, 2), cells.reshape(Q * W), group_ptr, tau))
-            gt_d = None if gt is None else torch.from_numpy(gt.astype(np.int32)).pin_memory().to(dev, non_blocking=True)
+            gt_d = _upload([gt], np.int32, dev)[0] if gt.size else None
             video_of = torch.arange(V, dtype=torch.int32, device=dev).repeat(Q)
             pair_ptr = torch.arange(Q + 1, dtype=torch.int32, device=dev) * V
             vr = rank_videos(score.reshape(-1), cells.reshape(-1), video_of, pair_ptr, n=1, alpha=0.0, gt_video=gt_d)
@@ -703,75 +763,43 @@ class _Retrieval:
                              "VideoEncoder.fused and QueryEncoder.fused); this module or these inputs are off that path")
         require_hip_tensors(what, dict(video_features=video_features, video_mask=video_mask, query_features=query_features, query_mask=query_mask,
                                        length_mask=length_mask, moment_mask=moment_mask))
-        lo, D = self.localization, self.D
-        heads = (lo.conv_layer_pm, lo.conv_layer_ps, lo.conv_layer_pe)
         with torch.cuda.device(video_features.device):
             fv = ve(video_features, video_mask.reshape(V, -1, 1))
             fs, _ = qe(query_features, query_mask)
-            w, b = torch.stack([h.weight.reshape(D) for h in heads]), torch.cat([h.bias.reshape(1) for h in heads])
+            w, b = self._first_stage_heads(self.D)
             pm0, ps0, pe0, score = prefilter_maps(fv, fs, w, b, length_mask, moment_mask, self.T, self.L, self.C, tau)
         L = self.L
         return pm0.reshape(Q * V, L, L), ps0.reshape(Q * V, L), pe0.reshape(Q * V, L), score
 
-    def _pair_moments_device(self, videos, queries, vi_d, qi_d, cell, k_video, nms_thresh, max_batch, pools=None):
-        """``_pair_moments`` over pair lists that exist on the device only (int32 ``vi_d`` / ``qi_d (P,)``): the same chunks, no host copy
-        of the lists.  ``cell``: every video's valid-cell count where the bank's are all one value -- a chunk's count is then its pairs
-        times it --, else None: no count is handed over and the node reads it once per chunk."""
-        idx, score, count, chunks = _chunk_buffers(vi_d.shape[0], k_video, max_batch, vi_d.device)
-        for c0, c1 in chunks:
-            pm, ps, pe, _ = self._score_pairs(videos, queries, None, None, vi_d[c0:c1], qi_d[c0:c1], cells=None if cell is None else (c1 - c0) * cell)
-            mm = videos.moment_mask.index_select(0, vi_d[c0:c1])
-            _top_moments_into(pm, ps, pe, mm, k_video, nms_thresh, idx[c0:c1], score[c0:c1], count[c0:c1])
-            if pools is not None:
-                _pair_pool_into(pm, ps, pe, mm, pools[0], pools[1][c0:c1], pools[2][c0:c1], pools[3][c0:c1])
-        return idx, score, count
-
     def _search_prefiltered(self, videos, queries, M, k, k_video, nms_thresh, duration, max_batch, video_weight, max_videos, tau, n_videos, gt_video):
         """``search(prefilter=M)``: prefilter_videos, then search's chunk loop and ranking over the device-built Q * Ms pair lists."""
-        what = "search"
-        k_video = k if k_video is None else k_video
-        require_ints(what, ("k", k, 1, MAX_K), ("k_video", k_video, 1, MAX_K), ("max_batch", max_batch, 1, 65535))
-        _require_banks(what, videos, queries)
+        o = _Options("search", k, k_video, max_batch)
+        _require_banks("search", videos, queries)
         if isinstance(videos, WindowBank):
             raise ValueError("search: prefilter takes a VideoBank (pruning a window search is out of scope: the surviving windows' list has a "
                              "data-dependent length)")
-        Q, V, dev = len(queries), len(videos), videos.device
-        if duration is not None and tuple(duration.shape) != (V,):
-            raise ValueError(f"{what}: duration must be (V,) = ({V},) seconds (got {tuple(duration.shape)})")
-        video_level = video_weight is not None or max_videos is not None
-        if video_level:
-            alpha, cut, tau, n_videos, gt = self._video_options(what, video_weight, max_videos, tau, n_videos, gt_video, k, Q)
+        o.duration(duration, len(videos))
+        if video_weight is not None or max_videos is not None:
+            tau = o.video_level(video_weight, max_videos, tau, n_videos, gt_video, len(queries)).tau
         pf = self.prefilter_videos(videos, queries, M, tau, gt_video)
-        vi_d, qi_d, Ms = pf["video_index"], pf["query_index"], pf["video"].shape[1]
-        counts = videos.cell_counts
-        cell = counts[0] if all(c == counts[0] for c in counts) else None
-        r = self._search_survivor_pairs(videos, queries, vi_d, vi_d, qi_d, Ms, cell, int(k), int(k_video), nms_thresh, max_batch,
-                                        (alpha, cut, tau, n_videos, gt) if video_level else None)
+        gt_d = _upload([o.gt], np.int32, videos.device)[0] if o.gt.size else None
+        r = self._search_survivor_pairs(o, videos, queries, pf["video_index"], pf["video_index"], pf["query_index"], pf["video"].shape[1],
+                                        videos.cell_count, nms_thresh, max_batch, gt_d)
         r.update(prefilter_video=pf["video"], prefilter_score=pf["score"], prefilter_gt_rank=pf["gt_rank"])
         return self._search_result(r, duration, self.L)
 
-    def _search_survivor_pairs(self, videos, queries, rows_d, video_d, qi_d, Ms, cell, k, k_video, nms_thresh, max_batch, video_level):
+    def _search_survivor_pairs(self, o, videos, queries, rows_d, video_d, qi_d, Ms, cell, nms_thresh, max_batch, gt_d):
         """The tail ``search(prefilter=M)`` and ``search_survivors`` share: the full model over the Q * Ms surviving pairs, sorted by (query,
         video), then the ranking.  ``rows_d (Q Ms,)`` int32: each pair's row of the bank ``videos``; ``video_d``: its video id as the
         ranking reads it (ties go to the lower video) and the result names it -- the same tensor for a VideoBank, the global ids for a
-        SurvivorBank --; ``cell`` as ``_pair_moments_device`` takes it; ``video_level``: None, or ``_video_options``' tuple (INTEGRATION.md
-        3t).  No host read."""
-        Q, dev = len(queries), videos.device
+        SurvivorBank --; ``cell`` as ``_pair_chunks`` takes it; ``o``: the checked options, ``gt_d``: ``o.gt`` on the device where the
+        video-level options read it.  No host read."""
+        dev = videos.device
         with torch.no_grad(), torch.cuda.device(dev):
-            pp_d = torch.arange(Q + 1, dtype=torch.int32, device=dev) * Ms
-            if video_level is not None:
-                alpha, cut, tau, n_videos, gt = video_level
-                gt_d = torch.from_numpy(gt.astype(np.int32)).pin_memory().to(dev, non_blocking=True) if gt.size else None
-                pools = _pool_buffers(Q * Ms, dev)
-                idx, score, count = self._pair_moments_device(videos, queries, rows_d, qi_d, cell, k_video, nms_thresh, max_batch, pools=(tau,) + pools)
-                vr = rank_videos(pools[0], pools[2], video_d, pp_d, n=n_videos, alpha=alpha, gt_video=gt_d)
-                w_score, w_count = reweight_moments(score, count, vr["pair_rank"], vr["weight"], cut)
-                r = corpus_topk(w_score, idx, w_count, video_d, pp_d, k=k)
-                r.update(video_rank=vr["video"], video_score=vr["score"], video_count=vr["count"], gt_rank=vr["gt_rank"])
-            else:
-                idx, score, count = self._pair_moments_device(videos, queries, rows_d, qi_d, cell, k_video, nms_thresh, max_batch)
-                r = corpus_topk(score, idx, count, video_d, pp_d, k=k)
-        return r
+            pp_d = torch.arange(len(queries) + 1, dtype=torch.int32, device=dev) * Ms
+            lists, pools = self._pair_chunks(videos, queries, rows_d, qi_d, max_batch, cell=cell, cut=(o.k_video, nms_thresh),
+                                             tau=o.tau if o.ranked else None)
+            return _rank_lists(o, lists, video_d, pp_d, gt_d, pools and (pools[0], pools[2]))
 
     # ---------------------------------------------------------------- the first-stage cut over a corpus in shards (INTEGRATION.md 3x)
     def _first_stage_heads(self, D):
@@ -813,8 +841,7 @@ class _Retrieval:
         if Q != survivors.Q:
             raise ValueError(f"{what}: the survivors were made for Q = {survivors.Q} queries (got {Q})")
         require_hip_tensors(what, dict(videos=videos.video_mask, queries=queries.query_features), must="hold HIP tensors")
-        if videos.fv is None or queries.fs is None:
-            raise ValueError("score_pairs: a bank was encoded while the module was off the one-node path (SMIN._plan); encode it again")
+        _require_node_banks(videos, queries)
         if survivors.seen + V > 0x7fff0000 // max(Q, 1):
             raise ValueError(f"{what}: {Q} queries over {survivors.seen + V} videos exceed the int32 pair lists")
         dev, D = videos.device, videos.fv.shape[2]
@@ -847,8 +874,7 @@ class _Retrieval:
         query).  ``duration (V,)``, ``gt_video``: over the global ids.  Valid-cell count: when every shard's ``cell_counts`` were one
         value c, each chunk's count is ``pairs * c`` and nothing is read back; otherwise the node reads it once per chunk."""
         what = "search_survivors"
-        k_video = k if k_video is None else k_video
-        require_ints(what, ("k", k, 1, MAX_K), ("k_video", k_video, 1, MAX_K), ("max_batch", max_batch, 1, 65535))
+        o = _Options(what, k, k_video, max_batch)
         if not isinstance(survivors, SurvivorBank) or not isinstance(queries, QueryBank):
             raise TypeError(f"{what}: survivors is a SurvivorBank (new_survivors) and queries a QueryBank (encode_queries)")
         Q, V, M, dev = len(queries), survivors.seen, survivors.M, survivors.device
@@ -856,55 +882,25 @@ class _Retrieval:
             raise ValueError(f"{what}: the survivors were made for Q = {survivors.Q} queries (got {Q})")
         if V < 1:
             raise ValueError(f"{what}: no shard has been folded (fold_survivors)")
-        if duration is not None and tuple(duration.shape) != (V,):
-            raise ValueError(f"{what}: duration must be (V,) = ({V},) seconds (got {tuple(duration.shape)})")
-        video_level = None
+        o.duration(duration, V)
         if video_weight is not None or max_videos is not None:
-            video_level = self._video_options(what, video_weight, max_videos, survivors.tau, n_videos, gt_video, k, Q)
-        gt = None
-        if gt_video is not None:
-            gt = host_array(gt_video)
-            if gt.shape[0] != Q:
-                raise ValueError(f"{what}: gt_video must name a video for each of the Q = {Q} queries (got {gt.shape[0]})")
+            o.video_level(video_weight, max_videos, survivors.tau, n_videos, gt_video, Q)
+        else:
+            o.gt_video(gt_video, Q)
         Ms = min(M, V)
         with torch.no_grad(), torch.cuda.device(dev):
             video, order = torch.sort(survivors.slot_video[:, :Ms], dim=1)
             rows = (torch.arange(Q, dtype=torch.int32, device=dev) * M).unsqueeze(1) + order.to(torch.int32)
             qi_d = torch.arange(Q, dtype=torch.int32, device=dev).unsqueeze(1).expand(Q, Ms).reshape(-1)
-            gt_d = None if gt is None else torch.from_numpy(gt.astype(np.int32)).pin_memory().to(dev, non_blocking=True)
+            gt_d = _upload([o.gt], np.int32, dev)[0] if o.gt.size else None
             score = survivors.score
             gt_rank = prefilter_gt_rank(score, survivors.candidate, gt_d)
-        r = self._search_survivor_pairs(survivors, queries, rows.reshape(-1), video.reshape(-1).contiguous(), qi_d, Ms, survivors.cell_count, int(k),
-                                        int(k_video), nms_thresh, max_batch, video_level)
+        r = self._search_survivor_pairs(o, survivors, queries, rows.reshape(-1), video.reshape(-1).contiguous(), qi_d, Ms, survivors.cell_count,
+                                        nms_thresh, max_batch, gt_d)
         r.update(prefilter_video=video.to(torch.int64), prefilter_score=score, prefilter_gt_rank=gt_rank)
         return self._search_result(r, duration, self.L)
 
     # ---------------------------------------------------------------- video ranking by the pooled pair score
-    @staticmethod
-    def _video_options(what, video_weight, max_videos, tau, n_videos, gt_video, k, Q):
-        """The checked video-level options of a search: ``(alpha, max_videos or None, tau, n_videos, gt_video as Q host ints or an empty
-        array)``.  ValueError for a bad value."""
-        alpha = _video_weight(what, 0.0 if video_weight is None else video_weight)
-        if max_videos is not None:
-            require_ints(what, ("max_videos", max_videos, 1, 2 ** 31 - 1))
-        n_videos = min(int(k), MAX_K) if n_videos is None else n_videos
-        require_ints(what, ("n_videos", n_videos, 1, MAX_K))
-        gt = np.zeros(0, np.int64) if gt_video is None else host_array(gt_video)
-        if gt_video is not None and gt.shape[0] != Q:
-            raise ValueError(f"{what}: gt_video must name a video for each of the Q = {Q} queries (got {gt.shape[0]})")
-        return alpha, None if max_videos is None else int(max_videos), _temperature(what, tau), int(n_videos), gt
-
-    def _pair_pools(self, videos, queries, vi, qi, vi_d, qi_d, tau, max_batch):
-        """search's chunk loop with pair_pool where search has the moment cut: ``(score (P,), pool (P, 2), cells (P,))`` of the P pairs of
-        the checked host lists vi / qi.  No host read."""
-        P = vi.shape[0]
-        score, pool, cells = _pool_buffers(P, vi_d.device)
-        for c0 in range(0, P, max_batch):
-            c1 = min(c0 + max_batch, P)
-            pm, ps, pe, _ = self._score_pairs(videos, queries, vi[c0:c1], qi[c0:c1], vi_d[c0:c1], qi_d[c0:c1])
-            _pair_pool_into(pm, ps, pe, videos.moment_mask.index_select(0, vi_d[c0:c1]), tau, score[c0:c1], pool[c0:c1], cells[c0:c1])
-        return score, pool, cells
-
     def rank_videos(self, videos, queries, pairs=None, n=5, tau=0.1, gt_video=None, max_batch=64):
         """Which video: each of the Q queries' videos ranked by the pooled pair score, the score training.pair_rank_loss contrasts
          -- video retrieval only, no moment is cut.  ``videos``: a VideoBank, or a WindowBank of videos of any
@@ -921,23 +917,21 @@ class _Retrieval:
         require_ints(what, ("n", n, 1, MAX_K))
         windowed = isinstance(videos, WindowBank)
         if windowed:
-            _, _, _, p = self._window_search_plan(what, videos, queries, pairs, 1, 1, 1, max_batch, None)
-            vi, qi, pair_ptr = p["vi"], p["qi"], p["query_ptr"]
+            o, p = self._window_search_plan(what, videos, queries, pairs, 1, 1, 1, max_batch, None)
+            vi, pair_ptr, rest = p["vi"], p["query_ptr"], [p["wi"], p["wq"], p["group_ptr"]]
         else:
-            _, _, vi, qi, pair_ptr = self._search_plan(what, videos, queries, pairs, 1, 1, max_batch, None)
+            o, vi, qi, pair_ptr = self._search_plan(what, videos, queries, pairs, 1, 1, max_batch, None)
+            rest = [qi]
         require_hip_tensors(what, dict(videos=videos.video_mask, queries=queries.query_features), must="hold HIP tensors")
-        Q, P, dev = len(queries), vi.shape[0], videos.device
-        _, _, tau, n, gt = self._video_options(what, None, None, tau, int(n), gt_video, n, Q)
-        parts = [vi, pair_ptr, gt] + ([p["wi"], p["wq"], p["group_ptr"]] if windowed else [qi])
-        with torch.no_grad(), torch.cuda.device(dev):
-            plan = torch.from_numpy(np.concatenate(parts).astype(np.int32)).pin_memory().to(dev, non_blocking=True)
-            vi_d, pp_d, gt_d, *rest = plan.split([a.shape[0] for a in parts])
+        o.video_level(None, None, tau, int(n), gt_video, len(queries))
+        with torch.no_grad(), torch.cuda.device(videos.device):
+            vi_d, pp_d, gt_d, *rest_d = _upload([vi, pair_ptr, o.gt] + rest, np.int32, videos.device)
             if windowed:
-                _, pool, cells = self._pair_pools(videos, queries, p["wi"], p["wq"], rest[0], rest[1], tau, max_batch)
-                score, cells = group_pool(pool, cells, rest[2], tau)
+                _, (_, pool, cells) = self._pair_chunks(videos, queries, rest_d[0], rest_d[1], max_batch, host=(p["wi"], p["wq"]), tau=o.tau)
+                score, cells = group_pool(pool, cells, rest_d[2], o.tau)
             else:
-                score, _, cells = self._pair_pools(videos, queries, vi, qi, vi_d, rest[0], tau, max_batch)
-            vr = rank_videos(score, cells, vi_d, pp_d, n=n, alpha=0.0, gt_video=gt_d if gt.size else None)
+                _, (score, _, cells) = self._pair_chunks(videos, queries, vi_d, rest_d[0], max_batch, host=(vi, qi), tau=o.tau)
+            vr = rank_videos(score, cells, vi_d, pp_d, n=o.n_videos, alpha=0.0, gt_video=gt_d if o.gt.size else None)
         return dict(video=vr["video"], score=vr["score"], count=vr["count"], pair_score=score, pair_rank=vr["pair_rank"], gt_rank=vr["gt_rank"])
 
     # ---------------------------------------------------------------- corpus search over long videos
@@ -971,8 +965,8 @@ class _Retrieval:
         keep = not self._bank_plan(probe, probe)                                               # (the query side's dtype is checked when pairs are scored)
         with torch.no_grad(), torch.cuda.device(dev):
             # the whole plan in one pinned buffer, one asynchronous copy (the call never waits for the device)
-            plan = torch.from_numpy(np.concatenate([row_begin, starts, lens, vptr]).astype(np.int64)).pin_memory().to(dev, non_blocking=True)
-            rb_d, st_d, ln_d, vp_d = plan[:W], plan[W:2 * W], plan[2 * W:3 * W].to(torch.int32), plan[3 * W:]
+            rb_d, st_d, ln_d, vp_d = _upload([row_begin, starts, lens, vptr], np.int64, dev)
+            ln_d = ln_d.to(torch.int32)
             vmask = torch.empty((W, T, 1), dtype=torch.uint8, device=dev)
             lmask = torch.empty((W, L), dtype=torch.bool, device=dev)
             mmask = torch.empty((W, L, L), dtype=torch.bool, device=dev)
@@ -992,32 +986,29 @@ class _Retrieval:
         return WindowBank(fv, feats, vmask, lmask, mmask, cells, starts, lens, vptr, n, st_d, ln_d, vp_d, window, stride, mode, plan_features=probe)
 
     def _window_search_plan(self, what, windows, queries, pairs, k, k_video, k_window, max_batch, duration):
-        """search_windows' checked arguments and its expansion, host arithmetic only: ``(k, k_video, k_window, plan)`` with ``plan`` a dict
-        of numpy int64 arrays -- ``vi`` / ``qi (G2,)`` the (query, video) groups sorted by (query, video), ``wi`` / ``wq (G,)`` the
-        (query, window) list (each group's windows in start order, ``wi`` a global window of the bank), ``group_ptr (G2 + 1,)`` over that
-        list and ``query_ptr (Q + 1,)`` over the groups."""
-        k_video = k if k_video is None else k_video
-        k_window = k_video if k_window is None else k_window
-        require_ints(what, ("k", k, 1, MAX_K), ("k_video", k_video, 1, MAX_K), ("k_window", k_window, 1, MAX_K), ("max_batch", max_batch, 1, 65535))
+        """search_windows' checked arguments and its expansion, host arithmetic only: ``(options, plan)`` with ``options`` an _Options
+        (``k``, ``k_video`` and ``k_window`` as ints, their defaults filled in) and ``plan`` a dict of numpy int64 arrays -- ``vi`` / ``qi
+        (G2,)`` the (query, video) groups sorted by (query, video), ``wi`` / ``wq (G,)`` the (query, window) list (each group's windows in
+        start order, ``wi`` a global window of the bank), ``group_ptr (G2 + 1,)`` over that list and ``query_ptr (Q + 1,)`` over the groups."""
+        o = _Options(what, k, k_video, max_batch, k_window, windows=True)
         if not isinstance(windows, WindowBank) or not isinstance(queries, QueryBank):
             raise ValueError(f"{what}: windows is a WindowBank (encode_windows) and queries a QueryBank (encode_queries)")
         V, Q = windows.n_videos, len(queries)
         vi, qi, query_ptr = self._listed_pairs(what, pairs, V, Q)
-        if duration is not None and tuple(duration.shape) != (V,):
-            raise ValueError(f"{what}: duration must be (V,) = ({V},) seconds (got {tuple(duration.shape)})")
+        o.duration(duration, V)
         vptr = windows.video_ptr
         nw = (vptr[1:] - vptr[:-1])[vi]                                                        # windows per group; 0 for a video without rows
         group_ptr = np.concatenate([[0], np.cumsum(nw)]).astype(np.int64)
         G2, G = vi.shape[0], int(group_ptr[-1])
-        if G * int(k_window) >= 2 ** 31 or G2 >= 2 ** 31:
-            raise ValueError(f"{what}: {G} (query, window) pairs of {k_window} moments in {G2} groups exceed the merges' 2**31 candidates / groups")
+        if G * o.k_window >= 2 ** 31 or G2 >= 2 ** 31:
+            raise ValueError(f"{what}: {G} (query, window) pairs of {o.k_window} moments in {G2} groups exceed the merges' 2**31 candidates / groups")
         wi = np.concatenate([np.arange(vptr[v], vptr[v + 1]) for v in vi]).astype(np.int64) if G else np.zeros(0, np.int64)
-        plan = dict(vi=vi, qi=qi, wi=wi, wq=np.repeat(qi, nw), group_ptr=group_ptr, query_ptr=query_ptr)
-        return int(k), int(k_video), int(k_window), plan
+        return o, dict(vi=vi, qi=qi, wi=wi, wq=np.repeat(qi, nw), group_ptr=group_ptr, query_ptr=query_ptr)
 
     @staticmethod
-    def _window_times(r, duration, n_rows):
-        r["times"] = window_times(r["video"], r["span"], duration, n_rows)           # moments' one formula, on each entry's own video
+    def _window_result(r, duration, n_rows):
+        if duration is not None:
+            r["times"] = window_times(r["video"], r["span"], duration, n_rows)       # moments' one formula, on each entry's own video
         return r
 
     def search_windows(self, windows, queries, pairs=None, k=5, k_video=None, k_window=None, nms_thresh=0.5, duration=None, max_batch=64,
@@ -1051,44 +1042,31 @@ class _Retrieval:
                              "shard's videos)")
         if carry and video_weight is None and max_videos is None:
             video_weight = 0.0
-        k, k_video, k_window, p = self._window_search_plan("search_windows", windows, queries, pairs, k, k_video, k_window, max_batch, duration)
-        video_level = video_weight is not None or max_videos is not None
-        if video_level:
-            alpha, cut_v, tau, n_videos, gt = self._video_options("search_windows", video_weight, max_videos, tau, n_videos, gt_video, k, len(queries))
+        o, p = self._window_search_plan("search_windows", windows, queries, pairs, k, k_video, k_window, max_batch, duration)
+        if video_weight is not None or max_videos is not None:
+            o.video_level(video_weight, max_videos, tau, n_videos, gt_video, len(queries))
         require_hip_tensors("search_windows", dict(windows=windows.video_mask, queries=queries.query_features), must="hold HIP tensors")
-        dev, G, G2, Q, V = windows.device, p["wi"].shape[0], p["vi"].shape[0], len(queries), windows.n_videos
-        if video_level:
-            parts = [p["wi"], p["wq"], p["group_ptr"], p["vi"], p["query_ptr"], windows.n_rows, gt]
-            with torch.no_grad(), torch.cuda.device(dev):
-                plan = torch.from_numpy(np.concatenate(parts).astype(np.int64)).pin_memory().to(dev, non_blocking=True)
-                wi_d, wq_d, gp_d, vid_d, qp_d, nr_d, gt_d = plan.split([a.shape[0] for a in parts])
-                wi32, wq32, vid32, qp32 = (x.to(torch.int32) for x in (wi_d, wq_d, vid_d, qp_d))
-                pools = _pool_buffers(G, dev)
-                idx, score, count = self._pair_moments(windows, queries, p["wi"], p["wq"], wi32, wq32, k_window, nms_thresh, max_batch,
-                                                       pools=(tau,) + pools)
-                g = merge_window_moments(idx, score, count, windows.start.index_select(0, wi_d), windows.len.index_select(0, wi_d), gp_d,
-                                         self.T, self.L, k=k_video, nms_thresh=nms_thresh)
-                gs, gc = group_pool(pools[1], pools[2], gp_d, tau)
-                vr = rank_videos(gs, gc, vid32, qp32, n=n_videos, alpha=alpha, gt_video=gt_d if gt.size else None)
-                g_score, g_count = reweight_moments(g["score"], g["count"], vr["pair_rank"], vr["weight"], cut_v)
-                r = corpus_span_topk(g["span"], g_score, g["window"], g["cell"], g_count, vid32, qp32, k=k)
-                if carry:
-                    r["raw"] = _carry_raw(r["video"], (r["window"].unsqueeze(-1), r["cell"]), (g["window"].unsqueeze(-1), g["cell"]), g["score"],
-                                          g["count"], V)
-                    r["pair_score"], r["pair_cells"] = gs.reshape(Q, V), gc.reshape(Q, V)
-                r.update(video_rank=vr["video"], video_score=vr["score"], video_count=vr["count"], gt_rank=vr["gt_rank"])
-                return r if duration is None else self._window_times(r, duration, nr_d)
-        host = np.concatenate([p["wi"], p["wq"], p["group_ptr"], p["vi"], p["query_ptr"], windows.n_rows]).astype(np.int64)
+        dev, Q, V = windows.device, len(queries), windows.n_videos
         with torch.no_grad(), torch.cuda.device(dev):
-            plan = torch.from_numpy(host).pin_memory().to(dev, non_blocking=True)
-            cut = np.cumsum([0, G, G, G2 + 1, G2, Q + 1, V])
-            wi_d, wq_d, gp_d, gv_d, qp_d, nr_d = (plan[cut[j]:cut[j + 1]] for j in range(6))
+            # the whole plan in one pinned buffer, one asynchronous copy (the call never waits for the device)
+            wi_d, wq_d, gp_d, vid_d, qp_d, nr_d, gt_d = _upload([p["wi"], p["wq"], p["group_ptr"], p["vi"], p["query_ptr"], windows.n_rows, o.gt],
+                                                                np.int64, dev)
             wi32, wq32 = wi_d.to(torch.int32), wq_d.to(torch.int32)
-            idx, score, count = self._pair_moments(windows, queries, p["wi"], p["wq"], wi32, wq32, k_window, nms_thresh, max_batch)
-            g = merge_window_moments(idx, score, count, windows.start.index_select(0, wi_d), windows.len.index_select(0, wi_d), gp_d,
-                                     self.T, self.L, k=k_video, nms_thresh=nms_thresh)
-            r = corpus_span_topk(g["span"], g["score"], g["window"], g["cell"], g["count"], gv_d.to(torch.int32), qp_d.to(torch.int32), k=k)
-            return r if duration is None else self._window_times(r, duration, nr_d)
+            # the groups' lists as the kernels read them, cast where each mode has always cast them -- in front of the loop with the
+            # video-level options, behind the merge without --: the device sees the same launches in the same order
+            narrow = lambda: (vid_d.to(torch.int32), qp_d.to(torch.int32))
+            groups = narrow() if o.ranked else None
+            lists, pools = self._pair_chunks(windows, queries, wi32, wq32, max_batch, host=(p["wi"], p["wq"]), cut=(o.k_window, nms_thresh),
+                                             tau=o.tau if o.ranked else None)
+            g = merge_window_moments(lists["idx"], lists["score"], lists["count"], windows.start.index_select(0, wi_d),
+                                     windows.len.index_select(0, wi_d), gp_d, self.T, self.L, k=o.k_video, nms_thresh=nms_thresh)
+            pooled = group_pool(pools[1], pools[2], gp_d, o.tau) if o.ranked else None
+            r = _rank_lists(o, g, *(groups or narrow()), gt_d, pooled)
+            if carry:
+                r["raw"] = _carry_raw(r["video"], (r["window"].unsqueeze(-1), r["cell"]), (g["window"].unsqueeze(-1), g["cell"]), g["score"],
+                                      g["count"], V)
+                r["pair_score"], r["pair_cells"] = pooled[0].reshape(Q, V), pooled[1].reshape(Q, V)
+        return self._window_result(r, duration, nr_d)
 
     def search_windows_torch(self, windows, queries, raw=None, pairs=None, k=5, k_video=None, k_window=None, nms_thresh=0.5, duration=None,
                              max_batch=64, scorer=None, pair_rank=None, weight=None, max_videos=None):
@@ -1101,7 +1079,8 @@ class _Retrieval:
         (G2,)`` with ``max_videos``: moments.reweight_moments_torch on the groups' merged lists in front of the ranking (the tests feed it
         the kernels' ranks and weights of ``search_windows(video_weight=..., max_videos=...)``)."""
         what = "search_windows_torch"
-        k, k_video, k_window, p = self._window_search_plan(what, windows, queries, pairs, k, k_video, k_window, max_batch, duration)
+        o, p = self._window_search_plan(what, windows, queries, pairs, k, k_video, k_window, max_batch, duration)
+        k, k_video, k_window = o.k, o.k_video, o.k_window
         if scorer is None and raw is None:
             raise ValueError(f"{what}: needs raw, the rows the bank was encoded from, or a scorer")
         dev, T, L, G = windows.device, self.T, self.L, p["wi"].shape[0]
@@ -1132,7 +1111,7 @@ class _Retrieval:
                 g["score"], g["count"] = reweight_moments_torch(g["score"], g["count"], pair_rank, weight, max_videos)
             r = corpus_span_topk_torch(g["span"], g["score"], g["window"], g["cell"], g["count"], on(p["vi"], torch.int32),
                                        on(p["query_ptr"], torch.int32), k=k)
-            return r if duration is None else self._window_times(r, duration, on(windows.n_rows))
+            return r if duration is None else self._window_result(r, duration, on(windows.n_rows))
 
     # ---------------------------------------------------------------- hard-negative mining
     def pair_scores(self, videos, queries, max_batch=64, pool=None, tau=0.1):
@@ -1143,13 +1122,14 @@ class _Retrieval:
         torch.no_grad(); no host read."""
         if pool not in (None, "lme"):
             raise ValueError(f"pair_scores: pool must be None (the best moment) or 'lme' (the pooled pair score), got {pool!r}")
-        _, _, vi, qi, _ = self._search_plan("pair_scores", videos, queries, None, 1, 1, max_batch, None)
-        dev = videos.video_features.device
+        _, vi, qi, _ = self._search_plan("pair_scores", videos, queries, None, 1, 1, max_batch, None)
+        dev = videos.device
         with torch.no_grad(), torch.cuda.device(dev):
-            vi_d, qi_d = torch.from_numpy(np.concatenate([vi, qi]).astype(np.int32)).pin_memory().to(dev, non_blocking=True).split(vi.shape[0])
+            vi_d, qi_d = _upload([vi, qi], np.int32, dev)
             if pool == "lme":
-                return self._pair_pools(videos, queries, vi, qi, vi_d, qi_d, _temperature("pair_scores", tau), max_batch)[0].reshape(len(queries), len(videos))
-            _, score, _ = self._pair_moments(videos, queries, vi, qi, vi_d, qi_d, 1, 1.0, max_batch)   # (an empty slot's score is 0)
+                score = self._pair_chunks(videos, queries, vi_d, qi_d, max_batch, host=(vi, qi), tau=_temperature("pair_scores", tau))[1][0]
+            else:
+                score = self._pair_chunks(videos, queries, vi_d, qi_d, max_batch, host=(vi, qi), cut=(1, 1.0))[0]["score"]   # (an empty slot's score is 0)
         return score.reshape(len(queries), len(videos))
 
     def mine_pairs(self, videos, queries, gt_video, negatives, skip=0, max_batch=64, pool=None, tau=0.1):
@@ -1168,8 +1148,8 @@ class _Retrieval:
         score_pairs, to compare the ranking on equal scores).  ``pair_rank`` / ``weight (P,)`` with ``max_videos``:
         moments.reweight_moments_torch on the pairs' lists in front of the ranking (the tests feed it the kernels' ranks and weights of
         ``search(video_weight=..., max_videos=...)``)."""
-        k, k_video, vi, qi, pair_ptr = self._search_plan("search_torch", videos, queries, pairs, k, k_video, max_batch, duration)
-        dev, L, P = videos.video_features.device, self.L, vi.shape[0]
+        o, vi, qi, pair_ptr = self._search_plan("search_torch", videos, queries, pairs, k, k_video, max_batch, duration)
+        k, k_video, dev, L, P = o.k, o.k_video, videos.device, self.L, vi.shape[0]
         idx, score, count, chunks = _chunk_buffers(P, k_video, max_batch, dev)
         with torch.no_grad():
             for c0, c1 in chunks:
