@@ -579,6 +579,80 @@ def test_model_windows(model, groups, meter=None, *, window=None, stride=None, k
 test_model_windows.__test__ = False
 
 
+# ---------------------------------------------------------------- a corpus in shards: the walk and the two folds of lists
+def _encode_shard(model, counted):
+    """A fold's encode step for a shard of videos: ``encode_videos`` on the shard's four arguments, where ``counted`` with the shard's
+    ``cell_counts`` (None if it has none)."""
+    def encode(shard):
+        counts = {"cell_counts": shard.get("cell_counts")} if counted else {}
+        return model.encode_videos(shard["video_features"], shard["video_mask"], shard["length_mask"], shard["moment_mask"], **counts)
+    return encode
+
+
+def _encode_window_shard(model, **options):
+    """A fold's encode step for a shard of long videos: ``encode_windows`` on the shard's ``raw`` and the host ``lengths`` the walk read."""
+    return lambda shard, lengths: model.encode_windows(shard["raw"], lengths, **options)
+
+
+def _walk_shards(what, shards, encode, fold, windows=False):
+    """The one walk over a corpus in shards.  A shard of videos is encoded by ``encode(shard)`` and its host ``duration (V_s,)`` then
+    checked against ``len(bank)``; a shard of ``windows`` has its duration checked against its ``lengths`` first and is then encoded by
+    ``encode(shard, lengths)``.  ``fold(bank, seen)`` gets each bank with the number of videos before it.  Returns the durations
+    (float64) and, for windows, the row counts (int64), each concatenated as a host array.  ValueError under the name ``what`` for a
+    duration that does not cover its shard, and for no shard at all."""
+    seen, durations, rows = 0, [], []
+    for shard in shards:
+        if windows:
+            n = host_array(shard["lengths"])
+        else:
+            bank = encode(shard)
+        d = host_array(shard["duration"], np.float64)
+        count = n.shape[0] if windows else len(bank)
+        if d.shape[0] != count:
+            raise ValueError(f"{what}: duration must cover the shard's {count} videos (got {d.shape[0]})")
+        if windows:
+            bank = encode(shard, n)
+            rows.append(n)
+        fold(bank, seen)
+        seen += count
+        durations.append(d)
+    if not durations:
+        raise ValueError(f"{what}: at least one shard of videos")
+    return (np.concatenate(durations), np.concatenate(rows)) if windows else (np.concatenate(durations),)
+
+
+def _fold_lists(what, shards, encode, search, merge, k, windows=False):
+    """The plain fold: ``search(bank)`` per shard, the first list taken as it is, then ``carry = merge([carry, r], [0, videos seen],
+    k=k)``.  Returns the carry and the walk's host arrays."""
+    carry = None
+
+    def fold(bank, seen):
+        nonlocal carry
+        r = search(bank)
+        carry = r if carry is None else merge([carry, r], [0, seen], k=k)
+    totals = _walk_shards(what, shards, encode, fold, windows)
+    return (carry, *totals)
+
+
+def _fold_lists_weighted(what, shards, encode, search, merge, k, k_video, video_weight, max_videos, n_videos, gt_video, windows=False):
+    """The fold with the video-level options: ``search(bank, k=slots, ..., carry=True)`` per shard, then ``carry = merge([carry, r], [0,
+    videos seen], k=slots, ...)`` with the first list merged alone; ``gt_video`` goes to the device once, at the first shard.  Returns
+    the carry cut to ``k`` and the walk's host arrays."""
+    from .moments import MAX_K, carry_slots, truncate_search
+    slots = carry_slots(k, k_video, max_videos)                  # what every list of the fold holds, so that the cut drops none of the final k
+    options = dict(video_weight=video_weight, max_videos=max_videos, n_videos=min(k, MAX_K) if n_videos is None else n_videos)
+    carry = gt_d = None
+
+    def fold(bank, seen):
+        nonlocal carry, gt_d
+        r = search(bank, k=slots, carry=True, **options)
+        if carry is None:
+            gt_d = _gt_on_device(gt_video, bank.device)
+        carry = merge([r] if carry is None else [carry, r], [0] if carry is None else [0, seen], k=slots, gt_video=gt_d, **options)
+    totals = _walk_shards(what, shards, encode, fold, windows)
+    return (truncate_search(carry, k), *totals)
+
+
 def search_shards(model, video_shards, queries, *, k=25, k_video=5, nms_thresh=0.5, max_batch=64):
     """``model.search`` over a corpus that comes in shards: ``queries`` is a QueryBank (``model.encode_queries``), ``video_shards`` an
     iterable of dicts with ``encode_videos``' four arguments and a host ``duration (V_s,)``.  Per shard: ``encode_videos``, ``search``
@@ -586,21 +660,9 @@ def search_shards(model, video_shards, queries, *, k=25, k_video=5, nms_thresh=0
     on one bank of all the videos.  One shard's bank is alive at a time.  Returns ``(carry, duration)``: the
     ranked list with global video ids in shard order, and the shards' durations concatenated as a host float64 array.  Host reads:
     ``encode_videos``' own count read per shard."""
-    import numpy as np
     from .moments import merge_search
-    carry, seen, durations = None, 0, []
-    for shard in video_shards:
-        bank = model.encode_videos(shard["video_features"], shard["video_mask"], shard["length_mask"], shard["moment_mask"])
-        d = host_array(shard["duration"], np.float64)
-        if d.shape[0] != len(bank):
-            raise ValueError(f"search_shards: duration must cover the shard's {len(bank)} videos (got {d.shape[0]})")
-        r = model.search(bank, queries, k=k, k_video=k_video, nms_thresh=nms_thresh, max_batch=max_batch)
-        carry = r if carry is None else merge_search([carry, r], [0, seen], k=k)
-        seen += len(bank)
-        durations.append(d)
-    if carry is None:
-        raise ValueError("search_shards: at least one shard of videos")
-    return carry, np.concatenate(durations)
+    return _fold_lists("search_shards", video_shards, _encode_shard(model, counted=False),        # not the shard's cell_counts, as ever
+                       lambda bank: model.search(bank, queries, k=k, k_video=k_video, nms_thresh=nms_thresh, max_batch=max_batch), merge_search, k)
 
 
 def _video_level(video_weight, max_videos, video_meter):
@@ -611,18 +673,64 @@ def _video_level(video_weight, max_videos, video_meter):
     return on, 0.0 if on and video_weight is None and max_videos is None else video_weight
 
 
-def _corpus_result(model, carry, meter, gv, gt, duration, dev):
-    """The end of a corpus test loop over a merged list ``carry``: gt_video (int64, first: 8-byte aligned), then the durations and gt_times
-    (fp32), as bytes of one pinned buffer -- one asynchronous copy --, the list's ``times``, one ``meter.update`` and the one
-    ``meter.result()``."""
-    import numpy as np
-    from .moments import search_times
-    Q, V_all = gv.shape[0], duration.shape[0]
-    host = np.concatenate([gv.astype(np.int64).view(np.uint8), np.concatenate([duration, gt.reshape(-1)]).astype(np.float32).view(np.uint8)])
+def _corpus_loop_check(what, meter, k, k_video, queries, gt_video, gt_times):
+    """What a corpus test loop refuses before anything runs: a ``k`` below ``max(n) * k_video`` of the meter (of the default one, if none
+    is given) and a ground truth that does not cover the queries.  Returns ``(gt_video, gt_times (Q, 2) float64, Q)`` as host values."""
+    n_max = 5 if meter is None else max(meter.n)
+    if k < n_max or k < n_max * k_video:
+        raise ValueError(f"{what}: k = {k} entries per query cannot give an exact R@{n_max} / VR@{n_max} at k_video = {k_video}: "
+                         f"needs k >= max(n) * k_video = {n_max * k_video}")
+    gv, gt = host_array(gt_video), host_array(gt_times, np.float64, (-1, 2))
+    Q = queries["query_features"].shape[0]
+    if gv.shape[0] != Q or gt.shape[0] != Q:
+        raise ValueError(f"{what}: gt_video (Q,) and gt_times (Q, 2) must cover the Q = {Q} queries (got {gv.shape}, {gt.shape})")
+    return gv, gt, Q
+
+
+def _corpus_loop_begin(model, queries, meter):
+    """The start of a corpus test loop once ``_corpus_loop_check`` has passed: ``model.eval()``, the queries encoded once, and a default
+    ``CorpusMeter`` on their device if none is given.  Returns ``(query bank, meter, device)``."""
+    model.eval()
+    bank = model.encode_queries(queries["query_features"], queries["query_mask"])
+    dev = queries["query_features"].device
+    if meter is None:
+        from .meter import CorpusMeter
+        meter = CorpusMeter(device=dev)
+    return bank, meter, dev
+
+
+def _gt_video_check(what, gv, V, of="shards"):
+    """ValueError under the name ``what`` unless every query's video is one of the ``V`` videos of the shard(s)."""
+    if gv.shape[0] and (gv.min() < 0 or gv.max() >= V):
+        raise ValueError(f"{what}: gt_video must lie in [0, {V}), the videos of the {of}")
+
+
+def _send_ground_truth(gv, n_rows, duration, gt, dev):
+    """A corpus test loop's host values on ``dev``: gt_video and, if given, the videos' row counts (int64, first: 8-byte aligned), then the
+    durations and gt_times (fp32), as bytes of one pinned buffer -- one asynchronous copy.  Returns views of it by name: ``gt_video (Q,)``,
+    ``n_rows (V,)`` or None, ``duration (V,)`` and ``gt_times (Q, 2)``."""
+    Q, V = gv.shape[0], duration.shape[0]
+    ints = gv if n_rows is None else np.concatenate([gv, n_rows])
+    host = np.concatenate([ints.astype(np.int64).view(np.uint8), np.concatenate([duration, gt.reshape(-1)]).astype(np.float32).view(np.uint8)])
     buf = torch.from_numpy(host).pin_memory().to(dev, non_blocking=True)
-    gv_d, f32 = buf[:8 * Q].view(torch.int64), buf[8 * Q:].view(torch.float32)
-    carry["times"] = search_times(carry["video"], carry["idx"], f32[:V_all], model.L)
-    meter.update(carry, gv_d, f32[V_all:].reshape(Q, 2))
+    i64, f32 = buf[:8 * ints.shape[0]].view(torch.int64), buf[8 * ints.shape[0]:].view(torch.float32)
+    return dict(gt_video=i64[:Q], n_rows=None if n_rows is None else i64[Q:], duration=f32[:V], gt_times=f32[V:].reshape(Q, 2))
+
+
+def _corpus_loop_end(what, model, carry, meter, gv, gt, duration, dev, *, n_rows=None, video_meter=None, rank="gt_rank", sent=None):
+    """The end of a corpus test loop over its ranked list ``carry``: gt_video checked against the corpus' ``duration (V_all,)``,
+    ``video_meter`` (if any) updated with the list's ``rank`` key, the host values sent (``_send_ground_truth``), the list's ``times``
+    -- ``window_times`` with ``n_rows``, else ``search_times`` --, one ``meter.update`` and the one ``meter.result()``.  ``sent``: the
+    device views of a loop that sent them before its search, whose list then has its times."""
+    from .moments import search_times, window_times
+    _gt_video_check(what, gv, duration.shape[0])
+    if video_meter is not None:
+        video_meter.update(carry[rank])
+    if sent is None:
+        sent = _send_ground_truth(gv, n_rows, duration, gt, dev)
+        carry["times"] = (search_times(carry["video"], carry["idx"], sent["duration"], model.L) if n_rows is None else
+                          window_times(carry["video"], carry["span"], sent["duration"], sent["n_rows"]))
+    meter.update(carry, sent["gt_video"], sent["gt_times"])
     return meter.result()
 
 
@@ -645,45 +753,24 @@ def test_model_corpus(model, video_shards, queries, gt_video, gt_times, meter=No
     at ``video_weight=0.0``, which leaves the moments' list as it is and adds the video ranking).  With any of them the corpus
     must come as ONE shard -- the weight needs the corpus-wide best score and rank, which a merge of plain shard lists does not have;
     ValueError for more (``test_model_corpus_weighted_shards`` is the loop whose shard lists carry them).  The shard may carry ``cell_counts`` (encode_videos'), and the loop then reads nothing but ``meter.result()``."""
-    import numpy as np
+    what = "test_model_corpus"
     video_level, video_weight = _video_level(video_weight, max_videos, video_meter)
     if video_level:
         video_shards = list(video_shards)
         if len(video_shards) != 1:
             raise ValueError(f"test_model_corpus: video_weight / max_videos / video_meter need the corpus as one shard (got {len(video_shards)}): "
                              "the video weight and rank are corpus-wide, and the plain shard merges do not carry them (test_model_corpus_weighted_shards does)")
-    n_max = 5 if meter is None else max(meter.n)
-    if k < n_max or k < n_max * k_video:
-        raise ValueError(f"test_model_corpus: k = {k} entries per query cannot give an exact R@{n_max} / VR@{n_max} at k_video = {k_video}: "
-                         f"needs k >= max(n) * k_video = {n_max * k_video}")
-    gv, gt = host_array(gt_video), host_array(gt_times, np.float64, (-1, 2))
-    Q = queries["query_features"].shape[0]
-    if gv.shape[0] != Q or gt.shape[0] != Q:
-        raise ValueError(f"test_model_corpus: gt_video (Q,) and gt_times (Q, 2) must cover the Q = {Q} queries (got {gv.shape}, {gt.shape})")
-    model.eval()
-    bank = model.encode_queries(queries["query_features"], queries["query_mask"])
-    dev = queries["query_features"].device
-    if meter is None:
-        from .meter import CorpusMeter
-        meter = CorpusMeter(device=dev)
-    if video_level:
-        shard = video_shards[0]
-        videos = model.encode_videos(shard["video_features"], shard["video_mask"], shard["length_mask"], shard["moment_mask"],
-                                     cell_counts=shard.get("cell_counts"))
-        duration = host_array(shard["duration"], np.float64)
-        if duration.shape[0] != len(videos):
-            raise ValueError(f"test_model_corpus: duration must cover the shard's {len(videos)} videos (got {duration.shape[0]})")
-        if Q and (gv.min() < 0 or gv.max() >= duration.shape[0]):
-            raise ValueError(f"test_model_corpus: gt_video must lie in [0, {duration.shape[0]}), the videos of the shard")
-        carry = model.search(videos, bank, k=k, k_video=k_video, nms_thresh=nms_thresh, max_batch=max_batch, video_weight=video_weight,
-                             max_videos=max_videos, tau=tau, gt_video=gv)
-        if video_meter is not None:
-            video_meter.update(carry["gt_rank"])
+    gv, gt, _ = _corpus_loop_check(what, meter, k, k_video, queries, gt_video, gt_times)
+    bank, meter, dev = _corpus_loop_begin(model, queries, meter)
+    if video_level:                                                       # the one shard, searched directly once gt_video is known to fit it
+        def search(videos):
+            _gt_video_check(what, gv, len(videos), of="shard")
+            return model.search(videos, bank, k=k, k_video=k_video, nms_thresh=nms_thresh, max_batch=max_batch, video_weight=video_weight,
+                                max_videos=max_videos, tau=tau, gt_video=gv)
+        carry, duration = _fold_lists(what, video_shards, _encode_shard(model, counted=True), search, None, k)      # one list: no merge
     else:
         carry, duration = search_shards(model, video_shards, bank, k=k, k_video=k_video, nms_thresh=nms_thresh, max_batch=max_batch)
-        if Q and (gv.min() < 0 or gv.max() >= duration.shape[0]):
-            raise ValueError(f"test_model_corpus: gt_video must lie in [0, {duration.shape[0]}), the videos of the shards")
-    return _corpus_result(model, carry, meter, gv, gt, duration, dev)
+    return _corpus_loop_end(what, model, carry, meter, gv, gt, duration, dev, video_meter=video_meter)
 
 
 test_model_corpus.__test__ = False
@@ -706,38 +793,19 @@ def test_model_corpus_windows(model, raw, lengths, queries, gt_video, gt_times, 
     meter.VideoRankMeter, updated with the search's ``gt_rank`` (given alone, the search runs at ``video_weight=0.0``: the same moments'
     list, plus the video ranking).  This loop searches one bank, so there is no shard limit here; the
     sharded loop (``test_model_corpus_window_shards``) takes none of these."""
-    import numpy as np
-    n_max = 5 if meter is None else max(meter.n)
-    if k < n_max or k < n_max * k_video:
-        raise ValueError(f"test_model_corpus_windows: k = {k} entries per query cannot give an exact R@{n_max} / VR@{n_max} at k_video = {k_video}: "
-                         f"needs k >= max(n) * k_video = {n_max * k_video}")
-    gv, gt, dur = host_array(gt_video), host_array(gt_times, np.float64, (-1, 2)), host_array(duration, np.float64)
-    Q, V = queries["query_features"].shape[0], host_array(lengths).shape[0]
-    if gv.shape[0] != Q or gt.shape[0] != Q:
-        raise ValueError(f"test_model_corpus_windows: gt_video (Q,) and gt_times (Q, 2) must cover the Q = {Q} queries (got {gv.shape}, {gt.shape})")
+    what = "test_model_corpus_windows"
+    gv, gt, Q = _corpus_loop_check(what, meter, k, k_video, queries, gt_video, gt_times)
+    dur, V = host_array(duration, np.float64), host_array(lengths).shape[0]
     if dur.shape[0] != V or (Q and (gv.min() < 0 or gv.max() >= V)):
         raise ValueError(f"test_model_corpus_windows: duration must be (V,) = ({V},) seconds and gt_video lie in [0, {V}) (got {dur.shape})")
-    model.eval()
-    dev = queries["query_features"].device
-    if meter is None:
-        from .meter import CorpusMeter
-        meter = CorpusMeter(device=dev)
-    # gt_video (int64, first: 8-byte aligned), then the durations and gt_times (fp32), as bytes of one pinned buffer: one asynchronous copy
-    host = np.concatenate([gv.astype(np.int64).view(np.uint8), np.concatenate([dur, gt.reshape(-1)]).astype(np.float32).view(np.uint8)])
-    buf = torch.from_numpy(host).pin_memory().to(dev, non_blocking=True)
-    gv_d, f32 = buf[:8 * Q].view(torch.int64), buf[8 * Q:].view(torch.float32)
-    bank = model.encode_queries(queries["query_features"], queries["query_mask"])
+    sent = _send_ground_truth(gv, None, dur, gt, queries["query_features"].device)        # before the search, which takes the durations
+    bank, meter, dev = _corpus_loop_begin(model, queries, meter)
     windows = model.encode_windows(raw, lengths, window=window, stride=stride, max_batch=max_batch)
     video_level, video_weight = _video_level(video_weight, max_videos, video_meter)
-    if video_level:
-        r = model.search_windows(windows, bank, k=k, k_video=k_video, k_window=k_window, nms_thresh=nms_thresh, duration=f32[:V], max_batch=max_batch,
-                                 video_weight=video_weight, max_videos=max_videos, tau=tau, gt_video=gv)
-        if video_meter is not None:
-            video_meter.update(r["gt_rank"])
-    else:
-        r = model.search_windows(windows, bank, k=k, k_video=k_video, k_window=k_window, nms_thresh=nms_thresh, duration=f32[:V], max_batch=max_batch)
-    meter.update(r, gv_d, f32[V:].reshape(Q, 2))
-    return meter.result()
+    options = dict(video_weight=video_weight, max_videos=max_videos, tau=tau, gt_video=gv) if video_level else {}
+    r = model.search_windows(windows, bank, k=k, k_video=k_video, k_window=k_window, nms_thresh=nms_thresh, duration=sent["duration"],
+                             max_batch=max_batch, **options)
+    return _corpus_loop_end(what, model, r, meter, gv, gt, dur, dev, video_meter=video_meter, sent=sent)
 
 
 test_model_corpus_windows.__test__ = False
@@ -751,22 +819,10 @@ def search_window_shards(model, shards, queries, *, window=None, stride=None, k=
     bank of all the videos.  A SHARD MUST HOLD WHOLE VIDEOS: the NMS of a (query, video) group runs within one bank.  One shard's bank
     is alive at a time.  Returns ``(carry, duration, n_rows)``: the ranked list with global video ids in shard order, and the shards'
     durations (float64) and row counts (int64) concatenated as host arrays.  No host read."""
-    import numpy as np
     from .moments import merge_search_windows
-    carry, seen, durations, rows = None, 0, [], []
-    for shard in shards:
-        n, d = host_array(shard["lengths"]), host_array(shard["duration"], np.float64)
-        if d.shape[0] != n.shape[0]:
-            raise ValueError(f"search_window_shards: duration must cover the shard's {n.shape[0]} videos (got {d.shape[0]})")
-        bank = model.encode_windows(shard["raw"], n, window=window, stride=stride, max_batch=max_batch)
-        r = model.search_windows(bank, queries, k=k, k_video=k_video, k_window=k_window, nms_thresh=nms_thresh, max_batch=max_batch)
-        carry = r if carry is None else merge_search_windows([carry, r], [0, seen], k=k)
-        seen += n.shape[0]
-        durations.append(d)
-        rows.append(n)
-    if carry is None:
-        raise ValueError("search_window_shards: at least one shard of videos")
-    return carry, np.concatenate(durations), np.concatenate(rows)
+    return _fold_lists("search_window_shards", shards, _encode_window_shard(model, window=window, stride=stride, max_batch=max_batch),
+                       lambda bank: model.search_windows(bank, queries, k=k, k_video=k_video, k_window=k_window, nms_thresh=nms_thresh,
+                                                         max_batch=max_batch), merge_search_windows, k, windows=True)
 
 
 def test_model_corpus_window_shards(model, shards, queries, gt_video, gt_times, meter=None, *, window=None, stride=None, k=25, k_video=5,
@@ -781,36 +837,12 @@ def test_model_corpus_window_shards(model, shards, queries, gt_video, gt_times, 
     The meter is not reset here.
 
     VR@n is exact when ``k >= max(n) * k_video``, as in ``test_model_corpus``; anything less raises ValueError before any retrieval runs."""
-    import numpy as np
-    from .moments import window_times
-    n_max = 5 if meter is None else max(meter.n)
-    if k < n_max or k < n_max * k_video:
-        raise ValueError(f"test_model_corpus_window_shards: k = {k} entries per query cannot give an exact R@{n_max} / VR@{n_max} at k_video = "
-                         f"{k_video}: needs k >= max(n) * k_video = {n_max * k_video}")
-    gv, gt = host_array(gt_video), host_array(gt_times, np.float64, (-1, 2))
-    Q = queries["query_features"].shape[0]
-    if gv.shape[0] != Q or gt.shape[0] != Q:
-        raise ValueError(f"test_model_corpus_window_shards: gt_video (Q,) and gt_times (Q, 2) must cover the Q = {Q} queries (got {gv.shape}, {gt.shape})")
-    model.eval()
-    bank = model.encode_queries(queries["query_features"], queries["query_mask"])
-    dev = queries["query_features"].device
-    if meter is None:
-        from .meter import CorpusMeter
-        meter = CorpusMeter(device=dev)
+    what = "test_model_corpus_window_shards"
+    gv, gt, _ = _corpus_loop_check(what, meter, k, k_video, queries, gt_video, gt_times)
+    bank, meter, dev = _corpus_loop_begin(model, queries, meter)
     carry, duration, n_rows = search_window_shards(model, shards, bank, window=window, stride=stride, k=k, k_video=k_video, k_window=k_window,
                                                    nms_thresh=nms_thresh, max_batch=max_batch)
-    V_all = duration.shape[0]
-    if Q and (gv.min() < 0 or gv.max() >= V_all):
-        raise ValueError(f"test_model_corpus_window_shards: gt_video must lie in [0, {V_all}), the videos of the shards")
-    # gt_video and the row counts (int64, first: 8-byte aligned), then the durations and gt_times (fp32), as bytes of one pinned buffer:
-    # one asynchronous copy
-    host = np.concatenate([np.concatenate([gv, n_rows]).astype(np.int64).view(np.uint8),
-                           np.concatenate([duration, gt.reshape(-1)]).astype(np.float32).view(np.uint8)])
-    buf = torch.from_numpy(host).pin_memory().to(dev, non_blocking=True)
-    i64, f32 = buf[:8 * (Q + V_all)].view(torch.int64), buf[8 * (Q + V_all):].view(torch.float32)
-    carry["times"] = window_times(carry["video"], carry["span"], f32[:V_all], i64[Q:])
-    meter.update(carry, i64[:Q], f32[V_all:].reshape(Q, 2))
-    return meter.result()
+    return _corpus_loop_end(what, model, carry, meter, gv, gt, duration, dev, n_rows=n_rows)
 
 
 test_model_corpus_window_shards.__test__ = False
@@ -838,28 +870,11 @@ def search_shards_weighted(model, video_shards, queries, *, k=25, k_video=5, nms
     ``Q * videos seen * 8`` bytes of pooled scores.  ``gt_video``: each query's video as a global index in shard order (Q host ints),
     for ``gt_rank``.  Returns ``(carry, duration)`` as ``search_shards``; the carry also holds ``video_rank``, ``video_score``,
     ``video_count`` and ``gt_rank`` of the last merge.  Host reads: ``encode_videos``' own per shard without ``cell_counts``, else none."""
-    import numpy as np
-    from .moments import MAX_K, carry_slots, merge_search_weighted, truncate_search
-    slots = carry_slots(k, k_video, max_videos)                  # what every list of the fold holds, so that the cut drops none of the final k
-    n_videos = min(k, MAX_K) if n_videos is None else n_videos
-    carry, seen, durations, gt_d = None, 0, [], None
-    for shard in video_shards:
-        bank = model.encode_videos(shard["video_features"], shard["video_mask"], shard["length_mask"], shard["moment_mask"],
-                                   cell_counts=shard.get("cell_counts"))
-        d = host_array(shard["duration"], np.float64)
-        if d.shape[0] != len(bank):
-            raise ValueError(f"search_shards_weighted: duration must cover the shard's {len(bank)} videos (got {d.shape[0]})")
-        r = model.search(bank, queries, k=slots, k_video=k_video, nms_thresh=nms_thresh, max_batch=max_batch, video_weight=video_weight,
-                         max_videos=max_videos, tau=tau, n_videos=n_videos, carry=True)
-        if carry is None:
-            gt_d = _gt_on_device(gt_video, bank.device)
-        carry = merge_search_weighted([r] if carry is None else [carry, r], [0] if carry is None else [0, seen], k=slots, video_weight=video_weight,
-                                      max_videos=max_videos, n_videos=n_videos, gt_video=gt_d)
-        seen += len(bank)
-        durations.append(d)
-    if carry is None:
-        raise ValueError("search_shards_weighted: at least one shard of videos")
-    return truncate_search(carry, k), np.concatenate(durations)
+    from .moments import merge_search_weighted
+    return _fold_lists_weighted("search_shards_weighted", video_shards, _encode_shard(model, counted=True),
+                                lambda bank, **options: model.search(bank, queries, k_video=k_video, nms_thresh=nms_thresh, max_batch=max_batch,
+                                                                     tau=tau, **options),
+                                merge_search_weighted, k, k_video, video_weight, max_videos, n_videos, gt_video)
 
 
 def search_window_shards_weighted(model, shards, queries, *, window=None, stride=None, k=25, k_video=5, k_window=None, nms_thresh=0.5, max_batch=64,
@@ -867,41 +882,12 @@ def search_window_shards_weighted(model, shards, queries, *, window=None, stride
     """``search_window_shards`` with the video-level options: ``search_shards_weighted`` over window banks of shards of whole videos --
     ``encode_windows``, ``search_windows(..., carry=True)``, ``merge_search_windows_weighted``.  Returns ``(carry, duration, n_rows)``.  No
     host read."""
-    import numpy as np
-    from .moments import MAX_K, carry_slots, merge_search_windows_weighted, truncate_search
-    slots = carry_slots(k, k_video, max_videos)
-    n_videos = min(k, MAX_K) if n_videos is None else n_videos
-    carry, seen, durations, rows, gt_d = None, 0, [], [], None
-    for shard in shards:
-        n, d = host_array(shard["lengths"]), host_array(shard["duration"], np.float64)
-        if d.shape[0] != n.shape[0]:
-            raise ValueError(f"search_window_shards_weighted: duration must cover the shard's {n.shape[0]} videos (got {d.shape[0]})")
-        bank = model.encode_windows(shard["raw"], n, window=window, stride=stride, max_batch=max_batch)
-        r = model.search_windows(bank, queries, k=slots, k_video=k_video, k_window=k_window, nms_thresh=nms_thresh, max_batch=max_batch,
-                                 video_weight=video_weight, max_videos=max_videos, tau=tau, n_videos=n_videos, carry=True)
-        if carry is None:
-            gt_d = _gt_on_device(gt_video, bank.device)
-        carry = merge_search_windows_weighted([r] if carry is None else [carry, r], [0] if carry is None else [0, seen], k=slots,
-                                              video_weight=video_weight, max_videos=max_videos, n_videos=n_videos, gt_video=gt_d)
-        seen += n.shape[0]
-        durations.append(d)
-        rows.append(n)
-    if carry is None:
-        raise ValueError("search_window_shards_weighted: at least one shard of videos")
-    return truncate_search(carry, k), np.concatenate(durations), np.concatenate(rows)
-
-
-def _corpus_loop_check(what, meter, k, k_video, queries, gt_video, gt_times):
-    import numpy as np
-    n_max = 5 if meter is None else max(meter.n)
-    if k < n_max or k < n_max * k_video:
-        raise ValueError(f"{what}: k = {k} entries per query cannot give an exact R@{n_max} / VR@{n_max} at k_video = {k_video}: "
-                         f"needs k >= max(n) * k_video = {n_max * k_video}")
-    gv, gt = host_array(gt_video), host_array(gt_times, np.float64, (-1, 2))
-    Q = queries["query_features"].shape[0]
-    if gv.shape[0] != Q or gt.shape[0] != Q:
-        raise ValueError(f"{what}: gt_video (Q,) and gt_times (Q, 2) must cover the Q = {Q} queries (got {gv.shape}, {gt.shape})")
-    return gv, gt, Q
+    from .moments import merge_search_windows_weighted
+    return _fold_lists_weighted("search_window_shards_weighted", shards,
+                                _encode_window_shard(model, window=window, stride=stride, max_batch=max_batch),
+                                lambda bank, **options: model.search_windows(bank, queries, k_video=k_video, k_window=k_window,
+                                                                             nms_thresh=nms_thresh, max_batch=max_batch, tau=tau, **options),
+                                merge_search_windows_weighted, k, k_video, video_weight, max_videos, n_videos, gt_video, windows=True)
 
 
 def test_model_corpus_weighted_shards(model, video_shards, queries, gt_video, gt_times, meter=None, *, k=25, k_video=5, nms_thresh=0.5,
@@ -912,20 +898,11 @@ def test_model_corpus_weighted_shards(model, video_shards, queries, gt_video, gt
     meter.VideoRankMeter) is updated with the last merge's ``gt_rank``.  With ``cell_counts`` in every shard the loop reads the host once,
     at ``meter.result()``.  At equal pair scores it gives ``test_model_corpus(one shard of all the videos, same options)``' metrics."""
     what = "test_model_corpus_weighted_shards"
-    gv, gt, Q = _corpus_loop_check(what, meter, k, k_video, queries, gt_video, gt_times)
-    model.eval()
-    bank = model.encode_queries(queries["query_features"], queries["query_mask"])
-    dev = queries["query_features"].device
-    if meter is None:
-        from .meter import CorpusMeter
-        meter = CorpusMeter(device=dev)
+    gv, gt, _ = _corpus_loop_check(what, meter, k, k_video, queries, gt_video, gt_times)
+    bank, meter, dev = _corpus_loop_begin(model, queries, meter)
     carry, duration = search_shards_weighted(model, video_shards, bank, k=k, k_video=k_video, nms_thresh=nms_thresh, max_batch=max_batch,
                                              video_weight=0.0 if video_weight is None else video_weight, max_videos=max_videos, tau=tau, gt_video=gv)
-    if Q and (gv.min() < 0 or gv.max() >= duration.shape[0]):
-        raise ValueError(f"{what}: gt_video must lie in [0, {duration.shape[0]}), the videos of the shards")
-    if video_meter is not None:
-        video_meter.update(carry["gt_rank"])
-    return _corpus_result(model, carry, meter, gv, gt, duration, dev)
+    return _corpus_loop_end(what, model, carry, meter, gv, gt, duration, dev, video_meter=video_meter)
 
 
 test_model_corpus_weighted_shards.__test__ = False
@@ -938,33 +915,14 @@ def test_model_corpus_window_shards_weighted(model, shards, queries, gt_video, g
     ``carry=True`` and folded by ``search_window_shards_weighted``.  Arguments and result as ``test_model_corpus_window_shards``;
     ``video_weight`` None means 0.0; ``video_meter`` is updated with the last merge's ``gt_rank``.  One host read, ``meter.result()``.  At
     equal pair scores it gives ``test_model_corpus_windows(the concatenated corpus, same options)``' metrics."""
-    import numpy as np
-    from .moments import window_times
     what = "test_model_corpus_window_shards_weighted"
-    gv, gt, Q = _corpus_loop_check(what, meter, k, k_video, queries, gt_video, gt_times)
-    model.eval()
-    bank = model.encode_queries(queries["query_features"], queries["query_mask"])
-    dev = queries["query_features"].device
-    if meter is None:
-        from .meter import CorpusMeter
-        meter = CorpusMeter(device=dev)
+    gv, gt, _ = _corpus_loop_check(what, meter, k, k_video, queries, gt_video, gt_times)
+    bank, meter, dev = _corpus_loop_begin(model, queries, meter)
     carry, duration, n_rows = search_window_shards_weighted(model, shards, bank, window=window, stride=stride, k=k, k_video=k_video,
                                                             k_window=k_window, nms_thresh=nms_thresh, max_batch=max_batch,
                                                             video_weight=0.0 if video_weight is None else video_weight,
                                                             max_videos=max_videos, tau=tau, gt_video=gv)
-    V_all = duration.shape[0]
-    if Q and (gv.min() < 0 or gv.max() >= V_all):
-        raise ValueError(f"{what}: gt_video must lie in [0, {V_all}), the videos of the shards")
-    if video_meter is not None:
-        video_meter.update(carry["gt_rank"])
-    # gt_video and the row counts (int64, first: 8-byte aligned), then the durations and gt_times (fp32): one pinned asynchronous copy
-    host = np.concatenate([np.concatenate([gv, n_rows]).astype(np.int64).view(np.uint8),
-                           np.concatenate([duration, gt.reshape(-1)]).astype(np.float32).view(np.uint8)])
-    buf = torch.from_numpy(host).pin_memory().to(dev, non_blocking=True)
-    i64, f32 = buf[:8 * (Q + V_all)].view(torch.int64), buf[8 * (Q + V_all):].view(torch.float32)
-    carry["times"] = window_times(carry["video"], carry["span"], f32[:V_all], i64[Q:])
-    meter.update(carry, i64[:Q], f32[V_all:].reshape(Q, 2))
-    return meter.result()
+    return _corpus_loop_end(what, model, carry, meter, gv, gt, duration, dev, n_rows=n_rows, video_meter=video_meter)
 
 
 test_model_corpus_window_shards_weighted.__test__ = False
@@ -982,21 +940,12 @@ def search_shards_prefiltered(model, video_shards, queries, *, prefilter, k=25, 
     stage's temperature and the video-level one.  Returns ``(result, duration)`` as ``search_shards``; the result also holds
     ``prefilter_video``, ``prefilter_score`` and ``prefilter_gt_rank``.  Host reads: ``encode_videos``' own per shard without
     ``cell_counts``; with them, and all of one value, none."""
-    import numpy as np
-    survivors, durations = model.new_survivors(queries, prefilter, tau), []
-    for shard in video_shards:
-        bank = model.encode_videos(shard["video_features"], shard["video_mask"], shard["length_mask"], shard["moment_mask"],
-                                   cell_counts=shard.get("cell_counts"))
-        d = host_array(shard["duration"], np.float64)
-        if d.shape[0] != len(bank):
-            raise ValueError(f"search_shards_prefiltered: duration must cover the shard's {len(bank)} videos (got {d.shape[0]})")
-        model.fold_survivors(survivors, bank, queries)
-        durations.append(d)
-    if not durations:
-        raise ValueError("search_shards_prefiltered: at least one shard of videos")
+    survivors = model.new_survivors(queries, prefilter, tau)
+    duration, = _walk_shards("search_shards_prefiltered", video_shards, _encode_shard(model, counted=True),
+                             lambda bank, seen: model.fold_survivors(survivors, bank, queries))
     r = model.search_survivors(survivors, queries, k=k, k_video=k_video, nms_thresh=nms_thresh, max_batch=max_batch, video_weight=video_weight,
                                max_videos=max_videos, n_videos=n_videos, gt_video=gt_video)
-    return r, np.concatenate(durations)
+    return r, duration
 
 
 def test_model_corpus_prefiltered_shards(model, video_shards, queries, gt_video, gt_times, meter=None, *, prefilter, k=25, k_video=5,
@@ -1009,20 +958,11 @@ def test_model_corpus_prefiltered_shards(model, video_shards, queries, gt_video,
     VR@M of it is the share of queries whose video the cut keeps.  With equal ``cell_counts`` in every shard the loop reads the host
     once, at ``meter.result()``.  What the pruning loses is not bounded."""
     what = "test_model_corpus_prefiltered_shards"
-    gv, gt, Q = _corpus_loop_check(what, meter, k, k_video, queries, gt_video, gt_times)
-    model.eval()
-    bank = model.encode_queries(queries["query_features"], queries["query_mask"])
-    dev = queries["query_features"].device
-    if meter is None:
-        from .meter import CorpusMeter
-        meter = CorpusMeter(device=dev)
+    gv, gt, _ = _corpus_loop_check(what, meter, k, k_video, queries, gt_video, gt_times)
+    bank, meter, dev = _corpus_loop_begin(model, queries, meter)
     carry, duration = search_shards_prefiltered(model, video_shards, bank, prefilter=prefilter, k=k, k_video=k_video, nms_thresh=nms_thresh,
                                                 max_batch=max_batch, video_weight=video_weight, max_videos=max_videos, tau=tau, gt_video=gv)
-    if Q and (gv.min() < 0 or gv.max() >= duration.shape[0]):
-        raise ValueError(f"{what}: gt_video must lie in [0, {duration.shape[0]}), the videos of the shards")
-    if video_meter is not None:
-        video_meter.update(carry["prefilter_gt_rank"])
-    return _corpus_result(model, carry, meter, gv, gt, duration, dev)
+    return _corpus_loop_end(what, model, carry, meter, gv, gt, duration, dev, video_meter=video_meter, rank="prefilter_gt_rank")
 
 
 test_model_corpus_prefiltered_shards.__test__ = False
