@@ -484,6 +484,43 @@ def test_merge_kernel_lists_of_different_k(dev):
     assert int(want["count"][1]) == 64
 
 
+def edge_lists(ks, Q, seed):
+    """len(ks) lists of ks[s] slots: scores from six values with a NaN, both zeros and a repeated value among them, local videos in
+    [0, 3) (with equal or overlapping offsets the lists name the same global videos: the list and the position decide), counts that
+    walk through k_s + 2, -1, 0, k_s and 1; query 1, where there is one, has no entry in any list"""
+    g = torch.Generator().manual_seed(seed)
+    values = torch.tensor([float("nan"), 0.5, 0.5, 0.0, -0.0, -0.25])
+    out = []
+    for s, k in enumerate(ks):
+        count = torch.tensor([(k + 2, -1, 0, k, 1)[(q + s) % 5] for q in range(Q)], dtype=torch.int32)
+        if Q > 1:
+            count[1] = (0, -1)[s % 2]
+        out.append({"video": torch.randint(0, 3, (Q, k), generator=g, dtype=torch.int64), "idx": torch.randint(0, 64, (Q, k, 2), generator=g, dtype=torch.int64),
+                    "score": values[torch.randint(0, 6, (Q, k), generator=g)], "count": count})
+    return out
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("S", [1, 2, 16])
+@pytest.mark.parametrize("K", [1, 64])
+def test_merge_kernel_edges(dev, S, K):
+    """What the lists cut from corpus_topk_torch leave out: k_s mixing 1 and 64, Q = 1 and 3, counts below 0 and above k_s, a query
+    without an entry, one global video at one score in several lists and in several slots of a list, -0 against +0 and NaN scores
+    (the highest order word) -- every output against merge_search_torch, bit for bit."""
+    A = V()
+    nans = 0
+    for ks in ([(64, 1)[s % 2] for s in range(S)], [(1, 64)[s % 2] for s in range(S)]):
+        for Q in (1, 3):
+            lists = edge_lists(ks, Q, seed=100 * S + Q + ks[0])
+            for offsets in ([0] * S, list(range(S))):
+                want = A.merge_search_torch(lists, offsets, k=K)
+                assert int(want["count"][0]) == min(K, sum(min(max(int(r["count"][0]), 0), k) for r, k in zip(lists, ks)))
+                assert Q == 1 or int(want["count"][1]) == 0
+                nans += int(torch.isnan(want["score"]).sum())
+                same_lists(A.merge_search([to_dev(r, dev) for r in lists], offsets, k=K), want, (ks, Q, offsets))
+    assert nans > 0
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("K", [1, 5, 64])
 def test_corpus_topk_and_merge_search_agree(dev, K):

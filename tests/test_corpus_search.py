@@ -269,6 +269,29 @@ def test_corpus_topk_small(dev, K):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("K", [1, 64])
+def test_corpus_topk_edges(dev, K):
+    """What random_lists leaves out, Q = 1 at k_video = 64 and Q = 3 (the middle query without pairs) at k_video = 3: a count above
+    k_video and one below 0; the query's last two pairs name one video and hold the same scores slot by slot, two of them equal within
+    the pair, so the slot and then the pair ordinal decide; their last slot holds a NaN, which has the highest order word."""
+    A = V()
+    for per_query, kv in (([4], 64), ([3, 0, 5], 3)):
+        score, idx, count, video, ptr = random_lists(per_query, kv, seed=40 + kv, garbage=float("nan"))
+        count[0], count[1], count[-2], count[-1] = kv + 3, -2, kv, kv
+        video[-1] = video[-2]
+        score[-2, 1] = score[-2, 0]
+        score[-2, kv - 1] = float("nan")
+        score[-1] = score[-2]
+        a = (score, idx, count, video, ptr)
+        want = A.corpus_topk_torch(*a, k=K)
+        last = len(per_query) - 1
+        assert int(want["count"][last]) == min(K, 2 * kv + max(int(count[ptr[last]:-2].clamp(0, kv).sum()), 0))
+        assert len(per_query) == 1 or int(want["count"][1]) == 0
+        same_merge(A.corpus_topk(*[t.to(dev) for t in a], k=K), want, (per_query, kv))
+        assert torch.isnan(want["score"][last, 0])
+
+
+@pytest.mark.gpu
 def test_corpus_topk_many_pairs_and_none(dev):
     A = V()
     a = random_lists([700], 5, seed=5, garbage=float("nan"))

@@ -340,6 +340,26 @@ def test_prefilter_fold_kernel(dev, M, Vs):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("M", [1, 5])
+def test_prefilter_fold_signed_zeros(dev, M):
+    """What kernel_shard leaves out: -0 against +0 (equal: the lower video goes first), in the incumbents and in the shard, among scores
+    of both signs; Q = 3, the shard past one 256-wide tile."""
+    A = V()
+    Q, V0, Vs = 3, 7, 300
+    g = torch.Generator().manual_seed(M)
+    values = torch.tensor([0.0, -0.0, 0.25, -0.25])
+    draw = lambda n: (values[torch.randint(0, 4, (Q, n), generator=g)], (torch.rand(Q, n, generator=g) < 0.8).float() * 3)
+    state = A.prefilter_fold_torch(*empty_state(Q, M), *draw(V0), 0)[:3]
+    score, cells = draw(Vs)
+    assert score.view(torch.int32).eq(-2 ** 31).any() and score.view(torch.int32).eq(0).any()
+    want = A.prefilter_fold_torch(*state, score, cells, V0)
+    rc, got, bufs, _ = fold_abi(dev, state, score, cells, V0, (float("nan"), -7))
+    assert rc == 0
+    for name, x, w, b in zip(("slot_score", "slot_cells", "slot_video", "copy_src"), got, want, bufs):
+        assert torch.equal(bits(x), bits(w)) and bands_ok(b), (name, M)
+
+
+@pytest.mark.gpu
 def test_prefilter_fold_rejections(dev):
     A = V()
     Q, M, Vs, seen = 3, 5, 7, 9

@@ -398,6 +398,24 @@ def test_video_rank_bit_exact(dev, Q, Vn, n):
         assert (want["gt_rank"] >= 0).any()
 
 
+@pytest.mark.gpu
+@pytest.mark.parametrize("n", [1, 64])
+def test_video_rank_repeated_videos(dev, n):
+    """What rank_case leaves out: a query that lists a video twice, at one score (the earlier pair goes first) and at -0 against +0;
+    Q = 3 with a query without pairs between the others; the last query has no candidate."""
+    A = V()
+    score = torch.tensor([0.5, 0.75, 0.5, -0.0, 0.0, 0.75, 0.25, 0.25])
+    cells = torch.tensor([3.0, 2.0, 3.0, 1.0, 1.0, 0.0, 0.0, 0.0])
+    video = torch.tensor([4, 9, 4, 2, 2, 1, 7, 7], dtype=torch.int32)
+    ptr = torch.tensor([0, 6, 6, 8], dtype=torch.int32)
+    gt = torch.tensor([4, 0, 7], dtype=torch.int32)
+    want = A.rank_videos_torch(score, cells, video, ptr, n=n, gt_video=gt)
+    assert want["pair_rank"].tolist() == [1, 0, 2, 3, 4, -1, -1, -1] and want["gt_rank"].tolist() == [1, -1, -1] and want["count"].tolist() == [min(n, 5), 0, 0]
+    got = A.rank_videos(*[t.to(dev) for t in (score, cells, video, ptr)], n=n, gt_video=gt.to(dev))
+    for key in ("video", "count", "pair_rank", "gt_rank", "score", "weight"):
+        assert got[key].dtype == want[key].dtype and torch.equal(bits(got[key]), bits(want[key])), key
+
+
 def video_rank_abi(dev, case, top, scale, fill, **kw):
     """smin_video_rank at n = top, alpha = scale through the C ABI over outputs pre-filled with ``fill``; kw overrides arguments by name"""
     L_ = V()._lib

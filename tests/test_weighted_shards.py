@@ -451,6 +451,39 @@ def test_merge_kernel_bit_exact(dev, S, K, spans):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("spans", [False, True], ids=["cells", "spans"])
+@pytest.mark.parametrize("S", [1, 2, 16])
+@pytest.mark.parametrize("K", [1, 64])
+def test_merge_kernel_nan_scores_full_cuts_and_no_videos(dev, S, K, spans):
+    """What test_merge_kernel_bit_exact leaves out, every output against the restatement: a NaN raw score inside the counts (NaN under
+    any weight: the highest order word) and, for spans, a NaN span with a payload of its own; ranks that all lie behind the cut, so
+    every candidate drops out; and V == 0, where no video table exists.  k_s mixing 1 and 64, Q = 1 and 3."""
+    M = V().moments
+    fields = M._WEIGHTED_SPAN_FIELDS if spans else M._WEIGHTED_SEARCH_FIELDS
+    keys = SPAN_KEYS if spans else IDX_KEYS
+    ks, offsets, Vn = [(64, 1)[s % 2] for s in range(S)], [2 * s for s in range(S)], 8 + 2 * S
+    for Q in (1, 3):
+        lists = carry_lists(ks, Q, seed=50 * S + Q, spans=spans, full_query=0)
+        for r in lists:
+            r["raw"][:, 0] = float("nan")
+            r["video"][:, 0] = 1
+            if spans:
+                r["span"].view(torch.int32)[:, 0, 0] = 0x7FC12345
+        rank, weight = video_tables(Q, Vn, seed=S, reverse=False)
+        rank = rank.clamp_min(0)
+        on = [to_dev(r, dev) for r in lists]
+        for what, (rk, cut, vn) in dict(nan=(rank, 99, Vn), cut=(rank + 2, 2, Vn), none=(rank[:, :0], 0, 0)).items():
+            wt = weight[:, :vn]
+            want = M._merge_weighted_torch(lists, offsets, Q, K, fields, rk, wt, vn, cut)
+            if what == "nan":
+                assert torch.isnan(want["score"][0, 0]) and torch.isnan(want["raw"][0, 0]) and int(want["video"][0, 0]) == 1
+                assert not spans or int(bits(want["span"])[0, 0, 0]) == 0x7FC12345
+            else:
+                assert want["count"].eq(0).all() and want["video"].eq(-1).all()
+            same(M._merge_weighted("test", on, offsets, Q, K, fields, rk.to(dev), wt.to(dev), vn, cut), want, keys, (Q, what))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("spans", [False, True], ids=["cells", "spans"])
 def test_rejections_leave_the_outputs_untouched(dev, spans):
     lists = carry_lists([3, 5], 2, seed=3, spans=spans)
     rank, weight = video_tables(2, 12, seed=1, reverse=False)

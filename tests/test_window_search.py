@@ -421,6 +421,32 @@ def test_corpus_span_topk_bit_exact(dev, K, kv):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("K", [1, 64])
+def test_corpus_span_topk_edges(dev, K):
+    """What random_span_lists leaves out, Q = 1 at k_video = 64 and Q = 3 (the middle query without groups) at k_video = 3: a count above
+    k_video and one below 0; the query's last two groups name one video and hold the same scores slot by slot, two of them equal
+    within the group, so the slot and then the group ordinal decide; their last slot holds a NaN score, which has the highest order
+    word, under a NaN span with a payload of its own, which leaves as it came."""
+    A = V()
+    for per_query, kv in (([4], 64), ([3, 0, 5], 3)):
+        span, score, window, cell, count, video, ptr = random_span_lists(per_query, kv, seed=40 + kv, garbage=1e30)
+        count[0], count[1], count[-2], count[-1] = kv + 3, -2, kv, kv
+        video[-1] = video[-2]
+        score[-2, 1] = score[-2, 0]
+        score[-2, kv - 1] = float("nan")
+        score[-1] = score[-2]
+        span.view(torch.int32)[-2:, kv - 1, 0] = 0x7FC12345
+        a = (span, score, window, cell, count, video, ptr)
+        want = A.corpus_span_topk_torch(*a, k=K)
+        last = len(per_query) - 1
+        assert torch.isnan(want["score"][last, 0]) and int(bits(want["span"])[last, 0, 0]) == 0x7FC12345
+        assert int(want["count"][last]) == min(K, 2 * kv + int(count[ptr[last]:-2].clamp(0, kv).sum()))
+        assert len(per_query) == 1 or int(want["count"][1]) == 0
+        same_lists(through_ctypes(a, K, dev), want, (per_query, kv))
+        same_lists(A.corpus_span_topk(*[t.to(dev) for t in a], k=K), want, (per_query, kv, "operator"))
+
+
+@pytest.mark.gpu
 def test_corpus_span_topk_many_groups_none_and_rejections(dev):
     A = V()
     a = random_span_lists([700], 5, seed=5, garbage=float("nan"))

@@ -366,6 +366,29 @@ def test_merge_kernel_bit_exact(dev, S, K):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("S", [1, 2, 16])
+@pytest.mark.parametrize("K", [1, 64])
+def test_merge_kernel_nan_scores_and_payloads(dev, S, K):
+    """What ranked_lists leaves out: every list opens with a NaN score (the highest order word, so the list stays ordered) on local
+    video 1 -- with equal offsets one global video at one score in every list -- under a NaN span with a payload of its own, which
+    leaves as it came; k_s mixing 1 and 64, Q = 1 and 3, equal and overlapping offsets."""
+    A = V()
+    ks = [(64, 1)[s % 2] for s in range(S)]
+    for Q in (1, 3):
+        lists = ranked_lists(ks, Q, seed=7 * S + Q, full_query=0)
+        for r in lists:
+            r["score"][:, 0] = float("nan")
+            r["video"][:, 0] = 1
+            r["span"].view(torch.int32)[:, 0, 0] = 0x7FC12345
+        for offsets in ([0] * S, [2 * s for s in range(S)]):
+            want = A.merge_search_windows_torch(lists, offsets, k=K)
+            assert int(want["count"][0]) == min(K, sum(ks)) and torch.isnan(want["score"][0, 0]) and int(bits(want["span"])[0, 0, 0]) == 0x7FC12345
+            assert int(want["video"][0, 0]) == 1 and torch.isnan(want["score"][0, :min(K, S)]).all()
+            same_lists(through_ctypes(lists, offsets, K, dev), want, (Q, offsets, "ctypes"))
+            same_lists(A.merge_search_windows([to_dev(r, dev) for r in lists], offsets, k=K), want, (Q, offsets, "merge_search_windows"))
+
+
+@pytest.mark.gpu
 def test_folded_equals_at_once_on_the_device(dev):
     A = V()
     nv, Q, K = 7, 3, 5

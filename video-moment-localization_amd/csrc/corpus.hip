@@ -12,7 +12,9 @@
 //                       found without the rounds -- the lists are sorted, so each candidate's rank is a sum of binary searches;
 //   smin_search_merge_weighted / smin_span_search_merge_weighted  merge shard lists that carry their unweighted scores, under the
 //                       video weights and ranks of the whole corpus: the lists are not sorted in that order, so
-//                       each candidate counts the order words ahead of it -- one templated body over what an entry holds.
+//                       each candidate counts the order words ahead of it.
+// What an entry holds beside video and score (IdxFields: the clips; SpanFields: span, window, cell) is one trait for all six: their
+// tables (ListTables), their output (ListOut), the host's checks (fill_tables) and the two group kernels are written once over it.
 // smin_pair_assemble has an adjoint, which is what lets a model train through shared banks:
 //   smin_pair_assemble_bwd  sums the pairs' gradients of f, f_w, f_s back onto the videos and queries they came from, through the
 //                           pairs grouped by video and by query (two CSR lists from the host): no atomics, a fixed order.
@@ -22,12 +24,14 @@
 //                           reading candidate c, a row of pair scores without the query's own video -- and groups the picked pairs by
 //                           video and by query on the device: the pair plan smin_pair_assemble_bwd reads, with no host in between.
 #include "common.h"
+#include "rank_order.h"
 #include "smin_hip.h"
 
 namespace smin {
 namespace {
 
 constexpr int CT = 256;                  // threads of a smin_corpus_topk workgroup
+static_assert(CT == 256, "rank_order.h's block helpers are written for four waves");
 constexpr int CORPUS_MAX_K = 64;
 
 // One float4 per thread over the P * (T + Nq + 1) * D4 output quads: row r of pair p is frame r of f (r < T), word r - T of f_w
@@ -169,24 +173,14 @@ void pair_bwd_query_kernel(const float* __restrict__ dfs, const float* __restric
 
 // ---- merge across videos: one workgroup per query, K rounds of "the best candidate strictly after the previous pick" (a block
 // argmax of order keys), as the cross-window merge of moments.hip without its suppression: no sort, no atomics, any pair count.
-typedef unsigned long long u64;
-
-__device__ __forceinline__ uint32_t corpus_score_ord(float v)      // score_ord of moments.hip
-{
-    if (v == 0.f) v = 0.f;                                       // -0 -> +0
-    const uint32_t u = __float_as_uint(v);
-    const uint32_t o = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-    return o ? o : 1u;                                           // hi == 0 is "no candidate"
-}
-
 // Order key of a candidate, larger = earlier: (score, lower video, lower slot, lower pair ordinal within the query -- the last
-// only separates two pairs of one query that name the same video).
+// only separates two pairs of one query that name the same video).  hi is rank_order.h's video_word: hi == 0 is "no candidate".
 struct Key { u64 hi, lo; };
 __device__ __forceinline__ bool key_less(const Key& a, const Key& b) { return a.hi < b.hi || (a.hi == b.hi && a.lo < b.lo); }
 __device__ __forceinline__ Key make_key(float score, int video, int slot, long long w)
 {
     Key k;
-    k.hi = ((u64)corpus_score_ord(score) << 32) | (uint32_t)~((uint32_t)video ^ 0x80000000u);      // int32 ascending -> uint32 descending
+    k.hi = video_word(score, video);
     k.lo = ((u64)(uint32_t)(CORPUS_MAX_K - 1 - slot) << 56) | (u64)(0x00ffffffffffffffull - (u64)w);
     return k;
 }
@@ -239,33 +233,85 @@ __device__ __forceinline__ int topk_rounds(const Src& src, long long ncand, int 
     return nk;
 }
 
-// Where the two merges leave query blockIdx.x's ranked list: entry r of K, and the empty slots behind the nk listed ones.
-struct RankedOut {
-    long long* video /* [Q][K] */; long long* idx /* [Q][K][2] */; float* score /* [Q][K] */; int* count /* [Q] */;
+// What an entry of a ranked list holds beside video and score -- F::In the tables of a list, F::Out the output's, with move() and
+// clear() (the empty pattern), and in(), which fills an In from the host's F::N table pointers -- is the parameter of everything below.
+// An output may not be an input, but the compiler cannot know that of pointers inside a struct: whoever moves an entry reads all of
+// it before the first store, so the loads go out together.
+struct IdxFields {                           // SMIN.search: the moment's clips
+    static constexpr int N = 1;
+    struct In {
+        const long long* idx;
+        __device__ __forceinline__ bool present() const { return idx != nullptr; }
+    };
+    struct Out {
+        long long* idx /* [Q][K][2] */;
+        __device__ __forceinline__ void move(size_t o, const In& in, long long i) const
+        {
+            const long long a = in.idx[2 * i], b = in.idx[2 * i + 1];
+            idx[2 * o] = a; idx[2 * o + 1] = b;
+        }
+        __device__ __forceinline__ void clear(size_t o) const { idx[2 * o] = idx[2 * o + 1] = -1; }
+    };
+    static In in(const void* const* p) { return In{(const long long*)p[0]}; }
+};
+struct SpanFields {                          // SMIN.search_windows: smin_merge_window_moments' span in raw rows, window and cell
+    static constexpr int N = 3;
+    struct In {
+        const float* span; const long long* window; const long long* cell;
+        __device__ __forceinline__ bool present() const { return span != nullptr && window != nullptr && cell != nullptr; }
+    };
+    struct Out {
+        float* span /* [Q][K][2] */; long long* window /* [Q][K] */; long long* cell /* [Q][K][2] */;
+        __device__ __forceinline__ void move(size_t o, const In& in, long long i) const
+        {
+            const float s0 = in.span[2 * i], s1 = in.span[2 * i + 1];                            // plain moves: the bits leave as they came
+            const long long w = in.window[i], c0 = in.cell[2 * i], c1 = in.cell[2 * i + 1];
+            span[2 * o] = s0; span[2 * o + 1] = s1;
+            window[o] = w;
+            cell[2 * o] = c0; cell[2 * o + 1] = c1;
+        }
+        __device__ __forceinline__ void clear(size_t o) const
+        {
+            span[2 * o] = span[2 * o + 1] = __uint_as_float(0x7fc00000u);
+            window[o] = -1;
+            cell[2 * o] = cell[2 * o + 1] = -1;
+        }
+    };
+    static In in(const void* const* p) { return In{(const float*)p[0], (const long long*)p[1], (const long long*)p[2]}; }
+};
+
+// Where a kernel leaves query blockIdx.x's ranked list: entry r of K, and the empty slots behind the nk listed ones.
+template <class F>
+struct ListOut {
+    long long* video /* [Q][K] */; float* score /* [Q][K] */; int* count /* [Q] */;
+    typename F::Out f;
     int K;
     __device__ __forceinline__ size_t at(int r) const { return (size_t)blockIdx.x * K + r; }
+    __device__ __forceinline__ void clear(size_t o) const
+    {
+        video[o] = -1;
+        score[o] = 0.f;
+        f.clear(o);
+    }
     __device__ __forceinline__ void finish(int nk) const
     {
-        for (int r = nk + threadIdx.x; r < K; r += CT) {
-            const size_t o = at(r);
-            video[o] = -1;
-            idx[2 * o] = idx[2 * o + 1] = -1;
-            score[o] = 0.f;
-        }
+        for (int r = nk + threadIdx.x; r < K; r += CT) clear(at(r));
         if (threadIdx.x == 0) count[blockIdx.x] = nk;
     }
 };
 
-// smin_corpus_topk's candidates: c = pair ordinal * kv + slot over the query's pairs g0 .. ; key parts (slot, pair ordinal)
-struct PairLists {
-    const float* score; const long long* idx; const int* count; const int* video;
-    long long g0; int kv; RankedOut out;
+// smin_corpus_topk's and smin_corpus_span_topk's candidates: c = group ordinal * kv + slot over the query's pairs (groups) g0 .. ; key
+// parts (slot, group ordinal)
+template <class F>
+struct GroupLists {
+    const float* score; const int* count; const int* video; typename F::In in;
+    long long g0; int kv; ListOut<F> out;
     __device__ __forceinline__ bool read(long long c, int& slot, long long& w, float& sc, int& vid) const
     {
         w = c / kv;
         slot = (int)(c - w * kv);
         const long long g = g0 + w;
-        if (slot >= min(count[g], kv)) return false;             // (a negative count lists nothing)
+        if (slot >= min(count[g], kv)) return false;             // behind the count (a negative one lists nothing): never read
         sc = score[g * kv + slot];
         vid = video[g];
         return true;
@@ -274,35 +320,40 @@ struct PairLists {
     {
         const long long g = g0 + w, c = g * kv + slot;
         const size_t o = out.at(r);
-        out.video[o] = video[g];
-        out.idx[2 * o] = idx[2 * c]; out.idx[2 * o + 1] = idx[2 * c + 1];
-        out.score[o] = score[c];
+        const int v = video[g];
+        const float sc = score[c];
+        out.f.move(o, in, c);
+        out.video[o] = v;
+        out.score[o] = sc;
     }
 };
 
+template <class F>
 __global__ __launch_bounds__(CT)
-void corpus_topk_kernel(const float* __restrict__ pair_score, const long long* __restrict__ pair_idx, const int* __restrict__ pair_count,
-                        const int* __restrict__ pair_video, const int* __restrict__ pair_ptr, int kv, int K,
-                        long long* __restrict__ out_video, long long* __restrict__ out_idx, float* __restrict__ out_score, int* __restrict__ out_count)
+void group_topk_kernel(const float* __restrict__ score, const int* __restrict__ count, const int* __restrict__ group_video,
+                       const int* __restrict__ group_ptr, const typename F::In in, int kv, const ListOut<F> out)
 {
     const int b = blockIdx.x;
-    const long long g0 = max(pair_ptr[b], 0);
-    const long long g1 = max((long long)pair_ptr[b + 1], g0);
-    const bool lists = pair_score && pair_idx && pair_count && pair_video;     // (NULL lists: no query may have a pair, none is read)
-    const PairLists src{pair_score, pair_idx, pair_count, pair_video, g0, kv, {out_video, out_idx, out_score, out_count, K}};
-    src.out.finish(topk_rounds(src, lists ? (g1 - g0) * kv : 0, K));
+    const long long g0 = max(group_ptr[b], 0);
+    const long long g1 = max((long long)group_ptr[b + 1], g0);
+    const bool lists = score && count && group_video && in.present();    // (NULL lists: no query may have a group, none is read)
+    const GroupLists<F> src{score, count, group_video, in, g0, kv, out};
+    out.finish(topk_rounds(src, lists ? (g1 - g0) * kv : 0, out.K));
 }
 
-// smin_search_merge's candidates: S ranked lists of k[s] slots per query, c = base[s] + p (base: the exclusive prefix of k); key
-// parts (list s <= 15, position p).  Passed to the kernel by value: the host tables need no copy of their own.
+// The tables of S <= 16 ranked lists of k[s] slots per query, from disjoint video shards: candidate c = base[s] + p (base: the exclusive
+// prefix of k), its global video = video + offset[s].  Passed to a kernel by value: the host tables need no copy of their own.
 constexpr int MERGE_MAX_S = 16;
-struct RankedTables {
-    const long long* video[MERGE_MAX_S]; const long long* idx[MERGE_MAX_S]; const float* score[MERGE_MAX_S]; const int* count[MERGE_MAX_S];
+template <class F>
+struct ListTables {
+    const long long* video[MERGE_MAX_S]; const float* score[MERGE_MAX_S]; const int* count[MERGE_MAX_S]; typename F::In in[MERGE_MAX_S];
     long long offset[MERGE_MAX_S];
     int k[MERGE_MAX_S], base[MERGE_MAX_S + 1], S;
 };
+
+// smin_search_merge's candidates: key parts (list s <= 15, position p)
 struct RankedLists {
-    const RankedTables& tb; long long q; RankedOut out;
+    const ListTables<IdxFields>& tb; long long q; ListOut<IdxFields> out;
     __device__ __forceinline__ bool read(long long c, int& slot, long long& w, float& sc, int& vid) const
     {
         int s = 0;
@@ -318,93 +369,26 @@ struct RankedLists {
     {
         const long long c = q * tb.k[s] + p;
         const size_t o = out.at(r);
-        out.video[o] = tb.video[s][c] + tb.offset[s];
-        out.idx[2 * o] = tb.idx[s][2 * c]; out.idx[2 * o + 1] = tb.idx[s][2 * c + 1];
-        out.score[o] = tb.score[s][c];
+        const long long v = tb.video[s][c] + tb.offset[s];
+        const float sc = tb.score[s][c];
+        out.f.move(o, tb.in[s], c);
+        out.video[o] = v;
+        out.score[o] = sc;
     }
 };
 
 __global__ __launch_bounds__(CT)
-void search_merge_kernel(const RankedTables tb, int K, long long* __restrict__ out_video, long long* __restrict__ out_idx,
-                         float* __restrict__ out_score, int* __restrict__ out_count)
+void search_merge_kernel(const ListTables<IdxFields> tb, const ListOut<IdxFields> out)
 {
-    const RankedLists src{tb, (long long)blockIdx.x, {out_video, out_idx, out_score, out_count, K}};
-    src.out.finish(topk_rounds(src, tb.base[tb.S], K));
-}
-
-// smin_corpus_span_topk: the lists are smin_merge_window_moments' -- a (query, video) group's moments as spans in
-// raw rows, with the window and the cell each came from -- so an entry is five fields wide and has an output writer of its own.
-struct SpanOut {
-    long long* video /* [Q][K] */; float* span /* [Q][K][2] */; float* score /* [Q][K] */; long long* window /* [Q][K] */;
-    long long* cell /* [Q][K][2] */; int* count /* [Q] */;
-    int K;
-    __device__ __forceinline__ size_t at(int r) const { return (size_t)blockIdx.x * K + r; }
-    __device__ __forceinline__ void finish(int nk) const
-    {
-        for (int r = nk + threadIdx.x; r < K; r += CT) {
-            const size_t o = at(r);
-            video[o] = -1;
-            span[2 * o] = span[2 * o + 1] = __uint_as_float(0x7fc00000u);
-            score[o] = 0.f;
-            window[o] = -1;
-            cell[2 * o] = cell[2 * o + 1] = -1;
-        }
-        if (threadIdx.x == 0) count[blockIdx.x] = nk;
-    }
-};
-
-// Its candidates: c = group ordinal * kv + slot over the query's groups g0 .. ; key parts (slot, group ordinal), as PairLists
-struct SpanLists {
-    const float* span; const float* score; const long long* window; const long long* cell; const int* count; const int* video;
-    long long g0; int kv; SpanOut out;
-    __device__ __forceinline__ bool read(long long c, int& slot, long long& w, float& sc, int& vid) const
-    {
-        w = c / kv;
-        slot = (int)(c - w * kv);
-        const long long g = g0 + w;
-        if (slot >= min(count[g], kv)) return false;             // behind the count (NaN spans, -1): never read
-        sc = score[g * kv + slot];
-        vid = video[g];
-        return true;
-    }
-    __device__ __forceinline__ void emit(int r, int slot, long long w) const
-    {
-        const long long g = g0 + w, c = g * kv + slot;
-        const size_t o = out.at(r);
-        out.video[o] = video[g];
-        out.span[2 * o] = span[2 * c]; out.span[2 * o + 1] = span[2 * c + 1];          // plain moves: the bits leave as they came
-        out.score[o] = score[c];
-        out.window[o] = window[c];
-        out.cell[2 * o] = cell[2 * c]; out.cell[2 * o + 1] = cell[2 * c + 1];
-    }
-};
-
-__global__ __launch_bounds__(CT)
-void corpus_span_topk_kernel(const float* __restrict__ span, const float* __restrict__ score, const long long* __restrict__ window,
-                             const long long* __restrict__ cell, const int* __restrict__ count, const int* __restrict__ group_video,
-                             const int* __restrict__ group_ptr, int kv, int K, long long* __restrict__ out_video, float* __restrict__ out_span,
-                             float* __restrict__ out_score, long long* __restrict__ out_window, long long* __restrict__ out_cell,
-                             int* __restrict__ out_count)
-{
-    const int b = blockIdx.x;
-    const long long g0 = max(group_ptr[b], 0);
-    const long long g1 = max((long long)group_ptr[b + 1], g0);
-    const bool lists = span && score && window && cell && count && group_video;   // (NULL lists: no query may have a group, none is read)
-    const SpanLists src{span, score, window, cell, count, group_video, g0, kv, {out_video, out_span, out_score, out_window, out_cell, out_count, K}};
-    src.out.finish(topk_rounds(src, lists ? (g1 - g0) * kv : 0, K));
+    const RankedLists src{tb, (long long)blockIdx.x, out};
+    out.finish(topk_rounds(src, tb.base[tb.S], out.K));
 }
 
 // smin_span_search_merge: S ranked span lists of disjoint video shards into one, in ONE pass instead of K rounds.
 // Each list is sorted, so a candidate's place in the merge is its own position plus, for every other list, the number of entries
 // that go ahead of it -- a binary search over that list's order words.  Only Key::hi (score order, inverted global video) takes part:
 // the two low fields of smin_search_merge's key are (list, position), which the rank spells out as ">=" for the lists before s, ">"
-// for those after, and p itself.  Passed to the kernel by value, as RankedTables.
-struct SpanTables {
-    const long long* video[MERGE_MAX_S]; const float* span[MERGE_MAX_S]; const float* score[MERGE_MAX_S]; const long long* window[MERGE_MAX_S];
-    const long long* cell[MERGE_MAX_S]; const int* count[MERGE_MAX_S];
-    long long offset[MERGE_MAX_S];
-    int k[MERGE_MAX_S], base[MERGE_MAX_S + 1], S;
-};
+// for those after, and p itself.
 
 // The number of the n words at a (descending) that go ahead of `mine`: those >= mine (or_equal) or > mine.  n <= CORPUS_MAX_K, so
 // seven halvings; every index read is < n whatever the words hold.
@@ -424,7 +408,7 @@ __device__ __forceinline__ int count_ahead(const u64* a, int n, u64 mine, bool o
 // ordered as assumed the ranks are a permutation of 0 .. sum(cnt) - 1: each slot below nk is written once more, by one thread.  For
 // any other input rank <= p + the other lists' counts < sum(cnt), so a write stays inside the query's K slots.
 __global__ __launch_bounds__(CT)
-void span_search_merge_kernel(const SpanTables tb, const SpanOut out)
+void span_search_merge_kernel(const ListTables<SpanFields> tb, const ListOut<SpanFields> out)
 {
     __shared__ u64 hi[MERGE_MAX_S * CORPUS_MAX_K];
     __shared__ int cnt[MERGE_MAX_S];
@@ -439,7 +423,7 @@ void span_search_merge_kernel(const SpanTables tb, const SpanOut out)
         const int p = c - tb.base[s];
         if (p >= cnt[s]) continue;                               // behind the count: never read
         const long long i = q * tb.k[s] + p;
-        hi[c] = make_key(tb.score[s][i], (int)(tb.video[s][i] + tb.offset[s]), 0, 0).hi;
+        hi[c] = video_word(tb.score[s][i], (int)(tb.video[s][i] + tb.offset[s]));
     }
     __syncthreads();
     int total = 0;
@@ -457,11 +441,11 @@ void span_search_merge_kernel(const SpanTables tb, const SpanOut out)
         if (rank >= nk) continue;
         const long long i = q * tb.k[s] + p;
         const size_t r = out.at(rank);
-        out.video[r] = tb.video[s][i] + tb.offset[s];
-        out.span[2 * r] = tb.span[s][2 * i]; out.span[2 * r + 1] = tb.span[s][2 * i + 1];      // plain moves: the bits leave as they came
-        out.score[r] = tb.score[s][i];
-        out.window[r] = tb.window[s][i];
-        out.cell[2 * r] = tb.cell[s][2 * i]; out.cell[2 * r + 1] = tb.cell[s][2 * i + 1];
+        const long long v = tb.video[s][i] + tb.offset[s];
+        const float sc = tb.score[s][i];
+        out.f.move(r, tb.in[s], i);
+        out.video[r] = v;
+        out.score[r] = sc;
     }
     if (t == 0) out.count[q] = nk;
 }
@@ -515,18 +499,6 @@ __device__ __forceinline__ int pair_of(const int* __restrict__ video_index, int 
     return p;
 }
 
-__device__ __forceinline__ int block_sum(int v, int* red /* [CT / 64] */)
-{
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    int s = 0;
-#pragma unroll
-    for (int w = 0; w < CT / 64; ++w) s += red[w];
-    return s;
-}
-
 // One workgroup per video: the number of pairs that name it.
 __global__ __launch_bounds__(CT)
 void mine_count_kernel(const int* __restrict__ video_index, int Q, int S, int* __restrict__ counts /* [V] */)
@@ -575,24 +547,15 @@ void mine_scan_kernel(const int* __restrict__ counts, int V, int* __restrict__ v
 __global__ __launch_bounds__(CT)
 void mine_fill_kernel(const int* __restrict__ video_index, const int* __restrict__ v_ptr, int Q, int S, int* __restrict__ v_pairs /* [P] */)
 {
-    __shared__ int wave_sum[CT / 64];
-    const int v = blockIdx.x, t = threadIdx.x, lane = t & 63, wv = t >> 6;
+    __shared__ int red[CT / 64];
+    const int v = blockIdx.x, t = threadIdx.x;
     const long long P = (long long)Q * S;
     long long base = v_ptr[v];
     for (int q0 = 0; q0 < Q; q0 += CT) {
         const int q = q0 + t;
         const int p = q < Q ? pair_of(video_index, q, S, v) : -1;
-        const u64 hits = __ballot(p >= 0);
-        __syncthreads();
-        if (lane == 0) wave_sum[wv] = __popcll(hits);
-        __syncthreads();
-        int before = 0, total = 0;
-#pragma unroll
-        for (int w = 0; w < CT / 64; ++w) {
-            if (w < wv) before += wave_sum[w];
-            total += wave_sum[w];
-        }
-        const long long o = base + before + __popcll(hits & ((1ull << lane) - 1ull));
+        int total;
+        const long long o = base + block_scan_flag(p >= 0, red, total);
         if (p >= 0 && o >= 0 && o < P) v_pairs[o] = p;
         base += total;
     }
@@ -604,52 +567,14 @@ void mine_fill_kernel(const int* __restrict__ video_index, const int* __restrict
 // binary search.  One workgroup per query stages the order word of every candidate in LDS (0 for one that dropped out; at most
 // 16 * 64 words, 8 KB) and each candidate counts the words ahead of it, as video_rank_kernel does: a larger word, or an equal one
 // earlier in (list, position) order.  That order is strict and total, so the survivors' ranks are a permutation of 0 .. n - 1 and,
-// after the fill with the empty pattern, each slot below nk = min(n, K) has exactly one writer.  What an entry holds beside video, raw
-// and score is the template parameter: F::In the lists' tables, F::Out the output's, with move() and clear().
-struct IdxFields {                           // SMIN.search: the moment's clips
-    struct In { const long long* idx; };
-    struct Out {
-        long long* idx /* [Q][K][2] */;
-        __device__ __forceinline__ void move(size_t o, const In& in, long long i) const { idx[2 * o] = in.idx[2 * i]; idx[2 * o + 1] = in.idx[2 * i + 1]; }
-        __device__ __forceinline__ void clear(size_t o) const { idx[2 * o] = idx[2 * o + 1] = -1; }
-    };
-};
-struct SpanFields {                          // SMIN.search_windows: span, window, cell (SpanOut's fields and empty pattern)
-    struct In { const float* span; const long long* window; const long long* cell; };
-    struct Out {
-        float* span /* [Q][K][2] */; long long* window /* [Q][K] */; long long* cell /* [Q][K][2] */;
-        __device__ __forceinline__ void move(size_t o, const In& in, long long i) const
-        {
-            span[2 * o] = in.span[2 * i]; span[2 * o + 1] = in.span[2 * i + 1];                  // plain moves: the bits leave as they came
-            window[o] = in.window[i];
-            cell[2 * o] = in.cell[2 * i]; cell[2 * o + 1] = in.cell[2 * i + 1];
-        }
-        __device__ __forceinline__ void clear(size_t o) const
-        {
-            span[2 * o] = span[2 * o + 1] = __uint_as_float(0x7fc00000u);
-            window[o] = -1;
-            cell[2 * o] = cell[2 * o + 1] = -1;
-        }
-    };
-};
-template <class F>
-struct WeightedTables {                      // by value, as RankedTables
-    const long long* video[MERGE_MAX_S]; const float* raw[MERGE_MAX_S]; const int* count[MERGE_MAX_S]; typename F::In in[MERGE_MAX_S];
-    long long offset[MERGE_MAX_S];
-    int k[MERGE_MAX_S], base[MERGE_MAX_S + 1], S;
-};
-template <class F>
-struct WeightedOut {
-    long long* video /* [Q][K] */; float* score /* [Q][K] */; float* raw /* [Q][K] */; int* count /* [Q] */;
-    typename F::Out f;
-    int K;
-};
+// after the fill with the empty pattern, each slot below nk = min(n, K) has exactly one writer.  The tables' score column holds the
+// lists' raw scores; the output has a raw column beside the weighted score.
 constexpr int WM_OWN = MERGE_MAX_S * CORPUS_MAX_K / CT;          // candidates a thread owns at most: c = t, t + CT, ...
 
 template <class F>
 __global__ __launch_bounds__(CT)
-void merge_weighted_kernel(const WeightedTables<F> tb, const int* __restrict__ video_rank, const float* __restrict__ video_weight, int V,
-                           int max_videos, const WeightedOut<F> out)
+void merge_weighted_kernel(const ListTables<F> tb, const int* __restrict__ video_rank, const float* __restrict__ video_weight, int V,
+                           int max_videos, const ListOut<F> out, float* __restrict__ out_raw /* [Q][K] */)
 {
     __shared__ u64 word[MERGE_MAX_S * CORPUS_MAX_K];
     __shared__ int cnt[MERGE_MAX_S];
@@ -658,11 +583,9 @@ void merge_weighted_kernel(const WeightedTables<F> tb, const int* __restrict__ v
     const long long q = blockIdx.x;
     if (t < S) cnt[t] = min(max(tb.count[t][q], 0), tb.k[t]);
     for (int r = t; r < out.K; r += CT) {                         // all K slots empty
-        const size_t o = (size_t)q * out.K + r;
-        out.video[o] = -1;
-        out.score[o] = 0.f;
-        out.raw[o] = 0.f;
-        out.f.clear(o);
+        const size_t o = out.at(r);
+        out.clear(o);
+        out_raw[o] = 0.f;
     }
     __syncthreads();
     const int nown = (ncand + CT - 1) / CT;                       // (uniform)
@@ -685,8 +608,8 @@ void merge_weighted_kernel(const WeightedTables<F> tb, const int* __restrict__ v
                 const size_t e = (size_t)q * V + (size_t)g;
                 const int vr = video_rank[e];
                 if (vr >= 0 && (max_videos <= 0 || vr < max_videos)) {
-                    val[r] = tb.raw[s][i] * video_weight[e];     // smin_moment_reweight's product
-                    mine[r] = make_key(val[r], (int)g, 0, 0).hi; // >= 2^32: never the 0 of a dropped candidate
+                    val[r] = tb.score[s][i] * video_weight[e];   // smin_moment_reweight's product
+                    mine[r] = video_word(val[r], (int)g);        // >= 2^32: never the 0 of a dropped candidate
                     src[r] = i; lst[r] = s; gvid[r] = (int)g;
                     ++alive;
                 }
@@ -707,22 +630,33 @@ void merge_weighted_kernel(const WeightedTables<F> tb, const int* __restrict__ v
 #pragma unroll
     for (int r = 0; r < WM_OWN; ++r) {
         if (mine[r] == 0ull || rank[r] >= nk) continue;
-        const size_t o = (size_t)q * out.K + rank[r];
+        const size_t o = out.at(rank[r]);
         const int s = lst[r];
+        const float raw = tb.score[s][src[r]];
+        out.f.move(o, tb.in[s], src[r]);
         out.video[o] = gvid[r];
         out.score[o] = val[r];
-        out.raw[o] = tb.raw[s][src[r]];
-        out.f.move(o, tb.in[s], src[r]);
+        out_raw[o] = raw;
     }
     if (t == 0) out.count[q] = nk;
 }
 
-// What the two weighted merges check and fill alike, in front of their own fields.
-template <class F>
-int weighted_tables(WeightedTables<F>& tb, int S, const int64_t* const* video, const float* const* raw, const int32_t* const* count,
-                    const int32_t* k_list, const int64_t* video_offset, const int32_t* video_rank, const float* video_weight, int V, int Q, int K)
+// An output that is the input p (NULL is none): a kernel would read it while other threads write the result.
+bool aliased(const void* p, const void* const* outs, int n_out)
 {
-    SMIN_REQUIRE(S >= 1 && S <= MERGE_MAX_S && K >= 1 && K <= CORPUS_MAX_K && Q >= 0 && V >= 0);
+    for (int o = 0; o < n_out; ++o)
+        if (p != nullptr && p == outs[o]) return true;
+    return false;
+}
+
+// What the four merges check and fill alike.  fields: F::N arrays of S tables, in the order F::in() reads them; outs: every output.
+// With Q == 0 it returns 0 after the checks of S, K, Q and a given k_list, and the caller has nothing to launch.
+template <class F>
+int fill_tables(ListTables<F>& tb, int S, const int64_t* const* video, const float* const* score, const int32_t* const* count,
+                const void* const* const* fields, const int32_t* k_list, const int64_t* video_offset, int Q, int K,
+                const void* const* outs, int n_out)
+{
+    SMIN_REQUIRE(S >= 1 && S <= MERGE_MAX_S && K >= 1 && K <= CORPUS_MAX_K && Q >= 0);
     tb.S = S;
     if (k_list) {
         for (int s = 0; s < S; ++s) {
@@ -732,14 +666,32 @@ int weighted_tables(WeightedTables<F>& tb, int S, const int64_t* const* video, c
         }
     }
     if (Q == 0) return 0;
-    SMIN_REQUIRE(video != nullptr && raw != nullptr && count != nullptr && k_list != nullptr && video_offset != nullptr);
-    SMIN_REQUIRE(V == 0 || (video_rank != nullptr && video_weight != nullptr));      // (V == 0: every candidate drops out, neither is read)
+    SMIN_REQUIRE(video != nullptr && score != nullptr && count != nullptr && k_list != nullptr && video_offset != nullptr);
+    for (int c = 0; c < F::N; ++c) SMIN_REQUIRE(fields[c] != nullptr);
+    for (int o = 0; o < n_out; ++o) SMIN_REQUIRE(outs[o] != nullptr);
     for (int s = 0; s < S; ++s) {
-        SMIN_REQUIRE(video[s] != nullptr && raw[s] != nullptr && count[s] != nullptr);
         SMIN_REQUIRE(video_offset[s] >= 0 && video_offset[s] <= 0x7fffffffll);
-        tb.video[s] = (const long long*)video[s]; tb.raw[s] = raw[s]; tb.count[s] = count[s];
+        const void* in[3 + F::N] = {video[s], score[s], count[s]};
+        for (int c = 0; c < F::N; ++c) in[3 + c] = fields[c][s];
+        for (const void* p : in) SMIN_REQUIRE(p != nullptr && !aliased(p, outs, n_out));
+        tb.video[s] = (const long long*)video[s]; tb.score[s] = score[s]; tb.count[s] = count[s];
+        tb.in[s] = F::in(in + 3);
         tb.offset[s] = video_offset[s];
     }
+    return 0;
+}
+
+// The weighted merges': the video tables of the whole corpus beside the lists.
+template <class F>
+int fill_weighted_tables(ListTables<F>& tb, int S, const int64_t* const* video, const float* const* raw, const int32_t* const* count,
+                         const void* const* const* fields, const int32_t* k_list, const int64_t* video_offset, const int32_t* video_rank,
+                         const float* video_weight, int V, int Q, int K, const void* const* outs, int n_out)
+{
+    SMIN_REQUIRE(V >= 0);
+    const int rc = fill_tables(tb, S, video, raw, count, fields, k_list, video_offset, Q, K, outs, n_out);
+    if (rc != 0 || Q == 0) return rc;
+    SMIN_REQUIRE(V == 0 || (video_rank != nullptr && video_weight != nullptr));      // (V == 0: every candidate drops out, neither is read)
+    SMIN_REQUIRE(!aliased(video_rank, outs, n_out) && !aliased(video_weight, outs, n_out));
     return 0;
 }
 
@@ -799,8 +751,9 @@ extern "C" int smin_corpus_topk(void* stream, const float* pair_score, const int
     if (Q == 0) return 0;
     SMIN_REQUIRE(pair_ptr != nullptr && out_video != nullptr && out_idx != nullptr && out_score != nullptr && out_count != nullptr);
     // (whether a query has pairs is known on the device only: with a NULL pair list the kernel reads none of the four and every query comes out empty)
-    hipLaunchKernelGGL(corpus_topk_kernel, dim3(Q), dim3(CT), 0, (hipStream_t)stream, pair_score, (const long long*)pair_idx, pair_count, pair_video,
-                       pair_ptr, k_video, K, (long long*)out_video, (long long*)out_idx, out_score, out_count);
+    const ListOut<IdxFields> out{(long long*)out_video, out_score, out_count, {(long long*)out_idx}, K};
+    hipLaunchKernelGGL(group_topk_kernel<IdxFields>, dim3(Q), dim3(CT), 0, (hipStream_t)stream, pair_score, pair_count, pair_video, pair_ptr,
+                       IdxFields::In{(const long long*)pair_idx}, k_video, out);
     SMIN_LAUNCH_CHECK();
     return 0;
 }
@@ -809,30 +762,13 @@ extern "C" int smin_search_merge(void* stream, int S, const int64_t* const* vide
                                  const int32_t* const* count, const int32_t* k_list, const int64_t* video_offset, int Q, int K,
                                  int64_t* out_video, int64_t* out_idx, float* out_score, int32_t* out_count)
 {
-    SMIN_REQUIRE(S >= 1 && S <= MERGE_MAX_S && K >= 1 && K <= CORPUS_MAX_K && Q >= 0);
-    RankedTables tb{};
-    tb.S = S;
-    if (k_list) {
-        for (int s = 0; s < S; ++s) {
-            SMIN_REQUIRE(k_list[s] >= 1 && k_list[s] <= CORPUS_MAX_K);
-            tb.k[s] = k_list[s];
-            tb.base[s + 1] = tb.base[s] + k_list[s];
-        }
-    }
-    if (Q == 0) return 0;
-    SMIN_REQUIRE(video != nullptr && idx != nullptr && score != nullptr && count != nullptr && k_list != nullptr && video_offset != nullptr);
-    SMIN_REQUIRE(out_video != nullptr && out_idx != nullptr && out_score != nullptr && out_count != nullptr);
-    for (int s = 0; s < S; ++s) {
-        SMIN_REQUIRE(video[s] != nullptr && idx[s] != nullptr && score[s] != nullptr && count[s] != nullptr);
-        SMIN_REQUIRE(video_offset[s] >= 0 && video_offset[s] <= 0x7fffffffll);
-        const void* in[4] = {video[s], idx[s], score[s], count[s]};
-        for (const void* p : in)                                 // the rounds read the lists while thread 0 writes the result
-            SMIN_REQUIRE(p != (const void*)out_video && p != (const void*)out_idx && p != (const void*)out_score && p != (const void*)out_count);
-        tb.video[s] = (const long long*)video[s]; tb.idx[s] = (const long long*)idx[s]; tb.score[s] = score[s]; tb.count[s] = count[s];
-        tb.offset[s] = video_offset[s];
-    }
-    hipLaunchKernelGGL(search_merge_kernel, dim3(Q), dim3(CT), 0, (hipStream_t)stream, tb, K, (long long*)out_video, (long long*)out_idx, out_score,
-                       out_count);
+    ListTables<IdxFields> tb{};
+    const void* const* fields[1] = {(const void* const*)idx};
+    const void* outs[4] = {out_video, out_idx, out_score, out_count};
+    const int rc = fill_tables(tb, S, video, score, count, fields, k_list, video_offset, Q, K, outs, 4);
+    if (rc != 0 || Q == 0) return rc;
+    const ListOut<IdxFields> out{(long long*)out_video, out_score, out_count, {(long long*)out_idx}, K};
+    hipLaunchKernelGGL(search_merge_kernel, dim3(Q), dim3(CT), 0, (hipStream_t)stream, tb, out);
     SMIN_LAUNCH_CHECK();
     return 0;
 }
@@ -847,9 +783,9 @@ extern "C" int smin_corpus_span_topk(void* stream, const float* span, const floa
     SMIN_REQUIRE(group_ptr != nullptr && out_video != nullptr && out_span != nullptr && out_score != nullptr && out_window != nullptr);
     SMIN_REQUIRE(out_cell != nullptr && out_count != nullptr);
     // (as smin_corpus_topk: with a NULL list the kernel reads none of the six and every query comes out empty)
-    hipLaunchKernelGGL(corpus_span_topk_kernel, dim3(Q), dim3(CT), 0, (hipStream_t)stream, span, score, (const long long*)window, (const long long*)cell,
-                       count, group_video, group_ptr, k_video, K, (long long*)out_video, out_span, out_score, (long long*)out_window,
-                       (long long*)out_cell, out_count);
+    const ListOut<SpanFields> out{(long long*)out_video, out_score, out_count, {out_span, (long long*)out_window, (long long*)out_cell}, K};
+    hipLaunchKernelGGL(group_topk_kernel<SpanFields>, dim3(Q), dim3(CT), 0, (hipStream_t)stream, score, count, group_video, group_ptr,
+                       SpanFields::In{span, (const long long*)window, (const long long*)cell}, k_video, out);
     SMIN_LAUNCH_CHECK();
     return 0;
 }
@@ -859,45 +795,15 @@ extern "C" int smin_span_search_merge(void* stream, int S, const int64_t* const*
                                       const int32_t* k_list, const int64_t* video_offset, int Q, int K, int64_t* out_video, float* out_span,
                                       float* out_score, int64_t* out_window, int64_t* out_cell, int32_t* out_count)
 {
-    SMIN_REQUIRE(S >= 1 && S <= MERGE_MAX_S && K >= 1 && K <= CORPUS_MAX_K && Q >= 0);
-    SpanTables tb{};
-    tb.S = S;
-    if (k_list) {
-        for (int s = 0; s < S; ++s) {
-            SMIN_REQUIRE(k_list[s] >= 1 && k_list[s] <= CORPUS_MAX_K);
-            tb.k[s] = k_list[s];
-            tb.base[s + 1] = tb.base[s] + k_list[s];
-        }
-    }
-    if (Q == 0) return 0;
-    SMIN_REQUIRE(video != nullptr && span != nullptr && score != nullptr && window != nullptr && cell != nullptr && count != nullptr);
-    SMIN_REQUIRE(k_list != nullptr && video_offset != nullptr);
+    ListTables<SpanFields> tb{};
+    const void* const* fields[3] = {(const void* const*)span, (const void* const*)window, (const void* const*)cell};
     const void* outs[6] = {out_video, out_span, out_score, out_window, out_cell, out_count};
-    for (const void* o : outs) SMIN_REQUIRE(o != nullptr);
-    for (int s = 0; s < S; ++s) {
-        SMIN_REQUIRE(video_offset[s] >= 0 && video_offset[s] <= 0x7fffffffll);
-        const void* in[6] = {video[s], span[s], score[s], window[s], cell[s], count[s]};
-        for (const void* p : in) {
-            SMIN_REQUIRE(p != nullptr);
-            for (const void* o : outs) SMIN_REQUIRE(p != o);     // the candidates read the lists while others write the result
-        }
-        tb.video[s] = (const long long*)video[s]; tb.span[s] = span[s]; tb.score[s] = score[s]; tb.window[s] = (const long long*)window[s];
-        tb.cell[s] = (const long long*)cell[s]; tb.count[s] = count[s];
-        tb.offset[s] = video_offset[s];
-    }
-    const SpanOut out{(long long*)out_video, out_span, out_score, (long long*)out_window, (long long*)out_cell, out_count, K};
+    const int rc = fill_tables(tb, S, video, score, count, fields, k_list, video_offset, Q, K, outs, 6);
+    if (rc != 0 || Q == 0) return rc;
+    const ListOut<SpanFields> out{(long long*)out_video, out_score, out_count, {out_span, (long long*)out_window, (long long*)out_cell}, K};
     hipLaunchKernelGGL(span_search_merge_kernel, dim3(Q), dim3(CT), 0, (hipStream_t)stream, tb, out);
     SMIN_LAUNCH_CHECK();
     return 0;
-}
-
-// An output that is one of the inputs (a list's tables or the two video tables): the candidates read while others write.
-static bool weighted_alias(const void* const* ins, int n_in, const void* const* outs, int n_out)
-{
-    for (int i = 0; i < n_in; ++i)
-        for (int o = 0; o < n_out; ++o)
-            if (ins[i] != nullptr && ins[i] == outs[o]) return true;
-    return false;
 }
 
 extern "C" int smin_search_merge_weighted(void* stream, int S, const int64_t* const* video, const int64_t* const* idx, const float* const* raw,
@@ -905,20 +811,14 @@ extern "C" int smin_search_merge_weighted(void* stream, int S, const int64_t* co
                                           const int32_t* video_rank, const float* video_weight, int V, int max_videos, int Q, int K,
                                           int64_t* out_video, int64_t* out_idx, float* out_score, float* out_raw, int32_t* out_count)
 {
-    WeightedTables<IdxFields> tb{};
-    const int rc = weighted_tables(tb, S, video, raw, count, k_list, video_offset, video_rank, video_weight, V, Q, K);
-    if (rc != 0 || Q == 0) return rc;
-    SMIN_REQUIRE(idx != nullptr);
+    ListTables<IdxFields> tb{};
+    const void* const* fields[1] = {(const void* const*)idx};
     const void* outs[5] = {out_video, out_idx, out_score, out_raw, out_count};
-    for (const void* o : outs) SMIN_REQUIRE(o != nullptr);
-    for (int s = 0; s < S; ++s) {
-        SMIN_REQUIRE(idx[s] != nullptr);
-        const void* ins[6] = {video[s], idx[s], raw[s], count[s], video_rank, video_weight};
-        SMIN_REQUIRE(!weighted_alias(ins, 6, outs, 5));
-        tb.in[s].idx = (const long long*)idx[s];
-    }
-    const WeightedOut<IdxFields> out{(long long*)out_video, out_score, out_raw, out_count, {(long long*)out_idx}, K};
-    hipLaunchKernelGGL(merge_weighted_kernel<IdxFields>, dim3(Q), dim3(CT), 0, (hipStream_t)stream, tb, video_rank, video_weight, V, max_videos, out);
+    const int rc = fill_weighted_tables(tb, S, video, raw, count, fields, k_list, video_offset, video_rank, video_weight, V, Q, K, outs, 5);
+    if (rc != 0 || Q == 0) return rc;
+    const ListOut<IdxFields> out{(long long*)out_video, out_score, out_count, {(long long*)out_idx}, K};
+    hipLaunchKernelGGL(merge_weighted_kernel<IdxFields>, dim3(Q), dim3(CT), 0, (hipStream_t)stream, tb, video_rank, video_weight, V, max_videos, out,
+                       out_raw);
     SMIN_LAUNCH_CHECK();
     return 0;
 }
@@ -929,20 +829,14 @@ extern "C" int smin_span_search_merge_weighted(void* stream, int S, const int64_
                                                const float* video_weight, int V, int max_videos, int Q, int K, int64_t* out_video, float* out_span,
                                                float* out_score, float* out_raw, int64_t* out_window, int64_t* out_cell, int32_t* out_count)
 {
-    WeightedTables<SpanFields> tb{};
-    const int rc = weighted_tables(tb, S, video, raw, count, k_list, video_offset, video_rank, video_weight, V, Q, K);
-    if (rc != 0 || Q == 0) return rc;
-    SMIN_REQUIRE(span != nullptr && window != nullptr && cell != nullptr);
+    ListTables<SpanFields> tb{};
+    const void* const* fields[3] = {(const void* const*)span, (const void* const*)window, (const void* const*)cell};
     const void* outs[7] = {out_video, out_span, out_score, out_raw, out_window, out_cell, out_count};
-    for (const void* o : outs) SMIN_REQUIRE(o != nullptr);
-    for (int s = 0; s < S; ++s) {
-        SMIN_REQUIRE(span[s] != nullptr && window[s] != nullptr && cell[s] != nullptr);
-        const void* ins[8] = {video[s], span[s], raw[s], window[s], cell[s], count[s], video_rank, video_weight};
-        SMIN_REQUIRE(!weighted_alias(ins, 8, outs, 7));
-        tb.in[s].span = span[s]; tb.in[s].window = (const long long*)window[s]; tb.in[s].cell = (const long long*)cell[s];
-    }
-    const WeightedOut<SpanFields> out{(long long*)out_video, out_score, out_raw, out_count, {out_span, (long long*)out_window, (long long*)out_cell}, K};
-    hipLaunchKernelGGL(merge_weighted_kernel<SpanFields>, dim3(Q), dim3(CT), 0, (hipStream_t)stream, tb, video_rank, video_weight, V, max_videos, out);
+    const int rc = fill_weighted_tables(tb, S, video, raw, count, fields, k_list, video_offset, video_rank, video_weight, V, Q, K, outs, 7);
+    if (rc != 0 || Q == 0) return rc;
+    const ListOut<SpanFields> out{(long long*)out_video, out_score, out_count, {out_span, (long long*)out_window, (long long*)out_cell}, K};
+    hipLaunchKernelGGL(merge_weighted_kernel<SpanFields>, dim3(Q), dim3(CT), 0, (hipStream_t)stream, tb, video_rank, video_weight, V, max_videos, out,
+                       out_raw);
     SMIN_LAUNCH_CHECK();
     return 0;
 }

@@ -5,6 +5,7 @@
 // One workgroup per sample reduces its map and boundary rows in a fixed order; a second tiny pass sums the samples,
 // so the scalar is bitwise reproducible.  Backward uses torch's BCELoss gradient w*(p-y)/max(p(1-p), 1e-12).
 #include "common.h"
+#include "rank_order.h"
 #include "smin_hip.h"
 
 namespace smin {
@@ -15,13 +16,6 @@ __device__ __forceinline__ float bce_elem(float p, float y) {
 }
 __device__ __forceinline__ float scaled_elem(float p, float y, float s) {
     return (s * y) * bce_elem(p, y) + ((1.f - s) * (1.f - y)) * bce_elem(1.f - p, 1.f - y);
-}
-__device__ __forceinline__ float block_sum(float v, float* red) {
-    v = wave_sum(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return (red[0] + red[1]) + (red[2] + red[3]);
 }
 
 // part[b] = { sum_m, cnt_m, sum_s, sum_e, sum_a, cnt_l }

@@ -29,6 +29,7 @@
 //   3. (metric) per-sample hit flags for every (n, m) pair from sm at the kept cells (empty slot = IoU 0), then one thread per pair
 //      sums the samples in order (no float atomics).
 #include "common.h"
+#include "rank_order.h"
 #include "smin_hip.h"
 
 #include <algorithm>
@@ -37,6 +38,7 @@ namespace smin {
 namespace {
 
 constexpr int MT = 256;                 // threads per workgroup (4 waves)
+static_assert(MT == 256, "rank_order.h's block helpers are written for four waves");
 constexpr int CAND = 4096;              // candidate keys held in LDS by the NMS workgroup
 constexpr int MAX_BANDS = 32;
 constexpr int MIN_BAND = 1024;          // cells per band at least
@@ -44,25 +46,11 @@ constexpr int MAX_K = 64;
 constexpr int MAX_N = 64;               // metric: up to 64 values of n ...
 constexpr int MAX_M = 16;               // ... and 16 thresholds m
 
-typedef unsigned long long u64;
-
 struct Map {                            // one sample's inputs
     const float* pm; const float* ps; const float* pe; const uint8_t* mm; int L; int n;
 };
 
-__device__ __forceinline__ uint32_t score_ord(float v)
-{
-    if (v == 0.f) v = 0.f;                                       // -0 -> +0
-    const uint32_t u = __float_as_uint(v);
-    const uint32_t o = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-    return o ? o : 1u;                                           // 0 is reserved for "no cell" (only -NaN 0xffffffff maps there)
-}
-
-__device__ __forceinline__ float ord_score(uint32_t o)
-{
-    return __uint_as_float((o & 0x80000000u) ? (o & 0x7fffffffu) : ~o);
-}
-
+// (the high word is rank_order.h's score_ord: 0 is "no cell")
 __device__ __forceinline__ u64 make_key(uint32_t o, int c) { return ((u64)o << 32) | (uint32_t)(0x7fffffff - c); }
 __device__ __forceinline__ int key_cell(u64 k) { return 0x7fffffff - (int)(uint32_t)k; }
 
@@ -86,19 +74,6 @@ __device__ __forceinline__ void for_cells(const Map& m, int lo, int hi, F&& f)
         i += dq; j += dr;
         if (j >= m.L) { j -= m.L; ++i; }
     }
-}
-
-// sum over the workgroup (every thread gets it); `red` is MT/64 ints of LDS
-__device__ __forceinline__ int block_sum(int v, int* red)
-{
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    int s = 0;
-#pragma unroll
-    for (int w = 0; w < MT / 64; ++w) s += red[w];
-    return s;
 }
 
 // The bin of hist[0..nb) (nb a multiple of MT, larger bin = earlier in the order) holding the need-th element counted from the top
@@ -446,21 +421,6 @@ __device__ __forceinline__ bool span_suppressed(float st, float en, const float*
         if (inter / uni > thr) return true;
     }
     return false;
-}
-
-__device__ __forceinline__ u64 block_max(u64 v, u64* red)
-{
-    for (int o = 32; o >= 1; o >>= 1) {
-        const u64 x = __shfl_xor(v, o);
-        v = x > v ? x : v;
-    }
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    u64 m = red[0];
-#pragma unroll
-    for (int w = 1; w < MT / 64; ++w) m = red[w] > m ? red[w] : m;
-    return m;
 }
 
 __global__ __launch_bounds__(MT)

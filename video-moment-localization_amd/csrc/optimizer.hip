@@ -11,6 +11,7 @@
 //            whichever of the two load paths a tensor's alignment selects.
 // Every fp32 operation of the update is rounded on its own (contract off); sqrtf and / are hipcc's correctly rounded defaults.
 #include "common.h"
+#include "rank_order.h"
 #include "smin_hip.h"
 
 namespace smin {
@@ -18,6 +19,7 @@ namespace smin {
 constexpr int ADAM_CAP = 96;            // tensors per launch (the 87 of the reference configurations: one launch)
 constexpr int ADAM_CHUNK = 4096;        // elements per workgroup: 16 KB, so a chunk keeps its tensor's 16-byte alignment
 constexpr int ADAM_THREADS = 256;
+static_assert(ADAM_THREADS == 256, "rank_order.h's block helpers are written for four waves");
 
 struct AdamTable {
     float* p[ADAM_CAP];
@@ -120,16 +122,6 @@ void adam_close_kernel(double* __restrict__ state, double beta1, double beta2, i
     if (!use_norm) { state[4] = __builtin_nan(""); state[5] = 1.0; state[7] = 0.0; }
 }
 
-// sum over the workgroup in a fixed order (butterfly inside each wave, then the four waves left to right); valid in thread 0
-__device__ __forceinline__ double block_sum_fixed(double acc, double* red /* [4] LDS */)
-{
-#pragma clang fp contract(off)
-    for (int o = 32; o >= 1; o >>= 1) acc += __shfl_xor(acc, o);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    return (red[0] + red[1]) + (red[2] + red[3]);
-}
-
 // partial[workgroup] = sum of g*g over the workgroup's chunk.  Thread t owns the quads t, t + 256, ... of the chunk and adds their
 // elements one by one in index order; the 16-byte and the scalar load path feed the same additions.
 __global__ __launch_bounds__(ADAM_THREADS)
@@ -156,7 +148,7 @@ void grad_sq_kernel(const AdamTable tb, double* __restrict__ partial)
             for (int i = e; i < end; ++i) { const double x = (double)g[i]; acc += x * x; }
         }
     }
-    const double s = block_sum_fixed(acc, red);
+    const double s = block_sum_f64_fixed(acc, red);
     if (threadIdx.x == 0) partial[bid] = s;
 }
 
@@ -170,7 +162,7 @@ void grad_norm_finalize_kernel(const double* __restrict__ partial, int np, doubl
     __shared__ double red[4];
     double acc = 0.0;
     for (int i = threadIdx.x; i < np; i += ADAM_THREADS) acc += partial[i];
-    const double sum = block_sum_fixed(acc, red);
+    const double sum = block_sum_f64_fixed(acc, red);
     if (threadIdx.x != 0) return;
     const double norm = sqrt(sum);
     float c = 1.0f;

@@ -6,6 +6,7 @@
 #include <cmath>
 
 #include "common.h"
+#include "rank_order.h"
 
 namespace smin {
 
@@ -26,14 +27,6 @@ __device__ __forceinline__ float wave_max(float v) {
     v = fmaxf(v, __shfl_xor(v, 16));
     v = fmaxf(v, __shfl_xor(v, 32));
     return v;
-}
-// the four waves' totals, ((w0 + w1) + (w2 + w3)): loss.hip's block_sum
-__device__ __forceinline__ float rank_block_sum(float v, float* red) {
-    v = wave_sum(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return (red[0] + red[1]) + (red[2] + red[3]);
 }
 __device__ __forceinline__ float rank_block_max(float v, float* red) {
     v = wave_max(v);
@@ -66,7 +59,7 @@ __device__ __forceinline__ PairPool pair_pool_cells(const float* __restrict__ pm
         if (j >= L) { j -= L; ++i; }
     }
     mx = rank_block_max(mx, red);
-    cnt = rank_block_sum(cnt, red);
+    cnt = block_sum(cnt, red);
     const float m = cnt > 0.f ? mx : 0.f;
     float sum = 0.f;
     for (int k = t, i = t / L, j = t % L; k < cells; k += 256) {
@@ -74,7 +67,7 @@ __device__ __forceinline__ PairPool pair_pool_cells(const float* __restrict__ pm
         i += di; j += dj;
         if (j >= L) { j -= L; ++i; }
     }
-    sum = rank_block_sum(sum, red);
+    sum = block_sum(sum, red);
     PairPool r;
     r.m = m;
     r.sum = cnt > 0.f ? sum : 0.f;

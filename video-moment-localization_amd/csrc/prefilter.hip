@@ -14,12 +14,14 @@
 #include "common.h"
 #include "gemm.h"
 #include "pair_pool.h"
+#include "rank_order.h"
 #include "smin_hip.h"
 
 namespace smin {
 namespace {
 
 constexpr int PT = 256;                      // threads of a workgroup (pair_pool.h's reductions are written for four waves)
+static_assert(PT == 256, "rank_order.h's block helpers are written for four waves");
 constexpr int PF_MAX_L = 64;                 // a wave owns the rows of a map: one lane per row
 constexpr int PF_MAX_T = 2048;               // 3 T projections + the L x L map + 4 L words in LDS: <= 41 KB per workgroup
 constexpr int PF_MAX_Q = 65535;              // blockIdx.y
@@ -142,21 +144,6 @@ void prefilter_cell_kernel(const float* __restrict__ proj, size_t ld, const floa
         pool[2 * p + 1] = res.sum;
         cells[p] = res.cnt;
     }
-}
-
-// exclusive prefix of a 0/1 flag over the workgroup's 256 threads and its total; red: 4 ints of LDS
-__device__ __forceinline__ int block_scan_flag(bool flag, int* red, int& total)
-{
-    const unsigned long long b = __ballot(flag);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int before = __popcll(b & ((1ull << lane) - 1ull));
-    __syncthreads();                                             // (the previous scan's reads of red are done)
-    if (lane == 0) red[wave] = __popcll(b);
-    __syncthreads();
-    int base = 0;
-    for (int k = 0; k < 4; ++k) base += k < wave ? red[k] : 0;
-    total = (red[0] + red[1]) + (red[2] + red[3]);
-    return base + before;
 }
 
 // One workgroup per query.  Pass 1 counts the kept candidates (0 <= rank < Ms); pass 2 walks the videos in tiles of 256, ascending,

@@ -16,46 +16,24 @@
 #include <cstdint>
 
 #include "common.h"
+#include "rank_order.h"
 #include "smin_hip.h"
 
 namespace smin {
 namespace {
 
 constexpr int FT = 256;                      // threads of a workgroup
+static_assert(FT == 256, "rank_order.h's block helpers are written for four waves");
 constexpr int FOLD_MAX_M = 2048;             // slots per query: their order words (16 KB) and the free-slot list (8 KB) stay in LDS
 constexpr int FOLD_TILE = 2048;              // order words of the shard staged in LDS at a time (16 KB)
 constexpr int FOLD_OWN = 4;                  // elements a thread places per pass over the words: one LDS read serves them all
 constexpr int ADMIT_CHUNK = 2048;            // float4 of an fv row copied per workgroup (32 KB)
-typedef unsigned long long u64;
 
-__device__ __forceinline__ uint32_t fold_score_ord(float v)      // rank_score_ord of video_rank.hip: smin_video_rank's comparison
-{
-    if (v == 0.f) v = 0.f;                                       // -0 -> +0
-    const uint32_t u = __float_as_uint(v);
-    const uint32_t o = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-    return o ? o : 1u;
-}
 // The order word of a video, larger = earlier: a candidate's is smin_video_rank's (score, then the lower video); a non-candidate's
 // high half is 0, below every candidate's, so the non-candidates come last in ascending video.  Distinct videos, distinct words.
 __device__ __forceinline__ u64 fold_word(float score, bool cand, int video)
 {
-    const uint32_t lo = ~((uint32_t)video ^ 0x80000000u);        // int32 ascending -> uint32 descending
-    return cand ? ((u64)fold_score_ord(score) << 32) | lo : (u64)lo;
-}
-
-// exclusive prefix of a 0/1 flag over the workgroup's 256 threads and its total; red: 4 ints of LDS (prefilter.hip's scan)
-__device__ __forceinline__ int fold_scan_flag(bool flag, int* red, int& total)
-{
-    const u64 b = __ballot(flag);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int before = __popcll(b & ((1ull << lane) - 1ull));
-    __syncthreads();                                             // (the previous scan's reads of red are done)
-    if (lane == 0) red[wave] = __popcll(b);
-    __syncthreads();
-    int base = 0;
-    for (int k = 0; k < 4; ++k) base += k < wave ? red[k] : 0;
-    total = (red[0] + red[1]) + (red[2] + red[3]);
-    return base + before;
+    return cand ? video_word(score, video) : (u64)video_ord(video);
 }
 
 // place[r] = the number of words of the union larger than mine[r]: the n_old old words (LDS), then the shard's, staged FOLD_TILE at a
@@ -133,7 +111,7 @@ void prefilter_fold_kernel(const float* __restrict__ score, const float* __restr
     for (int s0 = 0; s0 < M; s0 += FT) {
         const int s = s0 + t;
         const bool fr = s < n_new && (s >= n_old || evicted[s]);
-        const int pos = nfree + fold_scan_flag(fr, red, total);
+        const int pos = nfree + block_scan_flag(fr, red, total);
         nfree += total;
         if (fr) freeslot[pos] = s;
         else if (s < M) {
@@ -159,7 +137,7 @@ void prefilter_fold_kernel(const float* __restrict__ score, const float* __restr
         for (int r = 0; r < FOLD_OWN; ++r) {
             const int v = own0 + r * FT + t;
             const bool adm = v < Vs && place[r] < n_new;
-            const int pos = nadm + fold_scan_flag(adm, red, total);
+            const int pos = nadm + block_scan_flag(adm, red, total);
             nadm += total;
             if (adm && pos < nfree) {
                 const int s = freeslot[pos];
@@ -198,7 +176,7 @@ void survivors_admit_kernel(const int* __restrict__ copy_src, const float* __res
 }
 
 // One workgroup per query: the candidates whose word is larger than the own video's, counted by thread (v = t, t + 256, ...), then
-// over the wave and the four waves in a fixed order.
+// over the workgroup.
 __global__ __launch_bounds__(FT)
 void prefilter_gt_rank_kernel(const float* __restrict__ score, const uint8_t* __restrict__ cand, const int* __restrict__ gt_video, int V,
                               int* __restrict__ gt_rank)
@@ -213,10 +191,8 @@ void prefilter_gt_rank_kernel(const float* __restrict__ score, const uint8_t* __
         const u64 mine = fold_word(sc[gt], true, gt);
         for (int v = t; v < V; v += FT) n += cand[v] != 0 && fold_word(sc[v], true, v) > mine;
     }
-    for (int o = 32; o >= 1; o >>= 1) n += __shfl_xor(n, o);
-    if ((t & 63) == 0) red[t >> 6] = n;
-    __syncthreads();
-    if (t == 0) gt_rank[q] = ok ? (red[0] + red[1]) + (red[2] + red[3]) : -1;
+    n = block_sum(n, red);
+    if (t == 0) gt_rank[q] = ok ? n : -1;
 }
 
 }  // namespace

@@ -14,6 +14,7 @@
 //   close    one wave behind the update: step count, running powers of the betas, norm, scale, skipped-step counter and flag.
 #include "common.h"
 #include "embed_sort.h"
+#include "rank_order.h"
 #include "smin_hip.h"
 
 namespace smin {
@@ -22,6 +23,7 @@ constexpr int SORT_THREADS = 1024;       // the sorting workgroup; each thread t
 constexpr int SORT_WAVES = SORT_THREADS / 64;
 static_assert(4 * SORT_THREADS == EMBED_BWD_MAX, "thread t owns the sorted slots 4t .. 4t + 3");
 constexpr int ROWS_THREADS = 256;
+static_assert(ROWS_THREADS == 256, "rank_order.h's block helpers are written for four waves");
 constexpr int ROW_ADAM_THREADS = 128;    // E = 300: 75 quads, two waves
 
 // Workspace of smin_embed_tokens_bwd_rows for n positions: keys [n] u64 | partial [n] f64 | start [n + 1] i32.
@@ -87,16 +89,6 @@ void embed_rows_sort_kernel(const int* __restrict__ tokens, int n, int V, unsign
     if (threadIdx.x == 0) { start[total] = nvalid; count[0] = total; }
 }
 
-// sum over a 256-thread workgroup in a fixed order (butterfly inside each wave, then the four wave sums as (w0 + w1) + (w2 + w3)); valid in thread 0
-__device__ __forceinline__ double rows_block_sum(double acc, double* red /* [4] LDS */)
-{
-#pragma clang fp contract(off)
-    for (int o = 32; o >= 1; o >>= 1) acc += __shfl_xor(acc, o);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    return (red[0] + red[1]) + (red[2] + red[3]);
-}
-
 __global__ __launch_bounds__(ROWS_THREADS)
 void embed_rows_kernel(const float* __restrict__ dqf, const unsigned long long* __restrict__ keys, const int* __restrict__ start,
                        const int* __restrict__ count, int E4, float* __restrict__ rows, double* __restrict__ partial)
@@ -117,7 +109,7 @@ void embed_rows_kernel(const float* __restrict__ dqf, const unsigned long long* 
         acc += (double)v.z * (double)v.z;
         acc += (double)v.w * (double)v.w;
     }
-    const double sum = rows_block_sum(acc, red);
+    const double sum = block_sum_f64_fixed(acc, red);
     if (threadIdx.x == 0) partial[sl] = sum;
 }
 
@@ -130,7 +122,7 @@ void embed_rows_sqnorm_kernel(const double* __restrict__ partial, const int* __r
     const int np = count[0];
     double acc = 0.0;
     for (int i = threadIdx.x; i < np; i += ROWS_THREADS) acc += partial[i];
-    const double sum = rows_block_sum(acc, red);
+    const double sum = block_sum_f64_fixed(acc, red);
     if (threadIdx.x == 0) sqnorm[0] = sum;
 }
 
@@ -317,7 +309,7 @@ void merge_rows_kernel(const MergeLists L, int R, int N, const unsigned* __restr
         acc += (double)v.z * (double)v.z;
         acc += (double)v.w * (double)v.w;
     }
-    const double sum = rows_block_sum(acc, red);
+    const double sum = block_sum_f64_fixed(acc, red);
     if (threadIdx.x == 0) partial[sl] = sum;
 }
 

@@ -11,16 +11,17 @@
 
 #include "common.h"
 #include "pair_pool.h"
+#include "rank_order.h"
 #include "smin_hip.h"
 
 namespace smin {
 namespace {
 
 constexpr int VT = 256;                      // threads of a workgroup
+static_assert(VT == 256, "rank_order.h's block helpers are written for four waves");
 constexpr int VR_TILE = 2048;                // order words of a segment staged in LDS at a time (16 KB)
 constexpr int VR_OWN = 4;                    // pairs a thread ranks per pass over the segment: one LDS read serves them all
 constexpr int VR_MAX_N = 64;
-typedef unsigned long long u64;
 
 __device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
@@ -57,35 +58,10 @@ void group_pool_kernel(const float* __restrict__ pool, const float* __restrict__
     out_cells[g] = N;
 }
 
-__device__ __forceinline__ uint32_t rank_score_ord(float v)        // corpus_score_ord of corpus.hip (score_ord of moments.hip)
-{
-    if (v == 0.f) v = 0.f;                                       // -0 -> +0
-    const uint32_t u = __float_as_uint(v);
-    const uint32_t o = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-    return o ? o : 1u;                                           // 0 is "no candidate"
-}
 // The order word of a candidate, larger = earlier: smin_corpus_topk's Key::hi (score, lower video); 0 for a pair that is no candidate.
 __device__ __forceinline__ u64 rank_word(float score, float cells, int video)
 {
-    if (!(cells > 0.f)) return 0ull;
-    return ((u64)rank_score_ord(score) << 32) | (uint32_t)~((uint32_t)video ^ 0x80000000u);      // int32 ascending -> uint32 descending
-}
-
-__device__ __forceinline__ int block_sum_int(int v, int* red)
-{
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return (red[0] + red[1]) + (red[2] + red[3]);
-}
-__device__ __forceinline__ int block_min_int(int v, int* red)
-{
-    for (int o = 32; o >= 1; o >>= 1) v = min(v, __shfl_xor(v, o));
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return min(min(red[0], red[1]), min(red[2], red[3]));
+    return cells > 0.f ? video_word(score, video) : 0ull;
 }
 
 // One workgroup per query over its segment [beg, end) of the pair lists.  Pass 1: the number of candidates and their best score.
@@ -112,7 +88,7 @@ void video_rank_kernel(const float* __restrict__ pair_score, const float* __rest
     float smax = -INFINITY;
     for (int e = beg + t; e < end; e += VT)
         if (pair_cells[e] > 0.f) { ++mine_n; smax = fmaxf(smax, pair_score[e]); }
-    const int ncand = block_sum_int(mine_n, redi);
+    const int ncand = block_sum(mine_n, redi);
     smax = rank_block_max(smax, redf);
     const int nk = min(ncand, n);
     const bool has_gt = gt_video != nullptr;
@@ -162,7 +138,7 @@ void video_rank_kernel(const float* __restrict__ pair_score, const float* __rest
         out_video[o] = -1;
         out_score[o] = 0.f;
     }
-    best_gt = block_min_int(best_gt, redi);
+    best_gt = block_min(best_gt, redi);
     if (t == 0) {
         out_count[q] = nk;
         gt_rank[q] = best_gt == 0x7fffffff ? -1 : best_gt;
