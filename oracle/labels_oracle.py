@@ -1,8 +1,9 @@
 """TEST INFRASTRUCTURE ONLY -- per-sample restatement of the reference's target construction
-(`/root/reference/dataset.py:95-126, 141-155`), one function per reference method, same torch CPU ops in the same
-order.  PARITY UNPINNED: `dataset.py` cannot be imported in the build container (it needs torchtext and h5py, which
-are not installed, and downloads GloVe at class-definition time, dataset.py:19), and the reference holds no fixtures
-for these functions; the restatement below follows the source text line by line instead."""
+(the reference's `dataset.py:95-126, 141-155`), one function per reference method, same torch CPU ops in the same
+order.  PINNED to the reference's own code: `dataset.py` cannot be imported offline (torchtext, h5py, and GloVe fetched at
+class-definition time, dataset.py:19), but tests/golden/make_golden_targets.py extracts its methods with `ast` and runs them;
+tests/test_targets.py holds the three functions below to gb_targets.npz and `sample_targets` to the collated batches of
+gc_feeder_batch.npz: sm bit for bit, every label and mask exactly, ss / se within one fp32 spacing (the CPU's vector exp)."""
 import math
 
 import numpy as np

@@ -315,7 +315,7 @@ def test_smin_all_ones_moment_mask(dev):
 
 def test_batch_targets_on_device(dev):
     """build_targets on the HIP device against the per-sample restatement of dataset.py:95-155.
-    PARITY UNPINNED (dataset.py is not importable: torchtext / h5py absent; the reference holds no fixtures for it)."""
+    The restatement is pinned to the reference's own functions by tests/test_targets.py (gb_targets.npz, gc_feeder_batch.npz)."""
     import models
     from oracle import labels_oracle as LO
     g = torch.Generator().manual_seed(3)
@@ -435,7 +435,8 @@ def test_inputs_that_require_grad_take_the_python_host(dev):
 def test_target_kernel_and_feeder(dev):
     """csrc/labels.hip (one launch for every mask / target of a batch) against the per-sample restatement of dataset.py:95-155
     and the torch form; then the double-buffered BatchFeeder: what it yields equals direct construction, batch after batch, and
-    feeds SMIN.  PARITY UNPINNED for the targets (dataset.py is not importable here; the reference holds no fixtures for them)."""
+    feeds SMIN.  The targets are pinned to the reference's own code in tests/test_targets.py (kernel, feeder and restatement against
+    gb_targets.npz and gc_feeder_batch.npz, bit for bit); this test keeps the random shapes and the feeder's slot reuse."""
     import models
     from oracle import labels_oracle as LO
     V = models.vml_amd

@@ -250,8 +250,8 @@ def test_loss_and_metric_restatements_match_oracle_and_golden():
 
 def test_batch_targets_match_per_sample_restatement():
     """build_targets (device-side, batched) against the per-sample restatement of dataset.py:95-155.
-    PARITY UNPINNED: dataset.py is not importable here (torchtext / h5py absent) and the reference ships no fixtures
-    for these functions; oracle/labels_oracle.py follows its source text line by line."""
+    The restatement is pinned to the reference's own functions by tests/test_targets.py (gb_targets.npz, gc_feeder_batch.npz),
+    which also holds build_targets itself to them at the edges; this test keeps the random shapes."""
     import models
     from oracle import labels_oracle as LO
     g = torch.Generator().manual_seed(3)

@@ -19,6 +19,7 @@ import torch
 from . import _lib
 from ._host import host_array
 from ._lib import call, ptr
+from .labels import two_sigma_sq
 
 _BATCH_KEYS = ("video_features", "video_mask", "query_features", "query_mask", "length_mask", "moment_mask",
                "sm", "ym", "ss", "ys", "se", "ye", "ya")
@@ -42,6 +43,13 @@ class FedBatch(dict):
     cell_count = None
 
 
+def _annotation_times(times):
+    """A batch's ``times`` as a CPU tensor for staging: float64 where the loader still has the annotation's doubles (a float64 array
+    or tensor, or Python floats), so that build_targets_hip forms the Gaussians' denominator from them; float32 otherwise."""
+    t = times.detach().cpu() if isinstance(times, torch.Tensor) else torch.from_numpy(np.asarray(times))
+    return t if t.dtype == torch.float64 else t.float()
+
+
 def build_targets_hip(times, duration, nfeats, qlen, T, L, Nq, stream=None):
     """All masks and targets of a batch in one launch (device tensors in, dict of device tensors out; dtypes and shapes as
     main.py reads them: video_mask / query_mask uint8 (B, T, 1) / (B, Nq, 1), length_mask / moment_mask / y* bool)."""
@@ -54,9 +62,7 @@ def build_targets_hip(times, duration, nfeats, qlen, T, L, Nq, stream=None):
                sm=f32(B, L, L), ym=u8(B, L, L), ss=f32(B, L), ys=u8(B, L), se=f32(B, L), ye=u8(B, L), ya=u8(B, L))
     # annotation times that still carry their double precision: 2 sigma^2 in double, rounded once (dataset.py:116-119 does the same
     # arithmetic in Python floats); fp32 times: the kernel forms it in double from what it is given
-    den = None
-    if times.dtype == torch.float64:
-        den = (2.0 * ((times[:, 1] - times[:, 0]) / 5.0) ** 2).float().contiguous()
+    den = two_sigma_sq(times).contiguous() if times.dtype == torch.float64 else None
     times, duration = times.float().contiguous(), duration.float().contiguous()
     nfeats = nfeats.to(torch.int32).contiguous()
     qlen32 = qlen.to(torch.int32).contiguous() if qlen is not None else None
@@ -108,7 +114,9 @@ class BatchFeeder:
     """Double-buffered host -> device feeder.  ``feed(sample_batches)`` takes an iterable of host batches
     ``dict(video_features (B,T,Din) float32, query_features (B,Nq,300) float32, nfeats (B,), qlen (B,), times (B,2), duration (B,))``
     (numpy arrays or CPU tensors) and yields device batches with the thirteen entries main.py's loop reads, one batch ahead of
-    the consumer.  Each yielded batch is a ``FedBatch``: its int attribute ``cell_count`` is the number of valid cells of its
+    the consumer.  ``times`` given as float64 (a float64 array or tensor, or Python floats -- what a loader has) stay float64 up to
+    ``build_targets_hip``, which forms the Gaussians' denominator from them in double as dataset.py:116-119 does; this holds for the
+    raw and the window form as well.  fp32 ``times`` are taken as they are.  Each yielded batch is a ``FedBatch``: its int attribute ``cell_count`` is the number of valid cells of its
     ``moment_mask``, from the host's ``nfeats`` (raw form: ``min(raw length, T)``) -- nothing is read back for it.
 
     Raw batch form (chosen by its keys): ``dict(raw_features, tokens (B,Nq) int, times (B,2), duration (B,), spos (B,) optional)``
@@ -155,7 +163,8 @@ class BatchFeeder:
         if "raw_features" in hb:
             return self._stage_raw(slot, hb)
         t = {k: torch.as_tensor(v) for k, v in hb.items()}
-        host = {k: self._pinned(slot, k, t[k].float() if k in ("video_features", "query_features", "times", "duration") else t[k].to(torch.int32))
+        t["times"] = _annotation_times(hb["times"])                          # float64 annotations stay float64 up to build_targets_hip
+        host = {k: self._pinned(slot, k, t[k] if k == "times" else t[k].float() if k in ("video_features", "query_features", "duration") else t[k].to(torch.int32))
                 for k in ("video_features", "query_features", "nfeats", "qlen", "times", "duration")}
         with torch.cuda.device(self.device), torch.cuda.stream(self.copy_stream):
             if slot["consumed"] is not None:
@@ -210,7 +219,7 @@ class BatchFeeder:
                 np.copyto(dst[o:o + p.shape[0]], p.detach().cpu().numpy() if isinstance(p, torch.Tensor) else p, casting="same_kind")
                 o += p.shape[0]
         small = dict(offsets=torch.from_numpy(np.concatenate([[0], np.cumsum(lengths)]).astype(np.int64)), tokens=torch.from_numpy(tok.astype(np.int32)),
-                     times=torch.as_tensor(hb["times"]).float(), duration=torch.as_tensor(hb["duration"]).float())
+                     times=_annotation_times(hb["times"]), duration=torch.as_tensor(hb["duration"]).float())
         if spos is not None:
             small["spos"] = torch.from_numpy(spos)
         host = {k: self._pinned(slot, "raw_" + k, v) for k, v in small.items()}

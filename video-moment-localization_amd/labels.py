@@ -21,13 +21,26 @@ import math
 import torch
 
 
+def two_sigma_sq(times):
+    """The Gaussians' denominator ``2 * sigma**2``, ``sigma = (te - ts) / 5``, of float64 ``times (B, 2)``: formed in double and
+    rounded to fp32 once, as dataset.py:116-119 forms it in Python floats from the annotation.  The divisor is a tensor: on a device
+    torch multiplies by the reciprocal of a scalar divisor, which is not the reference's division.  Returns (B,) float32."""
+    d = times[:, 1] - times[:, 0]
+    sigma = d / torch.full_like(d, 5.0)
+    return (2.0 * (sigma * sigma)).float()
+
+
 def build_targets(times, duration, nfeats, T, L, device=None):
     """times (B, 2) = ground-truth (start, end) in seconds, duration (B,), nfeats (B,) sampled frames (<= T).
+    float64 ``times`` (a loader's annotations: a float64 array or tensor) keep their precision where the reference uses it, in the
+    Gaussians' denominator (``two_sigma_sq``); everything else, and fp32 ``times`` throughout, is fp32 arithmetic.
 
     Returns the dict of batch tensors ``main.py`` reads (``video_mask`` uint8 (B,T,1), ``length_mask`` bool (B,L),
     ``moment_mask`` bool (B,L,L), ``sm`` (B,L,L), ``ym``, ``ss``/``se`` (B,L), ``ys``/``ye``, ``ya`` bool (B,L)),
     all on ``device``.  No host loop, no sync."""
-    times = torch.as_tensor(times, dtype=torch.float32, device=device)
+    times = torch.as_tensor(times, device=device)
+    den = two_sigma_sq(times).unsqueeze(1) if times.dtype == torch.float64 else None
+    times = times.to(torch.float32)
     device = times.device
     duration = torch.as_tensor(duration, dtype=torch.float32, device=device)
     nfeats = torch.as_tensor(nfeats, device=device).to(torch.int64).clamp(max=T)
@@ -49,9 +62,11 @@ def build_targets(times, duration, nfeats, T, L, device=None):
     union = (torch.maximum(ej, ge) - torch.minimum(si, gs)).clamp(min=0.0)
     sm = inter / union                                                            # 0/0 -> nan exactly where the reference has it
 
-    sigma = (te - ts) / 5.0
-    ss = torch.exp(-(s_times - ts) ** 2 / (2.0 * sigma ** 2))
-    se = torch.exp(-(e_times - te) ** 2 / (2.0 * sigma ** 2))
+    if den is None:
+        sigma = (te - ts) / 5.0
+        den = 2.0 * sigma ** 2
+    ss = torch.exp(-(s_times - ts) ** 2 / den)
+    se = torch.exp(-(e_times - te) ** 2 / den)
     ya = (s_times >= ts) & (e_times <= te)
     return dict(video_mask=video_mask, length_mask=length_mask, moment_mask=moment_mask, sm=sm, ym=sm > 0.5,
                 ss=ss, ys=ss > 0.5, se=se, ye=se > 0.5, ya=ya)
