@@ -1216,6 +1216,60 @@ int smin_survivors_admit(void* stream, const int32_t* copy_src, const float* fv,
  *   a NULL pointer other than gt_video. */
 int smin_prefilter_gt_rank(void* stream, const float* score, const uint8_t* cand, const int32_t* gt_video, int Q, int V, int32_t* gt_rank);
 
+/* ---- compact video banks: fv [V][T][D] stored as codes, R = V T rows of D values, decoded by ONE fp32
+ * multiplication in front of the arithmetic the fp32 kernels do, so a compact bank gives the bits of an fp32 bank of the decoded values.
+ *   SMIN_BANK_BF16: codes [R][D] uint16, the upper half of the fp32 word rounded to nearest even, u' = (u + 0x7fff + ((u >> 16) & 1)) >> 16;
+ *     a NaN becomes the quiet NaN 0x7fc0 (the rounding add could carry it to an infinity); decode = bits << 16; no scale (NULL).
+ *   SMIN_BANK_INT8: codes [R][D] int8 and scale [R] fp32, per row: amax = max_d |x[d]|, scale = amax / 127.0f and q[d] =
+ *     clamp(rintf(x[d] / scale), -127, 127), both divisions correctly rounded (-128 is never produced); amax == 0 gives scale 0 and
+ *     codes 0; a row holding a NaN or an infinity gives scale NaN and codes 0 (it decodes to NaN); decode = (float)q * scale.
+ * Denormal inputs are not pinned. */
+#define SMIN_BANK_BF16 1
+#define SMIN_BANK_INT8 2
+
+/* smin_bank_encode: fv [R][D] fp32 -> codes (and scale [R] for SMIN_BANK_INT8; NULL for SMIN_BANK_BF16); one launch, one wave per row:
+ * a lane owns the quads lane, lane + 64, ... of the row (float4 loads; one 4-byte (int8) or 8-byte (bf16) store per quad).
+ * Arithmetic as above.  The row's amax is a maximum (a butterfly over the wave): any order gives the same bits.
+ * Limits.  R >= 1, D >= 4, D % 4 == 0, R D < 2^40; fv 16-byte, codes 8-byte (bf16) or 4-byte (int8) aligned.  No atomics, no host
+ * read, capturable.  Determinism.  The same bits every run.
+ * Rejection.  A nonzero status before the launch, the outputs untouched, for a size or mode out of range, a NULL pointer (scale only
+ * where the mode has one), a scale given to SMIN_BANK_BF16 or a misaligned pointer. */
+int smin_bank_encode(void* stream, const float* fv, int64_t R, int D, int mode, void* codes, float* scale);
+
+/* smin_bank_decode: the decoder alone: out [R][D] fp32 = decode(codes, scale); one launch, one quad per thread.
+ * Limits, determinism and rejection as smin_bank_encode (out 16-byte aligned). */
+int smin_bank_decode(void* stream, const void* codes, const float* scale, int64_t R, int D, int mode, float* out);
+
+/* smin_pair_assemble_compact: smin_pair_assemble over a compact video bank: f[p][t][:] = decode(codes[vi[p]][t][:]) * fs_bank[qi[p]][:]
+ * -- the decode multiplication, then the gate multiplication, each one fp32 product --, fw and fs gathered bit for bit: the bits of
+ * smin_pair_assemble on smin_bank_decode's output.  One launch: where D % 16 == 0 a thread takes 16 values of a frame (one 16-byte
+ * load of int8 codes, two of bf16) and writes four float4; otherwise one quad per thread.  Both indices are clamped to their banks
+ * before they form an address.
+ * Limits.  As smin_pair_assemble; codes 16-byte aligned.  No atomics, no host read, capturable; the same bits every run.
+ * Rejection.  A nonzero status before the launch, the outputs untouched, for a size or mode out of range, a NULL pointer (scale only
+ * where the mode has one) or a misaligned codes pointer. */
+int smin_pair_assemble_compact(void* stream, const void* codes, const float* scale, int mode, const float* fs_bank, const float* fw_bank,
+                               const int32_t* video_index, const int32_t* query_index, int P, int V, int Q, int T, int Nq, int D, float* f,
+                               float* fw, float* fs);
+
+/* smin_prefilter_scores_compact: smin_prefilter_scores with (codes, scale, mode) in place of fv.  Stage 1 is the same contraction
+ * with an A-operand loader that decodes four values at a time (csrc/gemm.h PlainMatH / CodeMatQ: an int8 row carries its scale), so the
+ * engine is handed the fp32 values of the decoded bank: the bits of smin_prefilter_scores on smin_bank_decode's output, in every
+ * mode of smin_set_gemm_mode.  Stage 2 and the workspace (smin_prefilter_ws_bytes) are shared unchanged.
+ * Limits and rejection as smin_prefilter_scores, plus the mode and scale rules of smin_bank_encode. */
+int smin_prefilter_scores_compact(void* stream, const void* codes, const float* scale, int mode, const float* fs, const float* w,
+                                  const float* b, const uint8_t* lmask, const uint8_t* mm, int Q, int V, int T, int L, int C, int D, float tau,
+                                  float* score, float* pool, float* cells, float* pm0, float* ps0, float* pe0, void* ws, size_t ws_bytes);
+
+/* smin_survivors_admit_compact: smin_survivors_admit for a compact bank: the admitted videos' code rows (T D esize bytes, 16 at a
+ * time where a row's byte count is a multiple of 16, else 4 at a time), their T scales (SMIN_BANK_INT8) and the three masks, bit for bit;
+ * rows with copy_src -1 (or naming no video of the shard) are left alone.  One launch, one workgroup per (row, 2048 pieces of its code row).
+ * Limits.  As smin_survivors_admit with T D esize / 4 <= 2048 * 65535; codes and out_codes 16-byte aligned.  Rejection.  As smin_survivors_admit, plus the mode and scale rules of smin_bank_encode. */
+int smin_survivors_admit_compact(void* stream, const int32_t* copy_src, const void* codes, const float* scale, int mode,
+                                 const uint8_t* video_mask, const uint8_t* length_mask, const uint8_t* moment_mask, int R, int Vs, int T, int L,
+                                 int D, void* out_codes, float* out_scale, uint8_t* out_video_mask, uint8_t* out_length_mask,
+                                 uint8_t* out_moment_mask);
+
 /* ---- stand-alone fp32 MFMA GEMM  C[M][N] = A[M][K] * B[N][K]^T  (used by tests and bench.py's
  * roofline probe; same engine as every contraction above). */
 int smin_gemm_nt(void* stream, const float* A, const float* Bm, float* Cm, int M, int N, int K);

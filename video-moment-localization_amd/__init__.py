@@ -34,6 +34,7 @@ from .moments import pair_pool, pair_pool_torch, group_pool, group_pool_torch, r
 from .moments import reweight_moments, reweight_moments_torch  # noqa: F401
 from .moments import prefilter_scores, prefilter_scores_torch, prefilter_select, prefilter_select_torch, prefilter_maps  # noqa: F401
 from .moments import prefilter_fold, prefilter_fold_torch, survivors_admit, survivors_admit_torch, prefilter_gt_rank, prefilter_gt_rank_torch  # noqa: F401
+from .moments import bank_encode, bank_encode_torch, bank_decode, bank_decode_torch, BANK_STORAGES  # noqa: F401
 from .moments import merge_search_weighted, merge_search_weighted_torch  # noqa: F401
 from .moments import merge_search_windows_weighted, merge_search_windows_weighted_torch  # noqa: F401
 from .moments import span_ious, span_ious_torch, compute_span_ious, compute_span_ious_torch  # noqa: F401

@@ -92,7 +92,7 @@ _torch_ops = None
 
 def load_torch():
     """The torch-extension binding (csrc/torch_binding.cpp): registers torch.ops.smin_hip.{smin_forward, smin_score, smin_loss, adam_step,
-    smin_encode_videos, smin_encode_queries, smin_score_pairs, smin_corpus_span_topk, smin_forward_pairs, smin_pair_rank_loss} -- the whole forward as one library call with its autograd graph built in
+    smin_encode_videos, smin_encode_queries, smin_score_pairs, smin_score_pairs_compact, smin_corpus_span_topk, smin_forward_pairs, smin_pair_rank_loss} -- the whole forward as one library call with its autograd graph built in
     C++, its forward-only scoring twin, the optimizer step over a parameter list, the corpus-search operators (the two encoders
     alone, the scorer over indexed pairs of their banks, the ranking of span-valued moments across videos) and the contrastive term over a pair plan.  Raises if the library is missing."""
     global _torch_ops
@@ -119,7 +119,7 @@ def ptr(t):
         raise SminHipError("the SMIN hot path runs on a HIP device only (got a CPU tensor); there is no CPU fallback")
     if not t.is_contiguous():
         raise SminHipError("internal error: non-contiguous tensor handed to the C ABI")
-    if t.dtype not in (torch.float32, torch.int32, torch.uint8, torch.float64, torch.bool, torch.int64):
+    if t.dtype not in (torch.float32, torch.int32, torch.uint8, torch.float64, torch.bool, torch.int64, torch.bfloat16, torch.int8):
         raise SminHipError(f"unsupported dtype {t.dtype}")
     return ctypes.c_void_p(t.data_ptr())
 

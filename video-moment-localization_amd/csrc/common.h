@@ -38,6 +38,10 @@ int launch_score_heads(hipStream_t st, const float* fb, int B, int L, int D, con
 size_t nms_hits_stage_bytes(int B, int L, int k, int nn, int nm);
 int nms_hits_stage(hipStream_t st, const float* pm, const float* ps, const float* pe, const uint8_t* mm, const float* sm, int B, int L, int k,
                    float nms_thresh, const int* n_list, int nn, const float* m_list, int nm, void* ws, float** hits_out, float* top1);
+// bank_codec.hip: what every entry point over a compact bank checks of (codes, scale, mode), codes aligned to `align` bytes; and the
+// bytes of four codes, the loaders' unit (mode 1 is SMIN_BANK_BF16)
+bool bank_code_ok(const void* codes, const float* scale, int mode, int align);
+static inline int bank_quad_bytes(int mode) { return mode == 1 ? 8 : 4; }
 }  // namespace smin
 
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }

@@ -151,6 +151,27 @@ struct CatMatH {
         return ldg4_bf16(q + r.off + (c - sg * w));
     }
 };
+// Compact video banks (smin_hip.h, SMIN_BANK_*; bank_codec.hip): four int8 codes of one 32-bit word times their row's scale -- the
+// decoder's one fp32 multiplication per value.  The product is ROUNDED: without the pragma the compiler contracts it with an addition
+// that follows in the caller (the bf16-core modes subtract the operand's upper part: v_fma_f32 instead of v_mul_f32 + v_sub_f32), and
+// the engine would see other values than the decoded bank's.
+__device__ __forceinline__ float4 dec4_q8(unsigned w, float s) {
+#pragma clang fp contract(off)
+    const int v = (int)w;
+    return make_float4((float)((v << 24) >> 24) * s, (float)((v << 16) >> 24) * s, (float)((v << 8) >> 24) * s, (float)(v >> 24) * s);
+}
+// A compact bank's rows [rows][ld] as an A operand: at() hands the engine the decoded fp32 values, so a contraction over codes has the
+// bits of the same contraction over the decoded bank.  The Row carries the row's scale, as ShiftRowsMat's carries its factor.  (A
+// SMIN_BANK_BF16 bank is a PlainMatH.)
+struct CodeMatQ {                       // SMIN_BANK_INT8
+    const signed char* p; const float* scale; int ld;
+    struct Row { const signed char* p; float s; };
+    struct Key { float s; };
+    __device__ __forceinline__ Row row(int r) const { return Row{p + (size_t)r * ld, scale[r]}; }
+    __device__ __forceinline__ Key key(int r) const { return Key{scale[r]}; }
+    __device__ __forceinline__ Row resolve(const Key& k, int r) const { return Row{p + (size_t)r * ld, k.s}; }
+    __device__ __forceinline__ float4 at(const Row& r, int c) const { return dec4_q8(*reinterpret_cast<const unsigned*>(r.p + c), r.s); }
+};
 // ------------------------------------------------------------------ helpers
 __device__ __forceinline__ f32x16 mfma32(float a, float b, f32x16 c) {
     return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0);

@@ -5,6 +5,8 @@
 //                          transposed so that a pair's T projections of a head are contiguous;
 //                          stage 2: one workgroup per (q, v) stages the pair's 3 T projections in LDS, forms every cell's range sum as
 //                          a running sum along its row (one wave), applies the sigmoid heads (all waves) and pools the fused scores through pair_pool.h.
+//   smin_prefilter_scores_compact  the same over a compact bank (bank_codec.hip): stage 1's A operand is a loader that decodes, so the
+//                          engine sees the decoded bank's fp32 values and the result has smin_prefilter_scores' bits on them.
 //   smin_prefilter_select  each query's best M videos of smin_video_rank's ranks, ascending by video, as the pair lists of a search.
 //   smin_prefilter_maps_bwd  the gradients of stage 2's maps by fv, fs and the heads (described where it begins below).
 // No atomics, plain stores, every output element written, every sum in an order that depends on the arguments only.
@@ -192,13 +194,18 @@ extern "C" size_t smin_prefilter_ws_bytes(int Q, int V, int T, int D)
     return pf_layout(Q, V, T, D).end * sizeof(float);
 }
 
-extern "C" int smin_prefilter_scores(void* stream, const float* fv, const float* fs, const float* w, const float* b, const uint8_t* lmask,
-                                     const uint8_t* mm, int Q, int V, int T, int L, int C, int D, float tau, float* score, float* pool,
-                                     float* cells, float* pm0, float* ps0, float* pe0, void* ws, size_t ws_bytes)
+// smin_prefilter_scores' body over any A operand that hands the engine the bank's fp32 values: PlainMat (fp32), PlainMatH (bf16
+// codes) or CodeMatQ (int8 codes and the rows' scales).  `bank_ok`: the caller's check of the bank's pointers.
+namespace smin {
+namespace {
+template <class AM>
+int prefilter_scores_over(void* stream, const AM& bank, bool bank_ok, const float* fs, const float* w, const float* b, const uint8_t* lmask,
+                          const uint8_t* mm, int Q, int V, int T, int L, int C, int D, float tau, float* score, float* pool, float* cells,
+                          float* pm0, float* ps0, float* pe0, void* ws, size_t ws_bytes)
 {
     SMIN_REQUIRE(pf_sizes_ok(Q, V, T, D) && L >= 1 && L <= PF_MAX_L && T >= L && C >= 1 && C <= 0x10000);
     SMIN_REQUIRE(rank_temperature(tau));
-    SMIN_REQUIRE(fv && fs && w && b && lmask && mm && score && pool && cells && ws);
+    SMIN_REQUIRE(bank_ok && fs && w && b && lmask && mm && score && pool && cells && ws);
     SMIN_REQUIRE((pm0 && ps0 && pe0) || (!pm0 && !ps0 && !pe0));
     SMIN_REQUIRE(ws_bytes >= smin_prefilter_ws_bytes(Q, V, T, D));
     const hipStream_t st = (hipStream_t)stream;
@@ -209,13 +216,36 @@ extern "C" int smin_prefilter_scores(void* stream, const float* fv, const float*
     const size_t total4 = (size_t)lay.N3 * (D / 4);
     hipLaunchKernelGGL(prefilter_operand_kernel, dim3((unsigned)((total4 + PT - 1) / PT)), dim3(PT), 0, st, fs, w, Q, D, total4, operand);
     SMIN_LAUNCH_CHECK();
-    const int rc = launch_gemm_nt(st, PlainMat{fv, D}, PlainMat{operand, D}, EpProjT{proj, lay.ld}, V * T, lay.N3, D);
+    const int rc = launch_gemm_nt(st, bank, PlainMat{operand, D}, EpProjT{proj, lay.ld}, V * T, lay.N3, D);
     if (rc) return rc;
     const size_t lds = sizeof(float) * ((size_t)3 * T + (size_t)L * L + 4 * L + 4);
     hipLaunchKernelGGL(prefilter_cell_kernel, dim3(V, Q), dim3(PT), lds, st, proj, lay.ld, b, lmask, mm, V, T, L, C, tau, score, pool, cells,
                        pm0, ps0, pe0);
     SMIN_LAUNCH_CHECK();
     return 0;
+}
+}  // namespace
+}  // namespace smin
+
+extern "C" int smin_prefilter_scores(void* stream, const float* fv, const float* fs, const float* w, const float* b, const uint8_t* lmask,
+                                     const uint8_t* mm, int Q, int V, int T, int L, int C, int D, float tau, float* score, float* pool,
+                                     float* cells, float* pm0, float* ps0, float* pe0, void* ws, size_t ws_bytes)
+{
+    return prefilter_scores_over(stream, PlainMat{fv, D}, fv != nullptr, fs, w, b, lmask, mm, Q, V, T, L, C, D, tau, score, pool, cells, pm0, ps0,
+                                 pe0, ws, ws_bytes);
+}
+
+extern "C" int smin_prefilter_scores_compact(void* stream, const void* codes, const float* scale, int mode, const float* fs, const float* w,
+                                             const float* b, const uint8_t* lmask, const uint8_t* mm, int Q, int V, int T, int L, int C, int D,
+                                             float tau, float* score, float* pool, float* cells, float* pm0, float* ps0, float* pe0, void* ws,
+                                             size_t ws_bytes)
+{
+    const bool ok = bank_code_ok(codes, scale, mode, bank_quad_bytes(mode));
+    if (mode == SMIN_BANK_BF16)
+        return prefilter_scores_over(stream, PlainMatH{static_cast<const unsigned short*>(codes), D}, ok, fs, w, b, lmask, mm, Q, V, T, L, C, D, tau,
+                                     score, pool, cells, pm0, ps0, pe0, ws, ws_bytes);
+    return prefilter_scores_over(stream, CodeMatQ{static_cast<const signed char*>(codes), scale, D}, ok, fs, w, b, lmask, mm, Q, V, T, L, C, D, tau,
+                                 score, pool, cells, pm0, ps0, pe0, ws, ws_bytes);
 }
 
 extern "C" int smin_prefilter_select(void* stream, const int32_t* pair_rank, int Q, int V, int M, int32_t* sel_video, int32_t* sel_query)

@@ -4,7 +4,8 @@
 //                          n_new = min(M, seen + Vs) elements of the union of the slots' videos and the shard's, in the order
 //                          smin_video_rank and smin_prefilter_select give one bank of all the videos; incumbents that stay keep their
 //                          slots, and copy_src names, per slot, the shard video it must receive.
-//   smin_survivors_admit   copies those videos' fv rows and masks from the shard's bank into the bank of survivors.
+//   smin_survivors_admit   copies those videos' fv rows and masks from the shard's bank into the bank of survivors;
+//   smin_survivors_admit_compact  the same for a compact bank (bank_codec.hip): code rows, the rows' scales and the masks.
 //   smin_prefilter_gt_rank the first-stage rank of each query's own video over the corpus' concatenated scores, O(V) per query.
 // How an element finds its place: by COUNTING, as smin_video_rank does -- every element of the union (old slots and shard videos
 // alike) gets one 64-bit order word, the words go through LDS 2048 at a time and an element's place is the number of words larger
@@ -175,6 +176,31 @@ void survivors_admit_kernel(const int* __restrict__ copy_src, const float* __res
     for (int i = t; i < LL; i += FT) out_mm[(size_t)row * LL + i] = mm[(size_t)src * LL + i];
 }
 
+// survivors_admit_kernel for a compact bank: a video's code row as `nw` words of type Wd (uint4 where the row's byte count is a multiple
+// of 16, else 32-bit words), its T scales (has_scale: int8 banks) and the masks with the workgroup of chunk 0.
+template <class Wd>
+__global__ __launch_bounds__(FT)
+void survivors_admit_compact_kernel(const int* __restrict__ copy_src, const Wd* __restrict__ codes, const float* __restrict__ scale,
+                                    const uint8_t* __restrict__ vmask, const uint8_t* __restrict__ lmask, const uint8_t* __restrict__ mm, int Vs,
+                                    int T, int L, int nw, Wd* __restrict__ out_codes, float* __restrict__ out_scale,
+                                    uint8_t* __restrict__ out_vmask, uint8_t* __restrict__ out_lmask, uint8_t* __restrict__ out_mm)
+{
+    const int row = blockIdx.x, chunk = blockIdx.y, t = threadIdx.x;
+    const int src = copy_src[row];
+    if (src < 0 || src >= Vs) return;
+    const Wd* s = codes + (size_t)src * nw;
+    Wd* d = out_codes + (size_t)row * nw;
+    const int i1 = min(nw, (chunk + 1) * ADMIT_CHUNK);
+    for (int i = chunk * ADMIT_CHUNK + t; i < i1; i += FT) d[i] = s[i];
+    if (chunk != 0) return;
+    const int LL = L * L;
+    if (scale != nullptr)
+        for (int i = t; i < T; i += FT) out_scale[(size_t)row * T + i] = scale[(size_t)src * T + i];
+    for (int i = t; i < T; i += FT) out_vmask[(size_t)row * T + i] = vmask[(size_t)src * T + i];
+    for (int i = t; i < L; i += FT) out_lmask[(size_t)row * L + i] = lmask[(size_t)src * L + i];
+    for (int i = t; i < LL; i += FT) out_mm[(size_t)row * LL + i] = mm[(size_t)src * LL + i];
+}
+
 // One workgroup per query: the candidates whose word is larger than the own video's, counted by thread (v = t, t + 256, ...), then
 // over the workgroup.
 __global__ __launch_bounds__(FT)
@@ -226,6 +252,32 @@ extern "C" int smin_survivors_admit(void* stream, const int32_t* copy_src, const
     const int TD4 = (int)((long long)T * D / 4);
     hipLaunchKernelGGL(survivors_admit_kernel, dim3(R, cdiv(TD4, ADMIT_CHUNK)), dim3(FT), 0, (hipStream_t)stream, copy_src, fv, video_mask,
                        length_mask, moment_mask, Vs, T, L, TD4, out_fv, out_video_mask, out_length_mask, out_moment_mask);
+    SMIN_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int smin_survivors_admit_compact(void* stream, const int32_t* copy_src, const void* codes, const float* scale, int mode,
+                                            const uint8_t* video_mask, const uint8_t* length_mask, const uint8_t* moment_mask, int R, int Vs, int T,
+                                            int L, int D, void* out_codes, float* out_scale, uint8_t* out_video_mask, uint8_t* out_length_mask,
+                                            uint8_t* out_moment_mask)
+{
+    SMIN_REQUIRE(R >= 1 && Vs >= 1 && T >= 1 && L >= 1 && L <= 4096 && D >= 4 && D % 4 == 0);
+    SMIN_REQUIRE(bank_code_ok(codes, scale, mode, 16) && bank_code_ok(out_codes, out_scale, mode, 16));
+    const long long row_bytes = (long long)T * D * (mode == SMIN_BANK_BF16 ? 2 : 1);
+    SMIN_REQUIRE(row_bytes / 4 <= (long long)ADMIT_CHUNK * 65535);
+    SMIN_REQUIRE(copy_src && video_mask && length_mask && moment_mask && out_video_mask && out_length_mask && out_moment_mask);
+    const hipStream_t st = (hipStream_t)stream;
+    if (row_bytes % 16 == 0) {
+        const int nw = (int)(row_bytes / 16);
+        hipLaunchKernelGGL(survivors_admit_compact_kernel<uint4>, dim3(R, cdiv(nw, ADMIT_CHUNK)), dim3(FT), 0, st, copy_src, (const uint4*)codes, scale,
+                           video_mask, length_mask, moment_mask, Vs, T, L, nw, (uint4*)out_codes, out_scale, out_video_mask, out_length_mask,
+                           out_moment_mask);
+    } else {
+        const int nw = (int)(row_bytes / 4);
+        hipLaunchKernelGGL(survivors_admit_compact_kernel<uint32_t>, dim3(R, cdiv(nw, ADMIT_CHUNK)), dim3(FT), 0, st, copy_src, (const uint32_t*)codes,
+                           scale, video_mask, length_mask, moment_mask, Vs, T, L, nw, (uint32_t*)out_codes, out_scale, out_video_mask,
+                           out_length_mask, out_moment_mask);
+    }
     SMIN_LAUNCH_CHECK();
     return 0;
 }

@@ -423,10 +423,14 @@ Tensor sum_list(const std::vector<Tensor>& ts)
 // smin_forward_pairs (train): no encoded banks -- the run encodes the V videos and Q queries itself (video_features / query_features
 // then have a row per video / per query) from the per-video and per-query masks vmask_v / qmask_q, and keeps what the backward needs:
 // the CSR groupings of the pairs by video and by query (smin_pair_assemble_bwd).
+// A compact video bank (smin_score_pairs_compact; csrc/bank_codec.hip): storage = SMIN_BANK_BF16 / SMIN_BANK_INT8, fv then holds the
+// codes (bf16 / int8) and fv_scale the int8 rows' scales (V, T); storage 0 is the fp32 bank.
 struct PairBank {
     Tensor fv, fw, fs, vi, qi;
     bool train = false;
     Tensor vmask_v, qmask_q, v_ptr, v_pairs, q_ptr, q_pairs;
+    int storage = 0;
+    Tensor fv_scale;
 };
 
 // The boolean options of the operators (their keyword arguments, named as the SMIN attributes) as one word.
@@ -554,8 +558,8 @@ struct SminCore : torch::autograd::Function<SminCore> {
         TORCH_CHECK(!bank || scoring != bank->train, "given banks are scored; a training run encodes its own");
         const bool own_bank = bank && bank->train;
         const ParamList& P = st.prm = ParamList(prm_in, prm_in.size(), nl);
-        const Tensor& like = bank && !own_bank ? bank->fv : video_features;
-        const int64_t Bq = bank ? bank->vi.size(0) : video_features.size(0), Tn = like.size(1);
+        const Tensor& like = bank && !own_bank ? (bank->storage ? bank->fw : bank->fv) : video_features;     // (fp32: its options make the run's tensors)
+        const int64_t Bq = bank ? bank->vi.size(0) : video_features.size(0), Tn = bank && !own_bank ? bank->fv.size(1) : like.size(1);
         TORCH_CHECK(Tn == T, "ProposalGeneration was built for T=", T, " but got ", Tn, " frames");
         const auto [dev, opt, B, D, Nq, dl, Li, Ci, Ti, curs, side] = Dims(like, Bq, P, T, L, C, maxq, flags);
         HStream prep = (flags & F_OVERLAP_PREP) ? side : curs;
@@ -683,8 +687,12 @@ struct SminCore : torch::autograd::Function<SminCore> {
             }
             // both encoders ran once per video and per query: the pairs' f = f_v * f_s, f_w and f_s in one launch (csrc/corpus.hip)
             fw = at::empty({Bq, maxq, (int64_t)D}, opt); fs = at::empty({Bq, (int64_t)D}, opt);
-            SMIN_CK(smin_pair_assemble(cur(), fp(bfv), fp(bfs), fp(bfw), ip(bank->vi), ip(bank->qi), B, i32(bfv.size(0)), i32(bfs.size(0)), Ti, Nq, D, fpm(f), fpm(fw),
-                                       fpm(fs)));
+            if (bank->storage)
+                SMIN_CK(smin_pair_assemble_compact(cur(), bfv.const_data_ptr(), bank->fv_scale.defined() ? fp(bank->fv_scale) : nullptr, bank->storage, fp(bfs), fp(bfw),
+                                                   ip(bank->vi), ip(bank->qi), B, i32(bfv.size(0)), i32(bfs.size(0)), Ti, Nq, D, fpm(f), fpm(fw), fpm(fs)));
+            else
+                SMIN_CK(smin_pair_assemble(cur(), fp(bfv), fp(bfs), fp(bfw), ip(bank->vi), ip(bank->qi), B, i32(bfv.size(0)), i32(bfs.size(0)), Ti, Nq, D, fpm(f), fpm(fw),
+                                           fpm(fs)));
         } else {
             std::tie(fw, fs) = query_encoder(st.lstm, P, query_features, st.len32, maxq, H, scoring);
             if (projection_ready) {
@@ -1542,28 +1550,55 @@ std::tuple<Tensor, Tensor> smin_encode_queries(const Tensor& query_features, con
 // SMIN.score_pairs: smin_score for the P pairs (video_index[p], query_index[p]) of banks fv / fw / fs.  The four byte masks are gathered
 // per pair, smin_step_prologue runs on the gathered masks, smin_pair_assemble stands where smin_score has its backbone, and from
 // "layout, part 2" on it is the code smin_score runs (SminCore::run).  Outputs as smin_score's, one row per pair.
+Scores score_pairs_of(const char* op, const Tensor& fv, const std::optional<Tensor>& scale, int storage, const Tensor& fw, const Tensor& fs, const Tensor& video_mask,
+                      const Tensor& query_mask_in, const Tensor& length_mask, const Tensor& moment_mask, const Tensor& video_index, const Tensor& query_index,
+                      at::TensorList prm, int64_t T, int64_t L, int64_t C, int64_t num_smi_layers, int64_t max_query_length, int64_t lstm_hidden_size, int64_t flags,
+                      std::optional<int64_t> known_cell_count)
+{
+    const int64_t maxq = max_query_length;
+    const auto code = storage == 0 ? at::kFloat : storage == SMIN_BANK_BF16 ? at::kBFloat16 : at::kChar;
+    TORCH_CHECK(fv.dim() == 3 && fw.dim() == 3 && fs.dim() == 2 && fv.scalar_type() == code && fw.scalar_type() == at::kFloat && fs.scalar_type() == at::kFloat, op,
+                ": fv (V, T, D) ", storage == 0 ? "float32" : "bfloat16 (no scale) or int8 (with scale)", ", fw (Q, max_query_length, D), fs (Q, D) float32");
+    const int64_t V = fv.size(0), Q = fs.size(0), D = fv.size(2);
+    TORCH_CHECK(V >= 1 && Q >= 1 && fv.size(1) == T && fw.size(0) == Q && fw.size(1) == maxq && fw.size(2) == D && fs.size(1) == D && D == 2 * lstm_hidden_size, op,
+                ": the banks do not fit each other or the model (T = ", T, ", max_query_length = ", maxq, ", D = ", 2 * lstm_hidden_size, ")");
+    TORCH_CHECK(!scale || scale->is_cuda(), op, " runs on a HIP device only (there is no CPU fallback)");
+    TORCH_CHECK(!scale || (scale->scalar_type() == at::kFloat && scale->dim() == 2 && scale->size(0) == V && scale->size(1) == T), op,
+                ": scale (V, T) float32, one per frame");
+    TORCH_CHECK(video_index.dim() == 1 && query_index.dim() == 1 && video_index.size(0) == query_index.size(0) && video_index.size(0) >= 1, op,
+                ": video_index and query_index are (P,) with P >= 1");
+    TORCH_CHECK(video_mask.size(0) == V && length_mask.size(0) == V && moment_mask.size(0) == V && query_mask_in.size(0) == Q, op,
+                ": video_mask, length_mask and moment_mask have a row per video, query_mask a row per query");
+    Tensor query_mask = query_mask_in.reshape({Q, -1});
+    TORCH_CHECK(query_mask.size(1) == maxq, op, ": query_mask (Q, max_query_length) as the query bank keeps it");
+    CoreCall call{video_mask, query_mask, length_mask, moment_mask, T, L, C, num_smi_layers, maxq, lstm_hidden_size, flags, known_cell_count.value_or(-1), true};
+    call.bank = PairBank{cont(fv.detach()), cont(fw.detach()), cont(fs.detach()), cont(video_index.to(at::kInt)), cont(query_index.to(at::kInt))};
+    call.bank->storage = storage;
+    if (scale) call.bank->fv_scale = cont(scale->detach());
+    return scores(run_call(op, {&fv, &fw, &fs, &video_mask, &query_mask_in, &length_mask, &moment_mask, &video_index, &query_index}, std::move(call), Tensor(), Tensor(), prm));
+}
+
 Scores smin_score_pairs(const Tensor& fv, const Tensor& fw, const Tensor& fs, const Tensor& video_mask, const Tensor& query_mask_in, const Tensor& length_mask,
                         const Tensor& moment_mask, const Tensor& video_index, const Tensor& query_index, at::TensorList prm, int64_t T, int64_t L, int64_t C,
                         int64_t num_smi_layers, int64_t max_query_length, int64_t lstm_hidden_size, bool overlap_boundary, bool overlap_prep, bool param_prep_kernel,
                         bool bf16_operand_storage, std::optional<int64_t> known_cell_count)
 {
-    const int64_t maxq = max_query_length;
-    TORCH_CHECK(fv.dim() == 3 && fw.dim() == 3 && fs.dim() == 2 && fv.scalar_type() == at::kFloat && fw.scalar_type() == at::kFloat && fs.scalar_type() == at::kFloat,
-                "smin_score_pairs: fv (V, T, D), fw (Q, max_query_length, D), fs (Q, D) float32");
-    const int64_t V = fv.size(0), Q = fs.size(0), D = fv.size(2);
-    TORCH_CHECK(V >= 1 && Q >= 1 && fv.size(1) == T && fw.size(0) == Q && fw.size(1) == maxq && fw.size(2) == D && fs.size(1) == D && D == 2 * lstm_hidden_size,
-                "smin_score_pairs: the banks do not fit each other or the model (T = ", T, ", max_query_length = ", maxq, ", D = ", 2 * lstm_hidden_size, ")");
-    TORCH_CHECK(video_index.dim() == 1 && query_index.dim() == 1 && video_index.size(0) == query_index.size(0) && video_index.size(0) >= 1,
-                "smin_score_pairs: video_index and query_index are (P,) with P >= 1");
-    TORCH_CHECK(video_mask.size(0) == V && length_mask.size(0) == V && moment_mask.size(0) == V && query_mask_in.size(0) == Q,
-                "smin_score_pairs: video_mask, length_mask and moment_mask have a row per video, query_mask a row per query");
-    Tensor query_mask = query_mask_in.reshape({Q, -1});
-    TORCH_CHECK(query_mask.size(1) == maxq, "smin_score_pairs: query_mask (Q, max_query_length) as the query bank keeps it");
-    const int64_t flags = flag_word(overlap_boundary, overlap_prep, param_prep_kernel, bf16_operand_storage);
-    CoreCall call{video_mask, query_mask, length_mask, moment_mask, T, L, C, num_smi_layers, maxq, lstm_hidden_size, flags, known_cell_count.value_or(-1), true};
-    call.bank = PairBank{cont(fv.detach()), cont(fw.detach()), cont(fs.detach()), cont(video_index.to(at::kInt)), cont(query_index.to(at::kInt))};
-    return scores(run_call("smin_score_pairs", {&fv, &fw, &fs, &video_mask, &query_mask_in, &length_mask, &moment_mask, &video_index, &query_index}, std::move(call),
-                           Tensor(), Tensor(), prm));
+    return score_pairs_of("smin_score_pairs", fv, std::nullopt, 0, fw, fs, video_mask, query_mask_in, length_mask, moment_mask, video_index, query_index, prm, T, L, C,
+                          num_smi_layers, max_query_length, lstm_hidden_size, flag_word(overlap_boundary, overlap_prep, param_prep_kernel, bf16_operand_storage),
+                          known_cell_count);
+}
+
+// SMIN.score_pairs over a compact video bank: codes (V, T, D) bfloat16 with scale None, or int8 with scale (V, T) float32.
+// smin_score_pairs with smin_pair_assemble_compact where it has smin_pair_assemble: the bits of smin_score_pairs on the decoded bank.
+Scores smin_score_pairs_compact(const Tensor& codes, const std::optional<Tensor>& scale, const Tensor& fw, const Tensor& fs, const Tensor& video_mask,
+                                const Tensor& query_mask_in, const Tensor& length_mask, const Tensor& moment_mask, const Tensor& video_index, const Tensor& query_index,
+                                at::TensorList prm, int64_t T, int64_t L, int64_t C, int64_t num_smi_layers, int64_t max_query_length, int64_t lstm_hidden_size,
+                                bool overlap_boundary, bool overlap_prep, bool param_prep_kernel, bool bf16_operand_storage, std::optional<int64_t> known_cell_count)
+{
+    const int storage = scale ? SMIN_BANK_INT8 : SMIN_BANK_BF16;
+    return score_pairs_of("smin_score_pairs_compact", codes, scale, storage, fw, fs, video_mask, query_mask_in, length_mask, moment_mask, video_index, query_index, prm,
+                          T, L, C, num_smi_layers, max_query_length, lstm_hidden_size, flag_word(overlap_boundary, overlap_prep, param_prep_kernel, bf16_operand_storage),
+                          known_cell_count);
 }
 
 // moments.corpus_span_topk (SMIN.search_windows' last stage): smin_corpus_span_topk over smin_merge_window_moments'
@@ -1731,6 +1766,11 @@ TORCH_LIBRARY(smin_hip, m)
     m.def("smin_score_pairs(Tensor fv, Tensor fw, Tensor fs, Tensor video_mask, Tensor query_mask, Tensor length_mask, Tensor moment_mask, Tensor video_index, "
           "Tensor query_index, Tensor[] params, int T, int L, int C, int num_smi_layers, int max_query_length, int lstm_hidden_size, *, bool overlap_boundary, "
           "bool overlap_prep, bool param_prep_kernel, bool bf16_operand_storage, int? known_cell_count) -> (Tensor, Tensor, Tensor, Tensor)", &smin_score_pairs);
+    // the same over a compact video bank: bf16 codes, or int8 codes and the frames' scales
+    m.def("smin_score_pairs_compact(Tensor codes, Tensor? scale, Tensor fw, Tensor fs, Tensor video_mask, Tensor query_mask, Tensor length_mask, Tensor moment_mask, "
+          "Tensor video_index, Tensor query_index, Tensor[] params, int T, int L, int C, int num_smi_layers, int max_query_length, int lstm_hidden_size, *, "
+          "bool overlap_boundary, bool overlap_prep, bool param_prep_kernel, bool bf16_operand_storage, int? known_cell_count) -> (Tensor, Tensor, Tensor, Tensor)",
+          &smin_score_pairs_compact);
     // SMIN.search_windows' ranking across videos: span-valued moments of (query, video) groups into one list per query
     m.def("smin_corpus_span_topk(Tensor span, Tensor score, Tensor window, Tensor cell, Tensor count, Tensor group_video, Tensor group_ptr, int k) -> "
           "(Tensor video, Tensor span, Tensor score, Tensor window, Tensor cell, Tensor count)", &corpus_span_topk_op);

@@ -861,6 +861,99 @@ def reweight_moments_torch(score, count, pair_rank, weight, max_videos=None):
     return score * weight.to(score.dtype).unsqueeze(1), torch.where(keep, count, torch.zeros_like(count))
 
 
+# ---------------------------------------------------------------- compact video banks
+BANK_STORAGES = {"fp32": 0, "bf16": 1, "int8": 2}       # include/smin_hip.h SMIN_BANK_BF16 / SMIN_BANK_INT8 (0: the fp32 bank, no code)
+_CODE_DTYPES = {torch.float32: "fp32", torch.bfloat16: "bf16", torch.int8: "int8"}
+
+
+def require_storage(what, storage):
+    if storage not in BANK_STORAGES:
+        raise ValueError(f"{what}: storage must be one of {sorted(BANK_STORAGES)} (got {storage!r})")
+    return storage
+
+
+def bank_storage(what, codes, scale=None):
+    """The storage a bank's ``fv`` is held in, from its dtype -- ``"fp32"`` (float32), ``"bf16"`` (bfloat16, no scale) or ``"int8"`` (int8
+    with ``scale``, float32, one value per row of D codes); ValueError for anything else."""
+    storage = _CODE_DTYPES.get(codes.dtype)
+    if storage is None:
+        raise ValueError(f"{what}: a bank holds float32 values, bfloat16 codes or int8 codes (got {codes.dtype})")
+    if (storage == "int8") != (scale is not None):
+        raise ValueError(f"{what}: int8 codes come with their rows' scales, {storage} with none")
+    if scale is not None and (scale.dtype != torch.float32 or tuple(scale.shape) != tuple(codes.shape[:-1])):
+        raise ValueError(f"{what}: scale must be float32 {tuple(codes.shape[:-1])}, one value per row of codes (got {scale.dtype} {tuple(scale.shape)})")
+    return storage
+
+
+def _encode_check(what, fv, storage):
+    require_storage(what, storage)
+    if storage == "fp32":
+        raise ValueError(f"{what}: storage must be 'bf16' or 'int8' (an fp32 bank has no code)")
+    if fv.dim() < 2 or fv.dtype != torch.float32 or fv.shape[-1] < 4 or fv.shape[-1] % 4 != 0 or fv.numel() < 1:
+        raise ValueError(f"{what}: fv must be float32 (..., D) with D >= 4, D % 4 == 0 and at least one row (got {fv.dtype} {tuple(fv.shape)})")
+
+
+def bank_encode_torch(fv, storage):
+    """``bank_encode`` as plain torch ops on any device: the tests' restatement of the code (include/smin_hip.h, SMIN_BANK_*), nothing
+    routes here.  ``"bf16"``: round to nearest even on the bit pattern, ``(u + 0x7fff + ((u >> 16) & 1)) >> 16``, a NaN -> 0x7fc0.
+    ``"int8"``, per row of D values, in float32 ops: ``amax = max |x|``, ``scale = amax / 127`` and ``q = clamp(round_half_even(x /
+    scale), -127, 127)``; a zero row gives scale 0 and a row with a NaN or an infinity scale NaN, codes 0 in both cases."""
+    _encode_check("bank_encode_torch", fv, storage)
+    x = fv.detach()
+    if storage == "bf16":
+        u = x.contiguous().view(torch.int32).to(torch.int64) & 0xffffffff
+        r = (u + 0x7fff + ((u >> 16) & 1)) >> 16
+        r = torch.where((u & 0x7fffffff) > 0x7f800000, torch.full_like(r, 0x7fc0), r)
+        r = torch.where(r >= 0x8000, r - 0x10000, r).to(torch.int16)               # the 16 bits as a signed word
+        return r.view(torch.bfloat16), None
+    finite = torch.isfinite(x).all(dim=-1)
+    amax = torch.where(torch.isfinite(x), x.abs(), torch.zeros_like(x)).amax(dim=-1)
+    scale = torch.where(finite, amax / 127.0, torch.full_like(amax, float("nan")))
+    live = (finite & (scale > 0)).unsqueeze(-1)
+    q = torch.round(x / torch.where(live, scale.unsqueeze(-1), torch.ones_like(x))).clamp(-127.0, 127.0)
+    return torch.where(live, q, torch.zeros_like(q)).to(torch.int8), scale
+
+
+def bank_decode_torch(codes, scale=None):
+    """``bank_decode`` as plain torch ops on any device: ``bits << 16`` for bfloat16 codes, ``float(q) * scale`` (one float32
+    multiplication) for int8 codes.  The tests' restatement, nothing routes here."""
+    if bank_storage("bank_decode_torch", codes, scale) == "int8":
+        return codes.to(torch.float32) * scale.unsqueeze(-1)
+    return codes.to(torch.float32)
+
+
+def bank_encode(fv, storage):
+    """``fv (..., D)`` float32 as a compact code (include/smin_hip.h, smin_bank_encode; csrc/bank_codec.hip): ``(codes, scale)`` with
+    ``codes (..., D)`` torch.bfloat16 and ``scale`` None for ``storage="bf16"``, ``codes`` torch.int8 and ``scale (...)`` float32, one per
+    row of D values, for ``"int8"``.  One launch, one wave per row; HIP tensors only; no host synchronisation."""
+    _require_hip(fv, "bank_encode")
+    _encode_check("bank_encode", fv, storage)
+    x = fv.detach().contiguous()
+    D, R = x.shape[-1], x.numel() // x.shape[-1]
+    codes = torch.empty(x.shape, dtype=torch.bfloat16 if storage == "bf16" else torch.int8, device=x.device)
+    scale = torch.empty(x.shape[:-1], dtype=torch.float32, device=x.device) if storage == "int8" else None
+    with torch.cuda.device(x.device):
+        call("smin_bank_encode", stream(), ptr(x), R, D, BANK_STORAGES[storage], ptr(codes), ptr(scale))
+    return codes, scale
+
+
+def bank_decode(codes, scale=None):
+    """The decoded values of a compact code, float32 ``(..., D)`` (include/smin_hip.h, smin_bank_decode): what every kernel over a
+    compact bank computes with.  HIP tensors only; one launch; no host synchronisation."""
+    _require_hip(codes, "bank_decode")
+    storage = bank_storage("bank_decode", codes, scale)
+    if storage == "fp32":
+        raise ValueError("bank_decode: float32 values are no code")
+    if codes.dim() < 2 or codes.shape[-1] < 4 or codes.shape[-1] % 4 != 0 or codes.numel() < 1:
+        raise ValueError(f"bank_decode: codes must be (..., D) with D >= 4, D % 4 == 0 and at least one row (got {tuple(codes.shape)})")
+    c = codes.detach().contiguous()
+    sc = None if scale is None else scale.detach().contiguous()
+    out = torch.empty(c.shape, dtype=torch.float32, device=c.device)
+    with torch.cuda.device(c.device):
+        call("smin_bank_decode", stream(), ptr(c), ptr(sc), c.numel() // c.shape[-1], c.shape[-1], BANK_STORAGES[storage], ptr(out))
+    return out
+
+
 # ---------------------------------------------------------------- first-stage video score from the banks alone (INTEGRATION.md 3v)
 PREFILTER_MAX_L, PREFILTER_MAX_T, PREFILTER_MAX_Q = 64, 2048, 65535        # csrc/prefilter.hip
 PREFILTER_WS_CAP = 256 << 20        # bytes of workspace per call of smin_prefilter_scores: the videos are tiled to stay under it
@@ -883,7 +976,7 @@ def _prefilter_check(what, fv, fs, w, b, length_mask, moment_mask, T, L, C, tau)
     return Q, V, D, _temperature(what, tau)
 
 
-def prefilter_scores(fv, fs, w, b, length_mask, moment_mask, T, L, C, tau=0.1, maps=False):
+def prefilter_scores(fv, fs, w, b, length_mask, moment_mask, T, L, C, tau=0.1, maps=False, fv_scale=None):
     """The first-stage score of every (query, video) of a video bank's ``fv (V, T, D)`` and a query bank's ``fs (Q, D)``
     (include/smin_hip.h, smin_prefilter_scores): the model with zero SMI layers -- the heads ``w (3, D)`` / ``b (3,)``, in the order
     (pm, ps, pe), on ProposalGeneration's output --, pooled as ``pair_pool`` pools the full model's maps, at temperature ``tau``.  One
@@ -891,11 +984,16 @@ def prefilter_scores(fv, fs, w, b, length_mask, moment_mask, T, L, C, tau=0.1, m
 
     Returns ``(score (Q, V), pool (Q, V, 2), cells (Q, V))`` fp32; with ``maps=True`` also ``pm0 (Q, V, L, L)``, ``ps0`` and ``pe0 (Q, V,
     L)``.  The videos are processed in tiles whose workspace stays under PREFILTER_WS_CAP; a tile changes no bits, every (q, v) is
-    computed alone.  HIP tensors only; no host synchronisation."""
+    computed alone.  A compact bank passes its codes as ``fv`` (torch.bfloat16, or torch.int8 with ``fv_scale (V,
+    T)``): smin_prefilter_scores_compact decodes inside the contraction's loader -- the bits of the decoded bank, which is never
+    formed.  HIP tensors only; no host synchronisation."""
     _require_hip(fv, "prefilter_scores")
     Q, V, D, tau = _prefilter_check("prefilter_scores", fv, fs, w, b, length_mask, moment_mask, T, L, C, tau)
     dev = fv.device
-    fv_, fs_, w_, b_ = (x.detach().float().contiguous() for x in (fv, fs, w, b))
+    storage = bank_storage("prefilter_scores", fv, fv_scale) if fv.dtype in (torch.bfloat16, torch.int8) or fv_scale is not None else "fp32"
+    fs_, w_, b_ = (x.detach().float().contiguous() for x in (fs, w, b))
+    fv_ = fv.detach().contiguous() if storage != "fp32" else fv.detach().float().contiguous()
+    sc_ = None if fv_scale is None else fv_scale.detach().contiguous()
     lm_, mm_ = byte_mask(length_mask), byte_mask(moment_mask)
     lib = load()
     per_video = max(int(lib.smin_prefilter_ws_bytes(Q, 2, T, D)) - int(lib.smin_prefilter_ws_bytes(Q, 1, T, D)), 1)
@@ -908,8 +1006,9 @@ def prefilter_scores(fv, fs, w, b, length_mask, moment_mask, T, L, C, tau=0.1, m
             tile = outs if (v0, v1) == (0, V) else [new(Q, v1 - v0, *o.shape[2:]) for o in outs]
             nbytes = int(lib.smin_prefilter_ws_bytes(Q, v1 - v0, T, D))
             ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
-            call("smin_prefilter_scores", stream(), ptr(fv_[v0:v1]), ptr(fs_), ptr(w_), ptr(b_), ptr(lm_[v0:v1]), ptr(mm_[v0:v1]), Q, v1 - v0,
-                 T, L, C, D, tau, *[ptr(o) for o in tile], *([] if maps else [None] * 3), ptr(ws), nbytes)
+            bank = [ptr(fv_[v0:v1])] if storage == "fp32" else [ptr(fv_[v0:v1]), None if sc_ is None else ptr(sc_[v0:v1]), BANK_STORAGES[storage]]
+            call("smin_prefilter_scores" if storage == "fp32" else "smin_prefilter_scores_compact", stream(), *bank, ptr(fs_), ptr(w_), ptr(b_),
+                 ptr(lm_[v0:v1]), ptr(mm_[v0:v1]), Q, v1 - v0, T, L, C, D, tau, *[ptr(o) for o in tile], *([] if maps else [None] * 3), ptr(ws), nbytes)
             if tile is not outs:
                 for o, part in zip(outs, tile):
                     o[:, v0:v1] = part
@@ -1103,21 +1202,31 @@ def _admit_check(what, copy_src, shard, out):
     return R, Vs, T, L, D
 
 
-def survivors_admit(copy_src, shard, out):
+def survivors_admit(copy_src, shard, out, scale=None, out_scale=None):
     """The payload of a fold (include/smin_hip.h, smin_survivors_admit): for every row r of ``copy_src`` (any shape, R elements, row ``q *
     M + slot``) with ``copy_src[r] >= 0``, row r of ``out`` -- the survivors' ``(fv (R, T, D), video_mask (R, T[, 1]), length_mask (R,
     L), moment_mask (R, L, L))``, updated IN PLACE -- becomes video ``copy_src[r]`` of ``shard``, the same four tensors of the
-    shard's bank (float32 fv, one byte per mask entry), bit for bit.  Rows with -1 are not touched.  HIP tensors only; one launch; no
-    host synchronisation."""
+    shard's bank (float32 fv, one byte per mask entry), bit for bit.  Rows with -1 are not touched.  A compact bank (INTEGRATION.md
+    3y) passes its codes as ``fv`` and, for int8 codes, ``scale (Vs, T)`` and the survivors' ``out_scale (R, T)``, which is copied
+    with the rows (smin_survivors_admit_compact).  HIP tensors only; one launch; no host synchronisation."""
     _require_hip(copy_src, "survivors_admit")
     R, Vs, T, L, D = _admit_check("survivors_admit", copy_src, shard, out)
-    if shard[0].dtype != torch.float32 or any(m.dtype not in (torch.bool, torch.uint8) for m in shard[1:]):
-        raise ValueError("survivors_admit: float32 fv and bool / uint8 masks (the banks' own)")
+    storage = bank_storage("survivors_admit", shard[0], scale)
+    if any(m.dtype not in (torch.bool, torch.uint8) for m in shard[1:]):
+        raise ValueError("survivors_admit: float32 fv (or a compact bank's codes) and bool / uint8 masks (the banks' own)")
+    if (scale is None) != (out_scale is None) or (scale is not None and (tuple(scale.shape) != (Vs, T) or tuple(out_scale.shape) != (R, T) or
+                                                                         out_scale.dtype != torch.float32 or not out_scale.is_contiguous())):
+        raise ValueError(f"survivors_admit: int8 codes come with scale (Vs, T) = {(Vs, T)} and a contiguous float32 out_scale (R, T) = {(R, T)}")
     if any(not t.is_contiguous() for t in out) or copy_src.dtype != torch.int32 or not copy_src.is_contiguous():
         raise ValueError("survivors_admit: the survivors are updated in place: contiguous tensors, and a contiguous int32 copy_src")
     src = [t.detach().contiguous() for t in shard]
     with torch.cuda.device(copy_src.device):
-        call("smin_survivors_admit", stream(), ptr(copy_src), *[ptr(t) for t in src], R, Vs, T, L, D, *[ptr(t) for t in out])
+        if storage == "fp32":
+            call("smin_survivors_admit", stream(), ptr(copy_src), *[ptr(t) for t in src], R, Vs, T, L, D, *[ptr(t) for t in out])
+        else:
+            sc = None if scale is None else scale.detach().contiguous()
+            call("smin_survivors_admit_compact", stream(), ptr(copy_src), ptr(src[0]), ptr(sc), BANK_STORAGES[storage], *[ptr(t) for t in src[1:]],
+                 R, Vs, T, L, D, ptr(out[0]), ptr(out_scale), *[ptr(t) for t in out[1:]])
     return out
 
 

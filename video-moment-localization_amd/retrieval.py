@@ -6,6 +6,8 @@ of videos of any length: ``encode_windows`` -> ``search_windows``), and the trai
 of ``score_pairs``, ``forward_pairs`` over (video, query) pairs that share their
 encoders: host code around the library's kernels and the model's own ``score`` / ``forward``, which ``modules.SMIN`` inherits
 through the stateless mixin ``_Retrieval``."""
+import copy
+
 import numpy as np
 import torch
 
@@ -13,7 +15,7 @@ from . import _lib
 from ._host import _AttnMaps, byte_mask, host_array, known_cells, query_mask_rows, require_hip_tensors, require_ints
 from .feeder import build_masks_hip, cell_count
 from .functional import attn_maps_gather
-from .moments import (MAX_K, PREFILTER_FOLD_MAX_M, prefilter_fold, prefilter_gt_rank, survivors_admit, _pair_pool_into, _temperature, _top_moments_into, _video_weight, corpus_span_topk, corpus_span_topk_torch, corpus_topk,
+from .moments import (MAX_K, PREFILTER_FOLD_MAX_M, bank_decode, bank_encode, bank_storage, require_storage, prefilter_fold, prefilter_gt_rank, survivors_admit, _pair_pool_into, _temperature, _top_moments_into, _video_weight, corpus_span_topk, corpus_span_topk_torch, corpus_topk,
                       corpus_topk_torch, group_pool, merge_window_moments, merge_window_moments_torch, mine_pairs, prefilter_maps, prefilter_scores, prefilter_select,
                       rank_videos, reweight_moments,
                       reweight_moments_torch, search_times, top_moments, top_moments_torch, window_times)
@@ -43,11 +45,56 @@ class VideoBank:
     itself (not a copy), kept for the configurations that score through SMIN.score.
 
     A bank is detached and is a snapshot of the parameters at the time of the call: a parameter update (an optimizer step,
-    load_state_dict) makes it stale -- encode again.  ``fv`` is None when the call would not take the one-node path (SMIN._plan)."""
+    load_state_dict) makes it stale -- encode again.  ``fv`` is None when the call would not take the one-node path (SMIN._plan).
 
-    def __init__(self, fv, video_features, video_mask, length_mask, moment_mask, cell_counts):
+    Compact storage: ``storage`` is ``"fp32"`` (the default), ``"bf16"`` or ``"int8"``.  A compact bank's ``fv`` holds
+    the codes themselves -- torch.bfloat16, or torch.int8 with ``fv_scale (V, T)`` float32, one scale per frame (None otherwise) --, so
+    a path that was not told about codes fails on a dtype check instead of reading them as floats.  ``compact(storage)`` encodes an
+    fp32 bank (moments.bank_encode), ``dequantized()`` gives the fp32 bank of the decoded values (moments.bank_decode); both keep
+    every other field.  Scoring, search and the first stage read the codes directly and give the bits of ``dequantized()``.
+    ``nbytes``: the bytes of ``fv`` and ``fv_scale``."""
+
+    def __init__(self, fv, video_features, video_mask, length_mask, moment_mask, cell_counts, fv_scale=None):
         self.fv, self.video_features, self.video_mask, self.length_mask, self.moment_mask = fv, video_features, video_mask, length_mask, moment_mask
         self.cell_counts = tuple(int(c) for c in cell_counts)
+        self.fv_scale = fv_scale
+        if fv is not None:
+            bank_storage("VideoBank", fv, fv_scale)
+
+    @property
+    def storage(self):
+        return "fp32" if self.fv is None else bank_storage("VideoBank", self.fv, self.fv_scale)
+
+    @property
+    def nbytes(self):
+        """The bytes the bank's ``fv`` (codes) and ``fv_scale`` hold; 0 without ``fv``."""
+        return sum(t.numel() * t.element_size() for t in (self.fv, self.fv_scale) if t is not None)
+
+    def _with_fv(self, fv, fv_scale):
+        bank = copy.copy(self)                                    # every other field, a WindowBank's plan included
+        bank.fv, bank.fv_scale = fv, fv_scale
+        return bank
+
+    def compact(self, storage):
+        """The bank in ``storage``: the bank itself where it is held so already, else an fp32 bank encoded by moments.bank_encode (one
+        launch).  ValueError for an unknown storage, a bank without ``fv`` (encoded off the one-node path) or a compact bank asked for
+        another code (go through ``dequantized()``: a second rounding is a decision)."""
+        require_storage("compact", storage)
+        if self.fv is None:
+            if storage == "fp32":
+                return self
+            raise ValueError("compact: a compact storage holds fv, which a bank encoded off the one-node path (SMIN._plan) does not have")
+        if storage == self.storage:
+            return self
+        if self.storage != "fp32":
+            raise ValueError(f"compact: the bank is held as {self.storage}; dequantized() gives the fp32 bank to encode again")
+        return self._with_fv(*bank_encode(self.fv, storage))
+
+    def dequantized(self):
+        """An fp32 bank of the decoded values (moments.bank_decode); an fp32 bank is returned as it is."""
+        if self.storage == "fp32":
+            return self
+        return self._with_fv(bank_decode(self.fv, self.fv_scale), None)
 
     def __len__(self):
         return (self.video_mask if self.video_features is None else self.video_features).shape[0]
@@ -81,8 +128,8 @@ class WindowBank(VideoBank):
     parameters, as every bank."""
 
     def __init__(self, fv, video_features, video_mask, length_mask, moment_mask, cell_counts, starts, lens, video_ptr, n_rows, start, len,
-                 video_ptr_d, window, stride, mode="pick", plan_features=None):
-        super().__init__(fv, video_features, video_mask, length_mask, moment_mask, cell_counts)
+                 video_ptr_d, window, stride, mode="pick", plan_features=None, fv_scale=None):
+        super().__init__(fv, video_features, video_mask, length_mask, moment_mask, cell_counts, fv_scale)
         self.starts, self.lens, self.video_ptr, self.n_rows = (host_array(x) for x in (starts, lens, video_ptr, n_rows))     # host values
         self.start, self.len, self.video_ptr_d = start, len, video_ptr_d                                                    # their device copies
         self.window, self.stride, self.mode = int(window), int(stride), mode
@@ -108,7 +155,8 @@ class SurvivorBank(VideoBank):
     ``cell_count`` is every video's valid-cell count where all the shards' ``cell_counts`` were one value, else None.
     ``video_features`` is None and ``plan_features`` an empty ``(0, T, Din)`` tensor, as WindowBank gives on the one-node path.
 
-    Memory: ``Q * M * (4 T D + T + L + L * L)`` bytes of rows, fixed by (Q, M), plus ``4 * Q * V`` bytes of kept scores (and V flag
+    Memory: ``Q * M * (T * D * esize [+ 4 T] + T + L + L * L)`` bytes of rows (esize 4, 2 or 1 by the storage, which is the first
+    shard's; the 4 T are an int8 bank's scales), fixed by (Q, M), plus ``4 * Q * V`` bytes of kept scores (and V flag
     bytes) -- the only part that grows with the corpus.  A snapshot of the parameters, as every bank."""
 
     def __init__(self, Q, M, tau, device, plan_features):
@@ -415,11 +463,19 @@ class _Retrieval:
         """Whether pairs of these inputs score on the one-node path from banks (as score(): _plan == "node" and no keep_attention)."""
         return not self.keep_attention and self._plan(video_features, query_features) == "node"
 
-    def encode_videos(self, video_features, video_mask, length_mask, moment_mask, cell_counts=None):
+    def encode_videos(self, video_features, video_mask, length_mask, moment_mask, cell_counts=None, storage="fp32", max_batch=None):
         """A VideoBank of V videos: the projection with position embedding and mask runs once per video (smin_hip::smin_encode_videos),
         not once per (video, query) pair.  ``video_features (V, T, Din)`` and the three masks as forward takes them.  One host read
         (the videos' valid-cell counts), none with ``cell_counts``, the V counts as host ints (feeder.cell_count); under
-        torch.no_grad().  The bank is stale after a parameter update."""
+        torch.no_grad().  The bank is stale after a parameter update.
+
+        ``storage``: ``"fp32"`` (default), ``"bf16"`` or ``"int8"`` -- the bank is held compact (VideoBank), with the
+        codes of ``encode_videos(...).compact(storage)``.  ``max_batch``: the videos are encoded (and encoded to codes) at most that
+        many at a time, so with a compact storage the fp32 ``fv`` of the whole corpus never exists.  Off the one-node path (``fv`` is
+        None) a compact storage raises ValueError."""
+        require_storage("encode_videos", storage)
+        if max_batch is not None:
+            require_ints("encode_videos", ("max_batch", max_batch, 1, 2 ** 31 - 1))
         require_hip_tensors("encode_videos", dict(video_features=video_features, video_mask=video_mask, length_mask=length_mask, moment_mask=moment_mask))
         V = video_features.shape[0]
         if video_features.dim() != 3 or V < 1 or video_mask.shape[0] != V or tuple(length_mask.shape) != (V, self.L) or tuple(moment_mask.shape) != (V, self.L, self.L):
@@ -428,16 +484,32 @@ class _Retrieval:
         with torch.no_grad(), torch.cuda.device(video_features.device):
             vf = video_features.detach()
             masks = [byte_mask(t) for t in (video_mask, length_mask, moment_mask)]
-            fv = None
+            fv = fv_scale = None
             if self.fused_core and self.backbone.videoencoder.fused(vf) and vf.shape[1] == self.T:
-                fv = _lib.load_torch().smin_encode_videos(vf, masks[0], self._native_params()[:3])
+                ops, prm, step = _lib.load_torch(), self._native_params()[:3], V if max_batch is None else int(max_batch)
+                for c0 in range(0, V, step):
+                    c1 = min(c0 + step, V)
+                    part = ops.smin_encode_videos(vf[c0:c1], masks[0][c0:c1], prm)
+                    part, part_scale = (part, None) if storage == "fp32" else bank_encode(part, storage)
+                    if (c0, c1) == (0, V):
+                        fv, fv_scale = part, part_scale
+                        break
+                    if fv is None:
+                        fv = torch.empty((V,) + tuple(part.shape[1:]), dtype=part.dtype, device=part.device)
+                        fv_scale = None if part_scale is None else torch.empty((V, part.shape[1]), dtype=torch.float32, device=part.device)
+                    fv[c0:c1] = part
+                    if part_scale is not None:
+                        fv_scale[c0:c1] = part_scale
+            elif storage != "fp32":
+                raise ValueError("encode_videos: a compact storage holds fv, which this module or these inputs do not form (off the one-node path, "
+                                 "SMIN._plan); encode with storage='fp32'")
             if cell_counts is None:
                 counts = masks[2].reshape(V, -1).ne(0).sum(dim=1).tolist()         # the bank's only host read
             else:
                 counts = host_array(cell_counts)
                 if counts.shape[0] != V:
                     raise ValueError(f"encode_videos: cell_counts must hold the V = {V} videos' counts (got {counts.shape[0]})")
-        return VideoBank(fv, vf, masks[0], masks[1], masks[2], counts)
+        return VideoBank(fv, vf, masks[0], masks[1], masks[2], counts, fv_scale)
 
     def encode_queries(self, query_features, query_mask):
         """A QueryBank of Q queries: the two BiLSTM layers and the sentence feature run once per query
@@ -481,11 +553,18 @@ class _Retrieval:
                 # as score(): configurations off the one-node path (and keep_attention) run the forward, here on expanded pairs
                 if videos.video_features is None:
                     raise ValueError("score_pairs: the window bank was encoded on the one-node path and keeps no features to expand; encode it again")
+                if videos.storage != "fp32":
+                    raise ValueError(f"score_pairs: a bank held as {videos.storage} is scored on the one-node path only (SMIN._plan; the forward "
+                                     "reads the videos' own features, not the codes)")
                 qm = queries.query_mask[:, :queries.query_features.shape[1]]
                 return self.score(videos.video_features.index_select(0, vi_d), videos.video_mask.index_select(0, vi_d),
                                   queries.query_features.index_select(0, qi_d), qm.index_select(0, qi_d),
                                   videos.length_mask.index_select(0, vi_d), videos.moment_mask.index_select(0, vi_d))
             _require_node_banks(videos, queries)
+            if videos.storage != "fp32":
+                return _lib.load_torch().smin_score_pairs_compact(
+                    videos.fv, videos.fv_scale, queries.fw, queries.fs, videos.video_mask, queries.query_mask, videos.length_mask, videos.moment_mask,
+                    vi_d, qi_d, *self._core_args(), **self._score_options())
             return _lib.load_torch().smin_score_pairs(
                 videos.fv, queries.fw, queries.fs, videos.video_mask, queries.query_mask, videos.length_mask, videos.moment_mask, vi_d, qi_d,
                 *self._core_args(), **self._score_options())
@@ -722,7 +801,8 @@ class _Retrieval:
             raise ValueError(f"{what}: {Q} queries over {max(V, W)} videos / windows exceed the int32 pair lists")
         with torch.no_grad(), torch.cuda.device(dev):
             w, b = self._first_stage_heads(videos.fv.shape[2])
-            score, pool, cells = prefilter_scores(videos.fv, queries.fs, w, b, videos.length_mask, videos.moment_mask, self.T, self.L, self.C, tau)
+            score, pool, cells = prefilter_scores(videos.fv, queries.fs, w, b, videos.length_mask, videos.moment_mask, self.T, self.L, self.C, tau,
+                                                  fv_scale=videos.fv_scale)
             if windowed:
                 first = torch.arange(Q, device=dev).unsqueeze(1) * W + videos.video_ptr_d[:-1].unsqueeze(0)           # group q * V + v begins here
                 group_ptr = torch.cat([first.reshape(-1), first.new_full((1,), Q * W)])
@@ -828,7 +908,8 @@ class _Retrieval:
         seen, in the order of search(prefilter=M)'s cut -- and ``survivors_admit``, which copies the admitted videos' fv rows and masks
         into the survivors' rows; the shard's bank may then be dropped.  The shard's videos get the global ids ``survivors.seen ..``.
         ValueError for a WindowBank (or a SurvivorBank), a bank encoded off the one-node path (score_pairs' message), another number of
-        queries than the survivors were made for or a bank of other shapes than the earlier shards'.  Under torch.no_grad(); reads
+        queries than the survivors were made for or a bank of other shapes or another storage than the earlier shards' (the survivors
+        take the first shard's storage: compact shards are kept as codes).  Under torch.no_grad(); reads
         nothing back.  Returns ``survivors``."""
         what = "fold_survivors"
         if not isinstance(survivors, SurvivorBank):
@@ -840,23 +921,28 @@ class _Retrieval:
         Q, V, M = len(queries), len(videos), survivors.M
         if Q != survivors.Q:
             raise ValueError(f"{what}: the survivors were made for Q = {survivors.Q} queries (got {Q})")
-        require_hip_tensors(what, dict(videos=videos.video_mask, queries=queries.query_features), must="hold HIP tensors")
         _require_node_banks(videos, queries)
-        if survivors.seen + V > 0x7fff0000 // max(Q, 1):
-            raise ValueError(f"{what}: {Q} queries over {survivors.seen + V} videos exceed the int32 pair lists")
-        dev, D = videos.device, videos.fv.shape[2]
         shard = (videos.fv, videos.video_mask, videos.length_mask, videos.moment_mask)
         if survivors.fv is not None and any(a.shape[1:] != b.shape[1:] or a.dtype != b.dtype
                                              for a, b in zip(shard, (survivors.fv, survivors.video_mask, survivors.length_mask, survivors.moment_mask))):
-            raise ValueError(f"{what}: the shard's bank differs from the earlier shards' in a shape or a mask's dtype")
+            raise ValueError(f"{what}: the shard's bank differs from the earlier shards' in a shape, a mask's dtype or the storage "
+                             f"({videos.storage} against {survivors.storage})")
+        require_hip_tensors(what, dict(videos=videos.video_mask, queries=queries.query_features), must="hold HIP tensors")
+        if survivors.seen + V > 0x7fff0000 // max(Q, 1):
+            raise ValueError(f"{what}: {Q} queries over {survivors.seen + V} videos exceed the int32 pair lists")
+        dev, D = videos.device, videos.fv.shape[2]
         with torch.no_grad(), torch.cuda.device(dev):
             if survivors.fv is None:
                 survivors.fv, survivors.video_mask, survivors.length_mask, survivors.moment_mask = (
                     torch.zeros((Q * M,) + tuple(t.shape[1:]), dtype=t.dtype, device=dev) for t in shard)
+                if videos.fv_scale is not None:                  # the survivors take the first shard's storage
+                    survivors.fv_scale = torch.zeros((Q * M, videos.fv.shape[1]), dtype=torch.float32, device=dev)
             w, b = self._first_stage_heads(D)
-            score, _, cells = prefilter_scores(videos.fv, queries.fs, w, b, videos.length_mask, videos.moment_mask, self.T, self.L, self.C, survivors.tau)
+            score, _, cells = prefilter_scores(videos.fv, queries.fs, w, b, videos.length_mask, videos.moment_mask, self.T, self.L, self.C, survivors.tau,
+                                               fv_scale=videos.fv_scale)
             prefilter_fold(survivors.slot_score, survivors.slot_cells, survivors.slot_video, score, cells, survivors.seen, copy_src=survivors.copy_src)
-            survivors_admit(survivors.copy_src, shard, (survivors.fv, survivors.video_mask, survivors.length_mask, survivors.moment_mask))
+            survivors_admit(survivors.copy_src, shard, (survivors.fv, survivors.video_mask, survivors.length_mask, survivors.moment_mask),
+                            scale=videos.fv_scale, out_scale=survivors.fv_scale)
             survivors.shard_scores.append(score)
             survivors.shard_candidates.append(cells[0] > 0)          # (a video's valid cells do not depend on the query)
         survivors.seen += V
@@ -935,15 +1021,18 @@ class _Retrieval:
         return dict(video=vr["video"], score=vr["score"], count=vr["count"], pair_score=score, pair_rank=vr["pair_rank"], gt_rank=vr["gt_rank"])
 
     # ---------------------------------------------------------------- corpus search over long videos
-    def encode_windows(self, raw, lengths, window=None, stride=None, mode="pick", max_batch=64):
+    def encode_windows(self, raw, lengths, window=None, stride=None, mode="pick", max_batch=64, storage="fp32"):
         """A WindowBank of the W windows of V videos of any length: sampling.window_plan's overlapping windows of ``window`` raw rows
         (default T: one row per clip) every ``stride`` rows (default window // 2), each resampled to T clips and encoded once --
         chunk by chunk, at most ``max_batch`` windows each: sample_windows, build_masks_hip, encode_videos (smin_hip::smin_encode_videos).
         ``raw (R, Din)`` HIP float32 tensor of the videos' rows back to back and ``lengths`` their V row counts (host), as
         localize_windows takes them.  A video of 0 rows has no window.  The windows' valid-cell counts come from the host plan
         (feeder.cell_count of min(len, T)) and the plan travels in one pinned asynchronous copy: nothing is read back.  The sampled
-        features are dropped chunk by chunk on the one-node path (WindowBank).  Under torch.no_grad(); stale after a parameter update."""
+        features are dropped chunk by chunk on the one-node path (WindowBank).  ``storage``: encode_videos' -- each chunk's windows are
+        encoded to codes as they come, so the fp32 ``fv`` of all windows never exists.  Under torch.no_grad(); stale after a parameter
+        update."""
         T, L = self.T, self.L
+        require_storage("encode_windows", storage)
         window = T if window is None else window
         stride = max(int(window) // 2, 1) if stride is None else stride
         require_ints("encode_windows", ("window", window, 1, MAX_ROWS), ("stride", stride, 1, MAX_ROWS), ("max_batch", max_batch, 1, 65535))
@@ -971,19 +1060,23 @@ class _Retrieval:
             lmask = torch.empty((W, L), dtype=torch.bool, device=dev)
             mmask = torch.empty((W, L, L), dtype=torch.bool, device=dev)
             feats = torch.empty((W, T, Din), dtype=torch.float32, device=dev) if keep else None
-            fv = None
+            fv = fv_scale = None
             for c0 in range(0, W, max_batch):
                 c1 = min(c0 + max_batch, W)
                 vf, nfeats = sample_windows(raw, rb_d[c0:c1], ln_d[c0:c1], T, mode=mode)
                 m = build_masks_hip(nfeats, T, L)
-                part = self.encode_videos(vf, m["video_mask"], m["length_mask"], m["moment_mask"], cell_counts=cells[c0:c1])
+                part = self.encode_videos(vf, m["video_mask"], m["length_mask"], m["moment_mask"], cell_counts=cells[c0:c1], storage=storage)
                 vmask[c0:c1], lmask[c0:c1], mmask[c0:c1] = part.video_mask, part.length_mask, part.moment_mask
                 if part.fv is not None:
-                    fv = torch.empty((W,) + tuple(part.fv.shape[1:]), dtype=torch.float32, device=dev) if fv is None else fv
+                    fv = torch.empty((W,) + tuple(part.fv.shape[1:]), dtype=part.fv.dtype, device=dev) if fv is None else fv
                     fv[c0:c1] = part.fv
+                    if part.fv_scale is not None:
+                        fv_scale = torch.empty((W, part.fv.shape[1]), dtype=torch.float32, device=dev) if fv_scale is None else fv_scale
+                        fv_scale[c0:c1] = part.fv_scale
                 if keep:
                     feats[c0:c1] = vf
-        return WindowBank(fv, feats, vmask, lmask, mmask, cells, starts, lens, vptr, n, st_d, ln_d, vp_d, window, stride, mode, plan_features=probe)
+        return WindowBank(fv, feats, vmask, lmask, mmask, cells, starts, lens, vptr, n, st_d, ln_d, vp_d, window, stride, mode, plan_features=probe,
+                          fv_scale=fv_scale)
 
     def _window_search_plan(self, what, windows, queries, pairs, k, k_video, k_window, max_batch, duration):
         """search_windows' checked arguments and its expansion, host arithmetic only: ``(options, plan)`` with ``options`` an _Options
@@ -1079,6 +1172,7 @@ class _Retrieval:
         (G2,)`` with ``max_videos``: moments.reweight_moments_torch on the groups' merged lists in front of the ranking (the tests feed it
         the kernels' ranks and weights of ``search_windows(video_weight=..., max_videos=...)``)."""
         what = "search_windows_torch"
+        windows = windows.dequantized() if isinstance(windows, VideoBank) else windows
         o, p = self._window_search_plan(what, windows, queries, pairs, k, k_video, k_window, max_batch, duration)
         k, k_video, k_window = o.k, o.k_video, o.k_window
         if scorer is None and raw is None:
@@ -1148,6 +1242,7 @@ class _Retrieval:
         score_pairs, to compare the ranking on equal scores).  ``pair_rank`` / ``weight (P,)`` with ``max_videos``:
         moments.reweight_moments_torch on the pairs' lists in front of the ranking (the tests feed it the kernels' ranks and weights of
         ``search(video_weight=..., max_videos=...)``)."""
+        videos = videos.dequantized() if isinstance(videos, VideoBank) else videos
         o, vi, qi, pair_ptr = self._search_plan("search_torch", videos, queries, pairs, k, k_video, max_batch, duration)
         k, k_video, dev, L, P = o.k, o.k_video, videos.device, self.L, vi.shape[0]
         idx, score, count, chunks = _chunk_buffers(P, k_video, max_batch, dev)

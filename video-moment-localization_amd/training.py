@@ -580,12 +580,14 @@ test_model_windows.__test__ = False
 
 
 # ---------------------------------------------------------------- a corpus in shards: the walk and the two folds of lists
-def _encode_shard(model, counted):
+def _encode_shard(model, counted, storage="fp32"):
     """A fold's encode step for a shard of videos: ``encode_videos`` on the shard's four arguments, where ``counted`` with the shard's
-    ``cell_counts`` (None if it has none)."""
+    ``cell_counts`` (None if it has none); ``storage``: the shard's bank is held compact."""
     def encode(shard):
-        counts = {"cell_counts": shard.get("cell_counts")} if counted else {}
-        return model.encode_videos(shard["video_features"], shard["video_mask"], shard["length_mask"], shard["moment_mask"], **counts)
+        options = {"cell_counts": shard.get("cell_counts")} if counted else {}
+        if storage != "fp32":
+            options["storage"] = storage
+        return model.encode_videos(shard["video_features"], shard["video_mask"], shard["length_mask"], shard["moment_mask"], **options)
     return encode
 
 
@@ -930,7 +932,7 @@ test_model_corpus_window_shards_weighted.__test__ = False
 
 # ---------------------------------------------------------------- pruned search over a corpus in shards
 def search_shards_prefiltered(model, video_shards, queries, *, prefilter, k=25, k_video=5, nms_thresh=0.5, max_batch=64, video_weight=None,
-                              max_videos=None, tau=0.1, n_videos=None, gt_video=None):
+                              max_videos=None, tau=0.1, n_videos=None, gt_video=None, storage="fp32"):
     """``model.search(prefilter=M)`` over a corpus that comes in shards: ``video_shards`` as ``search_shards`` takes
     them (a shard may carry ``cell_counts``), ``queries`` a QueryBank.  Per shard: ``encode_videos`` and ``fold_survivors`` -- the
     first-stage score of the shard's videos and the running corpus-wide cut, whose survivors take their rows along --; one shard's
@@ -939,9 +941,10 @@ def search_shards_prefiltered(model, video_shards, queries, *, prefilter, k=25, 
     ``video_weight`` / ``max_videos`` / ``n_videos`` / ``gt_video`` (global ids in shard order) acting as there; ``tau`` is the first
     stage's temperature and the video-level one.  Returns ``(result, duration)`` as ``search_shards``; the result also holds
     ``prefilter_video``, ``prefilter_score`` and ``prefilter_gt_rank``.  Host reads: ``encode_videos``' own per shard without
-    ``cell_counts``; with them, and all of one value, none."""
+    ``cell_counts``; with them, and all of one value, none.  ``storage``: every shard's bank, and so the survivors' rows, are held
+    compact (``"bf16"`` / ``"int8"``): the bits of ``search(prefilter=M)`` on one bank of the decoded values."""
     survivors = model.new_survivors(queries, prefilter, tau)
-    duration, = _walk_shards("search_shards_prefiltered", video_shards, _encode_shard(model, counted=True),
+    duration, = _walk_shards("search_shards_prefiltered", video_shards, _encode_shard(model, counted=True, storage=storage),
                              lambda bank, seen: model.fold_survivors(survivors, bank, queries))
     r = model.search_survivors(survivors, queries, k=k, k_video=k_video, nms_thresh=nms_thresh, max_batch=max_batch, video_weight=video_weight,
                                max_videos=max_videos, n_videos=n_videos, gt_video=gt_video)
