@@ -66,7 +66,9 @@ extern "C" {
  * by the pooled pair score -- smin_pair_pool, smin_group_pool, smin_video_rank and smin_moment_reweight (the score the contrastive loss
  * trains, read at inference: a video ranking, a weight on each video's moments and a cut to the best videos); that weight and cut
  * across shards -- smin_search_merge_weighted and smin_span_search_merge_weighted (shard lists that carry their unweighted scores,
- * merged under the video weights and ranks of all the shards' videos) */
+ * merged under the video weights and ranks of all the shards' videos); a listwise soft-target loss over a pair plan --
+ * smin_pair_distill_fwd and smin_pair_distill_ws_bytes (a query's softmax over its pair scores pulled towards a teacher's, through
+ * smin_pair_rank_bwd) */
 #define SMIN_HIP_ABI_VERSION 2
 
 int smin_abi_version(void);
@@ -1002,6 +1004,43 @@ int smin_pair_rank_fwd(void* stream, const float* pm, const float* ps, const flo
  * Rejection.  A nonzero status before the launch, the outputs untouched, for a size out of range, a NULL pointer or a bad tau. */
 int smin_pair_rank_bwd(void* stream, const float* dloss, const float* stats, const float* coef, const float* pool, const float* pm,
                        const float* ps, const float* pe, const uint8_t* mm, int P, int L, float tau, float* dpm, float* dps, float* dpe);
+
+/* ---- listwise soft-target loss over a pair plan (csrc/pair_rank.hip): each query's softmax over its pair scores
+ * pulled towards the softmax over a teacher's scores of the same pairs.  All arithmetic fp32.
+ *
+ * smin_pair_distill_fwd: three launches (pool, queries, total), no atomics; the first and the third are smin_pair_rank_fwd's kernels.
+ * Inputs.  pm, ps, pe, mm, q_ptr, q_pairs, tau: as smin_pair_rank_fwd (no positive flags are read).  teacher [P] fp32: one score per
+ *   pair, in pair order; it receives no gradient.  gamma: the temperature across a query's videos on the student's side,
+ *   gamma_teacher: on the teacher's.
+ * Pair score.  s_p of smin_pair_rank_fwd, BIT FOR BIT (the same kernel); n_p == 0: s_p = 0, and the pair still takes part.
+ * Query loss.  S_q the query's segment, t_p = teacher[p]:
+ *   xS_p = (s_p - max_{S_q} s) / gamma,          ZS = sum_{S_q} expf(xS),  pS_p = expf(xS_p) / ZS,  lS_p = xS_p - logf(ZS);
+ *   xT_p = (t_p - max_{S_q} t) / gamma_teacher,  ZT, pT_p, lT_p likewise;
+ *   l_q = sum_{S_q} pT_p * (lT_p - lS_p) = KL(teacher || student); no logf takes a probability.
+ *   Both sides run one device function in one expression order: teacher == pair_score with gamma_teacher == gamma gives a loss and
+ *   coefficients of exactly 0.
+ *   A query is counted when its segment lists at least two pairs and every teacher value in it is finite.
+ * Outputs, every element written.
+ *   loss [1] = (sum of l_q over the Nc counted queries) / Nc, exactly 0 when Nc == 0.
+ *   stats [2] = { Nc, agree }: a counted query agrees when the first entry in list order with the highest teacher score is also the
+ *     first entry in list order with the highest pair score.
+ *   pair_score [P] = s_p.
+ *   coef [P]: (pS_p - pT_p) / gamma, the derivative of l_q by s_p, 0 for the pairs of a query that is not counted (and for a pair no
+ *     segment lists);  pool [P][2]: as smin_pair_rank_fwd.
+ * Backward.  smin_pair_rank_bwd as it stands, called with this forward's stats, coef and pool.
+ * Order.  Pool and total: smin_pair_rank_fwd's.  Queries: one wave64 per query, four queries per workgroup; lane l takes entries l,
+ *   l + 64, ... of the segment in ascending order; every total is wave_sum or wave_max of the lanes' partials.
+ * Bounds.  Every value read from q_ptr (into [0, P], ascending) and q_pairs (into [0, P)) is clamped before it forms an address.
+ * Limits.  P, Q >= 1, 1 <= L <= 4096, tau, gamma and gamma_teacher finite and > 0; ws 16-byte aligned; the outputs and ws must not
+ *   overlap the inputs or each other.
+ * Workspace.  ws_bytes >= smin_pair_distill_ws_bytes(P, Q, L), exactly Q * 16; the query returns 0 for a size out of range.
+ * Determinism.  The same bits every run; no host read; no allocation; capturable.
+ * Rejection.  A nonzero status before any launch, the outputs untouched, for a size out of range, a NULL pointer, a tau, gamma or
+ *   gamma_teacher that is not finite and positive, or a workspace that is too small. */
+size_t smin_pair_distill_ws_bytes(int P, int Q, int L);
+int smin_pair_distill_fwd(void* stream, const float* pm, const float* ps, const float* pe, const uint8_t* mm, const int32_t* q_ptr,
+                          const int32_t* q_pairs, const float* teacher, int P, int Q, int L, float tau, float gamma, float gamma_teacher,
+                          float* loss, float* stats, float* pair_score, float* coef, float* pool, void* ws, size_t ws_bytes);
 
 /* ---- video ranking by the pooled pair score (csrc/video_rank.hip): the score smin_pair_rank_fwd contrasts, read
  * at inference.  All arithmetic fp32; no atomics, plain stores; no workspace; no host read; no allocation; capturable.

@@ -22,9 +22,10 @@ from .training import search_shards_weighted, search_window_shards_weighted  # n
 from .training import test_model_corpus_weighted_shards, test_model_corpus_window_shards_weighted  # noqa: F401
 from .training import pair_targets, train_epoch_pairs, train_epoch_mined, pair_rank_loss, pair_rank_loss_torch  # noqa: F401
 from .training import prefilter_rank_loss, train_epoch_prefilter  # noqa: F401
+from .training import pair_distill_loss, pair_distill_loss_torch, prefilter_distill_loss  # noqa: F401
 from .training import search_shards_prefiltered, test_model_corpus_prefiltered_shards  # noqa: F401
 from .retrieval import PairPlan, SurvivorBank, WindowBank  # noqa: F401
-from .meter import EpochMeter, EpochMeterTorch, CorpusMeter, CorpusMeterTorch, VideoRankMeter  # noqa: F401
+from .meter import EpochMeter, EpochMeterTorch, CorpusMeter, CorpusMeterTorch, VideoRankMeter, CutFidelityMeter  # noqa: F401
 from .optim import FusedAdam, FusedAdamTorch, RowSparseAdam, RowSparseAdamTorch  # noqa: F401
 from .labels import build_targets  # noqa: F401
 from .moments import top_moments, top_moments_torch, merge_window_moments, merge_window_moments_torch  # noqa: F401

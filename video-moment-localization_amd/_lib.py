@@ -92,9 +92,9 @@ _torch_ops = None
 
 def load_torch():
     """The torch-extension binding (csrc/torch_binding.cpp): registers torch.ops.smin_hip.{smin_forward, smin_score, smin_loss, adam_step,
-    smin_encode_videos, smin_encode_queries, smin_score_pairs, smin_score_pairs_compact, smin_corpus_span_topk, smin_forward_pairs, smin_pair_rank_loss} -- the whole forward as one library call with its autograd graph built in
+    smin_encode_videos, smin_encode_queries, smin_score_pairs, smin_score_pairs_compact, smin_corpus_span_topk, smin_forward_pairs, smin_pair_rank_loss, smin_pair_distill_loss} -- the whole forward as one library call with its autograd graph built in
     C++, its forward-only scoring twin, the optimizer step over a parameter list, the corpus-search operators (the two encoders
-    alone, the scorer over indexed pairs of their banks, the ranking of span-valued moments across videos) and the contrastive term over a pair plan.  Raises if the library is missing."""
+    alone, the scorer over indexed pairs of their banks, the ranking of span-valued moments across videos) and the contrastive and soft-target terms over a pair plan.  Raises if the library is missing."""
     global _torch_ops
     if _torch_ops is not None:
         return _torch_ops

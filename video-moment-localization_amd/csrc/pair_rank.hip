@@ -7,6 +7,8 @@
 // list order (l_q, the hit flag, each pair's coefficient dloss/ds_p without 1/Nc), one thread over the queries in ascending q.
 // Backward: one workgroup per pair recomputes f and the exponentials; a row sweep writes dpm and dps, a column sweep dpe.
 // Every sum has an order that depends on the arguments only; no atomics; plain stores; every output element is written.
+// smin_pair_distill_fwd is the same three launches with another query kernel: the KL divergence of a query's
+// softmax over its pair scores from the softmax over a teacher's scores; its coefficients go through the same backward.
 #include <cmath>
 
 #include "common.h"
@@ -74,6 +76,76 @@ void pair_rank_query_kernel(const float* __restrict__ score, const int32_t* __re
         coef[p] = c;
     }
     if (lane == 0) part[q] = make_float4(counted ? logf(zall) - logf(zpos) : 0.f, counted ? 1.f : 0.f, counted && mpos >= mneg ? 1.f : 0.f, 0.f);
+}
+
+// ---- the listwise soft-target term: KL(teacher || student) over a query's segment, the teacher one score per pair.
+// What a wave finds of ONE side of a segment, the same in every lane: mx = the maximum, z = sum exp((v - mx) / temp), first = the first
+// entry in list order that holds mx, bad = the number of values that are not finite.  Both sides go through this function and through
+// seg_logit, in one expression order: equal values and equal temperatures give equal bits.
+struct SegSoft { float mx, z, bad; int first; };
+
+__device__ __forceinline__ int wave_min_int(int v) {
+    v = min(v, __shfl_xor(v, 1));
+    v = min(v, __shfl_xor(v, 2));
+    v = min(v, __shfl_xor(v, 4));
+    v = min(v, __shfl_xor(v, 8));
+    v = min(v, __shfl_xor(v, 16));
+    v = min(v, __shfl_xor(v, 32));
+    return v;
+}
+
+__device__ __forceinline__ float seg_logit(float v, float mx, float temp) { return (v - mx) / temp; }
+
+__device__ __forceinline__ SegSoft seg_softmax(const float* __restrict__ val, const int32_t* __restrict__ q_pairs, int beg, int end, int lane, int P,
+                                               float temp)
+{
+    SegSoft r;
+    float mx = -INFINITY, bad = 0.f;
+    int first = 0x7fffffff;
+    for (int e = beg + lane; e < end; e += 64) {
+        const float v = val[clampi(q_pairs[e], 0, P - 1)];
+        if (!(fabsf(v) < INFINITY)) bad += 1.f;
+        if (v > mx) { mx = v; first = e; }
+    }
+    r.mx = wave_max(mx);
+    r.first = wave_min_int(mx == r.mx ? first : 0x7fffffff);
+    r.bad = wave_sum(bad);
+    float z = 0.f;
+    for (int e = beg + lane; e < end; e += 64) z += expf(seg_logit(val[clampi(q_pairs[e], 0, P - 1)], r.mx, temp));
+    r.z = wave_sum(z);
+    return r;
+}
+
+// One wave64 per query, four queries per workgroup, pair_rank_query_kernel's layout.  A query is counted when its segment lists at
+// least two pairs and every teacher value in it is finite.  part[q] = { l_q, counted, agree, 0 } with l_q = sum pT * (lT - lS) (no
+// logf of a probability); coef[p] = (pS - pT) / gamma, 0 for the pairs of a query that is not counted.
+__global__ __launch_bounds__(256)
+void pair_distill_query_kernel(const float* __restrict__ score, const float* __restrict__ teacher, const int32_t* __restrict__ q_ptr,
+                               const int32_t* __restrict__ q_pairs, int P, int Q, float gamma, float gamma_teacher, float* __restrict__ coef,
+                               float4* __restrict__ part)
+{
+    const int q = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (q >= Q) return;                                           // (the whole wave)
+    const int beg = clampi(q_ptr[q], 0, P), end = clampi(q_ptr[q + 1], beg, P);
+    const SegSoft T = seg_softmax(teacher, q_pairs, beg, end, lane, P, gamma_teacher);
+    const bool counted = end - beg >= 2 && T.bad == 0.f;
+    float kl = 0.f, agree = 0.f;
+    if (counted) {                                                // (uniform over the wave)
+        const SegSoft S = seg_softmax(score, q_pairs, beg, end, lane, P, gamma);
+        const float logzs = logf(S.z), logzt = logf(T.z);
+        for (int e = beg + lane; e < end; e += 64) {
+            const int p = clampi(q_pairs[e], 0, P - 1);
+            const float xs = seg_logit(score[p], S.mx, gamma), xt = seg_logit(teacher[p], T.mx, gamma_teacher);
+            const float ps = expf(xs) / S.z, pt = expf(xt) / T.z;
+            kl += pt * ((xt - logzt) - (xs - logzs));
+            coef[p] = (ps - pt) / gamma;
+        }
+        kl = wave_sum(kl);
+        agree = S.first == T.first ? 1.f : 0.f;
+    } else {
+        for (int e = beg + lane; e < end; e += 64) coef[clampi(q_pairs[e], 0, P - 1)] = 0.f;
+    }
+    if (lane == 0) part[q] = make_float4(kl, counted ? 1.f : 0.f, agree, 0.f);
 }
 
 __global__ void pair_rank_final_kernel(const float4* __restrict__ part, int Q, float* __restrict__ loss, float* __restrict__ stats)
@@ -169,6 +241,28 @@ extern "C" int smin_pair_rank_fwd(void* stream, const float* pm, const float* ps
     hipLaunchKernelGGL(pair_rank_pool_kernel, dim3(P), dim3(256), 0, st, pm, ps, pe, mm, L, tau, pair_score, pool, coef);
     SMIN_LAUNCH_CHECK();
     hipLaunchKernelGGL(pair_rank_query_kernel, dim3(cdiv(Q, 4)), dim3(256), 0, st, pair_score, q_ptr, q_pairs, positive, P, Q, gamma, coef, part);
+    SMIN_LAUNCH_CHECK();
+    hipLaunchKernelGGL(pair_rank_final_kernel, dim3(1), dim3(64), 0, st, part, Q, loss, stats);
+    SMIN_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" size_t smin_pair_distill_ws_bytes(int P, int Q, int L) { return smin_pair_rank_ws_bytes(P, Q, L); }
+
+extern "C" int smin_pair_distill_fwd(void* stream, const float* pm, const float* ps, const float* pe, const uint8_t* mm, const int32_t* q_ptr,
+                                     const int32_t* q_pairs, const float* teacher, int P, int Q, int L, float tau, float gamma, float gamma_teacher,
+                                     float* loss, float* stats, float* pair_score, float* coef, float* pool, void* ws, size_t ws_bytes)
+{
+    SMIN_REQUIRE(P >= 1 && Q >= 1 && L >= 1 && L <= RANK_MAX_L);
+    SMIN_REQUIRE(pm && ps && pe && mm && q_ptr && q_pairs && teacher && loss && stats && pair_score && coef && pool && ws);
+    SMIN_REQUIRE(rank_temperature(tau) && rank_temperature(gamma) && rank_temperature(gamma_teacher));
+    SMIN_REQUIRE(ws_bytes >= smin_pair_distill_ws_bytes(P, Q, L));
+    hipStream_t st = (hipStream_t)stream;
+    float4* part = (float4*)ws;
+    hipLaunchKernelGGL(pair_rank_pool_kernel, dim3(P), dim3(256), 0, st, pm, ps, pe, mm, L, tau, pair_score, pool, coef);
+    SMIN_LAUNCH_CHECK();
+    hipLaunchKernelGGL(pair_distill_query_kernel, dim3(cdiv(Q, 4)), dim3(256), 0, st, pair_score, teacher, q_ptr, q_pairs, P, Q, gamma, gamma_teacher,
+                       coef, part);
     SMIN_LAUNCH_CHECK();
     hipLaunchKernelGGL(pair_rank_final_kernel, dim3(1), dim3(64), 0, st, part, Q, loss, stats);
     SMIN_LAUNCH_CHECK();

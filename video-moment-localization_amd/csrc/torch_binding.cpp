@@ -347,6 +347,43 @@ struct PairRankNode : torch::autograd::Function<PairRankNode> {
 };
 
 
+// listwise soft-target loss over a pair plan (csrc/pair_rank.hip): three forward launches, PairRankNode's backward call
+struct PairDistillNode : torch::autograd::Function<PairDistillNode> {
+    static variable_list forward(AutogradContext* ctx, Tensor pm, Tensor ps, Tensor pe, Tensor mm, Tensor q_ptr, Tensor q_pairs, Tensor teacher, double tau,
+                                 double gamma, double gamma_teacher)
+    {
+        auto i = [](const Tensor& t) { return cont(t.scalar_type() == at::kInt ? t : t.to(at::kInt)); };
+        pm = cont(fl(pm)); ps = cont(fl(ps)); pe = cont(fl(pe)); teacher = cont(fl(teacher.detach()));
+        mm = cont((mm.scalar_type() == at::kBool || mm.scalar_type() == at::kByte) ? mm : mm.ne(0));
+        q_ptr = i(q_ptr); q_pairs = i(q_pairs);
+        const int P = i32(ps.size(0)), L = i32(ps.size(1)), Q = i32(q_ptr.size(0) - 1);
+        Tensor loss = at::empty({1}, pm.options()), stats = at::empty({2}, pm.options()), score = at::empty({(int64_t)P}, pm.options());
+        Tensor coef = at::empty({(int64_t)P}, pm.options()), pool = at::empty({(int64_t)P, 2}, pm.options());
+        const size_t need = smin_pair_distill_ws_bytes(P, Q, L);
+        Scratch ws = scratch(need, pm.device());
+        SMIN_CK(smin_pair_distill_fwd(cur(), fp(pm), fp(ps), fp(pe), u8(mm), ip(q_ptr), ip(q_pairs), fp(teacher), P, Q, L, (float)tau, (float)gamma,
+                                      (float)gamma_teacher, fpm(loss), fpm(stats), fpm(score), fpm(coef), fpm(pool), ws.p, ws.n));
+        ctx->save_for_backward({pm, ps, pe, mm, stats, coef, pool});
+        ctx->saved_data["tau"] = tau;
+        ctx->mark_non_differentiable({stats, score});
+        return {loss.reshape({}), stats, score};
+    }
+    static variable_list backward(AutogradContext* ctx, variable_list g)
+    {
+        auto sv = ctx->get_saved_variables();
+        const Tensor &pm = sv[0], &ps = sv[1], &pe = sv[2], &mm = sv[3], &stats = sv[4], &coef = sv[5], &pool = sv[6];
+        const int P = i32(ps.size(0)), L = i32(ps.size(1));
+        Tensor dloss = cont(fl(g[0].reshape({1})));
+        Tensor dpm = at::empty_like(pm), dps = at::empty_like(ps), dpe = at::empty_like(pe);
+        SMIN_CK(smin_pair_rank_bwd(cur(), fp(dloss), fp(stats), fp(coef), fp(pool), fp(pm), fp(ps), fp(pe), u8(mm), P, L, (float)ctx->saved_data["tau"].toDouble(),
+                                   fpm(dpm), fpm(dps), fpm(dpe)));
+        variable_list out{dpm, dps, dpe};
+        for (int k = 0; k < 7; ++k) out.push_back(undef());
+        return out;
+    }
+};
+
+
 // ---------------------------------------------------------------- the fused core
 // ProposalGeneration + every SMI layer + Localization (models.py:101-126, 306-344) as ONE autograd node: forward and backward
 // are straight-line sequences of the C entry points with hand-placed stream forks.  What a node per module (the Python host's
@@ -1695,6 +1732,26 @@ std::tuple<Tensor, Tensor, Tensor> smin_pair_rank_loss(const Tensor& pm, const T
     return std::make_tuple(out[0], out[1], out[2]);
 }
 
+// training.pair_distill_loss: the soft-target term over a pair plan's P pairs (see PairDistillNode above); gradients to pm, ps, pe only
+std::tuple<Tensor, Tensor, Tensor> smin_pair_distill_loss(const Tensor& pm, const Tensor& ps, const Tensor& pe, const Tensor& moment_mask, const Tensor& q_ptr,
+                                                          const Tensor& q_pairs, const Tensor& teacher, double tau, double gamma, double gamma_teacher)
+{
+    for (const Tensor* t : {&pm, &ps, &pe, &moment_mask, &q_ptr, &q_pairs, &teacher})
+        TORCH_CHECK(t->is_cuda(), "smin_pair_distill_loss runs on a HIP device only (there is no CPU fallback)");
+    for (const Tensor* t : {&ps, &pe, &moment_mask, &q_ptr, &q_pairs, &teacher})
+        TORCH_CHECK(t->device() == pm.device(), "smin_pair_distill_loss: every tensor on one device");
+    const int64_t P = pm.dim() == 3 ? pm.size(0) : -1, L = pm.dim() == 3 ? pm.size(1) : -1;
+    TORCH_CHECK(P >= 1 && L >= 1 && pm.size(2) == L && ps.sizes() == at::IntArrayRef({P, L}) && pe.sizes() == ps.sizes() && moment_mask.sizes() == pm.sizes(),
+                "smin_pair_distill_loss: pm (P, L, L), ps (P, L), pe (P, L) and moment_mask (P, L, L) with P, L >= 1");
+    TORCH_CHECK(q_ptr.dim() == 1 && q_ptr.size(0) >= 2 && q_pairs.dim() == 1 && q_pairs.size(0) == P && teacher.dim() == 1 && teacher.size(0) == P,
+                "smin_pair_distill_loss: q_ptr (Q + 1,) with Q >= 1, q_pairs (P,) and teacher (P,)");
+    TORCH_CHECK(std::isfinite(tau) && tau > 0 && std::isfinite(gamma) && gamma > 0 && std::isfinite(gamma_teacher) && gamma_teacher > 0,
+                "smin_pair_distill_loss: tau, gamma and gamma_teacher must be finite and positive");
+    c10::hip::HIPGuard device_guard(pm.device().index());
+    auto out = PairDistillNode::apply(pm, ps, pe, moment_mask, q_ptr, q_pairs, teacher, tau, gamma, gamma_teacher);
+    return std::make_tuple(out[0], out[1], out[2]);
+}
+
 // FusedAdam.step (optim.py): the pointers of the parameters and their gradients are gathered here -- with
 // zero_grad(set_to_none=True) the gradients move every step -- and handed to smin_grad_norm (when clipping or the guard is on) and
 // smin_adam_step on the current stream.  No host read: capturable as it stands, the pointers baked into the graph as for torch's own
@@ -1785,6 +1842,9 @@ TORCH_LIBRARY(smin_hip, m)
     // the contrastive term beside smin_loss: each query's own video ranked above the wrong ones of its pair plan
     m.def("smin_pair_rank_loss(Tensor pm, Tensor ps, Tensor pe, Tensor moment_mask, Tensor q_ptr, Tensor q_pairs, Tensor positive, float tau, float gamma) -> "
           "(Tensor loss, Tensor stats, Tensor pair_score)", &smin_pair_rank_loss);
+    // the soft-target term beside it: each query's softmax over its pairs pulled towards a teacher's scores of them
+    m.def("smin_pair_distill_loss(Tensor pm, Tensor ps, Tensor pe, Tensor moment_mask, Tensor q_ptr, Tensor q_pairs, Tensor teacher, float tau, float gamma, "
+          "float gamma_teacher) -> (Tensor loss, Tensor stats, Tensor pair_score)", &smin_pair_distill_loss);
     // FusedAdam.step: Adam / AdamW over a parameter list, gradient norm, clipping and the non-finite guard on the device (see adam_step above)
     m.def("adam_step(Tensor[] params, Tensor[] grads, Tensor exp_avg_flat, Tensor exp_avg_sq_flat, int[] offsets, Tensor state, Tensor? ws, float beta1, "
           "float beta2, float eps, float weight_decay, bool decoupled, float max_norm, bool skip_nonfinite) -> ()", &adam_step);

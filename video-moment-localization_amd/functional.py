@@ -650,6 +650,40 @@ class PairRankFn(Function):
         return (dpm, dps, dpe) + (None,) * 6
 
 
+class PairDistillFn(Function):
+    """The soft-target term over a pair plan (csrc/pair_rank.hip) on the ctypes route: smin_pair_distill_fwd (three
+    launches) and smin_pair_rank_bwd (one), the calls the extension's PairDistillNode makes.  Returns (loss, stats, pair_score);
+    gradients go to pm, ps and pe only."""
+
+    @staticmethod
+    def forward(ctx, pm, ps, pe, mm, q_ptr, q_pairs, teacher, tau, gamma, gamma_teacher):
+        pm, ps, pe, teacher = (_c(x.float()) for x in (pm, ps, pe, teacher.detach()))
+        mm = _c(mm if mm.dtype in (torch.bool, torch.uint8) else mm != 0)
+        q_ptr, q_pairs = (_c(x if x.dtype == torch.int32 else x.to(torch.int32)) for x in (q_ptr, q_pairs))
+        P, L = ps.shape
+        Q = q_ptr.shape[0] - 1
+        loss, stats, score = pm.new_empty((1,)), pm.new_empty((2,)), pm.new_empty((P,))
+        coef, pool = pm.new_empty((P,)), pm.new_empty((P, 2))
+        nbytes = _lib.load().smin_pair_distill_ws_bytes(P, Q, L)
+        ws = _lib.workspace(nbytes, pm.device)
+        call("smin_pair_distill_fwd", stream(), ptr(pm), ptr(ps), ptr(pe), ptr(mm), ptr(q_ptr), ptr(q_pairs), ptr(teacher), P, Q, L, tau, gamma,
+             gamma_teacher, ptr(loss), ptr(stats), ptr(score), ptr(coef), ptr(pool), ptr(ws), ws.numel())
+        ctx.save_for_backward(pm, ps, pe, mm, stats, coef, pool)
+        ctx.tau = tau
+        ctx.mark_non_differentiable(stats, score)
+        return loss.reshape(()), stats, score
+
+    @staticmethod
+    def backward(ctx, dloss, _dstats, _dscore):
+        pm, ps, pe, mm, stats, coef, pool = ctx.saved_tensors
+        P, L = ps.shape
+        dloss = _c(dloss.reshape(1).float())
+        dpm, dps, dpe = torch.empty_like(pm), torch.empty_like(ps), torch.empty_like(pe)
+        call("smin_pair_rank_bwd", stream(), ptr(dloss), ptr(stats), ptr(coef), ptr(pool), ptr(pm), ptr(ps), ptr(pe), ptr(mm), P, L, ctx.tau,
+             ptr(dpm), ptr(dps), ptr(dpe))
+        return (dpm, dps, dpe) + (None,) * 7
+
+
 class PrefilterMapsFn(Function):
     """The first-stage maps with their backward (csrc/prefilter.hip) on the ctypes route: smin_prefilter_scores
     with maps in ONE call, smin_prefilter_maps_bwd in the backward.  ``lmask`` / ``mm``: one byte per entry.  Returns (pm0 (Q, V, L,

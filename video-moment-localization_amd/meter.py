@@ -363,3 +363,47 @@ class VideoRankMeter:
         out["MRR"] = acc[1] / num if num else 0.0
         out["num_samples"] = int(num)
         return out
+
+
+class CutFidelityMeter:
+    """``CutFidelityMeter(n=(1, 5, 10), M=(8, 16, 32), device=...)``: what a first-stage cut to M videos loses of a teacher's best n,
+    measured without labels.  ``update(teacher_rank, student_rank)`` takes two ``(Q, V)`` integer rank tables --
+    ``rank_videos``' ``pair_rank`` over all pairs and ``prefilter_videos``' ``rank``; -1: no candidate -- and for every (n, M) adds
+    ``sum_q |{v : 0 <= teacher_rank < n and 0 <= student_rank < M}|`` to one total and ``sum_q min(n, c_q)`` to the other, c_q the
+    number of the query's teacher candidates: fp64 totals in a device tensor.  A few torch ops on the tensors' device per update, no
+    host read; ``result()`` is the one read (keys ``"keep@n/M"``, the ratio of the totals, 0 when empty, and ``"num_samples"``, the
+    queries), ``reset()`` zeroes, ``state`` is ``[queries, kept per (n, M) ..., possible per n ...]``."""
+
+    def __init__(self, n=(1, 5, 10), M=(8, 16, 32), device=None):
+        self.n, self.M = tuple(n), tuple(M)
+        for name, vals in (("n", self.n), ("M", self.M)):
+            if not vals or any(not isinstance(v, int) or isinstance(v, bool) or v < 1 for v in vals):
+                raise ValueError(f"CutFidelityMeter: {name} must be positive integers (got {vals!r})")
+        self.keys = [f"keep@{a}/{b}" for a in self.n for b in self.M]
+        self.device = torch.device("cuda" if device is None else device)
+        self.state = torch.zeros(1 + len(self.keys) + len(self.n), dtype=torch.float64, device=self.device)
+        self._n = torch.tensor(self.n, dtype=torch.int64).to(self.device, non_blocking=True)
+        self._M = torch.tensor(self.M, dtype=torch.int64).to(self.device, non_blocking=True)
+
+    def reset(self):
+        self.state.zero_()
+
+    def update(self, teacher_rank, student_rank):
+        for name, r in (("teacher_rank", teacher_rank), ("student_rank", student_rank)):
+            if r.dim() != 2 or r.is_floating_point() or r.shape != teacher_rank.shape:
+                raise ValueError(f"CutFidelityMeter.update: {name} must be an integer (Q, V) tensor, both of one shape; got {tuple(r.shape)} {r.dtype}")
+            if r.device != self.state.device:
+                raise ValueError(f"CutFidelityMeter on {self.state.device} got a tensor on {r.device}")
+        rt, rs = teacher_rank.to(torch.int64).reshape(-1, 1), student_rank.to(torch.int64).reshape(-1, 1)
+        best = ((rt >= 0) & (rt < self._n)).to(torch.float64)                      # (Q V, n): among the teacher's best n
+        kept = ((rs >= 0) & (rs < self._M)).to(torch.float64)                      # (Q V, M): survives the cut to M
+        cands = (teacher_rank >= 0).sum(dim=1, keepdim=True)
+        possible = torch.minimum(cands, self._n).sum(dim=0).to(torch.float64)
+        self.state += torch.cat([possible.new_full((1,), float(teacher_rank.shape[0])), (best.t() @ kept).reshape(-1), possible])
+
+    def result(self):
+        acc = self.state.tolist()                                              # the one host read
+        k, nm = len(self.keys), len(self.M)
+        out = {key: (acc[1 + a] / acc[1 + k + a // nm] if acc[1 + k + a // nm] else 0.0) for a, key in enumerate(self.keys)}
+        out["num_samples"] = int(acc[0])
+        return out

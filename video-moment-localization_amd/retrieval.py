@@ -818,6 +818,21 @@ class _Retrieval:
             r.update(video_index=video.reshape(-1), query_index=query.reshape(-1))
         return r
 
+    def prefilter_fidelity(self, videos, queries, meter, tau=0.1, max_batch=64):
+        """How much of the full model's video ranking a first-stage cut keeps, measured without labels: the teacher
+        ranks are ``rank_videos`` on all pairs (``pair_rank`` as ``(Q, V)``), the student ranks ``prefilter_videos(...)["rank"]``, both
+        pooled at ``tau``; ONE ``meter.update(teacher_rank, student_rank)`` (meter.CutFidelityMeter) and no host read.  ``videos``: a
+        VideoBank; a WindowBank raises ValueError.  Returns ``(teacher score (Q, V), student score (Q, V))``."""
+        what = "prefilter_fidelity"
+        _require_banks(what, videos, queries)
+        if isinstance(videos, WindowBank):
+            raise ValueError(f"{what}: takes a VideoBank; window banks are not measured here")
+        Q, V = len(queries), len(videos)
+        full = self.rank_videos(videos, queries, n=1, tau=tau, max_batch=max_batch)
+        first = self.prefilter_videos(videos, queries, 1, tau=tau)
+        meter.update(full["pair_rank"].reshape(Q, V), first["rank"])
+        return full["pair_score"].reshape(Q, V), first["score"]
+
     def prefilter_forward(self, video_features, video_mask, query_features, query_mask, length_mask, moment_mask, tau=0.1):
         """The first-stage maps of every (query, video) of V videos and Q queries, with grad: what prefilter_videos
         ranks by, differentiable with respect to the encoders and the three score heads; no SMI layer runs.  ``fv`` and ``fs`` come

@@ -68,17 +68,7 @@ def pair_rank_loss_torch(pm, ps, pe, moment_mask, plan, tau=0.1, gamma=0.1, retu
     P, Q = plan.P, plan.Q
     lists = torch.cat([plan.q_ptr.reshape(-1), plan.q_pairs.reshape(-1), plan.positive.reshape(-1)]).tolist()     # the one host read
     q_ptr, q_pairs, positive = lists[:Q + 1], lists[Q + 1:Q + 1 + P], lists[Q + 1 + P:]
-    valid = moment_mask != 0
-    f = (pm * torch.sqrt(ps.clamp_min(1e-12)).unsqueeze(2)) * torch.sqrt(pe.clamp_min(1e-12)).unsqueeze(1)
-    n = valid.reshape(P, -1).sum(dim=1)
-    some = n > 0
-    m = torch.where(valid, f.detach(), torch.full_like(f, float("-inf"))).reshape(P, -1).max(dim=1).values
-    m = torch.where(some, m, torch.zeros_like(m)).reshape(P, 1, 1)
-    # a masked cell stands at the maximum (exponent 0) and is multiplied away: nothing infinite reaches autograd
-    e = torch.exp((torch.where(valid, f, m) - m) / tau) * valid.to(f.dtype)
-    z = e.reshape(P, -1).sum(dim=1)
-    one = torch.ones_like(z)
-    s = torch.where(some, m.reshape(P) + tau * torch.log(torch.where(some, z, one) / torch.where(some, n.to(f.dtype), one)), torch.zeros_like(z))
+    s = _pooled_scores_torch(pm, ps, pe, moment_mask, tau)
     sd = s.detach()
     total, counted, hits = s.new_zeros(()), 0, 0
     for q in range(Q):
@@ -95,6 +85,23 @@ def pair_rank_loss_torch(pm, ps, pe, moment_mask, plan, tau=0.1, gamma=0.1, retu
     if not return_stats:
         return loss
     return loss, torch.tensor([counted, hits], dtype=torch.float32, device=pm.device), sd
+
+
+def _pooled_scores_torch(pm, ps, pe, moment_mask, tau):
+    """The pooled pair score ``s (P,)`` of pair_rank_loss_torch and pair_distill_loss_torch, with grad: the log-mean-exp at ``tau`` of
+    each pair's valid cells' fused scores, 0 for a pair without one."""
+    P = pm.shape[0]
+    valid = moment_mask != 0
+    f = (pm * torch.sqrt(ps.clamp_min(1e-12)).unsqueeze(2)) * torch.sqrt(pe.clamp_min(1e-12)).unsqueeze(1)
+    n = valid.reshape(P, -1).sum(dim=1)
+    some = n > 0
+    m = torch.where(valid, f.detach(), torch.full_like(f, float("-inf"))).reshape(P, -1).max(dim=1).values
+    m = torch.where(some, m, torch.zeros_like(m)).reshape(P, 1, 1)
+    # a masked cell stands at the maximum (exponent 0) and is multiplied away: nothing infinite reaches autograd
+    e = torch.exp((torch.where(valid, f, m) - m) / tau) * valid.to(f.dtype)
+    z = e.reshape(P, -1).sum(dim=1)
+    one = torch.ones_like(z)
+    return torch.where(some, m.reshape(P) + tau * torch.log(torch.where(some, z, one) / torch.where(some, n.to(f.dtype), one)), torch.zeros_like(z))
 
 
 def pair_rank_loss(pm, ps, pe, moment_mask, plan, tau=0.1, gamma=0.1, return_stats=False):
@@ -120,6 +127,84 @@ def pair_rank_loss(pm, ps, pe, moment_mask, plan, tau=0.1, gamma=0.1, return_sta
         from .functional import PairRankFn
         with torch.cuda.device(pm.device):
             out = PairRankFn.apply(pm, ps, pe, moment_mask, plan.q_ptr, plan.q_pairs, plan.positive, tau, gamma)
+    return tuple(out) if return_stats else out[0]
+
+
+def _teacher_temperature(what, tau, gamma, gamma_teacher):
+    """The three temperatures of the soft-target term checked; returns ``gamma_teacher`` with None resolved to ``gamma``."""
+    _temperatures(what, tau, gamma)
+    if gamma_teacher is None:
+        return float(gamma)
+    if not (isinstance(gamma_teacher, (int, float)) and 0.0 < float(gamma_teacher) < float("inf")):
+        raise ValueError(f"{what}: gamma_teacher must be None or a finite positive number (got {gamma_teacher!r})")
+    return float(gamma_teacher)
+
+
+def _pair_distill_check(what, pm, plan, teacher, tau, gamma, gamma_teacher):
+    from .retrieval import PairPlan
+    if not isinstance(plan, PairPlan):
+        raise ValueError(f"{what}: the plan must be a PairPlan (its q_ptr and q_pairs are read)")
+    if pm.dim() != 3 or plan.P != pm.shape[0]:
+        raise ValueError(f"{what}: the plan lists {plan.P} pairs and pm is {tuple(pm.shape)}: pm must be (P, L, L) of the plan's pairs")
+    if not torch.is_tensor(teacher) or tuple(teacher.shape) != (plan.P,) or not teacher.is_floating_point():
+        raise ValueError(f"{what}: teacher must be a float tensor of shape (P,) = ({plan.P},), one score per pair in pair order "
+                         f"(got {tuple(teacher.shape) if torch.is_tensor(teacher) else type(teacher).__name__})")
+    return _teacher_temperature(what, tau, gamma, gamma_teacher)
+
+
+def pair_distill_loss_torch(pm, ps, pe, moment_mask, plan, teacher, tau=0.1, gamma=0.1, gamma_teacher=None, return_stats=False):
+    """``pair_distill_loss`` as plain torch ops on any device and in any float dtype (the teacher is taken in pm's), differentiable by
+    autograd: the tests' reference; nothing routes here.  The plan's ``q_ptr`` / ``q_pairs`` and the teacher's finiteness are read once
+    on the host to form the loop over the queries, and each query's two first maxima once more: not for the training path."""
+    gamma_teacher = _pair_distill_check("pair_distill_loss_torch", pm, plan, teacher, tau, gamma, gamma_teacher)
+    P, Q = plan.P, plan.Q
+    t = teacher.detach().to(device=pm.device, dtype=pm.dtype)
+    lists = torch.cat([plan.q_ptr.reshape(-1), plan.q_pairs.reshape(-1), torch.isfinite(t).to(plan.q_ptr.dtype)]).tolist()     # the host read
+    q_ptr, q_pairs, finite = lists[:Q + 1], lists[Q + 1:Q + 1 + P], lists[Q + 1 + P:]
+    s = _pooled_scores_torch(pm, ps, pe, moment_mask, tau)
+    sd = s.detach()
+    first = lambda x: int(torch.nonzero(x == x.max())[0])        # the first entry in list order that holds the maximum
+    total, counted, agree = s.new_zeros(()), 0, 0
+    for q in range(Q):
+        seg = q_pairs[q_ptr[q]:q_ptr[q + 1]]
+        if len(seg) < 2 or not all(finite[p] for p in seg):
+            continue
+        xs, xt = (s[seg] - sd[seg].max()) / gamma, (t[seg] - t[seg].max()) / gamma_teacher
+        zt = torch.exp(xt).sum()
+        total = total + (torch.exp(xt) / zt * ((xt - torch.log(zt)) - (xs - torch.log(torch.exp(xs).sum())))).sum()
+        counted += 1
+        agree += int(first(t[seg]) == first(sd[seg]))
+    loss = total / counted if counted else (s.sum() * 0.0)
+    if not return_stats:
+        return loss
+    return loss, torch.tensor([counted, agree], dtype=torch.float32, device=pm.device), sd
+
+
+def pair_distill_loss(pm, ps, pe, moment_mask, plan, teacher, tau=0.1, gamma=0.1, gamma_teacher=None, return_stats=False):
+    """A listwise soft-target term beside ``pair_rank_loss``: for each query of a pair plan, the softmax over its
+    pairs' scores pulled towards the softmax over a teacher's scores of the same pairs.  ``pm``, ``ps``, ``pe``, ``moment_mask``: as
+    pair_rank_loss takes them; ``plan``: the PairPlan of these pairs (``q_ptr`` and ``q_pairs`` are read; no positive flags are
+    needed); ``teacher (P,)``: one score per pair in pair order, detached here.  A pair's score is pair_rank_loss' -- the
+    log-mean-exp at ``tau`` of its valid cells' fused scores, the same bits --; a query's loss is ``KL(softmax(teacher /
+    gamma_teacher) || softmax(score / gamma))`` over its pairs (``gamma_teacher`` None: ``gamma``); the loss is the mean over the
+    queries that list at least two pairs and whose teacher scores are all finite (0, with zero gradients, if there is none).  With the
+    teacher equal to the pair scores and equal temperatures the loss and every gradient are exactly 0.  HIP kernels forward and
+    backward (csrc/pair_rank.hip; the backward is pair_rank_loss'), fp32, the same bits every run, no host read; HIP tensors only.
+    Gradients go to pm, ps and pe.
+
+    Returns ``loss``; with ``return_stats`` ``(loss, stats, pair_score)``: ``stats = [counted queries, agree]`` fp32 on the device --
+    a counted query agrees when the teacher's first best pair in list order is also the student's -- and ``pair_score (P,)``,
+    detached."""
+    gamma_teacher = _pair_distill_check("pair_distill_loss", pm, plan, teacher, tau, gamma, gamma_teacher)
+    _require_hip(pm, "pair_distill_loss")
+    from . import _lib
+    tau, gamma = float(tau), float(gamma)
+    if NATIVE_LOSS:
+        out = _lib.load_torch().smin_pair_distill_loss(pm, ps, pe, moment_mask, plan.q_ptr, plan.q_pairs, teacher.detach(), tau, gamma, gamma_teacher)
+    else:
+        from .functional import PairDistillFn
+        with torch.cuda.device(pm.device):
+            out = PairDistillFn.apply(pm, ps, pe, moment_mask, plan.q_ptr, plan.q_pairs, teacher.detach(), tau, gamma, gamma_teacher)
     return tuple(out) if return_stats else out[0]
 
 
@@ -384,32 +469,93 @@ def prefilter_rank_loss(model, group, tau=0.1, gamma=0.1, return_stats=False):
     unchanged.  Gradients reach the encoders and the heads only; no SMI layer runs.  No host read.  Returns pair_rank_loss' value(s)."""
     what = "prefilter_rank_loss"
     _temperatures(what, tau, gamma)
+    pm0, ps0, pe0, mm_pairs, plan = _first_stage(what, model, group, tau)
+    return pair_rank_loss(pm0, ps0, pe0, mm_pairs, plan, tau, gamma, return_stats)
+
+
+def _group_size(group):
+    return group["moment_mask"].shape[0], group["query_features"].shape[0]
+
+
+def _first_stage(what, model, group, tau, need_gt=True):
+    """What the first-stage terms share of a group: ``(pm0, ps0, pe0, moment_mask per pair, the all-pairs plan)`` -- gt_video checked,
+    SMIN.prefilter_forward's maps with grad, all_pairs_plan and the mask gathered per pair.  Without ``need_gt`` a group that has no
+    gt_video gets the plan of video 0 for every query: its positive flags are then meaningless, and the soft-target term reads none."""
     mm = group["moment_mask"]
-    V, Q = mm.shape[0], group["query_features"].shape[0]
-    if "gt_video" not in group or group["gt_video"] is None:
-        raise ValueError(f"{what}: the group must carry gt_video, each query's own video")
-    gv = host_array(group["gt_video"])
+    V, Q = _group_size(group)
+    if group.get("gt_video") is None:
+        if need_gt:
+            raise ValueError(f"{what}: the group must carry gt_video, each query's own video")
+        gv = np.zeros(Q, dtype=np.int64)
+    else:
+        gv = host_array(group["gt_video"])
     if gv.shape[0] != Q or (gv.size and (gv.min() < 0 or gv.max() >= V)):
         raise ValueError(f"{what}: gt_video must name one of the V = {V} videos for each of the Q = {Q} queries")
     pm0, ps0, pe0, _ = model.prefilter_forward(*_inputs(group), tau=tau)
     plan = all_pairs_plan(V, Q, gv, mm.device, what)
-    mm_pairs = mm.index_select(0, plan.video_index)
-    return pair_rank_loss(pm0, ps0, pe0, mm_pairs, plan, tau, gamma, return_stats)
+    return pm0, ps0, pe0, mm.index_select(0, plan.video_index), plan
 
 
-def _pair_step(model, optimizer, g, plan, meter, rank_weight=0.0, tau=0.1, gamma=0.1, prefilter_weight=0.0):
+def _teacher_pairs(what, teacher, V, Q):
+    """A (Q, V) teacher table as the (Q * V,) scores of the all-pairs plan's pairs (``p = q * V + v``)."""
+    if not torch.is_tensor(teacher) or tuple(teacher.shape) != (Q, V) or not teacher.is_floating_point():
+        raise ValueError(f"{what}: teacher must be a float tensor of shape (Q, V) = ({Q}, {V}), row q in video order (SMIN.pair_scores' layout); "
+                         f"got {tuple(teacher.shape) if torch.is_tensor(teacher) else type(teacher).__name__}")
+    return teacher.detach().reshape(Q * V)
+
+
+def prefilter_distill_loss(model, group, teacher, tau=0.1, gamma=0.1, gamma_teacher=None, return_stats=False):
+    """``pair_distill_loss`` on the FIRST-STAGE maps of a group: each query's softmax over all the group's videos
+    by the score ``SMIN.search(prefilter=M)`` prunes with, pulled towards the softmax over ``teacher (Q, V)`` -- row q in video order,
+    ``SMIN.pair_scores``' layout; the full model's pooled scores (``pool="lme"``) make the first stage imitate the ranking it stands in
+    for.  ``group``: prefilter_rank_loss' dict; gt_video is not needed.  SMIN.prefilter_forward forms the maps with grad, the
+    all-pairs plan lists them by query, and pair_distill_loss does the rest.  Gradients reach the encoders and the heads only; no SMI
+    layer runs; the teacher gets none.  No host read.  Returns pair_distill_loss' value(s)."""
+    what = "prefilter_distill_loss"
+    _teacher_temperature(what, tau, gamma, gamma_teacher)
+    t = _teacher_pairs(what, teacher, *_group_size(group))
+    pm0, ps0, pe0, mm_pairs, plan = _first_stage(what, model, group, tau, need_gt=False)
+    return pair_distill_loss(pm0, ps0, pe0, mm_pairs, plan, t, tau, gamma, gamma_teacher, return_stats)
+
+
+def _first_stage_terms(what, model, group, tau, gamma, rank_weight=0.0, distill_weight=0.0, teacher=None, gamma_teacher=None):
+    """``rank_weight * prefilter_rank_loss + distill_weight * prefilter_distill_loss`` of a group over ONE prefilter_forward: a term
+    whose weight is 0 is not computed.  Returns ``(the sum, pair_rank_loss' stats or None, pair_distill_loss' stats or None)``."""
+    t = None if distill_weight == 0.0 else _teacher_pairs(what, teacher, *_group_size(group))
+    pm0, ps0, pe0, mm_pairs, plan = _first_stage(what, model, group, tau, need_gt=rank_weight != 0.0)
+    total = rank_stats = distill_stats = None
+    if rank_weight != 0.0:
+        loss, rank_stats, _ = pair_rank_loss(pm0, ps0, pe0, mm_pairs, plan, tau, gamma, True)
+        total = rank_weight * loss
+    if distill_weight != 0.0:
+        loss, distill_stats, _ = pair_distill_loss(pm0, ps0, pe0, mm_pairs, plan, t, tau, gamma, gamma_teacher, True)
+        total = distill_weight * loss if total is None else total + distill_weight * loss
+    return total, rank_stats, distill_stats
+
+
+def _distill_weight(what, distill_weight, tau, gamma, gamma_teacher):
+    """The loops' check of their soft-target term's arguments, ahead of the first step."""
+    if not (isinstance(distill_weight, (int, float)) and not isinstance(distill_weight, bool) and 0.0 <= float(distill_weight) < float("inf")):
+        raise ValueError(f"{what}: distill_weight must be a finite number >= 0 (got {distill_weight!r})")
+    _teacher_temperature(what, tau, gamma, gamma_teacher)
+    return float(distill_weight)
+
+
+def _pair_step(model, optimizer, g, plan, meter, rank_weight=0.0, tau=0.1, gamma=0.1, prefilter_weight=0.0, distill_weight=0.0, teacher=None,
+               gamma_teacher=None):
     """One step of train_epoch_pairs on group ``g`` through ``plan`` (built with its positive flags): forward_pairs, pair_targets,
     loss_fn over all the pairs -- plus ``rank_weight * pair_rank_loss`` over the plan when the weight is not 0 --, the meter over the
     positive ones, backward, optimizer.step.  ``prefilter_weight`` not 0: plus ``prefilter_weight * prefilter_rank_loss`` over all
-    the group's pairs.  No host read with ``cell_counts``."""
+    the group's pairs, and ``distill_weight`` not 0: plus ``distill_weight * prefilter_distill_loss`` against ``teacher (Q, V)``, both
+    over one prefilter_forward.  No host read with ``cell_counts``."""
     optimizer.zero_grad()
     out = model.forward_pairs(*_inputs(g), None, None, cell_counts=g.get("cell_counts"), plan=plan)
     tg = pair_targets(g, g, None, None, None, plan=plan)
     loss = _loss_of(out, tg)
     if rank_weight != 0.0:
         loss = loss + rank_weight * pair_rank_loss(out[0], out[1], out[2], tg["moment_mask"], plan, tau, gamma)
-    if prefilter_weight != 0.0:
-        loss = loss + prefilter_weight * prefilter_rank_loss(model, g, tau, gamma)
+    if prefilter_weight != 0.0 or distill_weight != 0.0:
+        loss = loss + _first_stage_terms("train_epoch_pairs", model, g, tau, gamma, prefilter_weight, distill_weight, teacher, gamma_teacher)[0]
     rows = plan.positive_rows
     meter.update(out[0].detach().index_select(0, rows), out[1].detach().index_select(0, rows), out[2].detach().index_select(0, rows),
                  tg["moment_mask"].index_select(0, rows), tg["sm"].index_select(0, rows), loss=loss.detach())
@@ -461,7 +607,7 @@ def train_epoch_pairs(model, optimizer, groups, meter=None, rank_weight=0.0, tau
 
 
 def train_epoch_mined(model, optimizer, groups, negatives, skip=0, meter=None, max_batch=64, rank_weight=0.0, tau=0.1, gamma=0.1, mine_pool=None,
-                      prefilter_weight=0.0):
+                      prefilter_weight=0.0, distill_weight=0.0, gamma_teacher=None):
     """train_epoch_pairs with the pairs chosen by the model (hard-negative mining).  A group is train_epoch_pairs'
     dict without the two lists: the tensors, ``gt_video`` (Q host ints) and optionally ``cell_counts``.  Per group, under
     torch.no_grad(): encode_videos / encode_queries with the current parameters and ``model.mine_pairs`` -- every query against every
@@ -473,45 +619,89 @@ def train_epoch_mined(model, optimizer, groups, negatives, skip=0, meter=None, m
     ``rank_weight``, ``tau``, ``gamma``: train_epoch_pairs' contrastive term over the mined plan -- what a hard negative is mined for.
     ``mine_pool``: SMIN.mine_pairs' ``pool`` -- ``"lme"`` mines by the pooled pair score at ``tau``, the score that term contrasts
     (INTEGRATION.md 3t); None by the best moment.  ``prefilter_weight``: train_epoch_pairs' first-stage term over all the group's
-    pairs; 0, the default, leaves the step unchanged bit for bit."""
-    rank_weight = _rank_weight("train_epoch_mined", rank_weight, tau, gamma)
-    prefilter_weight = _prefilter_weight("train_epoch_mined", prefilter_weight, tau, gamma)
+    pairs; 0, the default, leaves the step unchanged bit for bit.
+
+    ``distill_weight`` > 0: the loss also gains ``distill_weight * prefilter_distill_loss(model, group, teacher, tau, gamma,
+    gamma_teacher)``, the teacher being the (Q, V) pooled pair scores the mining computes anyway: it requires
+    ``mine_pool="lme"`` (ValueError otherwise, ahead of the first step), ``pair_scores(pool="lme")`` then runs ONCE per group, the plan
+    is mined from it (the plan ``model.mine_pairs`` gives, bit for bit) and the same table is the teacher.  With ``prefilter_weight``
+    as well, prefilter_forward runs once per step and both terms read its maps.  At 0, the default, nothing new is called and the
+    step is unchanged, bit for bit."""
+    what = "train_epoch_mined"
+    rank_weight = _rank_weight(what, rank_weight, tau, gamma)
+    prefilter_weight = _prefilter_weight(what, prefilter_weight, tau, gamma)
+    distill_weight = _distill_weight(what, distill_weight, tau, gamma, gamma_teacher)
+    if distill_weight != 0.0 and mine_pool != "lme":
+        raise ValueError(f"{what}: distill_weight > 0 requires mine_pool='lme' (got {mine_pool!r}): the teacher is the pooled pair score")
+    from .moments import mine_pairs
     model.train()
     for g in groups:
         meter = _meter_for(meter, g)
         with torch.no_grad():
             videos = model.encode_videos(g["video_features"], g["video_mask"], g["length_mask"], g["moment_mask"], cell_counts=g.get("cell_counts"))
             queries = model.encode_queries(g["query_features"], g["query_mask"])
-            plan = model.mine_pairs(videos, queries, g["gt_video"], negatives, skip=skip, max_batch=max_batch, pool=mine_pool, tau=tau)
-        _pair_step(model, optimizer, g, plan, meter, rank_weight, tau, gamma, prefilter_weight)
+            teacher = None
+            if distill_weight != 0.0:
+                teacher = model.pair_scores(videos, queries, max_batch, pool="lme", tau=tau)
+                plan = mine_pairs(teacher, g["gt_video"], negatives, skip)
+            else:
+                plan = model.mine_pairs(videos, queries, g["gt_video"], negatives, skip=skip, max_batch=max_batch, pool=mine_pool, tau=tau)
+        _pair_step(model, optimizer, g, plan, meter, rank_weight, tau, gamma, prefilter_weight, distill_weight, teacher, gamma_teacher)
     metrics = meter.result()
     return metrics["loss"], metrics
 
 
-def train_epoch_prefilter(model, optimizer, groups, tau=0.1, gamma=0.1):
+def train_epoch_prefilter(model, optimizer, groups, tau=0.1, gamma=0.1, distill_weight=0.0, rank_weight=1.0, gamma_teacher=None, teacher=None,
+                          max_batch=64):
     """The first stage alone: per group ``prefilter_rank_loss`` over all its Q * V pairs, backward,
     optimizer.step -- a cheap pre-training or fine-tuning pass of the encoders and the three score heads in which no SMI layer runs
     (the layers' parameters receive no gradient: give the optimizer the parameters to move, or all of them -- FusedAdam skips a
     parameter without a gradient).  A group is train_epoch_pairs' dict; only the six model inputs and ``gt_video`` are read.  The
     losses and pair_rank_loss' stats are summed on the device; ONE host read at the end.  Returns ``(mean loss over the groups,
     in-group hit rate)``: the share of the counted queries whose own video scores at least as high as every other video of its
-    group by the first-stage score."""
-    _temperatures("train_epoch_prefilter", tau, gamma)
+    group by the first-stage score.
+
+    ``distill_weight`` > 0: the step's loss is ``rank_weight * prefilter_rank_loss + distill_weight *
+    prefilter_distill_loss`` over one prefilter_forward (a term at weight 0 is not computed; with ``rank_weight`` 0 gt_video is not
+    needed).  The teacher table is scored per group under torch.no_grad() by ``teacher`` -- another SMIN with the model's T and L;
+    None: the model itself, with its current parameters -- through encode_videos, encode_queries and ``pair_scores(max_batch,
+    pool="lme", tau=tau)``: a full-model scoring pass over the group's Q * V pairs.  pair_distill_loss' stats are summed on the
+    device with the others, and the one host read stays.  Returns then ``(mean loss, hit rate, agree rate)``: the last the share of
+    the counted queries whose best video by the teacher is their best by the first stage.  Negative or non-finite weights and bad
+    temperatures raise ValueError ahead of the first step."""
+    what = "train_epoch_prefilter"
+    rank_weight = _rank_weight(what, rank_weight, tau, gamma)
+    distill_weight = _distill_weight(what, distill_weight, tau, gamma, gamma_teacher)
+    if rank_weight == 0.0 and distill_weight == 0.0:
+        raise ValueError(f"{what}: rank_weight and distill_weight are both 0: there is no loss")
+    scorer = model if teacher is None else teacher
+    if distill_weight != 0.0 and (getattr(scorer, "T", None), getattr(scorer, "L", None)) != (model.T, model.L):
+        raise ValueError(f"{what}: the teacher must be a SMIN with the model's T = {model.T} and L = {model.L}")
     model.train()
-    total = stats = None
+    total = None
+    stats = {}
     n = 0
     for g in groups:
+        table = None
+        if distill_weight != 0.0:
+            with torch.no_grad():
+                videos = scorer.encode_videos(g["video_features"], g["video_mask"], g["length_mask"], g["moment_mask"], cell_counts=g.get("cell_counts"))
+                table = scorer.pair_scores(videos, scorer.encode_queries(g["query_features"], g["query_mask"]), max_batch, pool="lme", tau=tau)
         optimizer.zero_grad()
-        loss, st, _ = prefilter_rank_loss(model, g, tau, gamma, return_stats=True)
+        loss, *st = _first_stage_terms(what, model, g, tau, gamma, rank_weight, distill_weight, table, gamma_teacher)
         loss.backward()
         optimizer.step()
         total = loss.detach().clone() if total is None else total + loss.detach()
-        stats = st.clone() if stats is None else stats + st
+        for k, v in zip(("rank", "distill"), st):
+            if v is not None:
+                stats[k] = v.clone() if k not in stats else stats[k] + v
         n += 1
     if n == 0:
-        raise ValueError("train_epoch_prefilter: no group")
-    loss_sum, counted, hits = torch.cat([total.reshape(1), stats.reshape(2)]).tolist()          # the one host read
-    return loss_sum / n, (hits / counted if counted else 0.0)
+        raise ValueError(f"{what}: no group")
+    zero = total.new_zeros(2)
+    loss_sum, counted, hits, kept, agree = torch.cat([total.reshape(1), stats.get("rank", zero), stats.get("distill", zero)]).tolist()   # the one host read
+    rates = (loss_sum / n, hits / counted if counted else 0.0)
+    return rates if distill_weight == 0.0 else rates + (agree / kept if kept else 0.0,)
 
 
 def eval_epoch(model, batches, meter=None):
