@@ -68,7 +68,8 @@ extern "C" {
  * across shards -- smin_search_merge_weighted and smin_span_search_merge_weighted (shard lists that carry their unweighted scores,
  * merged under the video weights and ranks of all the shards' videos); a listwise soft-target loss over a pair plan --
  * smin_pair_distill_fwd and smin_pair_distill_ws_bytes (a query's softmax over its pair scores pulled towards a teacher's, through
- * smin_pair_rank_bwd) */
+ * smin_pair_rank_bwd); the window plan of a pruned window search -- smin_window_expand (each query's surviving videos expanded to the
+ * (query, window) list and its group pointers on the device) */
 #define SMIN_HIP_ABI_VERSION 2
 
 int smin_abi_version(void);
@@ -1196,6 +1197,28 @@ int smin_prefilter_maps_bwd(void* stream, const float* dpm0, const float* dps0, 
  * Limits.  Q >= 1, 1 <= V <= 0x7fff0000, M >= 1.  Determinism.  The same bits every run.
  * Rejection.  A nonzero status before the launch, the outputs untouched, for a size out of range or a NULL pointer. */
 int smin_prefilter_select(void* stream, const int32_t* pair_rank, int Q, int V, int M, int32_t* sel_video, int32_t* sel_query);
+
+/* smin_window_expand (csrc/window_prune.hip): the (query, window) plan of a pruned window search -- each query's
+ * surviving videos expanded to their windows, as SMIN.search_windows expands host pairs sorted by (query, video).  Three launches of
+ * workgroups of 256, integers only: a scan of each query's Ms window counts in tiles of 256 (one workgroup per query), a scan of the Q
+ * totals in tiles (one workgroup), and the fill (one workgroup per group and ceil(cap / 256) for the padding).  No workgroup waits on
+ * another; no atomics, plain stores; no workspace; no host read; capturable.
+ * Inputs.  sel_video [Q][Ms] int32: smin_prefilter_select's output, ascending per query; an entry outside [0, V), -1 included, is an
+ *   empty group.  video_ptr [V + 1] int64: video v owns windows video_ptr[v] .. video_ptr[v + 1] of a bank of W windows (a pointer
+ *   outside [0, W] or below its predecessor is clamped: every window written is a window of the bank).  cap: the slots of the lists.
+ * Outputs, every element written.  group_ptr [Q Ms + 1] int64: group g = q Ms + j, the windows of video sel_video[q][j] in start order,
+ *   owns slots group_ptr[g] .. group_ptr[g + 1]; the groups in (query, video) order.  win_index [cap], win_query [cap] int32: slot s <
+ *   total holds its window, as a global window of the bank, and its query; every slot in [total, cap) holds (0, 0), a real window and
+ *   a real query that no group owns.  total [1] int64: the number of real slots, NOT clamped.  total > cap: nothing is written at or
+ *   past cap, and every group_ptr entry is clamped to cap (the groups behind own nothing).  group_ptr and total are int64 because
+ *   smin_merge_window_moments reads its pair_ptr as int64 (smin_group_pool's int32 copy is made only with the video-level options) and
+ *   because Q Ms W passes 2^31 long before cap does.
+ * Limits.  Q, Ms, V >= 0, Q Ms <= 0x7f000000, 0 <= W < 2^31, 0 <= cap < 2^31; Ms, Q and a video's window count are not limited to a
+ *   tile.  Q Ms == 0: nothing is launched and nothing written.  Determinism.  The same bits every run.
+ * Rejection.  A nonzero status before any launch, the outputs untouched, for a size out of range or a NULL pointer (win_index and
+ *   win_query may be NULL where cap == 0). */
+int smin_window_expand(void* stream, const int32_t* sel_video, const int64_t* video_ptr, int Q, int Ms, int V, int64_t W, int64_t cap,
+                       int64_t* group_ptr, int32_t* win_index, int32_t* win_query, int64_t* total);
 
 /* ---- the corpus-wide first-stage cut over shards (csrc/prefilter_fold.hip): smin_prefilter_select's cut of one bank
  * of all the videos, kept as a running best-M per query while the corpus' shards stream past.  wave64, workgroups of 256; no atomics,

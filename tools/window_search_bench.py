@@ -15,7 +15,13 @@ smin_corpus_span_topk back to back between two events, divided by 50 -- against 
     python tools/window_search_bench.py [--calls 100] [--warmup 5] [--block 10] [--runs 2] [--shapes tacos_yml,anet_yml] [--no-kernel]
 Prints one JSON line per shape and run -- the median and the 10-90 % spread of each side in microseconds, the time to build the banks,
 each side's peak device memory over one call (and over the build) in bytes above what was allocated before it -- and one per kernel
-shape and run."""
+shape and run.
+
+With ``--prefilter M[,M...]`` the sides are instead: "banks", the search over all pairs as above; "pruned_M",
+search_windows(prefilter=M) (``--trim``: trim=True) for each M; "first_stage", prefilter_videos alone over the Q x windows pairs; and
+"expand", smin_window_expand's three launches alone (50 calls back to back between two events, divided by 50) at the largest M's
+shape.  ``--corpus unequal`` replaces the corpus by 8 videos of 1, 2, 3, 5, 8, 13, 25 and 57 windows; the line then carries each M's
+``cap`` and ``total``.  The loop side (b) and the ranking kernel are not run in this mode."""
 import argparse
 import json
 import os
@@ -32,7 +38,10 @@ SHAPES = {   # T, L, C, D, dl, layers, Din, Nq, H  (BASELINE.json configs)
     "tacos_yml": (128, 32, 4, 512, 128, 3, 4096, 14, 256),
     "anet_yml": (128, 64, 4, 512, 128, 3, 500, 20, 256),
 }
-ROWS = (4.0, 3.9, 4.15, 3.75, 4.0, 4.4, 3.5, 4.0)       # a video's rows in units of T: 7 or 8 windows each at window T, stride T / 2
+CORPORA = {  # a video's rows in units of T, at window T and stride T / 2
+    "equal": (4.0, 3.9, 4.15, 3.75, 4.0, 4.4, 3.5, 4.0),                 # 7 or 8 windows each
+    "unequal": (1.0, 1.5, 2.0, 3.0, 4.5, 7.0, 13.0, 29.0),               # 1, 2, 3, 5, 8, 13, 25 and 57 windows
+}
 
 
 def summary(v):
@@ -86,6 +95,43 @@ def span_lists(Q, per_query, kv, dev, seed):
     return [t.to(dev) for t in (span, score, window, cell, count, video, ptr)]
 
 
+def pruned_mode(args, A, m, banks, side_a, prefilters, name, n_windows):
+    """--prefilter: the search over all pairs against search_windows(prefilter=M), the first stage alone and the expand launches alone"""
+    wb, qb = banks
+    Q, V, mb, k, REP = len(qb), wb.n_videos, args.max_batch, args.k, 50
+    sides, plan = {"banks": side_a}, {}
+    for M in prefilters:
+        sides[f"pruned_{M}"] = lambda M=M: m.search_windows(wb, qb, k=k, max_batch=mb, prefilter=M, trim=args.trim)
+        r = sides[f"pruned_{M}"]()
+        plan[str(M)] = {"cap": A.survivor_window_capacity(wb.video_ptr, min(M, V), Q), "total": int(r["window_pairs"])}
+    M = max(prefilters)
+    sides["first_stage"] = lambda: m.prefilter_videos(wb, qb, M)
+    sel = m.prefilter_videos(wb, qb, M)["video"].to(torch.int32)
+    cap = plan[str(M)]["cap"]
+    want = A.expand_survivor_windows_torch(sel, wb.video_ptr_d, len(wb), cap)
+    got = A.expand_survivor_windows(sel, wb.video_ptr_d, len(wb), cap)
+    assert all(torch.equal(g, w) for g, w in zip(got, want)), "the kernel and its restatement disagree"
+
+    def expand():                                                                          # REP calls back to back: the queue hides the host
+        for _ in range(REP):
+            A.expand_survivor_windows(sel, wb.video_ptr_d, len(wb), cap)
+
+    for _ in range(args.warmup):
+        for fn in sides.values():
+            fn()
+        expand()
+    torch.cuda.synchronize()
+    for run in range(args.runs):
+        us = alternate(sides, args.calls, args.block)
+        us["expand"] = [v / REP for v in alternate({"expand": expand}, max(args.calls // 5, 10), args.block)["expand"]]
+        res = {s: summary(v) for s, v in us.items()}
+        print(json.dumps({"shape": name, "run": run, "corpus": args.corpus, "Q": Q, "V": V, "windows": n_windows, "query_window_pairs": Q * n_windows,
+                          "windows_per_video": (wb.video_ptr[1:] - wb.video_ptr[:-1]).tolist(), "max_batch": mb, "k": k, "trim": args.trim,
+                          "gemm_mode": A.get_gemm_mode(), "calls": args.calls, "plan": plan, "us": res,
+                          "pruned_over_banks": {str(M): round(res[f"pruned_{M}"]["median"] / res["banks"]["median"], 3) for M in prefilters}}),
+              flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--Q", type=int, default=16)
@@ -97,7 +143,12 @@ def main():
     ap.add_argument("--runs", type=int, default=2)
     ap.add_argument("--shapes", default="tacos_yml,anet_yml")
     ap.add_argument("--no-kernel", action="store_true")
+    ap.add_argument("--prefilter", default="", help="M[,M...]: time search_windows(prefilter=M) against the search over all pairs")
+    ap.add_argument("--trim", action="store_true", help="with --prefilter: trim=True (one host read per call)")
+    ap.add_argument("--corpus", choices=sorted(CORPORA), default="equal")
     args = ap.parse_args()
+    prefilters = [int(x) for x in args.prefilter.split(",") if x]
+    ROWS = CORPORA[args.corpus]
     import models
     from oracle import smin_oracle as O
     from tests import helpers as H
@@ -139,6 +190,11 @@ def main():
             span = r["span"].reshape(Q, V * k, 2).gather(1, top.indices.unsqueeze(-1).expand(Q, k, 2))
             return video_of.gather(1, top.indices), span, top.values
 
+        if prefilters:
+            pruned_mode(args, A, m, banks, side_a, prefilters, name, n_windows)
+            del m, banks, raw, qf, qm, qf_pairs, qm_pairs
+            torch.cuda.empty_cache()
+            continue
         sides = {"banks": side_a, "loop": side_b}
         for _ in range(args.warmup):
             for fn in sides.values():
@@ -161,7 +217,7 @@ def main():
                               "max_score_difference": agree}), flush=True)
         del m, banks, raw, qf, qm, qf_pairs, qm_pairs, a, b
         torch.cuda.empty_cache()
-    if args.no_kernel:
+    if args.no_kernel or prefilters:
         return
     L_, REP = A._lib, 50
     for Qk, per_query, kv, K, torch_calls in ((16, 8, 5, 5, 20), (1024, 64, 5, 25, 3)):

@@ -34,6 +34,7 @@ from .moments import corpus_topk, corpus_topk_torch, merge_search, merge_search_
 from .moments import pair_pool, pair_pool_torch, group_pool, group_pool_torch, rank_videos, rank_videos_torch  # noqa: F401
 from .moments import reweight_moments, reweight_moments_torch  # noqa: F401
 from .moments import prefilter_scores, prefilter_scores_torch, prefilter_select, prefilter_select_torch, prefilter_maps  # noqa: F401
+from .moments import expand_survivor_windows, expand_survivor_windows_torch, survivor_window_capacity  # noqa: F401
 from .moments import prefilter_fold, prefilter_fold_torch, survivors_admit, survivors_admit_torch, prefilter_gt_rank, prefilter_gt_rank_torch  # noqa: F401
 from .moments import bank_encode, bank_encode_torch, bank_decode, bank_decode_torch, BANK_STORAGES  # noqa: F401
 from .moments import merge_search_weighted, merge_search_weighted_torch  # noqa: F401

@@ -80,6 +80,24 @@ __device__ __forceinline__ int block_scan_flag(bool flag, int* red, int& total)
     total = (red[0] + red[1]) + (red[2] + red[3]);
     return base + before;
 }
+// exclusive prefix of a non-negative 64-bit count over the workgroup's threads in ascending order, and its total: a shift-and-add scan
+// inside each wave, one LDS word per wave (red: 4 words), then the waves in front
+__device__ __forceinline__ long long block_scan_count(long long v, long long* red, long long& total)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    long long incl = v;
+    for (int o = 1; o < 64; o <<= 1) {
+        const long long x = __shfl_up(incl, o);
+        if (lane >= o) incl += x;
+    }
+    __syncthreads();                                             // (the previous scan's reads of red are done)
+    if (lane == 63) red[wave] = incl;
+    __syncthreads();
+    long long base = 0;
+    for (int k = 0; k < 4; ++k) base += k < wave ? red[k] : 0;
+    total = (red[0] + red[1]) + (red[2] + red[3]);
+    return base + (incl - v);
+}
 // fp64 sum in a fixed order -- the butterfly, then the four wave sums as (w0 + w1) + (w2 + w3), no contraction --; valid in thread 0.
 // No leading barrier: a kernel calls it once per `red`.
 __device__ __forceinline__ double block_sum_f64_fixed(double acc, double* red)

@@ -1112,6 +1112,72 @@ def prefilter_select_torch(pair_rank, M):
     return video, query
 
 
+# ---------------------------------------------------------------- the window plan of a pruned window search
+def _expand_check(what, sel_video, video_ptr, W, cap):
+    if sel_video.dim() != 2 or sel_video.shape[0] < 1 or sel_video.shape[1] < 1:
+        raise ValueError(f"{what}: sel_video must be (Q, Ms) with Q, Ms >= 1, got {tuple(sel_video.shape)}")
+    if video_ptr.dim() != 1 or video_ptr.shape[0] < 1:
+        raise ValueError(f"{what}: video_ptr must be (V + 1,)")
+    require_ints(what, ("W", W, 0, 2 ** 31 - 1), ("cap", cap, 0, 2 ** 31 - 1))
+    Q, Ms = sel_video.shape
+    if Q * Ms > 0x7f000000:
+        raise ValueError(f"{what}: {Q} queries of {Ms} surviving videos exceed the {0x7f000000} groups of one call")
+    return Q, Ms, video_ptr.shape[0] - 1
+
+
+def expand_survivor_windows(sel_video, video_ptr, W, cap):
+    """The (query, window) plan of a pruned window search (include/smin_hip.h, smin_window_expand): each query's surviving videos
+    ``sel_video (Q, Ms)`` (prefilter_select's, ascending per query; an entry outside [0, V) is an empty group) expanded to their windows
+    by ``video_ptr (V + 1,)`` int64, a WindowBank's ``video_ptr_d`` over its ``W`` windows, into lists of ``cap`` slots.  Returns
+    ``(group_ptr (Q * Ms + 1,) int64, win_index (cap,) int32, win_query (cap,) int32, total (1,) int64)``: group ``q * Ms + j`` owns the
+    slots of video ``sel_video[q, j]``'s windows in start order, slots ``>= total`` hold window 0 and query 0 (padding the model can
+    score and no group owns), ``total`` is not clamped; with ``total > cap`` nothing lies past ``cap`` and every ``group_ptr`` entry is
+    clamped to it.  HIP tensors only; three launches; no host synchronisation."""
+    _require_hip(sel_video, "expand_survivor_windows")
+    Q, Ms, V = _expand_check("expand_survivor_windows", sel_video, video_ptr, W, cap)
+    dev = sel_video.device
+    sel, vp = sel_video.to(torch.int32).contiguous(), video_ptr.to(torch.int64).contiguous()
+    group_ptr = torch.empty((Q * Ms + 1,), dtype=torch.int64, device=dev)
+    win_index = torch.empty((int(cap),), dtype=torch.int32, device=dev)
+    win_query = torch.empty((int(cap),), dtype=torch.int32, device=dev)
+    total = torch.empty((1,), dtype=torch.int64, device=dev)
+    with torch.cuda.device(dev):
+        call("smin_window_expand", stream(), ptr(sel), ptr(vp), Q, Ms, V, int(W), int(cap), ptr(group_ptr), ptr(win_index) if cap else None,
+             ptr(win_query) if cap else None, ptr(total))
+    return group_ptr, win_index, win_query, total
+
+
+def expand_survivor_windows_torch(sel_video, video_ptr, W, cap):
+    """``expand_survivor_windows`` as plain torch ops on any device: the tests' restatement (no host read)."""
+    Q, Ms, V = _expand_check("expand_survivor_windows_torch", sel_video, video_ptr, W, cap)
+    dev = sel_video.device
+    sel, vp = sel_video.to(torch.int64).reshape(-1), video_ptr.to(torch.int64)
+    inside = (sel >= 0) & (sel < V)
+    v = sel.clamp(0, max(V - 1, 0))
+    lo = vp[v].clamp(0, W)
+    hi = torch.minimum(torch.maximum(vp[(v + 1).clamp(max=V)], lo), torch.full_like(lo, W))
+    n = torch.where(inside, hi - lo, torch.zeros_like(lo))
+    ptr_ = torch.cat([n.new_zeros(1), n.cumsum(0)])
+    total = ptr_[-1:].clone()
+    slot = torch.arange(int(cap), dtype=torch.int64, device=dev)
+    g = torch.searchsorted(ptr_[1:].contiguous(), slot, right=True).clamp(max=Q * Ms - 1)         # the group whose slots hold s, for s < total
+    real = slot < total
+    win_index = torch.where(real, lo[g] + (slot - ptr_[g]), torch.zeros_like(slot)).to(torch.int32)
+    win_query = torch.where(real, g // Ms, torch.zeros_like(slot)).to(torch.int32)
+    return ptr_.clamp(max=int(cap)), win_index, win_query, total
+
+
+def survivor_window_capacity(video_ptr, Ms, Q):
+    """The slots ``expand_survivor_windows`` needs in the worst case, host arithmetic on a WindowBank's host ``video_ptr``: ``Q`` times the
+    sum of the ``Ms`` largest per-video window counts -- no query's ``Ms`` survivors own more.  Exact where all videos have one count."""
+    vp = host_array(video_ptr)
+    require_ints("survivor_window_capacity", ("Ms", Ms, 0, 2 ** 31 - 1), ("Q", Q, 0, 2 ** 31 - 1))
+    if vp.ndim != 1 or vp.shape[0] < 1:
+        raise ValueError("survivor_window_capacity: video_ptr must be (V + 1,)")
+    counts = np.sort(np.maximum(vp[1:] - vp[:-1], 0))[::-1]
+    return int(Q) * int(counts[:int(Ms)].sum())
+
+
 # ---------------------------------------------------------------- the corpus-wide first-stage cut over shards (INTEGRATION.md 3x)
 PREFILTER_FOLD_MAX_M = 2048         # csrc/prefilter_fold.hip: a query's slots and their free list stay in LDS
 

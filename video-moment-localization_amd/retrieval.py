@@ -2,7 +2,7 @@
 any length over overlapping windows (``localize_windows``) and of a corpus encoded once (``encode_videos`` / ``encode_queries`` ->
 ``score_pairs`` / ``search``, pruned by a first-stage score from the banks alone with ``prefilter_videos`` / ``search(prefilter=M)`` and, for a corpus that comes in
 shards, ``new_survivors`` / ``fold_survivors`` / ``search_survivors``; a corpus
-of videos of any length: ``encode_windows`` -> ``search_windows``), and the training counterpart
+of videos of any length: ``encode_windows`` -> ``search_windows``, pruned the same way with ``search_windows(prefilter=M)``), and the training counterpart
 of ``score_pairs``, ``forward_pairs`` over (video, query) pairs that share their
 encoders: host code around the library's kernels and the model's own ``score`` / ``forward``, which ``modules.SMIN`` inherits
 through the stateless mixin ``_Retrieval``."""
@@ -17,7 +17,7 @@ from .feeder import build_masks_hip, cell_count
 from .functional import attn_maps_gather
 from .moments import (MAX_K, PREFILTER_FOLD_MAX_M, bank_decode, bank_encode, bank_storage, require_storage, prefilter_fold, prefilter_gt_rank, survivors_admit, _pair_pool_into, _temperature, _top_moments_into, _video_weight, corpus_span_topk, corpus_span_topk_torch, corpus_topk,
                       corpus_topk_torch, group_pool, merge_window_moments, merge_window_moments_torch, mine_pairs, prefilter_maps, prefilter_scores, prefilter_select,
-                      rank_videos, reweight_moments,
+                      rank_videos, reweight_moments, expand_survivor_windows, survivor_window_capacity,
                       reweight_moments_torch, search_times, top_moments, top_moments_torch, window_times)
 from .sampling import MAX_ROWS, MODES, sample_windows, window_plan
 
@@ -871,8 +871,8 @@ class _Retrieval:
         o = _Options("search", k, k_video, max_batch)
         _require_banks("search", videos, queries)
         if isinstance(videos, WindowBank):
-            raise ValueError("search: prefilter takes a VideoBank (pruning a window search is out of scope: the surviving windows' list has a "
-                             "data-dependent length)")
+            raise ValueError("search: prefilter takes a VideoBank (a window search is pruned by search_windows(prefilter=M), which builds the "
+                             "surviving windows' list on the device)")
         o.duration(duration, len(videos))
         if video_weight is not None or max_videos is not None:
             tau = o.video_level(video_weight, max_videos, tau, n_videos, gt_video, len(queries)).tau
@@ -1120,7 +1120,7 @@ class _Retrieval:
         return r
 
     def search_windows(self, windows, queries, pairs=None, k=5, k_video=None, k_window=None, nms_thresh=0.5, duration=None, max_batch=64,
-                       video_weight=None, max_videos=None, tau=0.1, n_videos=None, gt_video=None, carry=False):
+                       video_weight=None, max_videos=None, tau=0.1, n_videos=None, gt_video=None, prefilter=None, trim=False, carry=False):
         """Which video, and where, over videos of any length: the k best moments of each of the Q queries of a QueryBank over the videos
         of a WindowBank, at the windows' native resolution.
 
@@ -1144,7 +1144,29 @@ class _Retrieval:
 
         ``carry=True``: as ``search`` takes it (``pairs`` must be None), for moments.merge_search_windows_weighted:
         ``raw (Q, k)`` holds the bits of the entry's score in its group's merge_window_moments list, matched by (video, window, cell), and
-        ``pair_score`` / ``pair_cells (Q, V)`` are the group_pool outputs."""
+        ``pair_score`` / ``pair_cells (Q, V)`` are the group_pool outputs.
+
+        ``prefilter=M`` (None: everything above, untouched) prunes the videos before the model runs, as ``search(prefilter=M)`` does
+        (INTEGRATION.md 3za): ``prefilter_videos`` pools the first-stage scores of every (query, window) into per-video scores and keeps
+        each query's best ``Ms = min(M, V)`` videos, moments.expand_survivor_windows turns them into the (query, window) list and its group
+        pointers on the device, and the chunk loop, the merge and the ranking above run over that list: the model scores the windows of
+        Q * Ms videos instead of Q * V.  The list's length depends on which videos survive, so it is built at a capacity the host can
+        bound without a read -- ``cap`` = moments.survivor_window_capacity: Q times the sum of the Ms largest per-video window counts --
+        and the slots behind the real ones hold window 0 and query 0.  ``trim=False``: no host read and no synchronisation; the chunk
+        loop runs over all ``cap`` slots, so THE MODEL ALSO SCORES THE PADDING (no group owns it; it costs time, not results): nothing
+        where every video has one window count, up to most of the work where a few videos are much longer than the rest.
+        ``trim=True`` reads the real length once (ONE small host read, a synchronisation) and runs the loop over the real slots only:
+        for corpora whose window counts are very unequal.  Each chunk's valid-cell count follows ``search(prefilter=M)``'s rule on the
+        windows' ``cell_counts``.  ``video_weight`` / ``max_videos`` / ``gt_video`` / ``tau`` act on the surviving pairs (``tau`` is also
+        the first stage's temperature).  With ``pairs`` or ``carry=True``: ValueError.  The result gains ``prefilter_video (Q, Ms)``
+        int64 ascending, ``prefilter_score (Q, V)``, ``prefilter_gt_rank (Q,)`` int32 and ``window_pairs (1,)`` int64, the real slots
+        (with ``cap`` it tells how much padding was scored).  What the pruning loses is not bounded."""
+        if prefilter is not None:
+            if pairs is not None or carry:
+                raise ValueError("search_windows: prefilter takes pairs=None and carry=False (it chooses the pairs itself, and a carried merge "
+                                 "needs every video's pooled score)")
+            return self._search_windows_prefiltered(windows, queries, prefilter, trim, k, k_video, k_window, nms_thresh, duration, max_batch,
+                                                    video_weight, max_videos, tau, n_videos, gt_video)
         if carry and pairs is not None:
             raise ValueError("search_windows: carry=True takes pairs=None, every query against every video of the bank (a merge re-ranks all the "
                              "shard's videos)")
@@ -1160,20 +1182,59 @@ class _Retrieval:
             wi_d, wq_d, gp_d, vid_d, qp_d, nr_d, gt_d = _upload([p["wi"], p["wq"], p["group_ptr"], p["vi"], p["query_ptr"], windows.n_rows, o.gt],
                                                                 np.int64, dev)
             wi32, wq32 = wi_d.to(torch.int32), wq_d.to(torch.int32)
-            # the groups' lists as the kernels read them, cast where each mode has always cast them -- in front of the loop with the
-            # video-level options, behind the merge without --: the device sees the same launches in the same order
-            narrow = lambda: (vid_d.to(torch.int32), qp_d.to(torch.int32))
-            groups = narrow() if o.ranked else None
-            lists, pools = self._pair_chunks(windows, queries, wi32, wq32, max_batch, host=(p["wi"], p["wq"]), cut=(o.k_window, nms_thresh),
-                                             tau=o.tau if o.ranked else None)
-            g = merge_window_moments(lists["idx"], lists["score"], lists["count"], windows.start.index_select(0, wi_d),
-                                     windows.len.index_select(0, wi_d), gp_d, self.T, self.L, k=o.k_video, nms_thresh=nms_thresh)
-            pooled = group_pool(pools[1], pools[2], gp_d, o.tau) if o.ranked else None
-            r = _rank_lists(o, g, *(groups or narrow()), gt_d, pooled)
+            r, g, pooled = self._window_search_tail(o, windows, queries, wi_d, wi32, wq32, gp_d, lambda: (vid_d.to(torch.int32), qp_d.to(torch.int32)),
+                                                    gt_d, nms_thresh, max_batch, host=(p["wi"], p["wq"]))
             if carry:
                 r["raw"] = _carry_raw(r["video"], (r["window"].unsqueeze(-1), r["cell"]), (g["window"].unsqueeze(-1), g["cell"]), g["score"],
                                       g["count"], V)
                 r["pair_score"], r["pair_cells"] = pooled[0].reshape(Q, V), pooled[1].reshape(Q, V)
+        return self._window_result(r, duration, nr_d)
+
+    def _window_search_tail(self, o, windows, queries, rows_d, wi32, wq32, gp_d, narrow, gt_d, nms_thresh, max_batch, host=None, cell=None):
+        """What every window search runs behind its plan: the chunk loop over the (query, window) list ``wi32`` / ``wq32`` (int32, on the
+        device; ``host`` / ``cell`` as ``_pair_chunks`` takes them), one merge_window_moments over the groups of ``gp_d`` (int64; slots no
+        group owns are scored and dropped) with ``start`` / ``len`` gathered by ``rows_d`` (the list as an index), group_pool with the
+        video-level options, and the ranking.  ``narrow() -> (video, query_ptr)``: the groups' lists as int32, formed where each mode has
+        always formed them -- in front of the loop with the video-level options, behind the merge without --, so the device sees the same
+        launches in the same order.  Returns ``(result, the groups' merged lists, the groups' pooled (score, cells) or None)``.  No host
+        read."""
+        groups = narrow() if o.ranked else None
+        lists, pools = self._pair_chunks(windows, queries, wi32, wq32, max_batch, host=host, cell=cell, cut=(o.k_window, nms_thresh),
+                                         tau=o.tau if o.ranked else None)
+        g = merge_window_moments(lists["idx"], lists["score"], lists["count"], windows.start.index_select(0, rows_d),
+                                 windows.len.index_select(0, rows_d), gp_d, self.T, self.L, k=o.k_video, nms_thresh=nms_thresh)
+        pooled = group_pool(pools[1], pools[2], gp_d, o.tau) if o.ranked else None
+        return _rank_lists(o, g, *(groups or narrow()), gt_d, pooled), g, pooled
+
+    def _search_windows_prefiltered(self, windows, queries, M, trim, k, k_video, k_window, nms_thresh, duration, max_batch, video_weight,
+                                    max_videos, tau, n_videos, gt_video):
+        """``search_windows(prefilter=M)``: prefilter_videos, the device-built window plan (moments.expand_survivor_windows) at the host's
+        capacity bound, then search_windows' own tail."""
+        what = "search_windows"
+        o = _Options(what, k, k_video, max_batch, k_window, windows=True)
+        if not isinstance(windows, WindowBank) or not isinstance(queries, QueryBank):
+            raise ValueError(f"{what}: windows is a WindowBank (encode_windows) and queries a QueryBank (encode_queries)")
+        require_ints(what, ("prefilter", M, 1, 2 ** 31 - 1))
+        Q, V, W, dev = len(queries), windows.n_videos, len(windows), windows.device
+        o.duration(duration, V)
+        if video_weight is not None or max_videos is not None:
+            tau = o.video_level(video_weight, max_videos, tau, n_videos, gt_video, Q).tau
+        Ms = min(int(M), V)
+        cap = survivor_window_capacity(windows.video_ptr, Ms, Q)
+        if cap * o.k_window >= 2 ** 31:
+            raise ValueError(f"{what}: {cap} (query, window) slots of {o.k_window} moments exceed the merges' 2**31 candidates")
+        pf = self.prefilter_videos(windows, queries, int(M), tau, gt_video)
+        with torch.no_grad(), torch.cuda.device(dev):
+            nr_d, gt_d = _upload([windows.n_rows, o.gt], np.int64, dev)
+            sel = pf["video"].to(torch.int32)
+            gp_d, wi32, wq32, total = expand_survivor_windows(sel, windows.video_ptr_d, W, cap)
+            if trim:
+                n = min(int(total.item()), cap)                                       # the one host read of trim=True
+                wi32, wq32 = wi32[:n], wq32[:n]
+            narrow = lambda: (sel.reshape(-1), torch.arange(Q + 1, dtype=torch.int32, device=dev) * Ms)
+            r, _, _ = self._window_search_tail(o, windows, queries, wi32, wi32, wq32, gp_d, narrow, gt_d if o.gt.size else None, nms_thresh,
+                                               max_batch, cell=windows.cell_count)
+        r.update(prefilter_video=pf["video"], prefilter_score=pf["score"], prefilter_gt_rank=pf["gt_rank"], window_pairs=total)
         return self._window_result(r, duration, nr_d)
 
     def search_windows_torch(self, windows, queries, raw=None, pairs=None, k=5, k_video=None, k_window=None, nms_thresh=0.5, duration=None,

@@ -970,7 +970,7 @@ test_model_corpus.__test__ = False
 
 def test_model_corpus_windows(model, raw, lengths, queries, gt_video, gt_times, duration, meter=None, *, window=None, stride=None, k=25,
                               k_video=5, k_window=None, nms_thresh=0.5, max_batch=64, video_weight=None, max_videos=None, tau=0.1,
-                              video_meter=None):
+                              video_meter=None, prefilter=None, trim=False):
     """The test loop of corpus search over videos of any length: VCMR R@n, IoU=m, VR R@n and mIoU of
     ``model.search_windows``, with no host read beside the meter's one at the end.  ``raw (R, Din)`` / ``lengths``: the V videos' rows
     back to back and their row counts, as ``encode_windows`` takes them; ``queries``: a dict with ``query_features`` and
@@ -984,7 +984,13 @@ def test_model_corpus_windows(model, raw, lengths, queries, gt_video, gt_times, 
     ``video_weight`` / ``max_videos`` / ``tau``: ``model.search_windows``' video-level options; ``video_meter``: a
     meter.VideoRankMeter, updated with the search's ``gt_rank`` (given alone, the search runs at ``video_weight=0.0``: the same moments'
     list, plus the video ranking).  This loop searches one bank, so there is no shard limit here; the
-    sharded loop (``test_model_corpus_window_shards``) takes none of these."""
+    sharded loop (``test_model_corpus_window_shards``) takes none of these.
+
+    ``prefilter`` / ``trim``: ``search_windows(prefilter=M, trim=...)`` (None, the default: the loop above as it
+    is) -- the full model scores the windows of each query's best ``prefilter`` videos by the first-stage score, and the metrics are
+    those of that list.  ``video_weight`` / ``max_videos`` both None then leave the video-level options off, and ``video_meter`` is
+    updated with ``prefilter_gt_rank``, the FIRST stage's rank of each query's own video, as
+    ``test_model_corpus_prefiltered_shards`` feeds it.  ``trim=True`` adds its one host read."""
     what = "test_model_corpus_windows"
     gv, gt, Q = _corpus_loop_check(what, meter, k, k_video, queries, gt_video, gt_times)
     dur, V = host_array(duration, np.float64), host_array(lengths).shape[0]
@@ -993,11 +999,14 @@ def test_model_corpus_windows(model, raw, lengths, queries, gt_video, gt_times, 
     sent = _send_ground_truth(gv, None, dur, gt, queries["query_features"].device)        # before the search, which takes the durations
     bank, meter, dev = _corpus_loop_begin(model, queries, meter)
     windows = model.encode_windows(raw, lengths, window=window, stride=stride, max_batch=max_batch)
-    video_level, video_weight = _video_level(video_weight, max_videos, video_meter)
-    options = dict(video_weight=video_weight, max_videos=max_videos, tau=tau, gt_video=gv) if video_level else {}
+    if prefilter is not None:                                              # as test_model_corpus_prefiltered_shards sets its search up
+        options, rank = dict(video_weight=video_weight, max_videos=max_videos, tau=tau, gt_video=gv, prefilter=prefilter, trim=trim), "prefilter_gt_rank"
+    else:
+        video_level, video_weight = _video_level(video_weight, max_videos, video_meter)
+        options, rank = dict(video_weight=video_weight, max_videos=max_videos, tau=tau, gt_video=gv) if video_level else {}, "gt_rank"
     r = model.search_windows(windows, bank, k=k, k_video=k_video, k_window=k_window, nms_thresh=nms_thresh, duration=sent["duration"],
                              max_batch=max_batch, **options)
-    return _corpus_loop_end(what, model, r, meter, gv, gt, dur, dev, video_meter=video_meter, sent=sent)
+    return _corpus_loop_end(what, model, r, meter, gv, gt, dur, dev, video_meter=video_meter, rank=rank, sent=sent)
 
 
 test_model_corpus_windows.__test__ = False
