@@ -1,5 +1,7 @@
-"""SHA-256 of everything the one-node core computes, over the options and paths of csrc/torch_binding.cpp: a change of that file that is
-meant to move no bit is checked by running this tool on a build from before and a build from after and comparing the listings.
+"""SHA-256 of everything the torch extension's host code computes, over the options and paths of csrc/torch_binding.cpp and the headers it
+is made of (core_forward.h, core_backward.h, loss_nodes.h ...): the one-node core, scoring over fp32 and compact banks, the two
+pair-plan losses and a weighted corpus search.  A change of those files that is meant to move no bit is checked by running this tool on
+a build from before and a build from after and comparing the listings.
 
     python tools/core_digest.py [--root CHECKOUT] > listing.txt
 
@@ -133,10 +135,30 @@ def main():
     videos, queries = m.encode_videos(vb["video_features"], vb["video_mask"], vb["length_mask"], vb["moment_mask"]), m.encode_queries(qf, qm)
     for name, o in zip(("pm", "ps", "pe", "pa"), m.score_pairs(videos, queries, vi, qi)):
         emit("score_pairs", name, o)
+    for storage in ("bf16", "int8"):                            # the same pairs over a compact bank: codes, and for int8 the frames' scales
+        for name, o in zip(("pm", "ps", "pe", "pa"), m.score_pairs(videos.compact(storage), queries, vi, qi)):
+            emit("score_pairs " + storage, name, o)
     pair_rows = torch.tensor(vi, device=dev)                    # a pair's targets: its video's
     for counts in (None, videos.cell_counts):
         step("forward_pairs" + ("" if counts is None else " counts"), model(shape), b, rows=pair_rows,
              run=lambda mm: mm.forward_pairs(vb["video_features"], vb["video_mask"], qf, qm, vb["length_mask"], vb["moment_mask"], vi, qi, cell_counts=counts))
+    # the two losses over the pair plan, forward and backward, on forward_pairs' outputs (leaves here: the gradients are the losses' own)
+    plan = vml.PairPlan(vi, qi, 3, 4, dev, gt_video=[2, 1, 0, 0])
+    pair_mask = vb["moment_mask"].index_select(0, pair_rows)
+    with torch.no_grad():
+        scores = m.forward_pairs(vb["video_features"], vb["video_mask"], qf, qm, vb["length_mask"], vb["moment_mask"], vi, qi)[:3]
+    teacher = torch.linspace(-1.0, 1.0, len(vi), device=dev)
+    for case, term in (("pair_rank_loss", lambda *s: vml.pair_rank_loss(*s, pair_mask, plan, return_stats=True)),
+                       ("pair_distill_loss", lambda *s: vml.pair_distill_loss(*s, pair_mask, plan, teacher, gamma_teacher=0.2, return_stats=True))):
+        leaves = [s.detach().clone().requires_grad_(True) for s in scores]
+        out = term(*leaves)
+        out[0].backward()
+        for name, t in zip(("loss", "stats", "pair_score", "grad pm", "grad ps", "grad pe"), list(out) + [s.grad for s in leaves]):
+            emit(case, name, t)
+    # which video, and where: the video-level score folded into the ranking (rank_videos' pooled pair score)
+    for k, v in sorted(m.search(videos, queries, k=4, video_weight=7.5, max_videos=2, max_batch=5).items()):     # 12 pairs in three chunks
+        if torch.is_tensor(v):
+            emit("search video_weight", k, v)
     torch.cuda.synchronize()
 
 
