@@ -11,92 +11,22 @@ import pytest
 import torch
 
 from tests import helpers as H
+from tests.support.device import dev  # noqa: F401  (the module's device fixture)
+from tests.support.compare import _rel
+from tests.support.references import (
+    _attn_inputs, _layout_to, _ragged_mask, _smi_params, attn_core_ref, attn_form, word_side_ref, ALL_FORMS, WORD_PARAM_NAMES)
 
 FWD_TOL = 1e-5          # max |got - ref| / max |ref|, per output and case (as test_standalone_attention_classes_against_oracle)
 GRAD_TOL = 1e-4
 
 
 # ---------------------------------------------------------------- float64 restatements
-
-def attn_core_ref(chat, cells, C, Mq, uq, what, shat, qmask):
-    """The packed attention core (reference models.py:207-226, 252-266) in the layout of ContentAttnFn: chat [N*C, dl], cells
-    [N, 4] (b, i, j, m) sorted by sample, per-sample Mq / what [B, Nq, dl], uq / qmask [B, Nq], shat [B, dl].  For each cell of
-    sample b with rows X [C, dl] and flag m:
-        S = (X Mq_b^T + uq_b) / sqrt(dl);  S = S * qm;  S[qm == 0] = -1e9;  P = softmax over words
-        a = m (P what_b);  q = X * (a + shat_b);  A = m softmax_c(q q^T / sqrt(dl));  cc = m (A X);  ccmean = mean_c cc
-    Returns (cc [N*C, dl], ccmean [N, dl], S of every cell [N, C, Nq]); differentiable."""
-    N, dl = cells.shape[0], chat.shape[1]
-    X = chat.reshape(N, C, dl)
-    b_of = cells[:, 0].long()
-    m_of = cells[:, 3].to(chat.dtype)
-    ccs, Ss = [], []
-    for b in range(Mq.shape[0]):
-        sel = (b_of == b).nonzero().flatten()
-        if sel.numel() == 0:
-            continue
-        assert sel[-1] - sel[0] + 1 == sel.numel(), "cells must be sorted by sample"
-        Xb = X[sel[0]:sel[-1] + 1]
-        m = m_of[sel[0]:sel[-1] + 1].view(-1, 1, 1)
-        qm = qmask[b].view(1, 1, -1)
-        S = (Xb @ Mq[b].t() + uq[b]) / math.sqrt(dl)
-        Ss.append(S)
-        S = (S * qm).masked_fill(qm == 0, -1e9)
-        P = torch.softmax(S, dim=-1)
-        a = m * (P @ what[b])
-        q = Xb * (a + shat[b])
-        A = m * torch.softmax(q @ q.transpose(1, 2) / math.sqrt(dl), dim=-1)
-        ccs.append(m * (A @ Xb))
-    cc = torch.cat(ccs) if ccs else chat.new_zeros((0, C, dl))
-    return cc.reshape(N * C, dl), cc.mean(dim=1), (torch.cat(Ss) if Ss else chat.new_zeros((0, C, Mq.shape[1])))
-
-
-WORD_PARAM_NAMES = ("linear_w_hat.weight", "linear_w_hat.bias", "linear_s_hat.weight", "linear_s_hat.bias",
-                    "attn_layer.W_k.weight", "attn_layer.W_k.bias", "attn_layer.W_q.weight", "attn_layer.W_q.bias")
-
-
-def word_side_ref(fw, fs, qmask, params):
-    """The five word-side operands of every layer (csrc/word_prep.hip header), 8 parameters per layer in WordPrepFn's order:
-        what = (f_w WH^T + bWH) * qmask;  shat = f_s SH^T + bSH;  kb = what AK^T + bAK;  Mq = kb AQ;  uq = kb . bAQ
-    Returns [(what, shat, kb, Mq, uq) per layer]."""
-    out = []
-    for k in range(len(params) // 8):
-        WH, bWH, SH, bSH, AK, bAK, AQ, bAQ = params[8 * k:8 * k + 8]
-        what = (fw @ WH.t() + bWH) * qmask.unsqueeze(-1)
-        shat = fs @ SH.t() + bSH
-        kb = what @ AK.t() + bAK
-        out.append((what, shat, kb, kb @ AQ, kb @ bAQ))
-    return out
-
-
-def attn_form(C, dl, Nq):
-    """(DL, WS, EXACT) of the instantiation SMIN_ATTN_DISPATCH (csrc/content_attn.hip) picks."""
-    nws = (Nq + 3) // 4
-    if not (C == 4 and dl in (16, 32, 64, 128)):
-        return (16 if dl <= 16 else 32 if dl <= 32 else 64 if dl <= 64 else 128, 8, False)
-    if dl < 128:
-        return (dl, 4 if nws <= 4 else 8, True)
-    return (128, 4 if nws <= 4 else nws if nws <= 6 else 8, True)
-
-
-ALL_FORMS = ([(dl, ws, True) for dl in (16, 32, 64) for ws in (4, 8)] + [(128, ws, True) for ws in (4, 5, 6, 8)]
-             + [(dl, 8, False) for dl in (16, 32, 64, 128)])
-
-
 def form_name(form):
     dl, ws, exact = form
     return f"<{dl},{ws},{'T' if exact else 'F'}>"
 
 
 # ---------------------------------------------------------------- CPU: the restatements against the oracle
-
-def _smi_params(D, dl, gain, seed):
-    from oracle import smin_oracle as O
-    shapes = {k: v for k, v in H.smin_shapes(32, 8, 4, D, dl, 1, 16, 4, D // 2).items() if k.startswith("smis.0.content_unit.")}
-    sd = O.formula_state_dict(shapes, gain=gain)
-    g = torch.Generator().manual_seed(seed)
-    return {k: (v + 0.05 * gain * torch.randn(v.shape, generator=g)).double() for k, v in sd.items()}
-
-
 @pytest.mark.parametrize("mask_kind", ["dense", "ragged"])
 def test_core_restatement_matches_oracle_content_unit(mask_kind):
     """linear_c(core) * m + f_c + gate == oracle.content_unit in float64, the core fed from linear_c_hat and word_side_ref."""
@@ -198,55 +128,6 @@ def test_attention_cases_reach_every_form():
     assert {48, 80, 96, 112} <= {dl for c, dl, nq in ATTN_CASES if not attn_form(c, dl, nq)[2]}
 
 
-def _query_mask(B, Nq, g):
-    """Per sample, cycling: a prefix mask, a mask with holes, fractional weights, and a fully masked query."""
-    qm = torch.ones(B, Nq, dtype=torch.float64)
-    for b in range(B):
-        kind = b % 4
-        if kind == 0:
-            qm[b, max(1, (2 * Nq + 2) // 3):] = 0
-        elif kind == 1:
-            qm[b, 1::3] = 0 if Nq > 1 else 1
-        elif kind == 2:
-            qm[b] = 0.25 + 0.75 * torch.rand(Nq, generator=g, dtype=torch.float64)
-            if Nq > 2:
-                qm[b, Nq // 2] = 0
-        else:
-            qm[b] = 0
-    return qm
-
-
-def _attn_inputs(C, dl, Nq, mask, all_cells, seed):
-    """Float64 inputs on the CPU for a batch with the given moment mask.  Scales put the word scores' spread near 1 and keep the
-    clip softmax off saturation; masked words carry garbage operands (their weight is exactly 0), a fully masked query has zero
-    what rows (the pipeline's invariant: what = linear_w_hat(f_w) * qmask)."""
-    import models
-    g = torch.Generator().manual_seed(seed)
-    B = mask.shape[0]
-    lay = models.vml_amd.CellLayout.all_cells(mask) if all_cells else models.vml_amd.CellLayout.from_mask(mask)
-    r = lambda *s: torch.randn(*s, generator=g, dtype=torch.float64)
-    qm = _query_mask(B, Nq, g)
-    chat = r(lay.N * C, dl)                                   # masked cells (all_cells) keep nonzero rows
-    sw = 0.8 * dl ** -0.25
-    Mq, uq, what, shat = 1.2 * r(B, Nq, dl), 0.5 * r(B, Nq), sw * r(B, Nq, dl), sw * r(B, dl)
-    off = (qm == 0)
-    Mq[off] = 50 * r(int(off.sum()), dl)
-    uq[off] = 50 * r(int(off.sum()))
-    what[off] = 50 * r(int(off.sum()), dl)
-    what[(qm == 0).all(dim=1)] = 0
-    x = dict(chat=chat, Mq=Mq, uq=uq, what=what, shat=shat, qmask=qm)
-    return lay, {k: v.float().double() for k, v in x.items()}          # the kernels' fp32 inputs, exactly
-
-
-def _ragged_mask(B, L, g):
-    p = torch.tensor([0.55, 0.8, 0.35, 0.7])[torch.arange(B) % 4].view(B, 1, 1)
-    return torch.rand(B, L, L, generator=g) < p
-
-
-def _rel(got, ref):
-    return (got.double().cpu() - ref).abs().max().item() / max(ref.abs().max().item(), 1e-30)
-
-
 ATTN_IN = ("chat", "Mq", "uq", "what", "shat")
 
 
@@ -323,20 +204,6 @@ def _run_attn_case(dev, C, dl, Nq, lay, x, label, check_masked=True):
             assert torch.all(d["chat"][rows] != 0)
     print(f"attn {label}: worst fwd {worst_f:.2e} grad {worst_g:.2e}")
     return worst_f, worst_g
-
-
-def _layout_to(lay, dev):
-    import models
-    CL = models.vml_amd.CellLayout
-    return CL(lay.cells.to(dev), lay.row_ptr.to(dev), lay.cellmap.to(dev), lay.B, lay.L, None, lay.all_valid)
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    import models
-    models.vml_amd._lib.load()
-    return torch.device("cuda:0")
 
 
 @pytest.mark.gpu

@@ -8,7 +8,8 @@ import pytest
 import torch
 
 from tests import helpers as H
-from tests.test_attention_core import ALL_FORMS, _attn_inputs, _layout_to, _ragged_mask, attn_form
+from tests.support.device import dev  # noqa: F401  (the module's device fixture)
+from tests.support.references import _attn_inputs, _layout_to, _ragged_mask, attn_form, ALL_FORMS
 
 ATTN_FIXTURES = ["ga_ragged", "ga_r2", "ga_c3_q18"]
 MAP_TOL = 1e-5
@@ -61,14 +62,6 @@ def _model(cfg, sd, dev, native):
     m = m.to(dev)
     m.fused_core = native
     return m
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    import models
-    models.vml_amd._lib.load()
-    return torch.device("cuda:0")
 
 
 # ---------------------------------------------------------------- CPU

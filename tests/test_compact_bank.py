@@ -15,9 +15,11 @@ import numpy as np
 import pytest
 import torch
 
-from tests.test_corpus_search import TINY_SHAPE, V, corpus_inputs, host_banks, tiny_model
-from tests.test_prefilter import SHAPES as PREFILTER_SHAPES, inputs as prefilter_inputs
-from tests import test_window_search as WS
+from tests.support import corpora as WS
+from tests.support.device import dev  # noqa: F401  (the module's device fixture)
+from tests.support.device import vml as V
+from tests.support.corpora import (
+    corpus_inputs, host_banks, inputs as prefilter_inputs, tiny_model, SEARCH_KEYS, SHAPES as PREFILTER_SHAPES, TINY_SHAPE)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 STORAGES = ["bf16", "int8"]
@@ -25,7 +27,6 @@ ENTRY_POINTS = ("smin_bank_encode", "smin_bank_decode", "smin_pair_assemble_comp
 INT8_BOUND = 0.5 + 2.0 ** -10
 BF16_BOUND = 2.0 ** -8
 BAND = 32                                              # bytes / elements of sentinel on either side of an output
-SEARCH_KEYS = ("video", "idx", "score", "count")
 
 
 def bits(t):
@@ -91,7 +92,7 @@ def test_surface():
     assert "Tensor codes, Tensor? scale, Tensor fw" in schema and "scale" not in plain and "codes" not in plain
     assert schema.split("Tensor fw", 1)[1] == plain.split("Tensor fw", 1)[1]            # the same options from there on
     m, _ = tiny_model()
-    vid, qry = corpus_inputs()
+    vid, qry, _ = corpus_inputs()
     for codes, scale in ((torch.zeros(5, 16, 32, dtype=torch.int8), torch.zeros(5, 16)), (torch.zeros(5, 16, 32, dtype=torch.bfloat16), None)):
         with pytest.raises(RuntimeError, match="no CPU fallback"):
             ops.smin_score_pairs_compact(codes, scale, torch.zeros(4, 5, 32), torch.zeros(4, 32), vid["video_mask"], qry["query_mask"], vid["length_mask"],
@@ -139,7 +140,7 @@ def test_encode_torch_is_the_pinned_code(D):
 def test_refusals():
     A = V()
     m, _ = tiny_model()
-    vid, qry = corpus_inputs()
+    vid, qry, _ = corpus_inputs()
     x = torch.randn(3, 8)
     for bad in ("fp16", "int4", None, 8):
         with pytest.raises(ValueError, match="storage"):
@@ -191,13 +192,6 @@ def test_refusals():
 
 
 # ---------------------------------------------------------------- GPU: the kernels
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    V()._lib.load()
-    return torch.device("cuda:0")
-
-
 def banded(shape, dtype, dev):
     """a contiguous tensor of ``shape`` between two bands of BAND bytes of 0x5A: ``(the whole byte buffer, the view)``"""
     n = int(np.prod(shape)) * torch.empty((), dtype=dtype).element_size()
@@ -427,7 +421,7 @@ def world(dev):
     m, _ = tiny_model(dev)
 
     def banks(snips):
-        vid, qry = corpus_inputs(snips=snips)
+        vid, qry, _ = corpus_inputs(snips=snips)
         vid_d, qry_d = {k: v.to(dev) for k, v in vid.items()}, {k: v.to(dev) for k, v in qry.items()}
         return vid_d, m.encode_videos(vid_d["video_features"], vid_d["video_mask"], vid_d["length_mask"], vid_d["moment_mask"]), m.encode_queries(
             qry_d["query_features"], qry_d["query_mask"])

@@ -9,23 +9,20 @@ import ctypes
 import multiprocessing as mp
 import os
 import re
-import socket
 
 import numpy as np
 import pytest
 import torch
 
 from tests import helpers as H
-from tests.test_corpus_search import SCORE_TOL, TINY_SHAPE, bits, build_model, corpus_inputs, same_merge, tiny_model
+from tests.support.device import dev  # noqa: F401  (the module's device fixture)
+from tests.support.device import free_port, to_dev, vml as V
+from tests.support.compare import bits, same_merge
+from tests.support.corpora import build_model, cell_topk_of as topk_of, corpus_inputs, pair_lists, shards_of, tiny_model, DURATION, SCORE_TOL
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 KEYS = ("video", "idx", "score", "count")
 SPLITS = ([3, 4], [1, 1, 5], [7], [2, 2, 2, 1])
-
-
-def V():
-    import models
-    return models.vml_amd
 
 
 def same_lists(got, want, what=""):
@@ -33,36 +30,6 @@ def same_lists(got, want, what=""):
 
 
 # ---------------------------------------------------------------- shared data
-def pair_lists(nv, Q, kv, seed, full_query=None, empty_query=None):
-    """top_moments-shaped lists of all Q * nv (query, video) pairs, query-major: scores randint(0, 6) / 8 sorted per pair (ties
-    everywhere), random counts in [0, kv]; ``full_query``: every count kv, ``empty_query``: every count 0."""
-    g = torch.Generator().manual_seed(seed)
-    P = Q * nv
-    score = (torch.randint(0, 6, (P, kv), generator=g).float() / 8).sort(dim=1, descending=True).values
-    idx = torch.randint(0, 64, (P, kv, 2), generator=g, dtype=torch.int64)
-    count = torch.randint(0, kv + 1, (P,), generator=g, dtype=torch.int32)
-    if full_query is not None:
-        count[full_query * nv:(full_query + 1) * nv] = kv
-    if empty_query is not None:
-        count[empty_query * nv:(empty_query + 1) * nv] = 0
-    return score, idx, count
-
-
-def topk_of(lists, nv, Q, v0, v1, K):
-    """corpus_topk_torch(k=K) of the videos v0 .. v1 of ``lists`` (pair_lists), numbered from 0 within the shard"""
-    score, idx, count = lists
-    rows = torch.tensor([q * nv + v for q in range(Q) for v in range(v0, v1)], dtype=torch.int64)
-    video = torch.arange(v1 - v0, dtype=torch.int32).repeat(Q)
-    ptr = torch.arange(Q + 1, dtype=torch.int32) * (v1 - v0)
-    return V().corpus_topk_torch(score[rows], idx[rows], count[rows], video, ptr, k=K)
-
-
-def shards_of(lists, nv, Q, split, K):
-    edges = np.concatenate([[0], np.cumsum(split)]).tolist()
-    assert edges[-1] == nv
-    return [topk_of(lists, nv, Q, a, b, K) for a, b in zip(edges[:-1], edges[1:])], edges[:-1]
-
-
 def with_garbage(r, garbage):
     """the ranked list r with ``garbage`` scores (and foreign ids) behind its counts"""
     k = r["score"].shape[1]
@@ -347,7 +314,7 @@ def test_refusals():
             cls(m=(0.5,) * 17, device="cpu")
     # test_model_corpus: before any device work (a host model and host tensors would raise SminHipError at the first encoder)
     m, _ = tiny_model()
-    vid, qry = corpus_inputs()
+    vid, qry, _ = corpus_inputs()
     shards = [dict(vid, duration=np.ones(5))]
     gv, gtimes = np.zeros(4, dtype=np.int64), np.ones((4, 2))
     with pytest.raises(ValueError, match="max\\(n\\) \\* k_video"):
@@ -360,14 +327,6 @@ def test_refusals():
 
 # ---------------------------------------------------------------- host: two gloo ranks
 GLOO = dict(nv=7, Q=3, kv=3, K=5, seed=4, split=[3, 4])
-
-
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
 
 
 def _gather_worker(rank, world, port, q):
@@ -397,7 +356,7 @@ def test_two_gloo_ranks_return_the_whole_corpus_list():
     returns the whole corpus' list on both, bitwise equal; ranks that pass different k raise ValueError on both."""
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
-    port = _free_port()
+    port = free_port()
     procs = [ctx.Process(target=_gather_worker, args=(r, 2, port, q)) for r in range(2)]
     for p in procs:
         p.start()
@@ -417,17 +376,6 @@ def test_two_gloo_ranks_return_the_whole_corpus_list():
 
 
 # ---------------------------------------------------------------- GPU
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    V()._lib.load()
-    return torch.device("cuda:0")
-
-
-def to_dev(r, dev):
-    return {key: v.to(dev) for key, v in r.items()}
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("S", [1, 2, 3])
 @pytest.mark.parametrize("K", [1, 5, 64])
@@ -578,9 +526,6 @@ def test_meter_kernel_hand_case(dev):
     assert meter.state.eq(0).all()
 
 
-DURATION = np.array([10.0, 3.5, 60.0, 7.25, 100.0])
-
-
 def shard_dicts(vid_d, split):
     edges = np.concatenate([[0], np.cumsum(split)]).tolist()
     return [dict({key: v[a:b] for key, v in vid_d.items()}, duration=DURATION[a:b]) for a, b in zip(edges[:-1], edges[1:])]
@@ -591,7 +536,7 @@ def tiny(dev):
     m, _ = tiny_model(dev)
     # seed 1: in the oracle's scores three of the four queries have their second-best moment in another video than their best (by
     # 5e-3 or more, far above SCORE_TOL) and one has both in one video, which test_model_corpus_end_to_end's planted truth needs
-    vid, qry = corpus_inputs(seed=1)
+    vid, qry, _ = corpus_inputs(seed=1)
     return dict(m=m, vid_d={key: v.to(dev) for key, v in vid.items()}, qry_d={key: v.to(dev) for key, v in qry.items()})
 
 

@@ -14,63 +14,14 @@ import pytest
 import torch
 
 from tests import helpers as H
+from tests.support.device import dev  # noqa: F401  (the module's device fixture)
+from tests.support.device import vml as V
+from tests.support.compare import bits, same_merge
+from tests.support.guards import WORD_SENTINEL as SENTINEL
+from tests.support.corpora import build_model, corpus_inputs, expand, host_banks, tiny_model, SCORE_TOL
 
-SCORE_TOL = 2e-5                                       # test_score_path.SCORE_TOL
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-TINY_SHAPE = (16, 8, 4, 32, 16, 2, 24, 5, 16)          # T, L, C, D, dl, layers, Din, Nq, H
 OPTIONS = ("bool overlap_boundary", "bool overlap_prep", "bool param_prep_kernel", "bool bf16_operand_storage", "int? known_cell_count")
-
-
-def V():
-    import models
-    return models.vml_amd
-
-
-def tiny_model(dev=None):
-    import models
-    from oracle import smin_oracle as O
-    sd = O.formula_state_dict(H.smin_shapes(*TINY_SHAPE), gain=1.2)
-    m = models.SMIN(*TINY_SHAPE) if dev is None else models.SMIN(*TINY_SHAPE, dev)
-    m.load_state_dict(sd, strict=True)
-    return (m if dev is None else m.to(dev)), sd
-
-
-def corpus_inputs(snips=(8, 1, 5, 8, 3), words=(5, 1, 3, 4), seed=3):
-    """V videos with the given numbers of valid snippets of L and Q queries with the given numbers of words, as host tensors in the
-    layout of oracle.synthetic_batch."""
-    T, L, _, _, _, _, Din, Nq, _ = TINY_SHAPE
-    g = torch.Generator().manual_seed(seed)
-    nv, nq = len(snips), len(words)
-    vf, qf = torch.randn(nv, T, Din, generator=g), torch.randn(nq, Nq, 300, generator=g)
-    vmask, qmask = torch.zeros(nv, T, 1, dtype=torch.uint8), torch.zeros(nq, Nq, 1, dtype=torch.uint8)
-    lmask = torch.zeros(nv, L, dtype=torch.bool)
-    for v, s in enumerate(snips):
-        nf = s * (T // L) - (v % 2)                    # odd videos end inside their last snippet
-        vf[v, nf:] = 0
-        vmask[v, :nf] = 1
-        lmask[v, :s] = True
-    for q, w in enumerate(words):
-        qf[q, w:] = 0
-        qmask[q, :w] = 1
-    mmask = torch.triu(lmask.unsqueeze(2) & lmask.unsqueeze(1))
-    return dict(video_features=vf, video_mask=vmask, length_mask=lmask, moment_mask=mmask), dict(query_features=qf, query_mask=qmask)
-
-
-def expand(vid, qry, vi, qi):
-    """the six forward inputs of the pairs (vi[p], qi[p])"""
-    vi, qi = torch.as_tensor(vi, dtype=torch.int64), torch.as_tensor(qi, dtype=torch.int64)
-    vi, qi = vi.to(vid["video_features"].device), qi.to(vid["video_features"].device)
-    return [vid["video_features"][vi], vid["video_mask"][vi], qry["query_features"][qi], qry["query_mask"][qi], vid["length_mask"][vi],
-            vid["moment_mask"][vi]]
-
-
-def host_banks():
-    vid, qry = corpus_inputs()
-    A = V()
-    counts = vid["moment_mask"].reshape(5, -1).sum(1).tolist()
-    vb = A.VideoBank(None, vid["video_features"], vid["video_mask"], vid["length_mask"], vid["moment_mask"], counts)
-    qb = A.QueryBank(None, None, qry["query_features"], qry["query_mask"].reshape(4, -1))
-    return vb, qb
 
 
 # ---------------------------------------------------------------- host: surface
@@ -97,7 +48,7 @@ def test_operators_are_registered_and_refuse_cpu():
     for name in ("async_weights", "grad_sync", "tail_split", "input_grads", "attention"):
         assert name not in schema, schema
     m, _ = tiny_model()
-    vid, qry = corpus_inputs()
+    vid, qry, _ = corpus_inputs()
     with pytest.raises(RuntimeError, match="no CPU fallback"):
         ops.smin_encode_videos(vid["video_features"], vid["video_mask"], m._native_params())
     with pytest.raises(RuntimeError, match="no CPU fallback"):
@@ -110,7 +61,7 @@ def test_operators_are_registered_and_refuse_cpu():
 
 def test_methods_fail_loudly_on_cpu():
     m, _ = tiny_model()
-    vid, qry = corpus_inputs()
+    vid, qry, _ = corpus_inputs()
     err = V()._lib.SminHipError
     with pytest.raises(err, match="no CPU fallback"):
         m.encode_videos(vid["video_features"], vid["video_mask"], vid["length_mask"], vid["moment_mask"])
@@ -187,20 +138,6 @@ def test_corpus_topk_torch_by_hand():
 
 
 # ---------------------------------------------------------------- GPU
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    V()._lib.load()
-    return torch.device("cuda:0")
-
-
-def bits(t):
-    return t.detach().cpu().contiguous().view(torch.int32)
-
-
-SENTINEL = 0x5A5A5A5A
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("nv,nq,P,T,Nq,D", [(3, 4, 17, 16, 5, 32), (2, 2, 1, 1, 1, 4), (5, 3, 9, 7, 5, 104)])
 def test_pair_assemble_bit_exact(dev, nv, nq, P, T, Nq, D):
@@ -245,13 +182,6 @@ def random_lists(per_query, kv, seed, garbage):
     score = torch.where(unused, torch.full_like(score, garbage), score)
     idx = torch.where(unused.unsqueeze(2), torch.full_like(idx, 777 if garbage == garbage else -5), idx)
     return score, idx, count, video, ptr
-
-
-def same_merge(got, want, what=""):
-    for key in ("video", "idx", "count"):
-        assert torch.equal(got[key].cpu(), want[key]), (what, key)
-    assert torch.equal(bits(got["score"]), bits(want["score"])), (what, "score")
-    assert got["video"].dtype == torch.int64 and got["idx"].dtype == torch.int64 and got["count"].dtype == torch.int32
 
 
 @pytest.mark.gpu
@@ -317,13 +247,6 @@ def test_corpus_topk_many_pairs_and_none(dev):
     assert lib.smin_corpus_topk(L_.stream(), *p, 1, 5, 5, None, *o[1:]) != 0
 
 
-def build_model(cfg, sd, dev):
-    import models
-    m = models.SMIN(cfg["T"], cfg["L"], cfg["C"], cfg["D"], cfg["dl"], cfg["layers"], cfg["Din"], cfg["Nq"], cfg["H"], dev)
-    m.load_state_dict(sd, strict=True)
-    return m.to(dev)
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("name", H.TINY)
 def test_identity_banks_are_score(dev, name):
@@ -348,7 +271,7 @@ def corpus(dev):
     """the tiny model, V = 5 / Q = 4 banks, all 20 pairs query-major, the oracle's scores of the expanded batch (computed once)"""
     from oracle import smin_oracle as O
     m, sd = tiny_model(dev)
-    vid, qry = corpus_inputs()
+    vid, qry, _ = corpus_inputs()
     qi, vi = np.repeat(np.arange(4), 5), np.tile(np.arange(5), 4)
     with torch.no_grad():
         ref = O.smin_forward(sd, dict(T=16, L=8, C=4), *expand(vid, qry, vi, qi))

@@ -4,19 +4,12 @@ so the network under DDP here is a stand-in torch module defined in this file, w
 of the same form as the restated loss: averaged shard gradients must equal full-batch gradients.  The
 SMIN HIP path under DDP is tests/test_ddp_hip.py (-m gpu)."""
 import os
-import socket
 
 import pytest
 import torch
 import torch.multiprocessing as mp
 
-
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
+from tests.support.device import free_port
 
 
 class _StandIn(torch.nn.Module):
@@ -72,7 +65,7 @@ def _worker(rank, world, port, q):
 def test_ddp_gradients_match_full_batch():
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
-    port = _free_port()
+    port = free_port()
     procs = [ctx.Process(target=_worker, args=(r, 2, port, q)) for r in range(2)]
     for p in procs:
         p.start()

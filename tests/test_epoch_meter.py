@@ -6,7 +6,6 @@ eval_epoch / test_model).
 per-batch ``compute_ious_torch`` counts and to the reference's recorded counts (g6_ious.npz); ``EpochMeter`` (HIP) is then
 compared to it bit for bit."""
 import os
-import socket
 
 import numpy as np
 import pytest
@@ -14,14 +13,12 @@ import torch
 import torch.multiprocessing as mp
 
 from tests import helpers as H
+from tests.support.device import dev  # noqa: F401  (the module's device fixture)
+from tests.support.device import free_port, vml as V
+from tests.support.compare import bits64
 
 REF_N, REF_M = (1, 5), (0.1, 0.3, 0.5, 0.7)
 OTHER_N, OTHER_M = (1, 3, 10), (0.5, 0.9)
-
-
-def V():
-    import models
-    return models.vml_amd
 
 
 def ragged(B, L, seed):
@@ -41,10 +38,6 @@ def ragged(B, L, seed):
 
 def fake_loss(seed):
     return torch.rand((), generator=torch.Generator().manual_seed(1000 + seed)) * 3 + 0.1
-
-
-def bits64(t):
-    return t.detach().cpu().contiguous().view(torch.int64)
 
 
 # ---------------------------------------------------------------- CPU: the cell count
@@ -185,14 +178,6 @@ def test_result_raises_on_status_words(monkeypatch):
     assert meter.result()["num_samples"] == 2
 
 
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
-
-
 GLOO_BATCHES = [(4, 12, 31), (3, 12, 32), (5, 12, 33), (2, 12, 34)]             # (B, L, seed); rank r takes batches r, r + 2
 
 
@@ -224,7 +209,7 @@ def test_result_over_two_gloo_ranks():
     loss_sum = sum(float(np.float32(fake_loss(seed).item())) * B for B, L, seed in GLOO_BATCHES)
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
-    port = _free_port()
+    port = free_port()
     procs = [ctx.Process(target=_gloo_worker, args=(r, 2, port, q)) for r in range(2)]
     for p in procs:
         p.start()
@@ -243,12 +228,6 @@ def test_result_over_two_gloo_ranks():
 
 
 # ---------------------------------------------------------------- GPU
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    import models
-    models.vml_amd._lib.load()
-    return torch.device("cuda", 0)
 
 
 RULES = [(None, REF_N, REF_M), (0.5, REF_N, REF_M), (0.45, (1, 3, 10, 64), (0.1, 0.5, 0.9))]

@@ -14,28 +14,18 @@ import numpy as np
 import pytest
 import torch
 
-from tests.test_input_grads import _sample_clips_ref
-from tests.test_row_sparse_table import backward_dense, backward_rows, batches, same_state
+from tests.support.device import dev  # noqa: F401  (the module's device fixture)
+from tests.support.device import vml as A
+from tests.support.compare import same_state
+from tests.support.references import _sample_clips_ref, backward_dense, backward_rows, batches
 
 gpu = pytest.mark.gpu
-
-
-def A():
-    import models
-    return models.vml_amd
 
 
 def S():
     import models  # noqa: F401  (loads the package as vml_amd)
     from vml_amd import sampling
     return sampling
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    A()._lib.load()
-    return torch.device("cuda:0")
 
 
 # ---------------------------------------------------------------- restatements

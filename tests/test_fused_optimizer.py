@@ -14,6 +14,9 @@ import pytest
 import torch
 
 from tests import helpers as H
+from tests.support.device import dev_torch  # noqa: F401  (the module's device fixture)
+from tests.support.device import vml as FA
+from tests.support.compare import bits
 
 SET_COUNTS = (1, 1, 3, 4, 5, 1023, 4096, 4097, 8193)
 VIEW_N = 4097
@@ -59,10 +62,6 @@ def set_grads(params, vals, grads, shift=0):
         p.grad = _placed(gr, (off or 0) + shift if (off or shift) else None, p.device, p.dtype)
 
 
-def bits(t):
-    return t.detach().cpu().contiguous().view(torch.int32)
-
-
 def same_bits(a, b):
     return torch.equal(bits(a), bits(b))
 
@@ -72,11 +71,6 @@ def assert_same_state(opt_a, ps_a, opt_b, ps_b, what=""):
         assert same_bits(a, b), (what, i, "p")
         for key in ("exp_avg", "exp_avg_sq"):
             assert same_bits(opt_a.state[a][key], opt_b.state[b][key]), (what, i, key)
-
-
-def FA():
-    import models
-    return models.vml_amd
 
 
 # ================================================================ CPU
@@ -286,13 +280,6 @@ def test_restatement_skips_and_schedules_like_the_device_class():
 
 
 # ================================================================ GPU
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    FA()._lib.load_torch()
-    return torch.device("cuda:0")
-
-
 def _pair(vals, dev, **kw):
     """the device optimizer and the restatement on equal copies of `vals`"""
     A = FA()

@@ -44,9 +44,13 @@ import pytest
 import torch
 
 from tests import helpers as H
-from tests.test_attention_core import WORD_PARAM_NAMES, _attn_inputs, _layout_to, _smi_params, attn_core_ref, word_side_ref
-from tests.test_gemm_engine import nt_form, tn_forms
-from tests.test_proposal_map import _assert_spread, _spread, lengths_mask, make_layout, moment_mask
+from tests.support.device import dev  # noqa: F401  (the module's device fixture)
+from tests.support.device import gemm_mode  # noqa: F401  (fixture)
+from tests.support.compare import _assert_spread, _spread
+from tests.support.guards import _nan, _ws_nan
+from tests.support.references import (
+    _attn_inputs, _layout_to, _smi_params, attn_core_ref, lengths_mask, make_layout, moment_mask, nt_form, tn_forms, word_side_ref,
+    WORD_PARAM_NAMES)
 
 FWD_TOL = 1e-5          # max |got - ref| / max |ref|, per output and case (tests/test_proposal_map.py, tests/test_attention_core.py)
 GRAD_TOL = 1e-4
@@ -551,23 +555,6 @@ def test_bounds_separate_fp32_rounding_from_wrong_formulas():
 
 
 # ---------------------------------------------------------------- GPU helpers
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    import models
-    models.vml_amd._lib.load()
-    return torch.device("cuda:0")
-
-
-@pytest.fixture()
-def gemm_mode():
-    """set_gemm_mode, restoring the library's starting mode (_lib.DEFAULT_GEMM_MODE) afterwards"""
-    import models
-    yield models.vml_amd.set_gemm_mode
-    models.vml_amd.set_gemm_mode(models.vml_amd._lib.DEFAULT_GEMM_MODE)
-
-
 def _rel(got, ref):
     """max |got - ref| / max |ref| (inf for a NaN: an element the kernel never wrote)"""
     if not ref.numel():
@@ -576,15 +563,6 @@ def _rel(got, ref):
     if not bool(torch.isfinite(got).all()):
         return float("inf")
     return (got - ref).abs().max().item() / max(ref.abs().max().item(), 1e-30)
-
-
-def _nan(shape, dev, dtype=torch.float32):
-    return torch.full(tuple(shape), float("nan"), dtype=dtype, device=dev)
-
-
-def _ws_nan(nbytes, dev):
-    """A NaN-filled workspace of at least nbytes (whole floats) and the byte count to declare: exactly nbytes."""
-    return _nan((max(1, cdiv(int(nbytes), 4)),), dev), int(nbytes)
 
 
 def _vp(t):

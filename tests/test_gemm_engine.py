@@ -20,6 +20,9 @@ import pytest
 import torch
 
 from tests.helpers import GEMM_SLOTS, cdiv, tn_splits
+from tests.support.device import dev  # noqa: F401  (the module's device fixture)
+from tests.support.device import gemm_mode  # noqa: F401  (fixture)
+from tests.support.references import nt_form, nt_grid, tn_forms, tn_grid
 
 MODES = ("f32", "bf16x3", "bf16", "f32e")
 KERNEL = {"f32": "gemm_nt", "bf16x3": "gemm_nt_x3<3>", "bf16": "gemm_nt_x3<1>", "f32e": "gemm_nt_x3<6>"}
@@ -31,34 +34,6 @@ SENTINEL = -7.375e33
 
 
 # ---------------------------------------------------------------- mirrors of the launch arithmetic
-
-def nt_grid(M, N, K):
-    """launch_gemm_nt: 128-row main tiles in XCD-aware order (main_blocks padded to whole groups of 8 row tiles), the rest of the rows
-    in 32-row mini tiles; KFULL = K % 16 == 0."""
-    tiles_m, tiles_n = cdiv(M, 128), cdiv(N, 128)
-    main = tiles_m
-    total = tiles_m * tiles_n
-    full_rounds = total // GEMM_SLOTS
-    if full_rounds >= 1 and total % GEMM_SLOTS != 0 and total % GEMM_SLOTS < 3 * GEMM_SLOTS // 4:
-        main = full_rounds * GEMM_SLOTS // tiles_n
-    elif total * 3 <= GEMM_SLOTS:
-        main = 0
-    rem_rows = M - main * 128
-    return dict(tiles_m=tiles_m, tiles_n=tiles_n, total=total, main_tiles_m=main, kfull=K % 16 == 0,
-                main_blocks=cdiv(main, 8) * 8 * tiles_n, mini_blocks=cdiv(rem_rows, 32) * tiles_n if rem_rows > 0 else 0)
-
-
-def nt_form(M, N, K):
-    g = nt_grid(M, N, K)
-    if g["main_tiles_m"] == 0:
-        return "mini"
-    if g["main_tiles_m"] < g["tiles_m"]:
-        return "rounds+mini"
-    if g["total"] > GEMM_SLOTS:
-        return "main-after-round"                      # a full round, then a remainder >= 3/4 of GEMM_SLOTS: main tiles only
-    return "main+idle-slots" if g["main_tiles_m"] % 8 else "main"
-
-
 def nt_block_tiles(M, N, K):
     """The (row0, rows, col0) output tile of every workgroup gemm_nt_kernel / gemm_nt_x3_kernel runs (idle slots omitted)."""
     g = nt_grid(M, N, K)
@@ -71,31 +46,6 @@ def nt_block_tiles(M, N, K):
     for i in range(g["mini_blocks"]):
         out.append((g["main_tiles_m"] * 128 + (i // g["tiles_n"]) * 32, 32, (i % g["tiles_n"]) * 128))
     return out
-
-
-def tn_grid(Mrows, I, J):
-    """launch_gemm_tn: splits, rows per split (whole 32-row groups), grid (split count padded to a multiple of 8 per output tile)."""
-    sp = tn_splits(Mrows, I, J)
-    rps = cdiv(cdiv(Mrows, sp), 32) * 32
-    tiles = cdiv(I, 128) * cdiv(J, 128)
-    return dict(splits=sp, rows_per_split=rps, tiles=tiles, grid=cdiv(sp, 8) * 8 * tiles,
-                empty=[z for z in range(sp) if z * rps >= Mrows])
-
-
-def tn_forms(Mrows, I, J):
-    g = tn_grid(Mrows, I, J)
-    f = set()
-    if g["splits"] == 1:
-        f.add("splits=1")
-    elif g["splits"] % 8:
-        f.add("splits%8!=0")                           # padded XCD slots: workgroups with z >= splits return at once
-    if g["empty"]:
-        f.add("empty-trailing-split")
-    if g["splits"] == GEMM_SLOTS:
-        f.add("slots-capped")
-    if Mrows < 32:
-        f.add("Mrows<32")
-    return f
 
 
 def tn_block_splits(Mrows, I, J):
@@ -290,23 +240,6 @@ def _rows(g, R, K, spread=2.0):
 
 
 # ---------------------------------------------------------------- GPU helpers
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    import models
-    models.vml_amd._lib.load()
-    return torch.device("cuda:0")
-
-
-@pytest.fixture()
-def gemm_mode():
-    """set_gemm_mode, restoring the library's starting mode (_lib.DEFAULT_GEMM_MODE) afterwards"""
-    import models
-    yield models.vml_amd.set_gemm_mode
-    models.vml_amd.set_gemm_mode(models.vml_amd._lib.DEFAULT_GEMM_MODE)
-
-
 def _p(t):
     return None if t is None else ctypes.c_void_p(t.data_ptr())
 

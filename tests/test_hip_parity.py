@@ -7,26 +7,10 @@ import pytest
 import torch
 
 from tests import helpers as H
+from tests.support.device import dev  # noqa: F401  (the module's device fixture)
+from tests.support.corpora import build_model, NATIVE_ROWS, SCORE_TOL
 
 pytestmark = pytest.mark.gpu
-
-SCORE_TOL = 2e-5
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    import models
-    models.vml_amd._lib.load()          # fail loudly if libsmin_hip.so is missing
-    return torch.device("cuda:0")
-
-
-def build_model(cfg, sd, dev):
-    import models
-    m = models.SMIN(cfg["T"], cfg["L"], cfg["C"], cfg["D"], cfg["dl"], cfg["layers"], cfg["Din"], cfg["Nq"], cfg["H"], dev)
-    missing = m.load_state_dict(sd, strict=True)
-    assert not missing.missing_keys and not missing.unexpected_keys
-    return m.to(dev)
 
 
 def rel_err(got, ref):
@@ -215,16 +199,6 @@ def test_full_size_against_golden(dev, name):
 
 
 # ---------------------------------------------------------------- oracle on fresh seeded inputs
-# rows that send the one-node extension path into attention-core forms no other model-level case reaches
-# (form <DL,WS,EXACT> as SMIN_ATTN_DISPATCH in csrc/content_attn.hip picks it)
-NATIVE_ROWS = [
-    (64, 16, 4, 128, 64, 2, 40, 9, 64, 3),       # <64,4,T>
-    (32, 16, 4, 64, 32, 1, 24, 17, 32, 5),       # <32,8,T>, extra-word slots partly used
-    (32, 8, 4, 64, 16, 2, 24, 32, 32, 2),        # <16,8,T>
-    (64, 16, 4, 256, 128, 2, 40, 23, 128, 3),    # <128,6,T>
-    (32, 8, 4, 192, 128, 2, 24, 29, 96, 4),      # <128,8,T>; parameter products in csrc/param_prep.hip
-    (64, 16, 4, 104, 48, 2, 24, 18, 52, 3),      # <64,8,F> with dl < DL; torch parameter prep (D % 32 != 0)
-]
 @pytest.mark.parametrize("T,L,C,D,dl,layers,Din,Nq,Hh,B", [
     (64, 16, 4, 64, 32, 2, 40, 9, 32, 5),
     (48, 24, 4, 128, 64, 1, 32, 20, 64, 3),      # r = 2 < C: empty clips and dropped frames

@@ -7,32 +7,13 @@ import pytest
 import torch
 
 from tests import helpers as H
+from tests.support.device import dev  # noqa: F401  (the module's device fixture)
+from tests.support.corpora import build_model, loss_of_batch as loss_of, one_node_only
+from tests.support.references import _sample_clips_ref
 
 pytestmark = pytest.mark.gpu
 
 KEYS = ["T", "L", "C", "D", "dl", "layers", "Din", "Nq", "H", "B"]
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    import models
-    models.vml_amd._lib.load()
-    return torch.device("cuda:0")
-
-
-def build_model(cfg, sd, dev):
-    import models
-    m = models.SMIN(cfg["T"], cfg["L"], cfg["C"], cfg["D"], cfg["dl"], cfg["layers"], cfg["Din"], cfg["Nq"], cfg["H"], dev)
-    m.load_state_dict(sd, strict=True)
-    return m.to(dev)
-
-
-def one_node_only(m):
-    """Fail the step if it leaves the one-node path (the Python host's content stream would run)."""
-    def python_host(*a):
-        raise AssertionError("the step ran the Python host")
-    m._forward_stream = python_host
 
 
 def cluster_error():
@@ -44,13 +25,6 @@ def close(got, want, rel):
     got, want = got.detach().double().cpu(), want.detach().double().cpu()
     err = float((got - want).abs().max())
     return err <= rel * float(want.abs().max()) + 1e-7, err
-
-
-def loss_of(out, b, oracle=False):
-    from oracle import smin_oracle as O
-    from vml_amd import loss_fn
-    return (O.loss_fn if oracle else loss_fn)(out[0], b["ym"], b["sm"], b["moment_mask"], out[1], b["ys"], b["ss"], out[2], b["ye"], b["se"], out[3], b["ya"],
-                   b["length_mask"])
 
 
 @pytest.mark.parametrize("case", ["tiny", "ragged"])
@@ -205,24 +179,6 @@ def test_embed_tokens_backward(dev):
     assert bool((runs[0][8:V - 1] == 0).all())                          # rows no token touches
     qf, _, _ = embed_tokens(tok.to(dev), table.to(dev).requires_grad_(True))
     assert not qf.requires_grad
-
-
-def _sample_clips_ref(raw64, lengths, T, spos, mode):
-    """sample_clips restated in torch (differentiable): clip_indices / mean_windows on the rows of each sample."""
-    from vml_amd.sampling import clip_indices, mean_windows
-    offs = np.concatenate([[0], np.cumsum(lengths)])
-    rows = []
-    for b, n in enumerate(lengths):
-        x = raw64[offs[b]:offs[b + 1]]
-        out = raw64.new_zeros((T, raw64.shape[1]))
-        if mode == "pick" or n <= T:
-            idx = clip_indices(n, T, spos[b])
-            out = torch.cat([x[torch.from_numpy(idx)], out[idx.shape[0]:]])
-        else:
-            a = mean_windows(n, T)
-            out = torch.stack([x[a[t]:a[t + 1]].sum(0) / float(a[t + 1] - a[t]) for t in range(T)])
-        rows.append(out)
-    return torch.stack(rows)
 
 
 @pytest.mark.parametrize("mode", ["pick", "mean"])

@@ -9,18 +9,11 @@ import pytest
 import torch
 
 from tests import helpers as H
+from tests.support.device import dev  # noqa: F401  (the module's device fixture)
 
 pytestmark = pytest.mark.gpu
 
 LONG = (1024, 512, 4, 512, 128, 3, 500, 20, 256)        # T, L, C, D, dl, layers, Din, Nq, H
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    import models
-    models.vml_amd._lib.load()
-    return torch.device("cuda:0")
 
 
 def _model(shape, sd, dev):

@@ -15,11 +15,12 @@ import numpy as np
 import pytest
 import torch
 
-from tests.test_pair_training import GT_VIDEO, V, bits, corpus_inputs, expand, loss_of, pair_args, tiny_model
+from tests.support.device import dev  # noqa: F401  (the module's device fixture)
+from tests.support.device import vml as V
+from tests.support.compare import bits
+from tests.support.corpora import corpus_inputs, expand, loss_of, on, pair_args, tiny_model, FULL, GT_VIDEO, NQ, NV
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NV, NQ = 5, 4                                          # corpus_inputs: V = 5 videos, Q = 4 queries
-FULL = (8, 8, 8, 8, 8)                                 # every video at full length: 36 valid cells each
 SENTINEL = -7
 
 
@@ -157,13 +158,6 @@ def test_wrapped_plan_through_pair_targets_and_group_checks():
 
 
 # ---------------------------------------------------------------- GPU
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    V()._lib.load()
-    return torch.device("cuda:0")
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("Q,Vn,N,skip", [(1, 2, 1, 0), (3, 5, 2, 0), (4, 65, 3, 1), (2, 300, 8, 2), (5, 9, 8, 0), (2, 70, 60, 4)])
 def test_kernel_against_torch(dev, Q, Vn, N, skip):
@@ -208,10 +202,6 @@ def test_kernel_against_torch(dev, Q, Vn, N, skip):
         assert rc != 0, hole
         for k, t in enumerate(outs):
             assert k == hole or t.eq(SENTINEL).all(), hole
-
-
-def on(dev, d):
-    return {k: v.to(dev) for k, v in d.items()}
 
 
 @pytest.fixture(scope="module")

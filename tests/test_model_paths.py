@@ -66,8 +66,9 @@ import torch
 
 from oracle import smin_oracle as O
 from tests import helpers as H
+from tests.support.device import dev  # noqa: F401  (the module's device fixture)
+from tests.support.corpora import SCORE_TOL
 
-SCORE_TOL = 2e-5                                       # test_hip_parity.SCORE_TOL
 KEYS = ["T", "L", "C", "D", "dl", "layers", "Din", "Nq", "H", "B"]
 
 
@@ -222,7 +223,7 @@ def reference(sd, cfg, batch, dtype=torch.float64, cut=None, forward=cut_forward
 # fewer frames and a shorter query).  Shapes are the smallest that reach each form; constants and seeds were chosen on the CPU, by the
 # five conditions below, before anything ran on a GPU.
 CASES = {
-    # test_hip_parity.NATIVE_ROWS[0], attention form <64,4,T>: the node, the node with input gradients, and both Python hosts
+    # NATIVE_ROWS[0] of tests/support/corpora.py, attention form <64,4,T>: the node, the node with input gradients, and both Python hosts
     "native2": ((64, 16, 4, 128, 64, 2, 40, 9, 64, 3), dict(START, lstm=3.5, loc=0.2), 208),
     # test_against_oracle_random's first row: two ragged samples with short queries among five
     "ragged5": ((64, 16, 4, 64, 32, 2, 40, 9, 32, 5), dict(START, loc=0.2), 144),
@@ -403,14 +404,6 @@ def test_the_ragged_case_is_ragged():
 RAISED = {
     ("deep5", "smis.4.content_unit.attn_layer.W_k.bias"): (0.894, 1.8),
 }
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    import models
-    models.vml_amd._lib.load()          # fail loudly if libsmin_hip.so is missing
-    return torch.device("cuda:0")
 
 
 def test_raised_bounds_stay_within_the_reference_noise():

@@ -25,7 +25,9 @@ import numpy as np
 import pytest
 import torch
 
-from tests.test_moments import _api, check_against_py, py_iou, py_nms, py_scores
+from tests.helpers import cdiv
+from tests.support.device import dev  # noqa: F401  (the module's device fixture)
+from tests.support.references import _api, check_against_py, py_iou, py_nms, py_scores
 
 CAND = 4096                       # csrc/moments.hip: candidate keys the NMS workgroup holds
 MAX_BANDS, MIN_BAND = 32, 1024    # csrc/moments.hip band_count
@@ -167,10 +169,6 @@ def assert_row(r, b, want, what):
 
 
 # ---------------------------------------------------------------- the layout model (band_count / ws_layout of csrc/moments.hip)
-def cdiv(a, b):
-    return -(-a // b)
-
-
 def layout(B, L):
     """(P, MB, band): bands per sample, keys each band hands over, cells per band."""
     n = L * L
@@ -443,14 +441,6 @@ def test_rule0_reference_by_hand():
 
 
 # ---------------------------------------------------------------- GPU
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    import models
-    models.vml_amd._lib.load()
-    return torch.device("cuda:0")
-
-
 @functools.lru_cache(maxsize=None)
 def torch_lists(L, rows, k, thr):
     """top_moments_torch of the first `rows` family samples at L."""

@@ -7,40 +7,11 @@ import pytest
 import torch
 
 from tests import helpers as H
+from tests.support.device import dev  # noqa: F401  (the module's device fixture)
+from tests.support.references import _api, check_against_py, py_nms, py_scores
 
 
 # ---------------------------------------------------------------- independent reference (definition, plain Python)
-def py_scores(pm, ps, pe):
-    """fp32 score (pm * sqrt(ps_i)) * sqrt(pe_j), -0 -> +0 (numpy fp32 ops are correctly rounded)."""
-    pm, ps, pe = (np.asarray(x, dtype=np.float32) for x in (pm, ps, pe))
-    s = (pm * np.sqrt(ps)[:, None]) * np.sqrt(pe)[None, :]
-    return np.where(s == 0, np.float32(0), s).astype(np.float32)
-
-
-def py_iou(a, b):
-    (i1, j1), (i2, j2) = a, b
-    inter = max(0, min(j1, j2) + 1 - max(i1, i2))
-    union = max(j1, j2) + 1 - min(i1, i2)
-    return np.float32(inter) / np.float32(union)
-
-
-def py_nms(pm, ps, pe, mm, k, thr):
-    """One sample: [(i, j, score)] kept in order."""
-    L = pm.shape[0]
-    s = py_scores(pm, ps, pe)
-    cand = [(-float(s[i, j]), i * L + j) for i in range(L) for j in range(L) if mm[i, j]]
-    cand.sort()
-    t = np.float32(thr)
-    kept = []
-    for _, c in cand:
-        if len(kept) >= k:
-            break
-        cell = (c // L, c % L)
-        if all(not (py_iou(cell, (a, b)) > t) for a, b, _ in kept):
-            kept.append((cell[0], cell[1], s[cell]))
-    return kept
-
-
 def ragged(B, L, seed, dense_pm=False):
     g = torch.Generator().manual_seed(seed)
     lens = torch.randint(1, L + 1, (B,), generator=g)
@@ -53,23 +24,7 @@ def ragged(B, L, seed, dense_pm=False):
     return pm, torch.rand(B, L, generator=g), torch.rand(B, L, generator=g), mm
 
 
-def check_against_py(r, pm, ps, pe, mm, k, thr):
-    B = pm.shape[0]
-    for b in range(B):
-        want = py_nms(pm[b].numpy(), ps[b].numpy(), pe[b].numpy(), mm[b].numpy(), k, thr)
-        n = len(want)
-        assert int(r["count"][b]) == n
-        assert r["idx"][b, :n].tolist() == [[i, j] for i, j, _ in want], (b, k, thr)
-        assert np.array_equal(r["score"][b, :n].numpy().view(np.int32), np.array([s for _, _, s in want], np.float32).view(np.int32))
-        assert (r["idx"][b, n:] == -1).all() and (r["score"][b, n:] == 0).all()
-
-
 # ---------------------------------------------------------------- CPU
-def _api():
-    import models
-    return models.vml_amd
-
-
 @pytest.mark.parametrize("L", [1, 3, 16, 64])
 def test_torch_restatement_equals_python_nms(L):
     api = _api()
@@ -171,14 +126,6 @@ def test_localize_adds_no_parameters():
 
 
 # ---------------------------------------------------------------- GPU
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    import models
-    models.vml_amd._lib.load()
-    return torch.device("cuda:0")
-
-
 def _same(got, want):
     assert torch.equal(got["count"].cpu(), want["count"])
     assert torch.equal(got["idx"].cpu(), want["idx"])

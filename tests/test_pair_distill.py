@@ -21,9 +21,14 @@ import warnings
 import pytest
 import torch
 
-from tests.test_pair_rank_loss import NQ, NV, bits, checked, full_group, hand_step, mined_plan, on, plan_of, probe, same_parameters, synthetic
-from tests.test_pair_training import GT_VIDEO, TINY_SHAPE, V, corpus_inputs, tiny_model
-from tests.test_prefilter import BAND, banded, bands_intact
+from tests.support.device import dev  # noqa: F401  (the module's device fixture)
+from tests.support.device import vml as V
+from tests.support.compare import bits
+from tests.support.guards import banded, bands_intact, BAND
+from tests.support.corpora import world  # noqa: F401  (fixture)
+from tests.support.corpora import (
+    checked, corpus_inputs, full_group, hand_step, mined_plan, plan_of, probe, same_parameters, synthetic, tiny_model, GT_VIDEO, NQ, NV, QI9,
+    TINY_SHAPE, VI9)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = ("smin_pair_distill_fwd", "smin_pair_distill_ws_bytes")
@@ -173,7 +178,6 @@ def test_torch_route_by_hand(P, Q, temps):
 
 def test_the_vi9_plan_needs_no_positive_flags():
     A = V()
-    from tests.test_pair_training import QI9, VI9
     bare = A.PairPlan(VI9, QI9, NV, NQ, "cpu")
     assert bare.positive is None and bare.q_ptr.tolist() == [0, 3, 7, 9, 9]
     x = synthetic(9, 3, seed=14, dtype=torch.float64)
@@ -353,13 +357,6 @@ def test_refusals_on_the_host():
 
 
 # ---------------------------------------------------------------- GPU: the kernel
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    V()._lib.load()
-    return torch.device("cuda:0")
-
-
 def kernel_route(x, plan, teacher, temps, dev, upstream=3.0):
     pm, ps, pe = (t.to(dev).requires_grad_(True) for t in x[:3])
     loss, stats, score = V().pair_distill_loss(pm, ps, pe, x[3].to(dev), plan, teacher.to(dev), *temps, return_stats=True)
@@ -632,13 +629,6 @@ def test_rejections_leave_the_outputs_untouched(dev):
 
 
 # ---------------------------------------------------------------- GPU: the model and the loops
-@pytest.fixture(scope="module")
-def world(dev):
-    m, sd = tiny_model(dev)
-    vid, qry, tg = corpus_inputs()
-    return dict(m=m, sd=sd, vid=vid, qry=qry, tg=tg, vid_d=on(dev, vid), qry_d=on(dev, qry), tg_d=on(dev, tg))
-
-
 def banks(m, g):
     with torch.no_grad():
         videos = m.encode_videos(g["video_features"], g["video_mask"], g["length_mask"], g["moment_mask"], cell_counts=g.get("cell_counts"))

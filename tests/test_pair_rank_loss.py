@@ -18,78 +18,18 @@ import re
 import pytest
 import torch
 
-from tests.test_pair_training import GT_VIDEO, QI9, VI9, V, corpus_inputs, expand, loss_of, p19_lists, pair_args, tiny_model
+from tests.support.device import dev  # noqa: F401  (the module's device fixture)
+from tests.support.device import vml as V
+from tests.support.compare import bits
+from tests.support.corpora import world  # noqa: F401  (fixture)
+from tests.support.corpora import (
+    checked, expand, full_group, hand_step, loss_of, mined_plan, p19_lists, pair_args, plan_of, probe, same_parameters, synthetic, tiny_model,
+    GT_VIDEO, NQ, NV, QI9, VI9)
+from tests.support.references import abi_call
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NV, NQ = 5, 4
-FULL = (8, 8, 8, 8, 8)
 TEMPS = [(1.0, 1.0), (0.1, 0.1), (0.01, 0.05)]
 NAMES = ("smin_pair_rank_fwd", "smin_pair_rank_bwd", "smin_pair_rank_ws_bytes")
-
-
-def bits(t):
-    return t.detach().cpu().contiguous().view(torch.int32)
-
-
-def mined_arrays(Q=3, Vn=5, N=2, seed=11):
-    """a mined layout from mine_pairs_torch on the CPU: the six arrays, the positive flags and gt_video"""
-    g = torch.Generator().manual_seed(seed)
-    score = torch.randn(Q, Vn, generator=g)
-    gt = torch.randint(0, Vn, (Q,), generator=g).tolist()
-    arrays = V().mine_pairs_torch(score, gt, N)
-    P = Q * (1 + N)
-    positive = torch.tensor([int(p % (1 + N) == 0) for p in range(P)], dtype=torch.int32)
-    return arrays, positive, gt, Vn, Q
-
-
-def mined_plan(dev="cpu", **kw):
-    arrays, positive, _, Vn, Q = mined_arrays(**kw)
-    rows = torch.nonzero(positive).reshape(-1)
-    return V().PairPlan.from_device(*[a.to(dev) for a in arrays], Vn, Q, positive=positive.to(dev), positive_rows=rows.to(dev), num_positive=Q)
-
-
-def plan_of(P, Q, dev="cpu"):
-    """the plan of a (P, Q) case: the VI9 lists (query 1 has two positives, query 2 pairs but no positive, query 3 no pair), the
-    P = 19 lists of test_pair_training, or small hand-made lists"""
-    api = V()
-    if (P, Q) == (9, 4):
-        return api.PairPlan(VI9, QI9, NV, NQ, dev, gt_video=GT_VIDEO)
-    if (P, Q) == (19, 4):
-        vi, qi = p19_lists()
-        return api.PairPlan(vi, qi, NV, NQ, dev, gt_video=GT_VIDEO)
-    if (P, Q) == (1, 1):
-        return api.PairPlan([0], [0], 1, 1, dev, gt_video=[0])
-    if (P, Q) == (6, 2):
-        return api.PairPlan([0, 0, 1, 1, 2, 2], [0, 1, 0, 1, 0, 1], 3, 2, dev, gt_video=[1, 2])
-    if (P, Q) == (2, 1):
-        return api.PairPlan([0, 1], [0, 0], 2, 1, dev, gt_video=[0])
-    raise KeyError((P, Q))
-
-
-def synthetic(P, L, seed, dtype=torch.float32):
-    """uniform pm, ps, pe in [0, 1] with exact 0 forced into ps and pe and exact 0 and 1 into pm, ragged upper-triangular masks and,
-    for P > 2, one pair without a valid cell (at P = 2 it would be the query's only negative, with s = 0: at gamma = 0.05 its softmax
-    weight exp(-18) is below fp32's unit roundoff beside 1, every fp32 route gives loss 0 and zero gradients, and the case checks nothing)"""
-    g = torch.Generator().manual_seed(seed)
-    pm, ps, pe = torch.rand(P, L, L, generator=g), torch.rand(P, L, generator=g), torch.rand(P, L, generator=g)
-    n = torch.randint(1, L + 1, (P,), generator=g)
-    n[0] = L
-    lm = torch.arange(L).unsqueeze(0) < n.unsqueeze(1)
-    mm = torch.triu(lm.unsqueeze(2) & lm.unsqueeze(1))
-    if P > 2:
-        mm[P // 2] = False
-    if P > 1:
-        for p in range(P):
-            last = int(n[p]) - 1
-            if p % 3 == 0:
-                ps[p, 0] = 0.0
-            if p % 4 == 1:
-                pe[p, last] = 0.0
-            if p % 2 == 0:
-                pm[p, 0, last] = 1.0
-            if p % 3 == 1:
-                pm[p, 0, 0] = 0.0
-    return pm.to(dtype), ps.to(dtype), pe.to(dtype), mm
 
 
 def by_hand(pm, ps, pe, mm, q_ptr, q_pairs, positive, tau, gamma):
@@ -247,13 +187,6 @@ def test_refusals():
 
 
 # ---------------------------------------------------------------- GPU
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    V()._lib.load()
-    return torch.device("cuda:0")
-
-
 def kernel_route(x, plan, tau, gamma, dev, upstream=3.0):
     pm, ps, pe = (t.to(dev).requires_grad_(True) for t in x[:3])
     loss, stats, score = V().pair_rank_loss(pm, ps, pe, x[3].to(dev), plan, tau, gamma, return_stats=True)
@@ -307,29 +240,6 @@ def test_kernels_against_fp64(dev, P, Q, L, tau, gamma):
         assert e_k <= 32 * e_t + 1e-6, (name, e_k, e_t)
     if not x[3].all():
         assert got[3].cpu()[~x[3]].abs().max().item() == 0.0
-
-
-def abi_call(dev, x, plan, tau=0.1, gamma=0.1, fill=float("nan"), **kw):
-    """smin_pair_rank_fwd and smin_pair_rank_bwd through the C ABI over outputs pre-filled with ``fill``; kw overrides arguments of the
-    forward by name.  Returns (rc_fwd, forward outputs, rc_bwd, backward outputs)."""
-    L_ = V()._lib
-    lib = L_.load()
-    P, L = x[1].shape
-    Q = plan.Q
-    pm, ps, pe = (t.to(dev).contiguous() for t in x[:3])
-    mm = x[3].to(dev).contiguous()
-    full = lambda *shape: torch.full(shape, fill, dtype=torch.float32, device=dev)
-    outs = dict(loss=full(1), stats=full(2), score=full(P), coef=full(P), pool=full(P, 2))
-    nbytes = lib.smin_pair_rank_ws_bytes(P, Q, L)
-    ws = torch.zeros(max(nbytes, 16), dtype=torch.uint8, device=dev)
-    a = dict(pm=pm, ps=ps, pe=pe, mm=mm, q_ptr=plan.q_ptr, q_pairs=plan.q_pairs, positive=plan.positive, P=P, Q=Q, L=L, tau=tau, gamma=gamma,
-             ws=ws, ws_bytes=nbytes, **outs)
-    a.update(kw)
-    p = lambda k: L_.ptr(a[k])
-    rc = lib.smin_pair_rank_fwd(L_.stream(), p("pm"), p("ps"), p("pe"), p("mm"), p("q_ptr"), p("q_pairs"), p("positive"), a["P"], a["Q"], a["L"],
-                                a["tau"], a["gamma"], p("loss"), p("stats"), p("score"), p("coef"), p("pool"), p("ws"), a["ws_bytes"])
-    torch.cuda.synchronize()
-    return rc, outs, a
 
 
 def abi_bwd(dev, a, fill=float("nan"), **kw):
@@ -436,17 +346,6 @@ def test_rejections_leave_the_outputs_untouched(dev):
 
 
 # ---------------------------------------------------------------- through the model
-def on(dev, d):
-    return {k: v.to(dev) for k, v in d.items()}
-
-
-@pytest.fixture(scope="module")
-def world(dev):
-    m, sd = tiny_model(dev)
-    vid, qry, tg = corpus_inputs()
-    return dict(m=m, sd=sd, vid=vid, qry=qry, tg=tg, vid_d=on(dev, vid), qry_d=on(dev, qry), tg_d=on(dev, tg))
-
-
 def oracle_grads(w, vi, qi, weight=0.5):
     """the fp64 oracle with autograd on the expanded pairs, loss_fn + weight * pair_rank_loss_torch in fp64: {name: gradient}"""
     from oracle import smin_oracle as O
@@ -517,55 +416,6 @@ def test_model_gradients_on_a_mined_plan(dev, world):
 
 
 # ---------------------------------------------------------------- the loops
-def full_group(dev, seed=3, lists=True):
-    vid, qry, tg = corpus_inputs(snips=FULL, seed=seed)
-    g = dict(**on(dev, vid), **on(dev, qry), **on(dev, tg), gt_video=GT_VIDEO, cell_counts=[36] * NV)
-    if lists:
-        g.update(video_index=VI9, query_index=QI9)
-    return g
-
-
-def probe(api):
-    class Probe(api.EpochMeter):
-        reads = 0
-
-        def result(self, group=None):
-            Probe.reads += 1
-            torch.cuda.set_sync_debug_mode("default")
-            return super().result(group)
-    return Probe
-
-
-def checked(fn):
-    torch.cuda.synchronize()
-    mode = torch.cuda.get_sync_debug_mode()
-    torch.cuda.set_sync_debug_mode("error")
-    try:
-        return fn()
-    finally:
-        torch.cuda.set_sync_debug_mode(mode)
-
-
-def hand_step(api, model, g, plan, weight, opt=None):
-    """the parent's _pair_step by hand, plus weight * pair_rank_loss when weight is not None; returns the loss"""
-    if opt is not None:
-        opt.zero_grad()
-    out = model.forward_pairs(*[g[k] for k in api.training.MODEL_INPUTS], None, None, cell_counts=g["cell_counts"], plan=plan)
-    t = api.pair_targets(g, g, None, None, None, plan=plan)
-    loss = loss_of(api.loss_fn, out, t)
-    if weight is not None:
-        loss = loss + weight * api.pair_rank_loss(out[0], out[1], out[2], t["moment_mask"], plan)
-    if opt is not None:
-        loss.backward()
-        opt.step()
-    return loss
-
-
-def same_parameters(a, b):
-    for (k, p), (_, r) in zip(a.named_parameters(), b.named_parameters()):
-        assert torch.equal(bits(p), bits(r)), k
-
-
 @pytest.mark.gpu
 def test_train_epoch_pairs_with_the_term(dev, world):
     api = V()

@@ -20,72 +20,16 @@ import numpy as np
 import pytest
 import torch
 
-from tests import helpers as H
+from tests.support.device import dev  # noqa: F401  (the module's device fixture)
+from tests.support.device import vml as V
+from tests.support.compare import bits
+from tests.support.corpora import corpus_inputs, expand, loss_of, p19_lists, pair_args, tiny_model, GT_VIDEO, QI9, SCORE_TOL, VI9
 
-SCORE_TOL = 2e-5                                       # test_score_path.SCORE_TOL
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-TINY_SHAPE = (16, 8, 4, 32, 16, 2, 24, 5, 16)          # T, L, C, D, dl, layers, Din, Nq, H
 U = 2.0 ** -24                                         # fp32 unit roundoff
-# P = 9 over V = 5, Q = 4: video 0 and query 0 have three pairs, video 3 and query 3 none, pair (0, 1) is listed twice
-VI9, QI9 = [0, 2, 0, 1, 4, 0, 2, 4, 2], [1, 0, 1, 2, 0, 2, 0, 1, 1]
-GT_VIDEO = [2, 0, 3, 1]                                # queries 0 and 1 have their own video among VI9 / QI9's pairs (p = 1, 6 and 0, 2)
 MASKS = ("video_mask", "length_mask", "moment_mask")
 TARGETS = ("ym", "sm", "ys", "ss", "ye", "se", "ya")
-
-
-def V():
-    import models
-    return models.vml_amd
-
-
-def tiny_model(dev=None):
-    import models
-    from oracle import smin_oracle as O
-    sd = O.formula_state_dict(H.smin_shapes(*TINY_SHAPE), gain=1.2)
-    m = models.SMIN(*TINY_SHAPE) if dev is None else models.SMIN(*TINY_SHAPE, dev)
-    m.load_state_dict(sd, strict=True)
-    return (m if dev is None else m.to(dev)), sd
-
-
-def corpus_inputs(snips=(8, 1, 5, 8, 3), words=(5, 1, 3, 4), seed=3):
-    """V ragged videos and Q queries as host tensors (tests/test_corpus_search.py corpus_inputs), and the queries' loss targets
-    against their own videos GT_VIDEO."""
-    T, L, _, _, _, _, Din, Nq, _ = TINY_SHAPE
-    g = torch.Generator().manual_seed(seed)
-    nv, nq = len(snips), len(words)
-    vf, qf = torch.randn(nv, T, Din, generator=g), torch.randn(nq, Nq, 300, generator=g)
-    vmask, qmask = torch.zeros(nv, T, 1, dtype=torch.uint8), torch.zeros(nq, Nq, 1, dtype=torch.uint8)
-    lmask = torch.zeros(nv, L, dtype=torch.bool)
-    for v, s in enumerate(snips):
-        nf = s * (T // L) - (v % 2)                    # odd videos end inside their last snippet
-        vf[v, nf:] = 0
-        vmask[v, :nf] = 1
-        lmask[v, :s] = True
-    for q, w in enumerate(words):
-        qf[q, w:] = 0
-        qmask[q, :w] = 1
-    mmask = torch.triu(lmask.unsqueeze(2) & lmask.unsqueeze(1))
-    gt = torch.as_tensor(GT_VIDEO[:nq]) % nv
-    sm = torch.rand(nq, L, L, generator=g) * mmask[gt]
-    ss, se = torch.rand(nq, L, generator=g), torch.rand(nq, L, generator=g)
-    tg = dict(sm=sm, ym=sm > 0.5, ss=ss, ys=ss > 0.5, se=se, ye=se > 0.5, ya=torch.rand(nq, L, generator=g) > 0.5)
-    return dict(video_features=vf, video_mask=vmask, length_mask=lmask, moment_mask=mmask), dict(query_features=qf, query_mask=qmask), tg
-
-
-def expand(vid, qry, vi, qi):
-    """the six forward inputs of the pairs (vi[p], qi[p])"""
-    vi, qi = torch.as_tensor(vi, dtype=torch.int64), torch.as_tensor(qi, dtype=torch.int64)
-    vi, qi = vi.to(vid["video_features"].device), qi.to(vid["video_features"].device)
-    return [vid["video_features"][vi], vid["video_mask"][vi], qry["query_features"][qi], qry["query_mask"][qi], vid["length_mask"][vi],
-            vid["moment_mask"][vi]]
-
-
-def pair_args(vid, qry):
-    return [vid["video_features"], vid["video_mask"], qry["query_features"], qry["query_mask"], vid["length_mask"], vid["moment_mask"]]
-
-
-def loss_of(fn, out, t):
-    return fn(out[0], t["ym"], t["sm"], t["moment_mask"], out[1], t["ys"], t["ss"], out[2], t["ye"], t["se"], out[3], t["ya"], t["length_mask"])
 
 
 def csr(idx, n):
@@ -161,17 +105,6 @@ def test_pair_targets_by_hand():
 
 
 # ---------------------------------------------------------------- GPU
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    V()._lib.load()
-    return torch.device("cuda:0")
-
-
-def bits(t):
-    return t.detach().cpu().contiguous().view(torch.int32)
-
-
 def kernel_lists(P, nv, nq, seed):
     if (P, nv, nq) == (9, 5, 4):
         return np.array(VI9), np.array(QI9)
@@ -338,15 +271,6 @@ def test_identity_lists_are_forward(dev, world):
     for k in same:                                     # the same kernels on the same bits
         assert torch.equal(bits(g_new[k]), bits(g_exp[k])), k
     assert int(V()._lib.load_torch().layout_status(dev)[0]) == 0
-
-
-def p19_lists():
-    rng = np.random.RandomState(19)
-    vi, qi = rng.randint(0, 5, 19), rng.randint(0, 4, 19)
-    clash = (qi >= 2) & (vi == np.array(GT_VIDEO)[qi])
-    vi[clash] = (vi[clash] + 1) % 5                    # queries 2 and 3 never meet their own videos ...
-    vi[:2], qi[:2] = [2, 0], [0, 1]                    # ... queries 0 and 1 do
-    return vi.tolist(), qi.tolist()
 
 
 @pytest.mark.gpu

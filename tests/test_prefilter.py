@@ -17,25 +17,15 @@ import numpy as np
 import pytest
 import torch
 
-from tests import test_window_search as WS
-from tests.test_pair_training import GT_VIDEO, TINY_SHAPE, V, corpus_inputs, expand, tiny_model
+from tests.support import corpora as WS
+from tests.support.device import dev  # noqa: F401  (the module's device fixture)
+from tests.support.device import vml as V
+from tests.support.compare import byte_bits as bits, gate, same
+from tests.support.guards import banded, bands_intact, untouched, BAND
+from tests.support.corpora import corpus_inputs, expand, host_pairs, inputs, tiny_model, GT_VIDEO, NO_ROWS, SEARCH_KEYS, SHAPES, TINY_SHAPE
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TAUS = [1.0, 0.1, 0.01]
-SENTINEL = -12345.5
-BAND = 32
-SEARCH_KEYS = ("video", "idx", "score", "count")
-NO_ROWS = (8, 1, 0, 8, 3)                               # corpus_inputs' snippets with a video without rows at an even index
-
-
-def bits(t):
-    return t.detach().cpu().contiguous().view(torch.uint8)
-
-
-def same(got, want, keys, what):
-    for key in keys:
-        assert got[key].dtype == want[key].dtype and got[key].shape == want[key].shape, (what, key)
-        assert torch.equal(bits(got[key]), bits(want[key])), (what, key)
 
 
 def heads64(sd, D):
@@ -213,60 +203,6 @@ def test_refusals_on_the_host():
 
 
 # ---------------------------------------------------------------- GPU
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    V()._lib.load()
-    return torch.device("cuda:0")
-
-
-def gate(name, got, want, ref32):
-    """e_kernel <= 32 * e_torch32 + 1e-6 with e = max|x - x64| / max|x64|; a quantity that is identically 0 must come out exactly 0"""
-    g, w, r = got.detach().cpu().double(), want.detach().cpu().double(), ref32.detach().cpu().double()
-    assert g.shape == w.shape and torch.isfinite(g).all(), name
-    scale = w.abs().max().item() if w.numel() else 0.0
-    if scale == 0.0:
-        assert g.abs().max().item() == 0.0 if g.numel() else True, name
-        return
-    e_k, e_t = (g - w).abs().max().item() / scale, (r - w).abs().max().item() / scale
-    print(f"{name}: e_kernel {e_k:.2e}  e_torch32 {e_t:.2e}")
-    assert e_k <= 32 * e_t + 1e-6, (name, e_k, e_t)
-
-
-def banded(shape, dev, fill=float("nan")):
-    """a contiguous fp32 tensor of ``shape`` pre-filled with ``fill`` between two bands of SENTINEL: ``(the whole buffer, the view)``"""
-    n = int(np.prod(shape))
-    buf = torch.full((n + 2 * BAND,), SENTINEL, dtype=torch.float32, device=dev)
-    buf[BAND:BAND + n] = fill
-    return buf, buf[BAND:BAND + n].view(*shape)
-
-
-def bands_intact(buf):
-    return bool(buf[:BAND].eq(SENTINEL).all()) and bool(buf[-BAND:].eq(SENTINEL).all())
-
-
-SHAPES = [(4, 5, 16, 8, 4, 32), (5, 3, 20, 5, 3, 20), (44, 9, 16, 8, 4, 32), (3, 2, 64, 16, 4, 64)]      # Q, V, T, L, C, D
-_INPUTS = {}
-
-
-def inputs(shape, dev):
-    """random fp32 banks and heads and ragged masks of a shape; video V // 2 has no valid cell.  Made once per shape, with the fp64
-    restatement (maps included) at each tau computed on demand and kept."""
-    if shape in _INPUTS:
-        return _INPUTS[shape]
-    Q, Vn, T, L, C, D = shape
-    g = torch.Generator().manual_seed(sum(shape))
-    fv, fs = torch.randn(Vn, T, D, generator=g), torch.randn(Q, D, generator=g)
-    w, b = torch.randn(3, D, generator=g) / D ** 0.5, torch.randn(3, generator=g) / 2
-    lens = torch.randint(1, L + 1, (Vn,), generator=g)
-    lens[0], lens[Vn // 2] = L, 0
-    lm = torch.arange(L).unsqueeze(0) < lens.unsqueeze(1)
-    mm = torch.triu(lm.unsqueeze(2) & lm.unsqueeze(1))
-    x = dict(fv=fv.to(dev), fs=fs.to(dev), w=w.to(dev), b=b.to(dev), lm=lm.to(dev), mm=mm.to(dev), shape=shape, ref={})
-    _INPUTS[shape] = x
-    return x
-
-
 def references(x, tau):
     """(fp64 restatement, fp32 restatement) on the device, maps included: computed once per (shape, tau)"""
     A = V()
@@ -305,10 +241,6 @@ def scores_abi(dev, x, tau, maps=True, v0=0, v1=None, fill=float("nan"), ws_delt
     torch.cuda.synchronize()
     assert bool(ws_buf[:BAND].eq(77).all()) and bool(ws_buf[BAND + max(nbytes, 0):].eq(77).all()), "the workspace's neighbours were written"
     return rc, outs, bufs
-
-
-def untouched(outs, bufs):
-    return all(bands_intact(b) for b in bufs.values()) and all(bool(torch.isnan(o).all()) for o in outs.values())
 
 
 @pytest.mark.gpu
@@ -528,12 +460,6 @@ def test_prefilter_videos(dev, world):
     off = A.VideoBank(None, vb.video_features, vb.video_mask, vb.length_mask, vb.moment_mask, vb.cell_counts)
     with pytest.raises(ValueError, match="off the one-node path"):
         m.prefilter_videos(off, qb, 2)
-
-
-def host_pairs(video):
-    """the host (query, video) rows of prefilter_video (Q, Ms)"""
-    v = video.cpu().numpy()
-    return np.stack([np.repeat(np.arange(v.shape[0]), v.shape[1]), v.reshape(-1)], axis=1)
 
 
 @pytest.mark.gpu

@@ -19,10 +19,11 @@ import numpy as np
 import pytest
 import torch
 
-from tests.test_pair_training import GT_VIDEO, TINY_SHAPE, V, corpus_inputs, tiny_model
-from tests.test_prefilter import BAND, NO_ROWS, SEARCH_KEYS, SENTINEL, bits, same
-from tests.test_weighted_shards import GT_TIMES, video_shards
-from tests.test_window_shards import DURATION
+from tests.support.device import dev  # noqa: F401  (the module's device fixture)
+from tests.support.device import vml as V
+from tests.support.compare import byte_bits as bits, same
+from tests.support.guards import BAND, SENTINEL
+from tests.support.corpora import corpus_inputs, tiny_model, video_shards, DURATION, GT_TIMES, GT_VIDEO, NO_ROWS, SEARCH_KEYS, TINY_SHAPE
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PREFILTER_KEYS = ("prefilter_video", "prefilter_score", "prefilter_gt_rank")
@@ -243,13 +244,6 @@ class _FakeSurvivorModel:
 
 
 # ---------------------------------------------------------------- GPU
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    V()._lib.load()
-    return torch.device("cuda:0")
-
-
 def banded_like(t, dev):
     """``t`` (a host tensor) on the device between two bands of a sentinel of its dtype: ``(the whole buffer, the view)``"""
     n = t.numel()

@@ -19,9 +19,13 @@ import numpy as np
 import pytest
 import torch
 
-from tests.test_pair_rank_loss import NQ, NV, checked, full_group, hand_step, on, probe, same_parameters
-from tests.test_pair_training import GT_VIDEO, TINY_SHAPE, V, corpus_inputs, pair_args, tiny_model
-from tests.test_prefilter import BAND, NO_ROWS, banded, bands_intact, bits
+from tests.support.device import dev  # noqa: F401  (the module's device fixture)
+from tests.support.device import vml as V
+from tests.support.compare import byte_bits as bits
+from tests.support.guards import banded, bands_intact, untouched, BAND
+from tests.support.corpora import world  # noqa: F401  (fixture)
+from tests.support.corpora import (
+    checked, corpus_inputs, full_group, hand_step, on, pair_args, probe, same_parameters, tiny_model, GT_VIDEO, NO_ROWS, NQ, NV, TINY_SHAPE)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GRADS = ("dfv", "dfs", "dw", "db")
@@ -125,11 +129,6 @@ def test_all_pairs_plan():
 
 
 # ---------------------------------------------------------------- GPU, C ABI
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    V()._lib.load()
-    return torch.device("cuda:0")
 
 
 _INPUTS = {}
@@ -204,10 +203,6 @@ def bwd_abi(dev, x, maps, up=None, fill=float("nan"), ws_delta=0, **kw):
     torch.cuda.synchronize()
     assert bool(ws_buf[:BAND].eq(77).all()) and bool(ws_buf[BAND + max(nbytes, 0):].eq(77).all()), "the workspace's neighbours were written"
     return rc, outs, bufs
-
-
-def untouched(outs, bufs):
-    return all(bands_intact(b) for b in bufs.values()) and all(bool(torch.isnan(o).all()) for o in outs.values())
 
 
 def gate(name, got, want, ref32):
@@ -328,13 +323,6 @@ def test_prefilter_maps_is_the_abi(dev, shape, monkeypatch):
     monkeypatch.setattr(A.moments, "PREFILTER_WS_CAP", 1000)
     with pytest.raises(ValueError, match="workspace"):
         A.prefilter_maps(*leaves, x["lm"], x["mm"], T, L, C, 0.1)
-
-
-@pytest.fixture(scope="module")
-def world(dev):
-    m, sd = tiny_model(dev)
-    vid, qry, tg = corpus_inputs()
-    return dict(m=m, sd=sd, vid=vid, qry=qry, tg=tg, vid_d=on(dev, vid), qry_d=on(dev, qry), tg_d=on(dev, tg))
 
 
 def stacked_heads(m):

@@ -14,6 +14,10 @@ import pytest
 import torch
 
 from tests import helpers as H
+from tests.support.device import dev  # noqa: F401  (the module's device fixture)
+from tests.support.compare import _assert_spread, _spread
+from tests.support.guards import _vp
+from tests.support.references import _layout_to, lengths_mask, make_layout, moment_mask
 
 FWD_TOL = 1e-5          # max |got - ref| / max |ref|, per output and case
 GRAD_TOL = 1e-4
@@ -109,39 +113,6 @@ def score_heads_ref(fm, fb, cells, wm, bm, wb, bb, lmask):
 
 
 # ---------------------------------------------------------------- inputs
-
-def lengths_mask(B, L, lens):
-    return torch.arange(L).view(1, L) < torch.tensor(lens).view(B, 1)
-
-
-def moment_mask(B, L, kind, lens, g):
-    """Upper-triangular mask within each sample's length: "tri" (all of it), "ragged" (a random part), "band<k>" (j - i < k),
-    "none" (no cell)."""
-    lm = lengths_mask(B, L, lens)
-    tri = torch.triu(lm.unsqueeze(2) & lm.unsqueeze(1))
-    if kind == "tri":
-        return tri
-    if kind == "none":
-        return torch.zeros_like(tri)
-    if kind == "ragged":
-        return tri & (torch.rand(B, L, L, generator=g) < 0.6)
-    k = int(kind[4:])
-    ii, jj = torch.arange(L).view(L, 1), torch.arange(L).view(1, L)
-    return tri & ((jj - ii) < k)
-
-
-def make_layout(mm, layout):
-    import models
-    CL = models.vml_amd.CellLayout
-    return CL.from_mask(mm) if layout == "from_mask" else CL.all_cells(mm)
-
-
-def _layout_to(lay, dev):
-    import models
-    CL = models.vml_amd.CellLayout
-    return CL(lay.cells.to(dev), lay.row_ptr.to(dev), lay.cellmap.to(dev), lay.B, lay.L, None, lay.all_valid)
-
-
 def default_lens(B, L):
     """Full length for even samples, ragged for odd ones (the synthetic batch's pattern)."""
     return [L if b % 2 == 0 else max(1, L - 1 - (b * 7) % max(1, L // 2)) for b in range(B)]
@@ -533,15 +504,6 @@ def test_map_cases_reach_every_form():
 
 
 # ---------------------------------------------------------------- GPU helpers
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    import models
-    models.vml_amd._lib.load()
-    return torch.device("cuda:0")
-
-
 def _rel(got, ref, scale=0.0):
     """max |got - ref| / max(max |ref|, scale)"""
     if not ref.numel():
@@ -556,29 +518,6 @@ def _nan(shape, dev, dtype=torch.float32):
 def _ws_nan(nbytes, dev):
     w = _nan((max(1, cdiv(int(nbytes), 4)),), dev)
     return w, w.numel() * 4
-
-
-def _vp(t):
-    return None if t is None or t.numel() == 0 else ctypes.c_void_p(t.data_ptr())
-
-
-def _spread(logits, live):
-    """Mean over rows (with >= 2 live entries) of the standard deviation of the live logits (None: no such row)."""
-    live = live.expand_as(logits)
-    cnt = live.sum(-1)
-    ok = cnt >= 2
-    if not ok.any():
-        return None
-    x = torch.where(live, logits, 0.0)
-    mean = x.sum(-1) / cnt.clamp(min=1)
-    var = (torch.where(live, logits - mean.unsqueeze(-1), 0.0) ** 2).sum(-1) / (cnt - 1).clamp(min=1)
-    return var.sqrt()[ok].mean().item()
-
-
-def _assert_spread(logits, live, label, what):
-    """The softmaxes must be neither uniform nor saturated, or a dropped or doubled entry would hide."""
-    sd = _spread(logits, live)
-    assert sd is None or 0.5 <= sd <= 3.0, f"{label}: {what} logit spread {sd:.3f}"
 
 
 def _check(label, what, got, ref, tol, worst, key, scale=0.0):

@@ -12,6 +12,9 @@ import pytest
 import torch
 
 from tests.helpers import tn_splits      # gemm.h tn_splits (one mirror for every test file)
+from tests.helpers import cdiv
+from tests.support.device import dev  # noqa: F401  (the module's device fixture)
+from tests.support.compare import _rel
 
 FWD_TOL = 1e-5          # max |got - ref| / max |ref|, per output and case (as test_query_encoder_matches_packed_lstm)
 GRAD_TOL = 2e-4
@@ -75,10 +78,6 @@ def _live(length, B, Nq):
 # ---------------------------------------------------------------- Python mirrors of the layer dispatch
 
 CL_U, CL_BS, GEMM_SLOTS = 32, 4, 768
-
-
-def cdiv(a, b):
-    return -(-a // b)
 
 
 def cluster_ok(H, streamed_env=False):
@@ -324,19 +323,6 @@ def test_layer_cases_reach_every_regime():
 
 
 # ---------------------------------------------------------------- GPU
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    import models
-    models.vml_amd._lib.load()
-    return torch.device("cuda:0")
-
-
-def _rel(got, ref):
-    return (got.double().cpu() - ref).abs().max().item() / max(ref.abs().max().item(), 1e-30)
-
-
 def _gemm_mode():
     import models
     return models.vml_amd._lib.GEMM_MODES[models.vml_amd._lib.get_gemm_mode()]

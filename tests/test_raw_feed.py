@@ -10,25 +10,14 @@ import pytest
 import torch
 
 from tests import helpers as H
-
-
-def V():
-    import models
-    return models.vml_amd
+from tests.support.device import dev  # noqa: F401  (the module's device fixture)
+from tests.support.device import vml as V
+from tests.support.compare import same_tensor as same
 
 
 def fixture():
     z = np.load(os.path.join(H.GOLDEN, "g8_clip_sampling.npz"))
     return {k: z[k] for k in z.files}
-
-
-def bits(t):
-    t = t.detach().cpu().contiguous()
-    return t.view(torch.int32) if t.dtype == torch.float32 else t
-
-
-def same(a, b):
-    return a.shape == b.shape and a.dtype == b.dtype and torch.equal(bits(a), bits(b))
 
 
 # ---------------------------------------------------------------- CPU: the rule against the reference's fixture
@@ -118,13 +107,6 @@ def test_host_side_checks():
 
 
 # ---------------------------------------------------------------- GPU
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    V()._lib.load()
-    return torch.device("cuda:0")
-
-
 def mixed_lengths(B, T, rng):
     """n = 0, n >> T, n < T, n = T, n = T + 1, then draws from [0, 4T]."""
     base = [0, 13 * T + 7, max(T // 3, 1), T, T + 1, 2 * T, (5 * T) // 2]

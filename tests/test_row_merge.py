@@ -7,25 +7,16 @@ batch, the refusals; on the CPU, the gather between two gloo ranks and the resta
 The lists come from embed_tokens(sparse_grad=True) on per-list tables; the rows of their slots >= count are overwritten with NaN before
 any merge, so a merge that read one would show it."""
 import os
-import socket
 
 import pytest
 import torch
 import torch.multiprocessing as mp
 
+from tests.support.device import dev  # noqa: F401  (the module's device fixture)
+from tests.support.device import free_port, vml as A
+from tests.support.compare import same_state
+
 gpu = pytest.mark.gpu
-
-
-def A():
-    import models
-    return models.vml_amd
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    A()._lib.load()
-    return torch.device("cuda:0")
 
 
 def backward_rows(tok, table, dqf, **kw):
@@ -36,15 +27,7 @@ def backward_rows(tok, table, dqf, **kw):
     return table.row_grad
 
 
-def same_state(opt, ref, table, rtable):
-    p = table
-    assert torch.equal(p.detach().cpu(), rtable.detach()), "table"
-    assert torch.equal(opt.state[p]["exp_avg"].cpu(), ref.state[rtable]["exp_avg"]), "exp_avg"
-    assert torch.equal(opt.state[p]["exp_avg_sq"].cpu(), ref.state[rtable]["exp_avg_sq"]), "exp_avg_sq"
-    assert torch.equal(opt._state[:3].cpu(), ref._state[:3]), (opt._state, ref._state)
-
-
-def bits(x):
+def device_bits(x):
     return x.contiguous().view(torch.int32 if x.dtype == torch.float32 else torch.int64)
 
 
@@ -153,7 +136,7 @@ def test_merge_equals_the_torch_restatement_bitwise(dev, name, scale):
     count = int(ref.count.item())
     assert torch.equal(merged.count.cpu(), ref.count) and ref.pending
     assert torch.equal(merged.ids.cpu(), ref.ids)
-    assert torch.equal(bits(merged.rows[:count].cpu()), bits(ref.rows[:count]))
+    assert torch.equal(device_bits(merged.rows[:count].cpu()), device_bits(ref.rows[:count]))
     sq = float((merged.rows[:count].double() * merged.rows[:count].double()).sum())
     got = float(merged.sq_norm.item())
     print(name, scale, "count", count, "sq_norm", got, "fp64 of rows", sq, "rel", abs(got - sq) / max(sq, 1e-300))
@@ -170,8 +153,8 @@ def test_one_list_alone_comes_back_bit_for_bit(dev, name):
     count = int(rg.count.item())
     assert merged is not rg and merged.rows.data_ptr() != rg.rows.data_ptr()
     assert torch.equal(merged.count, rg.count) and torch.equal(merged.ids, rg.ids)
-    assert torch.equal(bits(merged.rows[:count]), bits(rg.rows[:count]))
-    assert torch.equal(bits(merged.sq_norm), bits(rg.sq_norm))
+    assert torch.equal(device_bits(merged.rows[:count]), device_bits(rg.rows[:count]))
+    assert torch.equal(device_bits(merged.sq_norm), device_bits(rg.sq_norm))
 
 
 @gpu
@@ -180,8 +163,8 @@ def test_two_runs_give_the_same_bits(dev):
     a = A().merge_row_grads(grads, scale=1.0 / 3.0)
     b = A().merge_row_grads(grads, scale=1.0 / 3.0)
     count = int(a.count.item())
-    assert torch.equal(a.ids, b.ids) and torch.equal(a.count, b.count) and torch.equal(bits(a.sq_norm), bits(b.sq_norm))
-    assert torch.equal(bits(a.rows[:count]), bits(b.rows[:count]))
+    assert torch.equal(a.ids, b.ids) and torch.equal(a.count, b.count) and torch.equal(device_bits(a.sq_norm), device_bits(b.sq_norm))
+    assert torch.equal(device_bits(a.rows[:count]), device_bits(b.rows[:count]))
 
 
 @gpu
@@ -323,14 +306,6 @@ def gloo_batch(step, rank):
     return torch.randint(-1, V + 1, (B, Nq), generator=g), draw_dqf((B, Nq), E, g)
 
 
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
-
-
 def _worker(rank, world, port, q):
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), WORLD_SIZE=str(world), RANK=str(rank), LOCAL_RANK=str(rank))
     torch.set_num_threads(2)
@@ -374,7 +349,7 @@ def test_two_gloo_ranks_end_with_the_same_table():
     call raises RuntimeError."""
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
-    port = _free_port()
+    port = free_port()
     procs = [ctx.Process(target=_worker, args=(r, 2, port, q)) for r in range(2)]
     for p in procs:
         p.start()
@@ -420,7 +395,7 @@ def test_torch_restatement_against_fp64():
         sq = float((m.rows[:count].double() ** 2).sum())
         assert abs(float(m.sq_norm) - sq) <= 1e-12 * sq
     for rg, (i, r) in zip(grads, kept):
-        assert rg.pending and torch.equal(rg.ids, i) and torch.equal(bits(rg.rows), bits(r))
+        assert rg.pending and torch.equal(rg.ids, i) and torch.equal(device_bits(rg.rows), device_bits(r))
     with pytest.raises(ValueError, match="16"):
         A().merge_row_grads_torch(grads * 4)
 

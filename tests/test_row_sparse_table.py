@@ -9,34 +9,13 @@ import math
 import pytest
 import torch
 
+from tests.support.device import dev  # noqa: F401  (the module's device fixture)
+from tests.support.device import vml as A
+from tests.support.compare import same_state
+from tests.support.corpora import build_model, loss_of_batch as loss_of, one_node_only
+from tests.support.references import backward_dense, backward_rows, batches
+
 gpu = pytest.mark.gpu
-
-
-def A():
-    import models
-    return models.vml_amd
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    A()._lib.load()
-    return torch.device("cuda:0")
-
-
-def backward_rows(tok, table, dqf):
-    """embed_tokens(sparse_grad=True) then backward of dqf: table.row_grad"""
-    qf, _, _ = A().embed_tokens(tok, table, differentiable=True, sparse_grad=True)
-    qf.backward(dqf)
-    assert table.grad is None
-    return table.row_grad
-
-
-def backward_dense(tok, table, dqf):
-    table.grad = None
-    qf, _, _ = A().embed_tokens(tok, table, differentiable=True)
-    qf.backward(dqf)
-    return table.grad
 
 
 def draw_tokens(case, g):
@@ -82,26 +61,6 @@ def test_rows_equal_the_dense_gradient_bitwise(dev, case):
     got = float(rg.sq_norm.item())
     print(case, "count", count, "sq_norm", got, "fp64 of dense", ref, "rel", abs(got - ref) / max(ref, 1e-300))
     assert rg.sq_norm.dtype == torch.float64 and abs(got - ref) <= 1e-9 * ref
-
-
-def batches(B, Nq, V, E, steps, seed, cover=False):
-    g = torch.Generator().manual_seed(seed)
-    out = []
-    for _ in range(steps):
-        tok = torch.randint(-1, V + 1, (B, Nq), generator=g)             # -1 and V: out of range
-        if cover:
-            tok = torch.randint(0, V, (B, Nq), generator=g)
-            tok.view(-1)[torch.randperm(B * Nq, generator=g)[:V]] = torch.arange(V)
-        out.append((tok, torch.randn(B, Nq, E, generator=g) * 10.0 ** torch.randint(-4, 2, (B, Nq, 1), generator=g).float()))
-    return out
-
-
-def same_state(opt, ref, table, rtable):
-    p = table
-    assert torch.equal(p.detach().cpu(), rtable.detach()), "table"
-    assert torch.equal(opt.state[p]["exp_avg"].cpu(), ref.state[rtable]["exp_avg"]), "exp_avg"
-    assert torch.equal(opt.state[p]["exp_avg_sq"].cpu(), ref.state[rtable]["exp_avg_sq"]), "exp_avg_sq"
-    assert torch.equal(opt._state[:3].cpu(), ref._state[:3]), (opt._state, ref._state)
 
 
 @gpu
@@ -256,7 +215,6 @@ def test_end_to_end_through_the_model(dev):
     batch untouched and changes the rows of the ids the queries hold."""
     from oracle import smin_oracle as O
     from tests import helpers as H
-    from tests.test_input_grads import build_model, loss_of, one_node_only
     T, L, C, D, dl, layers, Din, Nq, Hh, B, V = 64, 16, 4, 64, 32, 2, 40, 9, 32, 5, 60
     sd = O.formula_state_dict(H.smin_shapes(T, L, C, D, dl, layers, Din, Nq, Hh), gain=1.2)
     batch = O.synthetic_batch(B, T, L, Nq, Din, seed=17)

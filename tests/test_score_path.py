@@ -15,14 +15,13 @@ import pytest
 import torch
 
 from tests import helpers as H
+from tests.support.device import dev  # noqa: F401  (the module's device fixture)
+from tests.support.device import vml as V
+from tests.support.compare import layout_ok
+from tests.support.corpora import build_model, NATIVE_ROWS, SCORE_TOL
+from tests.support.references import collapsed_pm
 
-SCORE_TOL = 2e-5
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def V():
-    import models
-    return models.vml_amd
 
 
 # ---------------------------------------------------------------- host: surface
@@ -63,37 +62,6 @@ def test_score_fails_loudly_on_cpu_and_switch_is_off():
 
 
 # ---------------------------------------------------------------- host: the collapsed formula on the oracle's seams
-def collapsed_pm(sd, seams, batch, nl):
-    """pm of the collapsed last layer (fp32): ccmean re-formed from the last layer's inputs with the oracle's own pieces."""
-    from oracle import smin_oracle as O
-    score_tail_torch = V().functional.score_tail_torch
-    k = nl - 1
-    p = f"smis.{k}."
-    cp = p + "content_unit."
-    f_m = seams["fm"] if k == 0 else seams[f"mu{k - 1}"]
-    f_c = seams["fc"] if k == 0 else seams[f"cu{k - 1}"]
-    bu, fs, fw = seams[f"bu{k}"], seams["fs"], seams["fw"]
-    B, L, _, C, D = f_c.shape
-    dl = sd[cp + "linear_c_hat.weight"].shape[0]
-    m = batch["moment_mask"].float()[:, :, :, None, None]
-    qm = batch["query_mask"].float()
-    c_hat = O._lin(sd, cp + "linear_c_hat", f_c) * m
-    w_hat = O._lin(sd, cp + "linear_w_hat", fw) * qm
-    s_hat = O._lin(sd, cp + "linear_s_hat", fs)
-    att = O._word_attention(sd, cp + "attn_layer.", c_hat.reshape(B, L * L * C, dl), w_hat, w_hat, qm.reshape(B, 1, -1), dl).reshape(B, L, L, C, dl) * m
-    q = c_hat * (att + s_hat[:, None, None, None, :])
-    A = torch.softmax(q @ q.transpose(3, 4) / math.sqrt(dl), dim=-1) * m
-    ccmean = (A @ c_hat).mean(dim=3)
-    hbar = torch.sigmoid(f_m * fs[:, None, None, :]) * f_m
-    b_idx, i_idx, j_idx = (t.reshape(-1) for t in torch.meshgrid(torch.arange(B), torch.arange(L), torch.arange(L), indexing="ij"))
-    logit = score_tail_torch(ccmean.reshape(-1, dl), f_c.mean(dim=3).reshape(-1, D), hbar.reshape(-1, D), f_m.reshape(-1, D), bu, b_idx, i_idx, j_idx,
-                             sd[cp + "linear_c.weight"], sd[cp + "linear_c.bias"], sd[p + "moment_unit.conv_layer_fb.weight"].reshape(D, D),
-                             sd[p + "moment_unit.conv_layer_fc.weight"].reshape(D, D),
-                             sd[p + "moment_unit.conv_layer_fb.bias"] + sd[p + "moment_unit.conv_layer_fc.bias"],
-                             sd["localization.conv_layer_pm.weight"].reshape(D), sd["localization.conv_layer_pm.bias"])
-    return torch.sigmoid(logit).reshape(B, L, L) * batch["moment_mask"].float()
-
-
 @pytest.mark.parametrize("name", H.TINY)
 def test_collapsed_formula_reproduces_golden_pm(name):
     from oracle import smin_oracle as O
@@ -153,13 +121,6 @@ def test_tail_cases_reach_every_form():
 
 
 # ---------------------------------------------------------------- GPU
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    V()._lib.load()
-    return torch.device("cuda:0")
-
-
 def tail_inputs(case, seed):
     B, L, D, dl, has_hbar, lens = case
     g = torch.Generator().manual_seed(seed)
@@ -292,14 +253,6 @@ def test_tail_refusals(dev):
 
 
 # ---------------------------------------------------------------- GPU: the model
-def build_model(cfg, sd, dev):
-    import models
-    m = models.SMIN(cfg["T"], cfg["L"], cfg["C"], cfg["D"], cfg["dl"], cfg["layers"], cfg["Din"], cfg["Nq"], cfg["H"], dev)
-    missing = m.load_state_dict(sd, strict=True)
-    assert not missing.missing_keys and not missing.unexpected_keys
-    return m.to(dev)
-
-
 def formula_model(shape, dev, gain=1.2):
     from oracle import smin_oracle as O
     T, L, C, D, dl, layers, Din, Nq, Hh = shape
@@ -396,10 +349,9 @@ ORACLE_ROWS = [
 
 
 def test_oracle_rows_cover_the_native_rows():
-    from tests import test_hip_parity as P
     import models
     assert callable(models.SMIN.score)
-    assert set(P.NATIVE_ROWS) <= set(ORACLE_ROWS)
+    assert set(NATIVE_ROWS) <= set(ORACLE_ROWS)
     assert any(r[5] == 1 for r in ORACLE_ROWS) and any(r[9] == 1 for r in ORACLE_ROWS)
 
 
@@ -442,10 +394,6 @@ def window_inputs(dev, seed=4):
     qf = torch.randn(4, SMALL[7], 300, generator=g).to(dev)
     qm = (torch.arange(SMALL[7]).unsqueeze(0) < torch.tensor([7, 3, 5, 6]).unsqueeze(1)).to(torch.uint8).to(dev)
     return raw, lengths, qf, qm
-
-
-def layout_ok(dev):
-    return int(V()._lib.load_torch().layout_status(dev)[0]) == 0
 
 
 @pytest.mark.gpu

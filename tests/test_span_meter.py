@@ -6,20 +6,10 @@ import ctypes
 import pytest
 import torch
 
-from tests.test_window_training import NAN, bits64, edge_cases, py_span_hits, py_span_ious, random_spans
-
-
-def V():
-    import models
-    return models.vml_amd
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    import models
-    models.vml_amd._lib.load()
-    return torch.device("cuda", 0)
+from tests.support.device import dev  # noqa: F401  (the module's device fixture)
+from tests.support.device import vml as V
+from tests.support.compare import bits64
+from tests.support.references import edge_cases, py_span_hits, py_span_ious, random_spans, NAN
 
 
 def cells(B, L, seed):

@@ -16,6 +16,8 @@ import pytest
 import torch
 
 from tests import helpers as H
+from tests.support.device import dev  # noqa: F401  (the module's device fixture)
+from tests.support.device import vml as V
 
 SMALL = (64, 16, 4, 128, 32, 3, 40, 9, 64, 4)             # T, L, C, D, dl, layers, Din, Nq, H, B
 # (B, L): byte loop; one 16-byte load; exactly one ballot round; vector loads and two ballot rounds; exactly 1024 rows (one scan
@@ -29,18 +31,6 @@ PLACEMENT_SHAPES = [
     (64, 16, 4, 104, 48, 2, 24, 18, 52, 3),               # D % 32 != 0: torch forms them, on the second stream
     (32, 16, 4, 512, 128, 3, 64, 32, 256, 4),             # the cluster LSTM (H = 256) and dl = 128
 ]
-
-
-def V():
-    import models
-    return models.vml_amd
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    V()._lib.load()                                       # fail loudly if libsmin_hip.so is missing
-    return torch.device("cuda:0")
 
 
 # ---------------------------------------------------------------- the layout's specification

@@ -26,6 +26,8 @@ import torch
 
 from oracle import labels_oracle as LO
 from tests import helpers as H
+from tests.support.device import dev  # noqa: F401  (the module's device fixture)
+from tests.support.device import vml as V
 
 f32 = np.float32
 LS = (5, 16, 17, 32, 64)
@@ -34,11 +36,6 @@ GROUPS = [(T, L, split) for T, L in ((64, 16), (128, 32)) for split in ("val", "
 MASKS, LABELS = ("video_mask", "length_mask", "moment_mask"), ("ym", "ys", "ye", "ya")
 KEYS = ["video_features", "video_mask", "query_features", "query_mask", "length_mask", "moment_mask", "sm", "ym", "ss", "ys", "se", "ye", "ya"]
 GUARD, SENTINEL = H.LAYOUT_GUARD, H.LAYOUT_SENTINEL
-
-
-def V():
-    import models
-    return models.vml_amd
 
 
 @functools.lru_cache(maxsize=None)
@@ -277,13 +274,6 @@ def test_torch_form_fp32_times_behave_as_before():
 
 
 # ---------------------------------------------------------------- GPU
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    V()._lib.load()
-    return torch.device("cuda:0")
-
-
 def to_numpy(d):
     return {k: v.cpu().numpy() for k, v in d.items()}
 

@@ -19,9 +19,12 @@ import numpy as np
 import pytest
 import torch
 
-from tests import test_window_search as WS
-from tests.test_pair_rank_loss import abi_call, bits, synthetic
-from tests.test_pair_training import GT_VIDEO, V, corpus_inputs, tiny_model
+from tests.support import corpora as WS
+from tests.support.device import dev  # noqa: F401  (the module's device fixture)
+from tests.support.device import vml as V
+from tests.support.compare import bits, gate, same
+from tests.support.corpora import corpus_inputs, synthetic, tiny_model, window_host_banks, DURATION_TENSOR, GT_VIDEO, SEARCH_KEYS
+from tests.support.references import abi_call
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = {"smin_pair_pool": 11, "smin_group_pool": 9, "smin_video_rank": 16, "smin_moment_reweight": 10}
@@ -172,8 +175,8 @@ def test_refusals():
         A.rank_videos(*f32)
     with pytest.raises(err, match="no CPU fallback"):
         A.reweight_moments(torch.zeros(2, 3), torch.zeros(2, dtype=torch.int32), torch.zeros(2, dtype=torch.int32), torch.zeros(2))
-    m = WS.tiny_model()
-    wb, qb = WS.host_banks()
+    m, _ = tiny_model()
+    wb, qb = window_host_banks()
     for kw in (dict(video_weight=float("nan")), dict(video_weight=0.5, tau=0), dict(max_videos=0), dict(video_weight=0.5, n_videos=65),
                dict(video_weight=0.5, gt_video=[0, 1])):
         with pytest.raises(ValueError, match="video weight|tau|max_videos|n_videos|gt_video"):
@@ -233,26 +236,6 @@ def test_video_rank_meter_on_the_host():
 
 
 # ---------------------------------------------------------------- GPU
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    V()._lib.load()
-    return torch.device("cuda:0")
-
-
-def gate(name, got, want, ref32):
-    """e_kernel <= 32 * e_torch32 + 1e-6 with e = max|x - x64| / max|x64|; a quantity that is identically 0 must come out exactly 0"""
-    g, w, r = got.detach().cpu().double(), want.detach().cpu().double(), ref32.detach().cpu().double()
-    assert g.shape == w.shape and torch.isfinite(g).all(), name
-    scale = w.abs().max().item() if w.numel() else 0.0
-    if scale == 0.0:
-        assert g.abs().max().item() == 0.0 if g.numel() else True, name
-        return
-    e_k, e_t = (g - w).abs().max().item() / scale, (r - w).abs().max().item() / scale
-    print(f"{name}: e_kernel {e_k:.2e}  e_torch32 {e_t:.2e}")
-    assert e_k <= 32 * e_t + 1e-6, (name, e_k, e_t)
-
-
 def pool_abi(dev, x, temp, fill=float("nan"), **kw):
     """smin_pair_pool at tau = temp through the C ABI over outputs pre-filled with ``fill``; kw overrides arguments by name"""
     L_ = V()._lib
@@ -508,7 +491,6 @@ def test_c_abi_writes_everything_and_rejects_before_any_launch(dev):
     assert lib.smin_moment_reweight(L_.stream(), None, None, None, None, 0, k, 2, None, None) == 0  # P == 0 launches nothing
 
 
-SEARCH_KEYS = ("video", "idx", "score", "count")
 TAU = 0.1
 
 
@@ -527,12 +509,6 @@ def world(dev):
     return dict(m=m, vid_d=vid_d, qry_d=qry_d, vb=vb, qb=qb, raw=raw_d, wqf=qf_d, wqm=qm_d, wqb=wqb, wb=wb)
 
 
-def same(got, want, keys, what):
-    for key in keys:
-        assert got[key].dtype == want[key].dtype and got[key].shape == want[key].shape, (what, key)
-        assert torch.equal(got[key].cpu().contiguous().view(torch.uint8), want[key].cpu().contiguous().view(torch.uint8)), (what, key)
-
-
 @pytest.mark.gpu
 def test_search_at_neutral_settings_is_todays_search(dev, world):
     m, vb, qb = world["m"], world["vb"], world["qb"]
@@ -546,7 +522,7 @@ def test_search_at_neutral_settings_is_todays_search(dev, world):
     listed = [(3, 4), (0, 2), (2, 3), (0, 0)]
     same(m.search(vb, qb, pairs=listed, k=7, k_video=3, video_weight=0.0), m.search(vb, qb, pairs=listed, k=7, k_video=3), SEARCH_KEYS, "listed pairs")
     wb, wqb = world["wb"], world["wqb"]
-    kw0 = dict(duration=WS.DURATION.to(dev), max_batch=7, **WS.KW)
+    kw0 = dict(duration=DURATION_TENSOR.to(dev), max_batch=7, **WS.KW)
     want = m.search_windows(wb, wqb, **kw0)
     for kw in (dict(video_weight=0.0), dict(max_videos=5)):
         got = m.search_windows(wb, wqb, **kw0, **kw)
@@ -612,7 +588,7 @@ def test_weighted_window_search_with_the_video_cut(dev, world):
     m, wb, qb = world["m"], world["wb"], world["wqb"]
     gt = [0, 4, 2, 3]                                                                # video 3 has no rows: never a candidate
     kw = dict(max_batch=7, **WS.KW)
-    r = m.search_windows(wb, qb, video_weight=7.5, max_videos=2, tau=TAU, gt_video=gt, duration=WS.DURATION.to(dev), **kw)
+    r = m.search_windows(wb, qb, video_weight=7.5, max_videos=2, tau=TAU, gt_video=gt, duration=DURATION_TENSOR.to(dev), **kw)
     # the restatement: the same expansion, pools and groups from the public pieces, then search_windows_torch with the kernels' rank and weight
     _, p = m._window_search_plan("test", wb, qb, None, 5, 3, 3, 7, None)
     on = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev).to(torch.int32)
@@ -625,7 +601,7 @@ def test_weighted_window_search_with_the_video_cut(dev, world):
         cells.append(cl)
     gs, gc = A.group_pool(torch.cat(pool), torch.cat(cells), on(p["group_ptr"]), TAU)
     vr = A.rank_videos(gs, gc, on(p["vi"]), on(p["query_ptr"]), n=5, alpha=7.5, gt_video=on(np.asarray(gt)))
-    want = m.search_windows_torch(wb, qb, scorer=scorer, pair_rank=vr["pair_rank"], weight=vr["weight"], max_videos=2, duration=WS.DURATION.to(dev), **kw)
+    want = m.search_windows_torch(wb, qb, scorer=scorer, pair_rank=vr["pair_rank"], weight=vr["weight"], max_videos=2, duration=DURATION_TENSOR.to(dev), **kw)
     same(r, want, WS.KEYS + ("times",), "search_windows(video_weight=7.5, max_videos=2)")
     same(dict(video_rank=r["video_rank"], gt_rank=r["gt_rank"], video_count=r["video_count"]),
          dict(video_rank=vr["video"], gt_rank=vr["gt_rank"], video_count=vr["count"]), ("video_rank", "gt_rank", "video_count"), "the video ranking")

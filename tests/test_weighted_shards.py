@@ -10,13 +10,17 @@ import itertools
 import multiprocessing as mp
 import os
 import re
-import socket
 
 import numpy as np
 import pytest
 import torch
 
-from tests.test_window_search import SENTINEL, bits, checked_no_sync
+from tests.support import corpora as WS
+from tests.support.device import dev  # noqa: F401  (the module's device fixture)
+from tests.support.device import checked_no_sync, free_port, to_cpu, to_dev, vml as V
+from tests.support.compare import bits
+from tests.support.guards import WORD_SENTINEL as SENTINEL
+from tests.support.corpora import corpus_inputs, shard_dicts, tiny_model, video_shards, DURATION, GT_TIMES, SHARD_SPLITS
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NV, NQ, KV = 7, 3, 3
@@ -29,19 +33,6 @@ IDX_KEYS = ("video", "idx", "score", "raw", "count")
 SPAN_KEYS = ("video", "span", "score", "raw", "window", "cell", "count")
 RANK_KEYS = ("video_rank", "video_score", "video_count", "gt_rank")
 TALLY = {"cases": 0, "mismatches": 0}
-
-
-def V():
-    import models
-    return models.vml_amd
-
-
-def to_dev(r, dev):
-    return {key: v.to(dev) for key, v in r.items()}
-
-
-def to_cpu(r):
-    return {key: v.cpu() for key, v in r.items()}
 
 
 def same(got, want, keys, what=""):
@@ -255,14 +246,6 @@ def test_the_cut_needs_the_extra_slots():
 GLOO = dict(K=5, seed=4, split=[3, 4], alpha=7.5, cut=2, gt=[0, 3, 6])
 
 
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
-
-
 def _gloo_shards(spans):
     c = GLOO
     lists, pooled, cells = corpus(c["seed"], spans)
@@ -304,7 +287,7 @@ def test_two_gloo_ranks_return_the_one_bank_list():
     their matrices' width, raise ValueError on both."""
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
-    port = _free_port()
+    port = free_port()
     procs = [ctx.Process(target=_gather_worker, args=(r, 2, port, q)) for r in range(2)]
     for p in procs:
         p.start()
@@ -324,13 +307,6 @@ def test_two_gloo_ranks_return_the_one_bank_list():
 
 
 # ---------------------------------------------------------------- GPU: the kernels against the restatement
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    V()._lib.load()
-    return torch.device("cuda:0")
-
-
 def carry_lists(ks, Q, seed, spans, empty_query=None, full_query=None):
     """len(ks) lists in NO particular order: raw scores from a few values and random, local videos in [-2, 8) (a negative id inside a
     count: g outside [0, V)), counts in [-1, k_s + 1], NaN and -1 behind them."""
@@ -545,18 +521,9 @@ def test_merge_past_the_rank_tile_and_without_a_host_read(dev):
 
 
 # ---------------------------------------------------------------- GPU: the model-level routes
-from tests import test_window_search as WS                                               # noqa: E402
-from tests.test_pair_training import corpus_inputs, tiny_model                           # noqa: E402
-from tests.test_window_shards import DURATION, SHARD_SPLITS, shard_dicts                  # noqa: E402
 
 TAU = 0.1
 MARGIN = 4e-5                                                                            # 2 * SCORE_TOL
-GT_TIMES = np.stack([np.array([1.0, 0.5, 2.0, 0.0]), np.array([6.0, 3.0, 30.0, 5.0])], axis=1)
-
-
-def video_shards(vid_d, split, cell_counts):
-    e = np.concatenate([[0], np.cumsum(split)])
-    return [dict({k: v[a:b] for k, v in vid_d.items()}, duration=DURATION[a:b], cell_counts=cell_counts[a:b]) for a, b in zip(e[:-1], e[1:])]
 
 
 @pytest.fixture(scope="module")

@@ -11,20 +11,9 @@ import pytest
 import torch
 
 from tests import helpers as H
-
-
-def V():
-    import models
-    return models.vml_amd
-
-
-def bits(t):
-    t = t.detach().cpu().contiguous()
-    return t.view(torch.int32) if t.dtype == torch.float32 else t
-
-
-def same(a, b):
-    return tuple(a.shape) == tuple(b.shape) and a.dtype == b.dtype and torch.equal(bits(a), bits(b))
+from tests.support.device import dev  # noqa: F401  (the module's device fixture)
+from tests.support.device import vml as V
+from tests.support.compare import layout_ok, same_tensor as same
 
 
 def same_merge(got, want):
@@ -236,14 +225,6 @@ def test_localize_windows_refuses_bad_arguments_on_the_host():
 
 
 # ---------------------------------------------------------------- GPU
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    import models
-    models.vml_amd._lib.load()
-    return torch.device("cuda:0")
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("Din,T", [(4, 16), (500, 64), (500, 7)])
 @pytest.mark.parametrize("mode", ["pick", "mean"])
@@ -344,10 +325,6 @@ def restate(m, raw, lengths, qf, qm, video_index, window, stride, k, k_window, t
                                           cat(count, (0,), torch.int32), torch.tensor([w[2] for w in wins], dtype=torch.int64).reshape(G),
                                           torch.tensor([w[3] for w in wins], dtype=torch.int32).reshape(G), torch.from_numpy(pair_ptr.astype(np.int64)),
                                           T, L, k=k, nms_thresh=thr)
-
-
-def layout_ok(dev):
-    return int(V()._lib.load_torch().layout_status(dev)[0]) == 0
 
 
 @pytest.mark.gpu

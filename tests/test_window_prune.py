@@ -18,28 +18,20 @@ import numpy as np
 import pytest
 import torch
 
-from tests import test_window_search as WS
+from tests.support import corpora as WS
+from tests.support.device import dev  # noqa: F401  (the module's device fixture)
+from tests.support.device import checked_no_sync, vml as V
+from tests.support.compare import byte_bits as bits, same
+from tests.support.corpora import host_pairs, tiny_model, window_host_banks, DURATION_TENSOR, KW
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-V = WS.V
 CANARY = 0x5A5A5A5A
 BAND = 64
 KEYS = WS.KEYS + ("times",)
 VIDEO_KEYS = ("video_rank", "video_score", "video_count", "gt_rank")
 PF_KEYS = ("prefilter_video", "prefilter_score", "prefilter_gt_rank")
 GT_VIDEO = [0, 4, 2, 1]
-KW = dict(k=5, k_video=3, k_window=3)
 EQUAL_LENGTHS = (40, 16, 16, 0, 24)                    # window 16, stride 8: 4, 1, 1, 0, 2 windows of 16 rows each -- one cell count
-
-
-def bits(t):
-    return t.detach().cpu().contiguous().view(torch.uint8)
-
-
-def same(got, want, keys, what):
-    for key in keys:
-        assert got[key].dtype == want[key].dtype and got[key].shape == want[key].shape, (what, key)
-        assert torch.equal(bits(got[key]), bits(want[key])), (what, key)
 
 
 def py_expand(sel, vptr, W, cap):
@@ -117,8 +109,8 @@ def test_expand_restatement_against_a_loop(name):
 
 def test_expand_equals_the_host_plan():
     """group order, window order and pointers are _window_search_plan's for the same pairs sorted by (query, video)"""
-    m = WS.tiny_model()
-    wb, qb = WS.host_banks()
+    m, _ = tiny_model()
+    wb, qb = window_host_banks()
     sel = [[0, 4], [1, 3], [2, 4], [0, 1]]
     pairs = [(q, v) for q, row in enumerate(sel) for v in row]
     _, plan = m._window_search_plan("search_windows", wb, qb, pairs[::-1], 5, None, None, 64, None)
@@ -141,8 +133,8 @@ def test_survivor_window_capacity():
 
 def test_refusals_on_the_host():
     A = V()
-    m = WS.tiny_model()
-    wb, qb = WS.host_banks()
+    m, _ = tiny_model()
+    wb, qb = window_host_banks()
     with pytest.raises(ValueError, match="prefilter takes pairs=None and carry=False"):
         m.search_windows(wb, qb, prefilter=2, pairs=[(0, 1)])
     with pytest.raises(ValueError, match="prefilter takes pairs=None and carry=False"):
@@ -171,13 +163,6 @@ def test_refusals_on_the_host():
 
 
 # ---------------------------------------------------------------- GPU: the kernel
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    V()._lib.load()
-    return torch.device("cuda:0")
-
-
 def buffers(G, cap, dev):
     """the four outputs with BAND canary words behind each: (raw tensors, their real lengths)"""
     sizes = (G + 1, cap, cap, 1)
@@ -247,24 +232,18 @@ def test_window_expand_rejections_leave_the_outputs_untouched(dev):
 
 
 # ---------------------------------------------------------------- GPU: the pruned search
-def host_pairs(video):
-    """the host (query, video) rows of prefilter_video (Q, Ms)"""
-    v = video.cpu().numpy()
-    return np.stack([np.repeat(np.arange(v.shape[0]), v.shape[1]), v.reshape(-1)], axis=1)
-
-
 @pytest.fixture(scope="module")
 def world(dev):
     """the tiny model and test_window_search's corpus (5 videos, 8 windows, counts 4, 1, 1, 0, 2; 4 ragged queries) as banks, and a
     corpus of the same counts whose windows all have 16 rows"""
-    m = WS.tiny_model(dev)
+    m, _ = tiny_model(dev)
     raw, qf, qm = WS.corpus_rows(WS.SEED)
     raw_d, qf_d, qm_d = raw.to(dev), qf.to(dev), qm.to(dev)
     qb = m.encode_queries(qf_d, qm_d)
     wb = m.encode_windows(raw_d, WS.LENGTHS, WS.WINDOW, WS.STRIDE)
     eraw = torch.randn(sum(EQUAL_LENGTHS), WS.DIN, generator=torch.Generator().manual_seed(9)).to(dev)
     ewb = m.encode_windows(eraw, EQUAL_LENGTHS, WS.WINDOW, WS.STRIDE)
-    return dict(m=m, raw=raw_d, qf=qf_d, qm=qm_d, qb=qb, wb=wb, ewb=ewb, duration=WS.DURATION.to(dev))
+    return dict(m=m, raw=raw_d, qf=qf_d, qm=qm_d, qb=qb, wb=wb, ewb=ewb, duration=DURATION_TENSOR.to(dev))
 
 
 def plan_of(wb, video, cap):
@@ -354,7 +333,7 @@ def test_search_windows_prefilter_reads_nothing_back(dev, world):
     weighted = dict(video_weight=7.5, max_videos=1, gt_video=GT_VIDEO, **kw)
     first, first_w = m.search_windows(wb, qb, **kw), m.search_windows(wb, qb, **weighted)          # first use outside the checked region
     torch.cuda.synchronize()
-    second, second_w = WS.checked_no_sync(lambda: (m.search_windows(wb, qb, **kw), m.search_windows(wb, qb, **weighted)))
+    second, second_w = checked_no_sync(lambda: (m.search_windows(wb, qb, **kw), m.search_windows(wb, qb, **weighted)))
     same(second, first, KEYS + PF_KEYS + ("window_pairs",), "second run")
     same(second_w, first_w, KEYS + VIDEO_KEYS + PF_KEYS + ("window_pairs",), "second weighted run")
     assert int(V()._lib.load_torch().layout_status(dev)[0]) == 0                     # the handed-over counts matched the masks, padding included
@@ -363,7 +342,7 @@ def test_search_windows_prefilter_reads_nothing_back(dev, world):
     print("equal windows: cap", cap, "total", total)
     same(first, m.search_windows(wb, qb, pairs=host_pairs(first["prefilter_video"]), duration=world["duration"], max_batch=3, **KW), KEYS, "equal windows")
     with pytest.raises(RuntimeError, match="synchroniz"):                            # trim=True is the documented host read
-        WS.checked_no_sync(lambda: m.search_windows(wb, qb, trim=True, **kw))
+        checked_no_sync(lambda: m.search_windows(wb, qb, trim=True, **kw))
 
 
 @pytest.mark.gpu
@@ -380,7 +359,7 @@ def test_model_corpus_windows_prefilter(dev, world):
         meter.update({key: v.cpu() for key, v in r.items()}, torch.from_numpy(gt_video), torch.from_numpy(gt_times).float())
         return meter.result()
 
-    args = (m, raw, WS.LENGTHS, queries, gt_video, gt_times, WS.DURATION.numpy())
+    args = (m, raw, WS.LENGTHS, queries, gt_video, gt_times, DURATION_TENSOR.numpy())
     for M in (1, 2):
         pf = m.prefilter_videos(wb, qb, M, gt_video=GT_VIDEO)
         by_hand = totals(m.search_windows(wb, qb, pairs=host_pairs(pf["video"]), k=25, k_video=5, duration=world["duration"]))

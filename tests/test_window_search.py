@@ -15,70 +15,15 @@ import pytest
 import torch
 
 from tests import helpers as H
+from tests.support.device import dev  # noqa: F401  (the module's device fixture)
+from tests.support.device import checked_no_sync, vml as V
+from tests.support.compare import bits
+from tests.support.guards import WORD_SENTINEL as SENTINEL
+from tests.support.corpora import (
+    corpus_rows, host_masks, random_span_lists, same_lists, same_search, separated, tiny_model, window_host_banks as host_banks, DIN,
+    DURATION_TENSOR as DURATION, KEYS, KW, L, LENGTHS, LENS, NAN_BITS, SEED, STARTS, STRIDE, T, TINY_SHAPE, VPTR, WINDOW)
 
-SCORE_TOL = 2e-5                                       # test_score_path.SCORE_TOL
-MARGIN = 2 * SCORE_TOL
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-TINY_SHAPE = (16, 8, 4, 32, 16, 2, 24, 5, 16)          # T, L, C, D, dl, layers, Din, Nq, H (test_corpus_search.TINY_SHAPE)
-T, L, DIN, NQ = TINY_SHAPE[0], TINY_SHAPE[1], TINY_SHAPE[6], TINY_SHAPE[7]
-LENGTHS = (40, 16, 9, 0, 23)                           # window 16, stride 8: sampling.window_plan gives 4, 1, 1, 0, 2 windows
-WINDOW, STRIDE = 16, 8
-STARTS = [0, 8, 16, 24, 0, 0, 0, 7]
-LENS = [16, 16, 16, 16, 16, 9, 16, 16]
-VPTR = [0, 4, 5, 6, 6, 8]
-WORDS = (5, 1, 3, 4)
-SENTINEL = 0x5A5A5A5A
-NAN_BITS = 0x7FC00000
-
-
-def V():
-    import models
-    return models.vml_amd
-
-
-def tiny_model(dev=None):
-    import models
-    from oracle import smin_oracle as O
-    sd = O.formula_state_dict(H.smin_shapes(*TINY_SHAPE), gain=1.2)
-    m = models.SMIN(*TINY_SHAPE) if dev is None else models.SMIN(*TINY_SHAPE, dev)
-    m.load_state_dict(sd, strict=True)
-    return m if dev is None else m.to(dev)
-
-
-def corpus_rows(seed):
-    """the videos' rows back to back and the four ragged queries, host tensors"""
-    g = torch.Generator().manual_seed(seed)
-    raw = torch.randn(sum(LENGTHS), DIN, generator=g)
-    qf = torch.randn(len(WORDS), NQ, 300, generator=g)
-    qm = torch.zeros(len(WORDS), NQ, 1, dtype=torch.uint8)
-    for q, w in enumerate(WORDS):
-        qf[q, w:] = 0
-        qm[q, :w] = 1
-    return raw, qf, qm
-
-
-def host_masks(lens):
-    nf = np.minimum(np.asarray(lens), T)
-    n_len = np.ceil(nf / (T / L)).astype(np.int64)
-    vmask = (torch.arange(T).unsqueeze(0) < torch.from_numpy(nf).unsqueeze(1)).to(torch.uint8).unsqueeze(2)
-    lmask = torch.arange(L).unsqueeze(0) < torch.from_numpy(n_len).unsqueeze(1)
-    mmask = torch.triu(lmask.unsqueeze(2) & lmask.unsqueeze(1))
-    return vmask, lmask, mmask, [int(x * (x + 1) // 2) for x in n_len]
-
-
-def host_banks():
-    """a WindowBank of LENGTHS' windows and a QueryBank of four queries on the CPU, formed by hand (no encoder ran: fv is None)"""
-    A = V()
-    vmask, lmask, mmask, cells = host_masks(LENS)
-    i64 = lambda x: torch.tensor(x, dtype=torch.int64)
-    wb = A.WindowBank(None, None, vmask, lmask, mmask, cells, STARTS, LENS, VPTR, LENGTHS, i64(STARTS), torch.tensor(LENS, dtype=torch.int32), i64(VPTR),
-                      WINDOW, STRIDE)
-    _, qf, qm = corpus_rows(0)
-    return wb, A.QueryBank(None, None, qf, qm.reshape(len(WORDS), -1))
-
-
-def bits(t):
-    return t.detach().cpu().contiguous().view(torch.int32)
 
 
 # ---------------------------------------------------------------- host: surface
@@ -102,7 +47,7 @@ def test_header_and_table_declare_the_span_kernel():
 
 
 def test_methods_fail_loudly_on_cpu():
-    m = tiny_model()
+    m, _ = tiny_model()
     err = V()._lib.SminHipError
     raw, qf, qm = corpus_rows(0)
     with pytest.raises(err, match="no CPU fallback"):
@@ -115,7 +60,7 @@ def test_methods_fail_loudly_on_cpu():
 
 
 def test_refusals():
-    m = tiny_model()
+    m, _ = tiny_model()
     wb, qb = host_banks()
     assert len(wb) == 8 and wb.n_videos == 5
     for kw in (dict(k=0), dict(k=65), dict(k_video=0), dict(k_video=65), dict(k_window=0), dict(k_window=65), dict(max_batch=0), dict(k=2.0)):
@@ -148,7 +93,7 @@ def test_refusals():
 def test_model_corpus_windows_refuses_a_short_list():
     """k < max(n) * k_video: refused before anything runs (CPU tensors would raise SminHipError first otherwise)"""
     A = V()
-    m = tiny_model()
+    m, _ = tiny_model()
     raw, qf, qm = corpus_rows(0)
     queries = dict(query_features=qf, query_mask=qm)
     gt = np.tile([0.0, 1.0], (4, 1))
@@ -251,7 +196,7 @@ def test_corpus_span_topk_torch_by_hand():
 # ---------------------------------------------------------------- host: the expansion of search_windows by hand
 def test_expansion_plan_by_hand():
     A = V()
-    m = tiny_model()
+    m, _ = tiny_model()
     wb, qb = host_banks()
     assert [x.tolist() for x in A.window_plan(LENGTHS, WINDOW, STRIDE)] == [STARTS, LENS, VPTR]
     assert wb.cell_counts == tuple(A.cell_count(min(n, T), T, L) for n in LENS) == (36, 36, 36, 36, 36, 15, 36, 36)
@@ -294,7 +239,7 @@ def test_restated_search_on_a_cpu_bank(max_batch):
     """search_windows_torch with a scorer, on the CPU: the two stages spelled out group by group give its list, and the list has the
     properties of a search (ordered, within the video's rows, times by the stated formula)"""
     A = V()
-    m = tiny_model()
+    m, _ = tiny_model()
     wb, qb = host_banks()
     scorer = fake_scorer(wb)
     duration = torch.tensor([10.0, 3.5, 60.0, 7.25, 100.0])
@@ -332,7 +277,7 @@ def test_restated_search_on_a_cpu_bank(max_batch):
 def test_corpus_meter_takes_the_result_as_it_stands():
     """CorpusMeterTorch.update reads video, count and times of a search_windows-shaped result: no idx"""
     A = V()
-    m = tiny_model()
+    m, _ = tiny_model()
     wb, qb = host_banks()
     r = m.search_windows_torch(wb, qb, k=5, k_video=1, duration=torch.tensor([10.0, 3.5, 60.0, 7.25, 100.0]), scorer=fake_scorer(wb))
     assert "idx" not in r
@@ -343,47 +288,6 @@ def test_corpus_meter_takes_the_result_as_it_stands():
 
 
 # ---------------------------------------------------------------- GPU
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    V()._lib.load()
-    return torch.device("cuda:0")
-
-
-def random_span_lists(per_query, kv, seed, garbage):
-    """merge_window_moments-shaped lists of sum(per_query) groups: scores from six values (both zeros among them), so ties are everywhere;
-    counts in [0, kv]; distinct videos within a query; behind each count a NaN span, -1 and `garbage` as the score"""
-    g = torch.Generator().manual_seed(seed)
-    G2 = sum(per_query)
-    values = torch.tensor([0.9, 0.5, 0.25, 0.0, -0.0, 1e-3])
-    score = values[torch.randint(0, 6, (G2, kv), generator=g)]
-    span = torch.rand(G2, kv, 2, generator=g) * 100
-    window = torch.randint(0, 9, (G2, kv), generator=g, dtype=torch.int64)
-    cell = torch.randint(0, 64, (G2, kv, 2), generator=g, dtype=torch.int64)
-    count = torch.randint(0, kv + 1, (G2,), generator=g, dtype=torch.int32)
-    if G2:
-        count[0] = kv
-    if G2 > 1:
-        count[-1] = 0
-    video = torch.cat([torch.randperm(max(n, 1) + 5, generator=g)[:n] for n in per_query]).to(torch.int32) if G2 else torch.zeros(0, dtype=torch.int32)
-    ptr = torch.tensor(np.concatenate([[0], np.cumsum(per_query)]), dtype=torch.int32)
-    unused = torch.arange(kv).unsqueeze(0) >= count.unsqueeze(1)
-    score = torch.where(unused, torch.full_like(score, garbage), score)
-    span = torch.where(unused.unsqueeze(2), torch.full_like(span, float("nan")), span)
-    window = torch.where(unused, torch.full_like(window, -1), window)
-    cell = torch.where(unused.unsqueeze(2), torch.full_like(cell, -1), cell)
-    return span, score, window, cell, count, video, ptr
-
-
-KEYS = ("video", "span", "score", "window", "cell", "count")
-
-
-def same_lists(got, want, what=""):
-    for key in KEYS:
-        assert got[key].dtype == want[key].dtype and got[key].shape == want[key].shape, (what, key)
-        assert torch.equal(got[key].cpu().contiguous().view(torch.uint8), want[key].cpu().contiguous().view(torch.uint8)), (what, key)
-
-
 def through_ctypes(lists, K, dev):
     """smin_corpus_span_topk into buffers pre-filled with a sentinel and four spare words behind each: every element written, none beyond"""
     L_ = V()._lib
@@ -482,24 +386,10 @@ def test_corpus_span_topk_many_groups_none_and_rejections(dev):
     torch.cuda.synchronize()
 
 
-def checked_no_sync(fn):
-    mode = torch.cuda.get_sync_debug_mode()
-    torch.cuda.set_sync_debug_mode("error")
-    try:
-        return fn()
-    finally:
-        torch.cuda.set_sync_debug_mode(mode)
-
-
-SEED = 3
-KW = dict(k=5, k_video=3, k_window=3)
-DURATION = torch.tensor([10.0, 3.5, 60.0, 7.25, 100.0])
-
-
 @pytest.fixture(scope="module")
 def world(dev):
     """the tiny model, LENGTHS' rows, four ragged queries, the two banks, and the restated search at KW (computed once)"""
-    m = tiny_model(dev)
+    m, _ = tiny_model(dev)
     raw, qf, qm = corpus_rows(SEED)
     raw_d, qf_d, qm_d = raw.to(dev), qf.to(dev), qm.to(dev)
     qb = m.encode_queries(qf_d, qm_d)
@@ -557,33 +447,6 @@ def test_window_bank_mean_mode(dev, world):
     ref = m.encode_videos(vf, masks["video_mask"], masks["length_mask"], masks["moment_mask"])
     assert torch.equal(bits(wb.fv), bits(ref.fv)) and torch.equal(wb.moment_mask, ref.moment_mask) and wb.cell_counts == ref.cell_counts
     assert wb.video_features is None
-
-
-def separated(score, count):
-    """(Q, k) bool: the listed entries whose score differs from both neighbours in the list by more than MARGIN"""
-    Q, k = score.shape
-    listed = torch.arange(k).unsqueeze(0) < count.to(torch.int64).unsqueeze(1)
-    gap = (score[:, :-1] - score[:, 1:]).abs() > MARGIN
-    apart = torch.ones(Q, k, dtype=torch.bool)
-    apart[:, 1:] &= gap | ~listed[:, 1:]
-    apart[:, :-1] &= gap | ~listed[:, 1:]
-    return apart & listed
-
-
-def same_search(got, want, keys=("video", "window", "cell", "span")):
-    """the comparison of lists whose scores come from differently composed batches: equal counts, sorted scores within MARGIN, and
-    wherever the restatement's neighbouring scores differ by more than MARGIN the same entry, the span bit for bit"""
-    got = {key: v.cpu() for key, v in got.items()}
-    assert torch.equal(got["count"], want["count"])
-    diff = (got["score"] - want["score"]).abs().max().item() if want["score"].numel() else 0.0
-    assert diff < MARGIN, diff
-    sep = separated(want["score"], want["count"])
-    for key in keys:
-        g, w = got[key], want[key]
-        if key == "span":
-            g, w = bits(g), bits(w)
-        assert g.shape == w.shape and torch.equal(g[sep], w[sep]), key
-    return sep, diff
 
 
 @pytest.mark.gpu

@@ -11,31 +11,22 @@ import ctypes
 import multiprocessing as mp
 import os
 import re
-import socket
 
 import numpy as np
 import pytest
 import torch
 
-from tests.test_window_search import (KEYS, L, LENGTHS, LENS, MARGIN, NAN_BITS, SENTINEL, STRIDE, VPTR, WINDOW, bits, checked_no_sync, corpus_rows,
-                                      host_masks, same_lists, same_search, tiny_model)
+from tests.support.device import dev  # noqa: F401  (the module's device fixture)
+from tests.support.device import checked_no_sync, free_port, to_cpu, to_dev, vml as V
+from tests.support.compare import bits
+from tests.support.guards import WORD_SENTINEL as SENTINEL
+from tests.support.corpora import (
+    corpus_rows, host_masks, pair_lists, random_span_lists, same_lists, same_search, shard_dicts, shards_of as cell_shards, tiny_model, DURATION,
+    KEYS, KW, L, LENGTHS, LENS, MARGIN, NAN_BITS, SEED, SHARD_SPLITS, STRIDE, VPTR, WINDOW)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SPLITS = ([3, 4], [1, 1, 5], [7], [2, 2, 2, 1])
 VALUES = torch.tensor([0.9, 0.5, 0.25, 0.0, -0.0, 1e-3])                              # six scores, both zeros among them: ties everywhere
-
-
-def V():
-    import models
-    return models.vml_amd
-
-
-def to_dev(r, dev):
-    return {key: v.to(dev) for key, v in r.items()}
-
-
-def to_cpu(r):
-    return {key: v.cpu() for key, v in r.items()}
 
 
 # ---------------------------------------------------------------- shared data
@@ -208,7 +199,7 @@ def test_refusals():
         with pytest.raises(ValueError, match="both duration and n_rows"):
             f(lists, [0, 2], n_rows=torch.ones(4))
     # test_model_corpus_window_shards: before any device work (a host model and host tensors would raise SminHipError at the first encoder)
-    m = tiny_model()
+    m, _ = tiny_model()
     raw, qf, qm = corpus_rows(0)
     shards = [dict(raw=raw, lengths=LENGTHS, duration=np.ones(5))]
     queries = dict(query_features=qf, query_mask=qm)
@@ -226,14 +217,6 @@ def test_refusals():
 
 # ---------------------------------------------------------------- host: two gloo ranks
 GLOO = dict(nv=7, Q=3, kv=3, K=5, seed=4, split=[3, 4])
-
-
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
 
 
 def _gather_worker(rank, world, port, q):
@@ -262,7 +245,7 @@ def test_two_gloo_ranks_return_the_whole_corpus_list():
     raise ValueError on both."""
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
-    port = _free_port()
+    port = free_port()
     procs = [ctx.Process(target=_gather_worker, args=(r, 2, port, q)) for r in range(2)]
     for p in procs:
         p.start()
@@ -283,13 +266,6 @@ def test_two_gloo_ranks_return_the_whole_corpus_list():
 
 
 # ---------------------------------------------------------------- GPU
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    V()._lib.load()
-    return torch.device("cuda:0")
-
-
 def ranked_lists(ks, Q, seed, empty_query=None, full_query=None):
     """len(ks) ranked span lists ordered as search_windows orders them (score, then video, through the order word), list s of ks[s]
     slots over 6 local videos: counts in [-1, k_s + 1], behind them NaN spans and scores and -1; ``empty_query``: no list has an entry,
@@ -412,22 +388,10 @@ def test_folded_equals_at_once_on_the_device(dev):
 
 
 # ---------------------------------------------------------------- GPU: sharded search_windows
-SEED = 3
-KW = dict(k=5, k_video=3, k_window=3)
-DURATION = np.array([10.0, 3.5, 60.0, 7.25, 100.0])
-SHARD_SPLITS = ([2, 3], [1, 1, 3])
-
-
-def shard_dicts(raw, split, lengths=LENGTHS, duration=DURATION):
-    ve = np.concatenate([[0], np.cumsum(split)])
-    re_ = np.concatenate([[0], np.cumsum(lengths)])
-    return [dict(raw=raw[re_[a]:re_[b]], lengths=list(lengths[a:b]), duration=duration[a:b]) for a, b in zip(ve[:-1], ve[1:])]
-
-
 @pytest.fixture(scope="module")
 def world(dev):
     """the tiny model, LENGTHS' rows (40, 16, 9, 0 and 23: 4, 1, 1, 0 and 2 windows), four ragged queries, the whole bank and its search"""
-    m = tiny_model(dev)
+    m, _ = tiny_model(dev)
     raw, qf, qm = corpus_rows(SEED)
     raw_d, qf_d, qm_d = raw.to(dev), qf.to(dev), qm.to(dev)
     qb = m.encode_queries(qf_d, qm_d)
@@ -557,8 +521,6 @@ def test_nothing_else_moved(dev, world):
     A = V()
     m, raw, qb, wb = world["m"], world["raw"], world["qb"], world["wb"]
     queries = dict(query_features=world["qf"], query_mask=world["qm"])
-    from tests.test_corpus_eval import pair_lists, shards_of as cell_shards
-    from tests.test_window_search import random_span_lists
     cells, cell_off = cell_shards(pair_lists(6, 4, 3, seed=3), 6, 4, [2, 4], 5)
     spans = random_span_lists([0, 1, 7, 3], 3, seed=14, garbage=float("nan"))
     duration = torch.from_numpy(DURATION).to(dev)

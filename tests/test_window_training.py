@@ -9,51 +9,13 @@ import pytest
 import torch
 
 from tests import helpers as H
-
-NAN = float("nan")
-
-
-def V():
-    import models
-    return models.vml_amd
-
-
-def bits64(t):
-    return t.detach().cpu().contiguous().view(torch.int64)
+from tests.support.device import dev  # noqa: F401  (the module's device fixture)
+from tests.support.device import vml as V
+from tests.support.compare import bits64
+from tests.support.references import edge_cases, py_span_hits, py_span_ious, random_spans
 
 
 # ---------------------------------------------------------------- the definition, in numpy fp32 scalars
-def py_span_iou(a, g):
-    """include/smin_hip.h, span metric: every operation on np.float32 scalars (each rounded once)."""
-    f = np.float32
-    st, en, gs, ge = f(a[0]), f(a[1]), f(g[0]), f(g[1])
-    inter = max(f(0), min(en, ge) - max(st, gs))
-    uni = max(en, ge) - min(st, gs)
-    return f(inter) / f(uni) if uni > 0 else f(0)
-
-
-def py_span_ious(span, count, gt):
-    span, count, gt = np.asarray(span, np.float32), np.asarray(count), np.asarray(gt, np.float32)
-    B, k = span.shape[0], span.shape[1]
-    out = np.zeros((B, k), np.float32)
-    for b in range(B):
-        for s in range(min(int(count[b]), k)):                                   # an empty slot is never read: IoU exactly 0
-            out[b, s] = py_span_iou(span[b, s], gt[b])
-    return out
-
-
-def py_span_hits(ious, count, n, m):
-    """{key: pairs with some slot s < min(n, count) whose iou > float32(m)}."""
-    out = {}
-    for n_ in n:
-        for m_ in m:
-            c = 0
-            for b in range(ious.shape[0]):
-                c += any(ious[b, s] > np.float32(m_) for s in range(min(n_, int(count[b]))))
-            out[f"R@{n_}, IoU={m_}"] = float(c)
-    return out
-
-
 def py_acc(acc, ious, count, n, m):
     """One update_spans on a float64 accumulator, in the order include/smin_hip.h fixes."""
     B = ious.shape[0]
@@ -66,42 +28,6 @@ def py_acc(acc, ious, count, n, m):
     for a, n_ in enumerate(n):
         for c, m_ in enumerate(m):
             acc[4 + a * len(m) + c] += np.float64(hits[f"R@{n_}, IoU={m_}"])
-
-
-def edge_cases():
-    """k = 5.  Pair by pair: a span equal to the ground truth then a disjoint one; count = 0 with NaN everywhere; empty slots holding
-    NaN behind two filled ones; uni == 0 (a point span on a point ground truth); IoUs exactly 0.5 and exactly 0.75 (not hits at
-    m = 0.5 / 0.75) next to one just above; a span containing the ground truth; negative coordinates."""
-    span = [[[10.0, 20.0], [30.0, 40.0], [NAN, NAN], [NAN, NAN], [NAN, NAN]],
-            [[NAN, NAN]] * 5,
-            [[0.0, 4.0], [2.5, 7.25], [NAN, NAN], [NAN, NAN], [NAN, NAN]],
-            [[3.0, 3.0], [3.0, 3.0], [1.0, 2.0], [NAN, NAN], [NAN, NAN]],
-            [[0.0, 4.0], [0.0, 6.0], [0.0, 8.0], [0.0, 7.9999995], [100.0, 101.0]],
-            [[-5.0, 50.0], [11.0, 12.5], [10.0, 12.0], [10.5, 12.0], [0.0, 100.0]],
-            [[-7.5, -2.25], [-3.0, 1.0], [-10.0, -9.0], [NAN, NAN], [NAN, NAN]]]
-    count = [2, 0, 2, 3, 5, 5, 3]
-    gt = [[10.0, 20.0], [1.0, 2.0], [1.0, 6.5], [3.0, 3.0], [0.0, 8.0], [10.0, 12.0], [-6.0, -2.0]]
-    return torch.tensor(span, dtype=torch.float32), torch.tensor(count, dtype=torch.int32), torch.tensor(gt, dtype=torch.float32)
-
-
-def random_spans(B, k, seed, nan_valid=False):
-    """Spans and ground truths on a 1/8-row grid inside [0, 600): overlaps, containments, equal spans and exact ties with thresholds
-    all occur; count ragged (0 .. k), empty slots NaN."""
-    g = torch.Generator().manual_seed(seed)
-    a = torch.randint(0, 4800, (B, k, 2), generator=g).float() / 8
-    span = torch.stack([a.min(dim=2).values, a.max(dim=2).values + 0.125 * torch.randint(0, 2, (B, k), generator=g)], 2)
-    c = torch.randint(0, 4800, (B, 2), generator=g).float() / 8
-    gt = torch.stack([c.min(dim=1).values, c.max(dim=1).values + 0.125], 1)
-    near = torch.rand(B, k, generator=g) < 0.5                                   # half the slots sit near the ground truth
-    jitter = torch.randint(-64, 65, (B, k, 2), generator=g).float() / 8
-    cand = gt.unsqueeze(1) + jitter
-    cand = torch.stack([cand.min(dim=2).values, cand.max(dim=2).values], 2)
-    span = torch.where(near.unsqueeze(2), cand, span)
-    count = torch.randint(0, k + 1, (B,), generator=g).to(torch.int32)
-    count[0] = k
-    empty = torch.arange(k).unsqueeze(0) >= count.unsqueeze(1)
-    span[empty] = NAN
-    return span, count, gt
 
 
 CASES = [("edge", (1, 5), (0.1, 0.3, 0.5, 0.7)), ("edge", (1, 2, 3, 4), (0.5, 0.75, 0.0, 0.9999)), ("rand5", (1, 5), (0.1, 0.3, 0.5, 0.7)),
@@ -330,12 +256,6 @@ def test_loop_is_exported_and_not_collected():
 
 
 # ---------------------------------------------------------------- GPU
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    import models
-    models.vml_amd._lib.load()
-    return torch.device("cuda", 0)
 
 
 KEYS = ["video_features", "video_mask", "query_features", "query_mask", "length_mask", "moment_mask", "sm", "ym", "ss", "ys", "se", "ye", "ya"]

@@ -14,7 +14,8 @@ import ctypes
 import pytest
 import torch
 
-from tests.test_gate_content_loss import _ws_nan
+from tests.support.device import dev  # noqa: F401  (the module's device fixture)
+from tests.support.guards import _vp, _ws_nan
 
 GUARD = 4096
 FILL = 7.0                                     # what the refusal runs pre-fill the outputs with
@@ -37,14 +38,6 @@ def test_lists_are_what_the_layouts_branch_on():
     assert int(_mask("small").sum()) < 256 and int(_mask("split").sum()) == 680 and int(_mask("empty").sum()) == 0
 
 
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    import models
-    models.vml_amd._lib.load()
-    return torch.device("cuda:0")
-
-
 _SETUPS = {}
 
 
@@ -54,10 +47,6 @@ def _setup(dev, name):
         import models
         _SETUPS[name] = models.vml_amd.CellLayout.from_mask(_mask(name).to(dev))
     return _SETUPS[name], torch.Generator().manual_seed(sorted(LISTS).index(name) + 11)
-
-
-def _vp(t):
-    return None if t is None or t.numel() == 0 else ctypes.c_void_p(t.data_ptr())
 
 
 def _arr(ts):

@@ -12,7 +12,7 @@ sys.path.insert(0, ROOT)
 
 from oracle import smin_oracle as O          # noqa: E402
 from tests import helpers as H               # noqa: E402
-from tests.test_score_path import collapsed_pm  # noqa: E402
+from tests.support.references import collapsed_pm  # noqa: E402
 
 
 def run(name, cfg, sd, batch, pm_gold):

@@ -8,7 +8,7 @@ sys.path.insert(0, ROOT)
 import models  # noqa: F401 (loads the package as vml_amd)
 from oracle import smin_oracle as O          # seeded inputs / weights only (a diagnostic tool, not the product)
 from tests import helpers as H
-from tests.test_hip_parity import build_model
+from tests.support.corpora import build_model
 from vml_amd import loss_fn
 dev = torch.device("cuda:0")
 reps = int(sys.argv[1]) if len(sys.argv) > 1 else 60
