@@ -960,8 +960,11 @@ int smin_mine_pairs(void* stream, const float* score, const int32_t* gt_video, i
  * Cell score.  f[p][i][j] = (pm[p][i][j] * sqrtf(max(ps[p][i], 1e-12f))) * sqrtf(max(pe[p][j], 1e-12f)), smin_top_moments' order.
  * Pair score.  Over the pair's n_p valid cells, m_p their maximum: s_p = m_p + tau * logf((sum_valid expf((f - m_p) / tau)) / n_p);
  *   n_p == 0: s_p = 0, a constant that still takes part in its query's sums.
- * Query loss.  S_q the query's segment, S_q+ its pairs with positive != 0, M_q = max_{S_q} s:
- *   l_q = logf(sum_{S_q} expf((s_p - M_q) / gamma)) - logf(sum_{S_q+} expf((s_p - M_q) / gamma)).
+ * Query loss.  S_q the query's segment, S_q+ its pairs with positive != 0, M_q = max_{S_q} s, M_q+ = max_{S_q+} s:
+ *   l_q = log sum_{S_q} exp(s_p / gamma) - log sum_{S_q+} exp(s_p / gamma), each sum shifted by the maximum of its own terms:
+ *   l_q = (M_q - M_q+) / gamma + logf(sum_{S_q} expf((s_p - M_q) / gamma)) - logf(sum_{S_q+} expf((s_p - M_q+) / gamma)).
+ *   Both sums are >= 1, so l_q and coef are finite however far a positive lies below the best negative, at any gamma for which
+ *   (M_q - M_q+) / gamma is finite in fp32.
  *   A query with S_q+ empty (a query without a pair among them) is not counted.
  * Outputs, every element written.
  *   loss [1] = (sum of l_q over the Nc counted queries) / Nc, exactly 0 when Nc == 0.

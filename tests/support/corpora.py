@@ -1,6 +1,8 @@
 """The inputs the tests share: the tiny model, the ragged corpus and its pair lists, the window corpus of long videos, the shard
 splitters, the rank-loss plans and probes, and the first-stage score's inputs.  Seeds and the order of draws are part of what the
 tests' tolerances were measured on."""
+import math
+
 import numpy as np
 import pytest
 import torch
@@ -252,8 +254,13 @@ _INPUTS = {}
 def inputs(shape, dev):
     """random fp32 banks and heads and ragged masks of a shape; video V // 2 has no valid cell.  Made once per shape, with the fp64
     restatement (maps included) at each tau computed on demand and kept."""
-    if shape in _INPUTS:
-        return _INPUTS[shape]
+    if shape not in _INPUTS:
+        _INPUTS[shape] = uncached_inputs(shape, dev)
+    return _INPUTS[shape]
+
+
+def uncached_inputs(shape, dev):
+    """what ``inputs`` makes and keeps, made anew (a host test must not leave host tensors where the device tests look)"""
     Q, Vn, T, L, C, D = shape
     g = torch.Generator().manual_seed(sum(shape))
     fv, fs = torch.randn(Vn, T, D, generator=g), torch.randn(Q, D, generator=g)
@@ -262,9 +269,28 @@ def inputs(shape, dev):
     lens[0], lens[Vn // 2] = L, 0
     lm = torch.arange(L).unsqueeze(0) < lens.unsqueeze(1)
     mm = torch.triu(lm.unsqueeze(2) & lm.unsqueeze(1))
-    x = dict(fv=fv.to(dev), fs=fs.to(dev), w=w.to(dev), b=b.to(dev), lm=lm.to(dev), mm=mm.to(dev), shape=shape, ref={})
-    _INPUTS[shape] = x
-    return x
+    return dict(fv=fv.to(dev), fs=fs.to(dev), w=w.to(dev), b=b.to(dev), lm=lm.to(dev), mm=mm.to(dev), shape=shape, ref={})
+
+
+PREFILTER_PRE = (20.0, 95.0, 110.0)
+
+
+def saturated_prefilter(x, level):
+    """A first-stage inputs dict (this module's ``inputs`` or tests/test_prefilter_train.py's) with banks and heads of rank one: every
+    frame of video v is c_v (1 + d_k) / D over the features k (d_k = +-1/2 in turn, so a contraction still adds D different
+    products), every feature of query q is k_q, the heads are all ones and the biases 0.  The three heads' pre-activations of the pair
+    (q, v) are then c_v k_q at every cell and clip whose window mean weighs whole frames (T // L >= C).  c_0 = +1, the others -1.
+    frozen: k_q runs through +-{20, 95, 110}; hard: through +20, -95 and three values inside +-4.  Returns a new dict."""
+    Q, Vn, T, L, C, D = x["shape"]
+    assert T // L >= C and D % 2 == 0
+    dev = x["fv"].device
+    c = -torch.ones(Vn)
+    c[0] = 1.0
+    k = torch.tensor([20.0, -95.0, 110.0, -20.0, 95.0, -110.0] if level == "frozen" else [20.0, -95.0, 1.5, -0.75, 3.0]).repeat(Q)[:Q]
+    d = 1 + torch.tensor([0.5, -0.5]).repeat(D // 2)
+    y = dict(x, fv=(c.view(Vn, 1, 1) * d / D).expand(Vn, T, D).contiguous().to(dev), fs=k.view(Q, 1).expand(Q, D).contiguous().to(dev),
+             w=torch.ones(3, D, device=dev), b=torch.zeros(3, device=dev), ref={})
+    return y, torch.outer(k, c)
 
 
 def host_pairs(video):
@@ -336,6 +362,71 @@ def synthetic(P, L, seed, dtype=torch.float32):
             if p % 3 == 1:
                 pm[p, 0, 0] = 0.0
     return pm.to(dtype), ps.to(dtype), pe.to(dtype), mm
+
+
+# d = (the segment's best score - the positives' best score) / gamma of the hard query -> (gamma, that difference): all dyadic, so the
+# scores, their differences and the quotients by gamma are exact in fp32 and d is what the kernel sees
+RANK_DEPTHS = {50: (2.0 ** -7, 50 / 128), 95: (2.0 ** -8, 95 / 256), 120: (2.0 ** -8, 120 / 256), 800: (2.0 ** -11, 800 / 2048)}
+RANK_BEST = 0.875
+
+
+def saturated_pairs(d, dtype=torch.float32):
+    """Constant maps with ps = pe = 1 over plan_of(6, 2) at L = 4 (segments [0, 2, 4] and [1, 3, 5], the positives p = 2 and p = 5): every
+    valid cell of pair p holds c_p, so the pooled score s_p is c_p exactly at any tau.  Query 0's own video is its best pair (0.875 over
+    0.5 and 0.25); query 1's own video lies d * gamma below its best negative (0.875), a second negative 0.125 below that.  Returns
+    ((pm, ps, pe, mm), gamma, c)."""
+    gamma, gap = RANK_DEPTHS[d]
+    c = [0.5, RANK_BEST, RANK_BEST, RANK_BEST - 0.125, 0.25, RANK_BEST - gap]
+    L = 4
+    mm = torch.triu(torch.ones(L, L, dtype=torch.bool)).repeat(len(c), 1, 1)
+    pm = torch.tensor(c, dtype=torch.float64).reshape(-1, 1, 1).expand(len(c), L, L).contiguous()
+    assert torch.equal(pm.float().double(), pm)                                  # fp32 holds every constant
+    return (pm.to(dtype), torch.ones(len(c), L, dtype=dtype), torch.ones(len(c), L, dtype=dtype), mm), gamma, c
+
+
+def saturated_teacher(dtype=torch.float32):
+    """a teacher over saturated_pairs' plan that puts each query's own video first: it agrees with the student on query 0 and, on
+    query 1, prefers the pair the student ranks last"""
+    return torch.tensor([0.5, 0.25, RANK_BEST, 0.625, 0.25, RANK_BEST], dtype=dtype)
+
+
+def stable_rank_loss(c, segments, positives, gamma):
+    """The contrastive loss' definition on given pair scores in Python floats (fp64), stable form: the mean over the queries of
+    logsumexp(s / gamma) over the segment minus the same over its positives, and d(loss)/d(s_p).  Returns (loss, [coef_p])."""
+    def lse(v):
+        top = max(v)
+        return top + math.log(sum(math.exp(x - top) for x in v))
+    total, coef = 0.0, [0.0] * len(c)
+    for seg, pos in zip(segments, positives):
+        za, zp = lse([c[p] / gamma for p in seg]), lse([c[p] / gamma for p in pos])
+        total += za - zp
+        for p in seg:
+            coef[p] += (math.exp(c[p] / gamma - za) - (math.exp(c[p] / gamma - zp) if p in pos else 0.0)) / gamma
+    n = len(segments)
+    return total / n, [v / n for v in coef]
+
+
+def tied_maps(P, L, seed, dtype=torch.float32):
+    """synthetic's masks under maps of eighths with ps = pe = 1, pair p capped at 1 - (p % 4) / 8: a pair's fused scores are multiples of
+    1/8, several cells may share the maximum, neighbouring pairs have different maxima, and at tau <= 1e-3 every other cell lies at
+    least 125 temperatures below its pair's maximum"""
+    pm, ps, pe, mm = synthetic(P, L, seed, dtype=torch.float64)
+    cap = 1.0 - (torch.arange(P, dtype=torch.float64) % 4) / 8
+    pm = torch.minimum(torch.round(pm * 8) / 8, cap.reshape(P, 1, 1))
+    return pm.to(dtype), torch.ones_like(ps).to(dtype), torch.ones_like(pe).to(dtype), mm
+
+
+def tied_pool_by_hand(pm, mm, tau):
+    """m + tau * log(k / n) per pair of tied_maps, k the number of valid cells at the maximum m of its n valid cells (0 without one), in
+    Python floats; also the lists of m, k and n"""
+    score, top, ties, cells = [], [], [], []
+    for p in range(pm.shape[0]):
+        vals = pm[p][mm[p]].tolist()
+        m = max(vals) if vals else 0.0
+        k = sum(v == m for v in vals)
+        score.append(m + tau * math.log(k / len(vals)) if vals else 0.0)
+        top.append(m), ties.append(k), cells.append(len(vals))
+    return score, top, ties, cells
 
 
 def on(dev, d):

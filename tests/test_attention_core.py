@@ -12,7 +12,7 @@ import torch
 
 from tests import helpers as H
 from tests.support.device import dev  # noqa: F401  (the module's device fixture)
-from tests.support.compare import _rel
+from tests.support.compare import _rel, gate
 from tests.support.references import (
     _attn_inputs, _layout_to, _ragged_mask, _smi_params, attn_core_ref, attn_form, word_side_ref, ALL_FORMS, WORD_PARAM_NAMES)
 
@@ -131,8 +131,21 @@ def test_attention_cases_reach_every_form():
 ATTN_IN = ("chat", "Mq", "uq", "what", "shat")
 
 
-def _run_attn_case(dev, C, dl, Nq, lay, x, label, check_masked=True):
-    """Every forward and backward flavour of one case against attn_core_ref; returns the worst (forward, gradient) ratio."""
+def _attn_refs(C, lay, x, Wcc, Wm, dtype):
+    """attn_core_ref in ``dtype``: (cc, ccmean, S, {flavour: the five gradients})"""
+    ref_in = {k: v.detach().to(dtype).clone().requires_grad_(k in ATTN_IN) for k, v in x.items()}
+    cc0, cm0, S0 = attn_core_ref(ref_in["chat"], lay.cells, C, ref_in["Mq"], ref_in["uq"], ref_in["what"], ref_in["shat"], ref_in["qmask"])
+    Wcc, Wm = Wcc.to(dtype), Wm.to(dtype)
+    refs = {}
+    for flav, loss in (("mean2", (cc0 * Wcc).sum() + (cm0 * Wm).sum()), ("percell", (cm0 * Wm).sum()), ("plain", (cc0 * Wcc).sum())):
+        refs[flav] = torch.autograd.grad(loss, [ref_in[k] for k in ATTN_IN], retain_graph=True)
+    return cc0.detach(), cm0.detach(), S0.detach(), refs
+
+
+def _run_attn_case(dev, C, dl, Nq, lay, x, label, check_masked=True, saturated=False):
+    """Every forward and backward flavour of one case against attn_core_ref; returns the worst (forward, gradient) ratio.
+    saturated: the case is run without the spread precondition, and every comparison is the project's gate (tests/support/compare.py)
+    with e_torch32 from attn_core_ref in fp32, in place of the fixed bounds."""
     import models
     F = models.vml_amd.functional
     from vml_amd._lib import call, ptr, stream
@@ -142,23 +155,34 @@ def _run_attn_case(dev, C, dl, Nq, lay, x, label, check_masked=True):
     g = torch.Generator().manual_seed(N + 7 * Nq + dl)
     Wcc, Wm = torch.randn(N * C, dl, generator=g, dtype=torch.float64), torch.randn(N, dl, generator=g, dtype=torch.float64)
 
-    ref_in = {k: v.clone().requires_grad_(k in ATTN_IN) for k, v in x.items()}
-    cc0, cm0, S0 = attn_core_ref(ref_in["chat"], lay.cells, C, ref_in["Mq"], ref_in["uq"], ref_in["what"], ref_in["shat"], ref_in["qmask"])
-    # the word scores must be spread (a saturated softmax hides a dropped or extra word)
-    live = (lay.cells[:, 3] != 0).view(-1, 1, 1) & (x["qmask"][lay.cells[:, 0].long()] != 0).unsqueeze(1)
-    sd = S0.detach()[live.expand_as(S0)].std().item()
-    assert 0.5 <= sd <= 3.0, f"{label}: word-score spread {sd:.3f}"
-    refs = {}
-    for flav, loss in (("mean2", (cc0 * Wcc).sum() + (cm0 * Wm).sum()), ("percell", (cm0 * Wm).sum()), ("plain", (cc0 * Wcc).sum())):
-        refs[flav] = torch.autograd.grad(loss, [ref_in[k] for k in ATTN_IN], retain_graph=True)
+    cc0, cm0, S0, refs = _attn_refs(C, lay, x, Wcc, Wm, torch.float64)
+    if saturated:
+        cc32, cm32, _, refs32 = _attn_refs(C, lay, x, Wcc.float(), Wm.float(), torch.float32)
+        ref32_of = {id(cc0): cc32, id(cm0): cm32}
+    else:
+        # the word scores must be spread (a saturated softmax hides a dropped or extra word)
+        live = (lay.cells[:, 3] != 0).view(-1, 1, 1) & (x["qmask"][lay.cells[:, 0].long()] != 0).unsqueeze(1)
+        sd = S0[live.expand_as(S0)].std().item()
+        assert 0.5 <= sd <= 3.0, f"{label}: word-score spread {sd:.3f}"
 
     d = {k: v.float().to(dev) for k, v in x.items()}
     Wcc_d, Wm_d = Wcc.float().to(dev), Wm.float().to(dev)
     worst_f = worst_g = 0.0
 
+    def check_fwd(what, got, ref):
+        nonlocal worst_f
+        if saturated:
+            return gate(f"attn {label} {what}", got, ref, ref32_of[id(ref)])
+        e = _rel(got, ref)
+        worst_f = max(worst_f, e)
+        assert e <= FWD_TOL, (label, what, e)
+
     def check_grads(flav, got):
         nonlocal worst_g
-        for name, gg, rr in zip(ATTN_IN, got, refs[flav]):
+        for k, (name, gg, rr) in enumerate(zip(ATTN_IN, got, refs[flav])):
+            if saturated:
+                gate(f"attn {label} {flav} d{name}", gg, rr, refs32[flav][k])
+                continue
             e = _rel(gg, rr)
             worst_g = max(worst_g, e)
             assert e <= GRAD_TOL, (label, flav, "d" + name, e)
@@ -173,18 +197,14 @@ def _run_attn_case(dev, C, dl, Nq, lay, x, label, check_masked=True):
     # rows + mean; backward on both outputs (MEAN2)
     cc, cm, grads = fwd_bwd(True)
     for got, ref in ((cc, cc0), (cm, cm0)):
-        e = _rel(got, ref.detach())
-        worst_f = max(worst_f, e)
-        assert e <= FWD_TOL, (label, "fwd rows+mean", e)
+        check_fwd("fwd rows+mean", got, ref)
     check_grads("mean2", grads)
     _, _, again = fwd_bwd(True)                                   # fixed-order slab sums: bit for bit
     assert all(torch.equal(a, b) for a, b in zip(grads, again)), (label, "backward not deterministic")
     # mean only; backward on the mean alone (PERCELL)
     cc_e, cm2, grads = fwd_bwd(False)
     assert cc_e.numel() == 0
-    e = _rel(cm2, cm0.detach())
-    worst_f = max(worst_f, e)
-    assert e <= FWD_TOL, (label, "fwd mean only", e)
+    check_fwd("fwd mean only", cm2, cm0)
     check_grads("percell", grads)
     # rows only (plain): ContentAttnFn always hands the kernel both gradients, so this flavour is called through the C ABI
     dchat, dMq, duq, dwhat, dshat = (torch.empty_like(d[k]) for k in ATTN_IN)
@@ -218,6 +238,115 @@ def test_content_attn_dispatch_table(dev, C, dl, Nq, layout):
     lay, x = _attn_inputs(C, dl, Nq, mask, layout == "all_cells", seed=C + dl + Nq)
     assert layout == "from_mask" or bool((lay.cells[:, 3] == 0).any())
     _run_attn_case(dev, C, dl, Nq, lay, x, f"{_attn_id((C, dl, Nq))}-{layout}")
+
+
+# ---------------------------------------------------------------- saturated word softmax
+
+LEVELS = ("hard", "frozen")
+
+
+def _saturated_attn_cases():
+    """Per form of the dispatch table its smallest existing case with more than one word, a word count that is no multiple of 4 where
+    the form has one (the -inf tail of the last word slot)"""
+    picked = []
+    for form in ALL_FORMS:
+        cands = [c for c in ATTN_CASES if attn_form(*c) == form and c[2] > 1]
+        if not form[2]:                                      # the general forms: C = 2 and C = 3 in turn
+            cands = [c for c in cands if c[0] == (3 if form[0] in (32, 128) else 2)]
+        odd = [c for c in cands if c[2] % 4]
+        picked.append(min(odd or cands, key=lambda c: (c[0] * c[1] * c[2], c)))
+    return picked
+
+
+SAT_ATTN_CASES = _saturated_attn_cases()
+
+
+def _word_probs(x, lay, C):
+    """(the word softmax P [N, C, Nq] of attn_core_ref, its masked logits) in the dtype of x"""
+    S = attn_core_ref(x["chat"], lay.cells, C, x["Mq"], x["uq"], x["what"], x["shat"], x["qmask"])[2]
+    qm = x["qmask"][lay.cells[:, 0].long()].unsqueeze(1)
+    S = (S * qm).masked_fill(qm == 0, -1e9)
+    return torch.softmax(S, dim=-1), S
+
+
+def _saturated_attn_inputs(C, dl, Nq, level):
+    """test_content_attn_dispatch_table's all_cells inputs with Mq and uq -- the word logits are linear in them -- scaled by the factor
+    the float64 reference asks for: frozen -- the live logits' standard deviation becomes 100; hard -- samples 0 and 2 by the smallest
+    power of 2 at which a quarter of all live rows have a largest probability above 1 - 1e-6, sample 1 as it is (a quarter of all
+    live rows below 0.9; one factor for all rows cannot give both: the gap between a row's two largest logits of 16 is too evenly
+    spread)."""
+    g = torch.Generator().manual_seed(1000 * C + 10 * dl + Nq)
+    lay, x = _attn_inputs(C, dl, Nq, _ragged_mask(4, 6, g), True, seed=C + dl + Nq)
+    live_rows = ((lay.cells[:, 3] != 0).view(-1, 1) & (x["qmask"][lay.cells[:, 0].long()] != 0).any(1, keepdim=True)).expand(-1, C)
+    def scaled(k, samples=(0, 1, 2, 3)):
+        f = torch.ones(x["Mq"].shape[0], dtype=torch.float64)
+        f[list(samples)] = k
+        return dict(x, Mq=(f.view(-1, 1, 1) * x["Mq"]).float().double(), uq=(f.view(-1, 1) * x["uq"]).float().double())
+    if level == "frozen":
+        S = _word_probs(x, lay, C)[1]
+        live = live_rows.unsqueeze(-1) & (S > -1e8)
+        return lay, scaled(100.0 / S[live].std().item()), live_rows
+    for e in range(1, 12):                                  # samples 0 and 2 are driven into saturation, sample 1 keeps its spread
+        y = scaled(2.0 ** e, (0, 2))
+        top = _word_probs(y, lay, C)[0].max(-1).values[live_rows]
+        if (top > 1 - 1e-6).double().mean().item() >= 0.25 and (top < 0.9).double().mean().item() >= 0.25:
+            return lay, y, live_rows
+    raise AssertionError(f"no scale puts C{C}-dl{dl}-Nq{Nq} into the hard regime")
+
+
+def test_saturated_attention_cases_reach_every_form():
+    assert {attn_form(*c) for c in SAT_ATTN_CASES} == set(ALL_FORMS) and len(SAT_ATTN_CASES) == len(ALL_FORMS)
+    assert any(c[2] % 4 for c in SAT_ATTN_CASES) and {2, 3} <= {c[0] for c in SAT_ATTN_CASES}       # the -inf word tail; absent clips
+
+
+@pytest.mark.parametrize("level", LEVELS)
+@pytest.mark.parametrize("C,dl,Nq", SAT_ATTN_CASES, ids=[_attn_id(c) for c in SAT_ATTN_CASES])
+def test_saturated_attention_inputs_hold_what_they_claim(C, dl, Nq, level):
+    """On the float64 reference.  hard: at least a quarter of the live word-softmax rows have a largest probability above 1 - 1e-6 and
+    at least a quarter below 0.9.  frozen: the live logits' standard deviation is 100 (to 1 %), at least 60 % of the rows are one-hot to
+    1e-6 and 95 % have one word above 0.5 (two of 16 logits at that spread are sometimes within a few units of each other).
+    Both: a sample whose query mask is all zero is there, every logit of it is -1e9 and its softmax uniform; masked cells are listed."""
+    lay, x, live_rows = _saturated_attn_inputs(C, dl, Nq, level)
+    P, S = _word_probs(x, lay, C)
+    top = P.max(-1).values[live_rows]
+    if level == "hard":
+        assert (top > 1 - 1e-6).double().mean().item() >= 0.25 and (top < 0.9).double().mean().item() >= 0.25
+    else:
+        sd = S[live_rows.unsqueeze(-1) & (S > -1e8)].std().item()
+        assert abs(sd - 100) <= 1.0 and (top > 1 - 1e-6).double().mean().item() >= 0.6 and (top > 0.5).double().mean().item() >= 0.95
+    blank = (x["qmask"] == 0).all(1)
+    of_blank = blank[lay.cells[:, 0].long()]
+    assert bool(blank.any()) and bool(of_blank.any()) and bool((S[of_blank] == -1e9).all())
+    assert (P[of_blank] - 1.0 / Nq).abs().max().item() <= 1e-15 and bool((lay.cells[:, 3] == 0).any())
+    assert all(bool(torch.isfinite(v).all()) for v in x.values())
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("level", LEVELS)
+@pytest.mark.parametrize("C,dl,Nq", SAT_ATTN_CASES, ids=[_attn_id(c) for c in SAT_ATTN_CASES])
+def test_content_attn_saturated_word_softmax(dev, C, dl, Nq, level):
+    """smin_content_attn_fwd and _bwd (ContentAttnFn's three flavours and the C ABI's rows-only backward) and smin_content_attn_fwd_probs
+    with the word softmax partly (hard) or wholly (frozen) one-hot, a sample without a word, word counts that leave the last slot's
+    tail at -inf, and C < 4: everything finite, masked cells exactly 0, and the project's gate against attn_core_ref in float64 with
+    e_torch32 from attn_core_ref in fp32.  Measured on an MI355X: INTEGRATION.md, "Saturated inputs"."""
+    from vml_amd._lib import call, ptr, stream
+    lay, x, live_rows = _saturated_attn_inputs(C, dl, Nq, level)
+    label = f"{_attn_id((C, dl, Nq))} {level}"
+    _run_attn_case(dev, C, dl, Nq, lay, x, label, saturated=True)
+    ld = _layout_to(lay, dev)
+    d = {k: v.float().to(dev).contiguous() for k, v in x.items()}
+    N, B = lay.N, x["Mq"].shape[0]
+    probs, cm = torch.full((N * C, Nq), float("nan"), device=dev), torch.full((N, dl), float("nan"), device=dev)
+    call("smin_content_attn_fwd_probs", stream(), ptr(d["chat"]), ptr(ld.cells), ptr(ld.row_ptr), N, B, ld.L, C, dl, Nq, ptr(d["Mq"]), ptr(d["uq"]),
+         ptr(d["what"]), ptr(d["shat"]), ptr(d["qmask"]), None, 0, ptr(cm), ptr(probs))
+    torch.cuda.synchronize()
+    rows = (lay.cells[:, 3] != 0).repeat_interleave(C)                            # (the rows of the sample without a word too: uniform)
+    want = _word_probs(x, lay, C)[0].reshape(N * C, Nq)
+    ref32 = _word_probs({k: v.float() for k, v in x.items()}, lay, C)[0].reshape(N * C, Nq)
+    assert bool(torch.isfinite(probs.cpu()[rows]).all())
+    gate(f"attn {label} probs", probs.cpu()[rows], want[rows], ref32[rows])
+    off = (x["qmask"][lay.cells[:, 0].long()] == 0).unsqueeze(1).expand(-1, C, -1).reshape(N * C, Nq)
+    assert bool((probs.cpu()[live_rows.reshape(-1, 1) & off] == 0).all())        # a masked word beside live ones: exactly 0
 
 
 def _range_cells(N, slots):

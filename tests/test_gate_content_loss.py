@@ -25,6 +25,12 @@ Forms reached
             scale targets at exactly 0 and 1, L = 300 (a second trip of the boundary loop), L * L < 256, B = 37, mask bytes 7 and 255,
             the part[B][6] partials, and the autograd wrapper vml_amd.loss_fn bit for bit against the direct calls.
 
+Saturated inputs (the project's gate e_kernel <= 32 * e_torch32 + 1e-6 in place of the fixed bounds; INTEGRATION.md "Saturated inputs")
+  gate      pre-activations fm * fs at +-{20, 90, 200, 1e4}, on every element and on half of them, at D = 48, D = 1056 and on the
+            non-triangular all_cells list.
+  loss      on the (5, 16) case, the mask bytes 7 / 255 and L = 300: p at 0, fp32's smallest denormal, 1e-30, 0.5, 1 - 2^-24 and 1 under both labels and the scale targets 0, 0.3, 1, in all four
+            heads, the gradients gated per (head, p, label) group.
+
 Left to other suites
   EpLastMean (and EpScale over MaskedRowsMat) on 128-row main tiles need more than 32 768 cells: the tile bodies are the engine
   tests' (tests/test_gemm_engine.py), the epilogue is covered here on mini tiles.  Gemm modes 1 and 2 stay with the whole-model tests
@@ -638,6 +644,88 @@ def test_gate_against_fp64(dev, case):
     _report("gate", label, worst)
 
 
+# ---------------------------------------------------------------- saturated inputs: gate
+
+# the smallest case of each form the table names beyond the chunk counts: D < 512 with an empty sample and both gradient lists; D = 1056
+# (three trips of the d loop, several reducer column blocks); the non-triangular all_cells list with the capped chunk count
+GATE_SAT_CASES = [GATE_CASES[1], GATE_CASES[4], GATE_CASES[5]]
+GATE_PRODUCTS = (20.0, 90.0, 200.0, 1e4)
+LEVELS = ("hard", "frozen")
+
+
+@functools.lru_cache(maxsize=None)
+def _gate_saturated(case, level):
+    """_gate_inputs of a case with fm chosen so that the gate's pre-activation fm * fs[b] takes given values: +-{20, 90, 200, 1e4}
+    everywhere (frozen), or on half of the elements with N(0, 2) on the rest (hard).  |fs| lies in [1, 4], so |fm| <= 1e4."""
+    lay = _gate_layout(case)
+    x = dict(_gate_inputs(case, lay))
+    g = torch.Generator().manual_seed(17 + len(level) + case[2])
+    B, D, N = case[0], case[2], lay.N
+    sign = lambda *s: torch.randint(0, 2, s, generator=g).double() * 2 - 1
+    fs = ((1 + 3 * torch.rand(B, D, generator=g, dtype=torch.float64)) * sign(B, D)).float().double()
+    t = torch.tensor(GATE_PRODUCTS, dtype=torch.float64)[torch.randint(0, 4, (N, D), generator=g)] * sign(N, D)
+    if level == "hard":
+        t = torch.where(torch.rand(N, D, generator=g) < 0.5, t, 2 * torch.randn(N, D, generator=g, dtype=torch.float64))
+    x["fs"], x["fm"] = fs, (t / fs[lay.cells[:, 0].long()]).float().double()
+    return lay, x, t
+
+
+@pytest.mark.parametrize("level", LEVELS)
+@pytest.mark.parametrize("case", GATE_SAT_CASES, ids=[_gate_id(c) for c in GATE_SAT_CASES])
+def test_gate_saturated_inputs_hold_what_they_claim(case, level):
+    """On the float64 reference: hard -- at least a quarter of the pre-activations beyond +-17 and a quarter inside +-4; frozen -- every
+    one within 1e-6 of +-{20, 90, 200, 1e4}, each value under both signs; |fm| <= 1e4; everything finite, the gradients included."""
+    lay, x, t = _gate_saturated(case, level)
+    z = x["fm"] * x["fs"][lay.cells[:, 0].long()]
+    assert x["fm"].abs().max().item() <= 1e4 and bool((z.float().double() - t).abs().le(1e-6 * t.abs() + 1e-6).all())
+    if level == "hard":
+        assert (z.abs() > 17).double().mean().item() >= 0.25 and (z.abs() < 4).double().mean().item() >= 0.25
+    else:
+        assert all(bool(((z - s * p).abs() <= 1e-6 * p).any()) for p in GATE_PRODUCTS for s in (-1, 1))
+    ref = gate_ref(x["fm"], x["fs"], lay.cells, x["dh"], x["dres"], x["A"], x["dout"])
+    assert all(bool(torch.isfinite(r).all()) for r in ref)
+    hi = z >= 19.9999                                                            # 1 - sigmoid(20) = 2.1e-9 < 2^-25: fp32 holds fm itself there
+    assert bool(((ref[0][hi] - x["fm"][hi]).abs() <= 2.2e-9 * x["fm"][hi].abs()).all())
+    assert bool((ref[0][z <= -745].abs() == 0).all())                            # exp(-745) is 0 in float64
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("level", LEVELS)
+@pytest.mark.parametrize("case", GATE_SAT_CASES, ids=[_gate_id(c) for c in GATE_SAT_CASES])
+def test_gate_saturated_against_fp64(dev, case, level):
+    """smin_gate_fwd and smin_gate_bwd on _gate_saturated: expf overflows on one side and underflows on the other.  hbar is fm exactly
+    where the pre-activation is >= 20 and +-0 where it is <= -110 (fp32's sigmoid is exactly 1 and 0 there), never NaN; dfm and dfs are
+    finite; the empty sample's dfs is exactly 0; the project's gate against gate_ref in float64, e_torch32 from gate_ref in fp32.
+    Measured on an MI355X: INTEGRATION.md, "Saturated inputs"."""
+    from tests.support.compare import gate
+    from vml_amd._lib import call, ptr, stream
+    B, L, D, kind, lens, ndh, ndr, bnd = case
+    lay, x, t = _gate_saturated(case, level)
+    N = lay.N
+    want = gate_ref(x["fm"], x["fs"], lay.cells, x["dh"], x["dres"], x["A"], x["dout"])
+    h = lambda v: v.float()
+    ref32 = gate_ref(h(x["fm"]), h(x["fs"]), lay.cells, [h(v) for v in x["dh"]], [h(v) for v in x["dres"]], h(x["A"]), h(x["dout"]))
+    lay_d = _layout_to(lay, dev)
+    f32 = lambda v: v.float().to(dev)
+    fm, fs, A, dout = (f32(x[k]) for k in ("fm", "fs", "A", "dout"))
+    dh, dres = [f32(v) for v in x["dh"]], [f32(v) for v in x["dres"]]
+    hbar = _nan((N, D), dev)
+    call("smin_gate_fwd", stream(), ptr(fm), ptr(fs), ptr(lay_d.cells), N, D, ptr(hbar))
+    _, mc = chunking_fine(L)
+    dfm, dfs = _nan((N, D), dev), _nan((B, D), dev)
+    ws, wn = _ws_nan(4 * B * mc * D, dev)
+    call("smin_gate_bwd", stream(), _arr(dh), ndh, _arr(dres), ndr, ptr(fm), ptr(fs), ptr(lay_d.row_ptr), N, B, L, D, ptr(dfm), ptr(dfs), ptr(ws), wn,
+         ptr(lay_d.cells), _vp(A), _vp(dout))
+    torch.cuda.synchronize()
+    assert all(bool(torch.isfinite(v).all()) for v in (hbar, dfm, dfs))
+    z = (fm * fs[lay_d.cells[:, 0].long()]).cpu()
+    assert torch.equal(hbar.cpu()[z >= 19.9999], fm.cpu()[z >= 19.9999]) and bool((hbar.cpu()[z <= -110] == 0).all())
+    for name, got, w, r in zip(("hbar", "dfm", "dfs"), (hbar, dfm, dfs), want, ref32):
+        gate(f"gate {_gate_id(case)} {level} {name}", got, w, r)
+    counts = torch.bincount(lay.cells[:, 0].long(), minlength=B)
+    assert bool((counts == 0).any()) == (case == GATE_CASES[1]) and all(bool((dfs[b] == 0).all()) for b in (counts == 0).nonzero().flatten().tolist())
+
+
 @pytest.mark.gpu
 def test_gate_refusals(dev):
     """Arguments outside the documented ranges are refused with a negative code before anything is launched: the NaN-prefilled
@@ -794,6 +882,125 @@ def test_loss_against_fp64(dev, case):
         bad = (got - ref).abs() > LOSS_TOL * ref.abs()
         assert not bool(bad.any()), (label, name, int(bad.sum()), worst[name])
     assert max(g.abs().max().item() for g in grads0) > 1e9 or case[1] < 16
+
+
+# ---------------------------------------------------------------- saturated inputs: loss
+
+# the smallest case whose every head has room for all 36 combinations; the mask bytes 7 and 255; L = 300, the boundary loop's second trip
+LOSS_SAT_CASES = [LOSS_CASES[1], LOSS_CASES[2], LOSS_CASES[3]]
+SAT_P = (0.0, 1e-45, 1e-30, 0.5, 1.0 - 2.0 ** -24, 1.0)          # 1e-45 rounds to fp32's smallest denormal
+SAT_P_NAMES = ("0", "1e-45", "1e-30", "0.5", "1-2^-24", "1")
+SAT_S = (0.0, 0.3, 1.0)
+HEADS = (("pm", "ym", "sm", "mm"), ("ps", "ys", "ss", "lm"), ("pe", "ye", "se", "lm"), ("pa", "ya", None, "lm"))
+
+
+@functools.lru_cache(maxsize=None)
+def _loss_saturated(case):
+    """A case's masks with every valid position of every head holding another of the 36 combinations (p, label, scale target) of
+    SAT_P x {0, 1} x SAT_S, in steps of 7 through their list (a head with fewer than 36 valid positions still meets every (p, label)).
+    Returns (x, {head: (valid flat positions, p index, label, s index)})."""
+    x = {k: v.clone() for k, v in _loss_inputs(case, plant=False)[0].items()}
+    p32, s32 = torch.tensor(SAT_P, dtype=torch.float64).float(), torch.tensor(SAT_S, dtype=torch.float64).float()
+    where = {}
+    for k, (p, y, s, mask) in enumerate(HEADS):
+        valid = (x[mask] != 0).reshape(-1).nonzero().flatten()
+        c = (7 * torch.arange(valid.numel()) + 5 * k) % 36
+        ip, lab, js = c // 6, (c // 3) % 2, c % 3
+        x[p].view(-1)[valid], x[y].view(-1)[valid] = p32[ip], lab.to(torch.uint8)
+        if s is not None:
+            x[s].view(-1)[valid] = s32[js]
+        where[p] = (valid, ip, lab, js)
+    return x, where
+
+
+def _loss_saturated_refs(case):
+    """float64: the oracle's value, loss_ref's partials, loss_grad_ref's gradients at dloss = 1.7.  fp32: training.loss_fn_torch's value
+    and autograd gradients (torch's BCELoss, with its -100 and 1e-12 clamps), loss_ref's partials."""
+    import models  # noqa: F401
+    from oracle import smin_oracle as O
+    from vml_amd.training import loss_fn_torch
+    x, _ = _loss_saturated(case)
+    xd = {k: x[k].double() if x[k].dtype == torch.float32 else x[k] != 0 for k in LOSS_KEYS}
+    value = O.loss_fn(xd["pm"], xd["ym"], xd["sm"], xd["mm"], xd["ps"], xd["ys"], xd["ss"], xd["pe"], xd["ye"], xd["se"], xd["pa"], xd["ya"], xd["lm"])
+    _, part = loss_ref(*[xd[k] for k in LOSS_KEYS])
+    grads = loss_grad_ref(1.7, *[xd[k] for k in LOSS_KEYS])
+    xs = {k: (x[k].clone().requires_grad_(True) if k in ("pm", "ps", "pe", "pa") else x[k] if x[k].dtype == torch.float32 else x[k] != 0)
+          for k in LOSS_KEYS}
+    v32 = loss_fn_torch(xs["pm"], xs["ym"], xs["sm"], xs["mm"], xs["ps"], xs["ys"], xs["ss"], xs["pe"], xs["ye"], xs["se"], xs["pa"], xs["ya"], xs["lm"])
+    g32 = torch.autograd.grad(1.7 * v32, [xs[k] for k in ("pm", "ps", "pe", "pa")])
+    _, p32 = loss_ref(*[x[k] if x[k].dtype == torch.float32 else x[k] != 0 for k in LOSS_KEYS])
+    return (value, part, grads), (v32.detach(), p32, g32)
+
+
+@pytest.mark.parametrize("case", LOSS_SAT_CASES, ids=[_loss_id(c) for c in LOSS_SAT_CASES])
+def test_loss_saturated_inputs_hold_what_they_claim(case):
+    """Every head with 36 valid positions or more (every head but ps, pe, pa of the L = 17 case, which hold every (p, label)) holds every combination of p in SAT_P (as fp32: 0 < 1e-45, 1 - 2^-24 < 1), both labels and -- for the three scaled
+    heads -- the scale targets 0, 0.3, 1 at valid positions; loss_ref in float64 is the oracle's loss_fn there; every reference value is
+    finite; the gradient is identically 0 where p equals its label at 0 or 1 and where the weight is 0."""
+    x, where = _loss_saturated(case)
+    p32 = torch.tensor(SAT_P, dtype=torch.float64).float()
+    assert 0.0 < p32[1].item() < 1e-44 and p32[4].item() < 1.0 and p32[2].item() > 0.0
+    for p, y, s, mask in HEADS:
+        valid, ip, lab, js = where[p]
+        seen = set(zip(ip.tolist(), lab.tolist(), js.tolist() if s else [0] * len(ip)))
+        assert valid.numel() >= 36 or (case == LOSS_CASES[2] and p != "pm")
+        if valid.numel() >= 36:
+            assert seen == {(a, b, c) for a in range(6) for b in (0, 1) for c in (range(3) if s else (0,))}, p
+        assert {(a, b) for a, b, _ in seen} == {(a, b) for a in range(6) for b in (0, 1)}, p
+        assert torch.equal(x[p].view(-1)[valid], p32[ip]) and bool((x[p] >= 0).all() and (x[p] <= 1).all())
+    (value, part, grads), (v32, part32, g32) = _loss_saturated_refs(case)
+    xd = [x[k].double() if x[k].dtype == torch.float32 else x[k] for k in LOSS_KEYS]
+    torch.testing.assert_close(loss_ref(*xd)[0], value, rtol=PIN_TOL, atol=PIN_TOL)
+    assert all(bool(torch.isfinite(t).all()) for t in (value, part, v32, part32, *grads, *g32))
+    for (p, y, s, mask), g in zip(HEADS, grads):
+        valid, ip, lab, js = where[p]
+        gv = g.reshape(-1)[valid]
+        assert bool((gv[((ip == 0) & (lab == 0)) | ((ip == 5) & (lab == 1))] == 0).all())
+        if s:
+            assert bool((gv[((js == 0) & (lab == 1)) | ((js == 2) & (lab == 0))] == 0).all())
+        assert gv.abs().max().item() > 1e7                                       # the floored quotient 1 / 1e-12 over B * count
+
+
+def _loss_run(dev, x, B, L):
+    """smin_loss_fwd / smin_loss_bwd at dloss = 1.7 into NaN-prefilled outputs: (loss, part, (dpm, dps, dpe, dpa))"""
+    from vml_amd._lib import call, ptr, stream
+    d = {k: v.to(dev) for k, v in x.items()}
+    args = [ptr(d[k]) for k in LOSS_KEYS]
+    loss, part = _nan((1,), dev), _nan((B, 6), dev)
+    call("smin_loss_fwd", stream(), *args, B, L, ptr(loss), ptr(part))
+    dloss = torch.tensor([1.7], device=dev)
+    o = [_nan((B, L, L), dev)] + [_nan((B, L), dev) for _ in range(3)]
+    call("smin_loss_bwd", stream(), ptr(dloss), ptr(part), *args, B, L, *[ptr(t) for t in o])
+    torch.cuda.synchronize()
+    return loss, part, o
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("case", LOSS_SAT_CASES, ids=[_loss_id(c) for c in LOSS_SAT_CASES])
+def test_loss_saturated_against_fp64(dev, case):
+    """smin_loss_fwd / smin_loss_bwd on _loss_saturated: p at 0, fp32's smallest denormal, 1e-30, 0.5, 1 - 2^-24 and 1 under both labels
+    and the scale targets 0, 0.3, 1, in all four heads -- logf(p), logf(1 - p) and p (1 - p) on their clamps.  Everything finite, masked
+    positions exactly +0.0, and the project's gate for the value, each column of the partials, and the gradients of every (head, p, label)
+    group taken on its own (a planted 0 or 1 gives a gradient near 1e11 that a whole tensor's max-norm would hide the rest behind; a
+    group whose float64 gradient is identically 0 must be exactly 0).  Measured on an MI355X: INTEGRATION.md, "Saturated inputs"."""
+    from tests.support.compare import gate
+    B, L, _ = case
+    x, where = _loss_saturated(case)
+    (value, part0, grads0), (v32, part32, g32) = _loss_saturated_refs(case)
+    tag = f"loss {_loss_id(case)}"
+    loss, part, grads = _loss_run(dev, x, B, L)
+    assert all(bool(torch.isfinite(t).all()) for t in (loss, part, *grads))
+    gate(f"{tag} value", loss.reshape(()), value, v32)
+    for k, name in enumerate(("sum_m", "cnt_m", "sum_s", "sum_e", "sum_a", "cnt_l")):
+        gate(f"{tag} part {name}", part[:, k], part0[:, k], part32[:, k])
+    for (p, y, s, mask), got, w, r in zip(HEADS, grads, grads0, g32):
+        valid, ip, lab, js = where[p]
+        got = got.cpu()
+        assert bool((got.reshape(-1)[(x[mask] == 0).reshape(-1)].view(torch.int32) == 0).all()), p
+        for a in range(6):
+            for b in (0, 1):
+                at = valid[(ip == a) & (lab == b)]
+                gate(f"{tag} d{p} p = {SAT_P_NAMES[a]} y = {b}", got.reshape(-1)[at], w.reshape(-1)[at], r.reshape(-1)[at])
 
 
 @pytest.mark.gpu

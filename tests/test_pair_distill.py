@@ -23,12 +23,12 @@ import torch
 
 from tests.support.device import dev  # noqa: F401  (the module's device fixture)
 from tests.support.device import vml as V
-from tests.support.compare import bits
+from tests.support.compare import bits, gate
 from tests.support.guards import banded, bands_intact, BAND
 from tests.support.corpora import world  # noqa: F401  (fixture)
 from tests.support.corpora import (
-    checked, corpus_inputs, full_group, hand_step, mined_plan, plan_of, probe, same_parameters, synthetic, tiny_model, GT_VIDEO, NQ, NV, QI9,
-    TINY_SHAPE, VI9)
+    checked, corpus_inputs, full_group, hand_step, mined_plan, plan_of, probe, same_parameters, saturated_pairs, saturated_teacher, synthetic,
+    tiny_model, GT_VIDEO, NQ, NV, QI9, RANK_DEPTHS, TINY_SHAPE, VI9)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = ("smin_pair_distill_fwd", "smin_pair_distill_ws_bytes")
@@ -209,6 +209,59 @@ def test_both_agree_rules():
         got = torch_route(x, plan, t, (0.1, 0.1, 0.1), torch.float64)
         assert want[1] == [2, want_agree] and got[1].tolist() == [2.0, float(want_agree)], (tie_after, best, want[1], got[1].tolist())
         close64(got, want)
+
+
+def stable_kl(c, t, segments, gamma, gamma_teacher):
+    """The term's definition on given pair scores in Python floats (fp64): the mean over the segments of KL(softmax(t / gamma_teacher)
+    || softmax(c / gamma)) from log-softmaxes shifted by their own maxima, and d(loss)/d(c_p).  Returns (loss, [coef_p])."""
+    def log_softmax(v):
+        top = max(v)
+        lz = top + math.log(sum(math.exp(x - top) for x in v))
+        return [x - lz for x in v]
+    total, coef = 0.0, [0.0] * len(c)
+    for seg in segments:
+        ls, lt = log_softmax([c[p] / gamma for p in seg]), log_softmax([t[p] / gamma_teacher for p in seg])
+        total += sum(math.exp(b) * (b - a) for a, b in zip(ls, lt))
+        for p, a, b in zip(seg, ls, lt):
+            coef[p] += (math.exp(a) - math.exp(b)) / gamma
+    return total / len(segments), [v / len(segments) for v in coef]
+
+
+def saturated_want(d, upstream=1.0):
+    """saturated_pairs(d) and saturated_teacher at gamma_teacher = gamma: (x, teacher, gamma, c, fp64 [loss, dpm, dps, dpe]) from
+    stable_kl on the constants; the cells of a pair share its gradient equally (tests/test_pair_rank_loss.py's saturated_want)."""
+    x, gamma, c = saturated_pairs(d, torch.float64)
+    t = saturated_teacher(torch.float64)
+    loss, coef = stable_kl(c, t.tolist(), [[0, 2, 4], [1, 3, 5]], gamma, gamma)
+    dpm = upstream * torch.tensor(coef, dtype=torch.float64).reshape(-1, 1, 1) * x[3].double() / 10
+    return x, t, gamma, c, [torch.tensor(loss, dtype=torch.float64), dpm, 0.5 * (dpm * x[0]).sum(2), 0.5 * (dpm * x[0]).sum(1)]
+
+
+@pytest.mark.parametrize("d", sorted(RANK_DEPTHS))
+def test_saturated_plans_hold_what_they_claim(d):
+    """On the fp64 reference: both temperatures are below 0.0115; the teacher's softmax is saturated on each query's own video (largest
+    probability > 1 - 1e-6); the student's is saturated on the same pair in query 0 and on another in query 1, d * gamma above, so the KL
+    is (about) d / 2; the restatement in fp64 equals the definition written out on the constants, and in fp32 on the host it is finite
+    and within a few roundings of it."""
+    x, t, gamma, c, want = saturated_want(d)
+    plan = plan_of(6, 2)
+    assert [plan.q_pairs.tolist()[a:b] for a, b in zip(plan.q_ptr.tolist(), plan.q_ptr.tolist()[1:])] == [[0, 2, 4], [1, 3, 5]]
+    assert 0.0 < gamma < 0.0115 and torch.tensor(gamma, dtype=torch.float32).item() == gamma
+    for seg, best_t, best_s in (([0, 2, 4], 2, 2), ([1, 3, 5], 5, 1)):
+        pt, ps = torch.softmax(t[seg] / gamma, 0), torch.softmax(torch.tensor(c, dtype=torch.float64)[seg] / gamma, 0)
+        assert pt.max().item() > 1 - 1e-6 and ps.max().item() > 1 - 1e-6
+        assert seg[int(pt.argmax())] == best_t and seg[int(ps.argmax())] == best_s
+    assert (c[1] - c[5]) / gamma == d
+    got = torch_route(x, plan, t, (0.1, gamma, gamma), torch.float64)
+    assert got[2].tolist() == c and got[1].tolist() == [2.0, 1.0]
+    assert abs(got[0].item() - d / 2) <= 1e-6 * d
+    for name, g, w in zip(("loss", "dpm", "dps", "dpe"), [got[0]] + got[3:], want):
+        assert torch.isfinite(g).all() and (g - w).abs().max().item() <= 1e-12 * w.abs().max().item(), (d, name)
+    got32 = torch_route(saturated_pairs(d)[0], plan, saturated_teacher(), (0.1, gamma, gamma), torch.float32)
+    for name, g, w in zip(("loss", "dpm", "dps", "dpe"), [got32[0]] + got32[3:], want):
+        e = (g - w).abs().max().item() / w.abs().max().item()
+        print(f"d = {d} {name}: e_torch32 on the host {e:.2e}")
+        assert torch.isfinite(g).all() and e <= 1e-6, (d, name, e)
 
 
 def excluded_teacher(dtype=torch.float64):
@@ -475,6 +528,28 @@ def test_kernel_on_long_segments(dev, Q, Vn, temps):
     plan, P = the_plan("all", (Q, Vn), dev)
     assert plan.q_ptr.tolist() == [q * Vn for q in range(Q + 1)]
     gate_case(dev, plan, P, 4, temps, f"all pairs (Q, V) = ({Q}, {Vn})")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("d", sorted(RANK_DEPTHS))
+def test_kernel_at_small_temperatures(dev, d):
+    """saturated_pairs(d) under saturated_teacher at gamma_teacher = gamma < 0.0115: both softmaxes saturated, on different pairs in query 1
+    (the KL is about d / 2).  Every output finite, masked cells of dpm exactly 0, and the project's gate for the loss, dpm, dps and dpe
+    against the definition in fp64 (stable_kl on the constants), e_torch32 from pair_distill_loss_torch in fp32 on the device, the
+    upstream gradient 3; pair_score is the constants exactly.
+
+    Measured on an MI355X: INTEGRATION.md, "Saturated inputs"."""
+    _, _, gamma, c, want = saturated_want(d, upstream=3.0)
+    x, t = saturated_pairs(d)[0], saturated_teacher()
+    plan = plan_of(6, 2, dev)
+    temps = (0.1, gamma, gamma)
+    ref32 = torch_route(x, plan, t, temps, torch.float32, dev, upstream=3.0)
+    got = kernel_route(x, plan, t, temps, dev)
+    assert all(torch.isfinite(v).all() for v in got)
+    assert got[1].cpu().tolist() == [2.0, 1.0] and got[2].cpu().tolist() == c
+    for name, g, w, r in zip(("loss", "dpm", "dps", "dpe"), [got[0]] + got[3:], want, [ref32[0]] + ref32[3:]):
+        gate(f"pair_distill d = {d} {name}", g, w, r)
+    assert bits(got[3].cpu()[~x[3]]).eq(0).all()
 
 
 def abi_call(dev, x, plan, t, temps=(0.1, 0.1, 0.1), fill=float("nan"), **kw):

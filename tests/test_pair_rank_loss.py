@@ -8,6 +8,9 @@ GPU: the kernels against pair_rank_loss_torch in fp64, gated by the error of pai
 (e_kernel <= 32 * e_torch32 + 1e-6, e = max|x - x64| / max|x64|); every output written over a sentinel, the same bits twice and on
 both routes, the rejections through the C ABI; through the tiny model against the fp64 oracle (e_new <= 2 * e_ref32 + 1e-6); the two
 loops without a host read and, at rank_weight 0, the parent's step bit for bit.
+Small gamma (saturated_pairs, tests/support/corpora.py): a query whose own video lies d = 50, 95, 120 and 800 temperatures below its best
+negative, against the definition in stable form -- on the host the restatement in fp64 and fp32 (and the formula it had before, which
+gives inf and NaN from d = 120 on), on the GPU the kernels.
 
 Figures measured on an MI355X (printed by the tests): in the docstrings of test_kernels_against_fp64 and the two model tests, and in
 INTEGRATION.md 3q."""
@@ -20,11 +23,11 @@ import torch
 
 from tests.support.device import dev  # noqa: F401  (the module's device fixture)
 from tests.support.device import vml as V
-from tests.support.compare import bits
+from tests.support.compare import bits, gate
 from tests.support.corpora import world  # noqa: F401  (fixture)
 from tests.support.corpora import (
-    checked, expand, full_group, hand_step, loss_of, mined_plan, p19_lists, pair_args, plan_of, probe, same_parameters, synthetic, tiny_model,
-    GT_VIDEO, NQ, NV, QI9, VI9)
+    checked, expand, full_group, hand_step, loss_of, mined_plan, p19_lists, pair_args, plan_of, probe, same_parameters, saturated_pairs,
+    stable_rank_loss, synthetic, tiny_model, GT_VIDEO, NQ, NV, QI9, RANK_DEPTHS, VI9)
 from tests.support.references import abi_call
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -159,6 +162,63 @@ def test_degenerate_plans():
     assert abs(loss.item() - want[0].item()) <= 1e-14 and stats.tolist() == [float(v) for v in want[1]]
 
 
+SEGMENTS, POSITIVES = [[0, 2, 4], [1, 3, 5]], [[2], [5]]                       # plan_of(6, 2)
+
+
+def saturated_want(d, upstream=1.0):
+    """(x, plan-free fp64 results) of saturated_pairs(d) from the definition in stable form on the constants: loss, dpm, dps, dpe.  With
+    constant maps and ps = pe = 1 the cells of a pair share its gradient equally: dpm = coef_p / n on the n = 10 valid cells, and a row's
+    dps (a column's dpe) is half the sum of its cells' dpm * c_p."""
+    x, gamma, c = saturated_pairs(d, torch.float64)
+    loss, coef = stable_rank_loss(c, SEGMENTS, POSITIVES, gamma)
+    mm = x[3].double()
+    dpm = upstream * torch.tensor(coef, dtype=torch.float64).reshape(-1, 1, 1) * mm / 10
+    dps, dpe = 0.5 * (dpm * x[0]).sum(2), 0.5 * (dpm * x[0]).sum(1)
+    return x, gamma, c, [torch.tensor(loss, dtype=torch.float64), dpm, dps, dpe]
+
+
+def parent_form(c, gamma, dtype):
+    """The formula this loss had before it shifted the positives' sum by their own maximum, on query 1 of saturated_pairs: both sums
+    shifted by the segment's maximum.  Returns (l_q, the positive pair's coefficient)."""
+    s = torch.tensor([c[p] for p in SEGMENTS[1]], dtype=dtype)
+    x = torch.exp((s - s.max()) / gamma)
+    zall, zpos = x.sum(), x[2:].sum()
+    return torch.log(zall) - torch.log(zpos), (x[2] / zall - x[2] / zpos) / gamma
+
+
+@pytest.mark.parametrize("d", sorted(RANK_DEPTHS))
+def test_saturated_plans_hold_what_they_claim(d):
+    """Each plan is in the regime it names, measured on the fp64 reference: query 0's own video is its best pair, query 1's lies d * gamma
+    below its best negative, the pooled scores are the constants exactly, and the loss is (about) d / 2.  The restatement in fp64 equals the
+    definition written out on the constants; in fp32 on the host it is finite and within fp32's reach of it, where the parent's formula --
+    both sums shifted by the segment's maximum -- gives inf and NaN from d = 120 on (and inf even in fp64 at d = 800)."""
+    x, gamma, c, want = saturated_want(d)
+    plan = plan_of(6, 2)
+    assert [plan.q_pairs.tolist()[a:b] for a, b in zip(plan.q_ptr.tolist(), plan.q_ptr.tolist()[1:])] == SEGMENTS
+    assert [p for p in range(6) if plan.positive.tolist()[p]] == [2, 5]
+    assert 4 <= plan.P <= 6 and plan.Q == 2 and x[0].shape == (6, 4, 4) and 0.0 < gamma < 0.0115
+    assert torch.tensor(gamma, dtype=torch.float32).item() == gamma
+    got = torch_route(x, plan, 0.1, gamma, torch.float64)
+    assert got[2].tolist() == c and got[1].tolist() == [2.0, 1.0]
+    s = got[2]
+    assert s[2] == s[SEGMENTS[0]].max() and (s[SEGMENTS[1]].max() - s[5]).item() / gamma == d
+    assert abs(got[0].item() - d / 2) <= 1e-7                                    # l_0 < exp(-48), l_1 = d + log(1 + exp(-16 or less))
+    for name, g, w in zip(("loss", "dpm", "dps", "dpe"), [got[0]] + got[3:], want):
+        assert torch.isfinite(g).all() and (g - w).abs().max().item() <= 1e-12 * w.abs().max().item(), (d, name)
+    # fp32 on the host: the restatement holds the definition to a few roundings (every input and s / gamma are exact in fp32) ...
+    got32 = torch_route(saturated_pairs(d)[0], plan, 0.1, gamma, torch.float32)
+    for name, g, w in zip(("loss", "dpm", "dps", "dpe"), [got32[0]] + got32[3:], want):
+        e = (g - w).abs().max().item() / w.abs().max().item()
+        print(f"d = {d} {name}: e_torch32 on the host {e:.2e}")
+        assert torch.isfinite(g).all() and e <= 1e-6, (d, name, e)
+    # ... and the parent's formula does not
+    l32, c32 = parent_form(c, gamma, torch.float32)
+    l64, c64 = parent_form(c, gamma, torch.float64)
+    if d >= 120:
+        assert not torch.isfinite(l32) and not torch.isfinite(c32), (d, l32, c32)
+    assert bool(torch.isfinite(l64)) == (d < 800)
+
+
 def test_refusals():
     api = V()
     x = synthetic(9, 3, seed=7)
@@ -208,14 +268,15 @@ def test_kernels_against_fp64(dev, P, Q, L, tau, gamma):
 
     Measured on an MI355X, e_kernel / e_torch32, the worst of dpm, dps, dpe and in brackets the loss (INTEGRATION.md 3q has the table):
         (P, Q, L)      (tau, gamma) = (1, 1)                   (0.1, 0.1)                              (0.01, 0.05)
-        (9, 4, 3)      2.8e-7 / 1.3e-7 (9.0e-8 / 1.6e-8)       2.0e-7 / 2.0e-7 (8.5e-8 / 1.3e-7)       1.3e-7 / 1.4e-7 (3.4e-8 / 3.4e-8)
-        (9, 4, 8)      1.6e-7 / 1.9e-7 (2.6e-8 / 2.6e-8)       3.5e-7 / 4.6e-7 (9.1e-8 / 1.1e-7)       1.6e-6 / 5.1e-7 (9.2e-7 / 3.7e-7)
-        (19, 4, 17)    1.5e-7 / 1.1e-7 (1.9e-9 / 1.9e-9)       1.1e-7 / 2.2e-7 (1.2e-8 / 1.2e-8)       3.0e-7 / 2.3e-7 (1.2e-7 / 6.9e-8)
-        (6, 2, 64)     1.7e-7 / 1.6e-7 (7.5e-8 / 7.5e-8)       4.9e-7 / 2.3e-7 (6.1e-9 / 7.7e-8)       2.4e-6 / 2.5e-6 (1.7e-7 / 1.7e-7)
-        (2, 1, 260)    2.8e-7 / 2.4e-7 (1.8e-7 / 8.3e-8)       5.9e-7 / 3.2e-7 (1.7e-7 / 1.7e-8)       1.2e-6 / 1.3e-6 (7.8e-8 / 7.1e-7)
-        mined, L = 8   9.3e-8 / 8.9e-8 (5.0e-8 / 5.0e-8)       3.4e-7 / 4.1e-7 (1.3e-7 / 2.3e-7)       7.5e-7 / 7.5e-7 (2.0e-7 / 2.0e-7)
+        (9, 4, 3)      1.2e-7 / 1.1e-7 (1.2e-7 / 1.2e-7)       2.0e-7 / 2.0e-7 (2.2e-8 / 1.3e-7)       1.3e-7 / 1.3e-7 (4.1e-8 / 3.4e-8)
+        (9, 4, 8)      1.6e-7 / 1.1e-7 (2.6e-8 / 2.6e-8)       3.5e-7 / 5.0e-7 (9.1e-8 / 1.1e-7)       1.6e-6 / 7.0e-7 (9.2e-7 / 3.7e-7)
+        (19, 4, 17)    1.5e-7 / 5.7e-8 (1.9e-9 / 1.9e-9)       1.1e-7 / 1.9e-7 (1.2e-8 / 1.2e-8)       3.0e-7 / 2.0e-7 (1.2e-7 / 6.9e-8)
+        (6, 2, 64)     1.7e-7 / 1.2e-7 (7.5e-8 / 7.5e-8)       4.9e-7 / 2.1e-7 (6.5e-8 / 6.5e-8)       2.4e-6 / 2.5e-6 (1.7e-7 / 1.7e-7)
+        (2, 1, 260)    2.8e-7 / 1.4e-7 (1.8e-7 / 8.3e-8)       5.9e-7 / 3.2e-7 (1.7e-7 / 1.7e-8)       1.2e-6 / 1.3e-6 (7.8e-8 / 7.1e-7)
+        mined, L = 8   9.3e-8 / 2.3e-7 (5.0e-8 / 5.0e-8)       3.4e-7 / 4.1e-7 (1.3e-7 / 2.3e-7)       7.5e-7 / 6.4e-7 (2.0e-7 / 2.0e-7)
     (1, 1, 1): loss and gradients identically 0, exactly 0 on the device; pair_score 1.1e-7 / 1.1e-7.  pair_score elsewhere: 1.8e-8 to
-    8.5e-7 on both sides.  The largest e_kernel / e_torch32 of any quantity: 10.4."""
+    8.5e-7 on both sides.  The largest e_kernel / e_torch32 of any quantity: 10.4.  (Figures of the kernel and the restatement that
+    shift each sum by its own maximum.)"""
     if P == "mined":
         plan, P = mined_plan(dev), 9
     else:
@@ -240,6 +301,28 @@ def test_kernels_against_fp64(dev, P, Q, L, tau, gamma):
         assert e_k <= 32 * e_t + 1e-6, (name, e_k, e_t)
     if not x[3].all():
         assert got[3].cpu()[~x[3]].abs().max().item() == 0.0
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("d", sorted(RANK_DEPTHS))
+def test_kernels_at_small_gamma(dev, d):
+    """saturated_pairs(d): the hard query's own video d * gamma below its best negative, d in {50, 95, 120, 800}.  Every output finite,
+    masked cells of dpm exactly 0, stats the fp64 reference's, and the project's gate for the loss, pair_score, dpm, dps and dpe against
+    the definition in stable form in fp64 (written out on the constants: saturated_want; pair_rank_loss_torch in fp64 equals it to 1e-12
+    on the host), e_torch32 from pair_rank_loss_torch in fp32 on the device, the upstream gradient 3.  With both sums shifted by the
+    segment's maximum the kernel returned loss inf and NaN gradients from d = 120 on.
+
+    Measured on an MI355X: INTEGRATION.md, "Saturated inputs"."""
+    _, gamma, c, want = saturated_want(d, upstream=3.0)
+    x = saturated_pairs(d)[0]
+    plan = plan_of(6, 2, dev)
+    ref32 = torch_route(x, plan, 0.1, gamma, torch.float32, dev, upstream=3.0)
+    got = kernel_route(x, plan, 0.1, gamma, dev)
+    assert all(torch.isfinite(t).all() for t in got)
+    assert got[1].cpu().tolist() == [2.0, 1.0] and got[2].cpu().tolist() == c
+    for name, g, w, r in zip(("loss", "dpm", "dps", "dpe"), [got[0]] + got[3:], want, [ref32[0]] + ref32[3:]):
+        gate(f"pair_rank d = {d} {name}", g, w, r)
+    assert bits(got[3].cpu()[~x[3]]).eq(0).all()
 
 
 def abi_bwd(dev, a, fill=float("nan"), **kw):

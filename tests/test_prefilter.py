@@ -321,6 +321,59 @@ def test_prefilter_scores_kernel(dev, shape, tau):
         gate(tag + " pool.sum", om["pool"][..., 1], want[1][..., 1], ref32[1][..., 1])
 
 
+SAT_SHAPE = SHAPES[1]                                  # the smallest shape, and one whose every window mean weighs whole frames (T // L >= C)
+LEVELS = ("hard", "frozen")
+
+
+@pytest.mark.parametrize("level", LEVELS)
+def test_saturated_first_stage_inputs_hold_what_they_claim(level):
+    """On the fp64 restatement: the three heads' pre-activations of a pair are c_v k_q at every valid cell and clip -- frozen: all in
+    +-{20, 95, 110}, each under both signs; hard: two fifths beyond +-17 and three fifths inside +-4 --, so the scores of a pair are all
+    sigmoid(c_v k_q), exactly 1.0f from +20 on and 0.0f at -110."""
+    A = V()
+    Q, Vn, T, L, C, D = SAT_SHAPE
+    x, z = WS.saturated_prefilter(WS.uncached_inputs(SAT_SHAPE, "cpu"), level)
+    out = A.prefilter_scores_torch(x["fv"].double(), x["fs"].double(), x["w"].double(), x["b"].double(), x["lm"], x["mm"], T, L, C, 0.1, maps=True)
+    p = torch.sigmoid(z.double())
+    for m, valid in ((out[3], x["mm"]), (out[4], x["lm"]), (out[5], x["lm"])):
+        assert bool(valid.any()) and not bool(valid.all())
+        want = p.view(Q, Vn, *([1] * (m.dim() - 2))) * valid.unsqueeze(0)
+        assert (m - want).abs().max().item() <= 1e-6 * 110                         # (sigmoid' <= 1/4; the inputs carry fp32's rounding)
+    live = z[:, x["lm"].any(1)]
+    if level == "frozen":
+        assert {abs(v) for v in live.flatten().tolist()} == set(WS.PREFILTER_PRE) and bool((live > 0).any() and (live < 0).any())
+        assert {v for v in live.flatten().tolist()} >= {s * m for m in WS.PREFILTER_PRE for s in (-1.0, 1.0)}
+    else:
+        assert (live.abs() > 17).double().mean().item() >= 0.25 and (live.abs() < 4).double().mean().item() >= 0.25
+    assert bool((p[z >= 20].float() == 1.0).all()) and bool((p[z <= -110].float() == 0.0).all())
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("level", LEVELS)
+def test_prefilter_scores_saturated(dev, level):
+    """smin_prefilter_scores on saturated_prefilter: the maps exactly 1.0 where the pair's pre-activation is +20 or more and exactly 0.0 at
+    -110, +0.0 at every masked cell and snippet, everything finite, and the project's gate for the maps, the score and the pool against
+    the fp64 restatement.  Measured on an MI355X: INTEGRATION.md, "Saturated inputs"."""
+    Q, Vn, T, L, C, D = SAT_SHAPE
+    x, z = WS.saturated_prefilter(inputs(SAT_SHAPE, dev), level)
+    rc, o, bufs = scores_abi(dev, x, 0.1)
+    assert rc == 0 and all(torch.isfinite(o[k]).all() and bands_intact(bufs[k]) for k in o)
+    maps = (o["pm0"].reshape(Q, Vn, L, L).cpu(), o["ps0"].reshape(Q, Vn, L).cpu(), o["pe0"].reshape(Q, Vn, L).cpu())
+    for m, valid in zip(maps, (x["mm"].cpu(), x["lm"].cpu(), x["lm"].cpu())):
+        keep = valid.unsqueeze(0).expand_as(m)
+        assert bool((m[~keep].view(torch.int32) == 0).all())
+        zz = z.view(Q, Vn, *([1] * (m.dim() - 2))).expand_as(m)
+        assert bool((m[keep & (zz >= 20)] == 1.0).all()) and bool((m[keep & (zz <= -110)] == 0.0).all())
+    want, ref32 = references(x, 0.1)
+    tag = f"prefilter_scores {level}"
+    gate(tag + " pm0", maps[0], want[3], ref32[3])
+    gate(tag + " ps0", maps[1], want[4], ref32[4])
+    gate(tag + " pe0", maps[2], want[5], ref32[5])
+    gate(tag + " score", o["score"], want[0], ref32[0])
+    gate(tag + " pool.m", o["pool"][..., 0], want[1][..., 0], ref32[1][..., 0])
+    gate(tag + " pool.sum", o["pool"][..., 1], want[1][..., 1], ref32[1][..., 1])
+
+
 @pytest.mark.gpu
 def test_prefilter_scores_workspace_and_rejections(dev):
     x = inputs(SHAPES[1], dev)

@@ -256,6 +256,39 @@ def test_maps_bwd_kernel(dev, shape, mode):
         gate(f"{shape} {mode} {name}", o[name], x["ref64"][k], x["ref32"][k])
 
 
+SAT_SHAPE = SHAPES[1]                                  # tests/test_prefilter.py's SAT_SHAPE: every window mean weighs whole frames
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("level", ["hard", "frozen"])
+def test_maps_bwd_saturated(dev, level):
+    """smin_prefilter_maps_bwd on saturated_prefilter (tests/support/corpora.py; tests/test_prefilter.py shows on the host that the cases
+    are in the regime they name), on the maps smin_prefilter_scores stored: everything finite and the project's gate for dfv, dfs, dw and
+    db against fp64 autograd of the restatement; and with an upstream gradient that is nonzero only where the stored score p has
+    p (1 - p) == 0 -- scores of exactly 0.0 and 1.0 -- every gradient is exactly 0.  Measured on an MI355X: INTEGRATION.md, "Saturated
+    inputs"."""
+    from tests.support.corpora import saturated_prefilter
+    A = V()
+    Q, Vn, T, L, C, D = SAT_SHAPE
+    x, z = saturated_prefilter(inputs(SAT_SHAPE, dev), level)
+
+    def autograd(dtype):
+        leaves = [x[k].to(dtype).requires_grad_(True) for k in ("fv", "fs", "w", "b")]
+        out = A.prefilter_scores_torch(*leaves, x["lm"], x["mm"], T, L, C, 0.1, maps=True)
+        loss = sum((o.reshape(u.shape) * u.to(dtype)).sum() for o, u in zip(out[3:], x["up"]))
+        return [t.detach() for t in torch.autograd.grad(loss, leaves)]
+    want, ref32 = autograd(torch.float64), autograd(torch.float32)
+    maps = forward_abi(dev, x)
+    rc, o, bufs = bwd_abi(dev, x, maps)
+    assert rc == 0 and all(torch.isfinite(o[name]).all() and bands_intact(bufs[name]) for name in GRADS)
+    for k, name in enumerate(GRADS):
+        gate(f"prefilter_maps_bwd {level} {name}", o[name], want[k], ref32[k])
+    flat = [(m * (1 - m) == 0) for m in maps]
+    assert all(bool(f.any()) for f in flat) and (level == "frozen" or not all(bool(f.all()) for f in flat))
+    rc, o, _ = bwd_abi(dev, x, maps, up=[torch.where(f, u, torch.zeros_like(u)) for f, u in zip(flat, x["up"])])
+    assert rc == 0 and all(bool((o[name] == 0).all()) for name in GRADS)
+
+
 @pytest.mark.gpu
 def test_zero_masks_give_exact_zeros(dev):
     """every lmask zero: dps0 and dpe0 contribute exactly 0 to dfv, dfs and dw (the map's heads alone remain), db[1] = db[2] = 0"""

@@ -636,9 +636,10 @@ def _bu_id(c):
     return "B{}_L{}_Nq{}_D{}_{}_{}".format(*c)
 
 
-def _bu_inputs(B, L, Nq, D, mask, g):
+def _bu_inputs(B, L, Nq, D, mask, g, spread=1.5):
     """Inputs whose two softmaxes are spread: f_b rows are mostly a per-row multiple of one direction, so that the self-attention
-    logits <bqv_i, bqv_j> / sqrt(D) vary along the row instead of being dominated by the diagonal."""
+    logits <bqv_i, bqv_j> / sqrt(D) vary along the row instead of being dominated by the diagonal.  spread: the standard deviation both
+    logit tensors are scaled to."""
     lens = default_lens(B, L)
     if B >= 3:
         lens[2] = 0                                                   # a sample of length 0
@@ -667,12 +668,12 @@ def _bu_inputs(B, L, Nq, D, mask, g):
                                              p["W_k.bias"], qmask, lm)
         sz = _spread(Z, slive)
         if sz:
-            fb = fb * math.sqrt(1.5 / sz)
+            fb = fb * math.sqrt(spread / sz)
         _, _, _, S, Z, _ = boundary_unit_ref(fb, fw, fs, fb.new_zeros(0, D), no_cells, p["W_q.weight"], p["W_q.bias"], p["W_k.weight"],
                                              p["W_k.bias"], qmask, lm)
         sw = _spread(S, wlive)
         if sw:
-            p["W_k.weight"], p["W_k.bias"] = p["W_k.weight"] * (1.5 / sw), p["W_k.bias"] * (1.5 / sw)
+            p["W_k.weight"], p["W_k.bias"] = p["W_k.weight"] * (spread / sw), p["W_k.bias"] * (spread / sw)
     return lm, mm, qmask, fb, fw, fs, p
 
 
@@ -906,3 +907,233 @@ def test_score_map_against_fp64(dev, case):
         again = run(with_pm, with_sea)
         assert all(torch.equal(o[k], again[k]) for k in keys), (label, "backward not deterministic")
     _report("score_map", label, worst)
+
+
+# ---------------------------------------------------------------- saturated inputs: boundary unit
+
+BU_SAT_CASES = [BU_CASES[2], BU_CASES[3]]     # the smallest from_mask case with an empty sample and a query without words; all_cells
+BU_NAMES = ("fb", "fw", "fs", "hbar", "Wq", "bq", "Wk", "bk")
+LEVELS = ("hard", "frozen")
+
+
+def _bu_saturated(case, level):
+    """test_boundary_unit_against_fp64's inputs with both softmaxes driven by what the float64 reference measures.  frozen: _bu_inputs'
+    own scaling aimed at a logit standard deviation of 100.  hard: the rows of the even samples -- the word logits are linear in f_b,
+    the self logits quadratic -- scaled by the smallest power of 2^(1/2) at which a quarter of all live rows of either softmax have a
+    largest probability above 1 - 1e-6; the odd samples keep their spread of 1.5.  Returns (lm, qmask, lay, x, G)."""
+    B, L, Nq, D, layout, mask = case
+    g = torch.Generator().manual_seed(B * 7 + L + Nq + D)
+    lm, mm, qmask, fb, fw, fs, p = _bu_inputs(B, L, Nq, D, mask, g, spread=100.0 if level == "frozen" else 1.5)
+    lay = make_layout(mm, layout)
+    hbar, G = torch.randn(lay.N, D, generator=g, dtype=torch.float64), torch.randn(B, L, D, generator=g, dtype=torch.float64)
+    x = dict(fb=fb, fw=fw, fs=fs, hbar=hbar, Wq=p["W_q.weight"], bq=p["W_q.bias"], Wk=p["W_k.weight"], bk=p["W_k.bias"])
+    x = {k: v.float().double() for k, v in x.items()}
+    if level == "hard":
+        even = (torch.arange(B) % 2 == 0).double().view(B, 1, 1)
+        for e in range(1, 24):
+            y = dict(x, fb=(x["fb"] * (1 + even * (2.0 ** (e / 2) - 1))).float().double())
+            tw, ts = _bu_tops(y, lay, qmask, lm)
+            if (tw > 1 - 1e-6).double().mean().item() >= 0.25 and (ts > 1 - 1e-6).double().mean().item() >= 0.25:
+                x = y
+                break
+        else:
+            raise AssertionError(f"no scale puts {_bu_id(case)} into the hard regime")
+    return lm, qmask, lay, x, G.float().double()
+
+
+def _bu_tops(x, lay, qmask, lm):
+    """the largest probability of every live row of the word softmax (rows of samples with a word) and of the self softmax"""
+    with torch.no_grad():
+        _, P, A, S, Z, _ = boundary_unit_ref(x["fb"], x["fw"], x["fs"], x["hbar"], lay.cells, x["Wq"], x["bq"], x["Wk"], x["bk"], qmask, lm)
+    rows = lm > 0
+    return P.max(-1).values[rows & (qmask > 0).any(1, keepdim=True)], torch.softmax(Z, -1).max(-1).values[rows]
+
+
+def _bu_refs(x, lay, qmask, lm, G, dtype):
+    leaves = {k: v.to(dtype).clone().requires_grad_(True) for k, v in x.items()}
+    out, P, A, S, Z, _ = boundary_unit_ref(*[leaves[k] for k in ("fb", "fw", "fs", "hbar")], lay.cells, *[leaves[k] for k in ("Wq", "bq", "Wk", "bk")],
+                                           qmask.to(dtype), lm.to(dtype))
+    grads = torch.autograd.grad((out * G.to(dtype)).sum(), [leaves[k] for k in BU_NAMES])
+    return out.detach(), P.detach(), A.detach(), S.detach(), Z.detach(), dict(zip(BU_NAMES, grads))
+
+
+@pytest.mark.parametrize("level", LEVELS)
+@pytest.mark.parametrize("case", BU_SAT_CASES, ids=[_bu_id(c) for c in BU_SAT_CASES])
+def test_boundary_unit_saturated_inputs_hold_what_they_claim(case, level):
+    """On the float64 reference, for the word softmax and for the self softmax.  hard: at least a quarter of the live rows with a largest
+    probability above 1 - 1e-6 and a quarter below 0.9.  frozen: a logit standard deviation of 100 (to 5 %) and at least 60 % of the rows
+    one-hot to 1e-6.  The first case holds a sample of length 0 (rows with length_mask == 0 everywhere) and a query whose every word is
+    masked (every logit -1e9: a uniform softmax); both hold rows beyond their sample's length."""
+    B, L, Nq, D, layout, mask = case
+    lm, qmask, lay, x, G = _bu_saturated(case, level)
+    out, P, A, S, Z, grads = _bu_refs(x, lay, qmask, lm, G, torch.float64)
+    assert all(bool(torch.isfinite(v).all()) for v in (out, P, A, *grads.values()))
+    tw, ts = _bu_tops(x, lay, qmask, lm)
+    for top in (tw, ts):
+        if level == "hard":
+            assert (top > 1 - 1e-6).double().mean().item() >= 0.25 and (top < 0.9).double().mean().item() >= 0.25
+        else:
+            assert (top > 1 - 1e-6).double().mean().item() >= 0.6
+    if level == "frozen":
+        sw = _spread(S, (qmask > 0).unsqueeze(1) & (lm > 0).unsqueeze(-1))
+        sz = _spread(Z, (lm > 0).unsqueeze(1) & (lm > 0).unsqueeze(-1))
+        assert abs(sw - 100) <= 5 and abs(sz - 100) <= 5, (sw, sz)
+    assert bool((lm == 0).any())
+    if B >= 4:
+        assert bool((lm[2] == 0).all()) and bool((qmask[3] == 0).all()) and bool((S[3] == -1e9).all())
+        assert (P[3] - 1.0 / Nq).abs().max().item() <= 1e-15
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("level", LEVELS)
+@pytest.mark.parametrize("case", BU_SAT_CASES, ids=[_bu_id(c) for c in BU_SAT_CASES])
+def test_boundary_unit_saturated_against_fp64(dev, case, level):
+    """smin_boundary_unit_fwd / _bwd through the C ABI with both softmaxes partly (hard) or wholly (frozen) one-hot, rows beyond the
+    length, an empty sample and a query without words: everything finite; out, P and A of the rows beyond the length as the reference
+    has them (A exactly 0); the project's gate for out, P, A and the eight gradients against boundary_unit_ref in float64 with
+    e_torch32 from the same in fp32.
+    Measured on an MI355X: INTEGRATION.md, "Saturated inputs"."""
+    import models
+    from tests.support.compare import gate
+    from vml_amd._lib import call, ptr, stream
+    B, L, Nq, D, layout, mask = case
+    lm, qmask, lay, x, G = _bu_saturated(case, level)
+    N = lay.N
+    out0, P0, A0, _, _, g0 = _bu_refs(x, lay, qmask, lm, G, torch.float64)
+    out32, P32, A32, _, _, g32 = _bu_refs(x, lay, qmask, lm, G, torch.float32)
+    lay_d = _layout_to(lay, dev)
+    d = {k: v.float().to(dev) for k, v in x.items()}
+    qm_d, lm_d, G_d = qmask.float().to(dev), lm.float().to(dev), G.float().to(dev)
+    outc, Qb, baq, bqv = (_nan((B, L, D), dev) for _ in range(4))
+    Kb_d, P, A = _nan((B, Nq, D), dev), _nan((B, L, Nq), dev), _nan((B, L, L), dev)
+    call("smin_boundary_unit_fwd", stream(), ptr(d["fb"]), ptr(d["fw"]), ptr(d["fs"]), _vp(d["hbar"]), ptr(lay_d.cells), ptr(lay_d.row_ptr),
+         N, B, L, Nq, D, ptr(d["Wq"]), ptr(d["bq"]), ptr(d["Wk"]), ptr(d["bk"]), ptr(qm_d), ptr(lm_d),
+         ptr(outc), ptr(Qb), ptr(Kb_d), ptr(P), ptr(baq), ptr(bqv), ptr(A))
+    nbytes = models.vml_amd._lib.load().smin_boundary_unit_bwd_ws_bytes(B, L, Nq, D)
+    WqT, WkT = d["Wq"].t().contiguous(), d["Wk"].t().contiguous()
+    o = {k: _nan(v.shape, dev) for k, v in d.items()}
+    ws, wn = _ws_nan(nbytes, dev)
+    call("smin_boundary_unit_bwd", stream(), ptr(G_d), ptr(d["fb"]), ptr(d["fw"]), ptr(d["fs"]), _vp(d["hbar"]), ptr(lay_d.cells),
+         ptr(lay_d.row_ptr), N, B, L, Nq, D, ptr(WqT), ptr(WkT), ptr(qm_d), ptr(lm_d), ptr(Qb), ptr(Kb_d), ptr(P), ptr(baq), ptr(bqv), ptr(A),
+         ptr(o["fb"]), ptr(o["fw"]), ptr(o["fs"]), _vp(o["hbar"]), ptr(o["Wq"]), ptr(o["bq"]), ptr(o["Wk"]), ptr(o["bk"]), ptr(ws), wn)
+    torch.cuda.synchronize()
+    assert all(bool(torch.isfinite(v).all()) for v in (outc, P, A, *o.values()))
+    assert bool((A.cpu()[lm == 0] == 0).all())
+    tag = f"boundary_unit {_bu_id(case)} {level}"
+    gate(tag + " out", outc, out0, out32)
+    gate(tag + " P", P, P0, P32)
+    gate(tag + " A", A, A0, A32)
+    for k in BU_NAMES:
+        gate(tag + " d" + k, o[k], g0[k], g32[k])
+
+
+# ---------------------------------------------------------------- saturated inputs: score map
+
+SC_SAT_CASES = [SC_CASES[0], SC_CASES[1]]     # the smallest case with D < 512 (cells absent from the list) and the one with D > 512
+SC_PRE = (20.0, 95.0, 110.0)
+
+
+def _sc_saturated(case, level):
+    """test_score_map_against_fp64's layout and weights with fm and fb moved along the heads' weight vectors so that the four heads'
+    pre-activations take given values: +-{20, 95, 110} everywhere (frozen), or on half of the cells and rows with N(0, 2) on the rest
+    (hard).  Returns (lay, lm, x, Gm, Gs, the targets of the map head [N] and of the three row heads [3, B, L])."""
+    B, L, D, layout, mask = case
+    lens = default_lens(B, L)
+    lay = make_layout(moment_mask(B, L, mask, lens, torch.Generator().manual_seed(B * 1000 + L)), layout)
+    N = lay.N
+    g = torch.Generator().manual_seed(B + L + D + len(level))
+    r = lambda *s: torch.randn(*s, generator=g, dtype=torch.float64)
+    lm = lengths_mask(B, L, lens).double()
+    x = dict(fm=r(N, D), fb=r(B, L, D), wm=r(D) * 1.5 / math.sqrt(D), bm=r(1), wb=r(3, D) * 1.5 / math.sqrt(D), bb=r(3))
+    x = {k: v.float().double() for k, v in x.items()}
+
+    def targets(*s):
+        t = torch.tensor(SC_PRE, dtype=torch.float64)[torch.randint(0, 3, s, generator=g)] * (torch.randint(0, 2, s, generator=g).double() * 2 - 1)
+        return t if level == "frozen" else torch.where(torch.rand(*s, generator=g) < 0.5, t, 2 * r(*s))
+    tm, tb = targets(N), targets(3, B, L)
+    wm, wb = x["wm"], x["wb"]
+    x["fm"] = (x["fm"] + ((tm - x["bm"] - x["fm"] @ wm) / (wm @ wm)).unsqueeze(1) * wm).float().double()
+    miss = tb - x["bb"].view(3, 1, 1) - torch.einsum("bld,kd->kbl", x["fb"], wb)
+    x["fb"] = (x["fb"] + torch.einsum("kbl,kd->bld", torch.linalg.solve(wb @ wb.t(), miss.reshape(3, -1)).reshape(3, B, L), wb)).float().double()
+    return lay, lm, x, r(B, L, L).float().double(), r(3, B, L).float().double(), tm, tb
+
+
+def _sc_refs(lay, lm, x, Gm, Gs, dtype):
+    """score_heads_ref and its gradients in ``dtype``: (pm, psea, {name: gradient})"""
+    leaves = {k: v.to(dtype).requires_grad_(True) for k, v in x.items()}
+    pm, psea = score_heads_ref(leaves["fm"], leaves["fb"], lay.cells, leaves["wm"], leaves["bm"], leaves["wb"], leaves["bb"], lm.to(dtype))
+    names = ("fm", "wm", "bm", "fb", "wb", "bb")
+    grads = torch.autograd.grad((pm * Gm.to(dtype)).sum() + (psea * Gs.to(dtype)).sum(), [leaves[k] for k in names])
+    return pm.detach(), psea.detach(), dict(zip(names, grads))
+
+
+@pytest.mark.parametrize("level", LEVELS)
+@pytest.mark.parametrize("case", SC_SAT_CASES, ids=[_sc_id(c) for c in SC_SAT_CASES])
+def test_score_map_saturated_inputs_hold_what_they_claim(case, level):
+    """On the float64 reference: the fp32 inputs' pre-activations are the targets to 1e-4; hard -- a quarter of them beyond +-17 and a
+    quarter inside +-4; frozen -- all of them at +-{20, 95, 110}, every value under both signs in the map head and in the row heads;
+    scores at +20 and above round to 1.0f and those at -110 to 0.0f."""
+    lay, lm, x, Gm, Gs, tm, tb = _sc_saturated(case, level)
+    zm = x["fm"] @ x["wm"] + x["bm"]
+    zb = torch.einsum("bld,kd->kbl", x["fb"], x["wb"]) + x["bb"].view(3, 1, 1)
+    assert (zm - tm).abs().max().item() <= 1e-4 and (zb - tb).abs().max().item() <= 1e-4
+    for z in (zm, zb):
+        if level == "hard":
+            assert (z.abs() > 17).double().mean().item() >= 0.25 and (z.abs() < 4).double().mean().item() >= 0.25
+        else:
+            assert all(bool(((z - s * p).abs() <= 1e-4).any()) for p in SC_PRE for s in (-1, 1)) and z.abs().min().item() > 19.99
+    pm, psea, grads = _sc_refs(lay, lm, x, Gm, Gs, torch.float64)
+    assert all(bool(torch.isfinite(v).all()) for v in (pm, psea, *grads.values()))
+    live = lay.cells[:, 3] != 0
+    s = torch.sigmoid(zm)[live]
+    assert bool((s[zm[live] > 19.99].float() == 1.0).all()) and bool((s[zm[live] < -109.99].float() == 0.0).all())
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("level", LEVELS)
+@pytest.mark.parametrize("case", SC_SAT_CASES, ids=[_sc_id(c) for c in SC_SAT_CASES])
+def test_score_map_saturated_against_fp64(dev, case, level):
+    """smin_score_map_fwd / _bwd on _sc_saturated.  Scores are exactly 1.0 from a pre-activation of +20 on and exactly 0.0 from -110 on;
+    cells absent from the list and rows beyond the length are +0.0; wherever the kernel's own score p has p (1 - p) == 0 the gradient
+    row of fm (of fb: when all three heads are there) is exactly 0; everything finite; the project's gate against score_heads_ref in
+    float64, e_torch32 from the same in fp32.  Measured on an MI355X: INTEGRATION.md, "Saturated inputs"."""
+    import models
+    from tests.support.compare import gate
+    from vml_amd._lib import call, ptr, stream
+    B, L, D, layout, mask = case
+    lay, lm, x, Gm, Gs, tm, tb = _sc_saturated(case, level)
+    N = lay.N
+    pm0, psea0, g0 = _sc_refs(lay, lm, x, Gm, Gs, torch.float64)
+    pm32, psea32, g32 = _sc_refs(lay, lm, x, Gm, Gs, torch.float32)
+    lay_d = _layout_to(lay, dev)
+    d = {k: v.float().to(dev) for k, v in x.items()}
+    lm_d = lm.float().to(dev)
+    pm, psea = _nan((B, L, L), dev), _nan((3, B, L), dev)
+    call("smin_score_map_fwd", stream(), ptr(d["fm"]), ptr(d["fb"]), ptr(lay_d.cells), N, B, L, D, ptr(d["wm"]), ptr(d["bm"]), ptr(d["wb"]),
+         ptr(d["bb"]), ptr(lm_d), ptr(pm), ptr(psea))
+    nbytes = models.vml_amd._lib.load().smin_score_map_bwd_ws_bytes(N, B, L, D)
+    o = {k: _nan(v.shape, dev) for k, v in d.items()}
+    ws, wn = _ws_nan(nbytes, dev)
+    Gm_d, Gs_d = Gm.float().to(dev), Gs.float().to(dev)
+    call("smin_score_map_bwd", stream(), ptr(Gm_d), ptr(Gs_d), ptr(pm), ptr(psea), ptr(d["fm"]), ptr(d["fb"]),
+         ptr(lay_d.cells), N, B, L, D, ptr(d["wm"]), ptr(d["wb"]), ptr(lm_d), ptr(o["fm"]), ptr(o["fb"]), ptr(o["wm"]), ptr(o["bm"]), ptr(o["wb"]),
+         ptr(o["bb"]), ptr(ws), wn)
+    torch.cuda.synchronize()
+    pm_h, psea_h = pm.cpu(), psea.cpu()
+    assert all(bool(torch.isfinite(v).all()) for v in (pm, psea, *o.values()))
+    assert bool((pm_h[lay.cellmap < 0].view(torch.int32) == 0).all()) and bool((psea_h[:, lm == 0].view(torch.int32) == 0).all())
+    c = lay.cells.long()
+    live = c[:, 3] != 0
+    at = pm_h[c[:, 0], c[:, 1], c[:, 2]]
+    assert bool((at[live & (tm > 19.99)] == 1.0).all()) and bool((at[live & (tm < -109.99)] == 0.0).all())
+    on = (lm != 0).expand(3, B, L)
+    assert bool((psea_h[on & (tb > 19.99)] == 1.0).all()) and bool((psea_h[on & (tb < -109.99)] == 0.0).all())
+    flat = (at * (1 - at) == 0) | ~live
+    assert bool(flat.any()) and bool((o["fm"].cpu()[flat] == 0).all())
+    flat_rows = ((psea_h * (1 - psea_h)) == 0).all(0)
+    assert bool((o["fb"].cpu()[flat_rows] == 0).all())
+    tag = f"score_map {_sc_id(case)} {level}"
+    gate(tag + " pm", pm, pm0, pm32)
+    gate(tag + " psea", psea, psea0, psea32)
+    for k in ("fm", "wm", "bm", "fb", "wb", "bb"):
+        gate(tag + " d" + k, o[k], g0[k], g32[k])

@@ -67,7 +67,7 @@ def pre_activation_grad(steps, B, Nq, H):
     ar = torch.arange(B)
     for d, pos, act, z in steps:
         if z.grad is not None:
-            dG[ar[act], pos[act], d] = z.grad[act]
+            dG[ar[act], pos[act], d] = z.grad[act].double()
     return dG
 
 
@@ -453,6 +453,108 @@ def test_layer_both_recurrences_against_fp64(dev, case, monkeypatch):
     monkeypatch.setenv("SMIN_LSTM_STREAMED", "1")
     _check_regime(case, True)
     _run_layer_case(dev, case, True, "forced-" + _layer_id(case, True))
+
+
+# ---------------------------------------------------------------- saturated gates
+
+# H = 32 through both recurrences (FORCED_CASES' case) and H = 256 at the module's smallest B (the cluster's eight-workgroup exchange)
+SAT_LAYER_CASES = [FORCED_CASES[0][:5], LAYER_CASES[7][:5]]
+LEVELS = ("hard", "frozen")
+
+
+def _saturated_inputs(case, level):
+    """_layer_inputs with b_ih moved so that b_ih + b_hh, which dominates the pre-activations, is large: on 40 % of the 8H gate units
+    +-[22, 30] (hard), or on all of them +-[120, 170] (frozen).  Frozen: in direction 0 the input and forget gates of the first half of
+    the units are open (+), so their cell state is a running sum of tanh(g) = +-1."""
+    H, B, Nq, In, kind = case
+    x, lens = _layer_inputs(H, B, Nq, In, kind, seed=H * 1000 + B * 10 + Nq)
+    g = torch.Generator().manual_seed(H + len(level))
+    sign = torch.randint(0, 2, (2, 4 * H), generator=g).double() * 2 - 1
+    if level == "frozen":
+        sign[0, :H // 2] = sign[0, H:H + H // 2] = 1.0
+        target = sign * (120 + 50 * torch.rand(2, 4 * H, generator=g, dtype=torch.float64))
+        x["b_ih"] = (target - x["b_hh"]).float().double()
+    else:
+        big = torch.rand(2, 4 * H, generator=g) < 0.4
+        target = sign * (22 + 8 * torch.rand(2, 4 * H, generator=g, dtype=torch.float64))
+        x["b_ih"] = torch.where(big, target - x["b_hh"], x["b_ih"]).float().double()
+    return x, lens
+
+
+def _pre_activations(x, lens):
+    """the live pre-activations [n, 4H] of both directions, detached, from lstm_layer_ref"""
+    B, Nq, _ = x["x"].shape
+    with torch.no_grad():
+        steps = lstm_layer_ref(x["x"], lens, x["w_ih"], x["w_hh"], x["b_ih"], x["b_hh"])[3]
+    return torch.cat([z[act] for _, _, act, z in steps])
+
+
+@pytest.mark.parametrize("level", LEVELS)
+@pytest.mark.parametrize("case", SAT_LAYER_CASES, ids=[_layer_id(c) for c in SAT_LAYER_CASES])
+def test_saturated_layer_inputs_hold_what_they_claim(case, level):
+    """On the float64 restatement.  hard: at least a quarter of the live pre-activations beyond +-17 and a quarter inside +-4.  frozen:
+    every one in +-[90, 200]; with the input and forget gates frozen open the cell state of a unit is +-(t + 1) after step t.  The
+    lengths are ragged and include 1; the H = 32 case runs either recurrence, the H = 256 case eight workgroups per cluster."""
+    H, B, Nq, In, kind = case
+    x, lens = _saturated_inputs(case, level)
+    assert 1 in lens.tolist() and Nq in lens.tolist() and cluster_ok(H) and (H == 32 or H // CL_U == 8)
+    z = _pre_activations(x, lens)
+    if level == "hard":
+        assert (z.abs() > 17).double().mean().item() >= 0.25 and (z.abs() < 4).double().mean().item() >= 0.25
+        return
+    assert 90 <= z.abs().min().item() and z.abs().max().item() <= 200
+    Cs = lstm_layer_ref(x["x"], lens, x["w_ih"], x["w_hh"], x["b_ih"], x["b_hh"])[2]
+    full = [b for b in range(B) if int(lens[b]) >= Nq][0]
+    c = Cs[full, :, 0, :H // 2]                                                  # direction 0 visits position t at step t
+    want = torch.arange(1, Nq + 1, dtype=torch.float64).unsqueeze(1)
+    assert (c.abs() - want).abs().max().item() <= 1e-9 and bool((c.abs()[1:] > c.abs()[:-1]).all())
+
+
+def _run_saturated_layer(dev, case, level, label):
+    """Both halves through the C ABI on _saturated_inputs: everything finite, exact zeros at padded positions, the error word 0, and the
+    project's gate against lstm_layer_ref in float64 with e_torch32 from lstm_layer_ref in fp32."""
+    import models
+    from tests.support.compare import gate
+    H, B, Nq, In, kind = case
+    x, lens = _saturated_inputs(case, level)
+    ref, ref32 = _reference(x, lens), _reference({k: v.float() for k, v in x.items()}, lens)
+    live = ref["live"]
+    got = _abi_layer(dev, x, lens)
+    for k in ("Hout", "G", "dG", "dX", "dWih", "dbias", "dWhh"):
+        assert torch.isfinite(got[k]).all(), f"{label}: {k} is not finite"
+    assert torch.isfinite(got["Cs"].cpu()[live]).all()
+    for k in ("Hout", "dG"):
+        assert torch.all(got[k].cpu()[~live] == 0), f"{label}: {k} not zero at padded positions"
+    for k in ("Hout", "dG", "dX", "dWih", "dbias", "dWhh"):
+        gate(f"bilstm {label} {k}", got[k], ref[k], ref32[k])
+    for k in ("G", "Cs"):
+        gate(f"bilstm {label} {k}", got[k].cpu()[live], ref[k][live], ref32[k][live])
+    if level == "frozen":
+        full = [b for b in range(B) if int(lens[b]) >= Nq][0]
+        c = got["Cs"].cpu()[full, :, 0, :H // 2].abs()
+        assert bool((c[1:] > c[:-1]).all()) and torch.equal(c[:, 0], torch.arange(1.0, Nq + 1))
+    assert models.vml_amd._lib.load().smin_lstm_cluster_error() == 0, f"{label}: a bounded poll of the cluster recurrence expired"
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("level", LEVELS)
+@pytest.mark.parametrize("case", SAT_LAYER_CASES, ids=[_layer_id(c) for c in SAT_LAYER_CASES])
+def test_saturated_layer_against_fp64(dev, case, level):
+    """smin_bilstm_layer_fwd, _bwd and the weights half through the cluster recurrence with the gates partly (hard) or wholly (frozen)
+    saturated: expf overflows in the sigmoids and the tanh on one side and underflows on the other.  Measured on an MI355X:
+    INTEGRATION.md, "Saturated inputs"."""
+    _check_regime(case + (set(),), False, {f"cluster-P{case[0] // 32}"})
+    _run_saturated_layer(dev, case, level, f"cluster-{_layer_id(case)} {level}")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("level", LEVELS)
+def test_saturated_layer_streamed_against_fp64(dev, level, monkeypatch):
+    """The H = 32 case through the streamed recurrence (SMIN_LSTM_STREAMED set, read at every call)."""
+    case = SAT_LAYER_CASES[0]
+    monkeypatch.setenv("SMIN_LSTM_STREAMED", "1")
+    _check_regime(case + (set(),), True, {"streamed-forced-H32"})
+    _run_saturated_layer(dev, case, level, f"forced-{_layer_id(case, True)} {level}")
 
 
 HALVES_CASES = [(64, 5, 7, 128, "mixed"), (64, 300, 2, 128, "mixed"), (256, 65, 4, 300, "mixed"), (256, 8, 5, 512, "mixed")]

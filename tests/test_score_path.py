@@ -210,6 +210,103 @@ def test_tail_kernel_against_fp64(dev, case):
     assert torch.equal(again, pm_new)                                       # issued as its two stages: the same bits
 
 
+TAIL_SAT_CASES = [TAIL_CASES[k] for k in (0, 1, 4, 7, 8, 9)]      # the smallest case of each (NV, hbar given / re-formed) instance
+TAIL_PRE = (20.0, 95.0, 110.0)
+LEVELS = ("hard", "frozen")
+
+
+def written(t, idx, has_hbar, dtype):
+    """written_fp64 in ``dtype``"""
+    c = {k: v.to(dtype) for k, v in t.items()}
+    b_idx, i_idx, j_idx = idx
+    hbar = c["hbar"] if has_hbar else torch.sigmoid(c["fm"] * c["fs"][b_idx]) * c["fm"]
+    cum = c["ccmean"] @ c["Wc"].t() + c["bc"] + c["cumean"] + hbar
+    x1 = c["bu"][b_idx, i_idx] * c["bu"][b_idx, j_idx]
+    mu = x1 @ c["Wfb"].t() + cum @ c["Wfc"].t() + (c["bfb"] + c["bfc"]) + c["fm"]
+    return mu @ c["wm"] + c["bm"]
+
+
+def tail_saturated(case, level):
+    """tail_inputs with bu moved along the three row heads' weights so that their logits take given values, and then cumean -- which
+    enters the map head's logit linearly, through Wfc^T wm -- moved along that direction so that each cell's logit does: +-{20, 95, 110}
+    (frozen), or that on half of the cells and rows and N(0, 2) on the rest (hard).  Returns (t, mask, idx, the map head's targets [N],
+    the row heads' targets [3, B, L])."""
+    B, L, D, dl, has_hbar, lens = case
+    t, mask, idx = tail_inputs(case, seed=B * 1000 + L * 100 + D + dl + int(has_hbar))
+    g = torch.Generator().manual_seed(D + dl + len(level))
+    N = idx[0].numel()
+
+    def targets(*s):
+        v = torch.tensor(TAIL_PRE, dtype=torch.float64)[torch.randint(0, 3, s, generator=g)] * (torch.randint(0, 2, s, generator=g).double() * 2 - 1)
+        return v if level == "frozen" else torch.where(torch.rand(*s, generator=g) < 0.5, v, 2 * torch.randn(*s, generator=g, dtype=torch.float64))
+    target, rows = targets(N), targets(3, B, L)
+    wb, bb = t["wb"].double(), t["bb"].double().reshape(3, 1, 1)
+    for _ in range(2):
+        miss = rows - bb - torch.einsum("bld,kd->kbl", t["bu"].double(), wb)
+        t["bu"] = (t["bu"].double() + torch.einsum("kbl,kd->bld", torch.linalg.solve(wb @ wb.t(), miss.reshape(3, -1)).reshape(3, B, L), wb)).float()
+    v = t["Wfc"].double().t() @ t["wm"].double()
+    for _ in range(2):                                      # (the second pass takes up the rounding of the first to fp32)
+        z = written(t, idx, has_hbar, torch.float64)
+        t["cumean"] = (t["cumean"].double() + ((target - z) / (v @ v)).unsqueeze(1) * v).float()
+    return t, mask, idx, target, rows
+
+
+@pytest.mark.parametrize("level", LEVELS)
+@pytest.mark.parametrize("case", TAIL_SAT_CASES, ids=lambda c: "B%d-L%d-D%d-dl%d-%s" % (c[0], c[1], c[2], c[3], "hbar" if c[4] else "gate"))
+def test_tail_saturated_inputs_hold_what_they_claim(case, level):
+    """The cases cover every (NV, hbar given / re-formed) instance; on the as-written formulas in fp64 the fp32 inputs' logits are the
+    targets to 1e-3: a quarter beyond +-17 and a quarter inside +-4 (hard), all at +-{20, 95, 110} with every value under both signs
+    over the cases (frozen); the scores at +20 and above round to 1.0f, those at -110 to 0.0f."""
+    assert {(tail_form(c[2], c[3]), c[4]) for c in TAIL_SAT_CASES} == {(nv, hb) for nv in (0, 1, 2) for hb in (True, False)}
+    t, mask, idx, target, rows = tail_saturated(case, level)
+    z = written(t, idx, case[4], torch.float64)
+    zb = torch.einsum("bld,kd->kbl", t["bu"].double(), t["wb"].double()) + t["bb"].double().reshape(3, 1, 1)
+    assert (z - target).abs().max().item() <= 1e-3 and (zb - rows).abs().max().item() <= 1e-3
+    if level == "hard":
+        assert (zb.abs() > 17).double().mean().item() >= 0.25 and (zb.abs() < 4).double().mean().item() >= 0.25
+    else:
+        assert zb.abs().min().item() > 19.99 and bool((zb > 0).any() and (zb < 0).any())
+    if level == "hard":
+        assert (z.abs() > 17).double().mean().item() >= 0.25 and (z.abs() < 4).double().mean().item() >= 0.25
+    else:
+        assert z.abs().min().item() > 19.99 and bool((z > 0).any() and (z < 0).any()) and len(set(target.abs().tolist())) == 3
+    p = torch.sigmoid(z)
+    assert bool((p[z > 19.99].float() == 1.0).all()) and bool((p[z < -109.99].float() == 0.0).all())
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("level", LEVELS)
+@pytest.mark.parametrize("case", TAIL_SAT_CASES, ids=lambda c: "B%d-L%d-D%d-dl%d-%s" % (c[0], c[1], c[2], c[3], "hbar" if c[4] else "gate"))
+def test_tail_kernel_saturated_against_fp64(dev, case, level):
+    """smin_score_tail_fwd on tail_saturated: pm and psea exactly 1.0 from a logit of +20 on and exactly 0.0 from -110 on, +0.0 outside
+    the list and beyond the length, finite everywhere, and the project's gate against the as-written formulas in fp64, e_torch32 from
+    the same formulas in fp32.
+    Measured on an MI355X: INTEGRATION.md, "Saturated inputs"."""
+    from tests.support.compare import gate
+    F = V().functional
+    B, L, D, dl, has_hbar, lens = case
+    t, mask, idx, target, rows = tail_saturated(case, level)
+    d = {k: v.to(dev).contiguous() for k, v in t.items()}
+    layout = V().CellLayout.from_mask(mask.to(dev))
+    Wcat = torch.cat([d["Wfb"], d["Wfc"]], dim=1).contiguous()
+    pm, psea = F.score_tail(d["ccmean"], d["cumean"], d["hbar"] if has_hbar else None, d["fm"], d["fs"], d["bu"], layout.cells, d["Wc"], d["bc"],
+                            Wcat, d["bfb"] + d["bfc"], d["wm"], d["bm"], d["wb"], d["bb"], d["lmask"])
+    torch.cuda.synchronize()
+    pm = pm.cpu()
+    assert bool(torch.isfinite(pm).all()) and bool(torch.isfinite(psea).all())
+    assert bool((pm[~mask].view(torch.int32) == 0).all())
+    got = pm[mask]
+    assert bool((got[target > 19.99] == 1.0).all()) and bool((got[target < -109.99] == 0.0).all())
+    tag = "score_tail B%d-L%d-D%d-dl%d-%s %s" % (B, L, D, dl, "hbar" if has_hbar else "gate", level)
+    gate(tag + " pm", got, torch.sigmoid(written(t, idx, has_hbar, torch.float64)), torch.sigmoid(written(t, idx, has_hbar, torch.float32)))
+    heads = lambda dt: torch.sigmoid(torch.einsum("bld,kd->kbl", t["bu"].to(dt), t["wb"].to(dt)) + t["bb"].to(dt).reshape(3, 1, 1)) * t["lmask"].to(dt)
+    psea = psea.cpu()
+    on = (t["lmask"] != 0).expand(3, B, L)
+    assert bool((psea[~on].view(torch.int32) == 0).all())
+    assert bool((psea[on & (rows > 19.99)] == 1.0).all()) and bool((psea[on & (rows < -109.99)] == 0.0).all())
+    gate(tag + " psea", psea, heads(torch.float64), heads(torch.float32))
+
+
 @pytest.mark.gpu
 def test_tail_refusals(dev):
     """D % 4, dl % 4, null pointers (beyond the two whole stages that may be skipped), a short or misaligned workspace: a negative

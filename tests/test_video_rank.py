@@ -23,7 +23,8 @@ from tests.support import corpora as WS
 from tests.support.device import dev  # noqa: F401  (the module's device fixture)
 from tests.support.device import vml as V
 from tests.support.compare import bits, gate, same
-from tests.support.corpora import corpus_inputs, synthetic, tiny_model, window_host_banks, DURATION_TENSOR, GT_VIDEO, SEARCH_KEYS
+from tests.support.corpora import (
+    corpus_inputs, synthetic, tied_maps, tied_pool_by_hand, tiny_model, window_host_banks, DURATION_TENSOR, GT_VIDEO, SEARCH_KEYS)
 from tests.support.references import abi_call
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -145,6 +146,69 @@ def test_pool_restatements_by_hand():
     assert abs(gs[1].item() - score[0].item()) <= 1e-14
     none = A.group_pool_torch(pool, torch.zeros_like(cells), gp, tau)
     assert none[0].eq(0).all() and none[1].eq(0).all()
+
+
+SAT_TAUS = [1e-3, 1e-4]
+SAT_POOL = [(7, 5), (5, 33)]                           # the smallest case with more than one pair, and the strided walk
+SAT_ALPHAS = [50.0, 500.0, -500.0]
+GROUP_PTR = [0, 0, 1, 3, 7]                            # test_group_pool's groups
+
+
+@pytest.mark.parametrize("tau", SAT_TAUS)
+@pytest.mark.parametrize("P,L", SAT_POOL + [(7, 8)])
+def test_tied_maps_hold_what_they_claim(P, L, tau):
+    """On the fp64 restatement: every cell below a pair's maximum lies at least 125 temperatures under it (its exponential is below
+    1e-54, and exactly 0 in fp32), some pair has several cells at the maximum and some pair has one, and the pooled score is
+    m + tau * log(k / n) with k the number of cells at the maximum; a group's score is the same over all its windows' cells."""
+    A = V()
+    x = tied_maps(P, L, seed=21 if L == 8 else 100 * P + L, dtype=torch.float64)
+    score, top, ties, cells = tied_pool_by_hand(x[0], x[3], tau)
+    for p in range(P):
+        below = [v for v in x[0][p][x[3][p]].tolist() if v != top[p]]
+        assert not below or (top[p] - max(below)) / tau >= 125.0
+    assert max(ties) > 1 and len(set(top)) > 2 and any(0 < k < n for k, n in zip(ties, cells)) and 0 in cells
+    got = A.pair_pool_torch(*x, tau=tau)
+    assert got[2].tolist() == [float(n) for n in cells] and got[1][:, 0].tolist() == top
+    assert (got[1][:, 1] - torch.tensor(ties, dtype=torch.float64)).abs().max().item() <= 1e-50
+    assert (got[0] - torch.tensor(score, dtype=torch.float64)).abs().max().item() <= 1e-15
+    if L == 8:
+        gs, gc = A.group_pool_torch(got[1], got[2], torch.tensor(GROUP_PTR, dtype=torch.int32), tau)
+        for g, (a, b) in enumerate(zip(GROUP_PTR, GROUP_PTR[1:])):
+            n = sum(cells[a:b])
+            m = max([top[w] for w in range(a, b) if cells[w]], default=0.0)
+            k = sum(ties[w] for w in range(a, b) if cells[w] and top[w] == m)
+            assert gc[g].item() == n and abs(gs[g].item() - (m + tau * math.log(k / n) if n else 0.0)) <= 1e-15, g
+        assert len({top[w] for w in range(3, 7) if cells[w]}) > 1                  # the last group's windows do not share a maximum
+
+
+def weight_case(alpha):
+    """rank_case(3, 5)'s lists under pair scores in [0, 1] on a grid of 1/64: over the whole interval for alpha > 0, within 1/8 of 0.875 for
+    alpha < 0 (a weight exp(|alpha| * gap) leaves fp32 at a gap of 88.7 / |alpha|: 0.177 at -500)"""
+    _, cells, video, ptr, gt = rank_case(3, 5, seed=7 * 3 + 5)
+    g = torch.Generator().manual_seed(int(abs(alpha)))
+    steps = torch.randint(0, 65 if alpha > 0 else 9, (cells.shape[0],), generator=g)
+    if alpha > 0:
+        steps[ptr[:-1].long()] = torch.tensor([0, 1, 64])                            # a best pair, its neighbour on the grid, the far end
+    return (64 - steps if alpha > 0 else 56 - steps).float() / 64, cells, video, ptr, gt
+
+
+@pytest.mark.parametrize("alpha", SAT_ALPHAS)
+def test_weight_cases_hold_what_they_claim(alpha):
+    A = V()
+    score, cells, video, ptr, gt = weight_case(alpha)
+    assert 0.0 <= score.min().item() and score.max().item() <= 1.0
+    r = A.rank_videos_torch(score.double(), cells.double(), video, ptr, n=5, alpha=alpha)
+    w, listed = r["weight"], r["pair_rank"] >= 0
+    assert listed.sum().item() >= 9 and not listed.all() and torch.isfinite(w).all()
+    assert all(w[listed & (r["pair_rank"] == 0)].tolist()) and (w[listed & (r["pair_rank"] == 0)] == 1.0).all()
+    if alpha > 0:
+        assert w.max().item() == 1.0 and (w[listed] < 1.0).any()
+        if alpha == 500.0:
+            assert (w[listed] < 1e-45).any() and ((w[listed] > 1e-30) & (w[listed] < 1.0)).any()      # gone in fp32, and alive
+        else:
+            assert w[listed].min().item() > 1e-30
+    else:
+        assert w[listed].min().item() == 1.0 and 1e10 < w.max().item() < 3e38                         # large, and inside fp32
 
 
 def test_refusals():
@@ -316,6 +380,66 @@ def test_group_pool(dev, tau):
     got = A.group_pool(pool, cells, wild, tau)
     ref = A.group_pool_torch(r_pool[1], r_pool[2], wild, tau)
     assert torch.isfinite(got[0]).all() and torch.equal(got[1].double(), ref[1].double())
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("tau", SAT_TAUS)
+@pytest.mark.parametrize("P,L", SAT_POOL)
+def test_pair_pool_at_small_tau(dev, P, L, tau):
+    """tied_maps: only the cells at a pair's maximum survive the exponential.  The score is m + tau * log(k / n); pool holds m and k
+    exactly (every other exponential is 0 in fp32); the pair without a cell gives +0.0 throughout; the project's gate against the fp64
+    restatement.  Measured on an MI355X: INTEGRATION.md, "Saturated inputs"."""
+    A = V()
+    x = tied_maps(P, L, seed=100 * P + L)
+    by_hand, top, ties, n = tied_pool_by_hand(x[0].double(), x[3], tau)
+    xd = [t.to(dev) for t in x]
+    score, pool, cells = A.pair_pool(*xd, tau=tau)
+    want, ref32 = A.pair_pool_torch(*[t.double() for t in xd[:3]], xd[3], tau=tau), A.pair_pool_torch(*xd, tau=tau)
+    assert all(torch.isfinite(t).all() for t in (score, pool, cells))
+    assert pool[:, 0].cpu().tolist() == top and pool[:, 1].cpu().tolist() == [float(k) for k in ties] and cells.cpu().tolist() == [float(c) for c in n]
+    tag = f"pair_pool (P, L) = ({P}, {L}) tau {tau}"
+    gate(tag + " score", score, want[0], ref32[0])
+    gate(tag + " score by hand", score, torch.tensor(by_hand, dtype=torch.float64), ref32[0])
+    assert bits(score[P // 2]).item() == 0 and bits(pool[P // 2]).eq(0).all() and cells[P // 2].item() == 0.0
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("tau", SAT_TAUS)
+def test_group_pool_at_small_tau(dev, tau):
+    """test_group_pool's groups over tied_maps: windows whose maximum lies below their group's drop out of its sum.  Measured on an
+    MI355X: INTEGRATION.md, "Saturated inputs"."""
+    A = V()
+    xd = [t.to(dev) for t in tied_maps(7, 8, seed=21)]
+    gp = torch.tensor(GROUP_PTR, dtype=torch.int32, device=dev)
+    _, pool, cells = A.pair_pool(*xd, tau=tau)
+    gs, gc = A.group_pool(pool, cells, gp, tau)
+    w_pool = A.pair_pool_torch(*[t.double() for t in xd[:3]], xd[3], tau=tau)
+    want = A.group_pool_torch(w_pool[1], w_pool[2], gp, tau)
+    r_pool = A.pair_pool_torch(*xd, tau=tau)
+    ref32 = A.group_pool_torch(r_pool[1], r_pool[2], gp, tau)
+    assert torch.isfinite(gs).all() and torch.equal(gc.double(), want[1])
+    gate(f"group_pool tau {tau} score", gs, want[0], ref32[0])
+    assert bits(gs[0]).item() == 0 and gc[0].item() == 0.0
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("alpha", SAT_ALPHAS)
+def test_video_rank_weights_at_large_alpha(dev, alpha):
+    """weight_case: exp(alpha * (s - s_max)) at alpha 50, 500 (most weights underflow; none may exceed 1) and -500 (weights up to
+    exp(62.5)).  Finite, exactly 1 for each query's best pair, +0.0 for the pairs that are no candidates, never above 1 for alpha > 0,
+    and the project's gate against the fp64 restatement.  Measured on an MI355X: INTEGRATION.md, "Saturated inputs"."""
+    A = V()
+    case = weight_case(alpha)
+    on = [t.to(dev) for t in case]
+    got = A.rank_videos(*on[:4], n=5, alpha=alpha, gt_video=on[4])
+    want = A.rank_videos_torch(case[0].double(), case[1].double(), case[2], case[3], n=5, alpha=alpha, gt_video=case[4])
+    r32 = A.rank_videos_torch(*on[:4], n=5, alpha=alpha)["weight"]
+    for key in ("video", "count", "pair_rank", "gt_rank"):
+        assert torch.equal(got[key].cpu(), want[key]), key
+    w, listed = got["weight"].cpu(), want["pair_rank"] >= 0
+    assert torch.isfinite(w).all() and bits(w[~listed]).eq(0).all() and (w[want["pair_rank"] == 0] == 1.0).all()
+    assert (w <= 1.0).all() if alpha > 0 else (w[listed] >= 1.0).all()
+    gate(f"video_rank alpha {alpha} weight", got["weight"], want["weight"], r32)
 
 
 def rank_case(Q, Vn, seed):

@@ -1,7 +1,8 @@
 // Video-level contrastive loss over a pair plan: which of a query's videos is its own.
 //   cell score    f[p,i,j] = (pm[p,i,j] * sqrt(max(ps[p,i], 1e-12))) * sqrt(max(pe[p,j], 1e-12))        (top_moments' order)
 //   pair score    s_p = m_p + tau * log( sum_valid exp((f - m_p) / tau) / n_p ),  m_p = max_valid f;  n_p == 0: s_p = 0
-//   query loss    l_q = log sum_{S_q} exp(s / gamma) - log sum_{S_q+} exp(s / gamma), both shifted by the segment's maximum
+//   query loss    l_q = log sum_{S_q} exp(s / gamma) - log sum_{S_q+} exp(s / gamma), each sum shifted by its own maximum:
+//                 l_q = (mx - mpos) / gamma + log sum_{S_q} exp((s - mx) / gamma) - log sum_{S_q+} exp((s - mpos) / gamma)
 //   loss = mean of l_q over the queries with a positive pair;  stats = [counted, hits]
 // Forward: one workgroup per pair (two sweeps over its map: maximum, then the sum), one wave64 per query over its segment in
 // list order (l_q, the hit flag, each pair's coefficient dloss/ds_p without 1/Nc), one thread over the queries in ascending q.
@@ -57,25 +58,28 @@ void pair_rank_query_kernel(const float* __restrict__ score, const int32_t* __re
     mx = wave_max(mx); mpos = wave_max(mpos); mneg = wave_max(mneg);
     npos = wave_sum(npos);
     const bool counted = npos > 0.f;
+    // each sum is shifted by the maximum of its own terms, so both are >= 1: a positive far below the best negative still has a
+    // finite logarithm and a finite coefficient at any gamma
     float zall = 0.f, zpos = 0.f;
     if (counted)
         for (int e = beg + lane; e < end; e += 64) {
             const int p = clampi(q_pairs[e], 0, P - 1);
-            const float x = expf((score[p] - mx) / gamma);
-            zall += x;
-            if (positive[p] != 0) zpos += x;
+            const float s = score[p];
+            zall += expf((s - mx) / gamma);
+            if (positive[p] != 0) zpos += expf((s - mpos) / gamma);
         }
     zall = wave_sum(zall); zpos = wave_sum(zpos);
     for (int e = beg + lane; e < end; e += 64) {
         const int p = clampi(q_pairs[e], 0, P - 1);
         float c = 0.f;
         if (counted) {
-            const float x = expf((score[p] - mx) / gamma);
-            c = (x / zall - (positive[p] != 0 ? x / zpos : 0.f)) / gamma;
+            const float s = score[p];
+            c = (expf((s - mx) / gamma) / zall - (positive[p] != 0 ? expf((s - mpos) / gamma) / zpos : 0.f)) / gamma;
         }
         coef[p] = c;
     }
-    if (lane == 0) part[q] = make_float4(counted ? logf(zall) - logf(zpos) : 0.f, counted ? 1.f : 0.f, counted && mpos >= mneg ? 1.f : 0.f, 0.f);
+    if (lane == 0)
+        part[q] = make_float4(counted ? (mx - mpos) / gamma + (logf(zall) - logf(zpos)) : 0.f, counted ? 1.f : 0.f, counted && mpos >= mneg ? 1.f : 0.f, 0.f);
 }
 
 // ---- the listwise soft-target term: KL(teacher || student) over a query's segment, the teacher one score per pair.

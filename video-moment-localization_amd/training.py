@@ -77,8 +77,10 @@ def pair_rank_loss_torch(pm, ps, pe, moment_mask, plan, tau=0.1, gamma=0.1, retu
         if not pos:
             continue
         neg = [p for p in seg if positive[p] == 0]
-        x = (s[seg] - sd[seg].max()) / gamma
-        total = total + (torch.log(torch.exp(x).sum()) - torch.log(torch.exp(x[[k for k, p in enumerate(seg) if positive[p] != 0]]).sum()))
+        # each logsumexp is shifted by the maximum of its own terms before the division by gamma: finite however far the positives lie
+        # below the best negative, and no rounding of s / gamma itself
+        top, top_pos = sd[seg].max(), sd[pos].max()
+        total = total + (torch.logsumexp((s[seg] - top) / gamma, 0) - torch.logsumexp((s[pos] - top_pos) / gamma, 0) + (top - top_pos) / gamma)
         counted += 1
         hits += int(not neg or bool(sd[pos].max() >= sd[neg].max()))
     loss = total / counted if counted else (s.sum() * 0.0)
