@@ -424,6 +424,56 @@ int smin_epoch_meter_update(void* stream, const float* pm, const float* ps, cons
                             int B, int L, int rule, int k, float nms_thresh, const int* n_list, int nn, const float* m_list, int nm,
                             const float* loss, double* acc, void* ws, size_t ws_bytes);
 
+/* ---- Soft-NMS moment retrieval (csrc/soft_nms.hip): top-k where a pick decays the candidates it overlaps instead of removing them,
+ * and the rest is ranked again.  Candidates, score, IoU, order (ties -> lower flat index, -0 counts as +0), empty slots and the limits
+ * on B, L and k are smin_top_moments' above.  Per sample, with cur(c) = score(c) initially:
+ *   pick:   the remaining candidate with the highest cur (order word of cur, then the lower flat index);
+ *   stop:   after k picks, when no candidate is left, or when the best cur < min_score (fp32; -inf never stops early);
+ *   record: idx, score = cur at pick time, raw_score = the picked cell's undecayed score (a zero is written as +0);
+ *   decay:  for every remaining candidate iou with the pick (one correctly rounded fp32 division), then cur = cur * w, one fp32
+ *           multiplication, no fma contraction:
+ *             method SMIN_NMS_LINEAR:    w = iou > nms_thresh ? 1.0f - iou : 1.0f      (sigma is not read)
+ *             method SMIN_NMS_GAUSSIAN:  w = expf(-(iou * iou) / sigma), every candidate; sigma > 0, +inf allowed (w = 1);
+ *                                        nms_thresh is not read
+ * The decays are applied in pick order, cur = ((s0 * w1) * w2) ...; the result does not depend on how the work is split.  The linear
+ * rule is made of correctly rounded fp32 operations and is reproducible bit for bit; the gaussian rule is as exact as the device
+ * library's expf.  With linear and nms_thresh >= 1, or gaussian and sigma = +inf, the lists are smin_top_moments' at nms_thresh >= 1.
+ * Signed scores follow the same formulas.  NaN and +-inf at VALID cells are out of scope for the soft rules; NaN and inf at masked
+ * cells are never read into the order.
+ * Worked example (L = 4, ps = pe = 1, valid cells (0,3) = 1.0, (0,2) = 0.9f, (3,3) = 0.5, every other valid cell 0; linear,
+ * nms_thresh = 0.5, k = 3): pick (0,3) at 1.0; (0,2) has IoU 3/4 with it and becomes 0.9f * 0.25f; (3,3) has IoU 1/4 and stays 0.5;
+ * the picks are (0,3), (3,3), (0,2) with scores 1.0, 0.5, 0.9f * 0.25f.  Plain top-k gives (0,3), (0,2), (3,3); hard NMS at 0.5 drops
+ * (0,2) and gives (0,3), (3,3) and a cell of score 0.
+ * Outputs: idx [B][k][2] (-1), score [B][k] (0), raw_score [B][k] (0), count [B].
+ * Launches: maps with L*L <= 12288 cells take one launch (one workgroup per sample, cur in LDS); larger maps take k + 1 launches over
+ * a band grid with cur in ws.  No workgroup waits on another, no float atomics, no host read: the same bits on every run, capturable
+ * in a HIP graph.  ws: device scratch of at least the _ws_bytes size; the query returns 0 when (B, L, k) are rejected, and 256 (unused)
+ * on the one-launch path.  A bad method, sigma <= 0 or NaN (gaussian), a NULL pointer or a short ws: a negative code, nothing launched. */
+#define SMIN_NMS_LINEAR 1
+#define SMIN_NMS_GAUSSIAN 2
+size_t smin_top_moments_soft_ws_bytes(int B, int L, int k);
+int smin_top_moments_soft(void* stream, const float* pm, const float* ps, const float* pe, const uint8_t* mm, int B, int L, int k,
+                          int method, float nms_thresh, float sigma, float min_score, long long* idx, float* score, float* raw_score,
+                          int* count, void* ws, size_t ws_bytes);
+/* the span form: smin_merge_window_moments' inputs, candidates, order, spans and span IoU, with the soft rule above in place of the
+ * threshold.  cur starts at the candidate's input score; out_score = cur at pick time, raw_score = the input score (both as they
+ * are, no sign change).  The caller passes UNDECAYED per-window scores (smin_top_moments_soft's raw_score): the merge decays once, in
+ * raw-row time.  One workgroup per pair, every round recomputes cur from the kept spans in pick order: no scratch. */
+int smin_merge_window_moments_soft(void* stream, const int64_t* idx, const float* score, const int32_t* count, const int64_t* start,
+                                   const int32_t* len, const int64_t* pair_ptr, int G, int B, int T, int L, int k_window, int k,
+                                   int method, float nms_thresh, float sigma, float min_score, float* span, float* out_score,
+                                   float* raw_score, int64_t* window, int64_t* cell, int32_t* out_count);
+/* smin_compute_ious_nms and rule 1 of the epoch meter with the soft selection (min_score = -inf) in place of the greedy hard NMS: the
+ * same hit flags, sums and closing wave behind it.  Same limits and rejections as above. */
+size_t smin_compute_ious_soft_ws_bytes(int B, int L, int k, int nn, int nm);
+int smin_compute_ious_soft(void* stream, const float* pm, const float* ps, const float* pe, const uint8_t* mm, const float* sm,
+                           int B, int L, int k, int method, float nms_thresh, float sigma, const int* n_list, int nn,
+                           const float* m_list, int nm, float* counts, void* ws, size_t ws_bytes);
+size_t smin_epoch_meter_soft_ws_bytes(int B, int L, int k, int nn, int nm);
+int smin_epoch_meter_update_soft(void* stream, const float* pm, const float* ps, const float* pe, const uint8_t* mm, const float* sm,
+                                 int B, int L, int k, int method, float nms_thresh, float sigma, const int* n_list, int nn,
+                                 const float* m_list, int nm, const float* loss, double* acc, void* ws, size_t ws_bytes);
+
 /* ---- span metric (csrc/metrics.hip): IoU, R@n, IoU=m and top-1 IoU of continuous spans -- smin_merge_window_moments' output --
  * against one ground-truth span per pair, and their accumulation into the epoch meter's acc.
  * Inputs: span [B][k][2] fp32 (st, en) and count [B] (slots s >= count[b] are empty; their span, NaN, is never used), gt [B][2]

@@ -28,7 +28,7 @@ from .retrieval import PairPlan, SurvivorBank, WindowBank  # noqa: F401
 from .meter import EpochMeter, EpochMeterTorch, CorpusMeter, CorpusMeterTorch, VideoRankMeter, CutFidelityMeter  # noqa: F401
 from .optim import FusedAdam, FusedAdamTorch, RowSparseAdam, RowSparseAdamTorch  # noqa: F401
 from .labels import build_targets  # noqa: F401
-from .moments import top_moments, top_moments_torch, merge_window_moments, merge_window_moments_torch  # noqa: F401
+from .moments import top_moments, top_moments_torch, top_moments_soft_torch, merge_window_moments, merge_window_moments_torch  # noqa: F401
 from .moments import corpus_span_topk, corpus_span_topk_torch, merge_search_windows, merge_search_windows_torch  # noqa: F401
 from .moments import corpus_topk, corpus_topk_torch, merge_search, merge_search_torch, mine_pairs, mine_pairs_torch  # noqa: F401
 from .moments import pair_pool, pair_pool_torch, group_pool, group_pool_torch, rank_videos, rank_videos_torch  # noqa: F401

@@ -38,6 +38,17 @@ int launch_score_heads(hipStream_t st, const float* fb, int B, int L, int D, con
 size_t nms_hits_stage_bytes(int B, int L, int k, int nn, int nm);
 int nms_hits_stage(hipStream_t st, const float* pm, const float* ps, const float* pe, const uint8_t* mm, const float* sm, int B, int L, int k,
                    float nms_thresh, const int* n_list, int nn, const float* m_list, int nm, void* ws, float** hits_out, float* top1);
+// the same stage under a selection rule: method 0 = greedy hard NMS (thr only), SMIN_NMS_LINEAR / SMIN_NMS_GAUSSIAN = Soft-NMS
+// (soft_nms.hip: decayed top-k; min_score = -inf never stops early)
+struct NmsRule { int method; float thr, sigma, min_score; };
+size_t rule_hits_stage_bytes(int method, int B, int L, int k, int nn, int nm);
+int rule_hits_stage(hipStream_t st, const float* pm, const float* ps, const float* pe, const uint8_t* mm, const float* sm, int B, int L, int k,
+                    const NmsRule& rule, const int* n_list, int nn, const float* m_list, int nm, void* ws, float** hits_out, float* top1);
+// soft_nms.hip: a soft rule's method and sigma are acceptable; the workspace its launches carve for checked (B, L); the launches
+bool soft_rule_ok(const NmsRule& rule);
+size_t soft_top_ws_total(int B, int L);
+int soft_top_launch(hipStream_t st, const float* pm, const float* ps, const float* pe, const uint8_t* mm, int B, int L, int k, const NmsRule& rule,
+                    long long* idx, float* score, float* raw_score, int* count, char* ws);
 // bank_codec.hip: what every entry point over a compact bank checks of (codes, scale, mode), codes aligned to `align` bytes; and the
 // bytes of four codes, the loaders' unit (mode 1 is SMIN_BANK_BF16)
 bool bank_code_ok(const void* codes, const float* scale, int mode, int align);

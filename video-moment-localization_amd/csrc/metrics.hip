@@ -260,6 +260,33 @@ extern "C" int smin_epoch_meter_update(void* stream, const float* pm, const floa
     return 0;
 }
 
+// the meter's rule 1 with a Soft-NMS selection (soft_nms.hip) in place of the greedy hard NMS: the same stage, the same closing wave
+extern "C" size_t smin_epoch_meter_soft_ws_bytes(int B, int L, int k, int nn, int nm)
+{
+    const size_t stage = rule_hits_stage_bytes(SMIN_NMS_LINEAR, B, L, k, nn, nm);
+    return stage ? stage + align256((size_t)B * sizeof(float)) : 0;
+}
+
+extern "C" int smin_epoch_meter_update_soft(void* stream, const float* pm, const float* ps, const float* pe, const uint8_t* mm, const float* sm,
+                                            int B, int L, int k, int method, float nms_thresh, float sigma, const int* n_list, int nn,
+                                            const float* m_list, int nm, const float* loss, double* acc, void* ws, size_t ws_bytes)
+{
+    hipStream_t st = (hipStream_t)stream;
+    const NmsRule rule{method, nms_thresh, sigma, -__builtin_inff()};
+    SMIN_REQUIRE(soft_rule_ok(rule));
+    SMIN_REQUIRE(pm != nullptr && ps != nullptr && pe != nullptr && mm != nullptr && sm != nullptr);
+    SMIN_REQUIRE(n_list != nullptr && m_list != nullptr && acc != nullptr && ws != nullptr);
+    const size_t need = smin_epoch_meter_soft_ws_bytes(B, L, k, nn, nm);
+    SMIN_REQUIRE(need != 0 && ws_bytes >= need);
+    float* hits = nullptr;
+    float* top1 = (float*)((char*)ws + rule_hits_stage_bytes(method, B, L, k, nn, nm));
+    const int rc = rule_hits_stage(st, pm, ps, pe, mm, sm, B, L, k, rule, n_list, nn, m_list, nm, ws, &hits, top1);
+    if (rc) return rc;
+    hipLaunchKernelGGL(meter_close_kernel, dim3(1), dim3(64), 0, st, hits, top1, B, nn * nm, loss, acc);
+    SMIN_LAUNCH_CHECK();
+    return 0;
+}
+
 extern "C" int smin_span_ious(void* stream, const float* span, const int32_t* count, const float* gt, int B, int k, float* iou)
 {
     SMIN_REQUIRE(B >= 0 && k >= 1 && k <= 64);

@@ -28,7 +28,10 @@
 //      bounded by the cell count; the result does not depend on CAND or MB.
 //   3. (metric) per-sample hit flags for every (n, m) pair from sm at the kept cells (empty slot = IoU 0), then one thread per pair
 //      sums the samples in order (no float atomics).
+// Soft-NMS (a pick decays what it overlaps, and the rest is ranked again) has kernels of its own in soft_nms.hip; moment_cells.h holds
+// what the two files share.  The metric stage below runs behind either selection.
 #include "common.h"
+#include "moment_cells.h"
 #include "rank_order.h"
 #include "smin_hip.h"
 
@@ -37,43 +40,22 @@
 namespace smin {
 namespace {
 
-constexpr int MT = 256;                 // threads per workgroup (4 waves)
+constexpr int MT = MOMENT_THREADS;      // threads per workgroup (4 waves)
 static_assert(MT == 256, "rank_order.h's block helpers are written for four waves");
 constexpr int CAND = 4096;              // candidate keys held in LDS by the NMS workgroup
 constexpr int MAX_BANDS = 32;
 constexpr int MIN_BAND = 1024;          // cells per band at least
-constexpr int MAX_K = 64;
+constexpr int MAX_K = MOMENT_MAX_K;
 constexpr int MAX_N = 64;               // metric: up to 64 values of n ...
 constexpr int MAX_M = 16;               // ... and 16 thresholds m
-
-struct Map {                            // one sample's inputs
-    const float* pm; const float* ps; const float* pe; const uint8_t* mm; int L; int n;
-};
-
-// (the high word is rank_order.h's score_ord: 0 is "no cell")
-__device__ __forceinline__ u64 make_key(uint32_t o, int c) { return ((u64)o << 32) | (uint32_t)(0x7fffffff - c); }
-__device__ __forceinline__ int key_cell(u64 k) { return 0x7fffffff - (int)(uint32_t)k; }
 
 // order word of cell c (row i, column j) of the map, 0 if it is masked or not strictly after `cursor`
 __device__ __forceinline__ uint32_t cell_ord(const Map& m, int c, int i, int j, u64 cursor)
 {
     if (!m.mm[c]) return 0;
-    const float v = (m.pm[c] * sqrtf(m.ps[i])) * sqrtf(m.pe[j]);
+    const float v = cell_score(m, c, i, j);
     const uint32_t o = score_ord(v);
     return make_key(o, c) < cursor ? o : 0u;
-}
-
-// Visit cells lo + t, lo + t + MT, ... < hi in index order, with their row / column, without a division per cell.
-template <typename F>
-__device__ __forceinline__ void for_cells(const Map& m, int lo, int hi, F&& f)
-{
-    const int t = threadIdx.x, dq = MT / m.L, dr = MT % m.L;
-    int c = lo + t, i = c / m.L, j = c - i * m.L;
-    for (; c < hi; c += MT) {
-        f(c, i, j);
-        i += dq; j += dr;
-        if (j >= m.L) { j -= m.L; ++i; }
-    }
 }
 
 // The bin of hist[0..nb) (nb a multiple of MT, larger bin = earlier in the order) holding the need-th element counted from the top
@@ -373,9 +355,8 @@ WsLayout ws_layout(int B, int L)
     return w;
 }
 
-constexpr int MAX_B = 65535;            // the band select puts the sample in the grid's second dimension
-
-bool args_ok(int B, int L, int k) { return B >= 1 && B <= MAX_B && L >= 1 && (long long)L * L < 0x7fffffffLL && k >= 1 && k <= MAX_K; }
+// 1 <= B <= 65535 (the band select puts the sample in the grid's second dimension), L*L < 2^31, 1 <= k <= 64: moment_cells.h
+bool args_ok(int B, int L, int k) { return moment_args_ok(B, L, k); }
 
 int launch_top(hipStream_t st, const float* pm, const float* ps, const float* pe, const uint8_t* mm, int B, int L, int k, float thr,
                long long* idx, float* score, int* count, char* ws)
@@ -395,23 +376,6 @@ int launch_top(hipStream_t st, const float* pm, const float* ps, const float* pe
 // ---- cross-window merge (smin_merge_window_moments): one workgroup per pair, k rounds of "the best candidate that no kept span
 // suppresses" (a block argmax of order keys strictly below the previous pick), the kept spans in LDS.  Suppression only grows
 // with the kept set, so round r's pick is the r-th moment the greedy walk keeps; no sort, no atomics, any candidate count.
-
-struct MergeIn {
-    const long long* idx; const float* score; const int* count; const long long* start; const int* len;
-    int G, T, L, kw;
-};
-
-// span in raw rows of cell (i, j) of window g (include/smin_hip.h, in this order, fp32; contraction off: a product and a sum are
-// rounded one by one, never fused into an fma)
-__device__ __forceinline__ void window_span(const MergeIn& in, int g, long long i, long long j, float& st, float& en)
-{
-#pragma clang fp contract(off)
-    const long long s = in.start[g];
-    const int n = in.len[g];
-    const float u = (float)max(n, in.T) / (float)in.L;
-    st = (float)s + (float)i * u;
-    en = fminf((float)s + (float)(j + 1) * u, (float)(s + n));
-}
 
 __device__ __forceinline__ bool span_suppressed(float st, float en, const float* kst, const float* ken, int nk, float thr)
 {
@@ -495,34 +459,62 @@ extern "C" int smin_top_moments(void* stream, const float* pm, const float* ps, 
     return launch_top((hipStream_t)stream, pm, ps, pe, mm, B, L, k, nms_thresh, idx, score, count, (char*)ws);
 }
 
-// ---- per-sample stage of the NMS metric, shared by smin_compute_ious_nms and the epoch meter (metrics.hip): the top-k launches and the
-// hit flags [B][nn * nm] (and, for the meter, the top-1 IoU per sample) in the caller's scratch
-size_t smin::nms_hits_stage_bytes(int B, int L, int k, int nn, int nm)
+// ---- per-sample stage of the NMS metric, shared by smin_compute_ious_nms, its soft form and the epoch meter (metrics.hip): the top-k
+// launches of the rule (hard: this file's; soft: soft_nms.hip's) and the hit flags [B][nn * nm] (and, for the meter, the top-1 IoU per
+// sample) in the caller's scratch.  Scratch: the selection's workspace | idx | score | count | raw_score (soft rules only) | hits.
+static size_t select_ws_bytes(int method, int B, int L) { return method == 0 ? ws_layout(B, L).total : soft_top_ws_total(B, L); }
+
+size_t smin::rule_hits_stage_bytes(int method, int B, int L, int k, int nn, int nm)
 {
-    if (!args_ok(B, L, k) || nn < 1 || nn > MAX_N || nm < 1 || nm > MAX_M) return 0;
+    if (!args_ok(B, L, k) || nn < 1 || nn > MAX_N || nm < 1 || nm > MAX_M || method < 0 || method > 2) return 0;
     const size_t npairs = (size_t)nn * nm;
     const size_t top = align256((size_t)B * k * 2 * sizeof(long long)) + align256((size_t)B * k * sizeof(float)) + align256((size_t)B * sizeof(int));
-    return ws_layout(B, L).total + top + align256((size_t)B * npairs * sizeof(float));
+    const size_t raw = method == 0 ? 0 : align256((size_t)B * k * sizeof(float));
+    return select_ws_bytes(method, B, L) + top + raw + align256((size_t)B * npairs * sizeof(float));
 }
 
-int smin::nms_hits_stage(hipStream_t st, const float* pm, const float* ps, const float* pe, const uint8_t* mm, const float* sm, int B, int L, int k,
-                         float nms_thresh, const int* n_list, int nn, const float* m_list, int nm, void* ws, float** hits_out, float* top1)
+int smin::rule_hits_stage(hipStream_t st, const float* pm, const float* ps, const float* pe, const uint8_t* mm, const float* sm, int B, int L, int k,
+                          const NmsRule& rule, const int* n_list, int nn, const float* m_list, int nm, void* ws, float** hits_out, float* top1)
 {
     SMIN_REQUIRE(args_ok(B, L, k) && nn >= 1 && nn <= MAX_N && nm >= 1 && nm <= MAX_M && n_list && m_list);
+    SMIN_REQUIRE(rule.method == 0 || soft_rule_ok(rule));
     Pairs pr{};
     pr.nn = nn; pr.nm = nm;
     for (int a = 0; a < nn; ++a) { SMIN_REQUIRE(n_list[a] >= 1 && n_list[a] <= k); pr.n[a] = n_list[a]; }
     for (int c = 0; c < nm; ++c) pr.m[c] = m_list[c];
-    char* p = (char*)ws + ws_layout(B, L).total;
+    char* p = (char*)ws + select_ws_bytes(rule.method, B, L);
     long long* idx = (long long*)p;   p += align256((size_t)B * k * 2 * sizeof(long long));
     float* score = (float*)p;         p += align256((size_t)B * k * sizeof(float));
     int* count = (int*)p;             p += align256((size_t)B * sizeof(int));
+    float* raw = (float*)p;           p += rule.method == 0 ? 0 : align256((size_t)B * k * sizeof(float));
     float* hits = (float*)p;
-    const int rc = launch_top(st, pm, ps, pe, mm, B, L, k, nms_thresh, idx, score, count, (char*)ws);
+    const int rc = rule.method == 0 ? launch_top(st, pm, ps, pe, mm, B, L, k, rule.thr, idx, score, count, (char*)ws)
+                                    : soft_top_launch(st, pm, ps, pe, mm, B, L, k, rule, idx, score, raw, count, (char*)ws);
     if (rc) return rc;
     hipLaunchKernelGGL(moments_hits_kernel, dim3(B), dim3(MT), 0, st, idx, sm, L, k, pr, hits, top1);
     SMIN_LAUNCH_CHECK();
     *hits_out = hits;
+    return 0;
+}
+
+size_t smin::nms_hits_stage_bytes(int B, int L, int k, int nn, int nm) { return rule_hits_stage_bytes(0, B, L, k, nn, nm); }
+
+int smin::nms_hits_stage(hipStream_t st, const float* pm, const float* ps, const float* pe, const uint8_t* mm, const float* sm, int B, int L, int k,
+                         float nms_thresh, const int* n_list, int nn, const float* m_list, int nm, void* ws, float** hits_out, float* top1)
+{
+    return rule_hits_stage(st, pm, ps, pe, mm, sm, B, L, k, NmsRule{0, nms_thresh, 0.f, 0.f}, n_list, nn, m_list, nm, ws, hits_out, top1);
+}
+
+// R@n, IoU=m over the moments a rule keeps: the stage above, then the samples summed in order
+static int launch_ious(hipStream_t st, const float* pm, const float* ps, const float* pe, const uint8_t* mm, const float* sm, int B, int L, int k,
+                       const NmsRule& rule, const int* n_list, int nn, const float* m_list, int nm, float* counts, void* ws)
+{
+    const int npairs = nn * nm;
+    float* hits = nullptr;
+    const int rc = rule_hits_stage(st, pm, ps, pe, mm, sm, B, L, k, rule, n_list, nn, m_list, nm, ws, &hits, nullptr);
+    if (rc) return rc;
+    hipLaunchKernelGGL(moments_hits_sum_kernel, dim3((npairs + 63) / 64), dim3(64), 0, st, hits, B, npairs, counts);
+    SMIN_LAUNCH_CHECK();
     return 0;
 }
 
@@ -537,14 +529,24 @@ extern "C" int smin_compute_ious_nms(void* stream, const float* pm, const float*
 {
     SMIN_REQUIRE(args_ok(B, L, k) && nn >= 1 && nn <= MAX_N && nm >= 1 && nm <= MAX_M && n_list && m_list);
     SMIN_REQUIRE(ws != nullptr && ws_bytes >= smin_compute_ious_nms_ws_bytes(B, L, k, nn, nm));
-    const int npairs = nn * nm;
-    hipStream_t st = (hipStream_t)stream;
-    float* hits = nullptr;
-    const int rc = nms_hits_stage(st, pm, ps, pe, mm, sm, B, L, k, nms_thresh, n_list, nn, m_list, nm, ws, &hits, nullptr);
-    if (rc) return rc;
-    hipLaunchKernelGGL(moments_hits_sum_kernel, dim3((npairs + 63) / 64), dim3(64), 0, st, hits, B, npairs, counts);
-    SMIN_LAUNCH_CHECK();
-    return 0;
+    return launch_ious((hipStream_t)stream, pm, ps, pe, mm, sm, B, L, k, NmsRule{0, nms_thresh, 0.f, 0.f}, n_list, nn, m_list, nm, counts, ws);
+}
+
+extern "C" size_t smin_compute_ious_soft_ws_bytes(int B, int L, int k, int nn, int nm)
+{
+    return rule_hits_stage_bytes(SMIN_NMS_LINEAR, B, L, k, nn, nm);     // both soft rules carve the same scratch
+}
+
+extern "C" int smin_compute_ious_soft(void* stream, const float* pm, const float* ps, const float* pe, const uint8_t* mm, const float* sm,
+                                      int B, int L, int k, int method, float nms_thresh, float sigma, const int* n_list, int nn,
+                                      const float* m_list, int nm, float* counts, void* ws, size_t ws_bytes)
+{
+    const NmsRule rule{method, nms_thresh, sigma, -__builtin_inff()};
+    SMIN_REQUIRE(soft_rule_ok(rule));
+    SMIN_REQUIRE(args_ok(B, L, k) && nn >= 1 && nn <= MAX_N && nm >= 1 && nm <= MAX_M && n_list && m_list);
+    SMIN_REQUIRE(pm && ps && pe && mm && sm && counts);
+    SMIN_REQUIRE(ws != nullptr && ws_bytes >= smin_compute_ious_soft_ws_bytes(B, L, k, nn, nm));
+    return launch_ious((hipStream_t)stream, pm, ps, pe, mm, sm, B, L, k, rule, n_list, nn, m_list, nm, counts, ws);
 }
 
 extern "C" int smin_merge_window_moments(void* stream, const int64_t* idx, const float* score, const int32_t* count, const int64_t* start,

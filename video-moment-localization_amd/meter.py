@@ -54,8 +54,13 @@ def _lstm_cluster_error(device):
 
 
 class _Meter:
-    def __init__(self, n=_REF_N, m=_REF_M, nms_thresh=None, device=None):
+    def __init__(self, n=_REF_N, m=_REF_M, nms_thresh=None, device=None, nms="hard", sigma=0.5):
         self.n, self.m = tuple(n), tuple(m)
+        from .moments import soft_rule
+        self.nms, self.sigma = nms, float(sigma)
+        self._soft = soft_rule(type(self).__name__, nms, 1.0 if nms_thresh is None else nms_thresh, sigma, None)   # ValueError: bad nms / sigma
+        if self._soft is not None and nms_thresh is None:
+            raise ValueError(f"{type(self).__name__}: nms={nms!r} ranks the valid cells like the nms_thresh rule; pass nms_thresh")
         self.keys = [f"R@{n_}, IoU={m_}" for n_ in self.n for m_ in self.m]
         if nms_thresh is None:
             if self.n != _REF_N or self.m != _REF_M:
@@ -116,6 +121,7 @@ class EpochMeter(_Meter):
     """``EpochMeter(n=(1, 5), m=(0.1, 0.3, 0.5, 0.7), nms_thresh=None, device=...)``: ``nms_thresh=None`` is the reference's rule
     (``compute_ious``'s kernel; only the reference's n / m -- ``compute_ious`` sends other lists to its torch form, which the meter
     does not offer); a number selects greedy temporal NMS over the valid cells (``compute_ious(..., nms_thresh=t)``, same limits).
+    With a number, ``nms="linear"`` / ``"gaussian"`` (and ``sigma``) rank by Soft-NMS instead (``compute_ious(..., nms=...)``).
 
     ``update(pm, ps, pe, moment_mask, sm, loss=None)`` enqueues the kernels on the current stream and returns nothing; ``loss``
     is the device scalar ``loss_fn`` returned.  HIP tensors only.  ``result()`` reads, ``reset()`` zeroes, ``state`` is the fp64
@@ -143,6 +149,16 @@ class EpochMeter(_Meter):
         mm_ = byte_mask(moment_mask)
         loss_ = None if loss is None else loss.detach().float().reshape(1).contiguous()
         nl, ml = (ctypes.c_int * len(self._n))(*self._n), (ctypes.c_float * len(self._m))(*self._m)
+        if self._soft is not None:                               # rule 1 with the Soft-NMS selection
+            with torch.cuda.device(pm.device):
+                nbytes = load().smin_epoch_meter_soft_ws_bytes(B, L, self.k, len(self._n), len(self._m))
+                if nbytes == 0:
+                    raise SminHipError(f"smin_epoch_meter_soft_ws_bytes rejected B={B}, L={L}, k={self.k}")
+                ws = torch.empty((nbytes,), dtype=torch.uint8, device=pm.device)
+                call("smin_epoch_meter_update_soft", stream(), ptr(pm_), ptr(ps_), ptr(pe_), ptr(mm_), ptr(sm_), B, L, self.k, *self._soft[:3],
+                     ctypes.cast(nl, ctypes.c_void_p), len(self._n), ctypes.cast(ml, ctypes.c_void_p), len(self._m), ptr(loss_),
+                     ptr(self.state), ptr(ws), nbytes)
+            return
         with torch.cuda.device(pm.device):
             nbytes = load().smin_epoch_meter_ws_bytes(B, L, self.rule, self.k, len(self._n), len(self._m))
             if nbytes == 0:
@@ -180,8 +196,11 @@ class EpochMeterTorch(_Meter):
         B, L = pm.shape[0], pm.shape[1]
         smf = sm.detach().float().reshape(B, -1)
         if self.rule == 1:
-            from .moments import top_moments_torch
-            idx = top_moments_torch(pm, ps, pe, moment_mask, k=1, nms_thresh=self.nms_thresh)["idx"][:, 0]
+            from .moments import top_moments_soft_torch, top_moments_torch
+            if self._soft is None:
+                idx = top_moments_torch(pm, ps, pe, moment_mask, k=1, nms_thresh=self.nms_thresh)["idx"][:, 0]
+            else:                                                # the first pick of a soft rule is the best valid cell
+                idx = top_moments_soft_torch(pm, ps, pe, moment_mask, k=1, nms_thresh=self.nms_thresh, nms=self.nms, sigma=self.sigma)["idx"][:, 0]
             flat = idx[:, 0] * L + idx[:, 1]
             iou = torch.gather(smf, 1, flat.clamp_min(0).unsqueeze(1)).squeeze(1)
             return torch.where(flat >= 0, iou, torch.zeros_like(iou))
@@ -195,7 +214,8 @@ class EpochMeterTorch(_Meter):
     def update(self, pm, ps, pe, moment_mask, sm, loss=None):
         from .training import compute_ious_torch
         B, L = _check(pm, ps, pe, moment_mask, 1)
-        counts = compute_ious_torch(pm.detach(), ps.detach(), pe.detach(), moment_mask, sm, self.n, self.m, nms_thresh=self.nms_thresh)
+        counts = compute_ious_torch(pm.detach(), ps.detach(), pe.detach(), moment_mask, sm, self.n, self.m, nms_thresh=self.nms_thresh,
+                                    nms=self.nms, sigma=self.sigma)
         delta = [0.0] * self.state.numel()
         delta[0] = float(B)
         if loss is not None:

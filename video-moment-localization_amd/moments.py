@@ -17,7 +17,10 @@ Semantics (csrc/moments.hip, include/smin_hip.h), for each sample b:
 
 ``top_moments`` is the product entry point (HIP kernels, HIP tensors only, no host synchronisation, capturable in a graph);
 ``top_moments_torch`` is the same function as plain torch + Python on any device, kept under its own name as the restatement
-the tests compare against -- nothing routes to it silently."""
+the tests compare against -- nothing routes to it silently.
+
+``nms="linear"`` / ``"gaussian"`` replace the greedy walk by Soft-NMS (csrc/soft_nms.hip; ``soft_rule`` states the rules): a pick
+decays the scores of the candidates it overlaps and the rest is ranked again.  ``top_moments_soft_torch`` is its restatement."""
 import ctypes
 import functools
 
@@ -75,20 +78,143 @@ def _top_moments_into(pm, ps, pe, moment_mask, k, nms_thresh, idx, score, count)
              ptr(idx), ptr(score), ptr(count), ptr(ws), nbytes)
 
 
-def top_moments(pm, ps, pe, moment_mask, k=5, nms_thresh=0.5, duration=None):
+def top_moments(pm, ps, pe, moment_mask, k=5, nms_thresh=0.5, duration=None, nms="hard", sigma=0.5, min_score=None):
     """The k best moments of each sample after greedy temporal NMS (module docstring), on the device: a band-parallel select
     and one NMS workgroup per sample (csrc/moments.hip).  HIP tensors only; no host synchronisation.
 
     Returns a dict: ``idx`` (B, k, 2) int64 start / end clip (-1 for empty slots), ``score`` (B, k) float32 (0 for empty
     slots), ``count`` (B,) int32; with ``duration`` (B,) seconds also ``times`` (B, k, 2) float32:
-    ``(i * duration / L, (j + 1) * duration / L)``, NaN for empty slots."""
+    ``(i * duration / L, (j + 1) * duration / L)``, NaN for empty slots.
+
+    ``nms="linear"`` / ``"gaussian"`` select Soft-NMS (csrc/soft_nms.hip; the rules are stated at ``soft_rule``): a pick decays the
+    score of the candidates it overlaps and the rest is ranked again.  ``score`` is then the decayed score at pick time and the dict
+    gains ``raw_score (B, k)``, the picked cells' undecayed scores (0 for empty slots); ``min_score`` ends a sample's list at the first
+    best decayed score below it (``None``: never).  ``nms="hard"`` (default) is the path above, unchanged; it reads neither ``sigma``
+    nor ``min_score``."""
     _require_hip(pm, "top_moments")
     B, L = _check(pm, ps, pe, moment_mask, k)
+    rule = soft_rule("top_moments", nms, nms_thresh, sigma, min_score)
     idx = torch.empty((B, k, 2), dtype=torch.int64, device=pm.device)
     score = torch.empty((B, k), dtype=torch.float32, device=pm.device)
     count = torch.empty((B,), dtype=torch.int32, device=pm.device)
-    _top_moments_into(pm, ps, pe, moment_mask, k, nms_thresh, idx, score, count)
-    return _result(idx, score, count, duration, L)
+    if rule is None:
+        _top_moments_into(pm, ps, pe, moment_mask, k, nms_thresh, idx, score, count)
+        return _result(idx, score, count, duration, L)
+    raw = torch.empty((B, k), dtype=torch.float32, device=pm.device)
+    _top_moments_soft_into(pm, ps, pe, moment_mask, k, rule, idx, score, raw, count)
+    out = _result(idx, score, count, duration, L)
+    out["raw_score"] = raw
+    return out
+
+
+# ---------------------------------------------------------------- Soft-NMS (csrc/soft_nms.hip)
+NMS_METHODS = {"linear": 1, "gaussian": 2}          # include/smin_hip.h SMIN_NMS_LINEAR / SMIN_NMS_GAUSSIAN
+
+
+def soft_rule(what, nms, nms_thresh, sigma, min_score):
+    """``None`` for ``nms="hard"``, else the checked soft rule ``(method, nms_thresh, sigma, min_score)`` as the C ABI takes it.
+
+    Per sample, with ``cur = score`` initially: pick the remaining candidate with the highest ``cur`` (ties -> lower index); stop
+    after k picks, when none is left or when the best ``cur < min_score`` (fp32; ``None`` = -inf); record it; then for every remaining
+    candidate ``cur = cur * w`` in fp32 with ``iou`` its IoU with the pick: ``"linear"``: ``w = 1 - iou if iou > nms_thresh else 1``;
+    ``"gaussian"``: ``w = expf(-(iou * iou) / sigma)`` for every candidate (``sigma > 0``, ``inf`` allowed: ``w = 1``).  NaN and inf
+    scores at valid cells are out of scope for the soft rules."""
+    if nms == "hard":
+        return None
+    if nms not in NMS_METHODS:
+        raise ValueError(f"{what}: nms must be 'hard', 'linear' or 'gaussian' (got {nms!r})")
+    sigma = float(sigma)
+    if nms == "gaussian" and not sigma > 0:
+        raise ValueError(f"{what}: nms='gaussian' needs sigma > 0 (got {sigma!r})")
+    floor = float("-inf") if min_score is None else float(min_score)
+    if floor != floor:
+        raise ValueError(f"{what}: min_score must not be NaN")
+    return NMS_METHODS[nms], float(nms_thresh), sigma, floor
+
+
+def _top_moments_soft_into(pm, ps, pe, moment_mask, k, rule, idx, score, raw, count):
+    """smin_top_moments_soft of B checked samples into the caller's contiguous outputs (``_top_moments_into``'s contract)."""
+    B, L = pm.shape[0], pm.shape[1]
+    pm_, ps_, pe_ = (x.detach().float().contiguous() for x in (pm, ps, pe))
+    mm_ = byte_mask(moment_mask)
+    with torch.cuda.device(pm.device):
+        nbytes = load().smin_top_moments_soft_ws_bytes(B, L, k)
+        ws = torch.empty((nbytes,), dtype=torch.uint8, device=pm.device)
+        call("smin_top_moments_soft", stream(), ptr(pm_), ptr(ps_), ptr(pe_), ptr(mm_), B, L, k, *rule,
+             ptr(idx), ptr(score), ptr(raw), ptr(count), ptr(ws), nbytes)
+
+
+def _f32(x, dev):
+    return torch.tensor(x, dtype=torch.float32, device=dev)
+
+
+def _decay_torch(cur, iou, rule, dev):
+    """One decay of fp32 ``cur`` by fp32 ``iou``.  linear: correctly rounded fp32 operations (bit for bit the kernel's); gaussian: the
+    weight and the product in fp64, returned as fp64 (the kernel's expf is checked against it, not reproduced)."""
+    method, thr, sigma, _ = rule
+    if method == NMS_METHODS["linear"]:
+        w = torch.where(iou > _f32(thr, dev), (1.0 - iou.double()).float(), torch.ones_like(iou))   # 1 - iou: one rounding
+        return _mul32(cur, w)
+    x = iou.double()
+    return cur * torch.exp(-(x * x) / sigma)
+
+
+def _soft_pick_loop(s0, valid, iou_with, k, rule, dev):
+    """The soft rule over one sample's candidates: ``s0`` (n,) fp32 start scores, ``valid`` (n,) bool, ``iou_with(c)`` -> (n,) fp32
+    IoUs with candidate c.  Returns the picks' candidate indices and their ``cur`` at pick time (fp32 for linear, fp64 for
+    gaussian)."""
+    gauss = rule[0] == NMS_METHODS["gaussian"]
+    cur = s0.double() if gauss else s0.clone()
+    alive = valid.clone()
+    picks, vals = [], []
+    floor = _f32(rule[3], dev)
+    for _ in range(k):
+        if not bool(alive.any()):
+            break
+        o = _order_word(cur.float())
+        o = torch.where(alive, o, torch.zeros_like(o))
+        c = int(torch.argmax((o == o.max()).to(torch.uint8)))                # the first index holding the maximum
+        if bool(cur[c].float() < floor):
+            break
+        picks.append(c)
+        vals.append(cur[c].clone())
+        alive[c] = False
+        cur = torch.where(alive, _decay_torch(cur, iou_with(c), rule, dev), cur)
+    return picks, vals
+
+
+def top_moments_soft_torch(pm, ps, pe, moment_mask, k=5, nms_thresh=0.5, duration=None, nms="linear", sigma=0.5, min_score=None):
+    """Soft ``top_moments`` as plain torch + Python on any device.  ``nms="linear"`` gives the kernels' result bit for bit (every
+    operation is a correctly rounded fp32 one); ``nms="gaussian"`` carries the decayed scores in fp64 (exact exp, unrounded
+    products) and rounds the recorded ``score`` to fp32 once -- the reference the device's expf is measured against."""
+    B, L = _check(pm, ps, pe, moment_mask, k)
+    rule = soft_rule("top_moments_soft_torch", nms, nms_thresh, sigma, min_score)
+    if rule is None:
+        raise ValueError("top_moments_soft_torch restates the soft rules; nms='hard' is top_moments_torch")
+    dev = pm.device
+    score = _mul32(_mul32(pm.detach(), _sqrt32(ps.detach()).unsqueeze(2)), _sqrt32(pe.detach()).unsqueeze(1))
+    score = torch.where(score == 0, torch.zeros_like(score), score).reshape(B, -1)              # -0 -> +0
+    valid = byte_mask(moment_mask).reshape(B, -1) != 0
+    score = torch.where(valid, score, torch.zeros_like(score))                                   # masked NaN / inf never enter
+    cells = torch.arange(L * L, device=dev)
+    ci, cj = cells // L, cells % L
+    idx = torch.full((B, k, 2), -1, dtype=torch.int64, device=dev)
+    out_score = torch.zeros((B, k), dtype=torch.float32, device=dev)
+    raw = torch.zeros((B, k), dtype=torch.float32, device=dev)
+    count = torch.zeros((B,), dtype=torch.int32, device=dev)
+    for b in range(B):
+        picks, vals = _soft_pick_loop(score[b], valid[b], lambda c: _iou(ci, cj, ci[c], cj[c]), k, rule, dev)
+        n = len(picks)
+        if n:
+            pc = torch.tensor(picks, dtype=torch.int64, device=dev)
+            idx[b, :n, 0], idx[b, :n, 1] = pc // L, pc % L
+            v = torch.stack(vals).float()
+            out_score[b, :n] = torch.where(v == 0, torch.zeros_like(v), v)
+            raw[b, :n] = score[b, pc]
+        count[b] = n
+    out = _result(idx, out_score, count, duration, L)
+    out["raw_score"] = raw
+    return out
 
 
 # Correctly rounded fp32 sqrt / product / quotient on any device: computed in fp64 and rounded once to fp32 (fp64 carries more than
@@ -170,7 +296,7 @@ def _nm_check(n, m):
     return n, m
 
 
-def compute_ious_nms(pm, ps, pe, moment_mask, sm, n, m, nms_thresh):
+def compute_ious_nms(pm, ps, pe, moment_mask, sm, n, m, nms_thresh, nms="hard", sigma=0.5):
     """R@n, IoU=m over the NMS-kept moments on the device (training.compute_ious(..., nms_thresh=t)): top-k with k = max(n), then
     sm gathered at the kept cells (empty slot = IoU 0) and the hits summed over the samples by the device.  One host read."""
     B, L = _check(pm, ps, pe, moment_mask, 1)
@@ -181,6 +307,14 @@ def compute_ious_nms(pm, ps, pe, moment_mask, sm, n, m, nms_thresh):
     mm_ = byte_mask(moment_mask)
     nl, ml = (ctypes.c_int * len(n))(*n), (ctypes.c_float * len(m))(*m)
     counts = torch.empty((len(n) * len(m),), dtype=torch.float32, device=pm.device)
+    rule = soft_rule("compute_ious", nms, nms_thresh, sigma, None)
+    if rule is not None:                                         # the soft selection in front of the same hit flags and sums
+        with torch.cuda.device(pm.device):
+            nbytes = load().smin_compute_ious_soft_ws_bytes(B, L, k, len(n), len(m))
+            ws = torch.empty((nbytes,), dtype=torch.uint8, device=pm.device)
+            call("smin_compute_ious_soft", stream(), ptr(pm_), ptr(ps_), ptr(pe_), ptr(mm_), ptr(sm_), B, L, k, *rule[:3],
+                 ctypes.cast(nl, ctypes.c_void_p), len(n), ctypes.cast(ml, ctypes.c_void_p), len(m), ptr(counts), ptr(ws), nbytes)
+        return dict(zip(keys, counts.tolist()))
     with torch.cuda.device(pm.device):
         nbytes = load().smin_compute_ious_nms_ws_bytes(B, L, k, len(n), len(m))
         ws = torch.empty((nbytes,), dtype=torch.uint8, device=pm.device)
@@ -189,12 +323,15 @@ def compute_ious_nms(pm, ps, pe, moment_mask, sm, n, m, nms_thresh):
     return dict(zip(keys, counts.tolist()))
 
 
-def compute_ious_nms_torch(pm, ps, pe, moment_mask, sm, n, m, nms_thresh):
+def compute_ious_nms_torch(pm, ps, pe, moment_mask, sm, n, m, nms_thresh, nms="hard", sigma=0.5):
     """``compute_ious_nms`` through ``top_moments_torch`` (any device)."""
     B, L = _check(pm, ps, pe, moment_mask, 1)
     keys = [f"R@{n_}, IoU={m_}" for n_ in n for m_ in m]
     n, m = _nm_check(n, m)
-    r = top_moments_torch(pm, ps, pe, moment_mask, k=max(n), nms_thresh=nms_thresh)
+    if nms == "hard":
+        r = top_moments_torch(pm, ps, pe, moment_mask, k=max(n), nms_thresh=nms_thresh)
+    else:
+        r = top_moments_soft_torch(pm, ps, pe, moment_mask, k=max(n), nms_thresh=nms_thresh, nms=nms, sigma=sigma)
     flat = r["idx"][..., 0] * L + r["idx"][..., 1]
     ious = torch.gather(sm.detach().float().reshape(B, -1), 1, flat.clamp_min(0))
     ious = torch.where(flat >= 0, ious, torch.zeros_like(ious))
@@ -219,7 +356,7 @@ def _merge_check(idx, score, count, start, lens, pair_ptr, T, L, k):
     return G, kw, pair_ptr.shape[0] - 1
 
 
-def merge_window_moments(idx, score, count, start, lens, pair_ptr, T, L, k=5, nms_thresh=0.5):
+def merge_window_moments(idx, score, count, start, lens, pair_ptr, T, L, k=5, nms_thresh=0.5, nms="hard", sigma=0.5, min_score=None):
     """Greedy temporal NMS, in raw-row time, of the per-window top moments of long videos (include/smin_hip.h,
     smin_merge_window_moments): one workgroup per (video, query) pair picks k times the best candidate that no kept span suppresses.
 
@@ -227,9 +364,15 @@ def merge_window_moments(idx, score, count, start, lens, pair_ptr, T, L, k=5, nm
     window's first row relative to its video, ``lens (G,)`` its row count; ``pair_ptr (B + 1,)``: pair b owns windows
     ``pair_ptr[b] .. pair_ptr[b + 1]``.  HIP tensors only; no host synchronisation.  Returns a dict: ``span (B, k, 2)`` float32 raw
     rows (NaN for empty slots), ``score (B, k)`` (0), ``window (B, k)`` int64 ordinal within the pair (-1), ``cell (B, k, 2)`` int64
-    (-1), ``count (B,)`` int32."""
+    (-1), ``count (B,)`` int32.
+
+    ``nms="linear"`` / ``"gaussian"``: the soft rule of ``soft_rule`` over the same candidates, spans and span IoU
+    (smin_merge_window_moments_soft).  ``score`` must then hold the windows' UNDECAYED scores (soft ``top_moments``' ``raw_score``):
+    the merge decays once, in raw-row time.  The result's ``score`` is the decayed score at pick time and ``raw_score (B, k)`` the
+    candidate's input score."""
     _require_hip(idx, "merge_window_moments")
     G, kw, B = _merge_check(idx, score, count, start, lens, pair_ptr, T, L, k)
+    rule = soft_rule("merge_window_moments", nms, nms_thresh, sigma, min_score)
     dev = idx.device
     args = [idx.to(torch.int64), score.detach().float(), count.to(torch.int32), start.to(torch.int64), lens.to(torch.int32),
             pair_ptr.to(torch.int64)]
@@ -239,6 +382,12 @@ def merge_window_moments(idx, score, count, start, lens, pair_ptr, T, L, k=5, nm
     window = torch.empty((B, k), dtype=torch.int64, device=dev)
     cell = torch.empty((B, k, 2), dtype=torch.int64, device=dev)
     out_count = torch.empty((B,), dtype=torch.int32, device=dev)
+    if rule is not None:
+        raw = torch.empty((B, k), dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            call("smin_merge_window_moments_soft", stream(), *[ptr(a) for a in args], G, B, int(T), int(L), kw, k, *rule,
+                 ptr(span), ptr(out_score), ptr(raw), ptr(window), ptr(cell), ptr(out_count))
+        return {"span": span, "score": out_score, "raw_score": raw, "window": window, "cell": cell, "count": out_count}
     with torch.cuda.device(dev):
         call("smin_merge_window_moments", stream(), *[ptr(a) for a in args], G, B, int(T), int(L), kw, k, float(nms_thresh),
              ptr(span), ptr(out_score), ptr(window), ptr(cell), ptr(out_count))
@@ -270,10 +419,14 @@ def _span_iou(st1, en1, st2, en2):
     return _div32(inter, uni)
 
 
-def merge_window_moments_torch(idx, score, count, start, lens, pair_ptr, T, L, k=5, nms_thresh=0.5):
+def merge_window_moments_torch(idx, score, count, start, lens, pair_ptr, T, L, k=5, nms_thresh=0.5, nms="hard", sigma=0.5, min_score=None):
     """``merge_window_moments`` as plain torch + Python on any device (same result, bit for bit): each pair's candidates sorted by
-    (score, window, slot), then the greedy walk."""
+    (score, window, slot), then the greedy walk.  With a soft ``nms``: the pick-and-decay loop of ``top_moments_soft_torch`` over the
+    pair's candidates and their span IoUs (linear bit for bit, gaussian in fp64)."""
     G, kw, B = _merge_check(idx, score, count, start, lens, pair_ptr, T, L, k)
+    rule = soft_rule("merge_window_moments_torch", nms, nms_thresh, sigma, min_score)
+    if rule is not None:
+        return _merge_window_moments_soft_torch(idx, score, count, start, lens, pair_ptr, T, L, k, rule)
     dev = idx.device
     score = score.detach().float()
     o = _order_word(score).reshape(-1)
@@ -311,6 +464,40 @@ def merge_window_moments_torch(idx, score, count, start, lens, pair_ptr, T, L, k
             cell[b, :n] = idx.reshape(-1, 2)[ks].to(torch.int64)
         out_count[b] = n
     return {"span": span, "score": out_score, "window": window, "cell": cell, "count": out_count}
+
+
+def _merge_window_moments_soft_torch(idx, score, count, start, lens, pair_ptr, T, L, k, rule):
+    G, kw, B = idx.shape[0], idx.shape[1], pair_ptr.shape[0] - 1
+    dev = idx.device
+    score = score.detach().float().reshape(-1)
+    st_all, en_all = window_spans(idx, start.unsqueeze(1), lens.unsqueeze(1), T, L)              # (G, kw)
+    st_all, en_all = st_all.reshape(-1), en_all.reshape(-1)
+    slot_ok = (torch.arange(kw, device=dev).unsqueeze(0) < count.to(torch.int64).unsqueeze(1)).reshape(-1)
+    span = torch.full((B, k, 2), float("nan"), dtype=torch.float32, device=dev)
+    out_score = torch.zeros((B, k), dtype=torch.float32, device=dev)
+    raw = torch.zeros((B, k), dtype=torch.float32, device=dev)
+    window = torch.full((B, k), -1, dtype=torch.int64, device=dev)
+    cell = torch.full((B, k, 2), -1, dtype=torch.int64, device=dev)
+    out_count = torch.zeros((B,), dtype=torch.int32, device=dev)
+    pp = pair_ptr.to(torch.int64).tolist()
+    for b in range(B):
+        g0 = min(max(pp[b], 0), G)
+        g1 = min(max(pp[b + 1], g0), G)
+        q = torch.arange(g0 * kw, g1 * kw, device=dev)                                             # candidates in (window, slot) order
+        if q.numel() == 0:
+            continue
+        st, en = st_all[q], en_all[q]
+        picks, vals = _soft_pick_loop(score[q], slot_ok[q], lambda c: _span_iou(st, en, st[c], en[c]), k, rule, dev)
+        n = len(picks)
+        if n:
+            ks = q[torch.tensor(picks, dtype=torch.int64, device=dev)]
+            span[b, :n, 0], span[b, :n, 1] = st_all[ks], en_all[ks]
+            out_score[b, :n] = torch.stack(vals).float()
+            raw[b, :n] = score[ks]
+            window[b, :n] = ks // kw - g0
+            cell[b, :n] = idx.reshape(-1, 2)[ks].to(torch.int64)
+        out_count[b] = n
+    return {"span": span, "score": out_score, "raw_score": raw, "window": window, "cell": cell, "count": out_count}
 
 
 # ---------------------------------------------------------------- metric of merged spans against ground-truth spans

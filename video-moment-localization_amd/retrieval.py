@@ -15,7 +15,7 @@ from . import _lib
 from ._host import _AttnMaps, byte_mask, host_array, known_cells, query_mask_rows, require_hip_tensors, require_ints
 from .feeder import build_masks_hip, cell_count
 from .functional import attn_maps_gather
-from .moments import (MAX_K, PREFILTER_FOLD_MAX_M, bank_decode, bank_encode, bank_storage, require_storage, prefilter_fold, prefilter_gt_rank, survivors_admit, _pair_pool_into, _temperature, _top_moments_into, _video_weight, corpus_span_topk, corpus_span_topk_torch, corpus_topk,
+from .moments import (MAX_K, PREFILTER_FOLD_MAX_M, bank_decode, bank_encode, bank_storage, require_storage, prefilter_fold, prefilter_gt_rank, survivors_admit, _pair_pool_into, _temperature, _top_moments_into, _top_moments_soft_into, soft_rule, _video_weight, corpus_span_topk, corpus_span_topk_torch, corpus_topk,
                       corpus_topk_torch, group_pool, merge_window_moments, merge_window_moments_torch, mine_pairs, prefilter_maps, prefilter_scores, prefilter_select,
                       rank_videos, reweight_moments, expand_survivor_windows, survivor_window_capacity,
                       reweight_moments_torch, search_times, top_moments, top_moments_torch, window_times)
@@ -360,10 +360,11 @@ class _Retrieval:
         return self.score(*inputs) if self.forward_only_scoring else self(*inputs)
 
     def localize(self, video_features, video_mask, query_features, query_mask, length_mask, moment_mask, k=5, nms_thresh=0.5,
-                 duration=None, attention=False):
+                 duration=None, attention=False, nms="hard", sigma=0.5, min_score=None):
         """The k best moments per sample: the forward under torch.no_grad() (score() with forward_only_scoring), then moments.top_moments of its (pm, ps, pe) -- greedy
         temporal NMS at ``nms_thresh`` over the valid cells of ``moment_mask``.  Returns top_moments' dict (``idx`` (B, k, 2) start
         / end clip, ``score``, ``count``; with ``duration`` (B,) seconds also ``times`` (B, k, 2) in seconds).
+        ``nms="linear"`` / ``"gaussian"`` with ``sigma`` and ``min_score``: top_moments' Soft-NMS rules (the dict gains ``raw_score``).
 
         attention=True: also ``content_attention`` (B, k, layers, C, Nq), the content unit's word weights of each clip of each kept
         moment, and ``boundary_attention`` (B, k, layers, 2, Nq), the boundary unit's word weights of its start and end rows (empty
@@ -374,14 +375,14 @@ class _Retrieval:
                 pm, ps, pe, _ = self._forward(video_features, video_mask, query_features, query_mask, length_mask, moment_mask, maps)
             else:
                 pm, ps, pe, _ = self._scores(video_features, video_mask, query_features, query_mask, length_mask, moment_mask)
-            r = top_moments(pm, ps, pe, moment_mask, k=k, nms_thresh=nms_thresh, duration=duration)
+            r = top_moments(pm, ps, pe, moment_mask, k=k, nms_thresh=nms_thresh, duration=duration, nms=nms, sigma=sigma, min_score=min_score)
             if attention:
                 r["content_attention"], r["boundary_attention"] = attn_maps_gather([c for c, _ in maps], [b for _, b in maps], maps.cellmap,
                                                                                    r["idx"], self.C)
         return r
 
     def localize_windows(self, raw, lengths, query_features, query_mask, video_index=None, window=None, stride=None, k=5, k_window=None,
-                         nms_thresh=0.5, mode="pick", duration=None, max_batch=64):
+                         nms_thresh=0.5, mode="pick", duration=None, max_batch=64, nms="hard", sigma=0.5, min_score=None):
         """The k best moments of (video, query) pairs over videos of any length: overlapping windows of ``window`` raw rows (default
         T: one row per clip) every ``stride`` rows (default window // 2) are each resampled to T clips, scored by the model and cut to
         their ``k_window`` (default k) best moments, which are then merged per pair by greedy NMS in raw-row time.
@@ -394,8 +395,13 @@ class _Retrieval:
 
         Returns a dict: ``span`` (B, k, 2) float32 raw rows of the video (NaN for empty slots), ``score`` (B, k), ``window`` (B, k)
         int64 window ordinal within the pair (-1), ``cell`` (B, k, 2) int64 cell of that window (-1), ``count`` (B,) int32 and
-        ``n_windows`` (B,) int64; with ``duration`` (B,) seconds also ``times`` = (span * duration) / n (fp32; n = the video's rows)."""
+        ``n_windows`` (B,) int64; with ``duration`` (B,) seconds also ``times`` = (span * duration) / n (fp32; n = the video's rows).
+
+        ``nms="linear"`` / ``"gaussian"`` (moments.soft_rule): each window picks its ``k_window`` candidates by the soft rule and hands
+        their UNDECAYED scores to the soft merge, which decays them once, in raw-row time, and applies ``min_score``; the result gains
+        ``raw_score`` (B, k)."""
         T, L = self.T, self.L
+        rule = soft_rule("localize_windows", nms, nms_thresh, sigma, min_score)
         k_window = k if k_window is None else k_window
         window = T if window is None else window
         stride = max(int(window) // 2, 1) if stride is None else stride
@@ -442,6 +448,7 @@ class _Retrieval:
                                                             pair_ptr, nw, n[vi]], np.int64, dev)
         ln_d = ln_d.to(torch.int32)
         idx, score, count, chunks = _chunk_buffers(G, k_window, max_batch, dev)
+        decayed = None if rule is None else torch.empty_like(score)                              # the windows' own decays: not used
         with torch.no_grad(), torch.cuda.device(dev):
             for c0, c1 in chunks:
                 vf, nfeats = sample_windows(raw, rb_d[c0:c1], ln_d[c0:c1], T, mode=mode)
@@ -450,8 +457,12 @@ class _Retrieval:
                 qf, qm = query_features.index_select(0, rows), query_mask.index_select(0, rows)
                 with known_cells(self, int(cells[c0:c1].sum())):
                     pm, ps, pe, _ = self._scores(vf, m["video_mask"], qf, qm, m["length_mask"], m["moment_mask"])
-                _top_moments_into(pm, ps, pe, m["moment_mask"], k_window, nms_thresh, idx[c0:c1], score[c0:c1], count[c0:c1])
-        r = merge_window_moments(idx, score, count, st_d, ln_d, pp_d, T, L, k=k, nms_thresh=nms_thresh)
+                if rule is None:
+                    _top_moments_into(pm, ps, pe, m["moment_mask"], k_window, nms_thresh, idx[c0:c1], score[c0:c1], count[c0:c1])
+                else:                                                                            # score <- the picks' raw scores
+                    _top_moments_soft_into(pm, ps, pe, m["moment_mask"], k_window, rule[:3] + (float("-inf"),), idx[c0:c1], decayed[c0:c1],
+                                           score[c0:c1], count[c0:c1])
+        r = merge_window_moments(idx, score, count, st_d, ln_d, pp_d, T, L, k=k, nms_thresh=nms_thresh, nms=nms, sigma=sigma, min_score=min_score)
         r["n_windows"] = nw_d
         if duration is not None:
             d = duration.to(device=dev, dtype=torch.float32).reshape(B, 1, 1)

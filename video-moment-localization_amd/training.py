@@ -210,12 +210,19 @@ def pair_distill_loss(pm, ps, pe, moment_mask, plan, teacher, tau=0.1, gamma=0.1
     return tuple(out) if return_stats else out[0]
 
 
-def compute_ious_torch(pm, ps, pe, moment_mask, sm, n=(1, 5), m=(0.1, 0.3, 0.5, 0.7), nms_thresh=None):
+def _nms_needs_thresh(what, nms, nms_thresh):
+    if nms != "hard" and nms_thresh is None:
+        raise ValueError(f"{what}: nms={nms!r} ranks the valid cells like the nms_thresh rule; pass nms_thresh (the linear rule reads it)")
+
+
+def compute_ious_torch(pm, ps, pe, moment_mask, sm, n=(1, 5), m=(0.1, 0.3, 0.5, 0.7), nms_thresh=None, nms="hard", sigma=0.5):
     """reference utils.py:10-31 as plain torch ops with a single host sync (the reference syncs once per (n, m) pair).
-    ``nms_thresh`` set: R@n, IoU=m over the moments kept by greedy temporal NMS (moments.top_moments_torch) instead."""
+    ``nms_thresh`` set: R@n, IoU=m over the moments kept by greedy temporal NMS (moments.top_moments_torch) instead, or, with
+    ``nms="linear"`` / ``"gaussian"``, over the Soft-NMS picks (moments.top_moments_soft_torch)."""
+    _nms_needs_thresh("compute_ious_torch", nms, nms_thresh)
     if nms_thresh is not None:
         from .moments import compute_ious_nms_torch
-        return compute_ious_nms_torch(pm, ps, pe, moment_mask, sm, n, m, nms_thresh)
+        return compute_ious_nms_torch(pm, ps, pe, moment_mask, sm, n, m, nms_thresh, nms=nms, sigma=sigma)
     score = pm * torch.sqrt(ps.unsqueeze(2)) * torch.sqrt(pe.unsqueeze(1)) * moment_mask
     B = score.shape[0]
     _, top = score.reshape(B, -1).topk(k=max(n), dim=1)
@@ -225,16 +232,18 @@ def compute_ious_torch(pm, ps, pe, moment_mask, sm, n=(1, 5), m=(0.1, 0.3, 0.5, 
     return {k: float(v) for k, v in zip(keys, counts)}
 
 
-def compute_ious(pm, ps, pe, moment_mask, sm, n=(1, 5), m=(0.1, 0.3, 0.5, 0.7), nms_thresh=None):
+def compute_ious(pm, ps, pe, moment_mask, sm, n=(1, 5), m=(0.1, 0.3, 0.5, 0.7), nms_thresh=None, nms="hard", sigma=0.5):
     """reference utils.py:10-31 on the device.  With the reference's default n / m the whole metric is one kernel
     (csrc/metrics.hip) and one host read, for any L -- the 512 x 512 long-video map included.  Other (n, m), or a map
     with fewer than five proposals (where the reference's topk raises), take the torch form on the device.
     ``nms_thresh`` set: R@n, IoU=m over the moments kept by greedy temporal NMS among the valid cells (moments.top_moments;
-    csrc/moments.hip), any n <= 64 and up to 16 thresholds m, one host read.  The reference has no NMS, so this is opt-in."""
+    csrc/moments.hip), any n <= 64 and up to 16 thresholds m, one host read.  The reference has no NMS, so this is opt-in.
+    With ``nms_thresh`` set, ``nms="linear"`` / ``"gaussian"`` (and ``sigma``) rank by Soft-NMS instead (csrc/soft_nms.hip)."""
     _require_hip(pm, "compute_ious")
+    _nms_needs_thresh("compute_ious", nms, nms_thresh)
     if nms_thresh is not None:
         from .moments import compute_ious_nms
-        return compute_ious_nms(pm, ps, pe, moment_mask, sm, n, m, nms_thresh)
+        return compute_ious_nms(pm, ps, pe, moment_mask, sm, n, m, nms_thresh, nms=nms, sigma=sigma)
     if tuple(n) == (1, 5) and tuple(m) == (0.1, 0.3, 0.5, 0.7) and pm.shape[1] * pm.shape[2] >= 5:
         from ._lib import call, ptr, stream
         B, L = ps.shape
