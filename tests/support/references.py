@@ -368,6 +368,19 @@ def random_spans(B, k, seed, nan_valid=False):
     return span, count, gt
 
 
+def merge_frame_edges():
+    """merge_window_moments inputs at the edges of the merge kernels' shared frame, with T = L = 8 and k = 3: G = 4 windows of
+    k_window = 2 over B = 3 pairs.  pair_ptr starts below 0 and ends above G (both clamped), pair 1 owns no window, window 1 has count
+    0 (its slots hold a score that must never be read into the order) and window 2 count 1; scores tie across windows (0.5 three
+    times) and one is -0.0.  Returns (idx, score, count, start, lens, pair_ptr)."""
+    idx = torch.tensor([[[0, 3], [2, 5]], [[1, 1], [0, 7]], [[4, 6], [3, 3]], [[0, 2], [5, 7]]], dtype=torch.int64)
+    score = torch.tensor([[0.5, 0.5], [0.9, 0.1], [-0.0, 0.3], [0.5, 0.25]], dtype=torch.float32)
+    count = torch.tensor([2, 0, 1, 2], dtype=torch.int32)
+    start = torch.tensor([0, 4, 8, 12], dtype=torch.int64)
+    lens = torch.tensor([8, 8, 8, 6], dtype=torch.int32)
+    return idx, score, count, start, lens, torch.tensor([-1, 2, 2, 9], dtype=torch.int64)
+
+
 def backward_rows(tok, table, dqf):
     """embed_tokens(sparse_grad=True) then backward of dqf: table.row_grad"""
     qf, _, _ = vml().embed_tokens(tok, table, differentiable=True, sparse_grad=True)

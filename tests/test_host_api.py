@@ -125,6 +125,23 @@ def test_workspace_bytes_covers_the_benchmarks_moment_unit_call():
             assert 0 < need <= lib.smin_workspace_bytes(N, B, 4, D, 4, 1), (B, L, N)
 
 
+def test_call_ws_names_a_rejecting_query_before_it_allocates(monkeypatch):
+    """_lib.call_ws: a size query that returns 0 has refused its arguments; the error names the query and the arguments, and neither a
+    workspace nor the entry point is reached (the query is host code: no device needed)."""
+    import models
+    L_ = models.vml_amd._lib
+
+    def no_allocation(*a, **kw):
+        raise AssertionError("call_ws allocated a workspace for rejected arguments")
+    monkeypatch.setattr(torch, "empty", no_allocation)
+    with pytest.raises(L_.SminHipError, match=r"smin_top_moments_ws_bytes.*\(0, 4, 1\)"):
+        L_.call_ws("smin_top_moments", (0, 4, 1))
+    with pytest.raises(L_.SminHipError, match=r"smin_top_moments_ws_bytes rejected B=0, L=4, k=1"):  # the arguments by the caller's names
+        L_.call_ws("smin_top_moments", (0, 4, 1), fields="B, L, k")
+    with pytest.raises(L_.SminHipError, match=r"smin_epoch_meter_ws_bytes.*\(2, 8, 7, 5, 2, 4\)"):   # a query named apart from the entry point
+        L_.call_ws("smin_epoch_meter_update", (2, 8, 7, 5, 2, 4), query="smin_epoch_meter_ws_bytes")
+
+
 def test_torch_extension_registers_operators():
     """csrc/torch_binding.cpp: TORCH_LIBRARY(smin_hip) loads without a GPU, exposes the two operators with the documented
     schemas, and refuses CPU tensors (no CPU fallback behind the extension either) -- called with SMIN's own options, which

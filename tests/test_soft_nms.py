@@ -23,6 +23,7 @@ from tests.support.compare import same_tensor as same
 from tests.support.device import dev  # noqa: F401  (the module's device fixture)
 from tests.support.device import vml as V
 from tests.support.guards import BAND, WORD_SENTINEL, bands_intact, banded
+from tests.support.references import merge_frame_edges
 
 LDS_CELLS, BAND_CELLS, MAX_BANDS = 12288, 4096, 32      # csrc/soft_nms.hip
 U = 2.0 ** -24                                           # half an ulp of fp32, relative: one correctly rounded operation
@@ -595,6 +596,19 @@ def test_span_form_equals_its_restatement(dev):
     assert sorted(hard) == ["cell", "count", "score", "span", "window"]
     for key in hard:
         assert same(hard[key], api.merge_window_moments(*on(dev, cand), WT, WL, k=6, nms_thresh=0.5, nms="hard")[key]), key
+
+
+@pytest.mark.gpu
+def test_span_form_at_the_frame_edges(dev):
+    """The hard merge's frame-edge case (test_window_localize) under the linear rule: pair_ptr outside [0, G], a pair without a window,
+    a window without a moment, tied scores and a -0.0.  Every field bit for bit, the NaN of the empty spans included."""
+    api = V()
+    cand = merge_frame_edges()
+    got = api.merge_window_moments(*on(dev, cand), 8, 8, k=3, nms_thresh=0.5, nms="linear")
+    want = api.merge_window_moments_torch(*cand, 8, 8, k=3, nms_thresh=0.5, nms="linear")
+    for key in MERGE_KEYS:
+        assert same(got[key].cpu(), want[key]), key
+    assert want["count"].tolist() == [2, 0, 3] and torch.equal(want["span"][1].view(torch.int32), torch.full((3, 2), 0x7FC00000, dtype=torch.int32))
 
 
 @pytest.mark.gpu

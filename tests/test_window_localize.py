@@ -14,6 +14,7 @@ from tests import helpers as H
 from tests.support.device import dev  # noqa: F401  (the module's device fixture)
 from tests.support.device import vml as V
 from tests.support.compare import layout_ok, same_tensor as same
+from tests.support.references import merge_frame_edges
 
 
 def same_merge(got, want):
@@ -254,14 +255,22 @@ def test_sample_windows_bit_exact(dev, Din, T, mode):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("G,kw,B,k,thr,seed", [(64, 5, 8, 1, 0.5, 0), (64, 5, 8, 64, 0.5, 1), (200, 16, 9, 10, 0.3, 2),
-                                               (90, 8, 12, 5, 1.0, 3), (0, 4, 3, 5, 0.5, 4)])
+                                               (90, 8, 12, 5, 1.0, 3), (0, 4, 3, 5, 0.5, 4), (4, 2, 3, 3, 0.5, "frame edges")])
 def test_merge_on_device_equals_torch(dev, G, kw, B, k, thr, seed):
     M = V().moments
-    T, L = 64, 16
-    args = rand_candidates(G, kw, B, T, L, seed)
-    args[5][1] = args[5][0]                                                # pair 0 has zero windows
+    if seed == "frame edges":                                              # pair_ptr outside [0, G], a pair and a window with nothing
+        T, L = 8, 8
+        args = list(merge_frame_edges())
+        assert tuple(args[0].shape) == (G, kw, 2) and args[5].shape[0] == B + 1
+    else:
+        T, L = 64, 16
+        args = rand_candidates(G, kw, B, T, L, seed)
+        args[5][1] = args[5][0]                                            # pair 0 has zero windows
     got = M.merge_window_moments(*[a.to(dev) for a in args], T, L, k=k, nms_thresh=thr)
-    same_merge(got, M.merge_window_moments_torch(*args, T, L, k=k, nms_thresh=thr))
+    want = M.merge_window_moments_torch(*args, T, L, k=k, nms_thresh=thr)
+    same_merge(got, want)                                                  # bit for bit, the NaN of the empty spans included
+    if seed == "frame edges":
+        assert want["count"].tolist() == [2, 0, 2] and torch.equal(want["span"][1].view(torch.int32), torch.full((3, 2), 0x7FC00000, dtype=torch.int32))
 
 
 @pytest.mark.gpu

@@ -152,6 +152,19 @@ def call(name, *args):
     check(getattr(load(), name)(*args), name)
 
 
+def call_ws(name, size_args, *args, query=None, fields=None):
+    """``call(name, *args, ws, ws_bytes)`` with a fresh workspace on the current device, sized by the entry point's own query
+    (``name + "_ws_bytes"`` unless ``query`` names another) at ``size_args``.  A size of 0 is the query's refusal of its arguments:
+    the error names the query and the arguments, by ``fields`` ("B, L, k") where the caller gives their names."""
+    query = query or name + "_ws_bytes"
+    nbytes = getattr(load(), query)(*size_args)
+    if nbytes == 0:
+        named = ", ".join(f"{f}={v}" for f, v in zip(fields.split(", "), size_args)) if fields else tuple(size_args)
+        raise SminHipError(f"{query} rejected {named}")
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device="cuda")
+    call(name, *args, ptr(ws), nbytes)
+
+
 PROF_TAGS = {1: "moment_fwd", 2: "moment_dx", 3: "moment_dw", 4: "attn_fwd", 5: "attn_bwd"}
 
 

@@ -33,13 +33,10 @@ int device_cus();
 int lds_optin(const void* kernel, size_t bytes);
 // score_map.hip: the three boundary heads of f_b [B][L][D] into psea [3][B][L], and the dense score map pm [B][L][L] cleared
 int launch_score_heads(hipStream_t st, const float* fb, int B, int L, int D, const float* wb, const float* bb, const float* lmask, float* psea, float* pm);
-// moments.hip: the per-sample stage of the NMS metric (top-k with greedy NMS, then the hit flags [B][nn * nm] at *hits_out inside ws;
-// top1 [B], if given, gets sm at each sample's first kept cell, 0 if none) and its scratch size (0 = arguments rejected)
-size_t nms_hits_stage_bytes(int B, int L, int k, int nn, int nm);
-int nms_hits_stage(hipStream_t st, const float* pm, const float* ps, const float* pe, const uint8_t* mm, const float* sm, int B, int L, int k,
-                   float nms_thresh, const int* n_list, int nn, const float* m_list, int nm, void* ws, float** hits_out, float* top1);
-// the same stage under a selection rule: method 0 = greedy hard NMS (thr only), SMIN_NMS_LINEAR / SMIN_NMS_GAUSSIAN = Soft-NMS
-// (soft_nms.hip: decayed top-k; min_score = -inf never stops early)
+// moments.hip: the per-sample stage of the NMS metric (top-k under a selection rule, then the hit flags [B][nn * nm] at *hits_out inside
+// ws; top1 [B], if given, gets sm at each sample's first kept cell, 0 if none) and its scratch size (0 = arguments rejected).
+// The rule: method 0 = greedy hard NMS (thr only), SMIN_NMS_LINEAR / SMIN_NMS_GAUSSIAN = Soft-NMS (soft_nms.hip: decayed top-k;
+// min_score = -inf never stops early)
 struct NmsRule { int method; float thr, sigma, min_score; };
 size_t rule_hits_stage_bytes(int method, int B, int L, int k, int nn, int nm);
 int rule_hits_stage(hipStream_t st, const float* pm, const float* ps, const float* pe, const uint8_t* mm, const float* sm, int B, int L, int k,

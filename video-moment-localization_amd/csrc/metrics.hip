@@ -225,12 +225,30 @@ extern "C" int smin_compute_ious(void* stream, const float* pm, const float* ps,
     return 0;
 }
 
+// the meter's rule 1 under a selection rule (hard or soft): the per-sample stage of moments.hip with the top-1 IoU [B] behind its
+// scratch, then the closing wave
+static size_t meter_stage_ws_bytes(int method, int B, int L, int k, int nn, int nm)
+{
+    const size_t stage = rule_hits_stage_bytes(method, B, L, k, nn, nm);
+    return stage ? stage + align256((size_t)B * sizeof(float)) : 0;
+}
+
+static int meter_stage_update(hipStream_t st, const float* pm, const float* ps, const float* pe, const uint8_t* mm, const float* sm, int B, int L, int k,
+                              const NmsRule& rule, const int* n_list, int nn, const float* m_list, int nm, const float* loss, double* acc, void* ws)
+{
+    float* hits = nullptr;
+    float* top1 = (float*)((char*)ws + rule_hits_stage_bytes(rule.method, B, L, k, nn, nm));
+    const int rc = rule_hits_stage(st, pm, ps, pe, mm, sm, B, L, k, rule, n_list, nn, m_list, nm, ws, &hits, top1);
+    if (rc) return rc;
+    hipLaunchKernelGGL(meter_close_kernel, dim3(1), dim3(64), 0, st, hits, top1, B, nn * nm, loss, acc);
+    SMIN_LAUNCH_CHECK();
+    return 0;
+}
+
 extern "C" size_t smin_epoch_meter_ws_bytes(int B, int L, int rule, int k, int nn, int nm)
 {
     if (rule == 0) return rule0_shape_ok(B, L, k, nn, nm) ? align256((size_t)B * 8 * sizeof(float)) + align256((size_t)B * sizeof(float)) : 0;
-    if (rule != 1) return 0;
-    const size_t stage = nms_hits_stage_bytes(B, L, k, nn, nm);
-    return stage ? stage + align256((size_t)B * sizeof(float)) : 0;
+    return rule == 1 ? meter_stage_ws_bytes(0, B, L, k, nn, nm) : 0;
 }
 
 extern "C" int smin_epoch_meter_update(void* stream, const float* pm, const float* ps, const float* pe, const uint8_t* mm, const float* sm,
@@ -242,49 +260,34 @@ extern "C" int smin_epoch_meter_update(void* stream, const float* pm, const floa
     SMIN_REQUIRE(n_list != nullptr && m_list != nullptr && acc != nullptr && ws != nullptr);
     const size_t need = smin_epoch_meter_ws_bytes(B, L, rule, k, nn, nm);
     SMIN_REQUIRE(need != 0 && ws_bytes >= need);
-    float* hits = nullptr;
-    float* top1 = nullptr;
-    if (rule == 0) {
-        SMIN_REQUIRE(n_list[0] == 1 && n_list[1] == 5 && m_list[0] == 0.1f && m_list[1] == 0.3f && m_list[2] == 0.5f && m_list[3] == 0.7f);
-        hits = (float*)ws;
-        top1 = (float*)((char*)ws + align256((size_t)B * 8 * sizeof(float)));
-        hipLaunchKernelGGL(ious_kernel, dim3(B), dim3(256), 0, st, pm, ps, pe, mm, sm, L, hits, top1);
-        SMIN_LAUNCH_CHECK();
-    } else {
-        top1 = (float*)((char*)ws + nms_hits_stage_bytes(B, L, k, nn, nm));
-        const int rc = nms_hits_stage(st, pm, ps, pe, mm, sm, B, L, k, nms_thresh, n_list, nn, m_list, nm, ws, &hits, top1);
-        if (rc) return rc;
-    }
+    if (rule == 1) return meter_stage_update(st, pm, ps, pe, mm, sm, B, L, k, NmsRule{0, nms_thresh, 0.f, 0.f}, n_list, nn, m_list, nm, loss, acc, ws);
+    SMIN_REQUIRE(n_list[0] == 1 && n_list[1] == 5 && m_list[0] == 0.1f && m_list[1] == 0.3f && m_list[2] == 0.5f && m_list[3] == 0.7f);
+    float* hits = (float*)ws;
+    float* top1 = (float*)((char*)ws + align256((size_t)B * 8 * sizeof(float)));
+    hipLaunchKernelGGL(ious_kernel, dim3(B), dim3(256), 0, st, pm, ps, pe, mm, sm, L, hits, top1);
+    SMIN_LAUNCH_CHECK();
     hipLaunchKernelGGL(meter_close_kernel, dim3(1), dim3(64), 0, st, hits, top1, B, nn * nm, loss, acc);
     SMIN_LAUNCH_CHECK();
     return 0;
 }
 
-// the meter's rule 1 with a Soft-NMS selection (soft_nms.hip) in place of the greedy hard NMS: the same stage, the same closing wave
+// the meter's rule 1 with a Soft-NMS selection (soft_nms.hip) in place of the greedy hard NMS
 extern "C" size_t smin_epoch_meter_soft_ws_bytes(int B, int L, int k, int nn, int nm)
 {
-    const size_t stage = rule_hits_stage_bytes(SMIN_NMS_LINEAR, B, L, k, nn, nm);
-    return stage ? stage + align256((size_t)B * sizeof(float)) : 0;
+    return meter_stage_ws_bytes(SMIN_NMS_LINEAR, B, L, k, nn, nm);      // both soft rules carve the same scratch
 }
 
 extern "C" int smin_epoch_meter_update_soft(void* stream, const float* pm, const float* ps, const float* pe, const uint8_t* mm, const float* sm,
                                             int B, int L, int k, int method, float nms_thresh, float sigma, const int* n_list, int nn,
                                             const float* m_list, int nm, const float* loss, double* acc, void* ws, size_t ws_bytes)
 {
-    hipStream_t st = (hipStream_t)stream;
     const NmsRule rule{method, nms_thresh, sigma, -__builtin_inff()};
     SMIN_REQUIRE(soft_rule_ok(rule));
     SMIN_REQUIRE(pm != nullptr && ps != nullptr && pe != nullptr && mm != nullptr && sm != nullptr);
     SMIN_REQUIRE(n_list != nullptr && m_list != nullptr && acc != nullptr && ws != nullptr);
     const size_t need = smin_epoch_meter_soft_ws_bytes(B, L, k, nn, nm);
     SMIN_REQUIRE(need != 0 && ws_bytes >= need);
-    float* hits = nullptr;
-    float* top1 = (float*)((char*)ws + rule_hits_stage_bytes(method, B, L, k, nn, nm));
-    const int rc = rule_hits_stage(st, pm, ps, pe, mm, sm, B, L, k, rule, n_list, nn, m_list, nm, ws, &hits, top1);
-    if (rc) return rc;
-    hipLaunchKernelGGL(meter_close_kernel, dim3(1), dim3(64), 0, st, hits, top1, B, nn * nm, loss, acc);
-    SMIN_LAUNCH_CHECK();
-    return 0;
+    return meter_stage_update((hipStream_t)stream, pm, ps, pe, mm, sm, B, L, k, rule, n_list, nn, m_list, nm, loss, acc, ws);
 }
 
 extern "C" int smin_span_ious(void* stream, const float* span, const int32_t* count, const float* gt, int B, int k, float* iou)

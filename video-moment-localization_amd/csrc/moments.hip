@@ -221,8 +221,7 @@ __device__ void nms_block(NmsLds& s, const u64* a, int nc, int L, int k, float t
         bool sup = !valid;
         for (int r = 0; r < nk; ++r) {                           // wave-uniform trip count: readlane of the kept cells
             const int i2 = __builtin_amdgcn_readlane(ki, r), j2 = __builtin_amdgcn_readlane(kj, r);
-            const int inter = max(0, min(j, j2) + 1 - max(i, i2)), uni = max(j, j2) + 1 - min(i, i2);
-            sup = sup || (float)inter / (float)uni > thr;
+            sup = sup || cell_iou(i, j, i2, j2) > thr;
         }
         u64 alive = __ballot(!sup);
         while (alive && nk < k) {
@@ -231,8 +230,7 @@ __device__ void nms_block(NmsLds& s, const u64* a, int nc, int L, int k, float t
             const u64 fk = __shfl(key, f);
             if (lane == nk) { ki = fi; kj = fj; kk = fk; }
             ++nk;
-            const int inter = max(0, min(j, fj) + 1 - max(i, fi)), uni = max(j, fj) + 1 - min(i, fi);
-            const bool kill = lane > f && (float)inter / (float)uni > thr;
+            const bool kill = lane > f && cell_iou(i, j, fi, fj) > thr;
             alive &= ~__ballot(kill);
             alive &= ~(1ull << f);
         }
@@ -339,8 +337,6 @@ int band_count(int B, int L)
     return (int)std::max<long long>(P, 1);
 }
 
-size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 struct WsLayout { int P, MB; size_t keys, kappa, cnt, total; };
 
 WsLayout ws_layout(int B, int L)
@@ -349,14 +345,11 @@ WsLayout ws_layout(int B, int L)
     w.P = band_count(B, L);
     w.MB = CAND / w.P;
     w.keys = 0;
-    w.kappa = align256((size_t)B * w.P * w.MB * sizeof(u64));
-    w.cnt = w.kappa + align256((size_t)B * w.P * sizeof(u64));
-    w.total = w.cnt + align256((size_t)B * w.P * sizeof(int));
+    w.kappa = moment_align256((size_t)B * w.P * w.MB * sizeof(u64));
+    w.cnt = w.kappa + moment_align256((size_t)B * w.P * sizeof(u64));
+    w.total = w.cnt + moment_align256((size_t)B * w.P * sizeof(int));
     return w;
 }
-
-// 1 <= B <= 65535 (the band select puts the sample in the grid's second dimension), L*L < 2^31, 1 <= k <= 64: moment_cells.h
-bool args_ok(int B, int L, int k) { return moment_args_ok(B, L, k); }
 
 int launch_top(hipStream_t st, const float* pm, const float* ps, const float* pe, const uint8_t* mm, int B, int L, int k, float thr,
                long long* idx, float* score, int* count, char* ws)
@@ -379,65 +372,38 @@ int launch_top(hipStream_t st, const float* pm, const float* ps, const float* pe
 
 __device__ __forceinline__ bool span_suppressed(float st, float en, const float* kst, const float* ken, int nk, float thr)
 {
-    for (int r = 0; r < nk; ++r) {
-        const float inter = fmaxf(0.f, fminf(en, ken[r]) - fmaxf(st, kst[r]));
-        const float uni = fmaxf(en, ken[r]) - fminf(st, kst[r]);
-        if (inter / uni > thr) return true;
-    }
+    for (int r = 0; r < nk; ++r)
+        if (span_iou(st, en, kst[r], ken[r]) > thr) return true;
     return false;
 }
 
 __global__ __launch_bounds__(MT)
-void merge_windows_kernel(MergeIn in, const long long* __restrict__ pair_ptr, int k, float thr,
-                          float* __restrict__ span /* [B][k][2] */, float* __restrict__ out_score /* [B][k] */,
-                          long long* __restrict__ window /* [B][k] */, long long* __restrict__ cell /* [B][k][2] */, int* __restrict__ out_count)
+void merge_windows_kernel(MergeIn in, const long long* __restrict__ pair_ptr, int k, float thr, MergeOut out)
 {
     __shared__ float kst[MAX_K], ken[MAX_K];
     __shared__ u64 red[MT / 64];
-    const int b = blockIdx.x, t = threadIdx.x, kw = in.kw;
-    const long long g0 = min(max(pair_ptr[b], 0LL), (long long)in.G);
-    const long long g1 = min(max(pair_ptr[b + 1], g0), (long long)in.G);
-    const int nslot = (int)(g1 - g0) * kw;                       // candidate q = window ordinal * kw + slot (< 2^31: checked on the host)
+    const int b = blockIdx.x, t = threadIdx.x;
+    const MergePair pr = merge_pair(in, pair_ptr, b);
     u64 cursor = ~0ull;
     int nk = 0;
     for (; nk < k; ++nk) {
         u64 best = 0;
-        for (int q = t; q < nslot; q += MT) {
-            const int w = q / kw, slot = q - w * kw;
-            const long long g = g0 + w;
-            if (slot >= in.count[g]) continue;
-            const u64 key = make_key(score_ord(in.score[g * kw + slot]), q);
+        for (int q = t; q < pr.nslot; q += MT) {
+            const MergeCand x = merge_cand(in, pr.g0, q);
+            if (x.slot >= in.count[x.g]) continue;
+            const u64 key = make_key(score_ord(in.score[x.c]), q);
             if (key >= cursor || key <= best) continue;
             float st, en;
-            window_span(in, (int)g, in.idx[2 * (g * kw + slot)], in.idx[2 * (g * kw + slot) + 1], st, en);
+            cand_span(in, x, st, en);
             if (!span_suppressed(st, en, kst, ken, nk, thr)) best = key;
         }
         best = block_max(best, red);
         if (best == 0) break;                                    // every candidate is taken or suppressed
         cursor = best;
-        if (t == 0) {
-            const int q = key_cell(best), w = q / kw, slot = q - w * kw;
-            const long long g = g0 + w, c = g * kw + slot;
-            const long long i = in.idx[2 * c], j = in.idx[2 * c + 1];
-            float st, en;
-            window_span(in, (int)g, i, j, st, en);
-            kst[nk] = st; ken[nk] = en;
-            const size_t o = (size_t)b * k + nk;
-            span[2 * o] = st; span[2 * o + 1] = en;
-            out_score[o] = in.score[c];
-            window[o] = w;
-            cell[2 * o] = i; cell[2 * o + 1] = j;
-        }
+        if (t == 0) merge_record(in, out, pr.g0, key_cell(best), (size_t)b * k + nk, 0.f, kst[nk], ken[nk]);
         __syncthreads();
     }
-    for (int r = nk + t; r < k; r += MT) {
-        const size_t o = (size_t)b * k + r;
-        span[2 * o] = span[2 * o + 1] = __int_as_float(0x7fc00000);
-        out_score[o] = 0.f;
-        window[o] = -1;
-        cell[2 * o] = cell[2 * o + 1] = -1;
-    }
-    if (t == 0) out_count[b] = nk;
+    merge_finish(out, b, k, nk);
 }
 
 }  // namespace
@@ -447,14 +413,14 @@ using namespace smin;
 
 extern "C" size_t smin_top_moments_ws_bytes(int B, int L, int k)
 {
-    if (!args_ok(B, L, k)) return 0;
+    if (!moment_args_ok(B, L, k)) return 0;
     return ws_layout(B, L).total;
 }
 
 extern "C" int smin_top_moments(void* stream, const float* pm, const float* ps, const float* pe, const uint8_t* mm, int B, int L, int k,
                                 float nms_thresh, long long* idx, float* score, int* count, void* ws, size_t ws_bytes)
 {
-    SMIN_REQUIRE(args_ok(B, L, k));
+    SMIN_REQUIRE(moment_args_ok(B, L, k));
     SMIN_REQUIRE(ws != nullptr && ws_bytes >= ws_layout(B, L).total);
     return launch_top((hipStream_t)stream, pm, ps, pe, mm, B, L, k, nms_thresh, idx, score, count, (char*)ws);
 }
@@ -466,27 +432,28 @@ static size_t select_ws_bytes(int method, int B, int L) { return method == 0 ? w
 
 size_t smin::rule_hits_stage_bytes(int method, int B, int L, int k, int nn, int nm)
 {
-    if (!args_ok(B, L, k) || nn < 1 || nn > MAX_N || nm < 1 || nm > MAX_M || method < 0 || method > 2) return 0;
+    if (!moment_args_ok(B, L, k) || nn < 1 || nn > MAX_N || nm < 1 || nm > MAX_M || method < 0 || method > 2) return 0;
     const size_t npairs = (size_t)nn * nm;
-    const size_t top = align256((size_t)B * k * 2 * sizeof(long long)) + align256((size_t)B * k * sizeof(float)) + align256((size_t)B * sizeof(int));
-    const size_t raw = method == 0 ? 0 : align256((size_t)B * k * sizeof(float));
-    return select_ws_bytes(method, B, L) + top + raw + align256((size_t)B * npairs * sizeof(float));
+    const size_t top = moment_align256((size_t)B * k * 2 * sizeof(long long)) + moment_align256((size_t)B * k * sizeof(float)) +
+                       moment_align256((size_t)B * sizeof(int));
+    const size_t raw = method == 0 ? 0 : moment_align256((size_t)B * k * sizeof(float));
+    return select_ws_bytes(method, B, L) + top + raw + moment_align256((size_t)B * npairs * sizeof(float));
 }
 
 int smin::rule_hits_stage(hipStream_t st, const float* pm, const float* ps, const float* pe, const uint8_t* mm, const float* sm, int B, int L, int k,
                           const NmsRule& rule, const int* n_list, int nn, const float* m_list, int nm, void* ws, float** hits_out, float* top1)
 {
-    SMIN_REQUIRE(args_ok(B, L, k) && nn >= 1 && nn <= MAX_N && nm >= 1 && nm <= MAX_M && n_list && m_list);
+    SMIN_REQUIRE(moment_args_ok(B, L, k) && nn >= 1 && nn <= MAX_N && nm >= 1 && nm <= MAX_M && n_list && m_list);
     SMIN_REQUIRE(rule.method == 0 || soft_rule_ok(rule));
     Pairs pr{};
     pr.nn = nn; pr.nm = nm;
     for (int a = 0; a < nn; ++a) { SMIN_REQUIRE(n_list[a] >= 1 && n_list[a] <= k); pr.n[a] = n_list[a]; }
     for (int c = 0; c < nm; ++c) pr.m[c] = m_list[c];
     char* p = (char*)ws + select_ws_bytes(rule.method, B, L);
-    long long* idx = (long long*)p;   p += align256((size_t)B * k * 2 * sizeof(long long));
-    float* score = (float*)p;         p += align256((size_t)B * k * sizeof(float));
-    int* count = (int*)p;             p += align256((size_t)B * sizeof(int));
-    float* raw = (float*)p;           p += rule.method == 0 ? 0 : align256((size_t)B * k * sizeof(float));
+    long long* idx = (long long*)p;   p += moment_align256((size_t)B * k * 2 * sizeof(long long));
+    float* score = (float*)p;         p += moment_align256((size_t)B * k * sizeof(float));
+    int* count = (int*)p;             p += moment_align256((size_t)B * sizeof(int));
+    float* raw = (float*)p;           p += rule.method == 0 ? 0 : moment_align256((size_t)B * k * sizeof(float));
     float* hits = (float*)p;
     const int rc = rule.method == 0 ? launch_top(st, pm, ps, pe, mm, B, L, k, rule.thr, idx, score, count, (char*)ws)
                                     : soft_top_launch(st, pm, ps, pe, mm, B, L, k, rule, idx, score, raw, count, (char*)ws);
@@ -495,14 +462,6 @@ int smin::rule_hits_stage(hipStream_t st, const float* pm, const float* ps, cons
     SMIN_LAUNCH_CHECK();
     *hits_out = hits;
     return 0;
-}
-
-size_t smin::nms_hits_stage_bytes(int B, int L, int k, int nn, int nm) { return rule_hits_stage_bytes(0, B, L, k, nn, nm); }
-
-int smin::nms_hits_stage(hipStream_t st, const float* pm, const float* ps, const float* pe, const uint8_t* mm, const float* sm, int B, int L, int k,
-                         float nms_thresh, const int* n_list, int nn, const float* m_list, int nm, void* ws, float** hits_out, float* top1)
-{
-    return rule_hits_stage(st, pm, ps, pe, mm, sm, B, L, k, NmsRule{0, nms_thresh, 0.f, 0.f}, n_list, nn, m_list, nm, ws, hits_out, top1);
 }
 
 // R@n, IoU=m over the moments a rule keeps: the stage above, then the samples summed in order
@@ -520,14 +479,14 @@ static int launch_ious(hipStream_t st, const float* pm, const float* ps, const f
 
 extern "C" size_t smin_compute_ious_nms_ws_bytes(int B, int L, int k, int nn, int nm)
 {
-    return nms_hits_stage_bytes(B, L, k, nn, nm);
+    return rule_hits_stage_bytes(0, B, L, k, nn, nm);
 }
 
 extern "C" int smin_compute_ious_nms(void* stream, const float* pm, const float* ps, const float* pe, const uint8_t* mm, const float* sm,
                                      int B, int L, int k, float nms_thresh, const int* n_list, int nn, const float* m_list, int nm,
                                      float* counts, void* ws, size_t ws_bytes)
 {
-    SMIN_REQUIRE(args_ok(B, L, k) && nn >= 1 && nn <= MAX_N && nm >= 1 && nm <= MAX_M && n_list && m_list);
+    SMIN_REQUIRE(moment_args_ok(B, L, k) && nn >= 1 && nn <= MAX_N && nm >= 1 && nm <= MAX_M && n_list && m_list);
     SMIN_REQUIRE(ws != nullptr && ws_bytes >= smin_compute_ious_nms_ws_bytes(B, L, k, nn, nm));
     return launch_ious((hipStream_t)stream, pm, ps, pe, mm, sm, B, L, k, NmsRule{0, nms_thresh, 0.f, 0.f}, n_list, nn, m_list, nm, counts, ws);
 }
@@ -543,7 +502,7 @@ extern "C" int smin_compute_ious_soft(void* stream, const float* pm, const float
 {
     const NmsRule rule{method, nms_thresh, sigma, -__builtin_inff()};
     SMIN_REQUIRE(soft_rule_ok(rule));
-    SMIN_REQUIRE(args_ok(B, L, k) && nn >= 1 && nn <= MAX_N && nm >= 1 && nm <= MAX_M && n_list && m_list);
+    SMIN_REQUIRE(moment_args_ok(B, L, k) && nn >= 1 && nn <= MAX_N && nm >= 1 && nm <= MAX_M && n_list && m_list);
     SMIN_REQUIRE(pm && ps && pe && mm && sm && counts);
     SMIN_REQUIRE(ws != nullptr && ws_bytes >= smin_compute_ious_soft_ws_bytes(B, L, k, nn, nm));
     return launch_ious((hipStream_t)stream, pm, ps, pe, mm, sm, B, L, k, rule, n_list, nn, m_list, nm, counts, ws);
@@ -553,14 +512,11 @@ extern "C" int smin_merge_window_moments(void* stream, const int64_t* idx, const
                                          const int32_t* len, const int64_t* pair_ptr, int G, int B, int T, int L, int k_window, int k,
                                          float nms_thresh, float* span, float* out_score, int64_t* window, int64_t* cell, int32_t* out_count)
 {
-    SMIN_REQUIRE(k >= 1 && k <= MAX_K && k_window >= 1 && k_window <= MAX_K && G >= 0 && B >= 0 && T >= 1 && L >= 1);
-    SMIN_REQUIRE((long long)G * k_window < 0x7fffffffLL);
-    if (B == 0) return 0;
-    SMIN_REQUIRE(pair_ptr != nullptr && span != nullptr && out_score != nullptr && window != nullptr && cell != nullptr && out_count != nullptr);
-    SMIN_REQUIRE(G == 0 || (idx != nullptr && score != nullptr && count != nullptr && start != nullptr && len != nullptr));
     const MergeIn in{(const long long*)idx, score, count, (const long long*)start, len, G, T, L, k_window};
-    hipLaunchKernelGGL(merge_windows_kernel, dim3(B), dim3(MT), 0, (hipStream_t)stream, in, (const long long*)pair_ptr, k, nms_thresh, span,
-                       out_score, (long long*)window, (long long*)cell, out_count);
+    const MergeOut out{span, out_score, nullptr, (long long*)window, (long long*)cell, out_count};
+    SMIN_REQUIRE(merge_args_ok(in, pair_ptr, B, k, out));
+    if (B == 0) return 0;
+    hipLaunchKernelGGL(merge_windows_kernel, dim3(B), dim3(MT), 0, (hipStream_t)stream, in, (const long long*)pair_ptr, k, nms_thresh, out);
     SMIN_LAUNCH_CHECK();
     return 0;
 }

@@ -207,30 +207,24 @@ WsLayout ws_layout(int B, int L)
 
 // ---- span form: the candidates, spans and span IoU of merge_windows_kernel (moment_cells.h), the soft rule in place of the threshold
 __global__ __launch_bounds__(MT)
-void soft_merge_windows_kernel(MergeIn in, const long long* __restrict__ pair_ptr, int k, NmsRule rule,
-                               float* __restrict__ span /* [B][k][2] */, float* __restrict__ out_score /* [B][k] */,
-                               float* __restrict__ raw_score /* [B][k] */, long long* __restrict__ window /* [B][k] */,
-                               long long* __restrict__ cell /* [B][k][2] */, int* __restrict__ out_count)
+void soft_merge_windows_kernel(MergeIn in, const long long* __restrict__ pair_ptr, int k, NmsRule rule, MergeOut out)
 {
     __shared__ float kst[MAX_K], ken[MAX_K];
     __shared__ int kq[MAX_K];
     __shared__ float pick_cur;
     __shared__ u64 red[MT / 64];
-    const int b = blockIdx.x, t = threadIdx.x, kw = in.kw;
-    const long long g0 = min(max(pair_ptr[b], 0LL), (long long)in.G);
-    const long long g1 = min(max(pair_ptr[b + 1], g0), (long long)in.G);
-    const int nslot = (int)(g1 - g0) * kw;                       // candidate q = window ordinal * kw + slot (< 2^31: checked on the host)
+    const int b = blockIdx.x, t = threadIdx.x;
+    const MergePair pr = merge_pair(in, pair_ptr, b);
     int nk = 0;
     for (; nk < k; ++nk) {
         u64 best = 0;
         float best_cur = 0.f;
-        for (int q = t; q < nslot; q += MT) {
-            const int w = q / kw, slot = q - w * kw;
-            const long long g = g0 + w;
-            if (slot >= in.count[g]) continue;
+        for (int q = t; q < pr.nslot; q += MT) {
+            const MergeCand x = merge_cand(in, pr.g0, q);
+            if (x.slot >= in.count[x.g]) continue;
             float st, en;
-            window_span(in, (int)g, in.idx[2 * (g * kw + slot)], in.idx[2 * (g * kw + slot) + 1], st, en);
-            float cur = in.score[g * kw + slot];
+            cand_span(in, x, st, en);
+            float cur = in.score[x.c];
             bool taken = false;
             for (int r = 0; r < nk; ++r) {                       // the decays in pick order
                 taken = taken || kq[r] == q;
@@ -247,30 +241,12 @@ void soft_merge_windows_kernel(MergeIn in, const long long* __restrict__ pair_pt
         const float v = pick_cur;
         if (v < rule.min_score) break;
         if (t == 0) {
-            const int q = key_cell(top), w = q / kw, slot = q - w * kw;
-            const long long g = g0 + w, c = g * kw + slot;
-            const long long i = in.idx[2 * c], j = in.idx[2 * c + 1];
-            float st, en;
-            window_span(in, (int)g, i, j, st, en);
-            kst[nk] = st; ken[nk] = en; kq[nk] = q;
-            const size_t o = (size_t)b * k + nk;
-            span[2 * o] = st; span[2 * o + 1] = en;
-            out_score[o] = v;
-            raw_score[o] = in.score[c];
-            window[o] = w;
-            cell[2 * o] = i; cell[2 * o + 1] = j;
+            kq[nk] = key_cell(top);
+            merge_record(in, out, pr.g0, kq[nk], (size_t)b * k + nk, v, kst[nk], ken[nk]);
         }
         __syncthreads();
     }
-    for (int r = nk + t; r < k; r += MT) {
-        const size_t o = (size_t)b * k + r;
-        span[2 * o] = span[2 * o + 1] = __int_as_float(0x7fc00000);
-        out_score[o] = 0.f;
-        raw_score[o] = 0.f;
-        window[o] = -1;
-        cell[2 * o] = cell[2 * o + 1] = -1;
-    }
-    if (t == 0) out_count[b] = nk;
+    merge_finish(out, b, k, nk);
 }
 
 }  // namespace
@@ -335,15 +311,11 @@ extern "C" int smin_merge_window_moments_soft(void* stream, const int64_t* idx, 
 {
     const NmsRule rule{method, nms_thresh, sigma, min_score};
     SMIN_REQUIRE(soft_rule_ok(rule));
-    SMIN_REQUIRE(k >= 1 && k <= MAX_K && k_window >= 1 && k_window <= MAX_K && G >= 0 && B >= 0 && T >= 1 && L >= 1);
-    SMIN_REQUIRE((long long)G * k_window < 0x7fffffffLL);
-    if (B == 0) return 0;
-    SMIN_REQUIRE(pair_ptr != nullptr && span != nullptr && out_score != nullptr && raw_score != nullptr && window != nullptr && cell != nullptr &&
-                 out_count != nullptr);
-    SMIN_REQUIRE(G == 0 || (idx != nullptr && score != nullptr && count != nullptr && start != nullptr && len != nullptr));
     const MergeIn in{(const long long*)idx, score, count, (const long long*)start, len, G, T, L, k_window};
-    hipLaunchKernelGGL(soft_merge_windows_kernel, dim3(B), dim3(MT), 0, (hipStream_t)stream, in, (const long long*)pair_ptr, k, rule, span,
-                       out_score, raw_score, (long long*)window, (long long*)cell, out_count);
+    const MergeOut out{span, out_score, raw_score, (long long*)window, (long long*)cell, out_count};
+    SMIN_REQUIRE(merge_args_ok(in, pair_ptr, B, k, out) && (B == 0 || raw_score != nullptr));
+    if (B == 0) return 0;
+    hipLaunchKernelGGL(soft_merge_windows_kernel, dim3(B), dim3(MT), 0, (hipStream_t)stream, in, (const long long*)pair_ptr, k, rule, out);
     SMIN_LAUNCH_CHECK();
     return 0;
 }

@@ -30,7 +30,7 @@ import ctypes
 import torch
 
 from ._host import byte_mask
-from .moments import MAX_K, _check, _mul32, _nm_check, _span_check, _span_meter_call, _sqrt32, _valid_slots, span_ious_torch
+from .moments import MAX_K, _check, _fused, _mul32, _nm_check, _span_check, _span_meter_call, _valid_slots, span_ious_torch
 
 _REF_N, _REF_M = (1, 5), (0.1, 0.3, 0.5, 0.7)
 
@@ -132,7 +132,7 @@ class EpochMeter(_Meter):
         return "cuda"
 
     def update(self, pm, ps, pe, moment_mask, sm, loss=None):
-        from ._lib import SminHipError, call, load, ptr, stream
+        from ._lib import SminHipError, call_ws, ptr, stream
         for t in (pm, ps, pe, moment_mask, sm) + (() if loss is None else (loss,)):
             if not t.is_cuda:
                 raise SminHipError("EpochMeter.update runs on a HIP device only (got a CPU tensor); there is no CPU fallback -- the plain-torch "
@@ -149,24 +149,19 @@ class EpochMeter(_Meter):
         mm_ = byte_mask(moment_mask)
         loss_ = None if loss is None else loss.detach().float().reshape(1).contiguous()
         nl, ml = (ctypes.c_int * len(self._n))(*self._n), (ctypes.c_float * len(self._m))(*self._m)
-        if self._soft is not None:                               # rule 1 with the Soft-NMS selection
-            with torch.cuda.device(pm.device):
-                nbytes = load().smin_epoch_meter_soft_ws_bytes(B, L, self.k, len(self._n), len(self._m))
-                if nbytes == 0:
-                    raise SminHipError(f"smin_epoch_meter_soft_ws_bytes rejected B={B}, L={L}, k={self.k}")
-                ws = torch.empty((nbytes,), dtype=torch.uint8, device=pm.device)
-                call("smin_epoch_meter_update_soft", stream(), ptr(pm_), ptr(ps_), ptr(pe_), ptr(mm_), ptr(sm_), B, L, self.k, *self._soft[:3],
-                     ctypes.cast(nl, ctypes.c_void_p), len(self._n), ctypes.cast(ml, ctypes.c_void_p), len(self._m), ptr(loss_),
-                     ptr(self.state), ptr(ws), nbytes)
-            return
+        nn, nm = len(self._n), len(self._m)
+        if self._soft is None:
+            name, query = "smin_epoch_meter_update", "smin_epoch_meter_ws_bytes"
+            shape, fields = (B, L, self.rule, self.k), "B, L, rule, k, nn, nm"
+            how = (1.0 if self.nms_thresh is None else self.nms_thresh,)
+        else:                                                    # rule 1 with the Soft-NMS selection
+            name, query = "smin_epoch_meter_update_soft", "smin_epoch_meter_soft_ws_bytes"
+            shape, fields = (B, L, self.k), "B, L, k, nn, nm"
+            how = self._soft[:3]
         with torch.cuda.device(pm.device):
-            nbytes = load().smin_epoch_meter_ws_bytes(B, L, self.rule, self.k, len(self._n), len(self._m))
-            if nbytes == 0:
-                raise SminHipError(f"smin_epoch_meter_ws_bytes rejected B={B}, L={L}, rule={self.rule}, k={self.k}")
-            ws = torch.empty((nbytes,), dtype=torch.uint8, device=pm.device)
-            call("smin_epoch_meter_update", stream(), ptr(pm_), ptr(ps_), ptr(pe_), ptr(mm_), ptr(sm_), B, L, self.rule, self.k,
-                 1.0 if self.nms_thresh is None else self.nms_thresh, ctypes.cast(nl, ctypes.c_void_p), len(self._n),
-                 ctypes.cast(ml, ctypes.c_void_p), len(self._m), ptr(loss_), ptr(self.state), ptr(ws), nbytes)
+            call_ws(name, shape + (nn, nm), stream(), ptr(pm_), ptr(ps_), ptr(pe_), ptr(mm_), ptr(sm_), *shape, *how,
+                    ctypes.cast(nl, ctypes.c_void_p), nn, ctypes.cast(ml, ctypes.c_void_p), nm, ptr(loss_), ptr(self.state),
+                    query=query, fields=fields)
 
     def update_spans(self, span, count, gt):
         """Adds B pairs' merged spans ``span (B, k, 2)`` / ``count (B,)`` against ``gt (B, 2)`` (same unit) to the state: samples,
@@ -205,8 +200,8 @@ class EpochMeterTorch(_Meter):
             iou = torch.gather(smf, 1, flat.clamp_min(0).unsqueeze(1)).squeeze(1)
             return torch.where(flat >= 0, iou, torch.zeros_like(iou))
         # the reference's rule as csrc/metrics.hip forms it: ((pm * sqrtf(ps_i)) * sqrtf(pe_j)) * mask over all cells, ties -> lower index
-        score = _mul32(_mul32(pm.detach(), _sqrt32(ps.detach()).unsqueeze(2)), _sqrt32(pe.detach()).unsqueeze(1))
-        score = _mul32(score, (byte_mask(moment_mask) != 0).float()).reshape(B, -1)
+        # (a product, not moments._score_map's selection: a masked NaN stays a NaN)
+        score = _mul32(_fused(pm, ps, pe), (byte_mask(moment_mask) != 0).float()).reshape(B, -1)
         cell = torch.arange(L * L, device=score.device).unsqueeze(0)
         best = torch.where(score == score.max(dim=1, keepdim=True).values, cell, torch.full_like(cell, L * L)).min(dim=1).values
         return torch.gather(smf, 1, best.unsqueeze(1)).squeeze(1)
@@ -288,7 +283,7 @@ class CorpusMeter(_CorpusMeter):
         return "cuda"
 
     def update(self, result, gt_video, gt):
-        from ._lib import SminHipError, call, load, ptr, stream
+        from ._lib import SminHipError, call_ws, ptr, stream
         video, span, count, gt_video, gt, Q, k = self._lists(result, gt_video, gt)
         for t in (video, span, count, gt_video, gt):
             if not t.is_cuda:
@@ -302,12 +297,8 @@ class CorpusMeter(_CorpusMeter):
         nn, nm = len(self._n), len(self._m)
         nl, ml = (ctypes.c_int * nn)(*self._n), (ctypes.c_float * nm)(*self._m)
         with torch.cuda.device(video.device):
-            nbytes = load().smin_corpus_meter_ws_bytes(Q, nn, nm)
-            if nbytes == 0:
-                raise SminHipError(f"smin_corpus_meter_ws_bytes rejected Q={Q}, nn={nn}, nm={nm}")
-            ws = torch.empty((nbytes,), dtype=torch.uint8, device=video.device)
-            call("smin_corpus_meter_update", stream(), *[ptr(a) for a in args], Q, k, ctypes.cast(nl, ctypes.c_void_p), nn,
-                 ctypes.cast(ml, ctypes.c_void_p), nm, ptr(self.state), ptr(ws), nbytes)
+            call_ws("smin_corpus_meter_update", (Q, nn, nm), stream(), *[ptr(a) for a in args], Q, k, ctypes.cast(nl, ctypes.c_void_p), nn,
+                    ctypes.cast(ml, ctypes.c_void_p), nm, ptr(self.state), query="smin_corpus_meter_ws_bytes", fields="Q, nn, nm")
 
 
 class CorpusMeterTorch(_CorpusMeter):

@@ -28,7 +28,7 @@ import numpy as np
 import torch
 
 from ._host import _require_hip, byte_mask, host_array, require_ints
-from ._lib import SminHipError, call, load, ptr, stream
+from ._lib import call, call_ws, load, ptr, stream
 
 MAX_K = 64
 MAX_B = 65535                       # csrc/moments.hip: the sample index is the band select's grid y coordinate
@@ -64,18 +64,17 @@ def _result(idx, score, count, duration, L):
     return out
 
 
-def _top_moments_into(pm, ps, pe, moment_mask, k, nms_thresh, idx, score, count):
-    """smin_top_moments of B checked samples on ``pm``'s device into the caller's contiguous ``idx (B, k, 2)`` int64, ``score (B, k)``
+def _select_into(pm, ps, pe, moment_mask, k, nms_thresh, rule, idx, score, count, raw=None):
+    """The selection of B checked samples on ``pm``'s device into the caller's contiguous ``idx (B, k, 2)`` int64, ``score (B, k)``
     float32 and ``count (B,)`` int32 (e.g. a chunk's rows of larger buffers): the workspace query, its allocation and the call.
+    ``rule=None``: smin_top_moments at ``nms_thresh``; else ``soft_rule``'s tuple: smin_top_moments_soft, which also fills ``raw (B, k)``.
     Detached fp32 contiguous scores and a contiguous byte mask are passed as they are: no launch or copy beside the kernels'."""
     B, L = pm.shape[0], pm.shape[1]
     pm_, ps_, pe_ = (x.detach().float().contiguous() for x in (pm, ps, pe))
     mm_ = byte_mask(moment_mask)
+    name, how, extra = ("smin_top_moments", (float(nms_thresh),), ()) if rule is None else ("smin_top_moments_soft", rule, (ptr(raw),))
     with torch.cuda.device(pm.device):
-        nbytes = load().smin_top_moments_ws_bytes(B, L, k)
-        ws = torch.empty((nbytes,), dtype=torch.uint8, device=pm.device)
-        call("smin_top_moments", stream(), ptr(pm_), ptr(ps_), ptr(pe_), ptr(mm_), B, L, k, float(nms_thresh),
-             ptr(idx), ptr(score), ptr(count), ptr(ws), nbytes)
+        call_ws(name, (B, L, k), stream(), ptr(pm_), ptr(ps_), ptr(pe_), ptr(mm_), B, L, k, *how, ptr(idx), ptr(score), *extra, ptr(count), fields="B, L, k")
 
 
 def top_moments(pm, ps, pe, moment_mask, k=5, nms_thresh=0.5, duration=None, nms="hard", sigma=0.5, min_score=None):
@@ -97,13 +96,11 @@ def top_moments(pm, ps, pe, moment_mask, k=5, nms_thresh=0.5, duration=None, nms
     idx = torch.empty((B, k, 2), dtype=torch.int64, device=pm.device)
     score = torch.empty((B, k), dtype=torch.float32, device=pm.device)
     count = torch.empty((B,), dtype=torch.int32, device=pm.device)
-    if rule is None:
-        _top_moments_into(pm, ps, pe, moment_mask, k, nms_thresh, idx, score, count)
-        return _result(idx, score, count, duration, L)
-    raw = torch.empty((B, k), dtype=torch.float32, device=pm.device)
-    _top_moments_soft_into(pm, ps, pe, moment_mask, k, rule, idx, score, raw, count)
+    raw = None if rule is None else torch.empty((B, k), dtype=torch.float32, device=pm.device)
+    _select_into(pm, ps, pe, moment_mask, k, nms_thresh, rule, idx, score, count, raw)
     out = _result(idx, score, count, duration, L)
-    out["raw_score"] = raw
+    if rule is not None:
+        out["raw_score"] = raw
     return out
 
 
@@ -130,18 +127,6 @@ def soft_rule(what, nms, nms_thresh, sigma, min_score):
     if floor != floor:
         raise ValueError(f"{what}: min_score must not be NaN")
     return NMS_METHODS[nms], float(nms_thresh), sigma, floor
-
-
-def _top_moments_soft_into(pm, ps, pe, moment_mask, k, rule, idx, score, raw, count):
-    """smin_top_moments_soft of B checked samples into the caller's contiguous outputs (``_top_moments_into``'s contract)."""
-    B, L = pm.shape[0], pm.shape[1]
-    pm_, ps_, pe_ = (x.detach().float().contiguous() for x in (pm, ps, pe))
-    mm_ = byte_mask(moment_mask)
-    with torch.cuda.device(pm.device):
-        nbytes = load().smin_top_moments_soft_ws_bytes(B, L, k)
-        ws = torch.empty((nbytes,), dtype=torch.uint8, device=pm.device)
-        call("smin_top_moments_soft", stream(), ptr(pm_), ptr(ps_), ptr(pe_), ptr(mm_), B, L, k, *rule,
-             ptr(idx), ptr(score), ptr(raw), ptr(count), ptr(ws), nbytes)
 
 
 def _f32(x, dev):
@@ -192,10 +177,7 @@ def top_moments_soft_torch(pm, ps, pe, moment_mask, k=5, nms_thresh=0.5, duratio
     if rule is None:
         raise ValueError("top_moments_soft_torch restates the soft rules; nms='hard' is top_moments_torch")
     dev = pm.device
-    score = _mul32(_mul32(pm.detach(), _sqrt32(ps.detach()).unsqueeze(2)), _sqrt32(pe.detach()).unsqueeze(1))
-    score = torch.where(score == 0, torch.zeros_like(score), score).reshape(B, -1)              # -0 -> +0
-    valid = byte_mask(moment_mask).reshape(B, -1) != 0
-    score = torch.where(valid, score, torch.zeros_like(score))                                   # masked NaN / inf never enter
+    score, valid = _score_map(pm, ps, pe, moment_mask)
     cells = torch.arange(L * L, device=dev)
     ci, cj = cells // L, cells % L
     idx = torch.full((B, k, 2), -1, dtype=torch.int64, device=dev)
@@ -228,6 +210,20 @@ def _mul32(a, b):
     return (a.float().double() * b.float().double()).float()
 
 
+def _fused(pm, ps, pe):
+    """(B, L, L) fp32 fused score of every cell: ``(pm * sqrtf(ps_i)) * sqrtf(pe_j)``, each operation rounded once."""
+    return _mul32(_mul32(pm.detach(), _sqrt32(ps.detach()).unsqueeze(2)), _sqrt32(pe.detach()).unsqueeze(1))
+
+
+def _score_map(pm, ps, pe, moment_mask):
+    """``(score, valid)``, both (B, L*L): the fused score with -0 as +0 and 0 at the masked cells (their NaN / inf never enter), and the
+    bool mask of the valid cells."""
+    score = _fused(pm, ps, pe)
+    score = torch.where(score == 0, torch.zeros_like(score), score).reshape(pm.shape[0], -1)     # -0 -> +0
+    valid = byte_mask(moment_mask).reshape(pm.shape[0], -1) != 0
+    return torch.where(valid, score, torch.zeros_like(score)), valid
+
+
 def _order_word(score):
     """fp32 scores as int64 words in the kernels' order: a higher score has the higher word, -0 counts as +0, and no word is below 1
     (0 stands for "no candidate")."""
@@ -247,11 +243,8 @@ def top_moments_torch(pm, ps, pe, moment_mask, k=5, nms_thresh=0.5, duration=Non
     then greedy NMS, testing ``chunk`` candidates at a time against the kept set."""
     B, L = _check(pm, ps, pe, moment_mask, k)
     dev = pm.device
-    score = _mul32(_mul32(pm.detach(), _sqrt32(ps.detach()).unsqueeze(2)), _sqrt32(pe.detach()).unsqueeze(1))
-    score = torch.where(score == 0, torch.zeros_like(score), score).reshape(B, -1)              # -0 -> +0
-    o = _order_word(score)
-    valid = byte_mask(moment_mask).reshape(B, -1) != 0
-    o = torch.where(valid, o, torch.zeros_like(o))
+    score, valid = _score_map(pm, ps, pe, moment_mask)
+    o = torch.where(valid, _order_word(score), torch.zeros_like(score, dtype=torch.int64))
     order = torch.sort(o, dim=1, descending=True, stable=True).indices                          # ties keep index order
     nvalid = valid.sum(dim=1).tolist()
     thr = torch.tensor(float(nms_thresh), dtype=torch.float32, device=dev)
@@ -308,18 +301,11 @@ def compute_ious_nms(pm, ps, pe, moment_mask, sm, n, m, nms_thresh, nms="hard", 
     nl, ml = (ctypes.c_int * len(n))(*n), (ctypes.c_float * len(m))(*m)
     counts = torch.empty((len(n) * len(m),), dtype=torch.float32, device=pm.device)
     rule = soft_rule("compute_ious", nms, nms_thresh, sigma, None)
-    if rule is not None:                                         # the soft selection in front of the same hit flags and sums
-        with torch.cuda.device(pm.device):
-            nbytes = load().smin_compute_ious_soft_ws_bytes(B, L, k, len(n), len(m))
-            ws = torch.empty((nbytes,), dtype=torch.uint8, device=pm.device)
-            call("smin_compute_ious_soft", stream(), ptr(pm_), ptr(ps_), ptr(pe_), ptr(mm_), ptr(sm_), B, L, k, *rule[:3],
-                 ctypes.cast(nl, ctypes.c_void_p), len(n), ctypes.cast(ml, ctypes.c_void_p), len(m), ptr(counts), ptr(ws), nbytes)
-        return dict(zip(keys, counts.tolist()))
+    # a soft rule puts its selection in front of the same hit flags and sums
+    name, how = ("smin_compute_ious_nms", (float(nms_thresh),)) if rule is None else ("smin_compute_ious_soft", rule[:3])
     with torch.cuda.device(pm.device):
-        nbytes = load().smin_compute_ious_nms_ws_bytes(B, L, k, len(n), len(m))
-        ws = torch.empty((nbytes,), dtype=torch.uint8, device=pm.device)
-        call("smin_compute_ious_nms", stream(), ptr(pm_), ptr(ps_), ptr(pe_), ptr(mm_), ptr(sm_), B, L, k, float(nms_thresh),
-             ctypes.cast(nl, ctypes.c_void_p), len(n), ctypes.cast(ml, ctypes.c_void_p), len(m), ptr(counts), ptr(ws), nbytes)
+        call_ws(name, (B, L, k, len(n), len(m)), stream(), ptr(pm_), ptr(ps_), ptr(pe_), ptr(mm_), ptr(sm_), B, L, k, *how,
+                ctypes.cast(nl, ctypes.c_void_p), len(n), ctypes.cast(ml, ctypes.c_void_p), len(m), ptr(counts), fields="B, L, k, nn, nm")
     return dict(zip(keys, counts.tolist()))
 
 
@@ -356,6 +342,15 @@ def _merge_check(idx, score, count, start, lens, pair_ptr, T, L, k):
     return G, kw, pair_ptr.shape[0] - 1
 
 
+def _merge_result(span, score, raw, window, cell, count):
+    """merge_window_moments' dict; ``raw_score`` (soft rules only) sits behind ``score``."""
+    out = {"span": span, "score": score}
+    if raw is not None:
+        out["raw_score"] = raw
+    out.update(window=window, cell=cell, count=count)
+    return out
+
+
 def merge_window_moments(idx, score, count, start, lens, pair_ptr, T, L, k=5, nms_thresh=0.5, nms="hard", sigma=0.5, min_score=None):
     """Greedy temporal NMS, in raw-row time, of the per-window top moments of long videos (include/smin_hip.h,
     smin_merge_window_moments): one workgroup per (video, query) pair picks k times the best candidate that no kept span suppresses.
@@ -382,16 +377,15 @@ def merge_window_moments(idx, score, count, start, lens, pair_ptr, T, L, k=5, nm
     window = torch.empty((B, k), dtype=torch.int64, device=dev)
     cell = torch.empty((B, k, 2), dtype=torch.int64, device=dev)
     out_count = torch.empty((B,), dtype=torch.int32, device=dev)
+    raw = None
+    name, how, extra = "smin_merge_window_moments", (float(nms_thresh),), ()
     if rule is not None:
         raw = torch.empty((B, k), dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            call("smin_merge_window_moments_soft", stream(), *[ptr(a) for a in args], G, B, int(T), int(L), kw, k, *rule,
-                 ptr(span), ptr(out_score), ptr(raw), ptr(window), ptr(cell), ptr(out_count))
-        return {"span": span, "score": out_score, "raw_score": raw, "window": window, "cell": cell, "count": out_count}
+        name, how, extra = "smin_merge_window_moments_soft", rule, (ptr(raw),)
     with torch.cuda.device(dev):
-        call("smin_merge_window_moments", stream(), *[ptr(a) for a in args], G, B, int(T), int(L), kw, k, float(nms_thresh),
-             ptr(span), ptr(out_score), ptr(window), ptr(cell), ptr(out_count))
-    return {"span": span, "score": out_score, "window": window, "cell": cell, "count": out_count}
+        call(name, stream(), *[ptr(a) for a in args], G, B, int(T), int(L), kw, k, *how, ptr(span), ptr(out_score), *extra,
+             ptr(window), ptr(cell), ptr(out_count))
+    return _merge_result(span, out_score, raw, window, cell, out_count)
 
 
 def _div32(a, b):
@@ -425,57 +419,15 @@ def merge_window_moments_torch(idx, score, count, start, lens, pair_ptr, T, L, k
     pair's candidates and their span IoUs (linear bit for bit, gaussian in fp64)."""
     G, kw, B = _merge_check(idx, score, count, start, lens, pair_ptr, T, L, k)
     rule = soft_rule("merge_window_moments_torch", nms, nms_thresh, sigma, min_score)
-    if rule is not None:
-        return _merge_window_moments_soft_torch(idx, score, count, start, lens, pair_ptr, T, L, k, rule)
-    dev = idx.device
-    score = score.detach().float()
-    o = _order_word(score).reshape(-1)
-    st_all, en_all = window_spans(idx, start.unsqueeze(1), lens.unsqueeze(1), T, L)              # (G, kw)
-    st_all, en_all = st_all.reshape(-1), en_all.reshape(-1)
-    slot_ok = (torch.arange(kw, device=dev).unsqueeze(0) < count.to(torch.int64).unsqueeze(1)).reshape(-1)
-    thr = torch.tensor(float(nms_thresh), dtype=torch.float32, device=dev)
-    span = torch.full((B, k, 2), float("nan"), dtype=torch.float32, device=dev)
-    out_score = torch.zeros((B, k), dtype=torch.float32, device=dev)
-    window = torch.full((B, k), -1, dtype=torch.int64, device=dev)
-    cell = torch.full((B, k, 2), -1, dtype=torch.int64, device=dev)
-    out_count = torch.zeros((B,), dtype=torch.int32, device=dev)
-    pp = pair_ptr.to(torch.int64).tolist()
-    for b in range(B):
-        g0 = min(max(pp[b], 0), G)
-        g1 = min(max(pp[b + 1], g0), G)
-        q = torch.arange(g0 * kw, g1 * kw, device=dev)
-        q = q[slot_ok[q]]
-        order = torch.sort(o[q], descending=True, stable=True).indices                             # ties keep (window, slot) order
-        kept = []
-        for c in q[order].tolist():
-            if len(kept) >= k:
-                break
-            if kept:
-                ks = torch.tensor(kept, dtype=torch.int64, device=dev)
-                if bool((_span_iou(st_all[c], en_all[c], st_all[ks], en_all[ks]) > thr).any()):
-                    continue
-            kept.append(c)
-        n = len(kept)
-        if n:
-            ks = torch.tensor(kept, dtype=torch.int64, device=dev)
-            span[b, :n, 0], span[b, :n, 1] = st_all[ks], en_all[ks]
-            out_score[b, :n] = score.reshape(-1)[ks]
-            window[b, :n] = ks // kw - g0
-            cell[b, :n] = idx.reshape(-1, 2)[ks].to(torch.int64)
-        out_count[b] = n
-    return {"span": span, "score": out_score, "window": window, "cell": cell, "count": out_count}
-
-
-def _merge_window_moments_soft_torch(idx, score, count, start, lens, pair_ptr, T, L, k, rule):
-    G, kw, B = idx.shape[0], idx.shape[1], pair_ptr.shape[0] - 1
     dev = idx.device
     score = score.detach().float().reshape(-1)
     st_all, en_all = window_spans(idx, start.unsqueeze(1), lens.unsqueeze(1), T, L)              # (G, kw)
     st_all, en_all = st_all.reshape(-1), en_all.reshape(-1)
     slot_ok = (torch.arange(kw, device=dev).unsqueeze(0) < count.to(torch.int64).unsqueeze(1)).reshape(-1)
+    thr = _f32(float(nms_thresh), dev)
     span = torch.full((B, k, 2), float("nan"), dtype=torch.float32, device=dev)
     out_score = torch.zeros((B, k), dtype=torch.float32, device=dev)
-    raw = torch.zeros((B, k), dtype=torch.float32, device=dev)
+    raw = None if rule is None else torch.zeros((B, k), dtype=torch.float32, device=dev)
     window = torch.full((B, k), -1, dtype=torch.int64, device=dev)
     cell = torch.full((B, k, 2), -1, dtype=torch.int64, device=dev)
     out_count = torch.zeros((B,), dtype=torch.int32, device=dev)
@@ -484,20 +436,34 @@ def _merge_window_moments_soft_torch(idx, score, count, start, lens, pair_ptr, T
         g0 = min(max(pp[b], 0), G)
         g1 = min(max(pp[b + 1], g0), G)
         q = torch.arange(g0 * kw, g1 * kw, device=dev)                                             # candidates in (window, slot) order
-        if q.numel() == 0:
-            continue
-        st, en = st_all[q], en_all[q]
-        picks, vals = _soft_pick_loop(score[q], slot_ok[q], lambda c: _span_iou(st, en, st[c], en[c]), k, rule, dev)
-        n = len(picks)
-        if n:
+        if rule is None:
+            cand = q[slot_ok[q]]
+            order = torch.sort(_order_word(score[cand]), descending=True, stable=True).indices     # ties keep (window, slot) order
+            kept = []
+            for c in cand[order].tolist():
+                if len(kept) >= k:
+                    break
+                if kept:
+                    ks = torch.tensor(kept, dtype=torch.int64, device=dev)
+                    if bool((_span_iou(st_all[c], en_all[c], st_all[ks], en_all[ks]) > thr).any()):
+                        continue
+                kept.append(c)
+            ks = torch.tensor(kept, dtype=torch.int64, device=dev)
+            vals = list(score[ks])
+        else:
+            st, en = st_all[q], en_all[q]
+            picks, vals = _soft_pick_loop(score[q], slot_ok[q], lambda c: _span_iou(st, en, st[c], en[c]), k, rule, dev)
             ks = q[torch.tensor(picks, dtype=torch.int64, device=dev)]
+        n = len(vals)
+        if n:
             span[b, :n, 0], span[b, :n, 1] = st_all[ks], en_all[ks]
             out_score[b, :n] = torch.stack(vals).float()
-            raw[b, :n] = score[ks]
+            if raw is not None:
+                raw[b, :n] = score[ks]
             window[b, :n] = ks // kw - g0
             cell[b, :n] = idx.reshape(-1, 2)[ks].to(torch.int64)
         out_count[b] = n
-    return {"span": span, "score": out_score, "raw_score": raw, "window": window, "cell": cell, "count": out_count}
+    return _merge_result(span, out_score, raw, window, cell, out_count)
 
 
 # ---------------------------------------------------------------- metric of merged spans against ground-truth spans
@@ -558,12 +524,8 @@ def _span_meter_call(span, count, gt, n, m, acc):
     span_, gt_, count_ = span.detach().float().contiguous(), gt.detach().float().contiguous(), count.to(torch.int32).contiguous()
     nl, ml = (ctypes.c_int * len(n))(*n), (ctypes.c_float * len(m))(*m)
     with torch.cuda.device(span.device):
-        nbytes = load().smin_span_meter_ws_bytes(B, len(n), len(m))
-        if nbytes == 0:
-            raise SminHipError(f"smin_span_meter_ws_bytes rejected B={B}, nn={len(n)}, nm={len(m)}")
-        ws = torch.empty((nbytes,), dtype=torch.uint8, device=span.device)
-        call("smin_span_meter_update", stream(), ptr(span_), ptr(count_), ptr(gt_), B, k, ctypes.cast(nl, ctypes.c_void_p), len(n),
-             ctypes.cast(ml, ctypes.c_void_p), len(m), ptr(acc), ptr(ws), nbytes)
+        call_ws("smin_span_meter_update", (B, len(n), len(m)), stream(), ptr(span_), ptr(count_), ptr(gt_), B, k, ctypes.cast(nl, ctypes.c_void_p),
+                len(n), ctypes.cast(ml, ctypes.c_void_p), len(m), ptr(acc), query="smin_span_meter_ws_bytes", fields="B, nn, nm")
 
 
 def compute_span_ious(span, count, gt, n=(1, 5), m=(0.1, 0.3, 0.5, 0.7)):
@@ -780,9 +742,7 @@ def mine_pairs(score, gt_video, negatives, skip=0):
         out = torch.empty((4 * P + V + Q + 2,), dtype=torch.int32, device=dev)
         cut = np.cumsum([0, P, P, V + 1, P, Q + 1, P])
         lists = [out[cut[k]:cut[k + 1]] for k in range(6)]
-        nbytes = load().smin_mine_pairs_ws_bytes(Q, V, N)
-        ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
-        call("smin_mine_pairs", stream(), ptr(sc), ptr(buf[:Q]), Q, V, N, int(skip), *[ptr(a) for a in lists], ptr(ws), nbytes)
+        call_ws("smin_mine_pairs", (Q, V, N), stream(), ptr(sc), ptr(buf[:Q]), Q, V, N, int(skip), *[ptr(a) for a in lists], fields="Q, V, N")
         return PairPlan.from_device(*lists, V, Q, positive=buf[Q:Q + P], positive_rows=buf[Q + P:].to(torch.int64), num_positive=Q)
 
 

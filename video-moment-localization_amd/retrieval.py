@@ -15,7 +15,7 @@ from . import _lib
 from ._host import _AttnMaps, byte_mask, host_array, known_cells, query_mask_rows, require_hip_tensors, require_ints
 from .feeder import build_masks_hip, cell_count
 from .functional import attn_maps_gather
-from .moments import (MAX_K, PREFILTER_FOLD_MAX_M, bank_decode, bank_encode, bank_storage, require_storage, prefilter_fold, prefilter_gt_rank, survivors_admit, _pair_pool_into, _temperature, _top_moments_into, _top_moments_soft_into, soft_rule, _video_weight, corpus_span_topk, corpus_span_topk_torch, corpus_topk,
+from .moments import (MAX_K, PREFILTER_FOLD_MAX_M, bank_decode, bank_encode, bank_storage, require_storage, prefilter_fold, prefilter_gt_rank, survivors_admit, _pair_pool_into, _temperature, _select_into, soft_rule, _video_weight, corpus_span_topk, corpus_span_topk_torch, corpus_topk,
                       corpus_topk_torch, group_pool, merge_window_moments, merge_window_moments_torch, mine_pairs, prefilter_maps, prefilter_scores, prefilter_select,
                       rank_videos, reweight_moments, expand_survivor_windows, survivor_window_capacity,
                       reweight_moments_torch, search_times, top_moments, top_moments_torch, window_times)
@@ -448,7 +448,10 @@ class _Retrieval:
                                                             pair_ptr, nw, n[vi]], np.int64, dev)
         ln_d = ln_d.to(torch.int32)
         idx, score, count, chunks = _chunk_buffers(G, k_window, max_batch, dev)
-        decayed = None if rule is None else torch.empty_like(score)                              # the windows' own decays: not used
+        # a soft rule's windows never stop early, and the merge is given their picks' RAW scores: `score` takes the selection's raw
+        # output and the windows' own decayed scores go to `decayed`, which nothing reads
+        wrule = None if rule is None else rule[:3] + (float("-inf"),)
+        decayed = None if rule is None else torch.empty_like(score)
         with torch.no_grad(), torch.cuda.device(dev):
             for c0, c1 in chunks:
                 vf, nfeats = sample_windows(raw, rb_d[c0:c1], ln_d[c0:c1], T, mode=mode)
@@ -457,11 +460,8 @@ class _Retrieval:
                 qf, qm = query_features.index_select(0, rows), query_mask.index_select(0, rows)
                 with known_cells(self, int(cells[c0:c1].sum())):
                     pm, ps, pe, _ = self._scores(vf, m["video_mask"], qf, qm, m["length_mask"], m["moment_mask"])
-                if rule is None:
-                    _top_moments_into(pm, ps, pe, m["moment_mask"], k_window, nms_thresh, idx[c0:c1], score[c0:c1], count[c0:c1])
-                else:                                                                            # score <- the picks' raw scores
-                    _top_moments_soft_into(pm, ps, pe, m["moment_mask"], k_window, rule[:3] + (float("-inf"),), idx[c0:c1], decayed[c0:c1],
-                                           score[c0:c1], count[c0:c1])
+                _select_into(pm, ps, pe, m["moment_mask"], k_window, nms_thresh, wrule, idx[c0:c1], (score if rule is None else decayed)[c0:c1],
+                             count[c0:c1], raw=None if rule is None else score[c0:c1])
         r = merge_window_moments(idx, score, count, st_d, ln_d, pp_d, T, L, k=k, nms_thresh=nms_thresh, nms=nms, sigma=sigma, min_score=min_score)
         r["n_windows"] = nw_d
         if duration is not None:
@@ -778,7 +778,7 @@ class _Retrieval:
                 pm, ps, pe, _ = self._score_pairs(videos, queries, None, None, vi_d[c0:c1], qi_d[c0:c1], cells=None if cell is None else (c1 - c0) * cell)
             mm = videos.moment_mask.index_select(0, vi_d[c0:c1])
             if cut is not None:
-                _top_moments_into(pm, ps, pe, mm, cut[0], cut[1], lists["idx"][c0:c1], lists["score"][c0:c1], lists["count"][c0:c1])
+                _select_into(pm, ps, pe, mm, cut[0], cut[1], None, lists["idx"][c0:c1], lists["score"][c0:c1], lists["count"][c0:c1])
             if tau is not None:
                 _pair_pool_into(pm, ps, pe, mm, tau, pools[0][c0:c1], pools[1][c0:c1], pools[2][c0:c1])
         return lists, pools
